@@ -10,7 +10,7 @@ Reddit-shaped stand-in of SURVEY.md 8(d) (n = 232 968, nnz = 114 848 860 with
 self-loops, heavy-tailed degrees up to 21 657, random columns as after the reference's
 vertex permutation), features N(0,1) [n x 608], 41 uniform classes.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -345,6 +345,9 @@ def main():
                          "the SpMM is HBM-bound there")
     ap.add_argument("--symmetric", action="store_true",
                     help="HEADLINE workload = the symmetric stand-in (pattern A = A^T like the real Reddit); manual mode")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (loss, accuracy, every layer's "
+                         "parameters and gradients) as DIR/<name>.npy; rank 0 only")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -480,10 +483,12 @@ def main():
     for _ in range(args.warmup):
         losses.append(epoch()[0])
     spmm_ms, narrow_ms = [], []
+    last_step = None
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses.append(epoch()[0])
+        last_step = epoch()
+        losses.append(last_step[0])
         spmm_ms.append([ctx.measure(t) for t in spmm_timers])     # hipEventElapsedTime, microseconds of host time
         narrow_ms.append([ctx.measure(t) for t in narrow_timers])
     barrier()
@@ -493,6 +498,12 @@ def main():
         t = torch.tensor([ms], dtype=torch.float64, device="cpu" if rehearsal else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         ms = float(t.item())
+    if args.dump_outputs:
+        # before the extras below: they run more epochs on the same model.  Every rank copies (the parameters are
+        # replicated after the gradient all-reduce), rank 0 writes.
+        dumped = dump_outputs(args.dump_outputs, last_step, G.layers(), write=(rank == 0))
+        if rank == 0:
+            sys.stderr.write(f"[bench] wrote {len(dumped)} arrays to {args.dump_outputs}\n")
 
     def spmm_roofline(ms_lists, d, launches_per_call, traffic_key):
         """achieved = ALGORITHMIC bytes of one SpMM call / its HIP-event time on the compute stream"""
@@ -664,6 +675,37 @@ def main():
     if rank == 0:
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, last_step, layers, write=True, limit=DUMP_LIMIT_BYTES):
+    """What the timed path handed its caller in its last step: train_step's (loss, accuracy) and the model it leaves behind
+    (every layer's W and b after the Adam update, and the gradients G_W, G_b that update was computed from).  float32 as
+    computed, the two scalars float64.  Should the arrays exceed `limit` bytes in all (very wide --hidden), every array larger
+    than its share keeps a fixed, seeded sample of its rows, so that two runs with the same arguments stay comparable."""
+    arrays = {}
+    if last_step is not None:
+        arrays["loss"] = np.array([last_step[0]], dtype=np.float64)
+        arrays["accuracy"] = np.array([last_step[1]], dtype=np.float64)
+    for li, layer in enumerate(layers):
+        for key, mat in (("W", layer.W()), ("b", layer.b()), ("grad_W", layer.GW()), ("grad_b", layer.Gb())):
+            mat = getattr(mat, "local", mat)                     # N > 1: the rank's copy of a replicated matrix
+            arrays[f"layer{li}_{key}"] = np.ascontiguousarray(mat.numpy(), dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        rng = np.random.default_rng(12345)
+        for name, a in arrays.items():
+            share = limit * a.nbytes // total
+            if a.nbytes > share and a.ndim == 2 and a.shape[0] > 1:
+                keep = max(1, share // max(a.itemsize * a.shape[1], 1))
+                arrays[name] = a[np.sort(rng.choice(a.shape[0], size=keep, replace=False))]
+    if write:
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def dist_min_is_negative(torch, dist, ex, rehearsal):

@@ -238,13 +238,19 @@ static void test_late_rank(std::size_t P) {
     const float delay = ctx[late].measure("delay"), t_on_time = ctx[on_time].measure("exchange");
     const std::vector<float> want(vals.begin(), vals.begin() + (rows / P) * d);
     for (std::size_t j = 0; j < P; j++) { ctx[j].set(); CHECK(R[j].to_host() == want); }
-    // the timing claim needs the on-time rank's streams on hardware queues of their own: on ONE device that holds up to four ranks
+    // the timing claim needs the on-time rank's streams on hardware queues of their own.  Streams are multiplexed over a few
+    // hardware queues per device and priority (GPU_MAX_HW_QUEUES, 4 by default) and two streams that share a queue run one
+    // after the other: with P ranks x (compute, comm, P - 1 pulling streams) on ONE device the late rank's queue of GEMMs
+    // holds up whoever shares its hardware queue.  Two queues per rank keep the ranks apart (measured with 4 and 8 queues at
+    // P = 4, profiles/experiments/time_dist_tests_r04.log); the test leaves the runtime's setting alone.
     // (delay == 0: the stream model of tests/native has no clock -- the data claims above still hold there)
-    const bool timed = ctx.transport() == "p2p" && P <= 4 && delay > 0.f;
+    const char *hwq = std::getenv("GPU_MAX_HW_QUEUES");
+    const std::size_t queues = hwq && std::atoi(hwq) > 0 ? (std::size_t)std::atoi(hwq) : 4;
+    const bool timed = ctx.transport() == "p2p" && 2 * P <= queues && delay > 0.f;
     if (timed) CHECK(t_on_time < 0.5f * delay);
-    std::printf("%s: late rank: delay %.2f ms, on-time receiver's exchange %.3f ms%s, transport %s, threads %d\n",
+    std::printf("%s: late rank: delay %.2f ms, on-time receiver's exchange %.3f ms%s, transport %s, threads %d, hw queues %zu\n",
                 (!timed || t_on_time < 0.5f * delay) ? "TEST PASSED" : "TEST FAILED", delay, t_on_time, timed ? "" : " (not asserted)",
-                ctx.transport().c_str(), (int)ctx.threaded());
+                ctx.transport().c_str(), (int)ctx.threaded(), queues);
     mggcn_set_device(0);
 }
 
@@ -252,12 +258,6 @@ int main(int argc, char **argv) {
     // test_dist P [n graph_seed F C hidden...]: the defaults are the fixed case of the suite; tests/test_gpu_host_cpp.py also
     // walks a few random shapes (odd widths, one hidden layer, class counts that need padding to a multiple of P)
     const std::size_t P = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 1;
-    // Streams are multiplexed over a few hardware queues per device and priority (4 by default) and two streams that share a
-    // queue run one after the other: with P ranks x (compute, comm, P - 1 pulling streams) on ONE device the late rank's
-    // queue of GEMMs holds up whoever shares its hardware queue.  Eight queues keep the ranks of P <= 4 apart (measured,
-    // profiles/experiments/time_dist_tests_r04.log: the suite runs as fast as with four; with 24 the driver time-slices
-    // the queues and the same binary takes 50x as long).  Must be set before the first HIP call.
-    setenv("GPU_MAX_HW_QUEUES", "8", 0);
     if (P == 1) setenv("MGGCN_DIST_SELF_GATHER", "1", 0);       // one rank: still put RCCL's all-gather through its paces
     const v_t n = argc > 2 ? (v_t)std::strtoull(argv[2], nullptr, 10) : 1536;      // 1536: divisible by 1, 2, 3, 4, 6, 8
     if (P == 0 || n % P != 0) { std::fprintf(stderr, "P must divide %u\n", n); return 2; }

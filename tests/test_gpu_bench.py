@@ -40,6 +40,32 @@ def test_bench_single_gpu_prints_one_json_line():
     assert out["hoisted_first_aggregation"]["epoch_ms"] > 0 and out["hoisted_first_aggregation"]["spmm_per_epoch"] == 6
 
 
+@pytest.mark.gpu
+def test_bench_dump_outputs_holds_the_last_timed_step(tmp_path):
+    """--dump-outputs DIR: --steps sets the timed steps, and DIR holds what the last of them computed -- its loss (the line's
+    last loss), accuracy, and every layer's parameters and gradients, finite, float32 / float64, 64 MB at most"""
+    import numpy as np
+    d = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.02", "--steps", "3", "--warmup", "1",
+                        "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(d)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = _one_json_line(r.stdout)
+    sizes = out["config"]["sizes"]
+    nl = len(sizes) - 1
+    calls = sum(1 if i == 0 else 2 for i in range(nl) if min(sizes[i], sizes[i + 1]) == 128)     # d = 128 SpMMs per step
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["roofline"]["calls_timed"] == 3 * calls
+    want = {"loss", "accuracy"} | {f"layer{i}_{k}" for i in range(nl) for k in ("W", "b", "grad_W", "grad_b")}
+    assert {p.stem for p in d.iterdir()} == want and all(p.suffix == ".npy" for p in d.iterdir())
+    assert sum(p.stat().st_size for p in d.iterdir()) <= 64 << 20
+    arrays = {p.stem: np.load(p) for p in d.iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert round(float(arrays["loss"][0]), 5) == out["loss_first_last"][1]
+    for i in range(nl):
+        assert arrays[f"layer{i}_W"].shape == arrays[f"layer{i}_grad_W"].shape == (sizes[i], sizes[i + 1])
+        assert np.abs(arrays[f"layer{i}_grad_W"]).max() > 0
+
+
 def _rehearsal(args, port_env=None):
     """plain `python bench.py --gpus 2 ...` -- NO launcher: bench.py starts its ranks itself"""
     env = dict(os.environ, MGGCN_BENCH_REHEARSAL="1")
