@@ -182,6 +182,24 @@ void mggcn_spmm_csr_f32(mggcn_stream_t stream, const mggcn_spmm_plan *plan, uint
                         const float *values, const float *B, size_t ldb, float *C, size_t ldc,
                         uint32_t d, float alpha, float beta, uint32_t flags, float slope);
 
+/* bf16 aggregation: the gathered operand B stored as bf16 (uint16_t bit patterns), half the bytes per row.
+ *   C = alpha * A * widen(B) + beta * C
+ * Everything else is mggcn_spmm_csr_f32's contract: A's values, the products, the sums, C and the fused
+ * leaky-ReLU epilogue are fp32; ldb is counted in ELEMENTS (ldb >= d); beta == 0 never reads C; C must not
+ * alias B; plan may be NULL.  The same plan serves both entries (a plan built for mggcn_spmm_csr_f32 is used as
+ * is; the bf16 copies of B that a narrow or relabelled plan makes are allocated by the first bf16 call that
+ * needs one).  Every form multiplies the exactly widened bf16 values in the order the fp32 form uses, so the
+ * result equals mggcn_spmm_csr_f32 on the widened B bit for bit, with the same plan and equally aligned
+ * operands. */
+void mggcn_spmm_csr_bf16(mggcn_stream_t stream, const mggcn_spmm_plan *plan, uint32_t n_rows,
+                         uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices,
+                         const float *values, const uint16_t *B, size_t ldb, float *C, size_t ldc,
+                         uint32_t d, float alpha, float beta, uint32_t flags, float slope);
+/* dst = bf16(src): n_rows x n_cols, row-major, leading dimensions in elements (ld_src, ld_dst >= n_cols).
+ * Round to nearest even; a NaN stays a NaN, overflow goes to +-inf.  src and dst must not overlap. */
+void mggcn_convert_f32_bf16(mggcn_stream_t stream, const float *src, size_t ld_src, uint16_t *dst, size_t ld_dst,
+                            size_t n_rows, size_t n_cols);
+
 /* ======================================================================== *
  * Dense GEMM  C = alpha * op(A) * op(B) + beta * C, row-major  (the MFMA path)
  * replaces matmul(context, dn A, dn B, dn C, alpha, beta, A_T, B_T) =

@@ -762,3 +762,51 @@ MGGCN_API void mggcn_adam_fused_f32(mggcn_stream_t stream, float *param, float *
                        grad, m, v, lr / c1, beta1, beta2, weight_decay, c2, eps, size);
     MGGCN_CHECK_LAUNCH();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// fp32 -> bf16 for the bf16 aggregation (mggcn_spmm_csr_bf16): round to nearest even, NaN stays NaN, overflow -> inf.
+// A plain cast: hipcc emits v_cvt_pk_bf16_f32 for it on gfx950 (integer rounding on the f32 bits would turn some NaNs
+// into a zero or an infinity).  Vector form: four columns per thread (16 bytes in, 8 out) when the rows allow it.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t bf16_pair(float lo, float hi) {
+    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)lo) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)hi) << 16);
+}
+
+__global__ __launch_bounds__(256) void convert_f32_bf16_vec4_kernel(const float *__restrict__ src, size_t ld_src,
+                                                                    uint16_t *__restrict__ dst, size_t ld_dst,
+                                                                    size_t n_rows, size_t q4) {
+    const size_t total = n_rows * q4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / q4, c = (i % q4) * 4;
+        const float4 v = *reinterpret_cast<const float4 *>(src + r * ld_src + c);
+        *reinterpret_cast<uint2 *>(dst + r * ld_dst + c) = make_uint2(bf16_pair(v.x, v.y), bf16_pair(v.z, v.w));
+    }
+}
+
+__global__ __launch_bounds__(256) void convert_f32_bf16_kernel(const float *__restrict__ src, size_t ld_src,
+                                                               uint16_t *__restrict__ dst, size_t ld_dst, size_t n_rows,
+                                                               size_t n_cols) {
+    const size_t total = n_rows * n_cols;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const size_t r = i / n_cols, c = i % n_cols;
+        dst[r * ld_dst + c] = __builtin_bit_cast(uint16_t, (__bf16)src[r * ld_src + c]);
+    }
+}
+
+MGGCN_API void mggcn_convert_f32_bf16(mggcn_stream_t stream, const float *src, size_t ld_src, uint16_t *dst,
+                                      size_t ld_dst, size_t n_rows, size_t n_cols) {
+    if (!n_rows || !n_cols) return;
+    MGGCN_REQUIRE(src && dst, "null operand");
+    MGGCN_REQUIRE(ld_src >= n_cols && ld_dst >= n_cols, "leading dimension smaller than the row");
+    const bool vec = n_cols % 4 == 0 && ld_src % 4 == 0 && ld_dst % 4 == 0 && aligned16(src) &&
+                     (reinterpret_cast<uintptr_t>(dst) & 7u) == 0;
+    const size_t work = vec ? n_rows * (n_cols / 4) : n_rows * n_cols;
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>((work + 255) / 256, (size_t)kNumCU * 16));
+    if (vec)
+        hipLaunchKernelGGL(convert_f32_bf16_vec4_kernel, dim3(grid), dim3(256), 0, as_stream(stream), src, ld_src, dst,
+                           ld_dst, n_rows, n_cols / 4);
+    else
+        hipLaunchKernelGGL(convert_f32_bf16_kernel, dim3(grid), dim3(256), 0, as_stream(stream), src, ld_src, dst, ld_dst,
+                           n_rows, n_cols);
+    MGGCN_CHECK_LAUNCH();
+}

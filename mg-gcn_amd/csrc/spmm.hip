@@ -29,6 +29,7 @@
 #include <numeric>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "common.h"
@@ -51,6 +52,17 @@ __device__ __forceinline__ float lrelu(float x, float slope) {
     return x > y ? x : y;  // max(x, slope*x), reference src/cuda_utils.cu:26-31
 }
 
+// Element type of B: float (mggcn_spmm_csr_f32) or uint16_t = bf16 bits (mggcn_spmm_csr_bf16), widened exactly
+// (bits << 16) on load -- the bf16 kernels run the fp32 kernels' FMAs in the same order on the widened values.
+__device__ __forceinline__ float4 load4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ float4 load4(const uint16_t *p) {
+    const uint2 w = *reinterpret_cast<const uint2 *>(p);
+    return make_float4(__builtin_bit_cast(float, w.x << 16), __builtin_bit_cast(float, w.x & 0xFFFF0000u),
+                       __builtin_bit_cast(float, w.y << 16), __builtin_bit_cast(float, w.y & 0xFFFF0000u));
+}
+__device__ __forceinline__ float load1(const float *p) { return *p; }
+__device__ __forceinline__ float load1(const uint16_t *p) { return __builtin_bit_cast(float, (uint32_t)*p << 16); }
+
 __device__ __forceinline__ float4 fma4(float s, float4 b, float4 a) {
     a.x = fmaf(s, b.x, a.x);
     a.y = fmaf(s, b.y, a.y);
@@ -64,11 +76,11 @@ __device__ __forceinline__ float4 fma4(float s, float4 b, float4 a) {
 // with float4 each (LPR*4 columns per pass); G = 64/LPR neighbour rows are
 // fetched by one wave-instruction.  Wider d loops over column tiles.
 // ---------------------------------------------------------------------------
-template <int LPR, int UNROLL, bool HAS_ITEMS>
-__global__ __launch_bounds__(256) void spmm_vec4_kernel(
+template <int LPR, int UNROLL, bool HAS_ITEMS, typename TB>
+__device__ __forceinline__ void vec4_body(
     const SpmmItem *__restrict__ items, uint32_t n_items, const uint32_t *__restrict__ indptr,
     const uint32_t *__restrict__ indices, const float *__restrict__ values,
-    const float *__restrict__ B, size_t ldb, float *__restrict__ C, size_t ldc,
+    const TB *__restrict__ B, size_t ldb, float *__restrict__ C, size_t ldc,
     float *__restrict__ partial, uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
     constexpr int G = 64 / LPR;
     const int lane = threadIdx.x & 63;
@@ -89,7 +101,7 @@ __global__ __launch_bounds__(256) void spmm_vec4_kernel(
     for (uint32_t col0 = 0; col0 < d; col0 += LPR * 4) {
         const uint32_t col = col0 + sub * 4;
         const bool active = col < d;
-        const float *__restrict__ Bc = B + col;
+        const TB *__restrict__ Bc = B + col;
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
 
         // software pipeline over 64-entry chunks of the row: the next chunk's
@@ -114,8 +126,7 @@ __global__ __launch_bounds__(256) void spmm_vec4_kernel(
                     const float vv = __shfl(my_v, src & 63);
                     const bool ok = active && src < cnt;
                     v[u] = ok ? vv : 0.f;
-                    b[u] = ok ? *reinterpret_cast<const float4 *>(Bc + (size_t)c * ldb)
-                              : make_float4(0.f, 0.f, 0.f, 0.f);
+                    b[u] = ok ? load4(Bc + (size_t)c * ldb) : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
 #pragma unroll
                 for (int u = 0; u < UNROLL; u++) acc = fma4(v[u], b[u], acc);
@@ -155,11 +166,11 @@ __global__ __launch_bounds__(256) void spmm_vec4_kernel(
 // 164-byte rows).  One lane per column, one neighbour row per wave-instruction;
 // index/value broadcast through v_readlane (wave-uniform -> scalar registers).
 // ---------------------------------------------------------------------------
-template <int UNROLL, bool HAS_ITEMS>
-__global__ __launch_bounds__(256) void spmm_scalar_kernel(
+template <int UNROLL, bool HAS_ITEMS, typename TB>
+__device__ __forceinline__ void scalar_body(
     const SpmmItem *__restrict__ items, uint32_t n_items, const uint32_t *__restrict__ indptr,
     const uint32_t *__restrict__ indices, const float *__restrict__ values,
-    const float *__restrict__ B, size_t ldb, float *__restrict__ C, size_t ldc,
+    const TB *__restrict__ B, size_t ldb, float *__restrict__ C, size_t ldc,
     float *__restrict__ partial, uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
     const int lane = threadIdx.x & 63;
     const uint32_t wave =
@@ -175,7 +186,7 @@ __global__ __launch_bounds__(256) void spmm_scalar_kernel(
     for (uint32_t col0 = 0; col0 < d; col0 += 64) {
         const uint32_t col = col0 + lane;
         const bool active = col < d;
-        const float *__restrict__ Bc = B + (active ? col : 0);
+        const TB *__restrict__ Bc = B + (active ? col : 0);
         float acc = 0.f;
         uint32_t nxt_c = 0;
         float nxt_v = 0.f;
@@ -197,7 +208,7 @@ __global__ __launch_bounds__(256) void spmm_scalar_kernel(
                         float, __builtin_amdgcn_readlane(__builtin_bit_cast(uint32_t, my_v), src));
                     const bool ok = (j + u) < cnt;            // padded lanes carry v = 0, c = 0
                     v[u] = ok ? vv : 0.f;
-                    b[u] = (ok && active) ? Bc[(size_t)c * ldb] : 0.f;
+                    b[u] = (ok && active) ? load1(Bc + (size_t)c * ldb) : 0.f;
                 }
 #pragma unroll
                 for (int u = 0; u < UNROLL; u++) acc = fmaf(v[u], b[u], acc);
@@ -215,6 +226,30 @@ __global__ __launch_bounds__(256) void spmm_scalar_kernel(
             }
         }
     }
+}
+
+#define MGGCN_ROWSPLIT_PARAMS(TB)                                                                                 \
+    const SpmmItem *__restrict__ items, uint32_t n_items, const uint32_t *__restrict__ indptr,                  \
+        const uint32_t *__restrict__ indices, const float *__restrict__ values, const TB *__restrict__ B, size_t ldb, \
+        float *__restrict__ C, size_t ldc, float *__restrict__ partial, uint32_t d, float alpha, float beta,     \
+        uint32_t flags, float slope
+#define MGGCN_ROWSPLIT_ARGS items, n_items, indptr, indices, values, B, ldb, C, ldc, partial, d, alpha, beta, flags, slope
+
+template <int LPR, int UNROLL, bool HAS_ITEMS>
+__global__ __launch_bounds__(256) void spmm_vec4_kernel(MGGCN_ROWSPLIT_PARAMS(float)) {
+    vec4_body<LPR, UNROLL, HAS_ITEMS, float>(MGGCN_ROWSPLIT_ARGS);
+}
+template <int LPR, int UNROLL, bool HAS_ITEMS>
+__global__ __launch_bounds__(256) void spmm_vec4_b16_kernel(MGGCN_ROWSPLIT_PARAMS(uint16_t)) {
+    vec4_body<LPR, UNROLL, HAS_ITEMS, uint16_t>(MGGCN_ROWSPLIT_ARGS);
+}
+template <int UNROLL, bool HAS_ITEMS>
+__global__ __launch_bounds__(256) void spmm_scalar_kernel(MGGCN_ROWSPLIT_PARAMS(float)) {
+    scalar_body<UNROLL, HAS_ITEMS, float>(MGGCN_ROWSPLIT_ARGS);
+}
+template <int UNROLL, bool HAS_ITEMS>
+__global__ __launch_bounds__(256) void spmm_scalar_b16_kernel(MGGCN_ROWSPLIT_PARAMS(uint16_t)) {
+    scalar_body<UNROLL, HAS_ITEMS, uint16_t>(MGGCN_ROWSPLIT_ARGS);
 }
 
 // Sum the slices of every split row in slot order, then the common epilogue.
@@ -259,6 +294,11 @@ struct mggcn_spmm_plan {
     // folds the permutation into its re-pitch pass)
     uint32_t *d_src_row = nullptr;
     float *d_bperm = nullptr;
+    // the same two scratch images in bf16, for mggcn_spmm_csr_bf16: allocated by the first bf16 call that needs one (a
+    // plan only ever used by the fp32 entry holds no more bytes than it did); counted in mggcn_spmm_plan_bytes from then on
+    mutable uint16_t *d_bpad16 = nullptr;      // n_cols x bpad16_dp, bpad16_dp = bpad_dp rounded up to 64 bytes
+    mutable uint16_t *d_bperm16 = nullptr;     // n_cols x max_d rounded up to 4
+    mutable size_t bytes16 = 0;
     // what the plan builder decided (mggcn_spmm_plan_describe)
     uint32_t d_hint = 0;
     int hot_columns = -1;          // -1: not measured (no sweep form considered)
@@ -456,6 +496,8 @@ MGGCN_API void mggcn_spmm_plan_destroy(mggcn_spmm_plan *plan) {
     if (plan->d_bpad) MGGCN_CHECK_HIP(hipFree(plan->d_bpad));
     if (plan->d_src_row) MGGCN_CHECK_HIP(hipFree(plan->d_src_row));
     if (plan->d_bperm) MGGCN_CHECK_HIP(hipFree(plan->d_bperm));
+    if (plan->d_bpad16) MGGCN_CHECK_HIP(hipFree(plan->d_bpad16));
+    if (plan->d_bperm16) MGGCN_CHECK_HIP(hipFree(plan->d_bperm16));
     delete plan;
 }
 
@@ -465,7 +507,7 @@ MGGCN_API void mggcn_spmm_plan_reserved_cus(uint32_t n) { mggcn_plan::set_reserv
 MGGCN_API uint32_t mggcn_spmm_plan_num_items(const mggcn_spmm_plan *plan) { return plan->n_items; }
 MGGCN_API uint32_t mggcn_spmm_plan_num_split_rows(const mggcn_spmm_plan *plan) { return plan->n_split_rows; }
 MGGCN_API size_t mggcn_spmm_plan_bytes(const mggcn_spmm_plan *plan) {
-    size_t b = plan->bytes;
+    size_t b = plan->bytes + plan->bytes16;
     for (auto *sp : plan->sweeps) b += sweep_plan_bytes(sp);
     return b;
 }
@@ -495,68 +537,108 @@ MGGCN_API uint32_t mggcn_spmm_plan_num_sweep_tasks(const mggcn_spmm_plan *plan) 
 
 namespace {
 
-template <bool HAS_ITEMS>
+// the fp32 row-split kernels for TB = float, their "_b16" twins for TB = uint16_t
+template <typename TB> struct RowsplitKernels;
+template <> struct RowsplitKernels<float> {
+    template <int L, int U, bool H> static constexpr auto vec4 = spmm_vec4_kernel<L, U, H>;
+    template <int U, bool H> static constexpr auto scalar = spmm_scalar_kernel<U, H>;
+};
+template <> struct RowsplitKernels<uint16_t> {
+    template <int L, int U, bool H> static constexpr auto vec4 = spmm_vec4_b16_kernel<L, U, H>;
+    template <int U, bool H> static constexpr auto scalar = spmm_scalar_b16_kernel<U, H>;
+};
+
+template <bool HAS_ITEMS, typename TB>
 void launch_main(hipStream_t st, const mggcn_spmm_plan *plan, uint32_t n_items, const uint32_t *indptr,
-                 const uint32_t *indices, const float *values, const float *B, size_t ldb, float *C,
+                 const uint32_t *indices, const float *values, const TB *B, size_t ldb, float *C,
                  size_t ldc, uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
+    using K = RowsplitKernels<TB>;
     const SpmmItem *items = HAS_ITEMS ? plan->d_items : nullptr;
     float *partial = HAS_ITEMS ? plan->d_partial : nullptr;
     const unsigned block = 256, waves_per_block = block / 64;
     const unsigned grid = (n_items + waves_per_block - 1) / waves_per_block;
-    const bool vec_ok = (d % 4 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) && aligned16(B) && aligned16(C);
+    // (alignment of B in elements: four of them per lane load)
+    const bool vec_ok = (d % 4 == 0) && (ldb % 4 == 0) && (ldc % 4 == 0) &&
+                        reinterpret_cast<uintptr_t>(B) % (4 * sizeof(TB)) == 0 && aligned16(C);
     if (vec_ok && d > 64) {
-        hipLaunchKernelGGL((spmm_vec4_kernel<32, 8, HAS_ITEMS>), dim3(grid), dim3(block), 0, st, items,
+        hipLaunchKernelGGL((K::template vec4<32, 8, HAS_ITEMS>), dim3(grid), dim3(block), 0, st, items,
                            n_items, indptr, indices, values, B, ldb, C, ldc, partial, d, alpha, beta,
                            flags, slope);
     } else if (vec_ok && d > 32) {
-        hipLaunchKernelGGL((spmm_vec4_kernel<16, 4, HAS_ITEMS>), dim3(grid), dim3(block), 0, st, items,
+        hipLaunchKernelGGL((K::template vec4<16, 4, HAS_ITEMS>), dim3(grid), dim3(block), 0, st, items,
                            n_items, indptr, indices, values, B, ldb, C, ldc, partial, d, alpha, beta,
                            flags, slope);
     } else if (vec_ok) {
-        hipLaunchKernelGGL((spmm_vec4_kernel<8, 2, HAS_ITEMS>), dim3(grid), dim3(block), 0, st, items,
+        hipLaunchKernelGGL((K::template vec4<8, 2, HAS_ITEMS>), dim3(grid), dim3(block), 0, st, items,
                            n_items, indptr, indices, values, B, ldb, C, ldc, partial, d, alpha, beta,
                            flags, slope);
     } else {
-        hipLaunchKernelGGL((spmm_scalar_kernel<8, HAS_ITEMS>), dim3(grid), dim3(block), 0, st, items,
+        hipLaunchKernelGGL((K::template scalar<8, HAS_ITEMS>), dim3(grid), dim3(block), 0, st, items,
                            n_items, indptr, indices, values, B, ldb, C, ldc, partial, d, alpha, beta,
                            flags, slope);
     }
     MGGCN_CHECK_LAUNCH();
 }
 
-}  // namespace
+// bf16 scratch of a plan (see mggcn_spmm_plan::d_bpad16), allocated on first use
+uint16_t *plan_scratch16(const mggcn_spmm_plan *plan, uint16_t *&p, size_t elems) {
+    if (!p) {
+        MGGCN_CHECK_HIP(hipMalloc(&p, elems * sizeof(uint16_t)));
+        plan->bytes16 += elems * sizeof(uint16_t);
+    }
+    return p;
+}
 
-MGGCN_API void mggcn_spmm_csr_f32(mggcn_stream_t stream, const mggcn_spmm_plan *plan, uint32_t n_rows,
-                                  uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices,
-                                  const float *values, const float *B, size_t ldb, float *C,
-                                  size_t ldc, uint32_t d, float alpha, float beta, uint32_t flags,
-                                  float slope) {
+// C = alpha A B + beta C with B in fp32 (TB = float) or bf16 bits (TB = uint16_t): one dispatch for both entries, so
+// that a bf16 call runs the form the fp32 call would run on the widened B
+template <typename TB>
+void spmm_csr(mggcn_stream_t stream, const mggcn_spmm_plan *plan, uint32_t n_rows, uint32_t n_cols,
+              const uint32_t *indptr, const uint32_t *indices, const float *values, const TB *B, size_t ldb, float *C,
+              size_t ldc, uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
     if (n_rows == 0 || d == 0) return;
     MGGCN_REQUIRE(indptr && B && C, "null operand");
     MGGCN_REQUIRE(ldb >= d && ldc >= d, "leading dimension smaller than the feature width");
     MGGCN_REQUIRE((const void *)B != (const void *)C, "C must not alias B");
     MGGCN_REQUIRE((uint64_t)n_cols * ldb < (1ull << 40), "B too large");
+    constexpr bool kB16 = std::is_same<TB, uint16_t>::value;
     hipStream_t st = as_stream(stream);
     if (plan) {
         MGGCN_REQUIRE(plan->n_rows == n_rows && plan->n_cols == n_cols, "plan built for another matrix");
         MGGCN_REQUIRE(d <= plan->max_d || plan->n_slots == 0, "feature width exceeds the plan's max_d");
-        if (!plan->sweeps.empty() && sweep_supports(plan->sweeps[0], d, ldb, ldc, B, C)) {
+        if (!plan->sweeps.empty() && sweep_supports(plan->sweeps[0], d, ldb, ldc, B, C, sizeof(TB))) {
             const size_t S = plan->sweeps.size();
             const uint32_t dp = (d + 15) / 16 * 16;
-            if (plan->d_bpad && dp <= plan->bpad_dp && (plan->d_src_row || sweep_wants_repack(plan->sweeps[0], d, ldb, B))) {
-                sweep_repack(st, B, ldb, n_cols, d, plan->d_bpad, dp, plan->d_src_row);     // 64-byte pitched (and permuted) copy of B
-                B = plan->d_bpad;
-                ldb = dp;
+            if (plan->d_bpad && dp <= plan->bpad_dp && (plan->d_src_row || sweep_wants_repack(plan->sweeps[0], d, ldb, B, sizeof(TB)))) {
+                if constexpr (kB16) {                                  // 64-byte pitched (and permuted) bf16 copy of B
+                    const uint32_t dp16 = (d + 31) / 32 * 32;
+                    uint16_t *out = plan_scratch16(plan, plan->d_bpad16, (size_t)n_cols * ((plan->bpad_dp + 31) / 32 * 32));
+                    sweep_repack_b16(st, B, ldb, n_cols, d, out, dp16, plan->d_src_row);
+                    B = out;
+                    ldb = dp16;
+                } else {
+                    sweep_repack(st, B, ldb, n_cols, d, plan->d_bpad, dp, plan->d_src_row);     // 64-byte pitched (and permuted) copy of B
+                    B = plan->d_bpad;
+                    ldb = dp;
+                }
             } else if (plan->d_src_row) {                                  // wide form on a permuted plan: B' = B[src_row]
                 const uint32_t d4 = (d + 3) / 4 * 4;
                 MGGCN_REQUIRE(plan->d_bperm != nullptr && d4 <= (plan->max_d + 3) / 4 * 4, "feature width exceeds the permuted plan's scratch");
-                sweep_repack(st, B, ldb, n_cols, d, plan->d_bperm, d4, plan->d_src_row);
-                B = plan->d_bperm;
+                if constexpr (kB16) {
+                    uint16_t *out = plan_scratch16(plan, plan->d_bperm16, (size_t)n_cols * ((plan->max_d + 3) / 4 * 4));
+                    sweep_repack_b16(st, B, ldb, n_cols, d, out, d4, plan->d_src_row);
+                    B = out;
+                } else {
+                    sweep_repack(st, B, ldb, n_cols, d, plan->d_bperm, d4, plan->d_src_row);
+                    B = plan->d_bperm;
+                }
                 ldb = d4;
             }
-            for (size_t k = 0; k < S; k++)       // beta only once, the fused activation only on the full sum
-                sweep_launch(st, plan->sweeps[k], B, ldb, C, ldc, d, alpha, k == 0 ? beta : 1.f,
-                             k + 1 == S ? flags : 0u, slope);
+            for (size_t k = 0; k < S; k++) {     // beta only once, the fused activation only on the full sum
+                if constexpr (kB16)
+                    sweep_launch_b16(st, plan->sweeps[k], B, ldb, C, ldc, d, alpha, k == 0 ? beta : 1.f, k + 1 == S ? flags : 0u, slope);
+                else
+                    sweep_launch(st, plan->sweeps[k], B, ldb, C, ldc, d, alpha, k == 0 ? beta : 1.f, k + 1 == S ? flags : 0u, slope);
+            }
             return;
         }
         launch_main<true>(st, plan, plan->n_items, indptr, indices, values, B, ldb, C, ldc, d, alpha,
@@ -571,4 +653,22 @@ MGGCN_API void mggcn_spmm_csr_f32(mggcn_stream_t stream, const mggcn_spmm_plan *
         launch_main<false>(st, nullptr, n_rows, indptr, indices, values, B, ldb, C, ldc, d, alpha, beta,
                            flags, slope);
     }
+}
+
+}  // namespace
+
+MGGCN_API void mggcn_spmm_csr_f32(mggcn_stream_t stream, const mggcn_spmm_plan *plan, uint32_t n_rows,
+                                  uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices,
+                                  const float *values, const float *B, size_t ldb, float *C,
+                                  size_t ldc, uint32_t d, float alpha, float beta, uint32_t flags,
+                                  float slope) {
+    spmm_csr<float>(stream, plan, n_rows, n_cols, indptr, indices, values, B, ldb, C, ldc, d, alpha, beta, flags, slope);
+}
+
+MGGCN_API void mggcn_spmm_csr_bf16(mggcn_stream_t stream, const mggcn_spmm_plan *plan, uint32_t n_rows,
+                                   uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices,
+                                   const float *values, const uint16_t *B, size_t ldb, float *C,
+                                   size_t ldc, uint32_t d, float alpha, float beta, uint32_t flags,
+                                   float slope) {
+    spmm_csr<uint16_t>(stream, plan, n_rows, n_cols, indptr, indices, values, B, ldb, C, ldc, d, alpha, beta, flags, slope);
 }

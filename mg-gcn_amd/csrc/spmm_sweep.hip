@@ -59,6 +59,46 @@ __device__ float mggcn_buffer_load_f32(__amdgpu_buffer_rsrc_t rsrc, int voffset,
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 __device__ f32x4_t mggcn_buffer_load_v4f32(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int aux)
     __asm("llvm.amdgcn.raw.ptr.buffer.load.v4f32");
+typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
+__device__ u32x2_t mggcn_buffer_load_v2i32(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int aux)
+    __asm("llvm.amdgcn.raw.ptr.buffer.load.v2i32");
+__device__ uint32_t mggcn_buffer_load_i32(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int aux)
+    __asm("llvm.amdgcn.raw.ptr.buffer.load.i32");
+__device__ short mggcn_buffer_load_i16(__amdgpu_buffer_rsrc_t rsrc, int voffset, int soffset, int aux)
+    __asm("llvm.amdgcn.raw.ptr.buffer.load.i16");
+
+// Element type of the gathered operand B.  float: the fp32 entry (mggcn_spmm_csr_f32).  uint16_t: bf16 bit patterns
+// (mggcn_spmm_csr_bf16) -- the same lanes fetch the same columns from rows of half the bytes (a float4 lane becomes a
+// dwordx2 lane, a float2 lane a dword lane), and every element is widened exactly (bits << 16) before the same FMAs in
+// the same order: the bf16 kernels compute bit for bit what the fp32 kernels compute on the widened B.
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __builtin_bit_cast(float, w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __builtin_bit_cast(float, w & 0xFFFF0000u); }
+template <typename TB> struct Gather;
+template <> struct Gather<float> {
+    __device__ __forceinline__ static f32x4_t x4(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, int aux) {
+        return mggcn_buffer_load_v4f32(rsrc, (int)voff, (int)soff, aux);
+    }
+    __device__ __forceinline__ static float2 x2(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
+        const f32x2_t x = mggcn_buffer_load_v2f32(rsrc, (int)voff, (int)soff, 0);
+        return make_float2(x[0], x[1]);
+    }
+    __device__ __forceinline__ static float x1(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
+        return mggcn_buffer_load_f32(rsrc, (int)voff, (int)soff, 0);
+    }
+};
+template <> struct Gather<uint16_t> {
+    __device__ __forceinline__ static f32x4_t x4(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff, int aux) {
+        const u32x2_t x = mggcn_buffer_load_v2i32(rsrc, (int)voff, (int)soff, aux);
+        return (f32x4_t){bf16_lo(x[0]), bf16_hi(x[0]), bf16_lo(x[1]), bf16_hi(x[1])};
+    }
+    __device__ __forceinline__ static float2 x2(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
+        const uint32_t a = mggcn_buffer_load_i32(rsrc, (int)voff, (int)soff, 0);
+        return make_float2(bf16_lo(a), bf16_hi(a));
+    }
+    __device__ __forceinline__ static float x1(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
+        return bf16_lo((uint32_t)(uint16_t)mggcn_buffer_load_i16(rsrc, (int)voff, (int)soff, 0));
+    }
+};
 
 // cache-policy bits of the pair kernel's row gathers (experiment, profiles/experiments/gather_aux.sh): gfx940+ encoding
 // 1 = sc0, 2 = nt, 16 = sc1
@@ -216,28 +256,29 @@ template <> __device__ __forceinline__ float2 vec_to2<2>(const Vec<2> &v) { retu
 // (buffer_load_dwordx2 v, v_lane_offset, s[rsrc], s_row_offset offen).  The kernel is
 // otherwise bound by scalar-instruction issue, not by memory (rocprof r01: 13 SALU
 // instructions per non-zero in the first version).
-template <int VEC> struct BufLoad;
-template <> struct BufLoad<1> {
+template <int VEC, typename TB> struct BufLoad;
+template <typename TB> struct BufLoad<1, TB> {
     __device__ __forceinline__ static Vec<1> load(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
         Vec<1> r;
-        r.v = mggcn_buffer_load_f32(rsrc, (int)voff, (int)soff, 0);
+        r.v = Gather<TB>::x1(rsrc, voff, soff);
         return r;
     }
 };
-template <> struct BufLoad<2> {
+template <typename TB> struct BufLoad<2, TB> {
     __device__ __forceinline__ static Vec<2> load(__amdgpu_buffer_rsrc_t rsrc, uint32_t voff, uint32_t soff) {
-        const f32x2_t x = mggcn_buffer_load_v2f32(rsrc, (int)voff, (int)soff, 0);
         Vec<2> r;
-        r.v = make_float2(x[0], x[1]);
+        r.v = Gather<TB>::x2(rsrc, voff, soff);
         return r;
     }
 };
 
-template <int VEC>
-__global__ __launch_bounds__(64 * kWavesPerBlock) void spmm_sweep_kernel(
+// The kernels below are bodies (templated on the element type TB of B) behind thin __global__ entries: the fp32 ones
+// keep their names, the bf16 ones carry "_b16" in theirs.
+template <int VEC, typename TB>
+__device__ __forceinline__ void sweep_body(
     const SweepTask *__restrict__ tasks, uint32_t task0, uint32_t n_launch,
     const uint2 *__restrict__ entries, const uint32_t *__restrict__ task_rows,
-    const float *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc,
+    const TB *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc,
     float *__restrict__ partial, uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
     static_assert(kRW == 16, "the accumulator planes hold 16 rows");
     constexpr int TILE = 64 * VEC;
@@ -248,12 +289,12 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void spmm_sweep_kernel(
     const uint32_t t = task0 + local;
     const SweepTask task = tasks[t];
     const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(B), 0, b_bytes, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<TB *>(B), 0, b_bytes, 0x00020000);
 
     for (uint32_t col0 = 0; col0 < d; col0 += TILE) {
         const uint32_t col = col0 + lane * VEC;
         const bool active = col < d;                  // VEC == 2 is only used with even d
-        const uint32_t lane_off = (active ? col : 0) * 4u;   // idle lanes re-read column 0 (never stored)
+        const uint32_t lane_off = (active ? col : 0) * (uint32_t)sizeof(TB);   // idle lanes re-read column 0 (never stored)
         f32x16 p0, p1;
 #pragma unroll
         for (int r = 0; r < 16; r++) { p0[r] = 0.f; p1[r] = 0.f; }
@@ -269,7 +310,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void spmm_sweep_kernel(
             {                                                                                     \
                 Vec<VEC> b[8];                                                                    \
                 _Pragma("unroll") for (int u = 0; u < 8; u++)                                     \
-                    b[u] = BufLoad<VEC>::load(rsrc, lane_off, (cur.pk(u) & kColMask) * row_bytes); \
+                    b[u] = BufLoad<VEC, TB>::load(rsrc, lane_off, (cur.pk(u) & kColMask) * row_bytes); \
                 _Pragma("unroll") for (int u = 0; u < 8; u++) {                                   \
                     const uint32_t pk = cur.pk(u);                                                \
                     if (pk & kRunFlag) { /* first entry of a (panel,row) run */                   \
@@ -331,6 +372,22 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void spmm_sweep_kernel(
     }
 }
 
+#define MGGCN_SWEEP_PARAMS(TB)                                                                           \
+    const SweepTask *__restrict__ tasks, uint32_t task0, uint32_t n_launch, const uint2 *__restrict__ entries, \
+        const uint32_t *__restrict__ task_rows, const TB *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, \
+        float *__restrict__ C, size_t ldc, float *__restrict__ partial, uint32_t d, float alpha, float beta,   \
+        uint32_t flags, float slope
+#define MGGCN_SWEEP_ARGS tasks, task0, n_launch, entries, task_rows, B, b_bytes, row_bytes, C, ldc, partial, d, alpha, beta, flags, slope
+
+template <int VEC>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void spmm_sweep_kernel(MGGCN_SWEEP_PARAMS(float)) {
+    sweep_body<VEC, float>(MGGCN_SWEEP_ARGS);
+}
+template <int VEC>
+__global__ __launch_bounds__(64 * kWavesPerBlock) void spmm_sweep_b16_kernel(MGGCN_SWEEP_PARAMS(uint16_t)) {
+    sweep_body<VEC, uint16_t>(MGGCN_SWEEP_ARGS);
+}
+
 // ---------------------------------------------------------------------------------------
 // float4 "pair" form (d % 4 == 0, 16-byte aligned rows): the 8-byte gathers of the kernel
 // above top out at ~17.5 TB/s even with every access hitting L2 (8-B accesses run at
@@ -349,11 +406,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void spmm_sweep_kernel(
 //   * the half's value through v_bfi_b32 (one move + one select instead of three instructions).
 // The per-wave instruction chain is on the critical path of this kernel (profiles/experiments/split_pairs_r03.log: six
 // more instructions per pair cost 16 % per batch).
-template <bool FAST>
-__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_pair_kernel(
+// bf16 (spmm_sweep_pair_b16_kernel): the same lanes, columns, pairs and sums; a lane fetches its four columns with a
+// buffer_load_dwordx2, so one instruction gathers two 256-byte rows (d = 128).  FAST there: pitch a power of two >= 256
+// bytes (>= 128 elements, as for fp32), and the same argument holds (the pitch is still a multiple of 32).
+template <bool FAST, typename TB>
+__device__ __forceinline__ void sweep_pair_body(
     const SweepTask *__restrict__ tasks, uint32_t task0, uint32_t n_launch,
     const uint2 *__restrict__ entries, const uint32_t *__restrict__ task_rows,
-    const float *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc,
+    const TB *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc,
     float *__restrict__ partial, uint32_t d, float alpha, float beta, uint32_t flags, float slope,
     unsigned long long *__restrict__ stamps, uint32_t wave_stride) {
     const int lane = threadIdx.x & 63;
@@ -361,7 +421,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr
     const uint32_t local = blockIdx.x * kWavesPerBlock + wib;
     if (local >= n_launch) return;                    // no barriers: waves are independent
     const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(B), 0, b_bytes, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<TB *>(B), 0, b_bytes, 0x00020000);
     const uint32_t sub = lane & 31;
     const uint32_t hmask = (lane & 32) ? 0xFFFFFFFFu : 0u;     // upper half-wave takes the pair's 2nd entry
     const uint32_t prio_slot = blockIdx.x / ((flags >> kNumCuPos) & kNumCuMask);   // blocks are dealt one per CU per "layer": layer = hardware wave slot
@@ -378,7 +438,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr
     for (uint32_t col0 = 0; col0 < d; col0 += 128) {
         const uint32_t col = col0 + sub * 4;
         const bool active = col < d;
-        const uint32_t lane_off = (active ? col : 0) * 4u;
+        const uint32_t lane_off = (active ? col : 0) * (uint32_t)sizeof(TB);
         MGGCN_PLANES_ZERO();
         uint32_t cur_row = 0;
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
@@ -399,10 +459,10 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr
                     if constexpr (FAST) {
                         const uint32_t fa = cur.pk(2 * u) * row_bytes, fb = cur.pk(2 * u + 1) * row_bytes;
                         const uint32_t voff = lane_off | ((fb - fa) & hmask);
-                        b[u] = mggcn_buffer_load_v4f32(rsrc, (int)voff, (int)fa, MGGCN_GATHER_AUX);
+                        b[u] = Gather<TB>::x4(rsrc, voff, fa, MGGCN_GATHER_AUX);
                     } else {
                         const uint32_t voff = lane_off + ((off_b - off_a) & hmask);
-                        b[u] = mggcn_buffer_load_v4f32(rsrc, (int)voff, (int)off_a, MGGCN_GATHER_AUX);
+                        b[u] = Gather<TB>::x4(rsrc, voff, off_a, MGGCN_GATHER_AUX);
                     }
                 }
 #pragma unroll
@@ -507,6 +567,18 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr
     }   // tasks of this wave
 }
 
+#define MGGCN_PAIR_PARAMS(TB) MGGCN_SWEEP_PARAMS(TB), unsigned long long *__restrict__ stamps, uint32_t wave_stride
+template <bool FAST>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_pair_kernel(
+    MGGCN_PAIR_PARAMS(float)) {
+    sweep_pair_body<FAST, float>(MGGCN_SWEEP_ARGS, stamps, wave_stride);
+}
+template <bool FAST>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_pair_b16_kernel(
+    MGGCN_PAIR_PARAMS(uint16_t)) {
+    sweep_pair_body<FAST, uint16_t>(MGGCN_SWEEP_ARGS, stamps, wave_stride);
+}
+
 // ---------------------------------------------------------------------------------------
 // float4 narrow-row form (d <= 64; the reference's logits layer has d = 41, 48 at P = 8).
 // Measured on this chip, everything hitting L1/L2 (profiles/experiments/narrow_spmm.py,
@@ -565,13 +637,16 @@ template <int LPE> __device__ __forceinline__ float reduce_groups(float x) {
     }
 }
 
-template <int LPE>
-__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_quad_lds_kernel(
+// bf16 (spmm_sweep_quad_lds_b16_kernel): the same LPE, groups and sums -- a lane fetches its four columns with a
+// buffer_load_dwordx2 -- over the bf16 image re-pitched to a multiple of 64 bytes (d = 41: 128 B, one line per row
+// against up to two at the fp32 image's 192 B).
+template <int LPE, typename TB>
+__device__ __forceinline__ void sweep_quad_lds_body(
     const SweepTask *__restrict__ tasks, uint32_t task0, uint32_t n_launch,
     const uint2 *__restrict__ entries, const uint32_t *__restrict__ task_rows,
-    const float *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc,
-    float *__restrict__ partial, uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
-    __shared__ uint4 ring[kWavesPerBlock][2][64];          // per wave: two slots of 128 entries
+    const TB *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc,
+    float *__restrict__ partial, uint32_t d, float alpha, float beta, uint32_t flags, float slope,
+    uint4 (&ring)[kWavesPerBlock][2][64]) {   // per wave: two slots of 128 entries
     const int lane = threadIdx.x & 63;
     const uint32_t wib = __builtin_amdgcn_readfirstlane((uint32_t)(threadIdx.x >> 6));
     const uint32_t local = blockIdx.x * kWavesPerBlock + wib;
@@ -579,7 +654,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr
     const uint32_t t = task0 + local;
     const SweepTask task = tasks[t];
     const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(B), 0, b_bytes, 0x00020000);
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<TB *>(B), 0, b_bytes, 0x00020000);
     constexpr int G = 64 / LPE;                       // entries per gather instruction
     constexpr int STEP = 4 * G;                       // entries per loop step (four gathers in flight)
     constexpr int CH = (128 / STEP) * STEP;           // entries consumed per 1 KiB LDS chunk
@@ -588,7 +663,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr
     const uint32_t grp = live ? lane / LPE : G - 1;
     const uint32_t col = sub * 4;
     const bool active = live && col < d;
-    const uint32_t lane_off = (active ? col : 0) * 4u;
+    const uint32_t lane_off = (active ? col : 0) * (uint32_t)sizeof(TB);
     MGGCN_PLANES_ZERO();
     uint32_t cur_row = 0;
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
@@ -621,7 +696,7 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr
                 if (active) {                                    // lanes past the row issue no load (3 % faster)
 #pragma unroll
                     for (int u = 0; u < 4; u++)
-                        b[u] = mggcn_buffer_load_v4f32(rsrc, (int)(__umul24(ent[u].x & kColMask, row_bytes) + lane_off), 0, 0);
+                        b[u] = Gather<TB>::x4(rsrc, __umul24(ent[u].x & kColMask, row_bytes) + lane_off, 0, 0);
                 }
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
@@ -693,6 +768,35 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr
     auto emit4_beta = [&](uint32_t r0, float (&x)[4][4]) { emit4_any(std::true_type{}, r0, x); };
     auto emit4_nobeta = [&](uint32_t r0, float (&x)[4][4]) { emit4_any(std::false_type{}, r0, x); };
     if (beta != 0.f) { MGGCN_PLANES_EMIT_FOURS(emit4_beta) } else { MGGCN_PLANES_EMIT_FOURS(emit4_nobeta) }
+}
+
+template <int LPE>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_quad_lds_kernel(
+    MGGCN_SWEEP_PARAMS(float)) {
+    __shared__ uint4 ring[kWavesPerBlock][2][64];
+    sweep_quad_lds_body<LPE, float>(MGGCN_SWEEP_ARGS, ring);
+}
+template <int LPE>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_quad_lds_b16_kernel(
+    MGGCN_SWEEP_PARAMS(uint16_t)) {
+    __shared__ uint4 ring[kWavesPerBlock][2][64];
+    sweep_quad_lds_body<LPE, uint16_t>(MGGCN_SWEEP_ARGS, ring);
+}
+
+// bf16 image of B for the narrow form / the permuted plan: pitch dp elements (a multiple of 4), columns d..dp-1 zero
+__global__ __launch_bounds__(256) void sweep_repack_b16_kernel(const uint16_t *__restrict__ B, size_t ldb, uint32_t n,
+                                                               uint32_t d, uint16_t *__restrict__ out, uint32_t dp,
+                                                               const uint32_t *__restrict__ src_row) {
+    const uint32_t q4 = dp / 4;
+    const size_t total = (size_t)n * q4;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t r = (uint32_t)(i / q4), c = (uint32_t)(i % q4) * 4;
+        const uint16_t *src = B + (size_t)(src_row ? src_row[r] : r) * ldb + c;
+        uint32_t e[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) e[k] = c + k < d ? src[k] : 0u;
+        *reinterpret_cast<uint2 *>(out + (size_t)r * dp + c) = make_uint2(e[0] | (e[1] << 16), e[2] | (e[3] << 16));
+    }
 }
 
 __global__ __launch_bounds__(256) void sweep_combine_kernel(
@@ -823,21 +927,29 @@ uint32_t sweep_plan_launches(const SweepPlan *p, uint32_t d) {
     return (p->n_tasks + per_launch - 1) / per_launch + (p->n_split_rows ? 1u : 0u);
 }
 
-bool sweep_supports(const SweepPlan *p, uint32_t d, size_t ldb, size_t ldc, const void *B, const void *C) {
+bool sweep_supports(const SweepPlan *p, uint32_t d, size_t ldb, size_t ldc, const void *B, const void *C, size_t elem_bytes) {
     if (!p) return false;
     if (p->n_slots && d > p->max_d) return false;
     // the row gathers address B through a 32-bit buffer descriptor
-    if ((uint64_t)p->n_cols * ldb * sizeof(float) > 0xFFFFFFFFull) return false;
+    if ((uint64_t)p->n_cols * ldb * elem_bytes > 0xFFFFFFFFull) return false;
     (void)ldc; (void)B; (void)C;
     return true;
 }
 
-bool sweep_wants_repack(const SweepPlan *p, uint32_t d, size_t ldb, const void *B) {
+bool sweep_wants_repack(const SweepPlan *p, uint32_t d, size_t ldb, const void *B, size_t elem_bytes) {
     if (!p || !p->lpe || d > 4 * p->lpe || !p->allow_quad) return false;
     // The gather path is priced per 128-byte line touched (~2.7 cycles each, narrow_spmm.py: 16 rows of
     // 64 B per instruction cost 62 cycles, 4 rows of 176 B 26): a 176-byte pitch puts 37 % of the rows
     // on three lines, a pitch that is a multiple of 64 B never more than two.
-    return !(ldb % 16 == 0 && (reinterpret_cast<uintptr_t>(B) & 63u) == 0);
+    return !((ldb * elem_bytes) % 64 == 0 && (reinterpret_cast<uintptr_t>(B) & 63u) == 0);
+}
+
+void sweep_repack_b16(hipStream_t st, const uint16_t *B, size_t ldb, uint32_t n_cols, uint32_t d, uint16_t *out, uint32_t dp,
+                      const uint32_t *src_row) {
+    const size_t total = (size_t)n_cols * (dp / 4);
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)kNumCU * 16);
+    hipLaunchKernelGGL(sweep_repack_b16_kernel, dim3(std::max(grid, 1u)), dim3(256), 0, st, B, ldb, n_cols, d, out, dp, src_row);
+    MGGCN_CHECK_LAUNCH();
 }
 
 void sweep_repack(hipStream_t st, const float *B, size_t ldb, uint32_t n_cols, uint32_t d, float *out, uint32_t dp,
@@ -848,19 +960,37 @@ void sweep_repack(hipStream_t st, const float *B, size_t ldb, uint32_t n_cols, u
     MGGCN_CHECK_LAUNCH();
 }
 
-void sweep_launch(hipStream_t st, const SweepPlan *p, const float *B, size_t ldb, float *C, size_t ldc,
-                  uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
+namespace {
+// the fp32 kernels for TB = float, their "_b16" twins for TB = uint16_t (bf16 bits): same forms, same conditions in
+// elements (a float4 lane's 16-byte alignment is a bf16 lane's 8)
+template <typename TB> struct SweepKernels;
+template <> struct SweepKernels<float> {
+    template <int L> static constexpr auto narrow = spmm_sweep_quad_lds_kernel<L>;
+    template <bool F> static constexpr auto pair = spmm_sweep_pair_kernel<F>;
+    template <int V> static constexpr auto generic = spmm_sweep_kernel<V>;
+};
+template <> struct SweepKernels<uint16_t> {
+    template <int L> static constexpr auto narrow = spmm_sweep_quad_lds_b16_kernel<L>;
+    template <bool F> static constexpr auto pair = spmm_sweep_pair_b16_kernel<F>;
+    template <int V> static constexpr auto generic = spmm_sweep_b16_kernel<V>;
+};
+
+template <typename TB>
+void sweep_launch_t(hipStream_t st, const SweepPlan *p, const TB *B, size_t ldb, float *C, size_t ldc,
+                    uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
+    using K = SweepKernels<TB>;
+    const uintptr_t b_addr = reinterpret_cast<uintptr_t>(B);
     // narrow rows on a quad-padded stream: B must be 16-byte pitched (the caller re-pitches it
     // with sweep_repack when sweep_wants_repack says so)
-    const bool quad = p->lpe && d <= 4 * p->lpe && ldb % 4 == 0 && aligned16(B) && p->allow_quad;
+    const bool quad = p->lpe && d <= 4 * p->lpe && ldb % 4 == 0 && b_addr % (4 * sizeof(TB)) == 0 && p->allow_quad;
     // float4 pair form: 16-byte aligned rows of >= 96 columns (narrower rows would idle most of
     // a half-wave); float2 lanes need 8-byte aligned rows; otherwise one column per lane
-    const bool vec4 = p->run_pad % 2 == 0 && d >= 96 && d % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 && aligned16(B) && aligned16(C) &&
-                      p->allow_vec4;
+    const bool vec4 = p->run_pad % 2 == 0 && d >= 96 && d % 4 == 0 && ldb % 4 == 0 && ldc % 4 == 0 &&
+                      b_addr % (4 * sizeof(TB)) == 0 && aligned16(C) && p->allow_vec4;
     const bool vec2 = d > 64 && d % 2 == 0 && ldb % 2 == 0 && ldc % 2 == 0 &&
-                      (reinterpret_cast<uintptr_t>(B) & 7u) == 0 && (reinterpret_cast<uintptr_t>(C) & 7u) == 0;
-    const uint32_t b_bytes = (uint32_t)((uint64_t)p->n_cols * ldb * sizeof(float));
-    const uint32_t row_bytes = (uint32_t)(ldb * sizeof(float));
+                      b_addr % (2 * sizeof(TB)) == 0 && (reinterpret_cast<uintptr_t>(C) & 7u) == 0;
+    const uint32_t b_bytes = (uint32_t)((uint64_t)p->n_cols * ldb * sizeof(TB));
+    const uint32_t row_bytes = (uint32_t)(ldb * sizeof(TB));
     // One launch = one round of RESIDENT tasks for the float4 kernels (128 VGPRs: four blocks of four
     // waves per CU; six blocks per launch left a third of the waves queued behind the others and out
     // of step: d = 41 1.64 / 1.71 ms against 1.52 / 1.55).  The one-column-per-lane kernels (56 VGPRs)
@@ -875,7 +1005,7 @@ void sweep_launch(hipStream_t st, const SweepPlan *p, const float *B, size_t ldb
         const uint32_t n_waves = tpw > 1 ? std::min(n_launch, p->round_tasks) : n_launch;
         const dim3 grid((n_waves + kWavesPerBlock - 1) / kWavesPerBlock), block(64 * kWavesPerBlock);
 #define MGGCN_LAUNCH_NARROW(L)                                                                             \
-    hipLaunchKernelGGL((spmm_sweep_quad_lds_kernel<L>), grid, block, 0, st, p->d_tasks, t0, n_launch, p->d_entries, \
+    hipLaunchKernelGGL((K::template narrow<L>), grid, block, 0, st, p->d_tasks, t0, n_launch, p->d_entries, \
                        p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d, alpha, beta, narrow_flags, slope)
         if (quad) {
             if (p->lpe == 4) MGGCN_LAUNCH_NARROW(4);
@@ -884,20 +1014,20 @@ void sweep_launch(hipStream_t st, const SweepPlan *p, const float *B, size_t ldb
             else MGGCN_LAUNCH_NARROW(16);
         }
 #undef MGGCN_LAUNCH_NARROW
-        else if (vec4 && row_bytes >= 512u && (row_bytes & (row_bytes - 1u)) == 0 && p->fast_pairs)   // power-of-two pitch
-            hipLaunchKernelGGL((spmm_sweep_pair_kernel<true>), grid, block, 0, st, p->d_tasks, t0, n_launch,
+        else if (vec4 && ldb >= 128u && (row_bytes & (row_bytes - 1u)) == 0 && p->fast_pairs)   // power-of-two pitch >= 128 elements
+            hipLaunchKernelGGL((K::template pair<true>), grid, block, 0, st, p->d_tasks, t0, n_launch,
                                p->d_entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
                                alpha, beta, wide_flags, slope, p->d_stamps, tpw > 1 ? p->round_tasks : n_launch);
         else if (vec4)
-            hipLaunchKernelGGL((spmm_sweep_pair_kernel<false>), grid, block, 0, st, p->d_tasks, t0, n_launch,
+            hipLaunchKernelGGL((K::template pair<false>), grid, block, 0, st, p->d_tasks, t0, n_launch,
                                p->d_entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
                                alpha, beta, wide_flags, slope, p->d_stamps, tpw > 1 ? p->round_tasks : n_launch);
         else if (vec2)
-            hipLaunchKernelGGL((spmm_sweep_kernel<2>), grid, block, 0, st, p->d_tasks, t0, n_launch,
+            hipLaunchKernelGGL((K::template generic<2>), grid, block, 0, st, p->d_tasks, t0, n_launch,
                                p->d_entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
                                alpha, beta, flags, slope);
         else
-            hipLaunchKernelGGL((spmm_sweep_kernel<1>), grid, block, 0, st, p->d_tasks, t0, n_launch,
+            hipLaunchKernelGGL((K::template generic<1>), grid, block, 0, st, p->d_tasks, t0, n_launch,
                                p->d_entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
                                alpha, beta, flags, slope);
         MGGCN_CHECK_LAUNCH();
@@ -907,4 +1037,15 @@ void sweep_launch(hipStream_t st, const SweepPlan *p, const float *B, size_t ldb
                            p->n_split_rows, p->d_partial, C, ldc, d, alpha, beta, flags, slope);
         MGGCN_CHECK_LAUNCH();
     }
+}
+}   // namespace
+
+void sweep_launch(hipStream_t st, const SweepPlan *p, const float *B, size_t ldb, float *C, size_t ldc,
+                  uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
+    sweep_launch_t<float>(st, p, B, ldb, C, ldc, d, alpha, beta, flags, slope);
+}
+
+void sweep_launch_b16(hipStream_t st, const SweepPlan *p, const uint16_t *B, size_t ldb, float *C, size_t ldc,
+                      uint32_t d, float alpha, float beta, uint32_t flags, float slope) {
+    sweep_launch_t<uint16_t>(st, p, B, ldb, C, ldc, d, alpha, beta, flags, slope);
 }

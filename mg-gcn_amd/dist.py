@@ -220,13 +220,25 @@ def gloo_all_gather_rows(host_shard, P: int, group=None):
     """[rows x d] per rank -> [P*rows x d] on every rank, rank order (== ncclAllGather /
     the P broadcasts of reference src/dist_matrix.hpp:458-467)."""
     torch, dist = _torch(), _dist()
-    # ONE output tensor: gloo's list form of all_gather (P output tensors + a concatenation) is 4x slower at these sizes
-    # -- 28 ms against 6.5 ms for four ranks x [2912 x 128] on loopback, the same as P broadcasts
-    # (profiles/experiments/gloo_allgather_r04.log).  That, not plan building, was the 45.9 ms against 12.4 / 9.8 ms of
-    # the all-gather schedule in the round-3 rehearsals (28 exchanges per epoch); the RCCL path never took this branch.
+    # P broadcasts straight into row views of ONE output tensor; this rank's own rows are placed by a plain memcpy.
+    # Nothing here goes through torch's multi-threaded CPU copy, and that is the point: in a rehearsal P ranks share one
+    # host, each with its full intra-op thread pool, and every gloo form that copies through torch ops (all_gather into a
+    # tensor, the list form, list + concatenation) slows down 3-13x there -- all_gather_into_tensor 13.9 ms against 2.1 ms
+    # for this form at four ranks x [2912 x 128] with 16 threads per rank, level with it at one thread per rank
+    # (profiles/experiments/gloo_allgather_views.{py,log}).  That was the all-gather schedule's 49-88 ms per epoch against
+    # 10-13 ms for the broadcast and halo schedules.  (Round 4 replaced the list form for the same symptom:
+    # profiles/experiments/gloo_allgather_r04.log.)  The RCCL path never takes this branch.
     host_shard = host_shard.contiguous()
-    out = torch.empty((P * host_shard.shape[0],) + tuple(host_shard.shape[1:]), dtype=host_shard.dtype)
-    dist.all_gather_into_tensor(out, host_shard, group=group)
+    rows = host_shard.shape[0]
+    out = torch.empty((P * rows,) + tuple(host_shard.shape[1:]), dtype=host_shard.dtype)
+    if rows == 0:
+        return out
+    me = dist.get_rank(group)
+    for i in range(P):
+        view = out[i * rows:(i + 1) * rows]
+        if i == me:
+            view.numpy()[...] = host_shard.numpy()
+        dist.broadcast(view, src=dist.get_global_rank(group, i) if group is not None else i, group=group)
     return out
 
 

@@ -13,6 +13,10 @@ kernels -- identical math, fewer passes:
     (layer i+1's G_out = G_HW . W^T, masked by layer i+1's own input = layer i's activated output),
   * one Adam launch for all parameter tensors of the model instead of 7 per layer.
 ``fused=False`` runs the reference's launch sequence one for one.
+
+``agg_dtype="bf16"`` (opt-in; default ``"f32"``) stores the gathered operand of every SpMM in bf16: each aggregation
+rounds its dense input to bf16 into one model-owned scratch and multiplies with the bf16 SpMM, C = A . bf16(B), sums
+and everything else in fp32 (GEMMs, loss, weights, gradients, Adam).
 """
 from __future__ import annotations
 
@@ -32,14 +36,37 @@ def _torch():
     return torch
 
 
+AGG_DTYPES = ("f32", "bf16")
+
+
+def _check_agg_dtype(agg_dtype: str) -> str:
+    if agg_dtype not in AGG_DTYPES:
+        raise ValueError(f"agg_dtype must be one of {AGG_DTYPES}, not {agg_dtype!r}")
+    return agg_dtype
+
+
 class sparse_linear:
     """reference src/gcn.hpp:13-48: holds (A, A_T); forward SpMM with A, backward with A_T."""
 
-    def __init__(self, name: str, A: csr_matrix, A_T: csr_matrix):
+    def __init__(self, name: str, A: csr_matrix, A_T: csr_matrix, agg_dtype: str = "f32", agg_buffer=None):
         self.name, self.A, self.A_T = name, A, A_T
         self.M = self.M2 = 0
         self.ext_buffer = self.ext_buffer2 = None
         self._max_d = [128, 128]     # plans are sized for at least the reference's hidden width
+        self.agg_dtype = _check_agg_dtype(agg_dtype)
+        self.agg_buffer = agg_buffer  # bf16: flat bf16 device tensor the dense operand is rounded into (grown on demand)
+
+    def _spmm(self, ctx: context, M: csr_matrix, B: dn_matrix, C: dn_matrix, plan, beta: float, flags: int) -> None:
+        if self.agg_dtype == "f32":
+            ops.matmul(ctx, M, B, C, plan, 1.0, beta, flags)
+            return
+        torch = _torch()
+        need = B.n() * B.m()
+        if self.agg_buffer is None or self.agg_buffer.numel() < need:
+            self.agg_buffer = torch.empty(need, dtype=torch.bfloat16, device=ctx.device)
+        B16 = self.agg_buffer[:need].view(B.n(), B.m())
+        ops.convert_bf16(ctx, B, B16)
+        ops.spmm_bf16(ctx, M, B16, C, plan, 1.0, beta, flags)
 
     def __call__(self, ctx: context, B: dn_matrix, C: dn_matrix, discard: bool = True, flags: int = 0) -> None:
         if B.m() != self.M:                                   # workspace cached per width, gcn.hpp:28-31
@@ -50,7 +77,7 @@ class sparse_linear:
                                                         max_d=self._max_d[0])
         n = self.name
         ctx.record(n + "0_0_matmul-spmm", 0)
-        ops.matmul(ctx, self.A, B, C, self.ext_buffer, 1.0, 0.0 if discard else 1.0, flags)
+        self._spmm(ctx, self.A, B, C, self.ext_buffer, 0.0 if discard else 1.0, flags)
         ctx.record(n + "0_1_matmul-spmm", 0)
         ctx.register_timer(n + "0_matmul-spmm", n + "0_0_matmul-spmm", n + "0_1_matmul-spmm")
 
@@ -63,7 +90,7 @@ class sparse_linear:
                                                          max_d=self._max_d[1])
         n = self.name
         ctx.record(n + "1_0_matmul-spmm", 0)
-        ops.matmul(ctx, self.A_T, G, G_out, self.ext_buffer2, 1.0, 0.0 if discard else 1.0)
+        self._spmm(ctx, self.A_T, G, G_out, self.ext_buffer2, 0.0 if discard else 1.0, 0)
         ctx.record(n + "1_1_matmul-spmm", 0)
         ctx.register_timer(n + "1_matmul-spmm", n + "1_0_matmul-spmm", n + "1_1_matmul-spmm")
 
@@ -173,10 +200,11 @@ class gcn_layer:
     AHW / G_out alias the layer's AHW_buffer (:433-434)."""
 
     def __init__(self, name: str, A: csr_matrix, A_T: csr_matrix, in_: int, out: int, activation: bool,
-                 residual_layer: bool = False, backward_spmm: bool = True, HW_buffer=None, fused: bool = False):
+                 residual_layer: bool = False, backward_spmm: bool = True, HW_buffer=None, fused: bool = False,
+                 agg_dtype: str = "f32", agg_buffer=None):
         torch = _torch()
         self.name = name
-        self.A = sparse_linear(name, A, A_T)
+        self.A = sparse_linear(name, A, A_T, agg_dtype, agg_buffer)
         self.lin = linear(name, in_, out, backward_spmm, fused)
         # residual connection (gcn.hpp:418, :430): a second linear when the widths differ, a plain add otherwise
         self.residual_layer = bool(residual_layer)
@@ -420,8 +448,12 @@ class gcn:
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], residual_layer: bool = False,
                  weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None, fused: bool = True,
-                 hoist_first_aggregation: bool = False):
+                 hoist_first_aggregation: bool = False, agg_dtype: str = "f32"):
         torch = _torch()
+        self.agg_dtype = _check_agg_dtype(agg_dtype)
+        if self.agg_dtype != "f32" and hoist_first_aggregation:
+            raise ValueError("hoist_first_aggregation is fp32-only: with agg_dtype='bf16' the hoisted product would "
+                             "round X instead of X W")
         self.fused = fused
         self.loss_layer = softmax_cross_entropy_loss(f"{len(sizes) - 1}_", residual_layer, fused)
         A.normalize(True)
@@ -429,10 +461,14 @@ class gcn:
         self.A, self.A_T = A, A_T
         max_d = max(min(sizes[i], sizes[i + 1]) for i in range(len(sizes) - 1))
         self.HW_buffer = torch.empty(max(A.n(), A.m()) * max_d, dtype=torch.float32, device="cuda")
+        # bf16 aggregation: every SpMM's dense operand is rounded into this one scratch (n x the widest SpMM width)
+        self.agg_buffer = (torch.empty(max(A.n(), A.m()) * max_d, dtype=torch.bfloat16, device="cuda")
+                           if self.agg_dtype == "bf16" else None)
         self.layers_: List[gcn_layer] = []
         for i in range(1, len(sizes)):
             self.layers_.append(gcn_layer(f"{i - 1}_", A_T, A, sizes[i - 1], sizes[i], i + 1 < len(sizes),
-                                          residual_layer, i != 1, self.HW_buffer, fused))
+                                          residual_layer, i != 1, self.HW_buffer, fused, self.agg_dtype,
+                                          self.agg_buffer))
         link_fused_backward(self.layers_, fused)
         self._adam = None
         self.set_hoist_first_aggregation(hoist_first_aggregation)
@@ -452,6 +488,9 @@ class gcn:
         """Pre-compute the first layer's aggregation A_fwd . X once (see gcn_layer.__call__): valid while the SAME
         feature matrix is passed every epoch (full-graph training does) and only for a GEMM-first first layer without a
         residual branch; 6 instead of 7 SpMMs per epoch on the Reddit model.  Off = the reference's epoch."""
+        if on and self.agg_dtype != "f32":
+            raise ValueError("hoist_first_aggregation is fp32-only: with agg_dtype='bf16' the hoisted product would "
+                             "round X instead of X W")
         l0 = self.layers_[0]
         # A_fwd (1 b^T) = 1 b^T needs EVERY row of A_fwd to sum to one: a vertex without a single entry in its row of
         # A_fwd (no self-loop, nobody points at it) has row sum 0 and would get 0 instead of b -- the reference's data-prep

@@ -20,6 +20,16 @@
 #include "matrix.hpp"
 #include "ops.hpp"
 
+// Storage of the gathered operand of the model's SpMMs: f32 (the reference's), or bf16 -- every aggregation rounds its
+// dense input to bf16 into one model-owned scratch and multiplies with mggcn_spmm_csr_bf16 (sums and all else fp32).
+enum class agg_dtype { f32, bf16 };
+
+inline agg_dtype agg_dtype_from_string(const std::string &s) {
+    if (s.empty() || s == "f32") return agg_dtype::f32;
+    if (s == "bf16") return agg_dtype::bf16;
+    throw std::invalid_argument("aggregation dtype must be f32 or bf16, not '" + s + "'");
+}
+
 template <typename x_t, typename v_t, typename r_t>
 class sparse_linear {
     using csr_t = csr_matrix<x_t, v_t, r_t>;
@@ -27,15 +37,30 @@ class sparse_linear {
     std::string name;
     csr_t A, A_T;
     spmm_buffer ext_buffer, ext_buffer2;
+    agg_dtype agg;
+    mggcn::device_ptr<std::uint16_t> agg_buffer;     // bf16: the rounded dense operand (shared by the model's layers)
+    std::size_t agg_capacity;
+
+    void spmm(context ctx, const csr_t &M, dn_t B, dn_t C, const spmm_buffer &plan, r_t beta, uint32_t flags) {
+        if (agg == agg_dtype::f32) { matmul(ctx, M, B, C, plan, (r_t)1, beta, flags); return; }
+        if (!agg_buffer || agg_capacity < B.n() * B.m()) {
+            agg_capacity = B.n() * B.m();
+            agg_buffer = mggcn::device_malloc<std::uint16_t>(agg_capacity);
+        }
+        convert_bf16(ctx, B, agg_buffer.get(), B.m());
+        matmul_bf16(ctx, M, agg_buffer.get(), B.m(), C, plan, (r_t)1, beta, flags);
+    }
 
 public:
-    sparse_linear(std::string name, csr_t A, csr_t A_T) : name(name), A(A), A_T(A_T) {}
+    sparse_linear(std::string name, csr_t A, csr_t A_T, agg_dtype agg = agg_dtype::f32,
+                  mggcn::device_ptr<std::uint16_t> agg_buffer = nullptr, std::size_t agg_capacity = 0)
+        : name(name), A(A), A_T(A_T), agg(agg), agg_buffer(agg_buffer), agg_capacity(agg_buffer ? agg_capacity : 0) {}
     const csr_t &forward_matrix() const { return A; }
 
     void operator()(context ctx, dn_t B, dn_t C, bool discard = true, uint32_t flags = 0) {
         if (!ext_buffer) ext_buffer = get_matmul_buffer(ctx, A, B, C);      // plan is width-independent up to 128+
         ctx.record(name + "0_0_matmul-spmm", 0);
-        matmul(ctx, A, B, C, ext_buffer, (r_t)1, discard ? (r_t)0 : (r_t)1, flags);
+        spmm(ctx, A, B, C, ext_buffer, discard ? (r_t)0 : (r_t)1, flags);
         ctx.record(name + "0_1_matmul-spmm", 0);
         ctx.register_timer(name + "0_matmul-spmm", name + "0_0_matmul-spmm", name + "0_1_matmul-spmm");
     }
@@ -43,7 +68,7 @@ public:
     void backward(context ctx, dn_t G, dn_t G_out, bool discard = true) {
         if (!ext_buffer2) ext_buffer2 = get_matmul_buffer(ctx, A_T, G, G_out);
         ctx.record(name + "1_0_matmul-spmm", 0);
-        matmul(ctx, A_T, G, G_out, ext_buffer2, (r_t)1, discard ? (r_t)0 : (r_t)1);
+        spmm(ctx, A_T, G, G_out, ext_buffer2, discard ? (r_t)0 : (r_t)1, 0);
         ctx.record(name + "1_1_matmul-spmm", 0);
         ctx.register_timer(name + "1_matmul-spmm", name + "1_0_matmul-spmm", name + "1_1_matmul-spmm");
     }
@@ -372,8 +397,9 @@ public:
 
     gcn_layer(std::string name, csr_matrix<x_t, v_t, r_t> A, csr_matrix<x_t, v_t, r_t> A_T, std::size_t in, std::size_t out,
               bool activation, bool residual_layer = false, bool backward_spmm = true,
-              mggcn::device_ptr<r_t> HW_buffer = nullptr, bool fused = false)
-        : name(name), A(name, A, A_T), lin(name, in, out, backward_spmm, fused),
+              mggcn::device_ptr<r_t> HW_buffer = nullptr, bool fused = false, agg_dtype agg = agg_dtype::f32,
+              mggcn::device_ptr<std::uint16_t> agg_buffer = nullptr, std::size_t agg_capacity = 0)
+        : name(name), A(name, A, A_T, agg, agg_buffer, agg_capacity), lin(name, in, out, backward_spmm, fused),
           res_lin(in == out || !residual_layer ? std::nullopt : std::make_optional(linear<r_t>(name, in, out, backward_spmm, false))),
           residual_layer(residual_layer),
           HW(A.m(), std::min(in, out), HW_buffer ? HW_buffer : mggcn::device_malloc<r_t>(std::max<std::size_t>(A.m(), A_T.n()) * std::min(in, out))),
@@ -705,19 +731,25 @@ class gcn {
     std::vector<gcn_layer<x_t, v_t, r_t>> layers_;
     softmax_cross_entropy_loss<r_t, std::int32_t> loss_layer;
     mggcn::device_ptr<r_t> HW_buffer;
+    agg_dtype agg_ = agg_dtype::f32;
+    mggcn::device_ptr<std::uint16_t> agg_buffer_;
 
 public:
     // normalises A by column, A_T = A^T, layers get (A_T, A) (reference :946-955)
-    gcn(csr_matrix<x_t, v_t, r_t> A, std::vector<std::size_t> sizes, bool residual_layer = false, bool fused = true)
-        : loss_layer(std::to_string(sizes.size() - 1) + "_", residual_layer, fused) {
+    // agg: storage of the SpMMs' gathered operand (agg_dtype::bf16: one bf16 scratch of n x the widest SpMM width)
+    gcn(csr_matrix<x_t, v_t, r_t> A, std::vector<std::size_t> sizes, bool residual_layer = false, bool fused = true,
+        agg_dtype agg = agg_dtype::f32)
+        : loss_layer(std::to_string(sizes.size() - 1) + "_", residual_layer, fused), agg_(agg) {
         A.normalize(true);
         auto A_T = A.transpose();
         std::size_t max_d = 0;
         for (std::size_t i = 0; i + 1 < sizes.size(); i++) max_d = std::max(max_d, std::min(sizes[i], sizes[i + 1]));
         HW_buffer = mggcn::device_malloc<r_t>(std::max<std::size_t>(A.n(), A.m()) * max_d);
+        const std::size_t agg_capacity = agg == agg_dtype::bf16 ? std::max<std::size_t>(A.n(), A.m()) * max_d : 0;
+        if (agg_capacity) agg_buffer_ = mggcn::device_malloc<std::uint16_t>(agg_capacity);
         for (std::size_t i = 1; i < sizes.size(); i++)
             layers_.emplace_back(std::to_string(i - 1) + "_", A_T, A, sizes[i - 1], sizes[i], i + 1 < sizes.size(), residual_layer,
-                                 i != 1, HW_buffer, fused);
+                                 i != 1, HW_buffer, fused, agg, agg_buffer_, agg_capacity);
         link_fused_backward(layers_, fused);
         fused_ = fused;
         // the SpMM plans of the model, built side by side now instead of one by one inside the first epoch
@@ -733,7 +765,11 @@ public:
     // Optional mode (never the reference's epoch): pre-compute the first layer's aggregation A_fwd . X once -- valid while
     // the SAME feature matrix is passed every epoch (full-graph training does); 6 instead of 7 SpMMs per epoch on the
     // Reddit model.  `mg_gcn` turns it on with MGGCN_HOIST_FIRST_AGGREGATION=1.
-    void set_hoist_first_aggregation(bool on) { layers_.front().set_hoist_input(on); }
+    // (fp32 aggregation only: with bf16 the hoisted product would round X instead of X W)
+    void set_hoist_first_aggregation(bool on) {
+        mggcn_require(!on || agg_ == agg_dtype::f32, "hoist_first_aggregation needs the f32 aggregation");
+        layers_.front().set_hoist_input(on);
+    }
 
     // test constructor with given weights (reference :957-963)
     gcn(csr_matrix<x_t, v_t, r_t> A, std::vector<std::size_t> sizes, std::vector<std::pair<std::vector<r_t>, std::vector<r_t>>> weights)

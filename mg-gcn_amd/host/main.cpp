@@ -13,7 +13,8 @@
 // reference's broadcast pipeline); MGGCN_FUSED=0 replays the reference's launch sequence;
 // MGGCN_OVERSUBSCRIBE=1 lets -P exceed the visible GPUs (ranks wrap over them, peer-copy transport);
 // MGGCN_HOIST_FIRST_AGGREGATION=1 (single GPU) pre-computes the first layer's A.X once (6 SpMMs per epoch: not the
-// reference's epoch, same results at 1e-4); MGGCN_TIMING=1 prints the start-up stages.
+// reference's epoch, same results at 1e-4); MGGCN_AGG_DTYPE=bf16 (single GPU, not -R 1) stores the SpMMs' gathered
+// operand in bf16 (f32 or unset: the reference's fp32); MGGCN_TIMING=1 prints the start-up stages.
 #include <unistd.h>
 
 #include <chrono>
@@ -103,6 +104,10 @@ int main_(int argc, char **argv) {
     const char *mode_env = std::getenv("MGGCN_DIST_MODE");
     const dist_mode mode = dist_mode_from_string(mode_env ? mode_env : "");
     const bool oversubscribe = std::getenv("MGGCN_OVERSUBSCRIBE") && !env_is("MGGCN_OVERSUBSCRIBE", "0");
+    const char *agg_env = std::getenv("MGGCN_AGG_DTYPE");
+    const agg_dtype agg = agg_dtype_from_string(agg_env ? agg_env : "");
+    if (agg != agg_dtype::f32 && (P > 1 || row_partition))          // the distributed classes have no bf16 aggregation
+        throw arg_error("MGGCN_AGG_DTYPE=bf16 is single-GPU only (not with -P > 1 or -R 1)");
 
     while (optind < argc && argv[optind] != nullptr) {
         const std::string command = argv[optind++];
@@ -149,7 +154,7 @@ int main_(int argc, char **argv) {
 
         if (P <= 1 && !row_partition) {
             auto ctx = context(0);
-            gcn<x_t, v_t, r_t> G(A, sizes, false, fused);
+            gcn<x_t, v_t, r_t> G(A, sizes, false, fused, agg);
             if (env_is("MGGCN_HOIST_FIRST_AGGREGATION", "1")) G.set_hoist_first_aggregation(true);   // optional 6-SpMM epoch
             ctx.sync();
             stage("model (normalize, transpose, layers)");

@@ -39,6 +39,36 @@ void matmul(const context ctx, const csr_matrix<x_t, v_t, r_t> A, const dn_matri
                        B.buffer(), B.m(), C.buffer(), C.m(), (uint32_t)B.m(), alpha, beta, flags, slope);
 }
 
+// bf16 aggregation (include/mggcn.h: mggcn_convert_f32_bf16, mggcn_spmm_csr_bf16): dst = bf16(src), dst an n x ld_dst
+// array of bf16 bit patterns; C = alpha A widen(B16) + beta C with B16 an A.m() x C.m() bf16 array of row pitch ldb.
+// The two entry points were added to ABI version 1 later: they are weak references here, so that a program built on this
+// layer still links and runs against a library (or a CPU model of the ABI) without them -- until it asks for bf16.
+#pragma weak mggcn_convert_f32_bf16
+#pragma weak mggcn_spmm_csr_bf16
+inline void require_bf16_aggregation() {
+    mggcn_require(&mggcn_convert_f32_bf16 != nullptr && &mggcn_spmm_csr_bf16 != nullptr,
+                  "this libmggcn_hip.so has no bf16 aggregation (mggcn_spmm_csr_bf16)");
+}
+
+template <typename r_t>
+void convert_bf16(const context ctx, const dn_matrix<r_t> src, std::uint16_t *dst, const std::size_t ld_dst) {
+    require_bf16_aggregation();
+    ctx.set();
+    mggcn_convert_f32_bf16(ctx.stream(0), src.buffer(), src.m(), dst, ld_dst, src.n(), src.m());
+}
+
+template <typename x_t, typename v_t, typename r_t>
+void matmul_bf16(const context ctx, const csr_matrix<x_t, v_t, r_t> A, const std::uint16_t *B16, const std::size_t ldb,
+                 const dn_matrix<r_t> C, const spmm_buffer ext_buffer, const r_t alpha, const r_t beta,
+                 const uint32_t flags = MGGCN_SPMM_DEFAULT, const r_t slope = 0.01f) {
+    require_bf16_aggregation();
+    mggcn_require(ldb >= C.m(), "matmul_bf16: ldb smaller than the feature width");
+    ctx.set();
+    auto [indptr, indices, data] = A.buffer();
+    mggcn_spmm_csr_bf16(ctx.stream(0), ext_buffer.get(), A.n(), A.m(), indptr.get(), indices.get(), data.get(),
+                        B16, ldb, C.buffer(), C.m(), (uint32_t)C.m(), alpha, beta, flags, slope);
+}
+
 // ---- GEMM ------------------------------------------------------------------------------
 template <typename r_t>
 void matmul(const context ctx, const dn_matrix<r_t> A, const dn_matrix<r_t> B, const dn_matrix<r_t> C, const r_t alpha,

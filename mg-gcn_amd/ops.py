@@ -124,18 +124,62 @@ def matmul(ctx: context, A, B: dn_matrix, C: dn_matrix, *args, **kw) -> None:
     return _gemm(ctx, A, B, C, *args, **kw)
 
 
+def _current_plan(ctx: context, A: csr_matrix, ext_buffer: Optional[spmm_buffer], d: int) -> Optional[spmm_buffer]:
+    if ext_buffer is not None and ext_buffer.version != A._version:
+        # the matrix was edited in place after the plan was built (csr_matrix.normalize / invalidate): the
+        # reference's cuSPARSE workspace holds no values, so the same call sequence must keep working
+        ext_buffer = spmm_plan_for(ctx, A, ext_buffer.max_d, ext_buffer.d_hint or d)
+    return ext_buffer
+
+
 def _spmm(ctx: context, A: csr_matrix, B: dn_matrix, C: dn_matrix, ext_buffer: Optional[spmm_buffer],
           alpha: float, beta: float, flags: int = 0, slope: float = 0.01, stream_id: int = 0) -> None:
     _req(A.m() == B.n() and B.m() == C.m() and A.n() == C.n(), "SpMM shape mismatch")
     ctx.set()
-    if ext_buffer is not None and ext_buffer.version != A._version:
-        # the matrix was edited in place after the plan was built (csr_matrix.normalize / invalidate): the
-        # reference's cuSPARSE workspace holds no values, so the same call sequence must keep working
-        ext_buffer = spmm_plan_for(ctx, A, ext_buffer.max_d, ext_buffer.d_hint or B.m())
+    ext_buffer = _current_plan(ctx, A, ext_buffer, B.m())
     ip, ix, dv = A.device(ctx.device)
     ctx.lib.mggcn_spmm_csr_f32(ctx.stream(stream_id), ext_buffer.handle if ext_buffer else None, A.n(), A.m(),
                                ip.data_ptr(), ix.data_ptr(), dv.data_ptr(), B.buffer(), B.m(), C.buffer(),
                                C.m(), B.m(), alpha, beta, flags, slope)
+
+
+def _bf16_view(t, what: str):
+    """(data pointer, rows, columns, leading dimension in elements) of a 2-D device tensor of 2-byte elements
+    (torch.bfloat16, or int16 / uint16 holding bf16 bit patterns) with unit column stride"""
+    _req(t.dim() == 2 and t.element_size() == 2 and t.is_cuda, f"{what}: a 2-D device tensor of bf16 (2-byte) elements")
+    _req(t.stride(1) == 1 or t.shape[1] <= 1, f"{what}: columns must be contiguous")
+    return t.data_ptr(), int(t.shape[0]), int(t.shape[1]), int(max(t.stride(0), t.shape[1]))
+
+
+def convert_bf16(ctx: context, src, dst, stream_id: int = 0) -> None:
+    """dst = bf16(src), rounded to nearest even (NaN stays NaN, overflow -> inf): mggcn_convert_f32_bf16.
+    src: a dn_matrix or a 2-D fp32 device tensor (unit column stride); dst: a 2-D bf16 device tensor of the same shape,
+    any row stride (see _bf16_view)."""
+    if isinstance(src, dn_matrix):
+        s_ptr, n, m, ld_s = src.buffer(), src.n(), src.m(), src.m()
+    else:
+        _req(src.dim() == 2 and src.element_size() == 4 and src.is_cuda and (src.stride(1) == 1 or src.shape[1] <= 1),
+             "convert_bf16: src must be a dn_matrix or a 2-D fp32 device tensor")
+        s_ptr, n, m, ld_s = src.data_ptr(), int(src.shape[0]), int(src.shape[1]), int(max(src.stride(0), src.shape[1]))
+    d_ptr, dn, dm, ld_d = _bf16_view(dst, "convert_bf16 dst")
+    _req((dn, dm) == (n, m), "convert_bf16: shape mismatch")
+    ctx.set()
+    ctx.lib.mggcn_convert_f32_bf16(ctx.stream(stream_id), s_ptr, ld_s, d_ptr, ld_d, n, m)
+
+
+def spmm_bf16(ctx: context, A: csr_matrix, B16, C: dn_matrix, ext_buffer: Optional[spmm_buffer] = None,
+              alpha: float = 1.0, beta: float = 0.0, flags: int = 0, slope: float = 0.01, stream_id: int = 0) -> None:
+    """C = alpha A widen(B16) + beta C with B stored in bf16 (mggcn_spmm_csr_bf16): the products and sums are fp32 and
+    equal those of matmul(ctx, A, widen(B16), C, ext_buffer, ...) bit for bit.  B16: 2-D bf16 device tensor of
+    A.m() x C.m() (any row stride, see _bf16_view); ext_buffer: the same plans the fp32 SpMM uses."""
+    b_ptr, bn, bm, ldb = _bf16_view(B16, "spmm_bf16 B")
+    _req(A.m() == bn and bm == C.m() and A.n() == C.n(), "SpMM shape mismatch")
+    ctx.set()
+    ext_buffer = _current_plan(ctx, A, ext_buffer, bm)
+    ip, ix, dv = A.device(ctx.device)
+    ctx.lib.mggcn_spmm_csr_bf16(ctx.stream(stream_id), ext_buffer.handle if ext_buffer else None, A.n(), A.m(),
+                                ip.data_ptr(), ix.data_ptr(), dv.data_ptr(), b_ptr, ldb, C.buffer(), C.m(), bm,
+                                alpha, beta, flags, slope)
 
 
 def _gemm(ctx: context, A: dn_matrix, B: dn_matrix, C: dn_matrix, alpha: float, beta: float,
