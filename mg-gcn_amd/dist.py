@@ -44,7 +44,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, ops
-from .gcn import MGGCN_SPMM_LEAKY_RELU, _SQRT_1_3, adam_update_all, link_fused_backward, softmax_cross_entropy_loss
+from .gcn import adam_update_all, layer_body, linear, link_fused_backward, softmax_cross_entropy_loss
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -742,126 +742,65 @@ class dist_sparse_linear:
         self._run(dctx, self.A_T, "1_", G, G_out, discard, 0)
 
 
-class dist_row_linear:
+class dist_row_linear(linear):
     """reference src/gcn.hpp:191-296: replicated W/b, row-sharded X; G_b and G_W are
-    summed over ranks (one fused all-reduce instead of the reference's two)."""
+    summed over ranks (one fused all-reduce instead of the reference's two).  The body is gcn.linear on this
+    rank's shard and replica; W()/b()/GW()/Gb() of the layer are repl_dn_matrix views of them."""
 
     def __init__(self, dctx: dist_context, name: str, in_: int, out: int, backward_out: bool = True,
                  fused: bool = False):
-        self.name = name
-        self.W, self.b = repl_dn_matrix(dctx, in_, out), repl_dn_matrix(dctx, 1, out)
+        self._dctx = dctx
+        self._grad_pending = None
+        with _torch().cuda.device(dctx.ctx.device):
+            linear.__init__(self, name, in_, out, backward_out, fused)
+
+    def _gradients(self, in_: int, out: int):
+        torch = _torch()
         # G_W and G_b live in ONE buffer: a single in-place all-reduce, no packing copies
         off_b = (in_ * out + 3) // 4 * 4                       # keep G_b 16-byte aligned
         # ... and four more floats after G_b: the model's LAST layer carries the epoch's two loss sums through its gradient
         # all-reduce there (dist_gcn.train_step: no collective of their own)
         off_t = (off_b + out + 3) // 4 * 4
-        self.G_flat = _torch().zeros(off_t + 4, dtype=_torch().float32, device=dctx.ctx.device)
+        self.G_flat = torch.zeros(off_t + 4, dtype=torch.float32, device=self._dctx.ctx.device)
         self.tail = self.G_flat[off_t:off_t + 2]
-        self.G_W = repl_dn_matrix.__new__(repl_dn_matrix)
-        self.G_W.local = dn_matrix(in_, out, self.G_flat)
-        self.G_b = repl_dn_matrix.__new__(repl_dn_matrix)
-        self.G_b.local = dn_matrix(1, out, self.G_flat[off_b:])
-        _torch().cuda.current_stream().synchronize()            # torch zeroes on ITS stream (the padding takes part in the sum);
-                                                                # the kernels run on the context's
-        self._grad_pending = None
-        self._dctx = dctx
-        self.backward_out, self.fused = backward_out, fused
-        self.W.init(dctx)
-        self.b.init(dctx, _SQRT_1_3)
-        self.X = None
-        self.ones = None
-        self.mW = self.vW = self.mb = self.vb = None
-        self.step = 0
+        torch.cuda.current_stream().synchronize()              # torch zeroes on ITS stream (the padding takes part in the sum);
+                                                               # the kernels run on the context's
+        return dn_matrix(in_, out, self.G_flat), dn_matrix(1, out, self.G_flat[off_b:])
 
-    def setX(self, X): self.X = X
-
-    def __call__(self, dctx: dist_context, X: dist_row_dn_matrix, XW: dist_row_dn_matrix,
-                 discard: bool = True) -> None:
-        ctx, n = dctx.ctx, self.name
-        if self.fused and discard:
-            ctx.record(n + "0_0_matmul-gemm", 0)
-            ops.linear_forward(ctx, X.local, self.W.local, self.b.local, XW.local)
-        else:
-            ops.broadcast_rows(ctx, self.b.local, XW.local, discard)
-            ctx.record(n + "0_0_matmul-gemm", 0)
-            ops.matmul(ctx, X.local, self.W.local, XW.local, 1.0, 1.0)
-        ctx.record(n + "0_1_matmul-gemm", 0)
-        ctx.register_timer(n + "0_matmul-gemm", n + "0_0_matmul-gemm", n + "0_1_matmul-gemm")
-        self.X = X
-
-    def backward(self, dctx: dist_context, G: dist_row_dn_matrix, G_out: Optional[dist_row_dn_matrix],
-                 discard: bool = True, mask: Optional[dist_row_dn_matrix] = None) -> None:
-        ctx, n = dctx.ctx, self.name
-        if self.ones is None or self.ones.m() != G.local.n():
-            self.ones = dn_matrix(1, G.local.n(), device=ctx.device)
-            ctx.fill(self.ones, 1.0)
-        ctx.record(n + "1_0_matmul-gemm", 0)
-        if self.fused:
-            ops.linear_backward_weights(ctx, self.X.local, G.local, self.G_W.local, self.G_b.local)
-        else:
-            ops.matmul(ctx, self.ones, G.local, self.G_b.local, 1.0, 0.0)
-            ops.matmul(ctx, self.X.local, G.local, self.G_W.local, 1.0, 0.0, True)
+    def _reduce_gradients(self, ctx: context) -> None:
         # summed over ranks on the comm stream while the backward pass goes on; awaited by
         # finish_backward() (end of dist_gcn.backward) / adam_update
-        self._grad_pending = dctx.all_reduce_sum_async(self.G_flat, 0)
-        ctx.record(n + "1_2_matmul-gemm", 0)
-        if self.backward_out and mask is not None:             # leaky_relu' of the layer below in the epilogue
-            ops.matmul_lrelu_backward(ctx, G.local, self.W.local, mask.local, G_out.local, 1.0, False, True)
-        elif self.backward_out:
-            ops.matmul(ctx, G.local, self.W.local, G_out.local, 1.0, 0.0 if discard else 1.0, False, True)
-        ctx.record(n + "1_3_matmul-gemm", 0)
-        ctx.register_timer(n + "1_matmul-gemm", n + "1_0_matmul-gemm", n + "1_3_matmul-gemm")
+        self._grad_pending = self._dctx.all_reduce_sum_async(self.G_flat, 0)
 
-    def finish_backward(self, dctx: dist_context) -> None:
+    def finish_backward(self, dctx) -> None:
         if self._grad_pending is not None:
             self._grad_pending.wait(0)
             self._grad_pending = None
 
-    def adam_state(self, ctx: context) -> None:
-        if self.mW is None:
-            d = self._dctx
-            self.mW, self.vW = repl_dn_matrix(d, self.W.shape()), repl_dn_matrix(d, self.W.shape())
-            self.mb, self.vb = repl_dn_matrix(d, self.b.shape()), repl_dn_matrix(d, self.b.shape())
-            for t in (self.mW, self.vW, self.mb, self.vb):
-                t.zero(d)
-            self.step = 0
-
-    def adam_tensors(self, weight_decay: float):
-        return [(self.W.local, self.G_W.local, self.mW.local, self.vW.local, weight_decay),
-                (self.b.local, self.G_b.local, self.mb.local, self.vb.local, 0.0)]
-
-    def adam_update(self, dctx: dist_context, lr, beta1, beta2, weight_decay, eps) -> None:
-        ctx = dctx.ctx
-        self.finish_backward(dctx)
-        self.adam_state(ctx)
-        self.step += 1
-        bc1 = float(np.float32(1 - beta1 ** self.step))
-        bc2 = float(np.float32(1 - beta2 ** self.step))
-        n = self.name
-        ctx.record(n + "0_adam-update", 0)
-        W, GW, b, Gb = self.W.local, self.G_W.local, self.b.local, self.G_b.local
-        if self.fused:
-            ops.adam_fused(ctx, W, GW, self.mW.local, self.vW.local, lr, beta1, beta2, weight_decay, bc1, bc2, eps)
-            ops.adam_fused(ctx, b, Gb, self.mb.local, self.vb.local, lr, beta1, beta2, 0.0, bc1, bc2, eps)
-        else:
-            ops.axpy(ctx, W, GW, weight_decay)
-            ops.axpby(ctx, GW, self.mW.local, 1 - beta1, beta1)
-            ops.axpby(ctx, Gb, self.mb.local, 1 - beta1, beta1)
-            ops.aaxpby(ctx, GW, self.vW.local, 1 - beta2, beta2)
-            ops.aaxpby(ctx, Gb, self.vb.local, 1 - beta2, beta2)
-            ops.adam_final(ctx, W, self.mW.local, self.vW.local, lr, bc1, bc2, eps)
-            ops.adam_final(ctx, b, self.mb.local, self.vb.local, lr, bc1, bc2, eps)
-        ctx.record(n + "1_adam-update", 0)
-        ctx.register_timer(n + "adam-update", n + "0_adam-update", n + "1_adam-update")
-
-    def get_b(self): return self.b
-    def get_W(self): return self.W
-    def get_G_W(self): return self.G_W
-    def get_G_b(self): return self.G_b
+    def get_b(self): return _repl_view(self.b)
+    def get_W(self): return _repl_view(self.W)
+    def get_G_W(self): return _repl_view(self.G_W)
+    def get_G_b(self): return _repl_view(self.G_b)
 
 
-class dist_gcn_layer:
-    """reference src/gcn.hpp:520-637 (row_partition = true)."""
+class _rank_aggregation:
+    """dist_sparse_linear as the aggregation operator of layer_body: this rank's shards in, the exchange over ``dctx``"""
+
+    def __init__(self, dctx: dist_context, op: "dist_sparse_linear"):
+        self.dctx, self.op = dctx, op
+
+    def _shard(self, M: dn_matrix) -> dist_row_dn_matrix:
+        return _wrap_local(M, M.n() * self.dctx.P)
+
+    def __call__(self, ctx: context, B: dn_matrix, C: dn_matrix, discard: bool = True, flags: int = 0) -> None:
+        self.op(self.dctx, self._shard(B), self._shard(C), discard, flags)
+
+    def backward(self, ctx: context, G: dn_matrix, G_out: dn_matrix, discard: bool = True) -> None:
+        self.op.backward(self.dctx, self._shard(G), self._shard(G_out), discard)
+
+
+class dist_gcn_layer(layer_body):
+    """reference src/gcn.hpp:520-637 (row_partition = true): gcn.layer_body on this rank's rows."""
 
     def __init__(self, dctx: dist_context, name: str, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
                  in_: int, out: int, activation: bool, residual_layer: bool = False, backward_spmm: bool = True,
@@ -869,94 +808,29 @@ class dist_gcn_layer:
                  mode: str = "allgather"):
         torch = _torch()
         P, dev = dctx.P, dctx.ctx.device
-        self.name = name
         self.A = dist_sparse_linear(name, A, A_T, bcast_buffer, bcast_buffer2, mode)
-        self.lin = dist_row_linear(dctx, name, in_, out, backward_spmm, fused)
-        self.residual_layer = bool(residual_layer)            # gcn.hpp:527-553
-        self.res_lin = dist_row_linear(dctx, name, in_, out, backward_spmm, False) if residual_layer and in_ != out else None
+        lin = dist_row_linear(dctx, name, in_, out, backward_spmm, fused)
+        res_lin = dist_row_linear(dctx, name, in_, out, backward_spmm, False) if residual_layer and in_ != out else None
         mn = min(in_, out)
         self.AHW_buffer = torch.empty(max(A.n() * out, A_T.n() * in_) // P, dtype=torch.float32, device=dev)
-        self.HW = dist_row_dn_matrix(dctx, A.m(), mn, HW_buffer)
-        self.AHW = dist_row_dn_matrix(dctx, A.n(), out, self.AHW_buffer)
-        self.G_HW = dist_row_dn_matrix(dctx, A_T.n(), mn, HW_buffer)
-        self.G_out = dist_row_dn_matrix(dctx, A_T.n(), in_, self.AHW_buffer)
-        self.activation, self.backward_spmm, self.fused = activation, backward_spmm, fused
-        self.H = None
-        self.mask_input_grad = self.grad_premasked = False      # see gcn.link_fused_backward
 
-    def gemm_first(self) -> bool:
-        return self.HW.m() == self.AHW.m()
+        def shard(N, M, buf):
+            return dist_row_dn_matrix(dctx, N, M, buf).local
+
+        layer_body.__init__(self, name, _rank_aggregation(dctx, self.A), lin, res_lin, residual_layer,
+                            shard(A.m(), mn, HW_buffer), shard(A.n(), out, self.AHW_buffer),
+                            shard(A_T.n(), mn, HW_buffer), shard(A_T.n(), in_, self.AHW_buffer),
+                            activation, backward_spmm, fused)
 
     def __call__(self, dctx: dist_context, H: dist_row_dn_matrix) -> dist_row_dn_matrix:
-        ctx, n = dctx.ctx, self.name
-        self.H = H
-        act_done = False
-        if self.HW.m() == self.AHW.m():
-            self.lin(dctx, H, self.HW)
-            if self.fused and self.activation:
-                self.A(dctx, self.HW, self.AHW, True, MGGCN_SPMM_LEAKY_RELU)
-                act_done = True
-            else:
-                self.A(dctx, self.HW, self.AHW)
-        else:
-            self.A(dctx, H, self.HW)
-            self.lin(dctx, self.HW, self.AHW)
-        if self.activation and not act_done:
-            ctx.record(n + "0_0_activation", 0)
-            ops.leaky_relu_forward(ctx, self.AHW.local, self.AHW.local)
-            ctx.record(n + "0_1_activation", 0)
-            ctx.register_timer(n + "0_activation", n + "0_0_activation", n + "0_1_activation")
-        if self.res_lin is not None:
-            self.res_lin(dctx, H, self.AHW, False)
-        elif self.residual_layer:
-            ops.axpy(ctx, H.local, self.AHW.local, 1.0)
-        return self.AHW
+        return _wrap_local(layer_body.__call__(self, dctx.ctx, H.local), self.AHW.n() * dctx.P)
 
     def backward(self, dctx: dist_context, G: dist_row_dn_matrix) -> dist_row_dn_matrix:
-        ctx, n = dctx.ctx, self.name
-        T = G
-        if self.activation and not self.grad_premasked:
-            ctx.record(n + "1_0_activation", 0)
-            ops.leaky_relu_backward(ctx, self.AHW.local, G.local, self.AHW.local)
-            ctx.record(n + "1_1_activation", 0)
-            ctx.register_timer(n + "1_activation", n + "1_0_activation", n + "1_1_activation")
-            T = self.AHW
-        if self.HW.m() == self.AHW.m():
-            G_HW = self.G_HW
-            if self.backward_spmm:
-                self.A.backward(dctx, T, G_HW)
-            else:
-                G_HW = T
-            self.lin.backward(dctx, G_HW, self.G_out, mask=self.H if self.mask_input_grad else None)
-            G_out = self.G_out
-        else:
-            self.lin.setX(self.H)
-            self.lin.backward(dctx, T, self.G_HW)
-            G_out = self.G_HW
-            if self.backward_spmm:
-                self.A.backward(dctx, self.G_HW, self.G_out)
-                G_out = self.G_out
-        if self.res_lin is not None:
-            self.res_lin.backward(dctx, G, G_out, False)
-        elif self.residual_layer:
-            ops.axpy(ctx, G.local, G_out.local, 1.0)
-        return G_out
-
-    def linears(self):
-        return [self.lin] + ([self.res_lin] if self.res_lin is not None else [])
-
-    def finish_backward(self, dctx) -> None:
-        for lin in self.linears():
-            lin.finish_backward(dctx)
+        G_out = layer_body.backward(self, dctx.ctx, G.local)
+        return _wrap_local(G_out, G_out.n() * dctx.P)
 
     def adam_update(self, dctx, lr, beta1, beta2, weight_decay, eps):
-        for lin in self.linears():
-            lin.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
-
-    def b(self): return self.lin.get_b()
-    def W(self): return self.lin.get_W()
-    def GW(self): return self.lin.get_G_W()
-    def Gb(self): return self.lin.get_G_b()
+        layer_body.adam_update(self, dctx.ctx, lr, beta1, beta2, weight_decay, eps)
 
 
 class dist_row_softmax_cross_entropy_loss:
@@ -999,6 +873,12 @@ class dist_row_softmax_cross_entropy_loss:
 def _wrap_local(dn, n_global):
     w = dist_row_dn_matrix.__new__(dist_row_dn_matrix)
     w.N_, w.local = n_global, dn
+    return w
+
+
+def _repl_view(dn):
+    w = repl_dn_matrix.__new__(repl_dn_matrix)
+    w.local = dn
     return w
 
 

@@ -96,12 +96,18 @@ class sparse_linear:
 
 
 class linear:
-    """reference src/gcn.hpp:88-189: XW = X.W + 1 b^T; backward G_b, G_W, G_out; Adam."""
+    """reference src/gcn.hpp:88-189: XW = X.W + 1 b^T; backward G_b, G_W, G_out; Adam.
+
+    The body of the row-partitioned form too (dist.dist_row_linear, gcn.hpp:191-296): every operand here is a dn_matrix
+    on ``ctx``'s device -- the rank's shard of X and G, its replica of W and b.  What the distributed form adds lives in
+    the two hooks it overrides: _gradients (where G_W / G_b are stored) and _reduce_gradients (runs after the
+    weight-gradient GEMMs), plus finish_backward."""
 
     def __init__(self, name: str, in_: int, out: int, backward_out: bool = True, fused: bool = False):
         self.name = name
-        self.W, self.G_W = dn_matrix(in_, out), dn_matrix(in_, out)
-        self.b, self.G_b = dn_matrix(1, out), dn_matrix(1, out)
+        self.W = dn_matrix(in_, out)
+        self.G_W, self.G_b = self._gradients(in_, out)
+        self.b = dn_matrix(1, out)
         self.backward_out, self.fused = backward_out, fused
         self.W.init()
         self.b.init(_SQRT_1_3)
@@ -109,6 +115,15 @@ class linear:
         self.ones: Optional[dn_matrix] = None
         self.mW = self.vW = self.mb = self.vb = None
         self.step = 0
+
+    def _gradients(self, in_: int, out: int) -> Tuple[dn_matrix, dn_matrix]:
+        return dn_matrix(in_, out), dn_matrix(1, out)
+
+    def _reduce_gradients(self, ctx: context) -> None:
+        """after the weight-gradient GEMMs: nothing to do on one GPU"""
+
+    def finish_backward(self, ctx) -> None:
+        """from here on the compute stream sees the final G_W / G_b: nothing to wait for on one GPU"""
 
     def setX(self, new_X: dn_matrix) -> None:
         self.X = new_X
@@ -132,7 +147,7 @@ class linear:
         multiplied by leaky_relu'(Z), i.e. it IS the T of that layer's backward (gcn.hpp:462-468)."""
         n = self.name
         if self.ones is None or self.ones.m() != G.n():
-            self.ones = dn_matrix(1, G.n())
+            self.ones = dn_matrix(1, G.n(), device=ctx.device)
             ctx.fill(self.ones, 1.0)        # host-side std::fill in the reference (gcn.hpp:127-128)
         ctx.record(n + "1_0_matmul-gemm", 0)
         if self.fused:                      # G_b rides on the B tiles of the G_W kernel: one pass over G
@@ -142,6 +157,7 @@ class linear:
             ops.matmul(ctx, self.ones, G, self.G_b, 1.0, 0.0)
             ctx.record(n + "1_1_matmul-gemm", 0)
             ops.matmul(ctx, self.X, G, self.G_W, 1.0, 0.0, True)
+        self._reduce_gradients(ctx)
         ctx.record(n + "1_2_matmul-gemm", 0)
         if self.backward_out and mask is not None:
             assert discard
@@ -157,8 +173,9 @@ class linear:
 
     def adam_state(self, ctx: context) -> None:
         if self.mW is None:
-            self.mW, self.vW = dn_matrix(self.W.shape()), dn_matrix(self.W.shape())
-            self.mb, self.vb = dn_matrix(self.b.shape()), dn_matrix(self.b.shape())
+            dev = self.W.t.device
+            self.mW, self.vW = dn_matrix(self.W.shape(), device=dev), dn_matrix(self.W.shape(), device=dev)
+            self.mb, self.vb = dn_matrix(self.b.shape(), device=dev), dn_matrix(self.b.shape(), device=dev)
             for t in (self.mW, self.vW, self.mb, self.vb):
                 t.zero(ctx)
             self.step = 0
@@ -169,6 +186,7 @@ class linear:
 
     def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float,
                     eps: float) -> None:
+        self.finish_backward(ctx)
         self.adam_state(ctx)
         self.step += 1
         bc1 = float(np.float32(1 - beta1 ** self.step))
@@ -195,28 +213,19 @@ class linear:
     def get_G_b(self): return self.G_b
 
 
-class gcn_layer:
-    """reference src/gcn.hpp:411-518.  HW / G_HW alias the model-wide HW_buffer,
-    AHW / G_out alias the layer's AHW_buffer (:433-434)."""
+class layer_body:
+    """Forward and backward of one GCN layer, reference src/gcn.hpp:411-518 (gcn_layer) and :520-637 (dist_gcn_layer),
+    over a context and dn_matrix operands: the layer's rows on this GPU.  HW / G_HW alias the model-wide HW_buffer,
+    AHW / G_out alias the layer's AHW_buffer (:433-434).  ``agg`` is the aggregation operator: agg(ctx, B, C, discard,
+    flags) and agg.backward(ctx, G, G_out) -- sparse_linear for one GPU, dist_sparse_linear bound to its dist_context
+    for the row partition."""
 
-    def __init__(self, name: str, A: csr_matrix, A_T: csr_matrix, in_: int, out: int, activation: bool,
-                 residual_layer: bool = False, backward_spmm: bool = True, HW_buffer=None, fused: bool = False,
-                 agg_dtype: str = "f32", agg_buffer=None):
-        torch = _torch()
-        self.name = name
-        self.A = sparse_linear(name, A, A_T, agg_dtype, agg_buffer)
-        self.lin = linear(name, in_, out, backward_spmm, fused)
+    def __init__(self, name: str, agg, lin: linear, res_lin: Optional[linear], residual_layer: bool, HW: dn_matrix,
+                 AHW: dn_matrix, G_HW: dn_matrix, G_out: dn_matrix, activation: bool, backward_spmm: bool, fused: bool):
+        self.name, self._agg, self.lin, self.res_lin = name, agg, lin, res_lin
         # residual connection (gcn.hpp:418, :430): a second linear when the widths differ, a plain add otherwise
         self.residual_layer = bool(residual_layer)
-        self.res_lin = linear(name, in_, out, backward_spmm, False) if residual_layer and in_ != out else None
-        mn = min(in_, out)
-        if HW_buffer is None:
-            HW_buffer = torch.empty(max(A.m(), A_T.n()) * mn, dtype=torch.float32, device="cuda")
-        self.AHW_buffer = torch.empty(max(A.n() * out, A_T.n() * in_), dtype=torch.float32, device="cuda")
-        self.HW = dn_matrix(A.m(), mn, HW_buffer)
-        self.AHW = dn_matrix(A.n(), out, self.AHW_buffer)
-        self.G_HW = dn_matrix(A_T.n(), mn, HW_buffer)
-        self.G_out = dn_matrix(A_T.n(), in_, self.AHW_buffer)
+        self.HW, self.AHW, self.G_HW, self.G_out = HW, AHW, G_HW, G_out
         self.activation, self.backward_spmm, self.fused = activation, backward_spmm, fused
         self.H: Optional[dn_matrix] = None
         # fused backward (set by the model): mask_input_grad -- my G_out GEMM applies leaky_relu'(H) of the layer
@@ -243,22 +252,22 @@ class gcn_layer:
             # keyed on the feature buffer AND the matrix's generation (csr_matrix bumps _version when it is re-normalised
             # or replaced).  An IN-PLACE update of the feature tensor is not visible here: call
             # set_hoist_first_aggregation(True) again (it drops the cached product) after changing X in place.
-            key = (H.buffer(), H.n(), H.m(), getattr(self.A.A, "_version", 0))
+            key = (H.buffer(), H.n(), H.m(), getattr(self._agg.A, "_version", 0))
             if self._AX is None or self._AX_key != key:
-                self._AX = dn_matrix(self.A.A.n(), H.m())
-                self.A(ctx, H, self._AX)
+                self._AX = dn_matrix(self._agg.A.n(), H.m())
+                self._agg(ctx, H, self._AX)
                 self._AX_key = key
             self.lin(ctx, self._AX, self.AHW)
             self.lin.setX(H)
         elif self.HW.m() == self.AHW.m():         # out <= in: GEMM first (gcn.hpp:439-442)
             self.lin(ctx, H, self.HW)
             if self.fused and self.activation:
-                self.A(ctx, self.HW, self.AHW, True, MGGCN_SPMM_LEAKY_RELU)
+                self._agg(ctx, self.HW, self.AHW, True, MGGCN_SPMM_LEAKY_RELU)
                 act_done = True
             else:
-                self.A(ctx, self.HW, self.AHW)
+                self._agg(ctx, self.HW, self.AHW)
         else:                                      # gcn.hpp:443-446
-            self.A(ctx, H, self.HW)
+            self._agg(ctx, H, self.HW)
             self.lin(ctx, self.HW, self.AHW)
         if self.activation and not act_done:
             ctx.record(n + "0_0_activation", 0)
@@ -283,7 +292,7 @@ class gcn_layer:
         if self.HW.m() == self.AHW.m():
             G_HW = self.G_HW
             if self.backward_spmm:
-                self.A.backward(ctx, T, G_HW)
+                self._agg.backward(ctx, T, G_HW)
             else:
                 G_HW = T
             self.lin.backward(ctx, G_HW, self.G_out, mask=self.H if self.mask_input_grad else None)
@@ -293,7 +302,7 @@ class gcn_layer:
             self.lin.backward(ctx, T, self.G_HW)
             G_out = self.G_HW
             if self.backward_spmm:
-                self.A.backward(ctx, self.G_HW, self.G_out)
+                self._agg.backward(ctx, self.G_HW, self.G_out)
                 G_out = self.G_out
         if self.res_lin is not None:              # gcn.hpp:484-487: the residual branch sees the incoming G
             self.res_lin.backward(ctx, G, G_out, False)
@@ -303,6 +312,10 @@ class gcn_layer:
 
     def linears(self):
         return [self.lin] + ([self.res_lin] if self.res_lin is not None else [])
+
+    def finish_backward(self, ctx) -> None:
+        for lin in self.linears():
+            lin.finish_backward(ctx)
 
     def update(self, ctx, lr, weight_decay):
         for lin in self.linears():
@@ -316,6 +329,26 @@ class gcn_layer:
     def W(self): return self.lin.get_W()
     def GW(self): return self.lin.get_G_W()
     def Gb(self): return self.lin.get_G_b()
+
+
+class gcn_layer(layer_body):
+    """reference src/gcn.hpp:411-518, one GPU."""
+
+    def __init__(self, name: str, A: csr_matrix, A_T: csr_matrix, in_: int, out: int, activation: bool,
+                 residual_layer: bool = False, backward_spmm: bool = True, HW_buffer=None, fused: bool = False,
+                 agg_dtype: str = "f32", agg_buffer=None):
+        torch = _torch()
+        self.A = sparse_linear(name, A, A_T, agg_dtype, agg_buffer)
+        mn = min(in_, out)
+        if HW_buffer is None:
+            HW_buffer = torch.empty(max(A.m(), A_T.n()) * mn, dtype=torch.float32, device="cuda")
+        self.AHW_buffer = torch.empty(max(A.n() * out, A_T.n() * in_), dtype=torch.float32, device="cuda")
+        lin = linear(name, in_, out, backward_spmm, fused)
+        res_lin = linear(name, in_, out, backward_spmm, False) if residual_layer and in_ != out else None
+        layer_body.__init__(self, name, self.A, lin, res_lin, residual_layer,
+                            dn_matrix(A.m(), mn, HW_buffer), dn_matrix(A.n(), out, self.AHW_buffer),
+                            dn_matrix(A_T.n(), mn, HW_buffer), dn_matrix(A_T.n(), in_, self.AHW_buffer),
+                            activation, backward_spmm, fused)
 
 
 class softmax:

@@ -124,7 +124,7 @@ public:
     }
 };
 
-// shared Adam step of linear / dist_row_linear (reference src/gcn.hpp:146-172)
+// Adam step of one GPU's parameters (reference src/gcn.hpp:146-172)
 template <typename r_t>
 void adam_step(context ctx, bool fused, dn_matrix<r_t> W, dn_matrix<r_t> G_W, dn_matrix<r_t> mW, dn_matrix<r_t> vW, dn_matrix<r_t> b,
                dn_matrix<r_t> G_b, dn_matrix<r_t> mb, dn_matrix<r_t> vb, r_t lr, r_t beta1, r_t beta2, r_t wd, r_t eps, std::size_t step) {
@@ -143,25 +143,63 @@ void adam_step(context ctx, bool fused, dn_matrix<r_t> W, dn_matrix<r_t> G_W, dn
     adam_final(ctx, W, mW, vW, lr, bc1, bc2, eps);
     adam_final(ctx, b, mb, vb, lr, bc1, bc2, eps);
 }
+template <typename r_t>
+void adam_step(dist_context ctx, bool fused, repl_dn_matrix<r_t> W, repl_dn_matrix<r_t> G_W, repl_dn_matrix<r_t> mW, repl_dn_matrix<r_t> vW,
+               repl_dn_matrix<r_t> b, repl_dn_matrix<r_t> G_b, repl_dn_matrix<r_t> mb, repl_dn_matrix<r_t> vb, r_t lr, r_t beta1, r_t beta2,
+               r_t wd, r_t eps, std::size_t step) {
+    for (std::size_t i = 0; i < ctx.size(); i++)
+        ctx.on(i, [c = ctx[i], fused, w = W[i], gw = G_W[i], mw = mW[i], vw = vW[i], bb = b[i], gb = G_b[i], m_b = mb[i], v_b = vb[i],
+                   lr, beta1, beta2, wd, eps, step] { adam_step(c, fused, w, gw, mw, vw, bb, gb, m_b, v_b, lr, beta1, beta2, wd, eps, step); });
+}
+
+// the row of ones of the reference's G_b GEMM (host-filled, :127-128), as long as one GPU's rows of G
+template <typename r_t>
+void ones_row(const context &, dn_matrix<r_t> &ones, const dn_matrix<r_t> &G) {
+    if (ones.n() != 1 || ones.m() != G.n()) { ones = dn_matrix<r_t>(1, G.n()); ones.fill(1); }
+}
+template <typename r_t>
+void ones_row(const dist_context &ctx, repl_dn_matrix<r_t> &ones, const dist_row_dn_matrix<r_t> &G) {
+    const std::size_t rows = G.n() / ctx.size();
+    if (ones.size() != ctx.size() || ones.m() != rows) { ctx.drain(); ones = repl_dn_matrix<r_t>(ctx, 1, rows); ones.fill(ctx, 1); }
+}
 
 template <typename r_t>
-class linear {
-    using dn_t = dn_matrix<r_t>;
+dn_matrix<r_t> zeros_like(const context &ctx, const dn_matrix<r_t> &A) {
+    dn_matrix<r_t> z(A.shape());
+    z.zero(ctx);
+    return z;
+}
+template <typename r_t>
+repl_dn_matrix<r_t> zeros_like(const dist_context &ctx, const repl_dn_matrix<r_t> &A) {
+    repl_dn_matrix<r_t> z(ctx, A.shape());
+    z.zero(ctx);
+    return z;
+}
+
+// One linear layer (reference :88-189 / :191-296), written once over the context and matrix types: one GPU
+// (context; rows and parameters dn_matrix) or the row partition (dist_context; rows dist_row_dn_matrix, parameters
+// repl_dn_matrix), whose per-GPU loops come from the dist_context overloads.  What the row partition adds lives in the two
+// hooks it overrides: reduce_gradients (after the weight-gradient GEMMs) and finish_backward.
+template <typename r_t, typename ctx_t, template <typename> class dn_t, template <typename> class rdn_t>
+class linear_body {
+protected:
     std::string name;
-    dn_t W, G_W, mW, vW, b, G_b, mb, vb, X, ones;
-    bool backward_out, fused;
+    rdn_t<r_t> W, G_W, mW, vW, b, G_b, mb, vb, ones;
+    dn_t<r_t> X;
+    bool backward_out, fused, has_moments = false;
     std::size_t step = 0;
 
+    linear_body(std::string name, rdn_t<r_t> W, rdn_t<r_t> G_W, rdn_t<r_t> b, rdn_t<r_t> G_b, bool backward_out, bool fused)
+        : name(name), W(W), G_W(G_W), b(b), G_b(G_b), backward_out(backward_out), fused(fused) {}
+    virtual void reduce_gradients(const ctx_t &) {}
+
 public:
-    linear(std::string name, std::size_t in, std::size_t out, bool backward_out = true, bool fused = false)
-        : name(name), W(in, out), G_W(in, out), b(1, out), G_b(1, out), backward_out(backward_out), fused(fused) {
-        W.init();
-        b.init(std::sqrt((r_t)1.0 / 3));
-    }
+    // the compute stream sees the final gradients from here on
+    virtual void finish_backward(const ctx_t &) {}
 
-    void setX(dn_t new_X) { X = new_X; }
+    void setX(dn_t<r_t> new_X) { X = new_X; }
 
-    void operator()(context ctx, dn_t X, dn_t XW, bool discard = true) {
+    void operator()(ctx_t ctx, dn_t<r_t> X, dn_t<r_t> XW, bool discard = true) {
         if (fused && discard) {                      // bias in the GEMM epilogue
             ctx.record(name + "0_0_matmul-gemm", 0);
             linear_forward(ctx, X, W, b, XW);
@@ -177,17 +215,11 @@ public:
 
     // mask (fused path): the activated output Z of the layer below; G_out leaves the GEMM already multiplied by
     // leaky_relu'(Z), i.e. it IS that layer's T (reference :462-468)
-    void backward(context ctx, dn_t G, dn_t G_out, bool discard = true, const dn_t *mask = nullptr) {
-        if (ones.n() != 1 || ones.m() != G.n()) { ones = dn_t(1, G.n()); ones.fill(1); }
+    void backward(ctx_t ctx, dn_t<r_t> G, dn_t<r_t> G_out, bool discard = true, const dn_t<r_t> *mask = nullptr) {
+        if (!fused) ones_row(ctx, ones, G);
         ctx.record(name + "1_0_matmul-gemm", 0);
-        if (fused) {                                  // G_b rides on the B tiles of the G_W kernel: one pass over G
-            ctx.record(name + "1_1_matmul-gemm", 0);
-            linear_backward_weights(ctx, X, G, G_W, G_b);
-        } else {
-            matmul(ctx, ones, G, G_b, (r_t)1, (r_t)0);
-            ctx.record(name + "1_1_matmul-gemm", 0);
-            matmul(ctx, X, G, G_W, (r_t)1, (r_t)0, true);
-        }
+        linear_weight_gradients(ctx, fused, ones, X, G, G_W, G_b);
+        reduce_gradients(ctx);
         ctx.record(name + "1_2_matmul-gemm", 0);
         if (backward_out && mask) matmul_lrelu_backward(ctx, G, W, *mask, G_out, (r_t)1, false, true);
         else if (backward_out) matmul(ctx, G, W, G_out, (r_t)1, discard ? (r_t)0 : (r_t)1, false, true);
@@ -195,7 +227,7 @@ public:
         ctx.register_timer(name + "1_matmul-gemm", name + "1_0_matmul-gemm", name + "1_3_matmul-gemm");
     }
 
-    void update(const context ctx, const r_t lr, const r_t weight_decay) {
+    void update(const ctx_t ctx, const r_t lr, const r_t weight_decay) {
         axpby(ctx, G_W, W, -lr, 1 - weight_decay);
         axpy(ctx, G_b, b, -lr);
     }
@@ -203,20 +235,16 @@ public:
     bool has_backward_out() const { return backward_out; }
 
     // Adam moments, zeroed on first use; bump_step() for the model-wide single launch (gcn::adam_update)
-    void adam_state(context ctx) {
-        if (mW.shape() != W.shape()) {
-            mW = dn_t(W.shape()); vW = dn_t(W.shape()); mb = dn_t(b.shape()); vb = dn_t(b.shape());
-            mW.zero(ctx); vW.zero(ctx); mb.zero(ctx); vb.zero(ctx);
-            step = 0;
-        }
+    void adam_state(ctx_t ctx) {
+        if (has_moments) return;
+        mW = zeros_like(ctx, W); vW = zeros_like(ctx, W); mb = zeros_like(ctx, b); vb = zeros_like(ctx, b);
+        has_moments = true;
+        step = 0;
     }
     std::size_t bump_step() { return ++step; }
-    void adam_tensors(std::vector<std::array<dn_t, 4>> &out, std::vector<r_t> &wd, r_t weight_decay) const {
-        out.push_back({W, G_W, mW, vW}); wd.push_back(weight_decay);       // W decays, b does not (reference :163)
-        out.push_back({b, G_b, mb, vb}); wd.push_back((r_t)0);
-    }
 
-    void adam_update(context ctx, const r_t lr, const r_t beta1, const r_t beta2, const r_t weight_decay, const r_t eps) {
+    void adam_update(ctx_t ctx, const r_t lr, const r_t beta1, const r_t beta2, const r_t weight_decay, const r_t eps) {
+        finish_backward(ctx);
         adam_state(ctx);
         step += 1;
         ctx.record(name + "0_adam-update", 0);
@@ -232,19 +260,31 @@ public:
 };
 
 template <typename r_t>
-class dist_row_linear {
-    using dn_t = dist_row_dn_matrix<r_t>;
+class linear : public linear_body<r_t, context, dn_matrix, dn_matrix> {
+    using body = linear_body<r_t, context, dn_matrix, dn_matrix>;
+
+public:
+    linear(std::string name, std::size_t in, std::size_t out, bool backward_out = true, bool fused = false)
+        : body(name, dn_matrix<r_t>(in, out), dn_matrix<r_t>(in, out), dn_matrix<r_t>(1, out), dn_matrix<r_t>(1, out), backward_out, fused) {
+        this->W.init();
+        this->b.init(std::sqrt((r_t)1.0 / 3));
+    }
+
+    void adam_tensors(std::vector<std::array<dn_matrix<r_t>, 4>> &out, std::vector<r_t> &wd, r_t weight_decay) const {
+        out.push_back({this->W, this->G_W, this->mW, this->vW}); wd.push_back(weight_decay);    // W decays, b does not (reference :163)
+        out.push_back({this->b, this->G_b, this->mb, this->vb}); wd.push_back((r_t)0);
+    }
+};
+
+template <typename r_t>
+class dist_row_linear : public linear_body<r_t, dist_context, dist_row_dn_matrix, repl_dn_matrix> {
+    using body = linear_body<r_t, dist_context, dist_row_dn_matrix, repl_dn_matrix>;
     using rdn_t = repl_dn_matrix<r_t>;
-    std::string name;
     // G_W and G_b of a layer live in ONE buffer per GPU: [G_W | pad to 4 floats | G_b] -> a single in-place
     // all-reduce per layer (the reference all-reduces them separately, :236-240), run on the comm stream
     // while the backward pass goes on; awaited by finish_backward() / adam_update()
-    std::vector<mggcn::device_ptr<r_t>> G_flat;
-    std::size_t off_b = 0, flat_len = 0;
-    rdn_t W, G_W, mW, vW, b, G_b, mb, vb, ones, G_all;
-    dn_t X;
-    bool backward_out, fused, pending = false;
-    std::size_t step = 0;
+    rdn_t G_all;
+    bool pending = false;
 
     static std::vector<mggcn::device_ptr<r_t>> alloc_flat(const dist_context &ctx, std::size_t len) {
         std::vector<mggcn::device_ptr<r_t>> t;
@@ -261,182 +301,97 @@ class dist_row_linear {
         return t;
     }
 
+    void reduce_gradients(const dist_context &ctx) override {
+        const int cs = ctx.bcast_stream_id();
+        ctx.record(this->name + "1_1_grad-local", 0);
+        ctx.wait(this->name + "1_1_grad-local", cs);
+        G_all.allreduce(ctx, cs);                                             // [G_W | G_b] summed over the GPUs
+        ctx.record(this->name + "1_2_grad-reduced", cs);
+        pending = true;
+    }
+
 public:
     dist_row_linear(const dist_context ctx, std::string name, std::size_t in, std::size_t out, bool backward_out = true, bool fused = false)
-        : name(name), off_b((in * out + 3) / 4 * 4), flat_len(off_b + out), W(ctx, in, out), b(ctx, 1, out),
-          backward_out(backward_out), fused(fused) {
-        G_flat = alloc_flat(ctx, flat_len);
-        G_W = rdn_t(ctx, in, out, G_flat);
-        G_b = rdn_t(ctx, 1, out, views(G_flat, off_b));
-        G_all = rdn_t(ctx, 1, flat_len, G_flat);
-        W.init(ctx);
-        b.init(ctx, std::sqrt((r_t)1.0 / 3));
+        : body(name, rdn_t(ctx, in, out), rdn_t(), rdn_t(ctx, 1, out), rdn_t(), backward_out, fused) {
+        const std::size_t off_b = (in * out + 3) / 4 * 4;
+        const auto G_flat = alloc_flat(ctx, off_b + out);
+        this->G_W = rdn_t(ctx, in, out, G_flat);
+        this->G_b = rdn_t(ctx, 1, out, views(G_flat, off_b));
+        G_all = rdn_t(ctx, 1, off_b + out, G_flat);
+        this->W.init(ctx);
+        this->b.init(ctx, std::sqrt((r_t)1.0 / 3));
     }
 
-    void setX(dn_t new_X) { X = new_X; }
-
-    void operator()(dist_context ctx, dn_t X, dn_t XW, bool discard = true) {
-        if (fused && discard) {
-            ctx.record(name + "0_0_matmul-gemm", 0);
-            linear_forward(ctx, X, W, b, XW);
-        } else {
-            broadcast_rows(ctx, b, XW, discard);
-            ctx.record(name + "0_0_matmul-gemm", 0);
-            matmul(ctx, X, W, XW, (r_t)1, (r_t)1);
-        }
-        ctx.record(name + "0_1_matmul-gemm", 0);
-        ctx.register_timer(name + "0_matmul-gemm", name + "0_0_matmul-gemm", name + "0_1_matmul-gemm");
-        this->X = X;
-    }
-
-    void backward(dist_context ctx, dn_t G, dn_t G_out, bool discard = true, const dn_t *mask = nullptr) {
-        if (!fused && (ones.size() != ctx.size() || ones.m() != G.n() / ctx.size())) { ctx.drain(); ones = rdn_t(ctx, 1, G.n() / ctx.size()); ones.fill(ctx, 1); }
-        const int cs = ctx.bcast_stream_id();
-        ctx.record(name + "1_0_matmul-gemm", 0);
-        for (std::size_t i = 0; i < ctx.size(); i++) {
-            if (fused) {
-                ctx.on(i, [c = ctx[i], x = X[i], g = G[i], gw = G_W[i], gb = G_b[i]] { linear_backward_weights(c, x, g, gw, gb); });
-                continue;
-            }
-            ctx.on(i, [c = ctx[i], o = ones[i], x = X[i], g = G[i], gw = G_W[i], gb = G_b[i]] {
-                matmul(c, o, g, gb, (r_t)1, (r_t)0);                          // G_b = 1^T G      (local part)
-                matmul(c, x, g, gw, (r_t)1, (r_t)0, true);                    // G_W = X^T G      (local part)
-            });
-        }
-        ctx.record(name + "1_1_grad-local", 0);
-        ctx.wait(name + "1_1_grad-local", cs);
-        G_all.allreduce(ctx, cs);                                             // [G_W | G_b] summed over the GPUs
-        ctx.record(name + "1_2_grad-reduced", cs);
-        pending = true;
-        ctx.record(name + "1_2_matmul-gemm", 0);
-        if (backward_out && mask)
-            for (std::size_t i = 0; i < ctx.size(); i++)
-                ctx.on(i, [c = ctx[i], g = G[i], w = W[i], z = (*mask)[i], go = G_out[i]] { matmul_lrelu_backward(c, g, w, z, go, (r_t)1, false, true); });
-        else if (backward_out) matmul(ctx, G, W, G_out, (r_t)1, discard ? (r_t)0 : (r_t)1, true);
-        ctx.record(name + "1_3_matmul-gemm", 0);
-        ctx.register_timer(name + "1_matmul-gemm", name + "1_0_matmul-gemm", name + "1_3_matmul-gemm");
-    }
-
-    // the compute stream sees the summed gradients from here on
-    void finish_backward(const dist_context ctx) {
-        if (pending) ctx.wait(name + "1_2_grad-reduced", 0);
+    void finish_backward(const dist_context &ctx) override {
+        if (pending) ctx.wait(this->name + "1_2_grad-reduced", 0);
         pending = false;
     }
 
-    bool has_backward_out() const { return backward_out; }
-
-    void adam_state(dist_context ctx) {
-        if (mW.size() != W.size()) {
-            mW = rdn_t(ctx, W.shape()); vW = rdn_t(ctx, W.shape()); mb = rdn_t(ctx, b.shape()); vb = rdn_t(ctx, b.shape());
-            mW.zero(ctx); vW.zero(ctx); mb.zero(ctx); vb.zero(ctx);
-            step = 0;
-        }
-    }
-    std::size_t bump_step() { return ++step; }
     void adam_tensors(std::size_t gpu, std::vector<std::array<dn_matrix<r_t>, 4>> &out, std::vector<r_t> &wd, r_t weight_decay) const {
-        out.push_back({W[gpu], G_W[gpu], mW[gpu], vW[gpu]}); wd.push_back(weight_decay);
-        out.push_back({b[gpu], G_b[gpu], mb[gpu], vb[gpu]}); wd.push_back((r_t)0);
+        out.push_back({this->W[gpu], this->G_W[gpu], this->mW[gpu], this->vW[gpu]}); wd.push_back(weight_decay);
+        out.push_back({this->b[gpu], this->G_b[gpu], this->mb[gpu], this->vb[gpu]}); wd.push_back((r_t)0);
     }
-
-    void adam_update(dist_context ctx, const r_t lr, const r_t beta1, const r_t beta2, const r_t weight_decay, const r_t eps) {
-        finish_backward(ctx);
-        adam_state(ctx);
-        step += 1;
-        ctx.record(name + "0_adam-update", 0);
-        for (std::size_t i = 0; i < ctx.size(); i++)
-            ctx.on(i, [c = ctx[i], f = fused, w = W[i], gw = G_W[i], mw = mW[i], vw = vW[i], bb = b[i], gb = G_b[i], m_b = mb[i], v_b = vb[i],
-                       lr, beta1, beta2, weight_decay, eps, st = step] {
-                adam_step(c, f, w, gw, mw, vw, bb, gb, m_b, v_b, lr, beta1, beta2, weight_decay, eps, st);
-            });
-        ctx.record(name + "1_adam-update", 0);
-        ctx.register_timer(name + "adam-update", name + "0_adam-update", name + "1_adam-update");
-    }
-
-    auto get_b() { return b; }
-    auto get_W() { return W; }
-    auto get_G_W() { return G_W; }
-    auto get_G_b() { return G_b; }
 };
 
-template <typename x_t, typename v_t, typename r_t>
-class gcn_layer {
+// One GCN layer (reference :411-518 / :520-637), written once over the context, matrix, aggregation (sparse_linear /
+// dist_sparse_linear) and linear types.  HW / G_HW alias the model-wide HW_buffer, AHW / G_out the layer's AHW_buffer
+// (:433-434); the thin classes below allocate them.
+template <typename r_t, typename ctx_t, typename dn_t, typename agg_t, typename linear_t>
+class gcn_layer_body {
+protected:
     std::string name;
-    sparse_linear<x_t, v_t, r_t> A;
-    linear<r_t> lin;
-    std::optional<linear<r_t>> res_lin;   // residual connection when in != out (reference :418, :430)
+    agg_t A;
+    linear_t lin;
+    std::optional<linear_t> res_lin;      // residual connection when in != out (reference :418, :430)
     bool residual_layer;
-    dn_matrix<r_t> HW;                    // HW_buffer
-    mggcn::device_ptr<r_t> AHW_buffer;
-    dn_matrix<r_t> AHW, G_HW, G_out;      // AHW_buffer / HW_buffer / AHW_buffer
+    dn_t HW, AHW, G_HW, G_out;            // HW_buffer / AHW_buffer / HW_buffer / AHW_buffer
     bool activation, backward_spmm, fused;
-    dn_matrix<r_t> H;
+    dn_t H;
     // fused backward (set by the model): mask_input_grad -- my G_out GEMM applies leaky_relu'(H) of the layer
     // below; grad_premasked -- the G I receive already carries my own activation's mask
     bool mask_input_grad = false, grad_premasked = false;
-    // optional, first layer only (gcn::set_hoist_first_aggregation): A_fwd . X computed once and kept
-    bool hoist_input = false;
-    dn_matrix<r_t> AX;
-    const r_t *AX_src = nullptr;
-    unsigned AX_generation = 0;
+
+    gcn_layer_body(std::string name, agg_t A, linear_t lin, std::optional<linear_t> res_lin, bool residual_layer, bool activation,
+                   bool backward_spmm, bool fused)
+        : name(name), A(A), lin(lin), res_lin(res_lin), residual_layer(residual_layer), activation(activation),
+          backward_spmm(backward_spmm), fused(fused) {}
+
+    // AHW = A (H W + 1 b^T) in the reference's order (:439-446); true when the SpMM's epilogue applied the activation
+    virtual bool aggregate_linear(ctx_t ctx, dn_t H) {
+        if (gemm_first()) {                      // out <= in: GEMM first
+            lin(ctx, H, HW);
+            if (fused && activation) { A(ctx, HW, AHW, true, MGGCN_SPMM_LEAKY_RELU); return true; }
+            A(ctx, HW, AHW);
+            return false;
+        }
+        A(ctx, H, HW);
+        lin(ctx, HW, AHW);
+        return false;
+    }
+
+    // reference :484-487: the residual branch sees the incoming (unmasked) gradient and adds to G_out
+    dn_t residual_backward(ctx_t ctx, dn_t G, dn_t out) {
+        if (res_lin) res_lin->backward(ctx, G, out, false);
+        else if (residual_layer) axpy(ctx, G, out, (r_t)1);
+        return out;
+    }
 
 public:
-    // A_fwd (1 b^T) = 1 b^T needs every row of A_fwd to sum to one: a vertex whose row of A_fwd is empty (no self-loop, nobody
-    // points at it) would get 0 instead of b -- such a graph keeps the plain path.  (Re-)enabling drops the cached product:
-    // the way to pick up an in-place change of the feature matrix, which the (buffer, shape, matrix generation) key cannot see.
-    void set_hoist_input(bool on) {
-        hoist_input = on && gemm_first() && !residual_layer && A.forward_matrix().every_row_nonempty();
-        AX = dn_matrix<r_t>();
-        AX_src = nullptr;
-    }
-    bool hoists_input() const { return hoist_input; }
     bool gemm_first() const { return HW.m() == AHW.m(); }           // out <= in (reference :439)
     bool has_activation() const { return activation; }
+    bool has_residual() const { return residual_layer; }
     bool propagates() const { return lin.has_backward_out(); }
     void set_fused_backward(bool mask_input, bool premasked) { if (mask_input) mask_input_grad = true; if (premasked) grad_premasked = true; }
-    linear<r_t> &linear_layer() { return lin; }
-
-    gcn_layer(std::string name, csr_matrix<x_t, v_t, r_t> A, csr_matrix<x_t, v_t, r_t> A_T, std::size_t in, std::size_t out,
-              bool activation, bool residual_layer = false, bool backward_spmm = true,
-              mggcn::device_ptr<r_t> HW_buffer = nullptr, bool fused = false, agg_dtype agg = agg_dtype::f32,
-              mggcn::device_ptr<std::uint16_t> agg_buffer = nullptr, std::size_t agg_capacity = 0)
-        : name(name), A(name, A, A_T, agg, agg_buffer, agg_capacity), lin(name, in, out, backward_spmm, fused),
-          res_lin(in == out || !residual_layer ? std::nullopt : std::make_optional(linear<r_t>(name, in, out, backward_spmm, false))),
-          residual_layer(residual_layer),
-          HW(A.m(), std::min(in, out), HW_buffer ? HW_buffer : mggcn::device_malloc<r_t>(std::max<std::size_t>(A.m(), A_T.n()) * std::min(in, out))),
-          AHW_buffer(mggcn::device_malloc<r_t>(std::max((std::size_t)A.n() * out, (std::size_t)A_T.n() * in))),
-          AHW(A.n(), out, AHW_buffer), G_HW(A_T.n(), std::min(in, out), HW.shared_buffer()), G_out(A_T.n(), in, AHW_buffer),
-          activation(activation), backward_spmm(backward_spmm), fused(fused) {}
-
-    bool has_residual() const { return residual_layer; }
-    std::vector<linear<r_t> *> linears() {
-        std::vector<linear<r_t> *> v{&lin};
+    linear_t &linear_layer() { return lin; }
+    std::vector<linear_t *> linears() {
+        std::vector<linear_t *> v{&lin};
         if (res_lin) v.push_back(&*res_lin);
         return v;
     }
 
-    auto operator()(context ctx, dn_matrix<r_t> H) {
+    auto operator()(ctx_t ctx, dn_t H) {
         this->H = H;
-        bool act_done = false;
-        if (hoist_input && HW.m() == AHW.m()) {
-            // layer 0's aggregation is loop-invariant: A_fwd (X W + 1 b^T) = (A_fwd X) W + 1 b^T (A_fwd is row-stochastic,
-            // X never changes between epochs): A_fwd X once, one SpMM fewer per epoch.  NOT the reference's epoch
-            // (:437-446): an option, off by default.  The backward pass stays the reference's (G_W = X^T T, :954).
-            if (!AX.buffer() || AX_src != H.buffer() || AX.n() != AHW.n() || AX.m() != H.m() || AX_generation != A.forward_matrix().generation()) {
-                AX = dn_matrix<r_t>(AHW.n(), H.m());
-                A(ctx, H, AX);
-                AX_src = H.buffer();
-                AX_generation = A.forward_matrix().generation();
-            }
-            lin(ctx, AX, AHW);
-            lin.setX(H);
-        } else if (HW.m() == AHW.m()) {          // out <= in: GEMM first (reference :439-442)
-            lin(ctx, H, HW);
-            if (fused && activation) { A(ctx, HW, AHW, true, MGGCN_SPMM_LEAKY_RELU); act_done = true; }
-            else A(ctx, HW, AHW);
-        } else {                                  // reference :443-446
-            A(ctx, H, HW);
-            lin(ctx, HW, AHW);
-        }
+        const bool act_done = aggregate_linear(ctx, H);
         if (activation && !act_done) {
             ctx.record(name + "0_0_activation", 0);
             leaky_relu_forward(ctx, AHW, AHW);
@@ -448,7 +403,7 @@ public:
         return AHW;
     }
 
-    auto backward(context ctx, dn_matrix<r_t> G) {
+    auto backward(ctx_t ctx, dn_t G) {
         auto T = G;
         if (activation && !grad_premasked) {
             ctx.record(name + "1_0_activation", 0);
@@ -457,7 +412,7 @@ public:
             ctx.register_timer(name + "1_activation", name + "1_0_activation", name + "1_1_activation");
             T = AHW;
         }
-        if (HW.m() == AHW.m()) {
+        if (gemm_first()) {
             auto g = G_HW;
             if (backward_spmm) A.backward(ctx, T, g); else g = T;
             lin.backward(ctx, g, G_out, true, mask_input_grad ? &H : nullptr);
@@ -469,15 +424,9 @@ public:
         return residual_backward(ctx, G, G_HW);
     }
 
-    // reference :484-487: the residual branch sees the incoming (unmasked) gradient and adds to G_out
-    dn_matrix<r_t> residual_backward(context ctx, dn_matrix<r_t> G, dn_matrix<r_t> out) {
-        if (res_lin) res_lin->backward(ctx, G, out, false);
-        else if (residual_layer) axpy(ctx, G, out, (r_t)1);
-        return out;
-    }
-
-    void update(const context ctx, const r_t lr, const r_t wd) { for (auto *l : linears()) l->update(ctx, lr, wd); }
-    void adam_update(const context ctx, const r_t lr, const r_t b1, const r_t b2, const r_t wd, const r_t eps) {
+    void finish_backward(const ctx_t ctx) { for (auto *l : linears()) l->finish_backward(ctx); }
+    void update(const ctx_t ctx, const r_t lr, const r_t wd) { for (auto *l : linears()) l->update(ctx, lr, wd); }
+    void adam_update(const ctx_t ctx, const r_t lr, const r_t b1, const r_t b2, const r_t wd, const r_t eps) {
         for (auto *l : linears()) l->adam_update(ctx, lr, b1, b2, wd, eps);
     }
     auto b() { return lin.get_b(); }
@@ -486,111 +435,88 @@ public:
     auto Gb() { return lin.get_G_b(); }
 };
 
+template <typename x_t, typename v_t, typename r_t>
+class gcn_layer : public gcn_layer_body<r_t, context, dn_matrix<r_t>, sparse_linear<x_t, v_t, r_t>, linear<r_t>> {
+    using body = gcn_layer_body<r_t, context, dn_matrix<r_t>, sparse_linear<x_t, v_t, r_t>, linear<r_t>>;
+    // optional, first layer only (gcn::set_hoist_first_aggregation): A_fwd . X computed once and kept
+    bool hoist_input = false;
+    dn_matrix<r_t> AX;
+    const r_t *AX_src = nullptr;
+    unsigned AX_generation = 0;
+
+    bool aggregate_linear(context ctx, dn_matrix<r_t> H) override {
+        if (!hoist_input) return body::aggregate_linear(ctx, H);
+        // layer 0's aggregation is loop-invariant: A_fwd (X W + 1 b^T) = (A_fwd X) W + 1 b^T (A_fwd is row-stochastic,
+        // X never changes between epochs): A_fwd X once, one SpMM fewer per epoch.  NOT the reference's epoch
+        // (:437-446): an option, off by default.  The backward pass stays the reference's (G_W = X^T T, :954).
+        auto &A = this->A;
+        if (!AX.buffer() || AX_src != H.buffer() || AX.n() != this->AHW.n() || AX.m() != H.m() ||
+            AX_generation != A.forward_matrix().generation()) {
+            AX = dn_matrix<r_t>(this->AHW.n(), H.m());
+            A(ctx, H, AX);
+            AX_src = H.buffer();
+            AX_generation = A.forward_matrix().generation();
+        }
+        this->lin(ctx, AX, this->AHW);
+        this->lin.setX(H);
+        return false;
+    }
+
+public:
+    // A_fwd (1 b^T) = 1 b^T needs every row of A_fwd to sum to one: a vertex whose row of A_fwd is empty (no self-loop, nobody
+    // points at it) would get 0 instead of b -- such a graph keeps the plain path.  (Re-)enabling drops the cached product:
+    // the way to pick up an in-place change of the feature matrix, which the (buffer, shape, matrix generation) key cannot see.
+    void set_hoist_input(bool on) {
+        hoist_input = on && this->gemm_first() && !this->residual_layer && this->A.forward_matrix().every_row_nonempty();
+        AX = dn_matrix<r_t>();
+        AX_src = nullptr;
+    }
+    bool hoists_input() const { return hoist_input; }
+
+    gcn_layer(std::string name, csr_matrix<x_t, v_t, r_t> A, csr_matrix<x_t, v_t, r_t> A_T, std::size_t in, std::size_t out,
+              bool activation, bool residual_layer = false, bool backward_spmm = true,
+              mggcn::device_ptr<r_t> HW_buffer = nullptr, bool fused = false, agg_dtype agg = agg_dtype::f32,
+              mggcn::device_ptr<std::uint16_t> agg_buffer = nullptr, std::size_t agg_capacity = 0)
+        : body(name, sparse_linear<x_t, v_t, r_t>(name, A, A_T, agg, agg_buffer, agg_capacity), linear<r_t>(name, in, out, backward_spmm, fused),
+               in == out || !residual_layer ? std::nullopt : std::make_optional(linear<r_t>(name, in, out, backward_spmm, false)),
+               residual_layer, activation, backward_spmm, fused) {
+        const std::size_t mn = std::min(in, out);
+        if (!HW_buffer) HW_buffer = mggcn::device_malloc<r_t>(std::max<std::size_t>(A.m(), A_T.n()) * mn);
+        const auto AHW_buffer = mggcn::device_malloc<r_t>(std::max((std::size_t)A.n() * out, (std::size_t)A_T.n() * in));
+        this->HW = dn_matrix<r_t>(A.m(), mn, HW_buffer);
+        this->AHW = dn_matrix<r_t>(A.n(), out, AHW_buffer);
+        this->G_HW = dn_matrix<r_t>(A_T.n(), mn, HW_buffer);
+        this->G_out = dn_matrix<r_t>(A_T.n(), in, AHW_buffer);
+    }
+};
+
 template <bool row_partition, typename x_t, typename v_t, typename r_t>
-class dist_gcn_layer {
+class dist_gcn_layer : public gcn_layer_body<r_t, dist_context, dist_row_dn_matrix<r_t>, dist_sparse_linear<row_partition, x_t, v_t, r_t>,
+                                             dist_row_linear<r_t>> {
+    using body = gcn_layer_body<r_t, dist_context, dist_row_dn_matrix<r_t>, dist_sparse_linear<row_partition, x_t, v_t, r_t>,
+                                dist_row_linear<r_t>>;
     using csr_t = dist_row_csr_matrix<x_t, v_t, r_t>;
     using dn_t = dist_row_dn_matrix<r_t>;
     using bufs_t = std::vector<mggcn::device_ptr<r_t>>;
-    std::string name;
-    dist_sparse_linear<row_partition, x_t, v_t, r_t> A;
-    dist_row_linear<r_t> lin;
-    std::optional<dist_row_linear<r_t>> res_lin;      // reference :527
-    bool residual_layer;
-    bufs_t AHW_buffer;
-    dn_t HW, AHW, G_HW, G_out;
-    bool activation, backward_spmm, fused;
-    dn_t H;
-    bool mask_input_grad = false, grad_premasked = false;     // see gcn_layer
-
-    static bufs_t alloc(const dist_context &ctx, std::size_t per_gpu) {
-        bufs_t t;
-        for (std::size_t i = 0; i < ctx.size(); i++) { ctx[i].set(); t.push_back(mggcn::device_malloc<r_t>(per_gpu)); }
-        return t;
-    }
 
 public:
     dist_gcn_layer(const dist_context ctx, std::string name, csr_t A, csr_t A_T, std::size_t in, std::size_t out, bool activation,
                    bool residual_layer = false, bool backward_spmm = true, bufs_t HW_buffer = {}, bufs_t bcast_buffer = {},
                    bufs_t bcast_buffer2 = {}, bool fused = false, dist_mode mode = dist_mode::allgather)
-        : name(name), A(name, A, A_T, bcast_buffer, bcast_buffer2, mode), lin(ctx, name, in, out, backward_spmm, fused),
-          res_lin(in == out || !residual_layer ? std::nullopt : std::make_optional(dist_row_linear<r_t>(ctx, name, in, out, backward_spmm, false))),
-          residual_layer(residual_layer),
-          AHW_buffer(alloc(ctx, std::max(A.n() * out, A_T.n() * in) / ctx.size())), HW(ctx, A.m(), std::min(in, out), HW_buffer),
-          AHW(ctx, A.n(), out, AHW_buffer), G_HW(ctx, A_T.n(), std::min(in, out), HW_buffer), G_out(ctx, A_T.n(), in, AHW_buffer),
-          activation(activation), backward_spmm(backward_spmm), fused(fused) {}
-
-    bool has_residual() const { return residual_layer; }
-    std::vector<dist_row_linear<r_t> *> linears() {
-        std::vector<dist_row_linear<r_t> *> v{&lin};
-        if (res_lin) v.push_back(&*res_lin);
-        return v;
-    }
-
-    auto operator()(dist_context ctx, dn_t H) {
-        this->H = H;
-        bool act_done = false;
-        if (HW.m() == AHW.m()) {
-            lin(ctx, H, HW);
-            if (fused && activation) { A(ctx, HW, AHW, true, MGGCN_SPMM_LEAKY_RELU); act_done = true; }
-            else A(ctx, HW, AHW);
-        } else {
-            A(ctx, H, HW);
-            lin(ctx, HW, AHW);
+        : body(name, dist_sparse_linear<row_partition, x_t, v_t, r_t>(name, A, A_T, bcast_buffer, bcast_buffer2, mode),
+               dist_row_linear<r_t>(ctx, name, in, out, backward_spmm, fused),
+               in == out || !residual_layer ? std::nullopt : std::make_optional(dist_row_linear<r_t>(ctx, name, in, out, backward_spmm, false)),
+               residual_layer, activation, backward_spmm, fused) {
+        bufs_t AHW_buffer;                        // per GPU: its rows only
+        for (std::size_t i = 0; i < ctx.size(); i++) {
+            ctx[i].set();
+            AHW_buffer.push_back(mggcn::device_malloc<r_t>(std::max(A.n() * out, A_T.n() * in) / ctx.size()));
         }
-        if (activation && !act_done) {
-            ctx.record(name + "0_0_activation", 0);
-            leaky_relu_forward(ctx, AHW, AHW);
-            ctx.record(name + "0_1_activation", 0);
-            ctx.register_timer(name + "0_activation", name + "0_0_activation", name + "0_1_activation");
-        }
-        if (res_lin) (*res_lin)(ctx, H, AHW, false);          // reference :572-575
-        else if (residual_layer)
-            for (std::size_t i = 0; i < ctx.size(); i++) ctx.on(i, [c = ctx[i], h = H[i], a = AHW[i]] { axpy(c, h, a, (r_t)1); });
-        return AHW;
+        this->HW = dn_t(ctx, A.m(), std::min(in, out), HW_buffer);
+        this->AHW = dn_t(ctx, A.n(), out, AHW_buffer);
+        this->G_HW = dn_t(ctx, A_T.n(), std::min(in, out), HW_buffer);
+        this->G_out = dn_t(ctx, A_T.n(), in, AHW_buffer);
     }
-
-    dn_t residual_backward(dist_context ctx, dn_t G, dn_t out) {      // reference :603-606
-        if (res_lin) res_lin->backward(ctx, G, out, false);
-        else if (residual_layer)
-            for (std::size_t i = 0; i < ctx.size(); i++) ctx.on(i, [c = ctx[i], g = G[i], o = out[i]] { axpy(c, g, o, (r_t)1); });
-        return out;
-    }
-
-    bool gemm_first() const { return HW.m() == AHW.m(); }
-    bool has_activation() const { return activation; }
-    bool propagates() const { return lin.has_backward_out(); }
-    void set_fused_backward(bool mask_input, bool premasked) { if (mask_input) mask_input_grad = true; if (premasked) grad_premasked = true; }
-    dist_row_linear<r_t> &linear_layer() { return lin; }
-
-    auto backward(dist_context ctx, dn_t G) {
-        auto T = G;
-        if (activation && !grad_premasked) {
-            ctx.record(name + "1_0_activation", 0);
-            leaky_relu_backward(ctx, AHW, G, AHW);
-            ctx.record(name + "1_1_activation", 0);
-            ctx.register_timer(name + "1_activation", name + "1_0_activation", name + "1_1_activation");
-            T = AHW;
-        }
-        if (HW.m() == AHW.m()) {
-            auto g = G_HW;
-            if (backward_spmm) A.backward(ctx, T, g); else g = T;
-            lin.backward(ctx, g, G_out, true, mask_input_grad ? &H : nullptr);
-            return residual_backward(ctx, G, G_out);
-        }
-        lin.setX(H);
-        lin.backward(ctx, T, G_HW);
-        if (backward_spmm) { A.backward(ctx, G_HW, G_out); return residual_backward(ctx, G, G_out); }
-        return residual_backward(ctx, G, G_HW);
-    }
-
-    void finish_backward(const dist_context ctx) { for (auto *l : linears()) l->finish_backward(ctx); }
-    void adam_update(const dist_context ctx, const r_t lr, const r_t b1, const r_t b2, const r_t wd, const r_t eps) {
-        for (auto *l : linears()) l->adam_update(ctx, lr, b1, b2, wd, eps);
-    }
-    auto b() { return lin.get_b(); }
-    auto W() { return lin.get_W(); }
-    auto GW() { return lin.get_G_W(); }
-    auto Gb() { return lin.get_G_b(); }
 };
 
 // softmax: row max, exp(x - max), row sums by a GEMM with a ones vector, divide (reference :639-676)

@@ -123,6 +123,16 @@ void linear_backward_weights(const context ctx, const dn_matrix<r_t> X, const dn
                              G.m(), G_W.buffer(), G_W.m(), G_b.buffer(), ctx.gemm_workspace(ws), ws);
 }
 
+// G_W = X^T G and G_b = 1^T G of one GPU's rows: one pass over G (fused), or the reference's two GEMMs with a row of
+// ones (src/gcn.hpp:125-134)
+template <typename r_t>
+void linear_weight_gradients(const context ctx, const bool fused, const dn_matrix<r_t> ones, const dn_matrix<r_t> X,
+                             const dn_matrix<r_t> G, const dn_matrix<r_t> G_W, const dn_matrix<r_t> G_b) {
+    if (fused) return linear_backward_weights(ctx, X, G, G_W, G_b);
+    matmul(ctx, ones, G, G_b, (r_t)1, (r_t)0);
+    matmul(ctx, X, G, G_W, (r_t)1, (r_t)0, true);
+}
+
 // every (param, grad, m, v) quadruple of a model on one GPU as a device table: ONE Adam launch per epoch
 // (include/mggcn.h: mggcn_adam_multi_f32; reference src/gcn.hpp:146-172 runs 7 launches per layer)
 template <typename r_t>
@@ -386,11 +396,24 @@ void matmul(const dist_context ctx, const dist_row_dn_matrix<r_t> A, const dist_
     C.allreduce(ctx);
 }
 
+// (a row shard cannot be transposed locally: A_T must be false; the flag keeps the one-GPU form's signature)
 template <typename r_t>
 void matmul(const dist_context ctx, const dist_row_dn_matrix<r_t> A, const repl_dn_matrix<r_t> B,
-            const dist_row_dn_matrix<r_t> C, const r_t alpha, const r_t beta, const bool B_T = false) {
+            const dist_row_dn_matrix<r_t> C, const r_t alpha, const r_t beta, const bool A_T = false, const bool B_T = false) {
+    mggcn_require(!A_T, "matmul(dist): a row-partitioned A cannot be transposed");
     for (std::size_t i = 0; i < ctx.size(); i++)
         ctx.on(i, [c = ctx[i], a = A[i], b = B[i], cc = C[i], alpha, beta, B_T] { matmul(c, a, b, cc, alpha, beta, false, B_T); });
+}
+
+template <typename r_t>
+void matmul_lrelu_backward(const dist_context ctx, const dist_row_dn_matrix<r_t> A, const repl_dn_matrix<r_t> B,
+                           const dist_row_dn_matrix<r_t> Z, const dist_row_dn_matrix<r_t> C, const r_t alpha,
+                           const bool A_T = false, const bool B_T = false) {
+    mggcn_require(!A_T, "matmul_lrelu_backward(dist): a row-partitioned A cannot be transposed");
+    for (std::size_t i = 0; i < ctx.size(); i++)
+        ctx.on(i, [c = ctx[i], a = A[i], b = B[i], z = Z[i], cc = C[i], alpha, B_T] {
+            matmul_lrelu_backward(c, a, b, z, cc, alpha, false, B_T);
+        });
 }
 
 template <typename r_t>
@@ -540,4 +563,18 @@ void broadcast_rows(const dist_context ctx, const d1<r_t> row, const d2<r_t> mat
 template <typename r_t, template <typename> class dn_t>
 void scale_mat(const dist_context ctx, const dn_t<r_t> mat, r_t s) {
     for (std::size_t i = 0; i < ctx.size(); i++) ctx.on(i, [c = ctx[i], m = mat[i], s] { scale_mat(c, m, s); });
+}
+template <typename r_t, template <typename> class dn_t>
+void axpy(const dist_context ctx, const dn_t<r_t> A, const dn_t<r_t> B, const r_t alpha) {
+    for (std::size_t i = 0; i < ctx.size(); i++) ctx.on(i, [c = ctx[i], a = A[i], b = B[i], alpha] { axpy(c, a, b, alpha); });
+}
+// the local parts only (every GPU's G_W / G_b of its own rows): the caller sums them over the GPUs
+template <typename r_t>
+void linear_weight_gradients(const dist_context ctx, const bool fused, const repl_dn_matrix<r_t> ones,
+                             const dist_row_dn_matrix<r_t> X, const dist_row_dn_matrix<r_t> G, const repl_dn_matrix<r_t> G_W,
+                             const repl_dn_matrix<r_t> G_b) {
+    for (std::size_t i = 0; i < ctx.size(); i++)
+        ctx.on(i, [c = ctx[i], fused, o = fused ? dn_matrix<r_t>() : ones[i], x = X[i], g = G[i], gw = G_W[i], gb = G_b[i]] {
+            linear_weight_gradients(c, fused, o, x, g, gw, gb);
+        });
 }
