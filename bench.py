@@ -10,7 +10,7 @@ Reddit-shaped stand-in of SURVEY.md 8(d) (n = 232 968, nnz = 114 848 860 with
 self-loops, heavy-tailed degrees up to 21 657, random columns as after the reference's
 vertex permutation), features N(0,1) [n x 608], 41 uniform classes.
 
-  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,9 +19,17 @@ feature shards over RCCL.  Total work is fixed as N grows -> "scaling": "strong"
 Rank 0 prints ONE JSON line.  Plain `python bench.py --gpus N` (no launcher, WORLD_SIZE
 unset) starts the N ranks itself -- torch.distributed.run as a CHILD process, before
 this process has touched the GPU -- and relays rank 0's line and the children's exit code:
-one command, like the reference (`mg_gcn -P N ...`, README.md:44).  At N > 1 the line also
-carries the drop-in CLI's own epoch time on the same files (`cli_epoch_ms` and friends: the
-single-process C++ form, one enqueue thread per GPU, RCCL and peer-copy transports).
+one command, like the reference (`mg_gcn -P N ...`, README.md:44).
+
+A run without --full does only what the headline needs: set-up, the warm-up epochs, the
+timed epochs, --dump-outputs, the line (`roofline` / `roofline_narrow` come from the SpMM
+timers of the timed epochs themselves).  --full adds everything that takes runs of its own,
+after the timed epochs: at N = 1 the drop-in CLI on the same workload (`cli_*`), the hoisted
+first aggregation, the symmetric stand-in and the CPU oracle (`cpu_baseline`); at N > 1 the
+comm report (`comm`), the other piece count (`alt_chunks`) and the drop-in CLI's own epoch
+time on the same files (`cli_epoch_ms` and friends: the single-process C++ form, one enqueue
+thread per GPU, RCCL and peer-copy transports).  --no-extras / --no-cpu-baseline leave parts
+of that out again.
 """
 from __future__ import annotations
 
@@ -336,9 +344,14 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="the reference's -S flag")
     ap.add_argument("--chunks", type=int, default=0, help="pieces of the all-gather exchange (0 = default: 2 at N = 2, 4 above)")
     ap.add_argument("--unfused", action="store_true", help="reference launch sequence, no fused kernels")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed epochs, also measure what the headline does not need: the CPU oracle, the mg_gcn "
+                         "CLI, the hoisted first aggregation, the symmetric stand-in (N = 1); the comm report, the other "
+                         "piece count, the mg_gcn CLI legs (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra keys (symmetric stand-in epoch, the mg_gcn CLI's own epoch time); never the headline")
+                    help="with --full: skip the extra keys (symmetric stand-in epoch, the mg_gcn CLI's own epoch time, the "
+                         "hoisted first aggregation, the other piece count); never the headline")
     ap.add_argument("--workload", default="reddit_like", choices=["reddit_like", "products_like"],
                     help="reddit_like = BASELINE.json's headline config (default); products_like = configs[3]'s graph shape "
                          "(n = 2 449 032, 126.2 M non-zeros, F = 128, 47 classes) -- manual mode, B >> Infinity Cache: "
@@ -349,6 +362,8 @@ def main():
                     help="after the timed steps, write what the last one computed (loss, accuracy, every layer's "
                          "parameters and gradients) as DIR/<name>.npy; rank 0 only")
     args = ap.parse_args()
+    if not args.full:                                  # a plain run measures the headline and nothing else
+        args.no_extras = args.no_cpu_baseline = True
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args.gpus, args))
@@ -582,9 +597,10 @@ def main():
             if rank == 0:
                 shutil.rmtree(tmp, ignore_errors=True)
             sys.exit(3)
-        out["comm"] = comm_report(torch, dist, dctx, G, epoch, rehearsal, local_rank, spmm_timers, args)
-        out["comm"]["high_priority_stream"] = high_priority_comm
-        out["comm"]["chunks"] = out["comm"].get("chunks") or D.default_chunks(P)
+        if args.full:
+            out["comm"] = comm_report(torch, dist, dctx, G, epoch, rehearsal, local_rank, spmm_timers, args)
+            out["comm"]["high_priority_stream"] = high_priority_comm
+            out["comm"]["chunks"] = out["comm"].get("chunks") or D.default_chunks(P)
         if P > 1 and args.mode == "allgather" and not args.no_extras:
             # the same epoch with the OTHER piece count (2 <-> 4): how many pieces pay depends on what the links deliver against
             # what a piece costs the compute stream (model: profiles/experiments/rank_epoch_model_r04.log) -- one more data point

@@ -5,7 +5,7 @@
 #   bash profiles/collect_scale.sh [steps] [warmup]   ->  profiles/scale_<date>.jsonl  (one bench.py line per run)
 #
 # N = 1, 2, 4, 8  x  exchange schedule {allgather (K pieces, default), rounds (the reference's broadcast pipeline,
-# src/cuda_utils.hpp:57-92), halo}  x  overlap {on, off = the reference's -S}.  Every line carries
+# src/cuda_utils.hpp:57-92), halo}  x  overlap {on, off = the reference's -S}.  Every N > 1 run is a --full one, so its line carries
 # comm{backend, world_size, devices[], rccl_version, exchange_ms, exposed_ms, overlap_frac} (bench.py: comm_report).
 # The Python ranks exchange over torch.distributed = RCCL; every N > 1 line also carries the drop-in CLI's epoch on the same files in
 # three legs (cli_*: one enqueue thread per GPU over RCCL, cli_p2p_*: copy-engine peer copies, cli_serial_*: one host thread), each
@@ -24,7 +24,7 @@ for N in 2 4 8; do
     for OV in "" "--no-overlap"; do
       PORT=$((PORT + 1))
       echo "N=$N mode=$MODE $OV" >&2
-      timeout -k 10 1500 python3 "$ROOT/bench.py" --gpus "$N" --steps "$STEPS" --warmup "$WARMUP" --mode "$MODE" $OV >> "$OUT" \
+      timeout -k 10 1500 python3 "$ROOT/bench.py" --gpus "$N" --steps "$STEPS" --warmup "$WARMUP" --mode "$MODE" $OV --full >> "$OUT" \
         || echo "{\"error\": \"N=$N mode=$MODE $OV\"}" >> "$OUT"
     done
   done
@@ -33,7 +33,7 @@ done
 for K in 1 2 8; do
   PORT=$((PORT + 1))
   echo "N=8 mode=allgather chunks=$K" >&2
-  timeout -k 10 1500 python3 "$ROOT/bench.py" --gpus 8 --steps "$STEPS" --warmup "$WARMUP" --mode allgather --chunks "$K" >> "$OUT" \
+  timeout -k 10 1500 python3 "$ROOT/bench.py" --gpus 8 --steps "$STEPS" --warmup "$WARMUP" --mode allgather --chunks "$K" --full >> "$OUT" \
     || echo "{\"error\": \"N=8 allgather chunks=$K\"}" >> "$OUT"
 done
 python3 - "$OUT" <<'PY'

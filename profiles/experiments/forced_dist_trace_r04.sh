@@ -5,7 +5,7 @@ cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/r04_forced_dist
 mkdir -p $O
-B="python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extras"
+B="python3 $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extras"
 export MGGCN_BENCH_FORCE_DIST=1
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/dist -o dist --output-format csv -- $B > $O/dist_bench.json 2> $O/dist.err
 echo "dist trace done"

@@ -20,7 +20,7 @@ def _one_json_line(stdout: str) -> dict:
 
 @pytest.mark.gpu
 def test_bench_single_gpu_prints_one_json_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.05", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.05", "--steps", "2", "--warmup", "1", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = _one_json_line(r.stdout)
@@ -38,6 +38,26 @@ def test_bench_single_gpu_prints_one_json_line():
     assert out["symmetric_epoch_ms"] > 0 and out["symmetric_spmm_ms_per_call"] > 0
     assert "traffic_kernel_source_current" in rf and rf["traffic"] is None      # counters exist for the full-size shape only
     assert out["hoisted_first_aggregation"]["epoch_ms"] > 0 and out["hoisted_first_aggregation"]["spmm_per_epoch"] == 6
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("force_dist", [False, True], ids=["single", "dist_one_rank"])
+def test_plain_bench_measures_the_headline_only(force_dist):
+    """without --full the line holds the headline and what the timed epochs measured themselves (`roofline`), nothing that
+    takes runs of its own: no CPU oracle, no CLI, no hoisted or symmetric epochs, no comm pass, no other piece count"""
+    env = dict(os.environ)
+    if force_dist:
+        env.update(MGGCN_BENCH_FORCE_DIST="1", MASTER_PORT="29548", MGGCN_DIST_SELF_GATHER="1")
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.05", "--steps", "2", "--warmup", "1"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = _one_json_line(r.stdout)
+    assert REQUIRED <= set(out) and out["steps"] == 2 and out["warmup"] == 1 and out["value"] == out["ms_per_step"] > 0
+    assert out["roofline"]["calls_timed"] > 0 and out["loss_first_last"][1] < out["loss_first_last"][0]
+    moved = {"cpu_baseline", "hoisted_first_aggregation", "symmetric_epoch_ms", "comm", "alt_chunks"}
+    assert not moved & set(out) and not [k for k in out if k.startswith("cli_")], sorted(out)
 
 
 @pytest.mark.gpu
@@ -114,7 +134,7 @@ def test_bench_whose_ranks_fail_after_the_timed_epochs_keeps_the_headline():
 
 @pytest.mark.gpu
 def test_bench_multi_rank_rehearsal_prints_one_json_line():
-    out = _rehearsal([])
+    out = _rehearsal(["--full"])
     assert REQUIRED <= set(out)
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["config"]["parallelism"].startswith("rows2")
     assert out["loss_first_last"][1] < out["loss_first_last"][0]
@@ -154,7 +174,7 @@ def test_bench_distributed_path_over_rccl_with_one_rank():
     env = dict(os.environ, MGGCN_BENCH_FORCE_DIST="1", MASTER_PORT="29549", MGGCN_DIST_SELF_GATHER="1")   # one rank: exchange anyway
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--scale", "0.05"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--scale", "0.05", "--full"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     out = _one_json_line(r.stdout)
