@@ -176,7 +176,9 @@ uint32_t mggcn_spmm_plan_read_stamps(const mggcn_spmm_plan *plan, uint32_t slice
 /* A: n_rows x n_cols CSR (device pointers), B: n_cols x d (ldb >= d), C: n_rows x d
  * (ldc >= d).  beta == 0 never reads C.  C must not alias B.  plan may be NULL
  * (one wave per row in row order: correct for any input, slow on skewed degrees).
- * slope is only read with MGGCN_SPMM_LEAKY_RELU. */
+ * slope is only read with MGGCN_SPMM_LEAKY_RELU.
+ * A non-finite row of B reaches exactly the rows of C that have an entry in its column, possibly as NaN where Inf is
+ * expected: the sweep form pads runs with zero-valued copies of a real entry, and 0 * Inf = NaN. */
 void mggcn_spmm_csr_f32(mggcn_stream_t stream, const mggcn_spmm_plan *plan, uint32_t n_rows,
                         uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices,
                         const float *values, const float *B, size_t ldb, float *C, size_t ldc,

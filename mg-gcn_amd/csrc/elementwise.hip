@@ -92,8 +92,10 @@ void launch_map2(hipStream_t st, const float *a, const float *b, float *out, siz
 
 struct LreluFwd { float s; __device__ float operator()(float x) const { return lrelu(x, s); } };
 struct LreluBwd { float s; __device__ float operator()(float in, float g) const { return in > 0.f ? g : s * g; } };
-struct Axpby { float a, b; __device__ float operator()(float x, float y) const { return a * x + b * y; } };
-struct Aaxpby { float a, b; __device__ float operator()(float x, float y) const { return a * x * x + b * y; } };
+// The contraction is written out: left to the compiler, a * x + b * y became fmaf(a, x, b * y) in the float4 kernel and
+// two roundings in the scalar one, so the result depended on the pointers' alignment and on size % 4.
+struct Axpby { float a, b; __device__ float operator()(float x, float y) const { return fmaf(a, x, b * y); } };
+struct Aaxpby { float a, b; __device__ float operator()(float x, float y) const { return fmaf(a * x, x, b * y); } };
 struct Axpy { float a; __device__ float operator()(float x, float y) const { return fmaf(a, x, y); } };
 struct Scal { float a; __device__ float operator()(float x) const { return x * a; } };
 
