@@ -383,7 +383,9 @@ class softmax:
 
 class softmax_cross_entropy_loss:
     """reference src/gcn.hpp:769-823.  Returns (loss, acc) = (sum|log p_y|, #correct) / n
-    after a device sync, exactly where the reference blocks (:816-817)."""
+    after a device sync, exactly where the reference blocks (:816-817).
+    fused=True is the one-pass kernel for 1 <= m <= ops.XENT_FUSED_MAX_CLASSES classes; any other width runs the
+    unfused chain, with the results of fused=False."""
 
     def __init__(self, name: str, copy: bool = True, fused: bool = False, host_sums: bool = True):
         """host_sums: keep the two reported scalars in mapped pinned host memory (read without a device-to-host copy);
@@ -403,7 +405,7 @@ class softmax_cross_entropy_loss:
         ctx.record(n + "0_loss-layer", 0)
         if self.sums is None:
             self.sums = host_scalars(2) if self.host_sums else torch.empty(2, dtype=torch.float32, device=ctx.device)
-        if self.fused:
+        if self.fused and 1 <= H.m() <= ops.XENT_FUSED_MAX_CLASSES:
             if self.copy:                       # the reference copies, then works in place (gcn.hpp:653-656): here the
                 if self.G is None or self.G.shape() != H.shape():   # pass reads the logits, writes the gradient elsewhere
                     self.G = dn_matrix(H.n(), H.m())

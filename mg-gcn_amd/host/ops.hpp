@@ -530,6 +530,7 @@ void adam_fused(const context ctx, const dn_matrix<r_t> p, const dn_matrix<r_t> 
     ctx.set();
     mggcn_adam_fused_f32(ctx.stream(0), p.buffer(), g.buffer(), m.buffer(), v.buffer(), lr, b1, b2, wd, c1, c2, eps, p.size());
 }
+// 1 <= H.m() <= 1024 classes (a row lives in the registers of one wave); outside that the library fails fast (mggcn.h)
 template <typename r_t, typename x_t>
 void softmax_xent_fused(const context ctx, const dn_matrix<r_t> H, const dn_matrix<x_t> Y, r_t grad_scale, r_t *sums_device) {
     mggcn_require(H.n() == Y.n() && Y.m() == 1, "softmax_xent_fused: labels must be n x 1");

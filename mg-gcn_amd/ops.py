@@ -335,11 +335,16 @@ def abssum(ctx: context, A: dn_matrix, result_device) -> None:
 
 
 # ---- fused tail ------------------------------------------------
+XENT_FUSED_MAX_CLASSES = 1024       # 64 lanes x kXentMaxPerLane logits per lane (elementwise.hip)
+
+
 def softmax_xent_fused(ctx: context, H: dn_matrix, Y: dn_matrix, grad_scale: float, sums_device,
                        out: Optional[dn_matrix] = None) -> None:
     """softmax + argmax + log-prob + gradient in one pass; in place on H, or H -> out (the loss layer's copy = True:
-    the pass is the copy)"""
+    the pass is the copy).  1 <= H.m() <= XENT_FUSED_MAX_CLASSES: the kernel keeps a row in the registers of one wave
+    (the library would print and exit, not raise)"""
     _req(H.n() == Y.n() and Y.m() == 1, "labels must be n x 1")
+    _req(1 <= H.m() <= XENT_FUSED_MAX_CLASSES, f"fused loss supports 1 <= m <= {XENT_FUSED_MAX_CLASSES} classes, got {H.m()}")
     if out is None:
         out = H
     _req(out.n() == H.n() and out.m() == H.m(), "fused loss: gradient matrix must have the logits' shape")

@@ -47,6 +47,20 @@ def test_missing_library_is_loud(pkg, tmp_path):
     assert r.returncode == 7 and "no CPU fallback" in r.stdout
 
 
+@pytest.mark.parametrize("m", [0, 1025, 5000])
+def test_fused_loss_rejects_unsupported_widths_before_the_library(pkg, m):
+    """more than 1024 classes (or none) would reach MGGCN_REQUIRE in the library, which prints and exits the process:
+    ops.softmax_xent_fused raises first -- no context, stream or buffer is touched, so shapes are all this needs"""
+    class shape_only:
+        def __init__(self, n, m): self.n_, self.m_ = n, m
+        def n(self): return self.n_
+        def m(self): return self.m_
+    with pytest.raises(ValueError):
+        pkg.ops.softmax_xent_fused(None, shape_only(3, m), shape_only(3, 1), 1.0, None)
+    with pytest.raises(ValueError):
+        pkg.ops.softmax_xent_fused(None, shape_only(3, m), shape_only(3, 1), 1.0, None, out=shape_only(3, m))
+
+
 def _rand_csr(n, m, dens, seed):
     import scipy.sparse as sp
     M = sp.random(n, m, density=dens, format="csr", dtype=np.float32, random_state=seed)

@@ -243,7 +243,7 @@ def test_loss_chain_and_fused_loss(pkg, oracle, ctx, n, m):
     assert abs(float(s.item()) - np.abs(H.astype(np.float64)).sum()) <= 1e-5 * np.abs(H).sum()
 
 
-@pytest.mark.parametrize("m", [1, 2, 15, 16, 17, 32, 33, 41, 48, 49, 63, 64, 65, 128, 129])
+@pytest.mark.parametrize("m", [1, 2, 15, 16, 17, 32, 33, 41, 48, 49, 63, 64, 65, 128, 129, 257, 512, 513, 1000, 1024])
 def test_fused_loss_widths_out_of_place_and_reproducible(pkg, oracle, ctx, m):
     """every lanes-per-row / logits-per-lane form of the fused loss (16-lane rows up to 64 classes, a wave per row
     above), out of place == in place bit for bit, and the two reported scalars bitwise equal from run to run (they
