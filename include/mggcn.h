@@ -324,6 +324,26 @@ void mggcn_softmax_xent_fused_f32(mggcn_stream_t stream, float *H, const int32_t
  * is the pass itself. */
 void mggcn_softmax_xent_fused_from_f32(mggcn_stream_t stream, const float *logits, float *G, const int32_t *Y,
                                        size_t n_rows, size_t m, float grad_scale, float *sums_device);
+/* The split-aware form of the pass above.  The reference loads sets.bin (0 train / 1 validation /
+ * 2 test) and ignores it, src/main.cpp:85: its loss, gradient and accuracy run over ALL vertices.  Here S[i] is row i's
+ * set, train_set is 0, 1 or 2, and slot(s) = s for 0 <= s <= 2, 3 for every other value (rows in no split, padding):
+ *   G[i, :] = (O[i, :] - onehot(Y[i])) * grad_scale  if S[i] == train_set, else +0.0 in EVERY column (written, not
+ *             skipped: G may alias the logits, and the backward GEMMs read every row);
+ *   sums[2k] += sum over slot(S[i]) == k of |loss_terms[i]|,  sums[2k+1] += the same of correct[i],  k = 0..3
+ *   (eight floats, zeroed by the caller; grad_scale = 1 / the GLOBAL number of training rows).
+ * 1 <= m <= 1024 and G == logits allowed, as above.  Same grid, row order and fixed-order final sum as
+ * mggcn_softmax_xent_fused_from_f32 (four pairs of workgroup partials instead of one, no atomics): bitwise reproducible,
+ * and with S == train_set everywhere G and the training slot's pair are bit for bit those of the call above. */
+void mggcn_softmax_xent_split_from_f32(mggcn_stream_t stream, const float *logits, float *G, const int32_t *Y,
+                                       const int32_t *S, size_t n_rows, size_t m, int32_t train_set, float grad_scale,
+                                       float *sums_device);
+/* The two steps the unfused chain (src/gcn.hpp:785-818) needs to do the same, next to sets.bin being loaded and ignored at
+ * src/main.cpp:85.  select_rows_by_set: row i of the [size / m x m] matrix stays if S[i] == set, else becomes +0.0. */
+void mggcn_select_rows_by_set_f32(mggcn_stream_t stream, float *mat, const int32_t *S, int32_t set, size_t size,
+                                  size_t m);
+/* abssum_by_set: result[k] = sum over slot(S[i]) == k of |x[i]|, k = 0..3 (four floats, overwritten): the per-split form
+ * of mggcn_abssum_f32, the same fixed-order two-level reduction. */
+void mggcn_abssum_by_set_f32(mggcn_stream_t stream, const float *x, const int32_t *S, size_t n, float *result_device);
 /* One launch for linear::adam_update on a parameter tensor (src/gcn.hpp:146-172):
  *   g += wd*p; m = b1*m + (1-b1)*g; v = b2*v + (1-b2)*g*g;
  *   p -= (lr/c1) * m / (sqrt(v/c2) + eps)      (g is updated in place like the reference) */

@@ -243,7 +243,8 @@ __global__ __launch_bounds__(256) void adam_final_kernel(float *__restrict__ par
 // ---- |x| sum: fixed-order two-level reduction (reproducible) ---------------
 constexpr unsigned kAsumBlocks = 1024;
 constexpr unsigned kXentBlocks = kNumCU * 8;               // grid cap of the fused loss (stream_grid)
-constexpr unsigned kScratchFloats = 2 * kXentBlocks;        // abssum partials / the fused loss's (loss, correct) pairs
+constexpr unsigned kScratchFloats = 8 * kXentBlocks;        // abssum partials / the fused loss's (loss, correct) pairs: one pair
+                                                            // per workgroup, four (one per split slot) in the split-aware form
 
 __global__ __launch_bounds__(256) void abssum_partial_kernel(const float *__restrict__ A, size_t size,
                                                              float *__restrict__ partial) {
@@ -292,23 +293,71 @@ constexpr int kXentMaxPerLane = 16;  // m <= 1024
 // HBM round trip -- load, six shuffle steps, store -- and the pass was latency-bound at 0.7 TB/s (r01: 110 us for
 // the 76 MB of the [233 k x 41] logits); four rows in flight hide it.
 // (src and dst may be the same matrix: a row is read whole before any of it is written)
-template <int K, int R>
+//
+// Split = true is the split-aware instance (mggcn_softmax_xent_split_from_f32): S[r] is loaded next to Y[r], a row
+// outside train_set stores +0.0 in every column, and the (loss, correct) pair of a row goes to the accumulator pair of
+// its slot (0 train / 1 validation / 2 test / 3 anything else) by selects -- the other three add +0.0, which keeps their
+// bits.  Grid, row order per wave and the order of every sum are those of Split = false, so with S == train_set
+// everywhere the gradient and the training slot's pair are the bits of the plain pass.
+constexpr int xent_slots(bool split) { return split ? 4 : 1; }
+__device__ __forceinline__ uint32_t xent_slot(int32_t s) { return (uint32_t)s < 3u ? (uint32_t)s : 3u; }
+
+// A row's (loss, correct) pair goes to its slot: slot 0 lives in the pair of scalars the plain form has, slots 1..3 in
+// loss_x / corr_x.
+__device__ __forceinline__ void xent_add_by_slot(int32_t set, float lt, float ct, float &loss_acc, float &corr_acc,
+                                                 float (&loss_x)[3], float (&corr_x)[3]) {
+    const uint32_t slot = xent_slot(set);
+    loss_acc += slot == 0u ? lt : 0.f;
+    corr_acc += slot == 0u ? ct : 0.f;
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        loss_x[j] += slot == (uint32_t)(j + 1) ? lt : 0.f;
+        corr_x[j] += slot == (uint32_t)(j + 1) ? ct : 0.f;
+    }
+}
+
+// The end of the split-aware kernels: lane 0 of every wave holds the wave's four pairs; one pair per workgroup and slot goes
+// to the partials ([workgroup][slot][loss, correct]), summed by sums_final_kernel<8>.
+__device__ __forceinline__ void xent_write_split_partials(float loss_acc, float corr_acc, const float (&loss_x)[3],
+                                                          const float (&corr_x)[3], float *s_loss, float *s_acc, int lane,
+                                                          int wid, float *__restrict__ partials) {
+    if (lane == 0) {
+        s_loss[wid] = loss_acc; s_acc[wid] = corr_acc;
+#pragma unroll
+        for (int j = 1; j < 4; j++) { s_loss[4 * j + wid] = loss_x[j - 1]; s_acc[4 * j + wid] = corr_x[j - 1]; }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            partials[8 * blockIdx.x + 2 * j + 0] = (s_loss[4 * j + 0] + s_loss[4 * j + 1]) + (s_loss[4 * j + 2] + s_loss[4 * j + 3]);
+            partials[8 * blockIdx.x + 2 * j + 1] = (s_acc[4 * j + 0] + s_acc[4 * j + 1]) + (s_acc[4 * j + 2] + s_acc[4 * j + 3]);
+        }
+    }
+}
+
+// (S and train_set come last: the arguments of the plain instances keep their places)
+template <int K, int R, bool Split>
 __global__ __launch_bounds__(256) void softmax_xent_fused_kernel(const float *src, float *dst,
                                                                  const int32_t *__restrict__ Y,
                                                                  size_t n_rows, size_t m, float grad_scale,
-                                                                 float *__restrict__ partials) {
-    __shared__ float s_loss[4], s_acc[4];
+                                                                 float *__restrict__ partials,
+                                                                 const int32_t *__restrict__ S, int32_t train_set) {
+    constexpr int NS = xent_slots(Split);
+    __shared__ float s_loss[4 * NS], s_acc[4 * NS];       // [slot][wave]
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const size_t wstride = ((size_t)gridDim.x * blockDim.x) >> 6;
     float loss_acc = 0.f, corr_acc = 0.f;
+    float loss_x[3] = {0.f, 0.f, 0.f}, corr_x[3] = {0.f, 0.f, 0.f};      // slots 1..3, Split only
     for (size_t r0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; r0 < n_rows; r0 += wstride * R) {
         float x[R][K];
-        int32_t y[R];
+        int32_t y[R], s[Split ? R : 1];
 #pragma unroll
         for (int q = 0; q < R; q++) {                     // all loads first
             const size_t r = r0 + (size_t)q * wstride;
             const bool live = r < n_rows;                 // wave-uniform
             y[q] = live ? Y[r] : 0;
+            if constexpr (Split) s[q] = live ? S[r] : 0;
 #pragma unroll
             for (int k = 0; k < K; k++) {
                 const size_t c = (size_t)lane + 64u * k;
@@ -345,7 +394,9 @@ __global__ __launch_bounds__(256) void softmax_xent_fused_kernel(const float *sr
                 if (c < m) {
                     const float o = x[q][k] / sum;
                     const bool hit = (int32_t)c == y[q];
-                    dst[r * m + c] = (hit ? o - 1.f : o) * grad_scale;
+                    const float g = (hit ? o - 1.f : o) * grad_scale;
+                    if constexpr (Split) dst[r * m + c] = s[q] == train_set ? g : 0.f;
+                    else dst[r * m + c] = g;
                     x[q][k] = o;
                 }
             }
@@ -356,18 +407,27 @@ __global__ __launch_bounds__(256) void softmax_xent_fused_kernel(const float *sr
                         py = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x[q][k]), y[q] & 63));
             }
             if (lane == 0) {
-                loss_acc += fabsf(logf(py));
                 // argmax of the softmax output == argmax of the logits (exp is monotone);
                 // a row whose maximum never beat -inf reports index 0 like the reference
-                corr_acc += ((idx == 0xFFFFFFFFu ? 0 : (int32_t)idx) == y[q]) ? 1.f : 0.f;
+                if constexpr (Split) {
+                    xent_add_by_slot(s[q], fabsf(logf(py)), ((idx == 0xFFFFFFFFu ? 0 : (int32_t)idx) == y[q]) ? 1.f : 0.f,
+                                     loss_acc, corr_acc, loss_x, corr_x);
+                } else {
+                    loss_acc += fabsf(logf(py));
+                    corr_acc += ((idx == 0xFFFFFFFFu ? 0 : (int32_t)idx) == y[q]) ? 1.f : 0.f;
+                }
             }
         }
     }
-    if (lane == 0) { s_loss[wid] = loss_acc; s_acc[wid] = corr_acc; }
-    __syncthreads();
-    if (threadIdx.x == 0) {              // one (loss, correct) pair per workgroup, summed by xent_final_kernel
-        partials[2 * blockIdx.x + 0] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
-        partials[2 * blockIdx.x + 1] = (s_acc[0] + s_acc[1]) + (s_acc[2] + s_acc[3]);
+    if constexpr (Split) {
+        xent_write_split_partials(loss_acc, corr_acc, loss_x, corr_x, s_loss, s_acc, lane, wid, partials);
+    } else {
+        if (lane == 0) { s_loss[wid] = loss_acc; s_acc[wid] = corr_acc; }
+        __syncthreads();
+        if (threadIdx.x == 0) {              // one (loss, correct) pair per workgroup, summed by xent_final_kernel
+            partials[2 * blockIdx.x + 0] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
+            partials[2 * blockIdx.x + 1] = (s_acc[0] + s_acc[1]) + (s_acc[2] + s_acc[3]);
+        }
     }
 }
 
@@ -388,25 +448,29 @@ __device__ __forceinline__ T row16_reduce(T v, Op op) {
     return v;
 }
 
-template <int KE, int R>
+template <int KE, int R, bool Split>
 __global__ __launch_bounds__(256) void softmax_xent_rows16_kernel(const float *src, float *dst,
                                                                   const int32_t *__restrict__ Y, size_t n_rows,
-                                                                  uint32_t m, float grad_scale, float *__restrict__ partials) {
-    __shared__ float s_loss[4], s_acc[4];
+                                                                  uint32_t m, float grad_scale, float *__restrict__ partials,
+                                                                  const int32_t *__restrict__ S, int32_t train_set) {
+    constexpr int NS = xent_slots(Split);
+    __shared__ float s_loss[4 * NS], s_acc[4 * NS];       // [slot][wave]
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     const uint32_t sub = lane & 15;
     const size_t gstride = ((size_t)gridDim.x * blockDim.x) >> 4;           // 16-lane groups in the grid
     const size_t g0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
     const size_t w0 = g0 & ~(size_t)3;                                       // first group of this wave
     float loss_acc = 0.f, corr_acc = 0.f;
+    float loss_x[3] = {0.f, 0.f, 0.f}, corr_x[3] = {0.f, 0.f, 0.f};      // slots 1..3, Split only
     for (size_t base = 0; w0 + base < n_rows; base += gstride * R) {         // wave-uniform trip count
         float x[R][KE];
-        int32_t y[R];
+        int32_t y[R], s[Split ? R : 1];
 #pragma unroll
         for (int q = 0; q < R; q++) {                                        // all loads first
             const size_t r = g0 + base + (size_t)q * gstride;
             const bool live = r < n_rows;
             y[q] = live ? Y[r] : 0;
+            if constexpr (Split) s[q] = live ? S[r] : 0;
 #pragma unroll
             for (int k = 0; k < KE; k++) {
                 const uint32_t c = sub + 16u * k;
@@ -440,23 +504,38 @@ __global__ __launch_bounds__(256) void softmax_xent_rows16_kernel(const float *s
                 const uint32_t c = sub + 16u * k;
                 const float o = x[q][k] / sum;
                 const bool hit = (int32_t)c == y[q];
-                if (live && c < m) dst[r * m + c] = (hit ? o - 1.f : o) * grad_scale;
+                const float g = (hit ? o - 1.f : o) * grad_scale;
+                if constexpr (Split) { if (live && c < m) dst[r * m + c] = s[q] == train_set ? g : 0.f; }
+                else { if (live && c < m) dst[r * m + c] = g; }
                 if (hit && c < m) py = o;
             }
             py = row16_reduce(py, [](float a, float b) { return a + b; });   // the others are exact zeros
             if (live && sub == 0) {
-                loss_acc += fabsf(logf(py));
-                corr_acc += ((idx == 0xFFFFFFFFu ? 0 : (int32_t)idx) == y[q]) ? 1.f : 0.f;
+                if constexpr (Split) {
+                    xent_add_by_slot(s[q], fabsf(logf(py)), ((idx == 0xFFFFFFFFu ? 0 : (int32_t)idx) == y[q]) ? 1.f : 0.f,
+                                     loss_acc, corr_acc, loss_x, corr_x);
+                } else {
+                    loss_acc += fabsf(logf(py));
+                    corr_acc += ((idx == 0xFFFFFFFFu ? 0 : (int32_t)idx) == y[q]) ? 1.f : 0.f;
+                }
             }
         }
     }
     loss_acc = wave_sum_dpp(loss_acc);
     corr_acc = wave_sum_dpp(corr_acc);
-    if (lane == 0) { s_loss[wid] = loss_acc; s_acc[wid] = corr_acc; }
-    __syncthreads();
-    if (threadIdx.x == 0) {              // one (loss, correct) pair per workgroup, summed by xent_final_kernel
-        partials[2 * blockIdx.x + 0] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
-        partials[2 * blockIdx.x + 1] = (s_acc[0] + s_acc[1]) + (s_acc[2] + s_acc[3]);
+    if constexpr (Split) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) { loss_x[j] = wave_sum_dpp(loss_x[j]); corr_x[j] = wave_sum_dpp(corr_x[j]); }
+    }
+    if constexpr (Split) {
+        xent_write_split_partials(loss_acc, corr_acc, loss_x, corr_x, s_loss, s_acc, lane, wid, partials);
+    } else {
+        if (lane == 0) { s_loss[wid] = loss_acc; s_acc[wid] = corr_acc; }
+        __syncthreads();
+        if (threadIdx.x == 0) {              // one (loss, correct) pair per workgroup, summed by xent_final_kernel
+            partials[2 * blockIdx.x + 0] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
+            partials[2 * blockIdx.x + 1] = (s_acc[0] + s_acc[1]) + (s_acc[2] + s_acc[3]);
+        }
     }
 }
 
@@ -475,6 +554,67 @@ __global__ __launch_bounds__(256) void xent_final_kernel(const float *__restrict
         sums[0] += (w[0][0] + w[0][1]) + (w[0][2] + w[0][3]);
         sums[1] += (w[1][0] + w[1][1]) + (w[1][2] + w[1][3]);
     }
+}
+
+// The same tree for NV values per workgroup, each summed on its own in the order above (8: one pair per split slot; 4: the
+// by-set |x| sums).  Add = false stores instead of adding (mggcn_abssum_by_set_f32, like abssum_final_kernel).
+template <int NV, bool Add>
+__global__ __launch_bounds__(256) void sums_final_kernel(const float *__restrict__ partials, unsigned n_blocks,
+                                                         float *__restrict__ sums) {
+    __shared__ float w[NV][4];
+    float v[NV];
+#pragma unroll
+    for (int j = 0; j < NV; j++) v[j] = 0.f;
+    for (unsigned i = threadIdx.x; i < n_blocks; i += 256) {
+#pragma unroll
+        for (int j = 0; j < NV; j++) v[j] += partials[NV * i + j];
+    }
+#pragma unroll
+    for (int j = 0; j < NV; j++) v[j] = wave_sum(v[j]);
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int j = 0; j < NV; j++) w[j][threadIdx.x >> 6] = v[j];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int j = 0; j < NV; j++) {
+            const float t = (w[j][0] + w[j][1]) + (w[j][2] + w[j][3]);
+            sums[j] = Add ? sums[j] + t : t;
+        }
+    }
+}
+
+// ---- the unfused chain's split steps ------------------------------------------
+// mat[i, :] = +0.0 where S[i] != set
+__global__ __launch_bounds__(256) void select_rows_by_set_kernel(float *__restrict__ mat, const int32_t *__restrict__ S,
+                                                                 int32_t set, size_t size, size_t m) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < size; i += stride)
+        if (S[i / m] != set) mat[i] = 0.f;
+}
+
+// partial[4 b + k] = this workgroup's sum of |x[i]| over slot(S[i]) == k
+__global__ __launch_bounds__(256) void abssum_by_set_partial_kernel(const float *__restrict__ x,
+                                                                    const int32_t *__restrict__ S, size_t n,
+                                                                    float *__restrict__ partial) {
+    __shared__ float wsum[4][4];
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    float acc[4] = {0.f, 0.f, 0.f, 0.f};
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const float a = fabsf(x[i]);
+        const uint32_t slot = xent_slot(S[i]);
+#pragma unroll
+        for (int k = 0; k < 4; k++) acc[k] += slot == (uint32_t)k ? a : 0.f;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        acc[k] = wave_sum(acc[k]);
+        if ((threadIdx.x & 63) == 0) wsum[k][threadIdx.x >> 6] = acc[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        partial[4 * blockIdx.x + threadIdx.x] = (wsum[threadIdx.x][0] + wsum[threadIdx.x][1]) + (wsum[threadIdx.x][2] + wsum[threadIdx.x][3]);
 }
 
 // ---- fused Adam -------------------------------------------------------------
@@ -700,42 +840,91 @@ MGGCN_API void mggcn_abssum_f32(mggcn_stream_t stream, const float *A, size_t si
     MGGCN_CHECK_LAUNCH();
 }
 
-MGGCN_API void mggcn_softmax_xent_fused_from_f32(mggcn_stream_t stream, const float *logits, float *G, const int32_t *Y,
-                                                 size_t n_rows, size_t m, float grad_scale, float *sums_device) {
-    if (!n_rows) return;
-    MGGCN_REQUIRE(m > 0 && m <= 64u * kXentMaxPerLane, "fused loss supports 1 <= m <= 1024 classes");
-    MGGCN_REQUIRE(logits != nullptr && G != nullptr && Y != nullptr && sums_device != nullptr, "fused loss: null operand");
-    hipStream_t st = as_stream(stream);
+namespace {
+// Both forms of the fused loss: the same grid, dispatch on KE / K / R and final tree; Split adds S and train_set to the
+// kernel and four pairs instead of one to the partials.
+template <bool Split>
+void xent_final(hipStream_t st, const float *partials, unsigned n_blocks, float *sums_device) {
+    if constexpr (Split)
+        hipLaunchKernelGGL((sums_final_kernel<8, true>), dim3(1), dim3(256), 0, st, partials, n_blocks, sums_device);
+    else
+        hipLaunchKernelGGL(xent_final_kernel, dim3(1), dim3(256), 0, st, partials, n_blocks, sums_device);
+    MGGCN_CHECK_LAUNCH();
+}
+
+template <bool Split>
+void launch_xent(hipStream_t st, const float *logits, float *G, const int32_t *Y, const int32_t *S, size_t n_rows, size_t m,
+                 int32_t train_set, float grad_scale, float *sums_device) {
     const dim3 block(256);
     float *partials = abssum_scratch(st);        // per (device, stream); stream order keeps its users apart
     if (m <= 64) {                               // one row per 16-lane group
         const dim3 grid(stream_grid(n_rows * 16));
-#define MGGCN_XENT16(KE)                                                                                   \
-    hipLaunchKernelGGL((softmax_xent_rows16_kernel<KE, 4>), grid, block, 0, st, logits, G, Y, n_rows, (uint32_t)m, \
-                       grad_scale, partials)
+#define MGGCN_XENT16(KE)                                                                                          \
+    hipLaunchKernelGGL((softmax_xent_rows16_kernel<KE, 4, Split>), grid, block, 0, st, logits, G, Y, n_rows, (uint32_t)m, \
+                       grad_scale, partials, S, train_set)
         if (m <= 16) MGGCN_XENT16(1);
         else if (m <= 32) MGGCN_XENT16(2);
         else if (m <= 48) MGGCN_XENT16(3);
         else MGGCN_XENT16(4);
 #undef MGGCN_XENT16
         MGGCN_CHECK_LAUNCH();
-        hipLaunchKernelGGL(xent_final_kernel, dim3(1), dim3(256), 0, st, partials, grid.x, sums_device);
-        MGGCN_CHECK_LAUNCH();
+        xent_final<Split>(st, partials, grid.x, sums_device);
         return;
     }
     // (tried on the wave-per-row form: two workgroups per CU to thin out the two contended scalar atomics at the end of
     //  every workgroup -- 105 -> 145 us: the pass wants the occupancy)
     const dim3 grid(stream_grid(n_rows * 64));
-#define MGGCN_XENT(K, R)                                                                              \
-    hipLaunchKernelGGL((softmax_xent_fused_kernel<K, R>), grid, block, 0, st, logits, G, Y, n_rows, m, grad_scale, \
-                       partials)
+#define MGGCN_XENT(K, R)                                                                                     \
+    hipLaunchKernelGGL((softmax_xent_fused_kernel<K, R, Split>), grid, block, 0, st, logits, G, Y, n_rows, m, grad_scale, \
+                       partials, S, train_set)
     if (m <= 128) MGGCN_XENT(2, 4);
     else if (m <= 256) MGGCN_XENT(4, 2);
     else if (m <= 512) MGGCN_XENT(8, 1);
     else MGGCN_XENT(16, 1);
 #undef MGGCN_XENT
     MGGCN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(xent_final_kernel, dim3(1), dim3(256), 0, st, partials, grid.x, sums_device);
+    xent_final<Split>(st, partials, grid.x, sums_device);
+}
+}  // namespace
+
+MGGCN_API void mggcn_softmax_xent_fused_from_f32(mggcn_stream_t stream, const float *logits, float *G, const int32_t *Y,
+                                                 size_t n_rows, size_t m, float grad_scale, float *sums_device) {
+    if (!n_rows) return;
+    MGGCN_REQUIRE(m > 0 && m <= 64u * kXentMaxPerLane, "fused loss supports 1 <= m <= 1024 classes");
+    MGGCN_REQUIRE(logits != nullptr && G != nullptr && Y != nullptr && sums_device != nullptr, "fused loss: null operand");
+    launch_xent<false>(as_stream(stream), logits, G, Y, nullptr, n_rows, m, 0, grad_scale, sums_device);
+}
+
+MGGCN_API void mggcn_softmax_xent_split_from_f32(mggcn_stream_t stream, const float *logits, float *G, const int32_t *Y,
+                                                 const int32_t *S, size_t n_rows, size_t m, int32_t train_set,
+                                                 float grad_scale, float *sums_device) {
+    if (!n_rows) return;
+    MGGCN_REQUIRE(m > 0 && m <= 64u * kXentMaxPerLane, "fused loss supports 1 <= m <= 1024 classes");
+    MGGCN_REQUIRE(train_set >= 0 && train_set <= 2, "train_set must be 0 (train), 1 (validation) or 2 (test)");
+    MGGCN_REQUIRE(logits != nullptr && G != nullptr && Y != nullptr && S != nullptr && sums_device != nullptr,
+                  "split-aware fused loss: null operand");
+    launch_xent<true>(as_stream(stream), logits, G, Y, S, n_rows, m, train_set, grad_scale, sums_device);
+}
+
+MGGCN_API void mggcn_select_rows_by_set_f32(mggcn_stream_t stream, float *mat, const int32_t *S, int32_t set, size_t size,
+                                            size_t m) {
+    if (!size) return;
+    MGGCN_REQUIRE(m > 0 && size % m == 0, "size must be n_rows * m");
+    MGGCN_REQUIRE(mat != nullptr && S != nullptr, "select_rows_by_set: null operand");
+    hipLaunchKernelGGL(select_rows_by_set_kernel, dim3(stream_grid(size)), dim3(256), 0, as_stream(stream), mat, S, set,
+                       size, m);
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_abssum_by_set_f32(mggcn_stream_t stream, const float *x, const int32_t *S, size_t n,
+                                       float *result_device) {
+    MGGCN_REQUIRE(result_device != nullptr && (!n || (x != nullptr && S != nullptr)), "abssum_by_set: null operand");
+    float *scratch = abssum_scratch(as_stream(stream));
+    const unsigned blocks = std::min<unsigned>(kAsumBlocks, stream_grid(n ? n : 1));
+    hipLaunchKernelGGL(abssum_by_set_partial_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), x, S, n, scratch);
+    MGGCN_CHECK_LAUNCH();
+    hipLaunchKernelGGL((sums_final_kernel<4, false>), dim3(1), dim3(256), 0, as_stream(stream), scratch, blocks,
+                       result_device);
     MGGCN_CHECK_LAUNCH();
 }
 

@@ -493,11 +493,12 @@ def read_edge_list(path: str):
 
 
 def prepare_dataset(dirname: str, adj, features, labels, sets=None, P: int = 8, seed: int = 0,
-                    permutation=None, partitioner=None) -> str:
+                    permutation=None, partitioner=None, pad_set: int = 0) -> str:
     """adj: scipy sparse (n x n) or (indptr, indices, data) CSR triple; features [n x F];
     labels [n]; sets [n] in {0 train, 1 val, 2 test}.
       * pads the vertex count and the feature width to multiples of P with zero vertices /
-        zero columns (prep.py:101-103, :122-124; padding vertices get label 0, set 0),
+        zero columns (prep.py:101-103, :122-124; padding vertices get label 0 and set ``pad_set``: 0 like the
+        reference, which never uses the sets; 3 keeps them out of every split of a split-aware training run),
       * adds a self-loop to every vertex, padding included (prep.py:113),
       * seed != 0: applies one random symmetric permutation to graph, features, labels, sets
         and writes under <dirname>/permuted/... like prep.py:80-94,
@@ -525,7 +526,9 @@ def prepare_dataset(dirname: str, adj, features, labels, sets=None, P: int = 8, 
     feats = np.zeros((n, F), dtype=np.float32)
     feats[:n0, :F0] = features
     labs = np.zeros(n, dtype=np.int64); labs[:n0] = labels
-    st = np.zeros(n, dtype=np.int64); st[:n0] = sets
+    if not 0 <= int(pad_set) <= 3:
+        raise ValueError(f"pad_set must be 0, 1, 2 (a split) or 3 (no split), got {pad_set!r}")
+    st = np.full(n, int(pad_set), dtype=np.int64); st[:n0] = sets
     out = dirname
     perm = None
     head, tail = os.path.split(os.path.normpath(dirname))

@@ -44,7 +44,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, ops
-from .gcn import adam_update_all, layer_body, linear, link_fused_backward, softmax_cross_entropy_loss
+from .gcn import (adam_update_all, check_splits, layer_body, linear, link_fused_backward, softmax_cross_entropy_loss,
+                  split_counts)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -585,7 +586,20 @@ def load_rank_local_host(dctx: host_comm, dirname: str):
     num_labels = 1 + (int(dctx.host_all_reduce(np.array([ymax], dtype=np.int64), "max")[0]) if P > 1 else ymax)
     info = {"n": n, "nnz_local": int(ip[-1]), "features": int(X.shape[1]), "num_labels": num_labels, "p": p,
             "host_bytes": int(ip.nbytes + ix.nbytes + 2 * dv.nbytes + ent.nbytes + X.nbytes)}
+    spath = os.path.join(dirname, "sets.bin")
+    if os.path.exists(spath):             # this rank's rows of the splits (0 train / 1 val / 2 test), for dist_gcn.set_splits
+        info["sets"] = ds.read_dense_rows(spath, "<i4", rb, re)
     return A_rows, AT_rows, X, Y, info
+
+
+def global_split_counts(comm: host_comm, local_sets: np.ndarray, train_set: int = 0) -> List[int]:
+    """Rows per slot (train, val, test, other) over ALL ranks from every rank's rows of the sets: ONE host all-reduce of
+    four integers; raises ValueError on every rank alike when nothing belongs to train_set.  Needs no GPU (host_comm)."""
+    mine = np.asarray(split_counts(local_sets), dtype=np.int64)
+    counts = [int(c) for c in (comm.host_all_reduce(mine) if comm.P > 1 else mine)]
+    if counts[train_set] == 0:
+        raise ValueError(f"no vertex belongs to set {train_set}: nothing to train on")
+    return counts
 
 
 def load_rank_local(dctx: dist_context, dirname: str, chunks: Optional[int] = None):
@@ -758,11 +772,12 @@ class dist_row_linear(linear):
         torch = _torch()
         # G_W and G_b live in ONE buffer: a single in-place all-reduce, no packing copies
         off_b = (in_ * out + 3) // 4 * 4                       # keep G_b 16-byte aligned
-        # ... and four more floats after G_b: the model's LAST layer carries the epoch's two loss sums through its gradient
-        # all-reduce there (dist_gcn.train_step: no collective of their own)
+        # ... and eight more floats after G_b: the model's LAST layer carries the epoch's loss sums through its gradient
+        # all-reduce there (dist_gcn.train_step: no collective of their own) -- two, or the eight of a split-aware epoch
         off_t = (off_b + out + 3) // 4 * 4
-        self.G_flat = torch.zeros(off_t + 4, dtype=torch.float32, device=self._dctx.ctx.device)
+        self.G_flat = torch.zeros(off_t + 8, dtype=torch.float32, device=self._dctx.ctx.device)
         self.tail = self.G_flat[off_t:off_t + 2]
+        self.tail8 = self.G_flat[off_t:off_t + 8]
         torch.cuda.current_stream().synchronize()              # torch zeroes on ITS stream (the padding takes part in the sum);
                                                                # the kernels run on the context's
         return dn_matrix(in_, out, self.G_flat), dn_matrix(1, out, self.G_flat[off_b:])
@@ -851,18 +866,31 @@ class dist_row_softmax_cross_entropy_loss:
         dctx.sync()                                   # the reference blocks here too (:928)
         return self.read(dctx)
 
+    def set_splits(self, S: Optional[dn_matrix], counts=None, train_set: int = 0) -> None:
+        """S: this rank's rows of the sets (int32, on the rank's device); counts: the GLOBAL rows per slot"""
+        self.inner.set_splits(S, counts, train_set)
+        self.global_sums = None
+
+    def split_metrics(self, sums=None):
+        """every split's global (loss, acc) of the last call that was read (read() / dist_gcn.train_step)"""
+        return self.inner.split_metrics(self.global_sums if sums is None else sums)
+
     def read(self, dctx: dist_context):
         """global (loss, acc) of the last call; the caller has synchronised"""
         dist = _dist()
         H_n = self._n
+        mine = self.inner.sums if self.inner.S is None else self.inner.split_sums      # 2 floats, or the 8 of the splits
         if dctx.backend == "nccl":
-            sums = self.inner.sums.clone()
+            sums = mine.clone()
             dist.all_reduce(sums, group=dctx.group)
             sums = sums.cpu()
         else:
-            sums = self.inner.sums.detach().cpu()
+            sums = mine.detach().cpu()
             dist.all_reduce(sums, group=dctx.group)
         s = sums.numpy()
+        if self.inner.S is not None:
+            self.global_sums = s.copy()
+            return self.split_metrics()[ops.SPLIT_NAMES[self.inner.train_set]]
         n = np.float32(H_n)
         return float(np.float32(s[0]) / n), float(np.float32(s[1]) / n)
 
@@ -907,6 +935,7 @@ class dist_gcn:
         link_fused_backward(self.layers_, fused)
         self.fused, self._adam = fused, None
         self._loss_host = None                                 # pinned host copy of the epoch's two global loss sums (train_step)
+        self._split_host = None                                # ... and of the eight of a split-aware epoch
         # this rank's SpMM plans, built side by side before the first epoch (ops.prebuild_plans) instead of one by one
         # inside it: the diagonal block and the pieces of the schedule that runs, both matrices, both widths
         self._plan_wants = []
@@ -916,6 +945,27 @@ class dist_gcn:
                 parts = list(M.blocks) if mode == "rounds" else \
                     [M.diag] + (list(M.remote_chunks) if mode == "allgather" and P > 1 else [])
                 self._plan_wants += [(blk, max(w, 128), w) for blk in parts]
+
+    def set_splits(self, dctx: dist_context, Sd, train_set: int = 0) -> None:
+        """Train on one split (see gcn.set_splits).  Sd: THIS RANK's rows of the sets, as an int32 dist_row_dn_matrix (or a
+        host array of the rank's rows); None switches the splits off.  The four global counts come from one host
+        all-reduce, here; every rank must call this."""
+        if Sd is None:
+            self.loss_layer.set_splits(None)
+            return
+        local = Sd.local if isinstance(Sd, dist_row_dn_matrix) else Sd
+        rows = self.layers_[-1].AHW.n()
+        host, mine = check_splits(local, rows, train_set, counts=[1, 1, 1, 1])       # shape, dtype and train_set only
+        counts = global_split_counts(dctx, host, train_set)
+        if not isinstance(local, dn_matrix):
+            local = dn_matrix.from_numpy(host, dctx.ctx.device)
+        self.loss_layer.set_splits(local, counts, train_set)
+
+    def split_metrics(self):
+        """every split's global (loss, acc) of the last epoch: the same numbers on every rank"""
+        if self.loss_layer.inner.S is None:
+            raise ValueError("split_metrics() needs set_splits(dctx, Sd) first")
+        return self.loss_layer.split_metrics()
 
     def __call__(self, dctx, H):
         if self._plan_wants:
@@ -967,6 +1017,19 @@ class dist_gcn:
         # ~0.1 ms of idle GPU per 3.5-ms epoch.  (The reference adds its P managed scalars on the host, src/gcn.hpp:929.)
         st = dctx.ctx.cuda_streams[0]
         last = self.layers_[-1].lin
+        inner = self.loss_layer.inner
+        if inner.S is not None:                                # the eight sums of the splits travel the same way
+            with torch.cuda.stream(st):
+                last.tail8.copy_(inner.split_sums)
+            self.backward(dctx)
+            self.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
+            if self._split_host is None:
+                self._split_host = torch.empty(8, dtype=torch.float32, pin_memory=True)
+            with torch.cuda.stream(st):
+                self._split_host.copy_(last.tail8, non_blocking=True)
+            dctx.sync()
+            self.loss_layer.global_sums = self._split_host.numpy().copy()
+            return self.loss_layer.split_metrics()[ops.SPLIT_NAMES[inner.train_set]]
         with torch.cuda.stream(st):
             last.tail.copy_(self.loss_layer.inner.sums)
         self.backward(dctx)                                    # ... -> finish_backward: the compute stream sees the summed buffers

@@ -385,7 +385,12 @@ class softmax_cross_entropy_loss:
     """reference src/gcn.hpp:769-823.  Returns (loss, acc) = (sum|log p_y|, #correct) / n
     after a device sync, exactly where the reference blocks (:816-817).
     fused=True is the one-pass kernel for 1 <= m <= ops.XENT_FUSED_MAX_CLASSES classes; any other width runs the
-    unfused chain, with the results of fused=False."""
+    unfused chain, with the results of fused=False.
+
+    set_splits(S, counts, train_set) (opt-in; the reference loads sets.bin and ignores it, src/main.cpp:85) makes the
+    layer split-aware: rows outside train_set get a zero gradient row, the gradient is scaled by 1 / (the global number
+    of training rows), (loss, acc) are the training split's, and split_metrics() reports every split of the last call --
+    from the same pass, which sums a (loss, correct) pair per slot train / val / test / other."""
 
     def __init__(self, name: str, copy: bool = True, fused: bool = False, host_sums: bool = True):
         """host_sums: keep the two reported scalars in mapped pinned host memory (read without a device-to-host copy);
@@ -395,6 +400,31 @@ class softmax_cross_entropy_loss:
         self.copy, self.fused, self.host_sums = copy, fused, host_sums
         self.G = self.L = self.P = self.T = None
         self.sums = None
+        self.S: Optional[dn_matrix] = None
+        self.counts = None                  # global row count of the slots train / val / test / other
+        self.train_set = 0
+        self.split_sums = None              # eight floats, allocated with the first split-aware call
+        self._planar = False                # layout of split_sums after the last call, see _split_call
+
+    def set_splits(self, S: Optional[dn_matrix], counts=None, train_set: int = 0) -> None:
+        """S: int32 [n x 1] on the device, the set of every row of the logits this layer sees (None switches the
+        splits off); counts: the GLOBAL number of rows per slot (train, val, test, other) -- counted here from S when
+        None, which is right on one GPU only; train_set: the set the gradient and the reported pair belong to."""
+        if S is None:
+            self.S, self.counts = None, None
+            return
+        if train_set not in ops.TRAIN_SETS:
+            raise ValueError(f"train_set must be one of {ops.TRAIN_SETS}, got {train_set!r}")
+        if not isinstance(S, dn_matrix) or S.t.dtype != _torch().int32 or S.m() != 1:
+            raise ValueError("the sets must be an int32 dn_matrix of n rows and one column")
+        if counts is None:
+            counts = split_counts(S.numpy())
+        counts = [int(c) for c in counts]
+        if len(counts) != 4 or min(counts) < 0:
+            raise ValueError("counts: the global number of rows of train, val, test and other")
+        if counts[train_set] == 0:
+            raise ValueError(f"no row belongs to set {train_set}: nothing to train on")
+        self.S, self.counts, self.train_set = S, counts, int(train_set)
 
     def __call__(self, ctx: context, H: dn_matrix, Y: dn_matrix, n_global: Optional[int] = None,
                  sync: bool = True):
@@ -403,6 +433,15 @@ class softmax_cross_entropy_loss:
         if n_global is None:
             n_global = Y.n()
         ctx.record(n + "0_loss-layer", 0)
+        if self.S is not None:
+            self._split_call(ctx, H, Y)
+            ctx.record(n + "1_loss-layer", 0)
+            ctx.register_timer(n + "loss-layer", n + "0_loss-layer", n + "1_loss-layer")
+            self._n = H.n()
+            if not sync:
+                return None
+            ctx.sync()
+            return self.read(ctx)
         if self.sums is None:
             self.sums = host_scalars(2) if self.host_sums else torch.empty(2, dtype=torch.float32, device=ctx.device)
         if self.fused and 1 <= H.m() <= ops.XENT_FUSED_MAX_CLASSES:
@@ -437,14 +476,101 @@ class softmax_cross_entropy_loss:
         ctx.sync()
         return self.read(ctx)
 
+    def _split_call(self, ctx: context, H: dn_matrix, Y: dn_matrix) -> None:
+        """the layer with splits on: the same two routes as __call__, split-aware"""
+        torch = _torch()
+        if self.S.n() != H.n():
+            raise ValueError(f"the sets have {self.S.n()} rows, the logits {H.n()}")
+        if self.split_sums is None:
+            self.split_sums = (host_scalars(8) if self.host_sums
+                               else torch.empty(8, dtype=torch.float32, device=ctx.device))
+        n_train = self.counts[self.train_set]
+        if self.fused and 1 <= H.m() <= ops.XENT_FUSED_MAX_CLASSES:
+            if self.copy:
+                if self.G is None or self.G.shape() != H.shape():
+                    self.G = dn_matrix(H.n(), H.m())
+            else:
+                self.G = H
+            ctx.lib.mggcn_memset_zero(self.split_sums.data_ptr(), 32, ctx.stream(0))
+            ops.softmax_xent_split(ctx, H, Y, self.S, self.train_set, 1.0 / n_train, self.split_sums, out=self.G)
+            self._planar = False            # (loss, correct) pairs, slot by slot
+            return
+        O = self.softmax_layer(ctx, H)
+        if self.P is None:
+            self.P = dn_matrix(Y.shape(), dtype=np.int32)
+        ops.max_row_indices(ctx, O, self.P)
+        if self.L is None:
+            self.L = dn_matrix(Y.shape())
+        ops.index_log_rows(ctx, O, Y, self.L)
+        self.G = O
+        ops.add_indexed_rows(ctx, self.G, Y, -1.0)
+        ops.scale_mat(ctx, self.G, float(np.float32(1) / np.float32(n_train)))
+        ops.select_rows_by_set(ctx, self.G, self.S, self.train_set)
+        if self.T is None:
+            self.T = dn_matrix(Y.shape())
+        ops.is_equal(ctx, Y, self.P, self.T)
+        ops.abssum_by_set(ctx, self.L, self.S, self.split_sums[0:4])
+        ops.abssum_by_set(ctx, self.T, self.S, self.split_sums[4:8])
+        self._planar = True                 # the four loss sums, then the four correct counts
+
+    def split_sums_host(self, sums=None) -> np.ndarray:
+        """the eight sums of the last call as (loss sum, correct count) pairs of train / val / test / other; ``sums``:
+        eight floats in the layout of the last call (the distributed wrapper passes the all-reduced ones)"""
+        if sums is None:
+            sums = self.split_sums.numpy() if self.host_sums else self.split_sums.cpu().numpy()
+        s = np.asarray(sums, dtype=np.float32).reshape(-1)[:8]
+        return s.reshape(2, 4).T.reshape(-1).copy() if self._planar else s.copy()
+
+    def split_metrics(self, sums=None):
+        """{"train": (loss, acc), "val": ..., "test": ..., "other": ..., "counts": {...}} of the last call (after the
+        caller's synchronisation); a split without a row reports nan"""
+        s = self.split_sums_host(sums)
+        out = {}
+        for k, name in enumerate(ops.SPLIT_NAMES):
+            c = self.counts[k]
+            out[name] = ((float(s[2 * k] / np.float32(c)), float(s[2 * k + 1] / np.float32(c))) if c
+                         else (float("nan"), float("nan")))
+        out["counts"] = dict(zip(ops.SPLIT_NAMES, self.counts))
+        return out
+
     def read(self, ctx: context):
         """(loss, acc) of the last call; the caller has synchronised (train_step reads after the
         whole epoch is done instead of blocking between forward and backward)."""
+        if self.S is not None:
+            return self.split_metrics()[ops.SPLIT_NAMES[self.train_set]]
         s = self.sums.numpy() if self.host_sums else self.sums.cpu().numpy()
         return float(np.float32(s[0]) / np.float32(self._n)), float(np.float32(s[1]) / np.float32(self._n))
 
     def backward(self) -> dn_matrix:
         return self.G
+
+
+def split_counts(S: np.ndarray) -> List[int]:
+    """rows per slot (train, val, test, other) of a host array of set values"""
+    s = np.asarray(S).reshape(-1)
+    c = [int((s == k).sum()) for k in range(3)]
+    return c + [int(s.size) - sum(c)]
+
+
+def check_splits(S, n: int, train_set: int, counts=None):
+    """Option checking of set_splits, before any device work: S is a numpy array of n integers or an int32 dn_matrix of
+    n x 1, train_set one of 0 / 1 / 2, and at least one row trains (``counts``: the global counts of a row partition;
+    None counts S).  Returns (the sets as a host int32 [n x 1] array, the counts)."""
+    if train_set not in ops.TRAIN_SETS:
+        raise ValueError(f"train_set must be one of {ops.TRAIN_SETS}, got {train_set!r}")
+    if isinstance(S, dn_matrix):
+        if S.t.dtype != _torch().int32 or S.shape() != (n, 1):
+            raise ValueError(f"the sets must be an int32 dn_matrix of {n} x 1, got {S.t.dtype} of {S.shape()}")
+        host = S.numpy()
+    else:
+        host = np.asarray(S)
+        if host.dtype.kind not in "iu" or host.size != n or host.ndim > 2 or (host.ndim == 2 and host.shape[1] != 1):
+            raise ValueError(f"the sets must be {n} integers, got {host.dtype} of shape {host.shape}")
+        host = np.ascontiguousarray(host.reshape(n, 1).astype(np.int32))
+    counts = split_counts(host) if counts is None else [int(c) for c in counts]
+    if counts[train_set] == 0:
+        raise ValueError(f"no vertex belongs to set {train_set}: nothing to train on")
+    return host, counts
 
 
 def link_fused_backward(layers, fused: bool) -> None:
@@ -534,6 +660,26 @@ class gcn:
         stochastic = bool(np.all(np.diff(fwd.indptr.astype(np.int64)) > 0)) if fwd.n() else True
         l0.hoist_input = bool(on) and l0.gemm_first() and not l0.residual_layer and stochastic
         l0._AX = l0._AX_key = None                  # (re-)enabling recomputes the product: the way to pick up an in-place change of X
+
+    def set_splits(self, S, train_set: int = 0) -> None:
+        """Train on one split (opt-in; the reference loads sets.bin and ignores it, src/main.cpp:85).  S: the set of every
+        vertex (0 train / 1 validation / 2 test, anything else belongs to no split) as a numpy array of n integers or an
+        int32 dn_matrix of n rows; None restores the loss over all vertices.  From here on train_forward / train_step
+        return the loss and accuracy of ``train_set`` and split_metrics() reports every split of the last epoch."""
+        if S is None:
+            self.loss_layer.set_splits(None)
+            return
+        host, counts = check_splits(S, self.A.n(), train_set)
+        if not isinstance(S, dn_matrix):
+            S = dn_matrix.from_numpy(host)
+        self.loss_layer.set_splits(S, counts, train_set)
+
+    def split_metrics(self):
+        """every split's (loss, acc) of the last epoch, see softmax_cross_entropy_loss.split_metrics; call after
+        train_forward / train_step (they synchronise)"""
+        if self.loss_layer.S is None:
+            raise ValueError("split_metrics() needs set_splits(S) first")
+        return self.loss_layer.split_metrics()
 
     def __call__(self, ctx: context, H: dn_matrix) -> dn_matrix:
         if self._plan_wants:                          # first call: the context (device) is known now

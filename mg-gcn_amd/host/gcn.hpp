@@ -10,7 +10,9 @@
 // one-pass loss and one-launch Adam kernels; fused = false replays the reference's launches.
 #pragma once
 
+#include <array>
 #include <cmath>
+#include <limits>
 #include <numeric>
 #include <optional>
 #include <string>
@@ -545,6 +547,41 @@ public:
     }
 };
 
+// Split-aware training (opt-in; the reference loads sets.bin and ignores it, src/main.cpp:85): S holds a set per row of
+// the logits (0 train / 1 validation / 2 test, anything else in no split), the loss is taken over the n_train rows of
+// train_set, every other row gets a zero gradient row, and a (loss sum, correct count) pair is kept per slot.
+template <typename x_t>
+struct loss_split {
+    dn_matrix<x_t> S;            // this GPU's rows
+    int train_set;
+    std::size_t n_train;         // GLOBAL number of rows in train_set
+};
+
+inline std::size_t split_slot(std::int64_t s) { return s >= 0 && s <= 2 ? (std::size_t)s : 3; }
+
+// rows per slot (train, val, test, other) of a host copy of the sets
+template <typename x_t>
+std::array<std::size_t, 4> split_counts(const std::vector<x_t> &sets) {
+    std::array<std::size_t, 4> c{0, 0, 0, 0};
+    for (const auto s : sets) c[split_slot((std::int64_t)s)]++;
+    return c;
+}
+
+inline void check_train_set(int train_set, std::size_t n_train) {
+    if (train_set < 0 || train_set > 2) throw std::invalid_argument("train_set must be 0 (train), 1 (validation) or 2 (test)");
+    if (n_train == 0) throw std::invalid_argument("no vertex belongs to the training set: nothing to train on");
+}
+
+// (loss, acc) per slot from the eight sums and the four counts; a split without a row reports nan
+template <typename r_t>
+std::array<std::pair<r_t, r_t>, 4> split_metrics_of(const std::array<r_t, 8> &s, const std::array<std::size_t, 4> &counts) {
+    std::array<std::pair<r_t, r_t>, 4> out;
+    for (std::size_t k = 0; k < 4; k++)
+        out[k] = counts[k] ? std::make_pair(s[2 * k] / (r_t)counts[k], s[2 * k + 1] / (r_t)counts[k])
+                           : std::make_pair(std::numeric_limits<r_t>::quiet_NaN(), std::numeric_limits<r_t>::quiet_NaN());
+    return out;
+}
+
 // One GPU's share of the loss: enqueues everything, leaves {sum|log p_y|, #correct} in
 // sums_device; the caller synchronises and reads (reference :785-818 / :890-930).
 template <typename r_t, typename x_t>
@@ -553,15 +590,28 @@ class loss_kernels {
     dn_matrix<r_t> G, L, T;
     dn_matrix<x_t> P;
     const bool copy, fused;
-    mggcn::device_ptr<r_t> sums_;
+    mggcn::device_ptr<r_t> sums_, split_sums_;
+    bool planar_ = false;        // split_sums_ of the last call: four loss sums then four counts (the unfused chain)
 
 public:
     loss_kernels(bool copy, bool fused) : softmax_layer(copy), copy(copy), fused(fused) {}
     r_t *sums() const { return sums_.get(); }
     auto gradient() const { return G; }
+    // the eight sums of the last split-aware call as (loss sum, correct count) pairs of train / val / test / other
+    std::array<r_t, 8> split_sums() const {
+        std::array<r_t, 8> out;
+        const r_t *s = split_sums_.get();                        // mapped pinned host memory
+        for (std::size_t k = 0; k < 4; k++) {
+            out[2 * k] = planar_ ? s[k] : s[2 * k];
+            out[2 * k + 1] = planar_ ? s[4 + k] : s[2 * k + 1];
+        }
+        return out;
+    }
 
-    void enqueue(context ctx, dn_matrix<r_t> H, dn_matrix<x_t> Y, std::size_t n_global) {
+    void enqueue(context ctx, dn_matrix<r_t> H, dn_matrix<x_t> Y, std::size_t n_global,
+                 std::optional<loss_split<x_t>> split = std::nullopt) {
         ctx.set();
+        if (split) { enqueue_split(ctx, H, Y, *split); return; }
         if (!sums_) sums_ = mggcn::host_malloc<r_t>(2);          // written by the kernels, read by the host after its sync
         if (fused) {
             if (copy) {                       // reference: copy, then in place (:653-656); here the pass writes elsewhere
@@ -586,6 +636,39 @@ public:
         abssum(ctx, L, sums_.get());
         abssum(ctx, T, sums_.get() + 1);
     }
+
+private:
+    // the same two routes, split-aware
+    void enqueue_split(context ctx, dn_matrix<r_t> H, dn_matrix<x_t> Y, const loss_split<x_t> &sp) {
+        check_train_set(sp.train_set, sp.n_train);
+        if (!split_sums_) split_sums_ = mggcn::host_malloc<r_t>(8);
+        const r_t scale = (r_t)1 / (r_t)sp.n_train;
+        if (fused && H.m() >= 1 && H.m() <= 1024) {
+            if (copy) {
+                if (!G.buffer() || G.shape() != H.shape()) G = dn_matrix<r_t>(H.n(), H.m());
+            } else {
+                G = H;
+            }
+            mggcn_memset_zero(split_sums_.get(), 8 * sizeof(r_t), ctx.stream(0));
+            softmax_xent_split(ctx, H, G, Y, sp.S, sp.train_set, scale, split_sums_.get());
+            planar_ = false;
+            return;
+        }
+        auto O = softmax_layer(ctx, H);
+        if (!P.buffer()) P = dn_matrix<x_t>(Y.shape());
+        max_row_indices(ctx, O, P);
+        if (!L.buffer()) L = dn_matrix<r_t>(Y.shape());
+        index_log_rows(ctx, O, Y, L);
+        G = O;
+        add_indexed_rows(ctx, G, Y, (r_t)-1);
+        scale_mat(ctx, G, scale);
+        select_rows_by_set(ctx, G, sp.S, sp.train_set);
+        if (!T.buffer()) T = dn_matrix<r_t>(Y.shape());
+        is_equal(ctx, Y, P, T);
+        abssum_by_set(ctx, L, sp.S, split_sums_.get());
+        abssum_by_set(ctx, T, sp.S, split_sums_.get() + 4);
+        planar_ = true;
+    }
 };
 
 template <typename r_t, typename x_t>
@@ -596,16 +679,38 @@ class softmax_cross_entropy_loss {
 public:
     softmax_cross_entropy_loss(std::string name, bool copy = true, bool fused = false) : name(name), k(copy, fused) {}
 
+    // train on the rows with S == train_set (see loss_split); counted here, on the host.  clear_splits() turns it off.
+    void set_splits(dn_matrix<x_t> S, int train_set = 0) {
+        if (train_set < 0 || train_set > 2) check_train_set(train_set, 1);
+        mggcn_require(S.m() == 1, "set_splits: the sets must be n x 1");
+        const auto c = split_counts(S.to_host());
+        check_train_set(train_set, c[(std::size_t)train_set]);
+        counts_ = c;
+        split_ = loss_split<x_t>{S, train_set, c[(std::size_t)train_set]};
+    }
+    void clear_splits() { split_.reset(); }
+    bool has_splits() const { return split_.has_value(); }
+    // the eight sums ((loss sum, correct count) of train / val / test / other) and the four row counts of the last call
+    auto split_sums() const { return k.split_sums(); }
+    auto split_counts_global() const { return counts_; }
+    auto split_metrics() const { return split_metrics_of<r_t>(k.split_sums(), counts_); }
+
     auto operator()(context ctx, dn_matrix<r_t> H, dn_matrix<x_t> Y) {
+        if (split_) mggcn_require(split_->S.n() == H.n(), "the sets and the logits differ in their row count");
         ctx.record(name + "0_loss-layer", 0);
-        k.enqueue(ctx, H, Y, Y.n());
+        k.enqueue(ctx, H, Y, Y.n(), split_);
         ctx.record(name + "1_loss-layer", 0);
         ctx.register_timer(name + "loss-layer", name + "0_loss-layer", name + "1_loss-layer");
         ctx.sync();
+        if (split_) return split_metrics()[(std::size_t)split_->train_set];          // the training split's pair
         const r_t *s = k.sums();                                 // mapped pinned host memory
         return std::make_pair(s[0] / H.n(), s[1] / H.n());
     }
     auto backward() { return k.gradient(); }
+
+private:
+    std::optional<loss_split<x_t>> split_;
+    std::array<std::size_t, 4> counts_{0, 0, 0, 0};
 };
 
 template <typename r_t, typename x_t>
@@ -618,9 +723,46 @@ class dist_row_softmax_cross_entropy_loss {
 public:
     dist_row_softmax_cross_entropy_loss(std::string name, bool copy = true, bool fused = false) : name(name), copy(copy), fused(fused) {}
 
+    // train on the rows with S == train_set: the global counts are summed here, on the host, over the P shards (as the
+    // scalars are below); a GPU without a training row is fine
+    void set_splits(dist_context ctx, dist_row_dn_matrix<x_t> Sd, int train_set = 0) {
+        if (train_set < 0 || train_set > 2) check_train_set(train_set, 1);
+        std::array<std::size_t, 4> c{0, 0, 0, 0};
+        for (std::size_t i = 0; i < ctx.size(); i++) {
+            const auto ci = split_counts(Sd[i].to_host());
+            for (std::size_t k = 0; k < 4; k++) c[k] += ci[k];
+        }
+        check_train_set(train_set, c[(std::size_t)train_set]);
+        counts_ = c;
+        Sd_ = Sd;
+        train_set_ = train_set;
+        on_ = true;
+    }
+    void clear_splits() { on_ = false; }
+    bool has_splits() const { return on_; }
+    auto split_sums() const { return split_sums_; }              // global, of the last call
+    auto split_counts_global() const { return counts_; }
+    auto split_metrics() const { return split_metrics_of<r_t>(split_sums_, counts_); }
+
     auto operator()(dist_context ctx, dist_row_dn_matrix<r_t> H, dist_row_dn_matrix<x_t> Y) {
         while (ks.size() < ctx.size()) ks.push_back(std::make_shared<loss_kernels<r_t, x_t>>(copy, fused));
         ctx.record(name + "0_loss-layer", 0);
+        if (on_) {
+            if (copy) throw std::invalid_argument("dist loss with copy = true is not used by the reference CLI");
+            for (std::size_t i = 0; i < ctx.size(); i++)         // S's handle is captured by value, like the other matrices
+                ctx.on(i, [k = ks[i], c = ctx[i], h = H[i], y = Y[i], n = Y.n(),
+                           sp = loss_split<x_t>{(*Sd_)[i], train_set_, counts_[(std::size_t)train_set_]}] { k->enqueue(c, h, y, n, sp); });
+            ctx.record(name + "1_loss-layer", 0);
+            ctx.register_timer(name + "loss-layer", name + "0_loss-layer", name + "1_loss-layer");
+            ctx.sync();
+            split_sums_.fill(0);
+            for (std::size_t i = 0; i < ctx.size(); i++) {      // host sum of the per-GPU sums, in GPU order
+                const auto s = ks[i]->split_sums();
+                for (std::size_t k = 0; k < 8; k++) split_sums_[k] += s[k];
+            }
+            G = H;
+            return split_metrics()[(std::size_t)train_set_];
+        }
         for (std::size_t i = 0; i < ctx.size(); i++)                                               // global n (reference :908)
             ctx.on(i, [k = ks[i], c = ctx[i], h = H[i], y = Y[i], n = Y.n()] { k->enqueue(c, h, y, n); });
         ctx.record(name + "1_loss-layer", 0);
@@ -637,6 +779,13 @@ public:
         return std::make_pair(loss / H.n(), acc / H.n());
     }
     auto backward() { return G; }
+
+private:
+    bool on_ = false;
+    int train_set_ = 0;
+    std::optional<dist_row_dn_matrix<x_t>> Sd_;
+    std::array<std::size_t, 4> counts_{0, 0, 0, 0};
+    std::array<r_t, 8> split_sums_{};
 };
 
 // fused backward: layer i+1's G_out GEMM applies layer i's leaky_relu' -- possible when layer i+1 is GEMM-first
@@ -714,6 +863,14 @@ public:
         H = operator()(ctx, H);
         return loss_layer(ctx, H, Y);
     }
+    // Train on one split (opt-in; the reference loads sets.bin and ignores it, src/main.cpp:85): S[i] is vertex i's set
+    // (0 train / 1 validation / 2 test, anything else in no split).  From here on train_forward returns the loss and
+    // accuracy of train_set; split_metrics() has every split's pair of the last epoch (train, val, test, other) from the
+    // same pass.  std::invalid_argument for a bad train_set or when no vertex trains, before any device work.
+    void set_splits(dn_matrix<std::int32_t> S, int train_set = 0) { loss_layer.set_splits(S, train_set); }
+    void clear_splits() { loss_layer.clear_splits(); }
+    auto split_metrics() const { return loss_layer.split_metrics(); }
+    auto split_counts() const { return loss_layer.split_counts_global(); }
     void backward(const context ctx) {
         auto G = loss_layer.backward();
         for (auto l = layers_.rbegin(); l != layers_.rend(); l++) G = l->backward(ctx, G);
@@ -786,6 +943,11 @@ public:
         H = operator()(ctx, H);
         return loss_layer(ctx, H, Y);
     }
+    // see gcn::set_splits; Sd: the sets, sharded like the labels
+    void set_splits(const dist_context ctx, idn_t Sd, int train_set = 0) { loss_layer.set_splits(ctx, Sd, train_set); }
+    void clear_splits() { loss_layer.clear_splits(); }
+    auto split_metrics() const { return loss_layer.split_metrics(); }
+    auto split_counts() const { return loss_layer.split_counts_global(); }
     void backward(const dist_context ctx) {
         auto G = loss_layer.backward();
         for (auto l = layers_.rbegin(); l != layers_.rend(); l++) G = l->backward(ctx, G);

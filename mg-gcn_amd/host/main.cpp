@@ -14,7 +14,10 @@
 // MGGCN_OVERSUBSCRIBE=1 lets -P exceed the visible GPUs (ranks wrap over them, peer-copy transport);
 // MGGCN_HOIST_FIRST_AGGREGATION=1 (single GPU) pre-computes the first layer's A.X once (6 SpMMs per epoch: not the
 // reference's epoch, same results at 1e-4); MGGCN_AGG_DTYPE=bf16 (single GPU, not -R 1) stores the SpMMs' gathered
-// operand in bf16 (f32 or unset: the reference's fp32); MGGCN_TIMING=1 prints the start-up stages.
+// operand in bf16 (f32 or unset: the reference's fp32); MGGCN_TRAIN_SET=0|1|2 trains on that split of sets.bin (0 train /
+// 1 validation / 2 test; unset: the reference's loss over all vertices): the epoch line reports the training split and
+// a second line, "[mggcn splits] <e> train <loss> <acc> val <loss> <acc> test <loss> <acc>", every split;
+// MGGCN_TIMING=1 prints the start-up stages.
 #include <unistd.h>
 
 #include <chrono>
@@ -49,6 +52,9 @@ static int help_() {
                  "    -R : enable the 1D row partition (required for -P > 1)\n"
                  "    -E : number of epochs (default 20)\n"
                  "    -S : disable communication/computation overlap\n"
+                 "Environment:\n"
+                 "    MGGCN_TRAIN_SET=0|1|2 : train on that split of sets.bin (0 train, 1 validation, 2 test) and report\n"
+                 "                            every split per epoch; unset: loss and accuracy over all vertices\n"
                  "Arguments:\n"
                  "    train <dir> <k> <h1> ... <hk> : dataset directory, number of hidden layers and their widths\n";
     return EXIT_SUCCESS;
@@ -76,6 +82,13 @@ struct stage_timer {
         last = now;
     }
 };
+
+// "[mggcn splits] <e> train <loss> <acc> val <loss> <acc> test <loss> <acc>": every split's pair of the epoch
+template <typename metrics_t>
+static void print_splits(std::size_t e, const metrics_t &m) {
+    std::cerr << "[mggcn splits] " << e << " train " << m[0].first << ' ' << m[0].second << " val " << m[1].first << ' '
+              << m[1].second << " test " << m[2].first << ' ' << m[2].second << std::endl;
+}
 
 static bool env_is(const char *name, const char *value) {
     const char *s = std::getenv(name);
@@ -108,6 +121,12 @@ int main_(int argc, char **argv) {
     const agg_dtype agg = agg_dtype_from_string(agg_env ? agg_env : "");
     if (agg != agg_dtype::f32 && (P > 1 || row_partition))          // the distributed classes have no bf16 aggregation
         throw arg_error("MGGCN_AGG_DTYPE=bf16 is single-GPU only (not with -P > 1 or -R 1)");
+    int train_set = -1;                                             // MGGCN_TRAIN_SET unset: the loss over all vertices
+    if (const char *ts = std::getenv("MGGCN_TRAIN_SET")) {
+        const std::string v = ts;
+        if (v != "0" && v != "1" && v != "2") throw arg_error("MGGCN_TRAIN_SET must be 0 (train), 1 (validation) or 2 (test), not '" + v + "'");
+        train_set = v[0] - '0';
+    }
 
     while (optind < argc && argv[optind] != nullptr) {
         const std::string command = argv[optind++];
@@ -123,8 +142,7 @@ int main_(int argc, char **argv) {
         csr_matrix<x_t, v_t, r_t> A(dir / "graph.bin");
         dn_matrix<r_t> X(dir / "features.bin");
         dn_matrix<std::int32_t> Y(dir / "labels.bin");
-        dn_matrix<std::int32_t> S(dir / "sets.bin");               // loaded, never used (reference :85)
-        (void)S;
+        dn_matrix<std::int32_t> S(dir / "sets.bin");               // loaded, never used (reference :85) -- unless MGGCN_TRAIN_SET
         stage("load-files");
         std::cerr << A.n() << ' ' << A.nnz() << std::endl;
         const auto labels = Y.to_host();
@@ -156,6 +174,7 @@ int main_(int argc, char **argv) {
             auto ctx = context(0);
             gcn<x_t, v_t, r_t> G(A, sizes, false, fused, agg);
             if (env_is("MGGCN_HOIST_FIRST_AGGREGATION", "1")) G.set_hoist_first_aggregation(true);   // optional 6-SpMM epoch
+            if (train_set >= 0) G.set_splits(S, train_set);
             ctx.sync();
             stage("model (normalize, transpose, layers)");
             ctx.record("training-start", 0);
@@ -174,6 +193,7 @@ int main_(int argc, char **argv) {
                 ctx.sync();
                 const auto duration = std::chrono::duration<double>{std::chrono::system_clock::now() - start}.count();
                 std::cerr << e << ' ' << loss << ' ' << acc << ' ' << duration << std::endl;
+                if (train_set >= 0) print_splits(e, G.split_metrics());
                 if (e == 0) stage("epoch 0 (SpMM plans built on first use)");
                 ctx.dump_timers(of, std::to_string(e) + "_0_");
             }
@@ -193,10 +213,19 @@ int main_(int argc, char **argv) {
             stage("block split (A, A_T)");
             dist_gcn<true, x_t, v_t, r_t> G(ctx, Ad, A_Td, sizes, false, fused, mode);
             dist_row_dn_matrix<r_t> Xd(ctx, X);
+            if (train_set >= 0) G.set_splits(ctx, dist_row_dn_matrix<std::int32_t>(ctx, S), train_set);
             ctx.sync();
             stage("model + shards");
             ctx.record("training-start", 0);
             for (std::size_t e = 0; e < num_epochs; e++) {
+                if (const char *dd = std::getenv("MGGCN_DUMP_WEIGHTS")) {     // GPU 0's replica: they are all the same
+                    ctx.sync();
+                    std::filesystem::create_directories(dd);
+                    for (std::size_t l = 0; l < G.layers().size(); l++) {
+                        dump_dense(std::filesystem::path(dd) / ("e" + std::to_string(e) + "_W" + std::to_string(l) + ".bin"), G.layers()[l].W()[0]);
+                        dump_dense(std::filesystem::path(dd) / ("e" + std::to_string(e) + "_b" + std::to_string(l) + ".bin"), G.layers()[l].b()[0]);
+                    }
+                }
                 const auto start = std::chrono::system_clock::now();
                 const double waited = ctx.device_wait_seconds();
                 auto [loss, acc] = G.train_forward(ctx, Xd, Yd);
@@ -205,6 +234,7 @@ int main_(int argc, char **argv) {
                 ctx.sync();
                 const auto duration = std::chrono::duration<double>{std::chrono::system_clock::now() - start}.count();
                 std::cerr << e << ' ' << loss << ' ' << acc << ' ' << duration << "\n";
+                if (train_set >= 0) print_splits(e, G.split_metrics());
                 // how much of the epoch the host needed to ISSUE it (wall time minus the time it sat waiting for the devices)
                 if (stage.on) std::cerr << "[mggcn timing] epoch " << e << " host-issue-ms " << (duration - (ctx.device_wait_seconds() - waited)) * 1e3 << std::endl;
                 if (e == 0) stage("epoch 0 (exchange forms + SpMM plans built on first use)");

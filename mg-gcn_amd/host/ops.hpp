@@ -547,6 +547,48 @@ void softmax_xent_fused(const context ctx, const dn_matrix<r_t> H, const dn_matr
     mggcn_softmax_xent_fused_from_f32(ctx.stream(0), H.buffer(), G.buffer(), Y.buffer(), H.n(), H.m(), grad_scale, sums_device);
 }
 
+// Split-aware loss (include/mggcn.h: mggcn_softmax_xent_split_from_f32, mggcn_select_rows_by_set_f32,
+// mggcn_abssum_by_set_f32): S holds a set per row (sets.bin: 0 train / 1 validation / 2 test), rows outside train_set get a
+// zero gradient row, sums_device holds a (loss sum, correct count) pair per slot train / val / test / other.  Added to ABI
+// version 1 later, like the bf16 entries above: weak references, checked when a program asks for splits.
+#pragma weak mggcn_softmax_xent_split_from_f32
+#pragma weak mggcn_select_rows_by_set_f32
+#pragma weak mggcn_abssum_by_set_f32
+inline void require_split_loss() {
+    mggcn_require(&mggcn_softmax_xent_split_from_f32 != nullptr && &mggcn_select_rows_by_set_f32 != nullptr &&
+                      &mggcn_abssum_by_set_f32 != nullptr,
+                  "this libmggcn_hip.so has no split-aware loss (mggcn_softmax_xent_split_from_f32)");
+}
+
+template <typename r_t, typename x_t>
+void softmax_xent_split(const context ctx, const dn_matrix<r_t> H, const dn_matrix<r_t> G, const dn_matrix<x_t> Y,
+                        const dn_matrix<x_t> S, int train_set, r_t grad_scale, r_t *sums_device) {
+    require_split_loss();
+    mggcn_require(H.n() == Y.n() && Y.m() == 1, "softmax_xent_split: labels must be n x 1");
+    mggcn_require(H.n() == S.n() && S.m() == 1, "softmax_xent_split: sets must be n x 1");
+    mggcn_require(G.n() == H.n() && G.m() == H.m(), "softmax_xent_split: gradient matrix must have the logits' shape");
+    mggcn_require(train_set >= 0 && train_set <= 2, "softmax_xent_split: train_set must be 0, 1 or 2");
+    ctx.set();
+    mggcn_softmax_xent_split_from_f32(ctx.stream(0), H.buffer(), G.buffer(), Y.buffer(), S.buffer(), H.n(), H.m(), train_set,
+                                      grad_scale, sums_device);
+}
+// mat[i, :] = +0 where S[i] != set
+template <typename r_t, typename x_t>
+void select_rows_by_set(const context ctx, const dn_matrix<r_t> mat, const dn_matrix<x_t> S, int set) {
+    require_split_loss();
+    mggcn_require(mat.n() == S.n() && S.m() == 1, "select_rows_by_set: sets must be n x 1");
+    ctx.set();
+    mggcn_select_rows_by_set_f32(ctx.stream(0), mat.buffer(), S.buffer(), set, mat.size(), mat.m());
+}
+// result_device[k] = sum of |x[i]| over the rows of slot k (four floats; enqueue-only like abssum)
+template <typename r_t, typename x_t>
+void abssum_by_set(const context ctx, const dn_matrix<r_t> x, const dn_matrix<x_t> S, r_t *result_device) {
+    require_split_loss();
+    mggcn_require(x.m() == 1 && x.n() == S.n() && S.m() == 1, "abssum_by_set: x and the sets must be n x 1");
+    ctx.set();
+    mggcn_abssum_by_set_f32(ctx.stream(0), x.buffer(), S.buffer(), x.n(), result_device);
+}
+
 // dist_context forms: per-GPU loops, as in the reference's "template<dn_t>" overloads
 template <typename r_t, template <typename> class dn_t>
 void leaky_relu_forward(const dist_context ctx, const dn_t<r_t> in, const dn_t<r_t> out, r_t a = 0.01) {

@@ -146,6 +146,9 @@ class host_scalars:
             return host_scalars(b - a, _base=self._owner, _offset=self._offset + a)
         raise TypeError("host_scalars supports slices only")
 
+    def numel(self) -> int:
+        return self._n
+
     def numpy(self) -> np.ndarray:
         """a COPY of the current values (call after synchronising the stream that writes them)"""
         return np.array(self._view[self._offset:self._offset + self._n], dtype=np.float32)

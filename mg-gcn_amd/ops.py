@@ -352,6 +352,48 @@ def softmax_xent_fused(ctx: context, H: dn_matrix, Y: dn_matrix, grad_scale: flo
                                               grad_scale, sums_device.data_ptr())
 
 
+TRAIN_SETS = (0, 1, 2)              # sets.bin: 0 train / 1 validation / 2 test; any other value is "other" (slot 3)
+SPLIT_NAMES = ("train", "val", "test", "other")
+
+
+def _req_sets(S: dn_matrix, n: int, what: str) -> None:
+    _req(isinstance(S, dn_matrix) and S.t.dtype == __import__("torch").int32, f"{what}: the sets must be an int32 dn_matrix")
+    _req(S.n() == n and S.m() == 1, f"{what}: the sets must be {n} x 1, got {S.n()} x {S.m()}")
+
+
+def softmax_xent_split(ctx: context, H: dn_matrix, Y: dn_matrix, S: dn_matrix, train_set: int, grad_scale: float,
+                       sums_device, out: Optional[dn_matrix] = None) -> None:
+    """The split-aware fused loss (mggcn_softmax_xent_split_from_f32): rows with S != train_set get a zero gradient row;
+    sums_device holds eight floats, a (loss sum, correct count) pair per slot train / val / test / other, zeroed by the
+    caller.  The same width limit and the same check before the library as softmax_xent_fused."""
+    _req(H.n() == Y.n() and Y.m() == 1, "labels must be n x 1")
+    _req(1 <= H.m() <= XENT_FUSED_MAX_CLASSES, f"fused loss supports 1 <= m <= {XENT_FUSED_MAX_CLASSES} classes, got {H.m()}")
+    _req(train_set in TRAIN_SETS, f"train_set must be one of {TRAIN_SETS}, got {train_set!r}")
+    _req_sets(S, H.n(), "split-aware fused loss")
+    if out is None:
+        out = H
+    _req(out.n() == H.n() and out.m() == H.m(), "fused loss: gradient matrix must have the logits' shape")
+    _req(sums_device.numel() >= 8, "split-aware fused loss: sums must hold eight floats")
+    ctx.lib.mggcn_softmax_xent_split_from_f32(ctx.stream(0), H.buffer(), out.buffer(), Y.buffer(), S.buffer(), H.n(),
+                                              H.m(), int(train_set), grad_scale, sums_device.data_ptr())
+
+
+def select_rows_by_set(ctx: context, mat: dn_matrix, S: dn_matrix, set_: int) -> None:
+    """mat[i, :] = +0.0 where S[i] != set_ (mggcn_select_rows_by_set_f32)"""
+    _req(mat.m() >= 1, "row width must be positive")
+    _req_sets(S, mat.n(), "select_rows_by_set")
+    ctx.lib.mggcn_select_rows_by_set_f32(ctx.stream(0), mat.buffer(), S.buffer(), int(set_), mat.size(), mat.m())
+
+
+def abssum_by_set(ctx: context, x: dn_matrix, S: dn_matrix, result_device) -> None:
+    """result_device[k] = sum of |x[i]| over the rows of slot k (train / val / test / other): four floats, overwritten
+    (mggcn_abssum_by_set_f32); x is n x 1.  Enqueue-only, like abssum."""
+    _req(x.m() == 1, "abssum_by_set: x must be n x 1")
+    _req_sets(S, x.n(), "abssum_by_set")
+    _req(result_device.numel() >= 4, "abssum_by_set: the result must hold four floats")
+    ctx.lib.mggcn_abssum_by_set_f32(ctx.stream(0), x.buffer(), S.buffer(), x.n(), result_device.data_ptr())
+
+
 def adam_fused(ctx: context, param: dn_matrix, grad: dn_matrix, m: dn_matrix, v: dn_matrix, lr: float,
                beta1: float, beta2: float, weight_decay: float, c1: float, c2: float, eps: float) -> None:
     _req(param.shape() == grad.shape() == m.shape() == v.shape(), "shape mismatch")

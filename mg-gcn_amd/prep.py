@@ -26,6 +26,8 @@ def main(argv=None) -> int:
     ap.add_argument("--features", required=True, help=".npy float array [n, F]")
     ap.add_argument("--labels", required=True, help=".npy integer array [n]")
     ap.add_argument("--sets", default=None, help=".npy integer array [n]: 0 train, 1 validation, 2 test")
+    ap.add_argument("--pad-set", type=int, default=0, choices=(0, 1, 2, 3),
+                    help="set value of the padding vertices (default 0 = train, like the reference; 3 = in no split)")
     ap.add_argument("--out", required=True)
     ap.add_argument("-P", type=int, default=8, help="GPUs the files must be divisible for (padding granularity)")
     ap.add_argument("--seed", type=int, default=1, help="random symmetric permutation (0: none)")
@@ -45,7 +47,7 @@ def main(argv=None) -> int:
         kw["partitioner"] = "blocks"
     elif a.partition:
         kw["permutation"] = a.partition
-    out = ds.prepare_dataset(a.out, A, X, y, sets, P=a.P, seed=a.seed, **kw)
+    out = ds.prepare_dataset(a.out, A, X, y, sets, P=a.P, seed=a.seed, pad_set=a.pad_set, **kw)
     ip, ix, _, n, _ = ds.read_csr(os.path.join(out, "graph.bin"))
     vol = ds.comm_volume_matrix(ip, ix, a.P)
     print(out)
