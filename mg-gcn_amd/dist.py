@@ -44,8 +44,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, ops
-from .gcn import (adam_update_all, check_splits, layer_body, linear, link_fused_backward, softmax_cross_entropy_loss,
-                  split_counts)
+from .gcn import (adam_update_all, check_counts, check_sets, layer_body, linear, link_fused_backward,
+                  softmax_cross_entropy_loss, split_counts)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -596,10 +596,7 @@ def global_split_counts(comm: host_comm, local_sets: np.ndarray, train_set: int 
     """Rows per slot (train, val, test, other) over ALL ranks from every rank's rows of the sets: ONE host all-reduce of
     four integers; raises ValueError on every rank alike when nothing belongs to train_set.  Needs no GPU (host_comm)."""
     mine = np.asarray(split_counts(local_sets), dtype=np.int64)
-    counts = [int(c) for c in (comm.host_all_reduce(mine) if comm.P > 1 else mine)]
-    if counts[train_set] == 0:
-        raise ValueError(f"no vertex belongs to set {train_set}: nothing to train on")
-    return counts
+    return check_counts(comm.host_all_reduce(mine) if comm.P > 1 else mine, train_set)
 
 
 def load_rank_local(dctx: dist_context, dirname: str, chunks: Optional[int] = None):
@@ -773,11 +770,11 @@ class dist_row_linear(linear):
         # G_W and G_b live in ONE buffer: a single in-place all-reduce, no packing copies
         off_b = (in_ * out + 3) // 4 * 4                       # keep G_b 16-byte aligned
         # ... and eight more floats after G_b: the model's LAST layer carries the epoch's loss sums through its gradient
-        # all-reduce there (dist_gcn.train_step: no collective of their own) -- two, or the eight of a split-aware epoch
+        # all-reduce there (dist_gcn.train_step: no collective of their own) -- the front two, or all eight of a split-aware
+        # epoch
         off_t = (off_b + out + 3) // 4 * 4
         self.G_flat = torch.zeros(off_t + 8, dtype=torch.float32, device=self._dctx.ctx.device)
-        self.tail = self.G_flat[off_t:off_t + 2]
-        self.tail8 = self.G_flat[off_t:off_t + 8]
+        self.tail = self.G_flat[off_t:off_t + 8]
         torch.cuda.current_stream().synchronize()              # torch zeroes on ITS stream (the padding takes part in the sum);
                                                                # the kernels run on the context's
         return dn_matrix(in_, out, self.G_flat), dn_matrix(1, out, self.G_flat[off_b:])
@@ -875,24 +872,21 @@ class dist_row_softmax_cross_entropy_loss:
         """every split's global (loss, acc) of the last call that was read (read() / dist_gcn.train_step)"""
         return self.inner.split_metrics(self.global_sums if sums is None else sums)
 
-    def read(self, dctx: dist_context):
-        """global (loss, acc) of the last call; the caller has synchronised"""
-        dist = _dist()
-        H_n = self._n
-        mine = self.inner.sums if self.inner.S is None else self.inner.split_sums      # 2 floats, or the 8 of the splits
-        if dctx.backend == "nccl":
-            sums = mine.clone()
-            dist.all_reduce(sums, group=dctx.group)
-            sums = sums.cpu()
-        else:
-            sums = mine.detach().cpu()
-            dist.all_reduce(sums, group=dctx.group)
-        s = sums.numpy()
-        if self.inner.S is not None:
-            self.global_sums = s.copy()
-            return self.split_metrics()[ops.SPLIT_NAMES[self.inner.train_set]]
-        n = np.float32(H_n)
-        return float(np.float32(s[0]) / n), float(np.float32(s[1]) / n)
+    def read(self, dctx: dist_context, sums=None):
+        """global (loss, acc) of the last call; the caller has synchronised.  ``sums``: the global sums as host floats when
+        the caller has them already (dist_gcn.train_step); None all-reduces this rank's: the two, or the eight of the splits"""
+        if sums is None:
+            dist = _dist()
+            if dctx.backend == "nccl":
+                sums = self.inner.active_sums().clone()
+                dist.all_reduce(sums, group=dctx.group)
+                sums = sums.cpu()
+            else:
+                sums = self.inner.active_sums().detach().cpu()
+                dist.all_reduce(sums, group=dctx.group)
+            sums = sums.numpy()
+        self.global_sums = np.array(sums, dtype=np.float32)
+        return self.inner.read(dctx.ctx, self.global_sums, self._n)
 
     def backward(self) -> dist_row_dn_matrix:
         return self._G
@@ -934,8 +928,7 @@ class dist_gcn:
                                                self.bcast_buffer, self.bcast_buffer2, fused, mode))
         link_fused_backward(self.layers_, fused)
         self.fused, self._adam = fused, None
-        self._loss_host = None                                 # pinned host copy of the epoch's two global loss sums (train_step)
-        self._split_host = None                                # ... and of the eight of a split-aware epoch
+        self._loss_host = None                                 # pinned host copy of the epoch's global loss sums (train_step)
         # this rank's SpMM plans, built side by side before the first epoch (ops.prebuild_plans) instead of one by one
         # inside it: the diagonal block and the pieces of the schedule that runs, both matrices, both widths
         self._plan_wants = []
@@ -955,7 +948,7 @@ class dist_gcn:
             return
         local = Sd.local if isinstance(Sd, dist_row_dn_matrix) else Sd
         rows = self.layers_[-1].AHW.n()
-        host, mine = check_splits(local, rows, train_set, counts=[1, 1, 1, 1])       # shape, dtype and train_set only
+        host = check_sets(local, rows, train_set)
         counts = global_split_counts(dctx, host, train_set)
         if not isinstance(local, dn_matrix):
             local = dn_matrix.from_numpy(host, dctx.ctx.device)
@@ -1012,35 +1005,23 @@ class dist_gcn:
         torch = _torch()
         out = self(dctx, H)
         self.loss_layer(dctx, out, Y, sync=False)
-        # The two loss sums ride on the LAST layer's gradient all-reduce (four spare floats behind [G_W | G_b]) instead of a
-        # collective and a device-to-host copy of their own after the epoch's synchronisation: at P = 8 that turn-around was
-        # ~0.1 ms of idle GPU per 3.5-ms epoch.  (The reference adds its P managed scalars on the host, src/gcn.hpp:929.)
+        # The loss sums (two, or the eight of the splits) ride on the LAST layer's gradient all-reduce (eight spare floats
+        # behind [G_W | G_b]) instead of a collective and a device-to-host copy of their own after the epoch's synchronisation:
+        # at P = 8 that turn-around was ~0.1 ms of idle GPU per 3.5-ms epoch.  (The reference adds its P managed scalars on
+        # the host, src/gcn.hpp:929.)
         st = dctx.ctx.cuda_streams[0]
-        last = self.layers_[-1].lin
-        inner = self.loss_layer.inner
-        if inner.S is not None:                                # the eight sums of the splits travel the same way
-            with torch.cuda.stream(st):
-                last.tail8.copy_(inner.split_sums)
-            self.backward(dctx)
-            self.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
-            if self._split_host is None:
-                self._split_host = torch.empty(8, dtype=torch.float32, pin_memory=True)
-            with torch.cuda.stream(st):
-                self._split_host.copy_(last.tail8, non_blocking=True)
-            dctx.sync()
-            self.loss_layer.global_sums = self._split_host.numpy().copy()
-            return self.loss_layer.split_metrics()[ops.SPLIT_NAMES[inner.train_set]]
+        mine = self.loss_layer.inner.active_sums()
+        tail = self.layers_[-1].lin.tail[:mine.numel()]
         with torch.cuda.stream(st):
-            last.tail.copy_(self.loss_layer.inner.sums)
+            tail.copy_(mine)
         self.backward(dctx)                                    # ... -> finish_backward: the compute stream sees the summed buffers
         self.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
         if self._loss_host is None:
-            self._loss_host = torch.empty(2, dtype=torch.float32, pin_memory=True)
+            self._loss_host = torch.empty(8, dtype=torch.float32, pin_memory=True)
+        host = self._loss_host[:mine.numel()]
         with torch.cuda.stream(st):
-            self._loss_host.copy_(last.tail, non_blocking=True)
+            host.copy_(tail, non_blocking=True)
         dctx.sync()
-        s = self._loss_host.numpy()
-        n = np.float32(self.loss_layer._n)
-        return float(np.float32(s[0]) / n), float(np.float32(s[1]) / n)
+        return self.loss_layer.read(dctx, host.numpy())
 
     def layers(self): return self.layers_

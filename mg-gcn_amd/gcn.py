@@ -393,18 +393,19 @@ class softmax_cross_entropy_loss:
     from the same pass, which sums a (loss, correct) pair per slot train / val / test / other."""
 
     def __init__(self, name: str, copy: bool = True, fused: bool = False, host_sums: bool = True):
-        """host_sums: keep the two reported scalars in mapped pinned host memory (read without a device-to-host copy);
+        """host_sums: keep the reported sums in mapped pinned host memory (read without a device-to-host copy);
         False = a device tensor (the distributed wrapper all-reduces it over RCCL)"""
         self.name = name
         self.softmax_layer = softmax(copy)
         self.copy, self.fused, self.host_sums = copy, fused, host_sums
         self.G = self.L = self.P = self.T = None
-        self.sums = None
+        # one allocation of eight floats, made with the first call, and its front two:
+        self.split_sums = None              # the eight sums of the last split-aware call
+        self.sums = None                    # (loss sum, correct count) of the last call without splits
         self.S: Optional[dn_matrix] = None
         self.counts = None                  # global row count of the slots train / val / test / other
         self.train_set = 0
-        self.split_sums = None              # eight floats, allocated with the first split-aware call
-        self._planar = False                # layout of split_sums after the last call, see _split_call
+        self._planar = False                # layout of split_sums after the last call, see __call__
 
     def set_splits(self, S: Optional[dn_matrix], counts=None, train_set: int = 0) -> None:
         """S: int32 [n x 1] on the device, the set of every row of the logits this layer sees (None switches the
@@ -413,45 +414,47 @@ class softmax_cross_entropy_loss:
         if S is None:
             self.S, self.counts = None, None
             return
-        if train_set not in ops.TRAIN_SETS:
-            raise ValueError(f"train_set must be one of {ops.TRAIN_SETS}, got {train_set!r}")
-        if not isinstance(S, dn_matrix) or S.t.dtype != _torch().int32 or S.m() != 1:
+        if not isinstance(S, dn_matrix):
             raise ValueError("the sets must be an int32 dn_matrix of n rows and one column")
-        if counts is None:
-            counts = split_counts(S.numpy())
-        counts = [int(c) for c in counts]
-        if len(counts) != 4 or min(counts) < 0:
-            raise ValueError("counts: the global number of rows of train, val, test and other")
-        if counts[train_set] == 0:
-            raise ValueError(f"no row belongs to set {train_set}: nothing to train on")
-        self.S, self.counts, self.train_set = S, counts, int(train_set)
+        _, self.counts = check_splits(S, S.n(), train_set, counts)
+        self.S, self.train_set = S, int(train_set)
+
+    def active_sums(self):
+        """the sums the last call wrote: the eight of the splits when they are on, the two plain ones otherwise"""
+        return self.sums if self.S is None else self.split_sums
 
     def __call__(self, ctx: context, H: dn_matrix, Y: dn_matrix, n_global: Optional[int] = None,
                  sync: bool = True):
+        """One body for both forms.  With splits on, the gradient is scaled by 1 / (the global number of training rows)
+        instead of 1 / n_global, rows outside train_set get a zero gradient row and eight sums are kept instead of two:
+        (loss, correct) pairs slot by slot from the fused kernel, the four loss sums then the four correct counts
+        (``_planar``) from the unfused chain."""
         torch = _torch()
         n = self.name
+        split = self.S is not None
         if n_global is None:
             n_global = Y.n()
-        ctx.record(n + "0_loss-layer", 0)
-        if self.S is not None:
-            self._split_call(ctx, H, Y)
-            ctx.record(n + "1_loss-layer", 0)
-            ctx.register_timer(n + "loss-layer", n + "0_loss-layer", n + "1_loss-layer")
-            self._n = H.n()
-            if not sync:
-                return None
-            ctx.sync()
-            return self.read(ctx)
+        if split and self.S.n() != H.n():
+            raise ValueError(f"the sets have {self.S.n()} rows, the logits {H.n()}")
+        rows = self.counts[self.train_set] if split else n_global      # what the gradient is averaged over
         if self.sums is None:
-            self.sums = host_scalars(2) if self.host_sums else torch.empty(2, dtype=torch.float32, device=ctx.device)
+            self.split_sums = (host_scalars(8) if self.host_sums
+                               else torch.empty(8, dtype=torch.float32, device=ctx.device))
+            self.sums = self.split_sums[0:2]
+        sums = self.active_sums()
+        ctx.record(n + "0_loss-layer", 0)
         if self.fused and 1 <= H.m() <= ops.XENT_FUSED_MAX_CLASSES:
             if self.copy:                       # the reference copies, then works in place (gcn.hpp:653-656): here the
                 if self.G is None or self.G.shape() != H.shape():   # pass reads the logits, writes the gradient elsewhere
                     self.G = dn_matrix(H.n(), H.m())
             else:
                 self.G = H
-            ctx.lib.mggcn_memset_zero(self.sums.data_ptr(), 8, ctx.stream(0))
-            ops.softmax_xent_fused(ctx, H, Y, 1.0 / n_global, self.sums, out=self.G)
+            ctx.lib.mggcn_memset_zero(sums.data_ptr(), 4 * sums.numel(), ctx.stream(0))
+            if split:
+                ops.softmax_xent_split(ctx, H, Y, self.S, self.train_set, 1.0 / rows, sums, out=self.G)
+            else:
+                ops.softmax_xent_fused(ctx, H, Y, 1.0 / rows, sums, out=self.G)
+            self._planar = False
         else:
             O = self.softmax_layer(ctx, H)
             if self.P is None:
@@ -462,12 +465,19 @@ class softmax_cross_entropy_loss:
             ops.index_log_rows(ctx, O, Y, self.L)
             self.G = O
             ops.add_indexed_rows(ctx, self.G, Y, -1.0)
-            ops.scale_mat(ctx, self.G, float(np.float32(1) / np.float32(n_global)))
+            ops.scale_mat(ctx, self.G, float(np.float32(1) / np.float32(rows)))
+            if split:
+                ops.select_rows_by_set(ctx, self.G, self.S, self.train_set)
             if self.T is None:
                 self.T = dn_matrix(Y.shape())
             ops.is_equal(ctx, Y, self.P, self.T)
-            ops.abssum(ctx, self.L, self.sums[0:1])
-            ops.abssum(ctx, self.T, self.sums[1:2])
+            if split:
+                ops.abssum_by_set(ctx, self.L, self.S, sums[0:4])
+                ops.abssum_by_set(ctx, self.T, self.S, sums[4:8])
+            else:
+                ops.abssum(ctx, self.L, sums[0:1])
+                ops.abssum(ctx, self.T, sums[1:2])
+            self._planar = True
         ctx.record(n + "1_loss-layer", 0)
         ctx.register_timer(n + "loss-layer", n + "0_loss-layer", n + "1_loss-layer")
         self._n = H.n()
@@ -475,43 +485,6 @@ class softmax_cross_entropy_loss:
             return None
         ctx.sync()
         return self.read(ctx)
-
-    def _split_call(self, ctx: context, H: dn_matrix, Y: dn_matrix) -> None:
-        """the layer with splits on: the same two routes as __call__, split-aware"""
-        torch = _torch()
-        if self.S.n() != H.n():
-            raise ValueError(f"the sets have {self.S.n()} rows, the logits {H.n()}")
-        if self.split_sums is None:
-            self.split_sums = (host_scalars(8) if self.host_sums
-                               else torch.empty(8, dtype=torch.float32, device=ctx.device))
-        n_train = self.counts[self.train_set]
-        if self.fused and 1 <= H.m() <= ops.XENT_FUSED_MAX_CLASSES:
-            if self.copy:
-                if self.G is None or self.G.shape() != H.shape():
-                    self.G = dn_matrix(H.n(), H.m())
-            else:
-                self.G = H
-            ctx.lib.mggcn_memset_zero(self.split_sums.data_ptr(), 32, ctx.stream(0))
-            ops.softmax_xent_split(ctx, H, Y, self.S, self.train_set, 1.0 / n_train, self.split_sums, out=self.G)
-            self._planar = False            # (loss, correct) pairs, slot by slot
-            return
-        O = self.softmax_layer(ctx, H)
-        if self.P is None:
-            self.P = dn_matrix(Y.shape(), dtype=np.int32)
-        ops.max_row_indices(ctx, O, self.P)
-        if self.L is None:
-            self.L = dn_matrix(Y.shape())
-        ops.index_log_rows(ctx, O, Y, self.L)
-        self.G = O
-        ops.add_indexed_rows(ctx, self.G, Y, -1.0)
-        ops.scale_mat(ctx, self.G, float(np.float32(1) / np.float32(n_train)))
-        ops.select_rows_by_set(ctx, self.G, self.S, self.train_set)
-        if self.T is None:
-            self.T = dn_matrix(Y.shape())
-        ops.is_equal(ctx, Y, self.P, self.T)
-        ops.abssum_by_set(ctx, self.L, self.S, self.split_sums[0:4])
-        ops.abssum_by_set(ctx, self.T, self.S, self.split_sums[4:8])
-        self._planar = True                 # the four loss sums, then the four correct counts
 
     def split_sums_host(self, sums=None) -> np.ndarray:
         """the eight sums of the last call as (loss sum, correct count) pairs of train / val / test / other; ``sums``:
@@ -533,13 +506,17 @@ class softmax_cross_entropy_loss:
         out["counts"] = dict(zip(ops.SPLIT_NAMES, self.counts))
         return out
 
-    def read(self, ctx: context):
+    def read(self, ctx: context, sums=None, n: Optional[int] = None):
         """(loss, acc) of the last call; the caller has synchronised (train_step reads after the
-        whole epoch is done instead of blocking between forward and backward)."""
+        whole epoch is done instead of blocking between forward and backward).  ``sums``: the host floats to read them
+        from, in the layout of the last call, and ``n``: the rows they were summed over (the distributed wrapper passes the
+        all-reduced sums and the global row count; None: this layer's own)."""
         if self.S is not None:
-            return self.split_metrics()[ops.SPLIT_NAMES[self.train_set]]
-        s = self.sums.numpy() if self.host_sums else self.sums.cpu().numpy()
-        return float(np.float32(s[0]) / np.float32(self._n)), float(np.float32(s[1]) / np.float32(self._n))
+            return self.split_metrics(sums)[ops.SPLIT_NAMES[self.train_set]]
+        if sums is None:
+            sums = self.sums.numpy() if self.host_sums else self.sums.cpu().numpy()
+        n = np.float32(self._n if n is None else n)
+        return float(np.float32(sums[0]) / n), float(np.float32(sums[1]) / n)
 
     def backward(self) -> dn_matrix:
         return self.G
@@ -552,25 +529,36 @@ def split_counts(S: np.ndarray) -> List[int]:
     return c + [int(s.size) - sum(c)]
 
 
-def check_splits(S, n: int, train_set: int, counts=None):
-    """Option checking of set_splits, before any device work: S is a numpy array of n integers or an int32 dn_matrix of
-    n x 1, train_set one of 0 / 1 / 2, and at least one row trains (``counts``: the global counts of a row partition;
-    None counts S).  Returns (the sets as a host int32 [n x 1] array, the counts)."""
+def check_sets(S, n: int, train_set: int) -> np.ndarray:
+    """train_set is one of 0 / 1 / 2 and S a numpy array of n integers or an int32 dn_matrix of n x 1; returns the sets as
+    a host int32 [n x 1] array"""
     if train_set not in ops.TRAIN_SETS:
         raise ValueError(f"train_set must be one of {ops.TRAIN_SETS}, got {train_set!r}")
     if isinstance(S, dn_matrix):
         if S.t.dtype != _torch().int32 or S.shape() != (n, 1):
             raise ValueError(f"the sets must be an int32 dn_matrix of {n} x 1, got {S.t.dtype} of {S.shape()}")
-        host = S.numpy()
-    else:
-        host = np.asarray(S)
-        if host.dtype.kind not in "iu" or host.size != n or host.ndim > 2 or (host.ndim == 2 and host.shape[1] != 1):
-            raise ValueError(f"the sets must be {n} integers, got {host.dtype} of shape {host.shape}")
-        host = np.ascontiguousarray(host.reshape(n, 1).astype(np.int32))
-    counts = split_counts(host) if counts is None else [int(c) for c in counts]
+        return S.numpy()
+    host = np.asarray(S)
+    if host.dtype.kind not in "iu" or host.size != n or host.ndim > 2 or (host.ndim == 2 and host.shape[1] != 1):
+        raise ValueError(f"the sets must be {n} integers, got {host.dtype} of shape {host.shape}")
+    return np.ascontiguousarray(host.reshape(n, 1).astype(np.int32))
+
+
+def check_counts(counts, train_set: int) -> List[int]:
+    """four global row counts (train, val, test, other) of which train_set's is not zero"""
+    counts = [int(c) for c in counts]
+    if len(counts) != 4 or min(counts) < 0:
+        raise ValueError("counts: the global number of rows of train, val, test and other")
     if counts[train_set] == 0:
         raise ValueError(f"no vertex belongs to set {train_set}: nothing to train on")
-    return host, counts
+    return counts
+
+
+def check_splits(S, n: int, train_set: int, counts=None):
+    """Option checking of set_splits, before any device work: check_sets, and at least one row trains (``counts``: the
+    global counts of a row partition; None counts S).  Returns (the sets as a host int32 [n x 1] array, the counts)."""
+    host = check_sets(S, n, train_set)
+    return host, check_counts(split_counts(host) if counts is None else counts, train_set)
 
 
 def link_fused_backward(layers, fused: bool) -> None:
@@ -742,7 +730,7 @@ class gcn:
         res = {"all": float(hit.mean())}
         if S is not None:
             s = S.numpy().reshape(-1)
-            for k, name in ((0, "train"), (1, "val"), (2, "test")):
+            for k, name in enumerate(ops.SPLIT_NAMES[:3]):
                 m = s == k
                 res[name] = float(hit[m].mean()) if m.any() else float("nan")
         return res

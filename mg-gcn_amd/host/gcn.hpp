@@ -567,8 +567,10 @@ std::array<std::size_t, 4> split_counts(const std::vector<x_t> &sets) {
     return c;
 }
 
-inline void check_train_set(int train_set, std::size_t n_train) {
+inline void check_train_set(int train_set) {
     if (train_set < 0 || train_set > 2) throw std::invalid_argument("train_set must be 0 (train), 1 (validation) or 2 (test)");
+}
+inline void check_somebody_trains(std::size_t n_train) {
     if (n_train == 0) throw std::invalid_argument("no vertex belongs to the training set: nothing to train on");
 }
 
@@ -582,75 +584,55 @@ std::array<std::pair<r_t, r_t>, 4> split_metrics_of(const std::array<r_t, 8> &s,
     return out;
 }
 
-// One GPU's share of the loss: enqueues everything, leaves {sum|log p_y|, #correct} in
-// sums_device; the caller synchronises and reads (reference :785-818 / :890-930).
+// One GPU's share of the loss: enqueues everything and leaves the sums in mapped pinned host memory -- {sum|log p_y|,
+// #correct} over its rows, or one such pair per slot with a loss_split; the caller synchronises and reads
+// (reference :785-818 / :890-930).
 template <typename r_t, typename x_t>
 class loss_kernels {
     softmax<r_t> softmax_layer;
     dn_matrix<r_t> G, L, T;
     dn_matrix<x_t> P;
     const bool copy, fused;
-    mggcn::device_ptr<r_t> sums_, split_sums_;
-    bool planar_ = false;        // split_sums_ of the last call: four loss sums then four counts (the unfused chain)
+    mggcn::device_ptr<r_t> sums_;    // eight floats, written by the kernels, read by the host after its sync
+    std::size_t slots_ = 1;          // pairs the last call wrote: 1, or the 4 of a split-aware call
+    bool planar_ = false;            // ... as all loss sums, then all correct counts (the unfused chain) instead of pair by pair
 
 public:
     loss_kernels(bool copy, bool fused) : softmax_layer(copy), copy(copy), fused(fused) {}
-    r_t *sums() const { return sums_.get(); }
     auto gradient() const { return G; }
-    // the eight sums of the last split-aware call as (loss sum, correct count) pairs of train / val / test / other
-    std::array<r_t, 8> split_sums() const {
-        std::array<r_t, 8> out;
-        const r_t *s = split_sums_.get();                        // mapped pinned host memory
-        for (std::size_t k = 0; k < 4; k++) {
+    // the sums of the last call as (loss sum, correct count) pairs: the one pair of a plain call first and zeros behind
+    // it, or train / val / test / other
+    std::array<r_t, 8> sums() const {
+        std::array<r_t, 8> out{};
+        const r_t *s = sums_.get();
+        for (std::size_t k = 0; k < slots_; k++) {
             out[2 * k] = planar_ ? s[k] : s[2 * k];
-            out[2 * k + 1] = planar_ ? s[4 + k] : s[2 * k + 1];
+            out[2 * k + 1] = planar_ ? s[slots_ + k] : s[2 * k + 1];
         }
         return out;
     }
 
+    // with a split: the gradient is scaled by 1 / n_train instead of 1 / n_global, rows outside train_set get a zero
+    // gradient row, and a pair of sums is kept per slot
     void enqueue(context ctx, dn_matrix<r_t> H, dn_matrix<x_t> Y, std::size_t n_global,
                  std::optional<loss_split<x_t>> split = std::nullopt) {
         ctx.set();
-        if (split) { enqueue_split(ctx, H, Y, *split); return; }
-        if (!sums_) sums_ = mggcn::host_malloc<r_t>(2);          // written by the kernels, read by the host after its sync
-        if (fused) {
+        if (split) {
+            check_train_set(split->train_set);
+            check_somebody_trains(split->n_train);
+        }
+        if (!sums_) sums_ = mggcn::host_malloc<r_t>(8);
+        slots_ = split ? 4 : 1;
+        const r_t scale = (r_t)1 / (r_t)(split ? split->n_train : n_global);
+        if (fused && H.m() >= 1 && H.m() <= 1024) {     // the one-pass kernel's widths; any other runs the chain below
             if (copy) {                       // reference: copy, then in place (:653-656); here the pass writes elsewhere
                 if (!G.buffer() || G.shape() != H.shape()) G = dn_matrix<r_t>(H.n(), H.m());
             } else {
                 G = H;
             }
-            mggcn_memset_zero(sums_.get(), 2 * sizeof(r_t), ctx.stream(0));
-            softmax_xent_fused(ctx, H, G, Y, (r_t)1 / (r_t)n_global, sums_.get());
-            return;
-        }
-        auto O = softmax_layer(ctx, H);
-        if (!P.buffer()) P = dn_matrix<x_t>(Y.shape());
-        max_row_indices(ctx, O, P);
-        if (!L.buffer()) L = dn_matrix<r_t>(Y.shape());
-        index_log_rows(ctx, O, Y, L);
-        G = O;
-        add_indexed_rows(ctx, G, Y, (r_t)-1);
-        scale_mat(ctx, G, (r_t)1 / (r_t)n_global);
-        if (!T.buffer()) T = dn_matrix<r_t>(Y.shape());
-        is_equal(ctx, Y, P, T);
-        abssum(ctx, L, sums_.get());
-        abssum(ctx, T, sums_.get() + 1);
-    }
-
-private:
-    // the same two routes, split-aware
-    void enqueue_split(context ctx, dn_matrix<r_t> H, dn_matrix<x_t> Y, const loss_split<x_t> &sp) {
-        check_train_set(sp.train_set, sp.n_train);
-        if (!split_sums_) split_sums_ = mggcn::host_malloc<r_t>(8);
-        const r_t scale = (r_t)1 / (r_t)sp.n_train;
-        if (fused && H.m() >= 1 && H.m() <= 1024) {
-            if (copy) {
-                if (!G.buffer() || G.shape() != H.shape()) G = dn_matrix<r_t>(H.n(), H.m());
-            } else {
-                G = H;
-            }
-            mggcn_memset_zero(split_sums_.get(), 8 * sizeof(r_t), ctx.stream(0));
-            softmax_xent_split(ctx, H, G, Y, sp.S, sp.train_set, scale, split_sums_.get());
+            mggcn_memset_zero(sums_.get(), 2 * slots_ * sizeof(r_t), ctx.stream(0));
+            if (split) softmax_xent_split(ctx, H, G, Y, split->S, split->train_set, scale, sums_.get());
+            else softmax_xent_fused(ctx, H, G, Y, scale, sums_.get());
             planar_ = false;
             return;
         }
@@ -662,11 +644,16 @@ private:
         G = O;
         add_indexed_rows(ctx, G, Y, (r_t)-1);
         scale_mat(ctx, G, scale);
-        select_rows_by_set(ctx, G, sp.S, sp.train_set);
+        if (split) select_rows_by_set(ctx, G, split->S, split->train_set);
         if (!T.buffer()) T = dn_matrix<r_t>(Y.shape());
         is_equal(ctx, Y, P, T);
-        abssum_by_set(ctx, L, sp.S, split_sums_.get());
-        abssum_by_set(ctx, T, sp.S, split_sums_.get() + 4);
+        if (split) {
+            abssum_by_set(ctx, L, split->S, sums_.get());
+            abssum_by_set(ctx, T, split->S, sums_.get() + 4);
+        } else {
+            abssum(ctx, L, sums_.get());
+            abssum(ctx, T, sums_.get() + 1);
+        }
         planar_ = true;
     }
 };
@@ -681,19 +668,19 @@ public:
 
     // train on the rows with S == train_set (see loss_split); counted here, on the host.  clear_splits() turns it off.
     void set_splits(dn_matrix<x_t> S, int train_set = 0) {
-        if (train_set < 0 || train_set > 2) check_train_set(train_set, 1);
+        check_train_set(train_set);
         mggcn_require(S.m() == 1, "set_splits: the sets must be n x 1");
         const auto c = split_counts(S.to_host());
-        check_train_set(train_set, c[(std::size_t)train_set]);
+        check_somebody_trains(c[(std::size_t)train_set]);
         counts_ = c;
         split_ = loss_split<x_t>{S, train_set, c[(std::size_t)train_set]};
     }
     void clear_splits() { split_.reset(); }
     bool has_splits() const { return split_.has_value(); }
     // the eight sums ((loss sum, correct count) of train / val / test / other) and the four row counts of the last call
-    auto split_sums() const { return k.split_sums(); }
+    auto split_sums() const { return k.sums(); }
     auto split_counts_global() const { return counts_; }
-    auto split_metrics() const { return split_metrics_of<r_t>(k.split_sums(), counts_); }
+    auto split_metrics() const { return split_metrics_of<r_t>(k.sums(), counts_); }
 
     auto operator()(context ctx, dn_matrix<r_t> H, dn_matrix<x_t> Y) {
         if (split_) mggcn_require(split_->S.n() == H.n(), "the sets and the logits differ in their row count");
@@ -702,9 +689,9 @@ public:
         ctx.record(name + "1_loss-layer", 0);
         ctx.register_timer(name + "loss-layer", name + "0_loss-layer", name + "1_loss-layer");
         ctx.sync();
-        if (split_) return split_metrics()[(std::size_t)split_->train_set];          // the training split's pair
-        const r_t *s = k.sums();                                 // mapped pinned host memory
-        return std::make_pair(s[0] / H.n(), s[1] / H.n());
+        const auto s = k.sums();
+        return split_ ? split_metrics()[(std::size_t)split_->train_set]             // the training split's pair
+                      : std::make_pair(s[0] / H.n(), s[1] / H.n());
     }
     auto backward() { return k.gradient(); }
 
@@ -726,66 +713,50 @@ public:
     // train on the rows with S == train_set: the global counts are summed here, on the host, over the P shards (as the
     // scalars are below); a GPU without a training row is fine
     void set_splits(dist_context ctx, dist_row_dn_matrix<x_t> Sd, int train_set = 0) {
-        if (train_set < 0 || train_set > 2) check_train_set(train_set, 1);
+        check_train_set(train_set);
         std::array<std::size_t, 4> c{0, 0, 0, 0};
         for (std::size_t i = 0; i < ctx.size(); i++) {
             const auto ci = split_counts(Sd[i].to_host());
             for (std::size_t k = 0; k < 4; k++) c[k] += ci[k];
         }
-        check_train_set(train_set, c[(std::size_t)train_set]);
+        check_somebody_trains(c[(std::size_t)train_set]);
         counts_ = c;
         Sd_ = Sd;
         train_set_ = train_set;
-        on_ = true;
     }
-    void clear_splits() { on_ = false; }
-    bool has_splits() const { return on_; }
-    auto split_sums() const { return split_sums_; }              // global, of the last call
+    void clear_splits() { Sd_.reset(); }
+    bool has_splits() const { return Sd_.has_value(); }
+    auto split_sums() const { return sums_; }                   // global, of the last call
     auto split_counts_global() const { return counts_; }
-    auto split_metrics() const { return split_metrics_of<r_t>(split_sums_, counts_); }
+    auto split_metrics() const { return split_metrics_of<r_t>(sums_, counts_); }
 
     auto operator()(dist_context ctx, dist_row_dn_matrix<r_t> H, dist_row_dn_matrix<x_t> Y) {
+        if (copy) throw std::invalid_argument("dist loss with copy = true is not used by the reference CLI");
         while (ks.size() < ctx.size()) ks.push_back(std::make_shared<loss_kernels<r_t, x_t>>(copy, fused));
         ctx.record(name + "0_loss-layer", 0);
-        if (on_) {
-            if (copy) throw std::invalid_argument("dist loss with copy = true is not used by the reference CLI");
-            for (std::size_t i = 0; i < ctx.size(); i++)         // S's handle is captured by value, like the other matrices
-                ctx.on(i, [k = ks[i], c = ctx[i], h = H[i], y = Y[i], n = Y.n(),
-                           sp = loss_split<x_t>{(*Sd_)[i], train_set_, counts_[(std::size_t)train_set_]}] { k->enqueue(c, h, y, n, sp); });
-            ctx.record(name + "1_loss-layer", 0);
-            ctx.register_timer(name + "loss-layer", name + "0_loss-layer", name + "1_loss-layer");
-            ctx.sync();
-            split_sums_.fill(0);
-            for (std::size_t i = 0; i < ctx.size(); i++) {      // host sum of the per-GPU sums, in GPU order
-                const auto s = ks[i]->split_sums();
-                for (std::size_t k = 0; k < 8; k++) split_sums_[k] += s[k];
-            }
-            G = H;
-            return split_metrics()[(std::size_t)train_set_];
+        for (std::size_t i = 0; i < ctx.size(); i++) {           // global n (reference :908); S's handle is captured by value,
+            std::optional<loss_split<x_t>> sp;                   // like the other matrices
+            if (Sd_) sp = loss_split<x_t>{(*Sd_)[i], train_set_, counts_[(std::size_t)train_set_]};
+            ctx.on(i, [k = ks[i], c = ctx[i], h = H[i], y = Y[i], n = Y.n(), sp] { k->enqueue(c, h, y, n, sp); });
         }
-        for (std::size_t i = 0; i < ctx.size(); i++)                                               // global n (reference :908)
-            ctx.on(i, [k = ks[i], c = ctx[i], h = H[i], y = Y[i], n = Y.n()] { k->enqueue(c, h, y, n); });
         ctx.record(name + "1_loss-layer", 0);
         ctx.register_timer(name + "loss-layer", name + "0_loss-layer", name + "1_loss-layer");
         ctx.sync();
-        r_t loss = 0, acc = 0;
-        for (std::size_t i = 0; i < ctx.size(); i++) {          // host sum of the per-GPU scalars (reference :929)
-            const r_t *s = ks[i]->sums();                       // mapped pinned host memory
-            loss += s[0];
-            acc += s[1];
+        sums_.fill(0);
+        for (std::size_t i = 0; i < ctx.size(); i++) {          // host sum of the per-GPU sums, in GPU order (reference :929)
+            const auto s = ks[i]->sums();
+            for (std::size_t k = 0; k < 8; k++) sums_[k] += s[k];
         }
         G = H;                                                   // copy = false: gradient in place, as in dist_gcn
-        if (copy) throw std::invalid_argument("dist loss with copy = true is not used by the reference CLI");
-        return std::make_pair(loss / H.n(), acc / H.n());
+        return Sd_ ? split_metrics()[(std::size_t)train_set_] : std::make_pair(sums_[0] / H.n(), sums_[1] / H.n());
     }
     auto backward() { return G; }
 
 private:
-    bool on_ = false;
     int train_set_ = 0;
-    std::optional<dist_row_dn_matrix<x_t>> Sd_;
+    std::optional<dist_row_dn_matrix<x_t>> Sd_;                  // set: the splits are on
     std::array<std::size_t, 4> counts_{0, 0, 0, 0};
-    std::array<r_t, 8> split_sums_{};
+    std::array<r_t, 8> sums_{};                                  // (loss sum, correct count) pairs of the last call, see loss_kernels
 };
 
 // fused backward: layer i+1's G_out GEMM applies layer i's leaky_relu' -- possible when layer i+1 is GEMM-first

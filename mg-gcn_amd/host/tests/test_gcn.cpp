@@ -1,5 +1,6 @@
 // test_gcn.cpp -- the reference's known-answer tests (test/test_gcn.cpp:98-249) restated over
 // the C++ host layer: same literals, same call sequence, HIP kernels underneath.
+#include <cstring>
 #include <vector>
 
 #include "check.hpp"
@@ -106,6 +107,67 @@ static void test_gcn_trains(const context ctx, const char *toy_dir) {
     CHECK(std::isfinite(last) && last < first);
 }
 
+static bool same_bits(const std::vector<float> &a, const std::vector<float> &b) {
+    return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(float)) == 0;
+}
+
+// 1030 classes are more than the one-pass loss kernel takes (1024): fused = true runs the unfused chain there, launch for
+// launch what fused = false runs -- the same loss, accuracy and gradient, bit for bit
+static void test_wide_loss_layer(const context ctx, bool copy) {
+    const std::size_t n = 5, m = 1030;
+    std::vector<float> h(n * m);
+    for (std::size_t i = 0; i < h.size(); i++) h[i] = (float)((i * 37 + i / m * 11) % 101) / 16.f - 3.f;
+    dn_matrix<std::int32_t> Y(n, 1);
+    Y.init({0, 1029, 512, 1024, 7});
+    std::vector<float> loss, acc;
+    std::vector<std::vector<float>> grad;
+    for (const bool fused : {true, false}) {
+        dn_matrix<float> logits(n, m);
+        logits.init(h);
+        softmax_cross_entropy_loss<float, std::int32_t> loss_layer("0_", copy, fused);
+        auto [l, a] = loss_layer(ctx, logits, Y);
+        loss.push_back(l);
+        acc.push_back(a);
+        grad.push_back(loss_layer.backward().to_host());
+    }
+    CHECK(std::isfinite(loss[0]) && loss[0] > 0);
+    CHECK(same_bits({loss[0]}, {loss[1]}) && same_bits({acc[0]}, {acc[1]}));
+    CHECK(same_bits(grad[0], grad[1]));
+}
+
+// ... and the model above it: a gcn with 1030 classes trains with fused = true (the default), and its epochs report the
+// loss, accuracy and weight gradients of the fused = false model started from the same weights, bit for bit
+static void test_gcn_wide_classes(const context ctx, const char *toy_dir) {
+    dn_matrix<float> X(std::string(toy_dir) + "/features.bin");
+    dn_matrix<std::int32_t> Y(std::string(toy_dir) + "/labels.bin");
+    std::vector<gcn<unsigned, unsigned, float>> G;
+    for (const bool fused : {true, false})
+        G.emplace_back(csr_matrix<unsigned, unsigned, float>(std::string(toy_dir) + "/graph.bin"),
+                       std::vector<std::size_t>{X.m(), 4, 1030}, false, fused);
+    for (std::size_t l = 0; l < G[0].layers().size(); l++) {
+        G[1].layers()[l].W().init(G[0].layers()[l].W().to_host());
+        G[1].layers()[l].b().init(G[0].layers()[l].b().to_host());
+    }
+    for (int e = 0; e < 2; e++) {
+        std::vector<float> loss, acc;
+        for (auto &g : G) {
+            auto [l, a] = g.train_forward(ctx, X, Y);
+            g.backward(ctx);
+            ctx.sync();
+            loss.push_back(l);
+            acc.push_back(a);
+        }
+        CHECK(std::isfinite(loss[0]) && loss[0] > 0);
+        CHECK(same_bits({loss[0]}, {loss[1]}) && same_bits({acc[0]}, {acc[1]}));
+        for (std::size_t l = 0; l < G[0].layers().size(); l++) {
+            CHECK(same_bits(G[0].layers()[l].GW().to_host(), G[1].layers()[l].GW().to_host()));
+            CHECK(same_bits(G[0].layers()[l].Gb().to_host(), G[1].layers()[l].Gb().to_host()));
+        }
+        for (auto &g : G) g.adam_update(ctx, 1e-2, 0.9, 0.999, 5e-4, 1e-8);
+        ctx.sync();
+    }
+}
+
 int main(int argc, char **argv) {
     const char *toy = argc > 1 ? argv[1] : "../../../tests/golden/toyB";
     const auto ctx = context(0);
@@ -116,5 +178,8 @@ int main(int argc, char **argv) {
     RUN(test_g_chain, ctx, false);
     RUN(test_g_chain, ctx, true);
     RUN(test_gcn_trains, ctx, toy);
+    RUN(test_wide_loss_layer, ctx, true);
+    RUN(test_wide_loss_layer, ctx, false);
+    RUN(test_gcn_wide_classes, ctx, toy);
     return g_failures != 0;
 }

@@ -259,6 +259,38 @@ void mggcn_softmax_xent_fused_from_f32(mggcn_stream_t s, const float *logits, fl
 void mggcn_softmax_xent_fused_f32(mggcn_stream_t s, float *H, const int32_t *Y, size_t n_rows, size_t m, float grad_scale, float *sums) {
     mggcn_softmax_xent_fused_from_f32(s, H, H, Y, n_rows, m, grad_scale, sums);
 }
+// ---- the split-aware loss: slot(s) = s for 0 <= s <= 2, 3 for every other value ---------------------
+static inline size_t slot_of(int32_t s) { return s >= 0 && s <= 2 ? (size_t)s : 3; }
+void mggcn_softmax_xent_split_from_f32(mggcn_stream_t s, const float *logits, float *G, const int32_t *Y, const int32_t *S, size_t n_rows,
+                                       size_t m, int32_t train_set, float grad_scale, float *sums) {
+    launch(s, [=] {
+        float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        std::vector<float> o(m);
+        for (size_t r = 0; r < n_rows; r++) {
+            const float *h = logits + r * m;
+            size_t arg = 0;
+            for (size_t c = 1; c < m; c++) if (h[c] > h[arg]) arg = c;
+            float sum = 0.f;
+            for (size_t c = 0; c < m; c++) { o[c] = std::exp(h[c] - h[arg]); sum += o[c]; }
+            const size_t y = (size_t)Y[r], k = slot_of(S[r]);
+            acc[2 * k] += std::fabs(std::log(o[y] / sum));
+            acc[2 * k + 1] += y == arg ? 1.f : 0.f;
+            const bool train = S[r] == train_set;                      // G may alias the logits: every column is written
+            for (size_t c = 0; c < m; c++) G[r * m + c] = train ? (o[c] / sum - (c == y ? 1.f : 0.f)) * grad_scale : 0.f;
+        }
+        for (size_t k = 0; k < 8; k++) sums[k] += acc[k];
+    });
+}
+void mggcn_select_rows_by_set_f32(mggcn_stream_t s, float *mat, const int32_t *S, int32_t set, size_t size, size_t m) {
+    launch(s, [=] { for (size_t i = 0; i < size; i++) if (S[i / m] != set) mat[i] = 0.f; });
+}
+void mggcn_abssum_by_set_f32(mggcn_stream_t s, const float *x, const int32_t *S, size_t n, float *result) {
+    launch(s, [=] {
+        float acc[4] = {0.f, 0.f, 0.f, 0.f};
+        for (size_t i = 0; i < n; i++) acc[slot_of(S[i])] += std::fabs(x[i]);
+        for (size_t k = 0; k < 4; k++) result[k] = acc[k];
+    });
+}
 static void adam_one(float *p, float *g, float *m, float *v, size_t n, float lr, float b1, float b2, float wd, float c1, float c2, float eps) {
     for (size_t i = 0; i < n; i++) {
         g[i] += wd * p[i];
