@@ -201,6 +201,13 @@ void mggcn_spmm_csr_bf16(mggcn_stream_t stream, const mggcn_spmm_plan *plan, uin
  * Round to nearest even; a NaN stays a NaN, overflow goes to +-inf.  src and dst must not overlap. */
 void mggcn_convert_f32_bf16(mggcn_stream_t stream, const float *src, size_t ld_src, uint16_t *dst, size_t ld_dst,
                             size_t n_rows, size_t n_cols);
+/* dst[k, 0:d] = src[indices[k], 0:d] on bf16 bit patterns: mggcn_gather_rows_f32 for a shard that has already been
+ * rounded (the halo pack of the row-partitioned model with bf16 aggregation).  A pure copy: every bit pattern
+ * survives.  Leading dimensions in ELEMENTS (ld_src, ld_dst >= d); indices: device, uint32; src and dst must not
+ * overlap.  16 bytes per lane when d and both leading dimensions are multiples of 8 and both bases 16-byte aligned,
+ * 4 bytes when all are even and 4-byte aligned, 2 bytes otherwise.  n_indices == 0 or d == 0: no launch. */
+void mggcn_gather_rows_bf16(mggcn_stream_t stream, const uint16_t *src, size_t ld_src, const uint32_t *indices,
+                            size_t n_indices, uint32_t d, uint16_t *dst, size_t ld_dst);
 
 /* ======================================================================== *
  * Dense GEMM  C = alpha * op(A) * op(B) + beta * C, row-major  (the MFMA path)

@@ -66,6 +66,7 @@ PROTOTYPES = {
     "mggcn_spmm_csr_bf16": (None, [vp, vp, c_uint32, c_uint32, vp, vp, vp, vp, c_size_t, vp, c_size_t,
                                    c_uint32, c_float, c_float, c_uint32, c_float]),
     "mggcn_convert_f32_bf16": (None, [vp, vp, c_size_t, vp, c_size_t, c_size_t, c_size_t]),
+    "mggcn_gather_rows_bf16": (None, [vp, vp, c_size_t, vp, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_gemm_workspace_bytes": (c_size_t, [c_int, c_int, c_uint32, c_uint32, c_uint32]),
     "mggcn_gemm_f32": (None, [vp, c_int, c_int, c_uint32, c_uint32, c_uint32, c_float, vp, c_size_t, vp,
                               c_size_t, c_float, vp, c_size_t, vp, c_size_t]),

@@ -1001,3 +1001,68 @@ MGGCN_API void mggcn_convert_f32_bf16(mggcn_stream_t stream, const float *src, s
                            n_rows, n_cols);
     MGGCN_CHECK_LAUNCH();
 }
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Halo pack of a shard that is already bf16 (the row-partitioned model with agg_dtype = "bf16" rounds its shard once and
+// sends that image): dst[k, 0:d] = src[idx[k], 0:d] on 2-byte bit patterns, a pure copy.
+// A bf16 row is short -- 256 bytes at d = 128 are 16 lanes of 16 bytes -- so a wave64 carries 64 / L rows, L lanes per
+// row (a power of two chosen on the host from the row's length in units of T): lane = sub * L + l copies units l, l + L,
+// ... of row (wave * 64 / L + sub).  The L lanes of a row read and write consecutive units, so a row is one contiguous
+// segment in both directions, and with ld_dst == d the 64 / L rows of a wave land back to back: a full 1 KiB store per
+// instruction at d = 128.  T = uint4 (16 bytes) / uint32_t / uint16_t is picked on the host from d, the leading
+// dimensions and the two base addresses.  Up to four units per lane are loaded before the first is stored: loads and
+// stores retire through ONE in-order counter (vmcnt), so a load issued behind a store is known complete only once that
+// store is -- load, store, load, store would pay a round trip per unit; this way the four loads are in flight together.
+// ---------------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr unsigned kGatherBf16Blocks = kNumCU * 8;      // 8 workgroups of 4 waves per CU: all resident at once
+
+template <typename T>
+__global__ __launch_bounds__(256) void gather_rows_u16_kernel(const uint16_t *__restrict__ src, size_t ld_src,
+                                                               const uint32_t *__restrict__ idx, size_t n_idx,
+                                                               uint32_t units, uint16_t *__restrict__ dst, size_t ld_dst,
+                                                               uint32_t lanes_log2) {
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t L = 1u << lanes_log2, rows_per_wave = 64u >> lanes_log2;
+    const uint32_t sub = lane >> lanes_log2, l = lane & (L - 1);
+    const size_t wave = (size_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    const size_t stride = (size_t)gridDim.x * (blockDim.x >> 6) * rows_per_wave;
+    for (size_t k = wave * rows_per_wave + sub; k < n_idx; k += stride) {
+        const T *s = reinterpret_cast<const T *>(src + (size_t)idx[k] * ld_src);
+        T *o = reinterpret_cast<T *>(dst + k * ld_dst);
+        size_t c = l;
+        for (; c + 3 * L < units; c += 4 * L) {
+            const T v0 = s[c], v1 = s[c + L], v2 = s[c + 2 * L], v3 = s[c + 3 * L];
+            o[c] = v0; o[c + L] = v1; o[c + 2 * L] = v2; o[c + 3 * L] = v3;
+        }
+        for (; c < units; c += L) o[c] = s[c];
+    }
+}
+
+template <typename T>
+void launch_gather_rows_bf16(hipStream_t st, const uint16_t *src, size_t ld_src, const uint32_t *indices, size_t n_indices,
+                             uint32_t units, uint16_t *dst, size_t ld_dst) {
+    uint32_t lanes_log2 = 0;                                // L = the power of two that covers a row, 64 at the most
+    while (lanes_log2 < 6 && (1u << lanes_log2) < units) ++lanes_log2;
+    const size_t rows_per_wave = 64u >> lanes_log2;
+    const size_t waves = (n_indices + rows_per_wave - 1) / rows_per_wave;
+    const unsigned blocks = (unsigned)std::min<size_t>((waves + 3) / 4, kGatherBf16Blocks);
+    hipLaunchKernelGGL(gather_rows_u16_kernel<T>, dim3(blocks), dim3(256), 0, st, src, ld_src, indices, n_indices, units,
+                       dst, ld_dst, lanes_log2);
+    MGGCN_CHECK_LAUNCH();
+}
+}  // namespace
+
+MGGCN_API void mggcn_gather_rows_bf16(mggcn_stream_t stream, const uint16_t *src, size_t ld_src, const uint32_t *indices,
+                                      size_t n_indices, uint32_t d, uint16_t *dst, size_t ld_dst) {
+    if (!n_indices || !d) return;
+    MGGCN_REQUIRE(src && indices && dst && ld_src >= d && ld_dst >= d, "gather_rows_bf16: bad operand");
+    const uintptr_t bases = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst);
+    const size_t pitches = d | ld_src | ld_dst;
+    if (pitches % 8 == 0 && bases % 16 == 0)
+        launch_gather_rows_bf16<uint4>(as_stream(stream), src, ld_src, indices, n_indices, d / 8, dst, ld_dst);
+    else if (pitches % 2 == 0 && bases % 4 == 0)
+        launch_gather_rows_bf16<uint32_t>(as_stream(stream), src, ld_src, indices, n_indices, d / 2, dst, ld_dst);
+    else
+        launch_gather_rows_bf16<uint16_t>(as_stream(stream), src, ld_src, indices, n_indices, d, dst, ld_dst);
+}

@@ -44,7 +44,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, ops
-from .gcn import (adam_update_all, check_counts, check_sets, layer_body, linear, link_fused_backward,
+from .gcn import (_check_agg_dtype, adam_update_all, check_counts, check_sets, layer_body, linear, link_fused_backward,
                   softmax_cross_entropy_loss, split_counts)
 from .matrix import context, csr_matrix, dn_matrix
 
@@ -237,7 +237,9 @@ def gloo_all_gather_rows(host_shard, P: int, group=None):
     me = dist.get_rank(group)
     for i in range(P):
         view = out[i * rows:(i + 1) * rows]
-        if i == me:
+        if i == me and host_shard.dtype == torch.bfloat16:     # numpy has no bf16: the same memcpy on the bit patterns
+            view.view(torch.int16).numpy()[...] = host_shard.view(torch.int16).numpy()
+        elif i == me:
             view.numpy()[...] = host_shard.numpy()
         dist.broadcast(view, src=dist.get_global_rank(group, i) if group is not None else i, group=group)
     return out
@@ -315,6 +317,9 @@ class dist_context(host_comm):
         # bench.py's exchange pass: extra events around every exchange (comm-stream time of the collectives, time the
         # compute stream spends waiting for each piece).  Off in timed epochs: ~10 more event records per SpMM.
         self.profile_exchange = False
+        # bytes of THIS rank's payload handed to the shard exchange so far (the all-gather's shard, the broadcast's shard
+        # on its root, the all-to-all's send rows; not the gradient all-reduces): a host integer, reset by assignment
+        self.exchange_bytes = 0
         # MGGCN_DIST_SELF_GATHER=1 (tests of the transport): run the all-gather with ONE rank too -- the only way to put
         # ProcessGroupNCCL's all_gather_into_tensor on a one-GPU box; by default a single rank exchanges nothing
         self.self_gather = os.environ.get("MGGCN_DIST_SELF_GATHER", "0") == "1"
@@ -339,6 +344,7 @@ class dist_context(host_comm):
         """out[rank*rows:(rank+1)*rows] = shard on every rank.  Returns a handle whose
         .wait(stream_id) orders the result before later work on that stream."""
         torch, dist = _torch(), _dist()
+        self.exchange_bytes += shard.numel() * shard.element_size()
         if self._nccl():
             with torch.cuda.stream(self.ctx.cuda_streams[stream_id]):
                 work = dist.all_gather_into_tensor(out, shard, group=self.group, async_op=True)
@@ -351,6 +357,8 @@ class dist_context(host_comm):
     def broadcast_rows(self, shard, out, root: int, stream_id: int):
         torch, dist = _torch(), _dist()
         src = dist.get_global_rank(self.group, root) if self.group is not None else root
+        if self.rank == root:
+            self.exchange_bytes += out.numel() * out.element_size()
         if self._nccl():
             with torch.cuda.stream(self.ctx.cuda_streams[stream_id]):
                 if self.rank == root:
@@ -385,6 +393,7 @@ class dist_context(host_comm):
         """Variable-size row exchange: rows [sum(send_rows[:s]), +send_rows[s]) of ``send`` go to rank s,
         ``recv`` receives recv_rows[s] rows from rank s, in rank order."""
         torch, dist = _torch(), _dist()
+        self.exchange_bytes += send.numel() * send.element_size()
         if self._nccl():
             with torch.cuda.stream(self.ctx.cuda_streams[stream_id]):
                 work = dist.all_to_all_single(recv, send, list(recv_rows), list(send_rows), group=self.group,
@@ -614,10 +623,18 @@ def load_rank_local(dctx: dist_context, dirname: str, chunks: Optional[int] = No
 
 
 class dist_sparse_linear:
-    """reference src/gcn.hpp:50-86 + the pipelined matmul src/cuda_utils.hpp:57-92."""
+    """reference src/gcn.hpp:50-86 + the pipelined matmul src/cuda_utils.hpp:57-92.
+
+    ``agg_dtype="bf16"``: the rank's shard is rounded ONCE per aggregation into ``agg_buffer`` (flat bf16 device tensor,
+    grown on demand; dist_gcn shares one among its layers); that image is the diagonal block's operand and what the
+    exchange sends, the receive buffers (``bcast_buffer``, ``bcast_buffer2``: flat torch.bfloat16 then) hold bf16 and
+    every SpMM is ops.spmm_bf16 with the plans of the fp32 schedule.  Same views element for element, same streams,
+    events and timers; C and the sums stay fp32."""
 
     def __init__(self, name: str, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix, bcast_buffer,
-                 bcast_buffer2, mode: str = "allgather"):
+                 bcast_buffer2, mode: str = "allgather", agg_dtype: str = "f32"):
+        self.agg_dtype = _check_agg_dtype(agg_dtype)
+        self.agg_buffer = None               # bf16: the shard image; dist_gcn hands every layer the model's
         self.name, self.A, self.A_T = name, A, A_T
         self.bcast = [bcast_buffer, bcast_buffer2]
         self.mode = mode
@@ -642,10 +659,22 @@ class dist_sparse_linear:
                     ctx.lib.mggcn_spmm_plan_reserved_cus(0)
         return pl
 
+    def _mm(self, ctx: context, M: csr_matrix, B, C: dn_matrix, plan, beta: float, flags: int) -> None:
+        """C = M . B + beta C with B as the schedule holds it: a dn_matrix (fp32) or a 2-D bf16 tensor"""
+        if self.agg_dtype == "f32":
+            ops._spmm(ctx, M, B, C, plan, 1.0, beta, flags)
+        else:
+            ops.spmm_bf16(ctx, M, B, C, plan, 1.0, beta, flags)
+
+    def _mat(self, n: int, d: int, buf):
+        """n x d over the front of a flat buffer: what a SpMM of this operator takes as B"""
+        return dn_matrix(n, d, buf) if self.agg_dtype == "f32" else buf[:n * d].view(n, d)
+
     def _run(self, dctx: dist_context, A: dist_row_csr_matrix, tag: str, B: dist_row_dn_matrix,
              C: dist_row_dn_matrix, discard: bool, flags: int) -> None:
         torch = _torch()
         ctx, P, r = dctx.ctx, dctx.P, dctx.rank
+        bf16 = self.agg_dtype == "bf16"
         self._shared_device = P > 1 and dctx.overlap
         name = self.name + tag
         beta = 0.0 if discard else 1.0
@@ -653,7 +682,22 @@ class dist_sparse_linear:
         rows = B.local.n()
         cs = dctx.bcast_stream_id()
         ctx.record(name + "0_matmul-spmm", 0)
-        ctx.wait(name + "0_matmul-spmm", cs)                   # comm stream sees the producer of B
+        if bf16:
+            # Round once, on the compute stream: the diagonal block's operand AND the send image of the exchange.  The
+            # scratch is shared by every aggregation of the model, so this write must come after the previous exchange
+            # has read it: in every mode the compute stream has by now passed that exchange's pend.wait(0) -- issued
+            # before its remote SpMMs, for every piece (allgather), the one all-to-all (halo, which read the pack; the
+            # pack itself ran on this stream) and every round (rounds) -- so plain stream order is enough.
+            if self.agg_buffer is None or self.agg_buffer.numel() < rows * d:
+                self.agg_buffer = torch.empty(max(rows * d, 1), dtype=torch.bfloat16, device=ctx.device)
+            shard = self.agg_buffer[:rows * d].view(rows, d)
+            ops.convert_bf16(ctx, B.local, shard)
+            ctx.record(name + "0_matmul-rounded", 0)
+            ctx.wait(name + "0_matmul-rounded", cs)            # comm stream sees the rounded shard
+            shard_t = shard
+        else:
+            ctx.wait(name + "0_matmul-spmm", cs)               # comm stream sees the producer of B
+            shard, shard_t = B.local, B.local.t
         if self.mode == "allgather":
             # the exchange, cut into K pieces of the shard (rows cb[c]..cb[c+1] of every rank): all K
             # all-gathers are queued on the comm stream at once and land one after the other
@@ -661,11 +705,11 @@ class dist_sparse_linear:
             ctx.record(name + "0_matmul-bcast-start", cs)
             # views of the receive buffer / of the shard per piece: built once per (matrix, operand, width) -- at
             # P = 8 the host issues ~30 collectives + ~200 launches per epoch against ~2.4 ms of device work
-            vkey = (tag, B.local.buffer(), d)
+            vkey = (tag, shard_t.data_ptr(), d)
             views = self._views.get(vkey)
             if views is None:
-                views = self._views[vkey] = [(dn_matrix(P * (cb[c + 1] - cb[c]), d, self.bcast[0][P * cb[c] * d:]),
-                                              B.local.t[cb[c]:cb[c + 1]]) for c in range(K)]
+                views = self._views[vkey] = [(self._mat(P * (cb[c + 1] - cb[c]), d, self.bcast[0][P * cb[c] * d:]),
+                                              shard_t[cb[c]:cb[c + 1]]) for c in range(K)]
             pend, gathered = [], []
             for c in range(K):
                 g, piece = views[c]
@@ -673,7 +717,7 @@ class dist_sparse_linear:
                 # one rank: nothing is remote, nobody reads the gathered copy -- and the "all-gather" would be a 119 MB
                 # copy kernel sharing the device with the local SpMM (profiles/r04_forced_dist_summary.md: the sweep
                 # round that meets it takes 500-700 us instead of 300)
-                pend.append(dctx.all_gather_rows(piece, g.t, cs) if (P > 1 or dctx.self_gather) else None)
+                pend.append(dctx.all_gather_rows(piece, g if bf16 else g.t, cs) if (P > 1 or dctx.self_gather) else None)
             prof = dctx.profile_exchange and (P > 1 or dctx.self_gather)
             if prof:                                           # comm-stream time of the whole exchange
                 for c in range(K):
@@ -682,8 +726,7 @@ class dist_sparse_linear:
                 ctx.register_timer(name + "matmul-exchange", name + "0_matmul-bcast-start", name + "matmul-exchange-end")
             # local block first: no dependency on the exchange
             last_local = flags if P == 1 else 0
-            ops._spmm(ctx, A.diag, B.local, C.local, self._plan(ctx, (tag, "diag"), A.diag, d), 1.0, beta,
-                      last_local)
+            self._mm(ctx, A.diag, shard, C.local, self._plan(ctx, (tag, "diag"), A.diag, d), beta, last_local)
             for c in range(K):                                 # piece c multiplies while piece c+1 is on the wire
                 if prof:                                       # how long the compute stream stalls for piece c
                     ctx.record(name + f"{c}_matmul-bcast-ready", 0)
@@ -694,28 +737,33 @@ class dist_sparse_linear:
                 ctx.record(name + f"{c}_matmul-bcast-finish", 0)
                 if P > 1:
                     blk = A.remote_chunks[c]
-                    ops._spmm(ctx, blk, gathered[c], C.local, self._plan(ctx, (tag, "remote", c), blk, d), 1.0,
-                              1.0, flags if c == K - 1 else 0)
+                    self._mm(ctx, blk, gathered[c], C.local, self._plan(ctx, (tag, "remote", c), blk, d), 1.0,
+                             flags if c == K - 1 else 0)
         elif self.mode == "halo":
             h = A.build_halo(ctx.device).halo
             n_send, n_recv = sum(h["send_rows"]), sum(h["recv_rows"])
             if self._halo_send is None or self._halo_send.numel() < max(n_send, 1) * d:
-                self._halo_send = torch.empty(max(n_send, 1) * d, dtype=torch.float32, device=ctx.device)
-            send = dn_matrix(max(n_send, 1), d, self._halo_send)
-            recv = dn_matrix(max(n_recv, 1), d, self.bcast[0])
-            ops.gather_rows(ctx, B.local, h["send_idx"], send)            # pack on the compute stream
+                self._halo_send = torch.empty(max(n_send, 1) * d, dtype=torch.bfloat16 if bf16 else torch.float32,
+                                              device=ctx.device)
+            send = self._mat(max(n_send, 1), d, self._halo_send)
+            recv = self._mat(max(n_recv, 1), d, self.bcast[0])
+            if bf16:                                                      # pack on the compute stream
+                ops.gather_rows_bf16(ctx, shard, h["send_idx"], send)
+            else:
+                ops.gather_rows(ctx, B.local, h["send_idx"], send)
+            send_t, recv_t = (send, recv) if bf16 else (send.t, recv.t)
             ctx.record(name + "0_matmul-halo-packed", 0)
             ctx.wait(name + "0_matmul-halo-packed", cs)
             ctx.record(name + "0_matmul-bcast-start", cs)
             pend = None
             if P > 1:
-                pend = dctx.all_to_all_rows(send.t[:n_send], recv.t[:n_recv], h["send_rows"], h["recv_rows"], cs)
+                pend = dctx.all_to_all_rows(send_t[:n_send], recv_t[:n_recv], h["send_rows"], h["recv_rows"], cs)
                 if dctx.profile_exchange:
                     pend.wait(cs)
                     ctx.record(name + "matmul-exchange-end", cs)
                     ctx.register_timer(name + "matmul-exchange", name + "0_matmul-bcast-start", name + "matmul-exchange-end")
-            ops._spmm(ctx, A.diag, B.local, C.local, self._plan(ctx, (tag, "diag"), A.diag, d), 1.0, beta,
-                      flags if P == 1 else 0)
+            self._mm(ctx, A.diag, shard, C.local, self._plan(ctx, (tag, "diag"), A.diag, d), beta,
+                     flags if P == 1 else 0)
             if P > 1:
                 if dctx.profile_exchange:
                     ctx.record(name + "0_matmul-bcast-ready", 0)
@@ -723,14 +771,14 @@ class dist_sparse_linear:
                 pend.wait(0)
                 ctx.record(name + "0_matmul-bcast-finish", 0)
                 blk = h["remote"]
-                ops._spmm(ctx, blk, recv, C.local, self._plan(ctx, (tag, "halo"), blk, d), 1.0, 1.0, flags)
+                self._mm(ctx, blk, recv, C.local, self._plan(ctx, (tag, "halo"), blk, d), 1.0, flags)
         else:  # reference schedule: round i = broadcast shard i || SpMM with block (r, i)
-            bufs = [dn_matrix(rows, d, self.bcast[0]), dn_matrix(rows, d, self.bcast[1])]
+            bufs = [self._mat(rows, d, self.bcast[0]), self._mat(rows, d, self.bcast[1])]
             for i in range(P):
                 if i > 1:
                     ctx.wait(name + f"{i - 1}_matmul-spmm", cs)      # double-buffer hazard (:66-67)
                 ctx.record(name + f"{i}_matmul-bcast-start", cs)
-                pend = dctx.broadcast_rows(B.local.t, bufs[i % 2].t, i, cs)
+                pend = dctx.broadcast_rows(shard_t, bufs[i % 2] if bf16 else bufs[i % 2].t, i, cs)
                 if dctx.profile_exchange:
                     pend.wait(cs)
                     ctx.record(name + f"{i}_matmul-exchange-end", cs)
@@ -740,8 +788,8 @@ class dist_sparse_linear:
                 pend.wait(0)
                 ctx.record(name + f"{i}_matmul-bcast-finish", 0)
                 blk = A.blocks[i]
-                ops._spmm(ctx, blk, bufs[i % 2], C.local, self._plan(ctx, (tag, i), blk, d), 1.0,
-                          beta if i == 0 else 1.0, flags if i == P - 1 else 0)
+                self._mm(ctx, blk, bufs[i % 2], C.local, self._plan(ctx, (tag, i), blk, d),
+                         beta if i == 0 else 1.0, flags if i == P - 1 else 0)
                 ctx.record(name + f"{i + 1}_matmul-spmm", 0)
         ctx.record(name + "end_matmul-spmm", 0)
         ctx.register_timer(name + "matmul-spmm", name + "0_matmul-spmm", name + "end_matmul-spmm")
@@ -817,10 +865,11 @@ class dist_gcn_layer(layer_body):
     def __init__(self, dctx: dist_context, name: str, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
                  in_: int, out: int, activation: bool, residual_layer: bool = False, backward_spmm: bool = True,
                  HW_buffer=None, bcast_buffer=None, bcast_buffer2=None, fused: bool = False,
-                 mode: str = "allgather"):
+                 mode: str = "allgather", agg_dtype: str = "f32"):
+        _check_agg_dtype(agg_dtype)
         torch = _torch()
         P, dev = dctx.P, dctx.ctx.device
-        self.A = dist_sparse_linear(name, A, A_T, bcast_buffer, bcast_buffer2, mode)
+        self.A = dist_sparse_linear(name, A, A_T, bcast_buffer, bcast_buffer2, mode, agg_dtype)
         lin = dist_row_linear(dctx, name, in_, out, backward_spmm, fused)
         res_lin = dist_row_linear(dctx, name, in_, out, backward_spmm, False) if residual_layer and in_ != out else None
         mn = min(in_, out)
@@ -909,7 +958,9 @@ class dist_gcn:
     receive buffers shared by all layers (:1016-1021); layers get (A_T, A) (:1023)."""
 
     def __init__(self, dctx: dist_context, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
-                 sizes: Sequence[int], residual_layer: bool = False, fused: bool = True, mode: str = "allgather"):
+                 sizes: Sequence[int], residual_layer: bool = False, fused: bool = True, mode: str = "allgather",
+                 agg_dtype: str = "f32"):
+        self.agg_dtype = _check_agg_dtype(agg_dtype)
         torch = _torch()
         P, dev = dctx.P, dctx.ctx.device
         self.loss_layer = dist_row_softmax_cross_entropy_loss(f"{len(sizes) - 1}_", residual_layer, fused)
@@ -919,13 +970,20 @@ class dist_gcn:
         # all-gather mode keeps the whole gathered B resident (n x max_d: 119 MB on Reddit,
         # nothing next to 288 GB); rounds mode needs the reference's two shard-sized buffers
         big = nmax * max_d if mode in ("allgather", "halo") else nmax * max_d // P
-        self.bcast_buffer = torch.empty(big, dtype=torch.float32, device=dev)
-        self.bcast_buffer2 = torch.empty(nmax * max_d // P, dtype=torch.float32, device=dev)
+        # bf16 aggregation: the receive buffers hold bf16 (half the bytes), and one bf16 image of the rank's shard, rounded
+        # once per aggregation, is both the diagonal block's operand and what the exchange sends (shared by the layers,
+        # like gcn.agg_buffer: n/P x the widest SpMM width)
+        xdt = torch.bfloat16 if agg_dtype == "bf16" else torch.float32
+        self.bcast_buffer = torch.empty(big, dtype=xdt, device=dev)
+        self.bcast_buffer2 = torch.empty(nmax * max_d // P, dtype=xdt, device=dev)
+        self.agg_buffer = torch.empty(max(nmax * max_d // P, 1), dtype=torch.bfloat16, device=dev) \
+            if agg_dtype == "bf16" else None
         self.layers_: List[dist_gcn_layer] = []
         for i in range(1, len(sizes)):
             self.layers_.append(dist_gcn_layer(dctx, f"{i - 1}_", A_T, A, sizes[i - 1], sizes[i],
                                                i + 1 < len(sizes), residual_layer, i != 1, self.HW_buffer,
-                                               self.bcast_buffer, self.bcast_buffer2, fused, mode))
+                                               self.bcast_buffer, self.bcast_buffer2, fused, mode, agg_dtype))
+            self.layers_[-1].A.agg_buffer = self.agg_buffer
         link_fused_backward(self.layers_, fused)
         self.fused, self._adam = fused, None
         self._loss_host = None                                 # pinned host copy of the epoch's global loss sums (train_step)

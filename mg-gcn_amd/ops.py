@@ -247,6 +247,18 @@ def gather_rows(ctx: context, src: dn_matrix, indices, dst: dn_matrix, stream_id
                                   dst.buffer(), dst.m())
 
 
+def gather_rows_bf16(ctx: context, src16, indices, dst16, stream_id: int = 0) -> None:
+    """dst16[k, :] = src16[indices[k], :] on bf16 bit patterns (mggcn_gather_rows_bf16): the halo pack of a shard that
+    is already rounded.  src16 / dst16: 2-D device tensors of 2-byte elements, any row stride (see _bf16_view);
+    indices: device uint32 tensor viewed as int32 storage."""
+    s_ptr, _, sm, ld_s = _bf16_view(src16, "gather_rows_bf16 src")
+    d_ptr, dn, dm, ld_d = _bf16_view(dst16, "gather_rows_bf16 dst")
+    n_idx = int(indices.numel())
+    _req(dn >= n_idx and dm == sm, "gather_rows_bf16 shape")
+    ctx.set()
+    ctx.lib.mggcn_gather_rows_bf16(ctx.stream(stream_id), s_ptr, ld_s, indices.data_ptr(), n_idx, sm, d_ptr, ld_d)
+
+
 # ---- element-wise / row kernels: src/cuda_utils.hpp:470-748 wrappers -----------------
 def leaky_relu_forward(ctx: context, in_: dn_matrix, out: dn_matrix, alpha: float = 0.01) -> None:
     _req(in_.shape() == out.shape(), "shape mismatch")
