@@ -298,6 +298,18 @@ void mggcn_adam_final_f32(mggcn_stream_t stream, float *param, const float *m, c
 void mggcn_axpy_f32(mggcn_stream_t stream, const float *A, float *B, float alpha, size_t size);
 /* cublasSscal   (src/cuda_utils.hpp:373-381)  mat *= scalar */
 void mggcn_scale_mat_f32(mggcn_stream_t stream, float *mat, float scalar, size_t size);
+/* Dropout with a mask that is never stored (opt-in; the reference has no dropout).  The matrix is [size / m x m],
+ * contiguous; in == out is allowed; row0 is the GLOBAL index of its first row.  Element (global row r, column c):
+ *   words = Philox4x32-10(counter = (c >> 2, r & 0xffffffff, r >> 32, dropout_stream), key = (seed & 0xffffffff, seed >> 32))
+ *   out   = words[c & 3] >= threshold ? in * scale : +0.0f      (+0.0 also where in is NaN or +-inf; one fp32 multiply)
+ * with the usual constants (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; ten rounds).
+ * The host computes threshold = (uint32) floor(p * 2^32) and scale = (float)(1 / (1 - p)) in double for 0 <= p < 1; the
+ * kernel never sees p.  The mask is a pure function of (seed, dropout_stream, r, c): it does not depend on the grid, on
+ * the alignment of the pointers (a float4 path when m % 4 == 0 and both are 16-byte aligned, an element path otherwise)
+ * or on row0's split of the rows -- the call on rows [a, b) with row0 = a gives rows [a, b) of the whole call -- and the
+ * backward pass of dropout is the same call on the gradient.  size == 0 returns; m > 0 and size % m == 0. */
+void mggcn_dropout_f32(mggcn_stream_t stream, const float *in, float *out, size_t size, size_t m, uint64_t row0,
+                       uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream);
 /* cublasSasum   (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

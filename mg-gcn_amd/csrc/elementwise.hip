@@ -658,6 +658,84 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const mggcn_adam_tensor
     }
 }
 
+// ---- dropout: the mask is never stored --------------------------------------
+// Philox4x32-10 (Salmon et al., SC'11) on counter (c >> 2, row low, row high, stream) and key (seed low, seed high): word
+// c & 3 of the output decides column c of global row `row`.  A pure function of (seed, stream, row, column): the backward
+// pass calls the same kernel on the gradient and gets the same mask, a row shard gets the rows of the whole matrix's mask.
+// The 32 x 32 -> 64 products are written as one 64-bit multiply each (v_mad_u64_u32: both halves from one instruction).
+struct philox4 { uint32_t w[4]; };
+
+__device__ __forceinline__ philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int round = 0; round < 10; round++) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return {{c0, c1, c2, c3}};
+}
+
+__device__ __forceinline__ float dropout_one(float x, uint32_t word, uint32_t threshold, float scale) {
+    return word >= threshold ? x * scale : 0.f;       // a select: +0.0 also where x is NaN or an infinity
+}
+
+// Both kernels walk (row, column group) without a division in the loop: a grid step is step_rows rows and step_cols
+// units (both from the host: the grid's thread count over the units per row), with one carry.  The first unit of a
+// thread is below 2^19 (stream_grid), so its division is a 32-bit one; a row of 2^32 units or more (q clamped) holds it
+// whole.
+struct dropout_walk {
+    uint64_t row;        // local row
+    uint64_t col;        // unit inside the row
+    __device__ dropout_walk(size_t q) {
+        const uint32_t i0 = blockIdx.x * blockDim.x + threadIdx.x;
+        const uint32_t q32 = q > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)q;
+        row = i0 / q32;
+        col = i0 % q32;
+    }
+    __device__ void step(size_t q, uint64_t step_rows, uint64_t step_cols) {
+        row += step_rows;
+        col += step_cols;
+        if (col >= q) { col -= q; row++; }
+    }
+};
+
+// four columns per lane: one generator call serves the lane's float4 (q4 = m / 4 column groups per row)
+__global__ __launch_bounds__(256) void dropout_vec4_kernel(const float4 *in, float4 *out, size_t size4, size_t q4,
+                                                           uint64_t step_rows, uint64_t step_cols, uint64_t row0,
+                                                           uint32_t threshold, float scale, uint32_t k0, uint32_t k1,
+                                                           uint32_t dstream) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    dropout_walk at(q4);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < size4; i += stride) {
+        float4 x = in[i];
+        const uint64_t row = row0 + at.row;
+        const philox4 r = philox4x32_10((uint32_t)at.col, (uint32_t)row, (uint32_t)(row >> 32), dstream, k0, k1);
+        x.x = dropout_one(x.x, r.w[0], threshold, scale);
+        x.y = dropout_one(x.y, r.w[1], threshold, scale);
+        x.z = dropout_one(x.z, r.w[2], threshold, scale);
+        x.w = dropout_one(x.w, r.w[3], threshold, scale);
+        out[i] = x;
+        at.step(q4, step_rows, step_cols);
+    }
+}
+
+// any width, any alignment: a lane computes its column group's call and keeps word c & 3
+__global__ __launch_bounds__(256) void dropout_kernel(const float *in, float *out, size_t size, size_t m, uint64_t step_rows,
+                                                      uint64_t step_cols, uint64_t row0, uint32_t threshold, float scale,
+                                                      uint32_t k0, uint32_t k1, uint32_t dstream) {
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    dropout_walk at(m);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < size; i += stride) {
+        const uint64_t row = row0 + at.row;
+        const philox4 r = philox4x32_10((uint32_t)(at.col >> 2), (uint32_t)row, (uint32_t)(row >> 32), dstream, k0, k1);
+        const uint32_t lane = (uint32_t)at.col & 3u;
+        const uint32_t word = lane == 0 ? r.w[0] : lane == 1 ? r.w[1] : lane == 2 ? r.w[2] : r.w[3];
+        out[i] = dropout_one(in[i], word, threshold, scale);
+        at.step(m, step_rows, step_cols);
+    }
+}
+
 }  // namespace
 
 // ============================ C ABI =========================================
@@ -802,6 +880,27 @@ MGGCN_API void mggcn_axpy_f32(mggcn_stream_t stream, const float *A, float *B, f
 
 MGGCN_API void mggcn_scale_mat_f32(mggcn_stream_t stream, float *mat, float scalar, size_t size) {
     launch_map1(as_stream(stream), mat, mat, size, Scal{scalar});
+}
+
+MGGCN_API void mggcn_dropout_f32(mggcn_stream_t stream, const float *in, float *out, size_t size, size_t m, uint64_t row0,
+                                 uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream) {
+    if (!size) return;
+    MGGCN_REQUIRE(m > 0 && size % m == 0, "size must be n_rows * m");
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    if (m % 4 == 0 && aligned16(in) && aligned16(out)) {
+        const size_t size4 = size / 4, q4 = m / 4;
+        const unsigned grid = stream_grid(size4);
+        const size_t threads = (size_t)grid * 256;
+        hipLaunchKernelGGL(dropout_vec4_kernel, dim3(grid), dim3(256), 0, as_stream(stream),
+                           reinterpret_cast<const float4 *>(in), reinterpret_cast<float4 *>(out), size4, q4,
+                           (uint64_t)(threads / q4), (uint64_t)(threads % q4), row0, threshold, scale, k0, k1, dropout_stream);
+    } else {
+        const unsigned grid = stream_grid(size);
+        const size_t threads = (size_t)grid * 256;
+        hipLaunchKernelGGL(dropout_kernel, dim3(grid), dim3(256), 0, as_stream(stream), in, out, size, m,
+                           (uint64_t)(threads / m), (uint64_t)(threads % m), row0, threshold, scale, k0, k1, dropout_stream);
+    }
+    MGGCN_CHECK_LAUNCH();
 }
 
 // The reduction scratch above belongs to a (device, stream) pair: mggcn_stream_destroy releases it with the stream;

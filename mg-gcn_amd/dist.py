@@ -44,8 +44,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, ops
-from .gcn import (_check_agg_dtype, adam_update_all, check_counts, check_sets, layer_body, linear, link_fused_backward,
-                  softmax_cross_entropy_loss, split_counts)
+from .gcn import (_check_agg_dtype, adam_update_all, check_counts, check_sets, dropout_option, layer_body, linear,
+                  link_fused_backward, softmax_cross_entropy_loss, split_counts)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -882,6 +882,7 @@ class dist_gcn_layer(layer_body):
                             shard(A.m(), mn, HW_buffer), shard(A.n(), out, self.AHW_buffer),
                             shard(A_T.n(), mn, HW_buffer), shard(A_T.n(), in_, self.AHW_buffer),
                             activation, backward_spmm, fused)
+        self.row0 = int(A.p[dctx.rank])           # dropout: this rank draws ITS rows of the global mask
 
     def __call__(self, dctx: dist_context, H: dist_row_dn_matrix) -> dist_row_dn_matrix:
         return _wrap_local(layer_body.__call__(self, dctx.ctx, H.local), self.AHW.n() * dctx.P)
@@ -953,13 +954,18 @@ def _repl_view(dn):
     return w
 
 
-class dist_gcn:
+class dist_gcn(dropout_option):
     """reference src/gcn.hpp:997-1056 (row_partition = true): per-GPU HW_buffer and two
-    receive buffers shared by all layers (:1016-1021); layers get (A_T, A) (:1023)."""
+    receive buffers shared by all layers (:1016-1021); layers get (A_T, A) (:1023).
+
+    ``dropout=p`` / set_dropout(p, seed, epoch): see gcn.dropout_option.  Every rank calls it with the same arguments;
+    a rank drops its rows of the mask the single-GPU model draws (row0 = p[rank] of the partition), on the compute
+    stream ahead of whatever the exchange waits for, and nothing is communicated for it."""
 
     def __init__(self, dctx: dist_context, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
                  sizes: Sequence[int], residual_layer: bool = False, fused: bool = True, mode: str = "allgather",
-                 agg_dtype: str = "f32"):
+                 agg_dtype: str = "f32", dropout: float = 0.0):
+        self._init_dropout(dropout, len(sizes) - 1)          # option checks come before any device work
         self.agg_dtype = _check_agg_dtype(agg_dtype)
         torch = _torch()
         P, dev = dctx.P, dctx.ctx.device
@@ -1018,7 +1024,8 @@ class dist_gcn:
             raise ValueError("split_metrics() needs set_splits(dctx, Sd) first")
         return self.loss_layer.split_metrics()
 
-    def __call__(self, dctx, H):
+    def __call__(self, dctx, H, training: bool = False):
+        """the forward pass; ``training``: a training forward (train_forward / train_step), the only kind that drops"""
         if self._plan_wants:
             # with more than one rank these SpMMs run while RCCL's kernels share the device: launch rounds that leave (at least) 12
             # CUs' worth of wave slots free (include/mggcn.h: mggcn_spmm_plan_reserved_cus; profiles/r04_forced_dist_summary.md)
@@ -1031,12 +1038,13 @@ class dist_gcn:
                 if shared:
                     dctx.ctx.lib.mggcn_spmm_plan_reserved_cus(0)
             self._plan_wants = []
+        self._arm_dropout(training)
         for layer in self.layers_:
             H = layer(dctx, H)
         return H
 
     def train_forward(self, dctx: dist_context, H: dist_row_dn_matrix, Y: dist_row_dn_matrix):
-        H = self(dctx, H)
+        H = self(dctx, H, training=True)
         return self.loss_layer(dctx, H, Y)
 
     def backward(self, dctx: dist_context) -> None:
@@ -1061,7 +1069,7 @@ class dist_gcn:
         """forward + loss + backward + Adam with ONE host synchronisation and the loss all-reduce at the
         end of the epoch (see gcn.train_step); the reference's loop body is src/main.cpp:159-166."""
         torch = _torch()
-        out = self(dctx, H)
+        out = self(dctx, H, training=True)
         self.loss_layer(dctx, out, Y, sync=False)
         # The loss sums (two, or the eight of the splits) ride on the LAST layer's gradient all-reduce (eight spare floats
         # behind [G_W | G_b]) instead of a collective and a device-to-host copy of their own after the epoch's synchronisation:

@@ -17,6 +17,10 @@ kernels -- identical math, fewer passes:
 ``agg_dtype="bf16"`` (opt-in; default ``"f32"``) stores the gathered operand of every SpMM in bf16: each aggregation
 rounds its dense input to bf16 into one model-owned scratch and multiplies with the bf16 SpMM, C = A . bf16(B), sums
 and everything else in fp32 (GEMMs, loss, weights, gradients, Adam).
+
+``dropout=p`` (opt-in; default 0: nothing is launched) drops the input of every layer but the first during a training
+forward, with a counter-based mask that is never stored (ops.dropout, include/mggcn.h: mggcn_dropout_f32): the backward
+pass regenerates it, a row-partitioned run draws the single-GPU run's mask, and numpy reproduces it bit for bit.
 """
 from __future__ import annotations
 
@@ -43,6 +47,55 @@ def _check_agg_dtype(agg_dtype: str) -> str:
     if agg_dtype not in AGG_DTYPES:
         raise ValueError(f"agg_dtype must be one of {AGG_DTYPES}, not {agg_dtype!r}")
     return agg_dtype
+
+
+DROPOUT_MAX_LAYERS = 64            # the dropout stream of a call is epoch * 64 + the consuming layer's index
+
+
+def check_dropout(p: float, n_layers: int):
+    """option checking of dropout, before any device work: (threshold, scale) of ops.dropout_params, and no more than
+    DROPOUT_MAX_LAYERS layers when p > 0"""
+    params = ops.dropout_params(p)
+    if float(p) > 0.0 and n_layers > DROPOUT_MAX_LAYERS:
+        raise ValueError(f"dropout supports at most {DROPOUT_MAX_LAYERS} layers, the model has {n_layers}")
+    return params
+
+
+class dropout_option:
+    """set_dropout of gcn and dist.dist_gcn (opt-in; the reference has no dropout).
+
+    Dropout applies to the INPUT of every layer but the first: the activated output of the layer below, after any
+    residual add, in place in that layer's AHW buffer.  The features X are the caller's buffer and are never dropped.
+    The mask of layer l in training forward number e (counted from set_dropout; ``dropout_epoch`` is the next one) is the
+    one of ops.dropout with (seed, stream = (e * 64 + l) mod 2^32, row0 = the global index of this GPU's first row);
+    backward() applies the same call to the gradient that layer returns.  Only train_forward / train_step drop: a plain
+    call of the model and evaluate() never do.  With splits on, split_metrics() of a training epoch therefore reports
+    the DROPPED forward's validation and test numbers; evaluate() gives the clean ones."""
+
+    def _init_dropout(self, p: float, n_layers: int) -> None:
+        self._dropout_layers = int(n_layers)
+        self._dropout_params = check_dropout(p, n_layers)
+        self.dropout_p, self.dropout_seed, self.dropout_epoch = float(p), 0, 0
+
+    def set_dropout(self, p: float, seed: int = 0, epoch: int = 0) -> None:
+        """p in [0, 1): the drop probability (0 switches dropout off: no kernel is launched); seed: 64 bits; epoch: the
+        number the next training forward gets (set_dropout(p, seed, epoch=e) replays training forward e).  ValueError for
+        a p outside [0, 1) or a model of more than 64 layers, before any device work."""
+        self._dropout_params = check_dropout(p, self._dropout_layers)
+        self.dropout_p = float(p)
+        self.dropout_seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        self.dropout_epoch = int(epoch)
+
+    def _arm_dropout(self, training: bool) -> None:
+        """hands every layer but the first its call of this forward (None: no dropout); a training forward takes the
+        current epoch number and moves it on"""
+        on = bool(training) and self.dropout_p > 0.0
+        threshold, scale = self._dropout_params
+        for li, layer in enumerate(self.layers_):
+            layer.dropout = ((threshold, scale, self.dropout_seed, (self.dropout_epoch * DROPOUT_MAX_LAYERS + li) & 0xFFFFFFFF)
+                             if on and li > 0 else None)
+        if on:
+            self.dropout_epoch += 1
 
 
 class sparse_linear:
@@ -235,11 +288,29 @@ class layer_body:
         self.hoist_input = False
         self._AX: Optional[dn_matrix] = None
         self._AX_key = None
+        # dropout of my input (set by the model before every forward, see dropout_option): None, or (threshold, scale,
+        # seed, stream) of ops.dropout_raw; row0: the global index of my first row (the row partition sets its shard's)
+        self.dropout = None
+        self.row0 = 0
+
+    def _drop(self, ctx: context, M: dn_matrix, tag: str) -> None:
+        """M = dropout(M) in place with this forward's mask: H on the way up ("0"), G_out on the way down ("1")"""
+        n = self.name
+        threshold, scale, seed, stream = self.dropout
+        ctx.record(n + tag + "_0_dropout", 0)
+        ops.dropout_raw(ctx, M, M, threshold, scale, seed, stream, self.row0)
+        ctx.record(n + tag + "_1_dropout", 0)
+        ctx.register_timer(n + tag + "_dropout", n + tag + "_0_dropout", n + tag + "_1_dropout")
 
     def gemm_first(self) -> bool:
         return self.HW.m() == self.AHW.m()        # out <= in (gcn.hpp:439)
 
     def __call__(self, ctx: context, H: dn_matrix) -> dn_matrix:
+        if self.dropout is not None:
+            # In place in the AHW buffer of the layer below.  Its backward reads that buffer for the SIGN of its
+            # activation only (leaky_relu_backward, or the epilogue of my G_out GEMM): scaling by 1 / (1 - p) > 0 keeps
+            # it, and where the element was dropped my backward returns a zero gradient whatever leaky_relu'(0) says.
+            self._drop(ctx, H, "0")
         self.H = H
         n = self.name
         act_done = False
@@ -308,6 +379,8 @@ class layer_body:
             self.res_lin.backward(ctx, G, G_out, False)
         elif self.residual_layer:
             ops.axpy(ctx, G, G_out, 1.0)
+        if self.dropout is not None:              # last: after the GEMM epilogue's leaky_relu' and the residual add
+            self._drop(ctx, G_out, "1")
         return G_out
 
     def linears(self):
@@ -591,13 +664,17 @@ def adam_update_all(ctx: context, lins, state, lr: float, beta1: float, beta2: f
     return state
 
 
-class gcn:
+class gcn(dropout_option):
     """reference src/gcn.hpp:937-995.  The constructor column-normalises A, builds
-    A_T and hands (A_T, A) to the layers -- forward multiplies by A_T (:946-955)."""
+    A_T and hands (A_T, A) to the layers -- forward multiplies by A_T (:946-955).
+
+    ``dropout=p`` / set_dropout(p, seed, epoch): see dropout_option -- the input of every layer but the first is dropped
+    in train_forward / train_step; the features X are the caller's buffer and are not dropped."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], residual_layer: bool = False,
                  weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None, fused: bool = True,
-                 hoist_first_aggregation: bool = False, agg_dtype: str = "f32"):
+                 hoist_first_aggregation: bool = False, agg_dtype: str = "f32", dropout: float = 0.0):
+        self._init_dropout(dropout, len(sizes) - 1)          # option checks come before any device work
         torch = _torch()
         self.agg_dtype = _check_agg_dtype(agg_dtype)
         if self.agg_dtype != "f32" and hoist_first_aggregation:
@@ -664,21 +741,25 @@ class gcn:
 
     def split_metrics(self):
         """every split's (loss, acc) of the last epoch, see softmax_cross_entropy_loss.split_metrics; call after
-        train_forward / train_step (they synchronise)"""
+        train_forward / train_step (they synchronise).  With dropout on these are the numbers of the DROPPED training
+        forward, validation and test included: evaluate() gives the clean ones."""
         if self.loss_layer.S is None:
             raise ValueError("split_metrics() needs set_splits(S) first")
         return self.loss_layer.split_metrics()
 
-    def __call__(self, ctx: context, H: dn_matrix) -> dn_matrix:
+    def __call__(self, ctx: context, H: dn_matrix, training: bool = False) -> dn_matrix:
+        """the forward pass; ``training``: a training forward (train_forward / train_step pass True), the only kind
+        that drops -- a plain call and evaluate() never do"""
         if self._plan_wants:                          # first call: the context (device) is known now
             ops.prebuild_plans(ctx, self._plan_wants)
             self._plan_wants = []
+        self._arm_dropout(training)
         for layer in self.layers_:
             H = layer(ctx, H)
         return H
 
     def train_forward(self, ctx: context, H: dn_matrix, Y: dn_matrix):
-        H = self(ctx, H)
+        H = self(ctx, H, training=True)
         return self.loss_layer(ctx, H, Y)
 
     def backward(self, ctx: context) -> None:
@@ -692,7 +773,7 @@ class gcn:
         adam_update, sync) with ONE host synchronisation: the loss / accuracy scalars are read after
         the epoch's last kernel instead of between forward and backward (the reference blocks inside
         its loss layer, src/gcn.hpp:816-817, and leaves the GPU idle while the host catches up)."""
-        out = self(ctx, H)
+        out = self(ctx, H, training=True)
         self.loss_layer(ctx, out, Y, sync=False)
         self.backward(ctx)
         self.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)

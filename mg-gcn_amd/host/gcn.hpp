@@ -16,6 +16,7 @@
 #include <numeric>
 #include <optional>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "dist_matrix.hpp"
@@ -352,6 +353,21 @@ protected:
     // fused backward (set by the model): mask_input_grad -- my G_out GEMM applies leaky_relu'(H) of the layer
     // below; grad_premasked -- the G I receive already carries my own activation's mask
     bool mask_input_grad = false, grad_premasked = false;
+    // dropout of my input (gcn::set_dropout; single GPU only): set by the model before every forward, empty = none.  In
+    // place in the AHW buffer of the layer below: its backward reads that buffer for the SIGN of its activation only,
+    // which scaling by 1 / (1 - p) > 0 keeps, and a dropped element gets a zero gradient from the call in backward().
+    std::optional<dropout_call> drop;
+
+    void apply_dropout(ctx_t ctx, dn_t M, const std::string &tag) {
+        if constexpr (std::is_same_v<ctx_t, context>) {
+            ctx.record(name + tag + "_0_dropout", 0);
+            dropout(ctx, M, M, *drop);
+            ctx.record(name + tag + "_1_dropout", 0);
+            ctx.register_timer(name + tag + "_dropout", name + tag + "_0_dropout", name + tag + "_1_dropout");
+        } else {
+            throw std::invalid_argument("dropout is single-GPU only in the C++ layer");
+        }
+    }
 
     gcn_layer_body(std::string name, agg_t A, linear_t lin, std::optional<linear_t> res_lin, bool residual_layer, bool activation,
                    bool backward_spmm, bool fused)
@@ -371,41 +387,8 @@ protected:
         return false;
     }
 
-    // reference :484-487: the residual branch sees the incoming (unmasked) gradient and adds to G_out
-    dn_t residual_backward(ctx_t ctx, dn_t G, dn_t out) {
-        if (res_lin) res_lin->backward(ctx, G, out, false);
-        else if (residual_layer) axpy(ctx, G, out, (r_t)1);
-        return out;
-    }
-
-public:
-    bool gemm_first() const { return HW.m() == AHW.m(); }           // out <= in (reference :439)
-    bool has_activation() const { return activation; }
-    bool has_residual() const { return residual_layer; }
-    bool propagates() const { return lin.has_backward_out(); }
-    void set_fused_backward(bool mask_input, bool premasked) { if (mask_input) mask_input_grad = true; if (premasked) grad_premasked = true; }
-    linear_t &linear_layer() { return lin; }
-    std::vector<linear_t *> linears() {
-        std::vector<linear_t *> v{&lin};
-        if (res_lin) v.push_back(&*res_lin);
-        return v;
-    }
-
-    auto operator()(ctx_t ctx, dn_t H) {
-        this->H = H;
-        const bool act_done = aggregate_linear(ctx, H);
-        if (activation && !act_done) {
-            ctx.record(name + "0_0_activation", 0);
-            leaky_relu_forward(ctx, AHW, AHW);
-            ctx.record(name + "0_1_activation", 0);
-            ctx.register_timer(name + "0_activation", name + "0_0_activation", name + "0_1_activation");
-        }
-        if (res_lin) (*res_lin)(ctx, H, AHW, false);          // reference :453-456
-        else if (residual_layer) axpy(ctx, H, AHW, (r_t)1);
-        return AHW;
-    }
-
-    auto backward(ctx_t ctx, dn_t G) {
+    // the backward pass up to the gradient of my input (reference :460-489)
+    dn_t input_gradient(ctx_t ctx, dn_t G) {
         auto T = G;
         if (activation && !grad_premasked) {
             ctx.record(name + "1_0_activation", 0);
@@ -424,6 +407,48 @@ public:
         lin.backward(ctx, T, G_HW);
         if (backward_spmm) { A.backward(ctx, G_HW, G_out); return residual_backward(ctx, G, G_out); }
         return residual_backward(ctx, G, G_HW);
+    }
+
+    // reference :484-487: the residual branch sees the incoming (unmasked) gradient and adds to G_out
+    dn_t residual_backward(ctx_t ctx, dn_t G, dn_t out) {
+        if (res_lin) res_lin->backward(ctx, G, out, false);
+        else if (residual_layer) axpy(ctx, G, out, (r_t)1);
+        return out;
+    }
+
+public:
+    bool gemm_first() const { return HW.m() == AHW.m(); }           // out <= in (reference :439)
+    bool has_activation() const { return activation; }
+    bool has_residual() const { return residual_layer; }
+    bool propagates() const { return lin.has_backward_out(); }
+    void set_fused_backward(bool mask_input, bool premasked) { if (mask_input) mask_input_grad = true; if (premasked) grad_premasked = true; }
+    void set_dropout_call(std::optional<dropout_call> d) { drop = d; }
+    linear_t &linear_layer() { return lin; }
+    std::vector<linear_t *> linears() {
+        std::vector<linear_t *> v{&lin};
+        if (res_lin) v.push_back(&*res_lin);
+        return v;
+    }
+
+    auto operator()(ctx_t ctx, dn_t H) {
+        if (drop) apply_dropout(ctx, H, "0");
+        this->H = H;
+        const bool act_done = aggregate_linear(ctx, H);
+        if (activation && !act_done) {
+            ctx.record(name + "0_0_activation", 0);
+            leaky_relu_forward(ctx, AHW, AHW);
+            ctx.record(name + "0_1_activation", 0);
+            ctx.register_timer(name + "0_activation", name + "0_0_activation", name + "0_1_activation");
+        }
+        if (res_lin) (*res_lin)(ctx, H, AHW, false);          // reference :453-456
+        else if (residual_layer) axpy(ctx, H, AHW, (r_t)1);
+        return AHW;
+    }
+
+    auto backward(ctx_t ctx, dn_t G) {
+        auto out = input_gradient(ctx, G);
+        if (drop) apply_dropout(ctx, out, "1");      // last: after the GEMM epilogue's leaky_relu' and the residual add
+        return out;
     }
 
     void finish_backward(const ctx_t ctx) { for (auto *l : linears()) l->finish_backward(ctx); }
@@ -826,14 +851,28 @@ public:
         }
     }
 
+    // the plain forward never drops; train_forward is the training forward
     auto operator()(const context ctx, dn_matrix<r_t> H) {
-        for (auto &layer : layers_) H = layer(ctx, H);
-        return H;
+        arm_dropout(false);
+        return forward(ctx, H);
     }
     auto train_forward(const context ctx, dn_matrix<r_t> H, dn_matrix<std::int32_t> Y) {
-        H = operator()(ctx, H);
+        arm_dropout(true);
+        H = forward(ctx, H);
         return loss_layer(ctx, H, Y);
     }
+    // Dropout (opt-in; the reference has none): train_forward drops the input of every layer but the first -- the
+    // activated output of the layer below, in place; the features are the caller's buffer and are not dropped -- with the
+    // mask of mggcn_dropout_f32 for (seed, stream = epoch * 64 + layer), never stored: backward() regenerates it.  epoch
+    // counts the train_forward calls since set_dropout.  p = 0 switches it off (nothing is launched);
+    // std::invalid_argument for a p outside [0, 1) or more than 64 layers, before any device work.
+    void set_dropout(double p, std::uint64_t seed = 0) {
+        const auto d = dropout_params(p, seed);
+        mggcn_require(p == 0.0 || layers_.size() <= 64, "dropout supports at most 64 layers");
+        dropout_ = p > 0.0 ? std::make_optional(d) : std::nullopt;
+        dropout_epoch_ = 0;
+    }
+    std::size_t dropout_epoch() const { return dropout_epoch_; }
     // Train on one split (opt-in; the reference loads sets.bin and ignores it, src/main.cpp:85): S[i] is vertex i's set
     // (0 train / 1 validation / 2 test, anything else in no split).  From here on train_forward returns the loss and
     // accuracy of train_set; split_metrics() has every split's pair of the last epoch (train, val, test, other) from the
@@ -869,9 +908,26 @@ public:
     auto &layers() { return layers_; }
 
 private:
+    auto forward(const context ctx, dn_matrix<r_t> H) {
+        for (auto &layer : layers_) H = layer(ctx, H);
+        return H;
+    }
+    // hands every layer but the first its call of this forward; a training forward takes the epoch number and moves it on
+    void arm_dropout(bool training) {
+        const bool on = training && dropout_;
+        for (std::size_t l = 0; l < layers_.size(); l++) {
+            std::optional<dropout_call> d;
+            if (on && l > 0) { d = dropout_; d->stream = (std::uint32_t)(dropout_epoch_ * 64 + l); }
+            layers_[l].set_dropout_call(d);
+        }
+        if (on) dropout_epoch_++;
+    }
+
     bool fused_ = true;
     adam_table<r_t> adam_;
     r_t adam_wd_ = 0;
+    std::optional<dropout_call> dropout_;
+    std::size_t dropout_epoch_ = 0;
 };
 
 template <bool row_partition, typename x_t, typename v_t, typename r_t>

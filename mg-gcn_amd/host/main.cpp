@@ -17,7 +17,9 @@
 // operand in bf16 (f32 or unset: the reference's fp32); MGGCN_TRAIN_SET=0|1|2 trains on that split of sets.bin (0 train /
 // 1 validation / 2 test; unset: the reference's loss over all vertices): the epoch line reports the training split and
 // a second line, "[mggcn splits] <e> train <loss> <acc> val <loss> <acc> test <loss> <acc>", every split;
-// MGGCN_TIMING=1 prints the start-up stages.
+// MGGCN_DROPOUT=<p> (single GPU, not -R 1; 0 <= p < 1, unset or 0: none) drops the input of every layer but the first in
+// the training forward, with the counter-based mask of mggcn_dropout_f32 for seed MGGCN_DROPOUT_SEED=<u64> (default 0);
+// epoch e of the run is dropout epoch e; MGGCN_TIMING=1 prints the start-up stages.
 #include <unistd.h>
 
 #include <chrono>
@@ -55,6 +57,8 @@ static int help_() {
                  "Environment:\n"
                  "    MGGCN_TRAIN_SET=0|1|2 : train on that split of sets.bin (0 train, 1 validation, 2 test) and report\n"
                  "                            every split per epoch; unset: loss and accuracy over all vertices\n"
+                 "    MGGCN_DROPOUT=<p>     : drop the input of every layer but the first with probability p in [0, 1)\n"
+                 "                            (single GPU); MGGCN_DROPOUT_SEED=<u64> picks the masks (default 0)\n"
                  "Arguments:\n"
                  "    train <dir> <k> <h1> ... <hk> : dataset directory, number of hidden layers and their widths\n";
     return EXIT_SUCCESS;
@@ -95,6 +99,22 @@ static bool env_is(const char *name, const char *value) {
     return s && std::string(s) == value;
 }
 
+// the whole string as a number, or an arg_error naming the variable
+static double env_double(const char *name, const std::string &v) {
+    std::size_t used = 0;
+    double x = 0;
+    try { x = std::stod(v, &used); } catch (const std::exception &) { used = 0; }
+    if (v.empty() || used != v.size()) throw arg_error(std::string(name) + " must be a number, not '" + v + "'");
+    return x;
+}
+static std::uint64_t env_u64(const char *name, const std::string &v) {
+    std::size_t used = 0;
+    unsigned long long x = 0;
+    try { x = std::stoull(v, &used, 0); } catch (const std::exception &) { used = 0; }
+    if (v.empty() || v[0] == '-' || used != v.size()) throw arg_error(std::string(name) + " must be an unsigned 64-bit integer, not '" + v + "'");
+    return (std::uint64_t)x;
+}
+
 int main_(int argc, char **argv) {
     opterr = 0;
     std::size_t P = 1, row_partition = 0, num_epochs = 20;
@@ -127,6 +147,15 @@ int main_(int argc, char **argv) {
         if (v != "0" && v != "1" && v != "2") throw arg_error("MGGCN_TRAIN_SET must be 0 (train), 1 (validation) or 2 (test), not '" + v + "'");
         train_set = v[0] - '0';
     }
+    double dropout_p = 0;                                           // MGGCN_DROPOUT unset: no dropout, nothing launched
+    std::uint64_t dropout_seed = 0;
+    if (const char *dp = std::getenv("MGGCN_DROPOUT")) {
+        dropout_p = env_double("MGGCN_DROPOUT", dp);
+        if (!(dropout_p >= 0.0 && dropout_p < 1.0)) throw arg_error("MGGCN_DROPOUT must be in [0, 1), not '" + std::string(dp) + "'");
+        if (dropout_p > 0.0 && (P > 1 || row_partition))            // the distributed classes have no dropout
+            throw arg_error("MGGCN_DROPOUT is single-GPU only (not with -P > 1 or -R 1)");
+    }
+    if (const char *sd = std::getenv("MGGCN_DROPOUT_SEED")) dropout_seed = env_u64("MGGCN_DROPOUT_SEED", sd);
 
     while (optind < argc && argv[optind] != nullptr) {
         const std::string command = argv[optind++];
@@ -175,6 +204,7 @@ int main_(int argc, char **argv) {
             gcn<x_t, v_t, r_t> G(A, sizes, false, fused, agg);
             if (env_is("MGGCN_HOIST_FIRST_AGGREGATION", "1")) G.set_hoist_first_aggregation(true);   // optional 6-SpMM epoch
             if (train_set >= 0) G.set_splits(S, train_set);
+            if (dropout_p > 0.0) G.set_dropout(dropout_p, dropout_seed);             // train_forward number e is dropout epoch e
             ctx.sync();
             stage("model (normalize, transpose, layers)");
             ctx.record("training-start", 0);

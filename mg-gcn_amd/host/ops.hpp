@@ -8,6 +8,7 @@
 #pragma once
 
 #include <array>
+#include <cmath>
 #include <memory>
 #include <string>
 #include <vector>
@@ -587,6 +588,30 @@ void abssum_by_set(const context ctx, const dn_matrix<r_t> x, const dn_matrix<x_
     mggcn_require(x.m() == 1 && x.n() == S.n() && S.m() == 1, "abssum_by_set: x and the sets must be n x 1");
     ctx.set();
     mggcn_abssum_by_set_f32(ctx.stream(0), x.buffer(), S.buffer(), x.n(), result_device);
+}
+
+// Dropout with a counter-based mask that is never stored (include/mggcn.h: mggcn_dropout_f32).  Added to ABI version 1
+// later, like the entries above: a weak reference, checked when a program asks for dropout.
+#pragma weak mggcn_dropout_f32
+// what the kernel takes instead of p (it never sees p): threshold = floor(p * 2^32), scale = 1 / (1 - p) rounded to
+// fp32 once, both computed in double; seed and stream select the mask (stream: epoch * 64 + the consuming layer)
+struct dropout_call {
+    std::uint32_t threshold = 0;
+    float scale = 1;
+    std::uint64_t seed = 0;
+    std::uint32_t stream = 0;
+};
+inline dropout_call dropout_params(double p, std::uint64_t seed = 0, std::uint32_t stream = 0) {
+    mggcn_require(p >= 0.0 && p < 1.0, "dropout: p must be in [0, 1)");          // a NaN fails both comparisons
+    return {(std::uint32_t)std::floor(p * 4294967296.0), (float)(1.0 / (1.0 - p)), seed, stream};
+}
+// out = keep ? in * scale : +0; in place allowed; row0: the global index of the first row
+template <typename r_t>
+void dropout(const context ctx, const dn_matrix<r_t> in, const dn_matrix<r_t> out, const dropout_call &d, std::uint64_t row0 = 0) {
+    mggcn_require(&mggcn_dropout_f32 != nullptr, "this libmggcn_hip.so has no dropout (mggcn_dropout_f32)");
+    mggcn_require(in.shape() == out.shape() && in.m() > 0, "dropout: shape mismatch");
+    ctx.set();
+    mggcn_dropout_f32(ctx.stream(0), in.buffer(), out.buffer(), in.size(), in.m(), row0, d.threshold, d.scale, d.seed, d.stream);
 }
 
 // dist_context forms: per-GPU loops, as in the reference's "template<dn_t>" overloads

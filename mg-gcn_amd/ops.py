@@ -7,9 +7,13 @@ Shape preconditions the reference only ``assert``s raise ``ValueError`` here.
 """
 from __future__ import annotations
 
+import math
+import numbers
 import os
 
 from typing import Optional
+
+import numpy as np
 
 from .matrix import context, csr_matrix, dn_matrix
 
@@ -340,6 +344,33 @@ def scale_mat(ctx: context, mat: dn_matrix, scalar: float) -> None:
     ctx.lib.mggcn_scale_mat_f32(ctx.stream(0), mat.buffer(), scalar, mat.size())
 
 
+def dropout_params(p: float):
+    """(threshold, scale) of mggcn_dropout_f32 for a drop probability 0 <= p < 1: threshold = floor(p * 2^32) as a
+    uint32 and scale = 1 / (1 - p) rounded to fp32 once, both computed in double; ValueError for any other p"""
+    _req(isinstance(p, numbers.Real) and 0.0 <= p < 1.0, f"dropout: p must be a number in [0, 1), got {p!r}")   # no NaN
+    p = float(p)
+    return int(math.floor(p * 4294967296.0)), float(np.float32(1.0 / (1.0 - p)))
+
+
+def dropout_raw(ctx: context, X: dn_matrix, out: dn_matrix, threshold: int, scale: float, seed: int, stream: int,
+                row0: int = 0) -> None:
+    """mggcn_dropout_f32 with the (threshold, scale) of dropout_params: what the layers call every epoch"""
+    _req(X.shape() == out.shape(), "shape mismatch")
+    _req(X.m() >= 1, "row width must be positive")
+    ctx.lib.mggcn_dropout_f32(ctx.stream(0), X.buffer(), out.buffer(), X.size(), X.m(), int(row0), int(threshold),
+                              scale, int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF)
+
+
+def dropout(ctx: context, X: dn_matrix, out: dn_matrix, p: float, seed: int, stream: int, row0: int = 0) -> None:
+    """out = keep ? X / (1 - p) : +0.0 with the counter-based mask of mggcn_dropout_f32 (include/mggcn.h): a pure
+    function of (seed, stream, row0 + local row, column), never stored.  out may be X; row0 is the global index of X's
+    first row (a row shard draws its rows of the whole matrix's mask); the backward pass is the same call on the
+    gradient.  ValueError for p outside [0, 1) before any library call."""
+    threshold, scale = dropout_params(p)
+    _req(int(row0) >= 0, "dropout: row0 must not be negative")
+    dropout_raw(ctx, X, out, threshold, scale, seed, stream, row0)
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
@@ -419,7 +450,6 @@ class adam_table:
 
     def __init__(self, ctx: context, tensors) -> None:
         """tensors: [(param, grad, m, v, weight_decay_on)] of dn_matrix"""
-        import numpy as np
         torch = __import__("torch")
         dt = np.dtype([("param", "<u8"), ("grad", "<u8"), ("m", "<u8"), ("v", "<u8"), ("size", "<u8"),
                        ("wd", "<f4"), ("first_block", "<u4")])
