@@ -59,9 +59,9 @@ void mggcn_device_synchronize(void);
  * (its compute stream). */
 mggcn_stream_t mggcn_stream_create(int high_priority);
 void mggcn_stream_destroy(mggcn_stream_t stream);
-/* Frees the small per-(device, stream) reduction scratch that mggcn_abssum_f32 / the fused loss allocate on first use
- * (synchronises that stream).  mggcn_stream_destroy calls it; a host layer that brings its own streams (e.g. torch's)
- * calls it when it drops one. */
+/* Frees the per-(device, stream) reduction scratch that mggcn_abssum_f32 / the fused loss, and the partials that
+ * mggcn_layer_norm_backward_f32, allocate on first use (synchronises that stream).  mggcn_stream_destroy calls it; a
+ * host layer that brings its own streams (e.g. torch's) calls it when it drops one. */
 void mggcn_stream_release_scratch(mggcn_stream_t stream);
 void mggcn_stream_synchronize(mggcn_stream_t stream);
 /* event_create / context::record / context::wait / context::measure
@@ -310,6 +310,26 @@ void mggcn_scale_mat_f32(mggcn_stream_t stream, float *mat, float scalar, size_t
  * backward pass of dropout is the same call on the gradient.  size == 0 returns; m > 0 and size % m == 0. */
 void mggcn_dropout_f32(mggcn_stream_t stream, const float *in, float *out, size_t size, size_t m, uint64_t row0,
                        uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream);
+/* Layer normalisation over the rows of a contiguous [n_rows x m] matrix, 1 <= m <= MGGCN_LN_MAX_WIDTH (opt-in; the
+ * reference has no normalisation).  Forward, per row:
+ *   mean = sum(x) / m;  var = sum((x - mean)^2) / m  (biased, two passes);  rstd = 1 / sqrt(var + eps)
+ *   xhat = (x - mean) * rstd;  z = xhat * gamma + beta;  y = flags & MGGCN_LN_LEAKY_RELU ? leaky_relu(z, 0.01) : z
+ * and y, xhat [n_rows x m] and rstd [n_rows] are written; gamma and beta hold m floats; x == y is allowed.  Backward:
+ *   dz = flags & MGGCN_LN_LEAKY_RELU ? (act > 0 ? G : 0.01 G) : G   (act is a sign source only and may be null without the flag)
+ *   g = dz . gamma;  G_in = rstd (g - mean(g) - xhat mean(g . xhat));  G_gamma[c] = sum_r dz xhat;  G_beta[c] = sum_r dz
+ * G_in may be G or act.  The column sums use no atomics: per-workgroup partials in a per-(device, stream) scratch (grown on
+ * first use, freed by mggcn_stream_release_scratch) are added in a fixed order, so two calls on the same input give the
+ * same bits.  A row's results do not depend on the other rows of the call: rows [a, b) alone give the bits they have in
+ * the whole call, for the same width and pointer alignment (m % 4 == 0 with every operand 16-byte aligned takes a float4 path,
+ * anything else an element path).  n_rows == 0 returns; the backward still writes zeros to G_gamma / G_beta. */
+#define MGGCN_LN_LEAKY_RELU 1u
+#define MGGCN_LN_MAX_WIDTH 1024u
+void mggcn_layer_norm_forward_f32(mggcn_stream_t stream, const float *x, float *y, float *xhat, float *rstd,
+                                  const float *gamma, const float *beta, size_t n_rows, size_t m, float eps,
+                                  uint32_t flags);
+void mggcn_layer_norm_backward_f32(mggcn_stream_t stream, const float *G, const float *act, const float *xhat,
+                                   const float *rstd, const float *gamma, float *G_in, float *G_gamma, float *G_beta,
+                                   size_t n_rows, size_t m, uint32_t flags);
 /* cublasSasum   (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

@@ -93,6 +93,8 @@ PROTOTYPES = {
     "mggcn_axpy_f32": (None, [vp, vp, vp, c_float, c_size_t]),
     "mggcn_scale_mat_f32": (None, [vp, vp, c_float, c_size_t]),
     "mggcn_dropout_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_uint64, c_uint32, c_float, c_uint64, c_uint32]),
+    "mggcn_layer_norm_forward_f32": (None, [vp, vp, vp, vp, vp, vp, vp, c_size_t, c_size_t, c_float, c_uint32]),
+    "mggcn_layer_norm_backward_f32": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_size_t, c_size_t, c_uint32]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),
     "mggcn_gather_rows_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_softmax_xent_fused_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_float, vp]),

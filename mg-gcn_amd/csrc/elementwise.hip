@@ -736,6 +736,278 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float *in, float *ou
     }
 }
 
+// ---- layer normalisation: one row per group of L lanes ------------------------
+// A row of m <= 1024 columns lives in the registers of L = 16 or 64 lanes: lane `sub` of the group holds the K units
+// sub + L * k (k < K) of V floats each (V = 4: float4 loads, m % 4 == 0 and 16-byte aligned operands; V = 1: any width and
+// alignment), i.e. columns (sub + L * k) * V + v.  The mapping depends on (V, L, K) alone, which the host picks from m and
+// the alignment, never on where the row sits in the grid: a row gives the same bits alone, in a shard or in the whole
+// matrix.  With L = 16 a wave works on four rows at once (the 16-lane-row form of the fused loss: every reduction is four
+// DPP rotations inside the row); with L = 64, R = 2 rows are in flight where the registers allow it.  All loads of a pass
+// are issued before the first reduction, so x may be y and G_in may be G or act: a row is read whole before any of it is
+// written.  Both sums of a pass are butterflies: every lane of a group ends with the same bits.
+constexpr unsigned kLayerNormBlocks = kNumCU * 4;          // grid cap of both passes: four workgroups of four waves per CU
+
+template <int L>
+__device__ __forceinline__ float ln_group_sum(float v) {
+    if constexpr (L == 16) return row16_reduce(v, [](float a, float b) { return a + b; });
+    else return wave_sum_dpp(v);
+}
+
+template <int V>
+__device__ __forceinline__ void ln_load(float *dst, const float *p, bool ok, float fill) {
+    if constexpr (V == 4) {
+        const float4 t = ok ? *reinterpret_cast<const float4 *>(p) : make_float4(fill, fill, fill, fill);
+        dst[0] = t.x; dst[1] = t.y; dst[2] = t.z; dst[3] = t.w;
+    } else {
+        dst[0] = ok ? *p : fill;
+    }
+}
+
+template <int V>
+__device__ __forceinline__ void ln_store(float *p, const float *src) {
+    if constexpr (V == 4) *reinterpret_cast<float4 *>(p) = make_float4(src[0], src[1], src[2], src[3]);
+    else *p = src[0];
+}
+
+// where group `sub`-lane of this thread starts and how the grid walks the rows (wave-uniform trip count: the DPP steps
+// want every lane of a row group in step)
+template <int L>
+struct ln_walk {
+    uint32_t sub;
+    size_t g0, w0, gstride;
+    __device__ ln_walk() {
+        sub = threadIdx.x & (L - 1);
+        gstride = ((size_t)gridDim.x * blockDim.x) / L;
+        g0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) / L;
+        w0 = ((size_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) / L;       // first group of this wave
+    }
+};
+
+// y = act(xhat * gamma + beta), xhat = (x - mean) * rstd, rstd = 1 / sqrt(var + eps): mean and the biased variance in two
+// passes over the registers (sum of (x - mean)^2, not E[x^2] - mean^2, which cancels for rows far from zero).
+template <int V, int L, int K, int R>
+__global__ __launch_bounds__(256) void layer_norm_forward_kernel(const float *x, float *y, float *xhat,
+                                                                 float *__restrict__ rstd_out,
+                                                                 const float *__restrict__ gamma,
+                                                                 const float *__restrict__ beta, size_t n_rows, uint32_t m,
+                                                                 float eps, float slope, int leaky) {
+    constexpr int NV = K * V;
+    const ln_walk<L> at;
+    const float fm = (float)m;
+    float ga[NV], be[NV];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const uint32_t c0 = (at.sub + (uint32_t)L * k) * V;
+        ln_load<V>(&ga[k * V], gamma + c0, c0 < m, 0.f);
+        ln_load<V>(&be[k * V], beta + c0, c0 < m, 0.f);
+    }
+    for (size_t base = 0; at.w0 + base < n_rows; base += at.gstride * R) {
+        float a[R][NV];
+#pragma unroll
+        for (int q = 0; q < R; q++) {                                            // all loads first
+            const size_t r = at.g0 + base + (size_t)q * at.gstride;
+            const bool live = r < n_rows;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint32_t c0 = (at.sub + (uint32_t)L * k) * V;
+                ln_load<V>(&a[q][k * V], x + r * m + c0, live && c0 < m, 0.f);
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < R; q++) {
+            const size_t r = at.g0 + base + (size_t)q * at.gstride;
+            const bool live = r < n_rows;
+            float s = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; i++) s += a[q][i];                           // columns past m hold +0.0
+            const float mean = ln_group_sum<L>(s) / fm;
+            float d2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; i++) {
+                const uint32_t c = (at.sub + (uint32_t)L * (i / V)) * V + (i % V);
+                const float d = c < m ? a[q][i] - mean : 0.f;
+                a[q][i] = d;
+                d2 = fmaf(d, d, d2);
+            }
+            const float rs = 1.f / sqrtf(ln_group_sum<L>(d2) / fm + eps);
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint32_t c0 = (at.sub + (uint32_t)L * k) * V;
+                float xh[V], o[V];
+#pragma unroll
+                for (int v = 0; v < V; v++) {
+                    xh[v] = a[q][k * V + v] * rs;
+                    const float z = fmaf(xh[v], ga[k * V + v], be[k * V + v]);
+                    o[v] = leaky ? lrelu(z, slope) : z;
+                }
+                if (live && c0 < m) {
+                    ln_store<V>(xhat + r * m + c0, xh);
+                    ln_store<V>(y + r * m + c0, o);
+                }
+            }
+            if (live && at.sub == 0) rstd_out[r] = rs;
+        }
+    }
+}
+
+// dz = G . leaky_relu'(act) (or G), g = dz . gamma, G_in = rstd (g - mean(g) - xhat mean(g . xhat)); the column sums
+// G_gamma = sum_r dz . xhat and G_beta = sum_r dz without a float atomic: a lane owns its columns for the whole grid-stride
+// loop and sums its rows in registers, the workgroup's 256 / L groups meet in LDS and are added in group order, and one
+// [2 x m] partial per workgroup goes to the scratch, which layer_norm_colsum_final_kernel adds in workgroup order.
+template <int V, int L, int K, int R>
+__global__ __launch_bounds__(256) void layer_norm_backward_kernel(const float *G, const float *act, const float *xhat,
+                                                                  const float *__restrict__ rstd,
+                                                                  const float *__restrict__ gamma, float *G_in,
+                                                                  float *__restrict__ partials, size_t n_rows, uint32_t m,
+                                                                  float slope, int leaky) {
+    constexpr int NV = K * V, NG = 256 / L, CP = L * NV;                         // CP: columns a group covers
+    __shared__ float s_part[2 * NG * CP];                                        // [gamma | beta][group][column]
+    const ln_walk<L> at;
+    const float fm = (float)m;
+    float ga[NV], dg[NV], db[NV];
+#pragma unroll
+    for (int k = 0; k < K; k++) {
+        const uint32_t c0 = (at.sub + (uint32_t)L * k) * V;
+        ln_load<V>(&ga[k * V], gamma + c0, c0 < m, 0.f);
+    }
+#pragma unroll
+    for (int i = 0; i < NV; i++) dg[i] = db[i] = 0.f;
+    for (size_t base = 0; at.w0 + base < n_rows; base += at.gstride * R) {
+        float g[R][NV], a[R][NV], xh[R][NV], rs[R];
+#pragma unroll
+        for (int q = 0; q < R; q++) {                                            // all loads first
+            const size_t r = at.g0 + base + (size_t)q * at.gstride;
+            const bool live = r < n_rows;
+            rs[q] = live ? rstd[r] : 0.f;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint32_t c0 = (at.sub + (uint32_t)L * k) * V;
+                const bool ok = live && c0 < m;
+                ln_load<V>(&g[q][k * V], G + r * m + c0, ok, 0.f);
+                ln_load<V>(&xh[q][k * V], xhat + r * m + c0, ok, 0.f);
+                if (leaky) {                                                     // uniform
+                    ln_load<V>(&a[q][k * V], act + r * m + c0, ok, 1.f);
+                } else {
+#pragma unroll
+                    for (int v = 0; v < V; v++) a[q][k * V + v] = 1.f;
+                }
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < R; q++) {
+            const size_t r = at.g0 + base + (size_t)q * at.gstride;
+            const bool live = r < n_rows;
+            float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+            for (int i = 0; i < NV; i++) {                                       // a dead row or column adds +0.0
+                const float dz = a[q][i] > 0.f ? g[q][i] : slope * g[q][i];
+                db[i] += dz;
+                dg[i] = fmaf(dz, xh[q][i], dg[i]);
+                const float gg = dz * ga[i];
+                g[q][i] = gg;
+                s1 += gg;
+                s2 = fmaf(gg, xh[q][i], s2);
+            }
+            const float c1 = ln_group_sum<L>(s1) / fm, c2 = ln_group_sum<L>(s2) / fm;
+#pragma unroll
+            for (int k = 0; k < K; k++) {
+                const uint32_t c0 = (at.sub + (uint32_t)L * k) * V;
+                float o[V];
+#pragma unroll
+                for (int v = 0; v < V; v++) o[v] = rs[q] * fmaf(-xh[q][k * V + v], c2, g[q][k * V + v] - c1);
+                if (live && c0 < m) ln_store<V>(G_in + r * m + c0, o);
+            }
+        }
+    }
+    const uint32_t grp = threadIdx.x / L;
+#pragma unroll
+    for (int i = 0; i < NV; i++) {
+        const uint32_t c = (at.sub + (uint32_t)L * (i / V)) * V + (i % V);
+        s_part[(0 * NG + grp) * CP + c] = dg[i];
+        s_part[(1 * NG + grp) * CP + c] = db[i];
+    }
+    __syncthreads();
+    for (uint32_t idx = threadIdx.x; idx < 2u * CP; idx += 256) {
+        const uint32_t j = idx / CP, c = idx % CP;
+        float s = s_part[(j * NG + 0) * CP + c];
+#pragma unroll
+        for (int w = 1; w < NG; w++) s += s_part[(j * NG + w) * CP + c];
+        if (c < m) partials[((size_t)blockIdx.x * 2 + j) * m + c] = s;
+    }
+}
+
+// G_gamma / G_beta = the workgroups' partials added in a fixed order: 64 of the 2 m sums per workgroup, each from four
+// slices (workgroups w, w + 4, ... in order) that meet in LDS.  n_blocks == 0 stores zeros.
+__global__ __launch_bounds__(256) void layer_norm_colsum_final_kernel(const float *__restrict__ partials, unsigned n_blocks,
+                                                                      uint32_t m, float *__restrict__ G_gamma,
+                                                                      float *__restrict__ G_beta) {
+    __shared__ float w[4][64];
+    const uint32_t lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
+    const uint32_t idx = blockIdx.x * 64 + lane, two_m = 2 * m;
+    float s = 0.f;
+    if (idx < two_m) {
+#pragma unroll 8
+        for (unsigned b = slice; b < n_blocks; b += 4) s += partials[(size_t)b * two_m + idx];
+    }
+    w[slice][lane] = s;
+    __syncthreads();
+    if (slice == 0 && idx < two_m) {
+        const float t = (w[0][lane] + w[1][lane]) + (w[2][lane] + w[3][lane]);
+        if (idx < m) G_gamma[idx] = t;
+        else G_beta[idx - m] = t;
+    }
+}
+
+// the backward's partials: [workgroups x 2 x m] floats per (device, stream), grown on first use like abssum_scratch (never
+// on a captured launch path) and freed by mggcn_stream_release_scratch
+struct ln_scratch { float *p = nullptr; size_t floats = 0; };
+std::map<std::pair<int, hipStream_t>, ln_scratch> g_ln_scratch;     // under g_scratch_mu
+
+float *layer_norm_scratch(hipStream_t st, size_t floats) {
+    int dev = 0;
+    MGGCN_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_scratch_mu);
+    ln_scratch &s = g_ln_scratch[{dev, st}];
+    if (s.floats < floats) {
+        if (s.p) {
+            MGGCN_CHECK_HIP(hipStreamSynchronize(st));                // an earlier backward may still be summing into it
+            MGGCN_CHECK_HIP(hipFree(s.p));
+            s.p = nullptr; s.floats = 0;
+        }
+        MGGCN_CHECK_HIP(hipMalloc(&s.p, floats * sizeof(float)));
+        s.floats = floats;
+    }
+    return s.p;
+}
+
+template <int L, int R>
+unsigned layer_norm_grid(size_t n_rows) {
+    const size_t per_block = (size_t)(256 / L) * R;
+    return (unsigned)std::min<size_t>((n_rows + per_block - 1) / per_block, kLayerNormBlocks);
+}
+
+// (V, L, K, R) from the width and the alignment; F(V, L, K, R) launches
+#define MGGCN_LN_DISPATCH(F, vec, m)                                          \
+    do {                                                                      \
+        if (vec) {                                                            \
+            const size_t q_ = (m) / 4;                                        \
+            if (q_ <= 16) F(4, 16, 1, 1);                                     \
+            else if (q_ <= 32) F(4, 16, 2, 1);                                \
+            else if (q_ <= 64) F(4, 16, 4, 1);                                \
+            else if (q_ <= 128) F(4, 64, 2, 2);                               \
+            else F(4, 64, 4, 1);                                              \
+        } else {                                                              \
+            if ((m) <= 16) F(1, 16, 1, 1);                                    \
+            else if ((m) <= 32) F(1, 16, 2, 1);                               \
+            else if ((m) <= 48) F(1, 16, 3, 1);                               \
+            else if ((m) <= 64) F(1, 16, 4, 1);                               \
+            else if ((m) <= 128) F(1, 64, 2, 2);                              \
+            else if ((m) <= 256) F(1, 64, 4, 2);                              \
+            else if ((m) <= 512) F(1, 64, 8, 1);                              \
+            else F(1, 64, 16, 1);                                             \
+        }                                                                     \
+    } while (0)
+
 }  // namespace
 
 // ============================ C ABI =========================================
@@ -903,6 +1175,53 @@ MGGCN_API void mggcn_dropout_f32(mggcn_stream_t stream, const float *in, float *
     MGGCN_CHECK_LAUNCH();
 }
 
+MGGCN_API void mggcn_layer_norm_forward_f32(mggcn_stream_t stream, const float *x, float *y, float *xhat, float *rstd,
+                                            const float *gamma, const float *beta, size_t n_rows, size_t m, float eps,
+                                            uint32_t flags) {
+    MGGCN_REQUIRE(m > 0 && m <= MGGCN_LN_MAX_WIDTH, "layer norm supports 1 <= m <= 1024 columns");
+    MGGCN_REQUIRE(xhat != nullptr && rstd != nullptr && gamma != nullptr && beta != nullptr, "layer norm: null operand");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(x != nullptr && y != nullptr, "layer norm: null operand");
+    const bool vec = m % 4 == 0 && aligned16(x) && aligned16(y) && aligned16(xhat) && aligned16(gamma) && aligned16(beta);
+    const int leaky = (flags & MGGCN_LN_LEAKY_RELU) != 0;
+#define MGGCN_LN_FWD(V, L, K, R)                                                                                         \
+    hipLaunchKernelGGL((layer_norm_forward_kernel<V, L, K, R>), dim3(layer_norm_grid<L, R>(n_rows)), dim3(256), 0,          \
+                       as_stream(stream), x, y, xhat, rstd, gamma, beta, n_rows, (uint32_t)m, eps, 0.01f, leaky)
+    MGGCN_LN_DISPATCH(MGGCN_LN_FWD, vec, m);
+#undef MGGCN_LN_FWD
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_layer_norm_backward_f32(mggcn_stream_t stream, const float *G, const float *act, const float *xhat,
+                                             const float *rstd, const float *gamma, float *G_in, float *G_gamma,
+                                             float *G_beta, size_t n_rows, size_t m, uint32_t flags) {
+    MGGCN_REQUIRE(m > 0 && m <= MGGCN_LN_MAX_WIDTH, "layer norm supports 1 <= m <= 1024 columns");
+    MGGCN_REQUIRE(xhat != nullptr && rstd != nullptr && gamma != nullptr, "layer norm backward: null operand");
+    MGGCN_REQUIRE(G_gamma != nullptr && G_beta != nullptr, "layer norm backward: null gradient");
+    const int leaky = (flags & MGGCN_LN_LEAKY_RELU) != 0;
+    const hipStream_t st = as_stream(stream);
+    const unsigned final_grid = (unsigned)((2 * m + 63) / 64);
+    if (!n_rows) {                                                    // the sums over no rows
+        hipLaunchKernelGGL(layer_norm_colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, nullptr, 0u, (uint32_t)m,
+                           G_gamma, G_beta);
+        MGGCN_CHECK_LAUNCH();
+        return;
+    }
+    MGGCN_REQUIRE(G != nullptr && G_in != nullptr && (!leaky || act != nullptr), "layer norm backward: null operand");
+    const bool vec = m % 4 == 0 && aligned16(G) && aligned16(xhat) && aligned16(G_in) && aligned16(gamma) && (!leaky || aligned16(act));
+    float *partials = layer_norm_scratch(st, (size_t)kLayerNormBlocks * 2 * m);
+    unsigned grid = 0;
+#define MGGCN_LN_BWD(V, L, K, R)                                                                                         \
+    hipLaunchKernelGGL((layer_norm_backward_kernel<V, L, K, R>), dim3(grid = layer_norm_grid<L, R>(n_rows)), dim3(256), 0,  \
+                       st, G, act, xhat, rstd, gamma, G_in, partials, n_rows, (uint32_t)m, 0.01f, leaky)
+    MGGCN_LN_DISPATCH(MGGCN_LN_BWD, vec, m);
+#undef MGGCN_LN_BWD
+    MGGCN_CHECK_LAUNCH();
+    hipLaunchKernelGGL(layer_norm_colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, partials, grid, (uint32_t)m,
+                       G_gamma, G_beta);
+    MGGCN_CHECK_LAUNCH();
+}
+
 // The reduction scratch above belongs to a (device, stream) pair: mggcn_stream_destroy releases it with the stream;
 // a host layer whose streams come from elsewhere (torch) calls this when it drops a stream, so that a recycled
 // stream handle never inherits a buffer another stream may still be using, and nothing accumulates.
@@ -915,6 +1234,9 @@ MGGCN_API void mggcn_stream_release_scratch(mggcn_stream_t stream) {
         std::lock_guard<std::mutex> lock(g_scratch_mu);
         for (auto it = g_scratch.begin(); it != g_scratch.end();)
             if (it->first.second == as_stream(stream)) { mine.push_back({it->first.first, it->second}); it = g_scratch.erase(it); }
+            else ++it;
+        for (auto it = g_ln_scratch.begin(); it != g_ln_scratch.end();)          // the layer-norm backward's partials
+            if (it->first.second == as_stream(stream)) { mine.push_back({it->first.first, it->second.p}); it = g_ln_scratch.erase(it); }
             else ++it;
     }
     if (mine.empty()) return;

@@ -44,8 +44,8 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, ops
-from .gcn import (_check_agg_dtype, adam_update_all, check_counts, check_sets, dropout_option, layer_body, linear,
-                  link_fused_backward, softmax_cross_entropy_loss, split_counts)
+from .gcn import (_check_agg_dtype, adam_update_all, check_counts, check_norm, check_sets, dropout_option, layer_body,
+                  layer_norm, linear, link_fused_backward, softmax_cross_entropy_loss, split_counts)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -807,9 +807,12 @@ class dist_row_linear(linear):
     rank's shard and replica; W()/b()/GW()/Gb() of the layer are repl_dn_matrix views of them."""
 
     def __init__(self, dctx: dist_context, name: str, in_: int, out: int, backward_out: bool = True,
-                 fused: bool = False):
+                 fused: bool = False, extra_grads: int = 0):
+        """extra_grads: floats behind [G_W | G_b | tail] that take part in the same all-reduce (``extra``): the layer's
+        norm keeps its two gradient rows there"""
         self._dctx = dctx
         self._grad_pending = None
+        self._extra_grads = int(extra_grads)
         with _torch().cuda.device(dctx.ctx.device):
             linear.__init__(self, name, in_, out, backward_out, fused)
 
@@ -821,8 +824,9 @@ class dist_row_linear(linear):
         # all-reduce there (dist_gcn.train_step: no collective of their own) -- the front two, or all eight of a split-aware
         # epoch
         off_t = (off_b + out + 3) // 4 * 4
-        self.G_flat = torch.zeros(off_t + 8, dtype=torch.float32, device=self._dctx.ctx.device)
+        self.G_flat = torch.zeros(off_t + 8 + self._extra_grads, dtype=torch.float32, device=self._dctx.ctx.device)
         self.tail = self.G_flat[off_t:off_t + 8]
+        self.extra = self.G_flat[off_t + 8:]
         torch.cuda.current_stream().synchronize()              # torch zeroes on ITS stream (the padding takes part in the sum);
                                                                # the kernels run on the context's
         return dn_matrix(in_, out, self.G_flat), dn_matrix(1, out, self.G_flat[off_b:])
@@ -865,12 +869,15 @@ class dist_gcn_layer(layer_body):
     def __init__(self, dctx: dist_context, name: str, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
                  in_: int, out: int, activation: bool, residual_layer: bool = False, backward_spmm: bool = True,
                  HW_buffer=None, bcast_buffer=None, bcast_buffer2=None, fused: bool = False,
-                 mode: str = "allgather", agg_dtype: str = "f32"):
+                 mode: str = "allgather", agg_dtype: str = "f32", norm=None):
         _check_agg_dtype(agg_dtype)
+        normed = check_norm(norm) == "layer" and activation
         torch = _torch()
         P, dev = dctx.P, dctx.ctx.device
         self.A = dist_sparse_linear(name, A, A_T, bcast_buffer, bcast_buffer2, mode, agg_dtype)
-        lin = dist_row_linear(dctx, name, in_, out, backward_spmm, fused)
+        # The norm's backward runs before lin.backward, whose all-reduce of [G_W | G_b | tail | G_gamma | G_beta] therefore
+        # sums the norm's two gradient rows too: no collective of their own
+        lin = dist_row_linear(dctx, name, in_, out, backward_spmm, fused, 2 * out if normed else 0)
         res_lin = dist_row_linear(dctx, name, in_, out, backward_spmm, False) if residual_layer and in_ != out else None
         mn = min(in_, out)
         self.AHW_buffer = torch.empty(max(A.n() * out, A_T.n() * in_) // P, dtype=torch.float32, device=dev)
@@ -881,7 +888,8 @@ class dist_gcn_layer(layer_body):
         layer_body.__init__(self, name, _rank_aggregation(dctx, self.A), lin, res_lin, residual_layer,
                             shard(A.m(), mn, HW_buffer), shard(A.n(), out, self.AHW_buffer),
                             shard(A_T.n(), mn, HW_buffer), shard(A_T.n(), in_, self.AHW_buffer),
-                            activation, backward_spmm, fused)
+                            activation, backward_spmm, fused,
+                            layer_norm(name, A.n() // P, out, fused, dev, lin.extra) if normed else None)
         self.row0 = int(A.p[dctx.rank])           # dropout: this rank draws ITS rows of the global mask
 
     def __call__(self, dctx: dist_context, H: dist_row_dn_matrix) -> dist_row_dn_matrix:
@@ -960,12 +968,17 @@ class dist_gcn(dropout_option):
 
     ``dropout=p`` / set_dropout(p, seed, epoch): see gcn.dropout_option.  Every rank calls it with the same arguments;
     a rank drops its rows of the mask the single-GPU model draws (row0 = p[rank] of the partition), on the compute
-    stream ahead of whatever the exchange waits for, and nothing is communicated for it."""
+    stream ahead of whatever the exchange waits for, and nothing is communicated for it.
+
+    ``norm="layer"``: see gcn.gcn.  Layer normalisation is row-local, so a rank normalises exactly its rows of the
+    single-GPU run and the forward communicates nothing; gamma / beta are replicated, and their gradients ride on the
+    all-reduce of the same layer's G_W / G_b (all three schedules, both overlap settings)."""
 
     def __init__(self, dctx: dist_context, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
                  sizes: Sequence[int], residual_layer: bool = False, fused: bool = True, mode: str = "allgather",
-                 agg_dtype: str = "f32", dropout: float = 0.0):
+                 agg_dtype: str = "f32", dropout: float = 0.0, norm=None):
         self._init_dropout(dropout, len(sizes) - 1)          # option checks come before any device work
+        self.norm = check_norm(norm)
         self.agg_dtype = _check_agg_dtype(agg_dtype)
         torch = _torch()
         P, dev = dctx.P, dctx.ctx.device
@@ -988,7 +1001,7 @@ class dist_gcn(dropout_option):
         for i in range(1, len(sizes)):
             self.layers_.append(dist_gcn_layer(dctx, f"{i - 1}_", A_T, A, sizes[i - 1], sizes[i],
                                                i + 1 < len(sizes), residual_layer, i != 1, self.HW_buffer,
-                                               self.bcast_buffer, self.bcast_buffer2, fused, mode, agg_dtype))
+                                               self.bcast_buffer, self.bcast_buffer2, fused, mode, agg_dtype, self.norm))
             self.layers_[-1].A.agg_buffer = self.agg_buffer
         link_fused_backward(self.layers_, fused)
         self.fused, self._adam = fused, None
@@ -1061,7 +1074,7 @@ class dist_gcn(dropout_option):
             return
         for layer in self.layers_:
             layer.finish_backward(dctx)
-        self._adam = adam_update_all(dctx.ctx, [lin for l in self.layers_ for lin in l.linears()], self._adam, lr,
+        self._adam = adam_update_all(dctx.ctx, [p for l in self.layers_ for p in l.params()], self._adam, lr,
                                      beta1, beta2, weight_decay, eps)
 
     def train_step(self, dctx: dist_context, H: dist_row_dn_matrix, Y: dist_row_dn_matrix, lr, beta1, beta2,

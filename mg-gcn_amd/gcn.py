@@ -21,6 +21,10 @@ and everything else in fp32 (GEMMs, loss, weights, gradients, Adam).
 ``dropout=p`` (opt-in; default 0: nothing is launched) drops the input of every layer but the first during a training
 forward, with a counter-based mask that is never stored (ops.dropout, include/mggcn.h: mggcn_dropout_f32): the backward
 pass regenerates it, a row-partitioned run draws the single-GPU run's mask, and numpy reproduces it bit for bit.
+
+``norm="layer"`` (opt-in; default None: nothing is launched) puts a layer normalisation between the aggregation / linear
+and the activation of every layer but the last (ops.layer_norm, include/mggcn.h: mggcn_layer_norm_forward_f32); the
+activation rides in the norm kernels, and the norm's gamma / beta are trained by Adam without weight decay.
 """
 from __future__ import annotations
 
@@ -59,6 +63,16 @@ def check_dropout(p: float, n_layers: int):
     if float(p) > 0.0 and n_layers > DROPOUT_MAX_LAYERS:
         raise ValueError(f"dropout supports at most {DROPOUT_MAX_LAYERS} layers, the model has {n_layers}")
     return params
+
+
+NORMS = (None, "layer")
+
+
+def check_norm(norm):
+    """option checking of norm=, before any device work: None (no normalisation) or "layer" """
+    if norm is not None and norm != "layer":
+        raise ValueError(f"norm must be one of {NORMS}, not {norm!r}")
+    return norm
 
 
 class dropout_option:
@@ -266,6 +280,71 @@ class linear:
     def get_G_b(self): return self.G_b
 
 
+class layer_norm:
+    """Layer normalisation of a layer's [n x out] pre-activation, in place, with the activation in the same launch
+    (opt-in; the reference has none): gamma (ones) and beta (zeros) [1 x out], their gradients and Adam moments, and what
+    the backward pass needs of the forward -- xhat [n x out] and rstd [n].  Row-local: a row shard normalises exactly the
+    rows the single-GPU model does, and its two gradient rows are summed over the ranks with the linear's
+    (``grad_buffer``: 2 * out floats inside that linear's all-reduced buffer)."""
+
+    def __init__(self, name: str, n: int, out: int, fused: bool = False, device=None, grad_buffer=None):
+        self.name, self.fused = name, fused
+        self.gamma, self.beta = dn_matrix(1, out, device=device), dn_matrix(1, out, device=device)
+        self.gamma.init(np.ones((1, out), dtype=np.float32))
+        self.beta.init(np.zeros((1, out), dtype=np.float32))
+        if grad_buffer is None:
+            self.G_gamma, self.G_beta = dn_matrix(1, out, device=device), dn_matrix(1, out, device=device)
+        else:
+            self.G_gamma, self.G_beta = dn_matrix(1, out, grad_buffer[:out]), dn_matrix(1, out, grad_buffer[out:2 * out])
+        self.xhat, self.rstd = dn_matrix(n, out, device=device), dn_matrix(n, 1, device=device)
+        self.mg = self.vg = self.mb = self.vb = None
+        self.step = 0
+
+    def __call__(self, ctx: context, Z: dn_matrix, activation: bool) -> None:
+        """Z = [leaky_relu](layer_norm(Z)) in place"""
+        n = self.name
+        ctx.record(n + "0_0_norm", 0)
+        ops.layer_norm(ctx, Z, Z, self.xhat, self.rstd, self.gamma, self.beta, ops.LAYER_NORM_LEAKY_RELU if activation else 0)
+        ctx.record(n + "0_1_norm", 0)
+        ctx.register_timer(n + "0_norm", n + "0_0_norm", n + "0_1_norm")
+
+    def backward(self, ctx: context, G: dn_matrix, act: Optional[dn_matrix], G_in: dn_matrix) -> None:
+        """G_in = the gradient of the norm's input, G_gamma / G_beta; ``act``: apply leaky_relu'(act) to G first"""
+        n = self.name
+        ctx.record(n + "1_0_norm", 0)
+        ops.layer_norm_backward(ctx, G, act, self.xhat, self.rstd, self.gamma, G_in, self.G_gamma, self.G_beta,
+                                ops.LAYER_NORM_LEAKY_RELU if act is not None else 0)
+        ctx.record(n + "1_1_norm", 0)
+        ctx.register_timer(n + "1_norm", n + "1_0_norm", n + "1_1_norm")
+
+    def init(self, gamma, beta) -> None:
+        self.gamma.init(np.asarray(gamma, dtype=np.float32))
+        self.beta.init(np.asarray(beta, dtype=np.float32))
+
+    def adam_state(self, ctx: context) -> None:
+        if self.mg is None:
+            dev = self.gamma.t.device
+            self.mg, self.vg, self.mb, self.vb = (dn_matrix(self.gamma.shape(), device=dev) for _ in range(4))
+            for t in (self.mg, self.vg, self.mb, self.vb):
+                t.zero(ctx)
+            self.step = 0
+
+    def adam_tensors(self, weight_decay: float):
+        """rows of ops.adam_table: neither gamma nor beta decays"""
+        return [(self.gamma, self.G_gamma, self.mg, self.vg, 0.0), (self.beta, self.G_beta, self.mb, self.vb, 0.0)]
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
+        """the unfused chain linear.adam_update runs for b"""
+        self.adam_state(ctx)
+        self.step += 1
+        bc1 = float(np.float32(1 - beta1 ** self.step))
+        bc2 = float(np.float32(1 - beta2 ** self.step))
+        for p, g, m, v, _ in self.adam_tensors(weight_decay):
+            ops.axpby(ctx, g, m, 1 - beta1, beta1)
+            ops.aaxpby(ctx, g, v, 1 - beta2, beta2)
+            ops.adam_final(ctx, p, m, v, lr, bc1, bc2, eps)
+
+
 class layer_body:
     """Forward and backward of one GCN layer, reference src/gcn.hpp:411-518 (gcn_layer) and :520-637 (dist_gcn_layer),
     over a context and dn_matrix operands: the layer's rows on this GPU.  HW / G_HW alias the model-wide HW_buffer,
@@ -274,8 +353,13 @@ class layer_body:
     for the row partition."""
 
     def __init__(self, name: str, agg, lin: linear, res_lin: Optional[linear], residual_layer: bool, HW: dn_matrix,
-                 AHW: dn_matrix, G_HW: dn_matrix, G_out: dn_matrix, activation: bool, backward_spmm: bool, fused: bool):
+                 AHW: dn_matrix, G_HW: dn_matrix, G_out: dn_matrix, activation: bool, backward_spmm: bool, fused: bool,
+                 norm: Optional[layer_norm] = None):
         self.name, self._agg, self.lin, self.res_lin = name, agg, lin, res_lin
+        # layer normalisation between aggregation / linear and activation (gcn(norm="layer")): only where there is an
+        # activation, i.e. never in the last layer
+        assert norm is None or activation
+        self.norm = norm
         # residual connection (gcn.hpp:418, :430): a second linear when the widths differ, a plain add otherwise
         self.residual_layer = bool(residual_layer)
         self.HW, self.AHW, self.G_HW, self.G_out = HW, AHW, G_HW, G_out
@@ -332,7 +416,7 @@ class layer_body:
             self.lin.setX(H)
         elif self.HW.m() == self.AHW.m():         # out <= in: GEMM first (gcn.hpp:439-442)
             self.lin(ctx, H, self.HW)
-            if self.fused and self.activation:
+            if self.fused and self.activation and self.norm is None:     # with a norm the activation rides in ITS kernel
                 self._agg(ctx, self.HW, self.AHW, True, MGGCN_SPMM_LEAKY_RELU)
                 act_done = True
             else:
@@ -340,6 +424,9 @@ class layer_body:
         else:                                      # gcn.hpp:443-446
             self._agg(ctx, H, self.HW)
             self.lin(ctx, self.HW, self.AHW)
+        if self.norm is not None:
+            self.norm(ctx, self.AHW, self.fused)          # fused: norm and activation in one launch
+            act_done = self.fused
         if self.activation and not act_done:
             ctx.record(n + "0_0_activation", 0)
             ops.leaky_relu_forward(ctx, self.AHW, self.AHW)
@@ -354,12 +441,19 @@ class layer_body:
     def backward(self, ctx: context, G: dn_matrix) -> dn_matrix:
         n = self.name
         T = G
-        if self.activation and not self.grad_premasked:
+        if self.norm is not None and self.fused:
+            # one launch: leaky_relu'(AHW as the forward left it) unless G already carries it, then the norm's backward;
+            # T lands in AHW
+            self.norm.backward(ctx, G, None if self.grad_premasked else self.AHW, self.AHW)
+            T = self.AHW
+        elif self.activation and not self.grad_premasked:
             ctx.record(n + "1_0_activation", 0)
             ops.leaky_relu_backward(ctx, self.AHW, G, self.AHW)
             ctx.record(n + "1_1_activation", 0)
             ctx.register_timer(n + "1_activation", n + "1_0_activation", n + "1_1_activation")
             T = self.AHW
+            if self.norm is not None:
+                self.norm.backward(ctx, self.AHW, None, self.AHW)
         if self.HW.m() == self.AHW.m():
             G_HW = self.G_HW
             if self.backward_spmm:
@@ -386,6 +480,10 @@ class layer_body:
     def linears(self):
         return [self.lin] + ([self.res_lin] if self.res_lin is not None else [])
 
+    def params(self):
+        """everything Adam updates: the linears, then the norm (linears() stays what the reference's layer has)"""
+        return self.linears() + ([self.norm] if self.norm is not None else [])
+
     def finish_backward(self, ctx) -> None:
         for lin in self.linears():
             lin.finish_backward(ctx)
@@ -395,8 +493,8 @@ class layer_body:
             lin.update(ctx, lr, weight_decay)
 
     def adam_update(self, ctx, lr, beta1, beta2, weight_decay, eps):
-        for lin in self.linears():
-            lin.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+        for p in self.params():
+            p.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
 
     def b(self): return self.lin.get_b()
     def W(self): return self.lin.get_W()
@@ -409,8 +507,9 @@ class gcn_layer(layer_body):
 
     def __init__(self, name: str, A: csr_matrix, A_T: csr_matrix, in_: int, out: int, activation: bool,
                  residual_layer: bool = False, backward_spmm: bool = True, HW_buffer=None, fused: bool = False,
-                 agg_dtype: str = "f32", agg_buffer=None):
+                 agg_dtype: str = "f32", agg_buffer=None, norm=None):
         torch = _torch()
+        check_norm(norm)
         self.A = sparse_linear(name, A, A_T, agg_dtype, agg_buffer)
         mn = min(in_, out)
         if HW_buffer is None:
@@ -421,7 +520,8 @@ class gcn_layer(layer_body):
         layer_body.__init__(self, name, self.A, lin, res_lin, residual_layer,
                             dn_matrix(A.m(), mn, HW_buffer), dn_matrix(A.n(), out, self.AHW_buffer),
                             dn_matrix(A_T.n(), mn, HW_buffer), dn_matrix(A_T.n(), in_, self.AHW_buffer),
-                            activation, backward_spmm, fused)
+                            activation, backward_spmm, fused,
+                            layer_norm(name, A.n(), out, fused) if norm == "layer" and activation else None)
 
 
 class softmax:
@@ -669,12 +769,17 @@ class gcn(dropout_option):
     A_T and hands (A_T, A) to the layers -- forward multiplies by A_T (:946-955).
 
     ``dropout=p`` / set_dropout(p, seed, epoch): see dropout_option -- the input of every layer but the first is dropped
-    in train_forward / train_step; the features X are the caller's buffer and are not dropped."""
+    in train_forward / train_step; the features X are the caller's buffer and are not dropped.
+
+    ``norm="layer"``: every layer but the last normalises its rows between aggregation / linear and activation (see
+    layer_norm; ``layer.norm.gamma`` / ``.beta``, ``layer.norm.init(gamma, beta)``).  It has no training mode: a plain
+    call and evaluate() run the same kernels.  None (the default) launches nothing new."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], residual_layer: bool = False,
                  weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None, fused: bool = True,
-                 hoist_first_aggregation: bool = False, agg_dtype: str = "f32", dropout: float = 0.0):
+                 hoist_first_aggregation: bool = False, agg_dtype: str = "f32", dropout: float = 0.0, norm=None):
         self._init_dropout(dropout, len(sizes) - 1)          # option checks come before any device work
+        self.norm = check_norm(norm)
         torch = _torch()
         self.agg_dtype = _check_agg_dtype(agg_dtype)
         if self.agg_dtype != "f32" and hoist_first_aggregation:
@@ -694,7 +799,7 @@ class gcn(dropout_option):
         for i in range(1, len(sizes)):
             self.layers_.append(gcn_layer(f"{i - 1}_", A_T, A, sizes[i - 1], sizes[i], i + 1 < len(sizes),
                                           residual_layer, i != 1, self.HW_buffer, fused, self.agg_dtype,
-                                          self.agg_buffer))
+                                          self.agg_buffer, self.norm))
         link_fused_backward(self.layers_, fused)
         self._adam = None
         self.set_hoist_first_aggregation(hoist_first_aggregation)
@@ -790,7 +895,7 @@ class gcn(dropout_option):
             for layer in self.layers_:
                 layer.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
             return
-        self._adam = adam_update_all(ctx, [lin for l in self.layers_ for lin in l.linears()], self._adam, lr, beta1,
+        self._adam = adam_update_all(ctx, [p for l in self.layers_ for p in l.params()], self._adam, lr, beta1,
                                      beta2, weight_decay, eps)
 
     def layers(self) -> List[gcn_layer]:

@@ -336,6 +336,44 @@ public:
     }
 };
 
+// Layer normalisation of one layer (gcn::set_layer_norm; opt-in, single GPU only -- the reference has none): gamma (ones),
+// beta (zeros), their gradients and Adam moments, and what the backward pass needs of the forward: xhat [n x out], rstd [n].
+template <typename r_t>
+struct layer_norm_state {
+    dn_matrix<r_t> gamma, beta, G_gamma, G_beta, mg, vg, mb, vb, xhat, rstd;
+    bool has_moments = false;
+    std::size_t step = 0;
+
+    layer_norm_state(std::size_t n, std::size_t out)
+        : gamma(1, out), beta(1, out), G_gamma(1, out), G_beta(1, out), xhat(n, out), rstd(n, 1) {
+        gamma.fill((r_t)1);
+        beta.fill((r_t)0);
+    }
+    void adam_state(const context &ctx) {
+        if (has_moments) return;
+        mg = zeros_like(ctx, gamma); vg = zeros_like(ctx, gamma); mb = zeros_like(ctx, beta); vb = zeros_like(ctx, beta);
+        has_moments = true;
+        step = 0;
+    }
+    // rows of the model-wide Adam table: neither decays
+    void adam_tensors(std::vector<std::array<dn_matrix<r_t>, 4>> &out, std::vector<r_t> &wd) const {
+        out.push_back({gamma, G_gamma, mg, vg}); wd.push_back((r_t)0);
+        out.push_back({beta, G_beta, mb, vb}); wd.push_back((r_t)0);
+    }
+    // the unfused chain linear::adam_update runs for b
+    void adam_update(const context &ctx, r_t lr, r_t beta1, r_t beta2, r_t eps) {
+        adam_state(ctx);
+        step += 1;
+        const r_t bc1 = 1 - std::pow(beta1, step), bc2 = 1 - std::pow(beta2, step);
+        axpby(ctx, G_gamma, mg, 1 - beta1, beta1);
+        axpby(ctx, G_beta, mb, 1 - beta1, beta1);
+        aaxpby(ctx, G_gamma, vg, 1 - beta2, beta2);
+        aaxpby(ctx, G_beta, vb, 1 - beta2, beta2);
+        adam_final(ctx, gamma, mg, vg, lr, bc1, bc2, eps);
+        adam_final(ctx, beta, mb, vb, lr, bc1, bc2, eps);
+    }
+};
+
 // One GCN layer (reference :411-518 / :520-637), written once over the context, matrix, aggregation (sparse_linear /
 // dist_sparse_linear) and linear types.  HW / G_HW alias the model-wide HW_buffer, AHW / G_out the layer's AHW_buffer
 // (:433-434); the thin classes below allocate them.
@@ -357,6 +395,31 @@ protected:
     // place in the AHW buffer of the layer below: its backward reads that buffer for the SIGN of its activation only,
     // which scaling by 1 / (1 - p) > 0 keeps, and a dropped element gets a zero gradient from the call in backward().
     std::optional<dropout_call> drop;
+    // layer normalisation between aggregation / linear and activation (gcn::set_layer_norm; single GPU only), with the
+    // activation in the same launch on the fused path
+    std::optional<layer_norm_state<r_t>> norm;
+
+    void norm_forward(ctx_t ctx) {
+        if constexpr (std::is_same_v<ctx_t, context>) {
+            ctx.record(name + "0_0_norm", 0);
+            layer_norm(ctx, AHW, AHW, norm->xhat, norm->rstd, norm->gamma, norm->beta, fused);
+            ctx.record(name + "0_1_norm", 0);
+            ctx.register_timer(name + "0_norm", name + "0_0_norm", name + "0_1_norm");
+        } else {
+            throw std::invalid_argument("layer norm is single-GPU only in the C++ layer");
+        }
+    }
+    // G_in = AHW; act: apply leaky_relu'(act) to G first
+    void norm_backward(ctx_t ctx, dn_t G, const dn_t *act) {
+        if constexpr (std::is_same_v<ctx_t, context>) {
+            ctx.record(name + "1_0_norm", 0);
+            layer_norm_backward(ctx, G, act, norm->xhat, norm->rstd, norm->gamma, AHW, norm->G_gamma, norm->G_beta);
+            ctx.record(name + "1_1_norm", 0);
+            ctx.register_timer(name + "1_norm", name + "1_0_norm", name + "1_1_norm");
+        } else {
+            throw std::invalid_argument("layer norm is single-GPU only in the C++ layer");
+        }
+    }
 
     void apply_dropout(ctx_t ctx, dn_t M, const std::string &tag) {
         if constexpr (std::is_same_v<ctx_t, context>) {
@@ -378,7 +441,7 @@ protected:
     virtual bool aggregate_linear(ctx_t ctx, dn_t H) {
         if (gemm_first()) {                      // out <= in: GEMM first
             lin(ctx, H, HW);
-            if (fused && activation) { A(ctx, HW, AHW, true, MGGCN_SPMM_LEAKY_RELU); return true; }
+            if (fused && activation && !norm) { A(ctx, HW, AHW, true, MGGCN_SPMM_LEAKY_RELU); return true; }   // a norm carries the activation
             A(ctx, HW, AHW);
             return false;
         }
@@ -390,12 +453,17 @@ protected:
     // the backward pass up to the gradient of my input (reference :460-489)
     dn_t input_gradient(ctx_t ctx, dn_t G) {
         auto T = G;
-        if (activation && !grad_premasked) {
+        if (norm && fused) {
+            // one launch: leaky_relu'(AHW as the forward left it) unless G already carries it, then the norm's backward
+            norm_backward(ctx, G, grad_premasked ? nullptr : &AHW);
+            T = AHW;
+        } else if (activation && !grad_premasked) {
             ctx.record(name + "1_0_activation", 0);
             leaky_relu_backward(ctx, AHW, G, AHW);
             ctx.record(name + "1_1_activation", 0);
             ctx.register_timer(name + "1_activation", name + "1_0_activation", name + "1_1_activation");
             T = AHW;
+            if (norm) norm_backward(ctx, AHW, nullptr);
         }
         if (gemm_first()) {
             auto g = G_HW;
@@ -423,6 +491,12 @@ public:
     bool propagates() const { return lin.has_backward_out(); }
     void set_fused_backward(bool mask_input, bool premasked) { if (mask_input) mask_input_grad = true; if (premasked) grad_premasked = true; }
     void set_dropout_call(std::optional<dropout_call> d) { drop = d; }
+    // on: a fresh norm (gamma = 1, beta = 0) if this layer has an activation; off: none
+    void set_layer_norm(bool on) {
+        if (on && activation) norm.emplace(AHW.n(), AHW.m());
+        else norm.reset();
+    }
+    layer_norm_state<r_t> *layer_norm_params() { return norm ? &*norm : nullptr; }
     linear_t &linear_layer() { return lin; }
     std::vector<linear_t *> linears() {
         std::vector<linear_t *> v{&lin};
@@ -433,7 +507,8 @@ public:
     auto operator()(ctx_t ctx, dn_t H) {
         if (drop) apply_dropout(ctx, H, "0");
         this->H = H;
-        const bool act_done = aggregate_linear(ctx, H);
+        bool act_done = aggregate_linear(ctx, H);
+        if (norm) { norm_forward(ctx); act_done = fused; }
         if (activation && !act_done) {
             ctx.record(name + "0_0_activation", 0);
             leaky_relu_forward(ctx, AHW, AHW);
@@ -455,6 +530,7 @@ public:
     void update(const ctx_t ctx, const r_t lr, const r_t wd) { for (auto *l : linears()) l->update(ctx, lr, wd); }
     void adam_update(const ctx_t ctx, const r_t lr, const r_t b1, const r_t b2, const r_t wd, const r_t eps) {
         for (auto *l : linears()) l->adam_update(ctx, lr, b1, b2, wd, eps);
+        if constexpr (std::is_same_v<ctx_t, context>) { if (norm) norm->adam_update(ctx, lr, b1, b2, eps); }
     }
     auto b() { return lin.get_b(); }
     auto W() { return lin.get_W(); }
@@ -873,6 +949,15 @@ public:
         dropout_epoch_ = 0;
     }
     std::size_t dropout_epoch() const { return dropout_epoch_; }
+    // Layer normalisation (opt-in; the reference has none): every layer but the last normalises its rows between
+    // aggregation / linear and activation (mggcn_layer_norm_forward_f32), the activation in the same launch on the fused
+    // path; gamma (ones) and beta (zeros) are trained by Adam without weight decay.  It has no training mode: the plain
+    // forward runs the same kernels.  Switching it on (again) starts from fresh parameters; off launches nothing new.
+    void set_layer_norm(bool on) {
+        if (on) require_layer_norm();
+        for (auto &l : layers_) l.set_layer_norm(on);
+        adam_ = adam_table<r_t>();               // the table holds raw pointers: rebuilt with the next step
+    }
     // Train on one split (opt-in; the reference loads sets.bin and ignores it, src/main.cpp:85): S[i] is vertex i's set
     // (0 train / 1 validation / 2 test, anything else in no split).  From here on train_forward returns the loss and
     // accuracy of train_set; split_metrics() has every split's pair of the last epoch (train, val, test, other) from the
@@ -892,11 +977,15 @@ public:
         std::size_t step = 0;
         for (auto &l : layers_)
             for (auto *lin : l.linears()) { lin->adam_state(ctx); step = lin->bump_step(); }
+        for (auto &l : layers_)
+            if (auto *nm = l.layer_norm_params()) { nm->adam_state(ctx); nm->step = step; }
         if (!adam_ || adam_wd_ != wd) {
             std::vector<std::array<dn_matrix<r_t>, 4>> t;
             std::vector<r_t> w;
-            for (auto &l : layers_)
+            for (auto &l : layers_) {
                 for (auto *lin : l.linears()) lin->adam_tensors(t, w, wd);
+                if (auto *nm = l.layer_norm_params()) nm->adam_tensors(t, w);
+            }
             adam_ = adam_table<r_t>(ctx, t, w);
             adam_wd_ = wd;
         }

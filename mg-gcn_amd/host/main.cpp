@@ -19,7 +19,9 @@
 // a second line, "[mggcn splits] <e> train <loss> <acc> val <loss> <acc> test <loss> <acc>", every split;
 // MGGCN_DROPOUT=<p> (single GPU, not -R 1; 0 <= p < 1, unset or 0: none) drops the input of every layer but the first in
 // the training forward, with the counter-based mask of mggcn_dropout_f32 for seed MGGCN_DROPOUT_SEED=<u64> (default 0);
-// epoch e of the run is dropout epoch e; MGGCN_TIMING=1 prints the start-up stages.
+// epoch e of the run is dropout epoch e; MGGCN_LAYER_NORM=1 (single GPU, not -R 1; 0 or unset: none) normalises the rows
+// of every layer but the last between aggregation / linear and activation (mggcn_layer_norm_forward_f32), gamma and beta
+// trained with the weights; MGGCN_TIMING=1 prints the start-up stages.
 #include <unistd.h>
 
 #include <chrono>
@@ -59,6 +61,7 @@ static int help_() {
                  "                            every split per epoch; unset: loss and accuracy over all vertices\n"
                  "    MGGCN_DROPOUT=<p>     : drop the input of every layer but the first with probability p in [0, 1)\n"
                  "                            (single GPU); MGGCN_DROPOUT_SEED=<u64> picks the masks (default 0)\n"
+                 "    MGGCN_LAYER_NORM=1    : layer normalisation before the activation of every layer but the last (single GPU)\n"
                  "Arguments:\n"
                  "    train <dir> <k> <h1> ... <hk> : dataset directory, number of hidden layers and their widths\n";
     return EXIT_SUCCESS;
@@ -156,6 +159,14 @@ int main_(int argc, char **argv) {
             throw arg_error("MGGCN_DROPOUT is single-GPU only (not with -P > 1 or -R 1)");
     }
     if (const char *sd = std::getenv("MGGCN_DROPOUT_SEED")) dropout_seed = env_u64("MGGCN_DROPOUT_SEED", sd);
+    bool layer_norm_on = false;                                     // MGGCN_LAYER_NORM unset or 0: no norm, nothing launched
+    if (const char *ln = std::getenv("MGGCN_LAYER_NORM")) {
+        const std::string v = ln;
+        if (v != "0" && v != "1") throw arg_error("MGGCN_LAYER_NORM must be 0 or 1, not '" + v + "'");
+        layer_norm_on = v == "1";
+        if (layer_norm_on && (P > 1 || row_partition))              // the distributed classes have no norm
+            throw arg_error("MGGCN_LAYER_NORM is single-GPU only (not with -P > 1 or -R 1)");
+    }
 
     while (optind < argc && argv[optind] != nullptr) {
         const std::string command = argv[optind++];
@@ -205,6 +216,7 @@ int main_(int argc, char **argv) {
             if (env_is("MGGCN_HOIST_FIRST_AGGREGATION", "1")) G.set_hoist_first_aggregation(true);   // optional 6-SpMM epoch
             if (train_set >= 0) G.set_splits(S, train_set);
             if (dropout_p > 0.0) G.set_dropout(dropout_p, dropout_seed);             // train_forward number e is dropout epoch e
+            if (layer_norm_on) G.set_layer_norm(true);
             ctx.sync();
             stage("model (normalize, transpose, layers)");
             ctx.record("training-start", 0);
@@ -214,6 +226,10 @@ int main_(int argc, char **argv) {
                     for (std::size_t l = 0; l < G.layers().size(); l++) {
                         dump_dense(std::filesystem::path(dd) / ("e" + std::to_string(e) + "_W" + std::to_string(l) + ".bin"), G.layers()[l].W());
                         dump_dense(std::filesystem::path(dd) / ("e" + std::to_string(e) + "_b" + std::to_string(l) + ".bin"), G.layers()[l].b());
+                        if (auto *nm = G.layers()[l].layer_norm_params()) {     // MGGCN_LAYER_NORM=1: _gamma<layer>.bin, _beta<layer>.bin too
+                            dump_dense(std::filesystem::path(dd) / ("e" + std::to_string(e) + "_gamma" + std::to_string(l) + ".bin"), nm->gamma);
+                            dump_dense(std::filesystem::path(dd) / ("e" + std::to_string(e) + "_beta" + std::to_string(l) + ".bin"), nm->beta);
+                        }
                     }
                 }
                 const auto start = std::chrono::system_clock::now();

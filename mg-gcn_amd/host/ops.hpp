@@ -614,6 +614,44 @@ void dropout(const context ctx, const dn_matrix<r_t> in, const dn_matrix<r_t> ou
     mggcn_dropout_f32(ctx.stream(0), in.buffer(), out.buffer(), in.size(), in.m(), row0, d.threshold, d.scale, d.seed, d.stream);
 }
 
+// Layer normalisation with the activation in the same launch (include/mggcn.h: mggcn_layer_norm_forward_f32 /
+// mggcn_layer_norm_backward_f32).  Added to ABI version 1 later, like the entries above: weak references, checked when a
+// program asks for a norm.
+#pragma weak mggcn_layer_norm_forward_f32
+#pragma weak mggcn_layer_norm_backward_f32
+constexpr float layer_norm_eps = 1e-5f;                 // torch.nn.LayerNorm's default
+inline void require_layer_norm() {
+    mggcn_require(&mggcn_layer_norm_forward_f32 != nullptr && &mggcn_layer_norm_backward_f32 != nullptr,
+                  "this libmggcn_hip.so has no layer norm (mggcn_layer_norm_forward_f32)");
+}
+// Y = [leaky_relu](xhat . gamma + beta), xhat = (X - mean) rstd; Y may be X; writes xhat [n x m] and rstd [n x 1]
+template <typename r_t>
+void layer_norm(const context ctx, const dn_matrix<r_t> X, const dn_matrix<r_t> Y, const dn_matrix<r_t> xhat, const dn_matrix<r_t> rstd,
+                const dn_matrix<r_t> gamma, const dn_matrix<r_t> beta, bool leaky) {
+    require_layer_norm();
+    mggcn_require(X.m() >= 1 && X.m() <= 1024, "layer_norm: 1 <= m <= 1024 columns");
+    mggcn_require(X.shape() == Y.shape() && X.shape() == xhat.shape() && rstd.size() == X.n(), "layer_norm: shape mismatch");
+    mggcn_require(gamma.size() == X.m() && beta.size() == X.m(), "layer_norm: gamma and beta must hold m floats");
+    ctx.set();
+    mggcn_layer_norm_forward_f32(ctx.stream(0), X.buffer(), Y.buffer(), xhat.buffer(), rstd.buffer(), gamma.buffer(), beta.buffer(),
+                                 X.n(), X.m(), layer_norm_eps, leaky ? 1u : 0u);
+}
+// act: the sign source of leaky_relu' applied to G first (nullptr: G is taken as it is); G_in may be G or act
+template <typename r_t>
+void layer_norm_backward(const context ctx, const dn_matrix<r_t> G, const dn_matrix<r_t> *act, const dn_matrix<r_t> xhat,
+                         const dn_matrix<r_t> rstd, const dn_matrix<r_t> gamma, const dn_matrix<r_t> G_in, const dn_matrix<r_t> G_gamma,
+                         const dn_matrix<r_t> G_beta) {
+    require_layer_norm();
+    mggcn_require(G.m() >= 1 && G.m() <= 1024, "layer_norm_backward: 1 <= m <= 1024 columns");
+    mggcn_require(G.shape() == xhat.shape() && G.shape() == G_in.shape() && rstd.size() == G.n() && (!act || act->shape() == G.shape()),
+                  "layer_norm_backward: shape mismatch");
+    mggcn_require(gamma.size() == G.m() && G_gamma.size() == G.m() && G_beta.size() == G.m(),
+                  "layer_norm_backward: gamma and its gradients must hold m floats");
+    ctx.set();
+    mggcn_layer_norm_backward_f32(ctx.stream(0), G.buffer(), act ? act->buffer() : nullptr, xhat.buffer(), rstd.buffer(), gamma.buffer(),
+                                  G_in.buffer(), G_gamma.buffer(), G_beta.buffer(), G.n(), G.m(), act ? 1u : 0u);
+}
+
 // dist_context forms: per-GPU loops, as in the reference's "template<dn_t>" overloads
 template <typename r_t, template <typename> class dn_t>
 void leaky_relu_forward(const dist_context ctx, const dn_t<r_t> in, const dn_t<r_t> out, r_t a = 0.01) {

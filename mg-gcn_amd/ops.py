@@ -371,6 +371,49 @@ def dropout(ctx: context, X: dn_matrix, out: dn_matrix, p: float, seed: int, str
     dropout_raw(ctx, X, out, threshold, scale, seed, stream, row0)
 
 
+LAYER_NORM_EPS = 1e-5               # torch.nn.LayerNorm's default
+LAYER_NORM_MAX_WIDTH = 1024         # MGGCN_LN_MAX_WIDTH: a row lives in the registers of at most one wave
+LAYER_NORM_LEAKY_RELU = 1           # MGGCN_LN_LEAKY_RELU: the activation (slope 0.01) rides in the norm kernels
+
+
+def _req_layer_norm(X, xhat, rstd, gamma, what: str) -> None:
+    """the shapes both passes share; shape-only objects are enough (nothing here touches a buffer)"""
+    n, m = X.n(), X.m()
+    _req(1 <= m <= LAYER_NORM_MAX_WIDTH, f"{what} supports 1 <= m <= {LAYER_NORM_MAX_WIDTH} columns, got {m}")
+    _req(xhat.shape() == (n, m), f"{what}: xhat must be {n} x {m}")
+    _req(rstd.size() == n, f"{what}: rstd must hold {n} floats")
+    _req(gamma.shape() == (1, m), f"{what}: gamma must be 1 x {m}")
+
+
+def layer_norm(ctx: context, X: dn_matrix, Y: dn_matrix, xhat: dn_matrix, rstd: dn_matrix, gamma: dn_matrix,
+               beta: dn_matrix, flags: int = 0) -> None:
+    """Y = act(xhat * gamma + beta) row by row, xhat = (X - mean) * rstd, rstd = 1 / sqrt(var + LAYER_NORM_EPS), biased
+    variance (mggcn_layer_norm_forward_f32); writes Y, xhat [n x m] and rstd [n].  flags = LAYER_NORM_LEAKY_RELU applies
+    the project's leaky ReLU in the same pass.  Y may be X.  ValueError for a width outside 1 .. LAYER_NORM_MAX_WIDTH or a
+    shape mismatch, before the library is touched (it would print and exit, not raise)."""
+    _req_layer_norm(X, xhat, rstd, gamma, "layer norm")
+    _req(Y.shape() == X.shape(), "layer norm: Y must have X's shape")
+    _req(beta.shape() == gamma.shape(), f"layer norm: beta must be 1 x {X.m()}")
+    ctx.lib.mggcn_layer_norm_forward_f32(ctx.stream(0), X.buffer(), Y.buffer(), xhat.buffer(), rstd.buffer(),
+                                         gamma.buffer(), beta.buffer(), X.n(), X.m(), LAYER_NORM_EPS, int(flags))
+
+
+def layer_norm_backward(ctx: context, G: dn_matrix, act: Optional[dn_matrix], xhat: dn_matrix, rstd: dn_matrix,
+                        gamma: dn_matrix, G_in: dn_matrix, G_gamma: dn_matrix, G_beta: dn_matrix, flags: int = 0) -> None:
+    """The backward pass of layer_norm (mggcn_layer_norm_backward_f32): G_in [n x m], G_gamma and G_beta [1 x m] from the
+    incoming gradient G and the forward's xhat / rstd.  With flags = LAYER_NORM_LEAKY_RELU, G is first multiplied by
+    leaky_relu'(act) -- act is a sign source only, as in leaky_relu_backward -- and may be None without it.  G_in may be
+    G or act.  The column sums are bitwise reproducible.  The same checks before the library as layer_norm."""
+    _req_layer_norm(G, xhat, rstd, gamma, "layer norm backward")
+    _req(G_in.shape() == G.shape(), "layer norm backward: G_in must have G's shape")
+    _req(G_gamma.shape() == gamma.shape() and G_beta.shape() == gamma.shape(), f"layer norm backward: G_gamma and G_beta must be 1 x {G.m()}")
+    leaky = bool(int(flags) & LAYER_NORM_LEAKY_RELU)
+    _req(not leaky or (act is not None and act.shape() == G.shape()), "layer norm backward: act must have G's shape")
+    ctx.lib.mggcn_layer_norm_backward_f32(ctx.stream(0), G.buffer(), act.buffer() if leaky else None, xhat.buffer(),
+                                          rstd.buffer(), gamma.buffer(), G_in.buffer(), G_gamma.buffer(), G_beta.buffer(),
+                                          G.n(), G.m(), int(flags))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
