@@ -376,6 +376,30 @@ void mggcn_softmax_xent_fused_from_f32(mggcn_stream_t stream, const float *logit
 void mggcn_softmax_xent_split_from_f32(mggcn_stream_t stream, const float *logits, float *G, const int32_t *Y,
                                        const int32_t *S, size_t n_rows, size_t m, int32_t train_set, float grad_scale,
                                        float *sums_device);
+/* Multi-label loss (no counterpart in the reference, whose vertices have exactly one class): sigmoid + binary
+ * cross-entropy + gradient + the counts behind micro-F1 in one pass.  logits, G and T are contiguous [n_rows x m], any
+ * m >= 1 (no row-wise reduction, so no 1024-column limit), G == logits allowed; T is int32, non-zero = positive.  S is the
+ * split-aware form's n_rows x 1 set vector with the slots of the call above; S == NULL: every row is in slot 0 and trains.
+ * Per element, with z the logit, t in {0, 1}, softplus(x) = max(x, 0) + log1pf(expf(-|x|)):
+ *   loss = t ? softplus(-z) : softplus(z)            (never inf - inf: z = +-inf gives 0 or +inf, not NaN)
+ *   p    = z >= 0 ? 1 / (1 + expf(-z)) : expf(z) / (1 + expf(z))
+ *   G    = (p - t) * grad_scale if the row trains (S == NULL or S[i] == train_set), else +0.0 (written, not skipped)
+ *   pred = z > 0                                     (+-0 and NaN predict negative)
+ *   sums[4k + 0..3] += loss sum, TP, FP, FN counts over the rows of slot k   (MGGCN_BCE_SUMS floats, zeroed by the
+ *   caller; grad_scale = 1 / (the GLOBAL number of training rows x m); micro-F1 = 2 TP / (2 TP + FP + FN)).
+ * No atomics: sixteen partials per workgroup go to the per-(device, stream) scratch and a one-workgroup final pass adds
+ * them in a fixed order, so two calls on the same input give the same bits.  A slot gets its contributions by selects: a
+ * NaN or inf in a row of slot k reaches slot k's loss sum only.  The counts are sums of per-thread integers held in fp32:
+ * every workgroup partial and the total are exact while a count stays below 2^24 per slot, an fp32-rounded sum above (like
+ * the correct counts of the softmax form).  G is element-wise: an element's bits depend neither on the grid, nor on the
+ * other rows (rows [a, b) alone give the bits they have in the whole call), nor on the load path -- 16-byte loads when
+ * m % 4 == 0 and all three matrices are 16-byte aligned, single elements otherwise; the SUMS of the two paths may differ in
+ * their last bits.  With S == NULL, G and sums[0..3] are bit for bit G and slot train_set's four sums of a call with
+ * S[i] == train_set everywhere.  n_rows == 0 returns; m >= 1, non-null logits / G / T / sums and train_set in 0..2 are
+ * checked. */
+#define MGGCN_BCE_SUMS 16u
+void mggcn_sigmoid_bce_from_f32(mggcn_stream_t stream, const float *logits, float *G, const int32_t *T, const int32_t *S,
+                                size_t n_rows, size_t m, int32_t train_set, float grad_scale, float *sums_device);
 /* The two steps the unfused chain (src/gcn.hpp:785-818) needs to do the same, next to sets.bin being loaded and ignored at
  * src/main.cpp:85.  select_rows_by_set: row i of the [size / m x m] matrix stays if S[i] == set, else becomes +0.0. */
 void mggcn_select_rows_by_set_f32(mggcn_stream_t stream, float *mat, const int32_t *S, int32_t set, size_t size,

@@ -100,6 +100,7 @@ PROTOTYPES = {
     "mggcn_softmax_xent_fused_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_float, vp]),
     "mggcn_softmax_xent_fused_from_f32": (None, [vp, vp, vp, vp, c_size_t, c_size_t, c_float, vp]),
     "mggcn_softmax_xent_split_from_f32": (None, [vp, vp, vp, vp, vp, c_size_t, c_size_t, c_int32, c_float, vp]),
+    "mggcn_sigmoid_bce_from_f32": (None, [vp, vp, vp, vp, vp, c_size_t, c_size_t, c_int32, c_float, vp]),
     "mggcn_select_rows_by_set_f32": (None, [vp, vp, vp, c_int32, c_size_t, c_size_t]),
     "mggcn_abssum_by_set_f32": (None, [vp, vp, vp, c_size_t, vp]),
     "mggcn_adam_fused_f32": (None, [vp, vp, vp, vp, vp, c_float, c_float, c_float, c_float, c_float,

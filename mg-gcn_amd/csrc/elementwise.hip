@@ -243,8 +243,9 @@ __global__ __launch_bounds__(256) void adam_final_kernel(float *__restrict__ par
 // ---- |x| sum: fixed-order two-level reduction (reproducible) ---------------
 constexpr unsigned kAsumBlocks = 1024;
 constexpr unsigned kXentBlocks = kNumCU * 8;               // grid cap of the fused loss (stream_grid)
-constexpr unsigned kScratchFloats = 8 * kXentBlocks;        // abssum partials / the fused loss's (loss, correct) pairs: one pair
-                                                            // per workgroup, four (one per split slot) in the split-aware form
+constexpr unsigned kScratchFloats = 16 * kXentBlocks;       // abssum partials / the fused loss's (loss, correct) pairs: one pair
+                                                            // per workgroup, four (one per split slot) in the split-aware form /
+                                                            // the sigmoid-BCE loss's (loss, TP, FP, FN) per split slot
 
 __global__ __launch_bounds__(256) void abssum_partial_kernel(const float *__restrict__ A, size_t size,
                                                              float *__restrict__ partial) {
@@ -734,6 +735,92 @@ __global__ __launch_bounds__(256) void dropout_kernel(const float *in, float *ou
         out[i] = dropout_one(in[i], word, threshold, scale);
         at.step(m, step_rows, step_cols);
     }
+}
+
+// ---- fused sigmoid + binary cross-entropy + gradient + micro-F1 counts -------
+// The multi-label loss (mggcn_sigmoid_bce_from_f32): every element is a task of its own, so the pass has no row-wise
+// reduction and no width limit.  One exp and one log1p serve the loss and the gradient: with e = exp(-|z|),
+// softplus(+-z) = max(+-z, 0) + log1p(e) and sigmoid(z) = z >= 0 ? 1 / (1 + e) : e / (1 + e)  (exp(z) = e for z < 0).
+struct bce_term { float loss, g, tp, fp, fn; };
+
+__device__ __forceinline__ bce_term bce_one(float z, int32_t t, bool trains, float grad_scale) {
+    const bool pos = t != 0;
+    const float e = expf(-fabsf(z));
+    const float zt = pos ? -z : z;                                      // t ? softplus(-z) : softplus(z): never inf - inf
+    const float p = z >= 0.f ? 1.f / (1.f + e) : e / (1.f + e);
+    const bool pred = z > 0.f;                                          // +-0 and NaN predict negative
+    bce_term r;
+    r.loss = fmaxf(zt, 0.f) + log1pf(e);
+    r.g = trains ? (p - (pos ? 1.f : 0.f)) * grad_scale : 0.f;          // a select: +0.0 also where p is NaN
+    r.tp = (pred && pos) ? 1.f : 0.f;
+    r.fp = (pred && !pos) ? 1.f : 0.f;
+    r.fn = (!pred && pos) ? 1.f : 0.f;
+    return r;
+}
+
+// acc = [slot][loss, tp, fp, fn]; the slots other than the row's add +0.0, which keeps their bits (xent_add_by_slot)
+template <bool Split>
+__device__ __forceinline__ void bce_add_by_slot(uint32_t slot, float l, float tp, float fp, float fn, float (&acc)[Split ? 16 : 4]) {
+    if constexpr (Split) {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool mine = slot == (uint32_t)k;
+            acc[4 * k + 0] += mine ? l : 0.f;
+            acc[4 * k + 1] += mine ? tp : 0.f;
+            acc[4 * k + 2] += mine ? fp : 0.f;
+            acc[4 * k + 3] += mine ? fn : 0.f;
+        }
+    } else {
+        acc[0] += l; acc[1] += tp; acc[2] += fp; acc[3] += fn;
+    }
+}
+
+// V = 4: a unit is a float4 / int4 of one row (m % 4 == 0, 16-byte aligned operands); V = 1: a unit is an element.  Units
+// are walked grid-stride with the row carried along (dropout_walk: no division in the loop).  Every thread reads a unit
+// whole before it writes it, and no other thread touches it: dst may be src.  A thread's counts are small integers and a
+// workgroup's are sums of those: exact in fp32 below 2^24.  Split = false is the S == NULL form: every row trains and
+// lands in slot 0, with the additions of slot 0 of the split form in the same order.
+template <int V, bool Split>
+__global__ __launch_bounds__(256) void sigmoid_bce_kernel(const float *src, float *dst, const int32_t *__restrict__ T,
+                                                          const int32_t *__restrict__ S, size_t units, size_t q,
+                                                          uint64_t step_rows, uint64_t step_cols, int32_t train_set,
+                                                          float grad_scale, float *__restrict__ partials) {
+    constexpr int NA = Split ? 16 : 4;
+    __shared__ float w[16][4];                                          // [value][wave]
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    float acc[NA];
+#pragma unroll
+    for (int j = 0; j < NA; j++) acc[j] = 0.f;
+    dropout_walk at(q);
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < units; i += stride) {
+        int32_t s = 0;
+        if constexpr (Split) s = S[at.row];
+        const bool trains = !Split || s == train_set;
+        const uint32_t slot = Split ? xent_slot(s) : 0u;
+        if constexpr (V == 4) {
+            const float4 z = reinterpret_cast<const float4 *>(src)[i];
+            const int4 t = reinterpret_cast<const int4 *>(T)[i];
+            const bce_term a = bce_one(z.x, t.x, trains, grad_scale), b = bce_one(z.y, t.y, trains, grad_scale),
+                           c = bce_one(z.z, t.z, trains, grad_scale), d = bce_one(z.w, t.w, trains, grad_scale);
+            reinterpret_cast<float4 *>(dst)[i] = make_float4(a.g, b.g, c.g, d.g);
+            bce_add_by_slot<Split>(slot, (a.loss + b.loss) + (c.loss + d.loss), (a.tp + b.tp) + (c.tp + d.tp),
+                                   (a.fp + b.fp) + (c.fp + d.fp), (a.fn + b.fn) + (c.fn + d.fn), acc);
+        } else {
+            const bce_term a = bce_one(src[i], T[i], trains, grad_scale);
+            dst[i] = a.g;
+            bce_add_by_slot<Split>(slot, a.loss, a.tp, a.fp, a.fn, acc);
+        }
+        at.step(q, step_rows, step_cols);
+    }
+#pragma unroll
+    for (int j = 0; j < NA; j++) {
+        acc[j] = wave_sum(acc[j]);
+        if ((threadIdx.x & 63) == 0) w[j][threadIdx.x >> 6] = acc[j];
+    }
+    __syncthreads();
+    if (threadIdx.x < 16)                                               // sixteen values per workgroup, summed by sums_final_kernel<16>
+        partials[16 * blockIdx.x + threadIdx.x] =
+            threadIdx.x < NA ? (w[threadIdx.x][0] + w[threadIdx.x][1]) + (w[threadIdx.x][2] + w[threadIdx.x][3]) : 0.f;
 }
 
 // ---- layer normalisation: one row per group of L lanes ------------------------
@@ -1325,6 +1412,39 @@ MGGCN_API void mggcn_softmax_xent_split_from_f32(mggcn_stream_t stream, const fl
     MGGCN_REQUIRE(logits != nullptr && G != nullptr && Y != nullptr && S != nullptr && sums_device != nullptr,
                   "split-aware fused loss: null operand");
     launch_xent<true>(as_stream(stream), logits, G, Y, S, n_rows, m, train_set, grad_scale, sums_device);
+}
+
+namespace {
+template <bool Split>
+void launch_bce(hipStream_t st, const float *logits, float *G, const int32_t *T, const int32_t *S, size_t n_rows, size_t m,
+                int32_t train_set, float grad_scale, float *sums_device) {
+    float *partials = abssum_scratch(st);        // per (device, stream); 16 floats per workgroup of a grid of <= kXentBlocks
+    const bool vec = m % 4 == 0 && aligned16(logits) && aligned16(G) && aligned16(T);
+    const size_t q = vec ? m / 4 : m, units = n_rows * q;
+    const unsigned grid = stream_grid(units);
+    const size_t threads = (size_t)grid * 256;
+    if (vec)
+        hipLaunchKernelGGL((sigmoid_bce_kernel<4, Split>), dim3(grid), dim3(256), 0, st, logits, G, T, S, units, q,
+                           (uint64_t)(threads / q), (uint64_t)(threads % q), train_set, grad_scale, partials);
+    else
+        hipLaunchKernelGGL((sigmoid_bce_kernel<1, Split>), dim3(grid), dim3(256), 0, st, logits, G, T, S, units, q,
+                           (uint64_t)(threads / q), (uint64_t)(threads % q), train_set, grad_scale, partials);
+    MGGCN_CHECK_LAUNCH();
+    hipLaunchKernelGGL((sums_final_kernel<16, true>), dim3(1), dim3(256), 0, st, partials, grid, sums_device);
+    MGGCN_CHECK_LAUNCH();
+}
+}  // namespace
+
+MGGCN_API void mggcn_sigmoid_bce_from_f32(mggcn_stream_t stream, const float *logits, float *G, const int32_t *T,
+                                          const int32_t *S, size_t n_rows, size_t m, int32_t train_set, float grad_scale,
+                                          float *sums_device) {
+    if (!n_rows) return;
+    MGGCN_REQUIRE(m >= 1, "sigmoid-BCE loss: the width must be positive");
+    MGGCN_REQUIRE(train_set >= 0 && train_set <= 2, "train_set must be 0 (train), 1 (validation) or 2 (test)");
+    MGGCN_REQUIRE(logits != nullptr && G != nullptr && T != nullptr && sums_device != nullptr, "sigmoid-BCE loss: null operand");
+    static_assert(16u * kXentBlocks <= kScratchFloats, "sixteen partials per workgroup of the capped grid");
+    if (S) launch_bce<true>(as_stream(stream), logits, G, T, S, n_rows, m, train_set, grad_scale, sums_device);
+    else launch_bce<false>(as_stream(stream), logits, G, T, nullptr, n_rows, m, train_set, grad_scale, sums_device);
 }
 
 MGGCN_API void mggcn_select_rows_by_set_f32(mggcn_stream_t stream, float *mat, const int32_t *S, int32_t set, size_t size,

@@ -94,14 +94,17 @@ def read_dense(path: str, dtype) -> np.ndarray:
 
 
 def write_dataset(dirname: str, indptr, indices, data, features, labels, sets=None) -> None:
-    """Writes graph.bin / features.bin / labels.bin / sets.bin (reference prep.py:78-99)."""
+    """Writes graph.bin / features.bin / labels.bin / sets.bin (reference prep.py:78-99).  labels: [n] or [n x 1] class
+    indices, or an [n x C] multi-label target matrix (C > 1, non-zero = positive: the loss="bce" models), kept as n x C."""
     os.makedirs(dirname, exist_ok=True)
     write_csr(os.path.join(dirname, "graph.bin"), indptr, indices, data)
     write_dense(os.path.join(dirname, "features.bin"), features, "<f4")
-    labels = np.asarray(labels).reshape(-1, 1)
+    labels = np.asarray(labels)
+    if not (labels.ndim == 2 and labels.shape[1] > 1):
+        labels = labels.reshape(-1, 1)
     write_dense(os.path.join(dirname, "labels.bin"), labels, "<u4")
     if sets is None:
-        sets = np.zeros_like(labels)
+        sets = np.zeros_like(labels[:, :1])
     write_dense(os.path.join(dirname, "sets.bin"), np.asarray(sets).reshape(-1, 1), "<u4")
 
 
@@ -495,7 +498,8 @@ def read_edge_list(path: str):
 def prepare_dataset(dirname: str, adj, features, labels, sets=None, P: int = 8, seed: int = 0,
                     permutation=None, partitioner=None, pad_set: int = 0) -> str:
     """adj: scipy sparse (n x n) or (indptr, indices, data) CSR triple; features [n x F];
-    labels [n]; sets [n] in {0 train, 1 val, 2 test}.
+    labels [n], or [n x C] multi-label targets (C > 1: permuted with the rows, all-zero on padding vertices); sets [n]
+    in {0 train, 1 val, 2 test}.
       * pads the vertex count and the feature width to multiples of P with zero vertices /
         zero columns (prep.py:101-103, :122-124; padding vertices get label 0 and set ``pad_set``: 0 like the
         reference, which never uses the sets; 3 keeps them out of every split of a split-aware training run),
@@ -515,7 +519,9 @@ def prepare_dataset(dirname: str, adj, features, labels, sets=None, P: int = 8, 
     adj = sp.csr_matrix(adj, dtype=np.float32)
     n0 = adj.shape[0]
     features = np.asarray(features, dtype=np.float32).reshape(n0, -1)
-    labels = np.asarray(labels).reshape(n0).astype(np.int64)
+    labels = np.asarray(labels)
+    multi = labels.ndim == 2 and labels.shape[1] > 1
+    labels = (labels.reshape(n0, -1) if multi else labels.reshape(n0)).astype(np.int64)
     sets = np.zeros(n0, dtype=np.int64) if sets is None else np.asarray(sets).reshape(n0).astype(np.int64)
     n = (n0 + P - 1) // P * P
     F0 = features.shape[1]
@@ -525,7 +531,7 @@ def prepare_dataset(dirname: str, adj, features, labels, sets=None, P: int = 8, 
     adj.data[:] = np.where(adj.data != 0, adj.data, 1.0)
     feats = np.zeros((n, F), dtype=np.float32)
     feats[:n0, :F0] = features
-    labs = np.zeros(n, dtype=np.int64); labs[:n0] = labels
+    labs = np.zeros((n,) + labels.shape[1:], dtype=np.int64); labs[:n0] = labels
     if not 0 <= int(pad_set) <= 3:
         raise ValueError(f"pad_set must be 0, 1, 2 (a split) or 3 (no split), got {pad_set!r}")
     st = np.full(n, int(pad_set), dtype=np.int64); st[:n0] = sets

@@ -44,8 +44,9 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, ops
-from .gcn import (_check_agg_dtype, adam_update_all, check_counts, check_norm, check_sets, dropout_option, layer_body,
-                  layer_norm, linear, link_fused_backward, softmax_cross_entropy_loss, split_counts)
+from .gcn import (_check_agg_dtype, adam_update_all, check_counts, check_loss, check_norm, check_sets, check_targets,
+                  dropout_option, layer_body, layer_norm, linear, link_fused_backward, sigmoid_bce_loss,
+                  softmax_cross_entropy_loss, split_counts)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -594,7 +595,8 @@ def load_rank_local_host(dctx: host_comm, dirname: str):
     ymax = int(Y.max()) if Y.size else 0
     num_labels = 1 + (int(dctx.host_all_reduce(np.array([ymax], dtype=np.int64), "max")[0]) if P > 1 else ymax)
     info = {"n": n, "nnz_local": int(ip[-1]), "features": int(X.shape[1]), "num_labels": num_labels, "p": p,
-            "host_bytes": int(ip.nbytes + ix.nbytes + 2 * dv.nbytes + ent.nbytes + X.nbytes)}
+            "host_bytes": int(ip.nbytes + ix.nbytes + 2 * dv.nbytes + ent.nbytes + X.nbytes),
+            "label_columns": int(Y.shape[1])}        # 1: class indices; more: a multi-label target matrix (loss="bce")
     spath = os.path.join(dirname, "sets.bin")
     if os.path.exists(spath):             # this rank's rows of the splits (0 train / 1 val / 2 test), for dist_gcn.set_splits
         info["sets"] = ds.read_dense_rows(spath, "<i4", rb, re)
@@ -807,12 +809,14 @@ class dist_row_linear(linear):
     rank's shard and replica; W()/b()/GW()/Gb() of the layer are repl_dn_matrix views of them."""
 
     def __init__(self, dctx: dist_context, name: str, in_: int, out: int, backward_out: bool = True,
-                 fused: bool = False, extra_grads: int = 0):
+                 fused: bool = False, extra_grads: int = 0, tail_floats: int = 8):
         """extra_grads: floats behind [G_W | G_b | tail] that take part in the same all-reduce (``extra``): the layer's
-        norm keeps its two gradient rows there"""
+        norm keeps its two gradient rows there.  tail_floats: the length of ``tail`` -- 8 holds the loss sums of the
+        softmax loss, the last layer of a loss="bce" model asks for 16"""
         self._dctx = dctx
         self._grad_pending = None
         self._extra_grads = int(extra_grads)
+        self._tail_floats = int(tail_floats)
         with _torch().cuda.device(dctx.ctx.device):
             linear.__init__(self, name, in_, out, backward_out, fused)
 
@@ -822,11 +826,12 @@ class dist_row_linear(linear):
         off_b = (in_ * out + 3) // 4 * 4                       # keep G_b 16-byte aligned
         # ... and eight more floats after G_b: the model's LAST layer carries the epoch's loss sums through its gradient
         # all-reduce there (dist_gcn.train_step: no collective of their own) -- the front two, or all eight of a split-aware
-        # epoch
+        # epoch (sixteen floats where the model's loss is the multi-label one: tail_floats)
         off_t = (off_b + out + 3) // 4 * 4
-        self.G_flat = torch.zeros(off_t + 8 + self._extra_grads, dtype=torch.float32, device=self._dctx.ctx.device)
-        self.tail = self.G_flat[off_t:off_t + 8]
-        self.extra = self.G_flat[off_t + 8:]
+        nt = self._tail_floats
+        self.G_flat = torch.zeros(off_t + nt + self._extra_grads, dtype=torch.float32, device=self._dctx.ctx.device)
+        self.tail = self.G_flat[off_t:off_t + nt]
+        self.extra = self.G_flat[off_t + nt:]
         torch.cuda.current_stream().synchronize()              # torch zeroes on ITS stream (the padding takes part in the sum);
                                                                # the kernels run on the context's
         return dn_matrix(in_, out, self.G_flat), dn_matrix(1, out, self.G_flat[off_b:])
@@ -869,7 +874,7 @@ class dist_gcn_layer(layer_body):
     def __init__(self, dctx: dist_context, name: str, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
                  in_: int, out: int, activation: bool, residual_layer: bool = False, backward_spmm: bool = True,
                  HW_buffer=None, bcast_buffer=None, bcast_buffer2=None, fused: bool = False,
-                 mode: str = "allgather", agg_dtype: str = "f32", norm=None):
+                 mode: str = "allgather", agg_dtype: str = "f32", norm=None, tail_floats: int = 8):
         _check_agg_dtype(agg_dtype)
         normed = check_norm(norm) == "layer" and activation
         torch = _torch()
@@ -877,7 +882,7 @@ class dist_gcn_layer(layer_body):
         self.A = dist_sparse_linear(name, A, A_T, bcast_buffer, bcast_buffer2, mode, agg_dtype)
         # The norm's backward runs before lin.backward, whose all-reduce of [G_W | G_b | tail | G_gamma | G_beta] therefore
         # sums the norm's two gradient rows too: no collective of their own
-        lin = dist_row_linear(dctx, name, in_, out, backward_spmm, fused, 2 * out if normed else 0)
+        lin = dist_row_linear(dctx, name, in_, out, backward_spmm, fused, 2 * out if normed else 0, tail_floats)
         res_lin = dist_row_linear(dctx, name, in_, out, backward_spmm, False) if residual_layer and in_ != out else None
         mn = min(in_, out)
         self.AHW_buffer = torch.empty(max(A.n() * out, A_T.n() * in_) // P, dtype=torch.float32, device=dev)
@@ -907,10 +912,14 @@ class dist_row_softmax_cross_entropy_loss:
     """reference src/gcn.hpp:872-935: everything is row-local; the gradient is scaled
     by the GLOBAL n (:908); loss / accuracy are the sums of the per-rank scalars (:929).
     The reference sums them on the host of its single process; here a 2-float
-    all-reduce does it."""
+    all-reduce does it.
 
-    def __init__(self, name: str, copy: bool = True, fused: bool = False):
-        self.inner = softmax_cross_entropy_loss(name, copy, fused, host_sums=False)     # all-reduced as a device tensor
+    ``loss="bce"`` wraps gcn.sigmoid_bce_loss instead: the same row-local pass, (loss, micro-F1) where the softmax layer
+    gives (loss, acc), four or sixteen sums where it has two or eight."""
+
+    def __init__(self, name: str, copy: bool = True, fused: bool = False, loss: str = "softmax"):
+        inner = sigmoid_bce_loss if check_loss(loss) == "bce" else softmax_cross_entropy_loss
+        self.inner = inner(name, copy, fused, host_sums=False)                          # all-reduced as a device tensor
 
     def __call__(self, dctx: dist_context, H: dist_row_dn_matrix, Y: dist_row_dn_matrix, sync: bool = True):
         self.inner(dctx.ctx, H.local, Y.local, n_global=Y.n(), sync=False)
@@ -976,13 +985,15 @@ class dist_gcn(dropout_option):
 
     def __init__(self, dctx: dist_context, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
                  sizes: Sequence[int], residual_layer: bool = False, fused: bool = True, mode: str = "allgather",
-                 agg_dtype: str = "f32", dropout: float = 0.0, norm=None):
+                 agg_dtype: str = "f32", dropout: float = 0.0, norm=None, loss: str = "softmax"):
         self._init_dropout(dropout, len(sizes) - 1)          # option checks come before any device work
         self.norm = check_norm(norm)
+        self.loss = check_loss(loss)
+        self._out_width = int(sizes[-1])
         self.agg_dtype = _check_agg_dtype(agg_dtype)
         torch = _torch()
         P, dev = dctx.P, dctx.ctx.device
-        self.loss_layer = dist_row_softmax_cross_entropy_loss(f"{len(sizes) - 1}_", residual_layer, fused)
+        self.loss_layer = dist_row_softmax_cross_entropy_loss(f"{len(sizes) - 1}_", residual_layer, fused, self.loss)
         max_d = max(min(sizes[i], sizes[i + 1]) for i in range(len(sizes) - 1))
         nmax = max(A.n(), A.m())
         self.HW_buffer = torch.empty(nmax * max_d // P, dtype=torch.float32, device=dev)
@@ -1001,7 +1012,10 @@ class dist_gcn(dropout_option):
         for i in range(1, len(sizes)):
             self.layers_.append(dist_gcn_layer(dctx, f"{i - 1}_", A_T, A, sizes[i - 1], sizes[i],
                                                i + 1 < len(sizes), residual_layer, i != 1, self.HW_buffer,
-                                               self.bcast_buffer, self.bcast_buffer2, fused, mode, agg_dtype, self.norm))
+                                               self.bcast_buffer, self.bcast_buffer2, fused, mode, agg_dtype, self.norm,
+                                               # the LAST layer's tail carries the loss sums (train_step): sixteen of them
+                                               # with the multi-label loss, on that layer only
+                                               ops.BCE_SUMS if self.loss == "bce" and i + 1 == len(sizes) else 8))
             self.layers_[-1].A.agg_buffer = self.agg_buffer
         link_fused_backward(self.layers_, fused)
         self.fused, self._adam = fused, None
@@ -1056,7 +1070,11 @@ class dist_gcn(dropout_option):
             H = layer(dctx, H)
         return H
 
+    def _check_targets(self, Y) -> None:
+        check_targets(self.loss, getattr(Y, "local", Y), self.layers_[-1].AHW.n(), self._out_width)
+
     def train_forward(self, dctx: dist_context, H: dist_row_dn_matrix, Y: dist_row_dn_matrix):
+        self._check_targets(Y)
         H = self(dctx, H, training=True)
         return self.loss_layer(dctx, H, Y)
 
@@ -1082,10 +1100,12 @@ class dist_gcn(dropout_option):
         """forward + loss + backward + Adam with ONE host synchronisation and the loss all-reduce at the
         end of the epoch (see gcn.train_step); the reference's loop body is src/main.cpp:159-166."""
         torch = _torch()
+        self._check_targets(Y)
         out = self(dctx, H, training=True)
         self.loss_layer(dctx, out, Y, sync=False)
-        # The loss sums (two, or the eight of the splits) ride on the LAST layer's gradient all-reduce (eight spare floats
-        # behind [G_W | G_b]) instead of a collective and a device-to-host copy of their own after the epoch's synchronisation:
+        # The loss sums (two, or the eight of the splits; four or sixteen with loss="bce") ride on the LAST layer's gradient
+        # all-reduce (eight or sixteen spare floats behind [G_W | G_b]) instead of a collective and a device-to-host copy of
+        # their own after the epoch's synchronisation:
         # at P = 8 that turn-around was ~0.1 ms of idle GPU per 3.5-ms epoch.  (The reference adds its P managed scalars on
         # the host, src/gcn.hpp:929.)
         st = dctx.ctx.cuda_streams[0]
@@ -1096,7 +1116,7 @@ class dist_gcn(dropout_option):
         self.backward(dctx)                                    # ... -> finish_backward: the compute stream sees the summed buffers
         self.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
         if self._loss_host is None:
-            self._loss_host = torch.empty(8, dtype=torch.float32, pin_memory=True)
+            self._loss_host = torch.empty(self.layers_[-1].lin.tail.numel(), dtype=torch.float32, pin_memory=True)
         host = self._loss_host[:mine.numel()]
         with torch.cuda.stream(st):
             host.copy_(tail, non_blocking=True)

@@ -695,6 +695,140 @@ class softmax_cross_entropy_loss:
         return self.G
 
 
+LOSSES = ("softmax", "bce")
+
+
+def check_loss(loss: str) -> str:
+    """the ``loss=`` option of gcn / dist_gcn: "softmax" (one class per vertex, the reference's) or "bce" (multi-label)"""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be one of {LOSSES}, got {loss!r}")
+    return loss
+
+
+def check_targets(loss: str, Y, n: int, width: int) -> None:
+    """loss="bce": the targets are an int32 dn_matrix of n x width (one column per logit); before any launch"""
+    if loss != "bce":
+        return
+    if not isinstance(Y, dn_matrix) or Y.t.dtype != _torch().int32 or Y.shape() != (n, width):
+        got = f"{Y.t.dtype} of {Y.shape()}" if isinstance(Y, dn_matrix) else type(Y).__name__
+        raise ValueError(f"loss='bce' needs int32 targets of {n} x {width} (one column per logit), got {got}")
+
+
+def micro_f1(tp: float, fp: float, fn: float) -> float:
+    """2 TP / (2 TP + FP + FN); nan when nothing is positive and nothing was predicted positive"""
+    den = 2.0 * tp + fp + fn
+    return float(2.0 * tp / den) if den else float("nan")
+
+
+class sigmoid_bce_loss:
+    """The multi-label loss (opt-in, ``loss="bce"``; the reference has none): every logit is a binary task of its own,
+    the loss is sigmoid + binary cross-entropy averaged over rows AND columns, the score is micro-F1 with ``z > 0`` as
+    the prediction.  The interface of softmax_cross_entropy_loss; ``Y`` is the int32 [n x m] target matrix (non-zero =
+    positive) and (loss, micro-F1) comes back where that layer returns (loss, acc).  One kernel (ops.sigmoid_bce) makes
+    the pass: there is no unfused chain to mirror, so ``fused`` is accepted and ignored.  copy=True writes the gradient
+    to a second matrix, copy=False works in place.
+
+    Sixteen sums are kept, (loss sum, TP, FP, FN) per slot train / val / test / other; without splits every row is in
+    slot 0 and the front four are the active ones."""
+
+    def __init__(self, name: str, copy: bool = True, fused: bool = False, host_sums: bool = True):
+        self.name = name
+        self.copy, self.fused, self.host_sums = copy, fused, host_sums
+        self.G = None
+        self.split_sums = None              # the sixteen sums of the last call
+        self.sums = None                    # its front four: (loss sum, TP, FP, FN) of a call without splits
+        self.S: Optional[dn_matrix] = None
+        self.counts = None
+        self.train_set = 0
+        self._n = self._m = 0
+
+    def set_splits(self, S: Optional[dn_matrix], counts=None, train_set: int = 0) -> None:
+        """see softmax_cross_entropy_loss.set_splits"""
+        if S is None:
+            self.S, self.counts = None, None
+            return
+        if not isinstance(S, dn_matrix):
+            raise ValueError("the sets must be an int32 dn_matrix of n rows and one column")
+        _, self.counts = check_splits(S, S.n(), train_set, counts)
+        self.S, self.train_set = S, int(train_set)
+
+    def active_sums(self):
+        """the sums the last call wrote: all sixteen when the splits are on, the four of slot 0 otherwise"""
+        return self.sums if self.S is None else self.split_sums
+
+    def __call__(self, ctx: context, H: dn_matrix, Y: dn_matrix, n_global: Optional[int] = None,
+                 sync: bool = True):
+        torch = _torch()
+        n = self.name
+        check_targets("bce", Y, H.n(), H.m())
+        split = self.S is not None
+        if n_global is None:
+            n_global = Y.n()
+        if split and self.S.n() != H.n():
+            raise ValueError(f"the sets have {self.S.n()} rows, the logits {H.n()}")
+        rows = self.counts[self.train_set] if split else n_global      # what the gradient is averaged over, times m
+        if self.sums is None:
+            self.split_sums = (host_scalars(ops.BCE_SUMS) if self.host_sums
+                               else torch.empty(ops.BCE_SUMS, dtype=torch.float32, device=ctx.device))
+            self.sums = self.split_sums[0:4]
+        ctx.record(n + "0_loss-layer", 0)
+        if self.copy:
+            if self.G is None or self.G.shape() != H.shape():
+                self.G = dn_matrix(H.n(), H.m())
+        else:
+            self.G = H
+        # all sixteen are zeroed and written (the kernel's final pass adds sixteen): the four of slot 0 are read without splits
+        ctx.lib.mggcn_memset_zero(self.split_sums.data_ptr(), 4 * ops.BCE_SUMS, ctx.stream(0))
+        ops.sigmoid_bce(ctx, H, Y, self.S, self.train_set, 1.0 / (float(rows) * H.m()), self.split_sums, out=self.G)
+        ctx.record(n + "1_loss-layer", 0)
+        ctx.register_timer(n + "loss-layer", n + "0_loss-layer", n + "1_loss-layer")
+        self._n, self._m = H.n(), H.m()
+        if not sync:
+            return None
+        ctx.sync()
+        return self.read(ctx)
+
+    def _host(self, sums, k: int) -> np.ndarray:
+        if sums is None:
+            t = self.split_sums if k == ops.BCE_SUMS else self.sums
+            sums = t.numpy() if self.host_sums else t.cpu().numpy()
+        return np.asarray(sums, dtype=np.float32).reshape(-1)[:k].copy()
+
+    def split_metrics(self, sums=None):
+        """{"train": (loss, micro_f1), "val": ..., "test": ..., "other": ..., "counts": {...}, "confusion": {"train":
+        (tp, fp, fn), ...}} of the last call (after the caller's synchronisation); a split without a row reports a nan
+        loss, one without a positive target or prediction a nan F1"""
+        s = self._host(sums, ops.BCE_SUMS)
+        out, conf = {}, {}
+        for k, name in enumerate(ops.SPLIT_NAMES):
+            c = self.counts[k]
+            tp, fp, fn = (float(v) for v in s[4 * k + 1:4 * k + 4])
+            conf[name] = (tp, fp, fn)
+            out[name] = ((float(s[4 * k]) / (float(c) * self._m), micro_f1(tp, fp, fn)) if c
+                         else (float("nan"), float("nan")))
+        out["counts"] = dict(zip(ops.SPLIT_NAMES, self.counts))
+        out["confusion"] = conf
+        return out
+
+    def confusion(self, sums=None):
+        """(tp, fp, fn) behind the micro-F1 that read() reports: train_set's with splits, every row's without"""
+        if self.S is not None:
+            return self.split_metrics(sums)["confusion"][ops.SPLIT_NAMES[self.train_set]]
+        return tuple(float(v) for v in self._host(sums, 4)[1:4])
+
+    def read(self, ctx: context, sums=None, n: Optional[int] = None):
+        """(loss, micro_f1) of the last call; the caller has synchronised.  ``sums`` / ``n``: see
+        softmax_cross_entropy_loss.read"""
+        if self.S is not None:
+            return self.split_metrics(sums)[ops.SPLIT_NAMES[self.train_set]]
+        s = self._host(sums, 4)
+        n = self._n if n is None else n
+        return float(s[0]) / (float(n) * self._m), micro_f1(float(s[1]), float(s[2]), float(s[3]))
+
+    def backward(self) -> dn_matrix:
+        return self.G
+
+
 def split_counts(S: np.ndarray) -> List[int]:
     """rows per slot (train, val, test, other) of a host array of set values"""
     s = np.asarray(S).reshape(-1)
@@ -732,6 +866,22 @@ def check_splits(S, n: int, train_set: int, counts=None):
     global counts of a row partition; None counts S).  Returns (the sets as a host int32 [n x 1] array, the counts)."""
     host = check_sets(S, n, train_set)
     return host, check_counts(split_counts(host) if counts is None else counts, train_set)
+
+
+def evaluate_micro_f1(logits: np.ndarray, targets: np.ndarray, sets: Optional[np.ndarray] = None):
+    """{"all": micro-F1 over every row, "train" / "val" / "test": over the rows of that set} from host logits and targets"""
+    pred, pos = np.asarray(logits) > 0, np.asarray(targets) != 0
+
+    def f1(rows):
+        p, t = pred[rows], pos[rows]
+        return micro_f1(float((p & t).sum()), float((p & ~t).sum()), float((~p & t).sum()))
+
+    res = {"all": f1(slice(None))}
+    if sets is not None:
+        s = np.asarray(sets).reshape(-1)
+        for k, name in enumerate(ops.SPLIT_NAMES[:3]):
+            res[name] = f1(s == k)
+    return res
 
 
 def link_fused_backward(layers, fused: bool) -> None:
@@ -777,16 +927,20 @@ class gcn(dropout_option):
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], residual_layer: bool = False,
                  weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None, fused: bool = True,
-                 hoist_first_aggregation: bool = False, agg_dtype: str = "f32", dropout: float = 0.0, norm=None):
+                 hoist_first_aggregation: bool = False, agg_dtype: str = "f32", dropout: float = 0.0, norm=None,
+                 loss: str = "softmax"):
         self._init_dropout(dropout, len(sizes) - 1)          # option checks come before any device work
         self.norm = check_norm(norm)
+        self.loss = check_loss(loss)
+        self._out_width = int(sizes[-1])
         torch = _torch()
         self.agg_dtype = _check_agg_dtype(agg_dtype)
         if self.agg_dtype != "f32" and hoist_first_aggregation:
             raise ValueError("hoist_first_aggregation is fp32-only: with agg_dtype='bf16' the hoisted product would "
                              "round X instead of X W")
         self.fused = fused
-        self.loss_layer = softmax_cross_entropy_loss(f"{len(sizes) - 1}_", residual_layer, fused)
+        loss_class = sigmoid_bce_loss if self.loss == "bce" else softmax_cross_entropy_loss
+        self.loss_layer = loss_class(f"{len(sizes) - 1}_", residual_layer, fused)
         A.normalize(True)
         A_T = A.transpose()
         self.A, self.A_T = A, A_T
@@ -864,6 +1018,7 @@ class gcn(dropout_option):
         return H
 
     def train_forward(self, ctx: context, H: dn_matrix, Y: dn_matrix):
+        check_targets(self.loss, Y, self.A.n(), self._out_width)
         H = self(ctx, H, training=True)
         return self.loss_layer(ctx, H, Y)
 
@@ -878,6 +1033,7 @@ class gcn(dropout_option):
         adam_update, sync) with ONE host synchronisation: the loss / accuracy scalars are read after
         the epoch's last kernel instead of between forward and backward (the reference blocks inside
         its loss layer, src/gcn.hpp:816-817, and leaves the GPU idle while the host catches up)."""
+        check_targets(self.loss, Y, self.A.n(), self._out_width)
         out = self(ctx, H, training=True)
         self.loss_layer(ctx, out, Y, sync=False)
         self.backward(ctx)
@@ -906,7 +1062,15 @@ class gcn(dropout_option):
         sets.bin (0 train / 1 val / 2 test, test/data/prep.py:115-118) and never uses it
         (src/main.cpp:85); its reported accuracy is over ALL vertices, which is what
         ``result["all"]`` repeats.  Device work: the model's forward kernels + the argmax
-        kernel; the per-split counting is a host reduction over n integers."""
+        kernel; the per-split counting is a host reduction over n integers.
+
+        With loss="bce" the numbers are micro-F1 instead of accuracy (prediction: logit > 0), a host reduction over the
+        copied logits."""
+        if self.loss == "bce":
+            check_targets(self.loss, Y, self.A.n(), self._out_width)
+            out = self(ctx, H)
+            ctx.sync()
+            return evaluate_micro_f1(out.numpy(), Y.numpy(), None if S is None else S.numpy())
         out = self(ctx, H)
         P = dn_matrix(Y.shape(), dtype=np.int32)
         ops.max_row_indices(ctx, out, P)

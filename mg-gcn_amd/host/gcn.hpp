@@ -685,6 +685,23 @@ std::array<std::pair<r_t, r_t>, 4> split_metrics_of(const std::array<r_t, 8> &s,
     return out;
 }
 
+// The multi-label loss (opt-in, set_loss_bce; the reference has none): sixteen sums, (loss sum, TP, FP, FN) per slot, from
+// mggcn_sigmoid_bce_from_f32.  micro-F1 = 2 TP / (2 TP + FP + FN), nan when nothing is positive and nothing predicted so.
+template <typename r_t>
+r_t micro_f1(r_t tp, r_t fp, r_t fn) {
+    const r_t den = 2 * tp + fp + fn;
+    return den != 0 ? 2 * tp / den : std::numeric_limits<r_t>::quiet_NaN();
+}
+// (loss, micro-F1) per slot: the loss is the mean over the slot's rows AND the m columns; a split without a row reports nan
+template <typename r_t>
+std::array<std::pair<r_t, r_t>, 4> bce_metrics_of(const std::array<r_t, 16> &s, const std::array<std::size_t, 4> &counts, std::size_t m) {
+    std::array<std::pair<r_t, r_t>, 4> out;
+    for (std::size_t k = 0; k < 4; k++)
+        out[k] = counts[k] ? std::make_pair((r_t)(s[4 * k] / ((double)counts[k] * (double)m)), micro_f1(s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]))
+                           : std::make_pair(std::numeric_limits<r_t>::quiet_NaN(), std::numeric_limits<r_t>::quiet_NaN());
+    return out;
+}
+
 // One GPU's share of the loss: enqueues everything and leaves the sums in mapped pinned host memory -- {sum|log p_y|,
 // #correct} over its rows, or one such pair per slot with a loss_split; the caller synchronises and reads
 // (reference :785-818 / :890-930).
@@ -694,13 +711,24 @@ class loss_kernels {
     dn_matrix<r_t> G, L, T;
     dn_matrix<x_t> P;
     const bool copy, fused;
-    mggcn::device_ptr<r_t> sums_;    // eight floats, written by the kernels, read by the host after its sync
+    mggcn::device_ptr<r_t> sums_;    // eight floats (sixteen allocated: the multi-label loss writes them all), written by the
+                                     // kernels, read by the host after its sync
+    bool bce_ = false;               // the multi-label loss instead of softmax cross-entropy (set_bce)
     std::size_t slots_ = 1;          // pairs the last call wrote: 1, or the 4 of a split-aware call
     bool planar_ = false;            // ... as all loss sums, then all correct counts (the unfused chain) instead of pair by pair
 
 public:
     loss_kernels(bool copy, bool fused) : softmax_layer(copy), copy(copy), fused(fused) {}
     auto gradient() const { return G; }
+    void set_bce(bool on) { bce_ = on; }
+    bool bce() const { return bce_; }
+    // the sixteen sums of the last multi-label call: (loss sum, TP, FP, FN) of train / val / test / other; without a
+    // split every row is in the first slot
+    std::array<r_t, 16> bce_sums() const {
+        std::array<r_t, 16> out{};
+        for (std::size_t k = 0; k < 16; k++) out[k] = sums_.get()[k];
+        return out;
+    }
     // the sums of the last call as (loss sum, correct count) pairs: the one pair of a plain call first and zeros behind
     // it, or train / val / test / other
     std::array<r_t, 8> sums() const {
@@ -722,8 +750,20 @@ public:
             check_train_set(split->train_set);
             check_somebody_trains(split->n_train);
         }
-        if (!sums_) sums_ = mggcn::host_malloc<r_t>(8);
+        if (!sums_) sums_ = mggcn::host_malloc<r_t>(16);
         slots_ = split ? 4 : 1;
+        if (bce_) {                           // Y: the int32 [n x m] targets; one kernel, copy = true writes G elsewhere
+            if (copy) {
+                if (!G.buffer() || G.shape() != H.shape()) G = dn_matrix<r_t>(H.n(), H.m());
+            } else {
+                G = H;
+            }
+            const double rows = (double)(split ? split->n_train : n_global);
+            mggcn_memset_zero(sums_.get(), 16 * sizeof(r_t), ctx.stream(0));
+            sigmoid_bce(ctx, H, G, Y, split ? &split->S : nullptr, split ? split->train_set : 0,
+                        (r_t)(1.0 / (rows * (double)H.m())), sums_.get());
+            return;
+        }
         const r_t scale = (r_t)1 / (r_t)(split ? split->n_train : n_global);
         if (fused && H.m() >= 1 && H.m() <= 1024) {     // the one-pass kernel's widths; any other runs the chain below
             if (copy) {                       // reference: copy, then in place (:653-656); here the pass writes elsewhere
@@ -781,22 +821,37 @@ public:
     // the eight sums ((loss sum, correct count) of train / val / test / other) and the four row counts of the last call
     auto split_sums() const { return k.sums(); }
     auto split_counts_global() const { return counts_; }
-    auto split_metrics() const { return split_metrics_of<r_t>(k.sums(), counts_); }
+    auto split_metrics() const {
+        return k.bce() ? bce_metrics_of<r_t>(k.bce_sums(), counts_, m_) : split_metrics_of<r_t>(k.sums(), counts_);
+    }
+    // Multi-label training (opt-in): Y becomes the int32 [n x m] target matrix (non-zero = positive), the loss sigmoid +
+    // binary cross-entropy averaged over rows and columns, and every (loss, acc) pair this class returns a
+    // (loss, micro-F1) pair; bce_sums() has the raw (loss sum, TP, FP, FN) per slot of the last call.
+    void set_loss_bce(bool on = true) {
+        if (on) mggcn_require(&mggcn_sigmoid_bce_from_f32 != nullptr, "this libmggcn_hip.so has no sigmoid-BCE loss (mggcn_sigmoid_bce_from_f32)");
+        k.set_bce(on);
+    }
+    bool loss_bce() const { return k.bce(); }
+    auto bce_sums() const { return k.bce_sums(); }
 
     auto operator()(context ctx, dn_matrix<r_t> H, dn_matrix<x_t> Y) {
         if (split_) mggcn_require(split_->S.n() == H.n(), "the sets and the logits differ in their row count");
+        if (k.bce()) mggcn_require(Y.n() == H.n() && Y.m() == H.m(), "the multi-label targets must have the logits' shape");
+        m_ = H.m();
         ctx.record(name + "0_loss-layer", 0);
         k.enqueue(ctx, H, Y, Y.n(), split_);
         ctx.record(name + "1_loss-layer", 0);
         ctx.register_timer(name + "loss-layer", name + "0_loss-layer", name + "1_loss-layer");
         ctx.sync();
+        if (split_) return split_metrics()[(std::size_t)split_->train_set];         // the training split's pair
+        if (k.bce()) return bce_metrics_of<r_t>(k.bce_sums(), {H.n(), 0, 0, 0}, H.m())[0];
         const auto s = k.sums();
-        return split_ ? split_metrics()[(std::size_t)split_->train_set]             // the training split's pair
-                      : std::make_pair(s[0] / H.n(), s[1] / H.n());
+        return std::make_pair(s[0] / H.n(), s[1] / H.n());
     }
     auto backward() { return k.gradient(); }
 
 private:
+    std::size_t m_ = 1;                                          // width of the last call's logits
     std::optional<loss_split<x_t>> split_;
     std::array<std::size_t, 4> counts_{0, 0, 0, 0};
 };
@@ -966,6 +1021,10 @@ public:
     void clear_splits() { loss_layer.clear_splits(); }
     auto split_metrics() const { return loss_layer.split_metrics(); }
     auto split_counts() const { return loss_layer.split_counts_global(); }
+    // Multi-label training (opt-in; the reference has none): see softmax_cross_entropy_loss::set_loss_bce.  Y of
+    // train_forward is then the int32 [n x sizes.back()] target matrix and the pairs are (loss, micro-F1).
+    void set_loss_bce(bool on = true) { loss_layer.set_loss_bce(on); }
+    auto bce_sums() const { return loss_layer.bce_sums(); }
     void backward(const context ctx) {
         auto G = loss_layer.backward();
         for (auto l = layers_.rbegin(); l != layers_.rend(); l++) G = l->backward(ctx, G);

@@ -21,7 +21,10 @@
 // the training forward, with the counter-based mask of mggcn_dropout_f32 for seed MGGCN_DROPOUT_SEED=<u64> (default 0);
 // epoch e of the run is dropout epoch e; MGGCN_LAYER_NORM=1 (single GPU, not -R 1; 0 or unset: none) normalises the rows
 // of every layer but the last between aggregation / linear and activation (mggcn_layer_norm_forward_f32), gamma and beta
-// trained with the weights; MGGCN_TIMING=1 prints the start-up stages.
+// trained with the weights; MGGCN_LOSS=bce (single GPU, not -R 1; softmax or unset: the reference's loss) trains a
+// multi-label model: labels.bin is the n x C target matrix (non-zero = positive), "num_labels = " prints C, the loss is
+// sigmoid + binary cross-entropy and the accuracy column of the epoch line and of "[mggcn splits]" holds micro-F1;
+// MGGCN_TIMING=1 prints the start-up stages.
 #include <unistd.h>
 
 #include <chrono>
@@ -62,6 +65,8 @@ static int help_() {
                  "    MGGCN_DROPOUT=<p>     : drop the input of every layer but the first with probability p in [0, 1)\n"
                  "                            (single GPU); MGGCN_DROPOUT_SEED=<u64> picks the masks (default 0)\n"
                  "    MGGCN_LAYER_NORM=1    : layer normalisation before the activation of every layer but the last (single GPU)\n"
+                 "    MGGCN_LOSS=softmax|bce: bce = multi-label training (single GPU): labels.bin is an n x C 0/1 matrix, the\n"
+                 "                            loss sigmoid + binary cross-entropy, the reported score micro-F1\n"
                  "Arguments:\n"
                  "    train <dir> <k> <h1> ... <hk> : dataset directory, number of hidden layers and their widths\n";
     return EXIT_SUCCESS;
@@ -167,6 +172,14 @@ int main_(int argc, char **argv) {
         if (layer_norm_on && (P > 1 || row_partition))              // the distributed classes have no norm
             throw arg_error("MGGCN_LAYER_NORM is single-GPU only (not with -P > 1 or -R 1)");
     }
+    bool loss_bce = false;                                          // MGGCN_LOSS unset or softmax: the reference's loss
+    if (const char *ls = std::getenv("MGGCN_LOSS")) {
+        const std::string v = ls;
+        if (v != "softmax" && v != "bce") throw arg_error("MGGCN_LOSS must be softmax or bce, not '" + v + "'");
+        loss_bce = v == "bce";
+        if (loss_bce && (P > 1 || row_partition))                   // the distributed classes have no multi-label loss
+            throw arg_error("MGGCN_LOSS=bce is single-GPU only (not with -P > 1 or -R 1)");
+    }
 
     while (optind < argc && argv[optind] != nullptr) {
         const std::string command = argv[optind++];
@@ -186,7 +199,8 @@ int main_(int argc, char **argv) {
         stage("load-files");
         std::cerr << A.n() << ' ' << A.nnz() << std::endl;
         const auto labels = Y.to_host();
-        const auto num_labels = 1 + *std::max_element(labels.begin(), labels.end());
+        // MGGCN_LOSS=bce: one logit per column of the target matrix
+        const auto num_labels = loss_bce ? (std::int32_t)Y.m() : 1 + *std::max_element(labels.begin(), labels.end());
         std::cerr << "num_labels = " << num_labels << std::endl;
         std::cerr << "feature size = " << X.m() << std::endl;
 
@@ -198,6 +212,8 @@ int main_(int argc, char **argv) {
             sizes.push_back(std::stoull(argv[optind++]));
         }
         sizes.push_back((std::size_t)num_labels);
+        if (loss_bce && Y.m() != sizes.back())
+            throw arg_error("MGGCN_LOSS=bce: labels.bin has " + std::to_string(Y.m()) + " columns, the last layer " + std::to_string(sizes.back()));
 
         // csvs/<[permuted_]name>_<sizes>_<P>.csv (reference :100-111)
         std::string filename;
@@ -217,6 +233,7 @@ int main_(int argc, char **argv) {
             if (train_set >= 0) G.set_splits(S, train_set);
             if (dropout_p > 0.0) G.set_dropout(dropout_p, dropout_seed);             // train_forward number e is dropout epoch e
             if (layer_norm_on) G.set_layer_norm(true);
+            if (loss_bce) G.set_loss_bce();
             ctx.sync();
             stage("model (normalize, transpose, layers)");
             ctx.record("training-start", 0);

@@ -590,6 +590,23 @@ void abssum_by_set(const context ctx, const dn_matrix<r_t> x, const dn_matrix<x_
     mggcn_abssum_by_set_f32(ctx.stream(0), x.buffer(), S.buffer(), x.n(), result_device);
 }
 
+// Multi-label loss (include/mggcn.h: mggcn_sigmoid_bce_from_f32): T is the int32 [n x m] target matrix (non-zero =
+// positive), S the sets or nullptr (every row trains, slot 0), sums_device holds MGGCN_BCE_SUMS floats: (loss sum, TP, FP,
+// FN) per slot.  Added to ABI version 1 later, like the entries above: a weak reference, checked when a program asks for it.
+#pragma weak mggcn_sigmoid_bce_from_f32
+template <typename r_t, typename x_t>
+void sigmoid_bce(const context ctx, const dn_matrix<r_t> H, const dn_matrix<r_t> G, const dn_matrix<x_t> T,
+                 const dn_matrix<x_t> *S, int train_set, r_t grad_scale, r_t *sums_device) {
+    mggcn_require(&mggcn_sigmoid_bce_from_f32 != nullptr, "this libmggcn_hip.so has no sigmoid-BCE loss (mggcn_sigmoid_bce_from_f32)");
+    mggcn_require(H.m() >= 1 && T.n() == H.n() && T.m() == H.m(), "sigmoid_bce: targets must have the logits' shape");
+    mggcn_require(!S || (H.n() == S->n() && S->m() == 1), "sigmoid_bce: sets must be n x 1");
+    mggcn_require(G.n() == H.n() && G.m() == H.m(), "sigmoid_bce: gradient matrix must have the logits' shape");
+    mggcn_require(train_set >= 0 && train_set <= 2, "sigmoid_bce: train_set must be 0, 1 or 2");
+    ctx.set();
+    mggcn_sigmoid_bce_from_f32(ctx.stream(0), H.buffer(), G.buffer(), T.buffer(), S ? S->buffer() : nullptr, H.n(), H.m(),
+                               train_set, grad_scale, sums_device);
+}
+
 // Dropout with a counter-based mask that is never stored (include/mggcn.h: mggcn_dropout_f32).  Added to ABI version 1
 // later, like the entries above: a weak reference, checked when a program asks for dropout.
 #pragma weak mggcn_dropout_f32

@@ -464,6 +464,31 @@ def softmax_xent_split(ctx: context, H: dn_matrix, Y: dn_matrix, S: dn_matrix, t
                                               H.m(), int(train_set), grad_scale, sums_device.data_ptr())
 
 
+BCE_SUMS = 16                       # MGGCN_BCE_SUMS: (loss sum, TP, FP, FN) per slot train / val / test / other
+
+
+def sigmoid_bce(ctx: context, H: dn_matrix, T: dn_matrix, S: Optional[dn_matrix], train_set: int, grad_scale: float,
+                sums_device, out: Optional[dn_matrix] = None) -> None:
+    """The multi-label loss (mggcn_sigmoid_bce_from_f32): sigmoid + binary cross-entropy + gradient + the micro-F1 counts
+    in one pass, in place on H or H -> out.  T: int32 targets of H's shape (non-zero = positive); S: the sets or None
+    (every row trains and counts as slot 0); sums_device holds BCE_SUMS floats, zeroed by the caller.  Any width >= 1."""
+    torch = __import__("torch")
+    _req(H.m() >= 1, "sigmoid-BCE loss: the width must be positive")
+    _req(isinstance(T, dn_matrix) and T.t.dtype == torch.int32, "sigmoid-BCE loss: the targets must be an int32 dn_matrix")
+    _req(T.n() == H.n() and T.m() == H.m(),
+         f"sigmoid-BCE loss: the targets must be {H.n()} x {H.m()} like the logits, got {T.n()} x {T.m()}")
+    _req(train_set in TRAIN_SETS, f"train_set must be one of {TRAIN_SETS}, got {train_set!r}")
+    if S is not None:
+        _req_sets(S, H.n(), "sigmoid-BCE loss")
+    if out is None:
+        out = H
+    _req(out.n() == H.n() and out.m() == H.m(), "sigmoid-BCE loss: gradient matrix must have the logits' shape")
+    _req(sums_device.numel() >= BCE_SUMS, f"sigmoid-BCE loss: sums must hold {BCE_SUMS} floats")
+    ctx.lib.mggcn_sigmoid_bce_from_f32(ctx.stream(0), H.buffer(), out.buffer(), T.buffer(),
+                                       S.buffer() if S is not None else None, H.n(), H.m(), int(train_set), grad_scale,
+                                       sums_device.data_ptr())
+
+
 def select_rows_by_set(ctx: context, mat: dn_matrix, S: dn_matrix, set_: int) -> None:
     """mat[i, :] = +0.0 where S[i] != set_ (mggcn_select_rows_by_set_f32)"""
     _req(mat.m() >= 1, "row width must be positive")

@@ -24,7 +24,7 @@ def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--edges", required=True, help='text file of "u v" lines, or .npy of shape [E, 2] / [2, E]')
     ap.add_argument("--features", required=True, help=".npy float array [n, F]")
-    ap.add_argument("--labels", required=True, help=".npy integer array [n]")
+    ap.add_argument("--labels", required=True, help=".npy integer array [n], or [n, C] multi-label targets (C > 1, for MGGCN_LOSS=bce / loss='bce')")
     ap.add_argument("--sets", default=None, help=".npy integer array [n]: 0 train, 1 validation, 2 test")
     ap.add_argument("--pad-set", type=int, default=0, choices=(0, 1, 2, 3),
                     help="set value of the padding vertices (default 0 = train, like the reference; 3 = in no split)")
@@ -37,7 +37,9 @@ def main(argv=None) -> int:
     ds = ge.load_package().datasets
     src, dst = ds.read_edge_list(a.edges)
     X = np.load(a.features, allow_pickle=False)
-    y = np.load(a.labels, allow_pickle=False).reshape(-1)
+    y = np.load(a.labels, allow_pickle=False)
+    if not (y.ndim == 2 and y.shape[1] > 1):                            # [n, C] targets stay a matrix
+        y = y.reshape(-1)
     sets = np.load(a.sets, allow_pickle=False).reshape(-1) if a.sets else None
     if X.shape[0] != y.shape[0]:
         sys.exit(f"features hold {X.shape[0]} vertices, labels {y.shape[0]}")
