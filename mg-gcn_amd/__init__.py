@@ -11,7 +11,9 @@ Layout:
   ops.py       matmul / get_matmul_buffer / kernels     (reference src/cuda_utils.hpp)
   gcn.py       sparse_linear / linear / gcn_layer / gcn (reference src/gcn.hpp)
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*)
-  datasets.py  on-disk format + synthetic generators    (reference test/data/prep.py)
+  datasets.py  on-disk format + synthetic generators    (reference test/data/prep.py); the checkpoint file
+  checkpoint.py  save / load / predict of gcn and dist_gcn (no reference counterpart)
+  selection.py   model_selector: best epoch on a split, early stopping
 """
 from . import _lib, datasets                                   # noqa: F401
 from ._lib import engine_error                                  # noqa: F401
@@ -26,6 +28,9 @@ from . import dist                                              # noqa: F401
 from .dist import (dist_context, dist_gcn, dist_gcn_layer, dist_row_csr_matrix,  # noqa: F401
                    dist_row_dn_matrix, dist_row_linear, dist_sparse_linear, repl_dn_matrix)
 
+from . import checkpoint, selection                             # noqa: F401
+from .selection import model_selector                           # noqa: F401
+
 __all__ = ["context", "csr_matrix", "dn_matrix", "matrix_error", "engine_error", "ops", "matmul",
            "get_matmul_buffer", "sparse_linear", "linear", "gcn_layer", "softmax",
-           "softmax_cross_entropy_loss", "gcn", "datasets"]
+           "softmax_cross_entropy_loss", "gcn", "datasets", "model_selector"]

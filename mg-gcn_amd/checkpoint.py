@@ -1,0 +1,134 @@
+"""save / load / predict of gcn and dist.dist_gcn (opt-in; the reference writes nothing to disk).
+
+The file is the one of datasets.write_checkpoint (INTEGRATION.md "Checkpoint file"): the model's configuration, every
+parameter tensor, optionally Adam's moments and step count, and the dropout state (p, seed, epoch).  Execution options
+(fused, agg_dtype, hoisting, the exchange schedule, P) are not model state and are not stored: weights are replicated and
+the dropout masks are counter-based on (seed, epoch, global row, column), so a file written by one form loads into any
+other and a resumed run draws the masks the uninterrupted run would have drawn.
+
+Nothing here launches a new kernel: the tensors move through dn_matrix.init (host to device, in place), dn_matrix.zero and
+dn_matrix.copy_to.  A model that never calls these members runs exactly what it ran before.
+"""
+from __future__ import annotations
+
+from typing import Dict, List
+
+import numpy as np
+
+from . import datasets, ops
+from .matrix import dn_matrix
+
+
+def raw_context(ctx):
+    """the matrix.context behind a context or a dist.dist_context"""
+    return getattr(ctx, "ctx", ctx)
+
+
+def model_params(model) -> List[tuple]:
+    """[(name, owner, parameter attribute, m attribute, v attribute)] in file order (datasets.checkpoint_tensors); the
+    owner is the linear or layer_norm that holds the tensor, its Adam moments and its step count"""
+    out = []
+    for l, layer in enumerate(model.layers_):
+        out += [(f"W{l}", layer.lin, "W", "mW", "vW"), (f"b{l}", layer.lin, "b", "mb", "vb")]
+        if layer.res_lin is not None:
+            out += [(f"res_W{l}", layer.res_lin, "W", "mW", "vW"), (f"res_b{l}", layer.res_lin, "b", "mb", "vb")]
+        if layer.norm is not None:
+            out += [(f"gamma{l}", layer.norm, "gamma", "mg", "vg"), (f"beta{l}", layer.norm, "beta", "mb", "vb")]
+    return out
+
+
+def model_owners(model) -> list:
+    """every linear and layer_norm of the model: what carries Adam state"""
+    return [p for layer in model.layers_ for p in layer.params()]
+
+
+def reset_adam(model, ctx) -> None:
+    """zero moments (allocated first where the model never stepped), step 0; stream-ordered"""
+    rc = raw_context(ctx)
+    for owner in model_owners(model):
+        owner.adam_state(rc)
+        owner.step = 0
+    for _, owner, _, m, v in model_params(model):
+        getattr(owner, m).zero(rc)
+        getattr(owner, v).zero(rc)
+
+
+def config_mismatch(file_cfg: dict, model_cfg: dict):
+    """the first differing field as "<field>: file <x>, model <y>", or None"""
+    for key in ("sizes", "residual_layer", "norm", "loss"):
+        if file_cfg[key] != model_cfg[key]:
+            return f"{key}: file {file_cfg[key]}, model {model_cfg[key]}"
+    return None
+
+
+class checkpoint_option:
+    """save / load / predict of gcn and dist.dist_gcn.  ``ctx`` is what the model's other members take: a context, or
+    the rank's dist_context -- every rank of a dist_gcn calls save and load (rank 0 alone writes, every rank reads) and
+    predict returns the rank's rows."""
+
+    def checkpoint_config(self) -> dict:
+        return {"sizes": [int(s) for s in self.sizes], "residual_layer": bool(self.residual_layer), "norm": self.norm,
+                "loss": self.loss, "dropout": (self.dropout_p, self.dropout_seed, self.dropout_epoch)}
+
+    def _write_checkpoint(self, ctx, path: str, tensors: Dict[str, np.ndarray], optimizer: bool, step: int) -> None:
+        """rank 0 writes; the others leave once the file is complete"""
+        if getattr(ctx, "rank", 0) == 0 or not hasattr(ctx, "P"):
+            datasets.write_checkpoint(path, dict(self.checkpoint_config(), optimizer=optimizer, step=step), tensors)
+        if getattr(ctx, "P", 1) > 1:
+            ctx.host_all_reduce(np.zeros(1, dtype=np.int64))
+
+    def save(self, ctx, path: str, optimizer: bool = True) -> None:
+        """Writes the parameters, the dropout state and (``optimizer``) Adam's moments and step count.  A model that has
+        not stepped yet stores zero moments and step 0."""
+        ctx.sync()
+        tensors, steps = {}, set()
+        for name, owner, p, m, v in model_params(self):
+            tensors[name] = getattr(owner, p).numpy()
+            if optimizer:
+                stepped = getattr(owner, m) is not None
+                steps.add(int(owner.step) if stepped else 0)
+                tensors["m." + name] = getattr(owner, m).numpy() if stepped else np.zeros_like(tensors[name])
+                tensors["v." + name] = getattr(owner, v).numpy() if stepped else np.zeros_like(tensors[name])
+        if len(steps) > 1:
+            raise ValueError(f"the model's tensors disagree on Adam's step count: {sorted(steps)}")
+        self._write_checkpoint(ctx, path, tensors, bool(optimizer), steps.pop() if steps else 0)
+
+    def load(self, ctx, path: str) -> None:
+        """Reads ``path`` into this model, in place: the parameter and moment buffers keep their addresses (the fused Adam
+        table holds raw pointers).  ValueError naming the first differing field of the configuration -- sizes,
+        residual_layer, norm, loss -- before anything is written.  A file without the optimiser section resets Adam
+        (zero moments, step 0).  Restores every step count and calls set_dropout with the file's (p, seed, epoch)."""
+        cfg, tensors = datasets.read_checkpoint(path)
+        bad = config_mismatch(cfg, self.checkpoint_config())
+        if bad is not None:
+            raise ValueError(f"{path}: {bad}")
+        self.set_dropout(*cfg["dropout"])                       # host state; its own refusals come before any device write
+        rc = raw_context(ctx)
+        for owner in model_owners(self):
+            owner.adam_state(rc)                                # a model that never stepped: allocate (and zero) first
+        ctx.sync()                                              # dn_matrix.init copies on torch's stream, then synchronises
+        for name, owner, p, m, v in model_params(self):
+            getattr(owner, p).init(tensors[name])
+            if cfg["optimizer"]:
+                getattr(owner, m).init(tensors["m." + name])
+                getattr(owner, v).init(tensors["v." + name])
+            else:
+                getattr(owner, m).zero(rc)
+                getattr(owner, v).zero(rc)
+        for owner in model_owners(self):
+            owner.step = int(cfg["step"])
+        ctx.sync()
+
+    def predict(self, ctx, X) -> np.ndarray:
+        """Host int32 predictions of a plain forward (it never drops): [n x 1] argmax, the first maximum winning
+        (ops.max_row_indices), or [n x C] 0 / 1 for logit > 0 with loss="bce".  dist_gcn: the rank's rows."""
+        rc = raw_context(ctx)
+        out = self(ctx, X)
+        out = getattr(out, "local", out)
+        if self.loss == "bce":
+            ctx.sync()
+            return (out.numpy() > 0).astype(np.int32)
+        P = dn_matrix(out.n(), 1, dtype=np.int32, device=rc.device)
+        ops.max_row_indices(rc, out, P)
+        ctx.sync()
+        return P.numpy()

@@ -119,6 +119,138 @@ def read_dataset(dirname: str):
 
 
 # ----------------------------------------------------------------------------
+# Checkpoint file (INTEGRATION.md "Checkpoint file"; the C++ twin is host/checkpoint.hpp).  One little-endian file,
+# nothing in it but the state: the same state gives the same bytes.
+#
+#   "MGGCNCKP" | u32 version = 1 | u32 L | u32 sizes[L] | u32 residual_layer | u32 norm (0 none, 1 layer) |
+#   u32 loss (0 softmax, 1 bce) | u32 optimizer (0 / 1) | f64 dropout p | u64 dropout seed | u64 dropout epoch |
+#   u64 Adam step | u32 T | T x { u32 name length | name | u32 rows | u32 cols | f32 payload[rows * cols] } |
+#   optimizer = 1: T x { f32 m[rows * cols] | f32 v[rows * cols] } in the order of the tensors | end of file
+#
+# The tensors are exactly those the configuration implies, in the order of checkpoint_tensors().
+# ----------------------------------------------------------------------------
+CHECKPOINT_MAGIC = b"MGGCNCKP"
+CHECKPOINT_VERSION = 1
+CHECKPOINT_NORMS = (None, "layer")
+CHECKPOINT_LOSSES = ("softmax", "bce")
+CHECKPOINT_MAX_LAYERS = 4096
+
+
+def checkpoint_tensors(sizes, residual_layer: bool, norm):
+    """[(name, (rows, cols))] of every parameter tensor of a model, in file order: per layer l W<l>, b<l>, then res_W<l>,
+    res_b<l> where a residual layer's widths differ, then gamma<l>, beta<l> where the layer has a norm (never the last)"""
+    out = []
+    for l in range(len(sizes) - 1):
+        i, o = int(sizes[l]), int(sizes[l + 1])
+        out += [(f"W{l}", (i, o)), (f"b{l}", (1, o))]
+        if residual_layer and i != o:
+            out += [(f"res_W{l}", (i, o)), (f"res_b{l}", (1, o))]
+        if norm == "layer" and l + 2 < len(sizes):
+            out += [(f"gamma{l}", (1, o)), (f"beta{l}", (1, o))]
+    return out
+
+
+def write_checkpoint(path: str, config: dict, tensors: dict) -> None:
+    """config: {"sizes", "residual_layer", "norm" (None / "layer"), "loss" ("softmax" / "bce"), "dropout": (p, seed,
+    epoch), "step", "optimizer" (bool)}; tensors: name -> float32 array for every name of checkpoint_tensors(), and
+    "m.<name>" / "v.<name>" as well when config["optimizer"]."""
+    sizes = [int(s) for s in config["sizes"]]
+    norm, loss = config.get("norm"), config.get("loss", "softmax")
+    if len(sizes) < 2 or len(sizes) > CHECKPOINT_MAX_LAYERS or min(sizes) < 1 or max(sizes) >= 2 ** 32:
+        raise format_error(f"{path}: sizes {sizes} cannot be stored")
+    if norm not in CHECKPOINT_NORMS or loss not in CHECKPOINT_LOSSES:
+        raise format_error(f"{path}: norm {norm!r} / loss {loss!r} cannot be stored")
+    optimizer = bool(config.get("optimizer", False))
+    p, seed, epoch = config.get("dropout", (0.0, 0, 0))
+    want = checkpoint_tensors(sizes, bool(config.get("residual_layer", False)), norm)
+
+    def payload(name, shape):
+        if name not in tensors:
+            raise format_error(f"{path}: tensor {name} is missing")
+        a = np.ascontiguousarray(tensors[name], dtype="<f4")
+        if a.size != shape[0] * shape[1]:
+            raise format_error(f"{path}: tensor {name} has {a.size} elements, the model {shape[0]} x {shape[1]}")
+        return a.tobytes()
+
+    parts = [CHECKPOINT_MAGIC, np.array([CHECKPOINT_VERSION, len(sizes)] + sizes, dtype="<u4").tobytes(),
+             np.array([int(bool(config.get("residual_layer", False))), CHECKPOINT_NORMS.index(norm),
+                       CHECKPOINT_LOSSES.index(loss), int(optimizer)], dtype="<u4").tobytes(),
+             np.array([float(p)], dtype="<f8").tobytes(),
+             np.array([int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(config.get("step", 0)) if optimizer else 0],
+                      dtype="<u8").tobytes(),
+             np.array([len(want)], dtype="<u4").tobytes()]
+    for name, shape in want:
+        parts += [np.array([len(name)], dtype="<u4").tobytes(), name.encode("ascii"),
+                  np.array(shape, dtype="<u4").tobytes(), payload(name, shape)]
+    if optimizer:
+        for name, shape in want:
+            parts += [payload("m." + name, shape), payload("v." + name, shape)]
+    with open(path, "wb") as f:
+        f.write(b"".join(parts))
+
+
+def read_checkpoint(path: str):
+    """(config, tensors) as write_checkpoint takes them.  Every length is checked against the file's size before anything
+    is copied; a truncated file, trailing bytes, a wrong magic or an unknown version is a format_error naming the file."""
+    with open(path, "rb") as f:
+        buf = f.read()
+    at = 0
+
+    def take(nbytes: int, what: str) -> bytes:
+        nonlocal at
+        if nbytes > len(buf) - at:
+            raise format_error(f"{path}: truncated in {what} (needs {nbytes} bytes at offset {at}, the file has {len(buf)})")
+        at += nbytes
+        return buf[at - nbytes:at]
+
+    def u32(what: str, count: int = 1):
+        return [int(x) for x in np.frombuffer(take(4 * count, what), dtype="<u4")]
+
+    if take(8, "the magic") != CHECKPOINT_MAGIC:
+        raise format_error(f"{path}: not a checkpoint file (wrong magic)")
+    version, = u32("the version")
+    if version != CHECKPOINT_VERSION:
+        raise format_error(f"{path}: checkpoint version {version} is not supported (this reader knows {CHECKPOINT_VERSION})")
+    L, = u32("the layer count")
+    if L < 2 or L > CHECKPOINT_MAX_LAYERS:
+        raise format_error(f"{path}: {L} sizes")
+    sizes = u32("the sizes", L)
+    if min(sizes) < 1:
+        raise format_error(f"{path}: a layer width of zero")
+    residual, norm_id, loss_id, optimizer = u32("the options", 4)
+    if residual > 1 or norm_id >= len(CHECKPOINT_NORMS) or loss_id >= len(CHECKPOINT_LOSSES) or optimizer > 1:
+        raise format_error(f"{path}: unknown option value ({residual}, {norm_id}, {loss_id}, {optimizer})")
+    p = float(np.frombuffer(take(8, "the dropout state"), dtype="<f8")[0])
+    seed, epoch, step = (int(x) for x in np.frombuffer(take(24, "the dropout state"), dtype="<u8"))
+    if not (0.0 <= p < 1.0):
+        raise format_error(f"{path}: dropout probability {p}")
+    if not optimizer and step:
+        raise format_error(f"{path}: a step count without an optimiser section")
+    norm = CHECKPOINT_NORMS[norm_id]
+    want = checkpoint_tensors(sizes, bool(residual), norm)
+    T, = u32("the tensor count")
+    if T != len(want):
+        raise format_error(f"{path}: {T} tensors, the configuration has {len(want)}")
+    tensors = {}
+    for name, shape in want:
+        k, = u32(f"the name of {name}")
+        if k != len(name) or take(k, f"the name of {name}") != name.encode("ascii"):
+            raise format_error(f"{path}: expected tensor {name}")
+        if tuple(u32(f"the shape of {name}", 2)) != shape:
+            raise format_error(f"{path}: tensor {name} is not {shape[0]} x {shape[1]}")
+        tensors[name] = np.frombuffer(take(4 * shape[0] * shape[1], name), dtype="<f4").reshape(shape).copy()
+    if optimizer:
+        for name, shape in want:
+            for k in ("m.", "v."):
+                tensors[k + name] = np.frombuffer(take(4 * shape[0] * shape[1], k + name), dtype="<f4").reshape(shape).copy()
+    if at != len(buf):
+        raise format_error(f"{path}: {len(buf) - at} trailing bytes")
+    config = {"sizes": sizes, "residual_layer": bool(residual), "norm": norm, "loss": CHECKPOINT_LOSSES[loss_id],
+              "dropout": (p, seed, epoch), "step": step, "optimizer": bool(optimizer)}
+    return config, tensors
+
+
+# ----------------------------------------------------------------------------
 # Synthetic inputs (SURVEY.md section 8(d)).  Deterministic, numpy only.
 # ----------------------------------------------------------------------------
 def synth_uniform_csr(n: int, deg: int, seed: int = 0):

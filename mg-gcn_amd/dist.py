@@ -44,6 +44,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib, ops
+from .checkpoint import checkpoint_option
 from .gcn import (_check_agg_dtype, adam_update_all, check_counts, check_loss, check_norm, check_sets, check_targets,
                   dropout_option, layer_body, layer_norm, linear, link_fused_backward, sigmoid_bce_loss,
                   softmax_cross_entropy_loss, split_counts)
@@ -971,7 +972,7 @@ def _repl_view(dn):
     return w
 
 
-class dist_gcn(dropout_option):
+class dist_gcn(dropout_option, checkpoint_option):
     """reference src/gcn.hpp:997-1056 (row_partition = true): per-GPU HW_buffer and two
     receive buffers shared by all layers (:1016-1021); layers get (A_T, A) (:1023).
 
@@ -981,7 +982,11 @@ class dist_gcn(dropout_option):
 
     ``norm="layer"``: see gcn.gcn.  Layer normalisation is row-local, so a rank normalises exactly its rows of the
     single-GPU run and the forward communicates nothing; gamma / beta are replicated, and their gradients ride on the
-    all-reduce of the same layer's G_W / G_b (all three schedules, both overlap settings)."""
+    all-reduce of the same layer's G_W / G_b (all three schedules, both overlap settings).
+
+    save(dctx, path, optimizer=True) / load(dctx, path) / predict(dctx, X): see checkpoint.checkpoint_option.  Every rank
+    calls them; rank 0 alone writes (the replicas are bitwise equal), every rank reads, predict returns the rank's rows.
+    The file is the single-GPU model's: it loads at any P and into either class."""
 
     def __init__(self, dctx: dist_context, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix,
                  sizes: Sequence[int], residual_layer: bool = False, fused: bool = True, mode: str = "allgather",
@@ -990,6 +995,7 @@ class dist_gcn(dropout_option):
         self.norm = check_norm(norm)
         self.loss = check_loss(loss)
         self._out_width = int(sizes[-1])
+        self.sizes, self.residual_layer = [int(s) for s in sizes], bool(residual_layer)      # the checkpoint's configuration
         self.agg_dtype = _check_agg_dtype(agg_dtype)
         torch = _torch()
         P, dev = dctx.P, dctx.ctx.device

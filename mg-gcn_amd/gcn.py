@@ -33,6 +33,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import ops
+from .checkpoint import checkpoint_option
 from .matrix import context, csr_matrix, dn_matrix, host_scalars
 
 MGGCN_SPMM_LEAKY_RELU = 1
@@ -914,7 +915,7 @@ def adam_update_all(ctx: context, lins, state, lr: float, beta1: float, beta2: f
     return state
 
 
-class gcn(dropout_option):
+class gcn(dropout_option, checkpoint_option):
     """reference src/gcn.hpp:937-995.  The constructor column-normalises A, builds
     A_T and hands (A_T, A) to the layers -- forward multiplies by A_T (:946-955).
 
@@ -923,7 +924,10 @@ class gcn(dropout_option):
 
     ``norm="layer"``: every layer but the last normalises its rows between aggregation / linear and activation (see
     layer_norm; ``layer.norm.gamma`` / ``.beta``, ``layer.norm.init(gamma, beta)``).  It has no training mode: a plain
-    call and evaluate() run the same kernels.  None (the default) launches nothing new."""
+    call and evaluate() run the same kernels.  None (the default) launches nothing new.
+
+    save(ctx, path, optimizer=True) / load(ctx, path) / predict(ctx, X): see checkpoint.checkpoint_option -- the file
+    carries the configuration, the parameters, Adam's state and the dropout state, and no execution option."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], residual_layer: bool = False,
                  weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None, fused: bool = True,
@@ -933,6 +937,7 @@ class gcn(dropout_option):
         self.norm = check_norm(norm)
         self.loss = check_loss(loss)
         self._out_width = int(sizes[-1])
+        self.sizes, self.residual_layer = [int(s) for s in sizes], bool(residual_layer)      # the checkpoint's configuration
         torch = _torch()
         self.agg_dtype = _check_agg_dtype(agg_dtype)
         if self.agg_dtype != "f32" and hoist_first_aggregation:

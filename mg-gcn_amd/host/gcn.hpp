@@ -19,6 +19,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "checkpoint.hpp"
 #include "dist_matrix.hpp"
 #include "matrix.hpp"
 #include "ops.hpp"
@@ -260,7 +261,75 @@ public:
     auto get_W() { return W; }
     auto get_G_W() { return G_W; }
     auto get_G_b() { return G_b; }
+    // checkpoints (gcn::save / load): Adam's moments (after adam_state) and the step count
+    auto get_mW() { return mW; }
+    auto get_vW() { return vW; }
+    auto get_mb() { return mb; }
+    auto get_vb() { return vb; }
+    bool has_adam_state() const { return has_moments; }
+    std::size_t adam_steps() const { return has_moments ? step : 0; }
+    void set_adam_steps(std::size_t s) { step = s; }
 };
+
+// Checkpoints, shared by gcn and dist_gcn (checkpoint.hpp has the file; INTEGRATION.md its layout).  A tensor of the
+// model as the file sees it: the parameter and its two moments as one device matrix per replica (one on a single GPU).
+template <typename r_t>
+struct checkpoint_slot {
+    std::string name;
+    std::vector<dn_matrix<r_t>> p, m, v;      // m, v: empty handles while the model has not stepped
+};
+
+// the slots of one layer in file order: W, b, the residual linear's, the norm's
+template <typename r_t, typename layer_t, typename pick_t>
+void checkpoint_slots_of(layer_t &layer, std::size_t l, pick_t &&pick, std::vector<checkpoint_slot<r_t>> &out) {
+    const auto s = std::to_string(l);
+    const auto lins = layer.linears();
+    for (std::size_t k = 0; k < lins.size(); k++) {
+        const std::string pre = k ? "res_" : "";
+        out.push_back({pre + "W" + s, pick(lins[k]->get_W()), pick(lins[k]->get_mW()), pick(lins[k]->get_vW())});
+        out.push_back({pre + "b" + s, pick(lins[k]->get_b()), pick(lins[k]->get_mb()), pick(lins[k]->get_vb())});
+    }
+    if (auto *nm = layer.layer_norm_params()) {
+        out.push_back({"gamma" + s, {nm->gamma}, {nm->mg}, {nm->vg}});
+        out.push_back({"beta" + s, {nm->beta}, {nm->mb}, {nm->vb}});
+    }
+}
+
+// host copy of the slots into a checkpoint whose configuration is already filled in; replica 0 is read.  `set(g)` makes
+// replica g's device current.  The caller has synchronised.
+template <typename r_t, typename set_t>
+void checkpoint_download(mggcn::checkpoint &c, const std::vector<checkpoint_slot<r_t>> &slots, bool stepped, set_t &&set) {
+    set(0);
+    for (const auto &sl : slots) {
+        mggcn::checkpoint_tensor t;
+        t.name = sl.name, t.rows = (std::uint32_t)sl.p[0].n(), t.cols = (std::uint32_t)sl.p[0].m();
+        t.data = sl.p[0].to_host();
+        if (c.optimizer) {
+            t.m = stepped ? sl.m[0].to_host() : std::vector<r_t>(t.size(), (r_t)0);
+            t.v = stepped ? sl.v[0].to_host() : std::vector<r_t>(t.size(), (r_t)0);
+        }
+        c.tensors.push_back(std::move(t));
+    }
+}
+
+// the file's tensors into every replica, in place (dn_matrix::init): the buffers keep their addresses, which the cached
+// Adam tables hold.  A file without the optimiser section zeroes the moments.  The caller has synchronised and has run
+// adam_state, so the moments exist.
+template <typename r_t, typename set_t>
+void checkpoint_upload(const mggcn::checkpoint &c, std::vector<checkpoint_slot<r_t>> &slots, set_t &&set) {
+    mggcn_require(slots.size() == c.tensors.size(), "checkpoint: tensor count");
+    for (std::size_t k = 0; k < slots.size(); k++) {
+        const auto &t = c.tensors[k];
+        auto &sl = slots[k];
+        mggcn_require(t.name == sl.name && t.rows == sl.p[0].n() && t.cols == sl.p[0].m(), "checkpoint: tensor name or shape");
+        for (std::size_t g = 0; g < sl.p.size(); g++) {
+            set(g);
+            sl.p[g].init(t.data);
+            sl.m[g].init(c.optimizer ? t.m : std::vector<r_t>(t.size(), (r_t)0));
+            sl.v[g].init(c.optimizer ? t.v : std::vector<r_t>(t.size(), (r_t)0));
+        }
+    }
+}
 
 template <typename r_t>
 class linear : public linear_body<r_t, context, dn_matrix, dn_matrix> {
@@ -942,6 +1011,8 @@ public:
     gcn(csr_matrix<x_t, v_t, r_t> A, std::vector<std::size_t> sizes, bool residual_layer = false, bool fused = true,
         agg_dtype agg = agg_dtype::f32)
         : loss_layer(std::to_string(sizes.size() - 1) + "_", residual_layer, fused), agg_(agg) {
+        for (auto s : sizes) sizes_.push_back((std::uint32_t)s);
+        residual_ = residual_layer;
         A.normalize(true);
         auto A_T = A.transpose();
         std::size_t max_d = 0;
@@ -997,11 +1068,13 @@ public:
     // mask of mggcn_dropout_f32 for (seed, stream = epoch * 64 + layer), never stored: backward() regenerates it.  epoch
     // counts the train_forward calls since set_dropout.  p = 0 switches it off (nothing is launched);
     // std::invalid_argument for a p outside [0, 1) or more than 64 layers, before any device work.
-    void set_dropout(double p, std::uint64_t seed = 0) {
+    // epoch: the number the next training forward gets (a loaded checkpoint continues its run's count)
+    void set_dropout(double p, std::uint64_t seed = 0, std::size_t epoch = 0) {
         const auto d = dropout_params(p, seed);
         mggcn_require(p == 0.0 || layers_.size() <= 64, "dropout supports at most 64 layers");
         dropout_ = p > 0.0 ? std::make_optional(d) : std::nullopt;
-        dropout_epoch_ = 0;
+        dropout_p_ = p, dropout_seed_ = seed;
+        dropout_epoch_ = epoch;
     }
     std::size_t dropout_epoch() const { return dropout_epoch_; }
     // Layer normalisation (opt-in; the reference has none): every layer but the last normalises its rows between
@@ -1055,7 +1128,64 @@ public:
     }
     auto &layers() { return layers_; }
 
+    // Checkpoints (opt-in; the reference writes nothing): the file of checkpoint.hpp -- configuration, every parameter,
+    // Adam's moments and step count (optimizer), the dropout state (p, seed, next epoch).  Execution options (fused, the
+    // aggregation dtype, hoisting) are not stored.  state() is the host copy that save() writes.
+    mggcn::checkpoint state(const context ctx, bool optimizer = true) {
+        ctx.sync();
+        auto c = describe();
+        c.optimizer = optimizer;
+        c.step = optimizer ? adam_steps() : 0;
+        checkpoint_download(c, slots(), layers_.front().linear_layer().has_adam_state(), [&](std::size_t) { ctx.set(); });
+        return c;
+    }
+    void save(const context ctx, const std::string &path, bool optimizer = true) { state(ctx, optimizer).write(path); }
+    // Compares the file's configuration with the model's first: mggcn::checkpoint_error naming the first difference
+    // ("sizes: file [..], model [..]") before a single device write.  Then parameters and moments are written in place,
+    // every step count is restored (a file without the optimiser section resets Adam: zero moments, step 0) and
+    // set_dropout gets the file's (p, seed, epoch).
+    void load(const context ctx, const std::string &path) { load_state(ctx, mggcn::checkpoint::read(path), path); }
+    void load_state(const context ctx, const mggcn::checkpoint &c, const std::string &path = "checkpoint") {
+        const auto mine = describe();
+        const auto bad = c.mismatch(mine.sizes, mine.residual_layer, mine.norm, mine.loss);
+        if (!bad.empty()) throw mggcn::checkpoint_error(path + ": " + bad);
+        set_dropout(c.dropout_p, c.dropout_seed, (std::size_t)c.dropout_epoch);
+        for (auto &l : layers_) {
+            for (auto *lin : l.linears()) lin->adam_state(ctx);
+            if (auto *nm = l.layer_norm_params()) nm->adam_state(ctx);
+        }
+        ctx.sync();
+        auto sl = slots();
+        checkpoint_upload(c, sl, [&](std::size_t) { ctx.set(); });
+        for (auto &l : layers_) {
+            for (auto *lin : l.linears()) lin->set_adam_steps((std::size_t)c.step);
+            if (auto *nm = l.layer_norm_params()) nm->step = (std::size_t)c.step;
+        }
+        ctx.sync();
+    }
+    // Adam steps taken so far (a loaded checkpoint's count included)
+    std::size_t adam_steps() { return layers_.front().linear_layer().adam_steps(); }
+
 private:
+    mggcn::checkpoint describe() {
+        mggcn::checkpoint c;
+        c.sizes = sizes_, c.residual_layer = residual_;
+        for (auto &l : layers_) if (l.layer_norm_params()) c.norm = 1;
+        c.loss = loss_layer.loss_bce() ? 1 : 0;
+        c.dropout_p = dropout_ ? dropout_p_ : 0.0, c.dropout_seed = dropout_seed_, c.dropout_epoch = dropout_epoch_;
+        return c;
+    }
+    std::vector<checkpoint_slot<r_t>> slots() {
+        std::vector<checkpoint_slot<r_t>> out;
+        auto one = [](dn_matrix<r_t> t) { return std::vector<dn_matrix<r_t>>{t}; };
+        for (std::size_t l = 0; l < layers_.size(); l++) checkpoint_slots_of<r_t>(layers_[l], l, one, out);
+        return out;
+    }
+    std::vector<std::uint32_t> sizes_;
+    bool residual_ = false;
+    double dropout_p_ = 0;
+    std::uint64_t dropout_seed_ = 0;
+
     auto forward(const context ctx, dn_matrix<r_t> H) {
         for (auto &layer : layers_) H = layer(ctx, H);
         return H;
@@ -1094,6 +1224,8 @@ public:
     dist_gcn(const dist_context ctx, csr_t A, csr_t A_T, std::vector<std::size_t> sizes, bool residual_layer = false,
              bool fused = true, dist_mode mode = dist_mode::allgather)
         : loss_layer(std::to_string(sizes.size() - 1) + "_", residual_layer, fused) {
+        for (auto s : sizes) sizes_.push_back((std::uint32_t)s);
+        residual_ = residual_layer;
         std::size_t max_d = 0;
         for (std::size_t i = 0; i + 1 < sizes.size(); i++) max_d = std::max(max_d, std::min(sizes[i], sizes[i + 1]));
         const std::size_t nmax = std::max(A.n(), A.m()), shard = nmax * max_d / ctx.size();
@@ -1156,7 +1288,53 @@ public:
     }
     auto &layers() { return layers_; }
 
+    // Checkpoints: see gcn::save / load -- the same file, so a checkpoint of the single-GPU model loads here at any P and
+    // the other way round.  GPU 0's replica is written (the replicas are bitwise equal); a load initialises every
+    // replica.  These classes have no layer norm, multi-label loss or dropout: a file that has one is refused.
+    mggcn::checkpoint state(const dist_context ctx, bool optimizer = true) {
+        ctx.sync();
+        auto c = describe();
+        c.optimizer = optimizer;
+        c.step = optimizer ? adam_steps() : 0;
+        checkpoint_download(c, slots(ctx), layers_.front().linear_layer().has_adam_state(), [&](std::size_t g) { ctx[g].set(); });
+        return c;
+    }
+    void save(const dist_context ctx, const std::string &path, bool optimizer = true) { state(ctx, optimizer).write(path); }
+    void load(const dist_context ctx, const std::string &path) { load_state(ctx, mggcn::checkpoint::read(path), path); }
+    void load_state(const dist_context ctx, const mggcn::checkpoint &c, const std::string &path = "checkpoint") {
+        const auto mine = describe();
+        const auto bad = c.mismatch(mine.sizes, mine.residual_layer, mine.norm, mine.loss);
+        if (!bad.empty()) throw mggcn::checkpoint_error(path + ": " + bad);
+        if (c.dropout_p > 0.0) throw mggcn::checkpoint_error(path + ": dropout: file " + std::to_string(c.dropout_p) + ", and dropout is single-GPU only in the C++ layer");
+        for (auto &l : layers_)
+            for (auto *lin : l.linears()) lin->adam_state(ctx);
+        ctx.sync();
+        auto sl = slots(ctx);
+        checkpoint_upload(c, sl, [&](std::size_t g) { ctx[g].set(); });
+        for (auto &l : layers_)
+            for (auto *lin : l.linears()) lin->set_adam_steps((std::size_t)c.step);
+        ctx.sync();
+    }
+    std::size_t adam_steps() { return layers_.front().linear_layer().adam_steps(); }
+
 private:
+    mggcn::checkpoint describe() const {
+        mggcn::checkpoint c;
+        c.sizes = sizes_, c.residual_layer = residual_;
+        return c;
+    }
+    std::vector<checkpoint_slot<r_t>> slots(const dist_context &ctx) {
+        std::vector<checkpoint_slot<r_t>> out;
+        auto all = [&ctx](repl_dn_matrix<r_t> t) {
+            std::vector<dn_matrix<r_t>> v;
+            for (std::size_t g = 0; g < ctx.size() && g < t.size(); g++) v.push_back(t[g]);
+            return v;
+        };
+        for (std::size_t l = 0; l < layers_.size(); l++) checkpoint_slots_of<r_t>(layers_[l], l, all, out);
+        return out;
+    }
+    std::vector<std::uint32_t> sizes_;
+    bool residual_ = false;
     bool fused_ = true;
     std::vector<std::shared_ptr<adam_table<r_t>>> adam_;     // one per GPU, shared with the commands in flight
     r_t adam_wd_ = 0;

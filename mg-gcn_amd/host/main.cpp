@@ -25,6 +25,19 @@
 // multi-label model: labels.bin is the n x C target matrix (non-zero = positive), "num_labels = " prints C, the loss is
 // sigmoid + binary cross-entropy and the accuracy column of the epoch line and of "[mggcn splits]" holds micro-F1;
 // MGGCN_TIMING=1 prints the start-up stages.
+// Checkpoints and model selection (all opt-in; with every variable unset nothing changes): MGGCN_LOAD=<file> starts from a
+// checkpoint (checkpoint.hpp; the epoch column, the timer prefixes and the dropout epoch continue from its step count, and
+// the file's dropout state replaces MGGCN_DROPOUT's); MGGCN_SAVE=<file> writes the full state after the last epoch that ran;
+// MGGCN_SAVE_BEST=<file> (needs MGGCN_TRAIN_SET) keeps the parameters of the best validation epoch, by MGGCN_SELECT=loss
+// (default) or score, one "[mggcn best] <epoch> <val loss> <val score>" line per improving epoch; MGGCN_PATIENCE=<k> (needs
+// MGGCN_TRAIN_SET) stops after k epochs without improvement.  The monitored number is the training forward's own, which
+// describes the parameters the epoch STARTED from: those are what is kept.
+//
+//   mg_gcn -P 1 predict <dir> <k> <h1> ... <hk>
+//
+// builds the model, loads MGGCN_LOAD, runs one plain forward, writes the int32 predictions ([n x 1] argmax, or [n x C] 0 / 1
+// with MGGCN_LOSS=bce) as a dense .bin to MGGCN_PREDICTIONS (default predictions.bin) and prints
+// "[mggcn predict] all <score> train <score> val <score> test <score>" from labels.bin and sets.bin.
 #include <unistd.h>
 
 #include <chrono>
@@ -48,7 +61,7 @@ public:
 };
 
 static int usage_(char *prog) {
-    std::cout << "Usage: " << prog << " [-h] [-P gpus] [-R 0/1] [-E epochs] [-S x] [-N] train <dir> <k> <h1..hk>" << std::endl;
+    std::cout << "Usage: " << prog << " [-h] [-P gpus] [-R 0/1] [-E epochs] [-S x] [-N] train|predict <dir> <k> <h1..hk>" << std::endl;
     return 0;
 }
 
@@ -67,8 +80,15 @@ static int help_() {
                  "    MGGCN_LAYER_NORM=1    : layer normalisation before the activation of every layer but the last (single GPU)\n"
                  "    MGGCN_LOSS=softmax|bce: bce = multi-label training (single GPU): labels.bin is an n x C 0/1 matrix, the\n"
                  "                            loss sigmoid + binary cross-entropy, the reported score micro-F1\n"
+                 "    MGGCN_LOAD=<file>     : start from a checkpoint; epochs and dropout masks continue from its step count\n"
+                 "    MGGCN_SAVE=<file>     : write the full state (with Adam's) after the last epoch that ran\n"
+                 "    MGGCN_SAVE_BEST=<file>: keep the best validation epoch's parameters (needs MGGCN_TRAIN_SET);\n"
+                 "                            MGGCN_SELECT=loss|score picks the monitored number (default loss)\n"
+                 "    MGGCN_PATIENCE=<k>    : stop after k epochs without improvement (needs MGGCN_TRAIN_SET)\n"
+                 "    MGGCN_PREDICTIONS=<f> : where predict writes (default predictions.bin)\n"
                  "Arguments:\n"
-                 "    train <dir> <k> <h1> ... <hk> : dataset directory, number of hidden layers and their widths\n";
+                 "    train <dir> <k> <h1> ... <hk> : dataset directory, number of hidden layers and their widths\n"
+                 "    predict <dir> <k> <h1> ... <hk> : load MGGCN_LOAD, one plain forward, predictions as a dense .bin (-P 1)\n";
     return EXIT_SUCCESS;
 }
 
@@ -121,6 +141,58 @@ static std::uint64_t env_u64(const char *name, const std::string &v) {
     try { x = std::stoull(v, &used, 0); } catch (const std::exception &) { used = 0; }
     if (v.empty() || v[0] == '-' || used != v.size()) throw arg_error(std::string(name) + " must be an unsigned 64-bit integer, not '" + v + "'");
     return (std::uint64_t)x;
+}
+
+// a path from the environment: unset is empty, set must not be empty
+static std::string env_path(const char *name) {
+    const char *s = std::getenv(name);
+    if (s && !*s) throw arg_error(std::string(name) + " must name a file, not ''");
+    return s ? s : "";
+}
+
+// `mg_gcn predict`: one plain forward of the loaded model; the predictions as a dense int32 .bin and one score line --
+// accuracy, or micro-F1 with MGGCN_LOSS=bce -- over all vertices and per split (nan for an empty split)
+template <typename model_t>
+static void run_predict(context ctx, model_t &G, dn_matrix<r_t> X, const dn_matrix<std::int32_t> &Y, const dn_matrix<std::int32_t> &S,
+                        bool bce, const std::string &out_path) {
+    auto H = G(ctx, X);
+    const std::size_t n = H.n(), C = H.m(), cols = bce ? C : 1;
+    std::vector<std::int32_t> pred;
+    if (bce) {
+        const auto logits = H.to_host();
+        pred.resize(logits.size());
+        for (std::size_t i = 0; i < logits.size(); i++) pred[i] = logits[i] > 0 ? 1 : 0;
+    } else {
+        dn_matrix<std::int32_t> P(n, 1);
+        max_row_indices(ctx, H, P);          // the first maximum wins
+        ctx.sync();
+        pred = P.to_host();
+    }
+    {
+        std::ofstream out(out_path, std::ios::binary);
+        const std::uint32_t shape[2] = {(std::uint32_t)n, (std::uint32_t)cols};
+        out.write(reinterpret_cast<const char *>(shape), sizeof shape);
+        out.write(reinterpret_cast<const char *>(pred.data()), (std::streamsize)(pred.size() * sizeof(std::int32_t)));
+        out.close();
+        if (!out) throw std::runtime_error(out_path + ": cannot write");
+    }
+    const auto y = Y.to_host(), sets = S.to_host();
+    auto score = [&](int set) {              // set < 0: every vertex
+        double hit = 0, rows = 0, tp = 0, fp = 0, fn = 0;
+        for (std::size_t i = 0; i < n; i++) {
+            if (set >= 0 && sets[i] != set) continue;
+            rows += 1;
+            if (!bce) { hit += pred[i] == y[i]; continue; }
+            for (std::size_t c = 0; c < C; c++) {
+                const bool p = pred[i * C + c] != 0, t = y[i * C + c] != 0;
+                tp += p && t, fp += p && !t, fn += !p && t;
+            }
+        }
+        const double nan = std::numeric_limits<double>::quiet_NaN();
+        if (bce) return 2 * tp + fp + fn > 0 ? 2 * tp / (2 * tp + fp + fn) : nan;
+        return rows > 0 ? hit / rows : nan;
+    };
+    std::cerr << "[mggcn predict] all " << score(-1) << " train " << score(0) << " val " << score(1) << " test " << score(2) << std::endl;
 }
 
 int main_(int argc, char **argv) {
@@ -180,11 +252,36 @@ int main_(int argc, char **argv) {
         if (loss_bce && (P > 1 || row_partition))                   // the distributed classes have no multi-label loss
             throw arg_error("MGGCN_LOSS=bce is single-GPU only (not with -P > 1 or -R 1)");
     }
+    // checkpoints and model selection: everything unset is today's run, line for line
+    const std::string load_path = env_path("MGGCN_LOAD"), save_path = env_path("MGGCN_SAVE"), best_path = env_path("MGGCN_SAVE_BEST");
+    const std::string pred_env = env_path("MGGCN_PREDICTIONS");
+    mggcn::model_selection selection;
+    if (const char *sl = std::getenv("MGGCN_SELECT")) {
+        const std::string v = sl;
+        if (v != "loss" && v != "score") throw arg_error("MGGCN_SELECT must be loss or score, not '" + v + "'");
+        selection.by_score = v == "score";
+        if (train_set < 0) throw arg_error("MGGCN_SELECT needs MGGCN_TRAIN_SET");
+    }
+    if (const char *pt = std::getenv("MGGCN_PATIENCE")) {
+        const std::string v = pt;
+        std::size_t used = 0;
+        unsigned long long k = 0;
+        try { k = std::stoull(v, &used, 10); } catch (const std::exception &) { used = 0; }
+        if (v.empty() || v[0] == '-' || v[0] == '+' || used != v.size() || k == 0)
+            throw arg_error("MGGCN_PATIENCE must be a positive integer, not '" + v + "'");
+        selection.patience = (std::size_t)k;
+        if (train_set < 0) throw arg_error("MGGCN_PATIENCE needs MGGCN_TRAIN_SET");
+    }
+    if (!best_path.empty() && train_set < 0) throw arg_error("MGGCN_SAVE_BEST needs MGGCN_TRAIN_SET");
+    const bool selecting = !best_path.empty() || selection.patience > 0;
 
     while (optind < argc && argv[optind] != nullptr) {
         const std::string command = argv[optind++];
-        if (command.rfind("train", 0) != 0) throw arg_error("Unknown command.");
-        if (optind >= argc) throw arg_error("train needs a dataset directory.");
+        const bool predicting = command == "predict";
+        if (!predicting && command.rfind("train", 0) != 0) throw arg_error("Unknown command.");
+        if (predicting && load_path.empty()) throw arg_error("predict needs MGGCN_LOAD");
+        if (predicting && (P > 1 || row_partition)) throw arg_error("predict is single-GPU only (not with -P > 1 or -R 1)");
+        if (optind >= argc) throw arg_error(command + " needs a dataset directory.");
         const std::filesystem::path dir = argv[optind++];
         if ((int)mggcn_device_count() < (int)std::max<std::size_t>(P, 1) && !(oversubscribe && mggcn_device_count() > 0))
             throw arg_error("not enough GPUs visible for -P");
@@ -223,8 +320,12 @@ int main_(int argc, char **argv) {
             else if (!part.empty() && part != "/" && part != ".") filename = (permuted ? std::string("permuted_") : std::string("")) + part.string();
         }
         for (auto s : sizes) filename += "_" + std::to_string(s);
-        std::filesystem::create_directories("csvs");
-        std::ofstream of("csvs/" + filename + "_" + std::to_string(P) + ".csv");
+        std::ofstream of;                                            // predict times nothing
+        if (!predicting) {
+            std::filesystem::create_directories("csvs");
+            of.open("csvs/" + filename + "_" + std::to_string(P) + ".csv");
+        }
+        mggcn::checkpoint candidate;                                 // selection: the parameters the running epoch started from
 
         if (P <= 1 && !row_partition) {
             auto ctx = context(0);
@@ -234,10 +335,19 @@ int main_(int argc, char **argv) {
             if (dropout_p > 0.0) G.set_dropout(dropout_p, dropout_seed);             // train_forward number e is dropout epoch e
             if (layer_norm_on) G.set_layer_norm(true);
             if (loss_bce) G.set_loss_bce();
+            std::size_t first_epoch = 0;
+            if (!load_path.empty()) {                                 // a configuration mismatch ends the run here
+                G.load(ctx, load_path);
+                first_epoch = G.adam_steps();
+            }
             ctx.sync();
             stage("model (normalize, transpose, layers)");
+            if (predicting) {
+                run_predict(ctx, G, X, Y, S, loss_bce, pred_env.empty() ? std::string("predictions.bin") : pred_env);
+                continue;
+            }
             ctx.record("training-start", 0);
-            for (std::size_t e = 0; e < num_epochs; e++) {
+            for (std::size_t e = first_epoch; e < first_epoch + num_epochs; e++) {
                 if (const char *dd = std::getenv("MGGCN_DUMP_WEIGHTS")) {
                     std::filesystem::create_directories(dd);
                     for (std::size_t l = 0; l < G.layers().size(); l++) {
@@ -249,6 +359,7 @@ int main_(int argc, char **argv) {
                         }
                     }
                 }
+                if (selecting) candidate = G.state(ctx, false);
                 const auto start = std::chrono::system_clock::now();
                 auto [loss, acc] = G.train_forward(ctx, X, Y);
                 G.backward(ctx);
@@ -257,9 +368,18 @@ int main_(int argc, char **argv) {
                 const auto duration = std::chrono::duration<double>{std::chrono::system_clock::now() - start}.count();
                 std::cerr << e << ' ' << loss << ' ' << acc << ' ' << duration << std::endl;
                 if (train_set >= 0) print_splits(e, G.split_metrics());
-                if (e == 0) stage("epoch 0 (SpMM plans built on first use)");
+                if (e == first_epoch) stage("epoch 0 (SpMM plans built on first use)");
                 ctx.dump_timers(of, std::to_string(e) + "_0_");
+                if (selecting) {
+                    const auto m = G.split_metrics();
+                    if (selection.step(e, m[1].first, m[1].second)) {
+                        std::cerr << "[mggcn best] " << e << ' ' << m[1].first << ' ' << m[1].second << std::endl;
+                        if (!best_path.empty()) candidate.write(best_path);
+                    }
+                    if (selection.stop) break;
+                }
             }
+            if (!save_path.empty()) G.save(ctx, save_path);
         } else if (row_partition) {
             sizes.back() = (sizes.back() + P - 1) / P * P;          // reference :135
             auto ctx = dist_context(P, overlap);
@@ -277,10 +397,15 @@ int main_(int argc, char **argv) {
             dist_gcn<true, x_t, v_t, r_t> G(ctx, Ad, A_Td, sizes, false, fused, mode);
             dist_row_dn_matrix<r_t> Xd(ctx, X);
             if (train_set >= 0) G.set_splits(ctx, dist_row_dn_matrix<std::int32_t>(ctx, S), train_set);
+            std::size_t first_epoch = 0;
+            if (!load_path.empty()) {                                 // every replica; a configuration mismatch ends the run here
+                G.load(ctx, load_path);
+                first_epoch = G.adam_steps();
+            }
             ctx.sync();
             stage("model + shards");
             ctx.record("training-start", 0);
-            for (std::size_t e = 0; e < num_epochs; e++) {
+            for (std::size_t e = first_epoch; e < first_epoch + num_epochs; e++) {
                 if (const char *dd = std::getenv("MGGCN_DUMP_WEIGHTS")) {     // GPU 0's replica: they are all the same
                     ctx.sync();
                     std::filesystem::create_directories(dd);
@@ -289,6 +414,7 @@ int main_(int argc, char **argv) {
                         dump_dense(std::filesystem::path(dd) / ("e" + std::to_string(e) + "_b" + std::to_string(l) + ".bin"), G.layers()[l].b()[0]);
                     }
                 }
+                if (selecting) candidate = G.state(ctx, false);       // GPU 0's replica
                 const auto start = std::chrono::system_clock::now();
                 const double waited = ctx.device_wait_seconds();
                 auto [loss, acc] = G.train_forward(ctx, Xd, Yd);
@@ -300,9 +426,18 @@ int main_(int argc, char **argv) {
                 if (train_set >= 0) print_splits(e, G.split_metrics());
                 // how much of the epoch the host needed to ISSUE it (wall time minus the time it sat waiting for the devices)
                 if (stage.on) std::cerr << "[mggcn timing] epoch " << e << " host-issue-ms " << (duration - (ctx.device_wait_seconds() - waited)) * 1e3 << std::endl;
-                if (e == 0) stage("epoch 0 (exchange forms + SpMM plans built on first use)");
+                if (e == first_epoch) stage("epoch 0 (exchange forms + SpMM plans built on first use)");
                 ctx.dump_timers(of, std::to_string(e) + "_");
+                if (selecting) {
+                    const auto m = G.split_metrics();
+                    if (selection.step(e, m[1].first, m[1].second)) {
+                        std::cerr << "[mggcn best] " << e << ' ' << m[1].first << ' ' << m[1].second << std::endl;
+                        if (!best_path.empty()) candidate.write(best_path);
+                    }
+                    if (selection.stop) break;
+                }
             }
+            if (!save_path.empty()) G.save(ctx, save_path);
         }
         // P > 1 without -R 1 trains nothing, exactly like the reference (:145, :171-189)
     }
