@@ -60,7 +60,7 @@ void mggcn_device_synchronize(void);
 mggcn_stream_t mggcn_stream_create(int high_priority);
 void mggcn_stream_destroy(mggcn_stream_t stream);
 /* Frees the per-(device, stream) reduction scratch that mggcn_abssum_f32 / the fused loss, and the partials that
- * mggcn_layer_norm_backward_f32, allocate on first use (synchronises that stream).  mggcn_stream_destroy calls it; a
+ * mggcn_layer_norm_backward_f32 and mggcn_gat_scores_backward_f32, allocate on first use (synchronises that stream).  mggcn_stream_destroy calls it; a
  * host layer that brings its own streams (e.g. torch's) calls it when it drops one. */
 void mggcn_stream_release_scratch(mggcn_stream_t stream);
 void mggcn_stream_synchronize(mggcn_stream_t stream);
@@ -330,6 +330,50 @@ void mggcn_layer_norm_forward_f32(mggcn_stream_t stream, const float *x, float *
 void mggcn_layer_norm_backward_f32(mggcn_stream_t stream, const float *G, const float *act, const float *xhat,
                                    const float *rstd, const float *gamma, float *G_in, float *G_gamma, float *G_beta,
                                    size_t n_rows, size_t m, uint32_t flags);
+/* Graph attention (GAT; opt-in, the reference has no attention layer).  F is a CSR PATTERN of n_rows destinations x n_cols
+ * sources (u32 indptr / indices on the device; there is no values array, and a duplicate (i, j) entry counts as two edges),
+ * K = heads, dh = width per head, 1 <= K <= MGGCN_GAT_MAX_HEADS and K * dh <= MGGCN_GAT_MAX_WIDTH; head k owns columns
+ * [k dh, (k + 1) dh) of every dense operand, att is [2 x K dh] contiguous (row 0: destination vector, row 1: source
+ * vector), and s_dst / s_src / lse / D / ds_dst / ds_src are contiguous [rows x K].  With x_ijk = s_dst[i, k] + s_src[j, k],
+ * e = x > 0 ? x : slope x and alpha_ijk = exp(e_ijk - lse[i, k]):
+ *   scores          s_dst[r, k] = sum_c Z[r, k dh + c] att[0, k dh + c];  s_src likewise with att[1]  (either may be NULL)
+ *   forward         lse[i, k] = log sum_j exp(e_ijk) (max-subtracted);  out[i, k dh + c] = sum_j alpha_ijk Z[j, k dh + c];
+ *                   a row without entries gets lse = 0 and an out row of +0.0 (written, not skipped)
+ *   backward_dst    over the rows of F:  D[i, k] = sum_c G[i, k dh + c] out[i, k dh + c];
+ *                   ds_dst[i, k] = sum_j ds_ijk,  ds_ijk = alpha_ijk (sum_c G[i, k dh + c] Z[j, k dh + c] - D[i, k]) (x_ijk > 0 ? 1 : slope)
+ *   backward_src    over the rows of F^T (n_rows sources x n_cols destinations; call it after backward_dst):
+ *                   ds_src[j, k] = sum_i ds_ijk;
+ *                   G_Z[j, k dh + c] = sum_i alpha_ijk G[i, k dh + c] + ds_dst[j, k] att[0, k dh + c] + ds_src[j, k] att[1, k dh + c]
+ *                   -- ds_dst here is indexed by SOURCE: the square case, where vertex j is destination j too, passes
+ *                   backward_dst's; NULL leaves that term out (a rectangular block whose destinations live elsewhere)
+ *   scores_backward G_att[0, c] = sum_i ds_dst[i, k(c)] Z_dst[i, c];  G_att[1, c] = sum_j ds_src[j, k(c)] Z_src[j, c]
+ *                   (n_dst / n_src rows; the square case passes the same Z twice).  n_dst == n_src == 0 writes zeros.
+ * Nothing of nnz x K is stored or read: alpha is recomputed from s_dst, s_src and lse where it is needed.  No atomics:
+ * sums over sources run over F's rows, sums over destinations over F^T's, and the column sums of G_att go through
+ * per-workgroup partials in the per-(device, stream) scratch of mggcn_layer_norm_backward_f32, added in a fixed order --
+ * two calls on the same input give the same bits in every output.  One wave per row in row order, no plan: correct for
+ * any input, slow on rows of many thousand entries.  16-byte loads when dh % 4 == 0 and every dense operand of the call
+ * is 16-byte aligned with a leading dimension that is a multiple of 4; single elements otherwise.  out must not alias Z;
+ * G_Z must not alias G or Z.  n_rows == 0 returns.  Leading dimensions are checked against K dh. */
+#define MGGCN_GAT_MAX_HEADS 16u
+#define MGGCN_GAT_MAX_WIDTH 1024u
+void mggcn_gat_scores_f32(mggcn_stream_t stream, const float *Z, size_t ldz, const float *att, float *s_dst, float *s_src,
+                          size_t n_rows, uint32_t K, uint32_t dh);
+void mggcn_gat_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                           const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
+                           uint32_t K, uint32_t dh, float slope, float *out, size_t ldo, float *lse);
+void mggcn_gat_backward_dst_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
+                                const float *lse, const float *G, size_t ldg, const float *out, size_t ldo, uint32_t K,
+                                uint32_t dh, float slope, float *D, float *ds_dst);
+void mggcn_gat_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
+                                const float *lse, const float *D, const float *G, size_t ldg, const float *att,
+                                const float *ds_dst, uint32_t K, uint32_t dh, float slope, float *ds_src, float *G_Z,
+                                size_t ldgz);
+void mggcn_gat_scores_backward_f32(mggcn_stream_t stream, const float *ds_dst, const float *Z_dst, size_t ldzd, size_t n_dst,
+                                   const float *ds_src, const float *Z_src, size_t ldzs, size_t n_src, uint32_t K, uint32_t dh,
+                                   float *G_att);
 /* cublasSasum   (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

@@ -10,6 +10,7 @@ Layout:
   matrix.py    context / csr_matrix / dn_matrix        (reference src/matrix.hpp)
   ops.py       matmul / get_matmul_buffer / kernels     (reference src/cuda_utils.hpp)
   gcn.py       sparse_linear / linear / gcn_layer / gcn (reference src/gcn.hpp)
+  gat.py       attention / gat_layer / gat: graph attention layers (no reference counterpart)
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*)
   datasets.py  on-disk format + synthetic generators    (reference test/data/prep.py); the checkpoint file
   checkpoint.py  save / load / predict of gcn and dist_gcn (no reference counterpart)
@@ -23,6 +24,7 @@ from . import ops                                               # noqa: F401
 from .ops import get_matmul_buffer, matmul                      # noqa: F401
 from .gcn import (gcn, gcn_layer, linear, softmax, softmax_cross_entropy_loss,  # noqa: F401
                   sparse_linear)
+from .gat import attention, gat, gat_layer                      # noqa: F401
 
 from . import dist                                              # noqa: F401
 from .dist import (dist_context, dist_gcn, dist_gcn_layer, dist_row_csr_matrix,  # noqa: F401
@@ -33,4 +35,4 @@ from .selection import model_selector                           # noqa: F401
 
 __all__ = ["context", "csr_matrix", "dn_matrix", "matrix_error", "engine_error", "ops", "matmul",
            "get_matmul_buffer", "sparse_linear", "linear", "gcn_layer", "softmax",
-           "softmax_cross_entropy_loss", "gcn", "datasets", "model_selector"]
+           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "datasets", "model_selector"]

@@ -17,6 +17,7 @@
 #include <utility>
 
 #include "common.h"
+#include "scratch_internal.h"
 
 namespace {
 
@@ -1096,6 +1097,10 @@ unsigned layer_norm_grid(size_t n_rows) {
     } while (0)
 
 }  // namespace
+
+// scratch_internal.h: the same per-(device, stream) partials for the column sums of gat.hip (stream order keeps the users
+// apart; released with the layer norm's by mggcn_stream_release_scratch)
+float *colsum_scratch(hipStream_t st, size_t floats) { return layer_norm_scratch(st, floats); }
 
 // ============================ C ABI =========================================
 MGGCN_API void mggcn_leaky_relu_forward_f32(mggcn_stream_t stream, const float *in, float *out,

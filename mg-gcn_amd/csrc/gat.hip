@@ -1,0 +1,566 @@
+// gat.hip -- graph attention (GAT) on gfx950: attention scores, the edge-softmax fused with the gather, and the
+// backward pass (per-edge dot products + weighted transposed gather + the column sums behind G_att).
+//
+// Layout of the three sparse kernels: the row-split form of spmm.hip without a plan -- one wave per CSR row, the row's
+// entries in 64-entry chunks, software-pipelined.  The heads of a row are walked one after the
+// other.  Within a head the wave is cut into G = 64 / LPR groups of LPR lanes (LPR: the power of two that covers one
+// head's dh columns, 64 at the most): a group holds one head-row of a dense operand, VEC columns per lane and NT column
+// tiles when dh > LPR * VEC, so one wave-instruction gathers the head-rows of G neighbours.
+//   * per chunk, lane l owns entry l: it loads the index (two chunks ahead) and the [rows x K] scalars of that entry
+//     (scores, lse, D; one chunk ahead) and evaluates exp ONCE per (entry, head); the groups pick index and weight up
+//     through ds_bpermute (__shfl);
+//   * the forward makes ONE pass over a row: a running maximum, the sum and the accumulators rescaled chunk by chunk;
+//   * the per-edge dot product (SDDMM) is a butterfly over the LPR lanes of a group -- log2(LPR) steps per G edges;
+//   * the sums over a row's entries fold the G groups in a fixed order at the end: no atomics anywhere, the same bits on
+//     every call.
+// No per-edge array exists: alpha is recomputed from s_dst, s_src and lse wherever it is needed.
+// VEC = 4 (16-byte loads) when dh % 4 == 0 and every dense operand and leading dimension is 16-byte aligned -- a float4
+// must not straddle two heads, so K * dh % 4 == 0 alone is not enough -- and VEC = 1 otherwise.
+// Heavy rows are slow here (one wave walks a whole row, ~21 k entries on the Reddit-shaped graph) but correct: cutting
+// them with a fixed-order combine is what the SpMM's plan does and is left to a plan for these kernels.
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+#include "scratch_internal.h"
+
+namespace {
+
+constexpr unsigned kGatColsumBlocks = kNumCU * 2;      // grid cap of the G_att partial pass = rows of partials in the scratch
+
+__device__ __forceinline__ float wave_sum(float v) {   // xor butterfly: every lane ends with the same bits
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+    return v;
+}
+// sum over the lanes of a group (offsets below lpr) / over the groups (offsets from lpr up)
+__device__ __forceinline__ float group_sum(float v, uint32_t lpr) {
+    for (uint32_t off = 1; off < lpr; off <<= 1) v += __shfl_xor(v, off);
+    return v;
+}
+__device__ __forceinline__ float fold_groups(float v, uint32_t lpr) {
+    for (uint32_t off = lpr; off < 64; off <<= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ float gat_lrelu(float x, float slope) { return x > 0.f ? x : slope * x; }
+
+template <int VEC>
+__device__ __forceinline__ void loadv(float (&r)[VEC], const float *p) {
+    if constexpr (VEC == 4) {
+        const float4 t = *reinterpret_cast<const float4 *>(p);
+        r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w;
+    } else {
+        r[0] = *p;
+    }
+}
+template <int VEC>
+__device__ __forceinline__ void storev(float *p, const float (&r)[VEC]) {
+    if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    else *p = r[0];
+}
+template <int VEC>
+__device__ __forceinline__ void zerov(float (&r)[VEC]) {
+#pragma unroll
+    for (int v = 0; v < VEC; v++) r[v] = 0.f;
+}
+
+// the head-row of `row` (NT tiles of VEC columns per lane), zeros beyond dh
+template <int VEC, int NT>
+__device__ __forceinline__ void load_head_row(float (&r)[NT][VEC], const float *p, uint32_t lpr, uint32_t sub, uint32_t dh,
+                                              bool on = true) {
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+        const uint32_t col = (t * lpr + sub) * VEC;
+        if (on && col < dh) loadv<VEC>(r[t], p + col);
+        else zerov<VEC>(r[t]);
+    }
+}
+template <int VEC, int NT>
+__device__ __forceinline__ float dot_head_row(const float (&a)[NT][VEC], const float (&b)[NT][VEC]) {
+    float p = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int v = 0; v < VEC; v++) p = fmaf(a[t][v], b[t][v], p);
+    return p;
+}
+
+#define MGGCN_GAT_WAVE_ROW(n_rows)                                                                            \
+    const uint32_t lane = threadIdx.x & 63;                                                                   \
+    const uint32_t lpr = 1u << lg, n_grp = 64u >> lg, sub = lane & (lpr - 1), grp = lane >> lg;               \
+    const size_t row = (size_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);             \
+    if (row >= (n_rows)) return
+
+// ---------------------------------------------------------------------------
+// s_dst[r, k] = Z[r, head k] . att[0, head k],  s_src[r, k] = Z[r, head k] . att[1, head k]
+// one wave per row, G heads at a time (one per group)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gat_scores_kernel(const float *__restrict__ Z, size_t ldz, const float *__restrict__ att,
+                                                         float *__restrict__ s_dst, float *__restrict__ s_src, size_t n_rows,
+                                                         uint32_t K, uint32_t dh, uint32_t lg) {
+    MGGCN_GAT_WAVE_ROW(n_rows);
+    const float *__restrict__ z = Z + row * ldz;
+    const uint32_t width = K * dh;
+    for (uint32_t k0 = 0; k0 < K; k0 += n_grp) {
+        const uint32_t k = k0 + grp;
+        float pd = 0.f, ps = 0.f;
+        if (k < K)
+            for (uint32_t c = sub; c < dh; c += lpr) {
+                const float v = z[k * dh + c];
+                pd = fmaf(v, att[k * dh + c], pd);
+                ps = fmaf(v, att[width + k * dh + c], ps);
+            }
+        pd = group_sum(pd, lpr);
+        ps = group_sum(ps, lpr);
+        if (k < K && sub == 0) {
+            if (s_dst) s_dst[row * K + k] = pd;
+            if (s_src) s_src[row * K + k] = ps;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// forward: lse[i, k] and out[i, head k] = sum_j alpha_ijk Z[j, head k] over the entries j of row i
+// ---------------------------------------------------------------------------
+template <int VEC, int NT, int U>
+__global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                          const uint32_t *__restrict__ indices, const float *__restrict__ Z,
+                                                          size_t ldz, const float *__restrict__ s_dst,
+                                                          const float *__restrict__ s_src, uint32_t K, uint32_t dh, float slope,
+                                                          uint32_t lg, float *__restrict__ out, size_t ldo,
+                                                          float *__restrict__ lse) {
+    MGGCN_GAT_WAVE_ROW(n_rows);
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    for (uint32_t k = 0; k < K; k++) {
+        const float sd = s_dst[row * K + k];
+        const float *__restrict__ Zk = Z + (size_t)k * dh;
+        // One pass over the row with a running maximum (the softmax of flash attention): per chunk, lane l owns entry l,
+        // m <- max(m, the chunk's scores), the sum and the accumulators are rescaled by exp(m_old - m_new), and the chunk is
+        // gathered with the weights exp(e - m).  out = acc / sum at the end: the weights of a row add up to one within
+        // rounding whatever the magnitude of the scores.  Indices are fetched two chunks ahead, the scores one chunk ahead.
+        float m = -INFINITY, sum = 0.f;
+        float acc[NT][VEC];
+#pragma unroll
+        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
+        uint32_t c1 = 0, c2 = 0;
+        float x1 = 0.f;
+        if (beg + lane < end) { c1 = indices[beg + lane]; x1 = s_src[(size_t)c1 * K + k]; }
+        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        for (uint32_t base = beg; base < end; base += 64) {
+            const uint32_t my_c = c1;
+            const float my_x = x1;
+            c1 = c2;
+            x1 = 0.f; c2 = 0;
+            if ((size_t)base + 64 + lane < end) x1 = s_src[(size_t)c1 * K + k];
+            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
+            const uint32_t cnt = min(64u, end - base);
+            const float e = lane < cnt ? gat_lrelu(sd + my_x, slope) : -INFINITY;
+            const float m_new = fmaxf(m, wave_max(e));
+            const float scale = expf(m - m_new);            // 0 at the first chunk (m = -inf), where sum and acc are 0
+            const float my_a = lane < cnt ? expf(e - m_new) : 0.f;
+            sum = fmaf(sum, scale, wave_sum(my_a));
+            m = m_new;
+            if (scale != 1.f) {                              // wave-uniform
+#pragma unroll
+                for (int t = 0; t < NT; t++)
+#pragma unroll
+                    for (int v = 0; v < VEC; v++) acc[t][v] *= scale;
+            }
+            for (uint32_t j = 0; j < cnt; j += n_grp * U) {
+                float z[U][NT][VEC], a[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const uint32_t c = __shfl(my_c, src & 63);
+                    const float av = __shfl(my_a, src & 63);
+                    const bool ok = src < cnt;
+                    a[u] = ok ? av : 0.f;
+                    load_head_row<VEC, NT>(z[u], Zk + (size_t)c * ldz, lpr, sub, dh, ok);
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++)
+#pragma unroll
+                    for (int t = 0; t < NT; t++)
+#pragma unroll
+                        for (int v = 0; v < VEC; v++) acc[t][v] = fmaf(a[u], z[u][t][v], acc[t][v]);
+            }
+        }
+        const float inv = beg < end ? 1.f / sum : 0.f;
+        if (lane == 0) lse[row * K + k] = beg < end ? m + logf(sum) : 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) acc[t][v] = fold_groups(acc[t][v], lpr) * inv;
+            const uint32_t col = (t * lpr + sub) * VEC;
+            if (grp == 0 && col < dh) storev<VEC>(out + row * ldo + (size_t)k * dh + col, acc[t]);   // an empty row: +0.0
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// backward over the rows of F:  D[i, k] = G[i, head k] . out[i, head k]
+//   ds_dst[i, k] = sum_j alpha_ijk (G[i, head k] . Z[j, head k] - D[i, k]) lrelu'(x_ijk)
+// ---------------------------------------------------------------------------
+template <int VEC, int NT, int U>
+__global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                               const uint32_t *__restrict__ indices,
+                                                               const float *__restrict__ Z, size_t ldz,
+                                                               const float *__restrict__ s_dst, const float *__restrict__ s_src,
+                                                               const float *__restrict__ lse, const float *__restrict__ G,
+                                                               size_t ldg, const float *__restrict__ out, size_t ldo, uint32_t K,
+                                                               uint32_t dh, float slope, uint32_t lg, float *__restrict__ D,
+                                                               float *__restrict__ ds_dst) {
+    MGGCN_GAT_WAVE_ROW(n_rows);
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    for (uint32_t k = 0; k < K; k++) {
+        float g[NT][VEC], o[NT][VEC];
+        load_head_row<VEC, NT>(g, G + row * ldg + (size_t)k * dh, lpr, sub, dh);
+        load_head_row<VEC, NT>(o, out + row * ldo + (size_t)k * dh, lpr, sub, dh, grp == 0);   // one group's worth
+        const float Dk = wave_sum(dot_head_row<VEC, NT>(g, o));
+        const float sd = s_dst[row * K + k], ls = lse[row * K + k];
+        const float *__restrict__ Zk = Z + (size_t)k * dh;
+        float acc = 0.f;
+        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead, scores one chunk ahead
+        float x1 = 0.f;
+        if (beg + lane < end) { c1 = indices[beg + lane]; x1 = s_src[(size_t)c1 * K + k]; }
+        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        for (uint32_t base = beg; base < end; base += 64) {
+            const uint32_t my_c = c1;
+            const float my_x = x1;
+            c1 = c2;
+            x1 = 0.f; c2 = 0;
+            if ((size_t)base + 64 + lane < end) x1 = s_src[(size_t)c1 * K + k];
+            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
+            const uint32_t cnt = min(64u, end - base);
+            float my_w = 0.f;                       // alpha lrelu'(x) of my entry
+            if (lane < cnt) {
+                const float x = sd + my_x;
+                my_w = expf(gat_lrelu(x, slope) - ls) * (x > 0.f ? 1.f : slope);
+            }
+            for (uint32_t j = 0; j < cnt; j += n_grp * U) {
+                float p[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const uint32_t c = __shfl(my_c, src & 63);
+                    float z[NT][VEC];
+                    load_head_row<VEC, NT>(z, Zk + (size_t)c * ldz, lpr, sub, dh, src < cnt);
+                    p[u] = dot_head_row<VEC, NT>(g, z);
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const float w = __shfl(my_w, src & 63);
+                    const float da = group_sum(p[u], lpr);
+                    acc += src < cnt ? w * (da - Dk) : 0.f;
+                }
+            }
+        }
+        acc = fold_groups(acc, lpr);                // every lane of a group holds the group's sum: one per group is added
+        if (lane == 0) {
+            D[row * K + k] = Dk;
+            ds_dst[row * K + k] = acc;
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// backward over the rows of F^T (row j lists the destinations i that gather j):
+//   ds_src[j, k] = sum_i alpha_ijk (G[i, head k] . Z[j, head k] - D[i, k]) lrelu'(x_ijk)
+//   G_Z[j, head k] = sum_i alpha_ijk G[i, head k] + ds_dst[j, k] att[0, head k] + ds_src[j, k] att[1, head k]
+// ---------------------------------------------------------------------------
+template <int VEC, int NT, int U>
+__global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                               const uint32_t *__restrict__ indices,
+                                                               const float *__restrict__ Z, size_t ldz,
+                                                               const float *__restrict__ s_dst, const float *__restrict__ s_src,
+                                                               const float *__restrict__ lse, const float *__restrict__ D,
+                                                               const float *__restrict__ G, size_t ldg,
+                                                               const float *__restrict__ att, const float *__restrict__ ds_dst,
+                                                               uint32_t K, uint32_t dh, float slope, uint32_t lg,
+                                                               float *__restrict__ ds_src, float *__restrict__ G_Z, size_t ldgz) {
+    MGGCN_GAT_WAVE_ROW(n_rows);
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    const uint32_t width = K * dh;
+    for (uint32_t k = 0; k < K; k++) {
+        float zr[NT][VEC], acc[NT][VEC];
+        load_head_row<VEC, NT>(zr, Z + row * ldz + (size_t)k * dh, lpr, sub, dh);
+#pragma unroll
+        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
+        const float ss = s_src[row * K + k];
+        const float *__restrict__ Gk = G + (size_t)k * dh;
+        float acc_ds = 0.f;
+        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead, the entries' scalars one chunk ahead
+        float x1 = 0.f, l1 = 0.f, D1 = 0.f;
+        if (beg + lane < end) {
+            c1 = indices[beg + lane];
+            const size_t ik = (size_t)c1 * K + k;
+            x1 = s_dst[ik]; l1 = lse[ik]; D1 = D[ik];
+        }
+        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        for (uint32_t base = beg; base < end; base += 64) {
+            const uint32_t my_c = c1;
+            const float my_x = x1, my_l = l1, my_D = D1;
+            c1 = c2;
+            x1 = 0.f; l1 = 0.f; D1 = 0.f; c2 = 0;
+            if ((size_t)base + 64 + lane < end) {
+                const size_t ik = (size_t)c1 * K + k;
+                x1 = s_dst[ik]; l1 = lse[ik]; D1 = D[ik];
+            }
+            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
+            const uint32_t cnt = min(64u, end - base);
+            float my_a = 0.f, my_w = 0.f;
+            if (lane < cnt) {
+                const float x = my_x + ss;
+                my_a = expf(gat_lrelu(x, slope) - my_l);
+                my_w = my_a * (x > 0.f ? 1.f : slope);
+            }
+            for (uint32_t j = 0; j < cnt; j += n_grp * U) {
+                float gv[U][NT][VEC], p[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const uint32_t c = __shfl(my_c, src & 63);
+                    load_head_row<VEC, NT>(gv[u], Gk + (size_t)c * ldg, lpr, sub, dh, src < cnt);
+                    p[u] = dot_head_row<VEC, NT>(zr, gv[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const bool ok = src < cnt;
+                    const float a = __shfl(my_a, src & 63), w = __shfl(my_w, src & 63), Dv = __shfl(my_D, src & 63);
+                    const float da = group_sum(p[u], lpr);
+                    acc_ds += ok ? w * (da - Dv) : 0.f;
+                    const float au = ok ? a : 0.f;
+#pragma unroll
+                    for (int t = 0; t < NT; t++)
+#pragma unroll
+                        for (int v = 0; v < VEC; v++) acc[t][v] = fmaf(au, gv[u][t][v], acc[t][v]);
+                }
+            }
+        }
+        acc_ds = fold_groups(acc_ds, lpr);
+        if (lane == 0) ds_src[row * K + k] = acc_ds;
+        const float dd = ds_dst ? ds_dst[row * K + k] : 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) acc[t][v] = fold_groups(acc[t][v], lpr);
+            const uint32_t col = (t * lpr + sub) * VEC;
+            if (grp == 0 && col < dh) {
+                float a0[VEC], a1[VEC];
+                loadv<VEC>(a0, att + (size_t)k * dh + col);
+                loadv<VEC>(a1, att + width + (size_t)k * dh + col);
+#pragma unroll
+                for (int v = 0; v < VEC; v++) acc[t][v] = fmaf(acc_ds, a1[v], fmaf(dd, a0[v], acc[t][v]));
+                storev<VEC>(G_Z + row * ldgz + (size_t)k * dh + col, acc[t]);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// G_att[0, c] = sum_i ds_dst[i, k(c)] Z_dst[i, c],  G_att[1, c] = sum_j ds_src[j, k(c)] Z_src[j, c]
+// A workgroup walks rows blockIdx * R + rr, + gridDim * R, ... (R = 256 / tpr rows at a time, tpr threads per row), folds its R
+// row slots in LDS in slot order and stores one [2 x width] partial; gat_colsum_final_kernel adds the partials in
+// workgroup order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gat_scores_backward_kernel(const float *__restrict__ ds_dst, const float *__restrict__ Zd,
+                                                                  size_t ldzd, size_t n_dst, const float *__restrict__ ds_src,
+                                                                  const float *__restrict__ Zs, size_t ldzs, size_t n_src,
+                                                                  uint32_t K, uint32_t dh, uint32_t tl,
+                                                                  float *__restrict__ partials) {
+    __shared__ float red[256];
+    const uint32_t tpr = 1u << tl, R = 256u >> tl, rr = threadIdx.x >> tl, cc = threadIdx.x & (tpr - 1);
+    const uint32_t width = K * dh;
+    for (int side = 0; side < 2; side++) {
+        const float *__restrict__ ds = side ? ds_src : ds_dst;
+        const float *__restrict__ Zp = side ? Zs : Zd;
+        const size_t ld = side ? ldzs : ldzd, n = side ? n_src : n_dst;
+        for (uint32_t c0 = 0; c0 < width; c0 += tpr) {      // every thread of the block takes every turn (barriers)
+            const uint32_t c = c0 + cc;
+            const bool on = c < width;
+            const uint32_t k = on ? c / dh : 0;
+            float acc = 0.f;
+            if (on)
+                for (size_t r = (size_t)blockIdx.x * R + rr; r < n; r += (size_t)gridDim.x * R)
+                    acc = fmaf(ds[r * K + k], Zp[r * ld + c], acc);
+            red[threadIdx.x] = acc;
+            __syncthreads();
+            if (rr == 0 && on) {
+                float s = red[cc];
+                for (uint32_t q = 1; q < R; q++) s += red[q * tpr + cc];
+                partials[((size_t)blockIdx.x * 2 + side) * width + c] = s;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// G_att[idx] = the workgroups' partials added in a fixed order (four slices b, b + 4, ... that meet in LDS), as
+// layer_norm_colsum_final_kernel does.  n_blocks == 0 stores zeros.
+__global__ __launch_bounds__(256) void gat_colsum_final_kernel(const float *__restrict__ partials, unsigned n_blocks,
+                                                               uint32_t two_w, float *__restrict__ G_att) {
+    __shared__ float w[4][64];
+    const uint32_t lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
+    const uint32_t idx = blockIdx.x * 64 + lane;
+    float s = 0.f;
+    if (idx < two_w) {
+#pragma unroll 8
+        for (unsigned b = slice; b < n_blocks; b += 4) s += partials[(size_t)b * two_w + idx];
+    }
+    w[slice][lane] = s;
+    __syncthreads();
+    if (slice == 0 && idx < two_w) G_att[idx] = (w[0][lane] + w[1][lane]) + (w[2][lane] + w[3][lane]);
+}
+
+uint32_t ceil_log2(uint32_t x) {
+    uint32_t l = 0;
+    while ((1u << l) < x) l++;
+    return l;
+}
+
+// group geometry of one head: log2(LPR) and the number of column tiles
+struct head_geometry { uint32_t lg, nt; };
+head_geometry head_geometry_for(uint32_t dh, bool vec) {
+    const uint32_t units = vec ? dh / 4 : dh;                   // lane slots one head-row needs
+    const uint32_t lg = std::min(ceil_log2(units), 6u);
+    return {lg, (units + (1u << lg) - 1) >> lg};
+}
+
+void require_heads(uint32_t K, uint32_t dh) {
+    MGGCN_REQUIRE(K >= 1 && K <= MGGCN_GAT_MAX_HEADS, "gat supports 1 <= heads <= 16");
+    MGGCN_REQUIRE(dh >= 1 && (size_t)K * dh <= MGGCN_GAT_MAX_WIDTH, "gat supports 1 <= heads * width per head <= 1024");
+}
+
+bool rows16(const float *p, size_t ld) { return aligned16(p) && ld % 4 == 0; }
+
+// (VEC, NT, U) from the path and the tile count: vec needs <= 4 tiles (dh <= 1024), the element path <= 16
+#define MGGCN_GAT_DISPATCH(F, vec, nt)        \
+    do {                                      \
+        if (vec) {                            \
+            if ((nt) == 1) F(4, 1, 4);        \
+            else F(4, 4, 1);                  \
+        } else {                              \
+            if ((nt) == 1) F(1, 1, 4);        \
+            else if ((nt) <= 4) F(1, 4, 2);   \
+            else F(1, 16, 1);                 \
+        }                                     \
+    } while (0)
+
+}  // namespace
+
+// ============================ C ABI =========================================
+MGGCN_API void mggcn_gat_scores_f32(mggcn_stream_t stream, const float *Z, size_t ldz, const float *att, float *s_dst,
+                                    float *s_src, size_t n_rows, uint32_t K, uint32_t dh) {
+    require_heads(K, dh);
+    MGGCN_REQUIRE(ldz >= (size_t)K * dh, "gat scores: ldz < heads * width per head");
+    MGGCN_REQUIRE(n_rows <= 0xFFFFFFFFu, "gat scores: more than 2^32 - 1 rows");
+    if (!n_rows || (!s_dst && !s_src)) return;
+    MGGCN_REQUIRE(Z != nullptr && att != nullptr, "gat scores: null operand");
+    const uint32_t lg = std::min(ceil_log2(dh), 6u);
+    hipLaunchKernelGGL(gat_scores_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, as_stream(stream), Z, ldz, att,
+                       s_dst, s_src, n_rows, K, dh, lg);
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_gat_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                     const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                     const float *s_src, uint32_t K, uint32_t dh, float slope, float *out, size_t ldo,
+                                     float *lse) {
+    require_heads(K, dh);
+    MGGCN_REQUIRE(ldz >= (size_t)K * dh && ldo >= (size_t)K * dh, "gat forward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && s_dst != nullptr && out != nullptr && lse != nullptr, "gat forward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Z != nullptr && s_src != nullptr), "gat forward: null operand");
+    MGGCN_REQUIRE(out != Z, "gat forward: out must not alias Z");
+    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(out, ldo);
+    const head_geometry hg = head_geometry_for(dh, vec);
+#define MGGCN_GAT_FWD(V, NT, U)                                                                                            \
+    hipLaunchKernelGGL((gat_forward_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, indptr, \
+                       indices, Z, ldz, s_dst, s_src, K, dh, slope, hg.lg, out, ldo, lse)
+    MGGCN_GAT_DISPATCH(MGGCN_GAT_FWD, vec, hg.nt);
+#undef MGGCN_GAT_FWD
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_gat_backward_dst_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                          const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                          const float *s_src, const float *lse, const float *G, size_t ldg, const float *out,
+                                          size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *ds_dst) {
+    require_heads(K, dh);
+    const size_t width = (size_t)K * dh;
+    MGGCN_REQUIRE(ldz >= width && ldg >= width && ldo >= width, "gat backward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && s_dst != nullptr && lse != nullptr && G != nullptr && out != nullptr && D != nullptr &&
+                      ds_dst != nullptr,
+                  "gat backward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Z != nullptr && s_src != nullptr), "gat backward: null operand");
+    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(out, ldo);
+    const head_geometry hg = head_geometry_for(dh, vec);
+#define MGGCN_GAT_BWD_DST(V, NT, U)                                                                                         \
+    hipLaunchKernelGGL((gat_backward_dst_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
+                       indptr, indices, Z, ldz, s_dst, s_src, lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, ds_dst)
+    MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_DST, vec, hg.nt);
+#undef MGGCN_GAT_BWD_DST
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_gat_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                          const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst,
+                                          const float *s_src, const float *lse, const float *D, const float *G, size_t ldg,
+                                          const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
+                                          float *ds_src, float *G_Z, size_t ldgz) {
+    require_heads(K, dh);
+    const size_t width = (size_t)K * dh;
+    MGGCN_REQUIRE(ldz >= width && ldg >= width && ldgz >= width, "gat backward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(t_indptr != nullptr && Z != nullptr && s_src != nullptr && att != nullptr && ds_src != nullptr &&
+                      G_Z != nullptr,
+                  "gat backward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && s_dst != nullptr && lse != nullptr && D != nullptr && G != nullptr),
+                  "gat backward: null operand");
+    MGGCN_REQUIRE(G_Z != G && G_Z != Z, "gat backward: G_Z must not alias G or Z");
+    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(G_Z, ldgz) && aligned16(att);
+    const head_geometry hg = head_geometry_for(dh, vec);
+#define MGGCN_GAT_BWD_SRC(V, NT, U)                                                                                         \
+    hipLaunchKernelGGL((gat_backward_src_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
+                       t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, G, ldg, att, ds_dst, K, dh, slope, hg.lg, ds_src,  \
+                       G_Z, ldgz)
+    MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_SRC, vec, hg.nt);
+#undef MGGCN_GAT_BWD_SRC
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_gat_scores_backward_f32(mggcn_stream_t stream, const float *ds_dst, const float *Z_dst, size_t ldzd,
+                                             size_t n_dst, const float *ds_src, const float *Z_src, size_t ldzs, size_t n_src,
+                                             uint32_t K, uint32_t dh, float *G_att) {
+    require_heads(K, dh);
+    const uint32_t width = K * dh;
+    MGGCN_REQUIRE(ldzd >= width && ldzs >= width, "gat scores backward: leading dimension < heads * width per head");
+    MGGCN_REQUIRE(G_att != nullptr, "gat scores backward: null gradient");
+    MGGCN_REQUIRE(n_dst == 0 || (ds_dst != nullptr && Z_dst != nullptr), "gat scores backward: null operand");
+    MGGCN_REQUIRE(n_src == 0 || (ds_src != nullptr && Z_src != nullptr), "gat scores backward: null operand");
+    const hipStream_t st = as_stream(stream);
+    const unsigned final_grid = (2 * width + 63) / 64;
+    const size_t n = std::max(n_dst, n_src);
+    unsigned grid = 0;
+    float *partials = nullptr;
+    if (n) {
+        const uint32_t tl = std::min(ceil_log2(width), 8u);            // threads per row: the power of two covering the width, <= 256
+        const size_t R = 256u >> tl;
+        grid = (unsigned)std::min<size_t>((n + R - 1) / R, kGatColsumBlocks);
+        partials = colsum_scratch(st, (size_t)kGatColsumBlocks * 2 * width);
+        hipLaunchKernelGGL(gat_scores_backward_kernel, dim3(grid), dim3(256), 0, st, ds_dst, Z_dst, ldzd, n_dst, ds_src, Z_src,
+                           ldzs, n_src, K, dh, tl, partials);
+        MGGCN_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(gat_colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, partials, grid, 2 * width, G_att);
+    MGGCN_CHECK_LAUNCH();
+}

@@ -1,0 +1,236 @@
+"""Graph attention (GAT) layers over the HIP engine, single GPU (opt-in; the reference has no attention layer).
+
+A layer of ``heads = K`` heads of width ``dh`` (``out = K * dh``) computes, over the pattern of the matrix the GCN forward
+aggregates with (F = A.transpose(): row i lists the sources j of destination i; values are ignored, a duplicate entry
+counts as two edges):
+
+    Z = H W + 1 b^T                                   (the existing ``linear``; always GEMM first)
+    s_dst[i, k] = Z[i, head k] . att[0, head k]       s_src[j, k] = Z[j, head k] . att[1, head k]
+    e_ijk = lrelu(s_dst[i, k] + s_src[j, k], slope)   alpha_ijk = softmax over the entries j of row i
+    out[i, head k] = sum_j alpha_ijk Z[j, head k]
+
+and every layer but the last applies the project's leaky ReLU (0.01) afterwards.  The bias sits inside Z and so enters the
+scores (PyG adds its bias after the aggregation instead).  The kernels are those of csrc/gat.hip (include/mggcn.h:
+mggcn_gat_*): nothing of nnz x heads is stored, the backward pass recomputes alpha from s_dst, s_src and lse.
+
+Not covered: dist_gcn, the C++ host layer and CLI, checkpoints, dropout, layer norm, bf16 gathers, attention dropout.
+"""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import _lib, ops
+from .gcn import (adam_update_all, check_loss, gcn, linear, sigmoid_bce_loss, softmax_cross_entropy_loss)
+from .matrix import context, csr_matrix, dn_matrix
+
+
+def check_heads(sizes: Sequence[int], heads) -> List[int]:
+    """heads per layer from ``heads=``: an int (every layer but the last has that many, the last 1) or one int per layer;
+    ValueError when a width is not divisible by its heads or a limit of the kernels is exceeded.  No device work."""
+    n_layers = len(sizes) - 1
+    if n_layers < 1:
+        raise ValueError("gat needs at least two sizes (one layer)")
+    if isinstance(heads, (list, tuple)):
+        per_layer = list(heads)
+        if len(per_layer) != n_layers:
+            raise ValueError(f"heads lists {len(per_layer)} layers, the model has {n_layers}")
+    else:
+        per_layer = [heads] * (n_layers - 1) + [1]
+    for li, h in enumerate(per_layer):
+        ops.check_gat_heads(h, int(sizes[li + 1]), f"gat layer {li}")
+    return [int(h) for h in per_layer]
+
+
+class attention:
+    """The attention of one layer: the parameter ``att`` [2 x out] (row 0 the destination vector, row 1 the source
+    vector; seed-99 uniform like W), its gradient and Adam state, and what the backward pass needs of the forward --
+    s_dst, s_src, lse [n x heads].  att is trained by Adam with the weight decay of W."""
+
+    def __init__(self, name: str, n_dst: int, n_src: int, out: int, heads: int, slope: float = ops.GAT_SLOPE, device=None):
+        self.name, self.heads, self.slope = name, int(heads), float(slope)
+        self.att, self.G_att = dn_matrix(2, out, device=device), dn_matrix(2, out, device=device)
+        host = np.empty((2, out), dtype=np.float32)
+        _lib.load().mggcn_init_uniform_host(host.ctypes.data, out, 2, -1.0)
+        self.att.init(host)
+        self.s_dst, self.lse, self.D, self.ds_dst = (dn_matrix(n_dst, heads, device=device) for _ in range(4))
+        self.s_src, self.ds_src = dn_matrix(n_src, heads, device=device), dn_matrix(n_src, heads, device=device)
+        self.m = self.v = None
+        self.step = 0
+
+    def __call__(self, ctx: context, F: csr_matrix, Z: dn_matrix, out: dn_matrix) -> None:
+        """out = the attention-weighted gather of Z over F's rows (destinations and sources are the same vertices)"""
+        n = self.name
+        ops.gat_scores(ctx, Z, self.att, self.s_dst, self.s_src, self.heads, n + "0_gat-scores")
+        ops.gat_forward(ctx, F, Z, self.s_dst, self.s_src, out, self.lse, self.heads, self.slope, n + "0_gat-forward")
+
+    def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z: dn_matrix, G: dn_matrix, out: dn_matrix,
+                 G_Z: dn_matrix) -> None:
+        """G_Z = the gradient of Z and G_att, from G = the gradient of ``out``"""
+        n = self.name
+        ops.gat_backward_dst(ctx, F, Z, self.s_dst, self.s_src, self.lse, G, out, self.D, self.ds_dst, self.heads, self.slope,
+                             n + "1_gat-backward-dst")
+        ops.gat_backward_src(ctx, F_T, Z, self.s_dst, self.s_src, self.lse, self.D, G, self.att, self.ds_dst, self.ds_src,
+                             G_Z, self.heads, self.slope, n + "1_gat-backward-src")
+        ops.gat_scores_backward(ctx, self.ds_dst, Z, self.ds_src, Z, self.G_att, self.heads, n + "1_gat-scores-backward")
+
+    def init(self, att) -> None:
+        self.att.init(np.asarray(att, dtype=np.float32))
+
+    def adam_state(self, ctx: context) -> None:
+        if self.m is None:
+            dev = self.att.t.device
+            self.m, self.v = dn_matrix(self.att.shape(), device=dev), dn_matrix(self.att.shape(), device=dev)
+            self.m.zero(ctx)
+            self.v.zero(ctx)
+            self.step = 0
+
+    def adam_tensors(self, weight_decay: float):
+        """row of ops.adam_table: att decays like W"""
+        return [(self.att, self.G_att, self.m, self.v, weight_decay)]
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
+        """one launch for this tensor: the element-wise math of the model-wide table, bit for bit"""
+        self.adam_state(ctx)
+        self.step += 1
+        bc1 = float(np.float32(1 - beta1 ** self.step))
+        bc2 = float(np.float32(1 - beta2 ** self.step))
+        ops.adam_fused(ctx, self.att, self.G_att, self.m, self.v, lr, beta1, beta2, weight_decay, bc1, bc2, eps)
+
+
+class gat_layer:
+    """One GAT layer: a ``linear`` (Z = H W + 1 b^T), an ``attention`` over (F, F^T) and the activation.  Z, the
+    aggregated ``out`` (before the activation: the backward pass needs it) and the activated output are kept per layer;
+    G_Z aliases the model-wide buffer.  ``backward_out=False`` (the first layer) skips the GEMM that only produces the
+    gradient of the layer's input."""
+
+    def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
+                 slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None):
+        n = F.n()
+        assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
+        self.name, self.F, self.F_T, self.activation = name, F, F_T, bool(activation)
+        # the linear's own fused kernels in every mode: gat(fused=...) only picks how Adam is launched
+        self.lin = linear(name, in_, out, backward_out, True)
+        self.attn = attention(name, n, n, out, heads, slope)
+        self.Z, self.out = dn_matrix(n, out), dn_matrix(n, out)
+        self.act = dn_matrix(n, out) if activation else self.out
+        self.G_Z = dn_matrix(n, out, G_Z_buffer) if G_Z_buffer is not None else dn_matrix(n, out)
+        self.G_out = dn_matrix(n, in_) if backward_out else None
+        self.H: Optional[dn_matrix] = None
+
+    def __call__(self, ctx: context, H: dn_matrix) -> dn_matrix:
+        n = self.name
+        self.H = H
+        self.lin(ctx, H, self.Z)
+        self.attn(ctx, self.F, self.Z, self.out)
+        if self.activation:
+            ctx.record(n + "0_0_activation", 0)
+            ops.leaky_relu_forward(ctx, self.out, self.act)
+            ctx.record(n + "0_1_activation", 0)
+            ctx.register_timer(n + "0_activation", n + "0_0_activation", n + "0_1_activation")
+        return self.act
+
+    def backward(self, ctx: context, G: dn_matrix) -> Optional[dn_matrix]:
+        n = self.name
+        T = G
+        if self.activation:
+            # the sign source is the aggregated output itself; T lands in the activated output's buffer, which the layer
+            # above has finished with (its G_W GEMM read it earlier on this stream)
+            ctx.record(n + "1_0_activation", 0)
+            ops.leaky_relu_backward(ctx, self.out, G, self.act)
+            ctx.record(n + "1_1_activation", 0)
+            ctx.register_timer(n + "1_activation", n + "1_0_activation", n + "1_1_activation")
+            T = self.act
+        self.attn.backward(ctx, self.F, self.F_T, self.Z, T, self.out, self.G_Z)
+        self.lin.setX(self.H)
+        self.lin.backward(ctx, self.G_Z, self.G_out)
+        return self.G_out
+
+    def linears(self):
+        return [self.lin]
+
+    def params(self):
+        """everything Adam updates"""
+        return [self.lin, self.attn]
+
+    def adam_update(self, ctx, lr, beta1, beta2, weight_decay, eps):
+        for p in self.params():
+            p.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+
+    def b(self): return self.lin.get_b()
+    def W(self): return self.lin.get_W()
+    def GW(self): return self.lin.get_G_W()
+    def Gb(self): return self.lin.get_G_b()
+    def att(self): return self.attn.att
+    def Gatt(self): return self.attn.G_att
+
+
+class gat:
+    """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
+
+    gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None): ``A`` as ``gcn`` takes it (the
+    layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
+    (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att).  ValueError
+    before any device work for a width that its heads do not divide or a limit of the kernels (ops.GAT_MAX_HEADS,
+    ops.GAT_MAX_WIDTH).  ``fused`` picks how Adam is launched -- one launch for every parameter tensor, or one per tensor;
+    the element-wise math is the same, so both give the same bits -- and every other kernel is the same in both modes.
+
+    __call__, train_forward, backward, adam_update, train_step (one synchronisation), evaluate, set_splits, split_metrics
+    and layers() mean what they mean on ``gcn``."""
+
+    def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
+                 loss: str = "softmax", fused: bool = True, weights=None):
+        self.sizes = [int(s) for s in sizes]
+        self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
+        self.loss = check_loss(loss)
+        if A.n() != A.m():
+            raise ValueError(f"gat needs a square matrix, got {A.n()} x {A.m()}")
+        self.attn_slope = float(attn_slope)
+        self._out_width = self.sizes[-1]
+        self.fused = bool(fused)
+        import torch
+        n_layers = len(self.sizes) - 1
+        # the loss reads the logits and writes the gradient elsewhere: the last layer's backward needs its own output
+        loss_class = sigmoid_bce_loss if self.loss == "bce" else softmax_cross_entropy_loss
+        self.loss_layer = loss_class(f"{n_layers}_", True, True)
+        self.A, self.A_T = A, A.transpose()                      # forward over A_T's rows, like gcn
+        self.G_Z_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
+        self.layers_: List[gat_layer] = []
+        for i in range(n_layers):
+            self.layers_.append(gat_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
+                                          i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer))
+        self._adam = None
+        if weights is not None:
+            assert len(weights) == n_layers
+            for layer, w in zip(self.layers_, weights):
+                layer.W().init(np.asarray(w[0], dtype=np.float32))
+                layer.b().init(np.asarray(w[1], dtype=np.float32))
+                if len(w) > 2:
+                    layer.attn.init(w[2])
+
+    def __call__(self, ctx: context, H: dn_matrix, training: bool = False) -> dn_matrix:
+        """the forward pass (``training`` changes nothing: there is no dropout here)"""
+        for layer in self.layers_:
+            H = layer(ctx, H)
+        return H
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
+        if not self.fused:
+            for layer in self.layers_:
+                layer.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+            return
+        self._adam = adam_update_all(ctx, [p for l in self.layers_ for p in l.params()], self._adam, lr, beta1, beta2,
+                                     weight_decay, eps)
+
+    def layers(self) -> List[gat_layer]:
+        return self.layers_
+
+    # the model-level plumbing is gcn's, word for word: it only touches what the two classes share (loss_layer, layers_,
+    # loss, A, _out_width and the calls above)
+    set_splits = gcn.set_splits
+    split_metrics = gcn.split_metrics
+    train_forward = gcn.train_forward
+    backward = gcn.backward
+    train_step = gcn.train_step
+    evaluate = gcn.evaluate

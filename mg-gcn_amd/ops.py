@@ -414,6 +414,107 @@ def layer_norm_backward(ctx: context, G: dn_matrix, act: Optional[dn_matrix], xh
                                           G.n(), G.m(), int(flags))
 
 
+GAT_MAX_HEADS = 16                  # MGGCN_GAT_MAX_HEADS
+GAT_MAX_WIDTH = 1024                # MGGCN_GAT_MAX_WIDTH: heads x width per head
+GAT_SLOPE = 0.2                     # the leaky ReLU of the attention scores (not the layers' 0.01)
+
+
+def check_gat_heads(heads: int, width: int, what: str = "gat") -> int:
+    """the width per head of ``width`` columns cut into ``heads`` heads; ValueError when a limit of the kernels is
+    exceeded or the width does not divide, before the library is touched (it would print and exit, not raise)"""
+    _req(isinstance(heads, numbers.Integral) and 1 <= heads <= GAT_MAX_HEADS,
+         f"{what} supports 1 <= heads <= {GAT_MAX_HEADS}, got {heads!r}")
+    _req(1 <= width <= GAT_MAX_WIDTH, f"{what} supports 1 <= heads x width per head <= {GAT_MAX_WIDTH}, got {width}")
+    _req(width % heads == 0, f"{what}: a width of {width} is not divisible by {heads} heads")
+    return width // int(heads)
+
+
+def _gat_timed(ctx: context, timer: Optional[str], call) -> None:
+    """``call()`` between two events on the compute stream, registered as ``timer`` (None: no events)"""
+    if timer is None:
+        return call()
+    ctx.record(timer + "_0", 0)
+    call()
+    ctx.record(timer + "_1", 0)
+    ctx.register_timer(timer, timer + "_0", timer + "_1")
+
+
+def gat_scores(ctx: context, Z: dn_matrix, att: dn_matrix, s_dst: Optional[dn_matrix], s_src: Optional[dn_matrix],
+               heads: int, timer: Optional[str] = None) -> None:
+    """s_dst[r, k] = Z[r, head k] . att[0, head k] and s_src likewise with att[1] (mggcn_gat_scores_f32); either output
+    may be None.  att is [2 x Z.m()], the outputs [Z.n() x heads]."""
+    check_gat_heads(heads, Z.m(), "gat scores")
+    _req(att.shape() == (2, Z.m()), f"gat scores: att must be 2 x {Z.m()}")
+    for s in (s_dst, s_src):
+        _req(s is None or s.shape() == (Z.n(), heads), f"gat scores: the scores must be {Z.n()} x {heads}")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_scores_f32(
+        ctx.stream(0), Z.buffer(), Z.m(), att.buffer(), s_dst.buffer() if s_dst is not None else None,
+        s_src.buffer() if s_src is not None else None, Z.n(), heads, Z.m() // heads))
+
+
+def gat_forward(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
+                lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """The edge-softmax fused with the gather (mggcn_gat_forward_f32): over F's pattern (values ignored), lse[i, k] =
+    log sum_j exp(lrelu(s_dst[i, k] + s_src[j, k])) and out[i, head k] = sum_j alpha_ijk Z[j, head k].  F: destinations x
+    sources; Z, s_src: one row per source; s_dst, out, lse: one row per destination."""
+    check_gat_heads(heads, Z.m(), "gat forward")
+    _req(F.m() == Z.n() and out.shape() == (F.n(), Z.m()), "gat forward: shape mismatch")
+    _req(s_dst.shape() == (F.n(), heads) and lse.shape() == (F.n(), heads) and s_src.shape() == (F.m(), heads),
+         "gat forward: the scores and lse must be rows x heads")
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_forward_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(), heads,
+        Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer()))
+
+
+def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
+                     G: dn_matrix, out: dn_matrix, D: dn_matrix, ds_dst: dn_matrix, heads: int, slope: float = GAT_SLOPE,
+                     timer: Optional[str] = None) -> None:
+    """The half of the backward pass that sums over sources, over F's rows (mggcn_gat_backward_dst_f32): D[i, k] =
+    G[i, head k] . out[i, head k] and ds_dst[i, k] = sum_j alpha_ijk (G[i, head k] . Z[j, head k] - D[i, k]) lrelu'(x_ijk)."""
+    check_gat_heads(heads, Z.m(), "gat backward")
+    _req(F.m() == Z.n() and G.shape() == (F.n(), Z.m()) and out.shape() == G.shape(), "gat backward: shape mismatch")
+    _req(all(s.shape() == (F.n(), heads) for s in (s_dst, lse, D, ds_dst)) and s_src.shape() == (F.m(), heads),
+         "gat backward: the scores, lse, D and ds must be rows x heads")
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_dst_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
+        lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer()))
+
+
+def gat_backward_src(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
+                     D: dn_matrix, G: dn_matrix, att: dn_matrix, ds_dst: Optional[dn_matrix], ds_src: dn_matrix,
+                     G_Z: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """The half that sums over destinations, over the rows of F^T (mggcn_gat_backward_src_f32; after gat_backward_dst):
+    ds_src[j, k] = sum_i ds_ijk and G_Z[j, head k] = sum_i alpha_ijk G[i, head k] + ds_dst[j, k] att[0, head k] +
+    ds_src[j, k] att[1, head k].  ds_dst is indexed by source here (the square case passes gat_backward_dst's); None leaves
+    its term out."""
+    check_gat_heads(heads, Z.m(), "gat backward")
+    _req(F_T.n() == Z.n() and G.shape() == (F_T.m(), Z.m()) and G_Z.shape() == Z.shape(), "gat backward: shape mismatch")
+    _req(att.shape() == (2, Z.m()), f"gat backward: att must be 2 x {Z.m()}")
+    _req(all(s.shape() == (F_T.m(), heads) for s in (s_dst, lse, D)) and s_src.shape() == (F_T.n(), heads)
+         and ds_src.shape() == (F_T.n(), heads) and (ds_dst is None or ds_dst.shape() == (F_T.n(), heads)),
+         "gat backward: the scores, lse, D and ds must be rows x heads")
+    ip, ix, _ = F_T.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_f32(
+        ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
+        lse.buffer(), D.buffer(), G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
+        Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m()))
+
+
+def gat_scores_backward(ctx: context, ds_dst: dn_matrix, Z_dst: dn_matrix, ds_src: dn_matrix, Z_src: dn_matrix,
+                        G_att: dn_matrix, heads: int, timer: Optional[str] = None) -> None:
+    """G_att[0] = the column sums of ds_dst[i, k(c)] Z_dst[i, c], G_att[1] those of ds_src and Z_src
+    (mggcn_gat_scores_backward_f32; bitwise reproducible).  The square case passes the same Z twice."""
+    check_gat_heads(heads, Z_src.m(), "gat scores backward")
+    _req(Z_dst.m() == Z_src.m() and G_att.shape() == (2, Z_src.m()), f"gat scores backward: G_att must be 2 x {Z_src.m()}")
+    _req(ds_dst.shape() == (Z_dst.n(), heads) and ds_src.shape() == (Z_src.n(), heads),
+         "gat scores backward: ds must be rows x heads")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_scores_backward_f32(
+        ctx.stream(0), ds_dst.buffer(), Z_dst.buffer(), Z_dst.m(), Z_dst.n(), ds_src.buffer(), Z_src.buffer(), Z_src.m(),
+        Z_src.n(), heads, Z_src.m() // heads, G_att.buffer()))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
