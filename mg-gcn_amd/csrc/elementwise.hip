@@ -10,13 +10,8 @@
 // passes over [n x m] fp32; none is reshaped into a GEMM.
 #include <algorithm>
 
-#include <map>
-#include <vector>
-#include <type_traits>
-#include <mutex>
-#include <utility>
-
 #include "common.h"
+#include "reduce.h"
 #include "scratch_internal.h"
 
 namespace {
@@ -132,17 +127,6 @@ __global__ __launch_bounds__(256) void subtract_rows_exp_kernel(const float *__r
 }
 
 // ---- one wave64 per row ---------------------------------------------------
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-
 // row max                              reference src/cuda_utils.cu:95-104
 __global__ __launch_bounds__(256) void max_rows_kernel(const float *__restrict__ mat,
                                                        float *__restrict__ maxs, size_t n_rows, size_t m) {
@@ -157,26 +141,6 @@ __global__ __launch_bounds__(256) void max_rows_kernel(const float *__restrict__
 }
 
 // argmax, first maximum wins           reference src/cuda_utils.cu:119-133
-// Wave-wide reductions on the DPP path (no LDS): four in-row steps (quad swaps, half-row and row mirrors) leave every
-// lane of a 16-lane row with its row's result, four v_readlane bring the row results together.  hipcc lowers
-// __shfl_xor to ds_bpermute_b32, an LDS-crossbar instruction: the fused loss kernel spent its time there (~30 per row).
-template <typename Op>
-__device__ __forceinline__ float wave_reduce_dpp(float v, Op op) {
-    auto dpp = [](float x, auto ctrl) {
-        return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
-    v = op(v, dpp(v, std::integral_constant<int, 0xB1>{}));     // quad_perm [1,0,3,2]
-    v = op(v, dpp(v, std::integral_constant<int, 0x4E>{}));     // quad_perm [2,3,0,1]
-    v = op(v, dpp(v, std::integral_constant<int, 0x141>{}));    // row_half_mirror
-    v = op(v, dpp(v, std::integral_constant<int, 0x140>{}));    // row_mirror
-    // (the builtin is typed int: a float argument would be CONVERTED, not re-interpreted)
-    auto lane_f = [](float x, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, x), l)); };
-    const float r0 = lane_f(v, 0), r1 = lane_f(v, 16), r2 = lane_f(v, 32), r3 = lane_f(v, 48);
-    return op(op(r0, r1), op(r2, r3));
-}
-__device__ __forceinline__ float wave_sum_dpp(float v) { return wave_reduce_dpp(v, [](float a, float b) { return a + b; }); }
-__device__ __forceinline__ float wave_max_dpp(float v) { return wave_reduce_dpp(v, [](float a, float b) { return fmaxf(a, b); }); }
-
 __device__ __forceinline__ void argmax_combine(float &v, uint32_t &i, float ov, uint32_t oi) {
     if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
@@ -241,50 +205,18 @@ __global__ __launch_bounds__(256) void adam_final_kernel(float *__restrict__ par
         param[i] -= step * m[i] / (sqrtf(v[i] / c2) + eps);
 }
 
-// ---- |x| sum: fixed-order two-level reduction (reproducible) ---------------
+// ---- |x| sum: the reduction tree of reduce.h (reproducible) -----------------
 constexpr unsigned kAsumBlocks = 1024;
-constexpr unsigned kXentBlocks = kNumCU * 8;               // grid cap of the fused loss (stream_grid)
-constexpr unsigned kScratchFloats = 16 * kXentBlocks;       // abssum partials / the fused loss's (loss, correct) pairs: one pair
-                                                            // per workgroup, four (one per split slot) in the split-aware form /
-                                                            // the sigmoid-BCE loss's (loss, TP, FP, FN) per split slot
+constexpr unsigned kXentBlocks = kNumCU * 8;               // grid cap of the fused losses (stream_grid)
 
 __global__ __launch_bounds__(256) void abssum_partial_kernel(const float *__restrict__ A, size_t size,
                                                              float *__restrict__ partial) {
-    __shared__ float wsum[4];
+    __shared__ float wsum[1][4];
     const size_t stride = (size_t)gridDim.x * blockDim.x;
     float s = 0.f;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < size; i += stride) s += fabsf(A[i]);
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) partial[blockIdx.x] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
-__global__ __launch_bounds__(256) void abssum_final_kernel(const float *__restrict__ partial, unsigned n,
-                                                           float *__restrict__ result) {
-    __shared__ float wsum[4];
-    float s = 0.f;
-    for (unsigned i = threadIdx.x; i < n; i += 256) s += partial[i];
-    s = wave_sum(s);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) *result = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
-}
-
-// scratch for the abssum partials: one per (device, stream), allocated on first use (never on a captured
-// launch path: the host layers call abssum once during warm-up).  Per STREAM, not per device: several
-// contexts may drive one GPU at once (a dist_context whose ranks share a device, two models on two
-// streams) and two sums in flight on different streams must not share their partials.
-std::mutex g_scratch_mu;
-std::map<std::pair<int, hipStream_t>, float *> g_scratch;
-
-float *abssum_scratch(hipStream_t st) {
-    int dev = 0;
-    MGGCN_CHECK_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    float *&p = g_scratch[{dev, st}];
-    if (!p) MGGCN_CHECK_HIP(hipMalloc(&p, kScratchFloats * sizeof(float)));
-    return p;
+    const float v[1] = {wave_sum(s)};
+    block_fold(v, wsum, partial + blockIdx.x);
 }
 
 // ---- fused softmax + cross-entropy + argmax + gradient ---------------------
@@ -318,24 +250,19 @@ __device__ __forceinline__ void xent_add_by_slot(int32_t set, float lt, float ct
     }
 }
 
-// The end of the split-aware kernels: lane 0 of every wave holds the wave's four pairs; one pair per workgroup and slot goes
-// to the partials ([workgroup][slot][loss, correct]), summed by sums_final_kernel<8>.
-__device__ __forceinline__ void xent_write_split_partials(float loss_acc, float corr_acc, const float (&loss_x)[3],
-                                                          const float (&corr_x)[3], float *s_loss, float *s_acc, int lane,
-                                                          int wid, float *__restrict__ partials) {
-    if (lane == 0) {
-        s_loss[wid] = loss_acc; s_acc[wid] = corr_acc;
+// The end of both fused kernels: the wave-reduced pairs as [slot][loss, correct], one set per workgroup in the partials
+// ([workgroup][slot][loss, correct]), summed by sums_final_kernel<2 * slots>.
+template <bool Split>
+__device__ __forceinline__ void xent_fold(float loss_acc, float corr_acc, const float (&loss_x)[3], const float (&corr_x)[3],
+                                          float (*lds)[4], float *__restrict__ partials) {
+    constexpr int NV = 2 * xent_slots(Split);
+    float v[NV];
+    v[0] = loss_acc; v[1] = corr_acc;
+    if constexpr (Split) {
 #pragma unroll
-        for (int j = 1; j < 4; j++) { s_loss[4 * j + wid] = loss_x[j - 1]; s_acc[4 * j + wid] = corr_x[j - 1]; }
+        for (int j = 0; j < 3; j++) { v[2 * j + 2] = loss_x[j]; v[2 * j + 3] = corr_x[j]; }
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            partials[8 * blockIdx.x + 2 * j + 0] = (s_loss[4 * j + 0] + s_loss[4 * j + 1]) + (s_loss[4 * j + 2] + s_loss[4 * j + 3]);
-            partials[8 * blockIdx.x + 2 * j + 1] = (s_acc[4 * j + 0] + s_acc[4 * j + 1]) + (s_acc[4 * j + 2] + s_acc[4 * j + 3]);
-        }
-    }
+    block_fold(v, lds, partials + (size_t)NV * blockIdx.x);
 }
 
 // (S and train_set come last: the arguments of the plain instances keep their places)
@@ -345,9 +272,8 @@ __global__ __launch_bounds__(256) void softmax_xent_fused_kernel(const float *sr
                                                                  size_t n_rows, size_t m, float grad_scale,
                                                                  float *__restrict__ partials,
                                                                  const int32_t *__restrict__ S, int32_t train_set) {
-    constexpr int NS = xent_slots(Split);
-    __shared__ float s_loss[4 * NS], s_acc[4 * NS];       // [slot][wave]
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __shared__ float s_sums[2 * xent_slots(Split)][4];    // [slot][loss, correct][wave]
+    const int lane = threadIdx.x & 63;
     const size_t wstride = ((size_t)gridDim.x * blockDim.x) >> 6;
     float loss_acc = 0.f, corr_acc = 0.f;
     float loss_x[3] = {0.f, 0.f, 0.f}, corr_x[3] = {0.f, 0.f, 0.f};      // slots 1..3, Split only
@@ -421,43 +347,21 @@ __global__ __launch_bounds__(256) void softmax_xent_fused_kernel(const float *sr
             }
         }
     }
-    if constexpr (Split) {
-        xent_write_split_partials(loss_acc, corr_acc, loss_x, corr_x, s_loss, s_acc, lane, wid, partials);
-    } else {
-        if (lane == 0) { s_loss[wid] = loss_acc; s_acc[wid] = corr_acc; }
-        __syncthreads();
-        if (threadIdx.x == 0) {              // one (loss, correct) pair per workgroup, summed by xent_final_kernel
-            partials[2 * blockIdx.x + 0] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
-            partials[2 * blockIdx.x + 1] = (s_acc[0] + s_acc[1]) + (s_acc[2] + s_acc[3]);
-        }
-    }
+    xent_fold<Split>(loss_acc, corr_acc, loss_x, corr_x, s_sums, partials);
 }
 
 // m <= 64 (the logits layer: 41 classes, 48 at P = 8): one row per 16-LANE GROUP, KE = ceil(m / 16) logits per lane, so a
-// wave works on four rows at once and every reduction is four DPP rotations inside the 16-lane row (row_ror 8, 4, 2, 1:
-// a butterfly -- both lanes of a pair add the same two numbers, so all 16 lanes end with the same bits), no v_readlane,
-// no cross-row step.  The wave-per-row form above keeps 41 of 64 lanes busy and spends a full wave reduction per row:
-// 105 us for the [233 k x 41] logits (0.7 TB/s); this one issues a quarter of the instructions per row.
-template <typename T, typename Op>
-__device__ __forceinline__ T row16_reduce(T v, Op op) {
-    auto ror = [](T x, auto ctrl) {
-        return __builtin_bit_cast(T, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), decltype(ctrl)::value, 0xF, 0xF, true));
-    };
-    v = op(v, ror(v, std::integral_constant<int, 0x128>{}));    // row_ror:8
-    v = op(v, ror(v, std::integral_constant<int, 0x124>{}));    // row_ror:4
-    v = op(v, ror(v, std::integral_constant<int, 0x122>{}));    // row_ror:2
-    v = op(v, ror(v, std::integral_constant<int, 0x121>{}));    // row_ror:1
-    return v;
-}
-
+// wave works on four rows at once and every reduction is four DPP rotations inside the 16-lane row (row16_reduce: all 16
+// lanes end with the same bits), no v_readlane, no cross-row step.  The wave-per-row form above keeps 41 of 64 lanes busy
+// and spends a full wave reduction per row: 105 us for the [233 k x 41] logits (0.7 TB/s); this one issues a quarter of the
+// instructions per row.
 template <int KE, int R, bool Split>
 __global__ __launch_bounds__(256) void softmax_xent_rows16_kernel(const float *src, float *dst,
                                                                   const int32_t *__restrict__ Y, size_t n_rows,
                                                                   uint32_t m, float grad_scale, float *__restrict__ partials,
                                                                   const int32_t *__restrict__ S, int32_t train_set) {
-    constexpr int NS = xent_slots(Split);
-    __shared__ float s_loss[4 * NS], s_acc[4 * NS];       // [slot][wave]
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    __shared__ float s_sums[2 * xent_slots(Split)][4];    // [slot][loss, correct][wave]
+    const int lane = threadIdx.x & 63;
     const uint32_t sub = lane & 15;
     const size_t gstride = ((size_t)gridDim.x * blockDim.x) >> 4;           // 16-lane groups in the grid
     const size_t g0 = ((size_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4;
@@ -529,62 +433,7 @@ __global__ __launch_bounds__(256) void softmax_xent_rows16_kernel(const float *s
 #pragma unroll
         for (int j = 0; j < 3; j++) { loss_x[j] = wave_sum_dpp(loss_x[j]); corr_x[j] = wave_sum_dpp(corr_x[j]); }
     }
-    if constexpr (Split) {
-        xent_write_split_partials(loss_acc, corr_acc, loss_x, corr_x, s_loss, s_acc, lane, wid, partials);
-    } else {
-        if (lane == 0) { s_loss[wid] = loss_acc; s_acc[wid] = corr_acc; }
-        __syncthreads();
-        if (threadIdx.x == 0) {              // one (loss, correct) pair per workgroup, summed by xent_final_kernel
-            partials[2 * blockIdx.x + 0] = (s_loss[0] + s_loss[1]) + (s_loss[2] + s_loss[3]);
-            partials[2 * blockIdx.x + 1] = (s_acc[0] + s_acc[1]) + (s_acc[2] + s_acc[3]);
-        }
-    }
-}
-
-// sums[0] += sum of the workgroups' loss terms, sums[1] += their correct counts, in a fixed order.  (First version: two
-// float atomics per workgroup on the same two addresses -- 4096 device-scope read-modify-writes in a row were most of the
-// pass: 61 us for any m <= 64; and the two scalars depended on arrival order in their last bits.)
-__global__ __launch_bounds__(256) void xent_final_kernel(const float *__restrict__ partials, unsigned n_blocks,
-                                                         float *__restrict__ sums) {
-    __shared__ float w[2][4];
-    float l = 0.f, a = 0.f;
-    for (unsigned i = threadIdx.x; i < n_blocks; i += 256) { l += partials[2 * i]; a += partials[2 * i + 1]; }
-    l = wave_sum(l); a = wave_sum(a);
-    if ((threadIdx.x & 63) == 0) { w[0][threadIdx.x >> 6] = l; w[1][threadIdx.x >> 6] = a; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        sums[0] += (w[0][0] + w[0][1]) + (w[0][2] + w[0][3]);
-        sums[1] += (w[1][0] + w[1][1]) + (w[1][2] + w[1][3]);
-    }
-}
-
-// The same tree for NV values per workgroup, each summed on its own in the order above (8: one pair per split slot; 4: the
-// by-set |x| sums).  Add = false stores instead of adding (mggcn_abssum_by_set_f32, like abssum_final_kernel).
-template <int NV, bool Add>
-__global__ __launch_bounds__(256) void sums_final_kernel(const float *__restrict__ partials, unsigned n_blocks,
-                                                         float *__restrict__ sums) {
-    __shared__ float w[NV][4];
-    float v[NV];
-#pragma unroll
-    for (int j = 0; j < NV; j++) v[j] = 0.f;
-    for (unsigned i = threadIdx.x; i < n_blocks; i += 256) {
-#pragma unroll
-        for (int j = 0; j < NV; j++) v[j] += partials[NV * i + j];
-    }
-#pragma unroll
-    for (int j = 0; j < NV; j++) v[j] = wave_sum(v[j]);
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int j = 0; j < NV; j++) w[j][threadIdx.x >> 6] = v[j];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int j = 0; j < NV; j++) {
-            const float t = (w[j][0] + w[j][1]) + (w[j][2] + w[j][3]);
-            sums[j] = Add ? sums[j] + t : t;
-        }
-    }
+    xent_fold<Split>(loss_acc, corr_acc, loss_x, corr_x, s_sums, partials);
 }
 
 // ---- the unfused chain's split steps ------------------------------------------
@@ -610,13 +459,8 @@ __global__ __launch_bounds__(256) void abssum_by_set_partial_kernel(const float 
         for (int k = 0; k < 4; k++) acc[k] += slot == (uint32_t)k ? a : 0.f;
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-        acc[k] = wave_sum(acc[k]);
-        if ((threadIdx.x & 63) == 0) wsum[k][threadIdx.x >> 6] = acc[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < 4)
-        partial[4 * blockIdx.x + threadIdx.x] = (wsum[threadIdx.x][0] + wsum[threadIdx.x][1]) + (wsum[threadIdx.x][2] + wsum[threadIdx.x][3]);
+    for (int k = 0; k < 4; k++) acc[k] = wave_sum(acc[k]);
+    block_fold(acc, wsum, partial + 4 * (size_t)blockIdx.x);
 }
 
 // ---- fused Adam -------------------------------------------------------------
@@ -789,7 +633,7 @@ __global__ __launch_bounds__(256) void sigmoid_bce_kernel(const float *src, floa
     constexpr int NA = Split ? 16 : 4;
     __shared__ float w[16][4];                                          // [value][wave]
     const size_t stride = (size_t)gridDim.x * blockDim.x;
-    float acc[NA];
+    float acc[NA], v[16];
 #pragma unroll
     for (int j = 0; j < NA; j++) acc[j] = 0.f;
     dropout_walk at(q);
@@ -814,14 +658,8 @@ __global__ __launch_bounds__(256) void sigmoid_bce_kernel(const float *src, floa
         at.step(q, step_rows, step_cols);
     }
 #pragma unroll
-    for (int j = 0; j < NA; j++) {
-        acc[j] = wave_sum(acc[j]);
-        if ((threadIdx.x & 63) == 0) w[j][threadIdx.x >> 6] = acc[j];
-    }
-    __syncthreads();
-    if (threadIdx.x < 16)                                               // sixteen values per workgroup, summed by sums_final_kernel<16>
-        partials[16 * blockIdx.x + threadIdx.x] =
-            threadIdx.x < NA ? (w[threadIdx.x][0] + w[threadIdx.x][1]) + (w[threadIdx.x][2] + w[threadIdx.x][3]) : 0.f;
+    for (int j = 0; j < 16; j++) v[j] = j < NA ? wave_sum(acc[j]) : 0.f;    // the plain form's slots 1..3: +0.0
+    block_fold(v, w, partials + 16 * (size_t)blockIdx.x);               // sixteen values per workgroup, summed by sums_final_kernel<16>
 }
 
 // ---- layer normalisation: one row per group of L lanes ------------------------
@@ -941,7 +779,7 @@ __global__ __launch_bounds__(256) void layer_norm_forward_kernel(const float *x,
 // dz = G . leaky_relu'(act) (or G), g = dz . gamma, G_in = rstd (g - mean(g) - xhat mean(g . xhat)); the column sums
 // G_gamma = sum_r dz . xhat and G_beta = sum_r dz without a float atomic: a lane owns its columns for the whole grid-stride
 // loop and sums its rows in registers, the workgroup's 256 / L groups meet in LDS and are added in group order, and one
-// [2 x m] partial per workgroup goes to the scratch, which layer_norm_colsum_final_kernel adds in workgroup order.
+// [2 x m] partial per workgroup goes to the scratch, which colsum_final_kernel (reduce.h) adds in workgroup order.
 template <int V, int L, int K, int R>
 __global__ __launch_bounds__(256) void layer_norm_backward_kernel(const float *G, const float *act, const float *xhat,
                                                                   const float *__restrict__ rstd,
@@ -1024,50 +862,6 @@ __global__ __launch_bounds__(256) void layer_norm_backward_kernel(const float *G
     }
 }
 
-// G_gamma / G_beta = the workgroups' partials added in a fixed order: 64 of the 2 m sums per workgroup, each from four
-// slices (workgroups w, w + 4, ... in order) that meet in LDS.  n_blocks == 0 stores zeros.
-__global__ __launch_bounds__(256) void layer_norm_colsum_final_kernel(const float *__restrict__ partials, unsigned n_blocks,
-                                                                      uint32_t m, float *__restrict__ G_gamma,
-                                                                      float *__restrict__ G_beta) {
-    __shared__ float w[4][64];
-    const uint32_t lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const uint32_t idx = blockIdx.x * 64 + lane, two_m = 2 * m;
-    float s = 0.f;
-    if (idx < two_m) {
-#pragma unroll 8
-        for (unsigned b = slice; b < n_blocks; b += 4) s += partials[(size_t)b * two_m + idx];
-    }
-    w[slice][lane] = s;
-    __syncthreads();
-    if (slice == 0 && idx < two_m) {
-        const float t = (w[0][lane] + w[1][lane]) + (w[2][lane] + w[3][lane]);
-        if (idx < m) G_gamma[idx] = t;
-        else G_beta[idx - m] = t;
-    }
-}
-
-// the backward's partials: [workgroups x 2 x m] floats per (device, stream), grown on first use like abssum_scratch (never
-// on a captured launch path) and freed by mggcn_stream_release_scratch
-struct ln_scratch { float *p = nullptr; size_t floats = 0; };
-std::map<std::pair<int, hipStream_t>, ln_scratch> g_ln_scratch;     // under g_scratch_mu
-
-float *layer_norm_scratch(hipStream_t st, size_t floats) {
-    int dev = 0;
-    MGGCN_CHECK_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_scratch_mu);
-    ln_scratch &s = g_ln_scratch[{dev, st}];
-    if (s.floats < floats) {
-        if (s.p) {
-            MGGCN_CHECK_HIP(hipStreamSynchronize(st));                // an earlier backward may still be summing into it
-            MGGCN_CHECK_HIP(hipFree(s.p));
-            s.p = nullptr; s.floats = 0;
-        }
-        MGGCN_CHECK_HIP(hipMalloc(&s.p, floats * sizeof(float)));
-        s.floats = floats;
-    }
-    return s.p;
-}
-
 template <int L, int R>
 unsigned layer_norm_grid(size_t n_rows) {
     const size_t per_block = (size_t)(256 / L) * R;
@@ -1097,10 +891,6 @@ unsigned layer_norm_grid(size_t n_rows) {
     } while (0)
 
 }  // namespace
-
-// scratch_internal.h: the same per-(device, stream) partials for the column sums of gat.hip (stream order keeps the users
-// apart; released with the layer norm's by mggcn_stream_release_scratch)
-float *colsum_scratch(hipStream_t st, size_t floats) { return layer_norm_scratch(st, floats); }
 
 // ============================ C ABI =========================================
 MGGCN_API void mggcn_leaky_relu_forward_f32(mggcn_stream_t stream, const float *in, float *out,
@@ -1294,14 +1084,14 @@ MGGCN_API void mggcn_layer_norm_backward_f32(mggcn_stream_t stream, const float 
     const hipStream_t st = as_stream(stream);
     const unsigned final_grid = (unsigned)((2 * m + 63) / 64);
     if (!n_rows) {                                                    // the sums over no rows
-        hipLaunchKernelGGL(layer_norm_colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, nullptr, 0u, (uint32_t)m,
-                           G_gamma, G_beta);
+        hipLaunchKernelGGL(colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, nullptr, 0u, 2 * (uint32_t)m, G_gamma,
+                           G_beta, (uint32_t)m);
         MGGCN_CHECK_LAUNCH();
         return;
     }
     MGGCN_REQUIRE(G != nullptr && G_in != nullptr && (!leaky || act != nullptr), "layer norm backward: null operand");
     const bool vec = m % 4 == 0 && aligned16(G) && aligned16(xhat) && aligned16(G_in) && aligned16(gamma) && (!leaky || aligned16(act));
-    float *partials = layer_norm_scratch(st, (size_t)kLayerNormBlocks * 2 * m);
+    float *partials = stream_scratch(st, scratch_kind::colsums, (size_t)kLayerNormBlocks * 2 * m);
     unsigned grid = 0;
 #define MGGCN_LN_BWD(V, L, K, R)                                                                                         \
     hipLaunchKernelGGL((layer_norm_backward_kernel<V, L, K, R>), dim3(grid = layer_norm_grid<L, R>(n_rows)), dim3(256), 0,  \
@@ -1309,46 +1099,18 @@ MGGCN_API void mggcn_layer_norm_backward_f32(mggcn_stream_t stream, const float 
     MGGCN_LN_DISPATCH(MGGCN_LN_BWD, vec, m);
 #undef MGGCN_LN_BWD
     MGGCN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(layer_norm_colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, partials, grid, (uint32_t)m,
-                       G_gamma, G_beta);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, partials, grid, 2 * (uint32_t)m, G_gamma,
+                       G_beta, (uint32_t)m);
     MGGCN_CHECK_LAUNCH();
-}
-
-// The reduction scratch above belongs to a (device, stream) pair: mggcn_stream_destroy releases it with the stream;
-// a host layer whose streams come from elsewhere (torch) calls this when it drops a stream, so that a recycled
-// stream handle never inherits a buffer another stream may still be using, and nothing accumulates.
-MGGCN_API void mggcn_stream_release_scratch(mggcn_stream_t stream) {
-    // by STREAM alone, whatever device is current on the calling thread (a stream handle belongs to one device; a context
-    // may be dropped from a thread that has another device current -- the entry must still be found, or a recycled handle
-    // inherits the buffer)
-    std::vector<std::pair<int, float *>> mine;
-    {
-        std::lock_guard<std::mutex> lock(g_scratch_mu);
-        for (auto it = g_scratch.begin(); it != g_scratch.end();)
-            if (it->first.second == as_stream(stream)) { mine.push_back({it->first.first, it->second}); it = g_scratch.erase(it); }
-            else ++it;
-        for (auto it = g_ln_scratch.begin(); it != g_ln_scratch.end();)          // the layer-norm backward's partials
-            if (it->first.second == as_stream(stream)) { mine.push_back({it->first.first, it->second.p}); it = g_ln_scratch.erase(it); }
-            else ++it;
-    }
-    if (mine.empty()) return;
-    int prev = 0;
-    MGGCN_CHECK_HIP(hipGetDevice(&prev));
-    for (const auto &m : mine) {
-        MGGCN_CHECK_HIP(hipSetDevice(m.first));
-        MGGCN_CHECK_HIP(hipStreamSynchronize(as_stream(stream)));      // nobody may still be summing into it
-        MGGCN_CHECK_HIP(hipFree(m.second));
-    }
-    MGGCN_CHECK_HIP(hipSetDevice(prev));
 }
 
 MGGCN_API void mggcn_abssum_f32(mggcn_stream_t stream, const float *A, size_t size, float *result_device) {
     MGGCN_REQUIRE(result_device != nullptr, "null result pointer");
-    float *scratch = abssum_scratch(as_stream(stream));
+    float *scratch = sums_scratch<1, kAsumBlocks>(as_stream(stream));
     const unsigned blocks = std::min<unsigned>(kAsumBlocks, stream_grid(size ? size : 1));
     hipLaunchKernelGGL(abssum_partial_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), A, size, scratch);
     MGGCN_CHECK_LAUNCH();
-    hipLaunchKernelGGL(abssum_final_kernel, dim3(1), dim3(256), 0, as_stream(stream), scratch, blocks,
+    hipLaunchKernelGGL((sums_final_kernel<1, false>), dim3(1), dim3(256), 0, as_stream(stream), scratch, blocks,
                        result_device);
     MGGCN_CHECK_LAUNCH();
 }
@@ -1357,21 +1119,13 @@ namespace {
 // Both forms of the fused loss: the same grid, dispatch on KE / K / R and final tree; Split adds S and train_set to the
 // kernel and four pairs instead of one to the partials.
 template <bool Split>
-void xent_final(hipStream_t st, const float *partials, unsigned n_blocks, float *sums_device) {
-    if constexpr (Split)
-        hipLaunchKernelGGL((sums_final_kernel<8, true>), dim3(1), dim3(256), 0, st, partials, n_blocks, sums_device);
-    else
-        hipLaunchKernelGGL(xent_final_kernel, dim3(1), dim3(256), 0, st, partials, n_blocks, sums_device);
-    MGGCN_CHECK_LAUNCH();
-}
-
-template <bool Split>
 void launch_xent(hipStream_t st, const float *logits, float *G, const int32_t *Y, const int32_t *S, size_t n_rows, size_t m,
                  int32_t train_set, float grad_scale, float *sums_device) {
+    constexpr int NV = 2 * xent_slots(Split);
     const dim3 block(256);
-    float *partials = abssum_scratch(st);        // per (device, stream); stream order keeps its users apart
+    float *partials = sums_scratch<NV, kXentBlocks>(st);     // stream order keeps its users apart
+    const dim3 grid(stream_grid(n_rows * (m <= 64 ? 16 : 64)));
     if (m <= 64) {                               // one row per 16-lane group
-        const dim3 grid(stream_grid(n_rows * 16));
 #define MGGCN_XENT16(KE)                                                                                          \
     hipLaunchKernelGGL((softmax_xent_rows16_kernel<KE, 4, Split>), grid, block, 0, st, logits, G, Y, n_rows, (uint32_t)m, \
                        grad_scale, partials, S, train_set)
@@ -1380,23 +1134,21 @@ void launch_xent(hipStream_t st, const float *logits, float *G, const int32_t *Y
         else if (m <= 48) MGGCN_XENT16(3);
         else MGGCN_XENT16(4);
 #undef MGGCN_XENT16
-        MGGCN_CHECK_LAUNCH();
-        xent_final<Split>(st, partials, grid.x, sums_device);
-        return;
-    }
-    // (tried on the wave-per-row form: two workgroups per CU to thin out the two contended scalar atomics at the end of
-    //  every workgroup -- 105 -> 145 us: the pass wants the occupancy)
-    const dim3 grid(stream_grid(n_rows * 64));
+    } else {
+        // (tried on the wave-per-row form: two workgroups per CU to thin out the two contended scalar atomics at the end
+        //  of every workgroup -- 105 -> 145 us: the pass wants the occupancy)
 #define MGGCN_XENT(K, R)                                                                                     \
     hipLaunchKernelGGL((softmax_xent_fused_kernel<K, R, Split>), grid, block, 0, st, logits, G, Y, n_rows, m, grad_scale, \
                        partials, S, train_set)
-    if (m <= 128) MGGCN_XENT(2, 4);
-    else if (m <= 256) MGGCN_XENT(4, 2);
-    else if (m <= 512) MGGCN_XENT(8, 1);
-    else MGGCN_XENT(16, 1);
+        if (m <= 128) MGGCN_XENT(2, 4);
+        else if (m <= 256) MGGCN_XENT(4, 2);
+        else if (m <= 512) MGGCN_XENT(8, 1);
+        else MGGCN_XENT(16, 1);
 #undef MGGCN_XENT
+    }
     MGGCN_CHECK_LAUNCH();
-    xent_final<Split>(st, partials, grid.x, sums_device);
+    hipLaunchKernelGGL((sums_final_kernel<NV, true>), dim3(1), dim3(256), 0, st, partials, grid.x, sums_device);
+    MGGCN_CHECK_LAUNCH();
 }
 }  // namespace
 
@@ -1423,7 +1175,7 @@ namespace {
 template <bool Split>
 void launch_bce(hipStream_t st, const float *logits, float *G, const int32_t *T, const int32_t *S, size_t n_rows, size_t m,
                 int32_t train_set, float grad_scale, float *sums_device) {
-    float *partials = abssum_scratch(st);        // per (device, stream); 16 floats per workgroup of a grid of <= kXentBlocks
+    float *partials = sums_scratch<16, kXentBlocks>(st);
     const bool vec = m % 4 == 0 && aligned16(logits) && aligned16(G) && aligned16(T);
     const size_t q = vec ? m / 4 : m, units = n_rows * q;
     const unsigned grid = stream_grid(units);
@@ -1447,7 +1199,6 @@ MGGCN_API void mggcn_sigmoid_bce_from_f32(mggcn_stream_t stream, const float *lo
     MGGCN_REQUIRE(m >= 1, "sigmoid-BCE loss: the width must be positive");
     MGGCN_REQUIRE(train_set >= 0 && train_set <= 2, "train_set must be 0 (train), 1 (validation) or 2 (test)");
     MGGCN_REQUIRE(logits != nullptr && G != nullptr && T != nullptr && sums_device != nullptr, "sigmoid-BCE loss: null operand");
-    static_assert(16u * kXentBlocks <= kScratchFloats, "sixteen partials per workgroup of the capped grid");
     if (S) launch_bce<true>(as_stream(stream), logits, G, T, S, n_rows, m, train_set, grad_scale, sums_device);
     else launch_bce<false>(as_stream(stream), logits, G, T, nullptr, n_rows, m, train_set, grad_scale, sums_device);
 }
@@ -1465,7 +1216,7 @@ MGGCN_API void mggcn_select_rows_by_set_f32(mggcn_stream_t stream, float *mat, c
 MGGCN_API void mggcn_abssum_by_set_f32(mggcn_stream_t stream, const float *x, const int32_t *S, size_t n,
                                        float *result_device) {
     MGGCN_REQUIRE(result_device != nullptr && (!n || (x != nullptr && S != nullptr)), "abssum_by_set: null operand");
-    float *scratch = abssum_scratch(as_stream(stream));
+    float *scratch = sums_scratch<4, kAsumBlocks>(as_stream(stream));
     const unsigned blocks = std::min<unsigned>(kAsumBlocks, stream_grid(n ? n : 1));
     hipLaunchKernelGGL(abssum_by_set_partial_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), x, S, n, scratch);
     MGGCN_CHECK_LAUNCH();

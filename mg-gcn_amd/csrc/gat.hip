@@ -22,22 +22,13 @@
 #include <cmath>
 
 #include "common.h"
+#include "reduce.h"
 #include "scratch_internal.h"
 
 namespace {
 
 constexpr unsigned kGatColsumBlocks = kNumCU * 2;      // grid cap of the G_att partial pass = rows of partials in the scratch
 
-__device__ __forceinline__ float wave_sum(float v) {   // xor butterfly: every lane ends with the same bits
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-    return v;
-}
 // sum over the lanes of a group (offsets below lpr) / over the groups (offsets from lpr up)
 __device__ __forceinline__ float group_sum(float v, uint32_t lpr) {
     for (uint32_t off = 1; off < lpr; off <<= 1) v += __shfl_xor(v, off);
@@ -368,7 +359,7 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
 // ---------------------------------------------------------------------------
 // G_att[0, c] = sum_i ds_dst[i, k(c)] Z_dst[i, c],  G_att[1, c] = sum_j ds_src[j, k(c)] Z_src[j, c]
 // A workgroup walks rows blockIdx * R + rr, + gridDim * R, ... (R = 256 / tpr rows at a time, tpr threads per row), folds its R
-// row slots in LDS in slot order and stores one [2 x width] partial; gat_colsum_final_kernel adds the partials in
+// row slots in LDS in slot order and stores one [2 x width] partial; colsum_final_kernel (reduce.h) adds the partials in
 // workgroup order.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gat_scores_backward_kernel(const float *__restrict__ ds_dst, const float *__restrict__ Zd,
@@ -401,23 +392,6 @@ __global__ __launch_bounds__(256) void gat_scores_backward_kernel(const float *_
             __syncthreads();
         }
     }
-}
-
-// G_att[idx] = the workgroups' partials added in a fixed order (four slices b, b + 4, ... that meet in LDS), as
-// layer_norm_colsum_final_kernel does.  n_blocks == 0 stores zeros.
-__global__ __launch_bounds__(256) void gat_colsum_final_kernel(const float *__restrict__ partials, unsigned n_blocks,
-                                                               uint32_t two_w, float *__restrict__ G_att) {
-    __shared__ float w[4][64];
-    const uint32_t lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const uint32_t idx = blockIdx.x * 64 + lane;
-    float s = 0.f;
-    if (idx < two_w) {
-#pragma unroll 8
-        for (unsigned b = slice; b < n_blocks; b += 4) s += partials[(size_t)b * two_w + idx];
-    }
-    w[slice][lane] = s;
-    __syncthreads();
-    if (slice == 0 && idx < two_w) G_att[idx] = (w[0][lane] + w[1][lane]) + (w[2][lane] + w[3][lane]);
 }
 
 uint32_t ceil_log2(uint32_t x) {
@@ -556,11 +530,12 @@ MGGCN_API void mggcn_gat_scores_backward_f32(mggcn_stream_t stream, const float 
         const uint32_t tl = std::min(ceil_log2(width), 8u);            // threads per row: the power of two covering the width, <= 256
         const size_t R = 256u >> tl;
         grid = (unsigned)std::min<size_t>((n + R - 1) / R, kGatColsumBlocks);
-        partials = colsum_scratch(st, (size_t)kGatColsumBlocks * 2 * width);
+        partials = stream_scratch(st, scratch_kind::colsums, (size_t)kGatColsumBlocks * 2 * width);
         hipLaunchKernelGGL(gat_scores_backward_kernel, dim3(grid), dim3(256), 0, st, ds_dst, Z_dst, ldzd, n_dst, ds_src, Z_src,
                            ldzs, n_src, K, dh, tl, partials);
         MGGCN_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(gat_colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, partials, grid, 2 * width, G_att);
+    hipLaunchKernelGGL(colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, partials, grid, 2 * width, G_att, G_att + width,
+                       width);
     MGGCN_CHECK_LAUNCH();
 }

@@ -3,8 +3,13 @@
 // cuda_malloc helpers (src/mg_gcn.hpp:74-90).  Thin on purpose: the host layers
 // (C++ headers, Python mirror) own all policy.
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <tuple>
+#include <vector>
 
 #include "common.h"
+#include "scratch_internal.h"
 
 MGGCN_API int mggcn_abi_version(void) { return MGGCN_ABI_VERSION; }
 
@@ -36,9 +41,58 @@ MGGCN_API mggcn_stream_t mggcn_stream_create(int high_priority) {
     return s;
 }
 
+// ---- the reduction scratch (scratch_internal.h) -----------------------------
+namespace {
+struct scratch_buffer { float *p = nullptr; size_t floats = 0; };
+std::mutex g_scratch_mu;
+std::map<std::tuple<int, hipStream_t, scratch_kind>, scratch_buffer> g_scratch;     // under g_scratch_mu
+}  // namespace
+
+float *stream_scratch(hipStream_t st, scratch_kind kind, size_t floats) {
+    int dev = 0;
+    MGGCN_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_scratch_mu);
+    scratch_buffer &s = g_scratch[{dev, st, kind}];
+    if (s.floats < floats) {
+        if (s.p) {
+            MGGCN_CHECK_HIP(hipStreamSynchronize(st));                // an earlier kernel may still be summing into it
+            MGGCN_CHECK_HIP(hipFree(s.p));
+            s.p = nullptr; s.floats = 0;
+        }
+        MGGCN_CHECK_HIP(hipMalloc(&s.p, floats * sizeof(float)));
+        s.floats = floats;
+    }
+    return s.p;
+}
+
+// The scratch belongs to a (device, stream) pair: mggcn_stream_destroy releases it with the stream; a host layer whose
+// streams come from elsewhere (torch) calls this when it drops a stream, so that a recycled stream handle never inherits a
+// buffer another stream may still be using, and nothing accumulates.
+MGGCN_API void mggcn_stream_release_scratch(mggcn_stream_t stream) {
+    // by STREAM alone, whatever device is current on the calling thread (a stream handle belongs to one device; a context
+    // may be dropped from a thread that has another device current -- the entry must still be found, or a recycled handle
+    // inherits the buffer)
+    std::vector<std::pair<int, float *>> mine;
+    {
+        std::lock_guard<std::mutex> lock(g_scratch_mu);
+        for (auto it = g_scratch.begin(); it != g_scratch.end();)
+            if (std::get<1>(it->first) == as_stream(stream)) { mine.push_back({std::get<0>(it->first), it->second.p}); it = g_scratch.erase(it); }
+            else ++it;
+    }
+    if (mine.empty()) return;
+    int prev = 0;
+    MGGCN_CHECK_HIP(hipGetDevice(&prev));
+    for (const auto &m : mine) {
+        MGGCN_CHECK_HIP(hipSetDevice(m.first));
+        MGGCN_CHECK_HIP(hipStreamSynchronize(as_stream(stream)));      // nobody may still be summing into it
+        MGGCN_CHECK_HIP(hipFree(m.second));
+    }
+    MGGCN_CHECK_HIP(hipSetDevice(prev));
+}
+
 MGGCN_API void mggcn_stream_destroy(mggcn_stream_t stream) {
     if (!stream) return;
-    mggcn_stream_release_scratch(stream);                  // per-stream reduction scratch (elementwise.hip)
+    mggcn_stream_release_scratch(stream);
     MGGCN_CHECK_HIP(hipStreamDestroy(as_stream(stream)));
 }
 
