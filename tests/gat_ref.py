@@ -11,7 +11,11 @@ F is a CSR pattern of n destinations x n_src sources; head k owns columns [k dh,
     ds = alpha (dalpha - D[i, k]) (x > 0 ? 1 : slope);  ds_dst[i, k] = sum_j ds;  ds_src[j, k] = sum_i ds
     G_Z[j, head k] = sum_i alpha G[i, head k] + ds_dst[j, k] att[0, head k] + ds_src[j, k] att[1, head k]
     G_att[0] = sum_i ds_dst[i, k(c)] Z_dst[i, c];  G_att[1] = sum_j ds_src[j, k(c)] Z[j, c]
-In the square case Z_dst is Z; a rectangular block has its own Z_dst and no ds_dst term in G_Z."""
+In the square case Z_dst is Z; a rectangular block has its own Z_dst and no ds_dst term in G_Z.
+
+For test_gpu_gat_edges.py: the row-scaled measure (rowdist, attention(scales=True)) and its bar ROW_TOL, the graph that is
+long on both sides, the shapes that reach every kernel variant, and the crafted-scalar cases (position probes, the running
+maximum under stress) through attention()'s injectable s_dst, s_src, lse and D."""
 import numpy as np
 
 SLOPE = 0.2
@@ -24,6 +28,29 @@ def relerr(got, want):
     """the matrix-normalised distance of test_gpu_gcn.py"""
     got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
     return float(np.abs(got - want).max() / (np.abs(want).max() + 1e-30))
+
+
+def rowdist(got, want, scale):
+    """per row, max over its columns of |got - want| / scale, where ``scale`` (same shape, fp64, from attention(scales=True))
+    is the magnitude the terms of that element add up to: a long row's output is small next to the matrix maximum, and a
+    cancelling one (ds_dst of a one-entry row) is small next to its own terms, so neither the matrix nor the element itself
+    is the yardstick.  An element whose scale is 0 has no terms (an empty row, an unreferenced column): it must match
+    exactly, and counts as inf where it does not."""
+    want = np.asarray(want, dtype=np.float64)
+    got, scale = np.asarray(got, dtype=np.float64).reshape(want.shape), np.asarray(scale, dtype=np.float64).reshape(want.shape)
+    diff = np.abs(got - want)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        q = np.where(scale > 0, diff / scale, np.where(diff == 0, 0.0, np.inf))
+    return q.reshape(want.shape[0], -1).max(axis=1) if want.size else np.zeros(want.shape[0])
+
+
+def rowerr(got, want, scale):
+    """(worst row, its rowdist)"""
+    q = rowdist(got, want, scale)
+    if not q.size:
+        return -1, 0.0
+    i = int(np.argmax(q))
+    return i, float(q[i])
 
 
 # ---- the kernel-test graph -------------------------------------------------------------------------------------------------------
@@ -49,6 +76,108 @@ def kernel_graph(n=320, n_src=320, seed=3):
     indices[b + 1] = indices[b]
     assert UNREFERENCED not in indices
     return indptr, np.ascontiguousarray(indices, dtype=np.uint32)
+
+
+LONG_ROWS = {0: 0, 1: 1, 2: 63, 3: 64, 4: 65, 5: 127, 6: 128, 7: 129, 8: 191, 9: 192, 10: 193, 11: 1000, 12: 4097}
+LONG_DUPLICATE_ROW = 13
+
+
+def kernel_graph_long(n=320, seed=5):
+    """the square pattern whose rows AND (through transpose_pattern) columns are long: rows 0..12 of LONG_ROWS entries -- one
+    on either side of one, two and three 64-entry chunks, so that the index prefetch (two chunks ahead) and the scalar
+    prefetch (one ahead) both meet a boundary --, row 13 with one column twice, the last row empty, every other row of
+    1..8 entries; random columns, none of them UNREFERENCED.  As F its transpose has rows of ~25 entries and no entry in
+    row UNREFERENCED, and F^T holds the long rows, which is what backward_src walks."""
+    rng = np.random.default_rng(seed)
+    lens = rng.integers(1, 9, size=n)
+    for r, l in LONG_ROWS.items():
+        lens[r] = l
+    lens[LONG_DUPLICATE_ROW] = 3
+    lens[n - 1] = 0
+    allowed = np.array([c for c in range(n) if c != UNREFERENCED], dtype=np.uint32)
+    indptr = np.zeros(n + 1, dtype=np.uint32)
+    indptr[1:] = np.cumsum(lens)
+    indices = allowed[rng.integers(0, allowed.size, size=int(indptr[-1]))]
+    b = int(indptr[LONG_DUPLICATE_ROW])
+    indices[b + 1] = indices[b]
+    return indptr, np.ascontiguousarray(indices, dtype=np.uint32)
+
+
+PROBE_ROWS = (64, 65, 129, 193, 4097)
+
+
+def probe_block(seed=9):
+    """(indptr, indices, n_src) of the 5 x 4548 block of the position probes: rows of PROBE_ROWS entries, every source in
+    exactly one row and exactly once, in a shuffled order -- so a scalar attached to a source is attached to one (row,
+    position), and every row carries its own crafted scores in one call"""
+    n_src = sum(PROBE_ROWS)
+    indptr = np.zeros(len(PROBE_ROWS) + 1, dtype=np.uint32)
+    indptr[1:] = np.cumsum(PROBE_ROWS)
+    indices = np.random.default_rng(seed).permutation(n_src).astype(np.uint32)
+    return indptr, indices, n_src
+
+
+def probe_positions(L):
+    """the positions of a row of L entries that sit at a chunk edge or at the row's end"""
+    return sorted({p for p in (0, 63, 64, 127, 128, L - 2, L - 1) if 0 <= p < L})
+
+
+PROBE_SLOTS = 7
+
+
+def probe_hot(t):
+    """slot t of PROBE_SLOTS: per row of the probe block the position probed (the row's t-th of probe_positions, its last
+    where it has fewer) and the source sitting there"""
+    indptr, indices, _ = probe_block()
+    pos = [probe_positions(L)[min(t, len(probe_positions(L)) - 1)] for L in PROBE_ROWS]
+    return pos, np.array([indices[int(indptr[r]) + p] for r, p in enumerate(pos)], dtype=np.int64)
+
+
+STRESS_KINDS = ("ascending", "descending", "constant", "late peak")
+
+
+def stress_scores(kind, K):
+    """s_src [n_src x K] of the probe block (s_dst is 0, so these are the scores x themselves, exact in fp32), by position
+    along each row: ascending from -80 to +80 (the running maximum moves on every chunk and the early chunks underflow),
+    descending (the maximum is the first entry's: the rescale factor is exactly 1 from the second chunk on), constant
+    (1 throughout), and -80 everywhere but +80 at the row's last entry"""
+    indptr, indices, n_src = probe_block()
+    s = np.zeros(n_src, dtype=np.float32)
+    for r, L in enumerate(PROBE_ROWS):
+        ramp = np.linspace(-80.0, 80.0, L)
+        v = {"ascending": ramp, "descending": ramp[::-1], "constant": np.full(L, 7.5),
+             "late peak": np.concatenate([np.full(L - 1, -80.0), [80.0]])}[kind]
+        s[indices[int(indptr[r]):int(indptr[r + 1])]] = v
+    return np.repeat(s[:, None], K, axis=1)
+
+
+# ---- mutations of the pattern: what an off-by-one in a kernel's chunk loop would compute ---------------------------------------------
+def long_row_positions(indptr, which):
+    """entry numbers (into indices) of one position in every row of 65 or more entries: "last" -- the row's last entry,
+    "chunk" -- the first entry of its last 64-entry chunk, "p63" -- position 63"""
+    ip = indptr.astype(np.int64)
+    rows = np.nonzero(np.diff(ip) >= 65)[0]
+    L = np.diff(ip)[rows]
+    pos = {"last": L - 1, "chunk": 64 * ((L - 1) // 64), "p63": np.full_like(L, 63)}[which]
+    return rows, ip[rows] + pos
+
+
+def without_entries(indptr, indices, drop):
+    keep = np.ones(indices.size, dtype=bool)
+    keep[drop] = False
+    rows = np.repeat(np.arange(indptr.size - 1), np.diff(indptr.astype(np.int64)))
+    ip = np.zeros(indptr.size, dtype=np.uint32)
+    ip[1:] = np.cumsum(np.bincount(rows[keep], minlength=indptr.size - 1))
+    return ip, np.ascontiguousarray(indices[keep])
+
+
+def swapped_scores(indptr, indices):
+    """score_cols for attention(): every row of 65 or more entries uses at position 63 the score of position 64's source and
+    the other way round (the entries still gather their own sources)"""
+    _, e = long_row_positions(indptr, "p63")
+    sc = indices.astype(np.int64).copy()
+    sc[e], sc[e + 1] = sc[e + 1].copy(), sc[e].copy()
+    return sc
 
 
 def transpose_pattern(indptr, indices, n_src):
@@ -91,8 +220,13 @@ def _segmax(vals, indptr):
     return out
 
 
-def attention(indptr, indices, Z, att, K, G=None, Z_dst=None, slope=SLOPE, dtype=np.float64):
-    """every quantity of NAMES (those of the backward pass when G is given) in ``dtype`` arithmetic, unrounded"""
+def attention(indptr, indices, Z, att, K, G=None, Z_dst=None, slope=SLOPE, dtype=np.float64, s_dst=None, s_src=None, lse=None,
+              D=None, score_cols=None, scales=False):
+    """every quantity of NAMES (those of the backward pass when G is given) in ``dtype`` arithmetic, unrounded.
+    ``s_dst``, ``s_src``, ``lse`` and ``D`` replace the intermediates of the same name, so that one entry point of the C ABI
+    can be mirrored with crafted scalars (each stage reads them as operands); ``score_cols`` names the source whose score
+    an entry uses, where that is not the source it gathers (a mutation the CPU tests apply).  With ``scales`` the result
+    has "scale": per output the magnitude its terms add up to (see rowerr)."""
     T = dtype
     n, n_src, d = indptr.size - 1, Z.shape[0], Z.shape[1]
     dh = d // K
@@ -103,23 +237,30 @@ def attention(indptr, indices, Z, att, K, G=None, Z_dst=None, slope=SLOPE, dtype
     rows = np.repeat(np.arange(n), np.diff(indptr.astype(np.int64)))
     cols = indices.astype(np.int64)
     r = {}
-    s_dst = (Zd3 * a3[0]).sum(axis=2, dtype=T)
-    s_src = (Z3 * a3[1]).sum(axis=2, dtype=T)
-    x = s_dst[rows] + s_src[cols]
+    s_dst = (Zd3 * a3[0]).sum(axis=2, dtype=T) if s_dst is None else np.asarray(s_dst, dtype=T).reshape(n, K)
+    s_src = (Z3 * a3[1]).sum(axis=2, dtype=T) if s_src is None else np.asarray(s_src, dtype=T).reshape(n_src, K)
+    x = s_dst[rows] + s_src[cols if score_cols is None else np.asarray(score_cols, dtype=np.int64)]
     e = np.where(x > 0, x, T(slope) * x)
-    m = _segmax(e, indptr)
-    empty = np.diff(indptr.astype(np.int64)) == 0
-    m[empty] = 0
-    ssum = _segsum(np.exp(e - m[rows]), indptr)
-    ssum[empty] = 1
-    lse = (m + np.log(ssum)).astype(T)
+    if lse is None:
+        m = _segmax(e, indptr)
+        empty = np.diff(indptr.astype(np.int64)) == 0
+        m[empty] = 0
+        ssum = _segsum(np.exp(e - m[rows]), indptr)
+        ssum[empty] = 1
+        lse = (m + np.log(ssum)).astype(T)
+    else:
+        lse = np.asarray(lse, dtype=T).reshape(n, K)
     alpha = np.exp(e - lse[rows])
     out = _segsum(alpha[:, :, None] * Z3[cols], indptr)
     r.update(s_dst=s_dst, s_src=s_src, out=out.reshape(n, d), lse=lse, alpha=alpha)
+    if scales:
+        sc = r["scale"] = dict(s_dst=np.abs(Zd3 * a3[0]).sum(axis=2), s_src=np.abs(Z3 * a3[1]).sum(axis=2),
+                               out=_segsum(alpha[:, :, None] * np.abs(Z3)[cols], indptr).reshape(n, d),
+                               lse=np.maximum(np.abs(lse), 1))
     if G is None:
         return r
     G3 = np.asarray(G, dtype=T).reshape(n, K, dh)
-    D = (G3 * out).sum(axis=2, dtype=T)
+    D = (G3 * out).sum(axis=2, dtype=T) if D is None else np.asarray(D, dtype=T).reshape(n, K)
     dalpha = (G3[rows] * Z3[cols]).sum(axis=2, dtype=T)
     ds = alpha * (dalpha - D[rows]) * np.where(x > 0, T(1), T(slope))
     ds_dst = _segsum(ds, indptr)
@@ -133,19 +274,182 @@ def attention(indptr, indices, Z, att, K, G=None, Z_dst=None, slope=SLOPE, dtype
     G_Z = G_Z + ds_src[:, :, None] * a3[1]
     G_att = np.stack([(ds_dst[:, :, None] * Zd3).sum(axis=0, dtype=T), (ds_src[:, :, None] * Z3).sum(axis=0, dtype=T)])
     r.update(D=D, ds_dst=ds_dst, ds_src=ds_src, G_Z=G_Z.reshape(n_src, d), G_att=G_att.reshape(2, d))
+    if scales:
+        w = alpha * (np.abs(dalpha) + np.abs(D[rows])) * np.where(x > 0, T(1), T(slope))
+        sd, ss = _segsum(w, indptr), _segsum(w[order], t_indptr)
+        gz = _segsum((alpha[:, :, None] * np.abs(G3[rows]))[order], t_indptr) + ss[:, :, None] * np.abs(a3[1])
+        if square:
+            gz = gz + sd[:, :, None] * np.abs(a3[0])
+        ga = np.stack([(sd[:, :, None] * np.abs(Zd3)).sum(axis=0), (ss[:, :, None] * np.abs(Z3)).sum(axis=0)])
+        sc.update(D=np.abs(G3 * out).sum(axis=2), ds_dst=sd, ds_src=ss, G_Z=gz.reshape(n_src, d), G_att=ga.reshape(2, d))
     return r
 
 
 def restate64(*a, exact=False, **kw):
     """the fp64 restatement: fp64 arithmetic on the fp32 inputs, rounded to fp32 at the end (exact: left in fp64)"""
     r = attention(*a, dtype=np.float64, **kw)
-    return r if exact else {k: v.astype(np.float32) for k, v in r.items()}
+    return r if exact else {k: v.astype(np.float32) for k, v in r.items() if k != "scale"}
 
 
 def twin32(*a, **kw):
     """the fp32 twin: the same formulas with every operation in fp32"""
     with np.errstate(over="ignore"):
         return {k: v.astype(np.float32) for k, v in attention(*a, dtype=np.float32, **kw).items()}
+
+
+# ---- the shapes that reach every template variant of the three sparse kernels ------------------------------------------------------
+def head_geometry_for(dh, vec):
+    """csrc/gat.hip head_geometry_for and MGGCN_GAT_DISPATCH restated: ((VEC, NT, U), nt) -- the compiled variant and the
+    number of column tiles the call really uses"""
+    units = dh // 4 if vec else dh
+    lg = min(max(units - 1, 0).bit_length(), 6)
+    nt = (units + (1 << lg) - 1) >> lg
+    if vec:
+        return ((4, 1, 4) if nt == 1 else (4, 4, 1)), nt
+    return ((1, 1, 4) if nt == 1 else (1, 4, 2) if nt <= 4 else (1, 16, 1)), nt
+
+
+# (K, dh): the variant on aligned operands (float4 path iff dh % 4 == 0); lanes per head-row x tiles
+EDGE_SHAPES = [
+    (4, 32),        # (4,1,4)  nt 1: 8 lanes, all used
+    (4, 12),        # (4,1,4)  nt 1: 3 of 4 lanes of a group
+    (2, 20),        # (4,1,4)  nt 1: 5 of 8 lanes
+    (1, 100),       # (4,1,4)  nt 1: 25 of 32 lanes
+    (1, 260),       # (4,4,1)  nt 2: 65 float4 over 64 lanes, the second tile one lane wide
+    (2, 512),       # (4,4,1)  nt 2: both tiles full
+    (1, 772),       # (4,4,1)  nt 4: 193 float4, the last tile one lane wide
+    (1, 1024),      # (4,4,1)  nt 4: the widest call, all tiles full
+    (3, 7),         # (1,1,4)  nt 1: 7 of 8 lanes
+    (2, 65),        # (1,4,2)  nt 2
+    (1, 130),       # (1,4,2)  nt 3: the last tile two lanes wide
+    (1, 255),       # (1,4,2)  nt 4: the last tile one lane short
+    (1, 257),       # (1,16,1) nt 5: the last tile one lane wide
+    (3, 341),       # (1,16,1) nt 6, three heads, 1023 columns
+    (1, 1023),      # (1,16,1) nt 16: the last tile one lane short
+]
+EDGE_MISALIGNED = [(1, 1024), (2, 512)]         # offset = 1, pad = 3: the same widths on the element path, (1,16,1) nt 16 and 8
+EDGE_RECT = [(4, 32), (1, 260), (3, 7), (1, 130), (1, 257)]     # one shape per variant on the 200 x 320 block
+
+# The row-scaled bar.  Largest rowdist of the fp32 twin from the exact restatement over every case of edge_cases(), measured
+# on the CPU (test_gat_cpu.py prints them): TWIN_ROW_MEASURED; the bar is 8 x that, rounded up -- the twin sums in numpy's
+# pairwise order, the kernels in lane-group order over up to 4097 terms.  Fixed before any device run.  Worst distances over
+# the 35 cases, twin / MI355X (DESIGN.md 3.10 has the table): s_dst 1.7e-7 / 1.2e-7, s_src 1.7e-7 / 1.3e-7, out 7.0e-7 / 1.3e-6,
+# lse 1.9e-7 / 2.3e-7, D 5.1e-7 / 5.8e-7, ds_dst 3.9e-6 / 1.7e-5, ds_src 9.9e-6 / 3.3e-6, G_Z 1.1e-6 / 3.1e-6,
+# G_att 1.2e-7 / 2.3e-7.  The worst are short rows whose ds nearly cancels, not the long ones.
+TWIN_ROW_MEASURED = 9.87e-6     # ds_src, row 16 of ("longT", 4, 32)
+ROW_TOL = 8e-5
+
+
+def edge_graphs():
+    g = kernel_graph_long()
+    return {"long": g + (320,), "longT": transpose_pattern(*g, 320) + (320,), "rect": kernel_graph(200, 320) + (320,)}
+
+
+def edge_cases():
+    """(graph name, K, dh) of every case the row-scaled bar is measured over and the device runs"""
+    return ([(g, K, dh) for g in ("long", "longT") for K, dh in EDGE_SHAPES] + [("rect", K, dh) for K, dh in EDGE_RECT])
+
+
+_cases = {}
+
+
+def edge_case(name, K, dh):
+    """inputs, the exact restatement with its row scales, and the twin of one case; computed once per process"""
+    key = (name, K, dh)
+    if key not in _cases:
+        indptr, indices, n_src = edge_graphs()[name]
+        n = indptr.size - 1
+        # att shrinks with sqrt(dh) beyond dh = 32, so that the scores keep the spread they have there: with a fixed 0.1 a
+        # head of 1024 columns has scores of +-10, the softmax of a 4097-entry row sits on a handful of entries, and an
+        # entry lost at the row's tail would move nothing
+        Z, Z_dst, G, att = tolerance_inputs(n, n_src, K, dh, att_scale=0.1 * min(1.0, (32.0 / dh) ** 0.5))
+        Zd = None if n == n_src else Z_dst
+        want = restate64(indptr, indices, Z, att, K, G=G, Z_dst=Zd, exact=True, scales=True)
+        twin = twin32(indptr, indices, Z, att, K, G=G, Z_dst=Zd)
+        _cases[key] = dict(indptr=indptr, indices=indices, n_src=n_src, Z=Z, Z_dst=Zd, G=G, att=att, want=want,
+                           scale=want["scale"], twin=twin)
+    return _cases[key]
+
+
+def alpha_row_sums(indptr, indices, s_src, lse, slope=SLOPE):
+    """sum_j alpha_ijk per (row, head) in fp64 from the scores (s_dst = 0) and a given lse: 1 where lse is right"""
+    x = np.asarray(s_src, dtype=np.float64)[indices.astype(np.int64)]
+    rows = np.repeat(np.arange(indptr.size - 1), np.diff(indptr.astype(np.int64)))
+    return _segsum(np.exp(np.where(x > 0, x, slope * x) - np.asarray(lse, dtype=np.float64)[rows]), indptr)
+
+
+def _normal(seed, K, dh, rows):
+    return np.random.default_rng(seed + 1000 * K + dh).standard_normal((rows, K * dh), dtype=np.float32)
+
+
+def _cached(fn):
+    def wrapped(*key):
+        if (fn.__name__,) + key not in _cases:
+            _cases[(fn.__name__,) + key] = fn(*key)
+        return _cases[(fn.__name__,) + key]
+    return wrapped
+
+
+@_cached
+def forward_probe_case(t, K, dh):
+    """slot t of the forward position probe: s_dst = 0 and s_src = 0 but +40 at the source at the probed position of each
+    row, so that out[row] is that source's row of Z and lse = 40 (the other weights add up to less than 4097 e^-40)"""
+    indptr, indices, n_src = probe_block()
+    n = indptr.size - 1
+    Z = _normal(21, K, dh, n_src)
+    pos, hot = probe_hot(t)
+    s_src = np.zeros((n_src, K), dtype=np.float32)
+    s_src[hot] = 40.0
+    kw = dict(Z_dst=np.zeros((n, K * dh), dtype=np.float32), s_dst=np.zeros((n, K), dtype=np.float32), s_src=s_src)
+    args = (indptr, indices, Z, np.zeros((2, K * dh), dtype=np.float32), K)
+    return dict(indptr=indptr, indices=indices, n_src=n_src, Z=Z, s_src=s_src, pos=pos, hot=hot,
+                want=restate64(*args, exact=True, scales=True, **kw), twin=twin32(*args, **kw))
+
+
+@_cached
+def backward_src_probe_case(t, K, dh):
+    """slot t of the backward_src position probe.  The probe block is F^T here (5 sources that list 4548 destinations), F
+    its transpose; lse = 0, D = 0, att = 0, s_src = 0, and s_dst = 0 at the destination at the probed position of each row
+    of F^T and -200 (e = -40) at every other: G_Z[j] is G of that destination, ds_src[j, k] = slope (G_p . Z_j)[head k]"""
+    t_indptr, t_indices, n = probe_block()
+    n_src = t_indptr.size - 1
+    indptr, indices = transpose_pattern(t_indptr, t_indices, n)
+    Z, G = _normal(22, K, dh, n_src), _normal(23, K, dh, n)
+    pos, hot = probe_hot(t)
+    s_dst = np.full((n, K), -200.0, dtype=np.float32)
+    s_dst[hot] = 0.0
+    zeros = np.zeros((n, K), dtype=np.float32)
+    kw = dict(G=G, Z_dst=np.zeros((n, K * dh), dtype=np.float32), s_dst=s_dst, s_src=np.zeros((n_src, K), dtype=np.float32),
+              lse=zeros, D=zeros)
+    args = (indptr, indices, Z, np.zeros((2, K * dh), dtype=np.float32), K)
+    dots = SLOPE * (G[hot].astype(np.float64) * Z).reshape(n_src, K, dh).sum(axis=2)
+    return dict(t_indptr=t_indptr, t_indices=t_indices, n=n, n_src=n_src, Z=Z, G=G, s_dst=s_dst, pos=pos, hot=hot, dots=dots,
+                want=restate64(*args, exact=True, scales=True, **kw), twin=twin32(*args, **kw))
+
+
+@_cached
+def stress_case(kind, K, dh):
+    """the probe block as F with stress_scores(kind) as s_src and s_dst = 0; Z, G standard normal, att 0.1 x normal (it only
+    enters G_Z here)"""
+    indptr, indices, n_src = probe_block()
+    n, d = indptr.size - 1, K * dh
+    Z, G = _normal(31, K, dh, n_src), _normal(32, K, dh, n)
+    att = (0.1 * np.random.default_rng(33).standard_normal((2, d))).astype(np.float32)
+    s_src = stress_scores(kind, K)
+    kw = dict(G=G, Z_dst=np.zeros((n, d), dtype=np.float32), s_dst=np.zeros((n, K), dtype=np.float32), s_src=s_src)
+    args = (indptr, indices, Z, att, K)
+    want = restate64(*args, exact=True, scales=True, **kw)
+    # Every source has exactly one entry here, so ds_src[j] and G_Z[j] are one term each, and where its weight alpha is
+    # below the smallest normal fp32 (e^-96 in "ascending" and "late peak") fp32 holds it with few bits or as zero.  That is
+    # the format, not the kernel: such a weight is off by less than FLT_MIN, so the scale of these two outputs gets
+    # FLT_MIN / ROW_TOL per unit of weight on top -- an absolute allowance of FLT_MIN x (the term at weight one).
+    alpha = np.empty((n_src, K))
+    alpha[indices.astype(np.int64)] = want["alpha"]
+    sc = want["scale"]
+    tiny = float(np.finfo(np.float32).tiny) / ROW_TOL
+    sc["ds_src"] = sc["ds_src"] * (1 + tiny / alpha)
+    sc["G_Z"] = (sc["G_Z"].reshape(n_src, K, dh) * (1 + tiny / alpha)[:, :, None]).reshape(n_src, d)
+    return dict(indptr=indptr, indices=indices, n_src=n_src, Z=Z, G=G, att=att, s_src=s_src, want=want, twin=twin32(*args, **kw))
 
 
 def row_mean(indptr, indices, Z):

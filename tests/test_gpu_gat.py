@@ -52,8 +52,9 @@ def _u32(a):
     return _torch().from_numpy(np.ascontiguousarray(a, dtype=np.uint32).view(np.int32)).cuda()
 
 
-def run_device(ctx, indptr, indices, Z, att, K, G, Z_dst=None, offset=0, pad=0, slope=ref.SLOPE, n_src=None):
-    """every entry point once, through the C ABI with raw pointers; returns the outputs of ref.NAMES as numpy arrays"""
+def run_device(ctx, indptr, indices, Z, att, K, G, Z_dst=None, offset=0, pad=0, slope=ref.SLOPE, n_src=None, off=None):
+    """every entry point once, through the C ABI with raw pointers; returns the outputs of ref.NAMES as numpy arrays.
+    ``off``: {"Z" | "G" | "out" | "G_Z" | "att": floats} moves the base of that operand alone, in place of ``offset``"""
     torch = _torch()
     lib, st = ctx.lib, ctx.stream(0)
     n = indptr.size - 1
@@ -63,11 +64,12 @@ def run_device(ctx, indptr, indices, Z, att, K, G, Z_dst=None, offset=0, pad=0, 
     square = Z_dst is None
     t_indptr, t_indices = ref.transpose_pattern(indptr, indices, n_src)
     ip, ix, tip, tix = _u32(indptr), _u32(indices), _u32(t_indptr), _u32(t_indices)
-    Zs = _dense(n_src, d, offset, pad, Z)
-    Zd = Zs if square else _dense(n, d, offset, pad, Z_dst)
-    Gd = _dense(n, d, offset, pad, G)
-    at = _dense(2, d, offset, 0, att)
-    out, G_Z = _dense(n, d, offset, pad), _dense(n_src, d, offset, pad)
+    o = dict(dict.fromkeys(("Z", "G", "out", "G_Z", "att"), offset), **(off or {}))
+    Zs = _dense(n_src, d, o["Z"], pad, Z)
+    Zd = Zs if square else _dense(n, d, o["Z"], pad, Z_dst)
+    Gd = _dense(n, d, o["G"], pad, G)
+    at = _dense(2, d, o["att"], 0, att)
+    out, G_Z = _dense(n, d, o["out"], pad), _dense(n_src, d, o["G_Z"], pad)
     small = {k: _dense(n if k in ("s_dst", "lse", "D", "ds_dst") else n_src, K) for k in
              ("s_dst", "s_src", "lse", "D", "ds_dst", "ds_src")}
     G_att = _dense(2, d)
