@@ -374,6 +374,42 @@ void mggcn_gat_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t
 void mggcn_gat_scores_backward_f32(mggcn_stream_t stream, const float *ds_dst, const float *Z_dst, size_t ldzd, size_t n_dst,
                                    const float *ds_src, const float *Z_src, size_t ldzs, size_t n_src, uint32_t K, uint32_t dh,
                                    float *G_att);
+/* Attention dropout: the three sparse GAT calls with a mask on the normalised coefficients that is never stored (opt-in).
+ * Each takes the operands of its plain twin plus (threshold, scale, seed, dropout_stream, dst0, src0), threshold and scale
+ * as mggcn_dropout_f32 takes them (threshold = (uint32) floor(p * 2^32), scale = (float)(1 / (1 - p)), from the host).  Entry
+ * (global destination i = dst0 + local destination, global source j = src0 + local source, head k):
+ *   words = Philox4x32-10(counter = (j, i, 0x80000000 | (k >> 2), dropout_stream), key = (seed & 0xffffffff, seed >> 32))
+ *   q_ijk = words[k & 3] >= threshold ? scale : 0
+ * The set top bit of the third counter word keeps these words apart from the ones mggcn_dropout_f32 draws with the same
+ * (seed, dropout_stream), whose third word is row >> 32.  lse and alpha are the plain call's -- the softmax runs over ALL
+ * entries of a row -- and only the gathered weight carries q (one fp32 multiply of the weight by q):
+ *   forward         out[i, k dh + c] = sum_j (alpha_ijk q_ijk) Z[j, k dh + c];  a row whose entries are all dropped gets +0.0
+ *   backward_dst    D[i, k] = sum_c G out (unchanged: out is the dropped forward's);
+ *                   ds_ijk = alpha_ijk (q_ijk sum_c G[i, k dh + c] Z[j, k dh + c] - D[i, k]) (x_ijk > 0 ? 1 : slope)
+ *   backward_src    G_Z[j, k dh + c] = sum_i (alpha_ijk q_ijk) G[i, k dh + c] + ds_dst[j, k] att[0, ..] + ds_src[j, k] att[1, ..]
+ * For backward_src the rows of F^T are sources (offset src0) and its entries destinations (offset dst0).  The mask is a pure
+ * function of (seed, dropout_stream, i, j, k): it does not depend on the grid, on the position of the entry in its row, on
+ * the float4 or element path, on which of F or F^T is walked, or on how the rows are split between calls -- rows [a, b) of
+ * F with dst0 = a give rows [a, b) of the whole call, bit for bit.  Duplicate entries (i, j) share one bit: both are kept or
+ * both dropped.  dst0 + destinations and src0 + sources must not exceed 2^32 (refused otherwise).  threshold == 0 launches
+ * the plain kernels: the plain twin's bits in every output (scale is not used then).  No atomics, the same bits on every
+ * call, nothing of nnz x K stored. */
+void mggcn_gat_forward_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
+                                uint32_t K, uint32_t dh, float slope, float *out, size_t ldo, float *lse, uint32_t threshold,
+                                float scale, uint64_t seed, uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
+void mggcn_gat_backward_dst_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                     const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                     const float *s_src, const float *lse, const float *G, size_t ldg, const float *out,
+                                     size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *ds_dst,
+                                     uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream, uint32_t dst0,
+                                     uint32_t src0);
+void mggcn_gat_backward_src_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                     const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst,
+                                     const float *s_src, const float *lse, const float *D, const float *G, size_t ldg,
+                                     const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
+                                     float *ds_src, float *G_Z, size_t ldgz, uint32_t threshold, float scale, uint64_t seed,
+                                     uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
 /* cublasSasum   (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "philox.h"
 #include "reduce.h"
 #include "scratch_internal.h"
 
@@ -508,20 +509,7 @@ __global__ __launch_bounds__(256) void adam_multi_kernel(const mggcn_adam_tensor
 // Philox4x32-10 (Salmon et al., SC'11) on counter (c >> 2, row low, row high, stream) and key (seed low, seed high): word
 // c & 3 of the output decides column c of global row `row`.  A pure function of (seed, stream, row, column): the backward
 // pass calls the same kernel on the gradient and gets the same mask, a row shard gets the rows of the whole matrix's mask.
-// The 32 x 32 -> 64 products are written as one 64-bit multiply each (v_mad_u64_u32: both halves from one instruction).
-struct philox4 { uint32_t w[4]; };
-
-__device__ __forceinline__ philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int round = 0; round < 10; round++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    return {{c0, c1, c2, c3}};
-}
-
+// The generator itself lives in philox.h, shared with the attention dropout of gat.hip.
 __device__ __forceinline__ float dropout_one(float x, uint32_t word, uint32_t threshold, float scale) {
     return word >= threshold ? x * scale : 0.f;       // a select: +0.0 also where x is NaN or an infinity
 }

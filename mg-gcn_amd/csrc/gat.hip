@@ -18,10 +18,16 @@
 // must not straddle two heads, so K * dh % 4 == 0 alone is not enough -- and VEC = 1 otherwise.
 // Heavy rows are slow here (one wave walks a whole row, ~21 k entries on the Reddit-shaped graph) but correct: cutting
 // them with a fixed-order combine is what the SpMM's plan does and is left to a plan for these kernels.
+// Attention dropout (DROP = true, the mggcn_gat_*_drop_f32 entry points): the lane that owns an entry draws its keep bit
+// from Philox on (source, destination, head) next to the exp, and the factor q = keep ? 1 / (1 - p) : 0 travels to the
+// groups through the same __shfl as the weight.  The softmax itself (maximum, sum, lse) takes every entry.  Nothing is
+// stored: the backward kernels draw the same words again, backward_src with the roles of row and entry swapped.  Duplicate
+// entries (i, j) share one bit.  DROP = false compiles to the kernels as they were.
 #include <algorithm>
 #include <cmath>
 
 #include "common.h"
+#include "philox.h"
 #include "reduce.h"
 #include "scratch_internal.h"
 
@@ -82,6 +88,23 @@ __device__ __forceinline__ float dot_head_row(const float (&a)[NT][VEC], const f
     return p;
 }
 
+// what a DROP kernel needs to draw the mask: threshold = floor(p 2^32), scale = fp32(1 / (1 - p)), the key (seed low, seed
+// high), the dropout stream and the global indices of the call's first destination and first source
+struct gat_drop {
+    uint32_t threshold;
+    float scale;
+    uint32_t k0, k1, stream, dst0, src0;
+};
+
+// q of entry (global destination i, global source j, head k): word k & 3 of Philox(counter = (j, i, 2^31 | k >> 2, stream)).
+// The set top bit of the third word keeps these counters apart from mggcn_dropout_f32's (row >> 32 there) under one
+// (seed, stream).  k is wave-uniform, so the word is picked by selects on a scalar condition.
+__device__ __forceinline__ float gat_keep_scale(const gat_drop &dp, uint32_t i, uint32_t j, uint32_t k) {
+    const philox4 r = philox4x32_10(j, i, 0x80000000u | (k >> 2), dp.stream, dp.k0, dp.k1);
+    const uint32_t word = (k & 2) ? ((k & 1) ? r.w[3] : r.w[2]) : ((k & 1) ? r.w[1] : r.w[0]);
+    return word >= dp.threshold ? dp.scale : 0.f;
+}
+
 #define MGGCN_GAT_WAVE_ROW(n_rows)                                                                            \
     const uint32_t lane = threadIdx.x & 63;                                                                   \
     const uint32_t lpr = 1u << lg, n_grp = 64u >> lg, sub = lane & (lpr - 1), grp = lane >> lg;               \
@@ -119,13 +142,14 @@ __global__ __launch_bounds__(256) void gat_scores_kernel(const float *__restrict
 // ---------------------------------------------------------------------------
 // forward: lse[i, k] and out[i, head k] = sum_j alpha_ijk Z[j, head k] over the entries j of row i
 // ---------------------------------------------------------------------------
-template <int VEC, int NT, int U>
+// DROP: out[i, head k] = sum_j (alpha_ijk q_ijk) Z[j, head k]; lse, the maximum and the sum are those of DROP = false
+template <int VEC, int NT, int U, bool DROP>
 __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
                                                           const uint32_t *__restrict__ indices, const float *__restrict__ Z,
                                                           size_t ldz, const float *__restrict__ s_dst,
                                                           const float *__restrict__ s_src, uint32_t K, uint32_t dh, float slope,
                                                           uint32_t lg, float *__restrict__ out, size_t ldo,
-                                                          float *__restrict__ lse) {
+                                                          float *__restrict__ lse, gat_drop dp) {
     MGGCN_GAT_WAVE_ROW(n_rows);
     const uint32_t beg = indptr[row], end = indptr[row + 1];
     for (uint32_t k = 0; k < K; k++) {
@@ -154,9 +178,12 @@ __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const
             const float e = lane < cnt ? gat_lrelu(sd + my_x, slope) : -INFINITY;
             const float m_new = fmaxf(m, wave_max(e));
             const float scale = expf(m - m_new);            // 0 at the first chunk (m = -inf), where sum and acc are 0
-            const float my_a = lane < cnt ? expf(e - m_new) : 0.f;
+            float my_a = lane < cnt ? expf(e - m_new) : 0.f;
             sum = fmaf(sum, scale, wave_sum(my_a));
             m = m_new;
+            if constexpr (DROP) {                            // after the sum: only the accumulator's weight carries q
+                if (lane < cnt) my_a *= gat_keep_scale(dp, dp.dst0 + (uint32_t)row, dp.src0 + my_c, k);
+            }
             if (scale != 1.f) {                              // wave-uniform
 #pragma unroll
                 for (int t = 0; t < NT; t++)
@@ -198,7 +225,8 @@ __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const
 // backward over the rows of F:  D[i, k] = G[i, head k] . out[i, head k]
 //   ds_dst[i, k] = sum_j alpha_ijk (G[i, head k] . Z[j, head k] - D[i, k]) lrelu'(x_ijk)
 // ---------------------------------------------------------------------------
-template <int VEC, int NT, int U>
+// DROP: ds_ijk = alpha_ijk (q_ijk dalpha_ijk - D[i, k]) lrelu'(x_ijk); D = G . out as before (out is the dropped forward's)
+template <int VEC, int NT, int U, bool DROP>
 __global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
                                                                const uint32_t *__restrict__ indices,
                                                                const float *__restrict__ Z, size_t ldz,
@@ -206,7 +234,7 @@ __global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, 
                                                                const float *__restrict__ lse, const float *__restrict__ G,
                                                                size_t ldg, const float *__restrict__ out, size_t ldo, uint32_t K,
                                                                uint32_t dh, float slope, uint32_t lg, float *__restrict__ D,
-                                                               float *__restrict__ ds_dst) {
+                                                               float *__restrict__ ds_dst, gat_drop dp) {
     MGGCN_GAT_WAVE_ROW(n_rows);
     const uint32_t beg = indptr[row], end = indptr[row + 1];
     for (uint32_t k = 0; k < K; k++) {
@@ -230,9 +258,11 @@ __global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, 
             if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
             const uint32_t cnt = min(64u, end - base);
             float my_w = 0.f;                       // alpha lrelu'(x) of my entry
+            [[maybe_unused]] float my_q = 0.f;
             if (lane < cnt) {
                 const float x = sd + my_x;
                 my_w = expf(gat_lrelu(x, slope) - ls) * (x > 0.f ? 1.f : slope);
+                if constexpr (DROP) my_q = gat_keep_scale(dp, dp.dst0 + (uint32_t)row, dp.src0 + my_c, k);
             }
             for (uint32_t j = 0; j < cnt; j += n_grp * U) {
                 float p[U];
@@ -248,7 +278,8 @@ __global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, 
                 for (int u = 0; u < U; u++) {
                     const uint32_t src = j + u * n_grp + grp;
                     const float w = __shfl(my_w, src & 63);
-                    const float da = group_sum(p[u], lpr);
+                    float da = group_sum(p[u], lpr);
+                    if constexpr (DROP) da *= __shfl(my_q, src & 63);
                     acc += src < cnt ? w * (da - Dk) : 0.f;
                 }
             }
@@ -266,7 +297,8 @@ __global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, 
 //   ds_src[j, k] = sum_i alpha_ijk (G[i, head k] . Z[j, head k] - D[i, k]) lrelu'(x_ijk)
 //   G_Z[j, head k] = sum_i alpha_ijk G[i, head k] + ds_dst[j, k] att[0, head k] + ds_src[j, k] att[1, head k]
 // ---------------------------------------------------------------------------
-template <int VEC, int NT, int U>
+// DROP: the row is the source and the entry the destination, so the counter is (row, entry) here: the words of the forward
+template <int VEC, int NT, int U, bool DROP>
 __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
                                                                const uint32_t *__restrict__ indices,
                                                                const float *__restrict__ Z, size_t ldz,
@@ -275,7 +307,8 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
                                                                const float *__restrict__ G, size_t ldg,
                                                                const float *__restrict__ att, const float *__restrict__ ds_dst,
                                                                uint32_t K, uint32_t dh, float slope, uint32_t lg,
-                                                               float *__restrict__ ds_src, float *__restrict__ G_Z, size_t ldgz) {
+                                                               float *__restrict__ ds_src, float *__restrict__ G_Z, size_t ldgz,
+                                                               gat_drop dp) {
     MGGCN_GAT_WAVE_ROW(n_rows);
     const uint32_t beg = indptr[row], end = indptr[row + 1];
     const uint32_t width = K * dh;
@@ -307,10 +340,15 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
             if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
             const uint32_t cnt = min(64u, end - base);
             float my_a = 0.f, my_w = 0.f;
+            [[maybe_unused]] float my_q = 0.f;
             if (lane < cnt) {
                 const float x = my_x + ss;
                 my_a = expf(gat_lrelu(x, slope) - my_l);
                 my_w = my_a * (x > 0.f ? 1.f : slope);
+                if constexpr (DROP) {
+                    my_q = gat_keep_scale(dp, dp.dst0 + my_c, dp.src0 + (uint32_t)row, k);
+                    my_a *= my_q;                   // the gather's weight alpha q; my_w keeps the plain alpha
+                }
             }
             for (uint32_t j = 0; j < cnt; j += n_grp * U) {
                 float gv[U][NT][VEC], p[U];
@@ -326,7 +364,8 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
                     const uint32_t src = j + u * n_grp + grp;
                     const bool ok = src < cnt;
                     const float a = __shfl(my_a, src & 63), w = __shfl(my_w, src & 63), Dv = __shfl(my_D, src & 63);
-                    const float da = group_sum(p[u], lpr);
+                    float da = group_sum(p[u], lpr);
+                    if constexpr (DROP) da *= __shfl(my_q, src & 63);
                     acc_ds += ok ? w * (da - Dv) : 0.f;
                     const float au = ok ? a : 0.f;
 #pragma unroll
@@ -428,6 +467,102 @@ bool rows16(const float *p, size_t ld) { return aligned16(p) && ld % 4 == 0; }
         }                                     \
     } while (0)
 
+// the mask's operands of a _drop entry point; both index ranges of the call must fit the 32-bit counter words
+gat_drop make_gat_drop(uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream, uint32_t dst0, uint32_t n_dst,
+                       uint32_t src0, uint32_t n_src) {
+    MGGCN_REQUIRE((uint64_t)dst0 + n_dst <= 0x100000000ull && (uint64_t)src0 + n_src <= 0x100000000ull,
+                  "gat dropout: dst0 + destinations and src0 + sources must not exceed 2^32");
+    return {threshold, scale, (uint32_t)seed, (uint32_t)(seed >> 32), dropout_stream, dst0, src0};
+}
+
+// The bodies of the plain entry points and of their _drop twins: dp == nullptr launches the DROP = false kernels.
+void gat_forward(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices,
+                 const float *Z, size_t ldz, const float *s_dst, const float *s_src, uint32_t K, uint32_t dh, float slope,
+                 float *out, size_t ldo, float *lse, const gat_drop *dp) {
+    require_heads(K, dh);
+    MGGCN_REQUIRE(ldz >= (size_t)K * dh && ldo >= (size_t)K * dh, "gat forward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && s_dst != nullptr && out != nullptr && lse != nullptr, "gat forward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Z != nullptr && s_src != nullptr), "gat forward: null operand");
+    MGGCN_REQUIRE(out != Z, "gat forward: out must not alias Z");
+    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(out, ldo);
+    const head_geometry hg = head_geometry_for(dh, vec);
+    const gat_drop d = dp ? *dp : gat_drop{};
+#define MGGCN_GAT_FWD_(V, NT, U, DROP)                                                                                         \
+    hipLaunchKernelGGL((gat_forward_kernel<V, NT, U, DROP>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
+                       indptr, indices, Z, ldz, s_dst, s_src, K, dh, slope, hg.lg, out, ldo, lse, d)
+#define MGGCN_GAT_FWD(V, NT, U)                \
+    do {                                       \
+        if (dp) MGGCN_GAT_FWD_(V, NT, U, true); \
+        else MGGCN_GAT_FWD_(V, NT, U, false);  \
+    } while (0)
+    MGGCN_GAT_DISPATCH(MGGCN_GAT_FWD, vec, hg.nt);
+#undef MGGCN_GAT_FWD
+#undef MGGCN_GAT_FWD_
+    MGGCN_CHECK_LAUNCH();
+}
+
+void gat_backward_dst(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices,
+                      const float *Z, size_t ldz, const float *s_dst, const float *s_src, const float *lse, const float *G,
+                      size_t ldg, const float *out, size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *ds_dst,
+                      const gat_drop *dp) {
+    require_heads(K, dh);
+    const size_t width = (size_t)K * dh;
+    MGGCN_REQUIRE(ldz >= width && ldg >= width && ldo >= width, "gat backward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && s_dst != nullptr && lse != nullptr && G != nullptr && out != nullptr && D != nullptr &&
+                      ds_dst != nullptr,
+                  "gat backward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Z != nullptr && s_src != nullptr), "gat backward: null operand");
+    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(out, ldo);
+    const head_geometry hg = head_geometry_for(dh, vec);
+    const gat_drop d = dp ? *dp : gat_drop{};
+#define MGGCN_GAT_BWD_DST_(V, NT, U, DROP)                                                                                   \
+    hipLaunchKernelGGL((gat_backward_dst_kernel<V, NT, U, DROP>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream),   \
+                       n_rows, indptr, indices, Z, ldz, s_dst, s_src, lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, ds_dst, d)
+#define MGGCN_GAT_BWD_DST(V, NT, U)                \
+    do {                                           \
+        if (dp) MGGCN_GAT_BWD_DST_(V, NT, U, true); \
+        else MGGCN_GAT_BWD_DST_(V, NT, U, false);  \
+    } while (0)
+    MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_DST, vec, hg.nt);
+#undef MGGCN_GAT_BWD_DST
+#undef MGGCN_GAT_BWD_DST_
+    MGGCN_CHECK_LAUNCH();
+}
+
+void gat_backward_src(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                      const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
+                      const float *lse, const float *D, const float *G, size_t ldg, const float *att, const float *ds_dst,
+                      uint32_t K, uint32_t dh, float slope, float *ds_src, float *G_Z, size_t ldgz, const gat_drop *dp) {
+    require_heads(K, dh);
+    const size_t width = (size_t)K * dh;
+    MGGCN_REQUIRE(ldz >= width && ldg >= width && ldgz >= width, "gat backward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(t_indptr != nullptr && Z != nullptr && s_src != nullptr && att != nullptr && ds_src != nullptr &&
+                      G_Z != nullptr,
+                  "gat backward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && s_dst != nullptr && lse != nullptr && D != nullptr && G != nullptr),
+                  "gat backward: null operand");
+    MGGCN_REQUIRE(G_Z != G && G_Z != Z, "gat backward: G_Z must not alias G or Z");
+    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(G_Z, ldgz) && aligned16(att);
+    const head_geometry hg = head_geometry_for(dh, vec);
+    const gat_drop d = dp ? *dp : gat_drop{};
+#define MGGCN_GAT_BWD_SRC_(V, NT, U, DROP)                                                                                   \
+    hipLaunchKernelGGL((gat_backward_src_kernel<V, NT, U, DROP>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream),   \
+                       n_rows, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, G, ldg, att, ds_dst, K, dh, slope, hg.lg,  \
+                       ds_src, G_Z, ldgz, d)
+#define MGGCN_GAT_BWD_SRC(V, NT, U)                \
+    do {                                           \
+        if (dp) MGGCN_GAT_BWD_SRC_(V, NT, U, true); \
+        else MGGCN_GAT_BWD_SRC_(V, NT, U, false);  \
+    } while (0)
+    MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_SRC, vec, hg.nt);
+#undef MGGCN_GAT_BWD_SRC
+#undef MGGCN_GAT_BWD_SRC_
+    MGGCN_CHECK_LAUNCH();
+}
+
 }  // namespace
 
 // ============================ C ABI =========================================
@@ -448,42 +583,15 @@ MGGCN_API void mggcn_gat_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uin
                                      const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
                                      const float *s_src, uint32_t K, uint32_t dh, float slope, float *out, size_t ldo,
                                      float *lse) {
-    require_heads(K, dh);
-    MGGCN_REQUIRE(ldz >= (size_t)K * dh && ldo >= (size_t)K * dh, "gat forward: leading dimension < heads * width per head");
-    if (!n_rows) return;
-    MGGCN_REQUIRE(indptr != nullptr && s_dst != nullptr && out != nullptr && lse != nullptr, "gat forward: null operand");
-    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Z != nullptr && s_src != nullptr), "gat forward: null operand");
-    MGGCN_REQUIRE(out != Z, "gat forward: out must not alias Z");
-    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(out, ldo);
-    const head_geometry hg = head_geometry_for(dh, vec);
-#define MGGCN_GAT_FWD(V, NT, U)                                                                                            \
-    hipLaunchKernelGGL((gat_forward_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, indptr, \
-                       indices, Z, ldz, s_dst, s_src, K, dh, slope, hg.lg, out, ldo, lse)
-    MGGCN_GAT_DISPATCH(MGGCN_GAT_FWD, vec, hg.nt);
-#undef MGGCN_GAT_FWD
-    MGGCN_CHECK_LAUNCH();
+    gat_forward(stream, n_rows, n_cols, indptr, indices, Z, ldz, s_dst, s_src, K, dh, slope, out, ldo, lse, nullptr);
 }
 
 MGGCN_API void mggcn_gat_backward_dst_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
                                           const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
                                           const float *s_src, const float *lse, const float *G, size_t ldg, const float *out,
                                           size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *ds_dst) {
-    require_heads(K, dh);
-    const size_t width = (size_t)K * dh;
-    MGGCN_REQUIRE(ldz >= width && ldg >= width && ldo >= width, "gat backward: leading dimension < heads * width per head");
-    if (!n_rows) return;
-    MGGCN_REQUIRE(indptr != nullptr && s_dst != nullptr && lse != nullptr && G != nullptr && out != nullptr && D != nullptr &&
-                      ds_dst != nullptr,
-                  "gat backward: null operand");
-    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Z != nullptr && s_src != nullptr), "gat backward: null operand");
-    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(out, ldo);
-    const head_geometry hg = head_geometry_for(dh, vec);
-#define MGGCN_GAT_BWD_DST(V, NT, U)                                                                                         \
-    hipLaunchKernelGGL((gat_backward_dst_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
-                       indptr, indices, Z, ldz, s_dst, s_src, lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, ds_dst)
-    MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_DST, vec, hg.nt);
-#undef MGGCN_GAT_BWD_DST
-    MGGCN_CHECK_LAUNCH();
+    gat_backward_dst(stream, n_rows, n_cols, indptr, indices, Z, ldz, s_dst, s_src, lse, G, ldg, out, ldo, K, dh, slope, D, ds_dst,
+                     nullptr);
 }
 
 MGGCN_API void mggcn_gat_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
@@ -491,25 +599,43 @@ MGGCN_API void mggcn_gat_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows
                                           const float *s_src, const float *lse, const float *D, const float *G, size_t ldg,
                                           const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
                                           float *ds_src, float *G_Z, size_t ldgz) {
-    require_heads(K, dh);
-    const size_t width = (size_t)K * dh;
-    MGGCN_REQUIRE(ldz >= width && ldg >= width && ldgz >= width, "gat backward: leading dimension < heads * width per head");
-    if (!n_rows) return;
-    MGGCN_REQUIRE(t_indptr != nullptr && Z != nullptr && s_src != nullptr && att != nullptr && ds_src != nullptr &&
-                      G_Z != nullptr,
-                  "gat backward: null operand");
-    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && s_dst != nullptr && lse != nullptr && D != nullptr && G != nullptr),
-                  "gat backward: null operand");
-    MGGCN_REQUIRE(G_Z != G && G_Z != Z, "gat backward: G_Z must not alias G or Z");
-    const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(G_Z, ldgz) && aligned16(att);
-    const head_geometry hg = head_geometry_for(dh, vec);
-#define MGGCN_GAT_BWD_SRC(V, NT, U)                                                                                         \
-    hipLaunchKernelGGL((gat_backward_src_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
-                       t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, G, ldg, att, ds_dst, K, dh, slope, hg.lg, ds_src,  \
-                       G_Z, ldgz)
-    MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_SRC, vec, hg.nt);
-#undef MGGCN_GAT_BWD_SRC
-    MGGCN_CHECK_LAUNCH();
+    gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, G, ldg, att, ds_dst, K, dh, slope,
+                     ds_src, G_Z, ldgz, nullptr);
+}
+
+// The _drop twins: threshold == 0 (p = 0: every entry kept, scale = 1) launches the plain kernels, so the bits are the plain
+// entry point's by construction; the index ranges are still checked.
+MGGCN_API void mggcn_gat_forward_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                          const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                          const float *s_src, uint32_t K, uint32_t dh, float slope, float *out, size_t ldo,
+                                          float *lse, uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream,
+                                          uint32_t dst0, uint32_t src0) {
+    const gat_drop dp = make_gat_drop(threshold, scale, seed, dropout_stream, dst0, n_rows, src0, n_cols);
+    gat_forward(stream, n_rows, n_cols, indptr, indices, Z, ldz, s_dst, s_src, K, dh, slope, out, ldo, lse,
+                threshold ? &dp : nullptr);
+}
+
+MGGCN_API void mggcn_gat_backward_dst_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                               const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                               const float *s_src, const float *lse, const float *G, size_t ldg,
+                                               const float *out, size_t ldo, uint32_t K, uint32_t dh, float slope, float *D,
+                                               float *ds_dst, uint32_t threshold, float scale, uint64_t seed,
+                                               uint32_t dropout_stream, uint32_t dst0, uint32_t src0) {
+    const gat_drop dp = make_gat_drop(threshold, scale, seed, dropout_stream, dst0, n_rows, src0, n_cols);
+    gat_backward_dst(stream, n_rows, n_cols, indptr, indices, Z, ldz, s_dst, s_src, lse, G, ldg, out, ldo, K, dh, slope, D, ds_dst,
+                     threshold ? &dp : nullptr);
+}
+
+// rows of F^T are sources (offset src0), its entries destinations (offset dst0)
+MGGCN_API void mggcn_gat_backward_src_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                               const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst,
+                                               const float *s_src, const float *lse, const float *D, const float *G, size_t ldg,
+                                               const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
+                                               float *ds_src, float *G_Z, size_t ldgz, uint32_t threshold, float scale,
+                                               uint64_t seed, uint32_t dropout_stream, uint32_t dst0, uint32_t src0) {
+    const gat_drop dp = make_gat_drop(threshold, scale, seed, dropout_stream, dst0, n_cols, src0, n_rows);
+    gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, G, ldg, att, ds_dst, K, dh, slope,
+                     ds_src, G_Z, ldgz, threshold ? &dp : nullptr);
 }
 
 MGGCN_API void mggcn_gat_scores_backward_f32(mggcn_stream_t stream, const float *ds_dst, const float *Z_dst, size_t ldzd,

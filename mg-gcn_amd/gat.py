@@ -13,7 +13,16 @@ and every layer but the last applies the project's leaky ReLU (0.01) afterwards.
 scores (PyG adds its bias after the aggregation instead).  The kernels are those of csrc/gat.hip (include/mggcn.h:
 mggcn_gat_*): nothing of nnz x heads is stored, the backward pass recomputes alpha from s_dst, s_src and lse.
 
-Not covered: dist_gcn, the C++ host layer and CLI, checkpoints, dropout, layer norm, bf16 gathers, attention dropout.
+Two dropouts (opt-in, both 0 by default: nothing new is launched or allocated), in training forwards only:
+  * ``dropout=p``: the input of every layer but the first goes through ops.dropout_raw, and so does the gradient that layer
+    returns -- gcn's convention, stream = epoch * 64 + layer; the features are never dropped;
+  * ``attn_dropout=p``: every layer's normalised coefficients, the first layer's included, are multiplied by
+    q_ijk = keep ? 1 / (1 - p) : 0 in the gather (out = sum_j alpha q Z; the softmax still runs over all entries), with a
+    Philox mask on (seed, the same stream number, destination, source, head) that the three sparse kernels regenerate
+    (mggcn_gat_*_drop_f32) -- no edge mask is stored.  Duplicate entries (i, j) share one bit.
+set_dropout(p, seed, epoch, attn) sets both; evaluate() and a plain call never drop.
+
+Not covered: dist_gcn, the C++ host layer and CLI, checkpoints, layer norm, bf16 gathers.
 """
 from __future__ import annotations
 
@@ -22,7 +31,8 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib, ops
-from .gcn import (adam_update_all, check_loss, gcn, linear, sigmoid_bce_loss, softmax_cross_entropy_loss)
+from .gcn import (DROPOUT_MAX_LAYERS, adam_update_all, check_dropout, check_loss, dropout_option, gcn, linear,
+                  sigmoid_bce_loss, softmax_cross_entropy_loss)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -59,20 +69,21 @@ class attention:
         self.m = self.v = None
         self.step = 0
 
-    def __call__(self, ctx: context, F: csr_matrix, Z: dn_matrix, out: dn_matrix) -> None:
-        """out = the attention-weighted gather of Z over F's rows (destinations and sources are the same vertices)"""
+    def __call__(self, ctx: context, F: csr_matrix, Z: dn_matrix, out: dn_matrix, drop=None) -> None:
+        """out = the attention-weighted gather of Z over F's rows (destinations and sources are the same vertices);
+        ``drop``: attention dropout, the tuple of ops.gat_forward (None: the plain entry point)"""
         n = self.name
         ops.gat_scores(ctx, Z, self.att, self.s_dst, self.s_src, self.heads, n + "0_gat-scores")
-        ops.gat_forward(ctx, F, Z, self.s_dst, self.s_src, out, self.lse, self.heads, self.slope, n + "0_gat-forward")
+        ops.gat_forward(ctx, F, Z, self.s_dst, self.s_src, out, self.lse, self.heads, self.slope, n + "0_gat-forward", drop)
 
     def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z: dn_matrix, G: dn_matrix, out: dn_matrix,
-                 G_Z: dn_matrix) -> None:
-        """G_Z = the gradient of Z and G_att, from G = the gradient of ``out``"""
+                 G_Z: dn_matrix, drop=None) -> None:
+        """G_Z = the gradient of Z and G_att, from G = the gradient of ``out``; ``drop``: what the forward was called with"""
         n = self.name
         ops.gat_backward_dst(ctx, F, Z, self.s_dst, self.s_src, self.lse, G, out, self.D, self.ds_dst, self.heads, self.slope,
-                             n + "1_gat-backward-dst")
+                             n + "1_gat-backward-dst", drop)
         ops.gat_backward_src(ctx, F_T, Z, self.s_dst, self.s_src, self.lse, self.D, G, self.att, self.ds_dst, self.ds_src,
-                             G_Z, self.heads, self.slope, n + "1_gat-backward-src")
+                             G_Z, self.heads, self.slope, n + "1_gat-backward-src", drop)
         ops.gat_scores_backward(ctx, self.ds_dst, Z, self.ds_src, Z, self.G_att, self.heads, n + "1_gat-scores-backward")
 
     def init(self, att) -> None:
@@ -118,12 +129,31 @@ class gat_layer:
         self.G_Z = dn_matrix(n, out, G_Z_buffer) if G_Z_buffer is not None else dn_matrix(n, out)
         self.G_out = dn_matrix(n, in_) if backward_out else None
         self.H: Optional[dn_matrix] = None
+        # set by the model before every forward and read again by backward(): ``dropout`` -- (threshold, scale, seed, stream)
+        # of ops.dropout_raw for my input and the gradient I return; ``attn_dropout`` -- the tuple of ops.gat_forward
+        self.dropout = None
+        self.attn_dropout = None
+
+    def _drop(self, ctx: context, M: dn_matrix, tag: str) -> None:
+        """M = dropout(M) in place with this forward's mask: H on the way up ("0"), G_out on the way down ("1")"""
+        n = self.name
+        threshold, scale, seed, stream = self.dropout
+        ctx.record(n + tag + "_0_dropout", 0)
+        ops.dropout_raw(ctx, M, M, threshold, scale, seed, stream, 0)
+        ctx.record(n + tag + "_1_dropout", 0)
+        ctx.register_timer(n + tag + "_dropout", n + tag + "_0_dropout", n + tag + "_1_dropout")
 
     def __call__(self, ctx: context, H: dn_matrix) -> dn_matrix:
         n = self.name
+        if self.dropout is not None:
+            # In place: H is the ``act`` buffer of the layer below, which no backward reads as a value -- that layer's own
+            # backward takes its signs and its D = G . out from its ``out``, a separate buffer wherever there is an
+            # activation (every layer that has a layer above), and overwrites ``act`` with T.  My G_W GEMM wants the
+            # dropped H, which is what stays here.
+            self._drop(ctx, H, "0")
         self.H = H
         self.lin(ctx, H, self.Z)
-        self.attn(ctx, self.F, self.Z, self.out)
+        self.attn(ctx, self.F, self.Z, self.out, self.attn_dropout)
         if self.activation:
             ctx.record(n + "0_0_activation", 0)
             ops.leaky_relu_forward(ctx, self.out, self.act)
@@ -142,9 +172,11 @@ class gat_layer:
             ctx.record(n + "1_1_activation", 0)
             ctx.register_timer(n + "1_activation", n + "1_0_activation", n + "1_1_activation")
             T = self.act
-        self.attn.backward(ctx, self.F, self.F_T, self.Z, T, self.out, self.G_Z)
+        self.attn.backward(ctx, self.F, self.F_T, self.Z, T, self.out, self.G_Z, self.attn_dropout)
         self.lin.setX(self.H)
         self.lin.backward(ctx, self.G_Z, self.G_out)
+        if self.dropout is not None and self.G_out is not None:
+            self._drop(ctx, self.G_out, "1")
         return self.G_out
 
     def linears(self):
@@ -166,23 +198,32 @@ class gat_layer:
     def Gatt(self): return self.attn.G_att
 
 
-class gat:
+class gat(dropout_option):
     """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
 
-    gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None): ``A`` as ``gcn`` takes it (the
-    layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
+    gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0):
+    ``A`` as ``gcn`` takes it (the layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
     (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att).  ValueError
     before any device work for a width that its heads do not divide or a limit of the kernels (ops.GAT_MAX_HEADS,
     ops.GAT_MAX_WIDTH).  ``fused`` picks how Adam is launched -- one launch for every parameter tensor, or one per tensor;
     the element-wise math is the same, so both give the same bits -- and every other kernel is the same in both modes.
 
+    ``dropout`` / ``attn_dropout`` / set_dropout(p, seed=0, epoch=0, attn=None): see the module docstring and
+    gcn.dropout_option -- ``dropout_p``, ``attn_dropout_p``, ``dropout_seed`` and ``dropout_epoch`` (the number the next
+    training forward gets) read the state; only train_forward / train_step drop, the backward pass uses the stream its
+    forward used, and with both probabilities 0 the plain entry points are called and nothing is launched or allocated.
+    ValueError for a probability outside [0, 1), or for more than 64 layers with one of them above 0, before any device work.
+
     __call__, train_forward, backward, adam_update, train_step (one synchronisation), evaluate, set_splits, split_metrics
     and layers() mean what they mean on ``gcn``."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
-                 loss: str = "softmax", fused: bool = True, weights=None):
+                 loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0):
         self.sizes = [int(s) for s in sizes]
         self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
+        self._attn_dropout_params = check_dropout(attn_dropout, len(self.sizes) - 1)
+        self._init_dropout(dropout, len(self.sizes) - 1)
+        self.attn_dropout_p = float(attn_dropout)
         self.loss = check_loss(loss)
         if A.n() != A.m():
             raise ValueError(f"gat needs a square matrix, got {A.n()} x {A.m()}")
@@ -209,8 +250,32 @@ class gat:
                 if len(w) > 2:
                     layer.attn.init(w[2])
 
+    def set_dropout(self, p: float, seed: int = 0, epoch: int = 0, attn: Optional[float] = None) -> None:
+        """p: the drop probability of the layer inputs, attn: that of the attention coefficients (None keeps the current
+        one), both in [0, 1) and 0 = off; seed: 64 bits, shared by both; epoch: the number the next training forward gets
+        (set_dropout(p, seed, epoch=e) replays training forward e).  ValueError before any device work, and before
+        anything is stored."""
+        attn = self.attn_dropout_p if attn is None else attn
+        attn_params = check_dropout(attn, self._dropout_layers)
+        dropout_option.set_dropout(self, p, seed, epoch)
+        self._attn_dropout_params, self.attn_dropout_p = attn_params, float(attn)
+
+    def _arm_dropout(self, training: bool) -> None:
+        """hands every layer its two calls of this forward (None: the plain path); a training forward with either
+        probability above 0 takes the current epoch number and moves it on.  Layer l uses stream epoch * 64 + l for both."""
+        feat = bool(training) and self.dropout_p > 0.0
+        attn = bool(training) and self.attn_dropout_p > 0.0
+        for li, layer in enumerate(self.layers_):
+            stream = (self.dropout_epoch * DROPOUT_MAX_LAYERS + li) & 0xFFFFFFFF
+            layer.dropout = (*self._dropout_params, self.dropout_seed, stream) if feat and li > 0 else None
+            layer.attn_dropout = (*self._attn_dropout_params, self.dropout_seed, stream, 0, 0) if attn else None
+        if feat or attn:
+            self.dropout_epoch += 1
+
     def __call__(self, ctx: context, H: dn_matrix, training: bool = False) -> dn_matrix:
-        """the forward pass (``training`` changes nothing: there is no dropout here)"""
+        """the forward pass; ``training``: a training forward (train_forward / train_step pass True), the only kind that
+        drops -- a plain call and evaluate() never do"""
+        self._arm_dropout(training)
         for layer in self.layers_:
             H = layer(ctx, H)
         return H

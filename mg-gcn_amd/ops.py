@@ -439,6 +439,17 @@ def _gat_timed(ctx: context, timer: Optional[str], call) -> None:
     ctx.register_timer(timer, timer + "_0", timer + "_1")
 
 
+def _gat_drop_args(drop, what: str, n_dst: int, n_src: int):
+    """the six trailing arguments of a mggcn_gat_*_drop_f32 call from ``drop`` = (threshold, scale, seed, stream, dst0, src0):
+    threshold and scale as dropout_params gives them; ValueError before the library for anything out of range"""
+    _req(len(drop) == 6, f"{what}: drop must be (threshold, scale, seed, stream, dst0, src0)")
+    threshold, scale, seed, stream, dst0, src0 = drop
+    _req(0 <= int(threshold) <= 0xFFFFFFFF, f"{what}: the dropout threshold must fit 32 bits")
+    _req(int(dst0) >= 0 and int(src0) >= 0 and int(dst0) + n_dst <= 1 << 32 and int(src0) + n_src <= 1 << 32,
+         f"{what}: dst0 + destinations and src0 + sources must not exceed 2^32 (the library would exit, not raise)")
+    return (int(threshold), float(scale), int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, int(dst0), int(src0))
+
+
 def gat_scores(ctx: context, Z: dn_matrix, att: dn_matrix, s_dst: Optional[dn_matrix], s_src: Optional[dn_matrix],
                heads: int, timer: Optional[str] = None) -> None:
     """s_dst[r, k] = Z[r, head k] . att[0, head k] and s_src likewise with att[1] (mggcn_gat_scores_f32); either output
@@ -453,53 +464,72 @@ def gat_scores(ctx: context, Z: dn_matrix, att: dn_matrix, s_dst: Optional[dn_ma
 
 
 def gat_forward(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
-                lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+                lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
     """The edge-softmax fused with the gather (mggcn_gat_forward_f32): over F's pattern (values ignored), lse[i, k] =
     log sum_j exp(lrelu(s_dst[i, k] + s_src[j, k])) and out[i, head k] = sum_j alpha_ijk Z[j, head k].  F: destinations x
-    sources; Z, s_src: one row per source; s_dst, out, lse: one row per destination."""
+    sources; Z, s_src: one row per source; s_dst, out, lse: one row per destination.
+
+    ``drop`` = (threshold, scale, seed, stream, dst0, src0) -- threshold, scale from dropout_params -- is attention dropout
+    (mggcn_gat_forward_drop_f32): alpha_ijk is multiplied by q_ijk = keep ? scale : 0 in the gather, lse is unchanged, and
+    the mask is a pure function of (seed, stream, dst0 + i, src0 + j, k) that is never stored; gat_backward_dst and
+    gat_backward_src take the same tuple and draw the same mask.  None calls the plain entry point."""
     check_gat_heads(heads, Z.m(), "gat forward")
     _req(F.m() == Z.n() and out.shape() == (F.n(), Z.m()), "gat forward: shape mismatch")
     _req(s_dst.shape() == (F.n(), heads) and lse.shape() == (F.n(), heads) and s_src.shape() == (F.m(), heads),
          "gat forward: the scores and lse must be rows x heads")
+    extra = None if drop is None else _gat_drop_args(drop, "gat forward", F.n(), F.m())
     ip, ix, _ = F.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_forward_f32(
-        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(), heads,
-        Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer()))
+    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(), heads,
+            Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer())
+    if extra is None:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_forward_f32(*args))
+    else:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_forward_drop_f32(*args, *extra))
 
 
 def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
                      G: dn_matrix, out: dn_matrix, D: dn_matrix, ds_dst: dn_matrix, heads: int, slope: float = GAT_SLOPE,
-                     timer: Optional[str] = None) -> None:
+                     timer: Optional[str] = None, drop=None) -> None:
     """The half of the backward pass that sums over sources, over F's rows (mggcn_gat_backward_dst_f32): D[i, k] =
-    G[i, head k] . out[i, head k] and ds_dst[i, k] = sum_j alpha_ijk (G[i, head k] . Z[j, head k] - D[i, k]) lrelu'(x_ijk)."""
+    G[i, head k] . out[i, head k] and ds_dst[i, k] = sum_j alpha_ijk (G[i, head k] . Z[j, head k] - D[i, k]) lrelu'(x_ijk).
+    ``drop``: the forward's tuple (see gat_forward; mggcn_gat_backward_dst_drop_f32) -- the dot product carries q_ijk."""
     check_gat_heads(heads, Z.m(), "gat backward")
     _req(F.m() == Z.n() and G.shape() == (F.n(), Z.m()) and out.shape() == G.shape(), "gat backward: shape mismatch")
     _req(all(s.shape() == (F.n(), heads) for s in (s_dst, lse, D, ds_dst)) and s_src.shape() == (F.m(), heads),
          "gat backward: the scores, lse, D and ds must be rows x heads")
+    extra = None if drop is None else _gat_drop_args(drop, "gat backward", F.n(), F.m())
     ip, ix, _ = F.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_dst_f32(
-        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
-        lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer()))
+    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
+            lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer())
+    if extra is None:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_dst_f32(*args))
+    else:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_dst_drop_f32(*args, *extra))
 
 
 def gat_backward_src(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
                      D: dn_matrix, G: dn_matrix, att: dn_matrix, ds_dst: Optional[dn_matrix], ds_src: dn_matrix,
-                     G_Z: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+                     G_Z: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
     """The half that sums over destinations, over the rows of F^T (mggcn_gat_backward_src_f32; after gat_backward_dst):
     ds_src[j, k] = sum_i ds_ijk and G_Z[j, head k] = sum_i alpha_ijk G[i, head k] + ds_dst[j, k] att[0, head k] +
     ds_src[j, k] att[1, head k].  ds_dst is indexed by source here (the square case passes gat_backward_dst's); None leaves
-    its term out."""
+    its term out.  ``drop``: the forward's tuple (see gat_forward; mggcn_gat_backward_src_drop_f32) -- F_T's rows are the
+    sources (offset src0), its entries the destinations (offset dst0)."""
     check_gat_heads(heads, Z.m(), "gat backward")
     _req(F_T.n() == Z.n() and G.shape() == (F_T.m(), Z.m()) and G_Z.shape() == Z.shape(), "gat backward: shape mismatch")
     _req(att.shape() == (2, Z.m()), f"gat backward: att must be 2 x {Z.m()}")
     _req(all(s.shape() == (F_T.m(), heads) for s in (s_dst, lse, D)) and s_src.shape() == (F_T.n(), heads)
          and ds_src.shape() == (F_T.n(), heads) and (ds_dst is None or ds_dst.shape() == (F_T.n(), heads)),
          "gat backward: the scores, lse, D and ds must be rows x heads")
+    extra = None if drop is None else _gat_drop_args(drop, "gat backward", F_T.m(), F_T.n())
     ip, ix, _ = F_T.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_f32(
-        ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
-        lse.buffer(), D.buffer(), G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
-        Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m()))
+    args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
+            lse.buffer(), D.buffer(), G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
+            Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m())
+    if extra is None:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_f32(*args))
+    else:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_drop_f32(*args, *extra))
 
 
 def gat_scores_backward(ctx: context, ds_dst: dn_matrix, Z_dst: dn_matrix, ds_src: dn_matrix, Z_src: dn_matrix,
