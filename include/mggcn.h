@@ -410,6 +410,26 @@ void mggcn_gat_backward_src_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uin
                                      const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
                                      float *ds_src, float *G_Z, size_t ldgz, uint32_t threshold, float scale, uint64_t seed,
                                      uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
+/* The packed destination record of backward_src (opt-in).  mggcn_gat_pack_dst_f32 writes, per destination i and head k,
+ *   rec[(i K + k) 4 + {0, 1, 2, 3}] = s_dst[i, k], lse[i, k], D[i, k], 0
+ * from the three contiguous [n_rows x K] arrays; rec holds n_rows K 4 floats and must be 16-byte aligned.  The _rec twins
+ * of backward_src take the operands of mggcn_gat_backward_src_f32 / _drop_f32 with rec in the place of s_dst, lse and D
+ * ([n_cols x K] records, 16-byte aligned): the lane that owns an entry issues one 16-byte load where the plain kernel
+ * gathers three 4-byte scalars, the fourth float is never read, and the arithmetic is the plain kernel's -- ds_src and G_Z
+ * are bit for bit those of the plain call on the arrays the record was packed from.  On a row partition the record is also
+ * what a rank needs of every other rank's destinations: one collective of 16 K bytes per vertex. */
+void mggcn_gat_pack_dst_f32(mggcn_stream_t stream, const float *s_dst, const float *lse, const float *D, size_t n_rows,
+                            uint32_t K, float *rec);
+void mggcn_gat_backward_src_rec_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                    const uint32_t *t_indices, const float *Z, size_t ldz, const float *rec,
+                                    const float *s_src, const float *G, size_t ldg, const float *att, const float *ds_dst,
+                                    uint32_t K, uint32_t dh, float slope, float *ds_src, float *G_Z, size_t ldgz);
+void mggcn_gat_backward_src_rec_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                         const uint32_t *t_indices, const float *Z, size_t ldz, const float *rec,
+                                         const float *s_src, const float *G, size_t ldg, const float *att,
+                                         const float *ds_dst, uint32_t K, uint32_t dh, float slope, float *ds_src,
+                                         float *G_Z, size_t ldgz, uint32_t threshold, float scale, uint64_t seed,
+                                         uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
 /* cublasSasum   (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

@@ -12,6 +12,7 @@ Layout:
   gcn.py       sparse_linear / linear / gcn_layer / gcn (reference src/gcn.hpp)
   gat.py       attention / gat_layer / gat: graph attention layers (no reference counterpart)
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*)
+  dist_gat.py  dist_attention / dist_gat_layer / dist_gat: gat on the row partition (exported by dist)
   datasets.py  on-disk format + synthetic generators    (reference test/data/prep.py); the checkpoint file
   checkpoint.py  save / load / predict of gcn and dist_gcn (no reference counterpart)
   selection.py   model_selector: best epoch on a split, early stopping

@@ -108,6 +108,12 @@ PROTOTYPES = {
                                                c_size_t, c_uint32, c_uint32, c_float, vp, vp, c_uint32, c_float, c_uint64, c_uint32, c_uint32, c_uint32]),
     "mggcn_gat_backward_src_drop_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, c_size_t,
                                                vp, vp, c_uint32, c_uint32, c_float, vp, vp, c_size_t, c_uint32, c_float, c_uint64, c_uint32, c_uint32, c_uint32]),
+    "mggcn_gat_pack_dst_f32": (None, [vp, vp, vp, vp, c_size_t, c_uint32, vp]),
+    "mggcn_gat_backward_src_rec_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, c_size_t, vp, vp,
+                                              c_uint32, c_uint32, c_float, vp, vp, c_size_t]),
+    "mggcn_gat_backward_src_rec_drop_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, c_size_t, vp,
+                                                   vp, c_uint32, c_uint32, c_float, vp, vp, c_size_t, c_uint32, c_float,
+                                                   c_uint64, c_uint32, c_uint32, c_uint32]),
     "mggcn_gat_scores_backward_f32": (None, [vp, vp, vp, c_size_t, c_size_t, vp, vp, c_size_t, c_size_t, c_uint32,
                                              c_uint32, vp]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),

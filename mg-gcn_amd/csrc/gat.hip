@@ -23,6 +23,10 @@
 // groups through the same __shfl as the weight.  The softmax itself (maximum, sum, lse) takes every entry.  Nothing is
 // stored: the backward kernels draw the same words again, backward_src with the roles of row and entry swapped.  Duplicate
 // entries (i, j) share one bit.  DROP = false compiles to the kernels as they were.
+// The packed destination record (REC = true, the mggcn_gat_backward_src_rec*_f32 entry points): backward_src reads (s_dst,
+// lse, D) of an entry's destination as ONE 16-byte load from rec[(i K + k) 4 + {0, 1, 2}] (gat_pack_dst_kernel writes it; the
+// fourth float is padding nobody reads) where the plain kernel gathers three 4-byte scalars.  Only the loads differ: the
+// arithmetic, and so every bit of ds_src and G_Z, is the plain kernel's.  REC = false compiles to the kernels as they were.
 #include <algorithm>
 #include <cmath>
 
@@ -298,12 +302,14 @@ __global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, 
 //   G_Z[j, head k] = sum_i alpha_ijk G[i, head k] + ds_dst[j, k] att[0, head k] + ds_src[j, k] att[1, head k]
 // ---------------------------------------------------------------------------
 // DROP: the row is the source and the entry the destination, so the counter is (row, entry) here: the words of the forward
-template <int VEC, int NT, int U, bool DROP>
+// REC: s_dst, lse and D are not read; the three scalars of destination i and head k come from rec + (i K + k) 4
+template <int VEC, int NT, int U, bool DROP, bool REC>
 __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
                                                                const uint32_t *__restrict__ indices,
                                                                const float *__restrict__ Z, size_t ldz,
                                                                const float *__restrict__ s_dst, const float *__restrict__ s_src,
                                                                const float *__restrict__ lse, const float *__restrict__ D,
+                                                               const float *__restrict__ rec,
                                                                const float *__restrict__ G, size_t ldg,
                                                                const float *__restrict__ att, const float *__restrict__ ds_dst,
                                                                uint32_t K, uint32_t dh, float slope, uint32_t lg,
@@ -325,7 +331,12 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
         if (beg + lane < end) {
             c1 = indices[beg + lane];
             const size_t ik = (size_t)c1 * K + k;
-            x1 = s_dst[ik]; l1 = lse[ik]; D1 = D[ik];
+            if constexpr (REC) {
+                const float4 t = *reinterpret_cast<const float4 *>(rec + ik * 4);
+                x1 = t.x; l1 = t.y; D1 = t.z;
+            } else {
+                x1 = s_dst[ik]; l1 = lse[ik]; D1 = D[ik];
+            }
         }
         if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
         for (uint32_t base = beg; base < end; base += 64) {
@@ -335,7 +346,12 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
             x1 = 0.f; l1 = 0.f; D1 = 0.f; c2 = 0;
             if ((size_t)base + 64 + lane < end) {
                 const size_t ik = (size_t)c1 * K + k;
-                x1 = s_dst[ik]; l1 = lse[ik]; D1 = D[ik];
+                if constexpr (REC) {
+                    const float4 t = *reinterpret_cast<const float4 *>(rec + ik * 4);
+                    x1 = t.x; l1 = t.y; D1 = t.z;
+                } else {
+                    x1 = s_dst[ik]; l1 = lse[ik]; D1 = D[ik];
+                }
             }
             if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
             const uint32_t cnt = min(64u, end - base);
@@ -393,6 +409,15 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
             }
         }
     }
+}
+
+// ---------------------------------------------------------------------------
+// rec[(i K + k) 4 + {0, 1, 2, 3}] = s_dst[i, k], lse[i, k], D[i, k], 0: one thread per (destination, head), one 16-byte store
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gat_pack_dst_kernel(const float *__restrict__ s_dst, const float *__restrict__ lse,
+                                                           const float *__restrict__ D, size_t n, float4 *__restrict__ rec) {
+    const size_t ik = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (ik < n) rec[ik] = make_float4(s_dst[ik], lse[ik], D[ik], 0.f);
 }
 
 // ---------------------------------------------------------------------------
@@ -531,10 +556,12 @@ void gat_backward_dst(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, c
     MGGCN_CHECK_LAUNCH();
 }
 
+// rec != nullptr launches the REC = true kernels, which read it in place of s_dst, lse and D (all three nullptr then)
 void gat_backward_src(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
                       const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
-                      const float *lse, const float *D, const float *G, size_t ldg, const float *att, const float *ds_dst,
-                      uint32_t K, uint32_t dh, float slope, float *ds_src, float *G_Z, size_t ldgz, const gat_drop *dp) {
+                      const float *lse, const float *D, const float *rec, const float *G, size_t ldg, const float *att,
+                      const float *ds_dst, uint32_t K, uint32_t dh, float slope, float *ds_src, float *G_Z, size_t ldgz,
+                      const gat_drop *dp) {
     require_heads(K, dh);
     const size_t width = (size_t)K * dh;
     MGGCN_REQUIRE(ldz >= width && ldg >= width && ldgz >= width, "gat backward: leading dimension < heads * width per head");
@@ -542,20 +569,26 @@ void gat_backward_src(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, c
     MGGCN_REQUIRE(t_indptr != nullptr && Z != nullptr && s_src != nullptr && att != nullptr && ds_src != nullptr &&
                       G_Z != nullptr,
                   "gat backward: null operand");
-    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && s_dst != nullptr && lse != nullptr && D != nullptr && G != nullptr),
+    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && G != nullptr &&
+                                  (rec != nullptr || (s_dst != nullptr && lse != nullptr && D != nullptr))),
                   "gat backward: null operand");
     MGGCN_REQUIRE(G_Z != G && G_Z != Z, "gat backward: G_Z must not alias G or Z");
     const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(G_Z, ldgz) && aligned16(att);
     const head_geometry hg = head_geometry_for(dh, vec);
     const gat_drop d = dp ? *dp : gat_drop{};
-#define MGGCN_GAT_BWD_SRC_(V, NT, U, DROP)                                                                                   \
-    hipLaunchKernelGGL((gat_backward_src_kernel<V, NT, U, DROP>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream),   \
-                       n_rows, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, G, ldg, att, ds_dst, K, dh, slope, hg.lg,  \
-                       ds_src, G_Z, ldgz, d)
-#define MGGCN_GAT_BWD_SRC(V, NT, U)                \
-    do {                                           \
-        if (dp) MGGCN_GAT_BWD_SRC_(V, NT, U, true); \
-        else MGGCN_GAT_BWD_SRC_(V, NT, U, false);  \
+#define MGGCN_GAT_BWD_SRC_(V, NT, U, DROP, REC)                                                                              \
+    hipLaunchKernelGGL((gat_backward_src_kernel<V, NT, U, DROP, REC>), dim3((n_rows + 3) / 4), dim3(256), 0,                 \
+                       as_stream(stream), n_rows, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, rec, G, ldg, att, ds_dst,  \
+                       K, dh, slope, hg.lg, ds_src, G_Z, ldgz, d)
+#define MGGCN_GAT_BWD_SRC(V, NT, U)                             \
+    do {                                                        \
+        if (rec) {                                              \
+            if (dp) MGGCN_GAT_BWD_SRC_(V, NT, U, true, true);   \
+            else MGGCN_GAT_BWD_SRC_(V, NT, U, false, true);     \
+        } else {                                                \
+            if (dp) MGGCN_GAT_BWD_SRC_(V, NT, U, true, false);  \
+            else MGGCN_GAT_BWD_SRC_(V, NT, U, false, false);    \
+        }                                                       \
     } while (0)
     MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_SRC, vec, hg.nt);
 #undef MGGCN_GAT_BWD_SRC
@@ -599,8 +632,8 @@ MGGCN_API void mggcn_gat_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows
                                           const float *s_src, const float *lse, const float *D, const float *G, size_t ldg,
                                           const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
                                           float *ds_src, float *G_Z, size_t ldgz) {
-    gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, G, ldg, att, ds_dst, K, dh, slope,
-                     ds_src, G_Z, ldgz, nullptr);
+    gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, nullptr, G, ldg, att, ds_dst, K,
+                     dh, slope, ds_src, G_Z, ldgz, nullptr);
 }
 
 // The _drop twins: threshold == 0 (p = 0: every entry kept, scale = 1) launches the plain kernels, so the bits are the plain
@@ -634,8 +667,45 @@ MGGCN_API void mggcn_gat_backward_src_drop_f32(mggcn_stream_t stream, uint32_t n
                                                float *ds_src, float *G_Z, size_t ldgz, uint32_t threshold, float scale,
                                                uint64_t seed, uint32_t dropout_stream, uint32_t dst0, uint32_t src0) {
     const gat_drop dp = make_gat_drop(threshold, scale, seed, dropout_stream, dst0, n_cols, src0, n_rows);
-    gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, G, ldg, att, ds_dst, K, dh, slope,
-                     ds_src, G_Z, ldgz, threshold ? &dp : nullptr);
+    gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, nullptr, G, ldg, att, ds_dst, K,
+                     dh, slope, ds_src, G_Z, ldgz, threshold ? &dp : nullptr);
+}
+
+// The packed destination record: rec[(i K + k) 4 + {0, 1, 2, 3}] = s_dst[i, k], lse[i, k], D[i, k], 0
+MGGCN_API void mggcn_gat_pack_dst_f32(mggcn_stream_t stream, const float *s_dst, const float *lse, const float *D,
+                                      size_t n_rows, uint32_t K, float *rec) {
+    MGGCN_REQUIRE(K >= 1 && K <= MGGCN_GAT_MAX_HEADS, "gat supports 1 <= heads <= 16");
+    MGGCN_REQUIRE(n_rows <= 0xFFFFFFFFu, "gat pack: more than 2^32 - 1 rows");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(s_dst != nullptr && lse != nullptr && D != nullptr && rec != nullptr, "gat pack: null operand");
+    MGGCN_REQUIRE(aligned16(rec), "gat pack: rec must be 16-byte aligned");
+    const size_t n = n_rows * K;
+    hipLaunchKernelGGL(gat_pack_dst_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), s_dst, lse, D, n,
+                       reinterpret_cast<float4 *>(rec));
+    MGGCN_CHECK_LAUNCH();
+}
+
+// backward_src on the record: rec in the place of s_dst, lse and D; the bits of the plain call on the arrays it was packed from
+MGGCN_API void mggcn_gat_backward_src_rec_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                              const uint32_t *t_indices, const float *Z, size_t ldz, const float *rec,
+                                              const float *s_src, const float *G, size_t ldg, const float *att,
+                                              const float *ds_dst, uint32_t K, uint32_t dh, float slope, float *ds_src,
+                                              float *G_Z, size_t ldgz) {
+    MGGCN_REQUIRE(!n_rows || !n_cols || (rec != nullptr && aligned16(rec)), "gat backward: rec must be 16-byte aligned");
+    gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, nullptr, s_src, nullptr, nullptr, rec, G, ldg, att,
+                     ds_dst, K, dh, slope, ds_src, G_Z, ldgz, nullptr);
+}
+
+MGGCN_API void mggcn_gat_backward_src_rec_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols,
+                                                   const uint32_t *t_indptr, const uint32_t *t_indices, const float *Z,
+                                                   size_t ldz, const float *rec, const float *s_src, const float *G, size_t ldg,
+                                                   const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
+                                                   float *ds_src, float *G_Z, size_t ldgz, uint32_t threshold, float scale,
+                                                   uint64_t seed, uint32_t dropout_stream, uint32_t dst0, uint32_t src0) {
+    MGGCN_REQUIRE(!n_rows || !n_cols || (rec != nullptr && aligned16(rec)), "gat backward: rec must be 16-byte aligned");
+    const gat_drop dp = make_gat_drop(threshold, scale, seed, dropout_stream, dst0, n_cols, src0, n_rows);
+    gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, nullptr, s_src, nullptr, nullptr, rec, G, ldg, att,
+                     ds_dst, K, dh, slope, ds_src, G_Z, ldgz, threshold ? &dp : nullptr);
 }
 
 MGGCN_API void mggcn_gat_scores_backward_f32(mggcn_stream_t stream, const float *ds_dst, const float *Z_dst, size_t ldzd,

@@ -492,9 +492,11 @@ class dist_row_csr_matrix:
     all-gather schedule."""
 
     def __init__(self, dctx: dist_context, A: csr_matrix, p: Sequence[int], q: Sequence[int],
-                 chunks: Optional[int] = None, row_block: bool = False):
+                 chunks: Optional[int] = None, row_block: bool = False, keep_rows: bool = False):
         """``row_block``: A holds ONLY this rank's rows p[r]..p[r+1] (rank-local load, load_rank_local) instead
-        of the whole matrix; everything below needs no more than that."""
+        of the whole matrix; everything below needs no more than that.  ``keep_rows``: hold on to A until the first
+        row_block_global(), which then returns its rows in A's own entry order (see there); off by default, so that nothing
+        but dist_gat on a matrix with unordered rows pays for it."""
         assert list(p) == list(q), "the reference only ever passes p == q (src/main.cpp:148-149)"
         self.N_, self.M_ = int(p[-1]), A.m()
         self.p = list(p)
@@ -510,6 +512,8 @@ class dist_row_csr_matrix:
         self.remote_chunks = split_remote_chunks(self.remote, dctx.P, rows, K)
         self._dctx, self._rank, self._P = dctx, r, dctx.P
         self.halo = None
+        self._rows = (A, rb, re) if keep_rows else None                   # row_block_global(): read once, then dropped
+        self._row_block = None
 
     def build_halo(self, device) -> "dist_row_csr_matrix":
         """Index lists and the renumbered remote block of the halo exchange (mode="halo").  need[s] = rows of
@@ -533,6 +537,35 @@ class dist_row_csr_matrix:
             "remote": merge_blocks_halo(self.blocks, need, r),
         }
         return self
+
+    def row_block_global(self) -> csr_matrix:
+        """This rank's rows as ONE csr_matrix with global column indices ([n/P x m], host only): what a kernel that must
+        walk a whole row in one piece takes (dist_gat).  Built once, by merging ``blocks`` in block order with the offsets
+        q[j]: for a matrix whose rows list their columns ascending (any transpose() output, load_rank_local's pair) that
+        is the matrix's rows entry for entry.  A row in another order comes out sorted by block, which is another order
+        of its sums; with ``keep_rows=True`` at construction the rows are taken from the source matrix instead, entry for
+        entry whatever their order, and the source is dropped afterwards."""
+        if self._row_block is None and self._rows is not None:
+            A, rb, re = self._rows
+            lo, hi = int(A.indptr[rb]), int(A.indptr[re])
+            self._row_block = csr_matrix(A.indptr[rb:re + 1] - A.indptr[rb], A.indices[lo:hi].copy(), A.data[lo:hi].copy(),
+                                         self.M_)
+            self._rows = None
+        if self._row_block is None:
+            rows = self.blocks[0].n()
+            lens = [np.diff(b.indptr.astype(np.int64)) for b in self.blocks]
+            indptr = np.zeros(rows + 1, dtype=np.int64)
+            np.cumsum(np.sum(lens, axis=0), out=indptr[1:])
+            indices = np.empty(int(indptr[-1]), dtype=np.uint32)
+            data = np.empty(int(indptr[-1]), dtype=np.float32)
+            start = indptr[:-1].copy()
+            for j, (b, ln) in enumerate(zip(self.blocks, lens)):
+                pos = np.repeat(start, ln) + (np.arange(int(ln.sum())) - np.repeat(b.indptr[:-1].astype(np.int64), ln))
+                indices[pos] = b.indices + np.uint32(self.p[j])
+                data[pos] = b.data
+                start = start + ln
+            self._row_block = csr_matrix(indptr.astype(np.uint32), indices, data, self.M_)
+        return self._row_block
 
     def n(self): return self.N_
     def m(self): return self.M_
@@ -1130,3 +1163,6 @@ class dist_gcn(dropout_option, checkpoint_option):
         return self.loss_layer.read(dctx, host.numpy())
 
     def layers(self): return self.layers_
+
+
+from .dist_gat import dist_attention, dist_gat, dist_gat_layer      # noqa: E402,F401  (it imports the classes above)

@@ -1,0 +1,242 @@
+"""The GAT model on the 1D row partition: one process per GPU, the classes of gat.py on this rank's rows (opt-in; the
+reference has no attention layer).  DESIGN.md 3.10.1 has the algebra, the bytes and the measurements.
+
+Rank r owns rows [p_r, p_{r+1}) of every activation; W, b and att are replicated.  The three sparse kernels walk a whole
+row of F (forward, backward_dst) or of F^T (backward_src) in one piece, so a rank runs them over ITS row block of each
+matrix with global column indices (dist_row_csr_matrix.row_block_global), and what it needs of the other ranks is gathered
+first:
+
+  forward    Z_loc = H_loc W + b; ONE all-gather gives Z_all [n x out] (kept until the layer's backward has run); one scores
+             launch over Z_all gives s_dst_all and s_src_all (cheaper than a collective); gat_forward over the row block of
+             F with Z_all, the rank's rows of s_dst_all and s_src_all gives out_loc and lse_loc.
+  backward   the all-gather of G_loc into G_all starts at once on the comm stream; backward_dst runs meanwhile (it needs
+             nothing remote beyond Z_all) and gives D_loc, ds_dst_loc; the rank packs (s_dst, lse, D) of its destinations
+             into 16-byte records (ops.gat_pack_dst) and ONE all-gather of 16 x heads bytes per vertex delivers the records
+             of all destinations; backward_src over the row block of F^T (rows: local sources, columns: global
+             destinations) reads G_all and the records and gives ds_src_loc, G_Z_loc; scores_backward over the rank's rows
+             gives the rank's PARTIAL G_att, which lives in the ``extra`` floats of the layer's dist_row_linear and is
+             summed over the ranks by that layer's gradient all-reduce -- no collective of its own.
+
+Every row of F and of F^T is walked by one rank, whole, in the order the single-GPU kernel walks it: out, lse, D, ds_dst,
+ds_src and G_Z are the single-GPU rows bit for bit at any P (given the same Z and G), with attention dropout too -- the
+mask is drawn with dst0 = p_r, src0 = 0 over F and dst0 = 0, src0 = p_r over F^T.  Only sums over vertices (G_W, G_b, G_att,
+the loss sums) round differently.  A single rank exchanges nothing unless dist_context.self_gather.
+
+Not covered: the halo and rounds schedules, bf16 on the wire, layer norm, checkpoints, the C++ host layer."""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence
+
+import numpy as np
+
+from . import ops
+from .dist import (_repl_view, _torch, _wrap_local, dist_context, dist_gcn, dist_row_csr_matrix, dist_row_dn_matrix,
+                   dist_row_linear, dist_row_softmax_cross_entropy_loss, partition_bounds)
+from .gat import attention, check_heads, gat, gat_layer
+from .gcn import check_dropout, check_loss, dropout_option
+from .matrix import context, csr_matrix, dn_matrix
+
+
+class dist_attention(attention):
+    """gat.attention on one rank's rows: ``att`` replicated, the scores of ALL vertices (s_dst_all, s_src_all [n x heads];
+    s_dst / s_src are views of the rank's rows), lse, D, ds_dst, ds_src of the rank's rows, and the three exchanges.
+
+    ``grad_buffer``: 2 x out floats that some all-reduce sums over the ranks (the layer's dist_row_linear.extra) -- G_att
+    lives there and is this rank's partial until then; None allocates it.  ``G_all_buffer`` (n x out floats) and
+    ``rec_buffer`` (n x heads x 4 floats, 16-byte aligned) may be shared by the layers of a model: a layer's gather into
+    them is ordered on the comm stream after everything the compute stream has queued, the previous layer's backward_src
+    included.  Z_all is this layer's own: it is written in the forward and read until the backward, so a second forward
+    before the backward overwrites it, as gat_layer's Z is."""
+
+    def __init__(self, dctx: dist_context, name: str, n: int, out: int, heads: int, slope: float = ops.GAT_SLOPE,
+                 grad_buffer=None, G_all_buffer=None, rec_buffer=None):
+        torch = _torch()
+        p = partition_bounds(n, dctx.P)
+        dev = dctx.ctx.device
+        self.n, self.rows, self.row0 = int(n), p[dctx.rank + 1] - p[dctx.rank], p[dctx.rank]
+        attention.__init__(self, name, self.rows, self.rows, out, heads, slope, dev)
+        self._dctx = dctx
+        self.exchanging = dctx.P > 1 or dctx.self_gather
+        if grad_buffer is not None:
+            self.G_att = dn_matrix(2, out, grad_buffer)
+        K, lo, hi = self.heads, self.row0, self.row0 + self.rows
+        self.s_dst_all, self.s_src_all = dn_matrix(n, K, device=dev), dn_matrix(n, K, device=dev)
+        self.s_dst, self.s_src = dn_matrix(self.rows, K, self.s_dst_all.t[lo:hi]), dn_matrix(self.rows, K, self.s_src_all.t[lo:hi])
+        self.rec = torch.empty(self.rows * K * 4, dtype=torch.float32, device=dev)
+        self.Z_all = self.G_all = None
+        self.rec_all = self.rec
+        if self.exchanging:
+            self.Z_all = dn_matrix(n, out, device=dev)
+            self.G_all = dn_matrix(n, out, G_all_buffer) if G_all_buffer is not None else dn_matrix(n, out, device=dev)
+            self.rec_all = (rec_buffer if rec_buffer is not None else torch.empty(n * K * 4, dtype=torch.float32, device=dev))[:n * K * 4]
+
+    def _exchange(self, shard, out, tag: str) -> str:
+        """the all-gather of this rank's [rows x d] ``shard`` into ``out`` [n x d] on the comm stream, after everything the
+        compute stream has queued so far -- the producer of the shard and the last reader of ``out``; all_gather_rows
+        orders neither.  Returns the event that marks the gathered ``out``; timer: the collective on the comm stream."""
+        dctx, ctx, tag = self._dctx, self._dctx.ctx, self.name + tag
+        cs = dctx.bcast_stream_id()
+        ctx.record(tag + "_ready", 0)
+        ctx.wait(tag + "_ready", cs)
+        ctx.record(tag + "_0", cs)
+        dctx.all_gather_rows(shard, out, cs).wait(cs)
+        ctx.record(tag + "_1", cs)
+        ctx.register_timer(tag, tag + "_0", tag + "_1")
+        return tag + "_1"
+
+    def __call__(self, ctx: context, F: csr_matrix, Z: dn_matrix, out: dn_matrix, drop=None) -> None:
+        """out = the attention-weighted gather over ``F``, the rank's row block of the forward matrix ([n/P x n], global
+        columns), of the rows of Z_all that ``Z``, the rank's rows, is gathered into.  ``drop``: the tuple of
+        ops.gat_forward with dst0 = the rank's first row and src0 = 0 (None: the plain entry points)"""
+        n = self.name
+        if self.exchanging:
+            ctx.wait(self._exchange(Z.t, self.Z_all.t, "0_gat-exchange"), 0)
+        else:
+            self.Z_all = Z
+        ops.gat_scores(ctx, self.Z_all, self.att, self.s_dst_all, self.s_src_all, self.heads, n + "0_gat-scores")
+        ops.gat_forward(ctx, F, self.Z_all, self.s_dst, self.s_src_all, out, self.lse, self.heads, self.slope,
+                        n + "0_gat-forward", drop)
+
+    def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z: dn_matrix, G: dn_matrix, out: dn_matrix,
+                 G_Z: dn_matrix, drop=None) -> None:
+        """G_Z = the gradient of the rank's rows of Z, and this rank's partial G_att, from G = the gradient of ``out``;
+        ``F_T``: the rank's row block of F^T; ``drop``: what the forward was called with (backward_src, whose rows are
+        sources, takes it with dst0 and src0 swapped)"""
+        n, K = self.name, self.heads
+        G_all, ready = G, None
+        if self.exchanging:
+            ready, G_all = self._exchange(G.t, self.G_all.t, "1_gat-exchange-G"), self.G_all
+        ops.gat_backward_dst(ctx, F, self.Z_all, self.s_dst, self.s_src_all, self.lse, G, out, self.D, self.ds_dst, K,
+                             self.slope, n + "1_gat-backward-dst", drop)
+        ops.gat_pack_dst(ctx, self.s_dst, self.lse, self.D, self.rec)
+        if self.exchanging:
+            ctx.wait(self._exchange(self.rec.view(self.rows, K * 4), self.rec_all.view(self.n, K * 4), "1_gat-exchange-rec"), 0)
+            ctx.wait(ready, 0)
+        drop_src = None if drop is None else (*drop[:4], drop[5], drop[4])
+        # ds_dst is the rank's own: backward_src indexes it by row, and its rows are the rank's sources
+        ops.gat_backward_src_rec(ctx, F_T, Z, self.rec_all, self.s_src, G_all, self.att, self.ds_dst, self.ds_src, G_Z, K,
+                                 self.slope, n + "1_gat-backward-src", drop_src)
+        ops.gat_scores_backward(ctx, self.ds_dst, Z, self.ds_src, Z, self.G_att, K, n + "1_gat-scores-backward")
+
+
+class dist_gat_layer(gat_layer):
+    """gat.gat_layer on this rank's rows: a dist_row_linear, a dist_attention over the rank's row blocks ``F`` / ``F_T``
+    ([n/P x n] csr_matrix, global columns) and the activation.  The rank's partial G_att sits behind [G_W | G_b | tail] in
+    the linear's gradient buffer: attention.backward runs before lin.backward, whose all-reduce therefore sums it too."""
+
+    def __init__(self, dctx: dist_context, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int,
+                 activation: bool, slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None,
+                 G_all_buffer=None, rec_buffer=None, tail_floats: int = 8):
+        n, dev = F.m(), dctx.ctx.device
+        assert F.n() == F_T.n() and F_T.m() == n, "the rank's row blocks of a square matrix and of its transpose"
+        lin = dist_row_linear(dctx, name, in_, out, backward_out, True, 2 * out, tail_floats)
+        attn = dist_attention(dctx, name, n, out, heads, slope, lin.extra, G_all_buffer, rec_buffer)
+        # row0: dropout -- this rank draws ITS rows of the global mask
+        self._setup(name, F, F_T, lin, attn, attn.rows, in_, out, activation, G_Z_buffer, dev, attn.row0)
+        self.n = n
+        self.AHW = self.act                             # the layer's output under the name dist_gcn's plumbing reads
+
+    def __call__(self, dctx: dist_context, H: dist_row_dn_matrix) -> dist_row_dn_matrix:
+        return _wrap_local(gat_layer.__call__(self, dctx.ctx, H.local), self.n)
+
+    def backward(self, dctx: dist_context, G: dist_row_dn_matrix) -> Optional[dist_row_dn_matrix]:
+        G_out = gat_layer.backward(self, dctx.ctx, G.local)
+        return None if G_out is None else _wrap_local(G_out, self.n)
+
+    def finish_backward(self, dctx) -> None:
+        self.lin.finish_backward(dctx)
+
+    def adam_update(self, dctx, lr, beta1, beta2, weight_decay, eps):
+        gat_layer.adam_update(self, dctx.ctx, lr, beta1, beta2, weight_decay, eps)
+
+    def att(self): return _repl_view(self.attn.att)
+    def Gatt(self): return _repl_view(self.attn.G_att)
+
+
+class dist_gat(dropout_option):
+    """gat.gat on the row partition.
+
+    dist_gat(dctx, A, A_T, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0,
+    attn_dropout=0.0): ``A`` / ``A_T`` are the dist_row_csr_matrix pair dist_gcn takes (load_rank_local feeds both; the
+    layers aggregate over A_T's pattern, values are ignored), everything else means what it means on gat.  ValueError
+    before any device work or collective, on every rank alike, for what gat refuses and for n % P != 0.
+
+    Every rank calls every method with the same arguments.  set_dropout(p, seed, epoch, attn): a rank drops its rows of
+    the masks the single-GPU model draws (feature dropout with row0 = p_r; attention dropout see the module docstring).
+    __call__, train_forward, backward, adam_update, train_step (one synchronisation; the loss sums ride on the last layer's
+    gradient all-reduce), set_splits(dctx, Sd), split_metrics and layers() are dist_gcn's, which has no evaluate()
+    either: a plain call is the forward that never drops."""
+
+    def __init__(self, dctx: dist_context, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix, sizes: Sequence[int], heads=4,
+                 attn_slope: float = ops.GAT_SLOPE, loss: str = "softmax", fused: bool = True, weights=None,
+                 dropout: float = 0.0, attn_dropout: float = 0.0):
+        self.sizes = [int(s) for s in sizes]
+        self.heads = check_heads(self.sizes, heads)              # option checks come before any device work or collective
+        n_layers = len(self.sizes) - 1
+        self._attn_dropout_params = check_dropout(attn_dropout, n_layers)
+        self._init_dropout(dropout, n_layers)
+        self.attn_dropout_p = float(attn_dropout)
+        self.loss = check_loss(loss)
+        if not (A.n() == A.m() == A_T.n() == A_T.m()):
+            raise ValueError(f"dist_gat needs a square matrix and its transpose, got {A.n()} x {A.m()} and {A_T.n()} x {A_T.m()}")
+        n = A.n()
+        p = partition_bounds(n, dctx.P)
+        self.attn_slope, self._out_width, self.fused, self._adam, self._loss_host = float(attn_slope), self.sizes[-1], bool(fused), None, None
+        torch = _torch()
+        dev = dctx.ctx.device
+        self.n, self.row0 = n, p[dctx.rank]
+        self.loss_layer = dist_row_softmax_cross_entropy_loss(f"{n_layers}_", True, True, self.loss)
+        self.F, self.F_T = A_T.row_block_global(), A.row_block_global()          # forward over A_T's rows, like gcn
+        widest = max(self.sizes[1:])
+        exchanging = dctx.P > 1 or dctx.self_gather
+        self.G_Z_buffer = torch.empty(n // dctx.P * widest, dtype=torch.float32, device=dev)
+        # the gathered gradient and the gathered records: one buffer each for all layers (Z_all is per layer)
+        self.G_all_buffer = torch.empty(n * widest, dtype=torch.float32, device=dev) if exchanging else None
+        self.rec_buffer = torch.empty(n * max(self.heads) * 4, dtype=torch.float32, device=dev) if exchanging else None
+        self.layers_: List[dist_gat_layer] = []
+        for i in range(n_layers):
+            last = i + 1 == n_layers
+            self.layers_.append(dist_gat_layer(dctx, f"{i}_", self.F, self.F_T, self.sizes[i], self.sizes[i + 1], self.heads[i],
+                                               not last, self.attn_slope, i != 0, self.G_Z_buffer, self.G_all_buffer,
+                                               self.rec_buffer, ops.BCE_SUMS if self.loss == "bce" and last else 8))
+        if weights is not None:
+            assert len(weights) == n_layers
+            for layer, w in zip(self.layers_, weights):
+                layer.W().local.init(np.asarray(w[0], dtype=np.float32))
+                layer.b().local.init(np.asarray(w[1], dtype=np.float32))
+                if len(w) > 2:
+                    layer.attn.init(w[2])
+
+    # gat's own functions, borrowed unbound (this class is no gat: its layers and its calls take a dist_context).  set_dropout
+    # touches _dropout_layers, _dropout_params, dropout_p, dropout_seed, dropout_epoch (dropout_option) and
+    # _attn_dropout_params, attn_dropout_p; _arm_dropout reads those and layers_, and sets every layer's ``dropout`` and
+    # ``attn_dropout``.  Nothing else.
+    set_dropout = gat.set_dropout
+
+    def _arm_dropout(self, training: bool) -> None:
+        """gat's, with the attention mask's destinations offset by the rank's first row"""
+        gat._arm_dropout(self, training)
+        for layer in self.layers_:
+            if layer.attn_dropout is not None:
+                layer.attn_dropout = (*layer.attn_dropout[:4], self.row0, 0)
+
+    def __call__(self, dctx: dist_context, H: dist_row_dn_matrix, training: bool = False) -> dist_row_dn_matrix:
+        """the forward pass; ``training``: a training forward (train_forward / train_step), the only kind that drops"""
+        self._arm_dropout(training)
+        for layer in self.layers_:
+            H = layer(dctx, H)
+        return H
+
+    def layers(self) -> List[dist_gat_layer]:
+        return self.layers_
+
+    # the model-level plumbing is dist_gcn's, word for word: it only touches what the two classes share (loss_layer, layers_
+    # with lin / AHW / finish_backward / params, loss, fused, _adam, _loss_host, _out_width and the calls above)
+    set_splits = dist_gcn.set_splits
+    split_metrics = dist_gcn.split_metrics
+    _check_targets = dist_gcn._check_targets
+    train_forward = dist_gcn.train_forward
+    backward = dist_gcn.backward
+    adam_update = dist_gcn.adam_update
+    train_step = dist_gcn.train_step
+

@@ -22,7 +22,9 @@ Two dropouts (opt-in, both 0 by default: nothing new is launched or allocated), 
     (mggcn_gat_*_drop_f32) -- no edge mask is stored.  Duplicate entries (i, j) share one bit.
 set_dropout(p, seed, epoch, attn) sets both; evaluate() and a plain call never drop.
 
-Not covered: dist_gcn, the C++ host layer and CLI, checkpoints, layer norm, bf16 gathers.
+The row-partitioned form is dist_gat.dist_gat (one process per GPU; DESIGN.md 3.10 "The row partition").
+
+Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, checkpoints, layer norm, bf16 gathers.
 """
 from __future__ import annotations
 
@@ -120,26 +122,33 @@ class gat_layer:
                  slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None):
         n = F.n()
         assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
-        self.name, self.F, self.F_T, self.activation = name, F, F_T, bool(activation)
         # the linear's own fused kernels in every mode: gat(fused=...) only picks how Adam is launched
-        self.lin = linear(name, in_, out, backward_out, True)
-        self.attn = attention(name, n, n, out, heads, slope)
-        self.Z, self.out = dn_matrix(n, out), dn_matrix(n, out)
-        self.act = dn_matrix(n, out) if activation else self.out
-        self.G_Z = dn_matrix(n, out, G_Z_buffer) if G_Z_buffer is not None else dn_matrix(n, out)
-        self.G_out = dn_matrix(n, in_) if backward_out else None
+        self._setup(name, F, F_T, linear(name, in_, out, backward_out, True), attention(name, n, n, out, heads, slope), n, in_,
+                    out, activation, G_Z_buffer)
+
+    def _setup(self, name: str, F: csr_matrix, F_T: csr_matrix, lin, attn, rows: int, in_: int, out: int, activation: bool,
+               G_Z_buffer=None, device=None, row0: int = 0) -> None:
+        """everything a layer holds besides building ``lin`` and ``attn``: its buffers over ``rows`` rows and the per-forward
+        state (the row-partitioned layer, dist_gat.dist_gat_layer, calls it with its rank's pieces)"""
+        self.name, self.F, self.F_T, self.activation = name, F, F_T, bool(activation)
+        self.lin, self.attn = lin, attn
+        self.Z, self.out = dn_matrix(rows, out, device=device), dn_matrix(rows, out, device=device)
+        self.act = dn_matrix(rows, out, device=device) if activation else self.out
+        self.G_Z = dn_matrix(rows, out, G_Z_buffer) if G_Z_buffer is not None else dn_matrix(rows, out, device=device)
+        self.G_out = dn_matrix(rows, in_, device=device) if lin.backward_out else None
         self.H: Optional[dn_matrix] = None
         # set by the model before every forward and read again by backward(): ``dropout`` -- (threshold, scale, seed, stream)
         # of ops.dropout_raw for my input and the gradient I return; ``attn_dropout`` -- the tuple of ops.gat_forward
         self.dropout = None
         self.attn_dropout = None
+        self.row0 = int(row0)               # the global index of my first row (dist_gat.dist_gat_layer: the rank's)
 
     def _drop(self, ctx: context, M: dn_matrix, tag: str) -> None:
         """M = dropout(M) in place with this forward's mask: H on the way up ("0"), G_out on the way down ("1")"""
         n = self.name
         threshold, scale, seed, stream = self.dropout
         ctx.record(n + tag + "_0_dropout", 0)
-        ops.dropout_raw(ctx, M, M, threshold, scale, seed, stream, 0)
+        ops.dropout_raw(ctx, M, M, threshold, scale, seed, stream, self.row0)
         ctx.record(n + tag + "_1_dropout", 0)
         ctx.register_timer(n + tag + "_dropout", n + tag + "_0_dropout", n + tag + "_1_dropout")
 

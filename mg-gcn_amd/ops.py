@@ -532,6 +532,47 @@ def gat_backward_src(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matr
         _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_drop_f32(*args, *extra))
 
 
+def _req_gat_rec(rec, rows: int, heads: int, what: str) -> None:
+    """``rec``: a float32 device tensor of rows x heads x 4 floats, contiguous and 16-byte aligned (the library would exit)"""
+    _req(rec.is_contiguous() and rec.numel() == rows * heads * 4 and rec.element_size() == 4 and rec.is_floating_point(),
+         f"{what}: rec must hold {rows} x {heads} records of 4 floats")
+    _req(rec.data_ptr() % 16 == 0, f"{what}: rec must be 16-byte aligned")
+
+
+def gat_pack_dst(ctx: context, s_dst: dn_matrix, lse: dn_matrix, D: dn_matrix, rec, timer: Optional[str] = None) -> None:
+    """rec[(i K + k) 4 + {0, 1, 2, 3}] = s_dst[i, k], lse[i, k], D[i, k], 0 (mggcn_gat_pack_dst_f32): the three scalars
+    gat_backward_src needs of a destination as one 16-byte record.  ``rec``: a float32 device tensor of rows x heads x 4."""
+    rows, heads = s_dst.shape()
+    _req(1 <= heads <= GAT_MAX_HEADS, f"gat pack supports 1 <= heads <= {GAT_MAX_HEADS}")
+    _req(lse.shape() == (rows, heads) and D.shape() == (rows, heads), "gat pack: s_dst, lse and D must have one shape")
+    _req_gat_rec(rec, rows, heads, "gat pack")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_pack_dst_f32(ctx.stream(0), s_dst.buffer(), lse.buffer(), D.buffer(), rows,
+                                                                  heads, rec.data_ptr()))
+
+
+def gat_backward_src_rec(ctx: context, F_T: csr_matrix, Z: dn_matrix, rec, s_src: dn_matrix, G: dn_matrix, att: dn_matrix,
+                         ds_dst: Optional[dn_matrix], ds_src: dn_matrix, G_Z: dn_matrix, heads: int, slope: float = GAT_SLOPE,
+                         timer: Optional[str] = None, drop=None) -> None:
+    """gat_backward_src with the destinations' (s_dst, lse, D) as the records of gat_pack_dst (mggcn_gat_backward_src_rec_f32
+    / _rec_drop_f32): one 16-byte load per (entry, head) where the plain call gathers three scalars, and the bits of the
+    plain call on the arrays the record was packed from.  ``rec``: F_T.m() x heads x 4 floats."""
+    check_gat_heads(heads, Z.m(), "gat backward")
+    _req(F_T.n() == Z.n() and G.shape() == (F_T.m(), Z.m()) and G_Z.shape() == Z.shape(), "gat backward: shape mismatch")
+    _req(att.shape() == (2, Z.m()), f"gat backward: att must be 2 x {Z.m()}")
+    _req(s_src.shape() == (F_T.n(), heads) and ds_src.shape() == (F_T.n(), heads)
+         and (ds_dst is None or ds_dst.shape() == (F_T.n(), heads)), "gat backward: the scores and ds must be rows x heads")
+    _req_gat_rec(rec, F_T.m(), heads, "gat backward")
+    extra = None if drop is None else _gat_drop_args(drop, "gat backward", F_T.m(), F_T.n())
+    ip, ix, _ = F_T.device(ctx.device)
+    args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), rec.data_ptr(), s_src.buffer(),
+            G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads, Z.m() // heads, slope,
+            ds_src.buffer(), G_Z.buffer(), G_Z.m())
+    if extra is None:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_rec_f32(*args))
+    else:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_rec_drop_f32(*args, *extra))
+
+
 def gat_scores_backward(ctx: context, ds_dst: dn_matrix, Z_dst: dn_matrix, ds_src: dn_matrix, Z_src: dn_matrix,
                         G_att: dn_matrix, heads: int, timer: Optional[str] = None) -> None:
     """G_att[0] = the column sums of ds_dst[i, k(c)] Z_dst[i, c], G_att[1] those of ds_src and Z_src
