@@ -430,6 +430,46 @@ void mggcn_gat_backward_src_rec_drop_f32(mggcn_stream_t stream, uint32_t n_rows,
                                          const float *ds_dst, uint32_t K, uint32_t dh, float slope, float *ds_src,
                                          float *G_Z, size_t ldgz, uint32_t threshold, float scale, uint64_t seed,
                                          uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
+/* Dynamic graph attention (GATv2; opt-in).  F, K, dh, the limits and the column layout of a head are those of the GAT block
+ * above; Zs is the source transform (one row per source: the row that gets aggregated), Zd the destination transform (one
+ * row per destination), att is [1 x K dh] contiguous, and lse / D are contiguous [destinations x K].  With
+ * t_ijk[c] = Zd[i, k dh + c] + Zs[j, k dh + c], u = t > 0 ? t : slope t, lrelu' = t > 0 ? 1 : slope,
+ * e_ijk = sum_c att[k dh + c] u_ijk[c] and alpha_ijk = exp(e_ijk - lse[i, k]):
+ *   forward       lse[i, k] = log sum_j exp(e_ijk) (max-subtracted);  out[i, k dh + c] = sum_j alpha_ijk Zs[j, k dh + c];
+ *                 a row without entries gets lse = 0 and an out row of +0.0 (written, not skipped); a row of one entry
+ *                 copies its source's row bit for bit
+ *   backward_dst  over the rows of F:  D[i, k] = sum_c G[i, k dh + c] out[i, k dh + c];
+ *                 ds_ijk = alpha_ijk (sum_c G[i, k dh + c] Zs[j, k dh + c] - D[i, k]);
+ *                 G_Zd[i, k dh + c] = att[k dh + c] sum_j ds_ijk lrelu'(t_ijk[c]);  P[i, k dh + c] = sum_j ds_ijk u_ijk[c]
+ *                 (row i's share of G_att; a row without entries gets zeros in both)
+ *   att_grad      G_att[c] = sum_i P[i, c] over n_rows rows of `width` columns (1 <= width <= MGGCN_GAT_MAX_WIDTH);
+ *                 n_rows == 0 writes zeros
+ *   backward_src  over the rows of F^T (n_rows sources x n_cols destinations; call it after backward_dst, whose D it reads):
+ *                 G_Zs[j, k dh + c] = sum_i (alpha_ijk G[i, k dh + c] + ds_ijk att[k dh + c] lrelu'(t_ijk[c]))
+ * The score of an entry exists only once the source's head-row has been gathered, so each sparse call computes e on the
+ * rows it gathers; nothing of nnz x K is stored or read.  No atomics: sums over sources run over F's rows, sums over
+ * destinations over F^T's, the softmax folds its lane groups in a fixed order, and att_grad goes through per-workgroup
+ * partials in the per-(device, stream) scratch of mggcn_gat_scores_backward_f32, added in a fixed order -- two calls on the
+ * same input give the same bits in every output, and rows [r0, r1) of a sparse call passed as a call of their own (indptr +
+ * r0, the row operands moved by r0 rows) give the whole call's rows bit for bit.  One wave per row, no plan: correct for any
+ * input, slow on rows of many thousand entries.  16-byte loads when dh % 4 == 0 and every dense operand of the call,
+ * att included, is 16-byte aligned with a leading dimension that is a multiple of 4; single elements otherwise.  Zs and Zd
+ * may be the two halves of one [rows x 2 K dh] buffer (ld = 2 K dh), and so may G_Zs and G_Zd.  out must not alias Zs or Zd;
+ * G_Zd, P and G_Zs must not alias an input.  n_rows == 0 returns.  Leading dimensions are checked against K dh. */
+void mggcn_gatv2_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                             const uint32_t *indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                             const float *att, uint32_t K, uint32_t dh, float slope, float *out, size_t ldo, float *lse);
+void mggcn_gatv2_backward_dst_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                  const uint32_t *indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                                  const float *att, const float *lse, const float *G, size_t ldg, const float *out,
+                                  size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *G_Zd, size_t ldgzd,
+                                  float *P, size_t ldp);
+void mggcn_gatv2_att_grad_f32(mggcn_stream_t stream, const float *P, size_t ldp, size_t n_rows, uint32_t width,
+                              float *G_att);
+void mggcn_gatv2_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                  const uint32_t *t_indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                                  const float *att, const float *lse, const float *D, const float *G, size_t ldg,
+                                  uint32_t K, uint32_t dh, float slope, float *G_Zs, size_t ldgzs);
 /* cublasSasum   (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

@@ -1,0 +1,413 @@
+// gatv2.hip -- dynamic graph attention (GATv2; Brody, Alon, Yahav: "How Attentive are Graph Attention Networks?") on
+// gfx950.  The score has its non-linearity INSIDE the dot product,
+//     t_ijk[c] = Zd[i, k dh + c] + Zs[j, k dh + c],   e_ijk = sum_c att[k dh + c] lrelu(t_ijk[c]),
+// so the score of an entry exists only after the source's head-row has been gathered: there are no [rows x K] score
+// scalars to stream, and every sparse kernel computes e with the group butterfly on the rows it gathers anyway.
+//
+// Layout: gat.hip's (gat_internal.h) -- one wave per CSR row, 64-entry chunks with the indices two chunks ahead, the heads
+// one after the other, G = 64 / LPR groups of LPR lanes that each hold one head-row of a neighbour, (VEC, NT, U) variants.
+//   * forward: ONE pass over a row with one gather of Zs per entry.  The group that gathered a neighbour computes its score,
+//     so the running maximum is kept PER GROUP (m, sum and the accumulators of a group are rescaled when its maximum
+//     moves); at the end the groups meet at the wave's maximum M: group g enters with the factor exp(m_g - M), the sums
+//     and accumulators are folded in the fixed order of fold_groups, out = acc / sum and lse = M + log(sum).
+//   * backward_dst (rows of F): D, G_Zd and P[i] = sum_j ds_ijk u_ijk, row i's share of G_att; e and dalpha are two
+//     butterflies over the same gathered row.
+//   * backward_src (rows of F^T): gathers the destination's head-rows of Zd and G, recomputes e, dalpha, alpha and ds, and
+//     accumulates alpha G_i + v.  lse and D of the destination are two 4-byte gathers by the lane that owns the entry, one
+//     chunk ahead (DESIGN.md 3.10.2 says why they are not packed).
+//   * att_grad: the column sums of P through per-workgroup partials and colsum_final_kernel (reduce.h).
+// Nothing of nnz x K is stored, no atomics, a row's result depends on that row alone: the same bits on every call and for
+// every split of the rows between calls.
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+#include "gat_internal.h"
+#include "reduce.h"
+#include "scratch_internal.h"
+
+namespace {
+
+// this lane's part of e = sum_c a[c] lrelu(zd[c] + z[c]) (columns beyond dh hold zeros in all three)
+template <int VEC, int NT>
+__device__ __forceinline__ float score_head_row(const float (&a)[NT][VEC], const float (&zd)[NT][VEC],
+                                                const float (&z)[NT][VEC], float slope) {
+    float p = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int v = 0; v < VEC; v++) p = fmaf(a[t][v], gat_lrelu(zd[t][v] + z[t][v], slope), p);
+    return p;
+}
+
+// ---------------------------------------------------------------------------
+// forward: lse[i, k] and out[i, head k] = sum_j alpha_ijk Zs[j, head k] over the entries j of row i
+// ---------------------------------------------------------------------------
+template <int VEC, int NT, int U>
+__global__ __launch_bounds__(256) void gatv2_forward_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                            const uint32_t *__restrict__ indices,
+                                                            const float *__restrict__ Zs, size_t ldzs,
+                                                            const float *__restrict__ Zd, size_t ldzd,
+                                                            const float *__restrict__ att, uint32_t K, uint32_t dh,
+                                                            float slope, uint32_t lg, float *__restrict__ out, size_t ldo,
+                                                            float *__restrict__ lse) {
+    MGGCN_GAT_WAVE_ROW(n_rows);
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    for (uint32_t k = 0; k < K; k++) {
+        float zd[NT][VEC], a[NT][VEC], acc[NT][VEC];
+        load_head_row<VEC, NT>(zd, Zd + row * ldzd + (size_t)k * dh, lpr, sub, dh);
+        load_head_row<VEC, NT>(a, att + (size_t)k * dh, lpr, sub, dh);
+#pragma unroll
+        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
+        const float *__restrict__ Zk = Zs + (size_t)k * dh;
+        float m = -INFINITY, sum = 0.f;             // of my group: every lane of a group holds the same bits
+        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead
+        if (beg + lane < end) c1 = indices[beg + lane];
+        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        for (uint32_t base = beg; base < end; base += 64) {
+            const uint32_t my_c = c1;
+            c1 = c2;
+            c2 = 0;
+            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
+            const uint32_t cnt = min(64u, end - base);
+            for (uint32_t j = 0; j < cnt; j += n_grp * U) {
+                float z[U][NT][VEC], e[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const uint32_t c = __shfl(my_c, src & 63);
+                    load_head_row<VEC, NT>(z[u], Zk + (size_t)c * ldzs, lpr, sub, dh, src < cnt);
+                    e[u] = score_head_row<VEC, NT>(a, zd, z[u], slope);
+                }
+                float m_new = m;
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    e[u] = group_sum(e[u], lpr);
+                    if (j + u * n_grp + grp >= cnt) e[u] = -INFINITY;
+                    m_new = fmaxf(m_new, e[u]);
+                }
+                // m_new = -inf: my group has not met an entry yet, nothing to rescale and every weight below is 0
+                const float scale = m_new == -INFINITY ? 1.f : expf(m - m_new);     // 0 at the group's first entry
+                float w[U], ws = 0.f;
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    w[u] = e[u] == -INFINITY ? 0.f : expf(e[u] - m_new);
+                    ws += w[u];
+                }
+                sum = fmaf(sum, scale, ws);
+                m = m_new;
+#pragma unroll
+                for (int t = 0; t < NT; t++)
+#pragma unroll
+                    for (int v = 0; v < VEC; v++) {
+                        float s = acc[t][v] * scale;
+#pragma unroll
+                        for (int u = 0; u < U; u++) s = fmaf(w[u], z[u][t][v], s);
+                        acc[t][v] = s;
+                    }
+            }
+        }
+        // the groups meet at the wave's maximum; a group that never met an entry (m = -inf) enters with 0
+        float M = m;
+        for (uint32_t off = lpr; off < 64; off <<= 1) M = fmaxf(M, __shfl_xor(M, off));
+        const float f = m == -INFINITY ? 0.f : expf(m - M);
+        sum = fold_groups(sum * f, lpr);
+        const float inv = beg < end ? 1.f / sum : 0.f;
+        if (lane == 0) lse[row * K + k] = beg < end ? M + logf(sum) : 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) acc[t][v] = fold_groups(acc[t][v] * f, lpr) * inv;
+            const uint32_t col = (t * lpr + sub) * VEC;
+            if (grp == 0 && col < dh) storev<VEC>(out + row * ldo + (size_t)k * dh + col, acc[t]);   // an empty row: +0.0
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// backward over the rows of F:  D[i, k] = G[i, head k] . out[i, head k],  ds_ijk = alpha_ijk (G[i, head k] . Zs[j, head k] - D[i, k])
+//   G_Zd[i, k dh + c] = att[k dh + c] sum_j ds_ijk lrelu'(t_ijk[c]),  P[i, k dh + c] = sum_j ds_ijk lrelu(t_ijk[c])
+// ---------------------------------------------------------------------------
+template <int VEC, int NT, int U>
+__global__ __launch_bounds__(256) void gatv2_backward_dst_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                                 const uint32_t *__restrict__ indices,
+                                                                 const float *__restrict__ Zs, size_t ldzs,
+                                                                 const float *__restrict__ Zd, size_t ldzd,
+                                                                 const float *__restrict__ att, const float *__restrict__ lse,
+                                                                 const float *__restrict__ G, size_t ldg,
+                                                                 const float *__restrict__ out, size_t ldo, uint32_t K,
+                                                                 uint32_t dh, float slope, uint32_t lg, float *__restrict__ D,
+                                                                 float *__restrict__ G_Zd, size_t ldgzd, float *__restrict__ P,
+                                                                 size_t ldp) {
+    MGGCN_GAT_WAVE_ROW(n_rows);
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    for (uint32_t k = 0; k < K; k++) {
+        float g[NT][VEC], zd[NT][VEC], a[NT][VEC], accv[NT][VEC], accp[NT][VEC];
+        load_head_row<VEC, NT>(g, G + row * ldg + (size_t)k * dh, lpr, sub, dh);
+        float Dk;
+        {
+            float o[NT][VEC];
+            load_head_row<VEC, NT>(o, out + row * ldo + (size_t)k * dh, lpr, sub, dh, grp == 0);   // one group's worth
+            Dk = wave_sum(dot_head_row<VEC, NT>(g, o));
+        }
+        load_head_row<VEC, NT>(zd, Zd + row * ldzd + (size_t)k * dh, lpr, sub, dh);
+        load_head_row<VEC, NT>(a, att + (size_t)k * dh, lpr, sub, dh);
+#pragma unroll
+        for (int t = 0; t < NT; t++) { zerov<VEC>(accv[t]); zerov<VEC>(accp[t]); }
+        const float ls = lse[row * K + k];
+        const float *__restrict__ Zk = Zs + (size_t)k * dh;
+        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead
+        if (beg + lane < end) c1 = indices[beg + lane];
+        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        for (uint32_t base = beg; base < end; base += 64) {
+            const uint32_t my_c = c1;
+            c1 = c2;
+            c2 = 0;
+            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
+            const uint32_t cnt = min(64u, end - base);
+            for (uint32_t j = 0; j < cnt; j += n_grp * U) {
+                float z[U][NT][VEC], pe[U], pd[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const uint32_t c = __shfl(my_c, src & 63);
+                    load_head_row<VEC, NT>(z[u], Zk + (size_t)c * ldzs, lpr, sub, dh, src < cnt);
+                    pe[u] = score_head_row<VEC, NT>(a, zd, z[u], slope);
+                    pd[u] = dot_head_row<VEC, NT>(g, z[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const float e = group_sum(pe[u], lpr), da = group_sum(pd[u], lpr);
+                    const float ds = j + u * n_grp + grp < cnt ? expf(e - ls) * (da - Dk) : 0.f;
+                    const float dss = ds * slope;
+#pragma unroll
+                    for (int t = 0; t < NT; t++)
+#pragma unroll
+                        for (int v = 0; v < VEC; v++) {
+                            const float tt = zd[t][v] + z[u][t][v];
+                            accv[t][v] += tt > 0.f ? ds : dss;
+                            accp[t][v] = fmaf(ds, gat_lrelu(tt, slope), accp[t][v]);
+                        }
+                }
+            }
+        }
+        if (lane == 0) D[row * K + k] = Dk;
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) {
+                accv[t][v] = fold_groups(accv[t][v], lpr) * a[t][v];
+                accp[t][v] = fold_groups(accp[t][v], lpr);
+            }
+            const uint32_t col = (t * lpr + sub) * VEC;
+            if (grp == 0 && col < dh) {
+                storev<VEC>(G_Zd + row * ldgzd + (size_t)k * dh + col, accv[t]);
+                storev<VEC>(P + row * ldp + (size_t)k * dh + col, accp[t]);
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// backward over the rows of F^T (row j lists the destinations i that gather j):
+//   G_Zs[j, k dh + c] = sum_i (alpha_ijk G[i, k dh + c] + ds_ijk att[k dh + c] lrelu'(t_ijk[c]))
+// ---------------------------------------------------------------------------
+template <int VEC, int NT, int U>
+__global__ __launch_bounds__(256) void gatv2_backward_src_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                                 const uint32_t *__restrict__ indices,
+                                                                 const float *__restrict__ Zs, size_t ldzs,
+                                                                 const float *__restrict__ Zd, size_t ldzd,
+                                                                 const float *__restrict__ att, const float *__restrict__ lse,
+                                                                 const float *__restrict__ D, const float *__restrict__ G,
+                                                                 size_t ldg, uint32_t K, uint32_t dh, float slope, uint32_t lg,
+                                                                 float *__restrict__ G_Zs, size_t ldgzs) {
+    MGGCN_GAT_WAVE_ROW(n_rows);
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    for (uint32_t k = 0; k < K; k++) {
+        float zs[NT][VEC], a[NT][VEC], acc[NT][VEC];
+        load_head_row<VEC, NT>(zs, Zs + row * ldzs + (size_t)k * dh, lpr, sub, dh);
+        load_head_row<VEC, NT>(a, att + (size_t)k * dh, lpr, sub, dh);
+#pragma unroll
+        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
+        const float *__restrict__ Zdk = Zd + (size_t)k * dh;
+        const float *__restrict__ Gk = G + (size_t)k * dh;
+        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead, the destinations' lse and D one chunk ahead
+        float l1 = 0.f, D1 = 0.f;
+        if (beg + lane < end) {
+            c1 = indices[beg + lane];
+            l1 = lse[(size_t)c1 * K + k];
+            D1 = D[(size_t)c1 * K + k];
+        }
+        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        for (uint32_t base = beg; base < end; base += 64) {
+            const uint32_t my_c = c1;
+            const float my_l = l1, my_D = D1;
+            c1 = c2;
+            l1 = 0.f; D1 = 0.f; c2 = 0;
+            if ((size_t)base + 64 + lane < end) {
+                l1 = lse[(size_t)c1 * K + k];
+                D1 = D[(size_t)c1 * K + k];
+            }
+            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
+            const uint32_t cnt = min(64u, end - base);
+            for (uint32_t j = 0; j < cnt; j += n_grp * U) {
+                float zv[U][NT][VEC], gv[U][NT][VEC], pe[U], pd[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const uint32_t c = __shfl(my_c, src & 63);
+                    load_head_row<VEC, NT>(zv[u], Zdk + (size_t)c * ldzd, lpr, sub, dh, src < cnt);
+                    load_head_row<VEC, NT>(gv[u], Gk + (size_t)c * ldg, lpr, sub, dh, src < cnt);
+                    pe[u] = score_head_row<VEC, NT>(a, zv[u], zs, slope);
+                    pd[u] = dot_head_row<VEC, NT>(zs, gv[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t src = j + u * n_grp + grp;
+                    const float l = __shfl(my_l, src & 63), Dv = __shfl(my_D, src & 63);
+                    const float e = group_sum(pe[u], lpr), da = group_sum(pd[u], lpr);
+                    const float al = src < cnt ? expf(e - l) : 0.f;
+                    const float ds = al * (da - Dv), dss = ds * slope;
+#pragma unroll
+                    for (int t = 0; t < NT; t++)
+#pragma unroll
+                        for (int v = 0; v < VEC; v++) {
+                            const float tt = zv[u][t][v] + zs[t][v];
+                            acc[t][v] = fmaf(al, gv[u][t][v], acc[t][v]);
+                            acc[t][v] = fmaf(tt > 0.f ? ds : dss, a[t][v], acc[t][v]);
+                        }
+                }
+            }
+        }
+#pragma unroll
+        for (int t = 0; t < NT; t++) {
+#pragma unroll
+            for (int v = 0; v < VEC; v++) acc[t][v] = fold_groups(acc[t][v], lpr);
+            const uint32_t col = (t * lpr + sub) * VEC;
+            if (grp == 0 && col < dh) storev<VEC>(G_Zs + row * ldgzs + (size_t)k * dh + col, acc[t]);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// partials[b, c] = the sum of P[r, c] over the rows r workgroup b walks: rows blockIdx * R + rr, + gridDim * R, ... (R = 256 / tpr
+// rows at a time, tpr threads per row), the R row slots folded in LDS in slot order; colsum_final_kernel (reduce.h) adds the
+// partials in workgroup order.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gatv2_att_grad_kernel(const float *__restrict__ P, size_t ldp, size_t n, uint32_t width,
+                                                             uint32_t tl, float *__restrict__ partials) {
+    __shared__ float red[256];
+    const uint32_t tpr = 1u << tl, R = 256u >> tl, rr = threadIdx.x >> tl, cc = threadIdx.x & (tpr - 1);
+    for (uint32_t c0 = 0; c0 < width; c0 += tpr) {          // every thread of the block takes every turn (barriers)
+        const uint32_t c = c0 + cc;
+        const bool on = c < width;
+        float acc = 0.f;
+        if (on)
+            for (size_t r = (size_t)blockIdx.x * R + rr; r < n; r += (size_t)gridDim.x * R) acc += P[r * ldp + c];
+        red[threadIdx.x] = acc;
+        __syncthreads();
+        if (rr == 0 && on) {
+            float s = red[cc];
+            for (uint32_t q = 1; q < R; q++) s += red[q * tpr + cc];
+            partials[(size_t)blockIdx.x * width + c] = s;
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+// ============================ C ABI =========================================
+MGGCN_API void mggcn_gatv2_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                       const uint32_t *indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                                       const float *att, uint32_t K, uint32_t dh, float slope, float *out, size_t ldo,
+                                       float *lse) {
+    require_heads(K, dh);
+    const size_t width = (size_t)K * dh;
+    MGGCN_REQUIRE(ldzs >= width && ldzd >= width && ldo >= width, "gatv2 forward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && Zd != nullptr && att != nullptr && out != nullptr && lse != nullptr,
+                  "gatv2 forward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Zs != nullptr), "gatv2 forward: null operand");
+    MGGCN_REQUIRE(out != Zs && out != Zd, "gatv2 forward: out must not alias Zs or Zd");
+    const bool vec = dh % 4 == 0 && rows16(Zs, ldzs) && rows16(Zd, ldzd) && rows16(out, ldo) && aligned16(att);
+    const head_geometry hg = head_geometry_for(dh, vec);
+#define MGGCN_GATV2_FWD(V, NT, U)                                                                                              \
+    hipLaunchKernelGGL((gatv2_forward_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows,      \
+                       indptr, indices, Zs, ldzs, Zd, ldzd, att, K, dh, slope, hg.lg, out, ldo, lse)
+    MGGCN_GAT_DISPATCH(MGGCN_GATV2_FWD, vec, hg.nt);
+#undef MGGCN_GATV2_FWD
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_gatv2_backward_dst_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                            const uint32_t *indices, const float *Zs, size_t ldzs, const float *Zd,
+                                            size_t ldzd, const float *att, const float *lse, const float *G, size_t ldg,
+                                            const float *out, size_t ldo, uint32_t K, uint32_t dh, float slope, float *D,
+                                            float *G_Zd, size_t ldgzd, float *P, size_t ldp) {
+    require_heads(K, dh);
+    const size_t width = (size_t)K * dh;
+    MGGCN_REQUIRE(ldzs >= width && ldzd >= width && ldg >= width && ldo >= width && ldgzd >= width && ldp >= width,
+                  "gatv2 backward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && Zd != nullptr && att != nullptr && lse != nullptr && G != nullptr && out != nullptr &&
+                      D != nullptr && G_Zd != nullptr && P != nullptr,
+                  "gatv2 backward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Zs != nullptr), "gatv2 backward: null operand");
+    MGGCN_REQUIRE(G_Zd != G && G_Zd != Zs && G_Zd != Zd && G_Zd != out && P != G && P != Zs && P != Zd && P != out && P != G_Zd,
+                  "gatv2 backward: G_Zd and P must not alias an input or each other");
+    const bool vec = dh % 4 == 0 && rows16(Zs, ldzs) && rows16(Zd, ldzd) && rows16(G, ldg) && rows16(out, ldo) &&
+                     rows16(G_Zd, ldgzd) && rows16(P, ldp) && aligned16(att);
+    const head_geometry hg = head_geometry_for(dh, vec);
+#define MGGCN_GATV2_BWD_DST(V, NT, U)                                                                                          \
+    hipLaunchKernelGGL((gatv2_backward_dst_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
+                       indptr, indices, Zs, ldzs, Zd, ldzd, att, lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, G_Zd, ldgzd, P, \
+                       ldp)
+    MGGCN_GAT_DISPATCH(MGGCN_GATV2_BWD_DST, vec, hg.nt);
+#undef MGGCN_GATV2_BWD_DST
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_gatv2_att_grad_f32(mggcn_stream_t stream, const float *P, size_t ldp, size_t n_rows, uint32_t width,
+                                        float *G_att) {
+    MGGCN_REQUIRE(width >= 1 && width <= MGGCN_GAT_MAX_WIDTH, "gatv2 att grad supports 1 <= width <= 1024");
+    MGGCN_REQUIRE(ldp >= width, "gatv2 att grad: ldp < width");
+    MGGCN_REQUIRE(G_att != nullptr, "gatv2 att grad: null gradient");
+    MGGCN_REQUIRE(n_rows == 0 || P != nullptr, "gatv2 att grad: null operand");
+    const hipStream_t st = as_stream(stream);
+    unsigned grid = 0;
+    float *partials = nullptr;
+    if (n_rows) {
+        const uint32_t tl = std::min(ceil_log2(width), 8u);            // threads per row: the power of two covering the width, <= 256
+        const size_t R = 256u >> tl;
+        grid = (unsigned)std::min<size_t>((n_rows + R - 1) / R, kGatColsumBlocks);
+        partials = stream_scratch(st, scratch_kind::colsums, (size_t)kGatColsumBlocks * width);
+        hipLaunchKernelGGL(gatv2_att_grad_kernel, dim3(grid), dim3(256), 0, st, P, ldp, n_rows, width, tl, partials);
+        MGGCN_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(colsum_final_kernel, dim3((width + 63) / 64), dim3(256), 0, st, partials, grid, width, G_att, G_att, width);
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_gatv2_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                            const uint32_t *t_indices, const float *Zs, size_t ldzs, const float *Zd,
+                                            size_t ldzd, const float *att, const float *lse, const float *D, const float *G,
+                                            size_t ldg, uint32_t K, uint32_t dh, float slope, float *G_Zs, size_t ldgzs) {
+    require_heads(K, dh);
+    const size_t width = (size_t)K * dh;
+    MGGCN_REQUIRE(ldzs >= width && ldzd >= width && ldg >= width && ldgzs >= width,
+                  "gatv2 backward: leading dimension < heads * width per head");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(t_indptr != nullptr && Zs != nullptr && att != nullptr && G_Zs != nullptr, "gatv2 backward: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && Zd != nullptr && G != nullptr && lse != nullptr && D != nullptr),
+                  "gatv2 backward: null operand");
+    MGGCN_REQUIRE(G_Zs != G && G_Zs != Zs && G_Zs != Zd, "gatv2 backward: G_Zs must not alias G, Zs or Zd");
+    const bool vec = dh % 4 == 0 && rows16(Zs, ldzs) && rows16(Zd, ldzd) && rows16(G, ldg) && rows16(G_Zs, ldgzs) && aligned16(att);
+    const head_geometry hg = head_geometry_for(dh, vec);
+#define MGGCN_GATV2_BWD_SRC(V, NT, U)                                                                                          \
+    hipLaunchKernelGGL((gatv2_backward_src_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
+                       t_indptr, t_indices, Zs, ldzs, Zd, ldzd, att, lse, D, G, ldg, K, dh, slope, hg.lg, G_Zs, ldgzs)
+    MGGCN_GAT_DISPATCH(MGGCN_GATV2_BWD_SRC, vec, hg.nt);
+#undef MGGCN_GATV2_BWD_SRC
+    MGGCN_CHECK_LAUNCH();
+}

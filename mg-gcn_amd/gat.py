@@ -24,6 +24,17 @@ set_dropout(p, seed, epoch, attn) sets both; evaluate() and a plain call never d
 
 The row-partitioned form is dist_gat.dist_gat (one process per GPU; DESIGN.md 3.10 "The row partition").
 
+``variant="v2"`` selects GATv2 (dynamic attention; Brody, Alon, Yahav 2022; PyG's GATv2Conv) in every layer:
+
+    Z2 = H W + 1 b^T, W [in x 2 out]                  Zs = Z2[:, :out] (PyG's lin_l)   Zd = Z2[:, out:] (lin_r)
+    e_ijk = att[head k] . lrelu(Zd[i, head k] + Zs[j, head k], slope)     att [1 x out]
+    alpha_ijk = softmax over the entries j of row i   out[i, head k] = sum_j alpha_ijk Zs[j, head k]
+
+The non-linearity sits inside the dot product, so a destination can rank its sources in an order of its own, which the
+v1 score (monotone in s_src[j]) cannot.  One GEMM forward, the linear's fused gradient GEMMs backward; the kernels are
+those of csrc/gatv2.hip (mggcn_gatv2_*).  The default ``variant="v1"`` is the model described above and calls exactly what
+it called before the keyword existed.  GATv2 has no attention dropout and no row-partitioned form yet (both refused).
+
 Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, checkpoints, layer norm, bf16 gathers.
 """
 from __future__ import annotations
@@ -112,6 +123,41 @@ class attention:
         ops.adam_fused(ctx, self.att, self.G_att, self.m, self.v, lr, beta1, beta2, weight_decay, bc1, bc2, eps)
 
 
+class attention_v2(attention):
+    """The GATv2 attention of one layer: the parameter ``att`` [1 x out] (seed-99 uniform like W), its gradient and Adam
+    state (``attention``'s: a row of the fused Adam table with W's weight decay), and what the backward pass needs of the
+    forward -- lse and D [n x heads].  ``P`` [n x out] holds the rows' shares of G_att between backward_dst and att_grad; it
+    aliases ``P_buffer`` (the model's, at its widest layer) when one is given.  __call__ and backward take the layer's
+    Z2 = [Zs | Zd] and G_Z2 = [G_Zs | G_Zd] buffers of 2 out columns."""
+
+    def __init__(self, name: str, n: int, out: int, heads: int, slope: float = ops.GAT_SLOPE, P_buffer=None, device=None):
+        self.name, self.heads, self.slope = name, int(heads), float(slope)
+        self.att, self.G_att = dn_matrix(1, out, device=device), dn_matrix(1, out, device=device)
+        host = np.empty((1, out), dtype=np.float32)
+        _lib.load().mggcn_init_uniform_host(host.ctypes.data, out, 1, -1.0)
+        self.att.init(host)
+        self.lse, self.D = dn_matrix(n, heads, device=device), dn_matrix(n, heads, device=device)
+        self.P = dn_matrix(n, out, P_buffer) if P_buffer is not None else dn_matrix(n, out, device=device)
+        self.m = self.v = None
+        self.step = 0
+
+    def __call__(self, ctx: context, F: csr_matrix, Z2: dn_matrix, out: dn_matrix, drop=None) -> None:
+        """out = the attention-weighted gather of Zs over F's rows, scored against Zd"""
+        assert drop is None, "GATv2 has no attention dropout"
+        ops.gatv2_forward(ctx, F, Z2, Z2, self.att, out, self.lse, self.heads, self.slope, self.name + "0_gatv2-forward")
+
+    def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z2: dn_matrix, G: dn_matrix, out: dn_matrix,
+                 G_Z2: dn_matrix, drop=None) -> None:
+        """G_Z2 = the gradient of Z2 (both halves) and G_att, from G = the gradient of ``out``"""
+        assert drop is None, "GATv2 has no attention dropout"
+        n = self.name
+        ops.gatv2_backward_dst(ctx, F, Z2, Z2, self.att, self.lse, G, out, self.D, G_Z2, self.P, self.heads, self.slope,
+                               n + "1_gatv2-backward-dst")
+        ops.gatv2_att_grad(ctx, self.P, self.G_att, n + "1_gatv2-att-grad")
+        ops.gatv2_backward_src(ctx, F_T, Z2, Z2, self.att, self.lse, self.D, G, G_Z2, self.heads, self.slope,
+                               n + "1_gatv2-backward-src")
+
+
 class gat_layer:
     """One GAT layer: a ``linear`` (Z = H W + 1 b^T), an ``attention`` over (F, F^T) and the activation.  Z, the
     aggregated ``out`` (before the activation: the backward pass needs it) and the activated output are kept per layer;
@@ -127,14 +173,16 @@ class gat_layer:
                     out, activation, G_Z_buffer)
 
     def _setup(self, name: str, F: csr_matrix, F_T: csr_matrix, lin, attn, rows: int, in_: int, out: int, activation: bool,
-               G_Z_buffer=None, device=None, row0: int = 0) -> None:
+               G_Z_buffer=None, device=None, row0: int = 0, z_width: Optional[int] = None) -> None:
         """everything a layer holds besides building ``lin`` and ``attn``: its buffers over ``rows`` rows and the per-forward
-        state (the row-partitioned layer, dist_gat.dist_gat_layer, calls it with its rank's pieces)"""
+        state (the row-partitioned layer, dist_gat.dist_gat_layer, calls it with its rank's pieces); ``z_width``: the columns
+        of Z and G_Z where they are not ``out`` (gatv2_layer: 2 out)"""
         self.name, self.F, self.F_T, self.activation = name, F, F_T, bool(activation)
         self.lin, self.attn = lin, attn
-        self.Z, self.out = dn_matrix(rows, out, device=device), dn_matrix(rows, out, device=device)
+        zw = out if z_width is None else int(z_width)
+        self.Z, self.out = dn_matrix(rows, zw, device=device), dn_matrix(rows, out, device=device)
         self.act = dn_matrix(rows, out, device=device) if activation else self.out
-        self.G_Z = dn_matrix(rows, out, G_Z_buffer) if G_Z_buffer is not None else dn_matrix(rows, out, device=device)
+        self.G_Z = dn_matrix(rows, zw, G_Z_buffer) if G_Z_buffer is not None else dn_matrix(rows, zw, device=device)
         self.G_out = dn_matrix(rows, in_, device=device) if lin.backward_out else None
         self.H: Optional[dn_matrix] = None
         # set by the model before every forward and read again by backward(): ``dropout`` -- (threshold, scale, seed, stream)
@@ -207,12 +255,42 @@ class gat_layer:
     def Gatt(self): return self.attn.G_att
 
 
+class gatv2_layer(gat_layer):
+    """One GATv2 layer: ONE ``linear`` of 2 out columns (Z2 = H W + 1 b^T = [Zs | Zd], the bias inside both halves), an
+    ``attention_v2`` over (F, F^T) and the activation.  ``Z`` is Z2 and ``G_Z`` its gradient [G_Zs | G_Zd] (aliasing the
+    model-wide buffer), so the forward is one GEMM and the backward the linear's fused weight-gradient and input-gradient
+    GEMMs over 2 out columns; everything else is gat_layer's, word for word."""
+
+    def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
+                 slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, P_buffer=None):
+        n = F.n()
+        assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
+        self._setup(name, F, F_T, linear(name, in_, 2 * out, backward_out, True),
+                    attention_v2(name, n, out, heads, slope, P_buffer), n, in_, out, activation, G_Z_buffer, z_width=2 * out)
+
+
+VARIANTS = ("v1", "v2")
+
+
+def check_variant(variant, attn_dropout: float = 0.0) -> str:
+    """``variant=`` of gat: "v1" or "v2"; ValueError for anything else and for GATv2 with attention dropout (the _drop
+    twins of its three sparse kernels do not exist).  No device work."""
+    if variant not in VARIANTS:
+        raise ValueError(f"gat variant must be one of {VARIANTS}, got {variant!r}")
+    if variant == "v2" and attn_dropout > 0.0:
+        raise ValueError("gat(variant=\"v2\") has no attention dropout: attn_dropout must be 0")
+    return variant
+
+
 class gat(dropout_option):
     """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
 
-    gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0):
+    gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
+    variant="v1"):
     ``A`` as ``gcn`` takes it (the layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
-    (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att).  ValueError
+    (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att);
+    ``variant``: "v1" (this model as it always was) or "v2" (GATv2, see the module docstring: W is [in x 2 out], b
+    [1 x 2 out], att [1 x out]; ValueError for another name, for attn_dropout > 0 and for set_dropout(attn > 0)).  ValueError
     before any device work for a width that its heads do not divide or a limit of the kernels (ops.GAT_MAX_HEADS,
     ops.GAT_MAX_WIDTH).  ``fused`` picks how Adam is launched -- one launch for every parameter tensor, or one per tensor;
     the element-wise math is the same, so both give the same bits -- and every other kernel is the same in both modes.
@@ -227,10 +305,12 @@ class gat(dropout_option):
     and layers() mean what they mean on ``gcn``."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
-                 loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0):
+                 loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0,
+                 variant: str = "v1"):
         self.sizes = [int(s) for s in sizes]
         self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
         self._attn_dropout_params = check_dropout(attn_dropout, len(self.sizes) - 1)
+        self.variant = check_variant(variant, float(attn_dropout))
         self._init_dropout(dropout, len(self.sizes) - 1)
         self.attn_dropout_p = float(attn_dropout)
         self.loss = check_loss(loss)
@@ -245,11 +325,18 @@ class gat(dropout_option):
         loss_class = sigmoid_bce_loss if self.loss == "bce" else softmax_cross_entropy_loss
         self.loss_layer = loss_class(f"{n_layers}_", True, True)
         self.A, self.A_T = A, A.transpose()                      # forward over A_T's rows, like gcn
-        self.G_Z_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
         self.layers_: List[gat_layer] = []
-        for i in range(n_layers):
-            self.layers_.append(gat_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
-                                          i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer))
+        if self.variant == "v2":                                 # G_Z2 = [G_Zs | G_Zd] and P, once at the widest layer
+            self.G_Z_buffer = torch.empty(A.n() * 2 * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
+            self.P_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
+            for i in range(n_layers):
+                self.layers_.append(gatv2_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
+                                                i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer, self.P_buffer))
+        else:
+            self.G_Z_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
+            for i in range(n_layers):
+                self.layers_.append(gat_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
+                                              i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer))
         self._adam = None
         if weights is not None:
             assert len(weights) == n_layers
@@ -266,6 +353,7 @@ class gat(dropout_option):
         anything is stored."""
         attn = self.attn_dropout_p if attn is None else attn
         attn_params = check_dropout(attn, self._dropout_layers)
+        check_variant(getattr(self, "variant", "v1"), float(attn))   # dist_gat borrows this method and is always v1
         dropout_option.set_dropout(self, p, seed, epoch)
         self._attn_dropout_params, self.attn_dropout_p = attn_params, float(attn)
 

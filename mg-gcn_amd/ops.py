@@ -586,6 +586,87 @@ def gat_scores_backward(ctx: context, ds_dst: dn_matrix, Z_dst: dn_matrix, ds_sr
         Z_src.n(), heads, Z_src.m() // heads, G_att.buffer()))
 
 
+def _gatv2_half(M: dn_matrix, width: int, half: int, what: str):
+    """(pointer, leading dimension) of a dense operand of the GATv2 calls: ``M`` is either the [rows x width] matrix itself
+    or the model's [rows x 2 width] buffer, whose columns [0, width) are the source half (half 0: Zs, G_Zs) and
+    [width, 2 width) the destination half (half 1: Zd, G_Zd)"""
+    _req(M.m() in (width, 2 * width), f"{what}: an operand of {M.m()} columns is neither {width} nor 2 x {width} wide")
+    return (M.buffer(), width) if M.m() == width else (M.buffer() + 4 * width * half, 2 * width)
+
+
+def _gatv2_width(att: dn_matrix, heads: int, what: str) -> int:
+    _req(att.n() == 1, f"{what}: att must be 1 x heads * width per head")
+    check_gat_heads(heads, att.m(), what)
+    return att.m()
+
+
+def gatv2_forward(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, out: dn_matrix, lse: dn_matrix,
+                  heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """The GATv2 edge-softmax fused with the score and the gather (mggcn_gatv2_forward_f32): over F's pattern,
+    e_ijk = att[head k] . lrelu(Zd[i, head k] + Zs[j, head k]), lse[i, k] = log sum_j exp(e_ijk) and out[i, head k] =
+    sum_j alpha_ijk Zs[j, head k].  F: destinations x sources; att: [1 x width]; out: [F.n() x width]; lse: [F.n() x heads].
+    Zs (one row per source) and Zd (one row per destination) are [rows x width] matrices, or the model's [rows x 2 width]
+    buffer, of which Zs takes columns [0, width) and Zd columns [width, 2 width) -- the same buffer may be passed as both."""
+    width = _gatv2_width(att, heads, "gatv2 forward")
+    _req(F.m() == Zs.n() and F.n() == Zd.n() and out.shape() == (F.n(), width), "gatv2 forward: shape mismatch")
+    _req(lse.shape() == (F.n(), heads), "gatv2 forward: lse must be rows x heads")
+    (zs, ldzs), (zd, ldzd) = _gatv2_half(Zs, width, 0, "gatv2 forward"), _gatv2_half(Zd, width, 1, "gatv2 forward")
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_forward_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), heads, width // heads,
+        slope, out.buffer(), out.m(), lse.buffer()))
+
+
+def gatv2_backward_dst(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, lse: dn_matrix,
+                       G: dn_matrix, out: dn_matrix, D: dn_matrix, G_Zd: dn_matrix, P: dn_matrix, heads: int,
+                       slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """The half of the GATv2 backward pass that sums over sources, over F's rows (mggcn_gatv2_backward_dst_f32):
+    D[i, k] = G[i, head k] . out[i, head k], ds_ijk = alpha_ijk (G[i, head k] . Zs[j, head k] - D[i, k]),
+    G_Zd[i, c] = att[c] sum_j ds_ijk lrelu'(t_ijk[c]) and P[i, c] = sum_j ds_ijk lrelu(t_ijk[c]), row i's share of G_att.
+    Zs, Zd as gatv2_forward takes them; G_Zd: [F.n() x width], or the [F.n() x 2 width] gradient buffer whose columns
+    [width, 2 width) are written; P: [F.n() x width]."""
+    what = "gatv2 backward"
+    width = _gatv2_width(att, heads, what)
+    _req(F.m() == Zs.n() and F.n() == Zd.n() and G.shape() == (F.n(), width) and out.shape() == G.shape()
+         and P.shape() == G.shape() and G_Zd.n() == F.n(), f"{what}: shape mismatch")
+    _req(lse.shape() == (F.n(), heads) and D.shape() == (F.n(), heads), f"{what}: lse and D must be rows x heads")
+    (zs, ldzs), (zd, ldzd), (gzd, ldgzd) = (_gatv2_half(Zs, width, 0, what), _gatv2_half(Zd, width, 1, what),
+                                            _gatv2_half(G_Zd, width, 1, what))
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_backward_dst_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), lse.buffer(), G.buffer(),
+        G.m(), out.buffer(), out.m(), heads, width // heads, slope, D.buffer(), gzd, ldgzd, P.buffer(), P.m()))
+
+
+def gatv2_att_grad(ctx: context, P: dn_matrix, G_att: dn_matrix, timer: Optional[str] = None) -> None:
+    """G_att[0, c] = sum_i P[i, c] (mggcn_gatv2_att_grad_f32; fixed order, bitwise reproducible): P is gatv2_backward_dst's
+    [rows x width], G_att [1 x width]"""
+    _req(1 <= P.m() <= GAT_MAX_WIDTH, f"gatv2 att grad supports 1 <= width <= {GAT_MAX_WIDTH}, got {P.m()}")
+    _req(G_att.shape() == (1, P.m()), f"gatv2 att grad: G_att must be 1 x {P.m()}")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_att_grad_f32(ctx.stream(0), P.buffer(), P.m(), P.n(), P.m(),
+                                                                    G_att.buffer()))
+
+
+def gatv2_backward_src(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, lse: dn_matrix,
+                       D: dn_matrix, G: dn_matrix, G_Zs: dn_matrix, heads: int, slope: float = GAT_SLOPE,
+                       timer: Optional[str] = None) -> None:
+    """The half that sums over destinations, over the rows of F^T (mggcn_gatv2_backward_src_f32; after gatv2_backward_dst,
+    whose D it reads): G_Zs[j, c] = sum_i (alpha_ijk G[i, c] + ds_ijk att[c] lrelu'(t_ijk[c])).  F_T: sources x destinations;
+    Zs, Zd as gatv2_forward takes them; G_Zs: [F_T.n() x width], or the [F_T.n() x 2 width] gradient buffer whose columns
+    [0, width) are written."""
+    what = "gatv2 backward"
+    width = _gatv2_width(att, heads, what)
+    _req(F_T.n() == Zs.n() and F_T.m() == Zd.n() and G.shape() == (F_T.m(), width) and G_Zs.n() == F_T.n(),
+         f"{what}: shape mismatch")
+    _req(lse.shape() == (F_T.m(), heads) and D.shape() == (F_T.m(), heads), f"{what}: lse and D must be rows x heads")
+    (zs, ldzs), (zd, ldzd), (gzs, ldgzs) = (_gatv2_half(Zs, width, 0, what), _gatv2_half(Zd, width, 1, what),
+                                            _gatv2_half(G_Zs, width, 0, what))
+    ip, ix, _ = F_T.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_backward_src_f32(
+        ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), lse.buffer(),
+        D.buffer(), G.buffer(), G.m(), heads, width // heads, slope, gzs, ldgzs))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
