@@ -2,13 +2,12 @@
 // backward pass (per-edge dot products + weighted transposed gather + the column sums behind G_att).
 //
 // Layout of the three sparse kernels: the row-split form of spmm.hip without a plan -- one wave per CSR row, the row's
-// entries in 64-entry chunks, software-pipelined.  The heads of a row are walked one after the
-// other.  Within a head the wave is cut into G = 64 / LPR groups of LPR lanes (LPR: the power of two that covers one
-// head's dh columns, 64 at the most): a group holds one head-row of a dense operand, VEC columns per lane and NT column
-// tiles when dh > LPR * VEC, so one wave-instruction gathers the head-rows of G neighbours.
-//   * per chunk, lane l owns entry l: it loads the index (two chunks ahead) and the [rows x K] scalars of that entry
-//     (scores, lse, D; one chunk ahead) and evaluates exp ONCE per (entry, head); the groups pick index and weight up
-//     through ds_bpermute (__shfl);
+// entries in 64-entry chunks, software-pipelined (entry_chunks of gat_internal.h is the walk).  The heads of a row are
+// walked one after the other.  Within a head the wave is cut into G = 64 / LPR groups of LPR lanes (LPR: the power of two
+// that covers one head's dh columns, 64 at the most): a group holds one head-row of a dense operand, VEC columns per lane
+// and NT column tiles when dh > LPR * VEC, so one wave-instruction gathers the head-rows of G neighbours.
+//   * per chunk, the lane that owns an entry has its index and its [rows x K] scalars (scores, lse, D) from the walk and
+//     evaluates exp ONCE per (entry, head); the groups pick index and weight up through ds_bpermute (chunk_entry);
 //   * the forward makes ONE pass over a row: a running maximum, the sum and the accumulators rescaled chunk by chunk;
 //   * the per-edge dot product (SDDMM) is a butterfly over the LPR lanes of a group -- log2(LPR) steps per G edges;
 //   * the sums over a row's entries fold the G groups in a fixed order at the end: no atomics anywhere, the same bits on
@@ -34,7 +33,6 @@
 #include "gat_internal.h"
 #include "philox.h"
 #include "reduce.h"
-#include "scratch_internal.h"
 
 namespace {
 
@@ -102,23 +100,18 @@ __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const
         // One pass over the row with a running maximum (the softmax of flash attention): per chunk, lane l owns entry l,
         // m <- max(m, the chunk's scores), the sum and the accumulators are rescaled by exp(m_old - m_new), and the chunk is
         // gathered with the weights exp(e - m).  out = acc / sum at the end: the weights of a row add up to one within
-        // rounding whatever the magnitude of the scores.  Indices are fetched two chunks ahead, the scores one chunk ahead.
+        // rounding whatever the magnitude of the scores.  The walk fetches s_src of the entry.
         float m = -INFINITY, sum = 0.f;
         float acc[NT][VEC];
 #pragma unroll
         for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
-        uint32_t c1 = 0, c2 = 0;
-        float x1 = 0.f;
-        if (beg + lane < end) { c1 = indices[beg + lane]; x1 = s_src[(size_t)c1 * K + k]; }
-        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        const auto fetch = [&](uint32_t c, float *s) { s[0] = s_src[(size_t)c * K + k]; };
+        entry_chunks<1> ch;
+        ch.start(indices, beg, end, lane, fetch);
         for (uint32_t base = beg; base < end; base += 64) {
-            const uint32_t my_c = c1;
-            const float my_x = x1;
-            c1 = c2;
-            x1 = 0.f; c2 = 0;
-            if ((size_t)base + 64 + lane < end) x1 = s_src[(size_t)c1 * K + k];
-            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
-            const uint32_t cnt = min(64u, end - base);
+            ch.next(indices, base, end, lane, fetch);
+            const uint32_t cnt = ch.cnt;
+            const float my_x = ch.my_s[0];
             const float e = lane < cnt ? gat_lrelu(sd + my_x, slope) : -INFINITY;
             const float m_new = fmaxf(m, wave_max(e));
             const float scale = expf(m - m_new);            // 0 at the first chunk (m = -inf), where sum and acc are 0
@@ -126,7 +119,7 @@ __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const
             sum = fmaf(sum, scale, wave_sum(my_a));
             m = m_new;
             if constexpr (DROP) {                            // after the sum: only the accumulator's weight carries q
-                if (lane < cnt) my_a *= gat_keep_scale(dp, dp.dst0 + (uint32_t)row, dp.src0 + my_c, k);
+                if (lane < cnt) my_a *= gat_keep_scale(dp, dp.dst0 + (uint32_t)row, dp.src0 + ch.my_c, k);
             }
             if (scale != 1.f) {                              // wave-uniform
 #pragma unroll
@@ -138,12 +131,10 @@ __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const
                 float z[U][NT][VEC], a[U];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const uint32_t c = __shfl(my_c, src & 63);
-                    const float av = __shfl(my_a, src & 63);
-                    const bool ok = src < cnt;
-                    a[u] = ok ? av : 0.f;
-                    load_head_row<VEC, NT>(z[u], Zk + (size_t)c * ldz, lpr, sub, dh, ok);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    const float av = en.of(my_a);
+                    a[u] = en.ok ? av : 0.f;
+                    load_head_row<VEC, NT>(z[u], Zk + (size_t)en.c * ldz, lpr, sub, dh, en.ok);
                 }
 #pragma unroll
                 for (int u = 0; u < U; u++)
@@ -155,13 +146,8 @@ __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const
         }
         const float inv = beg < end ? 1.f / sum : 0.f;
         if (lane == 0) lse[row * K + k] = beg < end ? m + logf(sum) : 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-#pragma unroll
-            for (int v = 0; v < VEC; v++) acc[t][v] = fold_groups(acc[t][v], lpr) * inv;
-            const uint32_t col = (t * lpr + sub) * VEC;
-            if (grp == 0 && col < dh) storev<VEC>(out + row * ldo + (size_t)k * dh + col, acc[t]);   // an empty row: +0.0
-        }
+        fold_store_head_row<VEC, NT>(out + row * ldo + (size_t)k * dh, acc, lpr, sub, grp, dh,
+                                     [&](int, int, float x) { return x * inv; });      // an empty row: +0.0
     }
 }
 
@@ -189,42 +175,36 @@ __global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, 
         const float sd = s_dst[row * K + k], ls = lse[row * K + k];
         const float *__restrict__ Zk = Z + (size_t)k * dh;
         float acc = 0.f;
-        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead, scores one chunk ahead
-        float x1 = 0.f;
-        if (beg + lane < end) { c1 = indices[beg + lane]; x1 = s_src[(size_t)c1 * K + k]; }
-        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        const auto fetch = [&](uint32_t c, float *s) { s[0] = s_src[(size_t)c * K + k]; };      // the entry's score
+        entry_chunks<1> ch;
+        ch.start(indices, beg, end, lane, fetch);
         for (uint32_t base = beg; base < end; base += 64) {
-            const uint32_t my_c = c1;
-            const float my_x = x1;
-            c1 = c2;
-            x1 = 0.f; c2 = 0;
-            if ((size_t)base + 64 + lane < end) x1 = s_src[(size_t)c1 * K + k];
-            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
-            const uint32_t cnt = min(64u, end - base);
+            ch.next(indices, base, end, lane, fetch);
+            const uint32_t cnt = ch.cnt;
+            const float my_x = ch.my_s[0];
             float my_w = 0.f;                       // alpha lrelu'(x) of my entry
             [[maybe_unused]] float my_q = 0.f;
             if (lane < cnt) {
                 const float x = sd + my_x;
                 my_w = expf(gat_lrelu(x, slope) - ls) * (x > 0.f ? 1.f : slope);
-                if constexpr (DROP) my_q = gat_keep_scale(dp, dp.dst0 + (uint32_t)row, dp.src0 + my_c, k);
+                if constexpr (DROP) my_q = gat_keep_scale(dp, dp.dst0 + (uint32_t)row, dp.src0 + ch.my_c, k);
             }
             for (uint32_t j = 0; j < cnt; j += n_grp * U) {
                 float p[U];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const uint32_t c = __shfl(my_c, src & 63);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
                     float z[NT][VEC];
-                    load_head_row<VEC, NT>(z, Zk + (size_t)c * ldz, lpr, sub, dh, src < cnt);
+                    load_head_row<VEC, NT>(z, Zk + (size_t)en.c * ldz, lpr, sub, dh, en.ok);
                     p[u] = dot_head_row<VEC, NT>(g, z);
                 }
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const float w = __shfl(my_w, src & 63);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    const float w = en.of(my_w);
                     float da = group_sum(p[u], lpr);
-                    if constexpr (DROP) da *= __shfl(my_q, src & 63);
-                    acc += src < cnt ? w * (da - Dk) : 0.f;
+                    if constexpr (DROP) da *= en.of(my_q);
+                    acc += en.ok ? w * (da - Dk) : 0.f;
                 }
             }
         }
@@ -266,35 +246,21 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
         const float ss = s_src[row * K + k];
         const float *__restrict__ Gk = G + (size_t)k * dh;
         float acc_ds = 0.f;
-        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead, the entries' scalars one chunk ahead
-        float x1 = 0.f, l1 = 0.f, D1 = 0.f;
-        if (beg + lane < end) {
-            c1 = indices[beg + lane];
-            const size_t ik = (size_t)c1 * K + k;
+        const auto fetch = [&](uint32_t c, float *s) {          // s_dst, lse and D of the entry's destination
+            const size_t ik = (size_t)c * K + k;
             if constexpr (REC) {
                 const float4 t = *reinterpret_cast<const float4 *>(rec + ik * 4);
-                x1 = t.x; l1 = t.y; D1 = t.z;
+                s[0] = t.x; s[1] = t.y; s[2] = t.z;
             } else {
-                x1 = s_dst[ik]; l1 = lse[ik]; D1 = D[ik];
+                s[0] = s_dst[ik]; s[1] = lse[ik]; s[2] = D[ik];
             }
-        }
-        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        };
+        entry_chunks<3> ch;
+        ch.start(indices, beg, end, lane, fetch);
         for (uint32_t base = beg; base < end; base += 64) {
-            const uint32_t my_c = c1;
-            const float my_x = x1, my_l = l1, my_D = D1;
-            c1 = c2;
-            x1 = 0.f; l1 = 0.f; D1 = 0.f; c2 = 0;
-            if ((size_t)base + 64 + lane < end) {
-                const size_t ik = (size_t)c1 * K + k;
-                if constexpr (REC) {
-                    const float4 t = *reinterpret_cast<const float4 *>(rec + ik * 4);
-                    x1 = t.x; l1 = t.y; D1 = t.z;
-                } else {
-                    x1 = s_dst[ik]; l1 = lse[ik]; D1 = D[ik];
-                }
-            }
-            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
-            const uint32_t cnt = min(64u, end - base);
+            ch.next(indices, base, end, lane, fetch);
+            const uint32_t cnt = ch.cnt;
+            const float my_x = ch.my_s[0], my_l = ch.my_s[1], my_D = ch.my_s[2];
             float my_a = 0.f, my_w = 0.f;
             [[maybe_unused]] float my_q = 0.f;
             if (lane < cnt) {
@@ -302,7 +268,7 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
                 my_a = expf(gat_lrelu(x, slope) - my_l);
                 my_w = my_a * (x > 0.f ? 1.f : slope);
                 if constexpr (DROP) {
-                    my_q = gat_keep_scale(dp, dp.dst0 + my_c, dp.src0 + (uint32_t)row, k);
+                    my_q = gat_keep_scale(dp, dp.dst0 + ch.my_c, dp.src0 + (uint32_t)row, k);
                     my_a *= my_q;                   // the gather's weight alpha q; my_w keeps the plain alpha
                 }
             }
@@ -310,20 +276,18 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
                 float gv[U][NT][VEC], p[U];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const uint32_t c = __shfl(my_c, src & 63);
-                    load_head_row<VEC, NT>(gv[u], Gk + (size_t)c * ldg, lpr, sub, dh, src < cnt);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    load_head_row<VEC, NT>(gv[u], Gk + (size_t)en.c * ldg, lpr, sub, dh, en.ok);
                     p[u] = dot_head_row<VEC, NT>(zr, gv[u]);
                 }
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const bool ok = src < cnt;
-                    const float a = __shfl(my_a, src & 63), w = __shfl(my_w, src & 63), Dv = __shfl(my_D, src & 63);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    const float a = en.of(my_a), w = en.of(my_w), Dv = en.of(my_D);
                     float da = group_sum(p[u], lpr);
-                    if constexpr (DROP) da *= __shfl(my_q, src & 63);
-                    acc_ds += ok ? w * (da - Dv) : 0.f;
-                    const float au = ok ? a : 0.f;
+                    if constexpr (DROP) da *= en.of(my_q);
+                    acc_ds += en.ok ? w * (da - Dv) : 0.f;
+                    const float au = en.ok ? a : 0.f;
 #pragma unroll
                     for (int t = 0; t < NT; t++)
 #pragma unroll
@@ -360,43 +324,18 @@ __global__ __launch_bounds__(256) void gat_pack_dst_kernel(const float *__restri
     if (ik < n) rec[ik] = make_float4(s_dst[ik], lse[ik], D[ik], 0.f);
 }
 
-// ---------------------------------------------------------------------------
-// G_att[0, c] = sum_i ds_dst[i, k(c)] Z_dst[i, c],  G_att[1, c] = sum_j ds_src[j, k(c)] Z_src[j, c]
-// A workgroup walks rows blockIdx * R + rr, + gridDim * R, ... (R = 256 / tpr rows at a time, tpr threads per row), folds its R
-// row slots in LDS in slot order and stores one [2 x width] partial; colsum_final_kernel (reduce.h) adds the partials in
-// workgroup order.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gat_scores_backward_kernel(const float *__restrict__ ds_dst, const float *__restrict__ Zd,
-                                                                  size_t ldzd, size_t n_dst, const float *__restrict__ ds_src,
-                                                                  const float *__restrict__ Zs, size_t ldzs, size_t n_src,
-                                                                  uint32_t K, uint32_t dh, uint32_t tl,
-                                                                  float *__restrict__ partials) {
-    __shared__ float red[256];
-    const uint32_t tpr = 1u << tl, R = 256u >> tl, rr = threadIdx.x >> tl, cc = threadIdx.x & (tpr - 1);
-    const uint32_t width = K * dh;
-    for (int side = 0; side < 2; side++) {
-        const float *__restrict__ ds = side ? ds_src : ds_dst;
-        const float *__restrict__ Zp = side ? Zs : Zd;
-        const size_t ld = side ? ldzs : ldzd, n = side ? n_src : n_dst;
-        for (uint32_t c0 = 0; c0 < width; c0 += tpr) {      // every thread of the block takes every turn (barriers)
-            const uint32_t c = c0 + cc;
-            const bool on = c < width;
-            const uint32_t k = on ? c / dh : 0;
-            float acc = 0.f;
-            if (on)
-                for (size_t r = (size_t)blockIdx.x * R + rr; r < n; r += (size_t)gridDim.x * R)
-                    acc = fmaf(ds[r * K + k], Zp[r * ld + c], acc);
-            red[threadIdx.x] = acc;
-            __syncthreads();
-            if (rr == 0 && on) {
-                float s = red[cc];
-                for (uint32_t q = 1; q < R; q++) s += red[q * tpr + cc];
-                partials[((size_t)blockIdx.x * 2 + side) * width + c] = s;
-            }
-            __syncthreads();
-        }
+// G_att[0, c] = sum_i ds_dst[i, k(c)] Z_dst[i, c],  G_att[1, c] = sum_j ds_src[j, k(c)] Z_src[j, c]: the term of
+// gat_column_sums, side 0 the destinations and side 1 the sources
+struct gat_scores_term {
+    const float *ds[2], *Z[2];
+    size_t ld[2], n[2];
+    uint32_t K, dh;
+    __device__ size_t rows(int side) const { return n[side]; }
+    __device__ uint32_t head(uint32_t c) const { return c / dh; }
+    __device__ float operator()(int side, size_t r, uint32_t c, uint32_t k, float acc) const {
+        return fmaf(ds[side][r * K + k], Z[side][r * ld[side] + c], acc);
     }
-}
+};
 
 // the mask's operands of a _drop entry point; both index ranges of the call must fit the 32-bit counter words
 gat_drop make_gat_drop(uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream, uint32_t dst0, uint32_t n_dst,
@@ -419,18 +358,12 @@ void gat_forward(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const 
     const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(out, ldo);
     const head_geometry hg = head_geometry_for(dh, vec);
     const gat_drop d = dp ? *dp : gat_drop{};
-#define MGGCN_GAT_FWD_(V, NT, U, DROP)                                                                                         \
-    hipLaunchKernelGGL((gat_forward_kernel<V, NT, U, DROP>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
-                       indptr, indices, Z, ldz, s_dst, s_src, K, dh, slope, hg.lg, out, ldo, lse, d)
-#define MGGCN_GAT_FWD(V, NT, U)                \
-    do {                                       \
-        if (dp) MGGCN_GAT_FWD_(V, NT, U, true); \
-        else MGGCN_GAT_FWD_(V, NT, U, false);  \
-    } while (0)
-    MGGCN_GAT_DISPATCH(MGGCN_GAT_FWD, vec, hg.nt);
-#undef MGGCN_GAT_FWD
-#undef MGGCN_GAT_FWD_
-    MGGCN_CHECK_LAUNCH();
+    gat_dispatch(vec, hg.nt, [&](auto v) {
+        with_flag(dp != nullptr, [&](auto drop) {
+            launch_rows(gat_forward_kernel<v.VEC, v.NT, v.U, drop>, n_rows, stream, n_rows, indptr, indices, Z, ldz, s_dst, s_src,
+                        K, dh, slope, hg.lg, out, ldo, lse, d);
+        });
+    });
 }
 
 void gat_backward_dst(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices,
@@ -448,18 +381,12 @@ void gat_backward_dst(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, c
     const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(out, ldo);
     const head_geometry hg = head_geometry_for(dh, vec);
     const gat_drop d = dp ? *dp : gat_drop{};
-#define MGGCN_GAT_BWD_DST_(V, NT, U, DROP)                                                                                   \
-    hipLaunchKernelGGL((gat_backward_dst_kernel<V, NT, U, DROP>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream),   \
-                       n_rows, indptr, indices, Z, ldz, s_dst, s_src, lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, ds_dst, d)
-#define MGGCN_GAT_BWD_DST(V, NT, U)                \
-    do {                                           \
-        if (dp) MGGCN_GAT_BWD_DST_(V, NT, U, true); \
-        else MGGCN_GAT_BWD_DST_(V, NT, U, false);  \
-    } while (0)
-    MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_DST, vec, hg.nt);
-#undef MGGCN_GAT_BWD_DST
-#undef MGGCN_GAT_BWD_DST_
-    MGGCN_CHECK_LAUNCH();
+    gat_dispatch(vec, hg.nt, [&](auto v) {
+        with_flag(dp != nullptr, [&](auto drop) {
+            launch_rows(gat_backward_dst_kernel<v.VEC, v.NT, v.U, drop>, n_rows, stream, n_rows, indptr, indices, Z, ldz, s_dst,
+                        s_src, lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, ds_dst, d);
+        });
+    });
 }
 
 // rec != nullptr launches the REC = true kernels, which read it in place of s_dst, lse and D (all three nullptr then)
@@ -482,24 +409,14 @@ void gat_backward_src(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, c
     const bool vec = dh % 4 == 0 && rows16(Z, ldz) && rows16(G, ldg) && rows16(G_Z, ldgz) && aligned16(att);
     const head_geometry hg = head_geometry_for(dh, vec);
     const gat_drop d = dp ? *dp : gat_drop{};
-#define MGGCN_GAT_BWD_SRC_(V, NT, U, DROP, REC)                                                                              \
-    hipLaunchKernelGGL((gat_backward_src_kernel<V, NT, U, DROP, REC>), dim3((n_rows + 3) / 4), dim3(256), 0,                 \
-                       as_stream(stream), n_rows, t_indptr, t_indices, Z, ldz, s_dst, s_src, lse, D, rec, G, ldg, att, ds_dst,  \
-                       K, dh, slope, hg.lg, ds_src, G_Z, ldgz, d)
-#define MGGCN_GAT_BWD_SRC(V, NT, U)                             \
-    do {                                                        \
-        if (rec) {                                              \
-            if (dp) MGGCN_GAT_BWD_SRC_(V, NT, U, true, true);   \
-            else MGGCN_GAT_BWD_SRC_(V, NT, U, false, true);     \
-        } else {                                                \
-            if (dp) MGGCN_GAT_BWD_SRC_(V, NT, U, true, false);  \
-            else MGGCN_GAT_BWD_SRC_(V, NT, U, false, false);    \
-        }                                                       \
-    } while (0)
-    MGGCN_GAT_DISPATCH(MGGCN_GAT_BWD_SRC, vec, hg.nt);
-#undef MGGCN_GAT_BWD_SRC
-#undef MGGCN_GAT_BWD_SRC_
-    MGGCN_CHECK_LAUNCH();
+    gat_dispatch(vec, hg.nt, [&](auto v) {
+        with_flag(dp != nullptr, [&](auto drop) {
+            with_flag(rec != nullptr, [&](auto packed) {
+                launch_rows(gat_backward_src_kernel<v.VEC, v.NT, v.U, drop, packed>, n_rows, stream, n_rows, t_indptr, t_indices,
+                            Z, ldz, s_dst, s_src, lse, D, rec, G, ldg, att, ds_dst, K, dh, slope, hg.lg, ds_src, G_Z, ldgz, d);
+            });
+        });
+    });
 }
 
 }  // namespace
@@ -513,9 +430,7 @@ MGGCN_API void mggcn_gat_scores_f32(mggcn_stream_t stream, const float *Z, size_
     if (!n_rows || (!s_dst && !s_src)) return;
     MGGCN_REQUIRE(Z != nullptr && att != nullptr, "gat scores: null operand");
     const uint32_t lg = std::min(ceil_log2(dh), 6u);
-    hipLaunchKernelGGL(gat_scores_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, as_stream(stream), Z, ldz, att,
-                       s_dst, s_src, n_rows, K, dh, lg);
-    MGGCN_CHECK_LAUNCH();
+    launch_rows(gat_scores_kernel, n_rows, stream, Z, ldz, att, s_dst, s_src, n_rows, K, dh, lg);
 }
 
 MGGCN_API void mggcn_gat_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
@@ -623,21 +538,6 @@ MGGCN_API void mggcn_gat_scores_backward_f32(mggcn_stream_t stream, const float 
     MGGCN_REQUIRE(G_att != nullptr, "gat scores backward: null gradient");
     MGGCN_REQUIRE(n_dst == 0 || (ds_dst != nullptr && Z_dst != nullptr), "gat scores backward: null operand");
     MGGCN_REQUIRE(n_src == 0 || (ds_src != nullptr && Z_src != nullptr), "gat scores backward: null operand");
-    const hipStream_t st = as_stream(stream);
-    const unsigned final_grid = (2 * width + 63) / 64;
-    const size_t n = std::max(n_dst, n_src);
-    unsigned grid = 0;
-    float *partials = nullptr;
-    if (n) {
-        const uint32_t tl = std::min(ceil_log2(width), 8u);            // threads per row: the power of two covering the width, <= 256
-        const size_t R = 256u >> tl;
-        grid = (unsigned)std::min<size_t>((n + R - 1) / R, kGatColsumBlocks);
-        partials = stream_scratch(st, scratch_kind::colsums, (size_t)kGatColsumBlocks * 2 * width);
-        hipLaunchKernelGGL(gat_scores_backward_kernel, dim3(grid), dim3(256), 0, st, ds_dst, Z_dst, ldzd, n_dst, ds_src, Z_src,
-                           ldzs, n_src, K, dh, tl, partials);
-        MGGCN_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(colsum_final_kernel, dim3(final_grid), dim3(256), 0, st, partials, grid, 2 * width, G_att, G_att + width,
-                       width);
-    MGGCN_CHECK_LAUNCH();
+    gat_column_sums<2>(stream, gat_scores_term{{ds_dst, ds_src}, {Z_dst, Z_src}, {ldzd, ldzs}, {n_dst, n_src}, K, dh},
+                       std::max(n_dst, n_src), width, G_att);
 }

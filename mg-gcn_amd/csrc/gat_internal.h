@@ -1,11 +1,15 @@
 // gat_internal.h -- what the graph attention kernels of gat.hip (GAT) and gatv2.hip (GATv2) share: the one-wave-per-row
-// layout with LPR-lane groups (gat.hip describes it), the group butterfly, the head-row loads, the head geometry and the
-// (VEC, NT, U) dispatch.  Internal linkage in each translation unit that includes it.  Not part of the ABI.
+// layout with LPR-lane groups (gat.hip describes it), the walk over a row's entries (entry_chunks), the group butterfly,
+// the head-row loads and the epilogue, the head geometry, the (VEC, NT, U) dispatch with the row launch, and the column-sum
+// pass behind G_att.  Internal linkage in each translation unit that includes it.  Not part of the ABI.
 #pragma once
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
+#include "reduce.h"
+#include "scratch_internal.h"
 
 namespace {
 
@@ -64,6 +68,75 @@ __device__ __forceinline__ float dot_head_row(const float (&a)[NT][VEC], const f
     return p;
 }
 
+// the sums over a row's entries: fold the G groups in fixed order, post(t, v, sum) gives the element its final value (the
+// forwards' 1 / sum, GATv2 backward_dst's att), and group 0 stores the columns below dh
+template <int VEC, int NT, class Post>
+__device__ __forceinline__ void fold_store_head_row(float *p, float (&acc)[NT][VEC], uint32_t lpr, uint32_t sub, uint32_t grp,
+                                                    uint32_t dh, Post post) {
+#pragma unroll
+    for (int t = 0; t < NT; t++) {
+#pragma unroll
+        for (int v = 0; v < VEC; v++) acc[t][v] = post(t, v, fold_groups(acc[t][v], lpr));
+        const uint32_t col = (t * lpr + sub) * VEC;
+        if (grp == 0 && col < dh) storev<VEC>(p + col, acc[t]);
+    }
+}
+template <int VEC, int NT>
+__device__ __forceinline__ void fold_store_head_row(float *p, float (&acc)[NT][VEC], uint32_t lpr, uint32_t sub, uint32_t grp,
+                                                    uint32_t dh) {
+    fold_store_head_row<VEC, NT>(p, acc, lpr, sub, grp, dh, [](int, int, float x) { return x; });
+}
+
+// The entry group `grp` handles at step (j, u) of a chunk: its number in the chunk, its index, whether it exists; of(x) is
+// the owner lane's x (ds_bpermute)
+struct chunk_entry {
+    uint32_t src, c;
+    bool ok;
+    template <class T>
+    __device__ __forceinline__ T of(T x) const { return __shfl(x, src & 63); }
+};
+
+// The walk of one wave over the CSR row [beg, end) in 64-entry chunks, software-pipelined: lane l owns entry l of the chunk,
+// its index is fetched two chunks ahead and its NS scalars -- fetch(c, s) loads those of index c into s[0 .. NS) -- one chunk
+// ahead; whatever lies beyond the row's end is not fetched and reads as zero.  start() before the loop over base = beg,
+// beg + 64, ...; next() at the top of every turn leaves the chunk's my_c, my_s and cnt = min(64, end - base).  The bounds are
+// tested in 64 bits: a row may end within 128 entries of 2^32.
+template <int NS>
+struct entry_chunks {
+    uint32_t my_c, cnt;
+    float my_s[NS ? NS : 1];
+
+    template <class Fetch>
+    __device__ __forceinline__ void start(const uint32_t *__restrict__ indices, uint32_t beg, uint32_t end, uint32_t lane,
+                                          Fetch fetch) {
+        c1 = c2 = 0;
+        zerov(s1);
+        if ((size_t)beg + lane < end) { c1 = indices[beg + lane]; fetch(c1, s1); }
+        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+    }
+    template <class Fetch>
+    __device__ __forceinline__ void next(const uint32_t *__restrict__ indices, uint32_t base, uint32_t end, uint32_t lane,
+                                         Fetch fetch) {
+        my_c = c1;
+#pragma unroll
+        for (int s = 0; s < NS; s++) my_s[s] = s1[s];
+        c1 = c2;
+        zerov(s1); c2 = 0;
+        if ((size_t)base + 64 + lane < end) fetch(c1, s1);
+        if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
+        cnt = min(64u, end - base);
+    }
+    __device__ __forceinline__ chunk_entry pick(uint32_t j, int u, uint32_t n_grp, uint32_t grp) const {
+        const uint32_t src = j + u * n_grp + grp;
+        return {src, (uint32_t)__shfl(my_c, src & 63), src < cnt};
+    }
+
+private:
+    uint32_t c1, c2;
+    float s1[NS ? NS : 1];
+};
+__device__ __forceinline__ void no_scalars(uint32_t, float *) {}
+
 #define MGGCN_GAT_WAVE_ROW(n_rows)                                                                            \
     const uint32_t lane = threadIdx.x & 63;                                                                   \
     const uint32_t lpr = 1u << lg, n_grp = 64u >> lg, sub = lane & (lpr - 1), grp = lane >> lg;               \
@@ -91,17 +164,84 @@ void require_heads(uint32_t K, uint32_t dh) {
 
 bool rows16(const float *p, size_t ld) { return aligned16(p) && ld % 4 == 0; }
 
-// (VEC, NT, U) from the path and the tile count: vec needs <= 4 tiles (dh <= 1024), the element path <= 16
-#define MGGCN_GAT_DISPATCH(F, vec, nt)        \
-    do {                                      \
-        if (vec) {                            \
-            if ((nt) == 1) F(4, 1, 4);        \
-            else F(4, 4, 1);                  \
-        } else {                              \
-            if ((nt) == 1) F(1, 1, 4);        \
-            else if ((nt) <= 4) F(1, 4, 2);   \
-            else F(1, 16, 1);                 \
-        }                                     \
-    } while (0)
+// (VEC, NT, U) from the path and the tile count: vec needs <= 4 tiles (dh <= 1024), the element path <= 16.  f gets the
+// variant as a tag; with_flag hands a run-time flag (DROP, REC) on as a std::bool_constant.
+template <int VEC_, int NT_, int U_>
+struct gat_variant { static constexpr int VEC = VEC_, NT = NT_, U = U_; };
+template <class F>
+void gat_dispatch(bool vec, uint32_t nt, F f) {
+    if (vec) {
+        if (nt == 1) f(gat_variant<4, 1, 4>{});
+        else f(gat_variant<4, 4, 1>{});
+    } else {
+        if (nt == 1) f(gat_variant<1, 1, 4>{});
+        else if (nt <= 4) f(gat_variant<1, 4, 2>{});
+        else f(gat_variant<1, 16, 1>{});
+    }
+}
+template <class F>
+void with_flag(bool flag, F f) {
+    if (flag) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+// one wave per row, four rows per workgroup (MGGCN_GAT_WAVE_ROW)
+template <class... P, class... A>
+void launch_rows(void (*kernel)(P...), size_t n_rows, mggcn_stream_t stream, A... args) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, as_stream(stream), args...);
+    MGGCN_CHECK_LAUNCH();
+}
+
+// ---------------------------------------------------------------------------
+// The column sums behind G_att: out[side][c] = sum over r < term.rows(side) of the term at (side, r, c), which `term` adds as
+// acc = term(side, r, c, term.head(c), acc).  A workgroup walks rows blockIdx * R + rr, + gridDim * R, ... (R = 256 / tpr rows
+// at a time, tpr threads per row), folds its R row slots in LDS in slot order and stores one [SIDES x width] partial;
+// colsum_final_kernel (reduce.h) adds the partials in workgroup order.
+// ---------------------------------------------------------------------------
+template <int SIDES, class Term>
+__global__ __launch_bounds__(256) void gat_colsum_partial_kernel(Term term, uint32_t width, uint32_t tl,
+                                                                 float *__restrict__ partials) {
+    __shared__ float red[256];
+    const uint32_t tpr = 1u << tl, R = 256u >> tl, rr = threadIdx.x >> tl, cc = threadIdx.x & (tpr - 1);
+#pragma unroll
+    for (int side = 0; side < SIDES; side++) {
+        const size_t n = term.rows(side);
+        for (uint32_t c0 = 0; c0 < width; c0 += tpr) {      // every thread of the block takes every turn (barriers)
+            const uint32_t c = c0 + cc;
+            const bool on = c < width;
+            const uint32_t k = on ? term.head(c) : 0;
+            float acc = 0.f;
+            if (on)
+                for (size_t r = (size_t)blockIdx.x * R + rr; r < n; r += (size_t)gridDim.x * R) acc = term(side, r, c, k, acc);
+            red[threadIdx.x] = acc;
+            __syncthreads();
+            if (rr == 0 && on) {
+                float s = red[cc];
+                for (uint32_t q = 1; q < R; q++) s += red[q * tpr + cc];
+                partials[((size_t)blockIdx.x * SIDES + side) * width + c] = s;
+            }
+            __syncthreads();
+        }
+    }
+}
+
+// G_att [SIDES x width] from the partials of at most kGatColsumBlocks workgroups; n = the most rows of a side
+template <int SIDES, class Term>
+void gat_column_sums(mggcn_stream_t stream, const Term &term, size_t n, uint32_t width, float *G_att) {
+    const hipStream_t st = as_stream(stream);
+    unsigned grid = 0;
+    float *partials = nullptr;
+    if (n) {
+        const uint32_t tl = std::min(ceil_log2(width), 8u);            // threads per row: the power of two covering the width, <= 256
+        const size_t R = 256u >> tl;
+        grid = (unsigned)std::min<size_t>((n + R - 1) / R, kGatColsumBlocks);
+        partials = stream_scratch(st, scratch_kind::colsums, (size_t)kGatColsumBlocks * SIDES * width);
+        hipLaunchKernelGGL((gat_colsum_partial_kernel<SIDES, Term>), dim3(grid), dim3(256), 0, st, term, width, tl, partials);
+        MGGCN_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(colsum_final_kernel, dim3((SIDES * width + 63) / 64), dim3(256), 0, st, partials, grid, SIDES * width, G_att,
+                       G_att + (SIDES - 1) * width, width);
+    MGGCN_CHECK_LAUNCH();
+}
 
 }  // namespace

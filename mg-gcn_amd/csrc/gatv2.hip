@@ -4,8 +4,8 @@
 // so the score of an entry exists only after the source's head-row has been gathered: there are no [rows x K] score
 // scalars to stream, and every sparse kernel computes e with the group butterfly on the rows it gathers anyway.
 //
-// Layout: gat.hip's (gat_internal.h) -- one wave per CSR row, 64-entry chunks with the indices two chunks ahead, the heads
-// one after the other, G = 64 / LPR groups of LPR lanes that each hold one head-row of a neighbour, (VEC, NT, U) variants.
+// Layout: gat.hip's -- one wave per CSR row, walked in 64-entry chunks by entry_chunks (gat_internal.h), the heads one
+// after the other, G = 64 / LPR groups of LPR lanes that each hold one head-row of a neighbour, (VEC, NT, U) variants.
 //   * forward: ONE pass over a row with one gather of Zs per entry.  The group that gathered a neighbour computes its score,
 //     so the running maximum is kept PER GROUP (m, sum and the accumulators of a group are rescaled when its maximum
 //     moves); at the end the groups meet at the wave's maximum M: group g enters with the factor exp(m_g - M), the sums
@@ -13,9 +13,9 @@
 //   * backward_dst (rows of F): D, G_Zd and P[i] = sum_j ds_ijk u_ijk, row i's share of G_att; e and dalpha are two
 //     butterflies over the same gathered row.
 //   * backward_src (rows of F^T): gathers the destination's head-rows of Zd and G, recomputes e, dalpha, alpha and ds, and
-//     accumulates alpha G_i + v.  lse and D of the destination are two 4-byte gathers by the lane that owns the entry, one
-//     chunk ahead (DESIGN.md 3.10.2 says why they are not packed).
-//   * att_grad: the column sums of P through per-workgroup partials and colsum_final_kernel (reduce.h).
+//     accumulates alpha G_i + v.  lse and D of the destination are two 4-byte gathers by the lane that owns the entry
+//     (the walk's scalars; DESIGN.md 3.10.2 says why they are not packed).
+//   * att_grad: the column sums of P through gat_column_sums (gat_internal.h).
 // Nothing of nnz x K is stored, no atomics, a row's result depends on that row alone: the same bits on every call and for
 // every split of the rows between calls.
 #include <algorithm>
@@ -24,7 +24,6 @@
 #include "common.h"
 #include "gat_internal.h"
 #include "reduce.h"
-#include "scratch_internal.h"
 
 namespace {
 
@@ -61,29 +60,24 @@ __global__ __launch_bounds__(256) void gatv2_forward_kernel(uint32_t n_rows, con
         for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
         const float *__restrict__ Zk = Zs + (size_t)k * dh;
         float m = -INFINITY, sum = 0.f;             // of my group: every lane of a group holds the same bits
-        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead
-        if (beg + lane < end) c1 = indices[beg + lane];
-        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        entry_chunks<0> ch;                         // the indices alone
+        ch.start(indices, beg, end, lane, no_scalars);
         for (uint32_t base = beg; base < end; base += 64) {
-            const uint32_t my_c = c1;
-            c1 = c2;
-            c2 = 0;
-            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
-            const uint32_t cnt = min(64u, end - base);
+            ch.next(indices, base, end, lane, no_scalars);
+            const uint32_t cnt = ch.cnt;
             for (uint32_t j = 0; j < cnt; j += n_grp * U) {
                 float z[U][NT][VEC], e[U];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const uint32_t c = __shfl(my_c, src & 63);
-                    load_head_row<VEC, NT>(z[u], Zk + (size_t)c * ldzs, lpr, sub, dh, src < cnt);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    load_head_row<VEC, NT>(z[u], Zk + (size_t)en.c * ldzs, lpr, sub, dh, en.ok);
                     e[u] = score_head_row<VEC, NT>(a, zd, z[u], slope);
                 }
                 float m_new = m;
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     e[u] = group_sum(e[u], lpr);
-                    if (j + u * n_grp + grp >= cnt) e[u] = -INFINITY;
+                    if (!ch.pick(j, u, n_grp, grp).ok) e[u] = -INFINITY;
                     m_new = fmaxf(m_new, e[u]);
                 }
                 // m_new = -inf: my group has not met an entry yet, nothing to rescale and every weight below is 0
@@ -115,12 +109,11 @@ __global__ __launch_bounds__(256) void gatv2_forward_kernel(uint32_t n_rows, con
         const float inv = beg < end ? 1.f / sum : 0.f;
         if (lane == 0) lse[row * K + k] = beg < end ? M + logf(sum) : 0.f;
 #pragma unroll
-        for (int t = 0; t < NT; t++) {
+        for (int t = 0; t < NT; t++)
 #pragma unroll
-            for (int v = 0; v < VEC; v++) acc[t][v] = fold_groups(acc[t][v] * f, lpr) * inv;
-            const uint32_t col = (t * lpr + sub) * VEC;
-            if (grp == 0 && col < dh) storev<VEC>(out + row * ldo + (size_t)k * dh + col, acc[t]);   // an empty row: +0.0
-        }
+            for (int v = 0; v < VEC; v++) acc[t][v] *= f;
+        fold_store_head_row<VEC, NT>(out + row * ldo + (size_t)k * dh, acc, lpr, sub, grp, dh,
+                                     [&](int, int, float x) { return x * inv; });      // an empty row: +0.0
     }
 }
 
@@ -156,29 +149,24 @@ __global__ __launch_bounds__(256) void gatv2_backward_dst_kernel(uint32_t n_rows
         for (int t = 0; t < NT; t++) { zerov<VEC>(accv[t]); zerov<VEC>(accp[t]); }
         const float ls = lse[row * K + k];
         const float *__restrict__ Zk = Zs + (size_t)k * dh;
-        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead
-        if (beg + lane < end) c1 = indices[beg + lane];
-        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        entry_chunks<0> ch;                         // the indices alone
+        ch.start(indices, beg, end, lane, no_scalars);
         for (uint32_t base = beg; base < end; base += 64) {
-            const uint32_t my_c = c1;
-            c1 = c2;
-            c2 = 0;
-            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
-            const uint32_t cnt = min(64u, end - base);
+            ch.next(indices, base, end, lane, no_scalars);
+            const uint32_t cnt = ch.cnt;
             for (uint32_t j = 0; j < cnt; j += n_grp * U) {
                 float z[U][NT][VEC], pe[U], pd[U];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const uint32_t c = __shfl(my_c, src & 63);
-                    load_head_row<VEC, NT>(z[u], Zk + (size_t)c * ldzs, lpr, sub, dh, src < cnt);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    load_head_row<VEC, NT>(z[u], Zk + (size_t)en.c * ldzs, lpr, sub, dh, en.ok);
                     pe[u] = score_head_row<VEC, NT>(a, zd, z[u], slope);
                     pd[u] = dot_head_row<VEC, NT>(g, z[u]);
                 }
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     const float e = group_sum(pe[u], lpr), da = group_sum(pd[u], lpr);
-                    const float ds = j + u * n_grp + grp < cnt ? expf(e - ls) * (da - Dk) : 0.f;
+                    const float ds = ch.pick(j, u, n_grp, grp).ok ? expf(e - ls) * (da - Dk) : 0.f;
                     const float dss = ds * slope;
 #pragma unroll
                     for (int t = 0; t < NT; t++)
@@ -192,19 +180,9 @@ __global__ __launch_bounds__(256) void gatv2_backward_dst_kernel(uint32_t n_rows
             }
         }
         if (lane == 0) D[row * K + k] = Dk;
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-#pragma unroll
-            for (int v = 0; v < VEC; v++) {
-                accv[t][v] = fold_groups(accv[t][v], lpr) * a[t][v];
-                accp[t][v] = fold_groups(accp[t][v], lpr);
-            }
-            const uint32_t col = (t * lpr + sub) * VEC;
-            if (grp == 0 && col < dh) {
-                storev<VEC>(G_Zd + row * ldgzd + (size_t)k * dh + col, accv[t]);
-                storev<VEC>(P + row * ldp + (size_t)k * dh + col, accp[t]);
-            }
-        }
+        fold_store_head_row<VEC, NT>(G_Zd + row * ldgzd + (size_t)k * dh, accv, lpr, sub, grp, dh,
+                                     [&](int t, int v, float x) { return x * a[t][v]; });
+        fold_store_head_row<VEC, NT>(P + row * ldp + (size_t)k * dh, accp, lpr, sub, grp, dh);
     }
 }
 
@@ -231,42 +209,32 @@ __global__ __launch_bounds__(256) void gatv2_backward_src_kernel(uint32_t n_rows
         for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
         const float *__restrict__ Zdk = Zd + (size_t)k * dh;
         const float *__restrict__ Gk = G + (size_t)k * dh;
-        uint32_t c1 = 0, c2 = 0;                    // indices two chunks ahead, the destinations' lse and D one chunk ahead
-        float l1 = 0.f, D1 = 0.f;
-        if (beg + lane < end) {
-            c1 = indices[beg + lane];
-            l1 = lse[(size_t)c1 * K + k];
-            D1 = D[(size_t)c1 * K + k];
-        }
-        if ((size_t)beg + 64 + lane < end) c2 = indices[beg + 64 + lane];
+        const auto fetch = [&](uint32_t c, float *s) {          // lse and D of the entry's destination
+            s[0] = lse[(size_t)c * K + k];
+            s[1] = D[(size_t)c * K + k];
+        };
+        entry_chunks<2> ch;
+        ch.start(indices, beg, end, lane, fetch);
         for (uint32_t base = beg; base < end; base += 64) {
-            const uint32_t my_c = c1;
-            const float my_l = l1, my_D = D1;
-            c1 = c2;
-            l1 = 0.f; D1 = 0.f; c2 = 0;
-            if ((size_t)base + 64 + lane < end) {
-                l1 = lse[(size_t)c1 * K + k];
-                D1 = D[(size_t)c1 * K + k];
-            }
-            if ((size_t)base + 128 + lane < end) c2 = indices[base + 128 + lane];
-            const uint32_t cnt = min(64u, end - base);
+            ch.next(indices, base, end, lane, fetch);
+            const uint32_t cnt = ch.cnt;
+            const float my_l = ch.my_s[0], my_D = ch.my_s[1];
             for (uint32_t j = 0; j < cnt; j += n_grp * U) {
                 float zv[U][NT][VEC], gv[U][NT][VEC], pe[U], pd[U];
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const uint32_t c = __shfl(my_c, src & 63);
-                    load_head_row<VEC, NT>(zv[u], Zdk + (size_t)c * ldzd, lpr, sub, dh, src < cnt);
-                    load_head_row<VEC, NT>(gv[u], Gk + (size_t)c * ldg, lpr, sub, dh, src < cnt);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    load_head_row<VEC, NT>(zv[u], Zdk + (size_t)en.c * ldzd, lpr, sub, dh, en.ok);
+                    load_head_row<VEC, NT>(gv[u], Gk + (size_t)en.c * ldg, lpr, sub, dh, en.ok);
                     pe[u] = score_head_row<VEC, NT>(a, zv[u], zs, slope);
                     pd[u] = dot_head_row<VEC, NT>(zs, gv[u]);
                 }
 #pragma unroll
                 for (int u = 0; u < U; u++) {
-                    const uint32_t src = j + u * n_grp + grp;
-                    const float l = __shfl(my_l, src & 63), Dv = __shfl(my_D, src & 63);
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    const float l = en.of(my_l), Dv = en.of(my_D);
                     const float e = group_sum(pe[u], lpr), da = group_sum(pd[u], lpr);
-                    const float al = src < cnt ? expf(e - l) : 0.f;
+                    const float al = en.ok ? expf(e - l) : 0.f;
                     const float ds = al * (da - Dv), dss = ds * slope;
 #pragma unroll
                     for (int t = 0; t < NT; t++)
@@ -279,41 +247,18 @@ __global__ __launch_bounds__(256) void gatv2_backward_src_kernel(uint32_t n_rows
                 }
             }
         }
-#pragma unroll
-        for (int t = 0; t < NT; t++) {
-#pragma unroll
-            for (int v = 0; v < VEC; v++) acc[t][v] = fold_groups(acc[t][v], lpr);
-            const uint32_t col = (t * lpr + sub) * VEC;
-            if (grp == 0 && col < dh) storev<VEC>(G_Zs + row * ldgzs + (size_t)k * dh + col, acc[t]);
-        }
+        fold_store_head_row<VEC, NT>(G_Zs + row * ldgzs + (size_t)k * dh, acc, lpr, sub, grp, dh);
     }
 }
 
-// ---------------------------------------------------------------------------
-// partials[b, c] = the sum of P[r, c] over the rows r workgroup b walks: rows blockIdx * R + rr, + gridDim * R, ... (R = 256 / tpr
-// rows at a time, tpr threads per row), the R row slots folded in LDS in slot order; colsum_final_kernel (reduce.h) adds the
-// partials in workgroup order.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void gatv2_att_grad_kernel(const float *__restrict__ P, size_t ldp, size_t n, uint32_t width,
-                                                             uint32_t tl, float *__restrict__ partials) {
-    __shared__ float red[256];
-    const uint32_t tpr = 1u << tl, R = 256u >> tl, rr = threadIdx.x >> tl, cc = threadIdx.x & (tpr - 1);
-    for (uint32_t c0 = 0; c0 < width; c0 += tpr) {          // every thread of the block takes every turn (barriers)
-        const uint32_t c = c0 + cc;
-        const bool on = c < width;
-        float acc = 0.f;
-        if (on)
-            for (size_t r = (size_t)blockIdx.x * R + rr; r < n; r += (size_t)gridDim.x * R) acc += P[r * ldp + c];
-        red[threadIdx.x] = acc;
-        __syncthreads();
-        if (rr == 0 && on) {
-            float s = red[cc];
-            for (uint32_t q = 1; q < R; q++) s += red[q * tpr + cc];
-            partials[(size_t)blockIdx.x * width + c] = s;
-        }
-        __syncthreads();
-    }
-}
+// G_att[0, c] = sum_i P[i, c]: the term of gat_column_sums, one side
+struct gatv2_att_term {
+    const float *P;
+    size_t ldp, n;
+    __device__ size_t rows(int) const { return n; }
+    __device__ uint32_t head(uint32_t) const { return 0; }
+    __device__ float operator()(int, size_t r, uint32_t c, uint32_t, float acc) const { return acc + P[r * ldp + c]; }
+};
 
 }  // namespace
 
@@ -332,12 +277,10 @@ MGGCN_API void mggcn_gatv2_forward_f32(mggcn_stream_t stream, uint32_t n_rows, u
     MGGCN_REQUIRE(out != Zs && out != Zd, "gatv2 forward: out must not alias Zs or Zd");
     const bool vec = dh % 4 == 0 && rows16(Zs, ldzs) && rows16(Zd, ldzd) && rows16(out, ldo) && aligned16(att);
     const head_geometry hg = head_geometry_for(dh, vec);
-#define MGGCN_GATV2_FWD(V, NT, U)                                                                                              \
-    hipLaunchKernelGGL((gatv2_forward_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows,      \
-                       indptr, indices, Zs, ldzs, Zd, ldzd, att, K, dh, slope, hg.lg, out, ldo, lse)
-    MGGCN_GAT_DISPATCH(MGGCN_GATV2_FWD, vec, hg.nt);
-#undef MGGCN_GATV2_FWD
-    MGGCN_CHECK_LAUNCH();
+    gat_dispatch(vec, hg.nt, [&](auto v) {
+        launch_rows(gatv2_forward_kernel<v.VEC, v.NT, v.U>, n_rows, stream, n_rows, indptr, indices, Zs, ldzs, Zd, ldzd, att, K, dh,
+                    slope, hg.lg, out, ldo, lse);
+    });
 }
 
 MGGCN_API void mggcn_gatv2_backward_dst_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
@@ -359,13 +302,10 @@ MGGCN_API void mggcn_gatv2_backward_dst_f32(mggcn_stream_t stream, uint32_t n_ro
     const bool vec = dh % 4 == 0 && rows16(Zs, ldzs) && rows16(Zd, ldzd) && rows16(G, ldg) && rows16(out, ldo) &&
                      rows16(G_Zd, ldgzd) && rows16(P, ldp) && aligned16(att);
     const head_geometry hg = head_geometry_for(dh, vec);
-#define MGGCN_GATV2_BWD_DST(V, NT, U)                                                                                          \
-    hipLaunchKernelGGL((gatv2_backward_dst_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
-                       indptr, indices, Zs, ldzs, Zd, ldzd, att, lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, G_Zd, ldgzd, P, \
-                       ldp)
-    MGGCN_GAT_DISPATCH(MGGCN_GATV2_BWD_DST, vec, hg.nt);
-#undef MGGCN_GATV2_BWD_DST
-    MGGCN_CHECK_LAUNCH();
+    gat_dispatch(vec, hg.nt, [&](auto v) {
+        launch_rows(gatv2_backward_dst_kernel<v.VEC, v.NT, v.U>, n_rows, stream, n_rows, indptr, indices, Zs, ldzs, Zd, ldzd, att,
+                    lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, G_Zd, ldgzd, P, ldp);
+    });
 }
 
 MGGCN_API void mggcn_gatv2_att_grad_f32(mggcn_stream_t stream, const float *P, size_t ldp, size_t n_rows, uint32_t width,
@@ -374,19 +314,7 @@ MGGCN_API void mggcn_gatv2_att_grad_f32(mggcn_stream_t stream, const float *P, s
     MGGCN_REQUIRE(ldp >= width, "gatv2 att grad: ldp < width");
     MGGCN_REQUIRE(G_att != nullptr, "gatv2 att grad: null gradient");
     MGGCN_REQUIRE(n_rows == 0 || P != nullptr, "gatv2 att grad: null operand");
-    const hipStream_t st = as_stream(stream);
-    unsigned grid = 0;
-    float *partials = nullptr;
-    if (n_rows) {
-        const uint32_t tl = std::min(ceil_log2(width), 8u);            // threads per row: the power of two covering the width, <= 256
-        const size_t R = 256u >> tl;
-        grid = (unsigned)std::min<size_t>((n_rows + R - 1) / R, kGatColsumBlocks);
-        partials = stream_scratch(st, scratch_kind::colsums, (size_t)kGatColsumBlocks * width);
-        hipLaunchKernelGGL(gatv2_att_grad_kernel, dim3(grid), dim3(256), 0, st, P, ldp, n_rows, width, tl, partials);
-        MGGCN_CHECK_LAUNCH();
-    }
-    hipLaunchKernelGGL(colsum_final_kernel, dim3((width + 63) / 64), dim3(256), 0, st, partials, grid, width, G_att, G_att, width);
-    MGGCN_CHECK_LAUNCH();
+    gat_column_sums<1>(stream, gatv2_att_term{P, ldp, n_rows}, n_rows, width, G_att);
 }
 
 MGGCN_API void mggcn_gatv2_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
@@ -404,10 +332,8 @@ MGGCN_API void mggcn_gatv2_backward_src_f32(mggcn_stream_t stream, uint32_t n_ro
     MGGCN_REQUIRE(G_Zs != G && G_Zs != Zs && G_Zs != Zd, "gatv2 backward: G_Zs must not alias G, Zs or Zd");
     const bool vec = dh % 4 == 0 && rows16(Zs, ldzs) && rows16(Zd, ldzd) && rows16(G, ldg) && rows16(G_Zs, ldgzs) && aligned16(att);
     const head_geometry hg = head_geometry_for(dh, vec);
-#define MGGCN_GATV2_BWD_SRC(V, NT, U)                                                                                          \
-    hipLaunchKernelGGL((gatv2_backward_src_kernel<V, NT, U>), dim3((n_rows + 3) / 4), dim3(256), 0, as_stream(stream), n_rows, \
-                       t_indptr, t_indices, Zs, ldzs, Zd, ldzd, att, lse, D, G, ldg, K, dh, slope, hg.lg, G_Zs, ldgzs)
-    MGGCN_GAT_DISPATCH(MGGCN_GATV2_BWD_SRC, vec, hg.nt);
-#undef MGGCN_GATV2_BWD_SRC
-    MGGCN_CHECK_LAUNCH();
+    gat_dispatch(vec, hg.nt, [&](auto v) {
+        launch_rows(gatv2_backward_src_kernel<v.VEC, v.NT, v.U>, n_rows, stream, n_rows, t_indptr, t_indices, Zs, ldzs, Zd, ldzd,
+                    att, lse, D, G, ldg, K, dh, slope, hg.lg, G_Zs, ldgzs);
+    });
 }

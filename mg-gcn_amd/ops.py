@@ -439,6 +439,14 @@ def _gat_timed(ctx: context, timer: Optional[str], call) -> None:
     ctx.register_timer(timer, timer + "_0", timer + "_1")
 
 
+def _gat_call(ctx: context, timer: Optional[str], name: str, args, extra) -> None:
+    """mggcn_<name>_f32(*args) under ``timer``; with ``extra`` (the tuple of _gat_drop_args) its _drop twin, which takes it last"""
+    if extra is None:
+        _gat_timed(ctx, timer, lambda: getattr(ctx.lib, f"mggcn_{name}_f32")(*args))
+    else:
+        _gat_timed(ctx, timer, lambda: getattr(ctx.lib, f"mggcn_{name}_drop_f32")(*args, *extra))
+
+
 def _gat_drop_args(drop, what: str, n_dst: int, n_src: int):
     """the six trailing arguments of a mggcn_gat_*_drop_f32 call from ``drop`` = (threshold, scale, seed, stream, dst0, src0):
     threshold and scale as dropout_params gives them; ValueError before the library for anything out of range"""
@@ -481,10 +489,7 @@ def gat_forward(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_s
     ip, ix, _ = F.device(ctx.device)
     args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(), heads,
             Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer())
-    if extra is None:
-        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_forward_f32(*args))
-    else:
-        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_forward_drop_f32(*args, *extra))
+    _gat_call(ctx, timer, "gat_forward", args, extra)
 
 
 def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
@@ -501,10 +506,17 @@ def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix
     ip, ix, _ = F.device(ctx.device)
     args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
             lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer())
-    if extra is None:
-        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_dst_f32(*args))
-    else:
-        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_dst_drop_f32(*args, *extra))
+    _gat_call(ctx, timer, "gat_backward_dst", args, extra)
+
+
+def _req_gat_backward_src(F_T, Z, dst_scalars, s_src, G, att, ds_dst, ds_src, G_Z, heads: int, which: str) -> None:
+    """the shapes of gat_backward_src and gat_backward_src_rec; ``dst_scalars``: the [destinations x heads] operands"""
+    check_gat_heads(heads, Z.m(), "gat backward")
+    _req(F_T.n() == Z.n() and G.shape() == (F_T.m(), Z.m()) and G_Z.shape() == Z.shape(), "gat backward: shape mismatch")
+    _req(att.shape() == (2, Z.m()), f"gat backward: att must be 2 x {Z.m()}")
+    _req(all(s.shape() == (F_T.m(), heads) for s in dst_scalars) and s_src.shape() == (F_T.n(), heads)
+         and ds_src.shape() == (F_T.n(), heads) and (ds_dst is None or ds_dst.shape() == (F_T.n(), heads)),
+         f"gat backward: {which} must be rows x heads")
 
 
 def gat_backward_src(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
@@ -515,21 +527,13 @@ def gat_backward_src(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matr
     ds_src[j, k] att[1, head k].  ds_dst is indexed by source here (the square case passes gat_backward_dst's); None leaves
     its term out.  ``drop``: the forward's tuple (see gat_forward; mggcn_gat_backward_src_drop_f32) -- F_T's rows are the
     sources (offset src0), its entries the destinations (offset dst0)."""
-    check_gat_heads(heads, Z.m(), "gat backward")
-    _req(F_T.n() == Z.n() and G.shape() == (F_T.m(), Z.m()) and G_Z.shape() == Z.shape(), "gat backward: shape mismatch")
-    _req(att.shape() == (2, Z.m()), f"gat backward: att must be 2 x {Z.m()}")
-    _req(all(s.shape() == (F_T.m(), heads) for s in (s_dst, lse, D)) and s_src.shape() == (F_T.n(), heads)
-         and ds_src.shape() == (F_T.n(), heads) and (ds_dst is None or ds_dst.shape() == (F_T.n(), heads)),
-         "gat backward: the scores, lse, D and ds must be rows x heads")
+    _req_gat_backward_src(F_T, Z, (s_dst, lse, D), s_src, G, att, ds_dst, ds_src, G_Z, heads, "the scores, lse, D and ds")
     extra = None if drop is None else _gat_drop_args(drop, "gat backward", F_T.m(), F_T.n())
     ip, ix, _ = F_T.device(ctx.device)
     args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
             lse.buffer(), D.buffer(), G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
             Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m())
-    if extra is None:
-        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_f32(*args))
-    else:
-        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_drop_f32(*args, *extra))
+    _gat_call(ctx, timer, "gat_backward_src", args, extra)
 
 
 def _req_gat_rec(rec, rows: int, heads: int, what: str) -> None:
@@ -556,21 +560,14 @@ def gat_backward_src_rec(ctx: context, F_T: csr_matrix, Z: dn_matrix, rec, s_src
     """gat_backward_src with the destinations' (s_dst, lse, D) as the records of gat_pack_dst (mggcn_gat_backward_src_rec_f32
     / _rec_drop_f32): one 16-byte load per (entry, head) where the plain call gathers three scalars, and the bits of the
     plain call on the arrays the record was packed from.  ``rec``: F_T.m() x heads x 4 floats."""
-    check_gat_heads(heads, Z.m(), "gat backward")
-    _req(F_T.n() == Z.n() and G.shape() == (F_T.m(), Z.m()) and G_Z.shape() == Z.shape(), "gat backward: shape mismatch")
-    _req(att.shape() == (2, Z.m()), f"gat backward: att must be 2 x {Z.m()}")
-    _req(s_src.shape() == (F_T.n(), heads) and ds_src.shape() == (F_T.n(), heads)
-         and (ds_dst is None or ds_dst.shape() == (F_T.n(), heads)), "gat backward: the scores and ds must be rows x heads")
+    _req_gat_backward_src(F_T, Z, (), s_src, G, att, ds_dst, ds_src, G_Z, heads, "the scores and ds")
     _req_gat_rec(rec, F_T.m(), heads, "gat backward")
     extra = None if drop is None else _gat_drop_args(drop, "gat backward", F_T.m(), F_T.n())
     ip, ix, _ = F_T.device(ctx.device)
     args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), rec.data_ptr(), s_src.buffer(),
             G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads, Z.m() // heads, slope,
             ds_src.buffer(), G_Z.buffer(), G_Z.m())
-    if extra is None:
-        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_rec_f32(*args))
-    else:
-        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_backward_src_rec_drop_f32(*args, *extra))
+    _gat_call(ctx, timer, "gat_backward_src_rec", args, extra)
 
 
 def gat_scores_backward(ctx: context, ds_dst: dn_matrix, Z_dst: dn_matrix, ds_src: dn_matrix, Z_src: dn_matrix,
