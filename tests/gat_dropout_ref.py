@@ -247,10 +247,11 @@ class oracle_gat_dropout(ref.oracle_gat):
         return self._keep[key]
 
     def _attention(self, li, L, on, G=None):
+        D = None if G is None else self._D(L, G)
         if on and self.attn_p > 0.0:
-            return twin32(self.indptr, self.indices, L.Z, L.att, L.heads, self._mask(li, L.heads),
-                          dropout_ref.params(self.attn_p)[1], G=G, slope=self.slope)
-        return ref.twin32(self.indptr, self.indices, L.Z, L.att, L.heads, G=G, slope=self.slope)
+            return (restate64 if self.exact else twin32)(self.indptr, self.indices, L.Z, L.att, L.heads, self._mask(li, L.heads),
+                                                         dropout_ref.params(self.attn_p)[1], G=G, slope=self.slope, D=D)
+        return self._attend(self.indptr, self.indices, L.Z, L.att, L.heads, G=G, slope=self.slope, D=D)
 
     def forward(self, H):
         orc = self.orc

@@ -465,13 +465,16 @@ class oracle_gat:
     are, and the fp32 twin of the attention between them.  ``layers[i]`` has lin (oracle.Linear), att, G_att and the Adam
     state of att; att starts as the engine's (seed-99 uniform over an [out x 2] buffer) and is updated by the chain
     Linear.adam_update runs for W, with the oracle's own kernels.  ``loss``: None (the oracle's softmax cross-entropy over
-    all rows) or a callable H -> (G, (loss, score)) -- the BCE and split tests pass theirs."""
+    all rows) or a callable H -> (G, (loss, score)) -- the BCE and split tests pass theirs.  ``dtype``: np.float32 (the
+    default: the fp32 twin of the attention) or np.float64 (its fp64 restatement, rounded to fp32 where the linear takes
+    over) -- the model's other precision, which the option fuzz holds the twin against before the device is."""
 
     class _layer:
         pass
 
-    def __init__(self, oracle, A, sizes, heads, slope=SLOPE, loss=None):
+    def __init__(self, oracle, A, sizes, heads, slope=SLOPE, loss=None, dtype=np.float32):
         self.orc, self.slope, self.loss = oracle, slope, loss
+        self._set_dtype(dtype)
         F = oracle.transpose(A)                                 # the forward aggregates over A^T's rows, like oracle.Gcn
         self.indptr, self.indices = F.indptr.copy(), F.indices.copy()
         self.layers = []
@@ -485,12 +488,38 @@ class oracle_gat:
             L.step = 0
             self.layers.append(L)
 
+    def _set_dtype(self, dtype):
+        if np.dtype(dtype) not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError(f"dtype must be float32 or float64, not {dtype!r}")
+        self.dtype = np.dtype(dtype).type
+        self.exact = self.dtype is np.float64
+
+    def _attend(self, *a, **kw):
+        return (restate64 if self.exact else twin32)(*a, **kw)
+
+    reorder_D = False
+
+    def _D(self, L, T):
+        """D = G . out as the backward entry points take it: from the STORED fp32 out, in a sum of its own.  None leaves it to
+        attention(), which sums D and dalpha in one order, so that they cancel exactly in every one-entry row (alpha = 1,
+        out = Z[j]) -- no implementation with two kernels does.  fp64 restatement: the fp64 sum over the stored out.  Twin with
+        ``reorder_D`` set: the fp32 sum taken from the last column of a head to its first, the twin's "only the order of the
+        sums differs" applied to the one sum whose order decides whether ds of a one-entry row is 0 or rounding noise."""
+        if not (self.exact or self.reorder_D):
+            return None
+        n, d = L.out.shape
+        T3 = np.asarray(T).reshape(n, L.heads, d // L.heads)
+        o3 = L.out.reshape(n, L.heads, d // L.heads)
+        if self.exact:
+            return (T3.astype(np.float64) * o3.astype(np.float64)).sum(axis=2)
+        return np.ascontiguousarray((T3.astype(np.float32) * o3)[:, :, ::-1]).sum(axis=2, dtype=np.float32)
+
     def forward(self, H):
         orc = self.orc
         H = np.ascontiguousarray(H, dtype=np.float32)
         for L in self.layers:
             L.Z = L.lin.forward(H)
-            L.out = np.ascontiguousarray(twin32(self.indptr, self.indices, L.Z, L.att, L.heads, slope=self.slope)["out"])
+            L.out = np.ascontiguousarray(self._attend(self.indptr, self.indices, L.Z, L.att, L.heads, slope=self.slope)["out"])
             H = orc.leaky_relu_forward(L.out) if L.activation else L.out
         return H
 
@@ -507,7 +536,7 @@ class oracle_gat:
         orc, G = self.orc, self.G
         for L in reversed(self.layers):
             T = orc.leaky_relu_backward(L.out, G) if L.activation else G
-            r = twin32(self.indptr, self.indices, L.Z, L.att, L.heads, G=T, slope=self.slope)
+            r = self._attend(self.indptr, self.indices, L.Z, L.att, L.heads, G=T, slope=self.slope, D=self._D(L, T))
             L.G_att = r["G_att"]
             G = L.lin.backward(np.ascontiguousarray(r["G_Z"]))
 

@@ -235,8 +235,9 @@ class oracle_gatv2(ref.oracle_gat):
     e (counted from ``epoch``) the input of every layer l >= 1 is dropout_ref.apply(H) with stream e * 64 + l, and the gradient
     that layer returns goes through the same call."""
 
-    def __init__(self, oracle, A, sizes, heads, slope=SLOPE, loss=None, p=0.0, seed=0, epoch=0):
+    def __init__(self, oracle, A, sizes, heads, slope=SLOPE, loss=None, p=0.0, seed=0, epoch=0, dtype=np.float32):
         self.orc, self.slope, self.loss = oracle, slope, loss
+        self._set_dtype(dtype)
         F = oracle.transpose(A)
         self.indptr, self.indices = F.indptr.copy(), F.indices.copy()
         self.layers = []
@@ -257,8 +258,9 @@ class oracle_gatv2(ref.oracle_gat):
 
     def _twin(self, L, G=None):
         w = L.out_width
-        return twin32(self.indptr, self.indices, np.ascontiguousarray(L.Z[:, :w]), np.ascontiguousarray(L.Z[:, w:]), L.att,
-                      L.heads, G=G, slope=self.slope)
+        return (restate64 if self.exact else twin32)(self.indptr, self.indices, np.ascontiguousarray(L.Z[:, :w]),
+                                                     np.ascontiguousarray(L.Z[:, w:]), L.att, L.heads, G=G, slope=self.slope,
+                                                     D=None if G is None else self._D(L, G))
 
     def forward(self, H):
         orc = self.orc

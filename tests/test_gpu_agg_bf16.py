@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from bf16_ref import bf16_bits, round_bf16, widen
+from bf16_ref import GRAD_BAR, GRAD_BAR_REST, W_SOLID_BAR, bf16_bits, bf16_oracle as _bf16_oracle, round_bf16, widen
 
 pytestmark = pytest.mark.gpu
 
@@ -180,14 +180,6 @@ def _relerr(got, want):
     return float(np.abs(np.asarray(got, dtype=np.float64) - want).max() / (np.abs(want).max() + 1e-30))
 
 
-def _bf16_oracle(oracle, ip, ix, dv, n, sizes, residual_layer):
-    O = oracle.Gcn(oracle.Csr(ip, ix, dv, n), sizes, f64acc=True, residual_layer=residual_layer)
-    for L in O.layers:                                      # every aggregation multiplies by bf16(B)
-        L.spmm_fwd = lambda B, f=L.spmm_fwd: f(round_bf16(B))
-        L.spmm_bwd = lambda B, f=L.spmm_bwd: f(round_bf16(B))
-    return O
-
-
 def _sync_oracle_state(G, O):
     """identical inputs for the next epoch (as in test_gpu_gcn.py): weights and Adam moments of the device model"""
     for layer, ol in zip(G.layers(), O.layers):
@@ -197,17 +189,6 @@ def _sync_oracle_state(G, O):
                 olin.mW, olin.vW = lin.mW.numpy().copy(), lin.vW.numpy().copy()
                 olin.mb, olin.vb = lin.mb.numpy().copy(), lin.vb.numpy().copy()
                 olin.step = lin.step
-
-
-# Gradient bars.  The device and the oracle round DIFFERENT fp32 inputs to bf16 (they agree to ~1e-7, not bit for bit),
-# so an element within 1e-7 of a rounding midpoint goes one way here and the other way there: a 2^-8 relative jump.
-# The first layer's G_W = X^T T (random X) cancels down to a small fraction of its terms and shows those flips at
-# ~1e-3 of its largest entry (measured on the CPU with the fp32 oracle standing in for the device: up to 4.1e-3 over
-# three epochs); the layers above stay at <= 8e-5.  The bf16 model is farther from the fp32 model on the same
-# measure: 2.3e-2 .. 3.3e-2 on the first layer, >= 7e-4 above it -- while the LOSS of the two differs by ~1e-6 only.
-GRAD_BAR = {0: 1e-2}           # the first layer's G_W; every other gradient: GRAD_BAR_REST
-GRAD_BAR_REST = 3e-4
-W_SOLID_BAR = {0: 1e-2}        # well-conditioned entries of W after the Adam step (fp32 tests: TOL for all layers)
 
 
 @pytest.mark.parametrize("fused,residual", [(True, False), (False, False), (True, True)])
