@@ -470,7 +470,28 @@ void mggcn_gatv2_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32
                                   const uint32_t *t_indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
                                   const float *att, const float *lse, const float *D, const float *G, size_t ldg,
                                   uint32_t K, uint32_t dh, float slope, float *G_Zs, size_t ldgzs);
-/* cublasSasum   (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
+/* The export of the attention coefficients (opt-in: the one place where something of nnz x K is written, and no training
+ * call reads it).  Both take F as the calls above and the state a forward left behind -- s_dst, s_src, lse of
+ * mggcn_gat_scores_f32 / mggcn_gat_forward_f32, or Zs, Zd, att, lse of mggcn_gatv2_forward_f32 -- and write, for entry p of
+ * the indices array (row i, source j = indices[p]) and head k,
+ *   alpha[p lda + k] = exp(e_ijk - lse[i, k]),   lda >= K, offsets in size_t,
+ * which is the float expression the backward kernels of the same file evaluate: the exported value is the coefficient the
+ * model trains with (after a forward with attention dropout: the coefficient BEFORE the factor q, the softmax over all
+ * entries).  indptr values are used as they are: a call over rows [r0, r1) (indptr + r0, the row operands moved by r0 rows,
+ * alpha unmoved) writes exactly the positions the whole call writes for those rows.  Columns [K, lda) are never written and
+ * rows without entries write nothing.  No atomics, no reduction between entries: a value depends on its own entry and its
+ * row's lse alone, so it has the same bits on every call and for every split of the rows between calls.  v1 stores 16 bytes
+ * per (entry, four heads) when K % 4 == 0 and alpha is 16-byte aligned with lda % 4 == 0, single elements otherwise; v2
+ * picks its variant as mggcn_gatv2_forward_f32 does (from dh, Zs, Zd and att) and stores single elements.  alpha must not
+ * alias an input.  n_rows == 0 returns. */
+void mggcn_gat_alpha_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                         const uint32_t *indices, const float *s_dst, const float *s_src, const float *lse, uint32_t K,
+                         float slope, float *alpha, size_t lda);
+void mggcn_gatv2_alpha_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                           const uint32_t *indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                           const float *att, const float *lse, uint32_t K, uint32_t dh, float slope, float *alpha,
+                           size_t lda);
+/* cublasSasum  (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host
  * wrapper copies it back after its own sync (src/gcn.hpp:816-817). */

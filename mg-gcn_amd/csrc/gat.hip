@@ -12,7 +12,8 @@
 //   * the per-edge dot product (SDDMM) is a butterfly over the LPR lanes of a group -- log2(LPR) steps per G edges;
 //   * the sums over a row's entries fold the G groups in a fixed order at the end: no atomics anywhere, the same bits on
 //     every call.
-// No per-edge array exists: alpha is recomputed from s_dst, s_src and lse wherever it is needed.
+// No per-edge array exists: alpha is recomputed from s_dst, s_src and lse wherever it is needed.  The one exception is on
+// request: gat_alpha_kernel (mggcn_gat_alpha_f32) runs the same walk and writes alpha out for the user; nothing reads it back.
 // VEC = 4 (16-byte loads) when dh % 4 == 0 and every dense operand and leading dimension is 16-byte aligned -- a float4
 // must not straddle two heads, so K * dh % 4 == 0 alone is not enough -- and VEC = 1 otherwise.
 // Heavy rows are slow here (one wave walks a whole row, ~21 k entries on the Reddit-shaped graph) but correct: cutting
@@ -324,6 +325,47 @@ __global__ __launch_bounds__(256) void gat_pack_dst_kernel(const float *__restri
     if (ik < n) rec[ik] = make_float4(s_dst[ik], lse[ik], D[ik], 0.f);
 }
 
+// ---------------------------------------------------------------------------
+// the export: alpha[p, k] = exp(lrelu(s_dst[i, k] + s_src[j, k]) - lse[i, k]) for entry p = (i, j) of the indices array --
+// the float expression of the two backward kernels above.  The same walk, KV heads at a time: the lane that owns an entry
+// has its KV source scores from the walk and stores its KV coefficients (KV = 4: one 16-byte store).  No groups, no
+// reduction, no LDS; a value depends on its entry and its row's lse alone.
+// ---------------------------------------------------------------------------
+template <int KV>
+__global__ __launch_bounds__(256) void gat_alpha_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                        const uint32_t *__restrict__ indices,
+                                                        const float *__restrict__ s_dst, const float *__restrict__ s_src,
+                                                        const float *__restrict__ lse, uint32_t K, float slope,
+                                                        float *__restrict__ alpha, size_t lda) {
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    for (uint32_t k0 = 0; k0 < K; k0 += KV) {
+        float sd[KV], ls[KV];
+#pragma unroll
+        for (int v = 0; v < KV; v++) {
+            sd[v] = s_dst[row * K + k0 + v];
+            ls[v] = lse[row * K + k0 + v];
+        }
+        const auto fetch = [&](uint32_t c, float *s) {          // the entry's scores of heads k0 .. k0 + KV
+#pragma unroll
+            for (int v = 0; v < KV; v++) s[v] = s_src[(size_t)c * K + k0 + v];
+        };
+        entry_chunks<KV> ch;
+        ch.start(indices, beg, end, lane, fetch);
+        for (uint32_t base = beg; base < end; base += 64) {
+            ch.next(indices, base, end, lane, fetch);
+            if (lane < ch.cnt) {
+                float a[KV];
+#pragma unroll
+                for (int v = 0; v < KV; v++) a[v] = expf(gat_lrelu(sd[v] + ch.my_s[v], slope) - ls[v]);
+                storev<KV>(alpha + ((size_t)base + lane) * lda + k0, a);
+            }
+        }
+    }
+}
+
 // G_att[0, c] = sum_i ds_dst[i, k(c)] Z_dst[i, c],  G_att[1, c] = sum_j ds_src[j, k(c)] Z_src[j, c]: the term of
 // gat_column_sums, side 0 the destinations and side 1 the sources
 struct gat_scores_term {
@@ -527,6 +569,22 @@ MGGCN_API void mggcn_gat_backward_src_rec_drop_f32(mggcn_stream_t stream, uint32
     const gat_drop dp = make_gat_drop(threshold, scale, seed, dropout_stream, dst0, n_cols, src0, n_rows);
     gat_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Z, ldz, nullptr, s_src, nullptr, nullptr, rec, G, ldg, att,
                      ds_dst, K, dh, slope, ds_src, G_Z, ldgz, threshold ? &dp : nullptr);
+}
+
+// The export of the coefficients: the only GAT call that writes something of nnz x K, and nothing calls it but the user
+MGGCN_API void mggcn_gat_alpha_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                   const uint32_t *indices, const float *s_dst, const float *s_src, const float *lse,
+                                   uint32_t K, float slope, float *alpha, size_t lda) {
+    MGGCN_REQUIRE(K >= 1 && K <= MGGCN_GAT_MAX_HEADS, "gat supports 1 <= heads <= 16");
+    MGGCN_REQUIRE(lda >= K, "gat alpha: lda < heads");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && s_dst != nullptr && lse != nullptr, "gat alpha: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && s_src != nullptr && alpha != nullptr), "gat alpha: null operand");
+    MGGCN_REQUIRE(alpha != s_dst && alpha != s_src && alpha != lse, "gat alpha: alpha must not alias s_dst, s_src or lse");
+    if (K % 4 == 0 && rows16(alpha, lda))
+        launch_rows(gat_alpha_kernel<4>, n_rows, stream, n_rows, indptr, indices, s_dst, s_src, lse, K, slope, alpha, lda);
+    else
+        launch_rows(gat_alpha_kernel<1>, n_rows, stream, n_rows, indptr, indices, s_dst, s_src, lse, K, slope, alpha, lda);
 }
 
 MGGCN_API void mggcn_gat_scores_backward_f32(mggcn_stream_t stream, const float *ds_dst, const float *Z_dst, size_t ldzd,

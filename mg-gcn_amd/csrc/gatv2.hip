@@ -16,8 +16,9 @@
 //     accumulates alpha G_i + v.  lse and D of the destination are two 4-byte gathers by the lane that owns the entry
 //     (the walk's scalars; DESIGN.md 3.10.2 says why they are not packed).
 //   * att_grad: the column sums of P through gat_column_sums (gat_internal.h).
-// Nothing of nnz x K is stored, no atomics, a row's result depends on that row alone: the same bits on every call and for
-// every split of the rows between calls.
+//   * alpha (the export, on request): backward_dst cut down to its score, writing exp(e - lse) per (entry, head).
+// Nothing of nnz x K is stored (but what the export is asked to write), no atomics, a row's result depends on that row
+// alone: the same bits on every call and for every split of the rows between calls.
 #include <algorithm>
 #include <cmath>
 
@@ -251,6 +252,52 @@ __global__ __launch_bounds__(256) void gatv2_backward_src_kernel(uint32_t n_rows
     }
 }
 
+// ---------------------------------------------------------------------------
+// the export: alpha[p, k] = exp(e_ijk - lse[i, k]) for entry p = (i, j) of the indices array -- backward_dst cut down to its
+// score: the same gather of the source's head-row, the same partial products and butterfly, the same expf.  One lane of
+// the group that holds the entry stores the value; a value depends on its entry and its row's lse alone.
+// ---------------------------------------------------------------------------
+template <int VEC, int NT, int U>
+__global__ __launch_bounds__(256) void gatv2_alpha_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                          const uint32_t *__restrict__ indices,
+                                                          const float *__restrict__ Zs, size_t ldzs,
+                                                          const float *__restrict__ Zd, size_t ldzd,
+                                                          const float *__restrict__ att, const float *__restrict__ lse,
+                                                          uint32_t K, uint32_t dh, float slope, uint32_t lg,
+                                                          float *__restrict__ alpha, size_t lda) {
+    MGGCN_GAT_WAVE_ROW(n_rows);
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    for (uint32_t k = 0; k < K; k++) {
+        float zd[NT][VEC], a[NT][VEC];
+        load_head_row<VEC, NT>(zd, Zd + row * ldzd + (size_t)k * dh, lpr, sub, dh);
+        load_head_row<VEC, NT>(a, att + (size_t)k * dh, lpr, sub, dh);
+        const float ls = lse[row * K + k];
+        const float *__restrict__ Zk = Zs + (size_t)k * dh;
+        entry_chunks<0> ch;                         // the indices alone
+        ch.start(indices, beg, end, lane, no_scalars);
+        for (uint32_t base = beg; base < end; base += 64) {
+            ch.next(indices, base, end, lane, no_scalars);
+            const uint32_t cnt = ch.cnt;
+            for (uint32_t j = 0; j < cnt; j += n_grp * U) {
+                float pe[U];
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    float z[NT][VEC];
+                    load_head_row<VEC, NT>(z, Zk + (size_t)en.c * ldzs, lpr, sub, dh, en.ok);
+                    pe[u] = score_head_row<VEC, NT>(a, zd, z, slope);
+                }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const chunk_entry en = ch.pick(j, u, n_grp, grp);
+                    const float e = group_sum(pe[u], lpr);
+                    if (en.ok && sub == 0) alpha[((size_t)base + en.src) * lda + k] = expf(e - ls);
+                }
+            }
+        }
+    }
+}
+
 // G_att[0, c] = sum_i P[i, c]: the term of gat_column_sums, one side
 struct gatv2_att_term {
     const float *P;
@@ -305,6 +352,29 @@ MGGCN_API void mggcn_gatv2_backward_dst_f32(mggcn_stream_t stream, uint32_t n_ro
     gat_dispatch(vec, hg.nt, [&](auto v) {
         launch_rows(gatv2_backward_dst_kernel<v.VEC, v.NT, v.U>, n_rows, stream, n_rows, indptr, indices, Zs, ldzs, Zd, ldzd, att,
                     lse, G, ldg, out, ldo, K, dh, slope, hg.lg, D, G_Zd, ldgzd, P, ldp);
+    });
+}
+
+// The export of the coefficients: the only GATv2 call that writes something of nnz x K, and nothing calls it but the user.
+// alpha is stored element by element, so its alignment plays no part in the choice of the variant: the bits of a value do
+// not depend on where it lands.
+MGGCN_API void mggcn_gatv2_alpha_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                     const uint32_t *indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                                     const float *att, const float *lse, uint32_t K, uint32_t dh, float slope, float *alpha,
+                                     size_t lda) {
+    require_heads(K, dh);
+    const size_t width = (size_t)K * dh;
+    MGGCN_REQUIRE(ldzs >= width && ldzd >= width, "gatv2 alpha: leading dimension < heads * width per head");
+    MGGCN_REQUIRE(lda >= K, "gatv2 alpha: lda < heads");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && Zd != nullptr && att != nullptr && lse != nullptr, "gatv2 alpha: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (indices != nullptr && Zs != nullptr && alpha != nullptr), "gatv2 alpha: null operand");
+    MGGCN_REQUIRE(alpha != Zs && alpha != Zd && alpha != att && alpha != lse, "gatv2 alpha: alpha must not alias an input");
+    const bool vec = dh % 4 == 0 && rows16(Zs, ldzs) && rows16(Zd, ldzd) && aligned16(att);
+    const head_geometry hg = head_geometry_for(dh, vec);
+    gat_dispatch(vec, hg.nt, [&](auto v) {
+        launch_rows(gatv2_alpha_kernel<v.VEC, v.NT, v.U>, n_rows, stream, n_rows, indptr, indices, Zs, ldzs, Zd, ldzd, att, lse, K,
+                    dh, slope, hg.lg, alpha, lda);
     });
 }
 

@@ -22,6 +22,9 @@ ds_src and G_Z are the single-GPU rows bit for bit at any P (given the same Z an
 mask is drawn with dst0 = p_r, src0 = 0 over F and dst0 = 0, src0 = p_r over F^T.  Only sums over vertices (G_W, G_b, G_att,
 the loss sums) round differently.  A single rank exchanges nothing unless dist_context.self_gather.
 
+attention_weights / attention_pattern: a rank exports the coefficients of its rows' entries (gat.attention_weights on the
+row block; no collective of its own), the single-GPU export's rows bit for bit.
+
 Not covered: the halo and rounds schedules, bf16 on the wire, layer norm, checkpoints, the C++ host layer."""
 from __future__ import annotations
 
@@ -96,6 +99,12 @@ class dist_attention(attention):
         ops.gat_scores(ctx, self.Z_all, self.att, self.s_dst_all, self.s_src_all, self.heads, n + "0_gat-scores")
         ops.gat_forward(ctx, F, self.Z_all, self.s_dst, self.s_src_all, out, self.lse, self.heads, self.slope,
                         n + "0_gat-forward", drop)
+
+    def alpha(self, ctx: context, F: csr_matrix, Z: dn_matrix, alpha: dn_matrix) -> None:
+        """alpha [F.nnz() x heads] = the coefficients of the most recent forward over ``F``, the rank's row block: s_dst and
+        lse of the rank's rows, s_src of all vertices -- every value is the single-GPU export's, bit for bit, because the
+        scores and lse are.  No collective."""
+        ops.gat_alpha(ctx, F, self.s_dst, self.s_src_all, self.lse, alpha, self.heads, self.slope, self.name + "0_gat-alpha")
 
     def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z: dn_matrix, G: dn_matrix, out: dn_matrix,
                  G_Z: dn_matrix, drop=None) -> None:
@@ -229,6 +238,30 @@ class dist_gat(dropout_option):
 
     def layers(self) -> List[dist_gat_layer]:
         return self.layers_
+
+    _alpha_requests = gat._alpha_requests       # reads layers_ (their F) and heads: the checks that need no device
+
+    def attention_weights(self, dctx: dist_context, X: Optional[dist_row_dn_matrix] = None, layers=None,
+                          out=None) -> List[dn_matrix]:
+        """gat.attention_weights on the row partition; every rank calls it with the same arguments.  A rank gets the
+        entries of ITS rows: one [nnz of the rank's row block x heads] dn_matrix per requested layer, row p for entry p of
+        attention_pattern()'s ``indices`` -- the rows [indptr[p_r], indptr[p_{r+1}]) of the single-GPU model's export, bit
+        for bit given the same weights.  With ``X`` (a dist_row_dn_matrix) a plain forward runs first, with the collectives
+        every forward has; the export itself runs none.  Without, the state of the most recent forward is exported (after
+        attention dropout: the coefficients before the dropout factor).  ValueError before any device work or collective,
+        on every rank alike, for a layer index out of range, an ``out`` of the wrong length or shape, or no forward yet."""
+        which = self._alpha_requests(layers, out)
+        if X is not None:
+            self(dctx, X)
+        elif any(self.layers_[li].H is None for li in which):
+            raise ValueError("attention_weights: no forward has run, there are no attention coefficients yet (pass X)")
+        return [self.layers_[li].alpha(dctx.ctx, None if out is None else out[i]) for i, li in enumerate(which)]
+
+    def attention_pattern(self):
+        """(indptr, indices): the host arrays of the rank's row block of the matrix the forward walks -- row i is the
+        rank's destination p_r + i, its entries are its sources as GLOBAL vertex numbers, and row p of every matrix
+        attention_weights returns belongs to indices[p]"""
+        return self.F.indptr, self.F.indices
 
     # the model-level plumbing is dist_gcn's, word for word: it only touches what the two classes share (loss_layer, layers_
     # with lin / AHW / finish_backward / params, loss, fused, _adam, _loss_host, _out_width and the calls above)

@@ -35,6 +35,11 @@ v1 score (monotone in s_src[j]) cannot.  One GEMM forward, the linear's fused gr
 those of csrc/gatv2.hip (mggcn_gatv2_*).  The default ``variant="v1"`` is the model described above and calls exactly what
 it called before the keyword existed.  GATv2 has no attention dropout and no row-partitioned form yet (both refused).
 
+The coefficients can be written out: gat.attention_weights(ctx, X) returns one [nnz x heads] matrix per layer (PyG's
+return_attention_weights), attention_pattern() the (indptr, indices) their rows belong to; gat_layer.alpha is the layer's.
+The values are the backward kernels' own expression exp(e - lse) (mggcn_gat_alpha_f32 / mggcn_gatv2_alpha_f32); nothing is
+allocated or launched unless one of these is called.
+
 Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, checkpoints, layer norm, bf16 gathers.
 """
 from __future__ import annotations
@@ -99,6 +104,11 @@ class attention:
                              G_Z, self.heads, self.slope, n + "1_gat-backward-src", drop)
         ops.gat_scores_backward(ctx, self.ds_dst, Z, self.ds_src, Z, self.G_att, self.heads, n + "1_gat-scores-backward")
 
+    def alpha(self, ctx: context, F: csr_matrix, Z: dn_matrix, alpha: dn_matrix) -> None:
+        """alpha [F.nnz() x heads] = the coefficients of the most recent forward over ``F``, from its s_dst, s_src and lse
+        (Z is not read: the scores hold all of it that the coefficients need)"""
+        ops.gat_alpha(ctx, F, self.s_dst, self.s_src, self.lse, alpha, self.heads, self.slope, self.name + "0_gat-alpha")
+
     def init(self, att) -> None:
         self.att.init(np.asarray(att, dtype=np.float32))
 
@@ -145,6 +155,10 @@ class attention_v2(attention):
         """out = the attention-weighted gather of Zs over F's rows, scored against Zd"""
         assert drop is None, "GATv2 has no attention dropout"
         ops.gatv2_forward(ctx, F, Z2, Z2, self.att, out, self.lse, self.heads, self.slope, self.name + "0_gatv2-forward")
+
+    def alpha(self, ctx: context, F: csr_matrix, Z2: dn_matrix, alpha: dn_matrix) -> None:
+        """alpha [F.nnz() x heads] = the coefficients of the most recent forward over ``F``, from its Z2, att and lse"""
+        ops.gatv2_alpha(ctx, F, Z2, Z2, self.att, self.lse, alpha, self.heads, self.slope, self.name + "0_gatv2-alpha")
 
     def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z2: dn_matrix, G: dn_matrix, out: dn_matrix,
                  G_Z2: dn_matrix, drop=None) -> None:
@@ -235,6 +249,21 @@ class gat_layer:
         if self.dropout is not None and self.G_out is not None:
             self._drop(ctx, self.G_out, "1")
         return self.G_out
+
+    def alpha(self, ctx: context, out: Optional[dn_matrix] = None) -> dn_matrix:
+        """The attention coefficients of this layer's most recent forward: [F.nnz() x heads], row p for entry p of F's
+        indices array (row i of F lists the sources of destination i), column k for head k.  ``out``: where to put them
+        (None allocates).  After a training forward with attention dropout these are the normalised coefficients BEFORE
+        the dropout factor.  ValueError when no forward has run, or for an ``out`` of another shape."""
+        if self.H is None:
+            raise ValueError(f"gat layer {self.name}: no forward has run, there are no attention coefficients yet")
+        shape = (self.F.nnz(), self.attn.heads)
+        if out is None:
+            out = dn_matrix(*shape, device=self.Z.t.device)
+        elif out.shape() != shape:
+            raise ValueError(f"gat layer {self.name}: out must be {shape[0]} x {shape[1]} (entries x heads), got {out.shape()}")
+        self.attn.alpha(ctx, self.F, self.Z, out)
+        return out
 
     def linears(self):
         return [self.lin]
@@ -387,6 +416,49 @@ class gat(dropout_option):
 
     def layers(self) -> List[gat_layer]:
         return self.layers_
+
+    def _alpha_requests(self, layers, out) -> List[int]:
+        """the layer indices ``layers=`` names, after every check attention_weights can make without the device"""
+        n_layers = len(self.layers_)
+        which = list(range(n_layers)) if layers is None else [int(li) for li in layers]
+        for li in which:
+            if not 0 <= li < n_layers:
+                raise ValueError(f"attention_weights: layer {li} is out of range, the model has {n_layers} layers")
+        if out is not None:
+            if len(out) != len(which):
+                raise ValueError(f"attention_weights: out lists {len(out)} matrices for {len(which)} layers")
+            for li, o in zip(which, out):
+                want = (self.layers_[li].F.nnz(), self.heads[li])
+                if o.shape() != want:
+                    raise ValueError(f"attention_weights: out of layer {li} must be {want[0]} x {want[1]}, got {o.shape()}")
+        return which
+
+    def attention_weights(self, ctx, X=None, layers=None, out=None) -> List[dn_matrix]:
+        """The attention coefficients alpha_ijk per layer (PyG's return_attention_weights): a list with one [nnz x heads]
+        dn_matrix per requested layer, whose row p belongs to entry p of attention_pattern()'s ``indices`` and whose
+        column k to head k.  With ``X`` a plain forward runs first (self(ctx, X), the forward that never drops); without,
+        the export is taken from the state the most recent forward left behind -- ValueError when there was none.  After
+        a training forward with attention dropout that state is the normalised coefficient BEFORE the dropout factor q:
+        the softmax runs over all entries there too, so the export is what a plain forward of the same weights and
+        inputs gives, not alpha q.  ``layers``: None for all, or layer indices, returned in the order given; ``out``: one
+        dn_matrix per requested layer to write into (None allocates).  ValueError before any device work for an index
+        out of range and for an ``out`` of the wrong length or shape.
+
+        The values are exp(e_ijk - lse[i, k]) as the backward kernels evaluate it (mggcn_gat_alpha_f32 /
+        mggcn_gatv2_alpha_f32): the coefficients the model trains with, the same bits on every call.  This is the one place
+        where something of nnz x heads is stored: the Reddit-shaped graph (114.8 M entries) at 4 heads needs 1.84 GB per
+        layer.  Nothing is allocated or launched unless this method (or gat_layer.alpha) is called."""
+        which = self._alpha_requests(layers, out)
+        if X is not None:
+            self(ctx, X)
+        elif any(self.layers_[li].H is None for li in which):
+            raise ValueError("attention_weights: no forward has run, there are no attention coefficients yet (pass X)")
+        return [self.layers_[li].alpha(ctx, None if out is None else out[i]) for i, li in enumerate(which)]
+
+    def attention_pattern(self):
+        """(indptr, indices): the host arrays of the matrix the forward walks, A.transpose() -- row i is a destination, its
+        entries are its sources, and row p of every matrix attention_weights returns belongs to indices[p]"""
+        return self.A_T.indptr, self.A_T.indices
 
     # the model-level plumbing is gcn's, word for word: it only touches what the two classes share (loss_layer, layers_,
     # loss, A, _out_width and the calls above)

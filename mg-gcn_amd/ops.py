@@ -583,6 +583,30 @@ def gat_scores_backward(ctx: context, ds_dst: dn_matrix, Z_dst: dn_matrix, ds_sr
         Z_src.n(), heads, Z_src.m() // heads, G_att.buffer()))
 
 
+def _req_gat_alpha(F, lse, alpha, heads: int, what: str) -> None:
+    """the output of the two exports: one row per entry of F, one column per head; lse one row per destination"""
+    _req(alpha.shape() == (F.nnz(), heads), f"{what}: alpha must be {F.nnz()} x {heads} (entries x heads)")
+    _req(lse.shape() == (F.n(), heads), f"{what}: lse must be rows x heads")
+
+
+def gat_alpha(ctx: context, F: csr_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix, alpha: dn_matrix, heads: int,
+              slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """The attention coefficients of a forward, written out (mggcn_gat_alpha_f32): alpha[p, k] = exp(lrelu(s_dst[i, k] +
+    s_src[j, k]) - lse[i, k]) for entry p = (i, j) of F's indices array -- the expression gat_backward_dst and
+    gat_backward_src evaluate, from what gat_scores and gat_forward left behind.  ``alpha``: [F.nnz() x heads], row p
+    belongs to F's entry p.  The only GAT call that writes something of entries x heads; no training call reads it."""
+    _req(isinstance(heads, numbers.Integral) and 1 <= heads <= GAT_MAX_HEADS,
+         f"gat alpha supports 1 <= heads <= {GAT_MAX_HEADS}, got {heads!r}")
+    _req(s_dst.shape() == (F.n(), heads) and s_src.shape() == (F.m(), heads), "gat alpha: the scores must be rows x heads")
+    _req_gat_alpha(F, lse, alpha, heads, "gat alpha")
+    if not F.nnz():
+        return
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_alpha_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), s_dst.buffer(), s_src.buffer(), lse.buffer(), heads, slope,
+        alpha.buffer(), alpha.m()))
+
+
 def _gatv2_half(M: dn_matrix, width: int, half: int, what: str):
     """(pointer, leading dimension) of a dense operand of the GATv2 calls: ``M`` is either the [rows x width] matrix itself
     or the model's [rows x 2 width] buffer, whose columns [0, width) are the source half (half 0: Zs, G_Zs) and
@@ -612,6 +636,24 @@ def gatv2_forward(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_forward_f32(
         ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), heads, width // heads,
         slope, out.buffer(), out.m(), lse.buffer()))
+
+
+def gatv2_alpha(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, lse: dn_matrix, alpha: dn_matrix,
+                heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """The GATv2 attention coefficients of a forward, written out (mggcn_gatv2_alpha_f32): alpha[p, k] = exp(e_ijk -
+    lse[i, k]) for entry p = (i, j) of F's indices array, e recomputed from the gathered head-row as gatv2_backward_dst
+    does, lse from gatv2_forward.  Zs, Zd as gatv2_forward takes them; ``alpha``: [F.nnz() x heads], row p belongs to F's
+    entry p.  The only GATv2 call that writes something of entries x heads; no training call reads it."""
+    width = _gatv2_width(att, heads, "gatv2 alpha")
+    _req(F.m() == Zs.n() and F.n() == Zd.n(), "gatv2 alpha: shape mismatch")
+    _req_gat_alpha(F, lse, alpha, heads, "gatv2 alpha")
+    (zs, ldzs), (zd, ldzd) = _gatv2_half(Zs, width, 0, "gatv2 alpha"), _gatv2_half(Zd, width, 1, "gatv2 alpha")
+    if not F.nnz():
+        return
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_alpha_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), lse.buffer(), heads,
+        width // heads, slope, alpha.buffer(), alpha.m()))
 
 
 def gatv2_backward_dst(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, lse: dn_matrix,

@@ -72,6 +72,7 @@ def run_v1(tag, F, F_T, n, n_src, K, dh, off):
         ops.gat_backward_src(ctx, F_T, Z, s_dst, s_src, lse, D, G, att, dd, ds_src, G_Z, K, drop=drop)
         report("gat_backward_src" + sfx, tag, ds_src=ds_src, G_Z=G_Z)
         rec = torch.zeros(n * K * 4, dtype=torch.float32, device=ctx.device)
+        torch.cuda.synchronize()            # the fill runs on torch's stream, the pack on the context's
         ops.gat_pack_dst(ctx, s_dst, lse, D, rec)
         report("gat_pack_dst" + sfx, tag, rec=rec)
         ds_src_r, G_Z_r = dense((n_src, K)), dense((n_src, d), off)
