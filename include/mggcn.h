@@ -470,6 +470,21 @@ void mggcn_gatv2_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32
                                   const uint32_t *t_indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
                                   const float *att, const float *lse, const float *D, const float *G, size_t ldg,
                                   uint32_t K, uint32_t dh, float slope, float *G_Zs, size_t ldgzs);
+/* The packed destination record of the GATv2 backward_src (opt-in).  mggcn_gatv2_pack_dst_f32 writes, per destination i and
+ * head k,
+ *   rec[(i K + k) 2 + {0, 1}] = lse[i, k], D[i, k]
+ * from the two contiguous [n_rows x K] arrays (bit patterns are copied as they are); rec holds n_rows K 2 floats and must be
+ * 8-byte aligned; n_rows == 0 returns.  mggcn_gatv2_backward_src_rec_f32 takes the operands of mggcn_gatv2_backward_src_f32
+ * with rec in the place of lse and D ([n_cols x K] records, 8-byte aligned): the lane that owns an entry issues one 8-byte
+ * load where the plain kernel gathers two 4-byte scalars, one chunk ahead as there, and the arithmetic and the choice of the
+ * variant are the plain kernel's -- G_Zs is bit for bit that of the plain call on the arrays the record was packed from, and
+ * a row range passed as a call of its own gives the whole call's rows.  On a row partition the record is what a rank needs
+ * of every other rank's destinations: one collective of 8 K bytes per vertex. */
+void mggcn_gatv2_pack_dst_f32(mggcn_stream_t stream, const float *lse, const float *D, size_t n_rows, uint32_t K, float *rec);
+void mggcn_gatv2_backward_src_rec_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                      const uint32_t *t_indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                                      const float *att, const float *rec, const float *G, size_t ldg, uint32_t K,
+                                      uint32_t dh, float slope, float *G_Zs, size_t ldgzs);
 /* The export of the attention coefficients (opt-in: the one place where something of nnz x K is written, and no training
  * call reads it).  Both take F as the calls above and the state a forward left behind -- s_dst, s_src, lse of
  * mggcn_gat_scores_f32 / mggcn_gat_forward_f32, or Zs, Zd, att, lse of mggcn_gatv2_forward_f32 -- and write, for entry p of

@@ -123,7 +123,10 @@ PROTOTYPES = {
     "mggcn_gatv2_att_grad_f32": (None, [vp, vp, c_size_t, c_size_t, c_uint32, vp]),
     "mggcn_gatv2_backward_src_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, vp, vp, vp, vp,
                                             c_size_t, c_uint32, c_uint32, c_float, vp, c_size_t]),
-    "mggcn_gat_alpha_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, vp, vp, c_uint32, c_float, vp, c_size_t]),
+    "mggcn_gatv2_pack_dst_f32": (None, [vp, vp, vp, c_size_t, c_uint32, vp]),
+    "mggcn_gatv2_backward_src_rec_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, vp, vp, vp,
+                                                c_size_t, c_uint32, c_uint32, c_float, vp, c_size_t]),
+    "mggcn_gat_alpha_f32": (None,[vp, c_uint32, c_uint32, vp, vp, vp, vp, vp, c_uint32, c_float, vp, c_size_t]),
     "mggcn_gatv2_alpha_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, vp, vp, c_uint32, c_uint32,
                                      c_float, vp, c_size_t]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),

@@ -14,7 +14,8 @@
 //     butterflies over the same gathered row.
 //   * backward_src (rows of F^T): gathers the destination's head-rows of Zd and G, recomputes e, dalpha, alpha and ds, and
 //     accumulates alpha G_i + v.  lse and D of the destination are two 4-byte gathers by the lane that owns the entry
-//     (the walk's scalars; DESIGN.md 3.10.2 says why they are not packed).
+//     (the walk's scalars), or, in the REC form, one 8-byte load of the packed (lse, D) record that pack_dst writes: what
+//     the row-partitioned model gathers from the other ranks in one collective.
 //   * att_grad: the column sums of P through gat_column_sums (gat_internal.h).
 //   * alpha (the export, on request): backward_dst cut down to its score, writing exp(e - lse) per (entry, head).
 // Nothing of nnz x K is stored (but what the export is asked to write), no atomics, a row's result depends on that row
@@ -191,14 +192,16 @@ __global__ __launch_bounds__(256) void gatv2_backward_dst_kernel(uint32_t n_rows
 // backward over the rows of F^T (row j lists the destinations i that gather j):
 //   G_Zs[j, k dh + c] = sum_i (alpha_ijk G[i, k dh + c] + ds_ijk att[k dh + c] lrelu'(t_ijk[c]))
 // ---------------------------------------------------------------------------
-template <int VEC, int NT, int U>
+// REC: lse and D are not read; the two scalars of destination i and head k come from rec + (i K + k) 2
+template <int VEC, int NT, int U, bool REC>
 __global__ __launch_bounds__(256) void gatv2_backward_src_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
                                                                  const uint32_t *__restrict__ indices,
                                                                  const float *__restrict__ Zs, size_t ldzs,
                                                                  const float *__restrict__ Zd, size_t ldzd,
                                                                  const float *__restrict__ att, const float *__restrict__ lse,
-                                                                 const float *__restrict__ D, const float *__restrict__ G,
-                                                                 size_t ldg, uint32_t K, uint32_t dh, float slope, uint32_t lg,
+                                                                 const float *__restrict__ D, const float *__restrict__ rec,
+                                                                 const float *__restrict__ G, size_t ldg, uint32_t K,
+                                                                 uint32_t dh, float slope, uint32_t lg,
                                                                  float *__restrict__ G_Zs, size_t ldgzs) {
     MGGCN_GAT_WAVE_ROW(n_rows);
     const uint32_t beg = indptr[row], end = indptr[row + 1];
@@ -211,8 +214,13 @@ __global__ __launch_bounds__(256) void gatv2_backward_src_kernel(uint32_t n_rows
         const float *__restrict__ Zdk = Zd + (size_t)k * dh;
         const float *__restrict__ Gk = G + (size_t)k * dh;
         const auto fetch = [&](uint32_t c, float *s) {          // lse and D of the entry's destination
-            s[0] = lse[(size_t)c * K + k];
-            s[1] = D[(size_t)c * K + k];
+            const size_t ik = (size_t)c * K + k;
+            if constexpr (REC) {
+                const float2 t = *reinterpret_cast<const float2 *>(rec + ik * 2);
+                s[0] = t.x; s[1] = t.y;
+            } else {
+                s[0] = lse[ik]; s[1] = D[ik];
+            }
         };
         entry_chunks<2> ch;
         ch.start(indices, beg, end, lane, fetch);
@@ -250,6 +258,15 @@ __global__ __launch_bounds__(256) void gatv2_backward_src_kernel(uint32_t n_rows
         }
         fold_store_head_row<VEC, NT>(G_Zs + row * ldgzs + (size_t)k * dh, acc, lpr, sub, grp, dh);
     }
+}
+
+// ---------------------------------------------------------------------------
+// rec[(i K + k) 2 + {0, 1}] = lse[i, k], D[i, k]: one thread per (destination, head), one 8-byte store
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void gatv2_pack_dst_kernel(const float *__restrict__ lse, const float *__restrict__ D,
+                                                             size_t n, float2 *__restrict__ rec) {
+    const size_t ik = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (ik < n) rec[ik] = make_float2(lse[ik], D[ik]);
 }
 
 // ---------------------------------------------------------------------------
@@ -387,23 +404,63 @@ MGGCN_API void mggcn_gatv2_att_grad_f32(mggcn_stream_t stream, const float *P, s
     gat_column_sums<1>(stream, gatv2_att_term{P, ldp, n_rows}, n_rows, width, G_att);
 }
 
-MGGCN_API void mggcn_gatv2_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
-                                            const uint32_t *t_indices, const float *Zs, size_t ldzs, const float *Zd,
-                                            size_t ldzd, const float *att, const float *lse, const float *D, const float *G,
-                                            size_t ldg, uint32_t K, uint32_t dh, float slope, float *G_Zs, size_t ldgzs) {
+// The body of backward_src and of its record form: rec != nullptr launches the REC = true kernels, which read it in place of
+// lse and D (both nullptr then).  Internal linkage.
+namespace {
+void gatv2_backward_src(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                        const uint32_t *t_indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd, const float *att,
+                        const float *lse, const float *D, const float *rec, const float *G, size_t ldg, uint32_t K, uint32_t dh,
+                        float slope, float *G_Zs, size_t ldgzs) {
     require_heads(K, dh);
     const size_t width = (size_t)K * dh;
     MGGCN_REQUIRE(ldzs >= width && ldzd >= width && ldg >= width && ldgzs >= width,
                   "gatv2 backward: leading dimension < heads * width per head");
     if (!n_rows) return;
     MGGCN_REQUIRE(t_indptr != nullptr && Zs != nullptr && att != nullptr && G_Zs != nullptr, "gatv2 backward: null operand");
-    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && Zd != nullptr && G != nullptr && lse != nullptr && D != nullptr),
+    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && Zd != nullptr && G != nullptr &&
+                                  (rec != nullptr || (lse != nullptr && D != nullptr))),
                   "gatv2 backward: null operand");
     MGGCN_REQUIRE(G_Zs != G && G_Zs != Zs && G_Zs != Zd, "gatv2 backward: G_Zs must not alias G, Zs or Zd");
     const bool vec = dh % 4 == 0 && rows16(Zs, ldzs) && rows16(Zd, ldzd) && rows16(G, ldg) && rows16(G_Zs, ldgzs) && aligned16(att);
     const head_geometry hg = head_geometry_for(dh, vec);
     gat_dispatch(vec, hg.nt, [&](auto v) {
-        launch_rows(gatv2_backward_src_kernel<v.VEC, v.NT, v.U>, n_rows, stream, n_rows, t_indptr, t_indices, Zs, ldzs, Zd, ldzd,
-                    att, lse, D, G, ldg, K, dh, slope, hg.lg, G_Zs, ldgzs);
+        with_flag(rec != nullptr, [&](auto packed) {
+            launch_rows(gatv2_backward_src_kernel<v.VEC, v.NT, v.U, packed>, n_rows, stream, n_rows, t_indptr, t_indices, Zs, ldzs,
+                        Zd, ldzd, att, lse, D, rec, G, ldg, K, dh, slope, hg.lg, G_Zs, ldgzs);
+        });
     });
+}
+}  // namespace
+
+MGGCN_API void mggcn_gatv2_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                            const uint32_t *t_indices, const float *Zs, size_t ldzs, const float *Zd,
+                                            size_t ldzd, const float *att, const float *lse, const float *D, const float *G,
+                                            size_t ldg, uint32_t K, uint32_t dh, float slope, float *G_Zs, size_t ldgzs) {
+    gatv2_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Zs, ldzs, Zd, ldzd, att, lse, D, nullptr, G, ldg, K, dh, slope,
+                       G_Zs, ldgzs);
+}
+
+// The packed destination record: rec[(i K + k) 2 + {0, 1}] = lse[i, k], D[i, k]
+MGGCN_API void mggcn_gatv2_pack_dst_f32(mggcn_stream_t stream, const float *lse, const float *D, size_t n_rows, uint32_t K,
+                                        float *rec) {
+    MGGCN_REQUIRE(K >= 1 && K <= MGGCN_GAT_MAX_HEADS, "gat supports 1 <= heads <= 16");
+    MGGCN_REQUIRE(n_rows <= 0xFFFFFFFFu, "gatv2 pack: more than 2^32 - 1 rows");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(lse != nullptr && D != nullptr && rec != nullptr, "gatv2 pack: null operand");
+    MGGCN_REQUIRE(((uintptr_t)rec & 7) == 0, "gatv2 pack: rec must be 8-byte aligned");
+    const size_t n = n_rows * K;
+    hipLaunchKernelGGL(gatv2_pack_dst_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, as_stream(stream), lse, D, n,
+                       reinterpret_cast<float2 *>(rec));
+    MGGCN_CHECK_LAUNCH();
+}
+
+// backward_src on the record: rec in the place of lse and D; the bits of the plain call on the arrays it was packed from
+MGGCN_API void mggcn_gatv2_backward_src_rec_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols,
+                                                const uint32_t *t_indptr, const uint32_t *t_indices, const float *Zs,
+                                                size_t ldzs, const float *Zd, size_t ldzd, const float *att, const float *rec,
+                                                const float *G, size_t ldg, uint32_t K, uint32_t dh, float slope, float *G_Zs,
+                                                size_t ldgzs) {
+    MGGCN_REQUIRE(!n_rows || !n_cols || (rec != nullptr && ((uintptr_t)rec & 7) == 0), "gatv2 backward: rec must be 8-byte aligned");
+    gatv2_backward_src(stream, n_rows, n_cols, t_indptr, t_indices, Zs, ldzs, Zd, ldzd, att, nullptr, nullptr, rec, G, ldg, K, dh,
+                       slope, G_Zs, ldgzs);
 }

@@ -1165,4 +1165,5 @@ class dist_gcn(dropout_option, checkpoint_option):
     def layers(self): return self.layers_
 
 
-from .dist_gat import dist_attention, dist_gat, dist_gat_layer      # noqa: E402,F401  (it imports the classes above)
+from .dist_gat import (dist_attention, dist_attention_v2, dist_gat, dist_gat_layer,       # noqa: E402,F401
+                       dist_gatv2_layer)                                                # noqa: E402,F401  (it imports the classes above)

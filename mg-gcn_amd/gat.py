@@ -33,7 +33,8 @@ The row-partitioned form is dist_gat.dist_gat (one process per GPU; DESIGN.md 3.
 The non-linearity sits inside the dot product, so a destination can rank its sources in an order of its own, which the
 v1 score (monotone in s_src[j]) cannot.  One GEMM forward, the linear's fused gradient GEMMs backward; the kernels are
 those of csrc/gatv2.hip (mggcn_gatv2_*).  The default ``variant="v1"`` is the model described above and calls exactly what
-it called before the keyword existed.  GATv2 has no attention dropout and no row-partitioned form yet (both refused).
+it called before the keyword existed.  GATv2 has no attention dropout (refused); its
+row-partitioned form is dist_gat.dist_gat(variant="v2").
 
 The coefficients can be written out: gat.attention_weights(ctx, X) returns one [nnz x heads] matrix per layer (PyG's
 return_attention_weights), attention_pattern() the (indptr, indices) their rows belong to; gat_layer.alpha is the layer's.
@@ -382,7 +383,7 @@ class gat(dropout_option):
         anything is stored."""
         attn = self.attn_dropout_p if attn is None else attn
         attn_params = check_dropout(attn, self._dropout_layers)
-        check_variant(getattr(self, "variant", "v1"), float(attn))   # dist_gat borrows this method and is always v1
+        check_variant(getattr(self, "variant", "v1"), float(attn))   # dist_gat borrows this method
         dropout_option.set_dropout(self, p, seed, epoch)
         self._attn_dropout_params, self.attn_dropout_p = attn_params, float(attn)
 

@@ -706,6 +706,42 @@ def gatv2_backward_src(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_matr
         D.buffer(), G.buffer(), G.m(), heads, width // heads, slope, gzs, ldgzs))
 
 
+def _req_gatv2_rec(rec, rows: int, heads: int, what: str) -> None:
+    """``rec``: a float32 device tensor of rows x heads x 2 floats, contiguous and 8-byte aligned (the library would exit)"""
+    _req(rec.is_contiguous() and rec.numel() == rows * heads * 2 and rec.element_size() == 4 and rec.is_floating_point(),
+         f"{what}: rec must hold {rows} x {heads} records of 2 floats")
+    _req(rec.data_ptr() % 8 == 0, f"{what}: rec must be 8-byte aligned")
+
+
+def gatv2_pack_dst(ctx: context, lse: dn_matrix, D: dn_matrix, rec, timer: Optional[str] = None) -> None:
+    """rec[(i K + k) 2 + {0, 1}] = lse[i, k], D[i, k] (mggcn_gatv2_pack_dst_f32): the two scalars gatv2_backward_src needs of
+    a destination as one 8-byte record.  ``rec``: a float32 device tensor of rows x heads x 2."""
+    rows, heads = lse.shape()
+    _req(1 <= heads <= GAT_MAX_HEADS, f"gatv2 pack supports 1 <= heads <= {GAT_MAX_HEADS}")
+    _req(D.shape() == (rows, heads), "gatv2 pack: lse and D must have one shape")
+    _req_gatv2_rec(rec, rows, heads, "gatv2 pack")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_pack_dst_f32(ctx.stream(0), lse.buffer(), D.buffer(), rows, heads,
+                                                                    rec.data_ptr()))
+
+
+def gatv2_backward_src_rec(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, rec, G: dn_matrix,
+                           G_Zs: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """gatv2_backward_src with the destinations' (lse, D) as the records of gatv2_pack_dst (mggcn_gatv2_backward_src_rec_f32):
+    one 8-byte load per (entry, head) where the plain call gathers two scalars, and the bits of the plain call on the arrays
+    the record was packed from.  ``rec``: F_T.m() x heads x 2 floats; everything else as gatv2_backward_src takes it."""
+    what = "gatv2 backward"
+    width = _gatv2_width(att, heads, what)
+    _req(F_T.n() == Zs.n() and F_T.m() == Zd.n() and G.shape() == (F_T.m(), width) and G_Zs.n() == F_T.n(),
+         f"{what}: shape mismatch")
+    _req_gatv2_rec(rec, F_T.m(), heads, what)
+    (zs, ldzs), (zd, ldzd), (gzs, ldgzs) = (_gatv2_half(Zs, width, 0, what), _gatv2_half(Zd, width, 1, what),
+                                            _gatv2_half(G_Zs, width, 0, what))
+    ip, ix, _ = F_T.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_backward_src_rec_f32(
+        ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), rec.data_ptr(),
+        G.buffer(), G.m(), heads, width // heads, slope, gzs, ldgzs))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
