@@ -441,7 +441,7 @@ void mggcn_gat_backward_src_rec_drop_f32(mggcn_stream_t stream, uint32_t n_rows,
  *   backward_dst  over the rows of F:  D[i, k] = sum_c G[i, k dh + c] out[i, k dh + c];
  *                 ds_ijk = alpha_ijk (sum_c G[i, k dh + c] Zs[j, k dh + c] - D[i, k]);
  *                 G_Zd[i, k dh + c] = att[k dh + c] sum_j ds_ijk lrelu'(t_ijk[c]);  P[i, k dh + c] = sum_j ds_ijk u_ijk[c]
- *                 (row i's share of G_att; a row without entries gets zeros in both)
+ *                 (row i's share of G_att; a row without entries gets +0.0 in both, whatever the sign of att)
  *   att_grad      G_att[c] = sum_i P[i, c] over n_rows rows of `width` columns (1 <= width <= MGGCN_GAT_MAX_WIDTH);
  *                 n_rows == 0 writes zeros
  *   backward_src  over the rows of F^T (n_rows sources x n_cols destinations; call it after backward_dst, whose D it reads):

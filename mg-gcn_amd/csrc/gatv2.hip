@@ -182,8 +182,10 @@ __global__ __launch_bounds__(256) void gatv2_backward_dst_kernel(uint32_t n_rows
             }
         }
         if (lane == 0) D[row * K + k] = Dk;
+        // the product rounded once, as x * att is, but + 0.0 on top: a row without entries (x = +0.0) gets +0.0 under a
+        // negative att too, where the bare product is -0.0
         fold_store_head_row<VEC, NT>(G_Zd + row * ldgzd + (size_t)k * dh, accv, lpr, sub, grp, dh,
-                                     [&](int t, int v, float x) { return x * a[t][v]; });
+                                     [&](int t, int v, float x) { return fmaf(x, a[t][v], 0.f); });
         fold_store_head_row<VEC, NT>(P + row * ldp + (size_t)k * dh, accp, lpr, sub, grp, dh);
     }
 }

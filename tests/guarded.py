@@ -1,5 +1,7 @@
-"""Guarded device views for the layout tests (test_gpu_layouts.py): a rows x cols matrix with leading dimension `ld`
-placed at element offset `off` inside one flat device buffer, with at least one guard row in front and one behind.
+"""Guarded device views for the layout tests (test_gpu_layouts.py, test_gpu_gat_layouts.py): a rows x cols matrix with
+leading dimension `ld` placed at element offset `off` inside one flat device buffer, with at least one guard row in front
+and one behind (`tail_rows`: that many behind, so that a kernel that walks the matrix with another operand's leading
+dimension still lands inside the allocation; `host`: the same buffer in host memory only, for the CPU model of the checks).
 Every element outside the logical matrix holds a fixed NaN bit pattern -- a different one for inputs and for outputs --
 so that a kernel that stores into a pad, or lets an input pad reach a stored result, is caught bit for bit."""
 import numpy as np
@@ -18,7 +20,7 @@ class Guarded:
     """`logical`: float32 values (fp32) or uint16 bit patterns (bf16) of the matrix; None leaves the logical elements
     at the fill pattern too (an output that must be written, or a NaN-filled C that beta = 0 must never read)."""
 
-    def __init__(self, rows, cols, ld, off=0, logical=None, output=False, bf16=False):
+    def __init__(self, rows, cols, ld, off=0, logical=None, output=False, bf16=False, tail_rows=None, host=False):
         assert ld >= cols and off >= 0
         self.rows, self.cols, self.ld, self.off, self.bf16 = rows, cols, ld, off, bf16
         self.bits_dtype = np.uint16 if bf16 else np.uint32
@@ -28,7 +30,9 @@ class Guarded:
         # 256-byte (fp32) / 128-byte (bf16) boundary of the allocation (torch aligns allocations to at least that)
         self.head = -(-max(ld, 1) // 64) * 64
         self.start = self.head + off
-        total = self.start + rows * ld + self.head
+        # the guard behind: the front guard's size, or tail_rows rows where that is more
+        self.tail = self.head if tail_rows is None else max(self.head, tail_rows * ld)
+        total = self.start + rows * ld + self.tail
         self.init = np.full(total, fill, dtype=self.bits_dtype)
         self.mask = np.zeros(total, dtype=bool)
         self._window(self.mask)[:] = True
@@ -36,6 +40,9 @@ class Guarded:
             src = np.asarray(logical)
             assert src.shape == (rows, cols), (src.shape, rows, cols)
             self._window(self.init)[:] = src.view(self.bits_dtype) if src.dtype != self.bits_dtype else src
+        if host:
+            self.t, self.host = None, self.init.copy()
+            return
         torch = _torch()
         self.t = torch.from_numpy(self.init.view(np.int16 if bf16 else np.int32).copy()).cuda()
 
@@ -48,6 +55,8 @@ class Guarded:
         return self.t.data_ptr() + self.start * self.itemsize
 
     def bits(self) -> np.ndarray:
+        if self.t is None:
+            return self.host
         return self.t.cpu().numpy().view(self.bits_dtype)
 
     def logical_bits(self, bits=None) -> np.ndarray:
