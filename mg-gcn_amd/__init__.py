@@ -15,7 +15,7 @@ Layout:
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*)
   dist_gat.py  dist_attention / dist_gat_layer / dist_gat (and the _v2 / gatv2 twins): gat on the row partition (exported by dist)
   datasets.py  on-disk format + synthetic generators    (reference test/data/prep.py); the checkpoint file
-  checkpoint.py  save / load / predict of gcn and dist_gcn (no reference counterpart)
+  checkpoint.py  save / load / predict of gcn, dist_gcn, gat and dist_gat (no reference counterpart)
   selection.py   model_selector: best epoch on a split, early stopping
 """
 from . import _lib, datasets                                   # noqa: F401

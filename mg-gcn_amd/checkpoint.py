@@ -1,10 +1,12 @@
-"""save / load / predict of gcn and dist.dist_gcn (opt-in; the reference writes nothing to disk).
+"""save / load / predict of gcn, dist.dist_gcn, gat.gat and dist_gat.dist_gat (opt-in; the reference writes nothing to disk).
 
 The file is the one of datasets.write_checkpoint (INTEGRATION.md "Checkpoint file"): the model's configuration, every
 parameter tensor, optionally Adam's moments and step count, and the dropout state (p, seed, epoch).  Execution options
 (fused, agg_dtype, hoisting, the exchange schedule, P) are not model state and are not stored: weights are replicated and
 the dropout masks are counter-based on (seed, epoch, global row, column), so a file written by one form loads into any
-other and a resumed run draws the masks the uninterrupted run would have drawn.
+other and a resumed run draws the masks the uninterrupted run would have drawn.  The attention models store their layer
+type with it (model, variant, heads, attn_slope, the attention dropout probability: version 3 of the file) and per layer
+W, b and att; their two masks are counter-based on (seed, epoch * 64 + layer, ...), so the same holds for them.
 
 Nothing here launches a new kernel: the tensors move through dn_matrix.init (host to device, in place), dn_matrix.zero and
 dn_matrix.copy_to.  A model that never calls these members runs exactly what it ran before.
@@ -26,19 +28,23 @@ def raw_context(ctx):
 
 def model_params(model) -> List[tuple]:
     """[(name, owner, parameter attribute, m attribute, v attribute)] in file order (datasets.checkpoint_tensors); the
-    owner is the linear or layer_norm that holds the tensor, its Adam moments and its step count"""
+    owner is the linear, attention or layer_norm that holds the tensor, its Adam moments and its step count.  A layer is
+    read generically: ``lin``, then ``attn`` (a GAT layer), ``res_lin`` and ``norm`` where it has one."""
     out = []
     for l, layer in enumerate(model.layers_):
         out += [(f"W{l}", layer.lin, "W", "mW", "vW"), (f"b{l}", layer.lin, "b", "mb", "vb")]
-        if layer.res_lin is not None:
-            out += [(f"res_W{l}", layer.res_lin, "W", "mW", "vW"), (f"res_b{l}", layer.res_lin, "b", "mb", "vb")]
-        if layer.norm is not None:
-            out += [(f"gamma{l}", layer.norm, "gamma", "mg", "vg"), (f"beta{l}", layer.norm, "beta", "mb", "vb")]
+        attn, res_lin, norm = (getattr(layer, a, None) for a in ("attn", "res_lin", "norm"))
+        if attn is not None:
+            out += [(f"att{l}", attn, "att", "m", "v")]
+        if res_lin is not None:
+            out += [(f"res_W{l}", res_lin, "W", "mW", "vW"), (f"res_b{l}", res_lin, "b", "mb", "vb")]
+        if norm is not None:
+            out += [(f"gamma{l}", norm, "gamma", "mg", "vg"), (f"beta{l}", norm, "beta", "mb", "vb")]
     return out
 
 
 def model_owners(model) -> list:
-    """every linear and layer_norm of the model: what carries Adam state"""
+    """every linear, attention and layer_norm of the model: what carries Adam state"""
     return [p for layer in model.layers_ for p in layer.params()]
 
 
@@ -54,21 +60,29 @@ def reset_adam(model, ctx) -> None:
 
 
 def config_mismatch(file_cfg: dict, model_cfg: dict):
-    """the first differing field as "<field>: file <x>, model <y>", or None"""
-    for key in ("sizes", "residual_layer", "norm", "loss"):
-        if file_cfg[key] != model_cfg[key]:
-            return f"{key}: file {file_cfg[key]}, model {model_cfg[key]}"
+    """the first differing field as "<field>: file <x>, model <y>", or None.  The layer type comes first: a gcn
+    configuration has no "model" key and counts as "gcn", and has none of variant, heads and attn_slope"""
+    defaults = {"model": "gcn"}
+    for key in ("model", "variant", "sizes", "heads", "attn_slope", "residual_layer", "norm", "loss"):
+        f, m = file_cfg.get(key, defaults.get(key)), model_cfg.get(key, defaults.get(key))
+        if f != m:
+            return f"{key}: file {f}, model {m}"
     return None
 
 
 class checkpoint_option:
-    """save / load / predict of gcn and dist.dist_gcn.  ``ctx`` is what the model's other members take: a context, or
-    the rank's dist_context -- every rank of a dist_gcn calls save and load (rank 0 alone writes, every rank reads) and
-    predict returns the rank's rows."""
+    """save / load / predict of gcn, dist.dist_gcn, gat.gat and dist_gat.dist_gat.  ``ctx`` is what the model's other
+    members take: a context, or the rank's dist_context -- every rank of a dist_gcn or dist_gat calls save and load (rank 0
+    alone writes, every rank reads) and predict returns the rank's rows."""
 
     def checkpoint_config(self) -> dict:
-        return {"sizes": [int(s) for s in self.sizes], "residual_layer": bool(self.residual_layer), "norm": self.norm,
-                "loss": self.loss, "dropout": (self.dropout_p, self.dropout_seed, self.dropout_epoch)}
+        cfg = {"sizes": [int(s) for s in self.sizes], "residual_layer": bool(getattr(self, "residual_layer", False)),
+               "norm": getattr(self, "norm", None), "loss": self.loss,
+               "dropout": (self.dropout_p, self.dropout_seed, self.dropout_epoch)}
+        if hasattr(self, "variant"):                            # gat, dist_gat: the layer type (version 3 of the file)
+            cfg.update(model="gat", variant=self.variant, heads=[int(h) for h in self.heads],
+                       attn_slope=float(self.attn_slope), attn_dropout=float(self.attn_dropout_p))
+        return cfg
 
     def _write_checkpoint(self, ctx, path: str, tensors: Dict[str, np.ndarray], optimizer: bool, step: int) -> None:
         """rank 0 writes; the others leave once the file is complete"""
@@ -95,14 +109,16 @@ class checkpoint_option:
 
     def load(self, ctx, path: str) -> None:
         """Reads ``path`` into this model, in place: the parameter and moment buffers keep their addresses (the fused Adam
-        table holds raw pointers).  ValueError naming the first differing field of the configuration -- sizes,
-        residual_layer, norm, loss -- before anything is written.  A file without the optimiser section resets Adam
-        (zero moments, step 0).  Restores every step count and calls set_dropout with the file's (p, seed, epoch)."""
+        table holds raw pointers).  ValueError naming the first differing field of the configuration -- model,
+        variant, sizes, heads, attn_slope, residual_layer, norm, loss -- before anything is written or stored.  A file
+        without the optimiser section resets Adam (zero moments, step 0).  Restores every step count and calls set_dropout
+        with the file's (p, seed, epoch), and the file's attention dropout probability on an attention model."""
         cfg, tensors = datasets.read_checkpoint(path)
         bad = config_mismatch(cfg, self.checkpoint_config())
         if bad is not None:
             raise ValueError(f"{path}: {bad}")
-        self.set_dropout(*cfg["dropout"])                       # host state; its own refusals come before any device write
+        attn = {"attn": cfg["attn_dropout"]} if "attn_dropout" in cfg else {}
+        self.set_dropout(*cfg["dropout"], **attn)               # host state; its own refusals come before any device write
         rc = raw_context(ctx)
         for owner in model_owners(self):
             owner.adam_state(rc)                                # a model that never stepped: allocate (and zero) first
@@ -121,7 +137,7 @@ class checkpoint_option:
 
     def predict(self, ctx, X) -> np.ndarray:
         """Host int32 predictions of a plain forward (it never drops): [n x 1] argmax, the first maximum winning
-        (ops.max_row_indices), or [n x C] 0 / 1 for logit > 0 with loss="bce".  dist_gcn: the rank's rows."""
+        (ops.max_row_indices), or [n x C] 0 / 1 for logit > 0 with loss="bce".  dist_gcn, dist_gat: the rank's rows."""
         rc = raw_context(ctx)
         out = self(ctx, X)
         out = getattr(out, "local", out)

@@ -127,21 +127,38 @@ def read_dataset(dirname: str):
 #   u64 Adam step | u32 T | T x { u32 name length | name | u32 rows | u32 cols | f32 payload[rows * cols] } |
 #   optimizer = 1: T x { f32 m[rows * cols] | f32 v[rows * cols] } in the order of the tensors | end of file
 #
+# An attention model (gat, dist_gat) writes version 3: the same file with one block between `loss` and `optimizer`,
+#
+#   u32 model (1 gat) | u32 variant (1 v1, 2 v2) | u32 heads[L - 1] | f64 attn_slope | f64 attention dropout p
+#
+# and residual_layer = norm = 0.  Version 2 was never written and both readers refuse it.
+#
 # The tensors are exactly those the configuration implies, in the order of checkpoint_tensors().
 # ----------------------------------------------------------------------------
 CHECKPOINT_MAGIC = b"MGGCNCKP"
 CHECKPOINT_VERSION = 1
+CHECKPOINT_VERSION_ATTENTION = 3
 CHECKPOINT_NORMS = (None, "layer")
 CHECKPOINT_LOSSES = ("softmax", "bce")
+CHECKPOINT_MODELS = ("gcn", "gat")                                  # the file's `model` field; gcn (0) is never written
+CHECKPOINT_VARIANTS = (None, "v1", "v2")                            # the file's `variant` field
 CHECKPOINT_MAX_LAYERS = 4096
+CHECKPOINT_MAX_HEADS = 16                                           # ops.GAT_MAX_HEADS
+CHECKPOINT_MAX_HEAD_WIDTH = 1024                                    # ops.GAT_MAX_WIDTH
 
 
-def checkpoint_tensors(sizes, residual_layer: bool, norm):
+def checkpoint_tensors(sizes, residual_layer: bool, norm, model: str = "gcn", variant=None):
     """[(name, (rows, cols))] of every parameter tensor of a model, in file order: per layer l W<l>, b<l>, then res_W<l>,
-    res_b<l> where a residual layer's widths differ, then gamma<l>, beta<l> where the layer has a norm (never the last)"""
+    res_b<l> where a residual layer's widths differ, then gamma<l>, beta<l> where the layer has a norm (never the last).
+    model="gat": per layer W<l>, b<l>, att<l> -- [in x out], [1 x out], [2 x out] for variant="v1" and [in x 2 out],
+    [1 x 2 out], [1 x out] for "v2"."""
     out = []
     for l in range(len(sizes) - 1):
         i, o = int(sizes[l]), int(sizes[l + 1])
+        if model == "gat":
+            z = 2 * o if variant == "v2" else o
+            out += [(f"W{l}", (i, z)), (f"b{l}", (1, z)), (f"att{l}", (1 if variant == "v2" else 2, o))]
+            continue
         out += [(f"W{l}", (i, o)), (f"b{l}", (1, o))]
         if residual_layer and i != o:
             out += [(f"res_W{l}", (i, o)), (f"res_b{l}", (1, o))]
@@ -150,19 +167,63 @@ def checkpoint_tensors(sizes, residual_layer: bool, norm):
     return out
 
 
+def _checkpoint_attention_problem(sizes, residual, norm, variant_id, heads, attn_p):
+    """what is wrong with the attention block of a version-3 file next to its header, or None; the writer and the reader
+    share it"""
+    if residual or norm:
+        return f"unknown option value (residual_layer {int(residual)}, norm {int(norm)} in an attention model's file)"
+    if variant_id not in (1, 2):
+        return f"unknown variant value {variant_id}"
+    if len(heads) != len(sizes) - 1:
+        return f"{len(heads)} heads for {len(sizes) - 1} layers"
+    for l, h in enumerate(heads):
+        o = sizes[l + 1]
+        if not 1 <= h <= CHECKPOINT_MAX_HEADS:
+            return f"layer {l} has {h} heads, not 1..{CHECKPOINT_MAX_HEADS}"
+        if o > CHECKPOINT_MAX_HEAD_WIDTH:
+            return f"layer {l} is {o} wide, an attention layer at most {CHECKPOINT_MAX_HEAD_WIDTH}"
+        if o % h:
+            return f"layer {l}: {h} heads do not divide the width {o}"
+    if not (0.0 <= attn_p < 1.0):
+        return f"attention dropout probability {attn_p}"
+    if variant_id == 2 and attn_p != 0.0:
+        return f"attention dropout probability {attn_p} with variant v2, which has none"
+    return None
+
+
 def write_checkpoint(path: str, config: dict, tensors: dict) -> None:
     """config: {"sizes", "residual_layer", "norm" (None / "layer"), "loss" ("softmax" / "bce"), "dropout": (p, seed,
     epoch), "step", "optimizer" (bool)}; tensors: name -> float32 array for every name of checkpoint_tensors(), and
-    "m.<name>" / "v.<name>" as well when config["optimizer"]."""
+    "m.<name>" / "v.<name>" as well when config["optimizer"].  config["model"] == "gat" (default "gcn", which writes
+    version 1 as ever) writes version 3 and takes "variant" ("v1" / "v2"), "heads" (one per layer), "attn_slope" and
+    "attn_dropout" as well."""
     sizes = [int(s) for s in config["sizes"]]
     norm, loss = config.get("norm"), config.get("loss", "softmax")
+    model = config.get("model", "gcn")
     if len(sizes) < 2 or len(sizes) > CHECKPOINT_MAX_LAYERS or min(sizes) < 1 or max(sizes) >= 2 ** 32:
         raise format_error(f"{path}: sizes {sizes} cannot be stored")
     if norm not in CHECKPOINT_NORMS or loss not in CHECKPOINT_LOSSES:
         raise format_error(f"{path}: norm {norm!r} / loss {loss!r} cannot be stored")
+    if model not in CHECKPOINT_MODELS:
+        raise format_error(f"{path}: model {model!r} cannot be stored")
     optimizer = bool(config.get("optimizer", False))
+    residual = bool(config.get("residual_layer", False))
     p, seed, epoch = config.get("dropout", (0.0, 0, 0))
-    want = checkpoint_tensors(sizes, bool(config.get("residual_layer", False)), norm)
+    attention = []
+    variant = None
+    if model == "gat":
+        variant = config.get("variant", "v1")
+        if variant not in CHECKPOINT_VARIANTS[1:]:
+            raise format_error(f"{path}: variant {variant!r} cannot be stored")
+        heads = [int(h) for h in config["heads"]]
+        slope, attn_p = float(config.get("attn_slope", 0.2)), float(config.get("attn_dropout", 0.0))
+        bad = _checkpoint_attention_problem(sizes, residual, CHECKPOINT_NORMS.index(norm), CHECKPOINT_VARIANTS.index(variant),
+                                            heads, attn_p)
+        if bad is not None:
+            raise format_error(f"{path}: {bad}")
+        attention = [np.array([CHECKPOINT_MODELS.index(model), CHECKPOINT_VARIANTS.index(variant)] + heads, dtype="<u4").tobytes(),
+                     np.array([slope, attn_p], dtype="<f8").tobytes()]
+    want = checkpoint_tensors(sizes, residual, norm, model=model, variant=variant)
 
     def payload(name, shape):
         if name not in tensors:
@@ -172,13 +233,15 @@ def write_checkpoint(path: str, config: dict, tensors: dict) -> None:
             raise format_error(f"{path}: tensor {name} has {a.size} elements, the model {shape[0]} x {shape[1]}")
         return a.tobytes()
 
-    parts = [CHECKPOINT_MAGIC, np.array([CHECKPOINT_VERSION, len(sizes)] + sizes, dtype="<u4").tobytes(),
-             np.array([int(bool(config.get("residual_layer", False))), CHECKPOINT_NORMS.index(norm),
-                       CHECKPOINT_LOSSES.index(loss), int(optimizer)], dtype="<u4").tobytes(),
-             np.array([float(p)], dtype="<f8").tobytes(),
-             np.array([int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(config.get("step", 0)) if optimizer else 0],
-                      dtype="<u8").tobytes(),
-             np.array([len(want)], dtype="<u4").tobytes()]
+    version = CHECKPOINT_VERSION_ATTENTION if model == "gat" else CHECKPOINT_VERSION
+    parts = [CHECKPOINT_MAGIC, np.array([version, len(sizes)] + sizes, dtype="<u4").tobytes(),
+             np.array([int(residual), CHECKPOINT_NORMS.index(norm), CHECKPOINT_LOSSES.index(loss)], dtype="<u4").tobytes()]
+    parts += attention
+    parts += [np.array([int(optimizer)], dtype="<u4").tobytes(),
+              np.array([float(p)], dtype="<f8").tobytes(),
+              np.array([int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), int(config.get("step", 0)) if optimizer else 0],
+                       dtype="<u8").tobytes(),
+              np.array([len(want)], dtype="<u4").tobytes()]
     for name, shape in want:
         parts += [np.array([len(name)], dtype="<u4").tobytes(), name.encode("ascii"),
                   np.array(shape, dtype="<u4").tobytes(), payload(name, shape)]
@@ -190,8 +253,10 @@ def write_checkpoint(path: str, config: dict, tensors: dict) -> None:
 
 
 def read_checkpoint(path: str):
-    """(config, tensors) as write_checkpoint takes them.  Every length is checked against the file's size before anything
-    is copied; a truncated file, trailing bytes, a wrong magic or an unknown version is a format_error naming the file."""
+    """(config, tensors) as write_checkpoint takes them; a version-3 file (an attention model's) adds "model", "variant",
+    "heads", "attn_slope" and "attn_dropout" to the configuration, a version-1 file has none of them.  Every length is
+    checked against the file's size before anything is copied; a truncated file, trailing bytes, a wrong magic or an
+    unknown version (2 among them: it was never written) is a format_error naming the file."""
     with open(path, "rb") as f:
         buf = f.read()
     at = 0
@@ -209,15 +274,31 @@ def read_checkpoint(path: str):
     if take(8, "the magic") != CHECKPOINT_MAGIC:
         raise format_error(f"{path}: not a checkpoint file (wrong magic)")
     version, = u32("the version")
-    if version != CHECKPOINT_VERSION:
-        raise format_error(f"{path}: checkpoint version {version} is not supported (this reader knows {CHECKPOINT_VERSION})")
+    if version not in (CHECKPOINT_VERSION, CHECKPOINT_VERSION_ATTENTION):
+        raise format_error(f"{path}: checkpoint version {version} is not supported (this reader knows {CHECKPOINT_VERSION} "
+                           f"and {CHECKPOINT_VERSION_ATTENTION})")
     L, = u32("the layer count")
     if L < 2 or L > CHECKPOINT_MAX_LAYERS:
         raise format_error(f"{path}: {L} sizes")
     sizes = u32("the sizes", L)
     if min(sizes) < 1:
         raise format_error(f"{path}: a layer width of zero")
-    residual, norm_id, loss_id, optimizer = u32("the options", 4)
+    residual, norm_id, loss_id = u32("the options", 3)
+    attention = {}
+    if version == CHECKPOINT_VERSION_ATTENTION:
+        model_id, variant_id = u32("the attention block", 2)
+        if model_id != 1:
+            raise format_error(f"{path}: unknown model value {model_id}")
+        heads = u32("the heads", L - 1)
+        slope, attn_p = (float(x) for x in np.frombuffer(take(16, "the attention block"), dtype="<f8"))
+        if norm_id >= len(CHECKPOINT_NORMS) or loss_id >= len(CHECKPOINT_LOSSES):
+            raise format_error(f"{path}: unknown option value ({residual}, {norm_id}, {loss_id})")
+        bad = _checkpoint_attention_problem(sizes, residual, norm_id, variant_id, heads, attn_p)
+        if bad is not None:
+            raise format_error(f"{path}: {bad}")
+        attention = {"model": CHECKPOINT_MODELS[model_id], "variant": CHECKPOINT_VARIANTS[variant_id], "heads": heads,
+                     "attn_slope": slope, "attn_dropout": attn_p}
+    optimizer, = u32("the options")
     if residual > 1 or norm_id >= len(CHECKPOINT_NORMS) or loss_id >= len(CHECKPOINT_LOSSES) or optimizer > 1:
         raise format_error(f"{path}: unknown option value ({residual}, {norm_id}, {loss_id}, {optimizer})")
     p = float(np.frombuffer(take(8, "the dropout state"), dtype="<f8")[0])
@@ -227,7 +308,7 @@ def read_checkpoint(path: str):
     if not optimizer and step:
         raise format_error(f"{path}: a step count without an optimiser section")
     norm = CHECKPOINT_NORMS[norm_id]
-    want = checkpoint_tensors(sizes, bool(residual), norm)
+    want = checkpoint_tensors(sizes, bool(residual), norm, model=attention.get("model", "gcn"), variant=attention.get("variant"))
     T, = u32("the tensor count")
     if T != len(want):
         raise format_error(f"{path}: {T} tensors, the configuration has {len(want)}")
@@ -247,6 +328,7 @@ def read_checkpoint(path: str):
         raise format_error(f"{path}: {len(buf) - at} trailing bytes")
     config = {"sizes": sizes, "residual_layer": bool(residual), "norm": norm, "loss": CHECKPOINT_LOSSES[loss_id],
               "dropout": (p, seed, epoch), "step": step, "optimizer": bool(optimizer)}
+    config.update(attention)
     return config, tensors
 
 

@@ -35,7 +35,10 @@ above); the rank packs (lse, D) of its destinations into 8-byte records (ops.gat
 heads bytes per vertex delivers all of them to backward_src (ops.gatv2_backward_src_rec).  out, lse, D, P, G_Zd and G_Zs
 are the single-GPU rows bit for bit at any P.  No attention dropout (refused, as gat refuses it).
 
-Not covered: the halo and rounds schedules, bf16 on the wire, layer norm, checkpoints, the C++ host layer."""
+save / load / predict (checkpoint.checkpoint_option): every rank calls them; rank 0 writes its replica of W, b and att and
+every rank reads the file, so a gat file loads here at any P and the other way round; predict returns the rank's rows.
+
+Not covered: the halo and rounds schedules, bf16 on the wire, layer norm, the C++ host layer."""
 from __future__ import annotations
 
 from typing import List, Optional, Sequence
@@ -43,6 +46,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import ops
+from .checkpoint import checkpoint_option
 from .dist import (_repl_view, _torch, _wrap_local, dist_context, dist_gcn, dist_row_csr_matrix, dist_row_dn_matrix,
                    dist_row_linear, dist_row_softmax_cross_entropy_loss, partition_bounds)
 from .gat import attention, attention_v2, check_heads, check_variant, gat, gat_layer
@@ -266,7 +270,7 @@ class dist_gatv2_layer(dist_gat_layer):
         self.AHW = self.act
 
 
-class dist_gat(dropout_option):
+class dist_gat(dropout_option, checkpoint_option):
     """gat.gat on the row partition.
 
     dist_gat(dctx, A, A_T, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0,
@@ -280,7 +284,8 @@ class dist_gat(dropout_option):
     the masks the single-GPU model draws (feature dropout with row0 = p_r; attention dropout see the module docstring).
     __call__, train_forward, backward, adam_update, train_step (one synchronisation; the loss sums ride on the last layer's
     gradient all-reduce), set_splits(dctx, Sd), split_metrics and layers() are dist_gcn's, which has no evaluate()
-    either: a plain call is the forward that never drops."""
+    either: a plain call is the forward that never drops.  save(dctx, path, optimizer=True) / load(dctx, path) /
+    predict(dctx, X): see checkpoint.checkpoint_option -- a refused load raises on every rank alike, before any collective."""
 
     def __init__(self, dctx: dist_context, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix, sizes: Sequence[int], heads=4,
                  attn_slope: float = ops.GAT_SLOPE, loss: str = "softmax", fused: bool = True, weights=None,

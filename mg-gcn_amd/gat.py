@@ -41,7 +41,12 @@ return_attention_weights), attention_pattern() the (indptr, indices) their rows 
 The values are the backward kernels' own expression exp(e - lse) (mggcn_gat_alpha_f32 / mggcn_gatv2_alpha_f32); nothing is
 allocated or launched unless one of these is called.
 
-Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, checkpoints, layer norm, bf16 gathers.
+save / load / predict and model_selector are gcn's (checkpoint.checkpoint_option, selection.model_selector): the file stores
+the layer type -- variant, heads, attn_slope, the attention dropout probability -- next to W, b and att of every layer
+(version 3 of the checkpoint file, INTEGRATION.md "Checkpoint file"), and a resumed run is the uninterrupted run bit for bit
+(DESIGN.md 3.10.6).  Nothing is allocated or launched unless one of these is called.
+
+Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, layer norm, bf16 gathers.
 """
 from __future__ import annotations
 
@@ -50,6 +55,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import _lib, ops
+from .checkpoint import checkpoint_option
 from .gcn import (DROPOUT_MAX_LAYERS, adam_update_all, check_dropout, check_loss, dropout_option, gcn, linear,
                   sigmoid_bce_loss, softmax_cross_entropy_loss)
 from .matrix import context, csr_matrix, dn_matrix
@@ -312,7 +318,7 @@ def check_variant(variant, attn_dropout: float = 0.0) -> str:
     return variant
 
 
-class gat(dropout_option):
+class gat(dropout_option, checkpoint_option):
     """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
 
     gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
@@ -332,7 +338,10 @@ class gat(dropout_option):
     ValueError for a probability outside [0, 1), or for more than 64 layers with one of them above 0, before any device work.
 
     __call__, train_forward, backward, adam_update, train_step (one synchronisation), evaluate, set_splits, split_metrics
-    and layers() mean what they mean on ``gcn``."""
+    and layers() mean what they mean on ``gcn``, and so do save(ctx, path, optimizer=True) / load(ctx, path) / predict(ctx, X)
+    (checkpoint.checkpoint_option): a file loads into a gat or dist_gat of the same variant, sizes, heads, attn_slope and
+    loss, whatever ``fused`` is -- ValueError naming the first differing field before anything is written -- and brings both
+    dropout probabilities, the seed and the epoch counter with it."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
                  loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0,

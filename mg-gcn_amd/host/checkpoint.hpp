@@ -8,6 +8,13 @@
 //   u64 Adam step | u32 T | T x { u32 name length | name | u32 rows | u32 cols | f32 payload[rows * cols] } |
 //   optimizer = 1: T x { f32 m[rows * cols] | f32 v[rows * cols] } in the order of the tensors | end of file
 //
+// An attention model (Python's gat and dist_gat; this layer has none and only refuses such a file by name) writes version 3:
+// the same file with one block between `loss` and `optimizer`,
+//
+//   u32 model (1 gat) | u32 variant (1 v1, 2 v2) | u32 heads[L - 1] | f64 attn_slope | f64 attention dropout p
+//
+// residual_layer = norm = 0, and per layer W<l>, b<l>, att<l>.  Version 2 was never written; it is refused.
+//
 // All integers and floats little-endian (the hosts this runs on are).  The reader checks every length against the file's
 // size before it allocates or copies; a truncated file, trailing bytes, a wrong magic or an unknown version is a
 // checkpoint_error that names the file.
@@ -39,8 +46,10 @@ struct checkpoint_tensor {
 
 struct checkpoint {
     static constexpr const char *magic = "MGGCNCKP";
-    static constexpr std::uint32_t version = 1;
+    static constexpr std::uint32_t version = 1;              // model == 0 (gcn)
+    static constexpr std::uint32_t version_attention = 3;    // model == 1 (gat)
     static constexpr std::uint32_t max_sizes = 4096;
+    static constexpr std::uint32_t max_heads = 16, max_attention_width = 1024;      // the limits of the GAT kernels
 
     std::vector<std::uint32_t> sizes;
     bool residual_layer = false;
@@ -49,13 +58,22 @@ struct checkpoint {
     bool optimizer = false;
     double dropout_p = 0;
     std::uint64_t dropout_seed = 0, dropout_epoch = 0, step = 0;
+    // version 3 only: model 0 is a gcn file (version 1), which has none of these
+    std::uint32_t model = 0;             // 0 gcn, 1 gat
+    std::uint32_t variant = 0;           // 1 v1, 2 v2
+    std::vector<std::uint32_t> heads;    // one per layer
+    double attn_slope = 0, attn_dropout_p = 0;
     std::vector<checkpoint_tensor> tensors;
 
     static const char *norm_name(std::uint32_t n) { return n == 1 ? "layer" : "none"; }
     static const char *loss_name(std::uint32_t l) { return l == 1 ? "bce" : "softmax"; }
+    static const char *model_name(std::uint32_t m) { return m == 1 ? "gat" : "gcn"; }
 
     // (name, rows, cols) of every parameter tensor the configuration implies, in file order
-    static std::vector<checkpoint_tensor> expected(const std::vector<std::uint32_t> &sizes, bool residual_layer, std::uint32_t norm) {
+    // (model 1: W<l>, b<l>, att<l> -- [in x out], [1 x out], [2 x out] for variant 1, [in x 2 out], [1 x 2 out], [1 x out] for 2;
+    // the caller has checked out <= max_attention_width)
+    static std::vector<checkpoint_tensor> expected(const std::vector<std::uint32_t> &sizes, bool residual_layer, std::uint32_t norm,
+                                                   std::uint32_t model = 0, std::uint32_t variant = 0) {
         std::vector<checkpoint_tensor> out;
         auto add = [&out](const std::string &name, std::uint32_t r, std::uint32_t c) {
             checkpoint_tensor t;
@@ -65,6 +83,11 @@ struct checkpoint {
         for (std::size_t l = 0; l + 1 < sizes.size(); l++) {
             const auto i = sizes[l], o = sizes[l + 1];
             const auto s = std::to_string(l);
+            if (model == 1) {
+                const auto z = variant == 2 ? 2 * o : o;
+                add("W" + s, i, z), add("b" + s, 1, z), add("att" + s, variant == 2 ? 1 : 2, o);
+                continue;
+            }
             add("W" + s, i, o), add("b" + s, 1, o);
             if (residual_layer && i != o) add("res_W" + s, i, o), add("res_b" + s, 1, o);
             if (norm == 1 && l + 2 < sizes.size()) add("gamma" + s, 1, o), add("beta" + s, 1, o);
@@ -84,7 +107,9 @@ struct checkpoint {
         for (std::size_t i = 0; i < v.size(); i++) s += (i ? ", " : "") + std::to_string(v[i]);
         return s + "]";
     }
-    std::string mismatch(const std::vector<std::uint32_t> &m_sizes, bool m_residual, std::uint32_t m_norm, std::uint32_t m_loss) const {
+    std::string mismatch(const std::vector<std::uint32_t> &m_sizes, bool m_residual, std::uint32_t m_norm, std::uint32_t m_loss,
+                         std::uint32_t m_model = 0) const {
+        if (model != m_model) return std::string("model: file ") + model_name(model) + ", model " + model_name(m_model);
         if (sizes != m_sizes) return "sizes: file " + list(sizes) + ", model " + list(m_sizes);
         if (residual_layer != m_residual)
             return std::string("residual_layer: file ") + (residual_layer ? "true" : "false") + ", model " + (m_residual ? "true" : "false");
@@ -93,19 +118,47 @@ struct checkpoint {
         return "";
     }
 
+    // what is wrong with the attention block next to the header, or ""; the writer and the reader share it
+    std::string attention_problem() const {
+        if (residual_layer || norm) return "unknown option value (residual_layer or norm in an attention model's file)";
+        if (variant != 1 && variant != 2) return "unknown variant value " + std::to_string(variant);
+        if (heads.size() + 1 != sizes.size()) return std::to_string(heads.size()) + " heads for " + std::to_string(sizes.size() - 1) + " layers";
+        for (std::size_t l = 0; l < heads.size(); l++) {
+            const auto h = heads[l], o = sizes[l + 1];
+            const auto layer = "layer " + std::to_string(l);
+            if (h < 1 || h > max_heads) return layer + " has " + std::to_string(h) + " heads, not 1.." + std::to_string(max_heads);
+            if (o > max_attention_width) return layer + " is " + std::to_string(o) + " wide, an attention layer at most " + std::to_string(max_attention_width);
+            if (o % h) return layer + ": " + std::to_string(h) + " heads do not divide the width " + std::to_string(o);
+        }
+        if (!(attn_dropout_p >= 0.0 && attn_dropout_p < 1.0)) return "attention dropout probability out of [0, 1)";
+        if (variant == 2 && attn_dropout_p != 0.0) return "attention dropout with variant v2, which has none";
+        return "";
+    }
+
     // ---- writer ------------------------------------------------------------------------------------------------------
     std::string bytes(const std::string &path_for_errors = "checkpoint") const {
-        const auto want = expected(sizes, residual_layer, norm);
         if (sizes.size() < 2 || sizes.size() > max_sizes) throw checkpoint_error(path_for_errors + ": " + std::to_string(sizes.size()) + " sizes cannot be stored");
+        if (model > 1) throw checkpoint_error(path_for_errors + ": model " + std::to_string(model) + " cannot be stored");
+        if (model == 1) {
+            const auto bad = attention_problem();
+            if (!bad.empty()) throw checkpoint_error(path_for_errors + ": " + bad);
+        }
+        const auto want = expected(sizes, residual_layer, norm, model, variant);
         if (want.size() != tensors.size()) throw checkpoint_error(path_for_errors + ": " + std::to_string(tensors.size()) + " tensors, the configuration has " + std::to_string(want.size()));
         std::string out;
         auto put = [&out](const void *p, std::size_t n) { out.append(static_cast<const char *>(p), n); };
         auto u32 = [&put](std::uint32_t x) { put(&x, 4); };
         auto u64 = [&put](std::uint64_t x) { put(&x, 8); };
         put(magic, 8);
-        u32(version), u32((std::uint32_t)sizes.size());
+        u32(model == 1 ? version_attention : version), u32((std::uint32_t)sizes.size());
         for (auto s : sizes) u32(s);
-        u32(residual_layer ? 1 : 0), u32(norm), u32(loss), u32(optimizer ? 1 : 0);
+        u32(residual_layer ? 1 : 0), u32(norm), u32(loss);
+        if (model == 1) {
+            u32(model), u32(variant);
+            for (auto h : heads) u32(h);
+            put(&attn_slope, 8), put(&attn_dropout_p, 8);
+        }
+        u32(optimizer ? 1 : 0);
         put(&dropout_p, 8);
         u64(dropout_seed), u64(dropout_epoch), u64(optimizer ? step : 0);
         u32((std::uint32_t)tensors.size());
@@ -158,21 +211,33 @@ struct checkpoint {
         take(mg, 8, "the magic");
         if (std::memcmp(mg, magic, 8) != 0) throw checkpoint_error(path + ": not a checkpoint file (wrong magic)");
         const auto ver = u32("the version");
-        if (ver != version) throw checkpoint_error(path + ": checkpoint version " + std::to_string(ver) + " is not supported (this reader knows " + std::to_string(version) + ")");
+        if (ver != version && ver != version_attention)
+            throw checkpoint_error(path + ": checkpoint version " + std::to_string(ver) + " is not supported (this reader knows " + std::to_string(version) + " and " + std::to_string(version_attention) + ")");
         const auto L = u32("the layer count");
         if (L < 2 || L > max_sizes) throw checkpoint_error(path + ": " + std::to_string(L) + " sizes");
         for (std::uint32_t i = 0; i < L; i++) {
             c.sizes.push_back(u32("the sizes"));
             if (c.sizes.back() == 0) throw checkpoint_error(path + ": a layer width of zero");
         }
-        const auto res = u32("the options"), norm = u32("the options"), loss = u32("the options"), opt = u32("the options");
+        const auto res = u32("the options"), norm = u32("the options"), loss = u32("the options");
+        if (ver == version_attention) {
+            c.model = u32("the attention block"), c.variant = u32("the attention block");
+            if (c.model != 1) throw checkpoint_error(path + ": unknown model value " + std::to_string(c.model));
+            for (std::uint32_t i = 0; i + 1 < L; i++) c.heads.push_back(u32("the heads"));
+            take(&c.attn_slope, 8, "the attention block"), take(&c.attn_dropout_p, 8, "the attention block");
+            if (res > 1 || norm > 1 || loss > 1) throw checkpoint_error(path + ": unknown option value");
+            c.residual_layer = res, c.norm = norm;
+            const auto bad = c.attention_problem();
+            if (!bad.empty()) throw checkpoint_error(path + ": " + bad);
+        }
+        const auto opt = u32("the options");
         if (res > 1 || norm > 1 || loss > 1 || opt > 1) throw checkpoint_error(path + ": unknown option value");
         c.residual_layer = res, c.norm = norm, c.loss = loss, c.optimizer = opt;
         take(&c.dropout_p, 8, "the dropout state");
         c.dropout_seed = u64("the dropout state"), c.dropout_epoch = u64("the dropout state"), c.step = u64("the dropout state");
         if (!(c.dropout_p >= 0.0 && c.dropout_p < 1.0)) throw checkpoint_error(path + ": dropout probability out of [0, 1)");
         if (!c.optimizer && c.step) throw checkpoint_error(path + ": a step count without an optimiser section");
-        c.tensors = expected(c.sizes, c.residual_layer, c.norm);
+        c.tensors = expected(c.sizes, c.residual_layer, c.norm, c.model, c.variant);
         const auto T = u32("the tensor count");
         if (T != c.tensors.size()) throw checkpoint_error(path + ": " + std::to_string(T) + " tensors, the configuration has " + std::to_string(c.tensors.size()));
         for (auto &t : c.tensors) {

@@ -1141,7 +1141,8 @@ public:
     }
     void save(const context ctx, const std::string &path, bool optimizer = true) { state(ctx, optimizer).write(path); }
     // Compares the file's configuration with the model's first: mggcn::checkpoint_error naming the first difference
-    // ("sizes: file [..], model [..]") before a single device write.  Then parameters and moments are written in place,
+    // ("sizes: file [..], model [..]"; the layer type first: an attention model's file is "model: file gat, model gcn",
+    // checkpoint::mismatch) before a single device write.  Then parameters and moments are written in place,
     // every step count is restored (a file without the optimiser section resets Adam: zero moments, step 0) and
     // set_dropout gets the file's (p, seed, epoch).
     void load(const context ctx, const std::string &path) { load_state(ctx, mggcn::checkpoint::read(path), path); }

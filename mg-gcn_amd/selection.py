@@ -1,7 +1,7 @@
 """Model selection on a split's loss or score: keep the best epoch's parameters, stop early, restore, save (opt-in; the
-reference reports over all vertices and keeps nothing).  Host bookkeeping around train_step for gcn and dist.dist_gcn; the
-only device work it adds is dn_matrix.copy_to of the parameters (and, with ``clean``, one plain forward and one loss-layer
-call per epoch).  A model without a selector launches and allocates nothing new.
+reference reports over all vertices and keeps nothing).  Host bookkeeping around train_step for gcn, dist.dist_gcn, gat.gat
+and dist_gat.dist_gat; the only device work it adds is dn_matrix.copy_to of the parameters (and, with ``clean``, one plain
+forward and one loss-layer call per epoch).  A model without a selector launches and allocates nothing new.
 """
 from __future__ import annotations
 
@@ -27,8 +27,8 @@ class model_selector:
     clean=True runs one extra plain forward and one loss-layer call after the update (no backward) and monitors that:
     ``history[e]`` speaks of the parameters epoch e ended with, snapshotted when the number improved.  The extra forward
     is not a training forward: it draws no mask and spends no dropout epoch.  split_metrics() of the model then reports
-    the clean pass.  The default is clean = (dropout_p > 0): with dropout on, the training forward's validation numbers
-    are the dropped forward's and a model must not be selected on them.
+    the clean pass.  The default is clean = (dropout_p > 0 or attn_dropout_p > 0): with either dropout on, the training
+    forward's validation numbers are the dropped forward's and a model must not be selected on them.
 
     "Improved" is strict -- lower loss, higher score; the first best epoch wins a tie; a NaN never improves.
     ``stop`` turns true once ``patience`` epochs have passed without improvement."""
@@ -48,7 +48,8 @@ class model_selector:
             raise ValueError(f"no vertex belongs to the {split} split: nothing to select on")
         self.model, self.split, self.metric = model, split, metric
         self.patience = None if patience is None else int(patience)
-        self.clean = bool(model.dropout_p > 0.0) if clean is None else bool(clean)
+        dropping = model.dropout_p > 0.0 or getattr(model, "attn_dropout_p", 0.0) > 0.0
+        self.clean = bool(dropping) if clean is None else bool(clean)
         self.history: List[float] = []
         self.best_epoch: Optional[int] = None
         self.best_value: Optional[float] = None
