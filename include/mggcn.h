@@ -506,6 +506,42 @@ void mggcn_gatv2_alpha_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_co
                            const uint32_t *indices, const float *Zs, size_t ldzs, const float *Zd, size_t ldzd,
                            const float *att, const float *lse, uint32_t K, uint32_t dh, float slope, float *alpha,
                            size_t lda);
+/* Dot-product (transformer) graph attention (opt-in; PyG's TransformerConv without root weight, gate and edge features).  F,
+ * K, dh, the limits and the column layout of a head are those of the GAT block above; Zq is the query transform (one row per
+ * destination), Zk the key and Zv the value transform (one row per source each), lse / D are contiguous [destinations x K],
+ * and the attention has no parameter of its own.  With `scale` = c (the model passes fp32(1 / sqrt(dh))),
+ * e_ijk = c sum_c Zq[i, k dh + c] Zk[j, k dh + c] and alpha_ijk = exp(e_ijk - lse[i, k]):
+ *   forward       lse[i, k] = log sum_j exp(e_ijk) (max-subtracted);  out[i, k dh + c] = sum_j alpha_ijk Zv[j, k dh + c];
+ *                 a row without entries gets lse = 0 and an out row of +0.0 (written, not skipped); a row of one entry
+ *                 copies its source's Zv row bit for bit
+ *   backward_dst  over the rows of F:  D[i, k] = sum_c G[i, k dh + c] out[i, k dh + c];
+ *                 dalpha_ijk = sum_c G[i, k dh + c] Zv[j, k dh + c];  ds_ijk = alpha_ijk (dalpha_ijk - D[i, k]);
+ *                 G_Zq[i, k dh + c] = c sum_j ds_ijk Zk[j, k dh + c]  (a row without entries gets +0.0)
+ *   backward_src  over the rows of F^T (n_rows sources x n_cols destinations; call it after backward_dst, whose D it reads):
+ *                 G_Zk[j, k dh + c] = c sum_i ds_ijk Zq[i, k dh + c];  G_Zv[j, k dh + c] = sum_i alpha_ijk G[i, k dh + c]
+ *                 (a source nobody gathers gets +0.0 in both)
+ * Each sparse call gathers two dense head-rows per entry and computes e on the rows it gathers; nothing of nnz x K is stored
+ * or read.  No atomics: sums over sources run over F's rows, sums over destinations over F^T's, and the softmax folds its
+ * lane groups in a fixed order -- two calls on the same input give the same bits in every output, and rows [r0, r1) of a call
+ * passed as a call of their own (indptr + r0, the row operands moved by r0 rows) give the whole call's rows bit for bit.  One
+ * wave per row, no plan.  Every dense operand has a leading dimension of its own: Zq, Zk and Zv may be the thirds of one
+ * [rows x 3 K dh] buffer (ld = 3 K dh), and so may G_Zq, G_Zk and G_Zv.  16-byte loads when dh % 4 == 0 and every dense
+ * operand of the call is 16-byte aligned with a leading dimension that is a multiple of 4; single elements otherwise.  out
+ * must not alias Zq, Zk or Zv; G_Zq, G_Zk and G_Zv must not alias an input or each other.  n_rows == 0 returns.  Leading
+ * dimensions are checked against K dh. */
+void mggcn_gatdot_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                              const uint32_t *indices, const float *Zq, size_t ldq, const float *Zk, size_t ldk,
+                              const float *Zv, size_t ldv, uint32_t K, uint32_t dh, float scale, float *out, size_t ldo,
+                              float *lse);
+void mggcn_gatdot_backward_dst_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                   const uint32_t *indices, const float *Zq, size_t ldq, const float *Zk, size_t ldk,
+                                   const float *Zv, size_t ldv, const float *lse, const float *G, size_t ldg, const float *out,
+                                   size_t ldo, uint32_t K, uint32_t dh, float scale, float *D, float *G_Zq, size_t ldgzq);
+void mggcn_gatdot_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                   const uint32_t *t_indices, const float *Zq, size_t ldq, const float *Zk, size_t ldk,
+                                   const float *Zv, size_t ldv, const float *lse, const float *D, const float *G, size_t ldg,
+                                   uint32_t K, uint32_t dh, float scale, float *G_Zk, size_t ldgzk, float *G_Zv,
+                                   size_t ldgzv);
 /* cublasSasum  (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

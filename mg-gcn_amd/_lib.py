@@ -129,6 +129,12 @@ PROTOTYPES = {
     "mggcn_gat_alpha_f32": (None,[vp, c_uint32, c_uint32, vp, vp, vp, vp, vp, c_uint32, c_float, vp, c_size_t]),
     "mggcn_gatv2_alpha_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, vp, vp, c_uint32, c_uint32,
                                      c_float, vp, c_size_t]),
+    "mggcn_gatdot_forward_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, vp, c_size_t, c_uint32,
+                                        c_uint32, c_float, vp, c_size_t, vp]),
+    "mggcn_gatdot_backward_dst_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, vp, c_size_t, vp, vp,
+                                             c_size_t, vp, c_size_t, c_uint32, c_uint32, c_float, vp, vp, c_size_t]),
+    "mggcn_gatdot_backward_src_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, vp, c_size_t, vp, vp,
+                                             vp, c_size_t, c_uint32, c_uint32, c_float, vp, c_size_t, vp, c_size_t]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),
     "mggcn_gather_rows_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_softmax_xent_fused_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_float, vp]),

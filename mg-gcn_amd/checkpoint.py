@@ -34,7 +34,7 @@ def model_params(model) -> List[tuple]:
     for l, layer in enumerate(model.layers_):
         out += [(f"W{l}", layer.lin, "W", "mW", "vW"), (f"b{l}", layer.lin, "b", "mb", "vb")]
         attn, res_lin, norm = (getattr(layer, a, None) for a in ("attn", "res_lin", "norm"))
-        if attn is not None:
+        if attn is not None and attn.att is not None:           # gat.attention_dot has no parameter
             out += [(f"att{l}", attn, "att", "m", "v")]
         if res_lin is not None:
             out += [(f"res_W{l}", res_lin, "W", "mW", "vW"), (f"res_b{l}", res_lin, "b", "mb", "vb")]

@@ -1,4 +1,4 @@
-// gat_internal.h -- what the graph attention kernels of gat.hip (GAT) and gatv2.hip (GATv2) share: the one-wave-per-row
+// gat_internal.h -- what the graph attention kernels of gat.hip (GAT), gatv2.hip (GATv2) and gatdot.hip share: the one-wave-per-row
 // layout with LPR-lane groups (gat.hip describes it), the walk over a row's entries (entry_chunks), the group butterfly,
 // the head-row loads and the epilogue, the head geometry, the (VEC, NT, U) dispatch with the row launch, and the column-sum
 // pass behind G_att.  Internal linkage in each translation unit that includes it.  Not part of the ABI.

@@ -49,7 +49,7 @@ from . import ops
 from .checkpoint import checkpoint_option
 from .dist import (_repl_view, _torch, _wrap_local, dist_context, dist_gcn, dist_row_csr_matrix, dist_row_dn_matrix,
                    dist_row_linear, dist_row_softmax_cross_entropy_loss, partition_bounds)
-from .gat import attention, attention_v2, check_heads, check_variant, gat, gat_layer
+from .gat import attention, attention_v2, check_heads, check_single_gpu_variant, check_variant, gat, gat_layer
 from .gcn import check_dropout, check_loss, dropout_option
 from .matrix import context, csr_matrix, dn_matrix
 
@@ -278,7 +278,8 @@ class dist_gat(dropout_option, checkpoint_option):
     both; the layers aggregate over A_T's pattern, values are ignored), everything else means what it means on gat --
     ``variant``: "v1" (this model as it always was) or "v2" (GATv2: W is [in x 2 out], b [1 x 2 out], att [1 x out]; no
     attention dropout).  ValueError before any device work or collective, on every rank alike, for what gat refuses (an
-    unknown variant, "v2" with attn_dropout > 0 and set_dropout(attn > 0) on a v2 model among it) and for n % P != 0.
+    unknown variant, "v2" with attn_dropout > 0 and set_dropout(attn > 0) on a v2 model among it), for variant="dot"
+    (dot-product attention has no row-partitioned form yet) and for n % P != 0.
 
     Every rank calls every method with the same arguments.  set_dropout(p, seed, epoch, attn): a rank drops its rows of
     the masks the single-GPU model draws (feature dropout with row0 = p_r; attention dropout see the module docstring).
@@ -295,6 +296,7 @@ class dist_gat(dropout_option, checkpoint_option):
         n_layers = len(self.sizes) - 1
         self._attn_dropout_params = check_dropout(attn_dropout, n_layers)
         self.variant = check_variant(variant, float(attn_dropout))
+        check_single_gpu_variant(self.variant)                   # "dot": refused on every rank alike
         self._init_dropout(dropout, n_layers)
         self.attn_dropout_p = float(attn_dropout)
         self.loss = check_loss(loss)

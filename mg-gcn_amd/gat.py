@@ -41,6 +41,22 @@ return_attention_weights), attention_pattern() the (indptr, indices) their rows 
 The values are the backward kernels' own expression exp(e - lse) (mggcn_gat_alpha_f32 / mggcn_gatv2_alpha_f32); nothing is
 allocated or launched unless one of these is called.
 
+``variant="dot"`` selects dot-product (transformer) attention (Vaswani et al. 2017; Shi et al. 2021, UniMP; PyG's
+TransformerConv without its root weight, gate and edge features) in every layer:
+
+    Z3 = H W + 1 b^T, W [in x 3 out]                  Zq = Z3[:, :out]   Zk = Z3[:, out:2 out]   Zv = Z3[:, 2 out:]
+    e_ijk = c (Zq[i, head k] . Zk[j, head k]),  c = fp32(1 / sqrt(dh))
+    alpha_ijk = softmax over the entries j of row i   out[i, head k] = sum_j alpha_ijk Zv[j, head k]
+
+The score is the scaled dot product of the destination's query and the source's key, the aggregated row is the source's
+value; the attention has no parameter of its own (a layer's parameters are W and b).  One GEMM forward, the linear's fused
+gradient GEMMs backward over 3 out columns; the kernels are those of csrc/gatdot.hip (mggcn_gatdot_*).  ``weights=`` takes
+(W [in x 3 out], b [1 x 3 out]) per layer.  Refused with ValueError before any device work: attention dropout, the export
+(attention_weights, gat_layer.alpha), save / load (the checkpoint file has no version for this variant yet; model_selector's
+in-memory restore works, save_best does not), dist_gat(variant="dot"), and a graph so large that rows x 3 x the widest
+layer reaches 2^31 elements (the limit of the GEMM's output).  predict, evaluate, split_metrics and model_selector work
+unchanged.
+
 save / load / predict and model_selector are gcn's (checkpoint.checkpoint_option, selection.model_selector): the file stores
 the layer type -- variant, heads, attn_slope, the attention dropout probability -- next to W, b and att of every layer
 (version 3 of the checkpoint file, INTEGRATION.md "Checkpoint file"), and a resumed run is the uninterrupted run bit for bit
@@ -305,17 +321,94 @@ class gatv2_layer(gat_layer):
                     attention_v2(name, n, out, heads, slope, P_buffer), n, in_, out, activation, G_Z_buffer, z_width=2 * out)
 
 
-VARIANTS = ("v1", "v2")
+class attention_dot:
+    """The dot-product attention of one layer: no parameter, only what the backward pass needs of the forward -- lse and D
+    [n x heads] --, the head count and the scale c = fp32(1 / sqrt(dh)).  __call__ and backward take the layer's
+    Z3 = [Zq | Zk | Zv] and G_Z3 = [G_Zq | G_Zk | G_Zv] buffers of 3 out columns.  It is a row of nobody's Adam table."""
+
+    att = G_att = m = v = None          # what the generic readers (checkpoint.model_params) look for on an attention
+    step = 0
+
+    def __init__(self, name: str, n: int, out: int, heads: int, device=None):
+        self.name, self.heads = name, int(heads)
+        self.scale = ops.gatdot_scale(out // self.heads)
+        self.lse, self.D = dn_matrix(n, heads, device=device), dn_matrix(n, heads, device=device)
+
+    def __call__(self, ctx: context, F: csr_matrix, Z3: dn_matrix, out: dn_matrix, drop=None) -> None:
+        """out = the attention-weighted gather of Zv over F's rows, Zq scored against Zk"""
+        assert drop is None, "dot-product attention has no attention dropout"
+        ops.gatdot_forward(ctx, F, Z3, Z3, Z3, out, self.lse, self.heads, self.scale, self.name + "0_gatdot-forward")
+
+    def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z3: dn_matrix, G: dn_matrix, out: dn_matrix,
+                 G_Z3: dn_matrix, drop=None) -> None:
+        """G_Z3 = the gradient of Z3 (all three thirds), from G = the gradient of ``out``"""
+        assert drop is None, "dot-product attention has no attention dropout"
+        n = self.name
+        ops.gatdot_backward_dst(ctx, F, Z3, Z3, Z3, self.lse, G, out, self.D, G_Z3, self.heads, self.scale,
+                                n + "1_gatdot-backward-dst")
+        ops.gatdot_backward_src(ctx, F_T, Z3, Z3, Z3, self.lse, self.D, G, G_Z3, G_Z3, self.heads, self.scale,
+                                n + "1_gatdot-backward-src")
+
+    def alpha(self, ctx, F, Z3, alpha) -> None:
+        raise ValueError('gat(variant="dot") has no export of the attention coefficients')
+
+    def init(self, att) -> None:
+        raise ValueError('gat(variant="dot") has no attention parameter: weights= takes (W, b) per layer')
+
+    def adam_state(self, ctx: context) -> None:
+        pass
+
+    def adam_tensors(self, weight_decay: float):
+        return []
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
+        pass
+
+
+class gatdot_layer(gat_layer):
+    """One dot-product attention layer: ONE ``linear`` of 3 out columns (Z3 = H W + 1 b^T = [Zq | Zk | Zv], the bias inside
+    all three thirds), an ``attention_dot`` over (F, F^T) and the activation.  ``Z`` is Z3 and ``G_Z`` its gradient
+    [G_Zq | G_Zk | G_Zv] (aliasing the model-wide buffer); the layer's parameters are the linear's alone."""
+
+    def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
+                 backward_out: bool = True, G_Z_buffer=None):
+        n = F.n()
+        assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
+        self._setup(name, F, F_T, linear(name, in_, 3 * out, backward_out, True), attention_dot(name, n, out, heads), n, in_,
+                    out, activation, G_Z_buffer, z_width=3 * out)
+
+    def alpha(self, ctx: context, out: Optional[dn_matrix] = None) -> dn_matrix:
+        raise ValueError(f'gat layer {self.name}: gat(variant="dot") has no export of the attention coefficients')
+
+    def params(self):
+        return [self.lin]
+
+
+VARIANTS = ("v1", "v2", "dot")
+DOT_MAX_ELEMENTS = 1 << 31          # csrc/gemm.hip: the output of one GEMM, rows x 3 out, stays below this
 
 
 def check_variant(variant, attn_dropout: float = 0.0) -> str:
-    """``variant=`` of gat: "v1" or "v2"; ValueError for anything else and for GATv2 with attention dropout (the _drop
-    twins of its three sparse kernels do not exist).  No device work."""
+    """``variant=`` of gat: "v1", "v2" or "dot"; ValueError for anything else and for GATv2 or dot-product attention with
+    attention dropout (the _drop twins of their three sparse kernels do not exist).  No device work."""
     if variant not in VARIANTS:
         raise ValueError(f"gat variant must be one of {VARIANTS}, got {variant!r}")
-    if variant == "v2" and attn_dropout > 0.0:
-        raise ValueError("gat(variant=\"v2\") has no attention dropout: attn_dropout must be 0")
+    if variant != "v1" and attn_dropout > 0.0:
+        raise ValueError(f"gat(variant=\"{variant}\") has no attention dropout: attn_dropout must be 0")
     return variant
+
+
+def check_single_gpu_variant(variant) -> None:
+    """what dist_gat.dist_gat refuses after check_variant: ValueError for "dot", which has no row-partitioned form yet.  No
+    device work, no collective."""
+    if variant == "dot":
+        raise ValueError('dist_gat has no variant="dot": dot-product attention is single-GPU only (gat(variant="dot"))')
+
+
+def refuse_dot(model, what: str) -> None:
+    """ValueError when ``model`` is a dot-product attention model: ``what`` is a member it does not have yet"""
+    if getattr(model, "variant", "v1") == "dot":
+        raise ValueError(f'gat(variant="dot") has no {what}')
 
 
 class gat(dropout_option, checkpoint_option):
@@ -326,7 +419,9 @@ class gat(dropout_option, checkpoint_option):
     ``A`` as ``gcn`` takes it (the layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
     (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att);
     ``variant``: "v1" (this model as it always was) or "v2" (GATv2, see the module docstring: W is [in x 2 out], b
-    [1 x 2 out], att [1 x out]; ValueError for another name, for attn_dropout > 0 and for set_dropout(attn > 0)).  ValueError
+    [1 x 2 out], att [1 x out]; ValueError for another name, for attn_dropout > 0 and for set_dropout(attn > 0)) or "dot"
+    (dot-product attention, see the module docstring: W is [in x 3 out], b [1 x 3 out], no att; the refusals of "v2" plus
+    attention_weights, save, load and rows x 3 out >= 2^31).  ValueError
     before any device work for a width that its heads do not divide or a limit of the kernels (ops.GAT_MAX_HEADS,
     ops.GAT_MAX_WIDTH).  ``fused`` picks how Adam is launched -- one launch for every parameter tensor, or one per tensor;
     the element-wise math is the same, so both give the same bits -- and every other kernel is the same in both modes.
@@ -358,6 +453,9 @@ class gat(dropout_option, checkpoint_option):
         self.attn_slope = float(attn_slope)
         self._out_width = self.sizes[-1]
         self.fused = bool(fused)
+        if self.variant == "dot" and A.n() * 3 * max(self.sizes[1:]) >= DOT_MAX_ELEMENTS:
+            raise ValueError(f"gat(variant=\"dot\"): {A.n()} rows x 3 x {max(self.sizes[1:])} columns reach 2^31 elements, "
+                             "more than one GEMM writes")
         import torch
         n_layers = len(self.sizes) - 1
         # the loss reads the logits and writes the gradient elsewhere: the last layer's backward needs its own output
@@ -371,6 +469,11 @@ class gat(dropout_option, checkpoint_option):
             for i in range(n_layers):
                 self.layers_.append(gatv2_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
                                                 i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer, self.P_buffer))
+        elif self.variant == "dot":                              # G_Z3 = [G_Zq | G_Zk | G_Zv], once at the widest layer
+            self.G_Z_buffer = torch.empty(A.n() * 3 * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
+            for i in range(n_layers):
+                self.layers_.append(gatdot_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
+                                                 i + 1 < n_layers, i != 0, self.G_Z_buffer))
         else:
             self.G_Z_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
             for i in range(n_layers):
@@ -458,6 +561,7 @@ class gat(dropout_option, checkpoint_option):
         mggcn_gatv2_alpha_f32): the coefficients the model trains with, the same bits on every call.  This is the one place
         where something of nnz x heads is stored: the Reddit-shaped graph (114.8 M entries) at 4 heads needs 1.84 GB per
         layer.  Nothing is allocated or launched unless this method (or gat_layer.alpha) is called."""
+        refuse_dot(self, "attention_weights: there is no export kernel for the dot-product coefficients yet")
         which = self._alpha_requests(layers, out)
         if X is not None:
             self(ctx, X)
@@ -469,6 +573,20 @@ class gat(dropout_option, checkpoint_option):
         """(indptr, indices): the host arrays of the matrix the forward walks, A.transpose() -- row i is a destination, its
         entries are its sources, and row p of every matrix attention_weights returns belongs to indices[p]"""
         return self.A_T.indptr, self.A_T.indices
+
+    def save(self, ctx, path: str, optimizer: bool = True) -> None:
+        """checkpoint.checkpoint_option.save; ValueError for variant="dot" before anything is read, written or created"""
+        refuse_dot(self, "save: the checkpoint file has no version for this variant yet")
+        checkpoint_option.save(self, ctx, path, optimizer)
+
+    def load(self, ctx, path: str) -> None:
+        """checkpoint.checkpoint_option.load; ValueError for variant="dot" before the file is opened"""
+        refuse_dot(self, "load: the checkpoint file has no version for this variant yet")
+        checkpoint_option.load(self, ctx, path)
+
+    def _write_checkpoint(self, ctx, path: str, tensors, optimizer: bool, step: int) -> None:
+        refuse_dot(self, "checkpoint file (model_selector.save_best included): it has no version for this variant yet")
+        checkpoint_option._write_checkpoint(self, ctx, path, tensors, optimizer, step)
 
     # the model-level plumbing is gcn's, word for word: it only touches what the two classes share (loss_layer, layers_,
     # loss, A, _out_width and the calls above)

@@ -742,6 +742,90 @@ def gatv2_backward_src_rec(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_
         G.buffer(), G.m(), heads, width // heads, slope, gzs, ldgzs))
 
 
+def _gatdot_third(M: dn_matrix, width: int, third: int, what: str):
+    """(pointer, leading dimension) of a dense operand of the dot-product attention calls: ``M`` is either the
+    [rows x width] matrix itself or the model's [rows x 3 width] buffer, whose columns [0, width) are the query third
+    (third 0: Zq, G_Zq), [width, 2 width) the key third (1: Zk, G_Zk) and [2 width, 3 width) the value third (2: Zv, G_Zv)"""
+    _req(M.m() in (width, 3 * width), f"{what}: an operand of {M.m()} columns is neither {width} nor 3 x {width} wide")
+    return (M.buffer(), width) if M.m() == width else (M.buffer() + 4 * width * third, 3 * width)
+
+
+def _gatdot_width(out: dn_matrix, heads: int, what: str) -> int:
+    check_gat_heads(heads, out.m(), what)
+    return out.m()
+
+
+def gatdot_scale(dh: int) -> float:
+    """c = fp32(1 / sqrt(dh)): the default ``scale`` of the dot-product attention calls"""
+    return float(np.float32(1 / np.sqrt(dh)))
+
+
+def gatdot_forward(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv: dn_matrix, out: dn_matrix, lse: dn_matrix,
+                   heads: int, scale: Optional[float] = None, timer: Optional[str] = None) -> None:
+    """The dot-product edge-softmax fused with the score and the gather (mggcn_gatdot_forward_f32): over F's pattern,
+    e_ijk = scale (Zq[i, head k] . Zk[j, head k]), lse[i, k] = log sum_j exp(e_ijk) and out[i, head k] =
+    sum_j alpha_ijk Zv[j, head k].  F: destinations x sources; out: [F.n() x width]; lse: [F.n() x heads]; ``scale``: None
+    for fp32(1 / sqrt(width / heads)).  Zq (one row per destination), Zk and Zv (one row per source) are [rows x width]
+    matrices, or the model's [rows x 3 width] buffer, of which Zq takes columns [0, width), Zk [width, 2 width) and Zv
+    [2 width, 3 width) -- the same buffer may be passed as all three."""
+    what = "gatdot forward"
+    width = _gatdot_width(out, heads, what)
+    _req(F.n() == Zq.n() and F.m() == Zk.n() and F.m() == Zv.n() and out.n() == F.n(), f"{what}: shape mismatch")
+    _req(lse.shape() == (F.n(), heads), f"{what}: lse must be rows x heads")
+    (zq, ldq), (zk, ldk), (zv, ldv) = (_gatdot_third(Zq, width, 0, what), _gatdot_third(Zk, width, 1, what),
+                                       _gatdot_third(Zv, width, 2, what))
+    scale = gatdot_scale(width // heads) if scale is None else float(scale)
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_forward_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zq, ldq, zk, ldk, zv, ldv, heads, width // heads, scale,
+        out.buffer(), out.m(), lse.buffer()))
+
+
+def gatdot_backward_dst(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv: dn_matrix, lse: dn_matrix, G: dn_matrix,
+                        out: dn_matrix, D: dn_matrix, G_Zq: dn_matrix, heads: int, scale: Optional[float] = None,
+                        timer: Optional[str] = None) -> None:
+    """The half of the dot-product backward pass that sums over sources, over F's rows (mggcn_gatdot_backward_dst_f32):
+    D[i, k] = G[i, head k] . out[i, head k], ds_ijk = alpha_ijk (G[i, head k] . Zv[j, head k] - D[i, k]) and
+    G_Zq[i, head k] = scale sum_j ds_ijk Zk[j, head k].  Zq, Zk, Zv, scale as gatdot_forward takes them; G_Zq: [F.n() x
+    width], or the [F.n() x 3 width] gradient buffer whose columns [0, width) are written."""
+    what = "gatdot backward"
+    width = _gatdot_width(out, heads, what)
+    _req(F.n() == Zq.n() and F.m() == Zk.n() and F.m() == Zv.n() and out.n() == F.n() and G.shape() == out.shape()
+         and G_Zq.n() == F.n(), f"{what}: shape mismatch")
+    _req(lse.shape() == (F.n(), heads) and D.shape() == (F.n(), heads), f"{what}: lse and D must be rows x heads")
+    (zq, ldq), (zk, ldk), (zv, ldv), (gzq, ldgzq) = (_gatdot_third(Zq, width, 0, what), _gatdot_third(Zk, width, 1, what),
+                                                     _gatdot_third(Zv, width, 2, what), _gatdot_third(G_Zq, width, 0, what))
+    scale = gatdot_scale(width // heads) if scale is None else float(scale)
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_backward_dst_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zq, ldq, zk, ldk, zv, ldv, lse.buffer(), G.buffer(), G.m(),
+        out.buffer(), out.m(), heads, width // heads, scale, D.buffer(), gzq, ldgzq))
+
+
+def gatdot_backward_src(ctx: context, F_T: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv: dn_matrix, lse: dn_matrix,
+                        D: dn_matrix, G: dn_matrix, G_Zk: dn_matrix, G_Zv: dn_matrix, heads: int,
+                        scale: Optional[float] = None, timer: Optional[str] = None) -> None:
+    """The half that sums over destinations, over the rows of F^T (mggcn_gatdot_backward_src_f32; after gatdot_backward_dst,
+    whose D it reads): G_Zk[j, head k] = scale sum_i ds_ijk Zq[i, head k] and G_Zv[j, head k] = sum_i alpha_ijk G[i, head k].
+    F_T: sources x destinations; G: [F_T.m() x width]; Zq, Zk, Zv, scale as gatdot_forward takes them; G_Zk, G_Zv:
+    [F_T.n() x width] each, or the [F_T.n() x 3 width] gradient buffer whose columns [width, 2 width) and [2 width, 3 width)
+    are written -- the same buffer may be passed as both."""
+    what = "gatdot backward"
+    width = _gatdot_width(G, heads, what)
+    _req(F_T.m() == Zq.n() and F_T.n() == Zk.n() and F_T.n() == Zv.n() and G.n() == F_T.m() and G_Zk.n() == F_T.n()
+         and G_Zv.n() == F_T.n(), f"{what}: shape mismatch")
+    _req(lse.shape() == (F_T.m(), heads) and D.shape() == (F_T.m(), heads), f"{what}: lse and D must be rows x heads")
+    _req(G_Zk is not G_Zv or G_Zk.m() == 3 * width, f"{what}: G_Zk and G_Zv must not be the same [rows x width] matrix")
+    (zq, ldq), (zk, ldk), (zv, ldv) = (_gatdot_third(Zq, width, 0, what), _gatdot_third(Zk, width, 1, what),
+                                       _gatdot_third(Zv, width, 2, what))
+    (gzk, ldgzk), (gzv, ldgzv) = _gatdot_third(G_Zk, width, 1, what), _gatdot_third(G_Zv, width, 2, what)
+    scale = gatdot_scale(width // heads) if scale is None else float(scale)
+    ip, ix, _ = F_T.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_backward_src_f32(
+        ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), zq, ldq, zk, ldk, zv, ldv, lse.buffer(), D.buffer(),
+        G.buffer(), G.m(), heads, width // heads, scale, gzk, ldgzk, gzv, ldgzv))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
