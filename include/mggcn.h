@@ -60,7 +60,7 @@ void mggcn_device_synchronize(void);
 mggcn_stream_t mggcn_stream_create(int high_priority);
 void mggcn_stream_destroy(mggcn_stream_t stream);
 /* Frees the per-(device, stream) reduction scratch that mggcn_abssum_f32 / the fused loss, and the partials that
- * mggcn_layer_norm_backward_f32 and mggcn_gat_scores_backward_f32, allocate on first use (synchronises that stream).  mggcn_stream_destroy calls it; a
+ * mggcn_layer_norm_backward_f32, mggcn_gated_skip_backward_f32 and mggcn_gat_scores_backward_f32, allocate on first use (synchronises that stream).  mggcn_stream_destroy calls it; a
  * host layer that brings its own streams (e.g. torch's) calls it when it drops one. */
 void mggcn_stream_release_scratch(mggcn_stream_t stream);
 void mggcn_stream_synchronize(mggcn_stream_t stream);
@@ -330,6 +330,38 @@ void mggcn_layer_norm_forward_f32(mggcn_stream_t stream, const float *x, float *
 void mggcn_layer_norm_backward_f32(mggcn_stream_t stream, const float *G, const float *act, const float *xhat,
                                    const float *rstd, const float *gamma, float *G_in, float *G_gamma, float *G_beta,
                                    size_t n_rows, size_t m, uint32_t flags);
+/* The skip connection of an attention layer (opt-in; PyG's GATConv(residual=True) and TransformerConv(beta=True)), row by
+ * row over [n_rows x m] operands, 1 <= m <= MGGCN_GS_MAX_WIDTH.  o is the attention output, r the skip linear's output, w
+ * the gate's parameter ([3 x m] contiguous), gate one float per row.  Forward:
+ *   without MGGCN_GS_GATE  t = o + r
+ *   with    MGGCN_GS_GATE  s = sum_c (w[0,c] o[c] + w[1,c] r[c] + w[2,c] (o[c] - r[c]));  g = 1 / (1 + exp(-s));
+ *                          t = g r + (1 - g) o;  gate[row] = g
+ *   y = flags & MGGCN_GS_LEAKY_RELU ? leaky_relu(t, 0.01) : t
+ * Backward, with dy = flags & MGGCN_GS_LEAKY_RELU ? (act > 0 ? G : 0.01 G) : G  (act is a sign source only -- the forward's y
+ * -- and may be null without the flag):
+ *   without MGGCN_GS_GATE  G_o = G_r = dy  (o, r, w, gate and G_w are not read or written and may be null)
+ *   with    MGGCN_GS_GATE  dg = sum_c dy[c] (r[c] - o[c]);  ds = dg g (1 - g);
+ *                          G_o[c] = (1 - g) dy[c] + ds (w[0,c] + w[2,c]);  G_r[c] = g dy[c] + ds (w[1,c] - w[2,c]);
+ *                          G_w[0,c] = sum_i ds_i o_i[c];  G_w[1,c] = sum_i ds_i r_i[c];  G_w[2,c] = sum_i ds_i (o_i[c] - r_i[c])
+ * Every [n_rows x m] operand has a leading dimension of its own (ld >= m), so r may be a column block of a wider matrix.
+ * The sigmoid is evaluated from exp(-|s|): no finite s gives NaN, and g is exactly 1 or 0 where fp32 saturates (then ds = 0).
+ * Aliasing: y aliases neither o nor r (the backward pass reads both).  G_o may be G or act.  Without MGGCN_GS_GATE G_r may be
+ * G_o (one store); with it G_r is distinct from every other operand and G_o from o and r.  w and gate need the flag and
+ * are null without it; with it they and G_w must not be null.
+ * A row's y, gate, G_o and G_r depend on that row alone: rows [a, b) alone give the bits they have in the whole call, for
+ * the same width and alignment (m % 4 == 0 with every operand 16-byte aligned and every leading dimension a multiple of 4
+ * takes a float4 path, anything else an element path).  G_w uses no atomics: per-workgroup partials in the per-(device,
+ * stream) scratch of mggcn_layer_norm_backward_f32 are added in a fixed order, so the same arguments give the same bits on
+ * every call.  n_rows == 0 launches nothing in the forward; the backward still writes zeros to G_w (with MGGCN_GS_GATE). */
+#define MGGCN_GS_GATE 1u
+#define MGGCN_GS_LEAKY_RELU 2u
+#define MGGCN_GS_MAX_WIDTH 1024u
+void mggcn_gated_skip_forward_f32(mggcn_stream_t stream, const float *o, size_t ldo, const float *r, size_t ldr,
+                                  const float *w, float *y, size_t ldy, float *gate, size_t n_rows, size_t m, uint32_t flags);
+void mggcn_gated_skip_backward_f32(mggcn_stream_t stream, const float *G, size_t ldg, const float *act, size_t lda,
+                                   const float *o, size_t ldo, const float *r, size_t ldr, const float *w, const float *gate,
+                                   float *G_o, size_t ldgo, float *G_r, size_t ldgr, float *G_w, size_t n_rows, size_t m,
+                                   uint32_t flags);
 /* Graph attention (GAT; opt-in, the reference has no attention layer).  F is a CSR PATTERN of n_rows destinations x n_cols
  * sources (u32 indptr / indices on the device; there is no values array, and a duplicate (i, j) entry counts as two edges),
  * K = heads, dh = width per head, 1 <= K <= MGGCN_GAT_MAX_HEADS and K * dh <= MGGCN_GAT_MAX_WIDTH; head k owns columns

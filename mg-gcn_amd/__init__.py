@@ -11,7 +11,8 @@ Layout:
   ops.py       matmul / get_matmul_buffer / kernels     (reference src/cuda_utils.hpp)
   gcn.py       sparse_linear / linear / gcn_layer / gcn (reference src/gcn.hpp)
   gat.py       attention / gat_layer / gat: graph attention layers, GAT and (variant="v2": attention_v2 / gatv2_layer)
-               GATv2 and (variant="dot": attention_dot / gatdot_layer) dot-product attention (no reference counterpart)
+               GATv2 and (variant="dot": attention_dot / gatdot_layer) dot-product attention; gated_skip: the skip
+               connection and gate of skip="add" | "gate" (no reference counterpart)
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*)
   dist_gat.py  dist_attention / dist_gat_layer / dist_gat (and the _v2 / gatv2 twins): gat on the row partition (exported by dist)
   datasets.py  on-disk format + synthetic generators    (reference test/data/prep.py); the checkpoint file
@@ -26,7 +27,7 @@ from . import ops                                               # noqa: F401
 from .ops import get_matmul_buffer, matmul                      # noqa: F401
 from .gcn import (gcn, gcn_layer, linear, softmax, softmax_cross_entropy_loss,  # noqa: F401
                   sparse_linear)
-from .gat import attention, attention_dot, attention_v2, gat, gat_layer, gatdot_layer, gatv2_layer  # noqa: F401
+from .gat import attention, attention_dot, attention_v2, gat, gat_layer, gatdot_layer, gated_skip, gatv2_layer  # noqa: F401
 
 from . import dist                                              # noqa: F401
 from .dist import (dist_context, dist_gcn, dist_gcn_layer, dist_row_csr_matrix,  # noqa: F401
@@ -37,4 +38,4 @@ from .selection import model_selector                           # noqa: F401
 
 __all__ = ["context", "csr_matrix", "dn_matrix", "matrix_error", "engine_error", "ops", "matmul",
            "get_matmul_buffer", "sparse_linear", "linear", "gcn_layer", "softmax",
-           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "datasets", "model_selector"]
+           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "datasets", "model_selector"]

@@ -95,7 +95,11 @@ PROTOTYPES = {
     "mggcn_dropout_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_uint64, c_uint32, c_float, c_uint64, c_uint32]),
     "mggcn_layer_norm_forward_f32": (None, [vp, vp, vp, vp, vp, vp, vp, c_size_t, c_size_t, c_float, c_uint32]),
     "mggcn_layer_norm_backward_f32": (None, [vp, vp, vp, vp, vp, vp, vp, vp, vp, c_size_t, c_size_t, c_uint32]),
-    "mggcn_gat_scores_f32": (None, [vp, vp, c_size_t, vp, vp, vp, c_size_t, c_uint32, c_uint32]),
+    "mggcn_gated_skip_forward_f32": (None, [vp, vp, c_size_t, vp, c_size_t, vp, vp, c_size_t, vp, c_size_t, c_size_t,
+                                            c_uint32]),
+    "mggcn_gated_skip_backward_f32": (None, [vp, vp, c_size_t, vp, c_size_t, vp, c_size_t, vp, c_size_t, vp, vp, vp,
+                                             c_size_t, vp, c_size_t, vp, c_size_t, c_size_t, c_uint32]),
+    "mggcn_gat_scores_f32":(None, [vp, vp, c_size_t, vp, vp, vp, c_size_t, c_uint32, c_uint32]),
     "mggcn_gat_forward_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, c_uint32, c_uint32, c_float, vp,
                                      c_size_t, vp]),
     "mggcn_gat_backward_dst_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, vp, c_size_t, vp,

@@ -33,11 +33,13 @@ def model_params(model) -> List[tuple]:
     out = []
     for l, layer in enumerate(model.layers_):
         out += [(f"W{l}", layer.lin, "W", "mW", "vW"), (f"b{l}", layer.lin, "b", "mb", "vb")]
-        attn, res_lin, norm = (getattr(layer, a, None) for a in ("attn", "res_lin", "norm"))
+        attn, res_lin, gate, norm = (getattr(layer, a, None) for a in ("attn", "res_lin", "gate", "norm"))
         if attn is not None and attn.att is not None:           # gat.attention_dot has no parameter
             out += [(f"att{l}", attn, "att", "m", "v")]
         if res_lin is not None:
             out += [(f"res_W{l}", res_lin, "W", "mW", "vW"), (f"res_b{l}", res_lin, "b", "mb", "vb")]
+        if gate is not None:                                    # gat.gated_skip with skip="gate"
+            out += [(f"gate{l}", gate, "w", "m", "v")]
         if norm is not None:
             out += [(f"gamma{l}", norm, "gamma", "mg", "vg"), (f"beta{l}", norm, "beta", "mb", "vb")]
     return out

@@ -1,11 +1,12 @@
 // scratch_internal.h -- the per-(device, stream) scratch for per-workgroup partials of the reduction tree (reduce.h), owned
-// by runtime.hip and used by elementwise.hip and gat.hip.  Not part of the ABI.
+// by runtime.hip and used by elementwise.hip, gat.hip and gated_skip.hip.  Not part of the ABI.
 #pragma once
 
 #include "common.h"
 
 // sums: the scalar partials ([workgroup][value]) of a kernel that ends in block_fold, always asked for at one size;
-// colsums: the column partials ([workgroup][width]) of the layer norm's and the GAT's backward, which grow with the width.
+// colsums: the column partials ([workgroup][width]) of the layer norm's, the GAT's and the gated skip's backward, which grow
+// with the width.
 // Two buffers, so that a wider column sum never moves the scalars' buffer.
 enum class scratch_kind { sums, colsums };
 

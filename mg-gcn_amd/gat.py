@@ -62,7 +62,24 @@ the layer type -- variant, heads, attn_slope, the attention dropout probability 
 (version 3 of the checkpoint file, INTEGRATION.md "Checkpoint file"), and a resumed run is the uninterrupted run bit for bit
 (DESIGN.md 3.10.6).  Nothing is allocated or launched unless one of these is called.
 
-Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, layer norm, bf16 gathers.
+``skip="add" | "gate"`` and ``norm="layer"`` (both None by default: nothing new is launched or allocated) put a skip
+connection and a layer normalisation after the aggregation of every variant -- attention -> skip -> norm -> activation:
+
+    r = H W_r + 1 b_r^T                               (``res_lin``: always a linear, PyG's lin_skip; H is what lin reads)
+    "add":  y = out + r                               (GATConv(residual=True))
+    "gate": g_i = sigmoid(sum_c (w[0,c] out[i,c] + w[1,c] r[i,c] + w[2,c] (out[i,c] - r[i,c])));  y = g r + (1 - g) out
+                                                      (TransformerConv(beta=True); w [3 x out], no bias, one g per row)
+    norm:   y <- layer_norm(y) with gamma, beta       (gcn's: every layer but the last)
+
+and the layer's leaky ReLU rides in whichever of the two kernels runs last (csrc/gated_skip.hip: mggcn_gated_skip_*; the
+norm's are gcn's).  With variant="dot", skip="gate", norm="layer" a layer is the UniMP / graph-transformer block.  W_r and
+b_r are trained like any linear's, w with W's weight decay, gamma and beta with none; ``skip_weights=`` takes (W_r, b_r) or
+(W_r, b_r, w) per layer, ``layer.res_lin``, ``layer.gate`` (``.w``, the rows' ``.gate``) and ``layer.norm`` hold them.
+Refused with ValueError before anything is created, read or written: save, load and model_selector.save_best on a model
+with either option (the checkpoint file has no version that stores them; the selector's in-memory restore works), and
+dist_gat does not take the arguments.
+
+Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, bf16 gathers.
 """
 from __future__ import annotations
 
@@ -72,8 +89,8 @@ import numpy as np
 
 from . import _lib, ops
 from .checkpoint import checkpoint_option
-from .gcn import (DROPOUT_MAX_LAYERS, adam_update_all, check_dropout, check_loss, dropout_option, gcn, linear,
-                  sigmoid_bce_loss, softmax_cross_entropy_loss)
+from .gcn import (DROPOUT_MAX_LAYERS, adam_update_all, check_dropout, check_loss, check_norm, dropout_option, gcn,
+                  layer_norm, linear, sigmoid_bce_loss, softmax_cross_entropy_loss)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -195,30 +212,169 @@ class attention_v2(attention):
                                n + "1_gatv2-backward-src")
 
 
+SKIPS = (None, "add", "gate")
+
+
+def check_skip(skip):
+    """option checking of skip=, before any device work: None (no skip connection), "add" or "gate" """
+    if skip not in SKIPS:
+        raise ValueError(f"skip must be one of {SKIPS}, not {skip!r}")
+    return skip
+
+
+def check_skip_weights(skip, skip_weights, n_layers: int) -> None:
+    """``skip_weights=`` of gat: per layer (W_r, b_r), or (W_r, b_r, w_gate) with skip="gate"; ValueError otherwise.  No
+    device work."""
+    if skip_weights is None:
+        return
+    if skip is None:
+        raise ValueError("skip_weights needs skip=\"add\" or skip=\"gate\"")
+    if len(skip_weights) != n_layers:
+        raise ValueError(f"skip_weights lists {len(skip_weights)} layers, the model has {n_layers}")
+    for li, w in enumerate(skip_weights):
+        if len(w) not in ((2, 3) if skip == "gate" else (2,)):
+            raise ValueError(f"skip_weights of layer {li}: skip=\"{skip}\" takes (W_r, b_r"
+                             + (", w_gate)" if skip == "gate" else ")") + f", got {len(w)} tensors")
+
+
+def refuse_skip(model, what: str) -> None:
+    """ValueError naming the option when ``model`` has a skip connection or a layer norm: ``what`` is a member such a model
+    does not have yet (read with getattr: a model built without __init__ has neither)"""
+    for option in ("skip", "norm"):
+        value = getattr(model, option, None)
+        if value is not None:
+            raise ValueError(f'gat({option}="{value}") has no {what}')
+
+
+class gated_skip:
+    """The skip connection of one attention layer (gat(skip=...)): ``res_lin``, a linear r = H W_r + 1 b_r^T over the
+    layer's own input -- always a linear, also where in == out (PyG's lin_skip) --, and the row kernels of
+    csrc/gated_skip.hip that combine r with the attention output o: y = o + r ("add"), or y = g r + (1 - g) o with one
+    g = sigmoid(sum_c (w[0] o + w[1] r + w[2] (o - r))) per row ("gate": TransformerConv(beta=True); no bias in the gate).
+    "gate" holds the parameter ``w`` [3 x out] (seed-99 uniform like att), its gradient and Adam state -- a row of the
+    fused Adam table with W's weight decay -- and the rows' ``gate`` [n], which the backward pass reads again.  ``r`` is
+    kept per layer with the gate (its backward needs it) and lives in ``buffer`` (the model's, at its widest layer) without;
+    ``G_r`` aliases ``buffer`` with the gate and is the layer's G_o without (one store)."""
+
+    def __init__(self, name: str, n: int, in_: int, out: int, mode: str, backward_out: bool = True, buffer=None, device=None):
+        assert mode in ("add", "gate")
+        self.name, self.mode = name, mode
+        self.res_lin = linear(name, in_, out, backward_out, True)
+        shared = dn_matrix(n, out, buffer) if buffer is not None else dn_matrix(n, out, device=device)
+        self.w = self.G_w = self.gate = self.G_r = self.m = self.v = None
+        self.step = 0
+        if mode == "gate":
+            self.r, self.G_r = dn_matrix(n, out, device=device), shared
+            self.w, self.G_w = dn_matrix(3, out, device=device), dn_matrix(3, out, device=device)
+            host = np.empty((3, out), dtype=np.float32)
+            _lib.load().mggcn_init_uniform_host(host.ctypes.data, out, 3, -1.0)
+            self.w.init(host)
+            self.gate = dn_matrix(n, 1, device=device)
+        else:
+            self.r = shared
+
+    def flags(self, leaky: bool) -> int:
+        return (ops.GATED_SKIP_GATE if self.mode == "gate" else 0) | (ops.GATED_SKIP_LEAKY_RELU if leaky else 0)
+
+    def __call__(self, ctx: context, H: dn_matrix, o: dn_matrix, y: dn_matrix, leaky: bool) -> None:
+        """y = [leaky_relu](skip(o, H W_r + b_r))"""
+        n = self.name
+        self.res_lin(ctx, H, self.r)
+        ctx.record(n + "0_0_skip", 0)
+        ops.gated_skip(ctx, o, self.r, self.w, y, self.gate, self.flags(leaky))
+        ctx.record(n + "0_1_skip", 0)
+        ctx.register_timer(n + "0_skip", n + "0_0_skip", n + "0_1_skip")
+
+    def backward(self, ctx: context, G: dn_matrix, act: Optional[dn_matrix], o: dn_matrix, G_o: dn_matrix) -> dn_matrix:
+        """G_o = the gradient of o and, returned, the gradient of r (G_o itself without the gate), and G_w; ``act``: apply
+        leaky_relu'(act) to G first.  G_o may be G or act."""
+        n = self.name
+        gated = self.mode == "gate"
+        G_r = self.G_r if gated else G_o
+        ctx.record(n + "1_0_skip", 0)
+        ops.gated_skip_backward(ctx, G, act, o if gated else None, self.r if gated else None, self.w, self.gate, G_o, G_r,
+                                self.G_w, self.flags(act is not None))
+        ctx.record(n + "1_1_skip", 0)
+        ctx.register_timer(n + "1_skip", n + "1_0_skip", n + "1_1_skip")
+        return G_r
+
+    def init(self, w) -> None:
+        if self.mode != "gate":
+            raise ValueError('gat(skip="add") has no gate parameter: skip_weights= takes (W_r, b_r) per layer')
+        self.w.init(np.asarray(w, dtype=np.float32))
+
+    # the Adam rows of the gate's parameter (res_lin is a linear of its own in the layer's params())
+    def adam_state(self, ctx: context) -> None:
+        if self.m is None:
+            dev = self.w.t.device
+            self.m, self.v = dn_matrix(self.w.shape(), device=dev), dn_matrix(self.w.shape(), device=dev)
+            self.m.zero(ctx)
+            self.v.zero(ctx)
+            self.step = 0
+
+    def adam_tensors(self, weight_decay: float):
+        """row of ops.adam_table: w decays like W"""
+        return [(self.w, self.G_w, self.m, self.v, weight_decay)]
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
+        """one launch for this tensor: the element-wise math of the model-wide table, bit for bit"""
+        self.adam_state(ctx)
+        self.step += 1
+        bc1 = float(np.float32(1 - beta1 ** self.step))
+        bc2 = float(np.float32(1 - beta2 ** self.step))
+        ops.adam_fused(ctx, self.w, self.G_w, self.m, self.v, lr, beta1, beta2, weight_decay, bc1, bc2, eps)
+
+
+class gat_layer_norm(layer_norm):
+    """gcn.layer_norm as the attention layers use it: the same kernels, buffers and Adam rows (no weight decay); only the
+    per-tensor Adam step (gat(fused=False)) differs -- one ops.adam_fused per tensor, the element-wise math of the
+    model-wide table bit for bit, as for every other parameter of a gat model (gcn's own per-tensor step is the
+    reference's unfused chain, which rounds differently)."""
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
+        self.adam_state(ctx)
+        self.step += 1
+        bc1 = float(np.float32(1 - beta1 ** self.step))
+        bc2 = float(np.float32(1 - beta2 ** self.step))
+        for p, g, m, v, wd in self.adam_tensors(weight_decay):
+            ops.adam_fused(ctx, p, g, m, v, lr, beta1, beta2, wd, bc1, bc2, eps)
+
+
 class gat_layer:
     """One GAT layer: a ``linear`` (Z = H W + 1 b^T), an ``attention`` over (F, F^T) and the activation.  Z, the
     aggregated ``out`` (before the activation: the backward pass needs it) and the activated output are kept per layer;
     G_Z aliases the model-wide buffer.  ``backward_out=False`` (the first layer) skips the GEMM that only produces the
-    gradient of the layer's input."""
+    gradient of the layer's input.  ``skip`` ("add" | "gate") puts a ``gated_skip`` after the aggregation and ``norm``
+    ("layer") a gcn.layer_norm after that, in every layer that has an activation: attention -> skip -> norm -> activation,
+    the activation fused into whichever of the two runs last.  The attributes are ``res_lin`` (the skip's linear), ``gate``
+    (the skip itself where it has the gate parameter) and ``norm``, each None where the layer has none."""
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
-                 slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None):
+                 slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None,
+                 skip_buffer=None):
         n = F.n()
         assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
         # the linear's own fused kernels in every mode: gat(fused=...) only picks how Adam is launched
         self._setup(name, F, F_T, linear(name, in_, out, backward_out, True), attention(name, n, n, out, heads, slope), n, in_,
-                    out, activation, G_Z_buffer)
+                    out, activation, G_Z_buffer, skip=skip, norm=norm, skip_buffer=skip_buffer)
 
     def _setup(self, name: str, F: csr_matrix, F_T: csr_matrix, lin, attn, rows: int, in_: int, out: int, activation: bool,
-               G_Z_buffer=None, device=None, row0: int = 0, z_width: Optional[int] = None) -> None:
+               G_Z_buffer=None, device=None, row0: int = 0, z_width: Optional[int] = None, skip=None, norm=None,
+               skip_buffer=None) -> None:
         """everything a layer holds besides building ``lin`` and ``attn``: its buffers over ``rows`` rows and the per-forward
         state (the row-partitioned layer, dist_gat.dist_gat_layer, calls it with its rank's pieces); ``z_width``: the columns
-        of Z and G_Z where they are not ``out`` (gatv2_layer: 2 out)"""
+        of Z and G_Z where they are not ``out`` (gatv2_layer: 2 out); ``skip`` / ``norm`` / ``skip_buffer``: the gated_skip
+        (its model-wide buffer) and the layer norm, None for a layer without"""
         self.name, self.F, self.F_T, self.activation = name, F, F_T, bool(activation)
         self.lin, self.attn = lin, attn
         zw = out if z_width is None else int(z_width)
         self.Z, self.out = dn_matrix(rows, zw, device=device), dn_matrix(rows, out, device=device)
-        self.act = dn_matrix(rows, out, device=device) if activation else self.out
+        self.skip = gated_skip(name, rows, in_, out, skip, lin.backward_out, skip_buffer, device) if skip is not None else None
+        self.res_lin = self.skip.res_lin if self.skip is not None else None
+        self.gate = self.skip if skip == "gate" else None
+        self.norm = gat_layer_norm(name, rows, out, True, device) if norm == "layer" and activation else None
+        # the layer's output y: the last layer has no activation and returns ``out`` itself, unless a skip writes a y
+        self.act = dn_matrix(rows, out, device=device) if activation or self.skip is not None else self.out
         self.G_Z = dn_matrix(rows, zw, G_Z_buffer) if G_Z_buffer is not None else dn_matrix(rows, zw, device=device)
         self.G_out = dn_matrix(rows, in_, device=device) if lin.backward_out else None
         self.H: Optional[dn_matrix] = None
@@ -248,7 +404,14 @@ class gat_layer:
         self.H = H
         self.lin(ctx, H, self.Z)
         self.attn(ctx, self.F, self.Z, self.out, self.attn_dropout)
-        if self.activation:
+        if self.skip is not None or self.norm is not None:
+            # attention -> skip -> norm -> activation; ``out`` stays as the attention wrote it (its backward reads it), y
+            # goes to ``act``, the norm runs in place there, and the activation rides in whichever of the two runs last
+            if self.skip is not None:
+                self.skip(ctx, H, self.out, self.act, self.activation and self.norm is None)
+            if self.norm is not None:
+                self.norm(ctx, self.act if self.skip is not None else self.out, True, self.act)
+        elif self.activation:
             ctx.record(n + "0_0_activation", 0)
             ops.leaky_relu_forward(ctx, self.out, self.act)
             ctx.record(n + "0_1_activation", 0)
@@ -257,8 +420,20 @@ class gat_layer:
 
     def backward(self, ctx: context, G: dn_matrix) -> Optional[dn_matrix]:
         n = self.name
-        T = G
-        if self.activation:
+        T, G_r = G, None
+        if self.skip is not None or self.norm is not None:
+            # The sign source of the fused activation is the activated output ``act``, as in gcn and the layer norm.  The
+            # layer above may have dropped that buffer in place: a kept element keeps its sign (the scale is positive), and a
+            # dropped one is 0 here and carries a zero gradient (the layer above dropped its G_out with the same mask), so
+            # either branch of leaky_relu' gives 0.  Every gradient lands in ``act``, which the layer above has finished with.
+            sign = self.act if self.activation else None
+            if self.norm is not None:
+                self.norm.backward(ctx, G, sign, self.act)
+                T, sign = self.act, None
+            if self.skip is not None:
+                G_r = self.skip.backward(ctx, T, sign, self.out, self.act)
+                T = self.act
+        elif self.activation:
             # the sign source is the aggregated output itself; T lands in the activated output's buffer, which the layer
             # above has finished with (its G_W GEMM read it earlier on this stream)
             ctx.record(n + "1_0_activation", 0)
@@ -269,6 +444,9 @@ class gat_layer:
         self.attn.backward(ctx, self.F, self.F_T, self.Z, T, self.out, self.G_Z, self.attn_dropout)
         self.lin.setX(self.H)
         self.lin.backward(ctx, self.G_Z, self.G_out)
+        if G_r is not None:                                  # the skip branch adds its share of the input's gradient
+            self.res_lin.setX(self.H)
+            self.res_lin.backward(ctx, G_r, self.G_out, False)
         if self.dropout is not None and self.G_out is not None:
             self._drop(ctx, self.G_out, "1")
         return self.G_out
@@ -291,9 +469,13 @@ class gat_layer:
     def linears(self):
         return [self.lin]
 
+    def _skip_params(self):
+        """res_lin, gate and norm where the layer has them (read with getattr: a layer built without _setup has none)"""
+        return [p for p in (getattr(self, a, None) for a in ("res_lin", "gate", "norm")) if p is not None]
+
     def params(self):
         """everything Adam updates"""
-        return [self.lin, self.attn]
+        return [self.lin, self.attn] + self._skip_params()
 
     def adam_update(self, ctx, lr, beta1, beta2, weight_decay, eps):
         for p in self.params():
@@ -314,11 +496,13 @@ class gatv2_layer(gat_layer):
     GEMMs over 2 out columns; everything else is gat_layer's, word for word."""
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
-                 slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, P_buffer=None):
+                 slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, P_buffer=None, skip=None,
+                 norm=None, skip_buffer=None):
         n = F.n()
         assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
         self._setup(name, F, F_T, linear(name, in_, 2 * out, backward_out, True),
-                    attention_v2(name, n, out, heads, slope, P_buffer), n, in_, out, activation, G_Z_buffer, z_width=2 * out)
+                    attention_v2(name, n, out, heads, slope, P_buffer), n, in_, out, activation, G_Z_buffer, z_width=2 * out,
+                    skip=skip, norm=norm, skip_buffer=skip_buffer)
 
 
 class attention_dot:
@@ -371,17 +555,17 @@ class gatdot_layer(gat_layer):
     [G_Zq | G_Zk | G_Zv] (aliasing the model-wide buffer); the layer's parameters are the linear's alone."""
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
-                 backward_out: bool = True, G_Z_buffer=None):
+                 backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None, skip_buffer=None):
         n = F.n()
         assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
         self._setup(name, F, F_T, linear(name, in_, 3 * out, backward_out, True), attention_dot(name, n, out, heads), n, in_,
-                    out, activation, G_Z_buffer, z_width=3 * out)
+                    out, activation, G_Z_buffer, z_width=3 * out, skip=skip, norm=norm, skip_buffer=skip_buffer)
 
     def alpha(self, ctx: context, out: Optional[dn_matrix] = None) -> dn_matrix:
         raise ValueError(f'gat layer {self.name}: gat(variant="dot") has no export of the attention coefficients')
 
     def params(self):
-        return [self.lin]
+        return [self.lin] + self._skip_params()
 
 
 VARIANTS = ("v1", "v2", "dot")
@@ -415,13 +599,15 @@ class gat(dropout_option, checkpoint_option):
     """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
 
     gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
-    variant="v1"):
+    variant="v1", skip=None, norm=None, skip_weights=None):
     ``A`` as ``gcn`` takes it (the layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
     (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att);
     ``variant``: "v1" (this model as it always was) or "v2" (GATv2, see the module docstring: W is [in x 2 out], b
     [1 x 2 out], att [1 x out]; ValueError for another name, for attn_dropout > 0 and for set_dropout(attn > 0)) or "dot"
     (dot-product attention, see the module docstring: W is [in x 3 out], b [1 x 3 out], no att; the refusals of "v2" plus
-    attention_weights, save, load and rows x 3 out >= 2^31).  ValueError
+    attention_weights, save, load and rows x 3 out >= 2^31); ``skip``: None, "add" or "gate", ``norm``: None or "layer",
+    ``skip_weights``: per layer (W_r, b_r) or (W_r, b_r, w_gate) -- see the module docstring; ValueError for another name or
+    a list that does not fit, and for save / load / save_best on a model that has either.  ValueError
     before any device work for a width that its heads do not divide or a limit of the kernels (ops.GAT_MAX_HEADS,
     ops.GAT_MAX_WIDTH).  ``fused`` picks how Adam is launched -- one launch for every parameter tensor, or one per tensor;
     the element-wise math is the same, so both give the same bits -- and every other kernel is the same in both modes.
@@ -440,11 +626,13 @@ class gat(dropout_option, checkpoint_option):
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
                  loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0,
-                 variant: str = "v1"):
+                 variant: str = "v1", skip=None, norm=None, skip_weights=None):
         self.sizes = [int(s) for s in sizes]
         self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
         self._attn_dropout_params = check_dropout(attn_dropout, len(self.sizes) - 1)
         self.variant = check_variant(variant, float(attn_dropout))
+        self.skip, self.norm = check_skip(skip), check_norm(norm)
+        check_skip_weights(self.skip, skip_weights, len(self.sizes) - 1)
         self._init_dropout(dropout, len(self.sizes) - 1)
         self.attn_dropout_p = float(attn_dropout)
         self.loss = check_loss(loss)
@@ -463,23 +651,36 @@ class gat(dropout_option, checkpoint_option):
         self.loss_layer = loss_class(f"{n_layers}_", True, True)
         self.A, self.A_T = A, A.transpose()                      # forward over A_T's rows, like gcn
         self.layers_: List[gat_layer] = []
+        # the skip's r ("add") or G_r ("gate"), once at the widest layer; the defaults add nothing to a layer's arguments
+        more = {}
+        if self.skip is not None or self.norm is not None:
+            self.skip_buffer = (torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
+                                if self.skip is not None else None)
+            more = dict(skip=self.skip, norm=self.norm, skip_buffer=self.skip_buffer)
         if self.variant == "v2":                                 # G_Z2 = [G_Zs | G_Zd] and P, once at the widest layer
             self.G_Z_buffer = torch.empty(A.n() * 2 * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
             self.P_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
             for i in range(n_layers):
                 self.layers_.append(gatv2_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
-                                                i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer, self.P_buffer))
+                                                i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer, self.P_buffer,
+                                                **more))
         elif self.variant == "dot":                              # G_Z3 = [G_Zq | G_Zk | G_Zv], once at the widest layer
             self.G_Z_buffer = torch.empty(A.n() * 3 * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
             for i in range(n_layers):
                 self.layers_.append(gatdot_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
-                                                 i + 1 < n_layers, i != 0, self.G_Z_buffer))
+                                                 i + 1 < n_layers, i != 0, self.G_Z_buffer, **more))
         else:
             self.G_Z_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
             for i in range(n_layers):
                 self.layers_.append(gat_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
-                                              i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer))
+                                              i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer, **more))
         self._adam = None
+        if skip_weights is not None:
+            for layer, w in zip(self.layers_, skip_weights):
+                layer.res_lin.W.init(np.asarray(w[0], dtype=np.float32))
+                layer.res_lin.b.init(np.asarray(w[1], dtype=np.float32))
+                if len(w) > 2:
+                    layer.skip.init(w[2])
         if weights is not None:
             assert len(weights) == n_layers
             for layer, w in zip(self.layers_, weights):
@@ -577,15 +778,18 @@ class gat(dropout_option, checkpoint_option):
     def save(self, ctx, path: str, optimizer: bool = True) -> None:
         """checkpoint.checkpoint_option.save; ValueError for variant="dot" before anything is read, written or created"""
         refuse_dot(self, "save: the checkpoint file has no version for this variant yet")
+        refuse_skip(self, "save: the checkpoint file has no version that stores this option yet")
         checkpoint_option.save(self, ctx, path, optimizer)
 
     def load(self, ctx, path: str) -> None:
         """checkpoint.checkpoint_option.load; ValueError for variant="dot" before the file is opened"""
         refuse_dot(self, "load: the checkpoint file has no version for this variant yet")
+        refuse_skip(self, "load: the checkpoint file has no version that stores this option yet")
         checkpoint_option.load(self, ctx, path)
 
     def _write_checkpoint(self, ctx, path: str, tensors, optimizer: bool, step: int) -> None:
         refuse_dot(self, "checkpoint file (model_selector.save_best included): it has no version for this variant yet")
+        refuse_skip(self, "checkpoint file (model_selector.save_best included): it has no version that stores this option yet")
         checkpoint_option._write_checkpoint(self, ctx, path, tensors, optimizer, step)
 
     # the model-level plumbing is gcn's, word for word: it only touches what the two classes share (loss_layer, layers_,

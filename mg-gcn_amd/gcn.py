@@ -301,11 +301,12 @@ class layer_norm:
         self.mg = self.vg = self.mb = self.vb = None
         self.step = 0
 
-    def __call__(self, ctx: context, Z: dn_matrix, activation: bool) -> None:
-        """Z = [leaky_relu](layer_norm(Z)) in place"""
+    def __call__(self, ctx: context, Z: dn_matrix, activation: bool, out: Optional[dn_matrix] = None) -> None:
+        """Z = [leaky_relu](layer_norm(Z)) in place, or into ``out`` where Z has to stay (a gat layer's aggregated output)"""
         n = self.name
         ctx.record(n + "0_0_norm", 0)
-        ops.layer_norm(ctx, Z, Z, self.xhat, self.rstd, self.gamma, self.beta, ops.LAYER_NORM_LEAKY_RELU if activation else 0)
+        ops.layer_norm(ctx, Z, Z if out is None else out, self.xhat, self.rstd, self.gamma, self.beta,
+                       ops.LAYER_NORM_LEAKY_RELU if activation else 0)
         ctx.record(n + "0_1_norm", 0)
         ctx.register_timer(n + "0_norm", n + "0_0_norm", n + "0_1_norm")
 

@@ -414,6 +414,69 @@ def layer_norm_backward(ctx: context, G: dn_matrix, act: Optional[dn_matrix], xh
                                           G.n(), G.m(), int(flags))
 
 
+GATED_SKIP_GATE = 1                 # MGGCN_GS_GATE: y = g r + (1 - g) o with g = sigmoid(the row's score); without it y = o + r
+GATED_SKIP_LEAKY_RELU = 2           # MGGCN_GS_LEAKY_RELU: the activation (slope 0.01) rides in the skip kernels
+GATED_SKIP_MAX_WIDTH = 1024         # MGGCN_GS_MAX_WIDTH: a row lives in the registers of at most one wave
+
+
+def _req_gated_skip(o, r, w, gate, flags: int, what: str) -> bool:
+    """the shapes both passes share; shape-only objects are enough.  Returns whether the gate is on."""
+    n, m = o.n(), o.m()
+    _req(int(flags) & ~(GATED_SKIP_GATE | GATED_SKIP_LEAKY_RELU) == 0, f"{what}: unknown flags {int(flags):#x}")
+    _req(1 <= m <= GATED_SKIP_MAX_WIDTH, f"{what} supports 1 <= m <= {GATED_SKIP_MAX_WIDTH} columns, got {m}")
+    gated = bool(int(flags) & GATED_SKIP_GATE)
+    if gated:
+        _req(r is not None and r.shape() == (n, m), f"{what}: r must be {n} x {m}")
+        _req(w is not None and w.shape() == (3, m), f"{what}: w must be 3 x {m}")
+        _req(gate is not None and gate.size() == n, f"{what}: gate must hold {n} floats")
+    else:
+        _req(w is None and gate is None, f"{what}: w and gate need GATED_SKIP_GATE")
+    return gated
+
+
+def gated_skip(ctx: context, o: dn_matrix, r: dn_matrix, w: Optional[dn_matrix], y: dn_matrix, gate: Optional[dn_matrix],
+               flags: int = 0) -> None:
+    """The skip connection of an attention layer, row by row (mggcn_gated_skip_forward_f32): y = o + r, or with
+    flags & GATED_SKIP_GATE y = g r + (1 - g) o, g = sigmoid(sum_c (w[0] o + w[1] r + w[2] (o - r))) written to ``gate`` [n];
+    GATED_SKIP_LEAKY_RELU applies the project's leaky ReLU in the same pass.  o, r, y: [n x m]; w: [3 x m] (None without
+    the gate, and so is ``gate``).  y must be neither o nor r.  ValueError for a width outside 1 .. GATED_SKIP_MAX_WIDTH, a
+    shape mismatch or an alias, before the library is touched (it would print and exit, not raise)."""
+    what = "gated skip"
+    gated = _req_gated_skip(o, r, w, gate, flags, what)
+    _req(r is not None and r.shape() == o.shape() and y.shape() == o.shape(), f"{what}: r and y must have o's shape")
+    _req(y is not o and y is not r, f"{what}: y must not be o or r (the backward pass reads both)")
+    ctx.lib.mggcn_gated_skip_forward_f32(ctx.stream(0), o.buffer(), o.m(), r.buffer(), r.m(), w.buffer() if gated else None,
+                                         y.buffer(), y.m(), gate.buffer() if gated else None, o.n(), o.m(), int(flags))
+
+
+def gated_skip_backward(ctx: context, G: dn_matrix, act: Optional[dn_matrix], o: Optional[dn_matrix], r: Optional[dn_matrix],
+                        w: Optional[dn_matrix], gate: Optional[dn_matrix], G_o: dn_matrix, G_r: dn_matrix,
+                        G_w: Optional[dn_matrix], flags: int = 0) -> None:
+    """The backward pass of gated_skip (mggcn_gated_skip_backward_f32): from G, the gradient of y, the gradients G_o and
+    G_r [n x m] of o and r and, with the gate, G_w [3 x m].  With GATED_SKIP_LEAKY_RELU G is first multiplied by
+    leaky_relu'(act) -- act is a sign source only -- and may be None without it.  Without the gate G_o = G_r = that, o, r,
+    w, gate and G_w are not used (None), and G_r may be G_o; with it G_r is a matrix of its own.  G_o may be G or act.  G_w
+    is bitwise reproducible.  The same checks before the library as gated_skip."""
+    what = "gated skip backward"
+    _req(o is not None or not int(flags) & GATED_SKIP_GATE, f"{what}: GATED_SKIP_GATE needs o")
+    gated = _req_gated_skip(G if o is None else o, r, w, gate, flags, what)
+    _req(o is None or o.shape() == G.shape(), f"{what}: o must have G's shape")
+    _req(G_o.shape() == G.shape() and G_r.shape() == G.shape(), f"{what}: G_o and G_r must have G's shape")
+    leaky = bool(int(flags) & GATED_SKIP_LEAKY_RELU)
+    _req(not leaky or (act is not None and act.shape() == G.shape()), f"{what}: act must have G's shape")
+    if gated:
+        _req(G_w is not None and G_w.shape() == w.shape(), f"{what}: G_w must be 3 x {G.m()}")
+        _req(all(G_r is not x for x in (G, act, o, r, G_o)), f"{what}: with the gate G_r must be a matrix of its own")
+        _req(G_o is not o and G_o is not r, f"{what}: G_o must not be o or r")
+    else:
+        _req(G_w is None, f"{what}: G_w needs GATED_SKIP_GATE")
+    m = G.m()
+    ctx.lib.mggcn_gated_skip_backward_f32(ctx.stream(0), G.buffer(), m, act.buffer() if leaky else None, m,
+                                          o.buffer() if gated else None, m, r.buffer() if gated else None, m,
+                                          w.buffer() if gated else None, gate.buffer() if gated else None, G_o.buffer(), m,
+                                          G_r.buffer(), m, G_w.buffer() if gated else None, G.n(), m, int(flags))
+
+
 GAT_MAX_HEADS = 16                  # MGGCN_GAT_MAX_HEADS
 GAT_MAX_WIDTH = 1024                # MGGCN_GAT_MAX_WIDTH: heads x width per head
 GAT_SLOPE = 0.2                     # the leaky ReLU of the attention scores (not the layers' 0.01)
