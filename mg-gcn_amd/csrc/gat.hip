@@ -104,8 +104,7 @@ __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const
         // rounding whatever the magnitude of the scores.  The walk fetches s_src of the entry.
         float m = -INFINITY, sum = 0.f;
         float acc[NT][VEC];
-#pragma unroll
-        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
+        zero_head_row<VEC, NT>(acc);
         const auto fetch = [&](uint32_t c, float *s) { s[0] = s_src[(size_t)c * K + k]; };
         entry_chunks<1> ch;
         ch.start(indices, beg, end, lane, fetch);
@@ -138,11 +137,7 @@ __global__ __launch_bounds__(256) void gat_forward_kernel(uint32_t n_rows, const
                     load_head_row<VEC, NT>(z[u], Zk + (size_t)en.c * ldz, lpr, sub, dh, en.ok);
                 }
 #pragma unroll
-                for (int u = 0; u < U; u++)
-#pragma unroll
-                    for (int t = 0; t < NT; t++)
-#pragma unroll
-                        for (int v = 0; v < VEC; v++) acc[t][v] = fmaf(a[u], z[u][t][v], acc[t][v]);
+                for (int u = 0; u < U; u++) axpy_head_row<VEC, NT>(acc, a[u], z[u]);
             }
         }
         const float inv = beg < end ? 1.f / sum : 0.f;
@@ -169,10 +164,9 @@ __global__ __launch_bounds__(256) void gat_backward_dst_kernel(uint32_t n_rows, 
     MGGCN_GAT_WAVE_ROW(n_rows);
     const uint32_t beg = indptr[row], end = indptr[row + 1];
     for (uint32_t k = 0; k < K; k++) {
-        float g[NT][VEC], o[NT][VEC];
+        float g[NT][VEC];
         load_head_row<VEC, NT>(g, G + row * ldg + (size_t)k * dh, lpr, sub, dh);
-        load_head_row<VEC, NT>(o, out + row * ldo + (size_t)k * dh, lpr, sub, dh, grp == 0);   // one group's worth
-        const float Dk = wave_sum(dot_head_row<VEC, NT>(g, o));
+        const float Dk = head_row_D<VEC, NT>(g, out + row * ldo + (size_t)k * dh, lpr, sub, grp, dh);
         const float sd = s_dst[row * K + k], ls = lse[row * K + k];
         const float *__restrict__ Zk = Z + (size_t)k * dh;
         float acc = 0.f;
@@ -242,8 +236,7 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
     for (uint32_t k = 0; k < K; k++) {
         float zr[NT][VEC], acc[NT][VEC];
         load_head_row<VEC, NT>(zr, Z + row * ldz + (size_t)k * dh, lpr, sub, dh);
-#pragma unroll
-        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
+        zero_head_row<VEC, NT>(acc);
         const float ss = s_src[row * K + k];
         const float *__restrict__ Gk = G + (size_t)k * dh;
         float acc_ds = 0.f;
@@ -288,11 +281,7 @@ __global__ __launch_bounds__(256) void gat_backward_src_kernel(uint32_t n_rows, 
                     float da = group_sum(p[u], lpr);
                     if constexpr (DROP) da *= en.of(my_q);
                     acc_ds += en.ok ? w * (da - Dv) : 0.f;
-                    const float au = en.ok ? a : 0.f;
-#pragma unroll
-                    for (int t = 0; t < NT; t++)
-#pragma unroll
-                        for (int v = 0; v < VEC; v++) acc[t][v] = fmaf(au, gv[u][t][v], acc[t][v]);
+                    axpy_head_row<VEC, NT>(acc, en.ok ? a : 0.f, gv[u]);
                 }
             }
         }

@@ -1,7 +1,9 @@
 // gat_internal.h -- what the graph attention kernels of gat.hip (GAT), gatv2.hip (GATv2) and gatdot.hip share: the one-wave-per-row
 // layout with LPR-lane groups (gat.hip describes it), the walk over a row's entries (entry_chunks), the group butterfly,
-// the head-row loads and the epilogue, the head geometry, the (VEC, NT, U) dispatch with the row launch, and the column-sum
-// pass behind G_att.  Internal linkage in each translation unit that includes it.  Not part of the ABI.
+// the head-row loads, zero, dot product, axpy and the epilogue, D = G . out of a row (head_row_D), the (lse, D) fetch of an
+// entry's destination (fetch_lse_D), the per-group online softmax of the GATv2 and dot-product forwards (group_softmax), the
+// head geometry, the (VEC, NT, U) dispatch with the row launch, and the column-sum pass behind G_att.  Internal linkage in
+// each translation unit that includes it.  Not part of the ABI.
 #pragma once
 
 #include <algorithm>
@@ -59,6 +61,11 @@ __device__ __forceinline__ void load_head_row(float (&r)[NT][VEC], const float *
     }
 }
 template <int VEC, int NT>
+__device__ __forceinline__ void zero_head_row(float (&r)[NT][VEC]) {
+#pragma unroll
+    for (int t = 0; t < NT; t++) zerov<VEC>(r[t]);
+}
+template <int VEC, int NT>
 __device__ __forceinline__ float dot_head_row(const float (&a)[NT][VEC], const float (&b)[NT][VEC]) {
     float p = 0.f;
 #pragma unroll
@@ -66,6 +73,23 @@ __device__ __forceinline__ float dot_head_row(const float (&a)[NT][VEC], const f
 #pragma unroll
         for (int v = 0; v < VEC; v++) p = fmaf(a[t][v], b[t][v], p);
     return p;
+}
+// acc += w z, element by element
+template <int VEC, int NT>
+__device__ __forceinline__ void axpy_head_row(float (&acc)[NT][VEC], float w, const float (&z)[NT][VEC]) {
+#pragma unroll
+    for (int t = 0; t < NT; t++)
+#pragma unroll
+        for (int v = 0; v < VEC; v++) acc[t][v] = fmaf(w, z[t][v], acc[t][v]);
+}
+// D[i, k] = G[i, head k] . out[i, head k] of the three backward_dst kernels: g is the row's head-row of G in every group,
+// out_row = out + i ldo + k dh
+template <int VEC, int NT>
+__device__ __forceinline__ float head_row_D(const float (&g)[NT][VEC], const float *out_row, uint32_t lpr, uint32_t sub,
+                                            uint32_t grp, uint32_t dh) {
+    float o[NT][VEC];
+    load_head_row<VEC, NT>(o, out_row, lpr, sub, dh, grp == 0);   // one group's worth
+    return wave_sum(dot_head_row<VEC, NT>(g, o));
 }
 
 // the sums over a row's entries: fold the G groups in fixed order, post(t, v, sum) gives the element its final value (the
@@ -136,6 +160,84 @@ private:
     float s1[NS ? NS : 1];
 };
 __device__ __forceinline__ void no_scalars(uint32_t, float *) {}
+
+// The fetch of entry_chunks<2> in the GATv2 and dot-product backward_src kernels: lse and D of the entry's destination i at
+// head k -- two 4-byte gathers, or (REC: lse and D are not read) one 8-byte load of the packed record rec[(i K + k) 2 + {0, 1}]
+template <bool REC>
+struct fetch_lse_D {
+    const float *__restrict__ lse, *__restrict__ D, *__restrict__ rec;
+    uint32_t K, k;
+    __device__ __forceinline__ void operator()(uint32_t i, float *s) const {
+        const size_t ik = (size_t)i * K + k;
+        if constexpr (REC) {
+            const float2 t = *reinterpret_cast<const float2 *>(rec + ik * 2);
+            s[0] = t.x; s[1] = t.y;
+        } else {
+            s[0] = lse[ik]; s[1] = D[ik];
+        }
+    }
+};
+
+// The softmax of one row and head in ONE pass where the score of an entry exists only in the group that gathered it (the
+// GATv2 and dot-product forwards; v1's forward has its scores per lane and a wave-wide maximum per chunk, a different
+// algorithm).  The running maximum is kept PER GROUP: m, sum and the accumulators of a group are rescaled when its maximum
+// moves.  start(); then add(e, z) per step of U entries -- e[u] the group-summed score of my group's u-th entry, -inf for
+// one that does not exist, z[u] the head-row it contributes; finish() lets the groups meet at the wave's maximum M: group
+// g enters with the factor exp(m_g - M), the sums and accumulators are folded in the fixed order of fold_groups,
+// out = acc / sum and lse = M + log(sum).  The state (m, sum, acc: of my group, every lane of a group holds the same bits)
+// is the kernel's own and every operation takes it by reference: as members of this struct, by value or by reference, the
+// compiler splits packed adds and multiplies of the float4 variants and gatdot_forward<4, 1, 4> loses a wave per SIMD.
+template <int VEC, int NT, int U>
+struct group_softmax {
+    __device__ static __forceinline__ void start(float &m, float &sum, float (&acc)[NT][VEC]) {
+        m = -INFINITY;
+        sum = 0.f;
+        zero_head_row<VEC, NT>(acc);
+    }
+    __device__ static __forceinline__ void add(float &m, float &sum, float (&acc)[NT][VEC], const float (&e)[U],
+                                               const float (&z)[U][NT][VEC]) {
+        float m_new = m;
+#pragma unroll
+        for (int u = 0; u < U; u++) m_new = fmaxf(m_new, e[u]);
+        // m_new = -inf: my group has not met an entry yet, nothing to rescale and every weight below is 0
+        const float scale = m_new == -INFINITY ? 1.f : expf(m - m_new);     // 0 at the group's first entry
+        float w[U], ws = 0.f;
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            w[u] = e[u] == -INFINITY ? 0.f : expf(e[u] - m_new);
+            ws += w[u];
+        }
+        sum = fmaf(sum, scale, ws);
+        m = m_new;
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int v = 0; v < VEC; v++) {
+                float s = acc[t][v] * scale;
+#pragma unroll
+                for (int u = 0; u < U; u++) s = fmaf(w[u], z[u][t][v], s);
+                acc[t][v] = s;
+            }
+    }
+    // out_row = out + i ldo + k dh, lse_ik = lse + i K + k; any: the row has an entry
+    __device__ static __forceinline__ void finish(float &m, float &sum, float (&acc)[NT][VEC], float *out_row, float *lse_ik,
+                                                  bool any, uint32_t lane, uint32_t lpr, uint32_t sub, uint32_t grp,
+                                                  uint32_t dh) {
+        // the groups meet at the wave's maximum; a group that never met an entry (m = -inf) enters with 0
+        float M = m;
+        for (uint32_t off = lpr; off < 64; off <<= 1) M = fmaxf(M, __shfl_xor(M, off));
+        const float f = m == -INFINITY ? 0.f : expf(m - M);
+        sum = fold_groups(sum * f, lpr);
+        const float inv = any ? 1.f / sum : 0.f;
+        if (lane == 0) *lse_ik = any ? M + logf(sum) : 0.f;
+#pragma unroll
+        for (int t = 0; t < NT; t++)
+#pragma unroll
+            for (int v = 0; v < VEC; v++) acc[t][v] *= f;
+        fold_store_head_row<VEC, NT>(out_row, acc, lpr, sub, grp, dh,
+                                     [&](int, int, float x) { return x * inv; });      // an empty row: +0.0
+    }
+};
 
 #define MGGCN_GAT_WAVE_ROW(n_rows)                                                                            \
     const uint32_t lane = threadIdx.x & 63;                                                                   \

@@ -8,9 +8,9 @@
 // Layout: gatv2.hip's -- one wave per CSR row, walked in 64-entry chunks by entry_chunks (gat_internal.h), the heads one after
 // the other, G = 64 / LPR groups of LPR lanes that each hold one head-row of a neighbour, (VEC, NT, U) variants.
 //   * forward: ONE pass over a row.  The group that gathered a neighbour's key computes its score (dot_head_row against the
-//     destination's query, group_sum), keeps a running maximum, sum and accumulators of its own and adds the neighbour's value
-//     row; both gathers of the U unrolled entries are issued before the first butterfly.  At the end the groups meet at the
-//     wave's maximum M and are folded in the fixed order of fold_groups: out = acc / sum, lse = M + log(sum).
+//     destination's query, group_sum) and hands it with the neighbour's value row to group_softmax (gat_internal.h): the
+//     running maximum, sum and accumulators per group, the groups' meeting at the wave's maximum and the fold, gatv2.hip's
+//     word for word.  Both gathers of the U unrolled entries are issued before the first butterfly.
 //   * backward_dst (rows of F): D[i, k] = G . out, and per entry e and dalpha = G[i] . Zv[j] as two butterflies,
 //     ds = exp(e - lse)(dalpha - D), accq += ds Zk[j]; G_Zq = c accq.
 //   * backward_src (rows of F^T): the row's own key and value head-rows stay in registers, lse and D of the entry's
@@ -31,15 +31,6 @@
 
 namespace {
 
-// acc += w z, element by element
-template <int VEC, int NT>
-__device__ __forceinline__ void axpy_head_row(float (&acc)[NT][VEC], float w, const float (&z)[NT][VEC]) {
-#pragma unroll
-    for (int t = 0; t < NT; t++)
-#pragma unroll
-        for (int v = 0; v < VEC; v++) acc[t][v] = fmaf(w, z[t][v], acc[t][v]);
-}
-
 // ---------------------------------------------------------------------------
 // forward: lse[i, k] and out[i, head k] = sum_j alpha_ijk Zv[j, head k] over the entries j of row i
 // ---------------------------------------------------------------------------
@@ -54,13 +45,13 @@ __global__ __launch_bounds__(256) void gatdot_forward_kernel(uint32_t n_rows, co
     MGGCN_GAT_WAVE_ROW(n_rows);
     const uint32_t beg = indptr[row], end = indptr[row + 1];
     for (uint32_t k = 0; k < K; k++) {
-        float q[NT][VEC], acc[NT][VEC];
+        float q[NT][VEC];
         load_head_row<VEC, NT>(q, Zq + row * ldq + (size_t)k * dh, lpr, sub, dh);
-#pragma unroll
-        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
         const float *__restrict__ Kk = Zk + (size_t)k * dh;
         const float *__restrict__ Vk = Zv + (size_t)k * dh;
-        float m = -INFINITY, sum = 0.f;             // of my group: every lane of a group holds the same bits
+        using sm = group_softmax<VEC, NT, U>;
+        float m, sum, acc[NT][VEC];
+        sm::start(m, sum, acc);
         entry_chunks<0> ch;                         // the indices alone
         ch.start(indices, beg, end, lane, no_scalars);
         for (uint32_t base = beg; base < end; base += 64) {
@@ -76,47 +67,15 @@ __global__ __launch_bounds__(256) void gatdot_forward_kernel(uint32_t n_rows, co
                     load_head_row<VEC, NT>(z[u], Vk + (size_t)en.c * ldv, lpr, sub, dh, en.ok);
                     e[u] = dot_head_row<VEC, NT>(q, kk);
                 }
-                float m_new = m;
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     e[u] = c * group_sum(e[u], lpr);
                     if (!ch.pick(j, u, n_grp, grp).ok) e[u] = -INFINITY;
-                    m_new = fmaxf(m_new, e[u]);
                 }
-                // m_new = -inf: my group has not met an entry yet, nothing to rescale and every weight below is 0
-                const float scale = m_new == -INFINITY ? 1.f : expf(m - m_new);     // 0 at the group's first entry
-                float w[U], ws = 0.f;
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    w[u] = e[u] == -INFINITY ? 0.f : expf(e[u] - m_new);
-                    ws += w[u];
-                }
-                sum = fmaf(sum, scale, ws);
-                m = m_new;
-#pragma unroll
-                for (int t = 0; t < NT; t++)
-#pragma unroll
-                    for (int v = 0; v < VEC; v++) {
-                        float s = acc[t][v] * scale;
-#pragma unroll
-                        for (int u = 0; u < U; u++) s = fmaf(w[u], z[u][t][v], s);
-                        acc[t][v] = s;
-                    }
+                sm::add(m, sum, acc, e, z);
             }
         }
-        // the groups meet at the wave's maximum; a group that never met an entry (m = -inf) enters with 0
-        float M = m;
-        for (uint32_t off = lpr; off < 64; off <<= 1) M = fmaxf(M, __shfl_xor(M, off));
-        const float f = m == -INFINITY ? 0.f : expf(m - M);
-        sum = fold_groups(sum * f, lpr);
-        const float inv = beg < end ? 1.f / sum : 0.f;
-        if (lane == 0) lse[row * K + k] = beg < end ? M + logf(sum) : 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int v = 0; v < VEC; v++) acc[t][v] *= f;
-        fold_store_head_row<VEC, NT>(out + row * ldo + (size_t)k * dh, acc, lpr, sub, grp, dh,
-                                     [&](int, int, float x) { return x * inv; });      // an empty row: +0.0
+        sm::finish(m, sum, acc, out + row * ldo + (size_t)k * dh, lse + row * K + k, beg < end, lane, lpr, sub, grp, dh);
     }
 }
 
@@ -139,15 +98,9 @@ __global__ __launch_bounds__(256) void gatdot_backward_dst_kernel(uint32_t n_row
     for (uint32_t k = 0; k < K; k++) {
         float g[NT][VEC], q[NT][VEC], accq[NT][VEC];
         load_head_row<VEC, NT>(g, G + row * ldg + (size_t)k * dh, lpr, sub, dh);
-        float Dk;
-        {
-            float o[NT][VEC];
-            load_head_row<VEC, NT>(o, out + row * ldo + (size_t)k * dh, lpr, sub, dh, grp == 0);   // one group's worth
-            Dk = wave_sum(dot_head_row<VEC, NT>(g, o));
-        }
+        const float Dk = head_row_D<VEC, NT>(g, out + row * ldo + (size_t)k * dh, lpr, sub, grp, dh);
         load_head_row<VEC, NT>(q, Zq + row * ldq + (size_t)k * dh, lpr, sub, dh);
-#pragma unroll
-        for (int t = 0; t < NT; t++) zerov<VEC>(accq[t]);
+        zero_head_row<VEC, NT>(accq);
         const float ls = lse[row * K + k];
         const float *__restrict__ Kk = Zk + (size_t)k * dh;
         const float *__restrict__ Vk = Zv + (size_t)k * dh;
@@ -202,14 +155,11 @@ __global__ __launch_bounds__(256) void gatdot_backward_src_kernel(uint32_t n_row
         float zk[NT][VEC], zv[NT][VEC], acck[NT][VEC], accv[NT][VEC];
         load_head_row<VEC, NT>(zk, Zk + row * ldk + (size_t)k * dh, lpr, sub, dh);
         load_head_row<VEC, NT>(zv, Zv + row * ldv + (size_t)k * dh, lpr, sub, dh);
-#pragma unroll
-        for (int t = 0; t < NT; t++) { zerov<VEC>(acck[t]); zerov<VEC>(accv[t]); }
+        zero_head_row<VEC, NT>(acck);
+        zero_head_row<VEC, NT>(accv);
         const float *__restrict__ Qk = Zq + (size_t)k * dh;
         const float *__restrict__ Gk = G + (size_t)k * dh;
-        const auto fetch = [&](uint32_t i, float *s) {          // lse and D of the entry's destination
-            const size_t ik = (size_t)i * K + k;
-            s[0] = lse[ik]; s[1] = D[ik];
-        };
+        const fetch_lse_D<false> fetch{lse, D, nullptr, K, k};  // lse and D of the entry's destination: no record form
         entry_chunks<2> ch;
         ch.start(indices, beg, end, lane, fetch);
         for (uint32_t base = beg; base < end; base += 64) {

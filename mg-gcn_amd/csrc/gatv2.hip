@@ -7,9 +7,8 @@
 // Layout: gat.hip's -- one wave per CSR row, walked in 64-entry chunks by entry_chunks (gat_internal.h), the heads one
 // after the other, G = 64 / LPR groups of LPR lanes that each hold one head-row of a neighbour, (VEC, NT, U) variants.
 //   * forward: ONE pass over a row with one gather of Zs per entry.  The group that gathered a neighbour computes its score,
-//     so the running maximum is kept PER GROUP (m, sum and the accumulators of a group are rescaled when its maximum
-//     moves); at the end the groups meet at the wave's maximum M: group g enters with the factor exp(m_g - M), the sums
-//     and accumulators are folded in the fixed order of fold_groups, out = acc / sum and lse = M + log(sum).
+//     so the running maximum is kept PER GROUP and the groups meet at the wave's maximum at the end: group_softmax
+//     (gat_internal.h) is that softmax, the kernel keeps its prologue loads, its gather and its partial score.
 //   * backward_dst (rows of F): D, G_Zd and P[i] = sum_j ds_ijk u_ijk, row i's share of G_att; e and dalpha are two
 //     butterflies over the same gathered row.
 //   * backward_src (rows of F^T): gathers the destination's head-rows of Zd and G, recomputes e, dalpha, alpha and ds, and
@@ -55,13 +54,13 @@ __global__ __launch_bounds__(256) void gatv2_forward_kernel(uint32_t n_rows, con
     MGGCN_GAT_WAVE_ROW(n_rows);
     const uint32_t beg = indptr[row], end = indptr[row + 1];
     for (uint32_t k = 0; k < K; k++) {
-        float zd[NT][VEC], a[NT][VEC], acc[NT][VEC];
+        float zd[NT][VEC], a[NT][VEC];
         load_head_row<VEC, NT>(zd, Zd + row * ldzd + (size_t)k * dh, lpr, sub, dh);
         load_head_row<VEC, NT>(a, att + (size_t)k * dh, lpr, sub, dh);
-#pragma unroll
-        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
         const float *__restrict__ Zk = Zs + (size_t)k * dh;
-        float m = -INFINITY, sum = 0.f;             // of my group: every lane of a group holds the same bits
+        using sm = group_softmax<VEC, NT, U>;
+        float m, sum, acc[NT][VEC];
+        sm::start(m, sum, acc);
         entry_chunks<0> ch;                         // the indices alone
         ch.start(indices, beg, end, lane, no_scalars);
         for (uint32_t base = beg; base < end; base += 64) {
@@ -75,47 +74,15 @@ __global__ __launch_bounds__(256) void gatv2_forward_kernel(uint32_t n_rows, con
                     load_head_row<VEC, NT>(z[u], Zk + (size_t)en.c * ldzs, lpr, sub, dh, en.ok);
                     e[u] = score_head_row<VEC, NT>(a, zd, z[u], slope);
                 }
-                float m_new = m;
 #pragma unroll
                 for (int u = 0; u < U; u++) {
                     e[u] = group_sum(e[u], lpr);
                     if (!ch.pick(j, u, n_grp, grp).ok) e[u] = -INFINITY;
-                    m_new = fmaxf(m_new, e[u]);
                 }
-                // m_new = -inf: my group has not met an entry yet, nothing to rescale and every weight below is 0
-                const float scale = m_new == -INFINITY ? 1.f : expf(m - m_new);     // 0 at the group's first entry
-                float w[U], ws = 0.f;
-#pragma unroll
-                for (int u = 0; u < U; u++) {
-                    w[u] = e[u] == -INFINITY ? 0.f : expf(e[u] - m_new);
-                    ws += w[u];
-                }
-                sum = fmaf(sum, scale, ws);
-                m = m_new;
-#pragma unroll
-                for (int t = 0; t < NT; t++)
-#pragma unroll
-                    for (int v = 0; v < VEC; v++) {
-                        float s = acc[t][v] * scale;
-#pragma unroll
-                        for (int u = 0; u < U; u++) s = fmaf(w[u], z[u][t][v], s);
-                        acc[t][v] = s;
-                    }
+                sm::add(m, sum, acc, e, z);
             }
         }
-        // the groups meet at the wave's maximum; a group that never met an entry (m = -inf) enters with 0
-        float M = m;
-        for (uint32_t off = lpr; off < 64; off <<= 1) M = fmaxf(M, __shfl_xor(M, off));
-        const float f = m == -INFINITY ? 0.f : expf(m - M);
-        sum = fold_groups(sum * f, lpr);
-        const float inv = beg < end ? 1.f / sum : 0.f;
-        if (lane == 0) lse[row * K + k] = beg < end ? M + logf(sum) : 0.f;
-#pragma unroll
-        for (int t = 0; t < NT; t++)
-#pragma unroll
-            for (int v = 0; v < VEC; v++) acc[t][v] *= f;
-        fold_store_head_row<VEC, NT>(out + row * ldo + (size_t)k * dh, acc, lpr, sub, grp, dh,
-                                     [&](int, int, float x) { return x * inv; });      // an empty row: +0.0
+        sm::finish(m, sum, acc, out + row * ldo + (size_t)k * dh, lse + row * K + k, beg < end, lane, lpr, sub, grp, dh);
     }
 }
 
@@ -139,16 +106,11 @@ __global__ __launch_bounds__(256) void gatv2_backward_dst_kernel(uint32_t n_rows
     for (uint32_t k = 0; k < K; k++) {
         float g[NT][VEC], zd[NT][VEC], a[NT][VEC], accv[NT][VEC], accp[NT][VEC];
         load_head_row<VEC, NT>(g, G + row * ldg + (size_t)k * dh, lpr, sub, dh);
-        float Dk;
-        {
-            float o[NT][VEC];
-            load_head_row<VEC, NT>(o, out + row * ldo + (size_t)k * dh, lpr, sub, dh, grp == 0);   // one group's worth
-            Dk = wave_sum(dot_head_row<VEC, NT>(g, o));
-        }
+        const float Dk = head_row_D<VEC, NT>(g, out + row * ldo + (size_t)k * dh, lpr, sub, grp, dh);
         load_head_row<VEC, NT>(zd, Zd + row * ldzd + (size_t)k * dh, lpr, sub, dh);
         load_head_row<VEC, NT>(a, att + (size_t)k * dh, lpr, sub, dh);
-#pragma unroll
-        for (int t = 0; t < NT; t++) { zerov<VEC>(accv[t]); zerov<VEC>(accp[t]); }
+        zero_head_row<VEC, NT>(accv);
+        zero_head_row<VEC, NT>(accp);
         const float ls = lse[row * K + k];
         const float *__restrict__ Zk = Zs + (size_t)k * dh;
         entry_chunks<0> ch;                         // the indices alone
@@ -211,19 +173,10 @@ __global__ __launch_bounds__(256) void gatv2_backward_src_kernel(uint32_t n_rows
         float zs[NT][VEC], a[NT][VEC], acc[NT][VEC];
         load_head_row<VEC, NT>(zs, Zs + row * ldzs + (size_t)k * dh, lpr, sub, dh);
         load_head_row<VEC, NT>(a, att + (size_t)k * dh, lpr, sub, dh);
-#pragma unroll
-        for (int t = 0; t < NT; t++) zerov<VEC>(acc[t]);
+        zero_head_row<VEC, NT>(acc);
         const float *__restrict__ Zdk = Zd + (size_t)k * dh;
         const float *__restrict__ Gk = G + (size_t)k * dh;
-        const auto fetch = [&](uint32_t c, float *s) {          // lse and D of the entry's destination
-            const size_t ik = (size_t)c * K + k;
-            if constexpr (REC) {
-                const float2 t = *reinterpret_cast<const float2 *>(rec + ik * 2);
-                s[0] = t.x; s[1] = t.y;
-            } else {
-                s[0] = lse[ik]; s[1] = D[ik];
-            }
-        };
+        const fetch_lse_D<REC> fetch{lse, D, rec, K, k};        // lse and D of the entry's destination
         entry_chunks<2> ch;
         ch.start(indices, beg, end, lane, fetch);
         for (uint32_t base = beg; base < end; base += 64) {

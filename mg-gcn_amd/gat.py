@@ -111,7 +111,42 @@ def check_heads(sizes: Sequence[int], heads) -> List[int]:
     return [int(h) for h in per_layer]
 
 
-class attention:
+class adam_row:
+    """The Adam state of one parameter tensor of an attention model that decays like W -- ``att`` of attention and
+    attention_v2, ``w`` of gated_skip: the step counter, the lazily made ``m`` / ``v``, the row of ops.adam_table, and the
+    per-tensor step of gat(fused=False): one ops.adam_fused per row of adam_tensors(), the element-wise math of the
+    model-wide table bit for bit.  A class names its (parameter, gradient) in adam_pair(), read at call time (dist_attention
+    rebinds G_att after __init__)."""
+
+    m = v = None
+    step = 0
+
+    def adam_pair(self):
+        raise NotImplementedError
+
+    def adam_state(self, ctx: context) -> None:
+        if self.m is None:
+            p, _ = self.adam_pair()
+            self.m, self.v = dn_matrix(p.shape(), device=p.t.device), dn_matrix(p.shape(), device=p.t.device)
+            self.m.zero(ctx)
+            self.v.zero(ctx)
+            self.step = 0
+
+    def adam_tensors(self, weight_decay: float):
+        """row of ops.adam_table: the parameter decays like W"""
+        return [self.adam_pair() + (self.m, self.v, weight_decay)]
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
+        """one launch per tensor: the element-wise math of the model-wide table, bit for bit"""
+        self.adam_state(ctx)
+        self.step += 1
+        bc1 = float(np.float32(1 - beta1 ** self.step))
+        bc2 = float(np.float32(1 - beta2 ** self.step))
+        for p, g, m, v, wd in self.adam_tensors(weight_decay):
+            ops.adam_fused(ctx, p, g, m, v, lr, beta1, beta2, wd, bc1, bc2, eps)
+
+
+class attention(adam_row):
     """The attention of one layer: the parameter ``att`` [2 x out] (row 0 the destination vector, row 1 the source
     vector; seed-99 uniform like W), its gradient and Adam state, and what the backward pass needs of the forward --
     s_dst, s_src, lse [n x heads].  att is trained by Adam with the weight decay of W."""
@@ -124,8 +159,9 @@ class attention:
         self.att.init(host)
         self.s_dst, self.lse, self.D, self.ds_dst = (dn_matrix(n_dst, heads, device=device) for _ in range(4))
         self.s_src, self.ds_src = dn_matrix(n_src, heads, device=device), dn_matrix(n_src, heads, device=device)
-        self.m = self.v = None
-        self.step = 0
+
+    def adam_pair(self):
+        return self.att, self.G_att
 
     def __call__(self, ctx: context, F: csr_matrix, Z: dn_matrix, out: dn_matrix, drop=None) -> None:
         """out = the attention-weighted gather of Z over F's rows (destinations and sources are the same vertices);
@@ -152,26 +188,6 @@ class attention:
     def init(self, att) -> None:
         self.att.init(np.asarray(att, dtype=np.float32))
 
-    def adam_state(self, ctx: context) -> None:
-        if self.m is None:
-            dev = self.att.t.device
-            self.m, self.v = dn_matrix(self.att.shape(), device=dev), dn_matrix(self.att.shape(), device=dev)
-            self.m.zero(ctx)
-            self.v.zero(ctx)
-            self.step = 0
-
-    def adam_tensors(self, weight_decay: float):
-        """row of ops.adam_table: att decays like W"""
-        return [(self.att, self.G_att, self.m, self.v, weight_decay)]
-
-    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
-        """one launch for this tensor: the element-wise math of the model-wide table, bit for bit"""
-        self.adam_state(ctx)
-        self.step += 1
-        bc1 = float(np.float32(1 - beta1 ** self.step))
-        bc2 = float(np.float32(1 - beta2 ** self.step))
-        ops.adam_fused(ctx, self.att, self.G_att, self.m, self.v, lr, beta1, beta2, weight_decay, bc1, bc2, eps)
-
 
 class attention_v2(attention):
     """The GATv2 attention of one layer: the parameter ``att`` [1 x out] (seed-99 uniform like W), its gradient and Adam
@@ -188,8 +204,6 @@ class attention_v2(attention):
         self.att.init(host)
         self.lse, self.D = dn_matrix(n, heads, device=device), dn_matrix(n, heads, device=device)
         self.P = dn_matrix(n, out, P_buffer) if P_buffer is not None else dn_matrix(n, out, device=device)
-        self.m = self.v = None
-        self.step = 0
 
     def __call__(self, ctx: context, F: csr_matrix, Z2: dn_matrix, out: dn_matrix, drop=None) -> None:
         """out = the attention-weighted gather of Zs over F's rows, scored against Zd"""
@@ -246,7 +260,7 @@ def refuse_skip(model, what: str) -> None:
             raise ValueError(f'gat({option}="{value}") has no {what}')
 
 
-class gated_skip:
+class gated_skip(adam_row):
     """The skip connection of one attention layer (gat(skip=...)): ``res_lin``, a linear r = H W_r + 1 b_r^T over the
     layer's own input -- always a linear, also where in == out (PyG's lin_skip) --, and the row kernels of
     csrc/gated_skip.hip that combine r with the attention output o: y = o + r ("add"), or y = g r + (1 - g) o with one
@@ -261,8 +275,7 @@ class gated_skip:
         self.name, self.mode = name, mode
         self.res_lin = linear(name, in_, out, backward_out, True)
         shared = dn_matrix(n, out, buffer) if buffer is not None else dn_matrix(n, out, device=device)
-        self.w = self.G_w = self.gate = self.G_r = self.m = self.v = None
-        self.step = 0
+        self.w = self.G_w = self.gate = self.G_r = None
         if mode == "gate":
             self.r, self.G_r = dn_matrix(n, out, device=device), shared
             self.w, self.G_w = dn_matrix(3, out, device=device), dn_matrix(3, out, device=device)
@@ -303,41 +316,18 @@ class gated_skip:
             raise ValueError('gat(skip="add") has no gate parameter: skip_weights= takes (W_r, b_r) per layer')
         self.w.init(np.asarray(w, dtype=np.float32))
 
-    # the Adam rows of the gate's parameter (res_lin is a linear of its own in the layer's params())
-    def adam_state(self, ctx: context) -> None:
-        if self.m is None:
-            dev = self.w.t.device
-            self.m, self.v = dn_matrix(self.w.shape(), device=dev), dn_matrix(self.w.shape(), device=dev)
-            self.m.zero(ctx)
-            self.v.zero(ctx)
-            self.step = 0
-
-    def adam_tensors(self, weight_decay: float):
-        """row of ops.adam_table: w decays like W"""
-        return [(self.w, self.G_w, self.m, self.v, weight_decay)]
-
-    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
-        """one launch for this tensor: the element-wise math of the model-wide table, bit for bit"""
-        self.adam_state(ctx)
-        self.step += 1
-        bc1 = float(np.float32(1 - beta1 ** self.step))
-        bc2 = float(np.float32(1 - beta2 ** self.step))
-        ops.adam_fused(ctx, self.w, self.G_w, self.m, self.v, lr, beta1, beta2, weight_decay, bc1, bc2, eps)
+    # the Adam row of the gate's parameter (res_lin is a linear of its own in the layer's params())
+    def adam_pair(self):
+        return self.w, self.G_w
 
 
 class gat_layer_norm(layer_norm):
     """gcn.layer_norm as the attention layers use it: the same kernels, buffers and Adam rows (no weight decay); only the
-    per-tensor Adam step (gat(fused=False)) differs -- one ops.adam_fused per tensor, the element-wise math of the
-    model-wide table bit for bit, as for every other parameter of a gat model (gcn's own per-tensor step is the
+    per-tensor Adam step (gat(fused=False)) differs -- adam_row's: one ops.adam_fused per tensor, the element-wise math of
+    the model-wide table bit for bit, as for every other parameter of a gat model (gcn's own per-tensor step is the
     reference's unfused chain, which rounds differently)."""
 
-    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
-        self.adam_state(ctx)
-        self.step += 1
-        bc1 = float(np.float32(1 - beta1 ** self.step))
-        bc2 = float(np.float32(1 - beta2 ** self.step))
-        for p, g, m, v, wd in self.adam_tensors(weight_decay):
-            ops.adam_fused(ctx, p, g, m, v, lr, beta1, beta2, wd, bc1, bc2, eps)
+    adam_update = adam_row.adam_update
 
 
 class gat_layer:

@@ -670,12 +670,14 @@ def gat_alpha(ctx: context, F: csr_matrix, s_dst: dn_matrix, s_src: dn_matrix, l
         alpha.buffer(), alpha.m()))
 
 
-def _gatv2_half(M: dn_matrix, width: int, half: int, what: str):
-    """(pointer, leading dimension) of a dense operand of the GATv2 calls: ``M`` is either the [rows x width] matrix itself
-    or the model's [rows x 2 width] buffer, whose columns [0, width) are the source half (half 0: Zs, G_Zs) and
-    [width, 2 width) the destination half (half 1: Zd, G_Zd)"""
-    _req(M.m() in (width, 2 * width), f"{what}: an operand of {M.m()} columns is neither {width} nor 2 x {width} wide")
-    return (M.buffer(), width) if M.m() == width else (M.buffer() + 4 * width * half, 2 * width)
+def _split_operand(M: dn_matrix, width: int, part: int, parts: int, what: str):
+    """(pointer, leading dimension) of a dense operand of the GATv2 (``parts`` = 2) and dot-product (3) attention calls:
+    ``M`` is either the [rows x width] matrix itself or the model's [rows x parts width] buffer, of which the operand is
+    columns [part width, (part + 1) width).  GATv2: part 0 is the source half (Zs, G_Zs), 1 the destination half (Zd,
+    G_Zd); dot: 0 the query third (Zq, G_Zq), 1 the key third (Zk, G_Zk), 2 the value third (Zv, G_Zv)"""
+    _req(M.m() in (width, parts * width),
+         f"{what}: an operand of {M.m()} columns is neither {width} nor {parts} x {width} wide")
+    return (M.buffer(), width) if M.m() == width else (M.buffer() + 4 * width * part, parts * width)
 
 
 def _gatv2_width(att: dn_matrix, heads: int, what: str) -> int:
@@ -694,7 +696,7 @@ def gatv2_forward(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att
     width = _gatv2_width(att, heads, "gatv2 forward")
     _req(F.m() == Zs.n() and F.n() == Zd.n() and out.shape() == (F.n(), width), "gatv2 forward: shape mismatch")
     _req(lse.shape() == (F.n(), heads), "gatv2 forward: lse must be rows x heads")
-    (zs, ldzs), (zd, ldzd) = _gatv2_half(Zs, width, 0, "gatv2 forward"), _gatv2_half(Zd, width, 1, "gatv2 forward")
+    (zs, ldzs), (zd, ldzd) = (_split_operand(M, width, part, 2, "gatv2 forward") for part, M in enumerate((Zs, Zd)))
     ip, ix, _ = F.device(ctx.device)
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_forward_f32(
         ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), heads, width // heads,
@@ -710,7 +712,7 @@ def gatv2_alpha(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: 
     width = _gatv2_width(att, heads, "gatv2 alpha")
     _req(F.m() == Zs.n() and F.n() == Zd.n(), "gatv2 alpha: shape mismatch")
     _req_gat_alpha(F, lse, alpha, heads, "gatv2 alpha")
-    (zs, ldzs), (zd, ldzd) = _gatv2_half(Zs, width, 0, "gatv2 alpha"), _gatv2_half(Zd, width, 1, "gatv2 alpha")
+    (zs, ldzs), (zd, ldzd) = (_split_operand(M, width, part, 2, "gatv2 alpha") for part, M in enumerate((Zs, Zd)))
     if not F.nnz():
         return
     ip, ix, _ = F.device(ctx.device)
@@ -732,8 +734,8 @@ def gatv2_backward_dst(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix
     _req(F.m() == Zs.n() and F.n() == Zd.n() and G.shape() == (F.n(), width) and out.shape() == G.shape()
          and P.shape() == G.shape() and G_Zd.n() == F.n(), f"{what}: shape mismatch")
     _req(lse.shape() == (F.n(), heads) and D.shape() == (F.n(), heads), f"{what}: lse and D must be rows x heads")
-    (zs, ldzs), (zd, ldzd), (gzd, ldgzd) = (_gatv2_half(Zs, width, 0, what), _gatv2_half(Zd, width, 1, what),
-                                            _gatv2_half(G_Zd, width, 1, what))
+    (zs, ldzs), (zd, ldzd), (gzd, ldgzd) = (_split_operand(Zs, width, 0, 2, what), _split_operand(Zd, width, 1, 2, what),
+                                            _split_operand(G_Zd, width, 1, 2, what))
     ip, ix, _ = F.device(ctx.device)
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_backward_dst_f32(
         ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), lse.buffer(), G.buffer(),
@@ -761,8 +763,8 @@ def gatv2_backward_src(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_matr
     _req(F_T.n() == Zs.n() and F_T.m() == Zd.n() and G.shape() == (F_T.m(), width) and G_Zs.n() == F_T.n(),
          f"{what}: shape mismatch")
     _req(lse.shape() == (F_T.m(), heads) and D.shape() == (F_T.m(), heads), f"{what}: lse and D must be rows x heads")
-    (zs, ldzs), (zd, ldzd), (gzs, ldgzs) = (_gatv2_half(Zs, width, 0, what), _gatv2_half(Zd, width, 1, what),
-                                            _gatv2_half(G_Zs, width, 0, what))
+    (zs, ldzs), (zd, ldzd), (gzs, ldgzs) = (_split_operand(Zs, width, 0, 2, what), _split_operand(Zd, width, 1, 2, what),
+                                            _split_operand(G_Zs, width, 0, 2, what))
     ip, ix, _ = F_T.device(ctx.device)
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_backward_src_f32(
         ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), lse.buffer(),
@@ -797,20 +799,12 @@ def gatv2_backward_src_rec(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_
     _req(F_T.n() == Zs.n() and F_T.m() == Zd.n() and G.shape() == (F_T.m(), width) and G_Zs.n() == F_T.n(),
          f"{what}: shape mismatch")
     _req_gatv2_rec(rec, F_T.m(), heads, what)
-    (zs, ldzs), (zd, ldzd), (gzs, ldgzs) = (_gatv2_half(Zs, width, 0, what), _gatv2_half(Zd, width, 1, what),
-                                            _gatv2_half(G_Zs, width, 0, what))
+    (zs, ldzs), (zd, ldzd), (gzs, ldgzs) = (_split_operand(Zs, width, 0, 2, what), _split_operand(Zd, width, 1, 2, what),
+                                            _split_operand(G_Zs, width, 0, 2, what))
     ip, ix, _ = F_T.device(ctx.device)
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_backward_src_rec_f32(
         ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), rec.data_ptr(),
         G.buffer(), G.m(), heads, width // heads, slope, gzs, ldgzs))
-
-
-def _gatdot_third(M: dn_matrix, width: int, third: int, what: str):
-    """(pointer, leading dimension) of a dense operand of the dot-product attention calls: ``M`` is either the
-    [rows x width] matrix itself or the model's [rows x 3 width] buffer, whose columns [0, width) are the query third
-    (third 0: Zq, G_Zq), [width, 2 width) the key third (1: Zk, G_Zk) and [2 width, 3 width) the value third (2: Zv, G_Zv)"""
-    _req(M.m() in (width, 3 * width), f"{what}: an operand of {M.m()} columns is neither {width} nor 3 x {width} wide")
-    return (M.buffer(), width) if M.m() == width else (M.buffer() + 4 * width * third, 3 * width)
 
 
 def _gatdot_width(out: dn_matrix, heads: int, what: str) -> int:
@@ -835,8 +829,8 @@ def gatdot_forward(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv
     width = _gatdot_width(out, heads, what)
     _req(F.n() == Zq.n() and F.m() == Zk.n() and F.m() == Zv.n() and out.n() == F.n(), f"{what}: shape mismatch")
     _req(lse.shape() == (F.n(), heads), f"{what}: lse must be rows x heads")
-    (zq, ldq), (zk, ldk), (zv, ldv) = (_gatdot_third(Zq, width, 0, what), _gatdot_third(Zk, width, 1, what),
-                                       _gatdot_third(Zv, width, 2, what))
+    (zq, ldq), (zk, ldk), (zv, ldv) = (_split_operand(Zq, width, 0, 3, what), _split_operand(Zk, width, 1, 3, what),
+                                       _split_operand(Zv, width, 2, 3, what))
     scale = gatdot_scale(width // heads) if scale is None else float(scale)
     ip, ix, _ = F.device(ctx.device)
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_forward_f32(
@@ -856,8 +850,8 @@ def gatdot_backward_dst(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matri
     _req(F.n() == Zq.n() and F.m() == Zk.n() and F.m() == Zv.n() and out.n() == F.n() and G.shape() == out.shape()
          and G_Zq.n() == F.n(), f"{what}: shape mismatch")
     _req(lse.shape() == (F.n(), heads) and D.shape() == (F.n(), heads), f"{what}: lse and D must be rows x heads")
-    (zq, ldq), (zk, ldk), (zv, ldv), (gzq, ldgzq) = (_gatdot_third(Zq, width, 0, what), _gatdot_third(Zk, width, 1, what),
-                                                     _gatdot_third(Zv, width, 2, what), _gatdot_third(G_Zq, width, 0, what))
+    (zq, ldq), (zk, ldk), (zv, ldv), (gzq, ldgzq) = (_split_operand(M, width, part, 3, what)
+                                                     for M, part in ((Zq, 0), (Zk, 1), (Zv, 2), (G_Zq, 0)))
     scale = gatdot_scale(width // heads) if scale is None else float(scale)
     ip, ix, _ = F.device(ctx.device)
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_backward_dst_f32(
@@ -879,9 +873,9 @@ def gatdot_backward_src(ctx: context, F_T: csr_matrix, Zq: dn_matrix, Zk: dn_mat
          and G_Zv.n() == F_T.n(), f"{what}: shape mismatch")
     _req(lse.shape() == (F_T.m(), heads) and D.shape() == (F_T.m(), heads), f"{what}: lse and D must be rows x heads")
     _req(G_Zk is not G_Zv or G_Zk.m() == 3 * width, f"{what}: G_Zk and G_Zv must not be the same [rows x width] matrix")
-    (zq, ldq), (zk, ldk), (zv, ldv) = (_gatdot_third(Zq, width, 0, what), _gatdot_third(Zk, width, 1, what),
-                                       _gatdot_third(Zv, width, 2, what))
-    (gzk, ldgzk), (gzv, ldgzv) = _gatdot_third(G_Zk, width, 1, what), _gatdot_third(G_Zv, width, 2, what)
+    (zq, ldq), (zk, ldk), (zv, ldv) = (_split_operand(Zq, width, 0, 3, what), _split_operand(Zk, width, 1, 3, what),
+                                       _split_operand(Zv, width, 2, 3, what))
+    (gzk, ldgzk), (gzv, ldgzv) = _split_operand(G_Zk, width, 1, 3, what), _split_operand(G_Zv, width, 2, 3, what)
     scale = gatdot_scale(width // heads) if scale is None else float(scale)
     ip, ix, _ = F_T.device(ctx.device)
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_backward_src_f32(

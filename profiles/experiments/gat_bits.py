@@ -1,7 +1,8 @@
 """Do two trees compute the same bits in every GAT entry point?  
 Every call of the GAT part of ops -- scores, forward, backward_dst, backward_src with and without attention dropout,
-pack_dst, backward_src_rec with and without dropout, scores_backward, and the four GATv2 calls on [rows x width] operands
-and on the model's [Zs | Zd] buffers -- on the graphs "long", "longT" and "rect" of gat_ref.edge_graphs(), at one (K, dh)
+pack_dst, backward_src_rec with and without dropout, scores_backward, the four GATv2 calls on [rows x width] operands
+and on the model's [Zs | Zd] buffers, and the three dot-product calls (inputs of gatdot_ref) on [rows x width] operands and
+on the thirds of [rows x 3 width] buffers -- on the graphs "long", "longT" and "rect" of gat_ref.edge_graphs(), at one (K, dh)
 per compiled (VEC, NT, U) variant (gat_ref.EDGE_RECT) plus (1, 1024) with every dense operand one float off, which is the
 16-tile element path; and att_grad beyond two passes of its capped grid.  One line per output: the entry point, the graph,
 the shape and the SHA-256 of the raw bytes.  The tests hold the kernels against an fp64 restatement within a tolerance and
@@ -21,6 +22,7 @@ root = os.path.abspath(ap.parse_args().root)
 sys.path[:0] = [root, os.path.join(root, "tests")]
 import __graft_entry__ as g
 import gat_ref
+import gatdot_ref
 import gatv2_ref
 import torch
 
@@ -103,6 +105,26 @@ def run_v2(tag, F, F_T, n, n_src, K, dh, off):
         report("gatv2_backward_src" + sfx, tag, G_Zs=G_Zs)
 
 
+def run_dot(tag, F, F_T, n, n_src, K, dh, off):
+    d = K * dh
+    Zqh, Zkh, Zvh, Gh = gatdot_ref.inputs(n, n_src, K, dh)
+    G = dense(Gh, off)
+    zq, zs = np.zeros_like(Zqh), np.zeros_like(Zkh)
+    Zkv = dense(np.concatenate([zs, Zkh, Zvh], axis=1), off)                  # one buffer passed as Zk and as Zv
+    forms = {"": (dense(Zqh, off), dense(Zkh, off), dense(Zvh, off), d),
+             "[Zq|Zk|Zv]": (dense(np.concatenate([Zqh, zq, zq], axis=1), off), Zkv, Zkv, 3 * d)}
+    for sfx, (Zq, Zk, Zv, gw) in forms.items():
+        out, lse, D = dense((n, d), off), dense((n, K)), dense((n, K))
+        G_Zq, G_Zk = dense((n, gw), off), dense((n_src, gw), off)
+        G_Zv = G_Zk if sfx else dense((n_src, gw), off)                        # the thirds of one gradient buffer
+        ops.gatdot_forward(ctx, F, Zq, Zk, Zv, out, lse, K)
+        report("gatdot_forward" + sfx, tag, out=out, lse=lse)
+        ops.gatdot_backward_dst(ctx, F, Zq, Zk, Zv, lse, G, out, D, G_Zq, K)
+        report("gatdot_backward_dst" + sfx, tag, D=D, G_Zq=G_Zq)
+        ops.gatdot_backward_src(ctx, F_T, Zq, Zk, Zv, lse, D, G, G_Zk, G_Zv, K)
+        report("gatdot_backward_src" + sfx, tag, G_Zk=G_Zk, G_Zv=G_Zv)
+
+
 for name, (indptr, indices, n_src) in gat_ref.edge_graphs().items():
     n = indptr.size - 1
     F, F_T = csr(indptr, indices, n_src), csr(*gat_ref.transpose_pattern(indptr, indices, n_src), n)
@@ -110,6 +132,7 @@ for name, (indptr, indices, n_src) in gat_ref.edge_graphs().items():
         tag = f"{name} K={K} dh={dh}" + (" off=1" if off else "")
         run_v1(tag, F, F_T, n, n_src, K, dh, off)
         run_v2(tag, F, F_T, n, n_src, K, dh, off)
+        run_dot(tag, F, F_T, n, n_src, K, dh, off)
 
 rows = 2 * 256 * COLSUM_BLOCKS + 77                 # width 1: a workgroup takes 256 rows, so this is beyond two passes
 P, G_att = dense(np.random.default_rng(1).standard_normal((rows, 1), dtype=np.float32)), dense((1, 1))

@@ -239,16 +239,31 @@ def test_ops_refuse_bad_shapes_before_the_library(pkg):
         ops.gatdot_forward(None, F, M(8, 34), M(8, 34), M(8, 34), M(8, 34), M(8, 17), 17)
 
 
-def test_no_instantiation_uses_scratch(tmp_path):
-    """csrc/gatdot.hip compiled for gfx950 to assembly: the resource metadata of every kernel whose name contains gatdot_
-    reports a private segment of zero bytes and zero spilled vector registers -- all fifteen instantiations (three kernels x
-    five (VEC, NT, U)); backward_src holds six head-row arrays per lane and is the one closest to the limit"""
+# per attention file: the prefix of its kernels' names and the instantiations of each templated kernel -- gat_dispatch's five
+# (VEC, NT, U) x the flags (gat.hip: DROP on the three sparse kernels, REC on backward_src as well, KV = 4 / 1 on the export;
+# gatv2.hip: REC on backward_src)
+ATTENTION_KERNELS = {
+    "gat.hip": ("gat_", dict(gat_forward_kernel=10, gat_backward_dst_kernel=10, gat_backward_src_kernel=20,
+                             gat_alpha_kernel=2)),
+    "gatv2.hip": ("gatv2_", dict(gatv2_forward_kernel=5, gatv2_backward_dst_kernel=5, gatv2_backward_src_kernel=10,
+                                 gatv2_alpha_kernel=5)),
+    "gatdot.hip": ("gatdot_", dict(gatdot_forward_kernel=5, gatdot_backward_dst_kernel=5, gatdot_backward_src_kernel=5)),
+}
+
+
+@pytest.mark.parametrize("source", sorted(ATTENTION_KERNELS))
+def test_no_instantiation_uses_scratch(tmp_path, source):
+    """csrc/gat.hip, gatv2.hip and gatdot.hip compiled for gfx950 to assembly: the resource metadata of every kernel whose
+    name contains the file's prefix reports a private segment of zero bytes and zero spilled vector registers -- every
+    instantiation of ATTENTION_KERNELS, and in gatdot.hip nothing else: all fifteen (three kernels x five (VEC, NT, U));
+    its backward_src holds six head-row arrays per lane and is the one closest to the limit"""
+    prefix, counts = ATTENTION_KERNELS[source]
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
-    out = tmp_path / "gatdot.s"
+    out = tmp_path / (source + ".s")
     r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-S",
-                        "--cuda-device-only", os.path.join(ROOT, "mg-gcn_amd", "csrc", "gatdot.hip"), "-o", str(out)],
+                        "--cuda-device-only", os.path.join(ROOT, "mg-gcn_amd", "csrc", source), "-o", str(out)],
                        capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     text = out.read_text()
@@ -257,13 +272,14 @@ def test_no_instantiation_uses_scratch(tmp_path):
     for b in re.split(r"\n\s*- \.agpr_count:", "\n" + meta)[1:]:
         blk = ".agpr_count:" + b
         nm = re.search(r"\.name:\s+(\S+)", blk)
-        if not nm or "gatdot_" not in nm.group(1):
+        if not nm or prefix not in nm.group(1):
             continue
         field = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
                  for k in ("private_segment_fixed_size", "vgpr_spill_count", "vgpr_count", "agpr_count")}
         seen[nm.group(1)] = field
-        print(f"[gatdot] {nm.group(1)}: {field}")
+        print(f"[{source}] {nm.group(1)}: {field}")
         assert field["private_segment_fixed_size"] == 0 and field["vgpr_spill_count"] == 0, (nm.group(1), field)
-    assert len(seen) == 15, sorted(seen)
-    for kernel in ("gatdot_forward_kernel", "gatdot_backward_dst_kernel", "gatdot_backward_src_kernel"):
-        assert sum(kernel in k for k in seen) == 5, kernel
+    if source == "gatdot.hip":
+        assert len(seen) == 15, sorted(seen)
+    for kernel, count in counts.items():
+        assert sum(kernel in k for k in seen) == count, (kernel, sorted(seen))
