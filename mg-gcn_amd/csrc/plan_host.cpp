@@ -235,6 +235,23 @@ uint32_t sweep_panel_rows(uint32_t d_hint, bool hot_columns) {
     return std::max<uint32_t>(64u, env_u32("MGGCN_SPMM_PANEL_ROWS", 4096u));
 }
 
+double round_excess(const SweepHost &P) {
+    if (!P.round_tasks || P.tasks.empty()) return 0.0;
+    double sum_max = 0.0, sum_mean = 0.0;
+    for (size_t t0 = 0; t0 < P.tasks.size(); t0 += P.round_tasks) {
+        const size_t t1 = std::min(P.tasks.size(), t0 + (size_t)P.round_tasks);
+        uint64_t longest = 0, total = 0;
+        for (size_t t = t0; t < t1; t++) {
+            const uint64_t len = P.tasks[t].end - P.tasks[t].beg;
+            longest = std::max(longest, len);
+            total += len;
+        }
+        sum_max += (double)longest;
+        sum_mean += (double)total / (double)(t1 - t0);
+    }
+    return sum_mean > 0.0 ? sum_max / sum_mean - 1.0 : 0.0;
+}
+
 bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices, const float *values,
                       uint32_t max_d, bool force, uint32_t d_hint, bool hot_columns, uint32_t num_cu, SweepHost &P) {
     if (!n_rows || !indices || !values) return false;
@@ -511,6 +528,26 @@ bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, 
     std::vector<uint64_t> plen(T, 0);
     for (uint32_t t = 0; t < T; t++) plen[t] = plen_c[(size_t)t * NC + pick];
     std::vector<uint64_t>().swap(plen_c);
+    auto padded_len = [&](uint32_t t) { return (plen[t] + batch_pad - 1) / batch_pad * batch_pad; };
+    // Launch rounds of equal-length tasks.  A launch lasts as long as its longest task, and a wave that is done early leaves
+    // its slot empty: LPT on non-zeros with whole rows makes two classes of task (14 and 15 rows on the Reddit shape, 7 % of a
+    // task apart) and used to spread them over every round -- each round as long as a 15-row task with a 14.2-row mean.  The
+    // sum over the rounds of the longest task is smallest when the rounds are cut from the tasks in order of length.  Only
+    // the position in the task table moves: rows, entry sequence and partial-sum slots of every task stay
+    // (MGGCN_SPMM_SORT_ROUNDS=0: the table in LPT order).  Not for the XCD column layout: its task index encodes the slice.
+    if (XS == 1 && env_u32("MGGCN_SPMM_SORT_ROUNDS", 1u)) {
+        std::vector<uint32_t> order(T);
+        for (uint32_t t = 0; t < T; t++) order[t] = t;
+        std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return padded_len(a) > padded_len(b); });   // ties: old index
+        std::vector<std::vector<uint32_t>> sorted_bins(T);
+        std::vector<uint64_t> sorted_plen(T);
+        for (uint32_t t = 0; t < T; t++) {
+            sorted_bins[t].swap(bins[order[t]]);
+            sorted_plen[t] = plen[order[t]];
+        }
+        bins.swap(sorted_bins);
+        plen.swap(sorted_plen);
+    }
     std::vector<SweepTask> &tasks = P.tasks;
     std::vector<uint32_t> &task_rows = P.task_rows;
     tasks.assign(T, SweepTask{0, 0, 0, 0});
@@ -518,7 +555,7 @@ bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, 
     uint64_t off = 0;
     for (uint32_t t = 0; t < T; t++) {
         tasks[t].beg = (uint32_t)off;
-        off += (plen[t] + batch_pad - 1) / batch_pad * batch_pad;   // whole 64-byte batches (two per step in the quad form)
+        off += padded_len(t);                                       // whole 64-byte batches (two per step in the quad form)
         tasks[t].end = (uint32_t)off;
         tasks[t].n_rows = (uint32_t)bins[t].size();
         tasks[t].pad = 0;
@@ -566,6 +603,7 @@ bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, 
     P.n_tasks = T; P.round_tasks = round_tasks; P.run_pad = G; P.lpe = lpe;
     P.n_slots = n_slots;
     P.panel_rows = panel_rows; P.n_entries = off; P.num_cu = num_cu;
+    P.round_excess = round_excess(P);
     {   // priority rotation (float4 kernels; see rotate_priority): period 2^8 entries / every chunk of the narrow stream
         const uint32_t rot = (env_u32("MGGCN_SPMM_PRIO_ROTATE", 1u) ? kFlagPrioRotate : 0u) | (num_cu << kNumCuPos);
         P.prio_bits_wide = rot | (std::min(env_u32("MGGCN_SPMM_PRIO_SHIFT", 8u), 15u) << kPrioShiftPos);

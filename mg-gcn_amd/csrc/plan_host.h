@@ -82,6 +82,11 @@ struct SweepHost {
     uint32_t prio_bits_wide = 0, prio_bits_narrow = 0;   // kFlagPrioRotate | shift << kPrioShiftPos | CUs << kNumCuPos
     uint32_t tasks_per_wave = 1;
     bool allow_quad = true, allow_vec4 = true, fast_pairs = true;
+    double round_excess = 0.0;     // sum over the launch rounds of the longest task / sum of the rounds' mean task, minus 1
+    // Task order (MGGCN_SPMM_SORT_ROUNDS, default 1): tasks in non-increasing padded length (end - beg), ties in the order
+    // the LPT pass made them; a launch round is a contiguous chunk of round_tasks tasks of that order, so the tasks that
+    // share a launch are as close in length as the plan allows.  With the knob at 0, and always in the experimental XCD
+    // column layout (its task index encodes the slice), the table stays in LPT order.
     std::vector<SweepTask> tasks;
     std::vector<Entry> entries;
     std::vector<uint32_t> task_rows;           // n_tasks x kRW: output row or kSlotFlag | slot
@@ -94,6 +99,9 @@ uint32_t sweep_panel_rows(uint32_t d_hint, bool hot_columns);       // rows of B
 // units of the device the plan is for (a launch round = the resident set: num_cu x blocks per CU x 4 waves).
 bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices, const float *values,
                       uint32_t max_d, bool force, uint32_t d_hint, bool hot_columns, uint32_t num_cu, SweepHost &out);
+// what the rounds of a plan lose to their longest task: sum_rounds max(end - beg) / sum_rounds mean(end - beg) - 1 over
+// chunks of round_tasks tasks (0 = every launch ends together)
+double round_excess(const SweepHost &plan);
 
 // ---- passes of mggcn_spmm_plan_create_for over the whole matrix ----------------------------------
 // every column index < n_cols?  (one threaded read-only pass on behalf of the calling thread, which reports)

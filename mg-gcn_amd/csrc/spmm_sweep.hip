@@ -839,6 +839,7 @@ struct SweepPlan {
     uint32_t prio_bits_wide = 0, prio_bits_narrow = 0;   // kFlagPrioRotate | shift << kPrioShiftPos | CUs << kNumCuPos
     uint32_t tasks_per_wave = 1;
     bool allow_quad = true, allow_vec4 = true, fast_pairs = true;
+    double round_excess = 0.0;     // what the launch rounds lose to their longest task (mggcn_plan::round_excess)
 };
 
 // compute units of the current device (a launch round is sized to the resident set; a partitioned device has fewer)
@@ -863,6 +864,7 @@ SweepPlan *sweep_plan_build(uint32_t n_rows, uint32_t n_cols, const uint32_t *in
     p->panel_rows = h.panel_rows; p->n_entries = h.n_entries; p->num_cu = h.num_cu;
     p->prio_bits_wide = h.prio_bits_wide; p->prio_bits_narrow = h.prio_bits_narrow; p->tasks_per_wave = h.tasks_per_wave;
     p->allow_quad = h.allow_quad; p->allow_vec4 = h.allow_vec4; p->fast_pairs = h.fast_pairs;
+    p->round_excess = h.round_excess;
     const size_t tb = h.tasks.size() * sizeof(SweepTask), eb = h.entries.size() * sizeof(uint2);
     const size_t rb = h.task_rows.size() * sizeof(uint32_t), sb = h.split_rows.size() * sizeof(SweepSplitRow);
     const size_t pb = (size_t)h.n_slots * max_d * sizeof(float);
@@ -902,9 +904,9 @@ size_t sweep_plan_bytes(const SweepPlan *p) { return p ? p->bytes : 0; }
 // one line per slice plan for MGGCN_SPMM_PLAN_LOG / mggcn_spmm_plan_describe
 int sweep_plan_describe(const SweepPlan *p, char *out, size_t cap) {
     if (!p) return 0;
-    return std::snprintf(out, cap, "tasks=%u rounds=%u panel_rows=%u run_pad=%u lpe=%u entries=%llu split_rows=%u slots=%u",
+    return std::snprintf(out, cap, "tasks=%u rounds=%u panel_rows=%u run_pad=%u lpe=%u entries=%llu split_rows=%u slots=%u round_excess=%.4f",
                          p->n_tasks, (p->n_tasks + p->round_tasks - 1) / p->round_tasks, p->panel_rows, p->run_pad, p->lpe,
-                         (unsigned long long)p->n_entries, p->n_split_rows, p->n_slots);
+                         (unsigned long long)p->n_entries, p->n_split_rows, p->n_slots, p->round_excess);
 }
 uint32_t sweep_plan_tasks(const SweepPlan *p) { return p ? p->n_tasks : 0; }
 uint32_t sweep_plan_split_rows(const SweepPlan *p) { return p ? p->n_split_rows : 0; }
