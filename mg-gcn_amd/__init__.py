@@ -9,14 +9,18 @@ Layout:
   _lib.py      ctypes binding (fails loudly when the engine is missing; no CPU path)
   matrix.py    context / csr_matrix / dn_matrix        (reference src/matrix.hpp)
   ops.py       matmul / get_matmul_buffer / kernels     (reference src/cuda_utils.hpp)
-  gcn.py       sparse_linear / linear / gcn_layer / gcn (reference src/gcn.hpp)
+  gcn.py       sparse_linear / linear / gcn_layer / gcn (reference src/gcn.hpp); param_owner: one table row per trained
+               tensor; layer_params: a layer's owners; model_base: the epoch gcn and gat share
   gat.py       attention / gat_layer / gat: graph attention layers, GAT and (variant="v2": attention_v2 / gatv2_layer)
                GATv2 and (variant="dot": attention_dot / gatdot_layer) dot-product attention; gated_skip: the skip
-               connection and gate of skip="add" | "gate" (no reference counterpart)
-  dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*)
+               connection and gate of skip="add" | "gate" (no reference counterpart); attention_model: the dropouts and
+               the export gat and dist_gat share
+  dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*); dist_model_base:
+               the epoch dist_gcn and dist_gat share
   dist_gat.py  dist_attention / dist_gat_layer / dist_gat (and the _v2 / gatv2 twins): gat on the row partition (exported by dist)
   datasets.py  on-disk format + synthetic generators    (reference test/data/prep.py); the checkpoint file
-  checkpoint.py  save / load / predict of gcn, dist_gcn, gat and dist_gat (no reference counterpart)
+  checkpoint.py  save / load / predict of gcn, dist_gcn, gat and dist_gat, named from the owners' tables (no reference
+                 counterpart)
   selection.py   model_selector: best epoch on a split, early stopping
 """
 from . import _lib, datasets                                   # noqa: F401

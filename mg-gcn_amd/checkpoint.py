@@ -8,6 +8,9 @@ other and a resumed run draws the masks the uninterrupted run would have drawn. 
 type with it (model, variant, heads, attn_slope, the attention dropout probability: version 3 of the file) and per layer
 W, b and att; their two masks are counter-based on (seed, epoch * 64 + layer, ...), so the same holds for them.
 
+Which tensors a model has, under which names and in which order, is not listed here: model_params reads it from the layers'
+owners() and the owners' params_table (gcn.layer_params, gcn.param_owner), the tables Adam runs from.
+
 Nothing here launches a new kernel: the tensors move through dn_matrix.init (host to device, in place), dn_matrix.zero and
 dn_matrix.copy_to.  A model that never calls these members runs exactly what it ran before.
 """
@@ -28,25 +31,15 @@ def raw_context(ctx):
 
 def model_params(model) -> List[tuple]:
     """[(name, owner, parameter attribute, m attribute, v attribute)] in file order (datasets.checkpoint_tensors); the
-    owner is the linear, attention or layer_norm that holds the tensor, its Adam moments and its step count.  A layer is
-    read generically: ``lin``, then ``attn`` (a GAT layer), ``res_lin`` and ``norm`` where it has one."""
-    out = []
-    for l, layer in enumerate(model.layers_):
-        out += [(f"W{l}", layer.lin, "W", "mW", "vW"), (f"b{l}", layer.lin, "b", "mb", "vb")]
-        attn, res_lin, gate, norm = (getattr(layer, a, None) for a in ("attn", "res_lin", "gate", "norm"))
-        if attn is not None and attn.att is not None:           # gat.attention_dot has no parameter
-            out += [(f"att{l}", attn, "att", "m", "v")]
-        if res_lin is not None:
-            out += [(f"res_W{l}", res_lin, "W", "mW", "vW"), (f"res_b{l}", res_lin, "b", "mb", "vb")]
-        if gate is not None:                                    # gat.gated_skip with skip="gate"
-            out += [(f"gate{l}", gate, "w", "m", "v")]
-        if norm is not None:
-            out += [(f"gamma{l}", norm, "gamma", "mg", "vg"), (f"beta{l}", norm, "beta", "mb", "vb")]
-    return out
+    owner is the gcn.param_owner that holds the tensor, its Adam moments and its step count.  Nothing is listed here: a
+    layer names its owners and their file prefixes (owners()), an owner its tensors (params_table), and a tensor's name
+    is prefix + stem + layer index -- W0, b0, att0, res_W0, res_b0, gate0, gamma0, beta0 for a layer that has them all."""
+    return [(f"{prefix}{stem}{l}", owner, p, m, v) for l, layer in enumerate(model.layers_)
+            for prefix, owner in layer.owners() for stem, p, _, m, v, _ in owner.params_table]
 
 
 def model_owners(model) -> list:
-    """every linear, attention and layer_norm of the model: what carries Adam state"""
+    """every param_owner of the model that holds a tensor: what carries Adam state"""
     return [p for layer in model.layers_ for p in layer.params()]
 
 

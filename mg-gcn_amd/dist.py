@@ -1005,7 +1005,99 @@ def _repl_view(dn):
     return w
 
 
-class dist_gcn(dropout_option, checkpoint_option):
+class dist_model_base(dropout_option, checkpoint_option):
+    """The epoch of a row-partitioned model, whatever its layers are (dist_gcn, dist_gat.dist_gat): gcn.model_base with a
+    dist_context and dist_row_dn_matrix operands, the gradient all-reduces awaited before Adam and the loss sums riding on
+    the last layer's.  The constructor of the model sets ``loss_layer`` (a dist_row_softmax_cross_entropy_loss),
+    ``layers_``, ``loss``, ``_out_width``, ``fused``, ``_adam`` and ``_loss_host`` (both None); a layer is called with
+    (dctx, H), has backward(dctx, G), finish_backward, adam_update and params(), ``lin`` (a dist_row_linear: its ``tail``)
+    and ``AHW`` (its output), and takes its ``dropout`` from _arm_dropout."""
+
+    def set_splits(self, dctx: dist_context, Sd, train_set: int = 0) -> None:
+        """Train on one split (see gcn.set_splits).  Sd: THIS RANK's rows of the sets, as an int32 dist_row_dn_matrix (or a
+        host array of the rank's rows); None switches the splits off.  The four global counts come from one host
+        all-reduce, here; every rank must call this."""
+        if Sd is None:
+            self.loss_layer.set_splits(None)
+            return
+        local = Sd.local if isinstance(Sd, dist_row_dn_matrix) else Sd
+        rows = self.layers_[-1].AHW.n()
+        host = check_sets(local, rows, train_set)
+        counts = global_split_counts(dctx, host, train_set)
+        if not isinstance(local, dn_matrix):
+            local = dn_matrix.from_numpy(host, dctx.ctx.device)
+        self.loss_layer.set_splits(local, counts, train_set)
+
+    def split_metrics(self):
+        """every split's global (loss, acc) of the last epoch: the same numbers on every rank"""
+        if self.loss_layer.inner.S is None:
+            raise ValueError("split_metrics() needs set_splits(dctx, Sd) first")
+        return self.loss_layer.split_metrics()
+
+    def __call__(self, dctx, H, training: bool = False):
+        """the forward pass; ``training``: a training forward (train_forward / train_step), the only kind that drops"""
+        self._arm_dropout(training)
+        for layer in self.layers_:
+            H = layer(dctx, H)
+        return H
+
+    def _check_targets(self, Y) -> None:
+        check_targets(self.loss, getattr(Y, "local", Y), self.layers_[-1].AHW.n(), self._out_width)
+
+    def train_forward(self, dctx: dist_context, H: dist_row_dn_matrix, Y: dist_row_dn_matrix):
+        self._check_targets(Y)
+        H = self(dctx, H, training=True)
+        return self.loss_layer(dctx, H, Y)
+
+    def backward(self, dctx: dist_context) -> None:
+        G = self.loss_layer.backward()
+        for layer in reversed(self.layers_):
+            G = layer.backward(dctx, G)
+        for layer in self.layers_:                 # gradients are summed over ranks from here on
+            layer.finish_backward(dctx)
+
+    def adam_update(self, dctx, lr, beta1, beta2, weight_decay, eps) -> None:
+        if not self.fused:
+            for layer in self.layers_:
+                layer.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
+            return
+        for layer in self.layers_:
+            layer.finish_backward(dctx)
+        self._adam = adam_update_all(dctx.ctx, [p for l in self.layers_ for p in l.params()], self._adam, lr,
+                                     beta1, beta2, weight_decay, eps)
+
+    def train_step(self, dctx: dist_context, H: dist_row_dn_matrix, Y: dist_row_dn_matrix, lr, beta1, beta2,
+                   weight_decay, eps):
+        """forward + loss + backward + Adam with ONE host synchronisation and the loss all-reduce at the
+        end of the epoch (see gcn.train_step); the reference's loop body is src/main.cpp:159-166."""
+        torch = _torch()
+        self._check_targets(Y)
+        out = self(dctx, H, training=True)
+        self.loss_layer(dctx, out, Y, sync=False)
+        # The loss sums (two, or the eight of the splits; four or sixteen with loss="bce") ride on the LAST layer's gradient
+        # all-reduce (eight or sixteen spare floats behind [G_W | G_b]) instead of a collective and a device-to-host copy of
+        # their own after the epoch's synchronisation:
+        # at P = 8 that turn-around was ~0.1 ms of idle GPU per 3.5-ms epoch.  (The reference adds its P managed scalars on
+        # the host, src/gcn.hpp:929.)
+        st = dctx.ctx.cuda_streams[0]
+        mine = self.loss_layer.inner.active_sums()
+        tail = self.layers_[-1].lin.tail[:mine.numel()]
+        with torch.cuda.stream(st):
+            tail.copy_(mine)
+        self.backward(dctx)                                    # ... -> finish_backward: the compute stream sees the summed buffers
+        self.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
+        if self._loss_host is None:
+            self._loss_host = torch.empty(self.layers_[-1].lin.tail.numel(), dtype=torch.float32, pin_memory=True)
+        host = self._loss_host[:mine.numel()]
+        with torch.cuda.stream(st):
+            host.copy_(tail, non_blocking=True)
+        dctx.sync()
+        return self.loss_layer.read(dctx, host.numpy())
+
+    def layers(self): return self.layers_
+
+
+class dist_gcn(dist_model_base):
     """reference src/gcn.hpp:997-1056 (row_partition = true): per-GPU HW_buffer and two
     receive buffers shared by all layers (:1016-1021); layers get (A_T, A) (:1023).
 
@@ -1069,29 +1161,7 @@ class dist_gcn(dropout_option, checkpoint_option):
                     [M.diag] + (list(M.remote_chunks) if mode == "allgather" and P > 1 else [])
                 self._plan_wants += [(blk, max(w, 128), w) for blk in parts]
 
-    def set_splits(self, dctx: dist_context, Sd, train_set: int = 0) -> None:
-        """Train on one split (see gcn.set_splits).  Sd: THIS RANK's rows of the sets, as an int32 dist_row_dn_matrix (or a
-        host array of the rank's rows); None switches the splits off.  The four global counts come from one host
-        all-reduce, here; every rank must call this."""
-        if Sd is None:
-            self.loss_layer.set_splits(None)
-            return
-        local = Sd.local if isinstance(Sd, dist_row_dn_matrix) else Sd
-        rows = self.layers_[-1].AHW.n()
-        host = check_sets(local, rows, train_set)
-        counts = global_split_counts(dctx, host, train_set)
-        if not isinstance(local, dn_matrix):
-            local = dn_matrix.from_numpy(host, dctx.ctx.device)
-        self.loss_layer.set_splits(local, counts, train_set)
-
-    def split_metrics(self):
-        """every split's global (loss, acc) of the last epoch: the same numbers on every rank"""
-        if self.loss_layer.inner.S is None:
-            raise ValueError("split_metrics() needs set_splits(dctx, Sd) first")
-        return self.loss_layer.split_metrics()
-
     def __call__(self, dctx, H, training: bool = False):
-        """the forward pass; ``training``: a training forward (train_forward / train_step), the only kind that drops"""
         if self._plan_wants:
             # with more than one rank these SpMMs run while RCCL's kernels share the device: launch rounds that leave (at least) 12
             # CUs' worth of wave slots free (include/mggcn.h: mggcn_spmm_plan_reserved_cus; profiles/r04_forced_dist_summary.md)
@@ -1104,65 +1174,7 @@ class dist_gcn(dropout_option, checkpoint_option):
                 if shared:
                     dctx.ctx.lib.mggcn_spmm_plan_reserved_cus(0)
             self._plan_wants = []
-        self._arm_dropout(training)
-        for layer in self.layers_:
-            H = layer(dctx, H)
-        return H
-
-    def _check_targets(self, Y) -> None:
-        check_targets(self.loss, getattr(Y, "local", Y), self.layers_[-1].AHW.n(), self._out_width)
-
-    def train_forward(self, dctx: dist_context, H: dist_row_dn_matrix, Y: dist_row_dn_matrix):
-        self._check_targets(Y)
-        H = self(dctx, H, training=True)
-        return self.loss_layer(dctx, H, Y)
-
-    def backward(self, dctx: dist_context) -> None:
-        G = self.loss_layer.backward()
-        for layer in reversed(self.layers_):
-            G = layer.backward(dctx, G)
-        for layer in self.layers_:                 # gradients are summed over ranks from here on
-            layer.finish_backward(dctx)
-
-    def adam_update(self, dctx, lr, beta1, beta2, weight_decay, eps) -> None:
-        if not self.fused:
-            for layer in self.layers_:
-                layer.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
-            return
-        for layer in self.layers_:
-            layer.finish_backward(dctx)
-        self._adam = adam_update_all(dctx.ctx, [p for l in self.layers_ for p in l.params()], self._adam, lr,
-                                     beta1, beta2, weight_decay, eps)
-
-    def train_step(self, dctx: dist_context, H: dist_row_dn_matrix, Y: dist_row_dn_matrix, lr, beta1, beta2,
-                   weight_decay, eps):
-        """forward + loss + backward + Adam with ONE host synchronisation and the loss all-reduce at the
-        end of the epoch (see gcn.train_step); the reference's loop body is src/main.cpp:159-166."""
-        torch = _torch()
-        self._check_targets(Y)
-        out = self(dctx, H, training=True)
-        self.loss_layer(dctx, out, Y, sync=False)
-        # The loss sums (two, or the eight of the splits; four or sixteen with loss="bce") ride on the LAST layer's gradient
-        # all-reduce (eight or sixteen spare floats behind [G_W | G_b]) instead of a collective and a device-to-host copy of
-        # their own after the epoch's synchronisation:
-        # at P = 8 that turn-around was ~0.1 ms of idle GPU per 3.5-ms epoch.  (The reference adds its P managed scalars on
-        # the host, src/gcn.hpp:929.)
-        st = dctx.ctx.cuda_streams[0]
-        mine = self.loss_layer.inner.active_sums()
-        tail = self.layers_[-1].lin.tail[:mine.numel()]
-        with torch.cuda.stream(st):
-            tail.copy_(mine)
-        self.backward(dctx)                                    # ... -> finish_backward: the compute stream sees the summed buffers
-        self.adam_update(dctx, lr, beta1, beta2, weight_decay, eps)
-        if self._loss_host is None:
-            self._loss_host = torch.empty(self.layers_[-1].lin.tail.numel(), dtype=torch.float32, pin_memory=True)
-        host = self._loss_host[:mine.numel()]
-        with torch.cuda.stream(st):
-            host.copy_(tail, non_blocking=True)
-        dctx.sync()
-        return self.loss_layer.read(dctx, host.numpy())
-
-    def layers(self): return self.layers_
+        return dist_model_base.__call__(self, dctx, H, training)
 
 
 from .dist_gat import (dist_attention, dist_attention_v2, dist_gat, dist_gat_layer,       # noqa: E402,F401

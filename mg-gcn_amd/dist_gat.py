@@ -22,8 +22,12 @@ ds_src and G_Z are the single-GPU rows bit for bit at any P (given the same Z an
 mask is drawn with dst0 = p_r, src0 = 0 over F and dst0 = 0, src0 = p_r over F^T.  Only sums over vertices (G_W, G_b, G_att,
 the loss sums) round differently.  A single rank exchanges nothing unless dist_context.self_gather.
 
-attention_weights / attention_pattern: a rank exports the coefficients of its rows' entries (gat.attention_weights on the
-row block; no collective of its own), the single-GPU export's rows bit for bit.
+dist_gat is gat.attention_model (set_dropout, the masks, attention_weights: what gat has too) over dist.dist_model_base (the
+epoch of dist_gcn); of the mix-in it answers one hook, _mask_origin() = (p_r, 0).
+
+attention_weights / attention_pattern: a rank exports the coefficients of its rows' entries (gat.attention_model's
+attention_weights on the row block; no collective of its own), the single-GPU export's rows bit for bit: one [nnz of the rank's
+row block x heads] dn_matrix per requested layer, the rows [indptr[p_r], indptr[p_{r+1}]) of the single-GPU model's export.
 
 ``variant="v2"`` (GATv2): the layer's one linear gives Z2_loc = [Zs | Zd] of 2 out columns and ONE
 all-gather of that shard gives Z2_all, of which the forward and backward_dst over the row block of F read the Zs half
@@ -46,11 +50,11 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import ops
-from .checkpoint import checkpoint_option
-from .dist import (_repl_view, _torch, _wrap_local, dist_context, dist_gcn, dist_row_csr_matrix, dist_row_dn_matrix,
+from .dist import (_repl_view, _torch, _wrap_local, dist_context, dist_model_base, dist_row_csr_matrix, dist_row_dn_matrix,
                    dist_row_linear, dist_row_softmax_cross_entropy_loss, partition_bounds)
-from .gat import attention, attention_v2, check_heads, check_single_gpu_variant, check_variant, gat, gat_layer
-from .gcn import check_dropout, check_loss, dropout_option
+from .gat import (attention, attention_model, attention_v2, check_heads, check_single_gpu_variant, check_variant,
+                  gat_layer)
+from .gcn import check_dropout, check_loss
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -172,6 +176,9 @@ class dist_gat_layer(gat_layer):
     def adam_update(self, dctx, lr, beta1, beta2, weight_decay, eps):
         gat_layer.adam_update(self, dctx.ctx, lr, beta1, beta2, weight_decay, eps)
 
+    def alpha(self, dctx: dist_context, out: Optional[dn_matrix] = None) -> dn_matrix:
+        return gat_layer.alpha(self, dctx.ctx, out)
+
     def att(self): return _repl_view(self.attn.att)
     def Gatt(self): return _repl_view(self.attn.G_att)
 
@@ -270,7 +277,7 @@ class dist_gatv2_layer(dist_gat_layer):
         self.AHW = self.act
 
 
-class dist_gat(dropout_option, checkpoint_option):
+class dist_gat(attention_model, dist_model_base):
     """gat.gat on the row partition.
 
     dist_gat(dctx, A, A_T, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0,
@@ -284,8 +291,8 @@ class dist_gat(dropout_option, checkpoint_option):
     Every rank calls every method with the same arguments.  set_dropout(p, seed, epoch, attn): a rank drops its rows of
     the masks the single-GPU model draws (feature dropout with row0 = p_r; attention dropout see the module docstring).
     __call__, train_forward, backward, adam_update, train_step (one synchronisation; the loss sums ride on the last layer's
-    gradient all-reduce), set_splits(dctx, Sd), split_metrics and layers() are dist_gcn's, which has no evaluate()
-    either: a plain call is the forward that never drops.  save(dctx, path, optimizer=True) / load(dctx, path) /
+    gradient all-reduce), set_splits(dctx, Sd), split_metrics and layers() are dist.dist_model_base's, as for dist_gcn, which
+    has no evaluate() either: a plain call is the forward that never drops.  save(dctx, path, optimizer=True) / load(dctx, path) /
     predict(dctx, X): see checkpoint.checkpoint_option -- a refused load raises on every rank alike, before any collective."""
 
     def __init__(self, dctx: dist_context, A: dist_row_csr_matrix, A_T: dist_row_csr_matrix, sizes: Sequence[int], heads=4,
@@ -333,60 +340,12 @@ class dist_gat(dropout_option, checkpoint_option):
                 if len(w) > 2:
                     layer.attn.init(w[2])
 
-    # gat's own functions, borrowed unbound (this class is no gat: its layers and its calls take a dist_context).  set_dropout
-    # touches _dropout_layers, _dropout_params, dropout_p, dropout_seed, dropout_epoch (dropout_option) and
-    # _attn_dropout_params, attn_dropout_p; _arm_dropout reads those and layers_, and sets every layer's ``dropout`` and
-    # ``attn_dropout``.  Nothing else.
-    set_dropout = gat.set_dropout
-
-    def _arm_dropout(self, training: bool) -> None:
-        """gat's, with the attention mask's destinations offset by the rank's first row"""
-        gat._arm_dropout(self, training)
-        for layer in self.layers_:
-            if layer.attn_dropout is not None:
-                layer.attn_dropout = (*layer.attn_dropout[:4], self.row0, 0)
-
-    def __call__(self, dctx: dist_context, H: dist_row_dn_matrix, training: bool = False) -> dist_row_dn_matrix:
-        """the forward pass; ``training``: a training forward (train_forward / train_step), the only kind that drops"""
-        self._arm_dropout(training)
-        for layer in self.layers_:
-            H = layer(dctx, H)
-        return H
-
-    def layers(self) -> List[dist_gat_layer]:
-        return self.layers_
-
-    _alpha_requests = gat._alpha_requests       # reads layers_ (their F) and heads: the checks that need no device
-
-    def attention_weights(self, dctx: dist_context, X: Optional[dist_row_dn_matrix] = None, layers=None,
-                          out=None) -> List[dn_matrix]:
-        """gat.attention_weights on the row partition; every rank calls it with the same arguments.  A rank gets the
-        entries of ITS rows: one [nnz of the rank's row block x heads] dn_matrix per requested layer, row p for entry p of
-        attention_pattern()'s ``indices`` -- the rows [indptr[p_r], indptr[p_{r+1}]) of the single-GPU model's export, bit
-        for bit given the same weights.  With ``X`` (a dist_row_dn_matrix) a plain forward runs first, with the collectives
-        every forward has; the export itself runs none.  Without, the state of the most recent forward is exported (after
-        attention dropout: the coefficients before the dropout factor).  ValueError before any device work or collective,
-        on every rank alike, for a layer index out of range, an ``out`` of the wrong length or shape, or no forward yet."""
-        which = self._alpha_requests(layers, out)
-        if X is not None:
-            self(dctx, X)
-        elif any(self.layers_[li].H is None for li in which):
-            raise ValueError("attention_weights: no forward has run, there are no attention coefficients yet (pass X)")
-        return [self.layers_[li].alpha(dctx.ctx, None if out is None else out[i]) for i, li in enumerate(which)]
+    def _mask_origin(self):
+        """the rank's row block of the forward matrix: destinations from the rank's first row, every source"""
+        return self.row0, 0
 
     def attention_pattern(self):
         """(indptr, indices): the host arrays of the rank's row block of the matrix the forward walks -- row i is the
         rank's destination p_r + i, its entries are its sources as GLOBAL vertex numbers, and row p of every matrix
         attention_weights returns belongs to indices[p]"""
         return self.F.indptr, self.F.indices
-
-    # the model-level plumbing is dist_gcn's, word for word: it only touches what the two classes share (loss_layer, layers_
-    # with lin / AHW / finish_backward / params, loss, fused, _adam, _loss_host, _out_width and the calls above)
-    set_splits = dist_gcn.set_splits
-    split_metrics = dist_gcn.split_metrics
-    _check_targets = dist_gcn._check_targets
-    train_forward = dist_gcn.train_forward
-    backward = dist_gcn.backward
-    adam_update = dist_gcn.adam_update
-    train_step = dist_gcn.train_step
-

@@ -57,6 +57,11 @@ in-memory restore works, save_best does not), dist_gat(variant="dot"), and a gra
 layer reaches 2^31 elements (the limit of the GEMM's output).  predict, evaluate, split_metrics and model_selector work
 unchanged.
 
+The model is gcn.model_base (the epoch, splits, evaluate: what gcn is too) under attention_model, the mix-in dist_gat.dist_gat
+shares: set_dropout, the arming of the two masks and attention_weights.  Every trained tensor is one row of its owner's
+gcn.param_owner table -- att of attention and attention_v2, w of gated_skip, nothing of attention_dot -- and a layer lists
+its owners (gat_layer.owners): Adam, params() and the checkpoint's names follow from those.
+
 save / load / predict and model_selector are gcn's (checkpoint.checkpoint_option, selection.model_selector): the file stores
 the layer type -- variant, heads, attn_slope, the attention dropout probability -- next to W, b and att of every layer
 (version 3 of the checkpoint file, INTEGRATION.md "Checkpoint file"), and a resumed run is the uninterrupted run bit for bit
@@ -89,8 +94,8 @@ import numpy as np
 
 from . import _lib, ops
 from .checkpoint import checkpoint_option
-from .gcn import (DROPOUT_MAX_LAYERS, adam_update_all, check_dropout, check_loss, check_norm, dropout_option, gcn,
-                  layer_norm, linear, sigmoid_bce_loss, softmax_cross_entropy_loss)
+from .gcn import (DROPOUT_MAX_LAYERS, check_dropout, check_loss, check_norm, dropout_option, layer_norm, layer_params,
+                  linear, model_base, param_owner, sigmoid_bce_loss, softmax_cross_entropy_loss)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -111,45 +116,15 @@ def check_heads(sizes: Sequence[int], heads) -> List[int]:
     return [int(h) for h in per_layer]
 
 
-class adam_row:
-    """The Adam state of one parameter tensor of an attention model that decays like W -- ``att`` of attention and
-    attention_v2, ``w`` of gated_skip: the step counter, the lazily made ``m`` / ``v``, the row of ops.adam_table, and the
-    per-tensor step of gat(fused=False): one ops.adam_fused per row of adam_tensors(), the element-wise math of the
-    model-wide table bit for bit.  A class names its (parameter, gradient) in adam_pair(), read at call time (dist_attention
-    rebinds G_att after __init__)."""
-
-    m = v = None
-    step = 0
-
-    def adam_pair(self):
-        raise NotImplementedError
-
-    def adam_state(self, ctx: context) -> None:
-        if self.m is None:
-            p, _ = self.adam_pair()
-            self.m, self.v = dn_matrix(p.shape(), device=p.t.device), dn_matrix(p.shape(), device=p.t.device)
-            self.m.zero(ctx)
-            self.v.zero(ctx)
-            self.step = 0
-
-    def adam_tensors(self, weight_decay: float):
-        """row of ops.adam_table: the parameter decays like W"""
-        return [self.adam_pair() + (self.m, self.v, weight_decay)]
-
-    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
-        """one launch per tensor: the element-wise math of the model-wide table, bit for bit"""
-        self.adam_state(ctx)
-        self.step += 1
-        bc1 = float(np.float32(1 - beta1 ** self.step))
-        bc2 = float(np.float32(1 - beta2 ** self.step))
-        for p, g, m, v, wd in self.adam_tensors(weight_decay):
-            ops.adam_fused(ctx, p, g, m, v, lr, beta1, beta2, wd, bc1, bc2, eps)
-
-
-class attention(adam_row):
+class attention(param_owner):
     """The attention of one layer: the parameter ``att`` [2 x out] (row 0 the destination vector, row 1 the source
     vector; seed-99 uniform like W), its gradient and Adam state, and what the backward pass needs of the forward --
-    s_dst, s_src, lse [n x heads].  att is trained by Adam with the weight decay of W."""
+    s_dst, s_src, lse [n x heads].  att is trained by Adam with the weight decay of W; the per-tensor step of
+    gat(fused=False) is the fused kernel for every owner of an attention model, so both modes give the same bits."""
+
+    params_table = (("att", "att", "G_att", "m", "v", True),)
+    adam_fused = True
+    m = v = None
 
     def __init__(self, name: str, n_dst: int, n_src: int, out: int, heads: int, slope: float = ops.GAT_SLOPE, device=None):
         self.name, self.heads, self.slope = name, int(heads), float(slope)
@@ -159,9 +134,6 @@ class attention(adam_row):
         self.att.init(host)
         self.s_dst, self.lse, self.D, self.ds_dst = (dn_matrix(n_dst, heads, device=device) for _ in range(4))
         self.s_src, self.ds_src = dn_matrix(n_src, heads, device=device), dn_matrix(n_src, heads, device=device)
-
-    def adam_pair(self):
-        return self.att, self.G_att
 
     def __call__(self, ctx: context, F: csr_matrix, Z: dn_matrix, out: dn_matrix, drop=None) -> None:
         """out = the attention-weighted gather of Z over F's rows (destinations and sources are the same vertices);
@@ -260,7 +232,7 @@ def refuse_skip(model, what: str) -> None:
             raise ValueError(f'gat({option}="{value}") has no {what}')
 
 
-class gated_skip(adam_row):
+class gated_skip(param_owner):
     """The skip connection of one attention layer (gat(skip=...)): ``res_lin``, a linear r = H W_r + 1 b_r^T over the
     layer's own input -- always a linear, also where in == out (PyG's lin_skip) --, and the row kernels of
     csrc/gated_skip.hip that combine r with the attention output o: y = o + r ("add"), or y = g r + (1 - g) o with one
@@ -268,7 +240,12 @@ class gated_skip(adam_row):
     "gate" holds the parameter ``w`` [3 x out] (seed-99 uniform like att), its gradient and Adam state -- a row of the
     fused Adam table with W's weight decay -- and the rows' ``gate`` [n], which the backward pass reads again.  ``r`` is
     kept per layer with the gate (its backward needs it) and lives in ``buffer`` (the model's, at its widest layer) without;
-    ``G_r`` aliases ``buffer`` with the gate and is the layer's G_o without (one store)."""
+    ``G_r`` aliases ``buffer`` with the gate and is the layer's G_o without (one store).  The table is the gate's alone:
+    res_lin is a linear of its own among the layer's owners."""
+
+    params_table = (("gate", "w", "G_w", "m", "v", True),)
+    adam_fused = True
+    m = v = None
 
     def __init__(self, name: str, n: int, in_: int, out: int, mode: str, backward_out: bool = True, buffer=None, device=None):
         assert mode in ("add", "gate")
@@ -316,21 +293,8 @@ class gated_skip(adam_row):
             raise ValueError('gat(skip="add") has no gate parameter: skip_weights= takes (W_r, b_r) per layer')
         self.w.init(np.asarray(w, dtype=np.float32))
 
-    # the Adam row of the gate's parameter (res_lin is a linear of its own in the layer's params())
-    def adam_pair(self):
-        return self.w, self.G_w
 
-
-class gat_layer_norm(layer_norm):
-    """gcn.layer_norm as the attention layers use it: the same kernels, buffers and Adam rows (no weight decay); only the
-    per-tensor Adam step (gat(fused=False)) differs -- adam_row's: one ops.adam_fused per tensor, the element-wise math of
-    the model-wide table bit for bit, as for every other parameter of a gat model (gcn's own per-tensor step is the
-    reference's unfused chain, which rounds differently)."""
-
-    adam_update = adam_row.adam_update
-
-
-class gat_layer:
+class gat_layer(layer_params):
     """One GAT layer: a ``linear`` (Z = H W + 1 b^T), an ``attention`` over (F, F^T) and the activation.  Z, the
     aggregated ``out`` (before the activation: the backward pass needs it) and the activated output are kept per layer;
     G_Z aliases the model-wide buffer.  ``backward_out=False`` (the first layer) skips the GEMM that only produces the
@@ -338,6 +302,8 @@ class gat_layer:
     ("layer") a gcn.layer_norm after that, in every layer that has an activation: attention -> skip -> norm -> activation,
     the activation fused into whichever of the two runs last.  The attributes are ``res_lin`` (the skip's linear), ``gate``
     (the skip itself where it has the gate parameter) and ``norm``, each None where the layer has none."""
+
+    res_lin = gate = norm = None
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
                  slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None,
@@ -362,7 +328,7 @@ class gat_layer:
         self.skip = gated_skip(name, rows, in_, out, skip, lin.backward_out, skip_buffer, device) if skip is not None else None
         self.res_lin = self.skip.res_lin if self.skip is not None else None
         self.gate = self.skip if skip == "gate" else None
-        self.norm = gat_layer_norm(name, rows, out, True, device) if norm == "layer" and activation else None
+        self.norm = layer_norm(name, rows, out, True, device, adam_fused=True) if norm == "layer" and activation else None
         # the layer's output y: the last layer has no activation and returns ``out`` itself, unless a skip writes a y
         self.act = dn_matrix(rows, out, device=device) if activation or self.skip is not None else self.out
         self.G_Z = dn_matrix(rows, zw, G_Z_buffer) if G_Z_buffer is not None else dn_matrix(rows, zw, device=device)
@@ -459,22 +425,10 @@ class gat_layer:
     def linears(self):
         return [self.lin]
 
-    def _skip_params(self):
-        """res_lin, gate and norm where the layer has them (read with getattr: a layer built without _setup has none)"""
-        return [p for p in (getattr(self, a, None) for a in ("res_lin", "gate", "norm")) if p is not None]
+    def owners(self):
+        pairs = (("", self.lin), ("", self.attn), ("res_", self.res_lin), ("", self.gate), ("", self.norm))
+        return [(prefix, o) for prefix, o in pairs if o is not None]
 
-    def params(self):
-        """everything Adam updates"""
-        return [self.lin, self.attn] + self._skip_params()
-
-    def adam_update(self, ctx, lr, beta1, beta2, weight_decay, eps):
-        for p in self.params():
-            p.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
-
-    def b(self): return self.lin.get_b()
-    def W(self): return self.lin.get_W()
-    def GW(self): return self.lin.get_G_W()
-    def Gb(self): return self.lin.get_G_b()
     def att(self): return self.attn.att
     def Gatt(self): return self.attn.G_att
 
@@ -495,13 +449,12 @@ class gatv2_layer(gat_layer):
                     skip=skip, norm=norm, skip_buffer=skip_buffer)
 
 
-class attention_dot:
+class attention_dot(param_owner):
     """The dot-product attention of one layer: no parameter, only what the backward pass needs of the forward -- lse and D
     [n x heads] --, the head count and the scale c = fp32(1 / sqrt(dh)).  __call__ and backward take the layer's
-    Z3 = [Zq | Zk | Zv] and G_Z3 = [G_Zq | G_Zk | G_Zv] buffers of 3 out columns.  It is a row of nobody's Adam table."""
+    Z3 = [Zq | Zk | Zv] and G_Z3 = [G_Zq | G_Zk | G_Zv] buffers of 3 out columns.  Its table is empty: it is a row of nobody's Adam table."""
 
-    att = G_att = m = v = None          # what the generic readers (checkpoint.model_params) look for on an attention
-    step = 0
+    att = G_att = m = v = None          # what gat_layer.att() / Gatt() return for such a layer
 
     def __init__(self, name: str, n: int, out: int, heads: int, device=None):
         self.name, self.heads = name, int(heads)
@@ -529,15 +482,6 @@ class attention_dot:
     def init(self, att) -> None:
         raise ValueError('gat(variant="dot") has no attention parameter: weights= takes (W, b) per layer')
 
-    def adam_state(self, ctx: context) -> None:
-        pass
-
-    def adam_tensors(self, weight_decay: float):
-        return []
-
-    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
-        pass
-
 
 class gatdot_layer(gat_layer):
     """One dot-product attention layer: ONE ``linear`` of 3 out columns (Z3 = H W + 1 b^T = [Zq | Zk | Zv], the bias inside
@@ -553,9 +497,6 @@ class gatdot_layer(gat_layer):
 
     def alpha(self, ctx: context, out: Optional[dn_matrix] = None) -> dn_matrix:
         raise ValueError(f'gat layer {self.name}: gat(variant="dot") has no export of the attention coefficients')
-
-    def params(self):
-        return [self.lin] + self._skip_params()
 
 
 VARIANTS = ("v1", "v2", "dot")
@@ -585,7 +526,91 @@ def refuse_dot(model, what: str) -> None:
         raise ValueError(f'gat(variant="dot") has no {what}')
 
 
-class gat(dropout_option, checkpoint_option):
+def refuse_checkpoint(model, member: str) -> None:
+    """what save, load and _write_checkpoint of gat refuse, before anything is read, written or created: dot-product
+    attention and the skip options, which no version of the checkpoint file stores"""
+    refuse_dot(model, f"{member} has no version for this variant yet")
+    refuse_skip(model, f"{member} has no version that stores this option yet")
+
+
+class attention_model:
+    """What only the attention models have, gat and dist_gat.dist_gat alike (both list it first among their bases): the
+    two dropouts and the export of the coefficients.  It reads ``variant``, ``heads``, ``layers_`` (their F, H and alpha),
+    ``attn_dropout_p`` / ``_attn_dropout_params`` and the state of gcn.dropout_option; _mask_origin() is the hook of the row
+    partition."""
+
+    def set_dropout(self, p: float, seed: int = 0, epoch: int = 0, attn: Optional[float] = None) -> None:
+        """p: the drop probability of the layer inputs, attn: that of the attention coefficients (None keeps the current
+        one), both in [0, 1) and 0 = off; seed: 64 bits, shared by both; epoch: the number the next training forward gets
+        (set_dropout(p, seed, epoch=e) replays training forward e).  ValueError before any device work, and before
+        anything is stored."""
+        attn = self.attn_dropout_p if attn is None else attn
+        attn_params = check_dropout(attn, self._dropout_layers)
+        check_variant(self.variant, float(attn))
+        dropout_option.set_dropout(self, p, seed, epoch)
+        self._attn_dropout_params, self.attn_dropout_p = attn_params, float(attn)
+
+    def _mask_origin(self):
+        """(dst0, src0): the global vertex numbers of the first destination and the first source of this model's forward
+        matrix, which the attention mask is drawn on"""
+        return 0, 0
+
+    def _arm_dropout(self, training: bool) -> None:
+        """hands every layer its two calls of this forward (None: the plain path); a training forward with either
+        probability above 0 takes the current epoch number and moves it on.  Layer l uses stream epoch * 64 + l for both."""
+        feat = bool(training) and self.dropout_p > 0.0
+        attn = bool(training) and self.attn_dropout_p > 0.0
+        origin = self._mask_origin()
+        for li, layer in enumerate(self.layers_):
+            stream = (self.dropout_epoch * DROPOUT_MAX_LAYERS + li) & 0xFFFFFFFF
+            layer.dropout = (*self._dropout_params, self.dropout_seed, stream) if feat and li > 0 else None
+            layer.attn_dropout = (*self._attn_dropout_params, self.dropout_seed, stream, *origin) if attn else None
+        if feat or attn:
+            self.dropout_epoch += 1
+
+    def _alpha_requests(self, layers, out) -> List[int]:
+        """the layer indices ``layers=`` names, after every check attention_weights can make without the device"""
+        n_layers = len(self.layers_)
+        which = list(range(n_layers)) if layers is None else [int(li) for li in layers]
+        for li in which:
+            if not 0 <= li < n_layers:
+                raise ValueError(f"attention_weights: layer {li} is out of range, the model has {n_layers} layers")
+        if out is not None:
+            if len(out) != len(which):
+                raise ValueError(f"attention_weights: out lists {len(out)} matrices for {len(which)} layers")
+            for li, o in zip(which, out):
+                want = (self.layers_[li].F.nnz(), self.heads[li])
+                if o.shape() != want:
+                    raise ValueError(f"attention_weights: out of layer {li} must be {want[0]} x {want[1]}, got {o.shape()}")
+        return which
+
+    def attention_weights(self, ctx, X=None, layers=None, out=None) -> List[dn_matrix]:
+        """The attention coefficients alpha_ijk per layer (PyG's return_attention_weights): a list with one [nnz x heads]
+        dn_matrix per requested layer, whose row p belongs to entry p of attention_pattern()'s ``indices`` and whose
+        column k to head k.  With ``X`` a plain forward runs first (self(ctx, X), the forward that never drops); without,
+        the export is taken from the state the most recent forward left behind -- ValueError when there was none.  After
+        a training forward with attention dropout that state is the normalised coefficient BEFORE the dropout factor q:
+        the softmax runs over all entries there too, so the export is what a plain forward of the same weights and
+        inputs gives, not alpha q.  ``layers``: None for all, or layer indices, returned in the order given; ``out``: one
+        dn_matrix per requested layer to write into (None allocates).  ValueError before any device work for an index
+        out of range and for an ``out`` of the wrong length or shape.
+
+        On the row partition ``ctx`` and ``X`` are the rank's dist_context and dist_row_dn_matrix, every rank calls with the
+        same arguments and gets the entries of ITS rows (dist_gat.dist_gat); the export itself runs no collective.
+
+        The values are exp(e_ijk - lse[i, k]) as the backward kernels evaluate it (mggcn_gat_alpha_f32 /
+        mggcn_gatv2_alpha_f32): the coefficients the model trains with, the same bits on every call.  This is the one place
+        where something of nnz x heads is stored: the Reddit-shaped graph (114.8 M entries) at 4 heads needs 1.84 GB per
+        layer.  Nothing is allocated or launched unless this method (or gat_layer.alpha) is called."""
+        which = self._alpha_requests(layers, out)
+        if X is not None:
+            self(ctx, X)
+        elif any(self.layers_[li].H is None for li in which):
+            raise ValueError("attention_weights: no forward has run, there are no attention coefficients yet (pass X)")
+        return [self.layers_[li].alpha(ctx, None if out is None else out[i]) for i, li in enumerate(which)]
+
+
+class gat(attention_model, model_base):
     """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
 
     gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
@@ -679,86 +704,10 @@ class gat(dropout_option, checkpoint_option):
                 if len(w) > 2:
                     layer.attn.init(w[2])
 
-    def set_dropout(self, p: float, seed: int = 0, epoch: int = 0, attn: Optional[float] = None) -> None:
-        """p: the drop probability of the layer inputs, attn: that of the attention coefficients (None keeps the current
-        one), both in [0, 1) and 0 = off; seed: 64 bits, shared by both; epoch: the number the next training forward gets
-        (set_dropout(p, seed, epoch=e) replays training forward e).  ValueError before any device work, and before
-        anything is stored."""
-        attn = self.attn_dropout_p if attn is None else attn
-        attn_params = check_dropout(attn, self._dropout_layers)
-        check_variant(getattr(self, "variant", "v1"), float(attn))   # dist_gat borrows this method
-        dropout_option.set_dropout(self, p, seed, epoch)
-        self._attn_dropout_params, self.attn_dropout_p = attn_params, float(attn)
-
-    def _arm_dropout(self, training: bool) -> None:
-        """hands every layer its two calls of this forward (None: the plain path); a training forward with either
-        probability above 0 takes the current epoch number and moves it on.  Layer l uses stream epoch * 64 + l for both."""
-        feat = bool(training) and self.dropout_p > 0.0
-        attn = bool(training) and self.attn_dropout_p > 0.0
-        for li, layer in enumerate(self.layers_):
-            stream = (self.dropout_epoch * DROPOUT_MAX_LAYERS + li) & 0xFFFFFFFF
-            layer.dropout = (*self._dropout_params, self.dropout_seed, stream) if feat and li > 0 else None
-            layer.attn_dropout = (*self._attn_dropout_params, self.dropout_seed, stream, 0, 0) if attn else None
-        if feat or attn:
-            self.dropout_epoch += 1
-
-    def __call__(self, ctx: context, H: dn_matrix, training: bool = False) -> dn_matrix:
-        """the forward pass; ``training``: a training forward (train_forward / train_step pass True), the only kind that
-        drops -- a plain call and evaluate() never do"""
-        self._arm_dropout(training)
-        for layer in self.layers_:
-            H = layer(ctx, H)
-        return H
-
-    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
-        if not self.fused:
-            for layer in self.layers_:
-                layer.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
-            return
-        self._adam = adam_update_all(ctx, [p for l in self.layers_ for p in l.params()], self._adam, lr, beta1, beta2,
-                                     weight_decay, eps)
-
-    def layers(self) -> List[gat_layer]:
-        return self.layers_
-
-    def _alpha_requests(self, layers, out) -> List[int]:
-        """the layer indices ``layers=`` names, after every check attention_weights can make without the device"""
-        n_layers = len(self.layers_)
-        which = list(range(n_layers)) if layers is None else [int(li) for li in layers]
-        for li in which:
-            if not 0 <= li < n_layers:
-                raise ValueError(f"attention_weights: layer {li} is out of range, the model has {n_layers} layers")
-        if out is not None:
-            if len(out) != len(which):
-                raise ValueError(f"attention_weights: out lists {len(out)} matrices for {len(which)} layers")
-            for li, o in zip(which, out):
-                want = (self.layers_[li].F.nnz(), self.heads[li])
-                if o.shape() != want:
-                    raise ValueError(f"attention_weights: out of layer {li} must be {want[0]} x {want[1]}, got {o.shape()}")
-        return which
-
     def attention_weights(self, ctx, X=None, layers=None, out=None) -> List[dn_matrix]:
-        """The attention coefficients alpha_ijk per layer (PyG's return_attention_weights): a list with one [nnz x heads]
-        dn_matrix per requested layer, whose row p belongs to entry p of attention_pattern()'s ``indices`` and whose
-        column k to head k.  With ``X`` a plain forward runs first (self(ctx, X), the forward that never drops); without,
-        the export is taken from the state the most recent forward left behind -- ValueError when there was none.  After
-        a training forward with attention dropout that state is the normalised coefficient BEFORE the dropout factor q:
-        the softmax runs over all entries there too, so the export is what a plain forward of the same weights and
-        inputs gives, not alpha q.  ``layers``: None for all, or layer indices, returned in the order given; ``out``: one
-        dn_matrix per requested layer to write into (None allocates).  ValueError before any device work for an index
-        out of range and for an ``out`` of the wrong length or shape.
-
-        The values are exp(e_ijk - lse[i, k]) as the backward kernels evaluate it (mggcn_gat_alpha_f32 /
-        mggcn_gatv2_alpha_f32): the coefficients the model trains with, the same bits on every call.  This is the one place
-        where something of nnz x heads is stored: the Reddit-shaped graph (114.8 M entries) at 4 heads needs 1.84 GB per
-        layer.  Nothing is allocated or launched unless this method (or gat_layer.alpha) is called."""
+        """attention_model.attention_weights; ValueError for variant="dot" before anything else"""
         refuse_dot(self, "attention_weights: there is no export kernel for the dot-product coefficients yet")
-        which = self._alpha_requests(layers, out)
-        if X is not None:
-            self(ctx, X)
-        elif any(self.layers_[li].H is None for li in which):
-            raise ValueError("attention_weights: no forward has run, there are no attention coefficients yet (pass X)")
-        return [self.layers_[li].alpha(ctx, None if out is None else out[i]) for i, li in enumerate(which)]
+        return attention_model.attention_weights(self, ctx, X, layers, out)
 
     def attention_pattern(self):
         """(indptr, indices): the host arrays of the matrix the forward walks, A.transpose() -- row i is a destination, its
@@ -767,26 +716,14 @@ class gat(dropout_option, checkpoint_option):
 
     def save(self, ctx, path: str, optimizer: bool = True) -> None:
         """checkpoint.checkpoint_option.save; ValueError for variant="dot" before anything is read, written or created"""
-        refuse_dot(self, "save: the checkpoint file has no version for this variant yet")
-        refuse_skip(self, "save: the checkpoint file has no version that stores this option yet")
+        refuse_checkpoint(self, "save: the checkpoint file")
         checkpoint_option.save(self, ctx, path, optimizer)
 
     def load(self, ctx, path: str) -> None:
         """checkpoint.checkpoint_option.load; ValueError for variant="dot" before the file is opened"""
-        refuse_dot(self, "load: the checkpoint file has no version for this variant yet")
-        refuse_skip(self, "load: the checkpoint file has no version that stores this option yet")
+        refuse_checkpoint(self, "load: the checkpoint file")
         checkpoint_option.load(self, ctx, path)
 
     def _write_checkpoint(self, ctx, path: str, tensors, optimizer: bool, step: int) -> None:
-        refuse_dot(self, "checkpoint file (model_selector.save_best included): it has no version for this variant yet")
-        refuse_skip(self, "checkpoint file (model_selector.save_best included): it has no version that stores this option yet")
+        refuse_checkpoint(self, "checkpoint file (model_selector.save_best included): it")
         checkpoint_option._write_checkpoint(self, ctx, path, tensors, optimizer, step)
-
-    # the model-level plumbing is gcn's, word for word: it only touches what the two classes share (loss_layer, layers_,
-    # loss, A, _out_width and the calls above)
-    set_splits = gcn.set_splits
-    split_metrics = gcn.split_metrics
-    train_forward = gcn.train_forward
-    backward = gcn.backward
-    train_step = gcn.train_step
-    evaluate = gcn.evaluate

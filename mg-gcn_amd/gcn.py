@@ -163,26 +163,78 @@ class sparse_linear:
         ctx.register_timer(n + "1_matmul-spmm", n + "1_0_matmul-spmm", n + "1_1_matmul-spmm")
 
 
-class linear:
+class param_owner:
+    """Whatever holds parameter tensors that Adam trains: linear, layer_norm, and gat's attention, attention_v2, gated_skip
+    and attention_dot.  ``params_table`` describes each tensor once, one row per tensor in file order: (file-name stem,
+    parameter attribute, gradient attribute, m attribute, v attribute, decays like W).  The rows hold attribute NAMES, read
+    at call time: dist_gat.dist_attention rebinds G_att after __init__ and dist.dist_row_linear places G_W / G_b inside its
+    all-reduced buffer.  checkpoint.model_params names the file's tensors from the same rows.
+
+    ``adam_fused`` picks the per-tensor step (the model-wide one is adam_update_all): True is one ops.adam_fused per
+    tensor, the element-wise math of the model-wide table bit for bit; False is the reference's unfused chain
+    (gcn.hpp:146-172), which rounds differently."""
+
+    params_table = ()
+    adam_fused = False
+    step = 0
+
+    def adam_state(self, ctx: context) -> None:
+        """the moments, zeroed on the parameter's device, and step 0 -- made on first use"""
+        if self.params_table and getattr(self, self.params_table[0][3]) is None:
+            for _, p, _, m, v, _ in self.params_table:
+                p = getattr(self, p)
+                for moment in (m, v):
+                    setattr(self, moment, dn_matrix(p.shape(), device=p.t.device))
+                    getattr(self, moment).zero(ctx)
+            self.step = 0
+
+    def adam_tensors(self, weight_decay: float):
+        """(param, grad, m, v, weight decay) per tensor for ops.adam_table: only W and what decays like it (gcn.hpp:163)"""
+        return [(getattr(self, p), getattr(self, g), getattr(self, m), getattr(self, v), weight_decay if decays else 0.0)
+                for _, p, g, m, v, decays in self.params_table]
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
+        self.adam_state(ctx)
+        self.step += 1
+        bc1 = float(np.float32(1 - beta1 ** self.step))
+        bc2 = float(np.float32(1 - beta2 ** self.step))
+        rows = self.adam_tensors(weight_decay)
+        if self.adam_fused:
+            for p, g, m, v, wd in rows:
+                ops.adam_fused(ctx, p, g, m, v, lr, beta1, beta2, wd, bc1, bc2, eps)
+            return
+        for (p, g, *_), (*_, decays) in zip(rows, self.params_table):      # phase by phase over the tensors, as the reference
+            if decays:
+                ops.axpy(ctx, p, g, weight_decay)
+        for _, g, m, _, _ in rows:
+            ops.axpby(ctx, g, m, 1 - beta1, beta1)
+        for _, g, _, v, _ in rows:
+            ops.aaxpby(ctx, g, v, 1 - beta2, beta2)
+        for p, _, m, v, _ in rows:
+            ops.adam_final(ctx, p, m, v, lr, bc1, bc2, eps)
+
+
+class linear(param_owner):
     """reference src/gcn.hpp:88-189: XW = X.W + 1 b^T; backward G_b, G_W, G_out; Adam.
 
     The body of the row-partitioned form too (dist.dist_row_linear, gcn.hpp:191-296): every operand here is a dn_matrix
     on ``ctx``'s device -- the rank's shard of X and G, its replica of W and b.  What the distributed form adds lives in
     the two hooks it overrides: _gradients (where G_W / G_b are stored) and _reduce_gradients (runs after the
-    weight-gradient GEMMs), plus finish_backward."""
+    weight-gradient GEMMs), plus finish_backward.  ``fused`` picks the per-tensor Adam step too (param_owner)."""
+
+    params_table = (("W", "W", "G_W", "mW", "vW", True), ("b", "b", "G_b", "mb", "vb", False))
+    mW = vW = mb = vb = None
 
     def __init__(self, name: str, in_: int, out: int, backward_out: bool = True, fused: bool = False):
         self.name = name
         self.W = dn_matrix(in_, out)
         self.G_W, self.G_b = self._gradients(in_, out)
         self.b = dn_matrix(1, out)
-        self.backward_out, self.fused = backward_out, fused
+        self.backward_out, self.fused, self.adam_fused = backward_out, fused, fused
         self.W.init()
         self.b.init(_SQRT_1_3)
         self.X: Optional[dn_matrix] = None
         self.ones: Optional[dn_matrix] = None
-        self.mW = self.vW = self.mb = self.vb = None
-        self.step = 0
 
     def _gradients(self, in_: int, out: int) -> Tuple[dn_matrix, dn_matrix]:
         return dn_matrix(in_, out), dn_matrix(1, out)
@@ -239,39 +291,13 @@ class linear:
         ops.axpby(ctx, self.G_W, self.W, -lr, 1 - weight_decay)
         ops.axpy(ctx, self.G_b, self.b, -lr)
 
-    def adam_state(self, ctx: context) -> None:
-        if self.mW is None:
-            dev = self.W.t.device
-            self.mW, self.vW = dn_matrix(self.W.shape(), device=dev), dn_matrix(self.W.shape(), device=dev)
-            self.mb, self.vb = dn_matrix(self.b.shape(), device=dev), dn_matrix(self.b.shape(), device=dev)
-            for t in (self.mW, self.vW, self.mb, self.vb):
-                t.zero(ctx)
-            self.step = 0
-
-    def adam_tensors(self, weight_decay: float):
-        """(param, grad, m, v, weight decay) of this layer for ops.adam_table: W decays, b does not (gcn.hpp:163)"""
-        return [(self.W, self.G_W, self.mW, self.vW, weight_decay), (self.b, self.G_b, self.mb, self.vb, 0.0)]
-
     def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float,
                     eps: float) -> None:
         self.finish_backward(ctx)
-        self.adam_state(ctx)
-        self.step += 1
-        bc1 = float(np.float32(1 - beta1 ** self.step))
-        bc2 = float(np.float32(1 - beta2 ** self.step))
+        self.adam_state(ctx)                # the first step's zero fills stay outside the timer
         n = self.name
         ctx.record(n + "0_adam-update", 0)
-        if self.fused:
-            ops.adam_fused(ctx, self.W, self.G_W, self.mW, self.vW, lr, beta1, beta2, weight_decay, bc1, bc2, eps)
-            ops.adam_fused(ctx, self.b, self.G_b, self.mb, self.vb, lr, beta1, beta2, 0.0, bc1, bc2, eps)
-        else:
-            ops.axpy(ctx, self.W, self.G_W, weight_decay)
-            ops.axpby(ctx, self.G_W, self.mW, 1 - beta1, beta1)
-            ops.axpby(ctx, self.G_b, self.mb, 1 - beta1, beta1)
-            ops.aaxpby(ctx, self.G_W, self.vW, 1 - beta2, beta2)
-            ops.aaxpby(ctx, self.G_b, self.vb, 1 - beta2, beta2)
-            ops.adam_final(ctx, self.W, self.mW, self.vW, lr, bc1, bc2, eps)
-            ops.adam_final(ctx, self.b, self.mb, self.vb, lr, bc1, bc2, eps)
+        param_owner.adam_update(self, ctx, lr, beta1, beta2, weight_decay, eps)
         ctx.record(n + "1_adam-update", 0)
         ctx.register_timer(n + "adam-update", n + "0_adam-update", n + "1_adam-update")
 
@@ -281,15 +307,21 @@ class linear:
     def get_G_b(self): return self.G_b
 
 
-class layer_norm:
+class layer_norm(param_owner):
     """Layer normalisation of a layer's [n x out] pre-activation, in place, with the activation in the same launch
     (opt-in; the reference has none): gamma (ones) and beta (zeros) [1 x out], their gradients and Adam moments, and what
     the backward pass needs of the forward -- xhat [n x out] and rstd [n].  Row-local: a row shard normalises exactly the
     rows the single-GPU model does, and its two gradient rows are summed over the ranks with the linear's
-    (``grad_buffer``: 2 * out floats inside that linear's all-reduced buffer)."""
+    (``grad_buffer``: 2 * out floats inside that linear's all-reduced buffer).  Neither gamma nor beta decays;
+    ``adam_fused``: the per-tensor Adam step (param_owner) -- gcn's is the unfused chain linear runs for b, gat's the fused
+    kernel of every other parameter of an attention model."""
 
-    def __init__(self, name: str, n: int, out: int, fused: bool = False, device=None, grad_buffer=None):
-        self.name, self.fused = name, fused
+    params_table = (("gamma", "gamma", "G_gamma", "mg", "vg", False), ("beta", "beta", "G_beta", "mb", "vb", False))
+    mg = vg = mb = vb = None
+
+    def __init__(self, name: str, n: int, out: int, fused: bool = False, device=None, grad_buffer=None,
+                 adam_fused: bool = False):
+        self.name, self.fused, self.adam_fused = name, fused, adam_fused
         self.gamma, self.beta = dn_matrix(1, out, device=device), dn_matrix(1, out, device=device)
         self.gamma.init(np.ones((1, out), dtype=np.float32))
         self.beta.init(np.zeros((1, out), dtype=np.float32))
@@ -298,8 +330,6 @@ class layer_norm:
         else:
             self.G_gamma, self.G_beta = dn_matrix(1, out, grad_buffer[:out]), dn_matrix(1, out, grad_buffer[out:2 * out])
         self.xhat, self.rstd = dn_matrix(n, out, device=device), dn_matrix(n, 1, device=device)
-        self.mg = self.vg = self.mb = self.vb = None
-        self.step = 0
 
     def __call__(self, ctx: context, Z: dn_matrix, activation: bool, out: Optional[dn_matrix] = None) -> None:
         """Z = [leaky_relu](layer_norm(Z)) in place, or into ``out`` where Z has to stay (a gat layer's aggregated output)"""
@@ -323,31 +353,29 @@ class layer_norm:
         self.gamma.init(np.asarray(gamma, dtype=np.float32))
         self.beta.init(np.asarray(beta, dtype=np.float32))
 
-    def adam_state(self, ctx: context) -> None:
-        if self.mg is None:
-            dev = self.gamma.t.device
-            self.mg, self.vg, self.mb, self.vb = (dn_matrix(self.gamma.shape(), device=dev) for _ in range(4))
-            for t in (self.mg, self.vg, self.mb, self.vb):
-                t.zero(ctx)
-            self.step = 0
 
-    def adam_tensors(self, weight_decay: float):
-        """rows of ops.adam_table: neither gamma nor beta decays"""
-        return [(self.gamma, self.G_gamma, self.mg, self.vg, 0.0), (self.beta, self.G_beta, self.mb, self.vb, 0.0)]
+class layer_params:
+    """What a layer of any model says about its parameters: owners() lists (file-name prefix, param_owner) in file order,
+    and params(), the per-tensor adam_update and the reference's accessors follow from it."""
 
-    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float) -> None:
-        """the unfused chain linear.adam_update runs for b"""
-        self.adam_state(ctx)
-        self.step += 1
-        bc1 = float(np.float32(1 - beta1 ** self.step))
-        bc2 = float(np.float32(1 - beta2 ** self.step))
-        for p, g, m, v, _ in self.adam_tensors(weight_decay):
-            ops.axpby(ctx, g, m, 1 - beta1, beta1)
-            ops.aaxpby(ctx, g, v, 1 - beta2, beta2)
-            ops.adam_final(ctx, p, m, v, lr, bc1, bc2, eps)
+    def owners(self):
+        raise NotImplementedError
+
+    def params(self):
+        """everything Adam updates: the owners that hold a tensor"""
+        return [owner for _, owner in self.owners() if owner.params_table]
+
+    def adam_update(self, ctx, lr, beta1, beta2, weight_decay, eps):
+        for p in self.params():
+            p.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+
+    def b(self): return self.lin.get_b()
+    def W(self): return self.lin.get_W()
+    def GW(self): return self.lin.get_G_W()
+    def Gb(self): return self.lin.get_G_b()
 
 
-class layer_body:
+class layer_body(layer_params):
     """Forward and backward of one GCN layer, reference src/gcn.hpp:411-518 (gcn_layer) and :520-637 (dist_gcn_layer),
     over a context and dn_matrix operands: the layer's rows on this GPU.  HW / G_HW alias the model-wide HW_buffer,
     AHW / G_out alias the layer's AHW_buffer (:433-434).  ``agg`` is the aggregation operator: agg(ctx, B, C, discard,
@@ -482,9 +510,9 @@ class layer_body:
     def linears(self):
         return [self.lin] + ([self.res_lin] if self.res_lin is not None else [])
 
-    def params(self):
-        """everything Adam updates: the linears, then the norm (linears() stays what the reference's layer has)"""
-        return self.linears() + ([self.norm] if self.norm is not None else [])
+    def owners(self):
+        """the linears, then the norm (linears() stays what the reference's layer has)"""
+        return [(prefix, o) for prefix, o in (("", self.lin), ("res_", self.res_lin), ("", self.norm)) if o is not None]
 
     def finish_backward(self, ctx) -> None:
         for lin in self.linears():
@@ -493,15 +521,6 @@ class layer_body:
     def update(self, ctx, lr, weight_decay):
         for lin in self.linears():
             lin.update(ctx, lr, weight_decay)
-
-    def adam_update(self, ctx, lr, beta1, beta2, weight_decay, eps):
-        for p in self.params():
-            p.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
-
-    def b(self): return self.lin.get_b()
-    def W(self): return self.lin.get_W()
-    def GW(self): return self.lin.get_G_W()
-    def Gb(self): return self.lin.get_G_b()
 
 
 class gcn_layer(layer_body):
@@ -916,7 +935,107 @@ def adam_update_all(ctx: context, lins, state, lr: float, beta1: float, beta2: f
     return state
 
 
-class gcn(dropout_option, checkpoint_option):
+class model_base(dropout_option, checkpoint_option):
+    """The epoch of a single-GPU model, whatever its layers are (gcn, gat.gat): splits, the forward pass, the loss,
+    backward, Adam and evaluate, over what the constructor of the model sets -- ``loss_layer``, ``layers_``, ``loss``,
+    ``A``, ``_out_width``, ``fused`` and ``_adam`` (None).  A layer is called with (ctx, H), has backward(ctx, G),
+    adam_update and params() (layer_params), and takes its ``dropout`` from _arm_dropout."""
+
+    def set_splits(self, S, train_set: int = 0) -> None:
+        """Train on one split (opt-in; the reference loads sets.bin and ignores it, src/main.cpp:85).  S: the set of every
+        vertex (0 train / 1 validation / 2 test, anything else belongs to no split) as a numpy array of n integers or an
+        int32 dn_matrix of n rows; None restores the loss over all vertices.  From here on train_forward / train_step
+        return the loss and accuracy of ``train_set`` and split_metrics() reports every split of the last epoch."""
+        if S is None:
+            self.loss_layer.set_splits(None)
+            return
+        host, counts = check_splits(S, self.A.n(), train_set)
+        if not isinstance(S, dn_matrix):
+            S = dn_matrix.from_numpy(host)
+        self.loss_layer.set_splits(S, counts, train_set)
+
+    def split_metrics(self):
+        """every split's (loss, acc) of the last epoch, see softmax_cross_entropy_loss.split_metrics; call after
+        train_forward / train_step (they synchronise).  With dropout on these are the numbers of the DROPPED training
+        forward, validation and test included: evaluate() gives the clean ones."""
+        if self.loss_layer.S is None:
+            raise ValueError("split_metrics() needs set_splits(S) first")
+        return self.loss_layer.split_metrics()
+
+    def __call__(self, ctx: context, H: dn_matrix, training: bool = False) -> dn_matrix:
+        """the forward pass; ``training``: a training forward (train_forward / train_step pass True), the only kind
+        that drops -- a plain call and evaluate() never do"""
+        self._arm_dropout(training)
+        for layer in self.layers_:
+            H = layer(ctx, H)
+        return H
+
+    def train_forward(self, ctx: context, H: dn_matrix, Y: dn_matrix):
+        check_targets(self.loss, Y, self.A.n(), self._out_width)
+        H = self(ctx, H, training=True)
+        return self.loss_layer(ctx, H, Y)
+
+    def backward(self, ctx: context) -> None:
+        G = self.loss_layer.backward()
+        for layer in reversed(self.layers_):
+            G = layer.backward(ctx, G)
+
+    def train_step(self, ctx: context, H: dn_matrix, Y: dn_matrix, lr: float, beta1: float, beta2: float,
+                   weight_decay: float, eps: float):
+        """One epoch = the reference's loop body (src/main.cpp:122-129: train_forward, backward,
+        adam_update, sync) with ONE host synchronisation: the loss / accuracy scalars are read after
+        the epoch's last kernel instead of between forward and backward (the reference blocks inside
+        its loss layer, src/gcn.hpp:816-817, and leaves the GPU idle while the host catches up)."""
+        check_targets(self.loss, Y, self.A.n(), self._out_width)
+        out = self(ctx, H, training=True)
+        self.loss_layer(ctx, out, Y, sync=False)
+        self.backward(ctx)
+        self.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+        ctx.sync()
+        return self.loss_layer.read(ctx)
+
+    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float,
+                    eps: float) -> None:
+        if not self.fused:
+            for layer in self.layers_:
+                layer.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+            return
+        self._adam = adam_update_all(ctx, [p for l in self.layers_ for p in l.params()], self._adam, lr, beta1,
+                                     beta2, weight_decay, eps)
+
+    def layers(self):
+        return self.layers_
+
+    def evaluate(self, ctx: context, H: dn_matrix, Y: dn_matrix, S: Optional[dn_matrix] = None):
+        """Forward pass + accuracy per split (SURVEY.md 8(f) rank 4).  The reference loads
+        sets.bin (0 train / 1 val / 2 test, test/data/prep.py:115-118) and never uses it
+        (src/main.cpp:85); its reported accuracy is over ALL vertices, which is what
+        ``result["all"]`` repeats.  Device work: the model's forward kernels + the argmax
+        kernel; the per-split counting is a host reduction over n integers.
+
+        With loss="bce" the numbers are micro-F1 instead of accuracy (prediction: logit > 0), a host reduction over the
+        copied logits."""
+        if self.loss == "bce":
+            check_targets(self.loss, Y, self.A.n(), self._out_width)
+            out = self(ctx, H)
+            ctx.sync()
+            return evaluate_micro_f1(out.numpy(), Y.numpy(), None if S is None else S.numpy())
+        out = self(ctx, H)
+        P = dn_matrix(Y.shape(), dtype=np.int32)
+        ops.max_row_indices(ctx, out, P)
+        ctx.sync()
+        pred, y = P.numpy().reshape(-1), Y.numpy().reshape(-1)
+        hit = pred == y
+        res = {"all": float(hit.mean())}
+        if S is not None:
+            s = S.numpy().reshape(-1)
+            for k, name in enumerate(ops.SPLIT_NAMES[:3]):
+                m = s == k
+                res[name] = float(hit[m].mean()) if m.any() else float("nan")
+        return res
+
+
+class gcn(model_base):
     """reference src/gcn.hpp:937-995.  The constructor column-normalises A, builds
     A_T and hands (A_T, A) to the layers -- forward multiplies by A_T (:946-955).
 
@@ -991,102 +1110,12 @@ class gcn(dropout_option, checkpoint_option):
         l0.hoist_input = bool(on) and l0.gemm_first() and not l0.residual_layer and stochastic
         l0._AX = l0._AX_key = None                  # (re-)enabling recomputes the product: the way to pick up an in-place change of X
 
-    def set_splits(self, S, train_set: int = 0) -> None:
-        """Train on one split (opt-in; the reference loads sets.bin and ignores it, src/main.cpp:85).  S: the set of every
-        vertex (0 train / 1 validation / 2 test, anything else belongs to no split) as a numpy array of n integers or an
-        int32 dn_matrix of n rows; None restores the loss over all vertices.  From here on train_forward / train_step
-        return the loss and accuracy of ``train_set`` and split_metrics() reports every split of the last epoch."""
-        if S is None:
-            self.loss_layer.set_splits(None)
-            return
-        host, counts = check_splits(S, self.A.n(), train_set)
-        if not isinstance(S, dn_matrix):
-            S = dn_matrix.from_numpy(host)
-        self.loss_layer.set_splits(S, counts, train_set)
-
-    def split_metrics(self):
-        """every split's (loss, acc) of the last epoch, see softmax_cross_entropy_loss.split_metrics; call after
-        train_forward / train_step (they synchronise).  With dropout on these are the numbers of the DROPPED training
-        forward, validation and test included: evaluate() gives the clean ones."""
-        if self.loss_layer.S is None:
-            raise ValueError("split_metrics() needs set_splits(S) first")
-        return self.loss_layer.split_metrics()
-
     def __call__(self, ctx: context, H: dn_matrix, training: bool = False) -> dn_matrix:
-        """the forward pass; ``training``: a training forward (train_forward / train_step pass True), the only kind
-        that drops -- a plain call and evaluate() never do"""
         if self._plan_wants:                          # first call: the context (device) is known now
             ops.prebuild_plans(ctx, self._plan_wants)
             self._plan_wants = []
-        self._arm_dropout(training)
-        for layer in self.layers_:
-            H = layer(ctx, H)
-        return H
-
-    def train_forward(self, ctx: context, H: dn_matrix, Y: dn_matrix):
-        check_targets(self.loss, Y, self.A.n(), self._out_width)
-        H = self(ctx, H, training=True)
-        return self.loss_layer(ctx, H, Y)
-
-    def backward(self, ctx: context) -> None:
-        G = self.loss_layer.backward()
-        for layer in reversed(self.layers_):
-            G = layer.backward(ctx, G)
-
-    def train_step(self, ctx: context, H: dn_matrix, Y: dn_matrix, lr: float, beta1: float, beta2: float,
-                   weight_decay: float, eps: float):
-        """One epoch = the reference's loop body (src/main.cpp:122-129: train_forward, backward,
-        adam_update, sync) with ONE host synchronisation: the loss / accuracy scalars are read after
-        the epoch's last kernel instead of between forward and backward (the reference blocks inside
-        its loss layer, src/gcn.hpp:816-817, and leaves the GPU idle while the host catches up)."""
-        check_targets(self.loss, Y, self.A.n(), self._out_width)
-        out = self(ctx, H, training=True)
-        self.loss_layer(ctx, out, Y, sync=False)
-        self.backward(ctx)
-        self.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
-        ctx.sync()
-        return self.loss_layer.read(ctx)
+        return model_base.__call__(self, ctx, H, training)
 
     def update(self, ctx: context, lr: float, weight_decay: float) -> None:
         for layer in self.layers_:
             layer.update(ctx, lr, weight_decay)
-
-    def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float,
-                    eps: float) -> None:
-        if not self.fused:
-            for layer in self.layers_:
-                layer.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
-            return
-        self._adam = adam_update_all(ctx, [p for l in self.layers_ for p in l.params()], self._adam, lr, beta1,
-                                     beta2, weight_decay, eps)
-
-    def layers(self) -> List[gcn_layer]:
-        return self.layers_
-
-    def evaluate(self, ctx: context, H: dn_matrix, Y: dn_matrix, S: Optional[dn_matrix] = None):
-        """Forward pass + accuracy per split (SURVEY.md 8(f) rank 4).  The reference loads
-        sets.bin (0 train / 1 val / 2 test, test/data/prep.py:115-118) and never uses it
-        (src/main.cpp:85); its reported accuracy is over ALL vertices, which is what
-        ``result["all"]`` repeats.  Device work: the model's forward kernels + the argmax
-        kernel; the per-split counting is a host reduction over n integers.
-
-        With loss="bce" the numbers are micro-F1 instead of accuracy (prediction: logit > 0), a host reduction over the
-        copied logits."""
-        if self.loss == "bce":
-            check_targets(self.loss, Y, self.A.n(), self._out_width)
-            out = self(ctx, H)
-            ctx.sync()
-            return evaluate_micro_f1(out.numpy(), Y.numpy(), None if S is None else S.numpy())
-        out = self(ctx, H)
-        P = dn_matrix(Y.shape(), dtype=np.int32)
-        ops.max_row_indices(ctx, out, P)
-        ctx.sync()
-        pred, y = P.numpy().reshape(-1), Y.numpy().reshape(-1)
-        hit = pred == y
-        res = {"all": float(hit.mean())}
-        if S is not None:
-            s = S.numpy().reshape(-1)
-            for k, name in enumerate(ops.SPLIT_NAMES[:3]):
-                m = s == k
-                res[name] = float(hit[m].mean()) if m.any() else float("nan")
-        return res

@@ -196,13 +196,15 @@ def test_parameter_names_of_a_stand_in_layer(pkg):
     """checkpoint.model_params names a full layer W0, b0, att0, res_W0, res_b0, gate0, gamma0, beta0, params() lists the
     owners in the same order, and a layer without the attributes is what it was"""
     gat = import_module(pkg.__name__ + ".gat")
+    gcn = import_module(pkg.__name__ + ".gcn")
     checkpoint = import_module(pkg.__name__ + ".checkpoint")
+    new = lambda cls: cls.__new__(cls)                      # the real owner classes carry the tables; none has a tensor
     layer = gat.gat_layer.__new__(gat.gat_layer)
-    layer.lin, layer.attn = object(), type("a", (), {"att": object()})()
+    layer.lin, layer.attn = new(gcn.linear), new(gat.attention)
     assert layer.params() == [layer.lin, layer.attn]
     model = type("m", (), {"layers_": [layer]})()
     assert [name for name, *_ in checkpoint.model_params(model)] == ["W0", "b0", "att0"]
-    layer.res_lin, layer.gate, layer.norm = object(), object(), object()
+    layer.res_lin, layer.gate, layer.norm = new(gcn.linear), new(gat.gated_skip), new(gcn.layer_norm)
     assert layer.params() == [layer.lin, layer.attn, layer.res_lin, layer.gate, layer.norm]
     rows = checkpoint.model_params(model)
     assert [name for name, *_ in rows] == ["W0", "b0", "att0", "res_W0", "res_b0", "gate0", "gamma0", "beta0"]
@@ -210,9 +212,9 @@ def test_parameter_names_of_a_stand_in_layer(pkg):
     layer.gate = None                                       # skip="add"
     assert [name for name, *_ in checkpoint.model_params(model)] == ["W0", "b0", "att0", "res_W0", "res_b0", "gamma0", "beta0"]
     dotl = gat.gatdot_layer.__new__(gat.gatdot_layer)
-    dotl.lin, dotl.attn = object(), gat.attention_dot.__new__(gat.attention_dot)
+    dotl.lin, dotl.attn = new(gcn.linear), gat.attention_dot.__new__(gat.attention_dot)
     assert dotl.params() == [dotl.lin]
-    dotl.res_lin, dotl.gate, dotl.norm = object(), object(), None
+    dotl.res_lin, dotl.gate, dotl.norm = new(gcn.linear), new(gat.gated_skip), None
     assert dotl.params() == [dotl.lin, dotl.res_lin, dotl.gate]
 
 

@@ -202,7 +202,8 @@ def test_attention_dot_has_no_parameter(pkg):
     assert a.adam_tensors(5e-4) == [] and a.adam_update(None, 1e-2, 0.9, 0.999, 5e-4, 1e-8) is None
     assert a.att is None and a.m is None
     layer = gat.gatdot_layer.__new__(gat.gatdot_layer)
-    layer.lin, layer.attn = object(), a
+    linear = import_module(pkg.__name__ + ".gcn").linear
+    layer.lin, layer.attn = linear.__new__(linear), a         # the real owner class carries the table; it has no tensor
     assert layer.params() == [layer.lin]
     model = type("m", (), {"layers_": [layer]})()
     names = [name for name, *_ in import_module(pkg.__name__ + ".checkpoint").model_params(model)]
