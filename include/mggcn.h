@@ -60,7 +60,7 @@ void mggcn_device_synchronize(void);
 mggcn_stream_t mggcn_stream_create(int high_priority);
 void mggcn_stream_destroy(mggcn_stream_t stream);
 /* Frees the per-(device, stream) reduction scratch that mggcn_abssum_f32 / the fused loss, and the partials that
- * mggcn_layer_norm_backward_f32, mggcn_gated_skip_backward_f32 and mggcn_gat_scores_backward_f32, allocate on first use (synchronises that stream).  mggcn_stream_destroy calls it; a
+ * mggcn_layer_norm_backward_f32, mggcn_gated_skip_backward_f32, mggcn_label_input_backward_f32 and mggcn_gat_scores_backward_f32, allocate on first use (synchronises that stream).  mggcn_stream_destroy calls it; a
  * host layer that brings its own streams (e.g. torch's) calls it when it drops one. */
 void mggcn_stream_release_scratch(mggcn_stream_t stream);
 void mggcn_stream_synchronize(mggcn_stream_t stream);
@@ -362,6 +362,38 @@ void mggcn_gated_skip_backward_f32(mggcn_stream_t stream, const float *G, size_t
                                    const float *o, size_t ldo, const float *r, size_t ldr, const float *w, const float *gate,
                                    float *G_o, size_t ldgo, float *G_r, size_t ldgr, float *G_w, size_t n_rows, size_t m,
                                    uint32_t flags);
+/* Masked label inputs of the attention models (opt-in; the "label trick" of UniMP): a trained table E [n_classes x width]
+ * whose row E[y_i] is added to row i of layer 0's Z for the training rows that are FED this forward, and its gradient.
+ * Both calls walk the training rows only, as three device lists the host builds once: rows[t], the local row numbers, and
+ * cls[t], their classes, t < n_train, sorted by (class, row) without duplicates, and cls_ptr[n_classes + 1], the segment
+ * of each class (cls_ptr[0] = 0, cls_ptr[n_classes] = n_train).  Entry t is fed iff
+ *   feed_all != 0, or  Philox4x32-10(counter = (0xFFFFFFFF, r & 0xffffffff, r >> 32, epoch),
+ *                                    key = (seed & 0xffffffff, seed >> 32)).w[0] < threshold,   r = row0 + rows[t]
+ * (threshold = (uint32) floor(rate * 2^32), from the host).  The mask is never stored: both calls regenerate it, it does not
+ * depend on how the rows are split (row0 is the global number of local row 0), and the first counter word is a column
+ * group mggcn_dropout_f32 never draws, so a seed shared with dropout shares no bits.
+ *   forward    fed: Z[rows[t], :] += E[cls[t], :], one fp32 add per element, and S_out[rows[t]] = fed_set;
+ *              otherwise S_out[rows[t]] = kept_set.  S_out may be null.  Rows that are not listed are not touched, in Z or
+ *              in S_out; every listed row of S_out is written on every call.
+ *   backward   G_E[c, :] = the sum of G_Z[rows[t], :] over the fed entries of class c; a class without one gets +0.0
+ *              (written, not skipped).  No atomics: each segment is cut into chunks of 64 entries, whatever the grid is,
+ *              one partial per chunk goes to the per-(device, stream) scratch of mggcn_layer_norm_backward_f32 and the
+ *              partials of a class are added in a fixed order, so the same arguments give the same bits on every call.
+ * Z and G_Z have n_rows rows; an entry whose row is not below n_rows or whose class is not below n_classes is skipped and
+ * never dereferenced.  1 <= n_classes <= MGGCN_LABEL_INPUT_MAX_CLASSES, 1 <= width <= MGGCN_LABEL_INPUT_MAX_WIDTH (three
+ * times MGGCN_GAT_MAX_WIDTH: the Z of a dot-product layer), every leading dimension >= width.  width % 4 == 0 with every
+ * dense operand 16-byte aligned and every leading dimension a multiple of 4 takes a float4 path, anything else an element
+ * path.  n_train == 0: the forward launches nothing, the backward writes +0.0 to all of G_E (the lists may be null). */
+#define MGGCN_LABEL_INPUT_MAX_CLASSES 256u
+#define MGGCN_LABEL_INPUT_MAX_WIDTH 3072u
+void mggcn_label_input_forward_f32(mggcn_stream_t stream, const uint32_t *rows, const uint32_t *cls, size_t n_train,
+                                   const float *E, size_t lde, size_t n_classes, size_t width, uint32_t threshold,
+                                   int feed_all, uint64_t seed, uint32_t epoch, uint64_t row0, int32_t kept_set,
+                                   int32_t fed_set, float *Z, size_t ldz, size_t n_rows, int32_t *S_out);
+void mggcn_label_input_backward_f32(mggcn_stream_t stream, const uint32_t *rows, const uint32_t *cls,
+                                    const uint32_t *cls_ptr, size_t n_train, size_t n_classes, size_t width,
+                                    uint32_t threshold, int feed_all, uint64_t seed, uint32_t epoch, uint64_t row0,
+                                    const float *G_Z, size_t ldg, size_t n_rows, float *G_E, size_t ldge);
 /* Graph attention (GAT; opt-in, the reference has no attention layer).  F is a CSR PATTERN of n_rows destinations x n_cols
  * sources (u32 indptr / indices on the device; there is no values array, and a duplicate (i, j) entry counts as two edges),
  * K = heads, dh = width per head, 1 <= K <= MGGCN_GAT_MAX_HEADS and K * dh <= MGGCN_GAT_MAX_WIDTH; head k owns columns

@@ -13,8 +13,10 @@ Layout:
                tensor; layer_params: a layer's owners; model_base: the epoch gcn and gat share
   gat.py       attention / gat_layer / gat: graph attention layers, GAT and (variant="v2": attention_v2 / gatv2_layer)
                GATv2 and (variant="dot": attention_dot / gatdot_layer) dot-product attention; gated_skip: the skip
-               connection and gate of skip="add" | "gate" (no reference counterpart); attention_model: the dropouts and
+               connection and gate of skip="add" | "gate" (no reference counterpart); label_input: the table and lists of
+               label_input=rate; attention_model: the dropouts and
                the export gat and dist_gat share
+  label_mask.py  the host's restatement of the label-input mask: its count per epoch, without a synchronisation
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*); dist_model_base:
                the epoch dist_gcn and dist_gat share
   dist_gat.py  dist_attention / dist_gat_layer / dist_gat (and the _v2 / gatv2 twins): gat on the row partition (exported by dist)
@@ -31,7 +33,7 @@ from . import ops                                               # noqa: F401
 from .ops import get_matmul_buffer, matmul                      # noqa: F401
 from .gcn import (gcn, gcn_layer, linear, softmax, softmax_cross_entropy_loss,  # noqa: F401
                   sparse_linear)
-from .gat import attention, attention_dot, attention_v2, gat, gat_layer, gatdot_layer, gated_skip, gatv2_layer  # noqa: F401
+from .gat import attention, attention_dot, attention_v2, gat, gat_layer, gatdot_layer, gated_skip, gatv2_layer, label_input  # noqa: F401
 
 from . import dist                                              # noqa: F401
 from .dist import (dist_context, dist_gcn, dist_gcn_layer, dist_row_csr_matrix,  # noqa: F401
@@ -42,4 +44,4 @@ from .selection import model_selector                           # noqa: F401
 
 __all__ = ["context", "csr_matrix", "dn_matrix", "matrix_error", "engine_error", "ops", "matmul",
            "get_matmul_buffer", "sparse_linear", "linear", "gcn_layer", "softmax",
-           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "datasets", "model_selector"]
+           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "datasets", "model_selector"]

@@ -99,6 +99,10 @@ PROTOTYPES = {
                                             c_uint32]),
     "mggcn_gated_skip_backward_f32": (None, [vp, vp, c_size_t, vp, c_size_t, vp, c_size_t, vp, c_size_t, vp, vp, vp,
                                              c_size_t, vp, c_size_t, vp, c_size_t, c_size_t, c_uint32]),
+    "mggcn_label_input_forward_f32": (None, [vp, vp, vp, c_size_t, vp, c_size_t, c_size_t, c_size_t, c_uint32, c_int,
+                                             c_uint64, c_uint32, c_uint64, c_int32, c_int32, vp, c_size_t, c_size_t, vp]),
+    "mggcn_label_input_backward_f32": (None, [vp, vp, vp, vp, c_size_t, c_size_t, c_size_t, c_uint32, c_int, c_uint64,
+                                              c_uint32, c_uint64, vp, c_size_t, c_size_t, vp, c_size_t]),
     "mggcn_gat_scores_f32":(None, [vp, vp, c_size_t, vp, vp, vp, c_size_t, c_uint32, c_uint32]),
     "mggcn_gat_forward_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, c_uint32, c_uint32, c_float, vp,
                                      c_size_t, vp]),

@@ -4,7 +4,8 @@
 //   wave      wave_sum / wave_max (xor butterfly) or the DPP family -- a kernel keeps the flavour it has: the two add in
 //             different orders
 //   workgroup block_fold: four waves through LDS, (w0 + w1) + (w2 + w3), one partial per workgroup
-//   grid      sums_final_kernel / colsum_final_kernel: the partials in workgroup order
+//   grid      sums_final_kernel / colsum_final_kernel: the partials in workgroup order; segsum_final_kernel: one such sum
+//             per segment of a list, the partials in chunk order
 //
 // A kernel that needs such a sum calls these and never writes the tree out.
 #pragma once
@@ -108,6 +109,7 @@ __global__ __launch_bounds__(256) void sums_final_kernel(const float *__restrict
 // out[idx] = the workgroups' partials [n_blocks][width] added in a fixed order: 64 of the `width` sums per workgroup, each
 // from four slices (workgroups b, b + 4, ... in order) that meet in LDS.  idx < split lands in out_lo[idx], the rest in
 // out_hi[idx - split] (the two need not be adjacent).  n_blocks == 0 stores zeros.
+[[maybe_unused]]        // label_input.hip sums by segment instead
 __global__ __launch_bounds__(256) void colsum_final_kernel(const float *__restrict__ partials, unsigned n_blocks,
                                                            uint32_t width, float *__restrict__ out_lo,
                                                            float *__restrict__ out_hi, uint32_t split) {
@@ -126,6 +128,36 @@ __global__ __launch_bounds__(256) void colsum_final_kernel(const float *__restri
         if (idx < split) out_lo[idx] = t;
         else out_hi[idx - split] = t;
     }
+}
+
+// ---- grid level: columns, by segment -----------------------------------------
+// out[s][idx] = the partials of segment s added in a fixed order, for a sum whose rows are a list cut into segments
+// (seg_ptr[s] .. seg_ptr[s + 1], the list n_list long) and whose producer stored one [width] partial per chunk of Chunk
+// list entries of a segment: chunk q of segment s at row seg_ptr[s] / Chunk + s + q of `partials` (the rows of a segment
+// end before the next segment's begin).  The tree is colsum_final_kernel's: four slices (chunks q, q + 4, ... in order)
+// that meet in LDS.  Grid (width / 64 rounded up, segments); a segment without an entry, and every segment when
+// n_list == 0 (seg_ptr is not read then), stores +0.0.  A template, so that only its user carries it.
+template <unsigned Chunk>
+__global__ __launch_bounds__(256) void segsum_final_kernel(const float *__restrict__ partials,
+                                                           const uint32_t *__restrict__ seg_ptr, uint32_t n_list,
+                                                           uint32_t width, float *__restrict__ out, size_t ldo) {
+    __shared__ float w[4][64];
+    const uint32_t lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
+    const uint32_t idx = blockIdx.x * 64 + lane, seg = blockIdx.y;
+    uint32_t first = 0, chunks = 0;
+    if (n_list) {
+        const uint32_t lo = seg_ptr[seg], hi = seg_ptr[seg + 1] < n_list ? seg_ptr[seg + 1] : n_list;
+        first = lo / Chunk + seg;
+        chunks = hi > lo ? (hi - lo + Chunk - 1) / Chunk : 0;
+    }
+    float s = 0.f;
+    if (idx < width) {
+#pragma unroll 8
+        for (uint32_t q = slice; q < chunks; q += 4) s += partials[(size_t)(first + q) * width + idx];
+    }
+    w[slice][lane] = s;
+    __syncthreads();
+    if (slice == 0 && idx < width) out[(size_t)seg * ldo + idx] = (w[0][lane] + w[1][lane]) + (w[2][lane] + w[3][lane]);
 }
 
 }  // namespace

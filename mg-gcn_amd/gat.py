@@ -84,6 +84,27 @@ Refused with ValueError before anything is created, read or written: save, load 
 with either option (the checkpoint file has no version that stores them; the selector's in-memory restore works), and
 dist_gat does not take the arguments.
 
+``label_input=rate`` (0 by default: nothing new is allocated, launched or registered) feeds masked labels into layer 0, the
+other half of UniMP and the "label trick" of Wang et al. 2021.  Feeding a label is appending a masked one-hot label to the
+features, [X | M onehot(y)] [W ; E] = X W + M E[y], so the feature is a trained table E [classes x width of layer 0's Z]:
+
+    Z[i] += E[y_i] for the fed rows i, after layer 0's GEMM and before its attention (the skip's res_lin sees H only)
+    G_E[c] = sum of G_Z[i] over the fed rows of class c            (csrc/label_input.hip: mggcn_label_input_*)
+
+In training forward e a vertex r is fed iff it is in the training set and word 0 of Philox4x32-10((0xFFFFFFFF, r, r >> 32, e),
+seed) is below floor(rate 2^32) -- never stored, regenerated by both kernels, no bits shared with dropout -- and the loss runs
+over the training rows that were NOT fed: the loss layer sees them in its "other" slot and the counts of the epoch
+(train = T - fed, other = other + fed), which the host takes from its own Philox (label_mask) one epoch ahead, under the
+device's work.  A plain call, evaluate() and predict() feed every training row.  set_label_input(Y, rate=None, seed=0, epoch=0)
+after set_splits hands the model its labels (epoch=e replays training forward e); ``label_input_p``, ``label_seed``,
+``label_epoch`` and ``layers()[0].label`` (``.E``) read the state; ``label_weights=`` takes E.  E is a row of the fused Adam
+table with W's weight decay, listed by layer 0 alone.  Refused with ValueError naming label_input before any device work: a
+rate outside [0, 1), loss="bce", more than ops.LABEL_INPUT_MAX_CLASSES classes, a label outside [0, classes) on a training
+row, set_label_input before set_splits, a forward before set_label_input, an epoch that leaves no row to predict, and save /
+load / save_best (no version of the checkpoint file stores E; the selector's in-memory restore includes it).  Not built: the
+row partition (dist_gat does not take the arguments; the partial G_E would ride on layer 0's all-reduce), the checkpoint
+version, gcn, multi-label targets, the C++ layer.
+
 Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, bf16 gathers.
 """
 from __future__ import annotations
@@ -92,7 +113,7 @@ from typing import List, Optional, Sequence
 
 import numpy as np
 
-from . import _lib, ops
+from . import _lib, label_mask, ops
 from .checkpoint import checkpoint_option
 from .gcn import (DROPOUT_MAX_LAYERS, check_dropout, check_loss, check_norm, dropout_option, layer_norm, layer_params,
                   linear, model_base, param_owner, sigmoid_bce_loss, softmax_cross_entropy_loss)
@@ -294,6 +315,108 @@ class gated_skip(param_owner):
         self.w.init(np.asarray(w, dtype=np.float32))
 
 
+def check_label_input(rate, loss: str, n_classes: int) -> int:
+    """option checking of label_input=, before any device work: the threshold floor(rate * 2^32) of a rate in [0, 1);
+    ValueError naming label_input for another rate and, with a rate above 0, for loss="bce" (a row has one label to feed)
+    and for more classes than the kernels take"""
+    threshold = label_mask.threshold(rate)
+    if rate > 0.0:
+        if loss == "bce":
+            raise ValueError('label_input needs one class per vertex: loss="bce" (multi-label targets) has no label input')
+        if n_classes > ops.LABEL_INPUT_MAX_CLASSES:
+            raise ValueError(f"label_input supports at most {ops.LABEL_INPUT_MAX_CLASSES} classes, the model has {n_classes}")
+    return threshold
+
+
+def refuse_label_input(model, what: str) -> None:
+    """ValueError naming the option when ``model`` feeds labels: ``what`` is a member such a model does not have yet (read
+    with getattr: a model built without __init__ has neither attribute)"""
+    if getattr(model, "label", None) is not None or getattr(model, "label_input_p", 0.0) > 0.0:
+        raise ValueError(f"gat(label_input={getattr(model, 'label_input_p', 0.0)}) has no {what}")
+
+
+def label_lists(S, Y, train_set: int, n_classes: int):
+    """(rows, cls, cls_ptr) of the label-input kernels from host arrays of n sets and n labels: the rows of ``train_set``
+    sorted by (class, row), their classes, and the segment of each class -- int32 arrays of T, T and n_classes + 1.
+    ValueError naming label_input for a label outside [0, n_classes) on a training row."""
+    s, y = np.asarray(S).reshape(-1), np.asarray(Y).reshape(-1)
+    if s.size != y.size:
+        raise ValueError(f"label_input: {y.size} labels for {s.size} vertices")
+    train = np.flatnonzero(s == train_set)
+    yt = y[train].astype(np.int64)
+    bad = np.flatnonzero((yt < 0) | (yt >= n_classes))
+    if bad.size:
+        raise ValueError(f"label_input: training row {int(train[bad[0]])} has label {int(yt[bad[0]])}, outside [0, {n_classes})")
+    order = np.argsort(yt, kind="stable")               # ``train`` ascends, so a stable sort by class is (class, row)
+    cls_ptr = np.zeros(n_classes + 1, dtype=np.int64)
+    np.cumsum(np.bincount(yt, minlength=n_classes), out=cls_ptr[1:])
+    return train[order].astype(np.int32), yt[order].astype(np.int32), cls_ptr.astype(np.int32)
+
+
+class label_input:
+    """The masked label input of layer 0 (gat(label_input=rate); the label trick of UniMP): the trained table ``E``
+    [classes x width of layer 0's Z] (seed-99 uniform like att), its gradient and Adam state -- a row of the fused Adam
+    table with W's weight decay --, the device lists of the training rows the two kernels of csrc/label_input.hip walk
+    (``rows``, ``cls``, ``cls_ptr``: set_lists, None before) and ``S_e``, the sets the loss sees in a training forward
+    (fed rows in the "other" slot).  ``call`` is set by the model before every forward and read again by backward():
+    (threshold, feed_all, seed, epoch, write S_e).
+
+    A parameter owner by its table and gcn.param_owner's own three methods, not by inheritance: it sits in the MODEL's
+    slot of layer 0 alone, not in a slot every layer of a kind has, which is what the subclasses of param_owner are
+    enumerated for (the checkpoint's names per layer)."""
+
+    params_table = (("label", "E", "G_E", "m", "v", True),)
+    adam_fused = True
+    step = 0
+    m = v = None
+    adam_state, adam_tensors, adam_update = param_owner.adam_state, param_owner.adam_tensors, param_owner.adam_update
+
+    def __init__(self, name: str, n_classes: int, width: int, device=None):
+        self.name = name
+        self.E, self.G_E = dn_matrix(n_classes, width, device=device), dn_matrix(n_classes, width, device=device)
+        host = np.empty((n_classes, width), dtype=np.float32)
+        _lib.load().mggcn_init_uniform_host(host.ctypes.data, width, n_classes, -1.0)
+        self.E.init(host)
+        self.rows = self.cls = self.cls_ptr = self.S_e = None
+        self.train_set = 0
+        self.call = None
+
+    def set_lists(self, rows, cls, cls_ptr, S, train_set: int) -> None:
+        """the host lists of label_lists and the host sets (n x 1): uploaded once, S_e starts as a copy of the sets"""
+        device = self.E.t.device
+        self.rows, self.cls, self.cls_ptr = (dn_matrix.from_numpy(a.reshape(-1, 1), device=device) for a in (rows, cls, cls_ptr))
+        self.S_e = dn_matrix.from_numpy(np.ascontiguousarray(S, dtype=np.int32).reshape(-1, 1), device=device)
+        self.train_set = int(train_set)
+
+    def __call__(self, ctx: context, Z: dn_matrix, row0: int = 0) -> None:
+        """Z[fed rows] += E[their class]; a training forward also rewrites the training rows of S_e"""
+        n = self.name
+        threshold, feed_all, seed, epoch, write = self.call
+        ctx.record(n + "0_0_label-input", 0)
+        ops.label_input_forward(ctx, self.rows, self.cls, self.E, Z, threshold, feed_all, seed, epoch, row0, self.train_set,
+                                ops.LABEL_INPUT_FED_SET, self.S_e if write else None)
+        ctx.record(n + "0_1_label-input", 0)
+        ctx.register_timer(n + "0_label-input", n + "0_0_label-input", n + "0_1_label-input")
+
+    def backward(self, ctx: context, G_Z: dn_matrix, row0: int = 0) -> None:
+        """G_E from the gradient of Z, with the mask of the forward"""
+        n = self.name
+        threshold, feed_all, seed, epoch, _ = self.call
+        ctx.record(n + "1_0_label-input", 0)
+        ops.label_input_backward(ctx, self.rows, self.cls, self.cls_ptr, G_Z, self.G_E, threshold, feed_all, seed, epoch, row0)
+        ctx.record(n + "1_1_label-input", 0)
+        ctx.register_timer(n + "1_label-input", n + "1_0_label-input", n + "1_1_label-input")
+
+    def init(self, E) -> None:
+        E = np.asarray(E, dtype=np.float32)
+        if E.shape != self.E.shape():
+            raise ValueError(f"label_input: label_weights must be {self.E.n()} x {self.E.m()}, got {E.shape}")
+        self.E.init(E)
+
+
+_label_input_owner = label_input         # gat's constructor has an argument of that name
+
+
 class gat_layer(layer_params):
     """One GAT layer: a ``linear`` (Z = H W + 1 b^T), an ``attention`` over (F, F^T) and the activation.  Z, the
     aggregated ``out`` (before the activation: the backward pass needs it) and the activated output are kept per layer;
@@ -304,6 +427,7 @@ class gat_layer(layer_params):
     (the skip itself where it has the gate parameter) and ``norm``, each None where the layer has none."""
 
     res_lin = gate = norm = None
+    label = None                # the model's label_input, in layer 0 of gat(label_input=rate) only
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
                  slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None,
@@ -359,6 +483,8 @@ class gat_layer(layer_params):
             self._drop(ctx, H, "0")
         self.H = H
         self.lin(ctx, H, self.Z)
+        if self.label is not None:                           # [H | M onehot(y)] [W ; E] = H W + M E[y]: the skip sees H only
+            self.label(ctx, self.Z, self.row0)
         self.attn(ctx, self.F, self.Z, self.out, self.attn_dropout)
         if self.skip is not None or self.norm is not None:
             # attention -> skip -> norm -> activation; ``out`` stays as the attention wrote it (its backward reads it), y
@@ -398,6 +524,8 @@ class gat_layer(layer_params):
             ctx.register_timer(n + "1_activation", n + "1_0_activation", n + "1_1_activation")
             T = self.act
         self.attn.backward(ctx, self.F, self.F_T, self.Z, T, self.out, self.G_Z, self.attn_dropout)
+        if self.label is not None:
+            self.label.backward(ctx, self.G_Z, self.row0)
         self.lin.setX(self.H)
         self.lin.backward(ctx, self.G_Z, self.G_out)
         if G_r is not None:                                  # the skip branch adds its share of the input's gradient
@@ -426,7 +554,7 @@ class gat_layer(layer_params):
         return [self.lin]
 
     def owners(self):
-        pairs = (("", self.lin), ("", self.attn), ("res_", self.res_lin), ("", self.gate), ("", self.norm))
+        pairs = (("", self.lin), ("", self.attn), ("res_", self.res_lin), ("", self.gate), ("", self.norm), ("", self.label))
         return [(prefix, o) for prefix, o in pairs if o is not None]
 
     def att(self): return self.attn.att
@@ -528,9 +656,10 @@ def refuse_dot(model, what: str) -> None:
 
 def refuse_checkpoint(model, member: str) -> None:
     """what save, load and _write_checkpoint of gat refuse, before anything is read, written or created: dot-product
-    attention and the skip options, which no version of the checkpoint file stores"""
+    attention, the skip options and the label input, which no version of the checkpoint file stores"""
     refuse_dot(model, f"{member} has no version for this variant yet")
     refuse_skip(model, f"{member} has no version that stores this option yet")
+    refuse_label_input(model, f"{member} has no version that stores the label table E yet")
 
 
 class attention_model:
@@ -614,7 +743,7 @@ class gat(attention_model, model_base):
     """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
 
     gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
-    variant="v1", skip=None, norm=None, skip_weights=None):
+    variant="v1", skip=None, norm=None, skip_weights=None, label_input=0.0, label_weights=None):
     ``A`` as ``gcn`` takes it (the layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
     (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att);
     ``variant``: "v1" (this model as it always was) or "v2" (GATv2, see the module docstring: W is [in x 2 out], b
@@ -622,7 +751,8 @@ class gat(attention_model, model_base):
     (dot-product attention, see the module docstring: W is [in x 3 out], b [1 x 3 out], no att; the refusals of "v2" plus
     attention_weights, save, load and rows x 3 out >= 2^31); ``skip``: None, "add" or "gate", ``norm``: None or "layer",
     ``skip_weights``: per layer (W_r, b_r) or (W_r, b_r, w_gate) -- see the module docstring; ValueError for another name or
-    a list that does not fit, and for save / load / save_best on a model that has either.  ValueError
+    a list that does not fit, and for save / load / save_best on a model that has either; ``label_input``: the rate in
+    [0, 1) of masked label inputs and ``label_weights``: their table E -- see the module docstring and set_label_input.  ValueError
     before any device work for a width that its heads do not divide or a limit of the kernels (ops.GAT_MAX_HEADS,
     ops.GAT_MAX_WIDTH).  ``fused`` picks how Adam is launched -- one launch for every parameter tensor, or one per tensor;
     the element-wise math is the same, so both give the same bits -- and every other kernel is the same in both modes.
@@ -641,7 +771,8 @@ class gat(attention_model, model_base):
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
                  loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0,
-                 variant: str = "v1", skip=None, norm=None, skip_weights=None):
+                 variant: str = "v1", skip=None, norm=None, skip_weights=None, label_input: float = 0.0,
+                 label_weights=None):
         self.sizes = [int(s) for s in sizes]
         self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
         self._attn_dropout_params = check_dropout(attn_dropout, len(self.sizes) - 1)
@@ -651,6 +782,9 @@ class gat(attention_model, model_base):
         self._init_dropout(dropout, len(self.sizes) - 1)
         self.attn_dropout_p = float(attn_dropout)
         self.loss = check_loss(loss)
+        self._label_threshold = check_label_input(label_input, self.loss, self.sizes[-1])
+        if label_weights is not None and not label_input > 0.0:
+            raise ValueError("label_weights needs label_input > 0")
         if A.n() != A.m():
             raise ValueError(f"gat needs a square matrix, got {A.n()} x {A.m()}")
         self.attn_slope = float(attn_slope)
@@ -690,6 +824,11 @@ class gat(attention_model, model_base):
                 self.layers_.append(gat_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
                                               i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer, **more))
         self._adam = None
+        self.label_input_p = float(label_input)
+        if self.label_input_p > 0.0:                             # with 0 nothing is allocated, launched or registered
+            self.label = self.layers_[0].label = _label_input_owner("0_", self.sizes[-1], self.layers_[0].Z.m())
+            if label_weights is not None:
+                self.label.init(label_weights)
         if skip_weights is not None:
             for layer, w in zip(self.layers_, skip_weights):
                 layer.res_lin.W.init(np.asarray(w[0], dtype=np.float32))
@@ -703,6 +842,96 @@ class gat(attention_model, model_base):
                 layer.b().init(np.asarray(w[1], dtype=np.float32))
                 if len(w) > 2:
                     layer.attn.init(w[2])
+
+    # ---- masked label inputs (label_input=rate) ----------------------------------------------------------------------------
+    label = None                        # the label_input owner; layers()[0].label is the same object
+    label_input_p = 0.0
+    label_seed = label_epoch = 0
+    _label_Y = _label_rows = _label_splits = _label_count = None
+
+    def set_label_input(self, Y, rate: Optional[float] = None, seed: int = 0, epoch: int = 0) -> None:
+        """Hands a gat(label_input=rate) model the labels it feeds.  Y: what train_step takes (an int32 dn_matrix of n x 1,
+        or n integers); rate: None keeps the current one, else a number in [0, 1) -- with 0 a training forward feeds
+        nothing and a plain one still feeds every training row; seed: 64 bits; epoch: the number the next training forward
+        gets (set_label_input(Y, epoch=e) replays training forward e, the way set_dropout does).  Needs set_splits first;
+        a later set_splits rebuilds the lists.  ValueError naming label_input, before any device work and before anything is
+        stored, for a model built without the option, a rate outside [0, 1), missing splits and a label outside
+        [0, classes) on a training row."""
+        if self.label is None:
+            raise ValueError("set_label_input needs a model built with label_input > 0: gat(..., label_input=rate)")
+        threshold = self._label_threshold if rate is None else check_label_input(rate, self.loss, self.sizes[-1])
+        if self.loss_layer.S is None and self._label_splits is None:
+            raise ValueError("label_input: set_label_input needs set_splits(S) first (the training rows are the ones fed)")
+        y = np.ascontiguousarray(Y.numpy() if isinstance(Y, dn_matrix) else Y).reshape(-1)
+        if y.dtype.kind not in "iu" or y.size != self.A.n():
+            raise ValueError(f"label_input: Y must hold {self.A.n()} integer labels, got {y.dtype} of {y.size}")
+        self._build_label_lists(y)
+        self._label_Y, self._label_threshold = y, threshold
+        if rate is not None:
+            self.label_input_p = float(rate)
+        self.label_seed, self.label_epoch, self._label_count = int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch), None
+
+    def _build_label_lists(self, y) -> None:
+        """the kernels' lists from the labels and the splits the loss layer holds (one copy of S to the host, here only)"""
+        if self._label_splits is None:                           # (S, counts, train_set) as set_splits left them
+            ll = self.loss_layer
+            self._label_splits = (ll.S, list(ll.counts), ll.train_set)
+        S, _, train_set = self._label_splits
+        host = S.numpy()
+        rows, cls, cls_ptr = label_lists(host, y, train_set, self.sizes[-1])
+        self.label.set_lists(rows, cls, cls_ptr, host, train_set)
+        self._label_rows = np.sort(rows).astype(np.uint64) + np.uint64(self.layers_[0].row0)     # global row numbers
+
+    def set_splits(self, S, train_set: int = 0) -> None:
+        """model_base.set_splits; a label-input model that has its labels rebuilds its lists from the new splits"""
+        model_base.set_splits(self, S, train_set)
+        if self.label is not None:
+            self._label_splits, self._label_count = None, None
+            if self.loss_layer.S is None:
+                self.label.rows = None                           # no splits: a forward asks for set_label_input again
+            elif self._label_Y is not None:
+                self._build_label_lists(self._label_Y)
+
+    def _fed_count(self, epoch: int) -> int:
+        """how many training rows training forward ``epoch`` feeds: the host's own Philox over the T training rows
+        (label_mask), taken from _launched's look-ahead when that was for the same draw"""
+        key = (epoch, self.label_seed, self._label_threshold)
+        if self._label_count is None or self._label_count[0] != key:
+            self._label_count = (key, label_mask.fed_count(self._label_rows, self._label_threshold, self.label_seed, epoch))
+        return self._label_count[1]
+
+    def _arm_label_input(self, training: bool) -> None:
+        """hands layer 0's label_input the call of this forward and the loss layer the sets and counts that go with it: a
+        training forward draws epoch ``label_epoch`` (and moves it on), its fed rows count as "other"; any other forward
+        feeds every training row and leaves the splits as set_splits gave them.  ValueError before anything is launched."""
+        lab, ll = self.label, self.loss_layer
+        if lab.rows is None:
+            raise ValueError("gat(label_input=...): call set_label_input(Y) after set_splits(S) before the first forward")
+        S, counts, train_set = self._label_splits
+        if not training:
+            ll.S, ll.counts = S, list(counts)
+            lab.call = (0, True, 0, 0, False)
+            return
+        fed = self._fed_count(self.label_epoch)
+        if counts[train_set] - fed <= 0:
+            raise ValueError(f"label_input: training forward {self.label_epoch} feeds all {counts[train_set]} training "
+                             "rows, none is left to predict (lower the rate)")
+        now = list(counts)
+        now[train_set] -= fed
+        now[ops.LABEL_INPUT_FED_SET] += fed
+        ll.S, ll.counts = lab.S_e, now
+        lab.call = (self._label_threshold, False, self.label_seed, self.label_epoch & 0xFFFFFFFF, True)
+        self.label_epoch += 1
+
+    def __call__(self, ctx: context, H: dn_matrix, training: bool = False) -> dn_matrix:
+        if self.label is not None:
+            self._arm_label_input(training)
+        return model_base.__call__(self, ctx, H, training)
+
+    def _launched(self) -> None:
+        """train_step's hook between its last launch and its synchronisation: the next epoch's count, while the device works"""
+        if self.label is not None:
+            self._fed_count(self.label_epoch)
 
     def attention_weights(self, ctx, X=None, layers=None, out=None) -> List[dn_matrix]:
         """attention_model.attention_weights; ValueError for variant="dot" before anything else"""

@@ -991,8 +991,13 @@ class model_base(dropout_option, checkpoint_option):
         self.loss_layer(ctx, out, Y, sync=False)
         self.backward(ctx)
         self.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+        self._launched()
         ctx.sync()
         return self.loss_layer.read(ctx)
+
+    def _launched(self) -> None:
+        """hook: train_step has enqueued the whole epoch and is about to wait for it -- host work that can run under the
+        device's goes here (gat: the next epoch's label-input count).  Nothing by default."""
 
     def adam_update(self, ctx: context, lr: float, beta1: float, beta2: float, weight_decay: float,
                     eps: float) -> None:

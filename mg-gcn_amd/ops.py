@@ -492,6 +492,57 @@ def check_gat_heads(heads: int, width: int, what: str = "gat") -> int:
     return width // int(heads)
 
 
+LABEL_INPUT_MAX_CLASSES = 256       # MGGCN_LABEL_INPUT_MAX_CLASSES
+LABEL_INPUT_MAX_WIDTH = 3 * GAT_MAX_WIDTH      # MGGCN_LABEL_INPUT_MAX_WIDTH: the Z of a dot-product layer
+LABEL_INPUT_FED_SET = 3             # the "other" slot of the split-aware loss: where a fed training row is counted
+
+
+def _req_label_input(rows, cls, E, M, threshold: int, row0: int, what: str) -> None:
+    """what both passes share: the lists, the table's shape and limits, ``M`` = Z or G_Z; shape-only objects are enough"""
+    C, width = E.n(), E.m()
+    _req(1 <= C <= LABEL_INPUT_MAX_CLASSES, f"{what} supports 1 <= classes <= {LABEL_INPUT_MAX_CLASSES}, got {C}")
+    _req(1 <= width <= LABEL_INPUT_MAX_WIDTH, f"{what} supports 1 <= width <= {LABEL_INPUT_MAX_WIDTH} columns, got {width}")
+    _req(M.m() == width, f"{what}: the table has {width} columns, the rows {M.m()}")
+    _req(rows.m() == 1 and cls.shape() == rows.shape(), f"{what}: rows and cls must both be {rows.n()} x 1")
+    _req(rows.n() <= M.n(), f"{what}: {rows.n()} listed rows, the matrix has {M.n()}")
+    _req(isinstance(threshold, numbers.Integral) and 0 <= threshold < 1 << 32, f"{what}: threshold must be a uint32, got {threshold!r}")
+    _req(int(row0) >= 0, f"{what}: row0 must not be negative")
+
+
+def label_input_forward(ctx: context, rows: dn_matrix, cls: dn_matrix, E: dn_matrix, Z: dn_matrix, threshold: int,
+                        feed_all: bool, seed: int, epoch: int, row0: int = 0, kept_set: int = 0,
+                        fed_set: int = LABEL_INPUT_FED_SET, S_out: Optional[dn_matrix] = None) -> None:
+    """Z[rows[t]] += E[cls[t]] for the listed training rows that are fed this forward, and S_out[rows[t]] = fed_set for
+    those, kept_set for the other listed rows (mggcn_label_input_forward_f32).  rows, cls: int32 [T x 1], sorted by (class,
+    row) without duplicates; E: [classes x width]; Z: [n x width]; S_out: int32 [n x 1] or None.  A row is fed when
+    ``feed_all``, or when its Philox word (label_mask.words on row0 + row, seed, epoch) is below ``threshold``.
+    ValueError for a limit (LABEL_INPUT_MAX_CLASSES, LABEL_INPUT_MAX_WIDTH) or a shape that does not fit, before the library
+    is touched (it would print and exit, not raise)."""
+    what = "label input"
+    _req_label_input(rows, cls, E, Z, threshold, row0, what)
+    _req(S_out is None or S_out.shape() == (Z.n(), 1), f"{what}: S_out must be {Z.n()} x 1")
+    _req(kept_set in TRAIN_SETS and fed_set == int(fed_set), f"{what}: kept_set must be one of {TRAIN_SETS}, got {kept_set!r}")
+    ctx.lib.mggcn_label_input_forward_f32(ctx.stream(0), rows.buffer(), cls.buffer(), rows.n(), E.buffer(), E.m(), E.n(),
+                                          E.m(), int(threshold), int(bool(feed_all)), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                          int(epoch) & 0xFFFFFFFF, int(row0), int(kept_set), int(fed_set), Z.buffer(), Z.m(),
+                                          Z.n(), None if S_out is None else S_out.buffer())
+
+
+def label_input_backward(ctx: context, rows: dn_matrix, cls: dn_matrix, cls_ptr: dn_matrix, G_Z: dn_matrix, G_E: dn_matrix,
+                         threshold: int, feed_all: bool, seed: int, epoch: int, row0: int = 0) -> None:
+    """G_E[c] = the sum of G_Z[rows[t]] over the fed rows of class c, +0.0 for a class without one
+    (mggcn_label_input_backward_f32); the mask is the forward's, from the same (threshold, feed_all, seed, epoch, row0).
+    cls_ptr: int32 [(classes + 1) x 1], the segment of each class in the lists.  G_E is bitwise reproducible.  The same checks
+    before the library as label_input_forward."""
+    what = "label input backward"
+    _req_label_input(rows, cls, G_E, G_Z, threshold, row0, what)
+    _req(cls_ptr.shape() == (G_E.n() + 1, 1), f"{what}: cls_ptr must be {G_E.n() + 1} x 1")
+    ctx.lib.mggcn_label_input_backward_f32(ctx.stream(0), rows.buffer(), cls.buffer(), cls_ptr.buffer(), rows.n(), G_E.n(),
+                                           G_E.m(), int(threshold), int(bool(feed_all)), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(epoch) & 0xFFFFFFFF, int(row0), G_Z.buffer(), G_Z.m(), G_Z.n(), G_E.buffer(),
+                                           G_E.m())
+
+
 def _gat_timed(ctx: context, timer: Optional[str], call) -> None:
     """``call()`` between two events on the compute stream, registered as ``timer`` (None: no events)"""
     if timer is None:
