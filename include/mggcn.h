@@ -606,6 +606,83 @@ void mggcn_gatdot_backward_src_f32(mggcn_stream_t stream, uint32_t n_rows, uint3
                                    const float *Zv, size_t ldv, const float *lse, const float *D, const float *G, size_t ldg,
                                    uint32_t K, uint32_t dh, float scale, float *G_Zk, size_t ldgzk, float *G_Zv,
                                    size_t ldgzv);
+/* bf16 gathers of the attention kernels (opt-in; gat(agg_dtype="bf16")).  Every dense [rows x width] operand that a sparse
+ * attention kernel indexes by an entry's COLUMN -- the gathered role -- is read from a bf16 image of the fp32 tensor
+ * (uint16_t bit patterns, as mggcn_convert_f32_bf16 writes them: round to nearest even), half the bytes per gathered row.
+ * Everything else stays fp32 and is read from the fp32 tensor: every operand indexed by the kernel's own row, the [n x K]
+ * scalars (s_dst, s_src, lse, D, ds_*), all arithmetic and sums, every output.  The gathered roles:
+ *              forward / backward_dst (rows of F)     backward_src (rows of F^T)
+ *   gat        Z                                      G
+ *   gatv2      Zs                                     Zd, G
+ *   gatdot     Zk, Zv                                 Zq, G
+ * so a self-loop entry meets the rounded row in the gathered role and the fp32 row in the own role.
+ * Each entry below is the twin of the entry of the same name ending in _f32 (mggcn_gat_forward_bf16 of
+ * mggcn_gat_forward_f32, mggcn_gat_forward_drop_bf16 of mggcn_gat_forward_drop_f32, ...): the same argument list with the
+ * gathered operands as const uint16_t * and their leading dimensions counted in ELEMENTS, the same null-operand rules,
+ * n_rows == 0 returns, the same aliasing rules, the same limits (MGGCN_GAT_MAX_HEADS, MGGCN_GAT_MAX_WIDTH).  The kernel is
+ * the fp32 kernel with the gathered loads on the image -- one 8-byte load for a lane's four columns, one 2-byte load for a
+ * single column -- and each value widened exactly (bits << 16: -0.0 and the denormals survive); the lane -> column map, the
+ * summation order and the five (VEC, NT, U) variants are the fp32 entry's.  The variant follows the fp32 rule with the
+ * alignment counted in elements: a bf16 operand qualifies for the four-column path when its base is 8-byte aligned and
+ * its leading dimension is a multiple of 4 elements; the fp32 operands of the call keep the 16-byte rule.
+ * CONTRACT: the result equals that of the _f32 entry called on the exactly widened images (equally aligned in elements),
+ * bit for bit -- every output, for every variant, for a row range passed as a call of its own, and for the _drop forms with
+ * any (threshold, seed, stream, dst0, src0).  There is no bf16 form of the record entries (_rec_), the pack, scores and
+ * export entries. */
+void mggcn_gat_forward_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                            const uint32_t *indices, const uint16_t *Z, size_t ldz, const float *s_dst, const float *s_src,
+                            uint32_t K, uint32_t dh, float slope, float *out, size_t ldo, float *lse);
+void mggcn_gat_backward_dst_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                 const uint32_t *indices, const uint16_t *Z, size_t ldz, const float *s_dst, const float *s_src,
+                                 const float *lse, const float *G, size_t ldg, const float *out, size_t ldo, uint32_t K,
+                                 uint32_t dh, float slope, float *D, float *ds_dst);
+void mggcn_gat_backward_src_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                 const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
+                                 const float *lse, const float *D, const uint16_t *G, size_t ldg, const float *att,
+                                 const float *ds_dst, uint32_t K, uint32_t dh, float slope, float *ds_src, float *G_Z,
+                                 size_t ldgz);
+void mggcn_gat_forward_drop_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                 const uint32_t *indices, const uint16_t *Z, size_t ldz, const float *s_dst, const float *s_src,
+                                 uint32_t K, uint32_t dh, float slope, float *out, size_t ldo, float *lse, uint32_t threshold,
+                                 float scale, uint64_t seed, uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
+void mggcn_gat_backward_dst_drop_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                      const uint32_t *indices, const uint16_t *Z, size_t ldz, const float *s_dst,
+                                      const float *s_src, const float *lse, const float *G, size_t ldg, const float *out,
+                                      size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *ds_dst,
+                                      uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream, uint32_t dst0,
+                                      uint32_t src0);
+void mggcn_gat_backward_src_drop_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                      const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst,
+                                      const float *s_src, const float *lse, const float *D, const uint16_t *G, size_t ldg,
+                                      const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
+                                      float *ds_src, float *G_Z, size_t ldgz, uint32_t threshold, float scale, uint64_t seed,
+                                      uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
+void mggcn_gatv2_forward_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                              const uint32_t *indices, const uint16_t *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                              const float *att, uint32_t K, uint32_t dh, float slope, float *out, size_t ldo, float *lse);
+void mggcn_gatv2_backward_dst_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                   const uint32_t *indices, const uint16_t *Zs, size_t ldzs, const float *Zd, size_t ldzd,
+                                   const float *att, const float *lse, const float *G, size_t ldg, const float *out, size_t ldo,
+                                   uint32_t K, uint32_t dh, float slope, float *D, float *G_Zd, size_t ldgzd, float *P,
+                                   size_t ldp);
+void mggcn_gatv2_backward_src_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                   const uint32_t *t_indices, const float *Zs, size_t ldzs, const uint16_t *Zd, size_t ldzd,
+                                   const float *att, const float *lse, const float *D, const uint16_t *G, size_t ldg, uint32_t K,
+                                   uint32_t dh, float slope, float *G_Zs, size_t ldgzs);
+void mggcn_gatdot_forward_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                               const uint32_t *indices, const float *Zq, size_t ldq, const uint16_t *Zk, size_t ldk,
+                               const uint16_t *Zv, size_t ldv, uint32_t K, uint32_t dh, float scale, float *out, size_t ldo,
+                               float *lse);
+void mggcn_gatdot_backward_dst_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                    const uint32_t *indices, const float *Zq, size_t ldq, const uint16_t *Zk, size_t ldk,
+                                    const uint16_t *Zv, size_t ldv, const float *lse, const float *G, size_t ldg,
+                                    const float *out, size_t ldo, uint32_t K, uint32_t dh, float scale, float *D, float *G_Zq,
+                                    size_t ldgzq);
+void mggcn_gatdot_backward_src_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                    const uint32_t *t_indices, const uint16_t *Zq, size_t ldq, const float *Zk, size_t ldk,
+                                    const float *Zv, size_t ldv, const float *lse, const float *D, const uint16_t *G,
+                                    size_t ldg, uint32_t K, uint32_t dh, float scale, float *G_Zk, size_t ldgzk, float *G_Zv,
+                                    size_t ldgzv);
 /* cublasSasum  (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

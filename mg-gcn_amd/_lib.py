@@ -163,6 +163,15 @@ PROTOTYPES = {
     "mggcn_init_uniform_host": (None, [vp, c_size_t, c_size_t, c_float]),
 }
 
+# bf16 gathers of the attention kernels: each entry is its _f32 twin with the gathered operands as bf16 images -- pointers
+# in the same places, leading dimensions in elements --, so the foreign signature is the twin's
+GAT_BF16_ENTRIES = tuple(f"mggcn_{kernel}_{call}{drop}_bf16"
+                         for kernel, drops in (("gat", ("", "_drop")), ("gatv2", ("",)), ("gatdot", ("",)))
+                         for drop in drops for call in ("forward", "backward_dst", "backward_src"))
+for _name in GAT_BF16_ENTRIES:
+    PROTOTYPES[_name] = PROTOTYPES[_name[:-len("bf16")] + "f32"]
+del _name
+
 _lib = None
 
 

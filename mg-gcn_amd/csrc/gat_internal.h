@@ -1,6 +1,6 @@
 // gat_internal.h -- what the graph attention kernels of gat.hip (GAT), gatv2.hip (GATv2) and gatdot.hip share: the one-wave-per-row
 // layout with LPR-lane groups (gat.hip describes it), the walk over a row's entries (entry_chunks), the group butterfly,
-// the head-row loads, zero, dot product, axpy and the epilogue, D = G . out of a row (head_row_D), the (lse, D) fetch of an
+// the head-row loads (of fp32 rows and, for the _b16 translation units, of bf16 images), zero, dot product, axpy and the epilogue, D = G . out of a row (head_row_D), the (lse, D) fetch of an
 // entry's destination (fetch_lse_D), the per-group online softmax of the GATv2 and dot-product forwards (group_softmax), the
 // head geometry, the (VEC, NT, U) dispatch with the row launch, and the column-sum pass behind G_att.  Internal linkage in
 // each translation unit that includes it.  Not part of the ABI.
@@ -38,6 +38,19 @@ __device__ __forceinline__ void loadv(float (&r)[VEC], const float *p) {
         r[0] = *p;
     }
 }
+// The same columns of a bf16 image (bit patterns, uint16_t): one 8-byte load for four columns, one 2-byte load for one, and
+// every value widened exactly -- its bits shifted left by 16, so -0.0 and the denormals survive.  What follows a load is
+// the fp32 instruction stream in the fp32 order: a kernel on an image gives the bits it gives on the widened fp32 operand.
+template <int VEC>
+__device__ __forceinline__ void loadv(float (&r)[VEC], const uint16_t *p) {
+    if constexpr (VEC == 4) {
+        const uint2 t = *reinterpret_cast<const uint2 *>(p);
+        r[0] = __uint_as_float(t.x << 16); r[1] = __uint_as_float(t.x & 0xFFFF0000u);
+        r[2] = __uint_as_float(t.y << 16); r[3] = __uint_as_float(t.y & 0xFFFF0000u);
+    } else {
+        r[0] = __uint_as_float((uint32_t)*p << 16);
+    }
+}
 template <int VEC>
 __device__ __forceinline__ void storev(float *p, const float (&r)[VEC]) {
     if constexpr (VEC == 4) *reinterpret_cast<float4 *>(p) = make_float4(r[0], r[1], r[2], r[3]);
@@ -49,9 +62,9 @@ __device__ __forceinline__ void zerov(float (&r)[VEC]) {
     for (int v = 0; v < VEC; v++) r[v] = 0.f;
 }
 
-// the head-row of `row` (NT tiles of VEC columns per lane), zeros beyond dh
-template <int VEC, int NT>
-__device__ __forceinline__ void load_head_row(float (&r)[NT][VEC], const float *p, uint32_t lpr, uint32_t sub, uint32_t dh,
+// the head-row of `row` (NT tiles of VEC columns per lane), zeros beyond dh; T: float, or uint16_t for a bf16 image
+template <int VEC, int NT, class T>
+__device__ __forceinline__ void load_head_row(float (&r)[NT][VEC], const T *p, uint32_t lpr, uint32_t sub, uint32_t dh,
                                               bool on = true) {
 #pragma unroll
     for (int t = 0; t < NT; t++) {
@@ -265,6 +278,8 @@ void require_heads(uint32_t K, uint32_t dh) {
 }
 
 bool rows16(const float *p, size_t ld) { return aligned16(p) && ld % 4 == 0; }
+// the same rule counted in elements for a bf16 image: four columns are 8 bytes there
+[[maybe_unused]] bool rows16(const uint16_t *p, size_t ld) { return (reinterpret_cast<uintptr_t>(p) & 7u) == 0 && ld % 4 == 0; }
 
 // (VEC, NT, U) from the path and the tile count: vec needs <= 4 tiles (dh <= 1024), the element path <= 16.  f gets the
 // variant as a tag; with_flag hands a run-time flag (DROP, REC) on as a std::bool_constant.

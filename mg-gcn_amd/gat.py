@@ -105,7 +105,35 @@ load / save_best (no version of the checkpoint file stores E; the selector's in-
 row partition (dist_gat does not take the arguments; the partial G_E would ride on layer 0's all-reduce), the checkpoint
 version, gcn, multi-label targets, the C++ layer.
 
-Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI, bf16 gathers.
+``agg_dtype="bf16"`` (default "f32": nothing new is allocated, launched or registered, the same bits as before) stores the
+GATHERED operand of every sparse attention kernel in bf16, as gcn(agg_dtype="bf16") does for its SpMM: every dense operand a
+kernel indexes by an entry's column is read from a bf16 image of the fp32 tensor (round to nearest even,
+mggcn_convert_f32_bf16), half the bytes per gathered row --
+
+    variant   forward / backward_dst (rows of F)   backward_src (rows of F^T)
+    v1        Z                                    G
+    v2        Zs                                   Zd, G
+    dot       Zk, Zv                               Zq, G
+
+-- and everything else stays fp32 and is read from the fp32 tensor: every operand indexed by the kernel's own row, the scores
+kernel and the [n x heads] scalars, all arithmetic and sums, every output, the GEMMs, skip, norm, label input, loss and Adam.
+A self-loop entry therefore meets the rounded row in the gathered role and the fp32 row in the own role.  The kernels are the
+fp32 kernels with the gathered loads on the image (csrc/*_b16.hip: mggcn_gat*_bf16), so a call equals the fp32 call on the
+exactly widened image bit for bit.  The model owns two bf16 buffers shared by all layers, ``Z_image_buffer``
+(n x 1 / 2 / 3 x the widest layer) and ``G_image_buffer`` (n x the widest layer); a layer makes its images itself -- forward:
+after the GEMM and the label-input embed, immediately before the forward kernel; backward: ALL of the backward pass's images
+in one block ahead of backward_dst, i.e. the forward's image again (the layers above have overwritten the shared buffer; same
+input, same bits) and with it what backward_src gathers (G, v2 Zd, dot Zq), one kernel early: nothing in between writes Z or
+G -- only in the columns that are gathered, under the timers ``<layer>0_gat-convert`` and ``<layer>1_gat-convert``.  evaluate, predict and a plain call run
+the bf16 forward; both dropouts, skip=, norm=, label_input=, loss="bce", splits, both Adam modes and model_selector compose.
+agg_dtype is an execution option: it is not written to checkpoints, and a file saved by either form loads into the other.
+attention_weights on v1 is unchanged (its scores and lse never see an image); on variant="v2" with agg_dtype="bf16"
+attention_weights and gatv2_layer.alpha raise ValueError naming agg_dtype before any device work (the export kernel would
+score the fp32 Zs against an lse taken over rounded rows).  Not built: dist_gat and bf16 on the wire, bf16 record forms, the
+v2 and dot export under bf16, any change of the lane geometry (eight columns per lane), the C++ layer and CLI
+(DESIGN.md 3.10.10).
+
+Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI.
 """
 from __future__ import annotations
 
@@ -115,8 +143,8 @@ import numpy as np
 
 from . import _lib, label_mask, ops
 from .checkpoint import checkpoint_option
-from .gcn import (DROPOUT_MAX_LAYERS, check_dropout, check_loss, check_norm, dropout_option, layer_norm, layer_params,
-                  linear, model_base, param_owner, sigmoid_bce_loss, softmax_cross_entropy_loss)
+from .gcn import (DROPOUT_MAX_LAYERS, _check_agg_dtype, check_dropout, check_loss, check_norm, dropout_option, layer_norm,
+                  layer_params, linear, model_base, param_owner, sigmoid_bce_loss, softmax_cross_entropy_loss)
 from .matrix import context, csr_matrix, dn_matrix
 
 
@@ -137,17 +165,67 @@ def check_heads(sizes: Sequence[int], heads) -> List[int]:
     return [int(h) for h in per_layer]
 
 
-class attention(param_owner):
+class gathered_images:
+    """What the three attentions share for gat(agg_dtype="bf16"): the bf16 images their sparse kernels gather from and the
+    conversion that makes them.  ``Z16`` is the image of the layer's Z buffer (all its columns: 1, 2 or 3 x out) and ``G16``
+    that of the gradient G [rows x out]; both alias the model's two image buffers (``images``) when given, as G_Z aliases
+    G_Z_buffer, and are None with agg_dtype="f32", where nothing is allocated, launched or registered.  The forward makes its
+    image immediately before the forward kernel; the backward makes all of its images in one block ahead of backward_dst --
+    the forward's again, because the layers above have overwritten the shared buffer since, and those of backward_src one
+    kernel early (nothing in between writes Z or G) -- and only in the columns that are gathered."""
+
+    agg_dtype = "f32"
+    Z16 = G16 = None
+
+    def _init_images(self, agg_dtype: str, rows_z: int, z_cols: int, rows_g: int, g_cols: int, images, device) -> None:
+        self.agg_dtype = _check_agg_dtype(agg_dtype)
+        if self.agg_dtype != "bf16":
+            return
+        import torch
+        z_buffer, g_buffer = images if images is not None else (None, None)
+
+        def image(buffer, rows, cols):
+            if buffer is None:
+                buffer = torch.empty(rows * cols, dtype=torch.bfloat16, device=device or "cuda")
+            return ops.bf16_image(buffer.view(-1)[: rows * cols].view(rows, cols))
+        self.Z16, self.G16 = image(z_buffer, rows_z, z_cols), image(g_buffer, rows_g, g_cols)
+
+    def _convert(self, ctx: context, tag: str, *parts) -> None:
+        """image[:, c0:c1] = bf16(M[:, c0:c1]), round to nearest even, for every (M, image, c0, c1) of ``parts``, under the
+        timer ``<name><tag>_gat-convert`` ("0": the forward's, "1": the backward's)"""
+        n = self.name
+        ctx.record(n + tag + "_0_gat-convert", 0)
+        for M, image, c0, c1 in parts:
+            ops.convert_bf16(ctx, M.t[:, c0:c1], image.t[:, c0:c1])
+        ctx.record(n + tag + "_1_gat-convert", 0)
+        ctx.register_timer(n + tag + "_gat-convert", n + tag + "_0_gat-convert", n + tag + "_1_gat-convert")
+
+
+def refuse_bf16_export(owner, what: str) -> None:
+    """ValueError naming agg_dtype when ``owner`` (a gat model, a gatv2_layer or an attention_v2) is GATv2 with bf16 gathers:
+    the export kernel would score the fp32 Zs against an lse taken over the rounded rows, which is not the coefficient the
+    model trains with.  v1 exports unchanged: its scores and lse never see an image."""
+    if getattr(owner, "agg_dtype", "f32") == "bf16" and getattr(owner, "variant", "v2") == "v2":
+        raise ValueError(f'gat(variant="v2", agg_dtype="bf16") has no {what}: the export kernel reads the fp32 Zs, the '
+                         'coefficients were trained on its bf16 image')
+
+
+class attention(gathered_images, param_owner):
     """The attention of one layer: the parameter ``att`` [2 x out] (row 0 the destination vector, row 1 the source
     vector; seed-99 uniform like W), its gradient and Adam state, and what the backward pass needs of the forward --
     s_dst, s_src, lse [n x heads].  att is trained by Adam with the weight decay of W; the per-tensor step of
-    gat(fused=False) is the fused kernel for every owner of an attention model, so both modes give the same bits."""
+    gat(fused=False) is the fused kernel for every owner of an attention model, so both modes give the same bits.
+    ``agg_dtype="bf16"``: forward and backward_dst gather Z, and backward_src gathers G, from bf16 images (gathered_images;
+    ``images``: the model's two buffers); the scores, and so s_dst, s_src and lse, come from the fp32 Z."""
 
     params_table = (("att", "att", "G_att", "m", "v", True),)
     adam_fused = True
     m = v = None
+    variant = "v1"
 
-    def __init__(self, name: str, n_dst: int, n_src: int, out: int, heads: int, slope: float = ops.GAT_SLOPE, device=None):
+    def __init__(self, name: str, n_dst: int, n_src: int, out: int, heads: int, slope: float = ops.GAT_SLOPE, device=None,
+                 agg_dtype: str = "f32", images=None):
+        self._init_images(agg_dtype, n_src, out, n_dst, out, images, device)
         self.name, self.heads, self.slope = name, int(heads), float(slope)
         self.att, self.G_att = dn_matrix(2, out, device=device), dn_matrix(2, out, device=device)
         host = np.empty((2, out), dtype=np.float32)
@@ -161,16 +239,29 @@ class attention(param_owner):
         ``drop``: attention dropout, the tuple of ops.gat_forward (None: the plain entry point)"""
         n = self.name
         ops.gat_scores(ctx, Z, self.att, self.s_dst, self.s_src, self.heads, n + "0_gat-scores")
-        ops.gat_forward(ctx, F, Z, self.s_dst, self.s_src, out, self.lse, self.heads, self.slope, n + "0_gat-forward", drop)
+        if self.Z16 is None:
+            ops.gat_forward(ctx, F, Z, self.s_dst, self.s_src, out, self.lse, self.heads, self.slope, n + "0_gat-forward", drop)
+            return
+        self._convert(ctx, "0", (Z, self.Z16, 0, Z.m()))
+        ops.gat_forward_bf16(ctx, F, self.Z16, self.s_dst, self.s_src, out, self.lse, self.heads, self.slope,
+                             n + "0_gat-forward", drop)
 
     def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z: dn_matrix, G: dn_matrix, out: dn_matrix,
                  G_Z: dn_matrix, drop=None) -> None:
         """G_Z = the gradient of Z and G_att, from G = the gradient of ``out``; ``drop``: what the forward was called with"""
         n = self.name
-        ops.gat_backward_dst(ctx, F, Z, self.s_dst, self.s_src, self.lse, G, out, self.D, self.ds_dst, self.heads, self.slope,
-                             n + "1_gat-backward-dst", drop)
-        ops.gat_backward_src(ctx, F_T, Z, self.s_dst, self.s_src, self.lse, self.D, G, self.att, self.ds_dst, self.ds_src,
-                             G_Z, self.heads, self.slope, n + "1_gat-backward-src", drop)
+        if self.Z16 is None:
+            ops.gat_backward_dst(ctx, F, Z, self.s_dst, self.s_src, self.lse, G, out, self.D, self.ds_dst, self.heads,
+                                 self.slope, n + "1_gat-backward-dst", drop)
+            ops.gat_backward_src(ctx, F_T, Z, self.s_dst, self.s_src, self.lse, self.D, G, self.att, self.ds_dst, self.ds_src,
+                                 G_Z, self.heads, self.slope, n + "1_gat-backward-src", drop)
+        else:
+            # both images in one timed block: nothing between the two kernels writes Z or G
+            self._convert(ctx, "1", (Z, self.Z16, 0, Z.m()), (G, self.G16, 0, G.m()))
+            ops.gat_backward_dst_bf16(ctx, F, self.Z16, self.s_dst, self.s_src, self.lse, G, out, self.D, self.ds_dst,
+                                      self.heads, self.slope, n + "1_gat-backward-dst", drop)
+            ops.gat_backward_src_bf16(ctx, F_T, Z, self.s_dst, self.s_src, self.lse, self.D, self.G16, self.att, self.ds_dst,
+                                      self.ds_src, G_Z, self.heads, self.slope, n + "1_gat-backward-src", drop)
         ops.gat_scores_backward(ctx, self.ds_dst, Z, self.ds_src, Z, self.G_att, self.heads, n + "1_gat-scores-backward")
 
     def alpha(self, ctx: context, F: csr_matrix, Z: dn_matrix, alpha: dn_matrix) -> None:
@@ -187,9 +278,15 @@ class attention_v2(attention):
     state (``attention``'s: a row of the fused Adam table with W's weight decay), and what the backward pass needs of the
     forward -- lse and D [n x heads].  ``P`` [n x out] holds the rows' shares of G_att between backward_dst and att_grad; it
     aliases ``P_buffer`` (the model's, at its widest layer) when one is given.  __call__ and backward take the layer's
-    Z2 = [Zs | Zd] and G_Z2 = [G_Zs | G_Zd] buffers of 2 out columns."""
+    Z2 = [Zs | Zd] and G_Z2 = [G_Zs | G_Zd] buffers of 2 out columns.  ``agg_dtype="bf16"``: forward and backward_dst gather
+    Zs, and backward_src gathers Zd and G, from bf16 images -- ``Z16`` is the image of Z2, its halves made when they are
+    gathered; Zd in the forward and Zs in backward_src are the rows' own and stay fp32.  The export is refused then."""
 
-    def __init__(self, name: str, n: int, out: int, heads: int, slope: float = ops.GAT_SLOPE, P_buffer=None, device=None):
+    variant = "v2"
+
+    def __init__(self, name: str, n: int, out: int, heads: int, slope: float = ops.GAT_SLOPE, P_buffer=None, device=None,
+                 agg_dtype: str = "f32", images=None):
+        self._init_images(agg_dtype, n, 2 * out, n, out, images, device)
         self.name, self.heads, self.slope = name, int(heads), float(slope)
         self.att, self.G_att = dn_matrix(1, out, device=device), dn_matrix(1, out, device=device)
         host = np.empty((1, out), dtype=np.float32)
@@ -201,10 +298,17 @@ class attention_v2(attention):
     def __call__(self, ctx: context, F: csr_matrix, Z2: dn_matrix, out: dn_matrix, drop=None) -> None:
         """out = the attention-weighted gather of Zs over F's rows, scored against Zd"""
         assert drop is None, "GATv2 has no attention dropout"
-        ops.gatv2_forward(ctx, F, Z2, Z2, self.att, out, self.lse, self.heads, self.slope, self.name + "0_gatv2-forward")
+        if self.Z16 is None:
+            ops.gatv2_forward(ctx, F, Z2, Z2, self.att, out, self.lse, self.heads, self.slope, self.name + "0_gatv2-forward")
+            return
+        self._convert(ctx, "0", (Z2, self.Z16, 0, out.m()))                    # Zs
+        ops.gatv2_forward_bf16(ctx, F, self.Z16, Z2, self.att, out, self.lse, self.heads, self.slope,
+                               self.name + "0_gatv2-forward")
 
     def alpha(self, ctx: context, F: csr_matrix, Z2: dn_matrix, alpha: dn_matrix) -> None:
-        """alpha [F.nnz() x heads] = the coefficients of the most recent forward over ``F``, from its Z2, att and lse"""
+        """alpha [F.nnz() x heads] = the coefficients of the most recent forward over ``F``, from its Z2, att and lse;
+        ValueError naming agg_dtype with bf16 gathers"""
+        refuse_bf16_export(self, "export of the attention coefficients")
         ops.gatv2_alpha(ctx, F, Z2, Z2, self.att, self.lse, alpha, self.heads, self.slope, self.name + "0_gatv2-alpha")
 
     def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z2: dn_matrix, G: dn_matrix, out: dn_matrix,
@@ -212,11 +316,20 @@ class attention_v2(attention):
         """G_Z2 = the gradient of Z2 (both halves) and G_att, from G = the gradient of ``out``"""
         assert drop is None, "GATv2 has no attention dropout"
         n = self.name
-        ops.gatv2_backward_dst(ctx, F, Z2, Z2, self.att, self.lse, G, out, self.D, G_Z2, self.P, self.heads, self.slope,
-                               n + "1_gatv2-backward-dst")
+        if self.Z16 is None:
+            ops.gatv2_backward_dst(ctx, F, Z2, Z2, self.att, self.lse, G, out, self.D, G_Z2, self.P, self.heads, self.slope,
+                                   n + "1_gatv2-backward-dst")
+            ops.gatv2_att_grad(ctx, self.P, self.G_att, n + "1_gatv2-att-grad")
+            ops.gatv2_backward_src(ctx, F_T, Z2, Z2, self.att, self.lse, self.D, G, G_Z2, self.heads, self.slope,
+                                   n + "1_gatv2-backward-src")
+            return
+        # Zs for backward_dst, Zd and G for backward_src, in one timed block: nothing between the kernels writes Z2 or G
+        self._convert(ctx, "1", (Z2, self.Z16, 0, Z2.m()), (G, self.G16, 0, G.m()))
+        ops.gatv2_backward_dst_bf16(ctx, F, self.Z16, Z2, self.att, self.lse, G, out, self.D, G_Z2, self.P, self.heads,
+                                    self.slope, n + "1_gatv2-backward-dst")
         ops.gatv2_att_grad(ctx, self.P, self.G_att, n + "1_gatv2-att-grad")
-        ops.gatv2_backward_src(ctx, F_T, Z2, Z2, self.att, self.lse, self.D, G, G_Z2, self.heads, self.slope,
-                               n + "1_gatv2-backward-src")
+        ops.gatv2_backward_src_bf16(ctx, F_T, Z2, self.Z16, self.att, self.lse, self.D, self.G16, G_Z2, self.heads, self.slope,
+                                    n + "1_gatv2-backward-src")
 
 
 SKIPS = (None, "add", "gate")
@@ -431,11 +544,12 @@ class gat_layer(layer_params):
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
                  slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None,
-                 skip_buffer=None):
+                 skip_buffer=None, agg_dtype: str = "f32", images=None):
         n = F.n()
         assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
         # the linear's own fused kernels in every mode: gat(fused=...) only picks how Adam is launched
-        self._setup(name, F, F_T, linear(name, in_, out, backward_out, True), attention(name, n, n, out, heads, slope), n, in_,
+        self._setup(name, F, F_T, linear(name, in_, out, backward_out, True),
+                    attention(name, n, n, out, heads, slope, agg_dtype=agg_dtype, images=images), n, in_,
                     out, activation, G_Z_buffer, skip=skip, norm=norm, skip_buffer=skip_buffer)
 
     def _setup(self, name: str, F: csr_matrix, F_T: csr_matrix, lin, attn, rows: int, in_: int, out: int, activation: bool,
@@ -569,22 +683,32 @@ class gatv2_layer(gat_layer):
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
                  slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, P_buffer=None, skip=None,
-                 norm=None, skip_buffer=None):
+                 norm=None, skip_buffer=None, agg_dtype: str = "f32", images=None):
         n = F.n()
         assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
         self._setup(name, F, F_T, linear(name, in_, 2 * out, backward_out, True),
-                    attention_v2(name, n, out, heads, slope, P_buffer), n, in_, out, activation, G_Z_buffer, z_width=2 * out,
-                    skip=skip, norm=norm, skip_buffer=skip_buffer)
+                    attention_v2(name, n, out, heads, slope, P_buffer, agg_dtype=agg_dtype, images=images), n, in_, out,
+                    activation, G_Z_buffer, z_width=2 * out, skip=skip, norm=norm, skip_buffer=skip_buffer)
+
+    def alpha(self, ctx: context, out: Optional[dn_matrix] = None) -> dn_matrix:
+        """gat_layer.alpha; ValueError naming agg_dtype, before anything else, with bf16 gathers"""
+        refuse_bf16_export(self.attn, f"export of the attention coefficients (gat layer {self.name})")
+        return gat_layer.alpha(self, ctx, out)
 
 
-class attention_dot(param_owner):
+class attention_dot(gathered_images, param_owner):
     """The dot-product attention of one layer: no parameter, only what the backward pass needs of the forward -- lse and D
     [n x heads] --, the head count and the scale c = fp32(1 / sqrt(dh)).  __call__ and backward take the layer's
-    Z3 = [Zq | Zk | Zv] and G_Z3 = [G_Zq | G_Zk | G_Zv] buffers of 3 out columns.  Its table is empty: it is a row of nobody's Adam table."""
+    Z3 = [Zq | Zk | Zv] and G_Z3 = [G_Zq | G_Zk | G_Zv] buffers of 3 out columns.  Its table is empty: it is a row of nobody's Adam table.
+    ``agg_dtype="bf16"``: forward and backward_dst gather Zk and Zv, and backward_src gathers Zq and G, from bf16 images --
+    ``Z16`` is the image of Z3, its thirds made when they are gathered; Zq in the forward and Zk, Zv in backward_src are the
+    rows' own and stay fp32."""
 
     att = G_att = m = v = None          # what gat_layer.att() / Gatt() return for such a layer
+    variant = "dot"
 
-    def __init__(self, name: str, n: int, out: int, heads: int, device=None):
+    def __init__(self, name: str, n: int, out: int, heads: int, device=None, agg_dtype: str = "f32", images=None):
+        self._init_images(agg_dtype, n, 3 * out, n, out, images, device)
         self.name, self.heads = name, int(heads)
         self.scale = ops.gatdot_scale(out // self.heads)
         self.lse, self.D = dn_matrix(n, heads, device=device), dn_matrix(n, heads, device=device)
@@ -592,17 +716,30 @@ class attention_dot(param_owner):
     def __call__(self, ctx: context, F: csr_matrix, Z3: dn_matrix, out: dn_matrix, drop=None) -> None:
         """out = the attention-weighted gather of Zv over F's rows, Zq scored against Zk"""
         assert drop is None, "dot-product attention has no attention dropout"
-        ops.gatdot_forward(ctx, F, Z3, Z3, Z3, out, self.lse, self.heads, self.scale, self.name + "0_gatdot-forward")
+        if self.Z16 is None:
+            ops.gatdot_forward(ctx, F, Z3, Z3, Z3, out, self.lse, self.heads, self.scale, self.name + "0_gatdot-forward")
+            return
+        self._convert(ctx, "0", (Z3, self.Z16, out.m(), 3 * out.m()))          # [Zk | Zv]
+        ops.gatdot_forward_bf16(ctx, F, Z3, self.Z16, self.Z16, out, self.lse, self.heads, self.scale,
+                                self.name + "0_gatdot-forward")
 
     def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z3: dn_matrix, G: dn_matrix, out: dn_matrix,
                  G_Z3: dn_matrix, drop=None) -> None:
         """G_Z3 = the gradient of Z3 (all three thirds), from G = the gradient of ``out``"""
         assert drop is None, "dot-product attention has no attention dropout"
         n = self.name
-        ops.gatdot_backward_dst(ctx, F, Z3, Z3, Z3, self.lse, G, out, self.D, G_Z3, self.heads, self.scale,
-                                n + "1_gatdot-backward-dst")
-        ops.gatdot_backward_src(ctx, F_T, Z3, Z3, Z3, self.lse, self.D, G, G_Z3, G_Z3, self.heads, self.scale,
-                                n + "1_gatdot-backward-src")
+        if self.Z16 is None:
+            ops.gatdot_backward_dst(ctx, F, Z3, Z3, Z3, self.lse, G, out, self.D, G_Z3, self.heads, self.scale,
+                                    n + "1_gatdot-backward-dst")
+            ops.gatdot_backward_src(ctx, F_T, Z3, Z3, Z3, self.lse, self.D, G, G_Z3, G_Z3, self.heads, self.scale,
+                                    n + "1_gatdot-backward-src")
+            return
+        # Zk, Zv for backward_dst, Zq and G for backward_src, in one timed block: nothing between the kernels writes Z3 or G
+        self._convert(ctx, "1", (Z3, self.Z16, 0, Z3.m()), (G, self.G16, 0, G.m()))
+        ops.gatdot_backward_dst_bf16(ctx, F, Z3, self.Z16, self.Z16, self.lse, G, out, self.D, G_Z3, self.heads, self.scale,
+                                     n + "1_gatdot-backward-dst")
+        ops.gatdot_backward_src_bf16(ctx, F_T, self.Z16, Z3, Z3, self.lse, self.D, self.G16, G_Z3, G_Z3, self.heads, self.scale,
+                                     n + "1_gatdot-backward-src")
 
     def alpha(self, ctx, F, Z3, alpha) -> None:
         raise ValueError('gat(variant="dot") has no export of the attention coefficients')
@@ -617,10 +754,12 @@ class gatdot_layer(gat_layer):
     [G_Zq | G_Zk | G_Zv] (aliasing the model-wide buffer); the layer's parameters are the linear's alone."""
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
-                 backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None, skip_buffer=None):
+                 backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None, skip_buffer=None, agg_dtype: str = "f32",
+                 images=None):
         n = F.n()
         assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
-        self._setup(name, F, F_T, linear(name, in_, 3 * out, backward_out, True), attention_dot(name, n, out, heads), n, in_,
+        self._setup(name, F, F_T, linear(name, in_, 3 * out, backward_out, True),
+                    attention_dot(name, n, out, heads, agg_dtype=agg_dtype, images=images), n, in_,
                     out, activation, G_Z_buffer, z_width=3 * out, skip=skip, norm=norm, skip_buffer=skip_buffer)
 
     def alpha(self, ctx: context, out: Optional[dn_matrix] = None) -> dn_matrix:
@@ -743,7 +882,8 @@ class gat(attention_model, model_base):
     """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
 
     gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
-    variant="v1", skip=None, norm=None, skip_weights=None, label_input=0.0, label_weights=None):
+    variant="v1", skip=None, norm=None, skip_weights=None, label_input=0.0, label_weights=None,
+    agg_dtype="f32"):
     ``A`` as ``gcn`` takes it (the layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
     (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att);
     ``variant``: "v1" (this model as it always was) or "v2" (GATv2, see the module docstring: W is [in x 2 out], b
@@ -752,7 +892,9 @@ class gat(attention_model, model_base):
     attention_weights, save, load and rows x 3 out >= 2^31); ``skip``: None, "add" or "gate", ``norm``: None or "layer",
     ``skip_weights``: per layer (W_r, b_r) or (W_r, b_r, w_gate) -- see the module docstring; ValueError for another name or
     a list that does not fit, and for save / load / save_best on a model that has either; ``label_input``: the rate in
-    [0, 1) of masked label inputs and ``label_weights``: their table E -- see the module docstring and set_label_input.  ValueError
+    [0, 1) of masked label inputs and ``label_weights``: their table E -- see the module docstring and set_label_input;
+    ``agg_dtype``: "f32" or "bf16" (bf16 gathers in the sparse attention kernels, see the module docstring; gcn's names and
+    gcn's ValueError for another one).  ValueError
     before any device work for a width that its heads do not divide or a limit of the kernels (ops.GAT_MAX_HEADS,
     ops.GAT_MAX_WIDTH).  ``fused`` picks how Adam is launched -- one launch for every parameter tensor, or one per tensor;
     the element-wise math is the same, so both give the same bits -- and every other kernel is the same in both modes.
@@ -772,7 +914,8 @@ class gat(attention_model, model_base):
     def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
                  loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0,
                  variant: str = "v1", skip=None, norm=None, skip_weights=None, label_input: float = 0.0,
-                 label_weights=None):
+                 label_weights=None, agg_dtype: str = "f32"):
+        self.agg_dtype = _check_agg_dtype(agg_dtype)             # option checks come before any device work
         self.sizes = [int(s) for s in sizes]
         self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
         self._attn_dropout_params = check_dropout(attn_dropout, len(self.sizes) - 1)
@@ -806,6 +949,12 @@ class gat(attention_model, model_base):
             self.skip_buffer = (torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
                                 if self.skip is not None else None)
             more = dict(skip=self.skip, norm=self.norm, skip_buffer=self.skip_buffer)
+        if self.agg_dtype == "bf16":
+            # the images the sparse kernels gather from, once at the widest layer: Z (1, 2 or 3 x out columns) and G
+            zw = {"v1": 1, "v2": 2, "dot": 3}[self.variant]
+            self.Z_image_buffer = torch.empty(A.n() * zw * max(self.sizes[1:]), dtype=torch.bfloat16, device="cuda")
+            self.G_image_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.bfloat16, device="cuda")
+            more.update(agg_dtype="bf16", images=(self.Z_image_buffer, self.G_image_buffer))
         if self.variant == "v2":                                 # G_Z2 = [G_Zs | G_Zd] and P, once at the widest layer
             self.G_Z_buffer = torch.empty(A.n() * 2 * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
             self.P_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
@@ -933,9 +1082,13 @@ class gat(attention_model, model_base):
         if self.label is not None:
             self._fed_count(self.label_epoch)
 
+    Z_image_buffer = G_image_buffer = None      # the bf16 images of gat(agg_dtype="bf16")
+
     def attention_weights(self, ctx, X=None, layers=None, out=None) -> List[dn_matrix]:
-        """attention_model.attention_weights; ValueError for variant="dot" before anything else"""
+        """attention_model.attention_weights; ValueError for variant="dot", and for variant="v2" with agg_dtype="bf16",
+        before anything else"""
         refuse_dot(self, "attention_weights: there is no export kernel for the dot-product coefficients yet")
+        refuse_bf16_export(self, "attention_weights")
         return attention_model.attention_weights(self, ctx, X, layers, out)
 
     def attention_pattern(self):

@@ -553,12 +553,53 @@ def _gat_timed(ctx: context, timer: Optional[str], call) -> None:
     ctx.register_timer(timer, timer + "_0", timer + "_1")
 
 
-def _gat_call(ctx: context, timer: Optional[str], name: str, args, extra) -> None:
-    """mggcn_<name>_f32(*args) under ``timer``; with ``extra`` (the tuple of _gat_drop_args) its _drop twin, which takes it last"""
-    if extra is None:
-        _gat_timed(ctx, timer, lambda: getattr(ctx.lib, f"mggcn_{name}_f32")(*args))
-    else:
-        _gat_timed(ctx, timer, lambda: getattr(ctx.lib, f"mggcn_{name}_drop_f32")(*args, *extra))
+def _gat_call(ctx: context, timer: Optional[str], name: str, args, extra=None, image: bool = False) -> None:
+    """mggcn_<name>_f32(*args) under ``timer``; with ``extra`` (the tuple of _gat_drop_args) its _drop twin, which takes it
+    last; ``image``: the _bf16 twin of either (the gathered operands of ``args`` are bf16 images)"""
+    entry = getattr(ctx.lib, f"mggcn_{name}{'' if extra is None else '_drop'}_{'bf16' if image else 'f32'}")
+    _gat_timed(ctx, timer, lambda: entry(*args, *(extra or ())))
+
+
+class bf16_image:
+    """A bf16 image of an fp32 [rows x columns] matrix, as the ``*_bf16`` attention calls gather from: a 2-D device tensor
+    of 2-byte elements (torch.bfloat16, or int16 / uint16 holding the bit patterns) with unit column stride and any row
+    stride -- a column range of a wider image is one too.  convert_bf16(ctx, src, image.t) makes it.  n(), m(), shape()
+    as on dn_matrix; ld(): the row stride in elements; buffer(): the device pointer (ValueError for a host tensor)."""
+
+    def __init__(self, t):
+        _req(hasattr(t, "dim") and t.dim() == 2 and t.element_size() == 2,
+             "bf16 image: a 2-D tensor of bf16 (2-byte) elements")
+        _req(t.stride(1) == 1 or t.shape[1] <= 1, "bf16 image: columns must be contiguous")
+        self.t = t
+
+    def n(self) -> int: return int(self.t.shape[0])
+    def m(self) -> int: return int(self.t.shape[1])
+    def shape(self): return (self.n(), self.m())
+    def ld(self) -> int: return int(max(self.t.stride(0), self.t.shape[1]))
+
+    def buffer(self) -> int:
+        _req(self.t.is_cuda, "bf16 image: a device tensor")
+        return self.t.data_ptr()
+
+    def columns(self, c0: int, c1: int) -> "bf16_image":
+        """the image of columns [c0, c1)"""
+        return bf16_image(self.t[:, c0:c1])
+
+
+def _ld(M) -> int:
+    """the leading dimension of a dense operand in elements: a dn_matrix is contiguous, an image has its row stride"""
+    return M.ld() if isinstance(M, bf16_image) else M.m()
+
+
+def _req_roles(what: str, image: bool, gathered, own=()) -> None:
+    """the element types of a sparse attention call: with ``image`` every gathered operand is a bf16_image and without it
+    none is; an operand read by the call's own rows never is.  ValueError before the library."""
+    for M in gathered:
+        _req(isinstance(M, bf16_image) == image,
+             f"{what}: a gathered operand must be " + ("a bf16 image (ops.bf16_image), not an fp32 matrix" if image
+                                                       else "an fp32 matrix, not a bf16 image (the _bf16 call takes images)"))
+    for M in own:
+        _req(not isinstance(M, bf16_image), f"{what}: an operand read by the call's own rows stays fp32, not a bf16 image")
 
 
 def _gat_drop_args(drop, what: str, n_dst: int, n_src: int):
@@ -595,15 +636,22 @@ def gat_forward(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_s
     (mggcn_gat_forward_drop_f32): alpha_ijk is multiplied by q_ijk = keep ? scale : 0 in the gather, lse is unchanged, and
     the mask is a pure function of (seed, stream, dst0 + i, src0 + j, k) that is never stored; gat_backward_dst and
     gat_backward_src take the same tuple and draw the same mask.  None calls the plain entry point."""
+    _gat_forward(False, ctx, F, Z, s_dst, s_src, out, lse, heads, slope, timer, drop)
+
+
+def _gat_forward(image: bool, ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
+                 lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
+    """the body of gat_forward and gat_forward_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
+    _req_roles("gat forward", image, (Z,))
     check_gat_heads(heads, Z.m(), "gat forward")
     _req(F.m() == Z.n() and out.shape() == (F.n(), Z.m()), "gat forward: shape mismatch")
     _req(s_dst.shape() == (F.n(), heads) and lse.shape() == (F.n(), heads) and s_src.shape() == (F.m(), heads),
          "gat forward: the scores and lse must be rows x heads")
     extra = None if drop is None else _gat_drop_args(drop, "gat forward", F.n(), F.m())
     ip, ix, _ = F.device(ctx.device)
-    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(), heads,
+    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), _ld(Z), s_dst.buffer(), s_src.buffer(), heads,
             Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer())
-    _gat_call(ctx, timer, "gat_forward", args, extra)
+    _gat_call(ctx, timer, "gat_forward", args, extra, image)
 
 
 def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
@@ -612,15 +660,23 @@ def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix
     """The half of the backward pass that sums over sources, over F's rows (mggcn_gat_backward_dst_f32): D[i, k] =
     G[i, head k] . out[i, head k] and ds_dst[i, k] = sum_j alpha_ijk (G[i, head k] . Z[j, head k] - D[i, k]) lrelu'(x_ijk).
     ``drop``: the forward's tuple (see gat_forward; mggcn_gat_backward_dst_drop_f32) -- the dot product carries q_ijk."""
+    _gat_backward_dst(False, ctx, F, Z, s_dst, s_src, lse, G, out, D, ds_dst, heads, slope, timer, drop)
+
+
+def _gat_backward_dst(image: bool, ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix,
+                      lse: dn_matrix, G: dn_matrix, out: dn_matrix, D: dn_matrix, ds_dst: dn_matrix, heads: int,
+                      slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
+    """the body of gat_backward_dst and gat_backward_dst_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
+    _req_roles("gat backward", image, (Z,), (G, out))
     check_gat_heads(heads, Z.m(), "gat backward")
     _req(F.m() == Z.n() and G.shape() == (F.n(), Z.m()) and out.shape() == G.shape(), "gat backward: shape mismatch")
     _req(all(s.shape() == (F.n(), heads) for s in (s_dst, lse, D, ds_dst)) and s_src.shape() == (F.m(), heads),
          "gat backward: the scores, lse, D and ds must be rows x heads")
     extra = None if drop is None else _gat_drop_args(drop, "gat backward", F.n(), F.m())
     ip, ix, _ = F.device(ctx.device)
-    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
+    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), _ld(Z), s_dst.buffer(), s_src.buffer(),
             lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer())
-    _gat_call(ctx, timer, "gat_backward_dst", args, extra)
+    _gat_call(ctx, timer, "gat_backward_dst", args, extra, image)
 
 
 def _req_gat_backward_src(F_T, Z, dst_scalars, s_src, G, att, ds_dst, ds_src, G_Z, heads: int, which: str) -> None:
@@ -641,13 +697,22 @@ def gat_backward_src(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matr
     ds_src[j, k] att[1, head k].  ds_dst is indexed by source here (the square case passes gat_backward_dst's); None leaves
     its term out.  ``drop``: the forward's tuple (see gat_forward; mggcn_gat_backward_src_drop_f32) -- F_T's rows are the
     sources (offset src0), its entries the destinations (offset dst0)."""
+    _gat_backward_src(False, ctx, F_T, Z, s_dst, s_src, lse, D, G, att, ds_dst, ds_src, G_Z, heads, slope, timer, drop)
+
+
+def _gat_backward_src(image: bool, ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix,
+                      lse: dn_matrix, D: dn_matrix, G: dn_matrix, att: dn_matrix, ds_dst: Optional[dn_matrix],
+                      ds_src: dn_matrix, G_Z: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None,
+                      drop=None) -> None:
+    """the body of gat_backward_src and gat_backward_src_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
+    _req_roles("gat backward", image, (G,), (Z, G_Z))
     _req_gat_backward_src(F_T, Z, (s_dst, lse, D), s_src, G, att, ds_dst, ds_src, G_Z, heads, "the scores, lse, D and ds")
     extra = None if drop is None else _gat_drop_args(drop, "gat backward", F_T.m(), F_T.n())
     ip, ix, _ = F_T.device(ctx.device)
     args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
-            lse.buffer(), D.buffer(), G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
+            lse.buffer(), D.buffer(), G.buffer(), _ld(G), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
             Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m())
-    _gat_call(ctx, timer, "gat_backward_src", args, extra)
+    _gat_call(ctx, timer, "gat_backward_src", args, extra, image)
 
 
 def _req_gat_rec(rec, rows: int, heads: int, what: str) -> None:
@@ -674,6 +739,7 @@ def gat_backward_src_rec(ctx: context, F_T: csr_matrix, Z: dn_matrix, rec, s_src
     """gat_backward_src with the destinations' (s_dst, lse, D) as the records of gat_pack_dst (mggcn_gat_backward_src_rec_f32
     / _rec_drop_f32): one 16-byte load per (entry, head) where the plain call gathers three scalars, and the bits of the
     plain call on the arrays the record was packed from.  ``rec``: F_T.m() x heads x 4 floats."""
+    _req_roles("gat backward", False, (G,), (Z, G_Z))
     _req_gat_backward_src(F_T, Z, (), s_src, G, att, ds_dst, ds_src, G_Z, heads, "the scores and ds")
     _req_gat_rec(rec, F_T.m(), heads, "gat backward")
     extra = None if drop is None else _gat_drop_args(drop, "gat backward", F_T.m(), F_T.n())
@@ -728,7 +794,9 @@ def _split_operand(M: dn_matrix, width: int, part: int, parts: int, what: str):
     G_Zd); dot: 0 the query third (Zq, G_Zq), 1 the key third (Zk, G_Zk), 2 the value third (Zv, G_Zv)"""
     _req(M.m() in (width, parts * width),
          f"{what}: an operand of {M.m()} columns is neither {width} nor {parts} x {width} wide")
-    return (M.buffer(), width) if M.m() == width else (M.buffer() + 4 * width * part, parts * width)
+    if M.m() == width:
+        return M.buffer(), _ld(M)
+    return M.buffer() + (2 if isinstance(M, bf16_image) else 4) * width * part, _ld(M)
 
 
 def _gatv2_width(att: dn_matrix, heads: int, what: str) -> int:
@@ -744,14 +812,21 @@ def gatv2_forward(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att
     sum_j alpha_ijk Zs[j, head k].  F: destinations x sources; att: [1 x width]; out: [F.n() x width]; lse: [F.n() x heads].
     Zs (one row per source) and Zd (one row per destination) are [rows x width] matrices, or the model's [rows x 2 width]
     buffer, of which Zs takes columns [0, width) and Zd columns [width, 2 width) -- the same buffer may be passed as both."""
+    _gatv2_forward(False, ctx, F, Zs, Zd, att, out, lse, heads, slope, timer)
+
+
+def _gatv2_forward(image: bool, ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, out: dn_matrix,
+                   lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """the body of gatv2_forward and gatv2_forward_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
+    _req_roles("gatv2 forward", image, (Zs,), (Zd,))
     width = _gatv2_width(att, heads, "gatv2 forward")
     _req(F.m() == Zs.n() and F.n() == Zd.n() and out.shape() == (F.n(), width), "gatv2 forward: shape mismatch")
     _req(lse.shape() == (F.n(), heads), "gatv2 forward: lse must be rows x heads")
     (zs, ldzs), (zd, ldzd) = (_split_operand(M, width, part, 2, "gatv2 forward") for part, M in enumerate((Zs, Zd)))
     ip, ix, _ = F.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_forward_f32(
+    _gat_call(ctx, timer, "gatv2_forward", (
         ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), heads, width // heads,
-        slope, out.buffer(), out.m(), lse.buffer()))
+        slope, out.buffer(), out.m(), lse.buffer()), None, image)
 
 
 def gatv2_alpha(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, lse: dn_matrix, alpha: dn_matrix,
@@ -780,7 +855,15 @@ def gatv2_backward_dst(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix
     G_Zd[i, c] = att[c] sum_j ds_ijk lrelu'(t_ijk[c]) and P[i, c] = sum_j ds_ijk lrelu(t_ijk[c]), row i's share of G_att.
     Zs, Zd as gatv2_forward takes them; G_Zd: [F.n() x width], or the [F.n() x 2 width] gradient buffer whose columns
     [width, 2 width) are written; P: [F.n() x width]."""
+    _gatv2_backward_dst(False, ctx, F, Zs, Zd, att, lse, G, out, D, G_Zd, P, heads, slope, timer)
+
+
+def _gatv2_backward_dst(image: bool, ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix, lse: dn_matrix,
+                        G: dn_matrix, out: dn_matrix, D: dn_matrix, G_Zd: dn_matrix, P: dn_matrix, heads: int,
+                        slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """the body of gatv2_backward_dst and gatv2_backward_dst_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
     what = "gatv2 backward"
+    _req_roles(what, image, (Zs,), (Zd, G, out, G_Zd, P))
     width = _gatv2_width(att, heads, what)
     _req(F.m() == Zs.n() and F.n() == Zd.n() and G.shape() == (F.n(), width) and out.shape() == G.shape()
          and P.shape() == G.shape() and G_Zd.n() == F.n(), f"{what}: shape mismatch")
@@ -788,9 +871,9 @@ def gatv2_backward_dst(ctx: context, F: csr_matrix, Zs: dn_matrix, Zd: dn_matrix
     (zs, ldzs), (zd, ldzd), (gzd, ldgzd) = (_split_operand(Zs, width, 0, 2, what), _split_operand(Zd, width, 1, 2, what),
                                             _split_operand(G_Zd, width, 1, 2, what))
     ip, ix, _ = F.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_backward_dst_f32(
+    _gat_call(ctx, timer, "gatv2_backward_dst", (
         ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), lse.buffer(), G.buffer(),
-        G.m(), out.buffer(), out.m(), heads, width // heads, slope, D.buffer(), gzd, ldgzd, P.buffer(), P.m()))
+        G.m(), out.buffer(), out.m(), heads, width // heads, slope, D.buffer(), gzd, ldgzd, P.buffer(), P.m()), None, image)
 
 
 def gatv2_att_grad(ctx: context, P: dn_matrix, G_att: dn_matrix, timer: Optional[str] = None) -> None:
@@ -809,7 +892,15 @@ def gatv2_backward_src(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_matr
     whose D it reads): G_Zs[j, c] = sum_i (alpha_ijk G[i, c] + ds_ijk att[c] lrelu'(t_ijk[c])).  F_T: sources x destinations;
     Zs, Zd as gatv2_forward takes them; G_Zs: [F_T.n() x width], or the [F_T.n() x 2 width] gradient buffer whose columns
     [0, width) are written."""
+    _gatv2_backward_src(False, ctx, F_T, Zs, Zd, att, lse, D, G, G_Zs, heads, slope, timer)
+
+
+def _gatv2_backward_src(image: bool, ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_matrix, att: dn_matrix,
+                        lse: dn_matrix, D: dn_matrix, G: dn_matrix, G_Zs: dn_matrix, heads: int, slope: float = GAT_SLOPE,
+                        timer: Optional[str] = None) -> None:
+    """the body of gatv2_backward_src and gatv2_backward_src_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
     what = "gatv2 backward"
+    _req_roles(what, image, (Zd, G), (Zs, G_Zs))
     width = _gatv2_width(att, heads, what)
     _req(F_T.n() == Zs.n() and F_T.m() == Zd.n() and G.shape() == (F_T.m(), width) and G_Zs.n() == F_T.n(),
          f"{what}: shape mismatch")
@@ -817,9 +908,9 @@ def gatv2_backward_src(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd: dn_matr
     (zs, ldzs), (zd, ldzd), (gzs, ldgzs) = (_split_operand(Zs, width, 0, 2, what), _split_operand(Zd, width, 1, 2, what),
                                             _split_operand(G_Zs, width, 0, 2, what))
     ip, ix, _ = F_T.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatv2_backward_src_f32(
+    _gat_call(ctx, timer, "gatv2_backward_src", (
         ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), zs, ldzs, zd, ldzd, att.buffer(), lse.buffer(),
-        D.buffer(), G.buffer(), G.m(), heads, width // heads, slope, gzs, ldgzs))
+        D.buffer(), G.buffer(), _ld(G), heads, width // heads, slope, gzs, ldgzs), None, image)
 
 
 def _req_gatv2_rec(rec, rows: int, heads: int, what: str) -> None:
@@ -876,7 +967,14 @@ def gatdot_forward(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv
     for fp32(1 / sqrt(width / heads)).  Zq (one row per destination), Zk and Zv (one row per source) are [rows x width]
     matrices, or the model's [rows x 3 width] buffer, of which Zq takes columns [0, width), Zk [width, 2 width) and Zv
     [2 width, 3 width) -- the same buffer may be passed as all three."""
+    _gatdot_forward(False, ctx, F, Zq, Zk, Zv, out, lse, heads, scale, timer)
+
+
+def _gatdot_forward(image: bool, ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv: dn_matrix, out: dn_matrix,
+                    lse: dn_matrix, heads: int, scale: Optional[float] = None, timer: Optional[str] = None) -> None:
+    """the body of gatdot_forward and gatdot_forward_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
     what = "gatdot forward"
+    _req_roles(what, image, (Zk, Zv), (Zq, out))
     width = _gatdot_width(out, heads, what)
     _req(F.n() == Zq.n() and F.m() == Zk.n() and F.m() == Zv.n() and out.n() == F.n(), f"{what}: shape mismatch")
     _req(lse.shape() == (F.n(), heads), f"{what}: lse must be rows x heads")
@@ -884,9 +982,9 @@ def gatdot_forward(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv
                                        _split_operand(Zv, width, 2, 3, what))
     scale = gatdot_scale(width // heads) if scale is None else float(scale)
     ip, ix, _ = F.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_forward_f32(
+    _gat_call(ctx, timer, "gatdot_forward", (
         ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zq, ldq, zk, ldk, zv, ldv, heads, width // heads, scale,
-        out.buffer(), out.m(), lse.buffer()))
+        out.buffer(), out.m(), lse.buffer()), None, image)
 
 
 def gatdot_backward_dst(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv: dn_matrix, lse: dn_matrix, G: dn_matrix,
@@ -896,7 +994,15 @@ def gatdot_backward_dst(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matri
     D[i, k] = G[i, head k] . out[i, head k], ds_ijk = alpha_ijk (G[i, head k] . Zv[j, head k] - D[i, k]) and
     G_Zq[i, head k] = scale sum_j ds_ijk Zk[j, head k].  Zq, Zk, Zv, scale as gatdot_forward takes them; G_Zq: [F.n() x
     width], or the [F.n() x 3 width] gradient buffer whose columns [0, width) are written."""
+    _gatdot_backward_dst(False, ctx, F, Zq, Zk, Zv, lse, G, out, D, G_Zq, heads, scale, timer)
+
+
+def _gatdot_backward_dst(image: bool, ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv: dn_matrix, lse: dn_matrix,
+                         G: dn_matrix, out: dn_matrix, D: dn_matrix, G_Zq: dn_matrix, heads: int,
+                         scale: Optional[float] = None, timer: Optional[str] = None) -> None:
+    """the body of gatdot_backward_dst and gatdot_backward_dst_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
     what = "gatdot backward"
+    _req_roles(what, image, (Zk, Zv), (Zq, G, out, G_Zq))
     width = _gatdot_width(out, heads, what)
     _req(F.n() == Zq.n() and F.m() == Zk.n() and F.m() == Zv.n() and out.n() == F.n() and G.shape() == out.shape()
          and G_Zq.n() == F.n(), f"{what}: shape mismatch")
@@ -905,9 +1011,9 @@ def gatdot_backward_dst(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk: dn_matri
                                                      for M, part in ((Zq, 0), (Zk, 1), (Zv, 2), (G_Zq, 0)))
     scale = gatdot_scale(width // heads) if scale is None else float(scale)
     ip, ix, _ = F.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_backward_dst_f32(
+    _gat_call(ctx, timer, "gatdot_backward_dst", (
         ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), zq, ldq, zk, ldk, zv, ldv, lse.buffer(), G.buffer(), G.m(),
-        out.buffer(), out.m(), heads, width // heads, scale, D.buffer(), gzq, ldgzq))
+        out.buffer(), out.m(), heads, width // heads, scale, D.buffer(), gzq, ldgzq), None, image)
 
 
 def gatdot_backward_src(ctx: context, F_T: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv: dn_matrix, lse: dn_matrix,
@@ -918,7 +1024,15 @@ def gatdot_backward_src(ctx: context, F_T: csr_matrix, Zq: dn_matrix, Zk: dn_mat
     F_T: sources x destinations; G: [F_T.m() x width]; Zq, Zk, Zv, scale as gatdot_forward takes them; G_Zk, G_Zv:
     [F_T.n() x width] each, or the [F_T.n() x 3 width] gradient buffer whose columns [width, 2 width) and [2 width, 3 width)
     are written -- the same buffer may be passed as both."""
+    _gatdot_backward_src(False, ctx, F_T, Zq, Zk, Zv, lse, D, G, G_Zk, G_Zv, heads, scale, timer)
+
+
+def _gatdot_backward_src(image: bool, ctx: context, F_T: csr_matrix, Zq: dn_matrix, Zk: dn_matrix, Zv: dn_matrix,
+                         lse: dn_matrix, D: dn_matrix, G: dn_matrix, G_Zk: dn_matrix, G_Zv: dn_matrix, heads: int,
+                         scale: Optional[float] = None, timer: Optional[str] = None) -> None:
+    """the body of gatdot_backward_src and gatdot_backward_src_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
     what = "gatdot backward"
+    _req_roles(what, image, (Zq, G), (Zk, Zv, G_Zk, G_Zv))
     width = _gatdot_width(G, heads, what)
     _req(F_T.m() == Zq.n() and F_T.n() == Zk.n() and F_T.n() == Zv.n() and G.n() == F_T.m() and G_Zk.n() == F_T.n()
          and G_Zv.n() == F_T.n(), f"{what}: shape mismatch")
@@ -929,9 +1043,76 @@ def gatdot_backward_src(ctx: context, F_T: csr_matrix, Zq: dn_matrix, Zk: dn_mat
     (gzk, ldgzk), (gzv, ldgzv) = _split_operand(G_Zk, width, 1, 3, what), _split_operand(G_Zv, width, 2, 3, what)
     scale = gatdot_scale(width // heads) if scale is None else float(scale)
     ip, ix, _ = F_T.device(ctx.device)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gatdot_backward_src_f32(
+    _gat_call(ctx, timer, "gatdot_backward_src", (
         ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), zq, ldq, zk, ldk, zv, ldv, lse.buffer(), D.buffer(),
-        G.buffer(), G.m(), heads, width // heads, scale, gzk, ldgzk, gzv, ldgzv))
+        G.buffer(), _ld(G), heads, width // heads, scale, gzk, ldgzk, gzv, ldgzv), None, image)
+
+
+# bf16 gathers (gat(agg_dtype="bf16")): one wrapper per mggcn_*_bf16 entry, the _drop forms through ``drop=`` as above.  Each
+# takes what the wrapper of the same name without _bf16 takes, with every GATHERED operand -- the one the kernel indexes by
+# an entry's column -- as a bf16_image (of the [rows x width] matrix, or of the model's [rows x parts width] buffer) and every
+# other operand as the fp32 dn_matrix; the shape checks are the fp32 wrapper's, and an fp32 matrix where an image belongs (or
+# the reverse) is a ValueError before the library is touched.  The result is that of the fp32 wrapper on the exactly widened
+# images, bit for bit (include/mggcn.h).
+
+def gat_forward_bf16(ctx: context, F: csr_matrix, Z16: bf16_image, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
+                     lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
+    """gat_forward gathering Z from its image (mggcn_gat_forward_bf16 / _drop_bf16); the scores come from the fp32 Z"""
+    _gat_forward(True, ctx, F, Z16, s_dst, s_src, out, lse, heads, slope, timer, drop)
+
+
+def gat_backward_dst_bf16(ctx: context, F: csr_matrix, Z16: bf16_image, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
+                          G: dn_matrix, out: dn_matrix, D: dn_matrix, ds_dst: dn_matrix, heads: int, slope: float = GAT_SLOPE,
+                          timer: Optional[str] = None, drop=None) -> None:
+    """gat_backward_dst gathering Z from its image (mggcn_gat_backward_dst_bf16 / _drop_bf16); G and out are the rows' own"""
+    _gat_backward_dst(True, ctx, F, Z16, s_dst, s_src, lse, G, out, D, ds_dst, heads, slope, timer, drop)
+
+
+def gat_backward_src_bf16(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
+                          D: dn_matrix, G16: bf16_image, att: dn_matrix, ds_dst: Optional[dn_matrix], ds_src: dn_matrix,
+                          G_Z: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
+    """gat_backward_src gathering G from its image (mggcn_gat_backward_src_bf16 / _drop_bf16); Z is the rows' own"""
+    _gat_backward_src(True, ctx, F_T, Z, s_dst, s_src, lse, D, G16, att, ds_dst, ds_src, G_Z, heads, slope, timer, drop)
+
+
+def gatv2_forward_bf16(ctx: context, F: csr_matrix, Zs16: bf16_image, Zd: dn_matrix, att: dn_matrix, out: dn_matrix,
+                       lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """gatv2_forward gathering Zs from its image (mggcn_gatv2_forward_bf16); Zd is the rows' own"""
+    _gatv2_forward(True, ctx, F, Zs16, Zd, att, out, lse, heads, slope, timer)
+
+
+def gatv2_backward_dst_bf16(ctx: context, F: csr_matrix, Zs16: bf16_image, Zd: dn_matrix, att: dn_matrix, lse: dn_matrix,
+                            G: dn_matrix, out: dn_matrix, D: dn_matrix, G_Zd: dn_matrix, P: dn_matrix, heads: int,
+                            slope: float = GAT_SLOPE, timer: Optional[str] = None) -> None:
+    """gatv2_backward_dst gathering Zs from its image (mggcn_gatv2_backward_dst_bf16); Zd, G and out are the rows' own"""
+    _gatv2_backward_dst(True, ctx, F, Zs16, Zd, att, lse, G, out, D, G_Zd, P, heads, slope, timer)
+
+
+def gatv2_backward_src_bf16(ctx: context, F_T: csr_matrix, Zs: dn_matrix, Zd16: bf16_image, att: dn_matrix, lse: dn_matrix,
+                            D: dn_matrix, G16: bf16_image, G_Zs: dn_matrix, heads: int, slope: float = GAT_SLOPE,
+                            timer: Optional[str] = None) -> None:
+    """gatv2_backward_src gathering Zd and G from their images (mggcn_gatv2_backward_src_bf16); Zs is the rows' own"""
+    _gatv2_backward_src(True, ctx, F_T, Zs, Zd16, att, lse, D, G16, G_Zs, heads, slope, timer)
+
+
+def gatdot_forward_bf16(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk16: bf16_image, Zv16: bf16_image, out: dn_matrix,
+                        lse: dn_matrix, heads: int, scale: Optional[float] = None, timer: Optional[str] = None) -> None:
+    """gatdot_forward gathering Zk and Zv from their images (mggcn_gatdot_forward_bf16); Zq is the rows' own"""
+    _gatdot_forward(True, ctx, F, Zq, Zk16, Zv16, out, lse, heads, scale, timer)
+
+
+def gatdot_backward_dst_bf16(ctx: context, F: csr_matrix, Zq: dn_matrix, Zk16: bf16_image, Zv16: bf16_image, lse: dn_matrix,
+                             G: dn_matrix, out: dn_matrix, D: dn_matrix, G_Zq: dn_matrix, heads: int,
+                             scale: Optional[float] = None, timer: Optional[str] = None) -> None:
+    """gatdot_backward_dst gathering Zk and Zv from their images (mggcn_gatdot_backward_dst_bf16); Zq, G, out are the rows' own"""
+    _gatdot_backward_dst(True, ctx, F, Zq, Zk16, Zv16, lse, G, out, D, G_Zq, heads, scale, timer)
+
+
+def gatdot_backward_src_bf16(ctx: context, F_T: csr_matrix, Zq16: bf16_image, Zk: dn_matrix, Zv: dn_matrix, lse: dn_matrix,
+                             D: dn_matrix, G16: bf16_image, G_Zk: dn_matrix, G_Zv: dn_matrix, heads: int,
+                             scale: Optional[float] = None, timer: Optional[str] = None) -> None:
+    """gatdot_backward_src gathering Zq and G from their images (mggcn_gatdot_backward_src_bf16); Zk, Zv are the rows' own"""
+    _gatdot_backward_src(True, ctx, F_T, Zq16, Zk, Zv, lse, D, G16, G_Zk, G_Zv, heads, scale, timer)
 
 
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
