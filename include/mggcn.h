@@ -59,7 +59,7 @@ void mggcn_device_synchronize(void);
  * (its compute stream). */
 mggcn_stream_t mggcn_stream_create(int high_priority);
 void mggcn_stream_destroy(mggcn_stream_t stream);
-/* Frees the per-(device, stream) reduction scratch that mggcn_abssum_f32 / the fused loss, and the partials that
+/* Frees the per-(device, stream) reduction scratch that mggcn_abssum_f32 / the fused loss / mggcn_cs_residual_f32, and the partials that
  * mggcn_layer_norm_backward_f32, mggcn_gated_skip_backward_f32, mggcn_label_input_backward_f32 and mggcn_gat_scores_backward_f32, allocate on first use (synchronises that stream).  mggcn_stream_destroy calls it; a
  * host layer that brings its own streams (e.g. torch's) calls it when it drops one. */
 void mggcn_stream_release_scratch(mggcn_stream_t stream);
@@ -394,6 +394,36 @@ void mggcn_label_input_backward_f32(mggcn_stream_t stream, const uint32_t *rows,
                                     const uint32_t *cls_ptr, size_t n_train, size_t n_classes, size_t width,
                                     uint32_t threshold, int feed_all, uint64_t seed, uint32_t epoch, uint64_t row0,
                                     const float *G_Z, size_t ldg, size_t n_rows, float *G_E, size_t ldge);
+/* Correct and Smooth (opt-in post-processing of a trained model's logits; Huang et al. 2021, PyG's CorrectAndSmooth): the
+ * row kernels around the two label-propagation loops, whose products are mggcn_spmm_csr_f32's.  Every dense operand is
+ * contiguous [n_rows x m] fp32, 1 <= m <= MGGCN_CS_MAX_WIDTH; Y (labels) and S (sets) are n_rows int32; a training row is
+ * one with S[i] == train_set.  No atomics: the same arguments give the same bits on every call.  n_rows == 0 returns
+ * before any pointer is looked at.  Labels are not checked here: Y[i] outside [0, m) on a training row gives a row
+ * without a one.
+ *   residual   P[i, :] = softmax(logits[i, :]) (max-subtracted, e / sum);  E0[i, c] = (c == Y[i] ? 1 : 0) - P[i, c] on the
+ *              training rows and +0.0 (written, not skipped) elsewhere;  sums_device[0] = the sum of |E0| (overwritten;
+ *              per-workgroup partials in the per-(device, stream) scratch, added in a fixed order).
+ *   step       out = min(max(fmaf(alpha, T, beta * R), lo), hi) element by element, beta * R rounded to fp32 once, with
+ *              max(v, lo) = v < lo ? lo : v and min(v, hi) = v > hi ? hi : v (so -0.0 stays -0.0 at lo = 0, a NaN stays a
+ *              NaN, and lo = -inf, hi = +inf clamp nothing).  With MGGCN_CS_FIX_TRAIN a training row of out is R's,
+ *              unchanged and unclamped; without it S may be NULL.  out may be T; it must not be R.  m % 4 == 0 with T, R
+ *              and out 16-byte aligned takes a float4 path, anything else an element path; both give the same bits.
+ *   correct    out[i, c] = fmaf(s_i, E[i, c], P[i, c]).  With MGGCN_CS_AUTOSCALE s_i = (sums_device[0] * inv_T) / l1_i,
+ *              l1_i = sum_c |E[i, c]| in fp32, and 1 where that quotient is not finite or above 1000 (a row of zeros in
+ *              E is P's row); sums_device is read on the device.  Without it s_i = scale and sums_device may be NULL.
+ *              With MGGCN_CS_SET_LABELS a training row of out is onehot(Y[i]) instead; without it Y and S may be NULL.
+ *              out may be P. */
+#define MGGCN_CS_FIX_TRAIN 1u
+#define MGGCN_CS_AUTOSCALE 2u
+#define MGGCN_CS_SET_LABELS 4u
+#define MGGCN_CS_MAX_WIDTH 1024u
+void mggcn_cs_residual_f32(mggcn_stream_t stream, const float *logits, const int32_t *Y, const int32_t *S, size_t n_rows,
+                           size_t m, int32_t train_set, float *P, float *E0, float *sums_device);
+void mggcn_cs_step_f32(mggcn_stream_t stream, const float *T, const float *R, const int32_t *S, size_t n_rows, size_t m,
+                       float alpha, float beta, float lo, float hi, int32_t train_set, uint32_t flags, float *out);
+void mggcn_cs_correct_f32(mggcn_stream_t stream, const float *P, const float *E, const int32_t *Y, const int32_t *S,
+                          size_t n_rows, size_t m, int32_t train_set, const float *sums_device, float inv_T, float scale,
+                          uint32_t flags, float *out);
 /* Graph attention (GAT; opt-in, the reference has no attention layer).  F is a CSR PATTERN of n_rows destinations x n_cols
  * sources (u32 indptr / indices on the device; there is no values array, and a duplicate (i, j) entry counts as two edges),
  * K = heads, dh = width per head, 1 <= K <= MGGCN_GAT_MAX_HEADS and K * dh <= MGGCN_GAT_MAX_WIDTH; head k owns columns

@@ -24,6 +24,8 @@ Layout:
   checkpoint.py  save / load / predict of gcn, dist_gcn, gat and dist_gat, named from the owners' tables (no reference
                  counterpart)
   selection.py   model_selector: best epoch on a split, early stopping
+  smoothing.py   correct_and_smooth: label-propagation post-processing of any model's logits (csrc/propagate.hip around the
+                 sweep SpMM; no reference counterpart)
 """
 from . import _lib, datasets                                   # noqa: F401
 from ._lib import engine_error                                  # noqa: F401
@@ -41,7 +43,9 @@ from .dist import (dist_context, dist_gcn, dist_gcn_layer, dist_row_csr_matrix, 
 
 from . import checkpoint, selection                             # noqa: F401
 from .selection import model_selector                           # noqa: F401
+from . import smoothing                                         # noqa: F401
+from .smoothing import correct_and_smooth                       # noqa: F401
 
 __all__ = ["context", "csr_matrix", "dn_matrix", "matrix_error", "engine_error", "ops", "matmul",
            "get_matmul_buffer", "sparse_linear", "linear", "gcn_layer", "softmax",
-           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "datasets", "model_selector"]
+           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "datasets", "model_selector", "correct_and_smooth"]

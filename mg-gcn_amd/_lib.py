@@ -103,6 +103,10 @@ PROTOTYPES = {
                                              c_uint64, c_uint32, c_uint64, c_int32, c_int32, vp, c_size_t, c_size_t, vp]),
     "mggcn_label_input_backward_f32": (None, [vp, vp, vp, vp, c_size_t, c_size_t, c_size_t, c_uint32, c_int, c_uint64,
                                               c_uint32, c_uint64, vp, c_size_t, c_size_t, vp, c_size_t]),
+    "mggcn_cs_residual_f32": (None, [vp, vp, vp, vp, c_size_t, c_size_t, c_int32, vp, vp, vp]),
+    "mggcn_cs_step_f32": (None, [vp, vp, vp, vp, c_size_t, c_size_t, c_float, c_float, c_float, c_float, c_int32, c_uint32,
+                                 vp]),
+    "mggcn_cs_correct_f32": (None, [vp, vp, vp, vp, vp, c_size_t, c_size_t, c_int32, vp, c_float, c_float, c_uint32, vp]),
     "mggcn_gat_scores_f32":(None, [vp, vp, c_size_t, vp, vp, vp, c_size_t, c_uint32, c_uint32]),
     "mggcn_gat_forward_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, c_uint32, c_uint32, c_float, vp,
                                      c_size_t, vp]),

@@ -468,6 +468,29 @@ def synth_symmetric_powerlaw_csr(n: int, nnz_target: int, max_deg: int, seed: in
     return indptr.astype(np.uint32), indices, np.ones(nnz_target, dtype=np.float32)
 
 
+def sym_normalize(indptr, indices, data) -> np.ndarray:
+    """The values of D^-1/2 A D^-1/2 for a square CSR matrix A, D = diag(the row sums of the values): entry (i, j) becomes
+    a_ij / sqrt(d_i d_j), and zero where either degree is zero.  Computed in double on the host, returned as float32 in the
+    order of ``data``; adds no self-loops and leaves its arguments alone.  This is the propagation matrix of label
+    propagation and of correct_and_smooth (for a symmetric A its eigenvalues lie in [-1, 1]); csr_matrix.normalize is the
+    reference's row / column form."""
+    ip = np.asarray(indptr).astype(np.int64)
+    ix = np.asarray(indices).astype(np.int64)
+    a = np.asarray(data, dtype=np.float64)
+    n = ip.shape[0] - 1
+    if n < 0 or ix.shape[0] != a.shape[0] or (n >= 0 and ip[-1] - ip[0] != a.shape[0]):
+        raise ValueError("sym_normalize: indptr, indices and data do not describe one CSR matrix")
+    if ix.size and (ix.min() < 0 or ix.max() >= n):
+        raise ValueError(f"sym_normalize: the matrix must be square, a column index is outside [0, {n})")
+    rows = np.repeat(np.arange(n, dtype=np.int64), np.diff(ip))
+    deg = np.bincount(rows, weights=a, minlength=n)[:n] if a.size else np.zeros(n)
+    if (deg < 0).any():
+        raise ValueError("sym_normalize: a row sum is negative")
+    with np.errstate(divide="ignore"):
+        r = np.where(deg > 0, 1.0 / np.sqrt(deg), 0.0)
+    return (a * r[rows] * r[ix]).astype(np.float32)
+
+
 REDDIT_SHAPE = dict(n=232_968, nnz=114_848_860, features=608, classes=41, max_deg=21_657)
 
 

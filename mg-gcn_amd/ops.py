@@ -1206,6 +1206,86 @@ def abssum_by_set(ctx: context, x: dn_matrix, S: dn_matrix, result_device) -> No
     ctx.lib.mggcn_abssum_by_set_f32(ctx.stream(0), x.buffer(), S.buffer(), x.n(), result_device.data_ptr())
 
 
+# ---- Correct and Smooth (smoothing.py): the row kernels around the two propagation loops ---------------------------------
+CS_FIX_TRAIN = 1                    # MGGCN_CS_FIX_TRAIN: a training row of the step's output is R's, unclamped
+CS_AUTOSCALE = 2                    # MGGCN_CS_AUTOSCALE: s_i = sigma / sum |E[i]| (1 where not finite or above 1000)
+CS_SET_LABELS = 4                   # MGGCN_CS_SET_LABELS: a training row of the corrected output is onehot(y)
+CS_MAX_WIDTH = 1024                 # MGGCN_CS_MAX_WIDTH: a row lives in the registers of at most one wave
+
+
+def _req_cs(mats, what: str) -> None:
+    """every (name, dn_matrix) of ``mats`` is fp32 and has the shape of the first, 1 <= m <= CS_MAX_WIDTH"""
+    torch = __import__("torch")
+    (_, first) = mats[0]
+    _req(1 <= first.m() <= CS_MAX_WIDTH, f"{what} supports 1 <= m <= {CS_MAX_WIDTH} columns, got {first.m()}")
+    for name, M in mats:
+        _req(M.n() == first.n() and M.m() == first.m(),
+             f"{what}: {name} must be {first.n()} x {first.m()}, got {M.n()} x {M.m()}")
+        _req(isinstance(M, dn_matrix) and M.t.dtype == torch.float32 and M.t.is_contiguous(),
+             f"{what}: {name} must be a contiguous fp32 dn_matrix")
+
+
+def _req_cs_labels(Y, S, n: int, train_set: int, what: str) -> None:
+    _req(train_set in TRAIN_SETS, f"train_set must be one of {TRAIN_SETS}, got {train_set!r}")
+    _req(isinstance(Y, dn_matrix) and Y.t.dtype == __import__("torch").int32, f"{what}: the labels must be an int32 dn_matrix")
+    _req(Y.n() == n and Y.m() == 1, f"{what}: the labels must be {n} x 1, got {Y.n()} x {Y.m()}")
+    _req_sets(S, n, what)
+
+
+def cs_residual(ctx: context, logits: dn_matrix, Y: dn_matrix, S: dn_matrix, train_set: int, P: dn_matrix, E0: dn_matrix,
+                sums_device) -> None:
+    """P = softmax(logits) row-wise, E0 = onehot(Y) - P on the rows with S == train_set and +0.0 elsewhere,
+    sums_device[0] = sum |E0| (mggcn_cs_residual_f32).  The labels of the training rows must lie in [0, m): the caller's
+    check (correct_and_smooth does it on the host), the kernel does not look."""
+    _req_cs([("logits", logits), ("P", P), ("E0", E0)], "cs_residual")
+    _req_cs_labels(Y, S, logits.n(), train_set, "cs_residual")
+    _req(sums_device.numel() >= 1, "cs_residual: sums must hold one float")
+    ctx.lib.mggcn_cs_residual_f32(ctx.stream(0), logits.buffer(), Y.buffer(), S.buffer(), logits.n(), logits.m(),
+                                  int(train_set), P.buffer(), E0.buffer(), sums_device.data_ptr())
+
+
+def cs_step(ctx: context, T: dn_matrix, R: dn_matrix, S: Optional[dn_matrix], alpha: float, beta: float, lo: float, hi: float,
+            train_set: int = 0, flags: int = 0, out: Optional[dn_matrix] = None) -> None:
+    """out = clamp(fma(alpha, T, beta R), lo, hi), in place on T by default (mggcn_cs_step_f32); with CS_FIX_TRAIN the rows
+    with S == train_set are R's.  out must not be R."""
+    if out is None:
+        out = T
+    _req_cs([("T", T), ("R", R), ("out", out)], "cs_step")
+    _req(flags & ~CS_FIX_TRAIN == 0, f"cs_step: unknown flags {flags:#x}")
+    _req(not lo > hi, f"cs_step: lo {lo} is above hi {hi}")
+    _req(out is not R and out.buffer() != R.buffer(), "cs_step: out must not alias R")
+    if flags & CS_FIX_TRAIN:
+        _req(train_set in TRAIN_SETS, f"train_set must be one of {TRAIN_SETS}, got {train_set!r}")
+        _req(S is not None, "cs_step: CS_FIX_TRAIN needs the sets")
+    if S is not None:
+        _req_sets(S, T.n(), "cs_step")
+    ctx.lib.mggcn_cs_step_f32(ctx.stream(0), T.buffer(), R.buffer(), S.buffer() if S is not None else None, T.n(), T.m(),
+                              alpha, beta, lo, hi, int(train_set), int(flags), out.buffer())
+
+
+def cs_correct(ctx: context, P: dn_matrix, E: dn_matrix, Y: Optional[dn_matrix], S: Optional[dn_matrix], train_set: int,
+               sums_device, inv_T: float, scale: float, flags: int, out: Optional[dn_matrix] = None) -> None:
+    """out = P + s E row by row, in place on P by default (mggcn_cs_correct_f32): s = (sums_device[0] inv_T) / sum |E[i]|
+    with CS_AUTOSCALE (1 where that is not finite or above 1000), else ``scale``; with CS_SET_LABELS the rows with
+    S == train_set are onehot(Y)."""
+    if out is None:
+        out = P
+    _req_cs([("P", P), ("E", E), ("out", out)], "cs_correct")
+    _req(flags & ~(CS_AUTOSCALE | CS_SET_LABELS) == 0, f"cs_correct: unknown flags {flags:#x}")
+    if flags & CS_AUTOSCALE:
+        _req(sums_device is not None and sums_device.numel() >= 1, "cs_correct: CS_AUTOSCALE needs the residual's sum")
+        _req(math.isfinite(inv_T) and inv_T > 0, f"cs_correct: inv_T must be positive and finite, got {inv_T}")
+    else:
+        _req(math.isfinite(scale), f"cs_correct: scale must be finite, got {scale}")
+    if flags & CS_SET_LABELS:
+        _req(Y is not None and S is not None, "cs_correct: CS_SET_LABELS needs the labels and the sets")
+        _req_cs_labels(Y, S, P.n(), train_set, "cs_correct")
+    ctx.lib.mggcn_cs_correct_f32(ctx.stream(0), P.buffer(), E.buffer(), Y.buffer() if Y is not None else None,
+                                 S.buffer() if S is not None else None, P.n(), P.m(), int(train_set),
+                                 sums_device.data_ptr() if sums_device is not None else None, inv_T, scale, int(flags),
+                                 out.buffer())
+
+
 def adam_fused(ctx: context, param: dn_matrix, grad: dn_matrix, m: dn_matrix, v: dn_matrix, lr: float,
                beta1: float, beta2: float, weight_decay: float, c1: float, c2: float, eps: float) -> None:
     _req(param.shape() == grad.shape() == m.shape() == v.shape(), "shape mismatch")
