@@ -713,6 +713,34 @@ void mggcn_gatdot_backward_src_bf16(mggcn_stream_t stream, uint32_t n_rows, uint
                                     const float *Zv, size_t ldv, const float *lse, const float *D, const uint16_t *G,
                                     size_t ldg, uint32_t K, uint32_t dh, float scale, float *G_Zk, size_t ldgzk, float *G_Zv,
                                     size_t ldgzv);
+
+/* The max aggregator of GraphSAGE (no reference counterpart): the element-wise maximum over a vertex's neighbours and its
+ * backward pass.  F is a CSR pattern as the attention entries take it (u32 indptr / indices on the device, no values), the
+ * width is 1 <= d <= MGGCN_GAT_MAX_WIDTH, every dense operand has its own leading dimension >= d, and the kernels are the
+ * one-wave-per-row layout of the attention kernels with their five (VEC, NT, U) variants: the four-column path when
+ * d % 4 == 0 and every dense operand -- arg counts as one, of 4-byte elements -- has a 16-byte aligned base and a leading
+ * dimension that is a multiple of 4, the element path otherwise.  n_rows == 0 returns.  No atomics.
+ *   forward    out[i, c] = max over the entries j of row i of B[j, c], arg[i, c] = src0 + j of the winner (src0: the global
+ *              index of column 0).  The order is total: the larger value wins, equal values (==, so -0.0 ties with +0.0) go
+ *              to the smaller j; a NaN is never selected.  out carries the winner's bits exactly.  A row in which nothing is
+ *              selected (no entry, or NaNs only) gives out = +0.0 and arg = MGGCN_AGG_NONE; a row of -inf entries selects its
+ *              smallest j.  arg may be NULL (the value only).  The result does not depend on the lane geometry, the
+ *              path, the order of a row's entries or duplicate entries.  out must not alias B; src0 + n_cols < 2^32 - 1.
+ *   backward   over the rows j of F^T (n_rows sources, n_cols destinations; an entry is a destination i):
+ *              G_B[j, c] = (flags & MGGCN_AGG_ACCUMULATE ? G_B[j, c] : 0) + sum_i [arg[i, c] == src0 + j] G[i, c].  An entry
+ *              whose index equals its predecessor's in the same row is skipped, so a pair (i, j) that occurs more than once
+ *              delivers its gradient once: equal indices of a row of F^T MUST be adjacent (rows in ascending order are, and
+ *              mggcn_csr_transpose_host emits those).  The terms are added in a fixed order (a group's entries in row order,
+ *              then the groups): every output has the same bits on every call and for every split of the rows between
+ *              calls.  G_B must not alias G; an unknown flag fails the precondition check. */
+#define MGGCN_AGG_ACCUMULATE 1u
+#define MGGCN_AGG_NONE 0xFFFFFFFFu
+void mggcn_agg_max_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                               const uint32_t *indices, const float *B, size_t ldb, uint32_t d, uint32_t src0, float *out,
+                               size_t ldo, uint32_t *arg, size_t lda);
+void mggcn_agg_max_backward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                const uint32_t *t_indices, const uint32_t *arg, size_t lda, const float *G, size_t ldg,
+                                uint32_t d, uint32_t src0, uint32_t flags, float *G_B, size_t ldgb);
 /* cublasSasum  (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

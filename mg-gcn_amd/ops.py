@@ -1115,6 +1115,58 @@ def gatdot_backward_src_bf16(ctx: context, F_T: csr_matrix, Zq16: bf16_image, Zk
     _gatdot_backward_src(True, ctx, F_T, Zq16, Zk, Zv, lse, D, G16, G_Zk, G_Zv, heads, scale, timer)
 
 
+AGG_ACCUMULATE = 1                  # MGGCN_AGG_ACCUMULATE
+AGG_NONE = 0xFFFFFFFF               # MGGCN_AGG_NONE: the arg of an element for which nothing was selected
+
+
+def _req_agg_max(what: str, d: int, arg, shape, src0: int, n_src: int) -> None:
+    """what both passes of the max aggregator share: the width, the arg matrix (4-byte integers of ``shape``) and src0"""
+    _req(1 <= d <= GAT_MAX_WIDTH, f"{what} supports 1 <= width <= {GAT_MAX_WIDTH}, got {d}")
+    if arg is not None:
+        _req(isinstance(arg, dn_matrix) and str(arg.t.dtype) in ("torch.int32", "torch.uint32") and arg.shape() == shape,
+             f"{what}: arg must be a uint32 / int32 matrix of {shape[0]} x {shape[1]}")
+    _req(isinstance(src0, numbers.Integral) and 0 <= src0 and src0 + n_src <= AGG_NONE,
+         f"{what}: src0 + sources must stay below 2^32 - 1 (the library would exit, not raise)")
+
+
+def agg_max_forward(ctx: context, F: csr_matrix, B: dn_matrix, out: dn_matrix, arg: Optional[dn_matrix] = None, src0: int = 0,
+                    timer: Optional[str] = None) -> None:
+    """The max aggregator (mggcn_agg_max_forward_f32): over F's pattern (values ignored) out[i, c] = max over the entries j
+    of row i of B[j, c] and arg[i, c] = src0 + j of the winner.  The larger value wins, equal values go to the smaller j, a NaN
+    is never selected; a row in which nothing is selected gives +0.0 and AGG_NONE.  F: destinations x sources; B: one row per
+    source; out, arg (uint32 / int32, or None: the value only): one row per destination.  ValueError for a shape that does
+    not fit, a width outside [1, GAT_MAX_WIDTH], a wrong arg or out aliasing B, before the library is touched (it would print
+    and exit, not raise)."""
+    what = "agg max forward"
+    _req(F.m() == B.n() and out.shape() == (F.n(), B.m()), f"{what}: shape mismatch")
+    _req_agg_max(what, B.m(), arg, out.shape(), src0, F.m())
+    _req(out.buffer() != B.buffer(), f"{what}: out must not alias B")
+    _req(arg is None or arg.buffer() not in (out.buffer(), B.buffer()), f"{what}: arg must not alias out or B")
+    ip, ix, _ = F.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_agg_max_forward_f32(
+        ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), B.buffer(), B.m(), B.m(), int(src0), out.buffer(), out.m(),
+        None if arg is None else arg.buffer(), 0 if arg is None else arg.m()))
+
+
+def agg_max_backward(ctx: context, F_T: csr_matrix, arg: dn_matrix, G: dn_matrix, G_B: dn_matrix, accumulate: bool = False,
+                     src0: int = 0, timer: Optional[str] = None) -> None:
+    """The backward pass of agg_max_forward over the rows of F^T (mggcn_agg_max_backward_f32): G_B[j, c] = (accumulate ?
+    G_B[j, c] : 0) + the sum of G[i, c] over the entries i of row j with arg[i, c] == src0 + j.  An entry equal to its
+    predecessor in the row is skipped (a duplicated pair delivers once), so equal indices of a row must be adjacent:
+    csr_matrix.transpose() returns rows in ascending order.  F_T: sources x destinations; arg, G: one row per destination;
+    G_B: one row per source.  No atomics, the same bits on every call.  The same checks before the library as the forward."""
+    what = "agg max backward"
+    _req(F_T.m() == G.n() and G_B.shape() == (F_T.n(), G.m()), f"{what}: shape mismatch")
+    _req(arg is not None, f"{what}: arg must be the forward's, not None")
+    _req_agg_max(what, G.m(), arg, G.shape(), src0, F_T.n())
+    _req(G_B.buffer() != G.buffer(), f"{what}: G_B must not alias G")
+    _req(arg.buffer() not in (G.buffer(), G_B.buffer()), f"{what}: arg must not alias G or G_B")
+    ip, ix, _ = F_T.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_agg_max_backward_f32(
+        ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), arg.buffer(), arg.m(), G.buffer(), G.m(), G.m(), int(src0),
+        AGG_ACCUMULATE if accumulate else 0, G_B.buffer(), G_B.m()))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
