@@ -732,7 +732,19 @@ void mggcn_gatdot_backward_src_bf16(mggcn_stream_t stream, uint32_t n_rows, uint
  *              delivers its gradient once: equal indices of a row of F^T MUST be adjacent (rows in ascending order are, and
  *              mggcn_csr_transpose_host emits those).  The terms are added in a fixed order (a group's entries in row order,
  *              then the groups): every output has the same bits on every call and for every split of the rows between
- *              calls.  G_B must not alias G; an unknown flag fails the precondition check. */
+ *              calls.  G_B must not alias G; an unknown flag fails the precondition check.
+ *   pack       rec[i, 2c] = arg[i, c] and rec[i, 2c + 1] = the bits of G[i, c] for i < n_rows, c < d, both unchanged (a NaN
+ *              keeps its payload): rows of 8-byte records, ldr >= 2 d in 32-bit words.  rec must be 8-byte aligned and ldr
+ *              even (precondition check); the four-column path -- two 16-byte loads and two 16-byte stores per lane -- when
+ *              d % 4 == 0 and arg, G and rec all have 16-byte rows, the element path (one 8-byte store per column) otherwise.
+ *              Words of a row beyond 2 d are not written.  rec must not alias an input.
+ *   backward_rec   the backward with arg and G of a destination read from its row of `rec` (as pack writes it: the one
+ *              matrix a row-partitioned model exchanges).  The row walk, the skip rule, the select, the order of the sums
+ *              and the flags are the backward's; a lane's four columns are 32 contiguous bytes (two adjacent 16-byte
+ *              loads), the element path reads one 8-byte record per column.  The four-column path when d % 4 == 0 and rec
+ *              and G_B have 16-byte rows: for operands aligned as the plain call's the same (VEC, NT, U) runs and G_B has
+ *              the plain call's bits, on every call and for every split of the rows between calls.  rec 8-byte aligned,
+ *              ldr even and >= 2 d, src0 + n_rows < 2^32 - 1, G_B must not alias rec. */
 #define MGGCN_AGG_ACCUMULATE 1u
 #define MGGCN_AGG_NONE 0xFFFFFFFFu
 void mggcn_agg_max_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
@@ -741,6 +753,11 @@ void mggcn_agg_max_forward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t 
 void mggcn_agg_max_backward_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
                                 const uint32_t *t_indices, const uint32_t *arg, size_t lda, const float *G, size_t ldg,
                                 uint32_t d, uint32_t src0, uint32_t flags, float *G_B, size_t ldgb);
+void mggcn_agg_max_pack_f32(mggcn_stream_t stream, const uint32_t *arg, size_t lda, const float *G, size_t ldg, size_t n_rows,
+                            uint32_t d, uint32_t *rec, size_t ldr);
+void mggcn_agg_max_backward_rec_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                    const uint32_t *t_indices, const uint32_t *rec, size_t ldr, uint32_t d, uint32_t src0,
+                                    uint32_t flags, float *G_B, size_t ldgb);
 /* cublasSasum  (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

@@ -22,6 +22,8 @@ Layout:
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*); dist_model_base:
                the epoch dist_gcn and dist_gat share
   dist_gat.py  dist_attention / dist_gat_layer / dist_gat (and the _v2 / gatv2 twins): gat on the row partition (exported by dist)
+  dist_sage.py dist_max_aggregate / dist_sage_layer / dist_sage: sage on the row partition, the max backward on a packed
+               (arg, gradient) record (exported by dist)
   datasets.py  on-disk format + synthetic generators    (reference test/data/prep.py); the checkpoint file
   checkpoint.py  save / load / predict of gcn, dist_gcn, gat and dist_gat, named from the owners' tables (no reference
                  counterpart)

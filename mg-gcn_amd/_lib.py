@@ -151,6 +151,9 @@ PROTOTYPES = {
                                          c_size_t]),
     "mggcn_agg_max_backward_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, c_uint32, c_uint32,
                                           c_uint32, vp, c_size_t]),
+    "mggcn_agg_max_pack_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_size_t, c_uint32, vp, c_size_t]),
+    "mggcn_agg_max_backward_rec_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, c_uint32, c_uint32, c_uint32, vp,
+                                              c_size_t]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),
     "mggcn_gather_rows_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_softmax_xent_fused_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_float, vp]),

@@ -14,6 +14,13 @@
 //             select; a group adds its entries in row order, the groups are folded by fold_groups.  An entry whose index
 //             equals its predecessor's in the row is skipped, so a pair (i, j) that the pattern holds twice delivers once:
 //             equal indices of a row must be adjacent, which holds for a row in ascending order.
+//   record    (REC = true, mggcn_agg_max_backward_rec_f32): the two gathered rows come from ONE matrix of 8-byte records that
+//             agg_max_pack_kernel interleaves -- words 2c and 2c + 1 of row i are the bits of arg[i, c] and of G[i, c].  A
+//             lane's four columns are 32 contiguous bytes (two adjacent 16-byte loads) where the plain kernel reads 16 bytes
+//             of each of two rows; the element path reads one 8-byte record per column.  Only the loads differ: the walk,
+//             the skip rule, the select and the order of the sums, and so every bit of G_B, are the plain kernel's.
+//             REC = false compiles to the kernel as it was.  What the row partition exchanges in one collective
+//             (DESIGN.md 3.13.1).
 #include <algorithm>
 #include <cmath>
 
@@ -37,6 +44,24 @@ template <int VEC>
 __device__ __forceinline__ void storev_u32(uint32_t *p, const uint32_t (&r)[VEC]) {
     if constexpr (VEC == 4) *reinterpret_cast<uint4 *>(p) = make_uint4(r[0], r[1], r[2], r[3]);
     else *p = r[0];
+}
+
+// (arg, G) of VEC columns from `col` on of one destination: two rows (ar, gr), or -- REC -- the row `ar` of interleaved records
+template <int VEC, bool REC>
+__device__ __forceinline__ void load_sel_grad(uint32_t (&a)[VEC], float (&g)[VEC], const uint32_t *__restrict__ ar,
+                                              const float *__restrict__ gr, uint32_t col) {
+    if constexpr (!REC) {
+        loadv_u32<VEC>(a, ar + col);
+        loadv<VEC>(g, gr + col);
+    } else if constexpr (VEC == 4) {
+        const uint4 lo = *reinterpret_cast<const uint4 *>(ar + 2 * (size_t)col);
+        const uint4 hi = *reinterpret_cast<const uint4 *>(ar + 2 * (size_t)col + 4);
+        a[0] = lo.x; g[0] = __uint_as_float(lo.y); a[1] = lo.z; g[1] = __uint_as_float(lo.w);
+        a[2] = hi.x; g[2] = __uint_as_float(hi.y); a[3] = hi.z; g[3] = __uint_as_float(hi.w);
+    } else {
+        const uint2 t = *reinterpret_cast<const uint2 *>(ar + 2 * (size_t)col);
+        a[0] = t.x; g[0] = __uint_as_float(t.y);
+    }
 }
 
 // the total order of the forward: does (x, j) beat (b, bj)?  A NaN x fails both comparisons; (-inf, NONE), the start, loses
@@ -118,7 +143,8 @@ __global__ __launch_bounds__(256) void agg_max_forward_kernel(uint32_t n_rows, c
 // ---------------------------------------------------------------------------
 // backward over the rows of F^T
 // ---------------------------------------------------------------------------
-template <int VEC, int NT, int U, bool ACC>
+// REC: G is not read; `arg` is the record matrix and `lda` its leading dimension in 32-bit words
+template <int VEC, int NT, int U, bool ACC, bool REC>
 __global__ __launch_bounds__(256) void agg_max_backward_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
                                                                const uint32_t *__restrict__ indices,
                                                                const uint32_t *__restrict__ arg, size_t lda,
@@ -151,13 +177,12 @@ __global__ __launch_bounds__(256) void agg_max_backward_kernel(uint32_t n_rows, 
                 const uint32_t live = en.of(my_live);       // by every lane: a ds_bpermute reads active lanes only
                 const bool on = en.ok && live != 0;
                 const uint32_t *__restrict__ ar = arg + (size_t)en.c * lda;
-                const float *__restrict__ gr = G + (size_t)en.c * ldg;
+                const float *__restrict__ gr = REC ? nullptr : G + (size_t)en.c * ldg;
 #pragma unroll
                 for (int t = 0; t < NT; t++) {              // the entry's rows of arg and G under one predicate
                     const uint32_t col = (t * lpr + sub) * VEC;
                     if (on && col < d) {
-                        loadv_u32<VEC>(a[u][t], ar + col);
-                        loadv<VEC>(g[u][t], gr + col);
+                        load_sel_grad<VEC, REC>(a[u][t], g[u][t], ar, gr, col);
                     } else {
                         zerov<VEC>(g[u][t]);
 #pragma unroll
@@ -191,7 +216,46 @@ __global__ __launch_bounds__(256) void agg_max_backward_kernel(uint32_t n_rows, 
     }
 }
 
+// ---------------------------------------------------------------------------
+// the record: rec[i, 2c] = arg[i, c], rec[i, 2c + 1] = the bits of G[i, c].  One thread per (row, VEC columns), grid-stride
+// ---------------------------------------------------------------------------
+template <int VEC>
+__global__ __launch_bounds__(256) void agg_max_pack_kernel(const uint32_t *__restrict__ arg, size_t lda,
+                                                           const float *__restrict__ G, size_t ldg, size_t n_rows, uint32_t d,
+                                                           uint32_t *__restrict__ rec, size_t ldr) {
+    const uint32_t units = d / VEC;
+    const size_t total = n_rows * units;
+    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
+        const size_t row = idx / units;
+        const uint32_t col = (uint32_t)(idx - row * units) * VEC;
+        uint32_t a[VEC], g[VEC];
+        loadv_u32<VEC>(a, arg + row * lda + col);
+        loadv_u32<VEC>(g, reinterpret_cast<const uint32_t *>(G) + row * ldg + col);
+        uint32_t *p = rec + row * ldr + 2 * (size_t)col;
+        if constexpr (VEC == 4) {
+            *reinterpret_cast<uint4 *>(p) = make_uint4(a[0], g[0], a[1], g[1]);
+            *reinterpret_cast<uint4 *>(p + 4) = make_uint4(a[2], g[2], a[3], g[3]);
+        } else {
+            *reinterpret_cast<uint2 *>(p) = make_uint2(a[0], g[0]);
+        }
+    }
+}
+
 bool rows16_u32(const uint32_t *p, size_t ld) { return aligned16(p) && ld % 4 == 0; }
+
+// the launch both backward entry points share: `vec` is the caller's float4 condition on its own operands
+template <bool REC>
+void agg_max_backward_launch(mggcn_stream_t stream, bool vec, uint32_t n_rows, const uint32_t *t_indptr,
+                             const uint32_t *t_indices, const uint32_t *arg, size_t lda, const float *G, size_t ldg, uint32_t d,
+                             uint32_t src0, uint32_t flags, float *G_B, size_t ldgb) {
+    const head_geometry hg = head_geometry_for(d, vec);
+    gat_dispatch(vec, hg.nt, [&](auto v) {
+        with_flag((flags & MGGCN_AGG_ACCUMULATE) != 0, [&](auto acc) {
+            launch_rows(agg_max_backward_kernel<v.VEC, v.NT, v.U, acc, REC>, n_rows, stream, n_rows, t_indptr, t_indices, arg,
+                        lda, G, ldg, d, src0, hg.lg, G_B, ldgb);
+        });
+    });
+}
 
 }  // namespace
 
@@ -226,11 +290,41 @@ MGGCN_API void mggcn_agg_max_backward_f32(mggcn_stream_t stream, uint32_t n_rows
     MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && arg != nullptr && G != nullptr), "agg max backward: null operand");
     MGGCN_REQUIRE((const void *)G_B != (const void *)G, "agg max backward: G_B must not alias G");
     const bool vec = d % 4 == 0 && rows16_u32(arg, lda) && rows16(G, ldg) && rows16(G_B, ldgb);
-    const head_geometry hg = head_geometry_for(d, vec);
-    gat_dispatch(vec, hg.nt, [&](auto v) {
-        with_flag((flags & MGGCN_AGG_ACCUMULATE) != 0, [&](auto acc) {
-            launch_rows(agg_max_backward_kernel<v.VEC, v.NT, v.U, acc>, n_rows, stream, n_rows, t_indptr, t_indices, arg, lda, G,
-                        ldg, d, src0, hg.lg, G_B, ldgb);
-        });
-    });
+    agg_max_backward_launch<false>(stream, vec, n_rows, t_indptr, t_indices, arg, lda, G, ldg, d, src0, flags, G_B, ldgb);
+}
+
+MGGCN_API void mggcn_agg_max_pack_f32(mggcn_stream_t stream, const uint32_t *arg, size_t lda, const float *G, size_t ldg,
+                                      size_t n_rows, uint32_t d, uint32_t *rec, size_t ldr) {
+    require_heads(1, d);
+    MGGCN_REQUIRE(lda >= d && ldg >= d && ldr >= 2 * (size_t)d, "agg max pack: leading dimension < width");
+    MGGCN_REQUIRE((reinterpret_cast<uintptr_t>(rec) & 7u) == 0 && ldr % 2 == 0,
+                  "agg max pack: rec must be 8-byte aligned with an even leading dimension");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(arg != nullptr && G != nullptr && rec != nullptr, "agg max pack: null operand");
+    MGGCN_REQUIRE((const void *)rec != (const void *)arg && (const void *)rec != (const void *)G,
+                  "agg max pack: rec must not alias an input");
+    const bool vec = d % 4 == 0 && rows16_u32(arg, lda) && rows16(G, ldg) && rows16_u32(rec, ldr);
+    const size_t total = n_rows * (vec ? d / 4 : d);
+    const unsigned grid = (unsigned)std::min<size_t>((total + 255) / 256, 1u << 20);
+    const auto kernel = vec ? agg_max_pack_kernel<4> : agg_max_pack_kernel<1>;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), 0, as_stream(stream), arg, lda, G, ldg, n_rows, d, rec, ldr);
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_agg_max_backward_rec_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                              const uint32_t *t_indices, const uint32_t *rec, size_t ldr, uint32_t d,
+                                              uint32_t src0, uint32_t flags, float *G_B, size_t ldgb) {
+    require_heads(1, d);
+    MGGCN_REQUIRE((flags & ~MGGCN_AGG_ACCUMULATE) == 0, "agg max backward rec: unknown flags");
+    MGGCN_REQUIRE(ldr >= 2 * (size_t)d && ldgb >= d, "agg max backward rec: leading dimension < width");
+    MGGCN_REQUIRE((reinterpret_cast<uintptr_t>(rec) & 7u) == 0 && ldr % 2 == 0,
+                  "agg max backward rec: rec must be 8-byte aligned with an even leading dimension");
+    MGGCN_REQUIRE((uint64_t)src0 + n_rows <= 0xFFFFFFFFull, "agg max backward rec: src0 + sources must stay below 2^32 - 1 (MGGCN_AGG_NONE)");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(t_indptr != nullptr && G_B != nullptr, "agg max backward rec: null operand");
+    MGGCN_REQUIRE(n_cols == 0 || (t_indices != nullptr && rec != nullptr), "agg max backward rec: null operand");
+    MGGCN_REQUIRE((const void *)G_B != (const void *)rec, "agg max backward rec: G_B must not alias rec");
+    // the plain call's condition on equally aligned operands: a 16-byte record row is a 16-byte arg row and a 16-byte G row
+    const bool vec = d % 4 == 0 && rows16_u32(rec, ldr) && rows16(G_B, ldgb);
+    agg_max_backward_launch<true>(stream, vec, n_rows, t_indptr, t_indices, rec, ldr, nullptr, 0, d, src0, flags, G_B, ldgb);
 }

@@ -1179,3 +1179,4 @@ class dist_gcn(dist_model_base):
 
 from .dist_gat import (dist_attention, dist_attention_v2, dist_gat, dist_gat_layer,       # noqa: E402,F401
                        dist_gatv2_layer)                                                # noqa: E402,F401  (it imports the classes above)
+from .dist_sage import dist_max_aggregate, dist_sage, dist_sage_layer                  # noqa: E402,F401  (likewise)

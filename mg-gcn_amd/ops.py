@@ -1167,6 +1167,44 @@ def agg_max_backward(ctx: context, F_T: csr_matrix, arg: dn_matrix, G: dn_matrix
         AGG_ACCUMULATE if accumulate else 0, G_B.buffer(), G_B.m()))
 
 
+def _req_agg_max_rec(rec, rows: int, d: int, what: str) -> None:
+    """``rec``: a device tensor of rows x d records of two 4-byte words, contiguous and 8-byte aligned (the library would
+    exit)"""
+    _req(rec.is_contiguous() and rec.numel() == rows * d * 2 and rec.element_size() == 4,
+         f"{what}: rec must hold {rows} x {d} records of two 4-byte words")
+    _req(rec.data_ptr() % 8 == 0, f"{what}: rec must be 8-byte aligned")
+
+
+def agg_max_pack(ctx: context, arg: dn_matrix, G: dn_matrix, rec, timer: Optional[str] = None) -> None:
+    """rec[i, 2c] = arg[i, c], rec[i, 2c + 1] = the bits of G[i, c] (mggcn_agg_max_pack_f32): what agg_max_backward gathers
+    of a destination -- its selection and its gradient -- as one row of 8-byte records.  ``rec``: a device tensor of
+    rows x width x 2 4-byte words (float32 or int32), contiguous, 8-byte aligned, not one of the inputs.  ValueError before
+    the library is touched."""
+    what = "agg max pack"
+    _req(arg is not None, f"{what}: arg must be the forward's, not None")
+    _req_agg_max(what, G.m(), arg, G.shape(), 0, 0)
+    _req_agg_max_rec(rec, G.n(), G.m(), what)
+    _req(rec.data_ptr() not in (arg.buffer(), G.buffer()) and arg.buffer() != G.buffer(), f"{what}: rec must not alias an input")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_agg_max_pack_f32(
+        ctx.stream(0), arg.buffer(), arg.m(), G.buffer(), G.m(), G.n(), G.m(), rec.data_ptr(), 2 * G.m()))
+
+
+def agg_max_backward_rec(ctx: context, F_T: csr_matrix, rec, d: int, G_B: dn_matrix, accumulate: bool = False, src0: int = 0,
+                         timer: Optional[str] = None) -> None:
+    """agg_max_backward with the destinations' (arg, G) as the records of agg_max_pack (mggcn_agg_max_backward_rec_f32): one
+    gather stream where the plain call has two, and the plain call's bits on the matrices the record was packed from.
+    ``rec``: F_T.m() x d records; G_B: one row per source, d wide; the rest as agg_max_backward takes it."""
+    what = "agg max backward"
+    _req(isinstance(d, numbers.Integral) and G_B.shape() == (F_T.n(), d), f"{what}: shape mismatch")
+    _req_agg_max(what, d, None, None, src0, F_T.n())
+    _req_agg_max_rec(rec, F_T.m(), d, what)
+    _req(rec.data_ptr() != G_B.buffer(), f"{what}: G_B must not alias rec")
+    ip, ix, _ = F_T.device(ctx.device)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_agg_max_backward_rec_f32(
+        ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), rec.data_ptr(), 2 * d, int(d), int(src0),
+        AGG_ACCUMULATE if accumulate else 0, G_B.buffer(), G_B.m()))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""

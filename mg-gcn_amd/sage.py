@@ -24,9 +24,11 @@ predict, model_selector's in-memory restore and smoothing.correct_and_smooth.pre
 
 Refused with ValueError naming the argument, before any device work: an unknown ``aggr``, a matrix that is not square, and
 gcn's own errors for ``norm``, ``loss`` and ``dropout``; save / load / model_selector.save_best (no version of the checkpoint
-file stores a sage: nothing is read, written or created).  Not built: the row partition, sum / min / the pooling MLP, the
-GEMM-first order for mean when out < in, bf16 gathers, checkpoints, the C++ layer and CLI, and a planned (non-row-walk) form
-for rows of many thousand entries.
+file stores a sage: nothing is read, written or created).  The row partition is dist_sage.dist_sage (a sage_layer per rank
+over dist_row_linear, with dist_max_aggregate or dist_sparse_linear).  Not built: sum / min / the pooling MLP, the GEMM-first
+order for mean when out < in, bf16 gathers (on one GPU, on the wire and in the packed max-backward record), the halo and
+rounds schedules for max, hiding the forward gather under the root GEMM, one all-reduce for both linears of a layer,
+checkpoints for any sage, the C++ layer and CLI, and a planned (non-row-walk) form for rows of many thousand entries.
 """
 from __future__ import annotations
 
@@ -96,14 +98,19 @@ class sage_layer(layer_params):
     across forwards (``reset_input_cache``) and which has no input gradient.  ``G_M`` aliases the model-wide buffer."""
 
     def __init__(self, name: str, agg, rows: int, in_: int, out: int, activation: bool, first: bool, G_M_buffer=None,
-                 norm=None):
+                 norm=None, lin=None, res_lin=None, norm_layer=None):
+        """``lin`` / ``res_lin`` / ``norm_layer``: the layer's two linears and its norm where the caller builds them (the row
+        partition: dist_sage.dist_sage_layer); None builds the single-GPU ones"""
         check_norm(norm)
         self.name, self.agg, self.first, self.activation = name, agg, bool(first), bool(activation)
         # the linears' own fused kernels in every mode, as in the attention models: sage(fused=...) only picks how Adam is
         # launched
-        self.lin = linear(name, in_, out, not first, True)
-        self.res_lin = linear(name + "root_", in_, out, not first, True)
-        self.norm = layer_norm(name, rows, out, True, adam_fused=True) if norm == "layer" and activation else None
+        self.lin = linear(name, in_, out, not first, True) if lin is None else lin
+        self.res_lin = linear(name + "root_", in_, out, not first, True) if res_lin is None else res_lin
+        if norm_layer is not None:
+            self.norm = norm_layer
+        else:
+            self.norm = layer_norm(name, rows, out, True, adam_fused=True) if norm == "layer" and activation else None
         self.Y = dn_matrix(rows, out)
         self.M: Optional[dn_matrix] = None if first else dn_matrix(rows, in_)
         self._M_key = None
@@ -171,6 +178,9 @@ class sage_layer(layer_params):
             T = self.Y
         self.lin.setX(self.M)
         self.lin.backward(ctx, T, self.G_M)
+        if not self.first and hasattr(self.agg, "start_backward"):
+            # an aggregator that exchanges G_M (dist_sage.dist_max_aggregate): the collective runs under the GEMMs below
+            self.agg.start_backward(ctx, self.G_M)
         self.res_lin.setX(self.H)
         self.res_lin.backward(ctx, T, self.G_out)
         if self.first:
