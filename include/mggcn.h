@@ -524,6 +524,65 @@ void mggcn_gat_backward_src_rec_drop_f32(mggcn_stream_t stream, uint32_t n_rows,
                                          const float *ds_dst, uint32_t K, uint32_t dh, float slope, float *ds_src,
                                          float *G_Z, size_t ldgz, uint32_t threshold, float scale, uint64_t seed,
                                          uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
+/* Edge features in the GAT score (opt-in; PyG's GATConv(edge_dim=de) with lin_edge and att_edge folded into one [K x de]
+ * matrix).  Each _efeat entry takes the argument list of its twin of the same name without _efeat (plain or _drop),
+ * followed by (E, lde, att_edge, de), and backward_dst by (P_e, ldp) after those:
+ *   E         [entries x de] fp32, lde >= de counted in elements: row p belongs to indices[p] of the CSR the call walks,
+ *             with the same base as indices -- a call on a block of rows (indptr + r0, the row operands moved by r0 rows)
+ *             passes the SAME E pointer as the call on all rows.  backward_src walks F^T and takes E in F^T's entry order.
+ *   att_edge  [K x de] contiguous;  1 <= de <= MGGCN_GAT_MAX_EDGE_DIM
+ * The score is defined to the bit: with p the entry (i, j),
+ *   t_pk = fmaf(E[p, de - 1], att_edge[k, de - 1], ... fmaf(E[p, 0], att_edge[k, 0], 0.f))      (c ascending)
+ *   x_ijk = (s_dst[i, k] + s_src[j, k]) + t_pk
+ * and everything after x is the twin's: e = x > 0 ? x : slope x, the one-pass softmax, lse, alpha, D, ds, the gather, and
+ * the q of the _drop forms (the same Philox words).  The three calls therefore recompute the same x and the same alpha for
+ * an edge whichever copy of E they read, provided both copies hold the same row for it.  With att_edge = 0 (and a finite
+ * E) every output shared with the twin has the twin's bits.  The edge term enters the score only; the message stays
+ * alpha Z[j].  backward_dst additionally writes row i's share of the gradient of att_edge,
+ *   P_e[i ldp + k de + c] = sum_j ds_ijk E[p, c]   over the entries of row i (+0.0 for a row without entries), ldp >= K de,
+ * from the ds it already forms (under _drop the sum carries q), on the lane that owns the entry: a lane's entries in row
+ * order, then the 64 lanes folded in a fixed order; mggcn_gatv2_att_grad_f32 on P_e (width = K de) gives G_att_edge [K x de].  Nothing of
+ * nnz x K is stored.  No atomics; every output has the same bits on every call, and every row-local output (out, lse, D,
+ * ds_dst, ds_src, G_Z, P_e) the same bits for every split of the rows between calls.  A row of E is read with 16-byte loads
+ * when de % 4 == 0, E is 16-byte aligned and lde % 4 == 0, and element by element otherwise; the (VEC, NT, U) variant is
+ * chosen as the twin chooses it.  P_e must not alias an input.  There is no record (_rec_) and no bf16 form.  The _drop
+ * forms with threshold == 0 launch the plain efeat kernels. */
+#define MGGCN_GAT_MAX_EDGE_DIM 16u
+void mggcn_gat_forward_efeat_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                 const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
+                                 uint32_t K, uint32_t dh, float slope, float *out, size_t ldo, float *lse, const float *E,
+                                 size_t lde, const float *att_edge, uint32_t de);
+void mggcn_gat_backward_dst_efeat_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                      const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                      const float *s_src, const float *lse, const float *G, size_t ldg, const float *out,
+                                      size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *ds_dst,
+                                      const float *E, size_t lde, const float *att_edge, uint32_t de, float *P_e, size_t ldp);
+void mggcn_gat_backward_src_efeat_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                      const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst,
+                                      const float *s_src, const float *lse, const float *D, const float *G, size_t ldg,
+                                      const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
+                                      float *ds_src, float *G_Z, size_t ldgz, const float *E, size_t lde,
+                                      const float *att_edge, uint32_t de);
+void mggcn_gat_forward_efeat_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                      const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                      const float *s_src, uint32_t K, uint32_t dh, float slope, float *out, size_t ldo,
+                                      float *lse, uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream,
+                                      uint32_t dst0, uint32_t src0, const float *E, size_t lde, const float *att_edge,
+                                      uint32_t de);
+void mggcn_gat_backward_dst_efeat_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                           const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                           const float *s_src, const float *lse, const float *G, size_t ldg, const float *out,
+                                           size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *ds_dst,
+                                           uint32_t threshold, float scale, uint64_t seed, uint32_t dropout_stream,
+                                           uint32_t dst0, uint32_t src0, const float *E, size_t lde, const float *att_edge,
+                                           uint32_t de, float *P_e, size_t ldp);
+void mggcn_gat_backward_src_efeat_drop_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                           const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst,
+                                           const float *s_src, const float *lse, const float *D, const float *G, size_t ldg,
+                                           const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
+                                           float *ds_src, float *G_Z, size_t ldgz, uint32_t threshold, float scale,
+                                           uint64_t seed, uint32_t dropout_stream, uint32_t dst0, uint32_t src0,
+                                           const float *E, size_t lde, const float *att_edge, uint32_t de);
 /* Dynamic graph attention (GATv2; opt-in).  F, K, dh, the limits and the column layout of a head are those of the GAT block
  * above; Zs is the source transform (one row per source: the row that gets aggregated), Zd the destination transform (one
  * row per destination), att is [1 x K dh] contiguous, and lse / D are contiguous [destinations x K].  With

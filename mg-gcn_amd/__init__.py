@@ -14,7 +14,8 @@ Layout:
   gat.py       attention / gat_layer / gat: graph attention layers, GAT and (variant="v2": attention_v2 / gatv2_layer)
                GATv2 and (variant="dot": attention_dot / gatdot_layer) dot-product attention; gated_skip: the skip
                connection and gate of skip="add" | "gate" (no reference counterpart); label_input: the table and lists of
-               label_input=rate; attention_model: the dropouts and
+               label_input=rate; attention_efeat: the attention of edge_attr=E (edge features in the score,
+               csrc/gat_efeat.hip); attention_model: the dropouts and
                the export gat and dist_gat share
   sage.py      max_aggregate / sage_layer / sage: GraphSAGE with the mean (gcn's SpMM) or the max aggregator (csrc/agg_max.hip;
                no reference counterpart)

@@ -126,6 +126,23 @@ PROTOTYPES = {
     "mggcn_gat_backward_src_rec_drop_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, c_size_t, vp,
                                                    vp, c_uint32, c_uint32, c_float, vp, vp, c_size_t, c_uint32, c_float,
                                                    c_uint64, c_uint32, c_uint32, c_uint32]),
+    # the _efeat entries: their twin's list, then (E, lde, att_edge, de) and, for backward_dst, (P_e, ldp)
+    "mggcn_gat_forward_efeat_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, c_uint32, c_uint32, c_float,
+                                           vp, c_size_t, vp, vp, c_size_t, vp, c_uint32]),
+    "mggcn_gat_backward_dst_efeat_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, vp, c_size_t, vp,
+                                                c_size_t, c_uint32, c_uint32, c_float, vp, vp, vp, c_size_t, vp, c_uint32, vp,
+                                                c_size_t]),
+    "mggcn_gat_backward_src_efeat_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, c_size_t, vp,
+                                                vp, c_uint32, c_uint32, c_float, vp, vp, c_size_t, vp, c_size_t, vp, c_uint32]),
+    "mggcn_gat_forward_efeat_drop_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, c_uint32, c_uint32,
+                                                c_float, vp, c_size_t, vp, c_uint32, c_float, c_uint64, c_uint32, c_uint32,
+                                                c_uint32, vp, c_size_t, vp, c_uint32]),
+    "mggcn_gat_backward_dst_efeat_drop_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, vp, c_size_t, vp,
+                                                     c_size_t, c_uint32, c_uint32, c_float, vp, vp, c_uint32, c_float, c_uint64,
+                                                     c_uint32, c_uint32, c_uint32, vp, c_size_t, vp, c_uint32, vp, c_size_t]),
+    "mggcn_gat_backward_src_efeat_drop_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, c_size_t,
+                                                     vp, vp, c_uint32, c_uint32, c_float, vp, vp, c_size_t, c_uint32, c_float,
+                                                     c_uint64, c_uint32, c_uint32, c_uint32, vp, c_size_t, vp, c_uint32]),
     "mggcn_gat_scores_backward_f32": (None, [vp, vp, vp, c_size_t, c_size_t, vp, vp, c_size_t, c_size_t, c_uint32,
                                              c_uint32, vp]),
     "mggcn_gatv2_forward_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, c_size_t, vp, c_uint32, c_uint32,

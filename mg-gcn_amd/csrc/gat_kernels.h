@@ -5,6 +5,9 @@
 // kernel's own row, the [rows x K] scalars, all arithmetic and every output are fp32 in both forms.  Only load_head_row
 // (gat_internal.h) knows the element type: a bf16 instantiation is the fp32 one with 8-byte (2-byte) gathers that widen
 // exactly.  Internal linkage in each translation unit that includes it.  Not part of the ABI.
+// gat_efeat.hip holds copies of the three kernels with an edge term added to x (mggcn_gat_*_efeat_f32); everything after x
+// there is meant to stay these kernels statement for statement -- a change here belongs there too
+// (tests/test_gpu_gat_efeat.py compares the bits with att_edge = 0).
 #pragma once
 
 #include <algorithm>

@@ -133,6 +133,32 @@ score the fp32 Zs against an lse taken over rounded rows).  Not built: dist_gat 
 v2 and dot export under bf16, any change of the lane geometry (eight columns per lane), the C++ layer and CLI
 (DESIGN.md 3.10.10).
 
+``edge_attr=E`` (None by default: nothing new is constructed, allocated, launched or registered, the same bits as before)
+puts edge features into the score of variant="v1", PyG's GATConv(edge_dim=de):
+
+    e_ijk = lrelu(s_dst[i, k] + s_src[j, k] + E_p . att_edge[k], slope),   p the entry (i, j)
+
+E is a numpy array [A.nnz() x de], 1 <= de <= ops.GAT_MAX_EDGE_DIM, converted to fp32; row p belongs to entry p of ``A`` as
+given (row r of A lists the destinations that gather source r), and the caller supplies a row for every entry, self-loops
+included -- there is no fill_value.  The edge term enters the score only, the message stays alpha Z[j].  The trained tensor
+is ``layer.attn.att_edge`` [heads x de] per layer, gradient ``G_att_edge``: PyG's lin_edge(E_p)[head k] . att_edge[k] is
+E_p . U[k] with U[k, c] = sum_d W_e[c, k dh + d] att_edge[k, d], and att_edge here IS U -- the same function class without
+the redundant factorisation.  It starts seed-99 uniform like att, is a row of the fused Adam table with W's weight decay,
+``edge_weights=`` takes one [heads x de] array per layer and ``model.edge_dim`` reads de (0 without the option).  The
+kernels are those of csrc/gat_efeat.hip (mggcn_gat_*_efeat_f32 and their _drop twins): de loads and FMAs per (entry, head)
+on the lane that owns the entry, nothing of nnz x heads stored, G_att_edge the fixed-order column sum of per-row shares
+P_e [n x heads de].  The model holds E twice on the device, shared by all layers -- ``E_A`` in A's entry order for
+backward_src and ``E_F`` = E[edge_permutation(A)] in A.transpose()'s for forward and backward_dst: 2 nnz de 4 bytes.  Both
+dropouts (attention dropout draws the same Philox words as without E), skip=, norm=, label_input=, loss="bce", splits,
+evaluate, predict, both Adam modes and model_selector's in-memory restore (att_edge included) compose.  Refused with
+ValueError naming edge_attr before any device work: variant="v2" / "dot", agg_dtype="bf16", an array that is not
+[A.nnz() x de] with de in range, a value that is not finite, a matrix whose indptr does not begin with 0 (row p of E is entry p
+of A's indices array), edge_weights without edge_attr, save / load / save_best (no
+version of the checkpoint file stores att_edge) and attention_weights / gat_layer.alpha (no export kernel has the edge
+term).  Not built: edge features for "v2" and "dot" and in the message, dist_gat (it does not take the arguments), bf16
+gathers or a bf16 E, the export and a checkpoint version, fill_value, reading E through a permutation instead of the second
+copy, the C++ layer and CLI.
+
 Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI.
 """
 from __future__ import annotations
@@ -271,6 +297,117 @@ class attention(gathered_images, param_owner):
 
     def init(self, att) -> None:
         self.att.init(np.asarray(att, dtype=np.float32))
+
+
+def check_edge_attr(edge_attr, edge_weights, variant: str, agg_dtype: str, n_layers: int):
+    """option checking of edge_attr= / edge_weights=, before any device work and before the matrix is looked at: the fp32
+    [entries x de] array (None without the option).  ValueError naming edge_attr for variant="v2" / "dot", agg_dtype="bf16",
+    an array that is not [entries x de] with 1 <= de <= ops.GAT_MAX_EDGE_DIM, a value that is not finite, and for
+    edge_weights without edge_attr or of another length than the layers."""
+    if edge_attr is None:
+        if edge_weights is not None:
+            raise ValueError("edge_weights needs edge_attr: gat(..., edge_attr=E)")
+        return None
+    if variant != "v1":
+        raise ValueError(f'gat(variant="{variant}") has no edge_attr: edge features are built for variant="v1" only (the '
+                         "other scores need a vector of the layer's width per entry)")
+    if agg_dtype != "f32":
+        raise ValueError(f'gat(agg_dtype="{agg_dtype}") has no edge_attr: the edge-feature kernels gather fp32 rows only')
+    E = np.asarray(edge_attr)
+    if E.ndim != 2 or E.dtype.kind not in "fiu":
+        raise ValueError(f"edge_attr must be a numeric [entries x de] array, got shape {E.shape} of {E.dtype}")
+    if not 1 <= E.shape[1] <= ops.GAT_MAX_EDGE_DIM:
+        raise ValueError(f"edge_attr supports 1 <= de <= {ops.GAT_MAX_EDGE_DIM} columns, got {E.shape[1]}")
+    E = np.ascontiguousarray(E, dtype=np.float32)
+    if not np.isfinite(E).all():
+        raise ValueError("edge_attr holds a value that is not finite")
+    if edge_weights is not None and len(edge_weights) != n_layers:
+        raise ValueError(f"edge_weights (of edge_attr) lists {len(edge_weights)} layers, the model has {n_layers}")
+    return E
+
+
+def edge_permutation(A: csr_matrix) -> np.ndarray:
+    """perm with E[perm] in the entry order of A.transpose() for E in A's: mggcn_csr_transpose_host emits a transposed row
+    in increasing source-row order, which is the stable order of A's entries by column; the two entries of a duplicate
+    pair (i, j) keep their order, a consistent bijection between the two copies.  int64, no device work.  Row p of E is entry
+    p of A's indices array and the kernels take indptr's values as the rows of E, so A must start at entry 0: ValueError
+    naming edge_attr for an indptr that does not begin with 0."""
+    if int(A.indptr[0]) != 0:
+        raise ValueError(f"edge_attr needs a matrix whose indptr begins with 0 (row p of E is entry p of A), got {int(A.indptr[0])}")
+    return np.argsort(A.indices[:int(A.indptr[A.n()])], kind="stable")
+
+
+def refuse_edge_attr(model, what: str) -> None:
+    """ValueError naming edge_attr when ``model`` has edge features: ``what`` is a member such a model does not have yet
+    (read with getattr: a model built without __init__ has no such attribute)"""
+    if getattr(model, "edge_dim", 0):
+        raise ValueError(f"gat(edge_attr=...) has no {what}")
+
+
+class attention_efeat(gathered_images):
+    """The attention of one gat(edge_attr=E) layer: ``attention``'s state and parameter with the edge term in the score,
+
+        e_ijk = lrelu(s_dst[i, k] + s_src[j, k] + E_p . att_edge[k]),   p the entry (i, j),
+
+    and one more trained tensor, ``att_edge`` [heads x de] (seed-99 uniform like att), with its gradient ``G_att_edge`` and
+    Adam moments -- the second row of this owner's table, W's weight decay like att.  PyG's GATConv(edge_dim=de) scores
+    an edge with lin_edge(E_p)[head k] . att_edge[k]; that product is E_p . U[k] with U[k, c] = sum_d W_e[c, k dh + d]
+    att_edge[k, d], so att_edge here IS U: the same function class without the redundant factorisation.  ``E_F`` / ``E_A``
+    are the model's two device copies of E ([entries x de]; E_F in the entry order of F, which forward and backward_dst
+    walk, E_A in that of F^T, which backward_src walks) and ``P_e`` [n x heads de] the rows' shares of G_att_edge between
+    backward_dst and the column sum; it aliases ``P_buffer`` (the model's, at the layer with the most heads).  The kernels
+    are those of csrc/gat_efeat.hip (mggcn_gat_*_efeat_f32 and their _drop twins).  There is no export and no bf16 form.
+
+    A parameter owner by its table and gcn.param_owner's own three methods, not by inheritance (as label_input is): the
+    subclasses of param_owner are enumerated for the checkpoint's names per slot, and no version of the checkpoint file
+    stores att_edge.  What it has of ``attention`` -- the constructor's buffers, init -- it takes by name."""
+
+    params_table = attention.params_table + (("att_edge", "att_edge", "G_att_edge", "m_edge", "v_edge", True),)
+    adam_fused = True
+    step = 0
+    m = v = m_edge = v_edge = None
+    variant = "v1"
+    adam_state, adam_tensors, adam_update = param_owner.adam_state, param_owner.adam_tensors, param_owner.adam_update
+    init = attention.init
+
+    def __init__(self, name: str, n_dst: int, n_src: int, out: int, heads: int, slope: float, E_F: dn_matrix, E_A: dn_matrix,
+                 P_buffer=None, device=None):
+        attention.__init__(self, name, n_dst, n_src, out, heads, slope, device)
+        self.E_F, self.E_A, self.edge_dim = E_F, E_A, E_F.m()
+        de = self.edge_dim
+        self.att_edge, self.G_att_edge = dn_matrix(heads, de, device=device), dn_matrix(heads, de, device=device)
+        host = np.empty((heads, de), dtype=np.float32)
+        _lib.load().mggcn_init_uniform_host(host.ctypes.data, de, heads, -1.0)
+        self.att_edge.init(host)
+        self.P_e = dn_matrix(n_dst, heads * de, P_buffer) if P_buffer is not None else dn_matrix(n_dst, heads * de, device=device)
+        self._G_row = dn_matrix(1, heads * de, self.G_att_edge.t)       # G_att_edge as the column sum's [1 x heads de]
+
+    def __call__(self, ctx: context, F: csr_matrix, Z: dn_matrix, out: dn_matrix, drop=None) -> None:
+        n = self.name
+        ops.gat_scores(ctx, Z, self.att, self.s_dst, self.s_src, self.heads, n + "0_gat-scores")
+        ops.gat_forward_efeat(ctx, F, Z, self.s_dst, self.s_src, out, self.lse, self.E_F, self.att_edge, self.heads, self.slope,
+                              n + "0_gat-forward", drop)
+
+    def backward(self, ctx: context, F: csr_matrix, F_T: csr_matrix, Z: dn_matrix, G: dn_matrix, out: dn_matrix,
+                 G_Z: dn_matrix, drop=None) -> None:
+        n = self.name
+        ops.gat_backward_dst_efeat(ctx, F, Z, self.s_dst, self.s_src, self.lse, G, out, self.D, self.ds_dst, self.E_F,
+                                   self.att_edge, self.P_e, self.heads, self.slope, n + "1_gat-backward-dst", drop)
+        ops.gatv2_att_grad(ctx, self.P_e, self._G_row, n + "1_gat-edge-grad")
+        ops.gat_backward_src_efeat(ctx, F_T, Z, self.s_dst, self.s_src, self.lse, self.D, G, self.att, self.ds_dst, self.ds_src,
+                                   G_Z, self.E_A, self.att_edge, self.heads, self.slope, n + "1_gat-backward-src", drop)
+        ops.gat_scores_backward(ctx, self.ds_dst, Z, self.ds_src, Z, self.G_att, self.heads, n + "1_gat-scores-backward")
+
+    def alpha(self, ctx: context, F: csr_matrix, Z: dn_matrix, alpha: dn_matrix) -> None:
+        raise ValueError("gat(edge_attr=...) has no export of the attention coefficients: there is no export kernel with "
+                         "the edge term yet")
+
+    def init_edge(self, att_edge) -> None:
+        att_edge = np.asarray(att_edge, dtype=np.float32)
+        if att_edge.shape != self.att_edge.shape():
+            raise ValueError(f"edge_attr: edge_weights of layer {self.name} must be {self.heads} x {self.edge_dim} "
+                             f"(heads x de), got {att_edge.shape}")
+        self.att_edge.init(att_edge)
 
 
 class attention_v2(attention):
@@ -544,12 +681,14 @@ class gat_layer(layer_params):
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
                  slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None,
-                 skip_buffer=None, agg_dtype: str = "f32", images=None):
+                 skip_buffer=None, agg_dtype: str = "f32", images=None, edge=None):
         n = F.n()
         assert F.n() == F.m() == F_T.n() == F_T.m(), "the single-GPU layer takes a square matrix"
+        # ``edge``: (E_F, E_A, P_buffer) of gat(edge_attr=...), the model's; None builds the attention as it always was
+        attn = (attention(name, n, n, out, heads, slope, agg_dtype=agg_dtype, images=images) if edge is None else
+                attention_efeat(name, n, n, out, heads, slope, *edge))
         # the linear's own fused kernels in every mode: gat(fused=...) only picks how Adam is launched
-        self._setup(name, F, F_T, linear(name, in_, out, backward_out, True),
-                    attention(name, n, n, out, heads, slope, agg_dtype=agg_dtype, images=images), n, in_,
+        self._setup(name, F, F_T, linear(name, in_, out, backward_out, True), attn, n, in_,
                     out, activation, G_Z_buffer, skip=skip, norm=norm, skip_buffer=skip_buffer)
 
     def _setup(self, name: str, F: csr_matrix, F_T: csr_matrix, lin, attn, rows: int, in_: int, out: int, activation: bool,
@@ -653,7 +792,10 @@ class gat_layer(layer_params):
         """The attention coefficients of this layer's most recent forward: [F.nnz() x heads], row p for entry p of F's
         indices array (row i of F lists the sources of destination i), column k for head k.  ``out``: where to put them
         (None allocates).  After a training forward with attention dropout these are the normalised coefficients BEFORE
-        the dropout factor.  ValueError when no forward has run, or for an ``out`` of another shape."""
+        the dropout factor.  ValueError when no forward has run, or for an ``out`` of another shape, and, naming edge_attr and
+        before anything else, on a layer of gat(edge_attr=...)."""
+        refuse_edge_attr(getattr(self, "attn", None), f"export of the attention coefficients (gat layer {self.name}): there is no export "
+                                    "kernel with the edge term yet")
         if self.H is None:
             raise ValueError(f"gat layer {self.name}: no forward has run, there are no attention coefficients yet")
         shape = (self.F.nnz(), self.attn.heads)
@@ -795,10 +937,11 @@ def refuse_dot(model, what: str) -> None:
 
 def refuse_checkpoint(model, member: str) -> None:
     """what save, load and _write_checkpoint of gat refuse, before anything is read, written or created: dot-product
-    attention, the skip options and the label input, which no version of the checkpoint file stores"""
+    attention, the skip options, the label input and the edge features, which no version of the checkpoint file stores"""
     refuse_dot(model, f"{member} has no version for this variant yet")
     refuse_skip(model, f"{member} has no version that stores this option yet")
     refuse_label_input(model, f"{member} has no version that stores the label table E yet")
+    refuse_edge_attr(model, f"{member} has no version that stores att_edge yet")
 
 
 class attention_model:
@@ -883,7 +1026,9 @@ class gat(attention_model, model_base):
 
     gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
     variant="v1", skip=None, norm=None, skip_weights=None, label_input=0.0, label_weights=None,
-    agg_dtype="f32"):
+    agg_dtype="f32", edge_attr=None, edge_weights=None):
+    ``edge_attr`` / ``edge_weights``: edge features in the score of variant="v1", a numpy [A.nnz() x de] array in A's entry
+    order and one [heads x de] att_edge per layer -- see the module docstring; ValueError naming edge_attr for what it refuses.
     ``A`` as ``gcn`` takes it (the layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
     (every layer but the last, which has 1) or one int per layer; ``weights``: per layer (W, b) or (W, b, att);
     ``variant``: "v1" (this model as it always was) or "v2" (GATv2, see the module docstring: W is [in x 2 out], b
@@ -914,12 +1059,17 @@ class gat(attention_model, model_base):
     def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
                  loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0,
                  variant: str = "v1", skip=None, norm=None, skip_weights=None, label_input: float = 0.0,
-                 label_weights=None, agg_dtype: str = "f32"):
+                 label_weights=None, agg_dtype: str = "f32", edge_attr=None, edge_weights=None):
         self.agg_dtype = _check_agg_dtype(agg_dtype)             # option checks come before any device work
         self.sizes = [int(s) for s in sizes]
         self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
         self._attn_dropout_params = check_dropout(attn_dropout, len(self.sizes) - 1)
         self.variant = check_variant(variant, float(attn_dropout))
+        E = check_edge_attr(edge_attr, edge_weights, self.variant, self.agg_dtype, len(self.sizes) - 1)
+        for li, w in enumerate(edge_weights if E is not None and edge_weights is not None else ()):
+            if np.shape(w) != (self.heads[li], E.shape[1]):
+                raise ValueError(f"edge_attr: edge_weights of layer {li} must be {self.heads[li]} x {E.shape[1]} (heads x de), "
+                                 f"got {np.shape(w)}")
         self.skip, self.norm = check_skip(skip), check_norm(norm)
         check_skip_weights(self.skip, skip_weights, len(self.sizes) - 1)
         self._init_dropout(dropout, len(self.sizes) - 1)
@@ -930,6 +1080,9 @@ class gat(attention_model, model_base):
             raise ValueError("label_weights needs label_input > 0")
         if A.n() != A.m():
             raise ValueError(f"gat needs a square matrix, got {A.n()} x {A.m()}")
+        if E is not None and E.shape[0] != A.nnz():
+            raise ValueError(f"edge_attr must have one row per entry of A, {A.nnz()}, got {E.shape[0]}")
+        perm = edge_permutation(A) if E is not None else None    # on the host; refuses an indptr that does not begin with 0
         self.attn_slope = float(attn_slope)
         self._out_width = self.sizes[-1]
         self.fused = bool(fused)
@@ -955,6 +1108,15 @@ class gat(attention_model, model_base):
             self.Z_image_buffer = torch.empty(A.n() * zw * max(self.sizes[1:]), dtype=torch.bfloat16, device="cuda")
             self.G_image_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.bfloat16, device="cuda")
             more.update(agg_dtype="bf16", images=(self.Z_image_buffer, self.G_image_buffer))
+        if E is not None:
+            # E twice on the device, shared by all layers: E_A in A's entry order for backward_src (it walks F^T = A), E_F in
+            # A.transpose()'s for forward and backward_dst; and P_e once, at the layer with the most heads
+            self.edge_dim = int(E.shape[1])
+            self.E_A = dn_matrix.from_numpy(E)
+            self.E_F = dn_matrix.from_numpy(E[perm])
+            del perm
+            self.P_e_buffer = torch.empty(A.n() * max(self.heads) * self.edge_dim, dtype=torch.float32, device="cuda")
+            more.update(edge=(self.E_F, self.E_A, self.P_e_buffer))
         if self.variant == "v2":                                 # G_Z2 = [G_Zs | G_Zd] and P, once at the widest layer
             self.G_Z_buffer = torch.empty(A.n() * 2 * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
             self.P_buffer = torch.empty(A.n() * max(self.sizes[1:]), dtype=torch.float32, device="cuda")
@@ -991,6 +1153,13 @@ class gat(attention_model, model_base):
                 layer.b().init(np.asarray(w[1], dtype=np.float32))
                 if len(w) > 2:
                     layer.attn.init(w[2])
+        if E is not None and edge_weights is not None:
+            for layer, w in zip(self.layers_, edge_weights):
+                layer.attn.init_edge(w)
+
+    # ---- edge features in the score (edge_attr=E) ----------------------------------------------------------------------------
+    edge_dim = 0                        # de, the columns of edge_attr; 0 without the option
+    E_A = E_F = P_e_buffer = None       # E in A's and in A.transpose()'s entry order, and the rows' shares of G_att_edge
 
     # ---- masked label inputs (label_input=rate) ----------------------------------------------------------------------------
     label = None                        # the label_input owner; layers()[0].label is the same object
@@ -1089,6 +1258,7 @@ class gat(attention_model, model_base):
         before anything else"""
         refuse_dot(self, "attention_weights: there is no export kernel for the dot-product coefficients yet")
         refuse_bf16_export(self, "attention_weights")
+        refuse_edge_attr(self, "attention_weights: there is no export kernel with the edge term yet")
         return attention_model.attention_weights(self, ctx, X, layers, out)
 
     def attention_pattern(self):

@@ -479,6 +479,7 @@ def gated_skip_backward(ctx: context, G: dn_matrix, act: Optional[dn_matrix], o:
 
 GAT_MAX_HEADS = 16                  # MGGCN_GAT_MAX_HEADS
 GAT_MAX_WIDTH = 1024                # MGGCN_GAT_MAX_WIDTH: heads x width per head
+GAT_MAX_EDGE_DIM = 16               # MGGCN_GAT_MAX_EDGE_DIM: columns of the edge features of gat(edge_attr=...)
 GAT_SLOPE = 0.2                     # the leaky ReLU of the attention scores (not the layers' 0.01)
 
 
@@ -761,6 +762,84 @@ def gat_scores_backward(ctx: context, ds_dst: dn_matrix, Z_dst: dn_matrix, ds_sr
     _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_gat_scores_backward_f32(
         ctx.stream(0), ds_dst.buffer(), Z_dst.buffer(), Z_dst.m(), Z_dst.n(), ds_src.buffer(), Z_src.buffer(), Z_src.m(),
         Z_src.n(), heads, Z_src.m() // heads, G_att.buffer()))
+
+
+def _gat_efeat_args(what: str, F: csr_matrix, E: dn_matrix, att_edge: dn_matrix, heads: int):
+    """the four trailing arguments (E, lde, att_edge, de) of a mggcn_gat_*_efeat call: E [F.nnz() x de], one row per entry of
+    the matrix the call walks, att_edge [heads x de]; ValueError before the library for a shape or limit that does not fit"""
+    de = E.m()
+    _req(1 <= de <= GAT_MAX_EDGE_DIM, f"{what} supports 1 <= edge dimension <= {GAT_MAX_EDGE_DIM}, got {de}")
+    _req(E.n() == F.nnz(), f"{what}: E must have one row per entry, {F.nnz()}, got {E.n()}")
+    _req(att_edge.shape() == (heads, de), f"{what}: att_edge must be {heads} x {de} (heads x edge dimension)")
+    return (E.buffer(), de, att_edge.buffer(), de)
+
+
+def _gat_efeat_call(ctx: context, timer: Optional[str], name: str, args, extra, tail) -> None:
+    """mggcn_<name>_efeat_f32(*args, *tail) under ``timer``; with ``extra`` (the tuple of _gat_drop_args) the _efeat_drop
+    twin, which takes it between the two"""
+    entry = getattr(ctx.lib, f"mggcn_{name}_efeat{'' if extra is None else '_drop'}_f32")
+    _gat_timed(ctx, timer, lambda: entry(*args, *(extra or ()), *tail))
+
+
+def gat_forward_efeat(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
+                      lse: dn_matrix, E: dn_matrix, att_edge: dn_matrix, heads: int, slope: float = GAT_SLOPE,
+                      timer: Optional[str] = None, drop=None) -> None:
+    """gat_forward with edge features in the score (mggcn_gat_forward_efeat_f32 / _efeat_drop_f32): x_ijk = (s_dst[i, k] +
+    s_src[j, k]) + sum_c E[p, c] att_edge[k, c] for entry p = (i, j) of F's indices array, and everything after x is
+    gat_forward's.  ``E``: [F.nnz() x de] in F's entry order, ``att_edge``: [heads x de], de <= GAT_MAX_EDGE_DIM."""
+    what = "gat forward"
+    _req_roles(what, False, (Z,))
+    check_gat_heads(heads, Z.m(), what)
+    _req(F.m() == Z.n() and out.shape() == (F.n(), Z.m()), f"{what}: shape mismatch")
+    _req(s_dst.shape() == (F.n(), heads) and lse.shape() == (F.n(), heads) and s_src.shape() == (F.m(), heads),
+         f"{what}: the scores and lse must be rows x heads")
+    tail = _gat_efeat_args(what, F, E, att_edge, heads)
+    extra = None if drop is None else _gat_drop_args(drop, what, F.n(), F.m())
+    ip, ix, _ = F.device(ctx.device)
+    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(), heads,
+            Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer())
+    _gat_efeat_call(ctx, timer, "gat_forward", args, extra, tail)
+
+
+def gat_backward_dst_efeat(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
+                           G: dn_matrix, out: dn_matrix, D: dn_matrix, ds_dst: dn_matrix, E: dn_matrix, att_edge: dn_matrix,
+                           P_e: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None,
+                           drop=None) -> None:
+    """gat_backward_dst with the edge term in the score (mggcn_gat_backward_dst_efeat_f32 / _efeat_drop_f32), which also
+    writes P_e[i, k de + c] = sum_j ds_ijk E[p, c] over the entries of row i: row i's share of the gradient of att_edge
+    (gatv2_att_grad(P_e, G_att_edge viewed as 1 x heads de) sums the rows).  ``E`` in F's entry order; ``P_e``: [F.n() x
+    heads de]."""
+    what = "gat backward"
+    _req_roles(what, False, (Z,), (G, out))
+    check_gat_heads(heads, Z.m(), what)
+    _req(F.m() == Z.n() and G.shape() == (F.n(), Z.m()) and out.shape() == G.shape(), f"{what}: shape mismatch")
+    _req(all(s.shape() == (F.n(), heads) for s in (s_dst, lse, D, ds_dst)) and s_src.shape() == (F.m(), heads),
+         f"{what}: the scores, lse, D and ds must be rows x heads")
+    tail = _gat_efeat_args(what, F, E, att_edge, heads)
+    _req(P_e.shape() == (F.n(), heads * E.m()), f"{what}: P_e must be {F.n()} x {heads * E.m()} (rows x heads x edge dimension)")
+    extra = None if drop is None else _gat_drop_args(drop, what, F.n(), F.m())
+    ip, ix, _ = F.device(ctx.device)
+    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
+            lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer())
+    _gat_efeat_call(ctx, timer, "gat_backward_dst", args, extra, tail + (P_e.buffer(), P_e.m()))
+
+
+def gat_backward_src_efeat(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
+                           D: dn_matrix, G: dn_matrix, att: dn_matrix, ds_dst: Optional[dn_matrix], ds_src: dn_matrix,
+                           G_Z: dn_matrix, E: dn_matrix, att_edge: dn_matrix, heads: int, slope: float = GAT_SLOPE,
+                           timer: Optional[str] = None, drop=None) -> None:
+    """gat_backward_src with the edge term in the score (mggcn_gat_backward_src_efeat_f32 / _efeat_drop_f32).  ``E``:
+    [F_T.nnz() x de] in F_T's entry order -- the other copy of what gat_forward_efeat read, row for row of the same edge."""
+    what = "gat backward"
+    _req_roles(what, False, (G,), (Z, G_Z))
+    _req_gat_backward_src(F_T, Z, (s_dst, lse, D), s_src, G, att, ds_dst, ds_src, G_Z, heads, "the scores, lse, D and ds")
+    tail = _gat_efeat_args(what, F_T, E, att_edge, heads)
+    extra = None if drop is None else _gat_drop_args(drop, what, F_T.m(), F_T.n())
+    ip, ix, _ = F_T.device(ctx.device)
+    args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
+            lse.buffer(), D.buffer(), G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
+            Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m())
+    _gat_efeat_call(ctx, timer, "gat_backward_src", args, extra, tail)
 
 
 def _req_gat_alpha(F, lse, alpha, heads: int, what: str) -> None:
