@@ -817,7 +817,39 @@ void mggcn_agg_max_pack_f32(mggcn_stream_t stream, const uint32_t *arg, size_t l
 void mggcn_agg_max_backward_rec_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
                                     const uint32_t *t_indices, const uint32_t *rec, size_t ldr, uint32_t d, uint32_t src0,
                                     uint32_t flags, float *G_B, size_t ldgb);
-/* cublasSasum  (src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
+
+/* The per-epoch edge sample of gat / sage(aggr="max") (no reference counterpart), drawn on the device: count, scan, compact.
+ * A CSR pattern (u32 indptr / indices on the device, no values) keeps entry (destination i, source j), both global vertex
+ * numbers, iff
+ *     i == j   or   thr_i == 0xFFFFFFFF   or   word 0 of Philox4x32-10(counter = (j, i, 0xC0000000, epoch),
+ *                                                   key = (seed & 0xFFFFFFFF, seed >> 32)) < thr_i,
+ * thr the destinations' thresholds (the host's floor(q_i 2^32), capped at 2^32 - 1).  The third counter word keeps the draw
+ * apart from mggcn_dropout_f32 (row >> 32), attention dropout (0x80000000 | k >> 2) and the label mask (first word
+ * 0xFFFFFFFF) under one seed.  The bit is a function of (seed, epoch, i, j) alone: duplicate entries share it, nothing of
+ * size nnz is stored between count and compact, and a matrix and its transpose keep the same pairs, each in its own entry
+ * order -- the two results are transposes of each other entry for entry.
+ *   transposed = 0: row r is destination row0 + r with threshold thr[r], column c is source col0 + c.
+ *   transposed = 1: row r is source row0 + r, column c is destination col0 + c with threshold thr[c] (gathered).
+ * row0 / col0 enter the counter and the self-loop test only: a call over a row range (indptr + r0, thr + r0 when not
+ * transposed, row0 = r0) gives the whole call's rows.
+ *   count     counts[r] = the kept entries of row r.  One wave per row.
+ *   scan      out_indptr[0] = 0, out_indptr[r + 1] = counts[0] + ... + counts[r] (mod 2^32), n_rows + 1 words, in three
+ *             launches (sums per 256-block, one workgroup over the block sums, add): no workgroup waits on another.
+ *             n_rows == 0 writes out_indptr[0].  out_indptr must not alias counts.
+ *   compact   draws the same bits again and writes the kept columns of row r, in their original order, at
+ *             out_indices + out_indptr[r]: one wave per row over 64-entry chunks, a ballot of the keep bits, a lane's rank
+ *             the population count of the lanes below it.  No atomics, no scratch, the same bits on every call and for
+ *             every split of the rows between calls; nothing is written at or beyond out_indptr[r + 1] for any row, so
+ *             nothing beyond out_indptr[n_rows] entries.  out_indices must not alias indices.
+ * n_rows == 0 returns (count, compact).  Values are not carried. */
+void mggcn_edge_sample_count_u32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr, const uint32_t *indices,
+                                 const uint32_t *thr, int transposed, uint32_t row0, uint32_t col0, uint64_t seed,
+                                 uint32_t epoch, uint32_t *counts);
+void mggcn_edge_sample_scan_u32(mggcn_stream_t stream, const uint32_t *counts, size_t n_rows, uint32_t *out_indptr);
+void mggcn_edge_sample_compact_u32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr, const uint32_t *indices,
+                                   const uint32_t *thr, int transposed, uint32_t row0, uint32_t col0, uint64_t seed,
+                                   uint32_t epoch, const uint32_t *out_indptr, uint32_t *out_indices);
+/* cublasSasum(src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host
  * wrapper copies it back after its own sync (src/gcn.hpp:816-817). */

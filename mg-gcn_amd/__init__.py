@@ -19,6 +19,8 @@ Layout:
                the export gat and dist_gat share
   sage.py      max_aggregate / sage_layer / sage: GraphSAGE with the mean (gcn's SpMM) or the max aggregator (csrc/agg_max.hip;
                no reference counterpart)
+  edge_sample.py thresholds / sampled_csr / edge_sampler / sampling_option: the per-epoch edge sample of gat and sage(aggr="max"),
+               drawn on the device (csrc/edge_sample.hip; no reference counterpart)
   label_mask.py  the host's restatement of the label-input mask: its count per epoch, without a synchronisation
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*); dist_model_base:
                the epoch dist_gcn and dist_gat share
@@ -43,6 +45,8 @@ from .gcn import (gcn, gcn_layer, linear, softmax, softmax_cross_entropy_loss,  
 from .gat import attention, attention_dot, attention_v2, gat, gat_layer, gatdot_layer, gated_skip, gatv2_layer, label_input  # noqa: F401
 
 from .sage import max_aggregate, sage, sage_layer               # noqa: F401
+from . import edge_sample                                       # noqa: F401
+from .edge_sample import edge_sampler, sampled_csr              # noqa: F401
 
 from . import dist                                              # noqa: F401
 from .dist import (dist_context, dist_gcn, dist_gcn_layer, dist_row_csr_matrix,  # noqa: F401
@@ -55,4 +59,4 @@ from .smoothing import correct_and_smooth                       # noqa: F401
 
 __all__ = ["context", "csr_matrix", "dn_matrix", "matrix_error", "engine_error", "ops", "matmul",
            "get_matmul_buffer", "sparse_linear", "linear", "gcn_layer", "softmax",
-           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "sage", "sage_layer", "max_aggregate", "datasets", "model_selector", "correct_and_smooth"]
+           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "sage", "sage_layer", "max_aggregate", "edge_sampler", "sampled_csr", "datasets", "model_selector", "correct_and_smooth"]

@@ -171,6 +171,10 @@ PROTOTYPES = {
     "mggcn_agg_max_pack_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_agg_max_backward_rec_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, c_uint32, c_uint32, c_uint32, vp,
                                               c_size_t]),
+    "mggcn_edge_sample_count_u32": (None, [vp, c_uint32, vp, vp, vp, c_int, c_uint32, c_uint32, c_uint64, c_uint32, vp]),
+    "mggcn_edge_sample_scan_u32": (None, [vp, vp, c_size_t, vp]),
+    "mggcn_edge_sample_compact_u32": (None, [vp, c_uint32, vp, vp, vp, c_int, c_uint32, c_uint32, c_uint64, c_uint32, vp,
+                                             vp]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),
     "mggcn_gather_rows_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_softmax_xent_fused_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_float, vp]),

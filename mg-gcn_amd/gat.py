@@ -159,6 +159,27 @@ term).  Not built: edge features for "v2" and "dot" and in the message, dist_gat
 gathers or a bf16 E, the export and a checkpoint version, fill_value, reading E through a permutation instead of the second
 copy, the C++ layer and CLI.
 
+``fanout=k`` / ``edge_keep=q`` (None and 1.0 by default: no sampler, no buffer, no launch, no timer, the same bits as before)
+train every epoch on a fresh sample of the edges, drawn on the device (edge_sample.py; csrc/edge_sample.hip): DropEdge with
+``edge_keep``, an expected GraphSAGE fan-out with ``fanout``, or both -- destination i keeps each of its entries with
+probability q_i = edge_keep * min(1, fanout / deg_i), self-loops always, by a Philox bit on (seed, epoch, i, j) that the
+forward matrix and its transpose draw independently and still end up exact transposes of each other.  A training forward
+(train_forward / train_step) draws the sample of ``sample_epoch``, runs every layer's sparse kernels, forward and backward,
+over that one pair (one sample per epoch, shared by all layers), and moves ``sample_epoch`` on, exactly as dropout_epoch
+moves; set_sampling(fanout=None, keep=1.0, seed=0, epoch=0) sets all of it (epoch=e replays training forward e) and
+``sample_fanout``, ``sample_keep``, ``sample_seed``, ``sample_epoch`` read the state; ``sampler`` is the edge_sampler (None
+when off).  A plain call, evaluate(), predict(), attention_weights(ctx, X) and correct_and_smooth.predict run on the full
+graph with the bits they always had; model_selector defaults to clean=True, so its validation number is the full graph's.
+All three variants, both dropouts (attention dropout is keyed by vertex numbers, not entry positions), skip=, norm=,
+label_input=, loss="bce", splits, agg_dtype="bf16" and both Adam modes compose without special cases.  ``fanout`` is an
+EXPECTED fan-out, not an exact one.  Checkpoints do not store the sampling state: save works, load leaves the state alone,
+and a resumed run calls set_sampling(..., epoch=...) itself.  Refused with ValueError naming the argument before any device
+work: a keep outside (0, 1], a fanout that is not None or an integer >= 1, sampling together with edge_attr= (the rows of E
+are aligned to entry positions), and attention_weights(ctx) / gat_layer.alpha without X when the most recent forward was a
+sampled one (its lse belongs to a pattern the export does not walk).  Not built: exact-k sampling, per-layer samples,
+carrying or renormalising values, dist_gat (it does not take the arguments), edge features under sampling, the export of a
+sampled forward, the state in checkpoints, the C++ layer and CLI.
+
 Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI.
 """
 from __future__ import annotations
@@ -169,6 +190,7 @@ import numpy as np
 
 from . import _lib, label_mask, ops
 from .checkpoint import checkpoint_option
+from .edge_sample import sampling_option
 from .gcn import (DROPOUT_MAX_LAYERS, _check_agg_dtype, check_dropout, check_loss, check_norm, dropout_option, layer_norm,
                   layer_params, linear, model_base, param_owner, sigmoid_bce_loss, softmax_cross_entropy_loss)
 from .matrix import context, csr_matrix, dn_matrix
@@ -667,6 +689,14 @@ class label_input:
 _label_input_owner = label_input         # gat's constructor has an argument of that name
 
 
+def refuse_sampled_export(layer, what: str) -> None:
+    """ValueError naming the sampling when ``layer``'s most recent forward ran on an edge sample: its lse belongs to a pattern
+    the export does not walk.  A plain forward (attention_weights(ctx, X)) clears it."""
+    if getattr(layer, "sample", None) is not None:
+        raise ValueError(f"{what}: the most recent forward was a sampled training forward (set_sampling / fanout / edge_keep); "
+                         "its lse belongs to the sample, not to the pattern the export walks -- pass X: attention_weights(ctx, X)")
+
+
 class gat_layer(layer_params):
     """One GAT layer: a ``linear`` (Z = H W + 1 b^T), an ``attention`` over (F, F^T) and the activation.  Z, the
     aggregated ``out`` (before the activation: the backward pass needs it) and the activated output are kept per layer;
@@ -678,6 +708,11 @@ class gat_layer(layer_params):
 
     res_lin = gate = norm = None
     label = None                # the model's label_input, in layer 0 of gat(label_input=rate) only
+    sample = None               # (F, F_T) of this forward where the model drew an edge sample (edge_sample.py); None: the full graph
+
+    def _matrices(self):
+        """(F, F_T) the most recent forward walked and its backward walks: the model's sample of the epoch, or the full graph"""
+        return self.sample if self.sample is not None else (self.F, self.F_T)
 
     def __init__(self, name: str, F: csr_matrix, F_T: csr_matrix, in_: int, out: int, heads: int, activation: bool,
                  slope: float = ops.GAT_SLOPE, backward_out: bool = True, G_Z_buffer=None, skip=None, norm=None,
@@ -738,7 +773,7 @@ class gat_layer(layer_params):
         self.lin(ctx, H, self.Z)
         if self.label is not None:                           # [H | M onehot(y)] [W ; E] = H W + M E[y]: the skip sees H only
             self.label(ctx, self.Z, self.row0)
-        self.attn(ctx, self.F, self.Z, self.out, self.attn_dropout)
+        self.attn(ctx, self._matrices()[0], self.Z, self.out, self.attn_dropout)
         if self.skip is not None or self.norm is not None:
             # attention -> skip -> norm -> activation; ``out`` stays as the attention wrote it (its backward reads it), y
             # goes to ``act``, the norm runs in place there, and the activation rides in whichever of the two runs last
@@ -776,7 +811,7 @@ class gat_layer(layer_params):
             ctx.record(n + "1_1_activation", 0)
             ctx.register_timer(n + "1_activation", n + "1_0_activation", n + "1_1_activation")
             T = self.act
-        self.attn.backward(ctx, self.F, self.F_T, self.Z, T, self.out, self.G_Z, self.attn_dropout)
+        self.attn.backward(ctx, *self._matrices(), self.Z, T, self.out, self.G_Z, self.attn_dropout)
         if self.label is not None:
             self.label.backward(ctx, self.G_Z, self.row0)
         self.lin.setX(self.H)
@@ -796,6 +831,7 @@ class gat_layer(layer_params):
         before anything else, on a layer of gat(edge_attr=...)."""
         refuse_edge_attr(getattr(self, "attn", None), f"export of the attention coefficients (gat layer {self.name}): there is no export "
                                     "kernel with the edge term yet")
+        refuse_sampled_export(self, f"gat layer {self.name}: alpha")
         if self.H is None:
             raise ValueError(f"gat layer {self.name}: no forward has run, there are no attention coefficients yet")
         shape = (self.F.nnz(), self.attn.heads)
@@ -1014,6 +1050,9 @@ class attention_model:
         where something of nnz x heads is stored: the Reddit-shaped graph (114.8 M entries) at 4 heads needs 1.84 GB per
         layer.  Nothing is allocated or launched unless this method (or gat_layer.alpha) is called."""
         which = self._alpha_requests(layers, out)
+        if X is None:
+            for li in which:
+                refuse_sampled_export(self.layers_[li], "attention_weights")
         if X is not None:
             self(ctx, X)
         elif any(self.layers_[li].H is None for li in which):
@@ -1021,12 +1060,14 @@ class attention_model:
         return [self.layers_[li].alpha(ctx, None if out is None else out[i]) for i, li in enumerate(which)]
 
 
-class gat(attention_model, model_base):
+class gat(attention_model, sampling_option, model_base):
     """A stack of GAT layers with the loss layers, splits and Adam of ``gcn``.
 
     gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
     variant="v1", skip=None, norm=None, skip_weights=None, label_input=0.0, label_weights=None,
-    agg_dtype="f32", edge_attr=None, edge_weights=None):
+    agg_dtype="f32", edge_attr=None, edge_weights=None, fanout=None, edge_keep=1.0):
+    ``fanout`` / ``edge_keep``: per-epoch edge sampling, set_sampling's fanout and keep -- see the module docstring and
+    edge_sample.sampling_option; ValueError naming the argument for what it refuses.
     ``edge_attr`` / ``edge_weights``: edge features in the score of variant="v1", a numpy [A.nnz() x de] array in A's entry
     order and one [heads x de] att_edge per layer -- see the module docstring; ValueError naming edge_attr for what it refuses.
     ``A`` as ``gcn`` takes it (the layers aggregate over the pattern of A.transpose(); A's values are neither used nor changed); ``heads``: an int
@@ -1059,13 +1100,17 @@ class gat(attention_model, model_base):
     def __init__(self, A: csr_matrix, sizes: Sequence[int], heads=4, attn_slope: float = ops.GAT_SLOPE,
                  loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0,
                  variant: str = "v1", skip=None, norm=None, skip_weights=None, label_input: float = 0.0,
-                 label_weights=None, agg_dtype: str = "f32", edge_attr=None, edge_weights=None):
+                 label_weights=None, agg_dtype: str = "f32", edge_attr=None, edge_weights=None, fanout=None,
+                 edge_keep: float = 1.0):
         self.agg_dtype = _check_agg_dtype(agg_dtype)             # option checks come before any device work
         self.sizes = [int(s) for s in sizes]
         self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
         self._attn_dropout_params = check_dropout(attn_dropout, len(self.sizes) - 1)
         self.variant = check_variant(variant, float(attn_dropout))
         E = check_edge_attr(edge_attr, edge_weights, self.variant, self.agg_dtype, len(self.sizes) - 1)
+        if E is not None:
+            self.edge_dim = int(E.shape[1])
+        self._init_sampling(fanout, edge_keep)                   # refuses edge_attr with sampling on
         for li, w in enumerate(edge_weights if E is not None and edge_weights is not None else ()):
             if np.shape(w) != (self.heads[li], E.shape[1]):
                 raise ValueError(f"edge_attr: edge_weights of layer {li} must be {self.heads[li]} x {E.shape[1]} (heads x de), "
@@ -1135,6 +1180,7 @@ class gat(attention_model, model_base):
                 self.layers_.append(gat_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
                                               i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer, **more))
         self._adam = None
+        self._make_sampler(self.A_T, self.A)                     # nothing unless sampling is on
         self.label_input_p = float(label_input)
         if self.label_input_p > 0.0:                             # with 0 nothing is allocated, launched or registered
             self.label = self.layers_[0].label = _label_input_owner("0_", self.sizes[-1], self.layers_[0].Z.m())
@@ -1244,7 +1290,16 @@ class gat(attention_model, model_base):
     def __call__(self, ctx: context, H: dn_matrix, training: bool = False) -> dn_matrix:
         if self.label is not None:
             self._arm_label_input(training)
+        pair = self._draw_sample(ctx, training)                  # one sample per epoch, shared by all layers; None: the full graph
+        for layer in self.layers_:
+            layer.sample = pair
         return model_base.__call__(self, ctx, H, training)
+
+    # ---- per-epoch edge sampling (fanout=, edge_keep=, set_sampling: edge_sample.sampling_option) ----------------------------
+    def _refuse_sampling(self, fanout, keep) -> None:
+        if getattr(self, "edge_dim", 0):
+            raise ValueError("gat(edge_attr=...) has no edge sampling (fanout / edge_keep / set_sampling): the rows of E are "
+                             "aligned to entry positions, which a sample does not keep")
 
     def _launched(self) -> None:
         """train_step's hook between its last launch and its synchronisation: the next epoch's count, while the device works"""

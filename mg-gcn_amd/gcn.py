@@ -34,6 +34,7 @@ import numpy as np
 
 from . import ops
 from .checkpoint import checkpoint_option
+from .edge_sample import refuse_sampling
 from .matrix import context, csr_matrix, dn_matrix, host_scalars
 
 MGGCN_SPMM_LEAKY_RELU = 1
@@ -1052,13 +1053,18 @@ class gcn(model_base):
     call and evaluate() run the same kernels.  None (the default) launches nothing new.
 
     save(ctx, path, optimizer=True) / load(ctx, path) / predict(ctx, X): see checkpoint.checkpoint_option -- the file
-    carries the configuration, the parameters, Adam's state and the dropout state, and no execution option."""
+    carries the configuration, the parameters, Adam's state and the dropout state, and no execution option.
+
+    ``fanout`` / ``edge_keep`` / set_sampling: per-epoch edge sampling (edge_sample.py) is REFUSED here with ValueError naming
+    the argument -- the sweep SpMM's plan is built on the host from host arrays and carries the values; gat and
+    sage(aggr="max") have it."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], residual_layer: bool = False,
                  weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None, fused: bool = True,
                  hoist_first_aggregation: bool = False, agg_dtype: str = "f32", dropout: float = 0.0, norm=None,
-                 loss: str = "softmax"):
-        self._init_dropout(dropout, len(sizes) - 1)          # option checks come before any device work
+                 loss: str = "softmax", fanout=None, edge_keep: float = 1.0):
+        refuse_sampling("gcn", fanout, edge_keep)            # option checks come before any device work
+        self._init_dropout(dropout, len(sizes) - 1)
         self.norm = check_norm(norm)
         self.loss = check_loss(loss)
         self._out_width = int(sizes[-1])
@@ -1120,6 +1126,11 @@ class gcn(model_base):
             ops.prebuild_plans(ctx, self._plan_wants)
             self._plan_wants = []
         return model_base.__call__(self, ctx, H, training)
+
+    def set_sampling(self, fanout=None, keep: float = 1.0, seed: int = 0, epoch: int = 0) -> None:
+        """gcn has no edge sampling (edge_sample.refuse_sampling): ValueError naming the argument for any setting that is on
+        or out of range; fanout=None, keep=1.0 is accepted and changes nothing"""
+        refuse_sampling("gcn", fanout, keep)
 
     def update(self, ctx: context, lr: float, weight_decay: float) -> None:
         for layer in self.layers_:

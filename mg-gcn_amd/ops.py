@@ -1284,6 +1284,69 @@ def agg_max_backward_rec(ctx: context, F_T: csr_matrix, rec, d: int, G_B: dn_mat
         AGG_ACCUMULATE if accumulate else 0, G_B.buffer(), G_B.m()))
 
 
+# ---- the per-epoch edge sample (csrc/edge_sample.hip) ----------------------------------------------------------------------
+EDGE_SAMPLE_DOMAIN = 0xC0000000     # the third Philox counter word of every draw of the edge sample
+
+
+def _req_u32(t, least: int, what: str) -> None:
+    """a contiguous device tensor of at least ``least`` 4-byte integers"""
+    _req(hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous() and t.element_size() == 4
+         and not t.dtype.is_floating_point and t.numel() >= least,
+         f"{what} must be a contiguous device tensor of at least {least} 4-byte integers")
+
+
+def _edge_sample_args(what: str, n_rows: int, indptr, indices, thr, transposed, row0: int, col0: int, seed: int, epoch: int):
+    _req(isinstance(n_rows, numbers.Integral) and 0 <= n_rows < 1 << 32, f"{what}: n_rows must fit 32 bits")
+    _req(transposed in (0, 1, False, True), f"{what}: transposed must be 0 or 1")
+    _req_u32(indptr, n_rows + 1, f"{what}: indptr")
+    _req_u32(indices, 0, f"{what}: indices")
+    _req_u32(thr, 0 if transposed else n_rows, f"{what}: thr")
+    for name, v in (("row0", row0), ("col0", col0)):
+        _req(isinstance(v, numbers.Integral) and 0 <= v < 1 << 32, f"{what}: {name} must fit 32 bits")
+    return (int(n_rows), indptr.data_ptr(), indices.data_ptr(), thr.data_ptr(), int(bool(transposed)), int(row0), int(col0),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF)
+
+
+def edge_sample_count(ctx: context, n_rows: int, indptr, indices, thr, transposed, counts, row0: int = 0, col0: int = 0,
+                      seed: int = 0, epoch: int = 0, timer: Optional[str] = None) -> None:
+    """counts[r] = the entries of row r that the edge sample keeps (mggcn_edge_sample_count_u32).  Entry (destination i,
+    source j) is kept iff i == j, or thr_i == 0xFFFFFFFF, or word 0 of Philox4x32-10((j, i, EDGE_SAMPLE_DOMAIN, epoch), seed)
+    is below thr_i.  ``transposed`` 0: rows are destinations (thr[r]); 1: rows are sources and the entry's column is the
+    destination (thr[c], which must cover every column).  row0 / col0: the global numbers of row 0 and column 0.  The
+    operands are device tensors of 4-byte integers: indptr of n_rows + 1 from its first element on (a row range passes a
+    slice), indices as the indptr values address it."""
+    what = "edge sample count"
+    args = _edge_sample_args(what, n_rows, indptr, indices, thr, transposed, row0, col0, seed, epoch)
+    _req_u32(counts, n_rows, f"{what}: counts")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_edge_sample_count_u32(ctx.stream(0), *args, counts.data_ptr()))
+
+
+def edge_sample_scan(ctx: context, counts, n_rows: int, out_indptr, timer: Optional[str] = None) -> None:
+    """out_indptr[0] = 0, out_indptr[r + 1] = counts[0] + ... + counts[r]: n_rows + 1 words (mggcn_edge_sample_scan_u32; three
+    launches, no workgroup waits on another)"""
+    what = "edge sample scan"
+    _req(isinstance(n_rows, numbers.Integral) and 0 <= n_rows < 1 << 32, f"{what}: n_rows must fit 32 bits")
+    _req_u32(counts, n_rows, f"{what}: counts")
+    _req_u32(out_indptr, n_rows + 1, f"{what}: out_indptr")
+    _req(counts.data_ptr() != out_indptr.data_ptr(), f"{what}: out_indptr must not alias counts")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_edge_sample_scan_u32(ctx.stream(0), counts.data_ptr(), int(n_rows),
+                                                                      out_indptr.data_ptr()))
+
+
+def edge_sample_compact(ctx: context, n_rows: int, indptr, indices, thr, transposed, out_indptr, out_indices, row0: int = 0,
+                        col0: int = 0, seed: int = 0, epoch: int = 0, timer: Optional[str] = None) -> None:
+    """the kept columns of row r, in their original order, at out_indices[out_indptr[r]:out_indptr[r + 1]]
+    (mggcn_edge_sample_compact_u32): the bits of edge_sample_count drawn again, out_indptr the scan of its counts.  Nothing
+    beyond out_indptr[n_rows] entries is written; out_indices must hold that many (the parent's nnz always does)."""
+    what = "edge sample compact"
+    args = _edge_sample_args(what, n_rows, indptr, indices, thr, transposed, row0, col0, seed, epoch)
+    _req_u32(out_indptr, n_rows + 1, f"{what}: out_indptr")
+    _req_u32(out_indices, 0, f"{what}: out_indices")
+    _req(out_indices.data_ptr() != indices.data_ptr() or indices.numel() == 0, f"{what}: out_indices must not alias indices")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_edge_sample_compact_u32(ctx.stream(0), *args, out_indptr.data_ptr(),
+                                                                         out_indices.data_ptr()))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""

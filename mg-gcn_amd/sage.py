@@ -22,6 +22,16 @@ mask, so both branches see the dropped H, and the gradient returned; ``loss="bce
 launched (one launch for the model or one per tensor: the same bits).  set_splits, split_metrics, train_step, evaluate,
 predict, model_selector's in-memory restore and smoothing.correct_and_smooth.predict are model_base's.
 
+``fanout=k`` / ``edge_keep=q`` with ``aggr="max"`` (None and 1.0 by default: nothing new is allocated, launched or registered)
+train every epoch on a fresh sample of the edges drawn on the device (edge_sample.py; set_sampling(fanout, keep, seed, epoch),
+``sample_fanout`` / ``sample_keep`` / ``sample_seed`` / ``sample_epoch``, as on gat): a training forward aggregates, forward and
+backward, over the pair of the epoch; every other forward runs on the full graph.  A sampled training forward neither reads
+nor writes layer 0's kept ``agg(X)``: it aggregates X over the sample into a buffer of its own every epoch (``_M_sampled``),
+and stores no ``arg`` there either -- layer 0 has no input gradient and its weight gradient reads M alone.  The sample keeps
+the entry order of the row-sorted pattern and duplicates share their bit, so equal indices of a sampled row stay adjacent,
+which the max backward needs.  ``aggr="mean"`` refuses sampling by name: the sweep SpMM's plan is built on the host from host
+arrays and carries the values.
+
 Refused with ValueError naming the argument, before any device work: an unknown ``aggr``, a matrix that is not square, and
 gcn's own errors for ``norm``, ``loss`` and ``dropout``; save / load / model_selector.save_best (no version of the checkpoint
 file stores a sage: nothing is read, written or created).  The row partition is dist_sage.dist_sage (a sage_layer per rank
@@ -37,6 +47,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import ops
+from .edge_sample import refuse_sampling, sampling_option
 from .gcn import (check_loss, check_norm, layer_norm, layer_params, linear, model_base, sigmoid_bce_loss,
                   softmax_cross_entropy_loss, sparse_linear)
 from .matrix import context, csr_matrix, dn_matrix
@@ -62,23 +73,30 @@ class max_aggregate:
     ``keep_arg=False`` (a layer without an input gradient) stores no selection and has no backward.  ``arg`` [rows x width],
     uint32 bits in an int32 dn_matrix, is made with the first call; ``launches`` counts the forward calls."""
 
+    sample = None               # (F, F_T) of this forward where the model drew an edge sample (edge_sample.py); None: the full graph
+
     def __init__(self, name: str, F: csr_matrix, F_T: Optional[csr_matrix], keep_arg: bool = True):
         self.name, self.F, self.F_T, self.keep_arg = name, F, F_T, bool(keep_arg)
         self.arg: Optional[dn_matrix] = None
         self.launches = 0
+
+    def _matrices(self):
+        """(F, F_T) the most recent forward walked and its backward walks.  A sample keeps the entry order of the matrix it was
+        drawn from and duplicates share their bit, so equal indices of a sampled row of F_T stay adjacent."""
+        return self.sample if self.sample is not None else (self.F, self.F_T)
 
     def __call__(self, ctx: context, B: dn_matrix, M: dn_matrix, discard: bool = True, flags: int = 0) -> None:
         if not discard or flags:
             raise ValueError("max_aggregate: the forward overwrites its output and has no epilogue")
         if self.keep_arg and (self.arg is None or self.arg.shape() != M.shape()):
             self.arg = dn_matrix(M.n(), M.m(), dtype=np.int32, device=ctx.device)
-        ops.agg_max_forward(ctx, self.F, B, M, self.arg if self.keep_arg else None, timer=self.name + "0_agg-max")
+        ops.agg_max_forward(ctx, self._matrices()[0], B, M, self.arg if self.keep_arg else None, timer=self.name + "0_agg-max")
         self.launches += 1
 
     def backward(self, ctx: context, G_M: dn_matrix, G_B: dn_matrix, discard: bool = True) -> None:
         if self.arg is None:
             raise ValueError("max_aggregate: no forward has stored a selection (keep_arg=False, or none has run)")
-        ops.agg_max_backward(ctx, self.F_T, self.arg, G_M, G_B, accumulate=not discard, timer=self.name + "1_agg-max")
+        ops.agg_max_backward(ctx, self._matrices()[1], self.arg, G_M, G_B, accumulate=not discard, timer=self.name + "1_agg-max")
 
 
 class counted_sparse_linear(sparse_linear):
@@ -114,6 +132,8 @@ class sage_layer(layer_params):
         self.Y = dn_matrix(rows, out)
         self.M: Optional[dn_matrix] = None if first else dn_matrix(rows, in_)
         self._M_key = None
+        self._M_sampled: Optional[dn_matrix] = None     # layer 0's aggregate over an edge sample: never the kept agg(X)
+        self._M_used: Optional[dn_matrix] = None        # what the most recent forward handed to lin, for its backward
         self.G_M = None if first else dn_matrix(rows, in_, G_M_buffer)
         self.G_out = None if first else dn_matrix(rows, in_)
         self.H: Optional[dn_matrix] = None
@@ -143,7 +163,14 @@ class sage_layer(layer_params):
             # activation only, which a positive scale keeps, and a dropped element carries a zero gradient either way.
             self._drop(ctx, H, "0")
         self.H = H
-        if self.first:
+        if self.first and getattr(self.agg, "sample", None) is not None:
+            # a sampled training forward: the aggregate is this epoch's, in a buffer of its own -- the kept agg(X) of the full
+            # graph is neither read nor written.  No arg: layer 0 has no input gradient, its backward reads M alone.
+            if self._M_sampled is None or self._M_sampled.shape() != (self.Y.n(), H.m()):
+                self._M_sampled = dn_matrix(self.Y.n(), H.m())
+            self.agg(ctx, H, self._M_sampled)
+            self._M_used = self._M_sampled
+        elif self.first:
             # loop-invariant: the features are never dropped.  An IN-PLACE change of X is not visible in the key:
             # reset_input_cache() drops the product.
             key = (H.buffer(), H.n(), H.m(), self._matrix_version())
@@ -151,9 +178,11 @@ class sage_layer(layer_params):
                 self.M = dn_matrix(self.Y.n(), H.m())
                 self.agg(ctx, H, self.M)
                 self._M_key = key
+            self._M_used = self.M
         else:
             self.agg(ctx, H, self.M)
-        self.lin(ctx, self.M, self.Y)
+            self._M_used = self.M
+        self.lin(ctx, self._M_used, self.Y)
         self.res_lin(ctx, H, self.Y, False)
         if self.norm is not None:
             self.norm(ctx, self.Y, True)
@@ -176,7 +205,7 @@ class sage_layer(layer_params):
             ctx.record(n + "1_1_activation", 0)
             ctx.register_timer(n + "1_activation", n + "1_0_activation", n + "1_1_activation")
             T = self.Y
-        self.lin.setX(self.M)
+        self.lin.setX(self._M_used)
         self.lin.backward(ctx, T, self.G_M)
         if not self.first and hasattr(self.agg, "start_backward"):
             # an aggregator that exchanges G_M (dist_sage.dist_max_aggregate): the collective runs under the GEMMs below
@@ -200,14 +229,16 @@ class sage_layer(layer_params):
     def b_root(self): return self.res_lin.get_b()
 
 
-class sage(model_base):
-    """sage(A, sizes, aggr="mean", loss="softmax", fused=True, weights=None, dropout=0.0, norm=None): see the module's text.
+class sage(sampling_option, model_base):
+    """sage(A, sizes, aggr="mean", loss="softmax", fused=True, weights=None, dropout=0.0, norm=None, fanout=None, edge_keep=1.0):
+    see the module's text.
     ``A`` is taken as gcn takes it (the forward aggregates over the rows of A.transpose()); ``weights``: (W_l, b_l, W_r, b_r)
     per layer."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], aggr: str = "mean", loss: str = "softmax", fused: bool = True,
-                 weights=None, dropout: float = 0.0, norm=None):
+                 weights=None, dropout: float = 0.0, norm=None, fanout=None, edge_keep: float = 1.0):
         self.aggr = check_aggr(aggr)                         # option checks come before any device work
+        self._init_sampling(fanout, edge_keep)               # refuses aggr="mean" with sampling on
         if A.n() != A.m():
             raise ValueError(f"A must be square, got {A.n()} x {A.m()}")
         self._init_dropout(dropout, len(sizes) - 1)
@@ -247,6 +278,8 @@ class sage(model_base):
             self.layers_.append(sage_layer(name, agg, n, self.sizes[l], self.sizes[l + 1], l + 1 < n_layers, l == 0,
                                            self.G_M_buffer, self.norm))
         self._adam = None
+        if self.aggr == "max":
+            self._make_sampler(self.A_T, self._A_sorted)         # nothing unless sampling is on
         if weights is not None:
             if len(weights) != n_layers or any(len(w) != 4 for w in weights):
                 raise ValueError(f"weights must be (W_l, b_l, W_r, b_r) for each of the {n_layers} layers")
@@ -260,7 +293,14 @@ class sage(model_base):
         if self._plan_wants:                          # first call: the context (device) is known now
             ops.prebuild_plans(ctx, self._plan_wants)
             self._plan_wants = []
+        pair = self._draw_sample(ctx, training)              # one sample per epoch, shared by all layers; None: the full graph
+        for layer in self.layers_:
+            layer.agg.sample = pair
         return model_base.__call__(self, ctx, H, training)
+
+    def _refuse_sampling(self, fanout, keep) -> None:
+        if self.aggr != "max":
+            refuse_sampling(f'sage(aggr="{self.aggr}")', fanout, keep)
 
     def reset_input_cache(self) -> None:
         """drops layer 0's kept aggregate agg(X): the next forward computes it again"""

@@ -27,8 +27,9 @@ class model_selector:
     clean=True runs one extra plain forward and one loss-layer call after the update (no backward) and monitors that:
     ``history[e]`` speaks of the parameters epoch e ended with, snapshotted when the number improved.  The extra forward
     is not a training forward: it draws no mask and spends no dropout epoch.  split_metrics() of the model then reports
-    the clean pass.  The default is clean = (dropout_p > 0 or attn_dropout_p > 0): with either dropout on, the training
-    forward's validation numbers are the dropped forward's and a model must not be selected on them.
+    the clean pass.  The default is clean = (dropout_p > 0 or attn_dropout_p > 0 or edge sampling on): with a dropout on, the
+    training forward's validation numbers are the dropped forward's, with edge sampling (set_sampling) they are the sampled
+    graph's, and a model must not be selected on either: the clean pass runs on the full graph.
 
     "Improved" is strict -- lower loss, higher score; the first best epoch wins a tie; a NaN never improves.
     ``stop`` turns true once ``patience`` epochs have passed without improvement."""
@@ -48,7 +49,8 @@ class model_selector:
             raise ValueError(f"no vertex belongs to the {split} split: nothing to select on")
         self.model, self.split, self.metric = model, split, metric
         self.patience = None if patience is None else int(patience)
-        dropping = model.dropout_p > 0.0 or getattr(model, "attn_dropout_p", 0.0) > 0.0
+        dropping = (model.dropout_p > 0.0 or getattr(model, "attn_dropout_p", 0.0) > 0.0
+                    or getattr(model, "sampler", None) is not None)         # edge sampling: validate on the full graph
         self.clean = bool(dropping) if clean is None else bool(clean)
         self.history: List[float] = []
         self.best_epoch: Optional[int] = None
