@@ -849,6 +849,61 @@ void mggcn_edge_sample_scan_u32(mggcn_stream_t stream, const uint32_t *counts, s
 void mggcn_edge_sample_compact_u32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr, const uint32_t *indices,
                                    const uint32_t *thr, int transposed, uint32_t row0, uint32_t col0, uint64_t seed,
                                    uint32_t epoch, const uint32_t *out_indptr, uint32_t *out_indices);
+/* The sample WITH VALUES, for the weighted sums of gcn / sage(aggr="mean") (edge_rescale=).  The keep bit is the one above
+ * (same counter, same domain word, same self-loop rule); a kept entry's value is multiplied by a factor of its DESTINATION,
+ * read from one array by both sides, so the samples of F and of F^T hold the same pairs with the same value bits.
+ *   rowscale     over F only (rows are destinations; row0 / col0 as in count): counts[r] with count's bits and
+ *                scale[r] = S_r / S'_r, S_r the sum of the row's values and S'_r the sum over its kept entries, both summed in
+ *                one walk and one fixed order (lane l adds entries l, l + 64, ...; one butterfly folds the lanes).  S'_r == 0
+ *                gives 0 (never a NaN), a row kept whole exactly 1.  One wave per row; no atomics, no scratch; the result
+ *                does not depend on the grid or on a split of the rows between calls.
+ *   compact_val  compact, and beside the kept columns out_values = value * scale[destination]: scale[r] when transposed = 0,
+ *                scale[c] (gathered) when transposed = 1, NULL = no factor; one fp32 multiply, skipped for i == j when
+ *                scale_self == 0.  Nothing is written at or beyond out_indptr[r + 1] in either output.  out_values must not
+ *                alias values. */
+void mggcn_edge_sample_rowscale_f32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr, const uint32_t *indices,
+                                    const float *values, const uint32_t *thr, uint32_t row0, uint32_t col0, uint64_t seed,
+                                    uint32_t epoch, uint32_t *counts, float *scale);
+void mggcn_edge_sample_compact_val_f32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr, const uint32_t *indices,
+                                       const float *values, const uint32_t *thr, int transposed, uint32_t row0, uint32_t col0,
+                                       uint64_t seed, uint32_t epoch, const float *scale, int scale_self,
+                                       const uint32_t *out_indptr, uint32_t *out_indices, float *out_values);
+
+/* The row-split SpMM over a device-resident CSR with a plan built ON THE DEVICE (csrc/spmm_dev.hip): what multiplies by the
+ * edge sample above, a matrix the host never sees.
+ *   capacity   out3 = (work items, partial-sum slots, split rows) of the row-split rule on a HOST indptr: a row of
+ *              len <= split + split / 2 entries is one item, a longer one ceil(len / split) slices.  The rule is monotone in the
+ *              row length, so the PARENT's three counts bound those of every sample of it.  split == 0: MGGCN_SPMM_SPLIT
+ *              (default 512); the floor is 64.  Host only.
+ *   create     allocates the tables, the partial sums (slots x max_d floats) and the builder's work space at the parent's
+ *              capacity; nothing is built.  destroy / bytes; describe: out5 = (the three capacities, split, max_d).
+ *   build      enqueue-only, no host read: per row the split flag and slice count, two exclusive scans
+ *              (mggcn_edge_sample_scan_u32), then the item and split-row tables in ROW order with the host builder's slice
+ *              boundaries (beg + len k / parts in 64-bit) and the three totals in device memory.  The host builder's
+ *              longest-first order is not reproduced.  Nothing at or beyond a table's capacity is written.  The plan holds
+ *              the row bounds of `indptr_dev` as they are at the build: build again after the matrix changes.
+ *   read       tests and reports: synchronises and copies out the whole tables (capacity x 4 words each; NULL skips one) and
+ *              the three totals (items, slots, split rows).
+ *   csr_dev    C = alpha A B + beta C with the contract of mggcn_spmm_csr_f32 / _bf16 (flags, leading dimensions, the vector
+ *              and the scalar path) over the built plan: launch geometry from the capacities, true counts from device memory.
+ *              A row is cut and summed exactly as a host row-split plan of the same split cuts and sums it: the same bits.
+ *              No atomics; the same bits on every call. */
+typedef struct mggcn_spmm_dev_plan mggcn_spmm_dev_plan;
+void mggcn_spmm_dev_plan_capacity(uint32_t n_rows, const uint32_t *host_parent_indptr, uint32_t split, uint32_t *out3);
+mggcn_spmm_dev_plan *mggcn_spmm_dev_plan_create(uint32_t n_rows, const uint32_t *host_parent_indptr, uint32_t max_d,
+                                                uint32_t split);
+void mggcn_spmm_dev_plan_destroy(mggcn_spmm_dev_plan *plan);
+size_t mggcn_spmm_dev_plan_bytes(const mggcn_spmm_dev_plan *plan);
+void mggcn_spmm_dev_plan_describe(const mggcn_spmm_dev_plan *plan, uint32_t *out5);
+void mggcn_spmm_dev_plan_build(mggcn_stream_t stream, mggcn_spmm_dev_plan *plan, const uint32_t *indptr_dev);
+void mggcn_spmm_dev_plan_read(const mggcn_spmm_dev_plan *plan, uint32_t *host_items, uint32_t *host_split_rows,
+                              uint32_t *host_totals);
+void mggcn_spmm_csr_dev_f32(mggcn_stream_t stream, const mggcn_spmm_dev_plan *plan, uint32_t n_rows, uint32_t n_cols,
+                            const uint32_t *indptr, const uint32_t *indices, const float *values, const float *B, size_t ldb,
+                            float *C, size_t ldc, uint32_t d, float alpha, float beta, uint32_t flags, float slope);
+void mggcn_spmm_csr_dev_bf16(mggcn_stream_t stream, const mggcn_spmm_dev_plan *plan, uint32_t n_rows, uint32_t n_cols,
+                             const uint32_t *indptr, const uint32_t *indices, const float *values, const uint16_t *B, size_t ldb,
+                             float *C, size_t ldc, uint32_t d, float alpha, float beta, uint32_t flags, float slope);
 /* cublasSasum(src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

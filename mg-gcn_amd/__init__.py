@@ -20,7 +20,9 @@ Layout:
   sage.py      max_aggregate / sage_layer / sage: GraphSAGE with the mean (gcn's SpMM) or the max aggregator (csrc/agg_max.hip;
                no reference counterpart)
   edge_sample.py thresholds / sampled_csr / edge_sampler / sampling_option: the per-epoch edge sample of gat and sage(aggr="max"),
-               drawn on the device (csrc/edge_sample.hip; no reference counterpart)
+               drawn on the device (csrc/edge_sample.hip; no reference counterpart); rescaled_sampling_option: the sample
+               with rescaled values of gcn and sage(aggr="mean") (edge_rescale=), multiplied by the row-split SpMM on a plan
+               built on the device (csrc/spmm_dev.hip)
   label_mask.py  the host's restatement of the label-input mask: its count per epoch, without a synchronisation
   dist.py      1D row partition, one process per GPU    (reference src/dist_matrix.hpp, gcn.hpp dist_*); dist_model_base:
                the epoch dist_gcn and dist_gat share

@@ -175,6 +175,20 @@ PROTOTYPES = {
     "mggcn_edge_sample_scan_u32": (None, [vp, vp, c_size_t, vp]),
     "mggcn_edge_sample_compact_u32": (None, [vp, c_uint32, vp, vp, vp, c_int, c_uint32, c_uint32, c_uint64, c_uint32, vp,
                                              vp]),
+    "mggcn_edge_sample_rowscale_f32": (None, [vp, c_uint32, vp, vp, vp, vp, c_uint32, c_uint32, c_uint64, c_uint32, vp, vp]),
+    "mggcn_edge_sample_compact_val_f32": (None, [vp, c_uint32, vp, vp, vp, vp, c_int, c_uint32, c_uint32, c_uint64, c_uint32,
+                                                 vp, c_int, vp, vp, vp]),
+    "mggcn_spmm_dev_plan_capacity": (None, [c_uint32, vp, c_uint32, vp]),
+    "mggcn_spmm_dev_plan_create": (vp, [c_uint32, vp, c_uint32, c_uint32]),
+    "mggcn_spmm_dev_plan_destroy": (None, [vp]),
+    "mggcn_spmm_dev_plan_bytes": (c_size_t, [vp]),
+    "mggcn_spmm_dev_plan_describe": (None, [vp, vp]),
+    "mggcn_spmm_dev_plan_build": (None, [vp, vp, vp]),
+    "mggcn_spmm_dev_plan_read": (None, [vp, vp, vp, vp]),
+    "mggcn_spmm_csr_dev_f32": (None, [vp, vp, c_uint32, c_uint32, vp, vp, vp, vp, c_size_t, vp, c_size_t,
+                                      c_uint32, c_float, c_float, c_uint32, c_float]),
+    "mggcn_spmm_csr_dev_bf16": (None, [vp, vp, c_uint32, c_uint32, vp, vp, vp, vp, c_size_t, vp, c_size_t,
+                                       c_uint32, c_float, c_float, c_uint32, c_float]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),
     "mggcn_gather_rows_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_softmax_xent_fused_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_float, vp]),

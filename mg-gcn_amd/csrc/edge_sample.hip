@@ -14,6 +14,14 @@
 //             count of the lanes below it, and a running base per row carries from chunk to chunk.  Kept columns land in
 //             their original order at out_indices + out_indptr[row]; a store at or beyond out_indptr[row + 1] is never issued.
 // No atomics, no LDS outside the scan, no scratch; the output does not depend on the grid.
+//
+// The sample WITH VALUES (gcn / sage(aggr="mean") with edge_rescale=): the same keep bit, and beside the kept columns the kept
+// values times a factor per DESTINATION -- one array that both sides read (scale[row] on F, gathered scale[column] on F^T), so
+// the two samples hold the same pairs with the same value bits.
+//   rowscale     the count kernel's walk over F with two fp32 sums riding along: S over the row's values, S' over the kept ones,
+//                both lane by lane over entries l, l + 64, ... and then through one fixed butterfly; scale = S / S' (0 where
+//                S' == 0, exactly 1 where every entry is kept: the two sums are then the same additions).
+//   compact_val  compact, storing value * scale[destination] (one fp32 multiply; skipped for i == j when scale_self == 0).
 #include <algorithm>
 
 #include "common.h"
@@ -86,6 +94,80 @@ __global__ __launch_bounds__(256) void edge_sample_compact_kernel(uint32_t n_row
         const uint64_t bits = __ballot(keep);
         const size_t at = base + (size_t)__popcll(bits & below);
         if (keep && at < out_end) out_indices[at] = c;              // the bound holds by construction: count drew the same bits
+        base += (size_t)__popcll(bits);
+    }
+}
+
+__device__ __forceinline__ float wave_sum_f32(float v) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);   // a + b == b + a: every lane ends with the same bits
+    return v;
+}
+
+// the count kernel's walk over F (rows are destinations) with the row's value sums: one wave per row, four rows per workgroup
+__global__ __launch_bounds__(256) void edge_sample_rowscale_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                                   const uint32_t *__restrict__ indices,
+                                                                   const float *__restrict__ values, sample_draw draw,
+                                                                   uint32_t *__restrict__ counts, float *__restrict__ scale) {
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    const uint32_t t_row = draw.row_threshold(row);
+    uint32_t kept = 0;
+    float all = 0.f, sub = 0.f;
+    for (size_t e = (size_t)beg + lane; e < end; e += 64) {
+        const bool keep = draw.keep(row, indices[e], t_row);
+        const float v = values[e];
+        kept += keep ? 1u : 0u;
+        all += v;
+        sub += keep ? v : 0.f;
+    }
+    kept = wave_sum_u32(kept);
+    all = wave_sum_f32(all);
+    sub = wave_sum_f32(sub);
+    if (lane == 0) {
+        counts[row] = kept;
+        scale[row] = sub == 0.f ? 0.f : (kept == end - beg ? 1.f : all / sub);
+    }
+}
+
+__global__ __launch_bounds__(256) void edge_sample_compact_val_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,
+                                                                      const uint32_t *__restrict__ indices,
+                                                                      const float *__restrict__ values, sample_draw draw,
+                                                                      const float *__restrict__ scale, bool scale_self,
+                                                                      const uint32_t *__restrict__ out_indptr,
+                                                                      uint32_t *__restrict__ out_indices,
+                                                                      float *__restrict__ out_values) {
+    const uint32_t lane = threadIdx.x & 63;
+    const size_t row = (size_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (row >= n_rows) return;
+    const uint32_t beg = indptr[row], end = indptr[row + 1];
+    const uint32_t t_row = draw.row_threshold(row);
+    const float f_row = (scale != nullptr && !draw.transposed) ? scale[row] : 1.f;
+    const uint64_t below = ((uint64_t)1 << lane) - 1;
+    size_t base = out_indptr[row];
+    const size_t out_end = out_indptr[row + 1];
+    for (size_t chunk = beg; chunk < end; chunk += 64) {            // wave-uniform trip count: the ballot wants every lane
+        const size_t e = chunk + lane;
+        uint32_t c = 0;
+        float v = 0.f;
+        bool keep = false;
+        if (e < end) {
+            c = indices[e];
+            keep = draw.keep(row, c, t_row);
+        }
+        if (keep) {
+            v = values[e];
+            const bool self = draw.row0 + (uint32_t)row == draw.col0 + c;
+            if (scale != nullptr && (scale_self || !self)) v *= draw.transposed ? scale[c] : f_row;
+        }
+        const uint64_t bits = __ballot(keep);
+        const size_t at = base + (size_t)__popcll(bits & below);
+        if (keep && at < out_end) {                                 // the bound holds by construction: count drew the same bits
+            out_indices[at] = c;
+            out_values[at] = v;
+        }
         base += (size_t)__popcll(bits);
     }
 }
@@ -186,5 +268,33 @@ MGGCN_API void mggcn_edge_sample_compact_u32(mggcn_stream_t stream, uint32_t n_r
                   "edge sample compact: out_indices must not alias indices");
     hipLaunchKernelGGL(edge_sample_compact_kernel, dim3((unsigned)(((size_t)n_rows + 3) / 4)), dim3(256), 0, as_stream(stream), n_rows, indptr,
                        indices, make_draw(thr, transposed, row0, col0, seed, epoch), out_indptr, out_indices);
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_edge_sample_rowscale_f32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr,
+                                              const uint32_t *indices, const float *values, const uint32_t *thr, uint32_t row0,
+                                              uint32_t col0, uint64_t seed, uint32_t epoch, uint32_t *counts, float *scale) {
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && thr != nullptr && counts != nullptr && scale != nullptr, "edge sample rowscale: null operand");
+    hipLaunchKernelGGL(edge_sample_rowscale_kernel, dim3((unsigned)(((size_t)n_rows + 3) / 4)), dim3(256), 0, as_stream(stream), n_rows,
+                       indptr, indices, values, make_draw(thr, 0, row0, col0, seed, epoch), counts, scale);
+    MGGCN_CHECK_LAUNCH();
+}
+
+MGGCN_API void mggcn_edge_sample_compact_val_f32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr,
+                                                 const uint32_t *indices, const float *values, const uint32_t *thr, int transposed,
+                                                 uint32_t row0, uint32_t col0, uint64_t seed, uint32_t epoch, const float *scale,
+                                                 int scale_self, const uint32_t *out_indptr, uint32_t *out_indices,
+                                                 float *out_values) {
+    MGGCN_REQUIRE(transposed == 0 || transposed == 1, "edge sample compact: transposed must be 0 or 1");
+    if (!n_rows) return;
+    MGGCN_REQUIRE(indptr != nullptr && thr != nullptr && out_indptr != nullptr, "edge sample compact: null operand");
+    MGGCN_REQUIRE((const void *)out_indices != (const void *)indices || indices == nullptr,
+                  "edge sample compact: out_indices must not alias indices");
+    MGGCN_REQUIRE((const void *)out_values != (const void *)values || values == nullptr,
+                  "edge sample compact: out_values must not alias values");
+    hipLaunchKernelGGL(edge_sample_compact_val_kernel, dim3((unsigned)(((size_t)n_rows + 3) / 4)), dim3(256), 0, as_stream(stream),
+                       n_rows, indptr, indices, values, make_draw(thr, transposed, row0, col0, seed, epoch), scale, scale_self != 0,
+                       out_indptr, out_indices, out_values);
     MGGCN_CHECK_LAUNCH();
 }

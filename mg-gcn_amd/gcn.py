@@ -34,7 +34,7 @@ import numpy as np
 
 from . import ops
 from .checkpoint import checkpoint_option
-from .edge_sample import refuse_sampling
+from .edge_sample import refuse_sampling, rescaled_sampling_option, sampling_on
 from .matrix import context, csr_matrix, dn_matrix, host_scalars
 
 MGGCN_SPMM_LEAKY_RELU = 1
@@ -115,7 +115,13 @@ class dropout_option:
 
 
 class sparse_linear:
-    """reference src/gcn.hpp:13-48: holds (A, A_T); forward SpMM with A, backward with A_T."""
+    """reference src/gcn.hpp:13-48: holds (A, A_T); forward SpMM with A, backward with A_T.
+
+    ``sample``: the pair (sample of A, sample of A_T) of this forward where the model drew an edge sample with values
+    (edge_sample.py), as max_aggregate has it; None: the full graph.  With a sample the forward and the backward multiply by it
+    through ops.spmm_dev on the plan built with the draw -- no host plan is looked up, made or touched."""
+
+    sample = None
 
     def __init__(self, name: str, A: csr_matrix, A_T: csr_matrix, agg_dtype: str = "f32", agg_buffer=None):
         self.name, self.A, self.A_T = name, A, A_T
@@ -137,27 +143,51 @@ class sparse_linear:
         ops.convert_bf16(ctx, B, B16)
         ops.spmm_bf16(ctx, M, B16, C, plan, 1.0, beta, flags)
 
+    def _spmm_sampled(self, ctx: context, S, B: dn_matrix, C: dn_matrix, beta: float, flags: int) -> None:
+        """_spmm over the sampled matrix ``S`` (edge_sample.sampled_csr with values and a built device plan)"""
+        if self.agg_dtype != "f32":
+            torch = _torch()
+            need = B.n() * B.m()
+            if self.agg_buffer is None or self.agg_buffer.numel() < need:
+                self.agg_buffer = torch.empty(need, dtype=torch.bfloat16, device=ctx.device)
+            B16 = self.agg_buffer[:need].view(B.n(), B.m())
+            ops.convert_bf16(ctx, B, B16)
+            B = B16
+        ops.spmm_dev(ctx, S, B, C, S.plan, 1.0, beta, flags)
+
     def __call__(self, ctx: context, B: dn_matrix, C: dn_matrix, discard: bool = True, flags: int = 0) -> None:
+        n = self.name
+        if self.sample is not None:
+            ctx.record(n + "0_0_matmul-spmm", 0)
+            self._spmm_sampled(ctx, self.sample[0], B, C, 0.0 if discard else 1.0, flags)
+            ctx.record(n + "0_1_matmul-spmm", 0)
+            ctx.register_timer(n + "0_matmul-spmm", n + "0_0_matmul-spmm", n + "0_1_matmul-spmm")
+            return
         if B.m() != self.M:                                   # workspace cached per width, gcn.hpp:28-31
             self.M = B.m()
             if self.ext_buffer is None or B.m() > self._max_d[0]:
                 self._max_d[0] = max(B.m(), self._max_d[0])
                 self.ext_buffer = ops.get_matmul_buffer(ctx, self.A, B, C, 1.0, 0.0 if discard else 1.0,
                                                         max_d=self._max_d[0])
-        n = self.name
         ctx.record(n + "0_0_matmul-spmm", 0)
         self._spmm(ctx, self.A, B, C, self.ext_buffer, 0.0 if discard else 1.0, flags)
         ctx.record(n + "0_1_matmul-spmm", 0)
         ctx.register_timer(n + "0_matmul-spmm", n + "0_0_matmul-spmm", n + "0_1_matmul-spmm")
 
     def backward(self, ctx: context, G: dn_matrix, G_out: dn_matrix, discard: bool = True) -> None:
+        n = self.name
+        if self.sample is not None:
+            ctx.record(n + "1_0_matmul-spmm", 0)
+            self._spmm_sampled(ctx, self.sample[1], G, G_out, 0.0 if discard else 1.0, 0)
+            ctx.record(n + "1_1_matmul-spmm", 0)
+            ctx.register_timer(n + "1_matmul-spmm", n + "1_0_matmul-spmm", n + "1_1_matmul-spmm")
+            return
         if G.m() != self.M2:
             self.M2 = G.m()
             if self.ext_buffer2 is None or G.m() > self._max_d[1]:
                 self._max_d[1] = max(G.m(), self._max_d[1])
                 self.ext_buffer2 = ops.get_matmul_buffer(ctx, self.A_T, G, G_out, 1.0, 0.0 if discard else 1.0,
                                                          max_d=self._max_d[1])
-        n = self.name
         ctx.record(n + "1_0_matmul-spmm", 0)
         self._spmm(ctx, self.A_T, G, G_out, self.ext_buffer2, 0.0 if discard else 1.0, 0)
         ctx.record(n + "1_1_matmul-spmm", 0)
@@ -1041,7 +1071,7 @@ class model_base(dropout_option, checkpoint_option):
         return res
 
 
-class gcn(model_base):
+class gcn(rescaled_sampling_option, model_base):
     """reference src/gcn.hpp:937-995.  The constructor column-normalises A, builds
     A_T and hands (A_T, A) to the layers -- forward multiplies by A_T (:946-955).
 
@@ -1055,15 +1085,20 @@ class gcn(model_base):
     save(ctx, path, optimizer=True) / load(ctx, path) / predict(ctx, X): see checkpoint.checkpoint_option -- the file
     carries the configuration, the parameters, Adam's state and the dropout state, and no execution option.
 
-    ``fanout`` / ``edge_keep`` / set_sampling: per-epoch edge sampling (edge_sample.py) is REFUSED here with ValueError naming
-    the argument -- the sweep SpMM's plan is built on the host from host arrays and carries the values; gat and
-    sage(aggr="max") have it."""
+    ``fanout`` / ``edge_keep`` / ``edge_rescale`` / set_sampling(fanout, keep, seed, epoch, rescale): per-epoch edge sampling
+    (edge_sample.py).  gcn is a weighted sum, so it samples only when told how the kept values are rescaled: with
+    ``edge_rescale`` None (the default) any setting that is on is refused with ValueError naming the argument; "row" keeps every
+    row sum (the mean over the sampled neighbours on the row-stochastic matrix built here), "inverse" divides by the keep
+    probability.  A training forward then multiplies, forward and backward, by the pair of the epoch through the row-split SpMM
+    on a plan built on the device (sparse_linear.sample, ops.spmm_dev); every other forward runs on the full graph with the
+    bits it has without sampling.  hoist_first_aggregation does not compose: the hoisted product belongs to the full graph."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], residual_layer: bool = False,
                  weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None, fused: bool = True,
                  hoist_first_aggregation: bool = False, agg_dtype: str = "f32", dropout: float = 0.0, norm=None,
-                 loss: str = "softmax", fanout=None, edge_keep: float = 1.0):
-        refuse_sampling("gcn", fanout, edge_keep)            # option checks come before any device work
+                 loss: str = "softmax", fanout=None, edge_keep: float = 1.0, edge_rescale=None):
+        self.hoist_first_aggregation = bool(hoist_first_aggregation)
+        self._init_sampling(fanout, edge_keep, edge_rescale)     # option checks come before any device work
         self._init_dropout(dropout, len(sizes) - 1)
         self.norm = check_norm(norm)
         self.loss = check_loss(loss)
@@ -1093,6 +1128,10 @@ class gcn(model_base):
         link_fused_backward(self.layers_, fused)
         self._adam = None
         self.set_hoist_first_aggregation(hoist_first_aggregation)
+        self._sample_max_d = int(max_d)
+        self._sample_matrices = (A_T, A)
+        if sampling_on(self.sample_fanout, self.sample_keep):
+            self._make_sampler(A_T, A)                           # forward multiplies by A_T: its rows are the destinations
         self._plan_wants = []                        # (matrix, max_d, width): built side by side on first use (prebuild_plans)
         for i in range(1, len(sizes)):
             w = min(sizes[i - 1], sizes[i])
@@ -1112,6 +1151,10 @@ class gcn(model_base):
         if on and self.agg_dtype != "f32":
             raise ValueError("hoist_first_aggregation is fp32-only: with agg_dtype='bf16' the hoisted product would "
                              "round X instead of X W")
+        if on and sampling_on(self.sample_fanout, self.sample_keep):
+            raise ValueError("hoist_first_aggregation does not compose with edge sampling (fanout / edge_keep / set_sampling): "
+                             "the hoisted product belongs to the full graph")
+        self.hoist_first_aggregation = bool(on)
         l0 = self.layers_[0]
         # A_fwd (1 b^T) = 1 b^T needs EVERY row of A_fwd to sum to one: a vertex without a single entry in its row of
         # A_fwd (no self-loop, nobody points at it) has row sum 0 and would get 0 instead of b -- the reference's data-prep
@@ -1125,12 +1168,20 @@ class gcn(model_base):
         if self._plan_wants:                          # first call: the context (device) is known now
             ops.prebuild_plans(ctx, self._plan_wants)
             self._plan_wants = []
+        if self.sampler is not None or self.layers_[0].A.sample is not None:
+            pair = self._draw_sample(ctx, training)          # one sample per epoch, shared by all layers; None: the full graph
+            for layer in self.layers_:
+                layer.A.sample = pair
         return model_base.__call__(self, ctx, H, training)
 
-    def set_sampling(self, fanout=None, keep: float = 1.0, seed: int = 0, epoch: int = 0) -> None:
-        """gcn has no edge sampling (edge_sample.refuse_sampling): ValueError naming the argument for any setting that is on
-        or out of range; fanout=None, keep=1.0 is accepted and changes nothing"""
-        refuse_sampling("gcn", fanout, keep)
+    hoist_first_aggregation = False
+
+    def _refuse_sampling(self, fanout, keep) -> None:
+        if self._rescale_checked() is None:
+            refuse_sampling("gcn", fanout, keep)
+        if self.hoist_first_aggregation:
+            raise ValueError("gcn(hoist_first_aggregation=True) has no edge sampling (fanout / edge_keep / set_sampling): the "
+                             "hoisted product belongs to the full graph")
 
     def update(self, ctx: context, lr: float, weight_decay: float) -> None:
         for layer in self.layers_:

@@ -1347,6 +1347,150 @@ def edge_sample_compact(ctx: context, n_rows: int, indptr, indices, thr, transpo
                                                                          out_indices.data_ptr()))
 
 
+def _req_f32(t, least: int, what: str) -> None:
+    """a contiguous fp32 device tensor of at least ``least`` elements"""
+    _req(hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous() and t.element_size() == 4
+         and t.dtype.is_floating_point and t.numel() >= least,
+         f"{what} must be a contiguous fp32 device tensor of at least {least} elements")
+
+
+def edge_sample_rowscale(ctx: context, n_rows: int, indptr, indices, values, thr, counts, scale, row0: int = 0, col0: int = 0,
+                         seed: int = 0, epoch: int = 0, timer: Optional[str] = None) -> None:
+    """edge_sample_count over a forward matrix WITH values (rows are destinations; mggcn_edge_sample_rowscale_f32): counts[r]
+    with count's bits and scale[r] = (the sum of row r's values) / (the sum over its kept entries) -- 0 where nothing of value
+    is kept, exactly 1 where the row is kept whole.  values: fp32, indexed like indices."""
+    what = "edge sample rowscale"
+    args = _edge_sample_args(what, n_rows, indptr, indices, thr, 0, row0, col0, seed, epoch)
+    _req_f32(values, 0, f"{what}: values")
+    _req(values.numel() >= indices.numel(), f"{what}: values must cover indices")
+    _req_u32(counts, n_rows, f"{what}: counts")
+    _req_f32(scale, n_rows, f"{what}: scale")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_edge_sample_rowscale_f32(
+        ctx.stream(0), *args[:3], values.data_ptr(), args[3], *args[5:], counts.data_ptr(), scale.data_ptr()))
+
+
+def edge_sample_compact_val(ctx: context, n_rows: int, indptr, indices, values, thr, transposed, scale, scale_self, out_indptr,
+                            out_indices, out_values, row0: int = 0, col0: int = 0, seed: int = 0, epoch: int = 0,
+                            timer: Optional[str] = None) -> None:
+    """edge_sample_compact with values (mggcn_edge_sample_compact_val_f32): beside the kept columns, out_values = value *
+    scale[destination] -- scale[r] when the rows are destinations, scale[c] when ``transposed``; None: no factor.  ``scale_self``
+    False leaves a self-loop (global row == global column) unscaled.  One array read by both sides: the samples of F and of F^T
+    hold the same value bits."""
+    what = "edge sample compact"
+    args = _edge_sample_args(what, n_rows, indptr, indices, thr, transposed, row0, col0, seed, epoch)
+    _req_f32(values, 0, f"{what}: values")
+    _req(values.numel() >= indices.numel(), f"{what}: values must cover indices")
+    if scale is not None:
+        _req_f32(scale, 0 if transposed else n_rows, f"{what}: scale")
+    _req(scale_self in (0, 1, False, True), f"{what}: scale_self must be 0 or 1")
+    _req_u32(out_indptr, n_rows + 1, f"{what}: out_indptr")
+    _req_u32(out_indices, 0, f"{what}: out_indices")
+    _req_f32(out_values, 0, f"{what}: out_values")
+    _req(out_values.numel() >= out_indices.numel(), f"{what}: out_values must cover out_indices")
+    _req(out_indices.data_ptr() != indices.data_ptr() or indices.numel() == 0, f"{what}: out_indices must not alias indices")
+    _req(out_values.data_ptr() != values.data_ptr() or values.numel() == 0, f"{what}: out_values must not alias values")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_edge_sample_compact_val_f32(
+        ctx.stream(0), *args[:3], values.data_ptr(), *args[3:], scale.data_ptr() if scale is not None else None,
+        int(bool(scale_self)), out_indptr.data_ptr(), out_indices.data_ptr(), out_values.data_ptr()))
+
+
+# ---- the row-split SpMM on a device-built plan (csrc/spmm_dev.hip) ------------------------------------------------------------
+def spmm_dev_capacity(lib, indptr, split: int = 0):
+    """(work items, partial-sum slots, split rows) of the row-split rule on a host indptr: the capacity that holds every
+    sample of that matrix (mggcn_spmm_dev_plan_capacity; no device work).  split 0: MGGCN_SPMM_SPLIT, default 512."""
+    ip = np.ascontiguousarray(indptr, dtype=np.uint32)
+    _req(ip.ndim == 1 and ip.size >= 1, "spmm dev capacity: indptr of n_rows + 1 words")
+    _req(isinstance(split, numbers.Integral) and 0 <= split < 1 << 32, "spmm dev capacity: split must fit 32 bits")
+    out = np.zeros(3, dtype=np.uint32)
+    lib.mggcn_spmm_dev_plan_capacity(ip.size - 1, ip.ctypes.data, int(split), out.ctypes.data)
+    return tuple(int(x) for x in out)
+
+
+class spmm_dev_buffer:
+    """What spmm_dev_plan returns: the capacity of a row-split plan for every sample of one parent matrix, built on the
+    device by spmm_dev_plan_build once per draw.  ``cap_items`` / ``cap_slots`` / ``cap_split``, ``split``, ``max_d``;
+    read() -> (items [cap_items x 4], split_rows [cap_split x 4], totals [3]) as uint32 host arrays, after a synchronisation."""
+
+    def __init__(self, lib, handle: int, n_rows: int):
+        self.lib, self.handle, self.n_rows = lib, handle, int(n_rows)
+        d = np.zeros(5, dtype=np.uint32)
+        lib.mggcn_spmm_dev_plan_describe(handle, d.ctypes.data)
+        self.cap_items, self.cap_slots, self.cap_split, self.split, self.max_d = (int(x) for x in d)
+        self.built = False
+
+    def nbytes(self) -> int: return self.lib.mggcn_spmm_dev_plan_bytes(self.handle)
+
+    def read(self):
+        items = np.zeros((self.cap_items, 4), dtype=np.uint32)
+        rows = np.zeros((self.cap_split, 4), dtype=np.uint32)
+        totals = np.zeros(3, dtype=np.uint32)
+        self.lib.mggcn_spmm_dev_plan_read(self.handle, items.ctypes.data if items.size else None,
+                                          rows.ctypes.data if rows.size else None, totals.ctypes.data)
+        return items, rows, totals
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.lib.mggcn_spmm_dev_plan_destroy(self.handle)
+                self.handle = 0
+        except Exception:
+            pass
+
+
+def spmm_dev_plan(ctx: context, parent_indptr, max_d: int, split: int = 0) -> spmm_dev_buffer:
+    """capacity for the device-built row-split plan of every sample of the matrix with the HOST row pointer ``parent_indptr``
+    (mggcn_spmm_dev_plan_create); nothing is built.  max_d: the widest feature width it will multiply at."""
+    ip = np.ascontiguousarray(parent_indptr, dtype=np.uint32)
+    _req(ip.ndim == 1 and ip.size >= 1, "spmm dev plan: indptr of n_rows + 1 words")
+    _req(isinstance(max_d, numbers.Integral) and max_d >= 1, "spmm dev plan: max_d must be positive")
+    _req(isinstance(split, numbers.Integral) and 0 <= split < 1 << 32, "spmm dev plan: split must fit 32 bits")
+    ctx.set()
+    return spmm_dev_buffer(ctx.lib, ctx.lib.mggcn_spmm_dev_plan_create(ip.size - 1, ip.ctypes.data, int(max_d), int(split)),
+                           ip.size - 1)
+
+
+def spmm_dev_plan_build(ctx: context, plan: spmm_dev_buffer, indptr, timer: Optional[str] = None) -> None:
+    """builds ``plan`` for the device CSR whose row pointer is ``indptr`` (n_rows + 1 4-byte integers on the device): enqueue-only,
+    no host read (mggcn_spmm_dev_plan_build).  No row may be longer than the parent's."""
+    _req(isinstance(plan, spmm_dev_buffer) and plan.handle, "spmm dev plan build: a spmm_dev_buffer")
+    _req_u32(indptr, plan.n_rows + 1, "spmm dev plan build: indptr")
+    ctx.set()
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_spmm_dev_plan_build(ctx.stream(0), plan.handle, indptr.data_ptr()))
+    plan.built = True
+
+
+def spmm_dev(ctx: context, A, B, C: dn_matrix, plan: spmm_dev_buffer, alpha: float = 1.0, beta: float = 0.0, flags: int = 0,
+             slope: float = 0.01) -> None:
+    """C = alpha A B + beta C over a device-resident CSR with values (``A``: an edge_sample.sampled_csr, or anything with n(),
+    m() and device() -> (indptr, indices, values)) and its built device plan; B: a dn_matrix (mggcn_spmm_csr_dev_f32) or a 2-D
+    bf16 device tensor of A.m() x C.m(), any row stride (mggcn_spmm_csr_dev_bf16).  The bits of matmul with a host row-split
+    plan of the same split on the same matrix."""
+    what = "spmm dev"
+    _req(isinstance(plan, spmm_dev_buffer) and plan.handle and plan.built, f"{what}: the plan has not been built")
+    ip, ix, dv = A.device(ctx.device)
+    _req(dv is not None, f"{what}: the matrix carries no values")
+    _req(plan.n_rows == A.n() == C.n(), f"{what}: the plan was made for another matrix")
+    _req_u32(ip, A.n() + 1, f"{what}: indptr")
+    _req_u32(ix, 0, f"{what}: indices")
+    _req_f32(dv, 0, f"{what}: values")
+    if isinstance(B, dn_matrix):
+        b_ptr, bn, bm, ldb, fn = B.buffer(), B.n(), B.m(), B.m(), ctx.lib.mggcn_spmm_csr_dev_f32
+    elif hasattr(B, "element_size") and B.element_size() == 4:              # a 2-D fp32 device tensor, any row stride
+        _req(B.dim() == 2 and B.is_cuda and B.dtype.is_floating_point and (B.stride(1) == 1 or B.shape[1] <= 1),
+             f"{what} B: a dn_matrix, a 2-D fp32 device tensor or a 2-D bf16 device tensor")
+        b_ptr, bn, bm, ldb = B.data_ptr(), int(B.shape[0]), int(B.shape[1]), int(max(B.stride(0), B.shape[1]))
+        fn = ctx.lib.mggcn_spmm_csr_dev_f32
+    else:
+        b_ptr, bn, bm, ldb = _bf16_view(B, f"{what} B")
+        fn = ctx.lib.mggcn_spmm_csr_dev_bf16
+    _req(A.m() == bn and bm == C.m(), "SpMM shape mismatch")
+    _req(bm <= plan.max_d or plan.cap_slots == 0, f"{what}: feature width exceeds the plan's max_d")
+    _req(b_ptr != C.buffer(), f"{what}: C must not alias B")
+    ctx.set()
+    fn(ctx.stream(0), plan.handle, A.n(), A.m(), ip.data_ptr(), ix.data_ptr(), dv.data_ptr(), b_ptr, ldb, C.buffer(), C.m(), bm,
+       alpha, beta, flags, slope)
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""

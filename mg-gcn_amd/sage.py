@@ -29,8 +29,12 @@ backward, over the pair of the epoch; every other forward runs on the full graph
 nor writes layer 0's kept ``agg(X)``: it aggregates X over the sample into a buffer of its own every epoch (``_M_sampled``),
 and stores no ``arg`` there either -- layer 0 has no input gradient and its weight gradient reads M alone.  The sample keeps
 the entry order of the row-sorted pattern and duplicates share their bit, so equal indices of a sampled row stay adjacent,
-which the max backward needs.  ``aggr="mean"`` refuses sampling by name: the sweep SpMM's plan is built on the host from host
-arrays and carries the values.
+which the max backward needs.  ``aggr="mean"`` is a weighted sum and samples only when told how the kept values are rescaled:
+``edge_rescale="row"`` (the mean over the sampled neighbours -- the published GraphSAGE recipe) or ``"inverse"``
+(set_sampling(..., rescale=)); with ``edge_rescale`` None (the default) any setting that is on is refused by the argument's
+name.  Its training forward multiplies by the pair of the epoch through the row-split SpMM on a plan built on the device
+(sparse_linear.sample, ops.spmm_dev), layer 0 again into ``_M_sampled``.  ``aggr="max"`` reads no values and refuses
+``edge_rescale``.
 
 Refused with ValueError naming the argument, before any device work: an unknown ``aggr``, a matrix that is not square, and
 gcn's own errors for ``norm``, ``loss`` and ``dropout``; save / load / model_selector.save_best (no version of the checkpoint
@@ -47,7 +51,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 
 from . import ops
-from .edge_sample import refuse_sampling, sampling_option
+from .edge_sample import refuse_sampling, rescaled_sampling_option
 from .gcn import (check_loss, check_norm, layer_norm, layer_params, linear, model_base, sigmoid_bce_loss,
                   softmax_cross_entropy_loss, sparse_linear)
 from .matrix import context, csr_matrix, dn_matrix
@@ -229,16 +233,16 @@ class sage_layer(layer_params):
     def b_root(self): return self.res_lin.get_b()
 
 
-class sage(sampling_option, model_base):
-    """sage(A, sizes, aggr="mean", loss="softmax", fused=True, weights=None, dropout=0.0, norm=None, fanout=None, edge_keep=1.0):
-    see the module's text.
+class sage(rescaled_sampling_option, model_base):
+    """sage(A, sizes, aggr="mean", loss="softmax", fused=True, weights=None, dropout=0.0, norm=None, fanout=None, edge_keep=1.0,
+    edge_rescale=None): see the module's text.
     ``A`` is taken as gcn takes it (the forward aggregates over the rows of A.transpose()); ``weights``: (W_l, b_l, W_r, b_r)
     per layer."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], aggr: str = "mean", loss: str = "softmax", fused: bool = True,
-                 weights=None, dropout: float = 0.0, norm=None, fanout=None, edge_keep: float = 1.0):
+                 weights=None, dropout: float = 0.0, norm=None, fanout=None, edge_keep: float = 1.0, edge_rescale=None):
         self.aggr = check_aggr(aggr)                         # option checks come before any device work
-        self._init_sampling(fanout, edge_keep)               # refuses aggr="mean" with sampling on
+        self._init_sampling(fanout, edge_keep, edge_rescale)  # aggr="mean": on only with a rescale; aggr="max": no rescale
         if A.n() != A.m():
             raise ValueError(f"A must be square, got {A.n()} x {A.m()}")
         self._init_dropout(dropout, len(sizes) - 1)
@@ -278,8 +282,11 @@ class sage(sampling_option, model_base):
             self.layers_.append(sage_layer(name, agg, n, self.sizes[l], self.sizes[l + 1], l + 1 < n_layers, l == 0,
                                            self.G_M_buffer, self.norm))
         self._adam = None
+        self._sample_max_d = max(self.sizes[:-1])
         if self.aggr == "max":
             self._make_sampler(self.A_T, self._A_sorted)         # nothing unless sampling is on
+        else:
+            self._make_sampler(self.A_T, self.A)                 # with values: the forward matrix and the matrix it came from
         if weights is not None:
             if len(weights) != n_layers or any(len(w) != 4 for w in weights):
                 raise ValueError(f"weights must be (W_l, b_l, W_r, b_r) for each of the {n_layers} layers")
@@ -299,8 +306,12 @@ class sage(sampling_option, model_base):
         return model_base.__call__(self, ctx, H, training)
 
     def _refuse_sampling(self, fanout, keep) -> None:
-        if self.aggr != "max":
+        if self.aggr != "max" and self._rescale_checked() is None:
             refuse_sampling(f'sage(aggr="{self.aggr}")', fanout, keep)
+
+    def _refuse_rescale(self, rescale) -> None:
+        if self.aggr == "max":
+            raise ValueError(f'sage(aggr="max") reads no values: edge_rescale (rescale) must be None, got {rescale!r}')
 
     def reset_input_cache(self) -> None:
         """drops layer 0's kept aggregate agg(X): the next forward computes it again"""
