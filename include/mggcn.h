@@ -904,6 +904,51 @@ void mggcn_spmm_csr_dev_f32(mggcn_stream_t stream, const mggcn_spmm_dev_plan *pl
 void mggcn_spmm_csr_dev_bf16(mggcn_stream_t stream, const mggcn_spmm_dev_plan *plan, uint32_t n_rows, uint32_t n_cols,
                              const uint32_t *indptr, const uint32_t *indices, const float *values, const uint16_t *B, size_t ldb,
                              float *C, size_t ldc, uint32_t d, float alpha, float beta, uint32_t flags, float slope);
+
+/* A stable segmented LSD radix sort of (u32 key, u32 value) pairs (csrc/radix_sort.hip; no reference counterpart): the one
+ * way to put anything in order on the device.  Segment s is [s seg_len, (s + 1) seg_len) of each array; every segment is
+ * sorted on its own, ascending on the key bits [begin_bit, end_bit) -- bits outside the range never influence the order --,
+ * and equal keys keep their input order.  The result always ends in keys / vals (an odd number of passes ends with a
+ * device-to-device copy); keys_alt / vals_alt are scratch of the same sizes.
+ *   One pass per 8-bit digit: per-tile digit histograms (MGGCN_RADIX_SORT_TILE pairs per workgroup, integer LDS counters),
+ *   ONE exclusive scan of the (segment, digit, tile) table with mggcn_edge_sample_scan_u32 -- every segment holds seg_len
+ *   pairs, so the scanned word is the absolute position --, and a scatter in which a pair's place is the scanned word of its
+ *   digit and tile plus its rank among the tile's equal digits, a rank made of ballots, population counts and prefix counts
+ *   and never of an atomic's arrival order: the same bits on every call.  No workgroup waits on another; enqueue-only, no
+ *   host read, no synchronisation, no scratch.
+ * work: mggcn_radix_sort_work_bytes(n_seg, seg_len) bytes of device memory, 4-byte aligned.  n_seg == 0 or seg_len == 0
+ * returns without a launch (work_bytes gives 0).  Refused before any launch: 0 <= begin_bit < end_bit <= 32 violated;
+ * n_seg seg_len >= 2^31; a work_bytes below the function's; any overlap among the four arrays. */
+#define MGGCN_RADIX_SORT_TILE 4096
+size_t mggcn_radix_sort_work_bytes(size_t n_seg, size_t seg_len);
+void mggcn_radix_sort_pairs_u32(mggcn_stream_t stream, size_t n_seg, size_t seg_len, uint32_t *keys, uint32_t *vals,
+                                uint32_t *keys_alt, uint32_t *vals_alt, int begin_bit, int end_bit, void *work,
+                                size_t work_bytes);
+
+/* The integers behind ROC-AUC of a multi-label model (csrc/roc_auc.hip; no reference counterpart).
+ *   keys    reads columns [c0, c0 + nc) of the row-major fp32 logits, of the int32 targets (non-zero = positive) and the
+ *           int32 sets (NULL: every row is slot 0), n rows each, and writes class-major keys[(c - c0) n + i], vals likewise:
+ *             key   = x = logit + 0.0f (so -0.0 ties with +0.0, as a float compare does), u = bits(x),
+ *                     (u >> 31) ? ~u : (u | 0x80000000): monotone over every finite value and both infinities.  A NaN
+ *                     falls where this map puts its bit pattern (sign clear: above +inf; sign set: below -inf).
+ *             value = slot << 1 | (target != 0), slot 0 train / 1 val / 2 test / 3 anything else.
+ *           The matrices are read along their rows and transposed through LDS; the stores are 64 consecutive rows of a
+ *           class.  n nc < 2^31; c0 + nc within both leading dimensions.
+ *   stats   over the nc segments of n pairs SORTED ascending on the key (mggcn_radix_sort_pairs_u32): stats[c][k] =
+ *           (2U, P, N), three u64, k = train, val, test, other, all ("all": every row).  P / N: the positives / negatives of
+ *           slot k; 2U = sum over the positives p of slot k of 2 #{negatives of slot k with key < key_p} + #{negatives of
+ *           slot k with key == key_p}: ties count one half, AUC = 2U / (2 P N).  Tie groups of any length across any number
+ *           of chunks (MGGCN_ROC_AUC_CHUNK pairs per wave) are exact.  Everything is an integer, summed in a fixed order
+ *           (partials per chunk, one workgroup per class); 2U <= 2 P N < 2^63.  Four launches, no atomics, no host read.
+ *           work: mggcn_roc_auc_stats_work_bytes(n, nc) bytes of device memory, 8-byte aligned.  n == 0 writes zeros. */
+#define MGGCN_ROC_AUC_CHUNK 1024
+void mggcn_roc_auc_keys_f32(mggcn_stream_t stream, const float *logits, size_t ld_logits, const int32_t *targets,
+                            size_t ld_targets, const int32_t *sets, size_t n, size_t c0, size_t nc, uint32_t *keys,
+                            uint32_t *vals);
+size_t mggcn_roc_auc_stats_work_bytes(size_t n, size_t nc);
+void mggcn_roc_auc_stats_u64(mggcn_stream_t stream, const uint32_t *keys, const uint32_t *vals, size_t n, size_t nc,
+                             uint64_t *stats, void *work, size_t work_bytes);
+
 /* cublasSasum(src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

@@ -33,6 +33,8 @@ Layout:
   checkpoint.py  save / load / predict of gcn, dist_gcn, gat and dist_gat, named from the owners' tables (no reference
                  counterpart)
   selection.py   model_selector: best epoch on a split, early stopping
+  metrics.py     roc_auc_evaluator: ROC-AUC per class and split of a multi-label model as exact integers, on a stable radix
+                 sort on the device (csrc/radix_sort.hip, csrc/roc_auc.hip; no reference counterpart)
   smoothing.py   correct_and_smooth: label-propagation post-processing of any model's logits (csrc/propagate.hip around the
                  sweep SpMM; no reference counterpart)
 """
@@ -56,9 +58,11 @@ from .dist import (dist_context, dist_gcn, dist_gcn_layer, dist_row_csr_matrix, 
 
 from . import checkpoint, selection                             # noqa: F401
 from .selection import model_selector                           # noqa: F401
+from . import metrics                                           # noqa: F401
+from .metrics import roc_auc_evaluator                          # noqa: F401
 from . import smoothing                                         # noqa: F401
 from .smoothing import correct_and_smooth                       # noqa: F401
 
 __all__ = ["context", "csr_matrix", "dn_matrix", "matrix_error", "engine_error", "ops", "matmul",
            "get_matmul_buffer", "sparse_linear", "linear", "gcn_layer", "softmax",
-           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "sage", "sage_layer", "max_aggregate", "edge_sampler", "sampled_csr", "datasets", "model_selector", "correct_and_smooth"]
+           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "sage", "sage_layer", "max_aggregate", "edge_sampler", "sampled_csr", "datasets", "model_selector", "correct_and_smooth", "roc_auc_evaluator"]

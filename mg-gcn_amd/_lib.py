@@ -189,6 +189,11 @@ PROTOTYPES = {
                                       c_uint32, c_float, c_float, c_uint32, c_float]),
     "mggcn_spmm_csr_dev_bf16": (None, [vp, vp, c_uint32, c_uint32, vp, vp, vp, vp, c_size_t, vp, c_size_t,
                                        c_uint32, c_float, c_float, c_uint32, c_float]),
+    "mggcn_radix_sort_work_bytes": (c_size_t, [c_size_t, c_size_t]),
+    "mggcn_radix_sort_pairs_u32": (None, [vp, c_size_t, c_size_t, vp, vp, vp, vp, c_int, c_int, vp, c_size_t]),
+    "mggcn_roc_auc_keys_f32": (None, [vp, vp, c_size_t, vp, c_size_t, vp, c_size_t, c_size_t, c_size_t, vp, vp]),
+    "mggcn_roc_auc_stats_work_bytes": (c_size_t, [c_size_t, c_size_t]),
+    "mggcn_roc_auc_stats_u64": (None, [vp, vp, vp, c_size_t, c_size_t, vp, vp, c_size_t]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),
     "mggcn_gather_rows_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_softmax_xent_fused_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_float, vp]),

@@ -1070,6 +1070,24 @@ class model_base(dropout_option, checkpoint_option):
                 res[name] = float(hit[m].mean()) if m.any() else float("nan")
         return res
 
+    _roc_auc_evaluator = None
+
+    def roc_auc(self, ctx: context, H: dn_matrix, Y: dn_matrix, S=None, max_workspace_bytes: Optional[int] = None):
+        """ROC-AUC per class and split of a loss="bce" model, computed on the device (metrics.roc_auc_evaluator: what it
+        returns; ogbn-proteins' score is result["test"] / ["val"]).  One plain forward on the full graph -- no dropout, no
+        sampling, no label mask beyond what a plain call does; no dropout or sample epoch is spent --, then keys, one stable
+        sort per class and the integer statistic; the logits are never copied to the host.  S: the sets (an int32 dn_matrix
+        of n x 1 or n integers); None uses those of set_splits when there are any, else every row is in slot "train".  The
+        evaluator is created with the first call and kept (``max_workspace_bytes``: its cap, read then).  ValueError before
+        any device work: a model whose loss is not "bce", targets that fail check_targets, an S of the wrong shape,
+        n >= 2^31."""
+        from . import metrics
+        S = metrics.model_roc_auc_checks(self, Y, S)
+        if self._roc_auc_evaluator is None:
+            kw = {} if max_workspace_bytes is None else dict(max_workspace_bytes=max_workspace_bytes)
+            self._roc_auc_evaluator = metrics.roc_auc_evaluator(self.A.n(), self._out_width, **kw)
+        return self._roc_auc_evaluator(ctx, self(ctx, H), Y, S)
+
 
 class gcn(rescaled_sampling_option, model_base):
     """reference src/gcn.hpp:937-995.  The constructor column-normalises A, builds

@@ -1491,6 +1491,130 @@ def spmm_dev(ctx: context, A, B, C: dn_matrix, plan: spmm_dev_buffer, alpha: flo
        alpha, beta, flags, slope)
 
 
+# ---- the stable segmented radix sort (csrc/radix_sort.hip) and the ROC-AUC integers on top of it (csrc/roc_auc.hip) ---------
+RADIX_SORT_TILE = 4096              # MGGCN_RADIX_SORT_TILE: pairs per workgroup of a digit pass
+ROC_AUC_CHUNK = 1024                # MGGCN_ROC_AUC_CHUNK: pairs per wave of the statistic
+ROC_AUC_VIEWS = ("train", "val", "test", "other", "all")        # the k of stats[c][k]: SPLIT_NAMES, then every row
+
+
+def _req_count(v, what: str) -> int:
+    _req(isinstance(v, numbers.Integral) and not isinstance(v, bool) and v >= 0, f"{what} must be a non-negative integer")
+    return int(v)
+
+
+def radix_sort_work_bytes(n_seg: int, seg_len: int) -> int:
+    """mggcn_radix_sort_work_bytes restated on the host (a digit histogram per tile and its scan, one word more)"""
+    n_seg, seg_len = _req_count(n_seg, "radix sort: n_seg"), _req_count(seg_len, "radix sort: seg_len")
+    if n_seg == 0 or seg_len == 0:
+        return 0
+    return 4 * (2 * n_seg * 256 * (-(-seg_len // RADIX_SORT_TILE)) + 1)
+
+
+def _req_work(work, least: int, what: str) -> None:
+    _req(work is not None and hasattr(work, "data_ptr") and work.is_cuda and work.is_contiguous()
+         and work.numel() * work.element_size() >= least and work.data_ptr() % 8 == 0,
+         f"{what}: work_bytes too small: work must be a contiguous, 8-byte aligned device tensor of at least {least} bytes")
+
+
+def radix_sort_pairs(ctx: context, n_seg: int, seg_len: int, keys, vals, keys_alt, vals_alt, work, begin_bit: int = 0,
+                     end_bit: int = 32, timer: Optional[str] = None) -> None:
+    """Sorts n_seg segments of seg_len (key, value) pairs each, every segment on its own, ascending on the key bits
+    [begin_bit, end_bit), equal keys in their input order (mggcn_radix_sort_pairs_u32: a stable LSD radix sort, one pass per
+    8-bit digit; the same bits on every call).  The four arrays are device tensors of 4-byte integers, at least
+    n_seg * seg_len long, none overlapping another; the result is in keys / vals, the _alt pair is scratch.  work: a device
+    tensor of radix_sort_work_bytes(n_seg, seg_len) bytes.  Enqueue-only.  Refused with ValueError before the library:
+    begin_bit / end_bit outside 0 <= begin_bit < end_bit <= 32, n_seg * seg_len >= 2^31, a work that is too small, any overlap."""
+    what = "radix sort"
+    for name, b in (("begin_bit", begin_bit), ("end_bit", end_bit)):
+        _req(isinstance(b, numbers.Integral) and not isinstance(b, bool), f"{what}: {name} must be an integer")
+    _req(0 <= begin_bit < end_bit <= 32, f"{what}: 0 <= begin_bit < end_bit <= 32, got begin_bit {begin_bit}, end_bit {end_bit}")
+    n_seg, seg_len = _req_count(n_seg, f"{what}: n_seg"), _req_count(seg_len, f"{what}: seg_len")
+    total = n_seg * seg_len
+    _req(total < 1 << 31, f"{what}: n_seg * seg_len must be below 2^31, got {total}")
+    if total == 0:
+        return
+    arrays = (("keys", keys), ("vals", vals), ("keys_alt", keys_alt), ("vals_alt", vals_alt))
+    for name, t in arrays:
+        _req_u32(t, total, f"{what}: {name}")
+    for i, (na, a) in enumerate(arrays):
+        for nb, b in arrays[i + 1:]:
+            _req(a.data_ptr() + 4 * total <= b.data_ptr() or b.data_ptr() + 4 * total <= a.data_ptr(),
+                 f"{what}: {na} and {nb} must not alias (overlap)")
+    need = radix_sort_work_bytes(n_seg, seg_len)
+    _req_work(work, need, what)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_radix_sort_pairs_u32(
+        ctx.stream(0), n_seg, seg_len, keys.data_ptr(), vals.data_ptr(), keys_alt.data_ptr(), vals_alt.data_ptr(),
+        int(begin_bit), int(end_bit), work.data_ptr(), work.numel() * work.element_size()))
+
+
+def _dense_window(M, dtype_float: bool, what: str):
+    """(pointer, leading dimension, rows, columns) of a row-major operand of 4-byte elements: a dn_matrix, or a 2-D device
+    tensor with unit column stride (a column window of a wider matrix)"""
+    t = M.t if isinstance(M, dn_matrix) else M
+    _req(hasattr(t, "dim") and t.dim() == 2 and t.element_size() == 4 and t.dtype.is_floating_point == dtype_float,
+         f"{what} must be a 2-D {'fp32' if dtype_float else 'int32'} matrix (a dn_matrix or a column window of one)")
+    _req(t.shape[1] <= 1 or t.stride(1) == 1, f"{what}: columns must be contiguous")
+    _req(t.is_cuda, f"{what} must be on the device")
+    n, m = int(t.shape[0]), int(t.shape[1])
+    return t.data_ptr(), (max(int(t.stride(0)), m) if n > 1 else max(m, 1)), n, m
+
+
+def roc_auc_keys(ctx: context, logits, targets, sets: Optional[dn_matrix], c0: int, nc: int, keys, vals,
+                 timer: Optional[str] = None) -> None:
+    """keys[(c - c0) n + i], vals[...] of columns [c0, c0 + nc) of the logits (mggcn_roc_auc_keys_f32): key = the logit's
+    bits made sortable (-0.0 ties with +0.0; a NaN falls where the map puts its bit pattern), value = slot << 1 |
+    (target != 0), slot as SPLIT_NAMES (sets None: every row is slot 0).  logits (fp32) / targets (int32): a dn_matrix or a
+    2-D device tensor with unit column stride, n rows and the same number of columns; keys / vals: device tensors of at
+    least n * nc 4-byte integers."""
+    what = "roc-auc keys"
+    lp, ldl, n, m = _dense_window(logits, True, f"{what}: logits")
+    tp, ldt, tn, tm = _dense_window(targets, False, f"{what}: targets")
+    _req((tn, tm) == (n, m), f"{what}: targets must be {n} x {m} like the logits, got {tn} x {tm}")
+    c0, nc = _req_count(c0, f"{what}: c0"), _req_count(nc, f"{what}: nc")
+    _req(c0 + nc <= m, f"{what}: columns [{c0}, {c0 + nc}) exceed the {m} of the logits")
+    _req(n < 1 << 31 and n * nc < 1 << 31, f"{what}: n * nc must be below 2^31")
+    if sets is not None:
+        _req_sets(sets, n, what)
+    _req_u32(keys, n * nc, f"{what}: keys")
+    _req_u32(vals, n * nc, f"{what}: vals")
+    _req(keys.data_ptr() != vals.data_ptr() or n * nc == 0, f"{what}: keys must not alias vals")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_roc_auc_keys_f32(
+        ctx.stream(0), lp, ldl, tp, ldt, sets.buffer() if sets is not None else None, n, c0, nc, keys.data_ptr(),
+        vals.data_ptr()))
+
+
+def roc_auc_stats_work_bytes(n: int, nc: int) -> int:
+    """mggcn_roc_auc_stats_work_bytes restated on the host: per class and chunk eight u32 counts and five i64 partials, eight
+    u32 totals per class, each table rounded up to 256 bytes"""
+    n, nc = _req_count(n, "roc-auc stats: n"), _req_count(nc, "roc-auc stats: nc")
+    if n == 0 or nc == 0:
+        return 0
+    chunks = -(-n // ROC_AUC_CHUNK)
+    return sum(-(-b // 256) * 256 for b in (nc * chunks * 32, nc * 32, nc * chunks * 40))
+
+
+def roc_auc_stats(ctx: context, keys, vals, n: int, nc: int, stats, work, timer: Optional[str] = None) -> None:
+    """stats[c][k] = (2U, P, N) as int64 words, k over ROC_AUC_VIEWS, from nc segments of n pairs SORTED on the key
+    (mggcn_roc_auc_stats_u64): P / N the positives / negatives of the view, 2U = 2 #{(p, n): key_n < key_p} + #{key_n ==
+    key_p}.  stats: a device tensor of at least nc * 15 8-byte integers; work: roc_auc_stats_work_bytes(n, nc) bytes."""
+    what = "roc-auc stats"
+    n, nc = _req_count(n, f"{what}: n"), _req_count(nc, f"{what}: nc")
+    _req(n < 1 << 31 and n * nc < 1 << 31, f"{what}: n * nc must be below 2^31")
+    if nc == 0:
+        return
+    _req_u32(keys, n * nc, f"{what}: keys")
+    _req_u32(vals, n * nc, f"{what}: vals")
+    _req(hasattr(stats, "data_ptr") and stats.is_cuda and stats.is_contiguous() and stats.element_size() == 8
+         and not stats.dtype.is_floating_point and stats.numel() >= nc * 15,
+         f"{what}: stats must be a contiguous device tensor of at least {nc * 15} 8-byte integers")
+    need = roc_auc_stats_work_bytes(n, nc)
+    if need:
+        _req_work(work, need, what)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_roc_auc_stats_u64(
+        ctx.stream(0), keys.data_ptr(), vals.data_ptr(), n, nc, stats.data_ptr(), work.data_ptr() if need else None,
+        work.numel() * work.element_size() if need else 0))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""

@@ -11,11 +11,12 @@ from typing import List, Optional
 from . import ops
 from .checkpoint import model_params, raw_context, reset_adam
 
-METRICS = ("loss", "score")
+METRICS = ("loss", "score")                 # the pair split_metrics() reports per split
+RANKING_METRICS = ("roc_auc",)              # computed by a pass of their own (model.roc_auc); always a clean pass
 
 
 class model_selector:
-    """model_selector(model, split="val", metric="loss" | "score", patience=None, clean=None)
+    """model_selector(model, split="val", metric="loss" | "score" | "roc_auc", patience=None, clean=None)
 
     step(ctx, X, Y, lr, beta1, beta2, weight_decay, eps) runs one train_step and returns what it returns.
 
@@ -31,13 +32,18 @@ class model_selector:
     training forward's validation numbers are the dropped forward's, with edge sampling (set_sampling) they are the sampled
     graph's, and a model must not be selected on either: the clean pass runs on the full graph.
 
-    "Improved" is strict -- lower loss, higher score; the first best epoch wins a tie; a NaN never improves.
+    metric="roc_auc" (models with loss="bce": gcn, gat, sage) monitors model.roc_auc(ctx, X, Y)[split], the mean ROC-AUC
+    over the classes that have both labels in the split, on the device.  It is always a clean pass -- one extra plain
+    forward after the update, then keys, sort and count; no loss-layer call, so split_metrics() keeps the training forward's
+    numbers --, hence clean=False together with it is refused.
+
+    "Improved" is strict -- lower loss, higher score or roc_auc; the first best epoch wins a tie; a NaN never improves.
     ``stop`` turns true once ``patience`` epochs have passed without improvement."""
 
     def __init__(self, model, split: str = "val", metric: str = "loss", patience: Optional[int] = None,
                  clean: Optional[bool] = None):
-        if metric not in METRICS:
-            raise ValueError(f"metric must be one of {METRICS}, not {metric!r}")
+        if metric not in METRICS + RANKING_METRICS:
+            raise ValueError(f"metric must be one of {METRICS + RANKING_METRICS}, not {metric!r}")
         if split not in ops.SPLIT_NAMES[:3]:
             raise ValueError(f"split must be one of {ops.SPLIT_NAMES[:3]}, not {split!r}")
         if patience is not None and (int(patience) != patience or patience < 1):
@@ -47,6 +53,15 @@ class model_selector:
             raise ValueError("model_selector needs set_splits(...) on the model first")
         if not loss_layer.counts[ops.SPLIT_NAMES.index(split)]:
             raise ValueError(f"no vertex belongs to the {split} split: nothing to select on")
+        if metric in RANKING_METRICS:
+            if clean is not None and not clean:
+                raise ValueError(f"clean=False does not go with metric={metric!r}: the ranking metric is a pass of its own "
+                                 "after the update (a clean pass), the training forward does not produce it")
+            if not callable(getattr(model, "roc_auc", None)):
+                raise ValueError(f"metric={metric!r} needs a model with roc_auc (gcn, gat, sage), not {type(model).__name__}")
+            from .metrics import model_roc_auc_checks
+            model_roc_auc_checks(model, None, None, targets=False)               # loss="bce", n < 2^31: before any device work
+            clean = True
         self.model, self.split, self.metric = model, split, metric
         self.patience = None if patience is None else int(patience)
         dropping = (model.dropout_p > 0.0 or getattr(model, "attn_dropout_p", 0.0) > 0.0
@@ -81,9 +96,12 @@ class model_selector:
         if not self.clean:
             self._candidate = self._snapshot(ctx, self._candidate)          # the parameters this epoch's metric describes
         result = self.model.train_step(ctx, X, Y, lr, beta1, beta2, weight_decay, eps)
-        if self.clean:
-            self.model.loss_layer(ctx, self.model(ctx, X), Y)               # plain forward, no mask; synchronises
-        value = float(self.model.split_metrics()[self.split][METRICS.index(self.metric)])
+        if self.metric in RANKING_METRICS:
+            value = float(self.model.roc_auc(ctx, X, Y)[self.split])        # plain forward, keys, sort, count; synchronises
+        else:
+            if self.clean:
+                self.model.loss_layer(ctx, self.model(ctx, X), Y)           # plain forward, no mask; synchronises
+            value = float(self.model.split_metrics()[self.split][METRICS.index(self.metric)])
         epoch = len(self.history)
         self.history.append(value)
         if self._improved(value):
