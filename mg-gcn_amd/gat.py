@@ -145,7 +145,7 @@ is ``layer.attn.att_edge`` [heads x de] per layer, gradient ``G_att_edge``: PyG'
 E_p . U[k] with U[k, c] = sum_d W_e[c, k dh + d] att_edge[k, d], and att_edge here IS U -- the same function class without
 the redundant factorisation.  It starts seed-99 uniform like att, is a row of the fused Adam table with W's weight decay,
 ``edge_weights=`` takes one [heads x de] array per layer and ``model.edge_dim`` reads de (0 without the option).  The
-kernels are those of csrc/gat_efeat.hip (mggcn_gat_*_efeat_f32 and their _drop twins): de loads and FMAs per (entry, head)
+entry points are those of csrc/gat_efeat.hip (mggcn_gat_*_efeat_f32 and their _drop twins): de loads and FMAs per (entry, head)
 on the lane that owns the entry, nothing of nnz x heads stored, G_att_edge the fixed-order column sum of per-row shares
 P_e [n x heads de].  The model holds E twice on the device, shared by all layers -- ``E_A`` in A's entry order for
 backward_src and ``E_F`` = E[edge_permutation(A)] in A.transpose()'s for forward and backward_dst: 2 nnz de 4 bytes.  Both
@@ -377,8 +377,8 @@ class attention_efeat(gathered_images):
     att_edge[k, d], so att_edge here IS U: the same function class without the redundant factorisation.  ``E_F`` / ``E_A``
     are the model's two device copies of E ([entries x de]; E_F in the entry order of F, which forward and backward_dst
     walk, E_A in that of F^T, which backward_src walks) and ``P_e`` [n x heads de] the rows' shares of G_att_edge between
-    backward_dst and the column sum; it aliases ``P_buffer`` (the model's, at the layer with the most heads).  The kernels
-    are those of csrc/gat_efeat.hip (mggcn_gat_*_efeat_f32 and their _drop twins).  There is no export and no bf16 form.
+    backward_dst and the column sum; it aliases ``P_buffer`` (the model's, at the layer with the most heads).  The entry
+    points are those of csrc/gat_efeat.hip (mggcn_gat_*_efeat_f32 and their _drop twins).  There is no export and no bf16 form.
 
     A parameter owner by its table and gcn.param_owner's own three methods, not by inheritance (as label_input is): the
     subclasses of param_owner are enumerated for the checkpoint's names per slot, and no version of the checkpoint file

@@ -554,11 +554,13 @@ def _gat_timed(ctx: context, timer: Optional[str], call) -> None:
     ctx.register_timer(timer, timer + "_0", timer + "_1")
 
 
-def _gat_call(ctx: context, timer: Optional[str], name: str, args, extra=None, image: bool = False) -> None:
+def _gat_call(ctx: context, timer: Optional[str], name: str, args, extra=None, image: bool = False, tail=None) -> None:
     """mggcn_<name>_f32(*args) under ``timer``; with ``extra`` (the tuple of _gat_drop_args) its _drop twin, which takes it
-    last; ``image``: the _bf16 twin of either (the gathered operands of ``args`` are bf16 images)"""
-    entry = getattr(ctx.lib, f"mggcn_{name}{'' if extra is None else '_drop'}_{'bf16' if image else 'f32'}")
-    _gat_timed(ctx, timer, lambda: entry(*args, *(extra or ())))
+    after ``args``; ``image``: the _bf16 twin of either (the gathered operands of ``args`` are bf16 images); with ``tail``
+    (the tuple of _gat_efeat_args) the _efeat twin of either, fp32 only, which takes it last"""
+    entry = getattr(ctx.lib, f"mggcn_{name}{'' if tail is None else '_efeat'}{'' if extra is None else '_drop'}"
+                             f"_{'bf16' if image else 'f32'}")
+    _gat_timed(ctx, timer, lambda: entry(*args, *(extra or ()), *(tail or ())))
 
 
 class bf16_image:
@@ -641,18 +643,21 @@ def gat_forward(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_s
 
 
 def _gat_forward(image: bool, ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
-                 lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
-    """the body of gat_forward and gat_forward_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
+                 lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None,
+                 edge=None) -> None:
+    """the body of gat_forward, gat_forward_bf16 and gat_forward_efeat; ``image``: the gathered operands are bf16 images
+    (the _bf16 entry); ``edge`` = (E, att_edge): the edge term in the score (the _efeat entry)"""
     _req_roles("gat forward", image, (Z,))
     check_gat_heads(heads, Z.m(), "gat forward")
     _req(F.m() == Z.n() and out.shape() == (F.n(), Z.m()), "gat forward: shape mismatch")
     _req(s_dst.shape() == (F.n(), heads) and lse.shape() == (F.n(), heads) and s_src.shape() == (F.m(), heads),
          "gat forward: the scores and lse must be rows x heads")
+    tail = None if edge is None else _gat_efeat_args("gat forward", F, *edge, heads)
     extra = None if drop is None else _gat_drop_args(drop, "gat forward", F.n(), F.m())
     ip, ix, _ = F.device(ctx.device)
     args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), _ld(Z), s_dst.buffer(), s_src.buffer(), heads,
             Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer())
-    _gat_call(ctx, timer, "gat_forward", args, extra, image)
+    _gat_call(ctx, timer, "gat_forward", args, extra, image, tail)
 
 
 def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
@@ -666,18 +671,27 @@ def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix
 
 def _gat_backward_dst(image: bool, ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix,
                       lse: dn_matrix, G: dn_matrix, out: dn_matrix, D: dn_matrix, ds_dst: dn_matrix, heads: int,
-                      slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
-    """the body of gat_backward_dst and gat_backward_dst_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
+                      slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None, edge=None) -> None:
+    """the body of gat_backward_dst, gat_backward_dst_bf16 and gat_backward_dst_efeat; ``image``: the gathered operands are
+    bf16 images (the _bf16 entry); ``edge`` = (E, att_edge, P_e): the edge term in the score and the output it adds (the
+    _efeat entry)"""
     _req_roles("gat backward", image, (Z,), (G, out))
     check_gat_heads(heads, Z.m(), "gat backward")
     _req(F.m() == Z.n() and G.shape() == (F.n(), Z.m()) and out.shape() == G.shape(), "gat backward: shape mismatch")
     _req(all(s.shape() == (F.n(), heads) for s in (s_dst, lse, D, ds_dst)) and s_src.shape() == (F.m(), heads),
          "gat backward: the scores, lse, D and ds must be rows x heads")
+    tail = None
+    if edge is not None:
+        E, att_edge, P_e = edge
+        tail = _gat_efeat_args("gat backward", F, E, att_edge, heads)
+        _req(P_e.shape() == (F.n(), heads * E.m()),
+             f"gat backward: P_e must be {F.n()} x {heads * E.m()} (rows x heads x edge dimension)")
+        tail += (P_e.buffer(), P_e.m())
     extra = None if drop is None else _gat_drop_args(drop, "gat backward", F.n(), F.m())
     ip, ix, _ = F.device(ctx.device)
     args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), _ld(Z), s_dst.buffer(), s_src.buffer(),
             lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer())
-    _gat_call(ctx, timer, "gat_backward_dst", args, extra, image)
+    _gat_call(ctx, timer, "gat_backward_dst", args, extra, image, tail)
 
 
 def _req_gat_backward_src(F_T, Z, dst_scalars, s_src, G, att, ds_dst, ds_src, G_Z, heads: int, which: str) -> None:
@@ -704,16 +718,18 @@ def gat_backward_src(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matr
 def _gat_backward_src(image: bool, ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix,
                       lse: dn_matrix, D: dn_matrix, G: dn_matrix, att: dn_matrix, ds_dst: Optional[dn_matrix],
                       ds_src: dn_matrix, G_Z: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None,
-                      drop=None) -> None:
-    """the body of gat_backward_src and gat_backward_src_bf16; ``image``: the gathered operands are bf16 images (the _bf16 entry)"""
+                      drop=None, edge=None) -> None:
+    """the body of gat_backward_src, gat_backward_src_bf16 and gat_backward_src_efeat; ``image``: the gathered operands are
+    bf16 images (the _bf16 entry); ``edge`` = (E, att_edge): the edge term in the score (the _efeat entry)"""
     _req_roles("gat backward", image, (G,), (Z, G_Z))
     _req_gat_backward_src(F_T, Z, (s_dst, lse, D), s_src, G, att, ds_dst, ds_src, G_Z, heads, "the scores, lse, D and ds")
+    tail = None if edge is None else _gat_efeat_args("gat backward", F_T, *edge, heads)
     extra = None if drop is None else _gat_drop_args(drop, "gat backward", F_T.m(), F_T.n())
     ip, ix, _ = F_T.device(ctx.device)
     args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
             lse.buffer(), D.buffer(), G.buffer(), _ld(G), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
             Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m())
-    _gat_call(ctx, timer, "gat_backward_src", args, extra, image)
+    _gat_call(ctx, timer, "gat_backward_src", args, extra, image, tail)
 
 
 def _req_gat_rec(rec, rows: int, heads: int, what: str) -> None:
@@ -774,31 +790,13 @@ def _gat_efeat_args(what: str, F: csr_matrix, E: dn_matrix, att_edge: dn_matrix,
     return (E.buffer(), de, att_edge.buffer(), de)
 
 
-def _gat_efeat_call(ctx: context, timer: Optional[str], name: str, args, extra, tail) -> None:
-    """mggcn_<name>_efeat_f32(*args, *tail) under ``timer``; with ``extra`` (the tuple of _gat_drop_args) the _efeat_drop
-    twin, which takes it between the two"""
-    entry = getattr(ctx.lib, f"mggcn_{name}_efeat{'' if extra is None else '_drop'}_f32")
-    _gat_timed(ctx, timer, lambda: entry(*args, *(extra or ()), *tail))
-
-
 def gat_forward_efeat(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
                       lse: dn_matrix, E: dn_matrix, att_edge: dn_matrix, heads: int, slope: float = GAT_SLOPE,
                       timer: Optional[str] = None, drop=None) -> None:
     """gat_forward with edge features in the score (mggcn_gat_forward_efeat_f32 / _efeat_drop_f32): x_ijk = (s_dst[i, k] +
     s_src[j, k]) + sum_c E[p, c] att_edge[k, c] for entry p = (i, j) of F's indices array, and everything after x is
     gat_forward's.  ``E``: [F.nnz() x de] in F's entry order, ``att_edge``: [heads x de], de <= GAT_MAX_EDGE_DIM."""
-    what = "gat forward"
-    _req_roles(what, False, (Z,))
-    check_gat_heads(heads, Z.m(), what)
-    _req(F.m() == Z.n() and out.shape() == (F.n(), Z.m()), f"{what}: shape mismatch")
-    _req(s_dst.shape() == (F.n(), heads) and lse.shape() == (F.n(), heads) and s_src.shape() == (F.m(), heads),
-         f"{what}: the scores and lse must be rows x heads")
-    tail = _gat_efeat_args(what, F, E, att_edge, heads)
-    extra = None if drop is None else _gat_drop_args(drop, what, F.n(), F.m())
-    ip, ix, _ = F.device(ctx.device)
-    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(), heads,
-            Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer())
-    _gat_efeat_call(ctx, timer, "gat_forward", args, extra, tail)
+    _gat_forward(False, ctx, F, Z, s_dst, s_src, out, lse, heads, slope, timer, drop, (E, att_edge))
 
 
 def gat_backward_dst_efeat(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
@@ -809,19 +807,7 @@ def gat_backward_dst_efeat(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_
     writes P_e[i, k de + c] = sum_j ds_ijk E[p, c] over the entries of row i: row i's share of the gradient of att_edge
     (gatv2_att_grad(P_e, G_att_edge viewed as 1 x heads de) sums the rows).  ``E`` in F's entry order; ``P_e``: [F.n() x
     heads de]."""
-    what = "gat backward"
-    _req_roles(what, False, (Z,), (G, out))
-    check_gat_heads(heads, Z.m(), what)
-    _req(F.m() == Z.n() and G.shape() == (F.n(), Z.m()) and out.shape() == G.shape(), f"{what}: shape mismatch")
-    _req(all(s.shape() == (F.n(), heads) for s in (s_dst, lse, D, ds_dst)) and s_src.shape() == (F.m(), heads),
-         f"{what}: the scores, lse, D and ds must be rows x heads")
-    tail = _gat_efeat_args(what, F, E, att_edge, heads)
-    _req(P_e.shape() == (F.n(), heads * E.m()), f"{what}: P_e must be {F.n()} x {heads * E.m()} (rows x heads x edge dimension)")
-    extra = None if drop is None else _gat_drop_args(drop, what, F.n(), F.m())
-    ip, ix, _ = F.device(ctx.device)
-    args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
-            lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer())
-    _gat_efeat_call(ctx, timer, "gat_backward_dst", args, extra, tail + (P_e.buffer(), P_e.m()))
+    _gat_backward_dst(False, ctx, F, Z, s_dst, s_src, lse, G, out, D, ds_dst, heads, slope, timer, drop, (E, att_edge, P_e))
 
 
 def gat_backward_src_efeat(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
@@ -830,16 +816,8 @@ def gat_backward_src_efeat(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: d
                            timer: Optional[str] = None, drop=None) -> None:
     """gat_backward_src with the edge term in the score (mggcn_gat_backward_src_efeat_f32 / _efeat_drop_f32).  ``E``:
     [F_T.nnz() x de] in F_T's entry order -- the other copy of what gat_forward_efeat read, row for row of the same edge."""
-    what = "gat backward"
-    _req_roles(what, False, (G,), (Z, G_Z))
-    _req_gat_backward_src(F_T, Z, (s_dst, lse, D), s_src, G, att, ds_dst, ds_src, G_Z, heads, "the scores, lse, D and ds")
-    tail = _gat_efeat_args(what, F_T, E, att_edge, heads)
-    extra = None if drop is None else _gat_drop_args(drop, what, F_T.m(), F_T.n())
-    ip, ix, _ = F_T.device(ctx.device)
-    args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
-            lse.buffer(), D.buffer(), G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
-            Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m())
-    _gat_efeat_call(ctx, timer, "gat_backward_src", args, extra, tail)
+    _gat_backward_src(False, ctx, F_T, Z, s_dst, s_src, lse, D, G, att, ds_dst, ds_src, G_Z, heads, slope, timer, drop,
+                      (E, att_edge))
 
 
 def _req_gat_alpha(F, lse, alpha, heads: int, what: str) -> None:

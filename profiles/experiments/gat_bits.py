@@ -1,7 +1,7 @@
 """Do two trees compute the same bits in every GAT entry point?  
 Every call of the GAT part of ops -- scores, forward, backward_dst, backward_src with and without attention dropout,
-pack_dst, backward_src_rec with and without dropout, scores_backward, the four GATv2 calls on [rows x width] operands
-and on the model's [Zs | Zd] buffers, and the three dot-product calls (inputs of gatdot_ref) on [rows x width] operands and
+pack_dst, backward_src_rec with and without dropout, scores_backward, the three edge-feature calls with and without dropout
+at de = 8 and de = 3 (E in the entry order of the matrix walked), the four GATv2 calls on [rows x width] operands and on the model's [Zs | Zd] buffers, and the three dot-product calls (inputs of gatdot_ref) on [rows x width] operands and
 on the thirds of [rows x 3 width] buffers -- on the graphs "long", "longT" and "rect" of gat_ref.edge_graphs(), at one (K, dh)
 per compiled (VEC, NT, U) variant (gat_ref.EDGE_RECT) plus (1, 1024) with every dense operand one float off, which is the
 16-tile element path; and att_grad beyond two passes of its capped grid.  One line per output: the entry point, the graph,
@@ -21,6 +21,7 @@ ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.dirnam
 root = os.path.abspath(ap.parse_args().root)
 sys.path[:0] = [root, os.path.join(root, "tests")]
 import __graft_entry__ as g
+import gat_efeat_ref
 import gat_ref
 import gatdot_ref
 import gatv2_ref
@@ -47,7 +48,7 @@ def report(call, tag, **outs):
     ctx.sync()
     for name, t in outs.items():
         a = (t.t if isinstance(t, dn) else t).detach().cpu().numpy()
-        print(f"{call:28s} {tag:26s} {name:7s} {'x'.join(map(str, a.shape)):12s} {hashlib.sha256(a.tobytes()).hexdigest()}", flush=True)
+        print(f"{call:28s} {tag:32s} {name:7s} {'x'.join(map(str, a.shape)):12s} {hashlib.sha256(a.tobytes()).hexdigest()}", flush=True)
 
 
 def csr(indptr, indices, m):
@@ -83,6 +84,31 @@ def run_v1(tag, F, F_T, n, n_src, K, dh, off):
         G_att = dense((2, d), off)
         ops.gat_scores_backward(ctx, ds_dst, Zd, ds_src, Z, G_att, K)
         report("gat_scores_backward" + sfx, tag, G_att=G_att)
+
+
+def run_efeat(tag, F, F_T, perm, n, n_src, K, dh, off):
+    """the edge-feature calls: de = 8 reads a row of E with 16-byte loads, de = 3 element by element; E_F is in F's entry
+    order (forward, backward_dst), E_F[perm] in F_T's (backward_src)"""
+    d = K * dh
+    Zh, Zdh, Gh, atth = gat_ref.tolerance_inputs(n, n_src, K, dh)
+    Z, G, att = dense(Zh, off), dense(Gh, off), dense(atth, off)
+    s_dst, s_src = dense((n, K)), dense((n_src, K))
+    ops.gat_scores(ctx, Z if n == n_src else dense(Zdh, off), att, s_dst, None, K)
+    ops.gat_scores(ctx, Z, att, None, s_src, K)
+    for de in (8, 3):
+        Eh, Uh = gat_efeat_ref.efeat_inputs(F.nnz(), K, de)
+        E_F, E_T, U = dense(Eh), dense(Eh[perm]), dense(Uh)
+        for drop, sfx in ((None, ""), (DROP, "+drop")):
+            etag = f"{tag} de={de}"
+            out, lse, D, ds_dst, P_e = dense((n, d), off), dense((n, K)), dense((n, K)), dense((n, K)), dense((n, K * de))
+            ops.gat_forward_efeat(ctx, F, Z, s_dst, s_src, out, lse, E_F, U, K, drop=drop)
+            report("gat_forward_efeat" + sfx, etag, out=out, lse=lse)
+            ops.gat_backward_dst_efeat(ctx, F, Z, s_dst, s_src, lse, G, out, D, ds_dst, E_F, U, P_e, K, drop=drop)
+            report("gat_backward_dst_efeat" + sfx, etag, D=D, ds_dst=ds_dst, P_e=P_e)
+            dd = ds_dst if n == n_src else None
+            ds_src, G_Z = dense((n_src, K)), dense((n_src, d), off)
+            ops.gat_backward_src_efeat(ctx, F_T, Z, s_dst, s_src, lse, D, G, att, dd, ds_src, G_Z, E_T, U, K, drop=drop)
+            report("gat_backward_src_efeat" + sfx, etag, ds_src=ds_src, G_Z=G_Z)
 
 
 def run_v2(tag, F, F_T, n, n_src, K, dh, off):
@@ -128,9 +154,11 @@ def run_dot(tag, F, F_T, n, n_src, K, dh, off):
 for name, (indptr, indices, n_src) in gat_ref.edge_graphs().items():
     n = indptr.size - 1
     F, F_T = csr(indptr, indices, n_src), csr(*gat_ref.transpose_pattern(indptr, indices, n_src), n)
+    perm = gat_efeat_ref.edge_perm(indices)
     for K, dh, off in [(K, dh, 0) for K, dh in gat_ref.EDGE_RECT] + [(1, 1024, 1)]:
         tag = f"{name} K={K} dh={dh}" + (" off=1" if off else "")
         run_v1(tag, F, F_T, n, n_src, K, dh, off)
+        run_efeat(tag, F, F_T, perm, n, n_src, K, dh, off)
         run_v2(tag, F, F_T, n, n_src, K, dh, off)
         run_dot(tag, F, F_T, n, n_src, K, dh, off)
 

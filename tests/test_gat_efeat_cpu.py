@@ -285,10 +285,14 @@ def test_ops_refuse_bad_shapes_before_the_library(pkg):
         ops.gat_backward_src_efeat(None, F, Z, s, s, s, s, o, M(2, 32), s, s, o, M(20, 3), M(3, 3), 4)
 
 
+GAT_KERNELS = ("gat_forward_kernel", "gat_backward_dst_kernel", "gat_backward_src_kernel")
+
+
 def test_no_instantiation_uses_scratch(tmp_path):
-    """csrc/gat_efeat.hip compiled for gfx950 to assembly: the resource metadata of all thirty instantiations -- three
-    kernels x gat_dispatch's five (VEC, NT, U) x DROP -- reports a private segment of zero bytes and no spilled vector
-    register (backward_dst holds sixteen P_e slots per lane on top of the plain kernel's state)"""
+    """csrc/gat_efeat.hip compiled for gfx950 to assembly: the resource metadata of all thirty instantiations -- the three
+    kernels of gat_kernels.h with the edge term, which their mangled names carry as the type gat_edge, x gat_dispatch's five
+    (VEC, NT, U) x DROP -- reports a private segment of zero bytes and no spilled vector register (backward_dst holds
+    sixteen P_e slots per lane on top of the plain kernel's state); the file instantiates none of the three without it"""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         pytest.skip("hipcc not available")
@@ -303,12 +307,22 @@ def test_no_instantiation_uses_scratch(tmp_path):
     for b in re.split(r"\n\s*- \.agpr_count:", "\n" + meta)[1:]:
         blk = ".agpr_count:" + b
         nm = re.search(r"\.name:\s+(\S+)", blk)
-        if not nm or "_efeat_kernel" not in nm.group(1):
+        if not nm or not any(kernel in nm.group(1) for kernel in GAT_KERNELS):
             continue
+        assert "gat_edge" in nm.group(1), nm.group(1)
         field = {k: int(re.search(r"\.%s:\s+(\d+)" % k, blk).group(1))
                  for k in ("private_segment_fixed_size", "vgpr_spill_count", "vgpr_count", "agpr_count")}
         seen[nm.group(1)] = field
         print(f"[gat_efeat.hip] {nm.group(1)}: {field}")
         assert field["private_segment_fixed_size"] == 0 and field["vgpr_spill_count"] == 0, (nm.group(1), field)
-    for kernel in ("gat_forward_efeat_kernel", "gat_backward_dst_efeat_kernel", "gat_backward_src_efeat_kernel"):
+    assert len(seen) == 30, sorted(seen)
+    for kernel in GAT_KERNELS:
         assert sum(kernel in k for k in seen) == 10, (kernel, sorted(seen))
+
+
+def test_the_file_defines_no_kernel():
+    """csrc/gat_efeat.hip holds entry points and the check of their edge operands: every kernel it launches is a template of
+    gat_kernels.h, the one the plain entry points instantiate"""
+    text = open(os.path.join(ROOT, "mg-gcn_amd", "csrc", "gat_efeat.hip")).read()
+    assert "__global__" not in text
+    assert '#include "gat_kernels.h"' in text
