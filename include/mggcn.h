@@ -524,6 +524,60 @@ void mggcn_gat_backward_src_rec_drop_f32(mggcn_stream_t stream, uint32_t n_rows,
                                          const float *ds_dst, uint32_t K, uint32_t dh, float slope, float *ds_src,
                                          float *G_Z, size_t ldgz, uint32_t threshold, float scale, uint64_t seed,
                                          uint32_t dropout_stream, uint32_t dst0, uint32_t src0);
+/* Long rows cut into slices (opt-in; gat(row_split=S)).  The plain sparse calls give one wave a whole row, so the longest
+ * row of the matrix bounds the time of the launch.  A mggcn_gat_split_plan holds, for ONE pattern, the item table of the
+ * SpMM's row-split plan: a row of len <= split + split / 2 entries is one item, a longer one ceil(len / split) contiguous
+ * slices with the boundaries beg + len k / parts, items longest first; plus the partial buffers of the slices,
+ * n_slots x max_width floats of accumulator rows and n_slots x max_heads x 2 floats of scalars.
+ *   create      from the HOST copy of indptr (n_rows + 1 values); split a multiple of 64, >= 64; 1 <= max_heads <=
+ *               MGGCN_GAT_MAX_HEADS and max_heads <= max_width <= MGGCN_GAT_MAX_WIDTH bound the K and K dh of the calls
+ *   num_items / num_split_rows / num_slots / bytes (device memory)     what was built
+ * Each _split call takes the argument list of its plain twin, then the plan, then drop: NULL, or the six values of the
+ * _drop twin (threshold == 0: no dropout).  One wave per item walks all K heads over its slice exactly as the plain kernel
+ * walks a row, with the plain kernel's (VEC, NT, U) variant.  An item that is a whole row stores as the plain kernel does:
+ * every output of an un-split row has the plain (or _drop) call's bits.  A slice stores a partial, and a second launch
+ * merges the slices of each split row in slot order, which is the order of the entries:
+ *   forward         slice s keeps (m_s, sum_s) of its one-pass softmax and its un-normalised accumulators acc_s;
+ *                   M = max_s m_s, sum = sum_s sum_s exp(m_s - M), out = (sum_s acc_s exp(m_s - M)) / sum, lse = M + log(sum).
+ *                   A slice is never empty: every m_s is finite and sum >= 1; a factor may underflow to 0, never a NaN.
+ *   backward_dst    every slice forms D[i, k] = G . out from the row's own data and its share of ds_dst[i, k] against it;
+ *                   the merge adds the shares and writes D once
+ *   backward_src    a slice keeps its share of ds_src and of sum_i alpha G; the merge adds both and then applies
+ *                   fmaf(ds_src, att[1], fmaf(ds_dst, att[0], acc)); ds_dst == NULL leaves its term out
+ * The mask of drop is keyed by (destination, source, head): the slices draw the words of the plain _drop calls.  No
+ * atomics: a result depends on the pattern, split and the operands alone -- not on the grid, the item order or the call.
+ * The plan must belong to the indptr passed (the kernels take every row's bounds from the plan): a plan of another n_rows,
+ * or a K or K dh above what it was created for, is refused.  The partial buffers make a plan stateful: like a
+ * mggcn_spmm_plan it may be in flight on ONE stream at a time.  fp32 only; no _efeat, _rec or _bf16 form. */
+typedef struct mggcn_gat_split_plan mggcn_gat_split_plan;
+typedef struct {
+    uint32_t threshold;
+    float scale;
+    uint64_t seed;
+    uint32_t dropout_stream, dst0, src0;
+} mggcn_gat_drop;
+mggcn_gat_split_plan *mggcn_gat_split_plan_create(uint32_t n_rows, const uint32_t *host_indptr, uint32_t split,
+                                                  uint32_t max_heads, uint32_t max_width);
+void mggcn_gat_split_plan_destroy(mggcn_gat_split_plan *plan);
+uint32_t mggcn_gat_split_plan_num_items(const mggcn_gat_split_plan *plan);
+uint32_t mggcn_gat_split_plan_num_split_rows(const mggcn_gat_split_plan *plan);
+uint32_t mggcn_gat_split_plan_num_slots(const mggcn_gat_split_plan *plan);
+size_t mggcn_gat_split_plan_bytes(const mggcn_gat_split_plan *plan);
+void mggcn_gat_forward_split_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                 const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst, const float *s_src,
+                                 uint32_t K, uint32_t dh, float slope, float *out, size_t ldo, float *lse,
+                                 const mggcn_gat_split_plan *plan, const mggcn_gat_drop *drop);
+void mggcn_gat_backward_dst_split_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                                      const uint32_t *indices, const float *Z, size_t ldz, const float *s_dst,
+                                      const float *s_src, const float *lse, const float *G, size_t ldg, const float *out,
+                                      size_t ldo, uint32_t K, uint32_t dh, float slope, float *D, float *ds_dst,
+                                      const mggcn_gat_split_plan *plan, const mggcn_gat_drop *drop);
+void mggcn_gat_backward_src_split_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *t_indptr,
+                                      const uint32_t *t_indices, const float *Z, size_t ldz, const float *s_dst,
+                                      const float *s_src, const float *lse, const float *D, const float *G, size_t ldg,
+                                      const float *att, const float *ds_dst, uint32_t K, uint32_t dh, float slope,
+                                      float *ds_src, float *G_Z, size_t ldgz, const mggcn_gat_split_plan *plan,
+                                      const mggcn_gat_drop *drop);
 /* Edge features in the GAT score (opt-in; PyG's GATConv(edge_dim=de) with lin_edge and att_edge folded into one [K x de]
  * matrix).  Each _efeat entry takes the argument list of its twin of the same name without _efeat (plain or _drop),
  * followed by (E, lde, att_edge, de), and backward_dst by (P_e, ldp) after those:

@@ -18,6 +18,12 @@ class engine_error(RuntimeError):
     """The HIP engine is unusable (library not built / no GPU)."""
 
 
+class gat_drop(ctypes.Structure):
+    """mggcn_gat_drop of include/mggcn.h: the attention dropout of a mggcn_gat_*_split_f32 call"""
+    _fields_ = [("threshold", c_uint32), ("scale", c_float), ("seed", c_uint64), ("dropout_stream", c_uint32),
+                ("dst0", c_uint32), ("src0", c_uint32)]
+
+
 u32p = ctypes.POINTER(c_uint32)
 f32p = ctypes.POINTER(c_float)
 vp = c_void_p
@@ -126,6 +132,20 @@ PROTOTYPES = {
     "mggcn_gat_backward_src_rec_drop_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, c_size_t, vp,
                                                    vp, c_uint32, c_uint32, c_float, vp, vp, c_size_t, c_uint32, c_float,
                                                    c_uint64, c_uint32, c_uint32, c_uint32]),
+    # the row-split plan of the GAT kernels and the _split entries: their plain twin's list, then (plan, drop) -- drop a
+    # pointer to a gat_drop (below) or None
+    "mggcn_gat_split_plan_create": (vp, [c_uint32, vp, c_uint32, c_uint32, c_uint32]),
+    "mggcn_gat_split_plan_destroy": (None, [vp]),
+    "mggcn_gat_split_plan_num_items": (c_uint32, [vp]),
+    "mggcn_gat_split_plan_num_split_rows": (c_uint32, [vp]),
+    "mggcn_gat_split_plan_num_slots": (c_uint32, [vp]),
+    "mggcn_gat_split_plan_bytes": (c_size_t, [vp]),
+    "mggcn_gat_forward_split_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, c_uint32, c_uint32, c_float,
+                                           vp, c_size_t, vp, vp, vp]),
+    "mggcn_gat_backward_dst_split_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, vp, c_size_t, vp,
+                                                c_size_t, c_uint32, c_uint32, c_float, vp, vp, vp, vp]),
+    "mggcn_gat_backward_src_split_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, vp, vp, vp, c_size_t, vp,
+                                                vp, c_uint32, c_uint32, c_float, vp, vp, c_size_t, vp, vp]),
     # the _efeat entries: their twin's list, then (E, lde, att_edge, de) and, for backward_dst, (P_e, ldp)
     "mggcn_gat_forward_efeat_f32": (None, [vp, c_uint32, c_uint32, vp, vp, vp, c_size_t, vp, vp, c_uint32, c_uint32, c_float,
                                            vp, c_size_t, vp, vp, c_size_t, vp, c_uint32]),

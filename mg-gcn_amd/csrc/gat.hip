@@ -17,7 +17,8 @@
 // VEC = 4 (16-byte loads) when dh % 4 == 0 and every dense operand and leading dimension is 16-byte aligned -- a float4
 // must not straddle two heads, so K * dh % 4 == 0 alone is not enough -- and VEC = 1 otherwise.
 // Heavy rows are slow here (one wave walks a whole row, ~21 k entries on the Reddit-shaped graph) but correct: cutting
-// them with a fixed-order combine is what the SpMM's plan does and is left to a plan for these kernels.
+// them with a fixed-order combine is what the SpMM's plan does, and gat_split.hip does it for these kernels on the same
+// item table (mggcn_gat_*_split_f32, gat(row_split=S)).  The kernels of this file stay the default.
 // Attention dropout (DROP = true, the mggcn_gat_*_drop_f32 entry points): the lane that owns an entry draws its keep bit
 // from Philox on (source, destination, head) next to the exp, and the factor q = keep ? 1 / (1 - p) : 0 travels to the
 // groups through the same __shfl as the weight.  The softmax itself (maximum, sum, lse) takes every entry.  Nothing is

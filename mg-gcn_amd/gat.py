@@ -180,6 +180,22 @@ sampled one (its lse belongs to a pattern the export does not walk).  Not built:
 carrying or renormalising values, dist_gat (it does not take the arguments), edge features under sampling, the export of a
 sampled forward, the state in checkpoints, the C++ layer and CLI.
 
+``row_split=S`` (None by default: nothing is built, allocated, launched or registered, the same bits as before) runs the
+three sparse kernels of variant="v1" over a plan that cuts every row of more than 1.5 S entries into slices of about S, one
+wave per slice, and merges a row's slices in the order of its entries (ops.gat_split_plan; csrc/gat_split.hip): the longest
+row no longer bounds the time of a launch.  S is a multiple of 64, at least 64.  The model keeps one plan for F and one for
+F^T, built from the host indptr at the first forward and shared by all layers (the pattern is the same).  A row the plan
+leaves whole has the default model's bits; a split row differs in the last bits (another order of the same sums), and two
+runs give the same bits.  Both dropouts, skip=, norm=, label_input=, loss="bce", splits and both Adam modes compose without
+special cases.  With fanout= / edge_keep= a training forward and its backward run over the device-resident sample with the
+plain kernels as always -- the host never sees the sampled sizes, and the plan belongs to the full pattern -- and every
+full-graph pass (a plain call, evaluate, predict, attention_weights(ctx, X), correct_and_smooth.predict, model_selector's
+clean validation) takes the split form.  row_split is an execution option: it is not written to checkpoints, and a file
+saved by either form loads into the other.  Refused with ValueError naming row_split before any device work: a value that
+is not None or a multiple of 64 that is >= 64, variant="v2" / "dot", agg_dtype="bf16" and edge_attr=.  Not built: GATv2,
+dot-product attention, bf16 images, edge features and the packed record under row_split, dist_gat (it does not take the
+argument), sage(aggr="max"), slicing a sampled pattern, the C++ layer and CLI, row_split as the default.
+
 Not covered: the halo and rounds schedules of dist_gcn, the C++ host layer and CLI.
 """
 from __future__ import annotations
@@ -270,6 +286,15 @@ class attention(gathered_images, param_owner):
     adam_fused = True
     m = v = None
     variant = "v1"
+    row_split = None            # gat(row_split=S): (S, F, F_T, heads, width) of the model -- its two matrices and the plans' limits
+
+    def _split(self, ctx: context, M: csr_matrix):
+        """M's split plan under gat(row_split=S) where M is one of the model's two full matrices; None without the option and
+        for an edge sample, which the plain kernels walk"""
+        rs = self.row_split
+        if rs is None or (M is not rs[1] and M is not rs[2]):
+            return None
+        return ops.gat_split_plan(ctx, M, rs[0], rs[3], rs[4])
 
     def __init__(self, name: str, n_dst: int, n_src: int, out: int, heads: int, slope: float = ops.GAT_SLOPE, device=None,
                  agg_dtype: str = "f32", images=None):
@@ -287,6 +312,11 @@ class attention(gathered_images, param_owner):
         ``drop``: attention dropout, the tuple of ops.gat_forward (None: the plain entry point)"""
         n = self.name
         ops.gat_scores(ctx, Z, self.att, self.s_dst, self.s_src, self.heads, n + "0_gat-scores")
+        plan = self._split(ctx, F)
+        if plan is not None:
+            ops.gat_forward_split(ctx, F, Z, self.s_dst, self.s_src, out, self.lse, self.heads, plan, self.slope,
+                                  n + "0_gat-forward", drop)
+            return
         if self.Z16 is None:
             ops.gat_forward(ctx, F, Z, self.s_dst, self.s_src, out, self.lse, self.heads, self.slope, n + "0_gat-forward", drop)
             return
@@ -298,7 +328,13 @@ class attention(gathered_images, param_owner):
                  G_Z: dn_matrix, drop=None) -> None:
         """G_Z = the gradient of Z and G_att, from G = the gradient of ``out``; ``drop``: what the forward was called with"""
         n = self.name
-        if self.Z16 is None:
+        plan, plan_T = self._split(ctx, F), self._split(ctx, F_T)
+        if plan is not None and plan_T is not None:
+            ops.gat_backward_dst_split(ctx, F, Z, self.s_dst, self.s_src, self.lse, G, out, self.D, self.ds_dst, self.heads,
+                                       plan, self.slope, n + "1_gat-backward-dst", drop)
+            ops.gat_backward_src_split(ctx, F_T, Z, self.s_dst, self.s_src, self.lse, self.D, G, self.att, self.ds_dst,
+                                       self.ds_src, G_Z, self.heads, plan_T, self.slope, n + "1_gat-backward-src", drop)
+        elif self.Z16 is None:
             ops.gat_backward_dst(ctx, F, Z, self.s_dst, self.s_src, self.lse, G, out, self.D, self.ds_dst, self.heads,
                                  self.slope, n + "1_gat-backward-dst", drop)
             ops.gat_backward_src(ctx, F_T, Z, self.s_dst, self.s_src, self.lse, self.D, G, self.att, self.ds_dst, self.ds_src,
@@ -319,6 +355,22 @@ class attention(gathered_images, param_owner):
 
     def init(self, att) -> None:
         self.att.init(np.asarray(att, dtype=np.float32))
+
+
+def check_row_split(row_split, variant: str, agg_dtype: str, edge_attr):
+    """option checking of row_split=, before any device work: None, or the slice length as an int.  ValueError naming
+    row_split for a value that is not a multiple of 64 and at least 64, for variant="v2" / "dot", agg_dtype="bf16" and
+    edge_attr= (the split kernels exist for the fp32 kernels of variant="v1" without an edge term)."""
+    if row_split is None:
+        return None
+    split = ops.check_row_split(row_split)
+    if variant != "v1":
+        raise ValueError(f'gat(variant="{variant}") has no row_split: the split kernels are built for variant="v1" only')
+    if agg_dtype != "f32":
+        raise ValueError(f'gat(agg_dtype="{agg_dtype}") has no row_split: the split kernels gather fp32 operands')
+    if edge_attr is not None:
+        raise ValueError("gat(edge_attr=...) has no row_split: the split kernels have no edge term")
+    return split
 
 
 def check_edge_attr(edge_attr, edge_weights, variant: str, agg_dtype: str, n_layers: int):
@@ -1065,7 +1117,10 @@ class gat(attention_model, sampling_option, model_base):
 
     gat(A, sizes, heads=4, attn_slope=0.2, loss="softmax", fused=True, weights=None, dropout=0.0, attn_dropout=0.0,
     variant="v1", skip=None, norm=None, skip_weights=None, label_input=0.0, label_weights=None,
-    agg_dtype="f32", edge_attr=None, edge_weights=None, fanout=None, edge_keep=1.0):
+    agg_dtype="f32", edge_attr=None, edge_weights=None, fanout=None, edge_keep=1.0, row_split=None):
+    ``row_split``: None, or the slice length S (a multiple of 64, >= 64) of the plan that cuts long rows for the sparse
+    kernels of variant="v1" -- see the module docstring; with fanout= / edge_keep= a training forward walks its sample with
+    the plain kernels and every full-graph pass takes the split form; ValueError naming row_split for what it refuses.
     ``fanout`` / ``edge_keep``: per-epoch edge sampling, set_sampling's fanout and keep -- see the module docstring and
     edge_sample.sampling_option; ValueError naming the argument for what it refuses.
     ``edge_attr`` / ``edge_weights``: edge features in the score of variant="v1", a numpy [A.nnz() x de] array in A's entry
@@ -1101,12 +1156,13 @@ class gat(attention_model, sampling_option, model_base):
                  loss: str = "softmax", fused: bool = True, weights=None, dropout: float = 0.0, attn_dropout: float = 0.0,
                  variant: str = "v1", skip=None, norm=None, skip_weights=None, label_input: float = 0.0,
                  label_weights=None, agg_dtype: str = "f32", edge_attr=None, edge_weights=None, fanout=None,
-                 edge_keep: float = 1.0):
+                 edge_keep: float = 1.0, row_split=None):
         self.agg_dtype = _check_agg_dtype(agg_dtype)             # option checks come before any device work
         self.sizes = [int(s) for s in sizes]
         self.heads = check_heads(self.sizes, heads)              # option checks come before any device work
         self._attn_dropout_params = check_dropout(attn_dropout, len(self.sizes) - 1)
         self.variant = check_variant(variant, float(attn_dropout))
+        self.row_split = check_row_split(row_split, self.variant, self.agg_dtype, edge_attr)
         E = check_edge_attr(edge_attr, edge_weights, self.variant, self.agg_dtype, len(self.sizes) - 1)
         if E is not None:
             self.edge_dim = int(E.shape[1])
@@ -1179,6 +1235,9 @@ class gat(attention_model, sampling_option, model_base):
             for i in range(n_layers):
                 self.layers_.append(gat_layer(f"{i}_", self.A_T, self.A, self.sizes[i], self.sizes[i + 1], self.heads[i],
                                               i + 1 < n_layers, self.attn_slope, i != 0, self.G_Z_buffer, **more))
+        if self.row_split is not None:                           # the plans themselves are built at the first forward
+            for layer in self.layers_:
+                layer.attn.row_split = (self.row_split, self.A_T, self.A, max(self.heads), max(self.sizes[1:]))
         self._adam = None
         self._make_sampler(self.A_T, self.A)                     # nothing unless sampling is on
         self.label_input_p = float(label_input)

@@ -7,6 +7,7 @@ Shape preconditions the reference only ``assert``s raise ``ValueError`` here.
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import numbers
 import os
@@ -554,10 +555,17 @@ def _gat_timed(ctx: context, timer: Optional[str], call) -> None:
     ctx.register_timer(timer, timer + "_0", timer + "_1")
 
 
-def _gat_call(ctx: context, timer: Optional[str], name: str, args, extra=None, image: bool = False, tail=None) -> None:
+def _gat_call(ctx: context, timer: Optional[str], name: str, args, extra=None, image: bool = False, tail=None,
+              split=None) -> None:
     """mggcn_<name>_f32(*args) under ``timer``; with ``extra`` (the tuple of _gat_drop_args) its _drop twin, which takes it
     after ``args``; ``image``: the _bf16 twin of either (the gathered operands of ``args`` are bf16 images); with ``tail``
-    (the tuple of _gat_efeat_args) the _efeat twin of either, fp32 only, which takes it last"""
+    (the tuple of _gat_efeat_args) the _efeat twin of either, fp32 only, which takes it last; with ``split`` (a
+    gat_split_buffer) the _split twin, fp32 only, which takes the plan and ``extra`` as one mggcn_gat_drop (or NULL)"""
+    if split is not None:
+        from ._lib import gat_drop
+        entry = getattr(ctx.lib, f"mggcn_{name}_split_f32")
+        d = None if extra is None else gat_drop(*extra)
+        return _gat_timed(ctx, timer, lambda: entry(*args, split.handle, None if d is None else ctypes.addressof(d)))
     entry = getattr(ctx.lib, f"mggcn_{name}{'' if tail is None else '_efeat'}{'' if extra is None else '_drop'}"
                              f"_{'bf16' if image else 'f32'}")
     _gat_timed(ctx, timer, lambda: entry(*args, *(extra or ()), *(tail or ())))
@@ -644,9 +652,11 @@ def gat_forward(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_s
 
 def _gat_forward(image: bool, ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
                  lse: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None,
-                 edge=None) -> None:
-    """the body of gat_forward, gat_forward_bf16 and gat_forward_efeat; ``image``: the gathered operands are bf16 images
-    (the _bf16 entry); ``edge`` = (E, att_edge): the edge term in the score (the _efeat entry)"""
+                 edge=None, split=None) -> None:
+    """the body of gat_forward, gat_forward_bf16, gat_forward_efeat and gat_forward_split; ``image``: the gathered operands
+    are bf16 images (the _bf16 entry); ``edge`` = (E, att_edge): the edge term in the score (the _efeat entry); ``split``:
+    F's gat_split_buffer (the _split entry)"""
+    _req_gat_split(split, F, heads, Z.m(), "gat forward")
     _req_roles("gat forward", image, (Z,))
     check_gat_heads(heads, Z.m(), "gat forward")
     _req(F.m() == Z.n() and out.shape() == (F.n(), Z.m()), "gat forward: shape mismatch")
@@ -657,7 +667,7 @@ def _gat_forward(image: bool, ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: 
     ip, ix, _ = F.device(ctx.device)
     args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), _ld(Z), s_dst.buffer(), s_src.buffer(), heads,
             Z.m() // heads, slope, out.buffer(), out.m(), lse.buffer())
-    _gat_call(ctx, timer, "gat_forward", args, extra, image, tail)
+    _gat_call(ctx, timer, "gat_forward", args, extra, image, tail, split)
 
 
 def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
@@ -671,10 +681,11 @@ def gat_backward_dst(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix
 
 def _gat_backward_dst(image: bool, ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix,
                       lse: dn_matrix, G: dn_matrix, out: dn_matrix, D: dn_matrix, ds_dst: dn_matrix, heads: int,
-                      slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None, edge=None) -> None:
-    """the body of gat_backward_dst, gat_backward_dst_bf16 and gat_backward_dst_efeat; ``image``: the gathered operands are
-    bf16 images (the _bf16 entry); ``edge`` = (E, att_edge, P_e): the edge term in the score and the output it adds (the
-    _efeat entry)"""
+                      slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None, edge=None, split=None) -> None:
+    """the body of gat_backward_dst, gat_backward_dst_bf16, gat_backward_dst_efeat and gat_backward_dst_split; ``image``: the
+    gathered operands are bf16 images (the _bf16 entry); ``edge`` = (E, att_edge, P_e): the edge term in the score and the
+    output it adds (the _efeat entry); ``split``: F's gat_split_buffer (the _split entry)"""
+    _req_gat_split(split, F, heads, Z.m(), "gat backward")
     _req_roles("gat backward", image, (Z,), (G, out))
     check_gat_heads(heads, Z.m(), "gat backward")
     _req(F.m() == Z.n() and G.shape() == (F.n(), Z.m()) and out.shape() == G.shape(), "gat backward: shape mismatch")
@@ -691,7 +702,7 @@ def _gat_backward_dst(image: bool, ctx: context, F: csr_matrix, Z: dn_matrix, s_
     ip, ix, _ = F.device(ctx.device)
     args = (ctx.stream(0), F.n(), F.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), _ld(Z), s_dst.buffer(), s_src.buffer(),
             lse.buffer(), G.buffer(), G.m(), out.buffer(), out.m(), heads, Z.m() // heads, slope, D.buffer(), ds_dst.buffer())
-    _gat_call(ctx, timer, "gat_backward_dst", args, extra, image, tail)
+    _gat_call(ctx, timer, "gat_backward_dst", args, extra, image, tail, split)
 
 
 def _req_gat_backward_src(F_T, Z, dst_scalars, s_src, G, att, ds_dst, ds_src, G_Z, heads: int, which: str) -> None:
@@ -718,9 +729,11 @@ def gat_backward_src(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matr
 def _gat_backward_src(image: bool, ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix,
                       lse: dn_matrix, D: dn_matrix, G: dn_matrix, att: dn_matrix, ds_dst: Optional[dn_matrix],
                       ds_src: dn_matrix, G_Z: dn_matrix, heads: int, slope: float = GAT_SLOPE, timer: Optional[str] = None,
-                      drop=None, edge=None) -> None:
-    """the body of gat_backward_src, gat_backward_src_bf16 and gat_backward_src_efeat; ``image``: the gathered operands are
-    bf16 images (the _bf16 entry); ``edge`` = (E, att_edge): the edge term in the score (the _efeat entry)"""
+                      drop=None, edge=None, split=None) -> None:
+    """the body of gat_backward_src, gat_backward_src_bf16, gat_backward_src_efeat and gat_backward_src_split; ``image``: the
+    gathered operands are bf16 images (the _bf16 entry); ``edge`` = (E, att_edge): the edge term in the score (the _efeat
+    entry); ``split``: F_T's gat_split_buffer (the _split entry)"""
+    _req_gat_split(split, F_T, heads, Z.m(), "gat backward")
     _req_roles("gat backward", image, (G,), (Z, G_Z))
     _req_gat_backward_src(F_T, Z, (s_dst, lse, D), s_src, G, att, ds_dst, ds_src, G_Z, heads, "the scores, lse, D and ds")
     tail = None if edge is None else _gat_efeat_args("gat backward", F_T, *edge, heads)
@@ -729,7 +742,7 @@ def _gat_backward_src(image: bool, ctx: context, F_T: csr_matrix, Z: dn_matrix, 
     args = (ctx.stream(0), F_T.n(), F_T.m(), ip.data_ptr(), ix.data_ptr(), Z.buffer(), Z.m(), s_dst.buffer(), s_src.buffer(),
             lse.buffer(), D.buffer(), G.buffer(), _ld(G), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads,
             Z.m() // heads, slope, ds_src.buffer(), G_Z.buffer(), G_Z.m())
-    _gat_call(ctx, timer, "gat_backward_src", args, extra, image, tail)
+    _gat_call(ctx, timer, "gat_backward_src", args, extra, image, tail, split)
 
 
 def _req_gat_rec(rec, rows: int, heads: int, what: str) -> None:
@@ -765,6 +778,93 @@ def gat_backward_src_rec(ctx: context, F_T: csr_matrix, Z: dn_matrix, rec, s_src
             G.buffer(), G.m(), att.buffer(), ds_dst.buffer() if ds_dst is not None else None, heads, Z.m() // heads, slope,
             ds_src.buffer(), G_Z.buffer(), G_Z.m())
     _gat_call(ctx, timer, "gat_backward_src_rec", args, extra)
+
+
+class gat_split_buffer:
+    """A mggcn_gat_split_plan: the item table that cuts the long rows of ONE pattern into slices of about ``split`` entries,
+    and the partial buffers of the slices.  gat_split_plan(ctx, F, split, max_heads, max_width) makes it; the three
+    ``*_split`` calls on F take it.  Like an spmm_buffer it may be in flight on one stream at a time."""
+
+    def __init__(self, lib, handle: int, F: csr_matrix, split: int, max_heads: int, max_width: int):
+        import weakref
+        self.lib, self.handle = lib, handle
+        self.matrix, self.version = weakref.ref(F), F._version
+        self.split, self.max_heads, self.max_width = split, max_heads, max_width
+
+    def num_items(self) -> int: return self.lib.mggcn_gat_split_plan_num_items(self.handle)
+    def num_split_rows(self) -> int: return self.lib.mggcn_gat_split_plan_num_split_rows(self.handle)
+    def num_slots(self) -> int: return self.lib.mggcn_gat_split_plan_num_slots(self.handle)
+    def nbytes(self) -> int: return self.lib.mggcn_gat_split_plan_bytes(self.handle)
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.lib.mggcn_gat_split_plan_destroy(self.handle)
+                self.handle = 0
+        except Exception:
+            pass
+
+
+def check_row_split(split) -> int:
+    """``split`` as an int; ValueError naming row_split unless it is a multiple of 64 and at least 64"""
+    _req(isinstance(split, numbers.Integral) and not isinstance(split, bool) and split >= 64 and split % 64 == 0,
+         f"row_split must be a multiple of 64 and at least 64, got {split!r}")
+    return int(split)
+
+
+def gat_split_plan(ctx: context, F: csr_matrix, split: int, max_heads: int, max_width: int) -> gat_split_buffer:
+    """The plan of F's pattern for the ``*_split`` calls, one per (matrix, device, split), kept on the matrix as its SpMM
+    plans are: built from the host indptr on the first request, and again when the matrix was edited in place or a
+    request exceeds the heads or the width (heads x width per head) it was built for."""
+    split = check_row_split(split)
+    _req(1 <= max_heads <= GAT_MAX_HEADS and max_heads <= max_width <= GAT_MAX_WIDTH,
+         f"gat split plan supports 1 <= heads <= {GAT_MAX_HEADS} and heads <= width <= {GAT_MAX_WIDTH}, got {max_heads} x {max_width}")
+    cache = F.__dict__.setdefault("_gat_split_plans", {})
+    buf = cache.get((ctx.rank, split))
+    if buf is None or buf.version != F._version or buf.max_heads < max_heads or buf.max_width < max_width:
+        if buf is not None:
+            max_heads, max_width = max(max_heads, buf.max_heads), max(max_width, buf.max_width)
+        ctx.set()
+        h = ctx.lib.mggcn_gat_split_plan_create(F.n(), F.indptr.ctypes.data, split, int(max_heads), int(max_width))
+        buf = cache[(ctx.rank, split)] = gat_split_buffer(ctx.lib, h, F, split, int(max_heads), int(max_width))
+    return buf
+
+
+def _req_gat_split(plan, F, heads: int, width: int, what: str) -> None:
+    """a ``*_split`` call's plan belongs to the matrix it walks and covers its heads and width; the library would exit"""
+    if plan is None:
+        return
+    _req(isinstance(plan, gat_split_buffer) and plan.matrix() is F and plan.version == F._version,
+         f"{what}: the split plan belongs to another matrix (ops.gat_split_plan(ctx, F, ...) of the matrix walked)")
+    _req(heads <= plan.max_heads and width <= plan.max_width,
+         f"{what}: {heads} heads x {width} columns exceed the plan's {plan.max_heads} x {plan.max_width}")
+
+
+def gat_forward_split(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, out: dn_matrix,
+                      lse: dn_matrix, heads: int, plan: gat_split_buffer, slope: float = GAT_SLOPE,
+                      timer: Optional[str] = None, drop=None) -> None:
+    """gat_forward over F's split plan (mggcn_gat_forward_split_f32): one wave per slice of a long row, the slices merged in
+    the order of the entries.  Rows the plan leaves whole get gat_forward's bits; ``drop`` as gat_forward takes it."""
+    _req(plan is not None, "gat forward: gat_forward_split needs a plan")
+    _gat_forward(False, ctx, F, Z, s_dst, s_src, out, lse, heads, slope, timer, drop, split=plan)
+
+
+def gat_backward_dst_split(ctx: context, F: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
+                           G: dn_matrix, out: dn_matrix, D: dn_matrix, ds_dst: dn_matrix, heads: int,
+                           plan: gat_split_buffer, slope: float = GAT_SLOPE, timer: Optional[str] = None, drop=None) -> None:
+    """gat_backward_dst over F's split plan (mggcn_gat_backward_dst_split_f32)"""
+    _req(plan is not None, "gat backward: gat_backward_dst_split needs a plan")
+    _gat_backward_dst(False, ctx, F, Z, s_dst, s_src, lse, G, out, D, ds_dst, heads, slope, timer, drop, split=plan)
+
+
+def gat_backward_src_split(ctx: context, F_T: csr_matrix, Z: dn_matrix, s_dst: dn_matrix, s_src: dn_matrix, lse: dn_matrix,
+                           D: dn_matrix, G: dn_matrix, att: dn_matrix, ds_dst: Optional[dn_matrix], ds_src: dn_matrix,
+                           G_Z: dn_matrix, heads: int, plan: gat_split_buffer, slope: float = GAT_SLOPE,
+                           timer: Optional[str] = None, drop=None) -> None:
+    """gat_backward_src over F_T's split plan (mggcn_gat_backward_src_split_f32); ``plan`` is F_T's, not F's"""
+    _req(plan is not None, "gat backward: gat_backward_src_split needs a plan")
+    _gat_backward_src(False, ctx, F_T, Z, s_dst, s_src, lse, D, G, att, ds_dst, ds_src, G_Z, heads, slope, timer, drop,
+                      split=plan)
 
 
 def gat_scores_backward(ctx: context, ds_dst: dn_matrix, Z_dst: dn_matrix, ds_src: dn_matrix, Z_src: dn_matrix,
