@@ -922,6 +922,32 @@ void mggcn_edge_sample_compact_val_f32(mggcn_stream_t stream, uint32_t n_rows, c
                                        const float *values, const uint32_t *thr, int transposed, uint32_t row0, uint32_t col0,
                                        uint64_t seed, uint32_t epoch, const float *scale, int scale_self,
                                        const uint32_t *out_indptr, uint32_t *out_indices, float *out_values);
+/* The EXACT fan-out (csrc/edge_select.hip): the thresholds themselves written on the device, one per-row order-statistic
+ * select over the words the keep rule draws.  Over F only (rows are destinations, row r is destination row0 + r, column c is
+ * source col0 + c); w(i, j) is word 0 of Philox4x32-10((j, i, 0xC0000000, epoch), seed) as above.  The candidates of row i are
+ * its entries with i != j, each as it lies -- a duplicated pair counts twice and carries the same word -- and m_i their number:
+ *     m_i <= k:   thr[i] = t_keep
+ *     otherwise:  thr[i] = min(s_i, t_keep, 0xFFFFFFFE),  s_i the (k+1)-th smallest candidate word (multiset order, 1-based).
+ * t_keep is the DropEdge threshold min(floor(keep 2^32), 2^32 - 1).  Under the keep rule above a destination then keeps all
+ * its self entries and at most k others: exactly min(k, #{w < t_keep}) unless the k-th and (k+1)-th smallest words are equal
+ * (a duplicated pair at the boundary, or a 32-bit collision), when it keeps fewer, never more; with keep < 1 this is
+ * "DropEdge, then at most k of the survivors".  thr is a pure function of (seed, epoch, the row's multiset of pairs): not of
+ * the entry order, the grid, the split of the rows between calls (indptr + r0, thr + r0, row0 = r0) or the path a row took.
+ * One wave per row: rows of at most 64 R entries hold their words in registers, drawn once, and find s_i by a bitwise descent
+ * over the value (ballots and scalar population counts); longer rows -- every row when force_stream != 0 -- histogram 8-bit
+ * digits in LDS, drawing again per pass, and finish in registers once the survivors fit.  Any row length up to 2^32 - 1.  No
+ * global atomics, no scratch, nothing of size nnz, nothing written but thr[0 .. n_rows).  n_rows == 0 returns without a
+ * launch; k == 0 is a precondition failure.
+ *   _reg_entries   64 R of the library as built (R = MGGCN_EDGE_SELECT_R): the longest row of the register path.
+ *   _r_u32         the same kernel at R in {4, 8, 12, 16}: the measurement behind the choice of R (same thr for every R). */
+#define MGGCN_EDGE_SELECT_R 8
+void mggcn_edge_sample_select_u32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr, const uint32_t *indices,
+                                  uint32_t k, uint32_t t_keep, uint32_t row0, uint32_t col0, uint64_t seed, uint32_t epoch,
+                                  int force_stream, uint32_t *thr);
+uint32_t mggcn_edge_sample_select_reg_entries(void);
+void mggcn_edge_sample_select_r_u32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr, const uint32_t *indices,
+                                    uint32_t k, uint32_t t_keep, uint32_t row0, uint32_t col0, uint64_t seed, uint32_t epoch,
+                                    int force_stream, uint32_t R, uint32_t *thr);
 
 /* The row-split SpMM over a device-resident CSR with a plan built ON THE DEVICE (csrc/spmm_dev.hip): what multiplies by the
  * edge sample above, a matrix the host never sees.

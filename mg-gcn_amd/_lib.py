@@ -198,6 +198,11 @@ PROTOTYPES = {
     "mggcn_edge_sample_rowscale_f32": (None, [vp, c_uint32, vp, vp, vp, vp, c_uint32, c_uint32, c_uint64, c_uint32, vp, vp]),
     "mggcn_edge_sample_compact_val_f32": (None, [vp, c_uint32, vp, vp, vp, vp, c_int, c_uint32, c_uint32, c_uint64, c_uint32,
                                                  vp, c_int, vp, vp, vp]),
+    "mggcn_edge_sample_select_u32": (None, [vp, c_uint32, vp, vp, c_uint32, c_uint32, c_uint32, c_uint32, c_uint64, c_uint32,
+                                            c_int, vp]),
+    "mggcn_edge_sample_select_reg_entries": (c_uint32, []),
+    "mggcn_edge_sample_select_r_u32": (None, [vp, c_uint32, vp, vp, c_uint32, c_uint32, c_uint32, c_uint32, c_uint64, c_uint32,
+                                              c_int, c_uint32, vp]),
     "mggcn_spmm_dev_plan_capacity": (None, [c_uint32, vp, c_uint32, vp]),
     "mggcn_spmm_dev_plan_create": (vp, [c_uint32, vp, c_uint32, c_uint32]),
     "mggcn_spmm_dev_plan_destroy": (None, [vp]),

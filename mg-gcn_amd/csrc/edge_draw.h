@@ -1,0 +1,31 @@
+// edge_draw.h -- the one draw of the per-epoch edge sample, shared by edge_sample.hip (the keep bit of count / compact /
+// rowscale / compact_val) and edge_select.hip (the per-row threshold of the exact fan-out): entry (destination i, source j),
+// global vertex numbers, draws word 0 of Philox4x32-10((j, i, 0xC0000000, epoch), seed) and is kept iff
+//     i == j   or   t_i == 0xFFFFFFFF   or   that word < t_i.
+#pragma once
+
+#include "philox.h"
+
+constexpr uint32_t kSampleDomain = 0xC0000000u;      // counter word 2: apart from feature dropout (row >> 32), attention
+                                                     // dropout (0x80000000 | k >> 2) and the label mask (word 0 = 0xFFFFFFFF)
+
+__device__ __forceinline__ uint32_t sample_word(uint32_t i, uint32_t j, uint32_t epoch, uint32_t k0, uint32_t k1) {
+    return philox4x32_10(j, i, kSampleDomain, epoch, k0, k1).w[0];
+}
+
+struct sample_draw {
+    const uint32_t *__restrict__ thr;
+    uint32_t row0, col0, k0, k1, epoch;
+    bool transposed;
+
+    // the row's own threshold where the rows are destinations (read once per row)
+    __device__ __forceinline__ uint32_t row_threshold(size_t row) const { return transposed ? 0u : thr[row]; }
+
+    __device__ __forceinline__ bool keep(size_t row, uint32_t c, uint32_t t_row) const {
+        const uint32_t r = row0 + (uint32_t)row, g = col0 + c;
+        const uint32_t i = transposed ? g : r, j = transposed ? r : g;
+        const uint32_t t = transposed ? thr[c] : t_row;
+        if (i == j || t == 0xFFFFFFFFu) return true;
+        return sample_word(i, j, epoch, k0, k1) < t;
+    }
+};

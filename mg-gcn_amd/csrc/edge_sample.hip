@@ -25,30 +25,11 @@
 #include <algorithm>
 
 #include "common.h"
-#include "philox.h"
+#include "edge_draw.h"
 
 namespace {
 
-constexpr uint32_t kSampleDomain = 0xC0000000u;      // counter word 2: apart from feature dropout (row >> 32), attention
-                                                     // dropout (0x80000000 | k >> 2) and the label mask (word 0 = 0xFFFFFFFF)
 constexpr uint32_t kScanBlock = 256;
-
-struct sample_draw {
-    const uint32_t *__restrict__ thr;
-    uint32_t row0, col0, k0, k1, epoch;
-    bool transposed;
-
-    // the row's own threshold where the rows are destinations (read once per row)
-    __device__ __forceinline__ uint32_t row_threshold(size_t row) const { return transposed ? 0u : thr[row]; }
-
-    __device__ __forceinline__ bool keep(size_t row, uint32_t c, uint32_t t_row) const {
-        const uint32_t r = row0 + (uint32_t)row, g = col0 + c;
-        const uint32_t i = transposed ? g : r, j = transposed ? r : g;
-        const uint32_t t = transposed ? thr[c] : t_row;
-        if (i == j || t == 0xFFFFFFFFu) return true;
-        return philox4x32_10(j, i, kSampleDomain, epoch, k0, k1).w[0] < t;
-    }
-};
 
 __device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
 #pragma unroll

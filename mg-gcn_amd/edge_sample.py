@@ -12,11 +12,26 @@ training forward e iff
     word 0 of Philox4x32-10(counter = (j, i, 0xC0000000, e), key = (seed & 0xFFFFFFFF, seed >> 32)) < t_i.
 
 The third counter word keeps the draw apart from feature dropout (row >> 32), attention dropout (0x80000000 | k >> 2) and
-the label mask (first word 0xFFFFFFFF) under one seed.  Duplicate entries share one bit.  ``fanout`` is an EXPECTED fan-out,
-not an exact one: "k of deg" cannot be decided from the transposed side without walking the destination's whole row, and
-the bit must be a function of the pair alone for F and F^T to be sampled independently ("row = destination" on F, "column =
-destination" on F^T) and still be each other's transpose, entry for entry.  Each keeps the entry order of the matrix it was
-drawn from (stable compaction), so every downstream kernel's summation order is a function of the sample alone.
+the label mask (first word 0xFFFFFFFF) under one seed.  Duplicate entries share one bit.  ``fanout`` is an EXPECTED fan-out
+unless ``exact=`` (fanout_exact=) asks for an exact one, below: "k of deg" cannot be decided as a keep BIT from the transposed
+side without walking the destination's whole row, and the bit must be a function of the pair and the destination's threshold
+alone for F and F^T to be sampled independently ("row = destination" on F, "column = destination" on F^T) and still be each
+other's transpose, entry for entry.  Each keeps the entry order of the matrix it was drawn from (stable compaction), so every
+downstream kernel's summation order is a function of the sample alone.
+
+The exact fan-out (``exact=True``; GraphSAGE's, NeighborLoader's and sample_neighbors' "k neighbours per destination").  What
+cannot be decided as a bit can be decided as a THRESHOLD: at the top of every draw one kernel over F (ops.edge_sample_select,
+csrc/edge_select.hip, timer ``sample-select``) writes t_i on the device as the (k+1)-th smallest word of row i -- m_i the
+row's entries with i != j, duplicates counted: t_i = t_keep where m_i <= k, min(that word, t_keep, 0xFFFFFFFE) otherwise,
+t_keep = min(floor(keep 2^32), 2^32 - 1) -- and "the k smallest words win" IS exact-k sampling under the rule above.  Everything
+after it (count, scan, compact, rowscale, the plan, every kernel that walks the sample, the transpose property) runs as it
+is and reads that buffer; no host thresholds are uploaded.  A destination keeps all its self entries and at most k others:
+exactly min(k, #{words < t_keep}) unless the k-th and (k+1)-th smallest words are equal (a duplicated pair at the boundary or
+a 32-bit collision), when it keeps fewer, never more.  With keep < 1 this is "DropEdge, then at most k of the survivors".
+t_i is a function of (seed, epoch, the row's multiset of pairs) alone.  "row" rescaling composes as it is (rowscale reads the
+thresholds on the device, after the select); "inverse" multiplies a kept entry with i != j by fp32(m_i / min(k, m_i))
+(exact_inverse_factors: once per setting, in float64, from F's pattern), which is the inverse inclusion probability for
+keep == 1.0 only -- with keep < 1 there is no closed form worth shipping and the combination is refused.
 
 The kernels (csrc/edge_sample.hip: ops.edge_sample_count / _scan / _compact) count the kept entries per row, scan the counts
 into an indptr and draw the same bits again to write the kept columns; nothing of size nnz is stored between the passes,
@@ -53,6 +68,19 @@ def check_sampling(fanout, keep):
     return (None if fanout is None else int(fanout)), float(keep)
 
 
+def check_exact(exact, fanout, keep=1.0, rescale=None) -> bool:
+    """option checking of exact= (fanout_exact=), before any device work: ValueError naming the argument for a value that is
+    not a bool, for True without a fanout, and for True with rescale "inverse" at keep < 1 (no closed-form factor)"""
+    if not isinstance(exact, bool):
+        raise ValueError(f"edge sampling: exact (fanout_exact) must be a bool, got {exact!r}")
+    if exact and fanout is None:
+        raise ValueError("edge sampling: exact (fanout_exact) = True needs a fanout, got fanout=None")
+    if exact and rescale == "inverse" and keep != 1.0:
+        raise ValueError(f'edge sampling: exact (fanout_exact) = True with edge_rescale (rescale) "inverse" needs keep (edge_keep) '
+                         f"== 1.0, got {keep}: the inclusion probability of DropEdge-then-k has no closed form")
+    return exact
+
+
 def sampling_on(fanout, keep) -> bool:
     """fanout=None, keep=1.0 is OFF (no sampler, no buffer, no launch); any other setting draws, even if every q_i is 1"""
     return fanout is not None or keep != 1.0
@@ -75,6 +103,16 @@ def inverse_factors(thr) -> np.ndarray:
     np.divide(4294967296.0, t, out=out, where=t > 0)
     out[t == 4294967295.0] = 1.0
     return out.astype(np.float32)
+
+
+def exact_inverse_factors(indptr, indices, k: int) -> np.ndarray:
+    """the Horvitz-Thompson factor of the exact fan-out at keep == 1 per destination: fp32(m_i / min(k, m_i)) computed in
+    float64, m_i the entries of row i of the square forward pattern off the diagonal (duplicates counted); 1 where m_i == 0"""
+    ip = np.asarray(indptr).astype(np.int64)
+    rows = np.repeat(np.arange(ip.size - 1, dtype=np.int64), np.diff(ip))
+    off = rows != np.asarray(indices)[: rows.size].astype(np.int64)
+    m = np.bincount(rows[off], minlength=ip.size - 1).astype(np.float64)
+    return (np.maximum(m, 1.0) / np.maximum(np.minimum(float(k), m), 1.0)).astype(np.float32)
 
 
 def refuse_sampling(model: str, fanout, keep, why: str = "a weighted sum needs to be told how the kept values are rescaled: "
@@ -137,7 +175,7 @@ class sampled_csr:
 
 
 class edge_sampler:
-    """edge_sampler(F, F_T, fanout=None, keep=1.0, rescale=None, max_d=128): the sample of a square forward matrix ``F``
+    """edge_sampler(F, F_T, fanout=None, keep=1.0, rescale=None, max_d=128, exact=False): the sample of a square forward matrix ``F``
     (csr_matrix; rows are destinations) and of its transpose ``F_T``.  Owns the thresholds on the device and, for each of the
     two matrices, a counts buffer, an indptr buffer and an indices buffer of the parent's nnz -- capacity equals nnz, so there
     is no overflow case (the Reddit-shaped graph: 2 x 459 MB) -- all made with the first draw, when the device is known.
@@ -149,21 +187,36 @@ class edge_sampler:
     beside the indices, one scale array per destination -- written by the count pass over F ("row": ops.edge_sample_rowscale)
     or uploaded with the thresholds ("inverse": inverse_factors) -- and one device-built row-split plan per matrix
     (ops.spmm_dev_plan at the parent's capacity and ``max_d``), built right after compact under ``sample-plan``.  The pair's
-    device() is then (indptr, indices, values) and its ``plan`` what ops.spmm_dev takes."""
+    device() is then (indptr, indices, values) and its ``plan`` what ops.spmm_dev takes.
 
-    def __init__(self, F: csr_matrix, F_T: csr_matrix, fanout=None, keep: float = 1.0, rescale=None, max_d: int = 128):
+    ``exact`` (see the module's text): the thresholds are not the host's but written on the device at the top of every draw,
+    by ONE launch over F (ops.edge_sample_select, timer ``sample-select``), so that every destination keeps its self entries
+    and its ``fanout`` smallest words; count -> scan -> compact (-> plan) then run unchanged on that buffer.  ``thr_host`` is
+    None in this mode and "inverse" uploads exact_inverse_factors.  With exact=False nothing differs from a sampler without
+    the argument: the same launches, timers, buffers and bits."""
+
+    def __init__(self, F: csr_matrix, F_T: csr_matrix, fanout=None, keep: float = 1.0, rescale=None, max_d: int = 128,
+                 exact: bool = False):
         if not (F.n() == F.m() == F_T.n() == F_T.m()):
             raise ValueError(f"edge sampling needs a square matrix and its transpose, got {F.shape()} and {F_T.shape()}")
         self.F, self.F_T = F, F_T
         self.rescale, self.max_d = check_rescale(rescale), int(max_d)
         self._thr = self._scale = self._bufs = self.pair = self.plans = None
-        self.set(fanout, keep)
+        self.set(fanout, keep, exact)
 
-    def set(self, fanout, keep) -> None:
-        """new thresholds (on the host; uploaded by the next draw)"""
-        self.fanout, self.keep = check_sampling(fanout, keep)
-        self.thr_host = thresholds(self.F.indptr, self.fanout, self.keep)
-        self.inv_host = inverse_factors(self.thr_host) if self.rescale == "inverse" else None
+    def set(self, fanout, keep, exact: bool = False) -> None:
+        """new thresholds (on the host; uploaded by the next draw) -- with ``exact`` the DropEdge threshold alone, the rest is
+        the select's every draw"""
+        fanout, keep = check_sampling(fanout, keep)
+        self.exact = check_exact(exact, fanout, keep, self.rescale)
+        self.fanout, self.keep = fanout, keep
+        if self.exact:
+            self.thr_host, self.t_keep = None, int(thresholds(np.zeros(2, dtype=np.int64), None, self.keep)[0])
+            self.inv_host = (exact_inverse_factors(self.F.indptr, self.F.indices, self.fanout)
+                             if self.rescale == "inverse" else None)
+        else:
+            self.thr_host = thresholds(self.F.indptr, self.fanout, self.keep)
+            self.inv_host = inverse_factors(self.thr_host) if self.rescale == "inverse" else None
         self._thr = None
 
     def _allocate(self, ctx: context) -> None:
@@ -186,13 +239,17 @@ class edge_sampler:
             self._allocate(ctx)
         if self._thr is None:
             import torch
-            self._thr = torch.from_numpy(self.thr_host.view(np.int32)).to(ctx.device)
+            self._thr = (torch.empty(max(self.F.n(), 1), dtype=torch.int32, device=ctx.device) if self.exact
+                         else torch.from_numpy(self.thr_host.view(np.int32)).to(ctx.device))
             if self.inv_host is not None:
                 self._scale.copy_(torch.from_numpy(self.inv_host))
             torch.cuda.current_stream(self._thr.device).synchronize()      # visible to every stream afterwards
         n = self.F.n()
         mats = [(M.device(ctx.device), t, b) for t, (M, b) in enumerate(zip((self.F, self.F_T), self._bufs))]
         kw = dict(seed=seed, epoch=epoch)
+        if self.exact:                                   # this epoch's thresholds: one launch, over F
+            ops.edge_sample_select(ctx, n, mats[0][0][0], mats[0][0][1], self.fanout, self.t_keep, self._thr,
+                                   timer="sample-select", **kw)
 
         def timed(name, call):
             ctx.record(name + "_0", 0)
@@ -233,6 +290,7 @@ class sampling_option:
     sample_fanout = None
     sample_keep = 1.0
     sample_seed = sample_epoch = 0
+    sample_exact = False                # fanout is an exact fan-out (edge_sampler's ``exact``), not an expected one
     sampler = None
     _sample_matrices = None
     sampled_forward = False             # the most recent forward ran on a sample
@@ -242,32 +300,49 @@ class sampling_option:
     def _refuse_sampling(self, fanout, keep) -> None:
         """hook: ValueError for a model option that does not compose with sampling (called only when sampling is on)"""
 
-    def _init_sampling(self, fanout, keep) -> None:
+    def _rescale_checked(self):
+        return self.edge_rescale
+
+    def _init_sampling(self, fanout, keep, exact: bool = False) -> None:
         fanout, keep = check_sampling(fanout, keep)
+        exact = check_exact(exact, fanout, keep, self._rescale_checked())
         if sampling_on(fanout, keep):
             self._refuse_sampling(fanout, keep)
-        self.sample_fanout, self.sample_keep = fanout, keep
+        self.sample_fanout, self.sample_keep, self.sample_exact = fanout, keep, exact
+
+    def _exact_checked(self, exact, fanout, keep) -> bool:
+        """set_sampling's ``exact`` after its checks: None is the model's ``sample_exact``, which rests while fanout is None
+        (set_sampling() still switches sampling off); a given value is checked as the constructor's"""
+        if exact is None:
+            check_exact(self.sample_exact and fanout is not None, fanout, keep, self._rescale_checked())
+            return self.sample_exact
+        return check_exact(exact, fanout, keep, self._rescale_checked())
 
     def _new_sampler(self, fanout, keep) -> edge_sampler:
-        return edge_sampler(*self._sample_matrices, fanout, keep, rescale=self.edge_rescale, max_d=self._sample_max_d)
+        return edge_sampler(*self._sample_matrices, fanout, keep, rescale=self.edge_rescale, max_d=self._sample_max_d,
+                            exact=self.sample_exact and fanout is not None)
 
     def _make_sampler(self, F: csr_matrix, F_T: csr_matrix) -> None:
         self._sample_matrices = (F, F_T)
         if sampling_on(self.sample_fanout, self.sample_keep):
             self.sampler = self._new_sampler(self.sample_fanout, self.sample_keep)
 
-    def set_sampling(self, fanout=None, keep: float = 1.0, seed: int = 0, epoch: int = 0) -> None:
-        """fanout: None or the expected fan-out per destination (an integer >= 1); keep: the DropEdge keep probability in
-        (0, 1]; seed: 64 bits; epoch: the number the next training forward gets (set_sampling(..., epoch=e) replays training
-        forward e).  fanout=None, keep=1.0 switches sampling off and frees the buffers.  ValueError naming the argument,
-        before any device work and before anything is stored."""
+    def set_sampling(self, fanout=None, keep: float = 1.0, seed: int = 0, epoch: int = 0, exact=None) -> None:
+        """fanout: None or the fan-out per destination (an integer >= 1) -- the expected one, or with ``exact`` True the exact
+        one (None keeps the model's ``sample_exact``, which rests while fanout is None); keep: the DropEdge keep probability
+        in (0, 1]; seed: 64 bits; epoch: the number the next training forward gets (set_sampling(..., epoch=e) replays
+        training forward e).  fanout=None, keep=1.0 switches sampling off and frees the buffers.  ValueError naming the
+        argument, before any device work and before anything is stored."""
         fanout, keep = check_sampling(fanout, keep)
+        exact = self._exact_checked(exact, fanout, keep)
         if sampling_on(fanout, keep):
             self._refuse_sampling(fanout, keep)
+        self.sample_exact = exact
+        if sampling_on(fanout, keep):
             if self.sampler is None or self.sampler.rescale != self.edge_rescale:
                 self.sampler = self._new_sampler(fanout, keep)
             else:
-                self.sampler.set(fanout, keep)
+                self.sampler.set(fanout, keep, exact and fanout is not None)
         else:
             self.sampler = None
         self.sample_fanout, self.sample_keep = fanout, keep
@@ -307,19 +382,21 @@ class rescaled_sampling_option(sampling_option):
         finally:
             self._rescale_wanted = ()
 
-    def _init_sampling(self, fanout, keep, rescale=None) -> None:
-        self._checked(fanout, keep, rescale, lambda f, k: sampling_option._init_sampling(self, f, k))
+    def _init_sampling(self, fanout, keep, rescale=None, exact: bool = False) -> None:
+        self._checked(fanout, keep, rescale, lambda f, k: sampling_option._init_sampling(self, f, k, exact))
         self.edge_rescale = rescale
 
-    def set_sampling(self, fanout=None, keep: float = 1.0, seed: int = 0, epoch: int = 0, rescale=None) -> None:
+    def set_sampling(self, fanout=None, keep: float = 1.0, seed: int = 0, epoch: int = 0, rescale=None, exact=None) -> None:
         """sampling_option.set_sampling, and ``rescale``: None keeps the model's ``edge_rescale``, "row" / "inverse" replace it.
-        A weighted-sum model whose edge_rescale is None refuses any setting that is on, by the argument's name."""
+        A weighted-sum model whose edge_rescale is None refuses any setting that is on, by the argument's name; "inverse" with
+        an exact fan-out needs keep == 1.0."""
         rescale = self.edge_rescale if rescale is None else rescale
 
         def check(f, k):
             f, k = check_sampling(f, k)
+            self._exact_checked(exact, f, k)
             if sampling_on(f, k):
                 self._refuse_sampling(f, k)
         self._checked(fanout, keep, rescale, check)
         self.edge_rescale = rescale
-        sampling_option.set_sampling(self, fanout, keep, seed, epoch)
+        sampling_option.set_sampling(self, fanout, keep, seed, epoch, exact)

@@ -172,11 +172,16 @@ when off).  A plain call, evaluate(), predict(), attention_weights(ctx, X) and c
 graph with the bits they always had; model_selector defaults to clean=True, so its validation number is the full graph's.
 All three variants, both dropouts (attention dropout is keyed by vertex numbers, not entry positions), skip=, norm=,
 label_input=, loss="bce", splits, agg_dtype="bf16" and both Adam modes compose without special cases.  ``fanout`` is an
-EXPECTED fan-out, not an exact one.  Checkpoints do not store the sampling state: save works, load leaves the state alone,
+EXPECTED fan-out unless set_sampling(..., exact=True) makes it exact (``sample_exact``; the constructor's parameter list is
+pinned by tests/test_gat_split_cpu.py and does not take the switch -- sage and gcn have ``fanout_exact=``): every destination then keeps
+its self-loops and exactly min(fanout, its other entries) sources -- the ``fanout`` smallest Philox words of its row, found by
+a per-row select on the device at the top of every draw (edge_sample.py; csrc/edge_select.hip; timer ``sample-select``),
+after which the sample is drawn, walked and transposed as before.  Checkpoints do not store the sampling state: save works, load leaves the state alone,
 and a resumed run calls set_sampling(..., epoch=...) itself.  Refused with ValueError naming the argument before any device
 work: a keep outside (0, 1], a fanout that is not None or an integer >= 1, sampling together with edge_attr= (the rows of E
 are aligned to entry positions), and attention_weights(ctx) / gat_layer.alpha without X when the most recent forward was a
-sampled one (its lse belongs to a pattern the export does not walk).  Not built: exact-k sampling, per-layer samples,
+sampled one (its lse belongs to a pattern the export does not walk), an ``exact`` that is not a bool, and True
+without a fanout.  Not built: per-layer samples,
 carrying or renormalising values, dist_gat (it does not take the arguments), edge features under sampling, the export of a
 sampled forward, the state in checkpoints, the C++ layer and CLI.
 

@@ -1103,20 +1103,23 @@ class gcn(rescaled_sampling_option, model_base):
     save(ctx, path, optimizer=True) / load(ctx, path) / predict(ctx, X): see checkpoint.checkpoint_option -- the file
     carries the configuration, the parameters, Adam's state and the dropout state, and no execution option.
 
-    ``fanout`` / ``edge_keep`` / ``edge_rescale`` / set_sampling(fanout, keep, seed, epoch, rescale): per-epoch edge sampling
+    ``fanout`` / ``edge_keep`` / ``edge_rescale`` / ``fanout_exact`` / set_sampling(fanout, keep, seed, epoch, rescale, exact): per-epoch edge sampling
     (edge_sample.py).  gcn is a weighted sum, so it samples only when told how the kept values are rescaled: with
     ``edge_rescale`` None (the default) any setting that is on is refused with ValueError naming the argument; "row" keeps every
     row sum (the mean over the sampled neighbours on the row-stochastic matrix built here), "inverse" divides by the keep
     probability.  A training forward then multiplies, forward and backward, by the pair of the epoch through the row-split SpMM
     on a plan built on the device (sparse_linear.sample, ops.spmm_dev); every other forward runs on the full graph with the
-    bits it has without sampling.  hoist_first_aggregation does not compose: the hoisted product belongs to the full graph."""
+    bits it has without sampling.  ``fanout_exact=True`` makes ``fanout`` an exact fan-out (every destination keeps its self-loops
+    and exactly min(fanout, its other entries) sources: a per-row select on the device at the top of every draw, edge_sample.py);
+    "inverse" then scales by m_i / min(k, m_i) and needs edge_keep == 1.0.  hoist_first_aggregation does not compose: the hoisted product belongs to the full graph."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], residual_layer: bool = False,
                  weights: Optional[List[Tuple[np.ndarray, np.ndarray]]] = None, fused: bool = True,
                  hoist_first_aggregation: bool = False, agg_dtype: str = "f32", dropout: float = 0.0, norm=None,
-                 loss: str = "softmax", fanout=None, edge_keep: float = 1.0, edge_rescale=None):
+                 loss: str = "softmax", fanout=None, edge_keep: float = 1.0, edge_rescale=None,
+                 fanout_exact: bool = False):
         self.hoist_first_aggregation = bool(hoist_first_aggregation)
-        self._init_sampling(fanout, edge_keep, edge_rescale)     # option checks come before any device work
+        self._init_sampling(fanout, edge_keep, edge_rescale, fanout_exact)     # option checks come before any device work
         self._init_dropout(dropout, len(sizes) - 1)
         self.norm = check_norm(norm)
         self.loss = check_loss(loss)

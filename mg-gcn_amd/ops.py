@@ -1425,6 +1425,34 @@ def edge_sample_compact(ctx: context, n_rows: int, indptr, indices, thr, transpo
                                                                          out_indices.data_ptr()))
 
 
+EDGE_SELECT_REG_ENTRIES = 512      # 64 R, R = MGGCN_EDGE_SELECT_R: the longest row edge_sample_select holds in registers
+EDGE_SELECT_RS = (4, 8, 12, 16)     # the R the library is built for (``regs=``: the measurement behind the choice)
+
+
+def edge_sample_select(ctx: context, n_rows: int, indptr, indices, k: int, t_keep: int, thr, row0: int = 0, col0: int = 0,
+                       seed: int = 0, epoch: int = 0, force_stream: bool = False, regs: Optional[int] = None,
+                       timer: Optional[str] = None) -> None:
+    """thr[r] = the threshold under which row r of a forward matrix (rows are destinations) keeps exactly its ``k`` smallest
+    Philox words (mggcn_edge_sample_select_u32): with m_r the row's entries off the diagonal (global row != global column,
+    duplicates counted), thr[r] = t_keep where m_r <= k and min(the (k+1)-th smallest of their words, t_keep, 0xFFFFFFFE)
+    otherwise -- the word of edge_sample_count's keep rule, so count / compact after it keep every self entry and at most k
+    others per destination, exactly min(k, #{word < t_keep}) unless the k-th and (k+1)-th smallest words are equal (the row then
+    keeps fewer, never more).  ``t_keep``: the DropEdge threshold, thresholds(indptr, None, keep)'s value.  thr depends on (seed,
+    epoch, the row's multiset of pairs) alone.  Rows of at most EDGE_SELECT_REG_ENTRIES entries are selected in registers,
+    longer ones -- all with ``force_stream`` -- by LDS digit histograms; ``regs`` (one of EDGE_SELECT_RS) runs the kernel built
+    for another register count, with the same result.  Operands as in edge_sample_count; thr: n_rows words."""
+    what = "edge sample select"
+    _req(isinstance(k, numbers.Integral) and not isinstance(k, bool) and 1 <= k < 1 << 32, f"{what}: k must be an integer >= 1")
+    _req(isinstance(t_keep, numbers.Integral) and 0 <= t_keep < 1 << 32, f"{what}: t_keep must fit 32 bits")
+    _req(regs is None or regs in EDGE_SELECT_RS, f"{what}: regs must be None or one of {EDGE_SELECT_RS}")
+    args = _edge_sample_args(what, n_rows, indptr, indices, thr, 0, row0, col0, seed, epoch)
+    args = (*args[:3], int(k), int(t_keep), *args[5:], int(bool(force_stream)))
+    if regs is None:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_edge_sample_select_u32(ctx.stream(0), *args, thr.data_ptr()))
+    else:
+        _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_edge_sample_select_r_u32(ctx.stream(0), *args, int(regs), thr.data_ptr()))
+
+
 def _req_f32(t, least: int, what: str) -> None:
     """a contiguous fp32 device tensor of at least ``least`` elements"""
     _req(hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous() and t.element_size() == 4

@@ -34,7 +34,10 @@ which the max backward needs.  ``aggr="mean"`` is a weighted sum and samples onl
 (set_sampling(..., rescale=)); with ``edge_rescale`` None (the default) any setting that is on is refused by the argument's
 name.  Its training forward multiplies by the pair of the epoch through the row-split SpMM on a plan built on the device
 (sparse_linear.sample, ops.spmm_dev), layer 0 again into ``_M_sampled``.  ``aggr="max"`` reads no values and refuses
-``edge_rescale``.
+``edge_rescale``.  ``fanout_exact=True`` (set_sampling(..., exact=True); both ``aggr``) makes ``fanout`` the exact fan-out
+of the published recipe: every destination keeps its self-loops and exactly min(fanout, its other entries) sources, by a per-row
+select on the device at the top of every draw (edge_sample.py; csrc/edge_select.hip); "inverse" then scales by m_i / min(k, m_i)
+and needs edge_keep == 1.0.
 
 Refused with ValueError naming the argument, before any device work: an unknown ``aggr``, a matrix that is not square, and
 gcn's own errors for ``norm``, ``loss`` and ``dropout``; save / load / model_selector.save_best (no version of the checkpoint
@@ -235,14 +238,15 @@ class sage_layer(layer_params):
 
 class sage(rescaled_sampling_option, model_base):
     """sage(A, sizes, aggr="mean", loss="softmax", fused=True, weights=None, dropout=0.0, norm=None, fanout=None, edge_keep=1.0,
-    edge_rescale=None): see the module's text.
+    edge_rescale=None, fanout_exact=False): see the module's text.
     ``A`` is taken as gcn takes it (the forward aggregates over the rows of A.transpose()); ``weights``: (W_l, b_l, W_r, b_r)
     per layer."""
 
     def __init__(self, A: csr_matrix, sizes: Sequence[int], aggr: str = "mean", loss: str = "softmax", fused: bool = True,
-                 weights=None, dropout: float = 0.0, norm=None, fanout=None, edge_keep: float = 1.0, edge_rescale=None):
+                 weights=None, dropout: float = 0.0, norm=None, fanout=None, edge_keep: float = 1.0, edge_rescale=None,
+                 fanout_exact: bool = False):
         self.aggr = check_aggr(aggr)                         # option checks come before any device work
-        self._init_sampling(fanout, edge_keep, edge_rescale)  # aggr="mean": on only with a rescale; aggr="max": no rescale
+        self._init_sampling(fanout, edge_keep, edge_rescale, fanout_exact)  # aggr="mean": on only with a rescale; aggr="max": no rescale
         if A.n() != A.m():
             raise ValueError(f"A must be square, got {A.n()} x {A.m()}")
         self._init_dropout(dropout, len(sizes) - 1)
