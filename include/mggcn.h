@@ -1029,6 +1029,57 @@ size_t mggcn_roc_auc_stats_work_bytes(size_t n, size_t nc);
 void mggcn_roc_auc_stats_u64(mggcn_stream_t stream, const uint32_t *keys, const uint32_t *vals, size_t n, size_t nc,
                              uint64_t *stats, void *work, size_t work_bytes);
 
+/* Link prediction: a dot-product decoder over pairs of rows of one embedding matrix, its binary cross-entropy against
+ * uniformly drawn negatives, and the gradient of both endpoints without atomics (csrc/link.hip; no reference counterpart).
+ * H is [n x d] row-major, 1 <= d <= MGGCN_GAT_MAX_WIDTH, n < 2^31.
+ *   Positives   the PATTERN of a CSR matrix P [n x n]: row u, entry v, values not read, indptr[0] == 0; M = nnz entries.
+ *               An undirected graph lists both directions, each a training example of its own.
+ *   Negatives   R >= 1 per positive entry, the head kept and the tail uniform: negative (p, r) of the entry at position p of
+ *               P's indices, head u, is (u, v') with v' = (uint32)(((uint64) w n) >> 32), w = word r & 3 of
+ *               Philox4x32-10((p, r >> 2, 0xE0000000, epoch), seed).  The third counter word keeps the draw apart from
+ *               mggcn_dropout_f32 (row >> 32), attention dropout (0x80000000 | k >> 2), the edge sample (0xC0000000) and the
+ *               label mask (first word 0xFFFFFFFF; p < 2^31 here).  A negative that happens to be an edge, or v' == u, is
+ *               kept: the plain uniform sampler.  M R < 2^31.
+ *   Score       s_uv = sum_c H[u, c] H[v, c].
+ *   Loss        L = (1 / M) sum_pos softplus(-s) + (1 / (M R)) sum_neg softplus(s), softplus(x) = max(x, 0) +
+ *               log1p(exp(-|x|)); per pair g = (sigma(s) - 1) / M (positive), sigma(s) / (M R) (negative), and
+ *               G[x] = sum over pairs (x, y) of g H[y] + sum over pairs (y, x) of g H[y], positives and negatives alike; a
+ *               pair (u, u) is in both sums.  A pair is predicted a link iff s > 0.
+ *   neg_draw    keys[p R + r] = v', vals[p R + r] = u for every negative; one wave per row of P, lanes over its entries;
+ *               nothing else is written.  Sorted by mggcn_radix_sort_pairs_u32 (one segment, bits [0, ceil(log2 n))) the
+ *               values are the indices of the "negative transpose" NT, the heads of a tail in the order of p R + r.
+ *   bounds      nt_indptr[v] = #{sorted keys < v}, v = 0 .. n: a binary search per vertex, no atomics; a tail never drawn
+ *               gets an empty row.
+ *   dot_loss    over a CSR pattern [n_rows x n_cols] of nnz entries whose row x lists the other endpoints y: every entry is a
+ *               pair of label `positive` and weight `weight`; with R > 0 entry p also brings its R negatives, drawn inside
+ *               the walk over [0, n_cols), of weight neg_weight.  g = (sigma(s) - 1) weight or sigma(s) weight, and
+ *               G[x] = beta G[x] + sum g H[y] (beta == 0 never reads G).  row_loss / row_correct (both or neither): row x's
+ *               sums of softplus(-s) over its positives and softplus(s) over its negatives, [n_rows x 2], and its number of
+ *               pairs on the label's side of 0 (s > 0 for a positive, !(s > 0) for a negative).  A training step is three
+ *               launches in a fixed order: P (positive, 1 / M, R, 1 / (M R), beta 0, row sums), P^T (positive, 1 / M,
+ *               beta 1), NT (negative, 1 / (M R), beta 1).  One wave per row holding H[x] in registers, lane groups that
+ *               own one entry at a time, one gather of H[y] per pair for the score and the gradient, the groups folded in
+ *               a fixed order: no atomics, no scratch, no LDS, the same bits on every call.  d % 4 == 0 with 16-byte aligned
+ *               H and G and leading dimensions that are multiples of 4 takes the float4 path, anything else the element path.
+ *               n_rows == 0 returns; nnz == 0 writes G = beta G and zero sums.
+ *   sums        loss_sums[0 .. 2) = the two columns of row_loss added in the fixed order of the reduction tree,
+ *               *correct_sum = the sum of row_correct in integers.  Enqueue-only; n_rows == 0 writes zeros.
+ *   edge_dot    out[e] = H[src[e]] . H[dst[e]] for a list of m pairs, one lane group per pair, the same two load paths:
+ *               what evaluation scores held-out pairs with.  m == 0 returns.
+ * Refused before any launch: d outside [1, MGGCN_GAT_MAX_WIDTH]; R == 0 in neg_draw; nnz R >= 2^31; n >= 2^31; outputs that
+ * overlap each other or an input. */
+void mggcn_link_neg_draw_u32(mggcn_stream_t stream, uint32_t n_rows, const uint32_t *indptr, size_t nnz, uint32_t n,
+                             uint32_t R, uint64_t seed, uint32_t epoch, uint32_t *keys, uint32_t *vals);
+void mggcn_link_bounds_u32(mggcn_stream_t stream, const uint32_t *sorted_keys, size_t m, uint32_t n, uint32_t *nt_indptr);
+void mggcn_link_dot_loss_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                             const uint32_t *indices, size_t nnz, const float *H, size_t ldh, uint32_t d, int positive,
+                             float weight, uint32_t R, float neg_weight, uint64_t seed, uint32_t epoch, float beta, float *G,
+                             size_t ldg, float *row_loss, uint32_t *row_correct);
+void mggcn_link_sums_f32(mggcn_stream_t stream, const float *row_loss, const uint32_t *row_correct, size_t n_rows,
+                         float *loss_sums, uint32_t *correct_sum);
+void mggcn_edge_dot_f32(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m, const float *H, size_t ldh,
+                        size_t n_rows, uint32_t d, float *out);
+
 /* cublasSasum(src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

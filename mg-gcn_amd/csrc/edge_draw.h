@@ -9,6 +9,23 @@
 constexpr uint32_t kSampleDomain = 0xC0000000u;      // counter word 2: apart from feature dropout (row >> 32), attention
                                                      // dropout (0x80000000 | k >> 2) and the label mask (word 0 = 0xFFFFFFFF)
 
+constexpr uint32_t kLinkDomain = 0xE0000000u;        // counter word 2 of the link head's negatives (link.hip): apart from all
+                                                     // of the above and from kSampleDomain; word 0 is an entry position
+                                                     // p < 2^31, which the label mask's 0xFFFFFFFF never is
+
+// Negative (p, r) of the link head: the tail of the entry at position p, r < R.  Word r & 3 of
+// Philox4x32-10((p, r >> 2, kLinkDomain, epoch), seed) mapped onto [0, n) by the high half of a 32 x 32 product.
+// link_negatives keeps the four words of one call: next(r) for r = 0, 1, ... in order draws again at every fourth.
+struct link_negatives {
+    uint32_t p, n, k0, k1, epoch;
+    philox4 w;
+    __device__ __forceinline__ uint32_t next(uint32_t r) {
+        if ((r & 3) == 0) w = philox4x32_10(p, r >> 2, kLinkDomain, epoch, k0, k1);
+        const uint32_t q = r & 3, word = q == 0 ? w.w[0] : q == 1 ? w.w[1] : q == 2 ? w.w[2] : w.w[3];
+        return (uint32_t)(((uint64_t)word * n) >> 32);
+    }
+};
+
 __device__ __forceinline__ uint32_t sample_word(uint32_t i, uint32_t j, uint32_t epoch, uint32_t k0, uint32_t k1) {
     return philox4x32_10(j, i, kSampleDomain, epoch, k0, k1).w[0];
 }

@@ -272,6 +272,7 @@ head_geometry head_geometry_for(uint32_t dh, bool vec) {
     return {lg, (units + (1u << lg) - 1) >> lg};
 }
 
+[[maybe_unused]]        // not every translation unit that shares the layout has heads
 void require_heads(uint32_t K, uint32_t dh) {
     MGGCN_REQUIRE(K >= 1 && K <= MGGCN_GAT_MAX_HEADS, "gat supports 1 <= heads <= 16");
     MGGCN_REQUIRE(dh >= 1 && (size_t)K * dh <= MGGCN_GAT_MAX_WIDTH, "gat supports 1 <= heads * width per head <= 1024");

@@ -1,0 +1,221 @@
+"""Link prediction (opt-in; the reference trains node classifiers only): a pairwise head over any single-GPU encoder.
+
+``link_predictor(model, P, neg_ratio=1, seed=0)`` trains ``model`` -- a gcn, sage or gat, any variant and option -- as the
+encoder of a graph auto-encoder (Kipf & Welling's GAE, the gcn / sage baselines of the ogbl-* leaderboards): the model's last
+layer gives the embeddings H [n x d], a pair (u, v) scores s = H[u] . H[v], and the loss is the mean of softplus(-s) over
+the positive pairs plus the mean of softplus(s) over negatives drawn on the device (PyG's ``GAE.recon_loss``).
+
+  Positives   the PATTERN of the csr_matrix P [n x n]: row u, entry v; the values are not read.  An undirected graph lists
+              both directions and each is a training example of its own.  M = P.nnz().
+  Negatives   ``neg_ratio`` R per positive entry, the head kept and the tail uniform over all vertices: negative (p, r) of
+              the entry at position p is (u, v') with v' = (w n) >> 32, w = word r & 3 of
+              Philox4x32-10((p, r >> 2, ops.LINK_DOMAIN, epoch), seed).  A negative that happens to be an edge, or v' == u,
+              is KEPT: this is the plain uniform sampler of the OGB examples, not a filtered one.  The draw is never stored
+              on the head's side -- the loss kernel draws it again inside its walk -- and stored once on the tail's side,
+              where a stable radix sort puts it in order of v'.
+  Loss        L = (1 / M) sum_pos softplus(-s) + (1 / (M R)) sum_neg softplus(s); accuracy: a pair is predicted a link
+              iff s > 0, acc = (#{pos: s > 0} + #{neg: not s > 0}) / (M (1 + R)).
+
+The head has no parameters: save / load / predict / model_selector of the encoder keep working.  It allocates on first use:
+P and P^T on the device, the four sort arrays and the sort's work space, the row pointer of the negatives' transpose, the row
+sums and G [n x d].  A program that never constructs one launches, allocates and registers what it did before.  Timers
+link-draw, link-sort, link-bounds and link-loss exist once train_step has run.
+"""
+from __future__ import annotations
+
+import numbers
+from typing import Optional
+
+import numpy as np
+
+from . import ops
+from .gcn import model_base
+from .matrix import context, csr_matrix, dn_matrix, host_scalars
+from .metrics import roc_auc_evaluator
+
+
+def _torch():
+    import torch
+    return torch
+
+
+def check_neg_ratio(neg_ratio, M: int) -> int:
+    if not isinstance(neg_ratio, numbers.Integral) or isinstance(neg_ratio, bool) or neg_ratio < 1:
+        raise ValueError(f"neg_ratio must be an integer >= 1, not {neg_ratio!r}")
+    if M * int(neg_ratio) >= 1 << 31:
+        raise ValueError(f"neg_ratio: P.nnz() * neg_ratio must be below 2^31 (the negatives are one sort), got {M * int(neg_ratio)}")
+    return int(neg_ratio)
+
+
+def check_pairs(pairs, n: int, what: str = "pairs") -> np.ndarray:
+    """an integer array [m x 2] of vertices in [0, n), as uint32"""
+    a = np.asarray(pairs)
+    if a.ndim != 2 or a.shape[1] != 2 or a.dtype.kind not in "iu":
+        raise ValueError(f"{what} must be an integer array of m x 2, got {a.dtype} of shape {a.shape}")
+    if a.shape[0] >= 1 << 31:
+        raise ValueError(f"{what}: at most 2^31 - 1 pairs, got {a.shape[0]}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= n):
+        raise ValueError(f"{what} must lie in [0, {n}), got {int(a.min())} .. {int(a.max())}")
+    return np.ascontiguousarray(a, dtype=np.uint32)
+
+
+def pair_metrics(s_pos, s_neg) -> tuple:
+    """(loss, acc) of the head's formulas over given scores, in float64 on the host: M = len(s_pos), M R = len(s_neg)"""
+    def softplus(x):
+        return np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x)))
+    s_pos, s_neg = np.asarray(s_pos, dtype=np.float64).reshape(-1), np.asarray(s_neg, dtype=np.float64).reshape(-1)
+    loss = (softplus(-s_pos).mean() if s_pos.size else 0.0) + (softplus(s_neg).mean() if s_neg.size else 0.0)
+    hits = int((s_pos > 0).sum()) + int((~(s_neg > 0)).sum())
+    return float(loss), hits / max(s_pos.size + s_neg.size, 1)
+
+
+class link_predictor:
+    """link_predictor(model, P, neg_ratio=1, seed=0): see the module's text.  ``model``: a single-GPU gcn, sage or gat whose
+    last layer's width is the embedding width d (1 <= d <= ops.LINK_MAX_WIDTH; that layer has no activation already).
+
+    train_step(ctx, X, lr, beta1, beta2, weight_decay, eps) -> (loss, acc): the model's training forward (its dropout and its
+    own edge sampling behave as in its train_step), draw, sort, bounds, the three loss launches, the layers' backward, Adam,
+    ONE synchronisation, the sums.  ``epoch`` advances by one per step; set_negatives(ratio, seed, epoch) replays one.
+    score(ctx, X, pairs) -> dn_matrix [m x 1]: a plain forward, then H[u] . H[v] of every pair (an int array [m x 2]).
+    evaluate(ctx, X, pos_pairs, neg_pairs) -> {"auc", "loss", "acc"}: exact ROC-AUC on the device (roc_auc_evaluator), loss
+    and accuracy by the formulas above with M = len(pos_pairs), M R = len(neg_pairs); no dropout, no sampling, no epoch spent.
+    Both upload their pairs (and evaluate its targets) and synchronise on every call: sized for a validation set scored now and
+    then, not for a call inside every training step.
+
+    ValueError naming the argument, before any device work: a dist_* model; P not square or not of model.A.n() rows, with
+    indptr[0] != 0, without an entry or with a column outside [0, n); neg_ratio < 1 or not an int; P.nnz() * neg_ratio >=
+    2^31; pairs outside [0, n)."""
+
+    def __init__(self, model, P: csr_matrix, neg_ratio: int = 1, seed: int = 0):
+        if not isinstance(model, model_base):
+            raise ValueError(f"model must be a single-GPU gcn, sage or gat (the row-partitioned dist_* models have no link "
+                             f"head), not {type(model).__name__}")
+        d = int(model._out_width)
+        if not 1 <= d <= ops.LINK_MAX_WIDTH:
+            raise ValueError(f"model: the last layer's width is the embedding width and must be 1 <= d <= {ops.LINK_MAX_WIDTH}, got {d}")
+        n = int(model.A.n())
+        if not isinstance(P, csr_matrix) or P.n() != P.m() or P.n() != n:
+            got = f"{P.n()} x {P.m()}" if isinstance(P, csr_matrix) else type(P).__name__
+            raise ValueError(f"P must be a square csr_matrix of the model's {n} vertices, got {got}")
+        if n >= 1 << 31:
+            raise ValueError(f"P: n must be below 2^31, got {n}")
+        if int(P.indptr[0]) != 0:
+            raise ValueError(f"P: indptr[0] must be 0 (an entry's position is its counter), got {int(P.indptr[0])}")
+        M = P.nnz()
+        if M == 0:
+            raise ValueError("P has no entry: there is no positive pair to train on")
+        if int(P.indices.max()) >= n:
+            raise ValueError(f"P: a column index lies outside [0, {n})")
+        self.neg_ratio = check_neg_ratio(neg_ratio, M)
+        self.model, self.P, self.n, self.d, self.M = model, P, n, d, M
+        self.seed, self.epoch = int(seed), 0
+        self.P_T: Optional[csr_matrix] = None
+        self._arrays = None
+        self._rows = None
+        self._auc = None
+
+    def set_negatives(self, ratio=None, seed=None, epoch=None) -> None:
+        """the ratio, seed and epoch of the next draw; None leaves one as it is.  The same (ratio, seed, epoch) on the same
+        embeddings gives the same bits."""
+        if ratio is not None:
+            ratio = check_neg_ratio(ratio, self.M)
+            if ratio != self.neg_ratio:
+                self.neg_ratio, self._arrays = ratio, None
+        if seed is not None:
+            self.seed = int(seed)
+        if epoch is not None:
+            self.epoch = int(epoch)
+
+    def sort_bits(self) -> int:
+        """the key bits the sort looks at: ceil(log2 n), at least one"""
+        return max(1, (self.n - 1).bit_length())
+
+    def _allocate(self, ctx: context) -> None:
+        torch = _torch()
+        if self.P_T is None:
+            self.P_T = self.P.transpose()
+        if self._rows is None:
+            dev = ctx.device
+            self._rows = dict(G=dn_matrix(self.n, self.d, device=dev),
+                              nt_indptr=torch.empty(self.n + 1, dtype=torch.int32, device=dev),
+                              row_loss=torch.empty(2 * self.n, dtype=torch.float32, device=dev),
+                              row_correct=torch.empty(self.n, dtype=torch.int32, device=dev), sums=host_scalars(3))
+        if self._arrays is None:
+            pairs = self.M * self.neg_ratio
+            four = [torch.empty(pairs, dtype=torch.int32, device=ctx.device) for _ in range(4)]
+            work = torch.empty(ops.radix_sort_work_bytes(1, pairs) // 8 + 1, dtype=torch.int64, device=ctx.device)
+            self._arrays = (four, work)
+
+    def loss_backward(self, ctx: context, H: dn_matrix) -> dn_matrix:
+        """draw, sort, bounds, the three loss launches and the sums on the embeddings H, with the negatives of (seed, epoch);
+        returns G = dL/dH.  Enqueue-only: read() after a synchronisation."""
+        if H.shape() != (self.n, self.d):
+            raise ValueError(f"H must be {self.n} x {self.d}, got {H.n()} x {H.m()}")
+        self._allocate(ctx)
+        n, M, R = self.n, self.M, self.neg_ratio
+        (keys, vals, keys_alt, vals_alt), work = self._arrays
+        r = self._rows
+        p_ip, p_ix, _ = self.P.device(ctx.device)
+        t_ip, t_ix, _ = self.P_T.device(ctx.device)
+        draw = dict(seed=self.seed, epoch=self.epoch)
+        ops.link_neg_draw(ctx, n, p_ip, M, n, R, self.seed, self.epoch, keys, vals, timer="link-draw")
+        ops.radix_sort_pairs(ctx, 1, M * R, keys, vals, keys_alt, vals_alt, work, 0, self.sort_bits(), timer="link-sort")
+        ops.link_bounds(ctx, keys, M * R, n, r["nt_indptr"], timer="link-bounds")
+        w_pos, w_neg = 1.0 / M, 1.0 / (M * R)
+        ctx.record("link-loss_0", 0)
+        ops.link_dot_loss(ctx, n, n, p_ip, p_ix, M, H, r["G"], True, w_pos, R, w_neg, beta=0.0, row_loss=r["row_loss"],
+                          row_correct=r["row_correct"], **draw)
+        ops.link_dot_loss(ctx, n, n, t_ip, t_ix, M, H, r["G"], True, w_pos, beta=1.0)
+        ops.link_dot_loss(ctx, n, n, r["nt_indptr"], vals, M * R, H, r["G"], False, w_neg, beta=1.0)
+        ops.link_sums(ctx, r["row_loss"], r["row_correct"], n, r["sums"])
+        ctx.record("link-loss_1", 0)
+        ctx.register_timer("link-loss", "link-loss_0", "link-loss_1")
+        return r["G"]
+
+    def read(self) -> tuple:
+        """(loss, acc) of the last loss_backward, after a synchronisation"""
+        words = self._rows["sums"].numpy()
+        M, R = self.M, self.neg_ratio
+        loss = float(words[0]) / M + float(words[1]) / (M * R)
+        return loss, int(words.view(np.uint32)[2]) / (M * (1 + R))
+
+    def train_step(self, ctx: context, X: dn_matrix, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float):
+        model = self.model
+        H = model(ctx, X, training=True)
+        G = self.loss_backward(ctx, H)
+        self.epoch += 1
+        for layer in reversed(model.layers()):
+            G = layer.backward(ctx, G)
+        model.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+        model._launched()
+        ctx.sync()
+        return self.read()
+
+    def score(self, ctx: context, X: dn_matrix, pairs) -> dn_matrix:
+        pairs = check_pairs(pairs, self.n)
+        return self._score(ctx, X, pairs)
+
+    def _score(self, ctx: context, X: dn_matrix, pairs: np.ndarray) -> dn_matrix:
+        m = pairs.shape[0]
+        out = dn_matrix(m, 1, device=ctx.device)
+        H = self.model(ctx, X)
+        if m:
+            src = dn_matrix.from_numpy(pairs[:, 0].view(np.int32), device=ctx.device)
+            dst = dn_matrix.from_numpy(pairs[:, 1].view(np.int32), device=ctx.device)
+            ops.edge_dot(ctx, src.t.view(-1), dst.t.view(-1), m, H, out.t.view(-1))
+        ctx.sync()
+        return out
+
+    def evaluate(self, ctx: context, X: dn_matrix, pos_pairs, neg_pairs) -> dict:
+        pos, neg = check_pairs(pos_pairs, self.n, "pos_pairs"), check_pairs(neg_pairs, self.n, "neg_pairs")
+        m_pos, m = pos.shape[0], pos.shape[0] + neg.shape[0]
+        if m >= 1 << 31:
+            raise ValueError(f"pos_pairs and neg_pairs: at most 2^31 - 1 pairs together, got {m}")
+        scores = self._score(ctx, X, np.concatenate([pos, neg]))
+        if self._auc is None or self._auc.n != m:
+            self._auc = roc_auc_evaluator(m, 1)
+        Y = dn_matrix.from_numpy(np.concatenate([np.ones(m_pos, np.int32), np.zeros(m - m_pos, np.int32)]), device=ctx.device)
+        auc = self._auc(ctx, scores, Y)["all"]
+        s = scores.numpy().reshape(-1)
+        loss, acc = pair_metrics(s[:m_pos], s[m_pos:])
+        return {"auc": auc, "loss": loss, "acc": acc}

@@ -1721,6 +1721,130 @@ def roc_auc_stats(ctx: context, keys, vals, n: int, nc: int, stats, work, timer:
         work.numel() * work.element_size() if need else 0))
 
 
+# ---- the link-prediction head (csrc/link.hip) --------------------------------------------------------------------------------
+LINK_DOMAIN = 0xE0000000            # the third Philox counter word of every negative of the link head
+LINK_MAX_WIDTH = 1024               # MGGCN_GAT_MAX_WIDTH: the widest embedding a wave holds in registers
+
+
+def _req_link_counts(what: str, nnz, neg_ratio, n, draws: bool) -> tuple:
+    nnz = _req_count(nnz, f"{what}: nnz")
+    _req(isinstance(neg_ratio, numbers.Integral) and not isinstance(neg_ratio, bool) and neg_ratio >= (1 if draws else 0),
+         f"{what}: neg_ratio must be an integer >= {1 if draws else 0}, got {neg_ratio!r}")
+    n = _req_count(n, f"{what}: n")
+    _req(n < 1 << 31, f"{what}: n must be below 2^31, got {n}")
+    _req(nnz * max(int(neg_ratio), 1) < 1 << 31, f"{what}: nnz * neg_ratio must be below 2^31, got {nnz * max(int(neg_ratio), 1)}")
+    return nnz, int(neg_ratio), n
+
+
+def _req_apart(what: str, a, a_bytes: int, na: str, b, b_bytes: int, nb: str) -> None:
+    _req(not a_bytes or not b_bytes or a + a_bytes <= b or b + b_bytes <= a, f"{what}: {na} and {nb} must not alias (overlap)")
+
+
+def link_neg_draw(ctx: context, n_rows: int, indptr, nnz: int, n: int, neg_ratio: int, seed: int, epoch: int, keys, vals,
+                  timer: Optional[str] = None) -> None:
+    """keys[p R + r] = v', vals[p R + r] = u for the R = neg_ratio negatives of every entry of the pattern with the device row
+    pointer ``indptr`` (n_rows + 1 4-byte integers, indptr[0] == 0, nnz entries; mggcn_link_neg_draw_u32): entry p of row u
+    draws v' = (w n) >> 32 with w = word r & 3 of Philox4x32-10((p, r >> 2, LINK_DOMAIN, epoch), seed) -- uniform tails, the
+    head kept, true edges and v' == u not filtered.  keys / vals: device tensors of at least nnz * R 4-byte integers."""
+    what = "link draw"
+    _req(isinstance(n_rows, numbers.Integral) and 0 <= n_rows < 1 << 31, f"{what}: n_rows must be below 2^31")
+    nnz, R, n = _req_link_counts(what, nnz, neg_ratio, n, True)
+    _req(n >= 1, f"{what}: n must be positive")
+    _req_u32(indptr, n_rows + 1, f"{what}: indptr")
+    _req_u32(keys, nnz * R, f"{what}: keys")
+    _req_u32(vals, nnz * R, f"{what}: vals")
+    _req_apart(what, keys.data_ptr(), 4 * nnz * R, "keys", vals.data_ptr(), 4 * nnz * R, "vals")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_neg_draw_u32(
+        ctx.stream(0), int(n_rows), indptr.data_ptr(), nnz, n, R, int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+        keys.data_ptr(), vals.data_ptr()))
+
+
+def link_bounds(ctx: context, keys, m: int, n: int, nt_indptr, timer: Optional[str] = None) -> None:
+    """nt_indptr[v] = #{keys[:m] < v} for v = 0 .. n over keys SORTED ascending (mggcn_link_bounds_u32): the row pointer of
+    the pattern whose row v holds the sorted values of key v; a key never drawn gets an empty row.  nt_indptr: n + 1 words."""
+    what = "link bounds"
+    m, _, n = _req_link_counts(what, m, 0, n, False)
+    _req_u32(keys, m, f"{what}: keys")
+    _req_u32(nt_indptr, n + 1, f"{what}: nt_indptr")
+    _req_apart(what, keys.data_ptr(), 4 * m, "keys", nt_indptr.data_ptr(), 4 * (n + 1), "nt_indptr")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_bounds_u32(ctx.stream(0), keys.data_ptr(), m, n, nt_indptr.data_ptr()))
+
+
+def _req_link_width(what: str, d: int) -> None:
+    _req(1 <= d <= LINK_MAX_WIDTH, f"{what}: the embedding width d must be 1 <= d <= {LINK_MAX_WIDTH}, got {d}")
+
+
+def link_dot_loss(ctx: context, n_rows: int, n_cols: int, indptr, indices, nnz: int, H, G, positive: bool, weight: float,
+                  neg_ratio: int = 0, neg_weight: float = 0.0, seed: int = 0, epoch: int = 0, beta: float = 0.0, row_loss=None,
+                  row_correct=None, timer: Optional[str] = None) -> None:
+    """One walk of the link head over a device CSR pattern [n_rows x n_cols] of nnz entries whose row x lists the other
+    endpoints y of its pairs (mggcn_link_dot_loss_f32): s = H[x] . H[y], g = (sigma(s) - 1) weight for a ``positive`` pattern
+    and sigma(s) weight for a negative one, G[x] = beta G[x] + sum g H[y].  ``neg_ratio`` R > 0 adds R negatives per entry,
+    drawn inside the walk exactly as link_neg_draw draws them (tails over [0, n_cols)), at ``neg_weight``.  row_loss (fp32,
+    2 n_rows) / row_correct (4-byte integers, n_rows), both or neither: the row's sum of softplus(-s) over its positives and of
+    softplus(s) over its negatives, and its number of pairs with s on the label's side of 0.  H ([max(n_rows, n_cols) x d]) and
+    G ([n_rows x d]): a dn_matrix or a 2-D fp32 device tensor with unit column stride, any row stride; 1 <= d <=
+    LINK_MAX_WIDTH.  The same bits on every call."""
+    what = "link loss"
+    for name, v in (("n_rows", n_rows), ("n_cols", n_cols)):
+        _req(isinstance(v, numbers.Integral) and 0 <= v < 1 << 31, f"{what}: {name} must be below 2^31")
+    nnz, R, _ = _req_link_counts(what, nnz, neg_ratio, n_cols, False)
+    hp, ldh, hn, d = _dense_window(H, True, f"{what}: H")
+    gp, ldg, gn, gd = _dense_window(G, True, f"{what}: G")
+    _req_link_width(what, d)
+    _req(hn >= max(n_rows, n_cols if nnz else 0), f"{what}: H must have a row for every row and column of the pattern, got {hn}")
+    _req((gn, gd) == (n_rows, d), f"{what}: G must be {n_rows} x {d}, got {gn} x {gd}")
+    _req_u32(indptr, n_rows + 1, f"{what}: indptr")
+    _req_u32(indices, nnz, f"{what}: indices")
+    h_bytes, g_bytes = 4 * ((hn - 1) * ldh + d) if hn else 0, 4 * ((gn - 1) * ldg + d) if gn else 0
+    _req_apart(what, gp, g_bytes, "G", hp, h_bytes, "H")
+    _req((row_loss is None) == (row_correct is None), f"{what}: row_loss and row_correct come together")
+    if row_loss is not None:
+        _req_f32(row_loss, 2 * n_rows, f"{what}: row_loss")
+        _req_u32(row_correct, n_rows, f"{what}: row_correct")
+        outs = (("row_loss", row_loss.data_ptr(), 8 * n_rows), ("row_correct", row_correct.data_ptr(), 4 * n_rows),
+                ("G", gp, g_bytes), ("H", hp, h_bytes))
+        for i, (na, a, ab) in enumerate(outs[:2]):
+            for nb, b, bb in outs[i + 1:]:
+                _req_apart(what, a, ab, na, b, bb, nb)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_dot_loss_f32(
+        ctx.stream(0), int(n_rows), int(n_cols), indptr.data_ptr(), indices.data_ptr(), nnz, hp, ldh, d, int(bool(positive)),
+        float(weight), R, float(neg_weight), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF, float(beta), gp, ldg,
+        row_loss.data_ptr() if row_loss is not None else None, row_correct.data_ptr() if row_correct is not None else None))
+
+
+def link_sums(ctx: context, row_loss, row_correct, n_rows: int, sums) -> None:
+    """sums[0], sums[1] = the two columns of row_loss [n_rows x 2] added in the fixed order of the reduction tree (fp32),
+    sums[2] = the integer sum of row_correct as a 4-byte integer (mggcn_link_sums_f32).  sums: three 4-byte words of device
+    memory or a host_scalars; enqueue-only."""
+    what = "link sums"
+    n_rows = _req_count(n_rows, f"{what}: n_rows")
+    _req_f32(row_loss, 2 * n_rows, f"{what}: row_loss")
+    _req_u32(row_correct, n_rows, f"{what}: row_correct")
+    _req(hasattr(sums, "data_ptr") and sums.numel() >= 3, f"{what}: sums must hold three 4-byte words")
+    ctx.lib.mggcn_link_sums_f32(ctx.stream(0), row_loss.data_ptr(), row_correct.data_ptr(), n_rows, sums.data_ptr(),
+                                sums.data_ptr() + 8)
+
+
+def edge_dot(ctx: context, src, dst, m: int, H, out, timer: Optional[str] = None) -> None:
+    """out[e] = H[src[e]] . H[dst[e]] for e < m (mggcn_edge_dot_f32): src / dst device tensors of 4-byte integers below H's
+    row count (the caller's to guarantee), H as in link_dot_loss, out a contiguous fp32 device tensor of at least m."""
+    what = "edge dot"
+    m = _req_count(m, f"{what}: m")
+    _req(m < 1 << 31, f"{what}: m must be below 2^31, got {m}")
+    hp, ldh, hn, d = _dense_window(H, True, f"{what}: H")
+    _req_link_width(what, d)
+    _req_u32(src, m, f"{what}: src")
+    _req_u32(dst, m, f"{what}: dst")
+    _req_f32(out, m, f"{what}: out")
+    _req(hn >= 1 or m == 0, f"{what}: H has no rows")
+    for name, p, nbytes in (("H", hp, 4 * ((hn - 1) * ldh + d) if hn else 0), ("src", src.data_ptr(), 4 * m),
+                            ("dst", dst.data_ptr(), 4 * m)):
+        _req_apart(what, out.data_ptr(), 4 * m, "out", p, nbytes, name)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_edge_dot_f32(ctx.stream(0), src.data_ptr(), dst.data_ptr(), m, hp, ldh, hn, d,
+                                                              out.data_ptr()))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
