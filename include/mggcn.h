@@ -1080,6 +1080,41 @@ void mggcn_link_sums_f32(mggcn_stream_t stream, const float *row_loss, const uin
 void mggcn_edge_dot_f32(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m, const float *H, size_t ldh,
                         size_t n_rows, uint32_t d, float *out);
 
+/* Link prediction, MLP decoder: the head above with a one-hidden-layer perceptron over the Hadamard product in place of the
+ * dot product (csrc/link_mlp.hip; the decoder of the ogbl-* gcn / sage baselines; no reference counterpart).
+ *   Score       x = H[u] (.) H[v], z = W1^T x + b1, a = leaky_relu(z) at the slope 0.01 of the gcn layers, s = w2 . a + b2.
+ *               W1 [d x hd] row-major and contiguous, b1 [hd], w2 [hd], b2 [1]; d and hd multiples of 32 in
+ *               [32, MGGCN_LINK_MLP_MAX_WIDTH], so that W1 (at most 64 KiB) stays in LDS.  s is symmetric in u and v.
+ *   mlp_loss    mggcn_link_dot_loss_f32 with this score: the same patterns, `positive`, weights, in-walk negatives, beta,
+ *               row_loss and row_correct, the same three launches in the same order.  G[x] = beta G[x] + sum over the row's
+ *               pairs of g (W1 dz) (.) H[y], dz_j = w2_j lrelu'(z_j): with the transposed launches that is all of dL/dH.
+ *               One wave per row on a persistent grid, tiles of 32 pairs on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf
+ *               chain), forward and backward of a tile in registers, nothing of size pairs x d or pairs x hd stored.  H and
+ *               G with 16-byte aligned rows take 16-byte loads, anything else 4-byte ones.  No atomics, no scratch, the same
+ *               bits on every call.
+ *   mlp_pairs   over a flat list of pairs: src != NULL the explicit list (src[e], dst[e]), e < m, every pair of label
+ *               `positive` and weight `weight`; src == NULL the training list of a pattern of M entries -- position q in
+ *               [0, M (1 + R)) is entry p = q / (1 + R), slot q % (1 + R): slot 0 the positive (head[p], indices[p]) at
+ *               `weight`, slot r + 1 the negative (head[p], v') of (p, r) drawn as above over [0, n_draw) at `neg_weight`;
+ *               head[p] = the row of entry p.  Writes out[q] = s (out != NULL) and / or (grads != NULL) the gradient of the
+ *               weighted loss in W1, b1, w2, b2, packed [d hd | hd | hd | 1] in `grads`.  At most 256 workgroups; workgroup b
+ *               takes the tiles b, b + grid, ... of 32 pairs in order (grid = min(tiles, 256)) and stores one partial in
+ *               `partials` (mggcn_link_mlp_partial_floats(d, hd) floats of the caller's), which one pass adds in workgroup
+ *               order: the same bits on every call, no atomics.  An empty list stores zero gradients.
+ * Refused before any launch: d or hd outside the range; grads without partials; neither out nor grads; overlapping outputs. */
+#define MGGCN_LINK_MLP_MAX_WIDTH 128
+void mggcn_link_mlp_loss_f32(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                             const uint32_t *indices, size_t nnz, const float *H, size_t ldh, uint32_t d, const float *W1,
+                             const float *b1, const float *w2, const float *b2, uint32_t hd, int positive, float weight,
+                             uint32_t R, float neg_weight, uint64_t seed, uint32_t epoch, float beta, float *G, size_t ldg,
+                             float *row_loss, uint32_t *row_correct);
+size_t mggcn_link_mlp_partial_floats(uint32_t d, uint32_t hd);
+void mggcn_link_mlp_pairs_f32(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m, const uint32_t *head,
+                              const uint32_t *indices, size_t M, uint32_t R, uint32_t n_draw, uint64_t seed, uint32_t epoch,
+                              int positive, float weight, float neg_weight, const float *H, size_t ldh, size_t n_rows,
+                              uint32_t d, const float *W1, const float *b1, const float *w2, const float *b2, uint32_t hd,
+                              float *out, float *grads, float *partials);
+
 /* cublasSasum(src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

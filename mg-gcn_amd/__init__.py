@@ -38,7 +38,8 @@ Layout:
                  sort on the device (csrc/radix_sort.hip, csrc/roc_auc.hip; no reference counterpart)
   link.py        link_predictor: link prediction over any single-GPU encoder -- a dot-product decoder, negatives drawn on the
                  device, loss and both endpoints' gradient in one fused kernel launched three times (csrc/link.hip; no
-                 reference counterpart)
+                 reference counterpart); mlp_link_predictor: the same with a Hadamard-MLP decoder on the matrix cores
+                 (csrc/link_mlp.hip)
   smoothing.py   correct_and_smooth: label-propagation post-processing of any model's logits (csrc/propagate.hip around the
                  sweep SpMM; no reference counterpart)
 """
@@ -65,10 +66,10 @@ from .selection import model_selector                           # noqa: F401
 from . import metrics                                           # noqa: F401
 from .metrics import roc_auc_evaluator                          # noqa: F401
 from . import link                                              # noqa: F401
-from .link import link_predictor                                # noqa: F401
+from .link import link_predictor, mlp_link_predictor            # noqa: F401
 from . import smoothing                                         # noqa: F401
 from .smoothing import correct_and_smooth                       # noqa: F401
 
 __all__ = ["context", "csr_matrix", "dn_matrix", "matrix_error", "engine_error", "ops", "matmul",
            "get_matmul_buffer", "sparse_linear", "linear", "gcn_layer", "softmax",
-           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "sage", "sage_layer", "max_aggregate", "edge_sampler", "sampled_csr", "datasets", "model_selector", "correct_and_smooth", "roc_auc_evaluator", "link_predictor"]
+           "softmax_cross_entropy_loss", "gcn", "attention", "gat_layer", "gat", "attention_v2", "gatv2_layer", "attention_dot", "gatdot_layer", "gated_skip", "label_input", "sage", "sage_layer", "max_aggregate", "edge_sampler", "sampled_csr", "datasets", "model_selector", "correct_and_smooth", "roc_auc_evaluator", "link_predictor", "mlp_link_predictor"]

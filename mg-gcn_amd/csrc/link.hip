@@ -17,25 +17,17 @@
 // four columns (float4 path) or one (element path) of H[y], the dot product a butterfly over the group's lanes, the pair's
 // scalar g formed on every lane of the group from the same s, and the gathered row used a second time for acc += g H[y]:
 // one gather per pair serves the score and the gradient.  The groups' accumulators meet in fold_groups' fixed order at the end
-// of the row.  A row's work is a matrix-vector product against gathered rows: nothing for the matrix cores.
+// of the row.  A row's work is a matrix-vector product against gathered rows: nothing for the matrix cores (the MLP decoder of
+// link_mlp.hip, whose hidden layer makes a tile of pairs a real GEMM, is).
 //
 // Launch (a) also leaves three numbers per row -- the sum of softplus(-s) over its positives, of softplus(s) over its
 // negatives, and the number of pairs on the right side of 0 -- which mggcn_link_sums_f32 adds through the tree of reduce.h
 // (the count in integers).
 #include "edge_draw.h"
 #include "gat_internal.h"
+#include "link_pair.h"
 
 namespace {
-
-// what one pair adds: g = dL/ds times the pair's weight, its loss term, whether s falls on the label's side of 0.
-// e = exp(-|s|) serves log1p and both sigmoids; sigma(s) - 1 is formed as -sigma(-s), which does not cancel.
-struct pair_terms { float g, loss; uint32_t hit; };
-__device__ __forceinline__ pair_terms link_pair(float s, bool positive, float weight) {
-    const float e = expf(-fabsf(s)), l1p = log1pf(e), inv = 1.f / (1.f + e);
-    const float sig_abs = inv, sig_neg = e * inv;               // sigma(|s|), sigma(-|s|)
-    if (positive) return {-(s >= 0.f ? sig_neg : sig_abs) * weight, fmaxf(-s, 0.f) + l1p, s > 0.f ? 1u : 0u};
-    return {(s >= 0.f ? sig_abs : sig_neg) * weight, fmaxf(s, 0.f) + l1p, s > 0.f ? 0u : 1u};
-}
 
 __device__ __forceinline__ uint32_t fold_groups_u32(uint32_t v, uint32_t lpr) {
     for (uint32_t off = lpr; off < 64; off <<= 1) v += (uint32_t)__shfl_xor((int)v, off);

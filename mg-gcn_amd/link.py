@@ -16,7 +16,10 @@ the positive pairs plus the mean of softplus(s) over negatives drawn on the devi
   Loss        L = (1 / M) sum_pos softplus(-s) + (1 / (M R)) sum_neg softplus(s); accuracy: a pair is predicted a link
               iff s > 0, acc = (#{pos: s > 0} + #{neg: not s > 0}) / (M (1 + R)).
 
-The head has no parameters: save / load / predict / model_selector of the encoder keep working.  It allocates on first use:
+``mlp_link_predictor(model, P, hidden=128, ...)`` is the same head with the decoder of the ogbl-* gcn / sage baselines, an MLP
+over H[u] (.) H[v] with one hidden layer, on the matrix cores: see the class.
+
+link_predictor has no parameters: save / load / predict / model_selector of the encoder keep working.  It allocates on first use:
 P and P^T on the device, the four sort arrays and the sort's work space, the row pointer of the negatives' transpose, the row
 sums and G [n x d].  A program that never constructs one launches, allocates and registers what it did before.  Timers
 link-draw, link-sort, link-bounds and link-loss exist once train_step has run.
@@ -29,7 +32,7 @@ from typing import Optional
 import numpy as np
 
 from . import ops
-from .gcn import model_base
+from .gcn import _SQRT_1_3, model_base, param_owner
 from .matrix import context, csr_matrix, dn_matrix, host_scalars
 from .metrics import roc_auc_evaluator
 
@@ -219,3 +222,145 @@ class link_predictor:
         s = scores.numpy().reshape(-1)
         loss, acc = pair_metrics(s[:m_pos], s[m_pos:])
         return {"auc": auc, "loss": loss, "acc": acc}
+
+
+def check_mlp_weights(weights, d: int, hidden: int) -> tuple:
+    """(W1 [d x hidden], b1 [1 x hidden], w2 [1 x hidden], b2 [1 x 1]) as finite float32 arrays"""
+    if not isinstance(weights, (tuple, list)) or len(weights) != 4:
+        raise ValueError(f"weights must be (W1, b1, w2, b2), got {type(weights).__name__}"
+                         + (f" of {len(weights)}" if isinstance(weights, (tuple, list)) else ""))
+    out = []
+    for name, w, shape in zip(("W1", "b1", "w2", "b2"), weights, ((d, hidden), (1, hidden), (1, hidden), (1, 1))):
+        a = np.asarray(w, dtype=np.float32)
+        if a.shape != shape:
+            raise ValueError(f"weights: {name} must be {shape[0]} x {shape[1]}, got shape {a.shape}")
+        if not np.isfinite(a).all():
+            raise ValueError(f"weights: {name} has a non-finite value")
+        out.append(np.ascontiguousarray(a))
+    return tuple(out)
+
+
+class mlp_link_predictor(link_predictor):
+    """mlp_link_predictor(model, P, hidden=128, neg_ratio=1, seed=0, weights=None): link_predictor with the decoder of the
+    ogbl-* gcn / sage baselines in place of the dot product -- x = H[u] (.) H[v], z = W1^T x + b1, a = leaky_relu(z) (the
+    slope of the gcn layers), s = w2 . a + b2 -- on the matrix cores (csrc/link_mlp.hip).
+
+    Parameters W1 [d x hidden], b1 [1 x hidden], w2 [1 x hidden], b2 [1 x 1], initialised like a linear's W and b (the
+    seeded initialiser) or from ``weights`` = (W1, b1, w2, b2); weights() returns them as numpy arrays.  They are not part
+    of the encoder's checkpoint: weights() / weights= carry them.  train_step trains them by Adam with the hyper-parameters of
+    the call after the model's own update: W1 and w2 decay like a linear's W, b1 and b2 do not, and the step is the fused
+    kernel per tensor where the model is fused, the reference's chain otherwise.  The tensors, their gradients and moments
+    sit on ``owner``, a plain param_owner described by ``params_table`` (the head is no layer: it has no slot in a checkpoint).
+
+    Positives, negatives, loss, accuracy, set_negatives, evaluate, score and read are the parent's; score and evaluate use
+    the MLP.  loss_backward adds one launch after the three walks: the parameters' gradient from one pass over the training
+    list of M (1 + R) pairs, the negatives drawn a third time (timer link-wgrad).  On first use it allocates what the parent
+    does plus the row of every entry (M words), the packed gradient and its per-workgroup partials.
+
+    ValueError naming the argument, before any device work: what link_predictor refuses; the model's last width d or
+    ``hidden`` not a multiple of 32 in [32, 128] (W1, at most 64 KiB, stays in LDS); ``weights`` of the wrong length or shapes or
+    with a non-finite value."""
+
+    params_table = (("W1", "W1", "G_W1", "mW1", "vW1", True), ("b1", "b1", "G_b1", "mb1", "vb1", False),
+                    ("w2", "w2", "G_w2", "mw2", "vw2", True), ("b2", "b2", "G_b2", "mb2", "vb2", False))
+
+    def __init__(self, model, P: csr_matrix, hidden: int = 128, neg_ratio: int = 1, seed: int = 0, weights=None):
+        link_predictor.__init__(self, model, P, neg_ratio, seed)
+        if self.d not in ops.LINK_MLP_WIDTHS:
+            raise ValueError(f"model: the MLP decoder needs an embedding width d that is a multiple of 32 in [32, 128], got {self.d}")
+        if not isinstance(hidden, numbers.Integral) or isinstance(hidden, bool) or hidden not in ops.LINK_MLP_WIDTHS:
+            raise ValueError(f"hidden must be a multiple of 32 in [32, 128], not {hidden!r}")
+        self.hidden = hd = int(hidden)
+        if weights is not None:
+            weights = check_mlp_weights(weights, self.d, hd)
+        self.W1, self.b1, self.w2, self.b2 = dn_matrix(self.d, hd), dn_matrix(1, hd), dn_matrix(1, hd), dn_matrix(1, 1)
+        if weights is None:
+            self.W1.init()
+            self.w2.init()
+            self.b1.init(_SQRT_1_3)
+            self.b2.init(_SQRT_1_3)
+        else:
+            for t, w in zip(self.params(), weights):
+                t.init(w)
+        sizes, dev = (self.d * hd, hd, hd, 1), self.W1.t.device
+        self._grads = _torch().empty(ops.link_mlp_grad_floats(self.d, hd), dtype=_torch().float32, device=dev)
+        cuts = np.concatenate([[0], np.cumsum(sizes)])
+        self.G_W1, self.G_b1, self.G_w2, self.G_b2 = (
+            dn_matrix(shape, buffer=self._grads[int(lo):int(hi)])
+            for shape, lo, hi in zip(((self.d, hd), (1, hd), (1, hd), (1, 1)), cuts[:-1], cuts[1:]))
+        o = self.owner = param_owner()
+        o.params_table, o.adam_fused = self.params_table, bool(model.fused)
+        for _, p, g, m, v, _ in self.params_table:
+            setattr(o, p, getattr(self, p))
+            setattr(o, g, getattr(self, g))
+            setattr(o, m, None)
+            setattr(o, v, None)
+        self._partials = self._head = None
+
+    def params(self) -> tuple:
+        return self.W1, self.b1, self.w2, self.b2
+
+    def weights(self) -> tuple:
+        """(W1, b1, w2, b2) as numpy arrays (synchronise first where a step is in flight)"""
+        return tuple(t.numpy() for t in self.params())
+
+    def _allocate(self, ctx: context) -> None:
+        link_predictor._allocate(self, ctx)
+        if self._head is None:
+            torch = _torch()
+            rows = np.repeat(np.arange(self.n, dtype=np.uint32), np.diff(self.P.indptr.astype(np.int64)))
+            self._head = torch.from_numpy(rows.view(np.int32)).to(ctx.device)
+            self._partials = torch.empty(ops.link_mlp_partial_floats(self.d, self.hidden), dtype=torch.float32, device=ctx.device)
+            torch.cuda.current_stream(ctx.device).synchronize()
+
+    def loss_backward(self, ctx: context, H: dn_matrix) -> dn_matrix:
+        """draw, sort, bounds, the three link_mlp_loss launches, the parameters' gradient from one link_mlp_pairs launch and
+        the sums on the embeddings H; returns G = dL/dH and leaves G_W1, G_b1, G_w2, G_b2.  Enqueue-only."""
+        if H.shape() != (self.n, self.d):
+            raise ValueError(f"H must be {self.n} x {self.d}, got {H.n()} x {H.m()}")
+        self._allocate(ctx)
+        n, M, R = self.n, self.M, self.neg_ratio
+        (keys, vals, keys_alt, vals_alt), work = self._arrays
+        r = self._rows
+        p_ip, p_ix, _ = self.P.device(ctx.device)
+        t_ip, t_ix, _ = self.P_T.device(ctx.device)
+        draw, params = dict(seed=self.seed, epoch=self.epoch), self.params()
+        ops.link_neg_draw(ctx, n, p_ip, M, n, R, self.seed, self.epoch, keys, vals, timer="link-draw")
+        ops.radix_sort_pairs(ctx, 1, M * R, keys, vals, keys_alt, vals_alt, work, 0, self.sort_bits(), timer="link-sort")
+        ops.link_bounds(ctx, keys, M * R, n, r["nt_indptr"], timer="link-bounds")
+        w_pos, w_neg = 1.0 / M, 1.0 / (M * R)
+        ctx.record("link-loss_0", 0)
+        ops.link_mlp_loss(ctx, n, n, p_ip, p_ix, M, H, params, r["G"], True, w_pos, R, w_neg, beta=0.0,
+                          row_loss=r["row_loss"], row_correct=r["row_correct"], **draw)
+        ops.link_mlp_loss(ctx, n, n, t_ip, t_ix, M, H, params, r["G"], True, w_pos, beta=1.0)
+        ops.link_mlp_loss(ctx, n, n, r["nt_indptr"], vals, M * R, H, params, r["G"], False, w_neg, beta=1.0)
+        ops.link_mlp_pairs(ctx, H, params, train=(self._head, p_ix, M, R, n, self.seed, self.epoch), weight=w_pos,
+                           neg_weight=w_neg, grads=self._grads, partials=self._partials, timer="link-wgrad")
+        ops.link_sums(ctx, r["row_loss"], r["row_correct"], n, r["sums"])
+        ctx.record("link-loss_1", 0)
+        ctx.register_timer("link-loss", "link-loss_0", "link-loss_1")
+        return r["G"]
+
+    def train_step(self, ctx: context, X: dn_matrix, lr: float, beta1: float, beta2: float, weight_decay: float, eps: float):
+        model = self.model
+        H = model(ctx, X, training=True)
+        G = self.loss_backward(ctx, H)
+        self.epoch += 1
+        for layer in reversed(model.layers()):
+            G = layer.backward(ctx, G)
+        model.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+        self.owner.adam_update(ctx, lr, beta1, beta2, weight_decay, eps)
+        model._launched()
+        ctx.sync()
+        return self.read()
+
+    def _score(self, ctx: context, X: dn_matrix, pairs: np.ndarray) -> dn_matrix:
+        m = pairs.shape[0]
+        out = dn_matrix(m, 1, device=ctx.device)
+        H = self.model(ctx, X)
+        if m:
+            src = dn_matrix.from_numpy(pairs[:, 0].view(np.int32), device=ctx.device)
+            dst = dn_matrix.from_numpy(pairs[:, 1].view(np.int32), device=ctx.device)
+            ops.link_mlp_pairs(ctx, H, self.params(), pairs=(src.t.view(-1), dst.t.view(-1), m), out=out.t.view(-1))
+        ctx.sync()
+        return out

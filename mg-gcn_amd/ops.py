@@ -1845,6 +1845,126 @@ def edge_dot(ctx: context, src, dst, m: int, H, out, timer: Optional[str] = None
                                                               out.data_ptr()))
 
 
+# ---- the MLP decoder of the link head (csrc/link_mlp.hip) -------------------------------------------------------------------------
+LINK_MLP_WIDTHS = (32, 64, 96, 128)     # d and hd: multiples of 32 up to MGGCN_LINK_MLP_MAX_WIDTH, W1 stays in LDS
+LINK_MLP_PAIRS_GRID = 256               # the workgroups of link_mlp_pairs = the rows of its partials
+
+
+def link_mlp_grad_floats(d: int, hd: int) -> int:
+    """the packed gradient [G_W1 (d hd) | G_b1 (hd) | G_w2 (hd) | G_b2 (1)] of link_mlp_pairs"""
+    return d * hd + 2 * hd + 1
+
+
+def link_mlp_partial_floats(d: int, hd: int) -> int:
+    """mggcn_link_mlp_partial_floats restated on the host: one packed gradient per workgroup"""
+    return LINK_MLP_PAIRS_GRID * link_mlp_grad_floats(d, hd)
+
+
+def _req_link_mlp(what: str, d: int, params) -> tuple:
+    """(pointers of W1, b1, w2, b2; hd): contiguous fp32 device tensors of d x hd, hd, hd and 1 elements"""
+    _req(d in LINK_MLP_WIDTHS, f"{what}: the embedding width d must be a multiple of 32 in [32, 128], got {d}")
+    _req(isinstance(params, (tuple, list)) and len(params) == 4, f"{what}: params must be (W1, b1, w2, b2)")
+    ts = [p.t if isinstance(p, dn_matrix) else p for p in params]
+    _req(hasattr(ts[1], "numel"), f"{what}: b1 must be a device tensor")
+    hd = int(ts[1].numel())
+    _req(hd in LINK_MLP_WIDTHS, f"{what}: the hidden width hd must be a multiple of 32 in [32, 128], got {hd}")
+    for name, t, size in zip(("W1", "b1", "w2", "b2"), ts, (d * hd, hd, hd, 1)):
+        _req_f32(t, size, f"{what}: {name}")
+        _req(t.numel() == size, f"{what}: {name} must have {size} elements, got {t.numel()}")
+    return [t.data_ptr() for t in ts], hd
+
+
+def link_mlp_loss(ctx: context, n_rows: int, n_cols: int, indptr, indices, nnz: int, H, params, G, positive: bool,
+                  weight: float, neg_ratio: int = 0, neg_weight: float = 0.0, seed: int = 0, epoch: int = 0, beta: float = 0.0,
+                  row_loss=None, row_correct=None, timer: Optional[str] = None) -> None:
+    """link_dot_loss with the MLP decoder (mggcn_link_mlp_loss_f32): s = w2 . leaky_relu(W1^T (H[x] (.) H[y]) + b1) + b2 with
+    ``params`` = (W1 [d x hd], b1, w2 [1 x hd], b2 [1 x 1]) as dn_matrix or contiguous fp32 device tensors, and
+    G[x] = beta G[x] + sum over the row's pairs of g (W1 dz) (.) H[y].  Everything else -- the pattern, ``positive``, the
+    weights, the negatives drawn in the walk, row_loss / row_correct, the three launches of a step -- is link_dot_loss's.
+    d and hd: multiples of 32 in [32, 128].  The same bits on every call."""
+    what = "link mlp loss"
+    for name, v in (("n_rows", n_rows), ("n_cols", n_cols)):
+        _req(isinstance(v, numbers.Integral) and 0 <= v < 1 << 31, f"{what}: {name} must be below 2^31")
+    nnz, R, _ = _req_link_counts(what, nnz, neg_ratio, n_cols, False)
+    hp, ldh, hn, d = _dense_window(H, True, f"{what}: H")
+    gp, ldg, gn, gd = _dense_window(G, True, f"{what}: G")
+    ptrs, hd = _req_link_mlp(what, d, params)
+    _req(hn >= max(n_rows, n_cols if nnz else 0), f"{what}: H must have a row for every row and column of the pattern, got {hn}")
+    _req((gn, gd) == (n_rows, d), f"{what}: G must be {n_rows} x {d}, got {gn} x {gd}")
+    _req_u32(indptr, n_rows + 1, f"{what}: indptr")
+    _req_u32(indices, nnz, f"{what}: indices")
+    h_bytes, g_bytes = 4 * ((hn - 1) * ldh + d) if hn else 0, 4 * ((gn - 1) * ldg + d) if gn else 0
+    _req_apart(what, gp, g_bytes, "G", hp, h_bytes, "H")
+    _req_apart(what, gp, g_bytes, "G", ptrs[0], 4 * d * hd, "W1")
+    _req((row_loss is None) == (row_correct is None), f"{what}: row_loss and row_correct come together")
+    if row_loss is not None:
+        _req_f32(row_loss, 2 * n_rows, f"{what}: row_loss")
+        _req_u32(row_correct, n_rows, f"{what}: row_correct")
+        outs = (("row_loss", row_loss.data_ptr(), 8 * n_rows), ("row_correct", row_correct.data_ptr(), 4 * n_rows),
+                ("G", gp, g_bytes), ("H", hp, h_bytes))
+        for i, (na, a, ab) in enumerate(outs[:2]):
+            for nb, b, bb in outs[i + 1:]:
+                _req_apart(what, a, ab, na, b, bb, nb)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_mlp_loss_f32(
+        ctx.stream(0), int(n_rows), int(n_cols), indptr.data_ptr(), indices.data_ptr(), nnz, hp, ldh, d, *ptrs, hd,
+        int(bool(positive)), float(weight), R, float(neg_weight), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF,
+        float(beta), gp, ldg, row_loss.data_ptr() if row_loss is not None else None,
+        row_correct.data_ptr() if row_correct is not None else None))
+
+
+def link_mlp_pairs(ctx: context, H, params, pairs=None, train=None, positive: bool = True, weight: float = 1.0,
+                   neg_weight: float = 0.0, out=None, grads=None, partials=None, timer: Optional[str] = None) -> None:
+    """The MLP decoder over a flat list of pairs (mggcn_link_mlp_pairs_f32), exactly one of
+      pairs = (src, dst, m)          explicit: device tensors of 4-byte integers below H's row count (the caller's to
+                                     guarantee), every pair of label ``positive`` and weight ``weight``;
+      train = (head, indices, M, R, n, seed, epoch)
+                                     the training list of a pattern of M entries: position q in [0, M (1 + R)) is entry
+                                     q // (1 + R); slot 0 the positive (head[p], indices[p]) at ``weight``, slot r + 1 negative r
+                                     of the entry, drawn as link_neg_draw draws it over [0, n), at ``neg_weight``.
+    out (fp32, one per pair): the scores.  grads (fp32, link_mlp_grad_floats(d, hd)): the gradient of the weighted loss in
+    [W1 | b1 | w2 | b2], with partials (fp32, link_mlp_partial_floats(d, hd)) as work space.  One of out and grads may be None.
+    H and params as in link_mlp_loss.  The same bits on every call; no atomics."""
+    what = "link mlp pairs"
+    hp, ldh, hn, d = _dense_window(H, True, f"{what}: H")
+    ptrs, hd = _req_link_mlp(what, d, params)
+    _req((pairs is None) != (train is None), f"{what}: exactly one of pairs and train")
+    _req(out is not None or grads is not None, f"{what}: one of out and grads is needed")
+    if pairs is not None:
+        src, dst, m = pairs
+        m = _req_count(m, f"{what}: m")
+        _req(m < 1 << 31, f"{what}: m must be below 2^31, got {m}")
+        _req_u32(src, m, f"{what}: src")
+        _req_u32(dst, m, f"{what}: dst")
+        lists = (src.data_ptr(), dst.data_ptr(), m, None, None, 0, 0, 0, 0, 0)
+    else:
+        head, indices, M, R, n, seed, epoch = train
+        M, R, n = _req_link_counts(what, M, R, n, False)
+        _req(n >= 1 or R == 0, f"{what}: n must be positive")
+        _req_u32(head, M, f"{what}: head")
+        _req_u32(indices, M, f"{what}: indices")
+        m = M * (1 + R)
+        lists = (None, None, 0, head.data_ptr(), indices.data_ptr(), M, R, n, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                 int(epoch) & 0xFFFFFFFF)
+    _req(hn >= 1 or m == 0, f"{what}: H has no rows")
+    h_bytes = 4 * ((hn - 1) * ldh + d) if hn else 0
+    if out is not None:
+        _req_f32(out, m, f"{what}: out")
+        _req_apart(what, out.data_ptr(), 4 * m, "out", hp, h_bytes, "H")
+    if grads is not None:
+        width = link_mlp_grad_floats(d, hd)
+        _req_f32(grads, width, f"{what}: grads")
+        _req(partials is not None, f"{what}: grads needs partials")
+        _req_f32(partials, link_mlp_partial_floats(d, hd), f"{what}: partials")
+        for name, p, nbytes in (("H", hp, h_bytes), ("W1", ptrs[0], 4 * d * hd), ("partials", partials.data_ptr(),
+                                                                                  4 * link_mlp_partial_floats(d, hd))):
+            _req_apart(what, grads.data_ptr(), 4 * width, "grads", p, nbytes, name)
+        _req_apart(what, partials.data_ptr(), 4 * link_mlp_partial_floats(d, hd), "partials", hp, h_bytes, "H")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_mlp_pairs_f32(
+        ctx.stream(0), *lists, int(bool(positive)), float(weight), float(neg_weight), hp, ldh, hn, d, *ptrs, hd,
+        out.data_ptr() if out is not None else None, grads.data_ptr() if grads is not None else None,
+        partials.data_ptr() if grads is not None else None))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
