@@ -1115,6 +1115,46 @@ void mggcn_link_mlp_pairs_f32(mggcn_stream_t stream, const uint32_t *src, const 
                               uint32_t d, const float *W1, const float *b1, const float *w2, const float *b2, uint32_t hd,
                               float *out, float *grads, float *partials);
 
+/* Link prediction, MLP decoder, bf16 operands: the two entries above on v_mfma_f32_32x32x16_bf16 (csrc/link_mlp_b16.hip; opt-in,
+ * no reference counterpart).  The patterns, `positive`, weights, in-walk negatives, beta, row sums, the three launches, the
+ * training list, the packed gradient, `partials` and mggcn_link_mlp_partial_floats are the fp32 entries'; H and W1 arrive as
+ * images of bf16 bit patterns.  The contract:
+ *   1 Rounding   The kernels see Hb = bf16(H) and W1b = bf16(W1), round to nearest even as mggcn_convert_f32_bf16 does.  Hb is
+ *                an [n x d] image of the caller's, written by mggcn_convert_f32_bf16 once per step; W1b is written by
+ *                mggcn_link_mlp_pack_bf16 once per step, after Adam has run on the fp32 master.  Both endpoints of a pair are
+ *                read from the image, the row's own H[x] included: s stays symmetric and the three walks still add up to all
+ *                of dL/dH.  b1, w2 and b2 stay fp32.
+ *   2 Forward    x = bf16(Hb[u] Hb[v]) -- the product of two bf16 values is exact in fp32, so this is one rounding;
+ *                z = b1 + W1b^T x with fp32 accumulation on the matrix cores; a, s, the loss, g and the hit in fp32, exactly
+ *                as the fp32 entries form them.
+ *   3 Backward   straight-through: the roundings have derivative 1.  dz = bf16(g w2 lrelu'(z)), dx = W1b dz with fp32
+ *                accumulation, G[x] = beta G[x] + sum dx (.) Hb[y] in fp32, G_W1 = sum x^T dz over the flat pair list with x
+ *                and dz the bf16 values above and fp32 accumulation; G_b1, G_w2 and G_b2 from the unrounded fp32 dz, g a and g.
+ *   4 Determinism  No atomics, the same bits on every call.  The grid caps (512 workgroups of the walk, 256 of the pairs
+ *                kernel), the tile rule (workgroup b takes tiles b, b + grid, ...) and the order of k inside a 32-block
+ *                (slot e of lane half h in step s is index 16 s + 8 (e / 4) + 4 h + e % 4) fix the order of the sums.  Bitwise
+ *                equality with a k-ordered fmaf chain is NOT claimed: the order inside the 16-deep instruction is the hardware's.
+ *   pack         image = both orientations of W1b in the kernels' slot order, mggcn_link_mlp_image_halves(d, hd) =
+ *                hd (d + 8) + d (hd + 8) uint16_t of the caller's, 16-byte aligned: F[j][perm(c)] = W1b[c][j] in rows of d + 8,
+ *                then B[c][perm(j)] = W1b[c][j] in rows of hd + 8, perm = bits 2 and 3 of the index swapped, the 8 elements
+ *                behind each row zero.  The layout is the library's own and may change with it.
+ *   Hb           row-major with ldhb >= d elements, an 8-byte aligned base and ldhb % 4 == 0 (the walk loads 8 bytes at a time).
+ * G is fp32 as before: 16-byte aligned rows take 16-byte stores, anything else 4-byte ones.
+ * Refused before any launch: what the fp32 entries refuse; an Hb whose base or pitch is not as above; an image that is not
+ * 16-byte aligned; an image that overlaps W1 or an output. */
+size_t mggcn_link_mlp_image_halves(uint32_t d, uint32_t hd);
+void mggcn_link_mlp_pack_bf16(mggcn_stream_t stream, const float *W1, uint32_t d, uint32_t hd, uint16_t *image);
+void mggcn_link_mlp_loss_bf16(mggcn_stream_t stream, uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr,
+                              const uint32_t *indices, size_t nnz, const uint16_t *Hb, size_t ldhb, uint32_t d,
+                              const uint16_t *image, const float *b1, const float *w2, const float *b2, uint32_t hd, int positive,
+                              float weight, uint32_t R, float neg_weight, uint64_t seed, uint32_t epoch, float beta, float *G,
+                              size_t ldg, float *row_loss, uint32_t *row_correct);
+void mggcn_link_mlp_pairs_bf16(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m, const uint32_t *head,
+                               const uint32_t *indices, size_t M, uint32_t R, uint32_t n_draw, uint64_t seed, uint32_t epoch,
+                               int positive, float weight, float neg_weight, const uint16_t *Hb, size_t ldhb, size_t n_rows,
+                               uint32_t d, const uint16_t *image, const float *b1, const float *w2, const float *b2, uint32_t hd,
+                               float *out, float *grads, float *partials);
+
 /* cublasSasum(src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

@@ -39,7 +39,7 @@ Layout:
   link.py        link_predictor: link prediction over any single-GPU encoder -- a dot-product decoder, negatives drawn on the
                  device, loss and both endpoints' gradient in one fused kernel launched three times (csrc/link.hip; no
                  reference counterpart); mlp_link_predictor: the same with a Hadamard-MLP decoder on the matrix cores
-                 (csrc/link_mlp.hip)
+                 (csrc/link_mlp.hip; decoder_dtype="bf16": the bf16 matrix cores, csrc/link_mlp_b16.hip)
   smoothing.py   correct_and_smooth: label-propagation post-processing of any model's logits (csrc/propagate.hip around the
                  sweep SpMM; no reference counterpart)
 """

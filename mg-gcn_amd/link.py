@@ -240,9 +240,21 @@ def check_mlp_weights(weights, d: int, hidden: int) -> tuple:
     return tuple(out)
 
 
-class mlp_link_predictor(link_predictor):
-    """mlp_link_predictor(model, P, hidden=128, neg_ratio=1, seed=0, weights=None): link_predictor with the decoder of the
-    ogbl-* gcn / sage baselines in place of the dot product -- x = H[u] (.) H[v], z = W1^T x + b1, a = leaky_relu(z) (the
+class _decoder_option(type):
+    """mlp_link_predictor(..., decoder_dtype="f32" | "bf16"): the keyword is an option of the call, taken and checked here --
+    before __init__ allocates anything -- and left on the instance; __init__ keeps its documented parameter list."""
+
+    def __call__(cls, *args, decoder_dtype: str = "f32", **kw):
+        if decoder_dtype not in ("f32", "bf16"):
+            raise ValueError(f'decoder_dtype must be "f32" or "bf16", not {decoder_dtype!r}')
+        head = super().__call__(*args, **kw)
+        head.decoder_dtype = decoder_dtype
+        return head
+
+
+class mlp_link_predictor(link_predictor, metaclass=_decoder_option):
+    """mlp_link_predictor(model, P, hidden=128, neg_ratio=1, seed=0, weights=None, decoder_dtype="f32"): link_predictor with
+    the decoder of the ogbl-* gcn / sage baselines in place of the dot product -- x = H[u] (.) H[v], z = W1^T x + b1, a = leaky_relu(z) (the
     slope of the gcn layers), s = w2 . a + b2 -- on the matrix cores (csrc/link_mlp.hip).
 
     Parameters W1 [d x hidden], b1 [1 x hidden], w2 [1 x hidden], b2 [1 x 1], initialised like a linear's W and b (the
@@ -257,12 +269,22 @@ class mlp_link_predictor(link_predictor):
     list of M (1 + R) pairs, the negatives drawn a third time (timer link-wgrad).  On first use it allocates what the parent
     does plus the row of every entry (M words), the packed gradient and its per-workgroup partials.
 
+    decoder_dtype="bf16" (keyword only, opt-in; "f32" constructs, allocates, launches and registers what it always did) runs the decoder on
+    the bf16 matrix cores (csrc/link_mlp_b16.hip; the contract in include/mggcn.h): loss_backward and _score round H once into
+    a bf16 image of the head's and W1 into its packed image -- the fp32 W1 that Adam has just updated is the master --, then
+    launch ops.link_mlp_loss_bf16 / link_mlp_pairs_bf16 in place of their fp32 twins.  x, dz and both operands of the two
+    products are bf16 (straight-through in the backward), every sum, the loss, G, the parameters, their gradients and Adam's
+    state stay fp32.  score and evaluate use the bf16 decoder too: the model is scored by what it was trained with.  On first
+    use it allocates the two images as well (2 n d bytes and at most 68 KiB) and registers the timer link-pack.
+
     ValueError naming the argument, before any device work: what link_predictor refuses; the model's last width d or
     ``hidden`` not a multiple of 32 in [32, 128] (W1, at most 64 KiB, stays in LDS); ``weights`` of the wrong length or shapes or
-    with a non-finite value."""
+    with a non-finite value; a decoder_dtype other than "f32" and "bf16"."""
 
     params_table = (("W1", "W1", "G_W1", "mW1", "vW1", True), ("b1", "b1", "G_b1", "mb1", "vb1", False),
                     ("w2", "w2", "G_w2", "mw2", "vw2", True), ("b2", "b2", "G_b2", "mb2", "vb2", False))
+
+    decoder_dtype = "f32"                           # the call's keyword (see _decoder_option) overrides it per instance
 
     def __init__(self, model, P: csr_matrix, hidden: int = 128, neg_ratio: int = 1, seed: int = 0, weights=None):
         link_predictor.__init__(self, model, P, neg_ratio, seed)
@@ -295,7 +317,7 @@ class mlp_link_predictor(link_predictor):
             setattr(o, g, getattr(self, g))
             setattr(o, m, None)
             setattr(o, v, None)
-        self._partials = self._head = None
+        self._partials = self._head = self._images = None
 
     def params(self) -> tuple:
         return self.W1, self.b1, self.w2, self.b2
@@ -313,6 +335,22 @@ class mlp_link_predictor(link_predictor):
             self._partials = torch.empty(ops.link_mlp_partial_floats(self.d, self.hidden), dtype=torch.float32, device=ctx.device)
             torch.cuda.current_stream(ctx.device).synchronize()
 
+    def _decoder(self, ctx: context, H: dn_matrix) -> tuple:
+        """(loss op, pairs op, embeddings, params) of decoder_dtype; bf16 rounds H and W1 into the head's images first"""
+        if self.decoder_dtype == "f32":
+            return ops.link_mlp_loss, ops.link_mlp_pairs, H, self.params()
+        if self._images is None:                    # fresh allocations: the pitch and the bases the kernels' loads assume
+            torch = _torch()
+            self._images = (torch.empty((self.n, self.d), dtype=torch.bfloat16, device=ctx.device),
+                            torch.empty(ops.link_mlp_image_halves(self.d, self.hidden), dtype=torch.bfloat16, device=ctx.device))
+        Hb, image = self._images
+        ctx.record("link-pack_0", 0)
+        ops.convert_bf16(ctx, H, Hb)
+        ops.link_mlp_pack_bf16(ctx, self.W1, image)
+        ctx.record("link-pack_1", 0)
+        ctx.register_timer("link-pack", "link-pack_0", "link-pack_1")
+        return ops.link_mlp_loss_bf16, ops.link_mlp_pairs_bf16, Hb, (image, self.b1, self.w2, self.b2)
+
     def loss_backward(self, ctx: context, H: dn_matrix) -> dn_matrix:
         """draw, sort, bounds, the three link_mlp_loss launches, the parameters' gradient from one link_mlp_pairs launch and
         the sums on the embeddings H; returns G = dL/dH and leaves G_W1, G_b1, G_w2, G_b2.  Enqueue-only."""
@@ -324,18 +362,19 @@ class mlp_link_predictor(link_predictor):
         r = self._rows
         p_ip, p_ix, _ = self.P.device(ctx.device)
         t_ip, t_ix, _ = self.P_T.device(ctx.device)
-        draw, params = dict(seed=self.seed, epoch=self.epoch), self.params()
+        draw = dict(seed=self.seed, epoch=self.epoch)
+        link_mlp_loss, link_mlp_pairs, H, params = self._decoder(ctx, H)
         ops.link_neg_draw(ctx, n, p_ip, M, n, R, self.seed, self.epoch, keys, vals, timer="link-draw")
         ops.radix_sort_pairs(ctx, 1, M * R, keys, vals, keys_alt, vals_alt, work, 0, self.sort_bits(), timer="link-sort")
         ops.link_bounds(ctx, keys, M * R, n, r["nt_indptr"], timer="link-bounds")
         w_pos, w_neg = 1.0 / M, 1.0 / (M * R)
         ctx.record("link-loss_0", 0)
-        ops.link_mlp_loss(ctx, n, n, p_ip, p_ix, M, H, params, r["G"], True, w_pos, R, w_neg, beta=0.0,
-                          row_loss=r["row_loss"], row_correct=r["row_correct"], **draw)
-        ops.link_mlp_loss(ctx, n, n, t_ip, t_ix, M, H, params, r["G"], True, w_pos, beta=1.0)
-        ops.link_mlp_loss(ctx, n, n, r["nt_indptr"], vals, M * R, H, params, r["G"], False, w_neg, beta=1.0)
-        ops.link_mlp_pairs(ctx, H, params, train=(self._head, p_ix, M, R, n, self.seed, self.epoch), weight=w_pos,
-                           neg_weight=w_neg, grads=self._grads, partials=self._partials, timer="link-wgrad")
+        link_mlp_loss(ctx, n, n, p_ip, p_ix, M, H, params, r["G"], True, w_pos, R, w_neg, beta=0.0,
+                      row_loss=r["row_loss"], row_correct=r["row_correct"], **draw)
+        link_mlp_loss(ctx, n, n, t_ip, t_ix, M, H, params, r["G"], True, w_pos, beta=1.0)
+        link_mlp_loss(ctx, n, n, r["nt_indptr"], vals, M * R, H, params, r["G"], False, w_neg, beta=1.0)
+        link_mlp_pairs(ctx, H, params, train=(self._head, p_ix, M, R, n, self.seed, self.epoch), weight=w_pos,
+                       neg_weight=w_neg, grads=self._grads, partials=self._partials, timer="link-wgrad")
         ops.link_sums(ctx, r["row_loss"], r["row_correct"], n, r["sums"])
         ctx.record("link-loss_1", 0)
         ctx.register_timer("link-loss", "link-loss_0", "link-loss_1")
@@ -361,6 +400,7 @@ class mlp_link_predictor(link_predictor):
         if m:
             src = dn_matrix.from_numpy(pairs[:, 0].view(np.int32), device=ctx.device)
             dst = dn_matrix.from_numpy(pairs[:, 1].view(np.int32), device=ctx.device)
-            ops.link_mlp_pairs(ctx, H, self.params(), pairs=(src.t.view(-1), dst.t.view(-1), m), out=out.t.view(-1))
+            _, link_mlp_pairs, H, params = self._decoder(ctx, H)
+            link_mlp_pairs(ctx, H, params, pairs=(src.t.view(-1), dst.t.view(-1), m), out=out.t.view(-1))
         ctx.sync()
         return out

@@ -1860,18 +1860,64 @@ def link_mlp_partial_floats(d: int, hd: int) -> int:
     return LINK_MLP_PAIRS_GRID * link_mlp_grad_floats(d, hd)
 
 
-def _req_link_mlp(what: str, d: int, params) -> tuple:
-    """(pointers of W1, b1, w2, b2; hd): contiguous fp32 device tensors of d x hd, hd, hd and 1 elements"""
+def link_mlp_image_halves(d: int, hd: int) -> int:
+    """mggcn_link_mlp_image_halves restated on the host: both orientations of bf16(W1), every row padded by 8 elements"""
+    return hd * (d + 8) + d * (hd + 8)
+
+
+def _req_link_mlp(what: str, d: int, params, b16: bool = False) -> tuple:
+    """(pointers of W1, b1, w2, b2; hd; bytes of W1): contiguous fp32 device tensors of d x hd, hd, hd and 1 elements; with
+    ``b16`` the first is the image link_mlp_pack_bf16 wrote, link_mlp_image_halves(d, hd) 2-byte elements, 16-byte aligned"""
     _req(d in LINK_MLP_WIDTHS, f"{what}: the embedding width d must be a multiple of 32 in [32, 128], got {d}")
-    _req(isinstance(params, (tuple, list)) and len(params) == 4, f"{what}: params must be (W1, b1, w2, b2)")
+    _req(isinstance(params, (tuple, list)) and len(params) == 4,
+         f"{what}: params must be ({'the W1 image' if b16 else 'W1'}, b1, w2, b2)")
     ts = [p.t if isinstance(p, dn_matrix) else p for p in params]
     _req(hasattr(ts[1], "numel"), f"{what}: b1 must be a device tensor")
     hd = int(ts[1].numel())
     _req(hd in LINK_MLP_WIDTHS, f"{what}: the hidden width hd must be a multiple of 32 in [32, 128], got {hd}")
     for name, t, size in zip(("W1", "b1", "w2", "b2"), ts, (d * hd, hd, hd, 1)):
+        if b16 and name == "W1":
+            halves = link_mlp_image_halves(d, hd)
+            _req(hasattr(t, "data_ptr") and t.is_cuda and t.is_contiguous() and t.element_size() == 2 and t.numel() == halves
+                 and t.data_ptr() % 16 == 0,
+                 f"{what}: the W1 image must be a contiguous, 16-byte aligned device tensor of link_mlp_image_halves(d, hd) = "
+                 f"{halves} 2-byte elements")
+            continue
         _req_f32(t, size, f"{what}: {name}")
         _req(t.numel() == size, f"{what}: {name} must have {size} elements, got {t.numel()}")
-    return [t.data_ptr() for t in ts], hd
+    return [t.data_ptr() for t in ts], hd, (2 * link_mlp_image_halves(d, hd) if b16 else 4 * d * hd)
+
+
+def _link_mlp_H(H, b16: bool, what: str) -> tuple:
+    """(pointer, leading dimension, rows, columns, bytes) of the embeddings: an fp32 window, or with ``b16`` the bf16 image
+    of one whose rows the walk can load 8 bytes at a time"""
+    if not b16:
+        hp, ldh, hn, d = _dense_window(H, True, what)
+        return hp, ldh, hn, d, (4 * ((hn - 1) * ldh + d) if hn else 0)
+    _req(hasattr(H, "dim"), f"{what}: a 2-D device tensor of bf16 (2-byte) elements")
+    hp, hn, d, ldh = _bf16_view(H, what)
+    _req(hp % 8 == 0 and ldh % 4 == 0, f"{what}: the image's row pitch must be a multiple of 4 elements on an 8-byte aligned "
+                                       f"base (the kernel loads 8 bytes at a time), got pitch {ldh}, base % 8 = {hp % 8}")
+    return hp, ldh, hn, d, (2 * ((hn - 1) * ldh + d) if hn else 0)
+
+
+def link_mlp_pack_bf16(ctx: context, W1, image, timer: Optional[str] = None) -> None:
+    """image = both orientations of bf16(W1) in the order the bf16 decoder's kernels read them (mggcn_link_mlp_pack_bf16; round
+    to nearest even).  W1: a dn_matrix or contiguous fp32 device tensor [d x hd]; image: a contiguous, 16-byte aligned device
+    tensor of link_mlp_image_halves(d, hd) 2-byte elements.  Once per step, after Adam has run on W1."""
+    what = "link mlp pack"
+    t = W1.t if isinstance(W1, dn_matrix) else W1
+    _req(hasattr(t, "dim") and t.dim() == 2, f"{what}: W1 must be a d x hd matrix")
+    d, hd = int(t.shape[0]), int(t.shape[1])
+    _req(d in LINK_MLP_WIDTHS, f"{what}: the embedding width d must be a multiple of 32 in [32, 128], got {d}")
+    _req(hd in LINK_MLP_WIDTHS, f"{what}: the hidden width hd must be a multiple of 32 in [32, 128], got {hd}")
+    _req_f32(t, d * hd, f"{what}: W1")
+    halves = link_mlp_image_halves(d, hd)
+    _req(hasattr(image, "data_ptr") and image.is_cuda and image.is_contiguous() and image.element_size() == 2
+         and image.numel() == halves and image.data_ptr() % 16 == 0,
+         f"{what}: image must be a contiguous, 16-byte aligned device tensor of {halves} 2-byte elements")
+    _req_apart(what, image.data_ptr(), 2 * halves, "image", t.data_ptr(), 4 * d * hd, "W1")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_mlp_pack_bf16(ctx.stream(0), t.data_ptr(), d, hd, image.data_ptr()))
 
 
 def link_mlp_loss(ctx: context, n_rows: int, n_cols: int, indptr, indices, nnz: int, H, params, G, positive: bool,
@@ -1882,20 +1928,37 @@ def link_mlp_loss(ctx: context, n_rows: int, n_cols: int, indptr, indices, nnz: 
     G[x] = beta G[x] + sum over the row's pairs of g (W1 dz) (.) H[y].  Everything else -- the pattern, ``positive``, the
     weights, the negatives drawn in the walk, row_loss / row_correct, the three launches of a step -- is link_dot_loss's.
     d and hd: multiples of 32 in [32, 128].  The same bits on every call."""
+    _link_mlp_loss(ctx, False, n_rows, n_cols, indptr, indices, nnz, H, params, G, positive, weight, neg_ratio, neg_weight, seed,
+                   epoch, beta, row_loss, row_correct, timer)
+
+
+def link_mlp_loss_bf16(ctx: context, n_rows: int, n_cols: int, indptr, indices, nnz: int, Hb, params, G, positive: bool,
+                       weight: float, neg_ratio: int = 0, neg_weight: float = 0.0, seed: int = 0, epoch: int = 0,
+                       beta: float = 0.0, row_loss=None, row_correct=None, timer: Optional[str] = None) -> None:
+    """link_mlp_loss on the bf16 matrix cores (mggcn_link_mlp_loss_bf16; the contract of include/mggcn.h, "MLP decoder, bf16
+    operands"): ``Hb`` the bf16 image of the embeddings (convert_bf16; a 2-D device tensor of 2-byte elements whose row pitch is a
+    multiple of 4 on an 8-byte aligned base), ``params`` = (the W1 image of link_mlp_pack_bf16, b1, w2, b2).  x, dz and both
+    operands of the two products are bf16, every sum, the loss and G fp32.  Everything else as link_mlp_loss."""
+    _link_mlp_loss(ctx, True, n_rows, n_cols, indptr, indices, nnz, Hb, params, G, positive, weight, neg_ratio, neg_weight, seed,
+                   epoch, beta, row_loss, row_correct, timer)
+
+
+def _link_mlp_loss(ctx, b16, n_rows, n_cols, indptr, indices, nnz, H, params, G, positive, weight, neg_ratio, neg_weight, seed,
+                   epoch, beta, row_loss, row_correct, timer) -> None:
     what = "link mlp loss"
     for name, v in (("n_rows", n_rows), ("n_cols", n_cols)):
         _req(isinstance(v, numbers.Integral) and 0 <= v < 1 << 31, f"{what}: {name} must be below 2^31")
     nnz, R, _ = _req_link_counts(what, nnz, neg_ratio, n_cols, False)
-    hp, ldh, hn, d = _dense_window(H, True, f"{what}: H")
+    hp, ldh, hn, d, h_bytes = _link_mlp_H(H, b16, f"{what}: H")
     gp, ldg, gn, gd = _dense_window(G, True, f"{what}: G")
-    ptrs, hd = _req_link_mlp(what, d, params)
+    ptrs, hd, w_bytes = _req_link_mlp(what, d, params, b16)
     _req(hn >= max(n_rows, n_cols if nnz else 0), f"{what}: H must have a row for every row and column of the pattern, got {hn}")
     _req((gn, gd) == (n_rows, d), f"{what}: G must be {n_rows} x {d}, got {gn} x {gd}")
     _req_u32(indptr, n_rows + 1, f"{what}: indptr")
     _req_u32(indices, nnz, f"{what}: indices")
-    h_bytes, g_bytes = 4 * ((hn - 1) * ldh + d) if hn else 0, 4 * ((gn - 1) * ldg + d) if gn else 0
+    g_bytes = 4 * ((gn - 1) * ldg + d) if gn else 0
     _req_apart(what, gp, g_bytes, "G", hp, h_bytes, "H")
-    _req_apart(what, gp, g_bytes, "G", ptrs[0], 4 * d * hd, "W1")
+    _req_apart(what, gp, g_bytes, "G", ptrs[0], w_bytes, "W1")
     _req((row_loss is None) == (row_correct is None), f"{what}: row_loss and row_correct come together")
     if row_loss is not None:
         _req_f32(row_loss, 2 * n_rows, f"{what}: row_loss")
@@ -1905,7 +1968,8 @@ def link_mlp_loss(ctx: context, n_rows: int, n_cols: int, indptr, indices, nnz: 
         for i, (na, a, ab) in enumerate(outs[:2]):
             for nb, b, bb in outs[i + 1:]:
                 _req_apart(what, a, ab, na, b, bb, nb)
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_mlp_loss_f32(
+    entry = ctx.lib.mggcn_link_mlp_loss_bf16 if b16 else ctx.lib.mggcn_link_mlp_loss_f32
+    _gat_timed(ctx, timer, lambda: entry(
         ctx.stream(0), int(n_rows), int(n_cols), indptr.data_ptr(), indices.data_ptr(), nnz, hp, ldh, d, *ptrs, hd,
         int(bool(positive)), float(weight), R, float(neg_weight), int(seed) & 0xFFFFFFFFFFFFFFFF, int(epoch) & 0xFFFFFFFF,
         float(beta), gp, ldg, row_loss.data_ptr() if row_loss is not None else None,
@@ -1924,9 +1988,21 @@ def link_mlp_pairs(ctx: context, H, params, pairs=None, train=None, positive: bo
     out (fp32, one per pair): the scores.  grads (fp32, link_mlp_grad_floats(d, hd)): the gradient of the weighted loss in
     [W1 | b1 | w2 | b2], with partials (fp32, link_mlp_partial_floats(d, hd)) as work space.  One of out and grads may be None.
     H and params as in link_mlp_loss.  The same bits on every call; no atomics."""
+    _link_mlp_pairs(ctx, False, H, params, pairs, train, positive, weight, neg_weight, out, grads, partials, timer)
+
+
+def link_mlp_pairs_bf16(ctx: context, Hb, params, pairs=None, train=None, positive: bool = True, weight: float = 1.0,
+                        neg_weight: float = 0.0, out=None, grads=None, partials=None, timer: Optional[str] = None) -> None:
+    """link_mlp_pairs on the bf16 matrix cores (mggcn_link_mlp_pairs_bf16): ``Hb`` and ``params`` as in link_mlp_loss_bf16, the
+    scores of the bf16 decoder, G_W1 = sum x^T dz from the bf16 x and dz with fp32 sums, G_b1, G_w2 and G_b2 from the
+    unrounded fp32 terms.  grads, partials and everything else as link_mlp_pairs."""
+    _link_mlp_pairs(ctx, True, Hb, params, pairs, train, positive, weight, neg_weight, out, grads, partials, timer)
+
+
+def _link_mlp_pairs(ctx, b16, H, params, pairs, train, positive, weight, neg_weight, out, grads, partials, timer) -> None:
     what = "link mlp pairs"
-    hp, ldh, hn, d = _dense_window(H, True, f"{what}: H")
-    ptrs, hd = _req_link_mlp(what, d, params)
+    hp, ldh, hn, d, h_bytes = _link_mlp_H(H, b16, f"{what}: H")
+    ptrs, hd, w_bytes = _req_link_mlp(what, d, params, b16)
     _req((pairs is None) != (train is None), f"{what}: exactly one of pairs and train")
     _req(out is not None or grads is not None, f"{what}: one of out and grads is needed")
     if pairs is not None:
@@ -1946,7 +2022,6 @@ def link_mlp_pairs(ctx: context, H, params, pairs=None, train=None, positive: bo
         lists = (None, None, 0, head.data_ptr(), indices.data_ptr(), M, R, n, int(seed) & 0xFFFFFFFFFFFFFFFF,
                  int(epoch) & 0xFFFFFFFF)
     _req(hn >= 1 or m == 0, f"{what}: H has no rows")
-    h_bytes = 4 * ((hn - 1) * ldh + d) if hn else 0
     if out is not None:
         _req_f32(out, m, f"{what}: out")
         _req_apart(what, out.data_ptr(), 4 * m, "out", hp, h_bytes, "H")
@@ -1955,11 +2030,12 @@ def link_mlp_pairs(ctx: context, H, params, pairs=None, train=None, positive: bo
         _req_f32(grads, width, f"{what}: grads")
         _req(partials is not None, f"{what}: grads needs partials")
         _req_f32(partials, link_mlp_partial_floats(d, hd), f"{what}: partials")
-        for name, p, nbytes in (("H", hp, h_bytes), ("W1", ptrs[0], 4 * d * hd), ("partials", partials.data_ptr(),
+        for name, p, nbytes in (("H", hp, h_bytes), ("W1", ptrs[0], w_bytes), ("partials", partials.data_ptr(),
                                                                                   4 * link_mlp_partial_floats(d, hd))):
             _req_apart(what, grads.data_ptr(), 4 * width, "grads", p, nbytes, name)
         _req_apart(what, partials.data_ptr(), 4 * link_mlp_partial_floats(d, hd), "partials", hp, h_bytes, "H")
-    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_mlp_pairs_f32(
+    entry = ctx.lib.mggcn_link_mlp_pairs_bf16 if b16 else ctx.lib.mggcn_link_mlp_pairs_f32
+    _gat_timed(ctx, timer, lambda: entry(
         ctx.stream(0), *lists, int(bool(positive)), float(weight), float(neg_weight), hp, ldh, hn, d, *ptrs, hd,
         out.data_ptr() if out is not None else None, grads.data_ptr() if grads is not None else None,
         partials.data_ptr() if grads is not None else None))
