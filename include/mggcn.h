@@ -1155,6 +1155,42 @@ void mggcn_link_mlp_pairs_bf16(mggcn_stream_t stream, const uint32_t *src, const
                                uint32_t d, const uint16_t *image, const float *b1, const float *w2, const float *b2, uint32_t hd,
                                float *out, float *grads, float *partials);
 
+/* Link prediction, ranking: the integers behind MRR and Hits@K of the three decoders above (csrc/link_rank.hip; opt-in, no
+ * reference counterpart).  For every positive pair i of score s_i every entry writes
+ *     counts[2 i] = greater[i] = #{negatives of i: s_neg > s_i},   counts[2 i + 1] = equal[i] = #{negatives of i: s_neg == s_i},
+ * scores compared as floats (-0.0 ties with +0.0).  OGB's rank is 1 + greater + equal / 2; the host forms MRR and Hits@K.
+ * Scores are assumed finite.  A NaN compares false both ways: in the three per-positive entries a NaN negative is counted in
+ * neither number and a NaN positive gets (0, 0); the sorted entry ranks a NaN where the key map puts its bit pattern.
+ *   rank_dot / rank_mlp / rank_mlp_bf16   per-positive negatives (ogbl-citation2): positive i is (src[i], dst[i]), its K
+ *               negatives are (src[i], tails[i K + k]), k < K; m K < 2^31.  One wave per positive, H[src[i]] loaded once, the
+ *               positive's tail scored first, no score stored.  rank_dot walks the tails on the layout of
+ *               mggcn_link_dot_loss_f32 and takes mggcn_edge_dot_f32's load path by its rule; the two MLP entries take the tails
+ *               32 at a time on the matrix instruction of mggcn_link_mlp_loss_f32 / _bf16, forward only, on a persistent grid
+ *               of at most 512 workgroups, with H, ldh, the parameters and the images exactly as those entries take them.
+ *               K == 0 writes zeros.
+ *   rank_sorted the shared list (ogbl-collab, -ppa, -ddi): pos_scores [m] are the positives' scores and sorted_keys [m_neg]
+ *               the negatives' scores as the keys of mggcn_roc_auc_keys_f32, sorted ascending over all 32 bits by
+ *               mggcn_radix_sort_pairs_u32; one lower-bound and one upper-bound bisection per positive on its own key,
+ *               greater = m_neg - upper, equal = upper - lower.
+ *   Bit equality  Each per-positive entry gives a pair the score, bit for bit, that the matching pair entry gives it --
+ *               mggcn_edge_dot_f32, mggcn_link_mlp_pairs_f32 or mggcn_link_mlp_pairs_bf16 with `out` -- on the same operands
+ *               and the same load path: the same order of k in every product and the same tree over the hidden units,
+ *               whatever lane group, tile slot or tile scores the pair.  So a tail equal to the positive's tail is always
+ *               counted in `equal`, and the counts are, integer for integer, what one would count from those entries' scores.
+ *   No atomics, no scratch; integer sums only, so no result depends on an order.  counts: 2 m words, 8-byte aligned.
+ * Refused before any launch: d or hd outside the decoder's range; m K >= 2^31, m or m_neg >= 2^31; a null operand; an Hb or an
+ * image that is not aligned as above; counts that overlap an input. */
+void mggcn_link_rank_dot_f32(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m, const uint32_t *tails,
+                             uint32_t K, const float *H, size_t ldh, size_t n_rows, uint32_t d, uint32_t *counts);
+void mggcn_link_rank_mlp_f32(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m, const uint32_t *tails,
+                             uint32_t K, const float *H, size_t ldh, size_t n_rows, uint32_t d, const float *W1, const float *b1,
+                             const float *w2, const float *b2, uint32_t hd, uint32_t *counts);
+void mggcn_link_rank_mlp_bf16(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m, const uint32_t *tails,
+                              uint32_t K, const uint16_t *Hb, size_t ldhb, size_t n_rows, uint32_t d, const uint16_t *image,
+                              const float *b1, const float *w2, const float *b2, uint32_t hd, uint32_t *counts);
+void mggcn_link_rank_sorted_u32(mggcn_stream_t stream, const float *pos_scores, size_t m, const uint32_t *sorted_keys,
+                                size_t m_neg, uint32_t *counts);
+
 /* cublasSasum(src/cuda_utils.hpp:362-371)  *result_device = sum |A[i]|.
  * Unlike cuBLAS' host-pointer mode this does NOT block: the sum lands in device
  * memory on `stream` (fixed-order two-level reduction -> reproducible); the host

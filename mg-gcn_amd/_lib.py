@@ -236,6 +236,12 @@ PROTOTYPES = {
                                         c_int, c_float, c_uint32, c_float, c_uint64, c_uint32, c_float, vp, c_size_t, vp, vp]),
     "mggcn_link_mlp_pairs_bf16": (None, [vp, vp, vp, c_size_t, vp, vp, c_size_t, c_uint32, c_uint32, c_uint64, c_uint32, c_int,
                                          c_float, c_float, vp, c_size_t, c_size_t, c_uint32, vp, vp, vp, vp, c_uint32, vp, vp, vp]),
+    "mggcn_link_rank_dot_f32": (None, [vp, vp, vp, c_size_t, vp, c_uint32, vp, c_size_t, c_size_t, c_uint32, vp]),
+    "mggcn_link_rank_mlp_f32": (None, [vp, vp, vp, c_size_t, vp, c_uint32, vp, c_size_t, c_size_t, c_uint32, vp, vp, vp, vp,
+                                       c_uint32, vp]),
+    "mggcn_link_rank_mlp_bf16": (None, [vp, vp, vp, c_size_t, vp, c_uint32, vp, c_size_t, c_size_t, c_uint32, vp, vp, vp, vp,
+                                        c_uint32, vp]),
+    "mggcn_link_rank_sorted_u32": (None, [vp, vp, c_size_t, vp, c_size_t, vp]),
     "mggcn_abssum_f32": (None, [vp, vp, c_size_t, vp]),
     "mggcn_gather_rows_f32": (None, [vp, vp, c_size_t, vp, c_size_t, c_uint32, vp, c_size_t]),
     "mggcn_softmax_xent_fused_f32": (None, [vp, vp, vp, c_size_t, c_size_t, c_float, vp]),

@@ -26,6 +26,10 @@ __device__ __forceinline__ float fold_groups(float v, uint32_t lpr) {
     for (uint32_t off = lpr; off < 64; off <<= 1) v += __shfl_xor(v, off);
     return v;
 }
+[[maybe_unused]] __device__ __forceinline__ uint32_t fold_groups_u32(uint32_t v, uint32_t lpr) {    // of the link walks' counts
+    for (uint32_t off = lpr; off < 64; off <<= 1) v += (uint32_t)__shfl_xor((int)v, off);
+    return v;
+}
 
 __device__ __forceinline__ float gat_lrelu(float x, float slope) { return x > 0.f ? x : slope * x; }
 

@@ -29,11 +29,6 @@
 
 namespace {
 
-__device__ __forceinline__ uint32_t fold_groups_u32(uint32_t v, uint32_t lpr) {
-    for (uint32_t off = lpr; off < 64; off <<= 1) v += (uint32_t)__shfl_xor((int)v, off);
-    return v;
-}
-
 // R == 0: no negatives are drawn (launches (b) and (c)); row_loss == nullptr: no row sums are written
 template <int VEC, int NT, int U>
 __global__ __launch_bounds__(256) void link_dot_loss_kernel(uint32_t n_rows, const uint32_t *__restrict__ indptr,

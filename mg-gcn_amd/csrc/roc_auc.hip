@@ -28,6 +28,7 @@
 //                     a butterfly, four waves through LDS.  Integer sums: exact in any order; the order is fixed all the same.
 // No atomics, no scratch, no host read.
 #include "common.h"
+#include "sort_key.h"
 
 namespace {
 
@@ -35,12 +36,7 @@ constexpr uint32_t kChunk = MGGCN_ROC_AUC_CHUNK;            // pairs per wave
 constexpr uint32_t kViews = 5;                              // train, val, test, other, all
 constexpr uint32_t kCats = 8;                               // slot << 1 | label
 
-// ---------------------------------------------------------------- keys
-__device__ __forceinline__ uint32_t sortable_key(float logit) {
-    const uint32_t u = __float_as_uint(logit + 0.0f);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-
+// ---------------------------------------------------------------- keys (the map itself: sort_key.h)
 __global__ __launch_bounds__(256) void roc_auc_keys_kernel(const float *__restrict__ logits, size_t ld_logits,
                                                            const int32_t *__restrict__ targets, size_t ld_targets,
                                                            const int32_t *__restrict__ sets, uint32_t n, uint32_t c0, uint32_t nc,

@@ -23,6 +23,10 @@ link_predictor has no parameters: save / load / predict / model_selector of the 
 P and P^T on the device, the four sort arrays and the sort's work space, the row pointer of the negatives' transpose, the row
 sums and G [n x d].  A program that never constructs one launches, allocates and registers what it did before.  Timers
 link-draw, link-sort, link-bounds and link-loss exist once train_step has run.
+
+``head.rank(ctx, X, pos_pairs, neg_pairs=... | neg_tails=...)`` gives the ranking metrics of the leaderboards, MRR and Hits@K,
+from exact integers counted on the device (csrc/link_rank.hip): see the method.  It allocates per call and registers the
+timer link-rank; a program that never calls it runs what it ran.
 """
 from __future__ import annotations
 
@@ -70,6 +74,23 @@ def pair_metrics(s_pos, s_neg) -> tuple:
     loss = (softplus(-s_pos).mean() if s_pos.size else 0.0) + (softplus(s_neg).mean() if s_neg.size else 0.0)
     hits = int((s_pos > 0).sum()) + int((~(s_neg > 0)).sum())
     return float(loss), hits / max(s_pos.size + s_neg.size, 1)
+
+
+def check_ks(ks) -> tuple:
+    if not isinstance(ks, (tuple, list)) or any(not isinstance(k, numbers.Integral) or isinstance(k, bool) or k < 1 for k in ks):
+        raise ValueError(f"ks must be a sequence of positive integers, not {ks!r}")
+    return tuple(int(k) for k in ks)
+
+
+def rank_metrics(greater, equal, ks, shared: bool) -> tuple:
+    """(mrr, {k: hits@k}) from the device's integers, in int64 and float64 on the host.  rank = 1 + greater + equal / 2 (OGB's
+    mean of the optimistic and the pessimistic rank), mrr = mean(1 / rank); per-positive negatives (OGB ``_eval_mrr``):
+    hits@k = mean(rank <= k); a shared list (OGB ``_eval_hits``, positive > k-th largest negative): hits@k =
+    mean(greater + equal < k), 1.0 by itself with fewer than k negatives."""
+    g, e = np.asarray(greater).astype(np.int64).reshape(-1), np.asarray(equal).astype(np.int64).reshape(-1)
+    rank = 1.0 + g.astype(np.float64) + e.astype(np.float64) / 2.0
+    hits = {int(k): float(np.mean(g + e < k) if shared else np.mean(rank <= k)) for k in ks}
+    return float(np.mean(1.0 / rank)), hits
 
 
 class link_predictor:
@@ -199,15 +220,84 @@ class link_predictor:
         return self._score(ctx, X, pairs)
 
     def _score(self, ctx: context, X: dn_matrix, pairs: np.ndarray) -> dn_matrix:
+        out = self._pair_scores(ctx, self.model(ctx, X), pairs)
+        ctx.sync()
+        return out
+
+    def _pair_scores(self, ctx: context, H: dn_matrix, pairs: np.ndarray) -> dn_matrix:
+        """the decoder's scores [m x 1] of a checked pair list on the embeddings H.  Enqueue-only."""
         m = pairs.shape[0]
         out = dn_matrix(m, 1, device=ctx.device)
-        H = self.model(ctx, X)
         if m:
             src = dn_matrix.from_numpy(pairs[:, 0].view(np.int32), device=ctx.device)
             dst = dn_matrix.from_numpy(pairs[:, 1].view(np.int32), device=ctx.device)
             ops.edge_dot(ctx, src.t.view(-1), dst.t.view(-1), m, H, out.t.view(-1))
-        ctx.sync()
         return out
+
+    def _rank_tails(self, ctx: context, H: dn_matrix, src, dst, m: int, tails, K: int, counts) -> None:
+        """the fused per-positive kernel of the decoder.  Enqueue-only."""
+        ops.link_rank_dot(ctx, src, dst, m, tails, K, H, counts)
+
+    def rank(self, ctx: context, X: dn_matrix, pos_pairs, neg_pairs=None, neg_tails=None, ks=(1, 3, 10, 20, 50, 100)) -> dict:
+        """The ranking metrics of the ogbl-* leaderboards -> {"greater": uint32[m], "equal": uint32[m], "mrr", "hits": {k:}}.
+        For every positive i the device counts greater[i] / equal[i], its negatives with a score above / equal to its own
+        (floats compared, -0.0 == +0.0); rank_metrics turns them into mrr and hits on the host.  Exactly one of
+          neg_tails [m x K]      negatives of its own per positive, (pos_pairs[i, 0], neg_tails[i, k]) -- ogbl-citation2's MRR:
+                                 one fused kernel scores, compares and counts, H[u] loaded once per positive, no score stored
+                                 (ops.link_rank_dot / link_rank_mlp / link_rank_mlp_bf16 by the head's decoder);
+          neg_pairs [m_neg x 2]  one list shared by all positives -- Hits@K of ogbl-collab, -ppa, -ddi: score()'s pair kernel
+                                 over both lists, the negatives' scores sorted as keys, two bisections per positive.
+        Either way the integers are those one would count from score() of the same pairs.  A plain forward: no dropout, no
+        sampling, no epoch spent; one synchronisation; timer link-rank.  ValueError naming the argument, before any device work:
+        both or neither neg_*; a wrong shape or dtype; a vertex outside [0, n); no positive; m K or m + m_neg >= 2^31; a ks that
+        is not a sequence of positive integers."""
+        if (neg_pairs is None) == (neg_tails is None):
+            raise ValueError("neg_pairs and neg_tails: exactly one of the two must be given")
+        pos = check_pairs(pos_pairs, self.n, "pos_pairs")
+        m = pos.shape[0]
+        if m == 0:
+            raise ValueError("pos_pairs has no pair: there is nothing to rank")
+        ks = check_ks(ks)
+        if neg_tails is not None:
+            tails = np.asarray(neg_tails)
+            if tails.ndim != 2 or tails.shape[0] != m or tails.dtype.kind not in "iu":
+                raise ValueError(f"neg_tails must be an integer array of {m} x K, got {tails.dtype} of shape {tails.shape}")
+            K = tails.shape[1]
+            if m * K >= 1 << 31:
+                raise ValueError(f"neg_tails: m * K must be below 2^31, got {m * K}")
+            if tails.size and (int(tails.min()) < 0 or int(tails.max()) >= self.n):
+                raise ValueError(f"neg_tails must lie in [0, {self.n}), got {int(tails.min())} .. {int(tails.max())}")
+            tails = np.ascontiguousarray(tails, dtype=np.uint32)
+        else:
+            shape = np.shape(neg_pairs)
+            if len(shape) == 2 and m + shape[0] >= 1 << 31:
+                raise ValueError(f"pos_pairs and neg_pairs: at most 2^31 - 1 pairs together, got {m + shape[0]}")
+            neg = check_pairs(neg_pairs, self.n, "neg_pairs")
+            m_neg = neg.shape[0]
+        torch = _torch()
+        H = self.model(ctx, X)
+        counts = torch.empty(2 * m, dtype=torch.int32, device=ctx.device)
+        ctx.record("link-rank_0", 0)
+        if neg_tails is not None:
+            src = dn_matrix.from_numpy(pos[:, 0].view(np.int32), device=ctx.device)
+            dst = dn_matrix.from_numpy(pos[:, 1].view(np.int32), device=ctx.device)
+            t = dn_matrix.from_numpy(tails.view(np.int32), device=ctx.device)
+            self._rank_tails(ctx, H, src.t.view(-1), dst.t.view(-1), m, t.t.view(-1), K, counts)
+        else:
+            scores = self._pair_scores(ctx, H, np.concatenate([pos, neg]))
+            keys, vals, keys_alt, vals_alt = (torch.empty(m_neg, dtype=torch.int32, device=ctx.device) for _ in range(4))
+            work = torch.empty(ops.radix_sort_work_bytes(1, m_neg) // 8 + 1, dtype=torch.int64, device=ctx.device)
+            zeros = torch.zeros((m_neg, 1), dtype=torch.int32, device=ctx.device)
+            ops.roc_auc_keys(ctx, scores.t[m:], zeros, None, 0, 1, keys, vals)
+            ops.radix_sort_pairs(ctx, 1, m_neg, keys, vals, keys_alt, vals_alt, work)
+            ops.link_rank_sorted(ctx, scores.t.view(-1)[:m], m, keys, m_neg, counts)
+        ctx.record("link-rank_1", 0)
+        ctx.register_timer("link-rank", "link-rank_0", "link-rank_1")
+        ctx.sync()
+        words = counts.cpu().numpy().view(np.uint32).reshape(m, 2)
+        greater, equal = np.ascontiguousarray(words[:, 0]), np.ascontiguousarray(words[:, 1])
+        mrr, hits = rank_metrics(greater, equal, ks, neg_tails is None)
+        return {"greater": greater, "equal": equal, "mrr": mrr, "hits": hits}
 
     def evaluate(self, ctx: context, X: dn_matrix, pos_pairs, neg_pairs) -> dict:
         pos, neg = check_pairs(pos_pairs, self.n, "pos_pairs"), check_pairs(neg_pairs, self.n, "neg_pairs")
@@ -393,14 +483,17 @@ class mlp_link_predictor(link_predictor, metaclass=_decoder_option):
         ctx.sync()
         return self.read()
 
-    def _score(self, ctx: context, X: dn_matrix, pairs: np.ndarray) -> dn_matrix:
+    def _pair_scores(self, ctx: context, H: dn_matrix, pairs: np.ndarray) -> dn_matrix:
         m = pairs.shape[0]
         out = dn_matrix(m, 1, device=ctx.device)
-        H = self.model(ctx, X)
         if m:
             src = dn_matrix.from_numpy(pairs[:, 0].view(np.int32), device=ctx.device)
             dst = dn_matrix.from_numpy(pairs[:, 1].view(np.int32), device=ctx.device)
             _, link_mlp_pairs, H, params = self._decoder(ctx, H)
             link_mlp_pairs(ctx, H, params, pairs=(src.t.view(-1), dst.t.view(-1), m), out=out.t.view(-1))
-        ctx.sync()
         return out
+
+    def _rank_tails(self, ctx: context, H: dn_matrix, src, dst, m: int, tails, K: int, counts) -> None:
+        _, _, H, params = self._decoder(ctx, H)
+        rank = ops.link_rank_mlp if self.decoder_dtype == "f32" else ops.link_rank_mlp_bf16
+        rank(ctx, src, dst, m, tails, K, H, params, counts)

@@ -2041,6 +2041,78 @@ def _link_mlp_pairs(ctx, b16, H, params, pairs, train, positive, weight, neg_wei
         partials.data_ptr() if grads is not None else None))
 
 
+# ---- the ranking metrics of the link head (csrc/link_rank.hip) ------------------------------------------------------------------
+def _link_rank_lists(what: str, src, dst, m, tails, K, counts, H_window) -> tuple:
+    """(m, K) of per-positive lists: src / dst of m, tails of m K 4-byte integers, counts of 2 m, 8-byte aligned, apart from
+    the lists and from H (pointer, bytes)"""
+    m, K = _req_count(m, f"{what}: m"), _req_count(K, f"{what}: K")
+    _req(m < 1 << 31 and K < 1 << 31 and m * max(K, 1) < 1 << 31, f"{what}: m * K must be below 2^31, got {m * max(K, 1)}")
+    _req_u32(src, m, f"{what}: src")
+    _req_u32(dst, m, f"{what}: dst")
+    _req_u32(tails, m * K, f"{what}: tails")
+    _req_u32(counts, 2 * m, f"{what}: counts")
+    _req(counts.data_ptr() % 8 == 0, f"{what}: counts must be 8-byte aligned")
+    for name, p, nbytes in (("H", *H_window), ("src", src.data_ptr(), 4 * m), ("dst", dst.data_ptr(), 4 * m),
+                            ("tails", tails.data_ptr(), 4 * m * K)):
+        _req_apart(what, counts.data_ptr(), 8 * m, "counts", p, nbytes, name)
+    return m, K
+
+
+def link_rank_dot(ctx: context, src, dst, m: int, tails, K: int, H, counts, timer: Optional[str] = None) -> None:
+    """counts[2 i], counts[2 i + 1] = #{k < K: s(src[i], tails[i K + k]) > s_i}, #{... == s_i} with s the dot product of
+    edge_dot and s_i = s(src[i], dst[i]) (mggcn_link_rank_dot_f32): one wave per positive, no score stored, every score with
+    edge_dot's bits.  src / dst (m) and tails (m K): device tensors of 4-byte integers below H's row count (the caller's to
+    guarantee); H as in edge_dot; counts: a contiguous, 8-byte aligned device tensor of 2 m 4-byte integers.  m K < 2^31."""
+    what = "link rank dot"
+    hp, ldh, hn, d = _dense_window(H, True, f"{what}: H")
+    _req_link_width(what, d)
+    m, K = _link_rank_lists(what, src, dst, m, tails, K, counts, (hp, 4 * ((hn - 1) * ldh + d) if hn else 0))
+    _req(hn >= 1 or m == 0, f"{what}: H has no rows")
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_rank_dot_f32(ctx.stream(0), src.data_ptr(), dst.data_ptr(), m,
+                                                                   tails.data_ptr(), K, hp, ldh, hn, d, counts.data_ptr()))
+
+
+def link_rank_mlp(ctx: context, src, dst, m: int, tails, K: int, H, params, counts, timer: Optional[str] = None) -> None:
+    """link_rank_dot with the MLP decoder (mggcn_link_rank_mlp_f32): every score has the bits link_mlp_pairs gives the pair.
+    H and ``params`` as in link_mlp_loss."""
+    _link_rank_mlp(ctx, False, src, dst, m, tails, K, H, params, counts, timer)
+
+
+def link_rank_mlp_bf16(ctx: context, src, dst, m: int, tails, K: int, Hb, params, counts, timer: Optional[str] = None) -> None:
+    """link_rank_mlp on the bf16 matrix cores (mggcn_link_rank_mlp_bf16): every score has the bits link_mlp_pairs_bf16 gives the
+    pair.  Hb and ``params`` as in link_mlp_loss_bf16."""
+    _link_rank_mlp(ctx, True, src, dst, m, tails, K, Hb, params, counts, timer)
+
+
+def _link_rank_mlp(ctx, b16, src, dst, m, tails, K, H, params, counts, timer) -> None:
+    what = "link rank mlp"
+    hp, ldh, hn, d, h_bytes = _link_mlp_H(H, b16, f"{what}: H")
+    ptrs, hd, w_bytes = _req_link_mlp(what, d, params, b16)
+    m, K = _link_rank_lists(what, src, dst, m, tails, K, counts, (hp, h_bytes))
+    _req(hn >= 1 or m == 0, f"{what}: H has no rows")
+    _req_apart(what, counts.data_ptr(), 8 * m, "counts", ptrs[0], w_bytes, "W1")
+    entry = ctx.lib.mggcn_link_rank_mlp_bf16 if b16 else ctx.lib.mggcn_link_rank_mlp_f32
+    _gat_timed(ctx, timer, lambda: entry(ctx.stream(0), src.data_ptr(), dst.data_ptr(), m, tails.data_ptr(), K, hp, ldh, hn, d,
+                                         *ptrs, hd, counts.data_ptr()))
+
+
+def link_rank_sorted(ctx: context, pos_scores, m: int, sorted_keys, m_neg: int, counts, timer: Optional[str] = None) -> None:
+    """counts[2 i], counts[2 i + 1] = #{sorted_keys > key_i}, #{== key_i} with key_i the roc_auc_keys key of pos_scores[i]
+    (mggcn_link_rank_sorted_u32): two bisections per positive over the m_neg keys SORTED ascending on all 32 bits.  pos_scores:
+    a contiguous fp32 device tensor of m; sorted_keys: 4-byte integers; counts as in link_rank_dot."""
+    what = "link rank sorted"
+    m, m_neg = _req_count(m, f"{what}: m"), _req_count(m_neg, f"{what}: m_neg")
+    _req(m < 1 << 31 and m_neg < 1 << 31, f"{what}: m and m_neg must be below 2^31")
+    _req_f32(pos_scores, m, f"{what}: pos_scores")
+    _req_u32(sorted_keys, m_neg, f"{what}: sorted_keys")
+    _req_u32(counts, 2 * m, f"{what}: counts")
+    _req(counts.data_ptr() % 8 == 0, f"{what}: counts must be 8-byte aligned")
+    for name, p, nbytes in (("pos_scores", pos_scores.data_ptr(), 4 * m), ("sorted_keys", sorted_keys.data_ptr(), 4 * m_neg)):
+        _req_apart(what, counts.data_ptr(), 8 * m, "counts", p, nbytes, name)
+    _gat_timed(ctx, timer, lambda: ctx.lib.mggcn_link_rank_sorted_u32(ctx.stream(0), pos_scores.data_ptr(), m,
+                                                                      sorted_keys.data_ptr(), m_neg, counts.data_ptr()))
+
+
 def abssum(ctx: context, A: dn_matrix, result_device) -> None:
     """cublasSasum (src/cuda_utils.hpp:362-371).  ``result_device``: 1-element float32
     device tensor; enqueue-only (the reference's call blocks the host)."""
