@@ -15,14 +15,22 @@ constexpr uint32_t kLinkDomain = 0xE0000000u;        // counter word 2 of the li
 
 // Negative (p, r) of the link head: the tail of the entry at position p, r < R.  Word r & 3 of
 // Philox4x32-10((p, r >> 2, kLinkDomain, epoch), seed) mapped onto [0, n) by the high half of a 32 x 32 product.
-// link_negatives keeps the four words of one call: next(r) for r = 0, 1, ... in order draws again at every fourth.
+// link_negative is one of them on its own; link_negatives keeps the four words of one call: next(r) for r = 0, 1, ... in
+// order draws again at every fourth.  Both pick their word where the four live: a shared function that took the four, by
+// reference or by value, moved the register allocation of every MLP walk kernel (link_mlp*.hip), which has none to spare.
+__device__ __forceinline__ uint32_t link_tail(uint32_t word, uint32_t n) { return (uint32_t)(((uint64_t)word * n) >> 32); }
+__device__ __forceinline__ uint32_t link_negative(uint32_t p, uint32_t r, uint32_t n, uint32_t epoch, uint32_t k0, uint32_t k1) {
+    const philox4 wd = philox4x32_10(p, r >> 2, kLinkDomain, epoch, k0, k1);
+    const uint32_t q = r & 3;
+    return link_tail(q == 0 ? wd.w[0] : q == 1 ? wd.w[1] : q == 2 ? wd.w[2] : wd.w[3], n);
+}
 struct link_negatives {
     uint32_t p, n, k0, k1, epoch;
     philox4 w;
     __device__ __forceinline__ uint32_t next(uint32_t r) {
         if ((r & 3) == 0) w = philox4x32_10(p, r >> 2, kLinkDomain, epoch, k0, k1);
-        const uint32_t q = r & 3, word = q == 0 ? w.w[0] : q == 1 ? w.w[1] : q == 2 ? w.w[2] : w.w[3];
-        return (uint32_t)(((uint64_t)word * n) >> 32);
+        const uint32_t q = r & 3;
+        return link_tail(q == 0 ? w.w[0] : q == 1 ? w.w[1] : q == 2 ? w.w[2] : w.w[3], n);
     }
 };
 

@@ -261,10 +261,7 @@ __global__ __launch_bounds__(256) void link_mlp_pairs_kernel(const uint32_t *__r
                         v = indices[p];
                         my_pos = true;
                     } else {
-                        const uint32_t r = slot - 1;
-                        const philox4 wd = philox4x32_10(p, r >> 2, kLinkDomain, epoch, k0, k1);
-                        const uint32_t qq = r & 3, word = qq == 0 ? wd.w[0] : qq == 1 ? wd.w[1] : qq == 2 ? wd.w[2] : wd.w[3];
-                        v = (uint32_t)(((uint64_t)word * n_draw) >> 32);
+                        v = link_negative(p, slot - 1, n_draw, epoch, k0, k1);
                         my_pos = false;
                         my_w = neg_weight;
                     }
@@ -296,7 +293,7 @@ __global__ __launch_bounds__(256) void link_mlp_pairs_kernel(const uint32_t *__r
 #pragma unroll
             for (int r = 0; r < 16; r++) {
                 a[r] = gat_lrelu(z[r], kLinkMlpSlope);
-                const float p = half_sum(w2j * a[r]);
+                const float p = half_dot(w2j, a[r]);
                 if (l31 == 0) sps[wave][c_row(r, h)] = p;
             }
         }
@@ -360,23 +357,8 @@ MGGCN_API void mggcn_link_mlp_loss_f32(mggcn_stream_t stream, uint32_t n_rows, u
                                        const float *W1, const float *b1, const float *w2, const float *b2, uint32_t hd,
                                        int positive, float weight, uint32_t R, float neg_weight, uint64_t seed, uint32_t epoch,
                                        float beta, float *G, size_t ldg, float *row_loss, uint32_t *row_correct) {
-    require_mlp_shape(d, hd);
-    MGGCN_REQUIRE(ldh >= d && ldg >= d, "link mlp loss: leading dimension < d");
-    MGGCN_REQUIRE(n_rows < (1u << 31) && n_cols < (1u << 31), "link mlp loss: n < 2^31");
-    MGGCN_REQUIRE(nnz < ((size_t)1 << 31) && nnz * (R ? R : 1) < ((size_t)1 << 31), "link mlp loss: nnz * neg_ratio must be below 2^31");
-    MGGCN_REQUIRE((row_loss == nullptr) == (row_correct == nullptr), "link mlp loss: row_loss and row_correct come together");
-    if (!n_rows) return;
-    MGGCN_REQUIRE(indptr != nullptr && H != nullptr && G != nullptr, "link mlp loss: null operand");
-    MGGCN_REQUIRE(W1 != nullptr && b1 != nullptr && w2 != nullptr && b2 != nullptr, "link mlp loss: null parameter");
-    MGGCN_REQUIRE(nnz == 0 || (indices != nullptr && n_cols != 0), "link mlp loss: null operand");
-    const size_t h_rows = n_rows > n_cols ? n_rows : n_cols;    // H is indexed by the row and by the entry
-    const size_t g_bytes = matrix_bytes(n_rows, ldg, d), h_bytes = matrix_bytes(h_rows, ldh, d);
-    MGGCN_REQUIRE(!overlap(G, g_bytes, H, h_bytes) && !overlap(G, g_bytes, W1, (size_t)d * hd * 4), "link mlp loss: G must not overlap an input");
-    if (row_loss != nullptr)
-        MGGCN_REQUIRE(!overlap(row_loss, (size_t)n_rows * 8, row_correct, (size_t)n_rows * 4) &&
-                          !overlap(row_loss, (size_t)n_rows * 8, G, g_bytes) && !overlap(row_correct, (size_t)n_rows * 4, G, g_bytes) &&
-                          !overlap(row_loss, (size_t)n_rows * 8, H, h_bytes) && !overlap(row_correct, (size_t)n_rows * 4, H, h_bytes),
-                      "link mlp loss: the outputs must not overlap each other or H");
+    if (!require_walk({H, ldh, 4, W1}, n_rows, n_cols, indptr, indices, nnz, d, hd, b1, w2, b2, R, G, ldg, row_loss, row_correct))
+        return;
     const bool vec = rows16(H, ldh) && rows16(G, ldg);
     const unsigned grid = (unsigned)std::min<size_t>(((size_t)n_rows + 3) / 4, kLinkMlpWalkGrid);
     mlp_dispatch(d, hd, [&](auto db, auto hb) {
@@ -388,7 +370,7 @@ MGGCN_API void mggcn_link_mlp_loss_f32(mggcn_stream_t stream, uint32_t n_rows, u
 }
 
 MGGCN_API size_t mggcn_link_mlp_partial_floats(uint32_t d, uint32_t hd) {
-    return (size_t)kLinkMlpPairsGrid * ((size_t)d * hd + 2 * (size_t)hd + 1);
+    return (size_t)kLinkMlpPairsGrid * link_mlp_grad_floats(d, hd);
 }
 
 MGGCN_API void mggcn_link_mlp_pairs_f32(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m,
@@ -397,30 +379,11 @@ MGGCN_API void mggcn_link_mlp_pairs_f32(mggcn_stream_t stream, const uint32_t *s
                                         const float *H, size_t ldh, size_t n_rows, uint32_t d, const float *W1, const float *b1,
                                         const float *w2, const float *b2, uint32_t hd, float *out, float *grads,
                                         float *partials) {
-    require_mlp_shape(d, hd);
-    MGGCN_REQUIRE(ldh >= d, "link mlp pairs: leading dimension < d");
-    MGGCN_REQUIRE((src == nullptr) == (dst == nullptr), "link mlp pairs: src and dst come together");
-    MGGCN_REQUIRE((grads == nullptr) == (partials == nullptr), "link mlp pairs: the gradients need their partials");
-    MGGCN_REQUIRE(out != nullptr || grads != nullptr, "link mlp pairs: nothing to write");
-    if (src == nullptr) {                           // the training list of P
-        MGGCN_REQUIRE(M < ((size_t)1 << 31) && M * (R ? R : 1) < ((size_t)1 << 31), "link mlp pairs: M * neg_ratio must be below 2^31");
-        MGGCN_REQUIRE(R == 0 || (n_draw >= 1 && n_draw < (1u << 31)), "link mlp pairs: 1 <= n < 2^31");
-        m = M * (1 + (size_t)R);
-        MGGCN_REQUIRE(m == 0 || (head != nullptr && indices != nullptr), "link mlp pairs: null operand");
-    }
-    MGGCN_REQUIRE(m < ((size_t)1 << 32), "link mlp pairs: the list must be shorter than 2^32");
-    const size_t width = (size_t)d * hd + 2 * (size_t)hd + 1;
+    m = require_pairs({H, ldh, 4, W1}, src, dst, m, head, indices, M, R, n_draw, n_rows, d, hd, b1, w2, b2, out, grads, partials,
+                      mggcn_link_mlp_partial_floats(d, hd));
     const hipStream_t st = as_stream(stream);
     unsigned grid = 0;
     if (m) {
-        MGGCN_REQUIRE(H != nullptr && n_rows != 0, "link mlp pairs: null operand");
-        MGGCN_REQUIRE(W1 != nullptr && b1 != nullptr && w2 != nullptr && b2 != nullptr, "link mlp pairs: null parameter");
-        const size_t h_bytes = matrix_bytes(n_rows, ldh, d);
-        MGGCN_REQUIRE(out == nullptr || !overlap(out, m * 4, H, h_bytes), "link mlp pairs: out must not overlap H");
-        MGGCN_REQUIRE(grads == nullptr || (!overlap(grads, width * 4, H, h_bytes) && !overlap(grads, width * 4, W1, (size_t)d * hd * 4) &&
-                                           !overlap(partials, mggcn_link_mlp_partial_floats(d, hd) * 4, H, h_bytes) &&
-                                           !overlap(partials, mggcn_link_mlp_partial_floats(d, hd) * 4, grads, width * 4)),
-                      "link mlp pairs: the gradients must not overlap an input or their partials");
         grid = (unsigned)std::min<size_t>((m + 31) / 32, kLinkMlpPairsGrid);
         mlp_dispatch(d, hd, [&](auto db, auto hb) {
             hipLaunchKernelGGL((link_mlp_pairs_kernel<db.value, hb.value>), dim3(grid), dim3(256), 0, st, src, dst, m, head,
@@ -429,9 +392,5 @@ MGGCN_API void mggcn_link_mlp_pairs_f32(mggcn_stream_t stream, const uint32_t *s
             MGGCN_CHECK_LAUNCH();
         });
     }
-    if (grads != nullptr) {                         // the partials in workgroup order; an empty list stores zeros
-        hipLaunchKernelGGL(colsum_final_kernel, dim3((unsigned)((width + 63) / 64)), dim3(256), 0, st, partials, grid,
-                           (uint32_t)width, grads, grads, (uint32_t)width);
-        MGGCN_CHECK_LAUNCH();
-    }
+    if (grads != nullptr) pairs_final(st, partials, grid, d, hd, grads);
 }

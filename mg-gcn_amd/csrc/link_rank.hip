@@ -26,13 +26,14 @@
 //         them with lane ^ 32: h = 0 ends with the even columns, h = 1 with the odd ones.
 //         bf16: the walk's own slots (slot e of half h in step s is column 16 s + 8 (e / 4) + 4 h + e % 4) are the pair
 //         kernel's; nothing is traded.
-//   s     the pair kernel adds w2_j a_j over the 32 hidden units of a block by four DPP rotations inside each row of 16 lanes
-//         and one exchange between the rows, stores what lane 0 holds, then adds the blocks in order, then b2.  As compiled,
-//         its first step is contracted: lane l holds fma(w2_l, a_l, rnd(w2_(l^8) a_(l^8))), so the lanes of a row no longer
-//         hold the same bits and lane 0's tree is the sum over the units 0, 12, 14, 10, 15, 11, 13, 9 of those terms, in that
-//         shape.  Here row i of the A operand holds hidden unit pi(i) = i with bits 2 and 4 swapped (W1, b1 and w2 are
-//         permuted as they are staged), so a lane half holds 16 consecutive units of a block in its own registers: that tree
-//         is spelled out in lane, with contraction off, and the two rows meet in one exchange with lane ^ 32.
+//   s     the pair kernel adds w2_j a_j over the 32 hidden units of a block by half_dot (link_mlp_internal.h): four DPP
+//         rotations inside each row of 16 lanes and one exchange between the rows; it stores what lane 0 holds, then adds the
+//         blocks in order, then b2.  half_dot's first step is written as an fma: lane l holds
+//         fma(w2_l, a_l, rnd(w2_(l^8) a_(l^8))), so the lanes of a row do not hold the same bits and lane 0's tree is the sum
+//         over the units 0, 12, 14, 10, 15, 11, 13, 9 of those terms, in that shape.  Here row i of the A operand holds hidden
+//         unit pi(i) = i with bits 2 and 4 swapped (W1, b1 and w2 are permuted as they are staged), so a lane half holds 16
+//         consecutive units of a block in its own registers: that tree is spelled out in lane, with contraction off as in
+//         half_dot, and the two rows meet in one exchange with lane ^ 32.
 //
 // link_rank_sorted_kernel -- the shared list.  The negatives' scores, as sort_key.h keys sorted ascending by
 // mggcn_radix_sort_pairs_u32, and per positive one lower-bound and one upper-bound bisection on its own key:
@@ -116,7 +117,7 @@ __device__ __forceinline__ float rank_score(const f32x16 (&z)[HB], const float *
             q[l] = w[l] * a[l];
         }
         // lane 0 of a 16-lane row after row_ror 8, 4, 2, 1 (lane l takes lane l - n): the units 0, 12, 14, 10, 15, 11, 13, 9,
-        // each entering as fma(w2 a, its partner's rounded product) -- the pair kernel's first step as it is compiled
+        // each entering as fma(w2 a, its partner's rounded product) -- half_dot's first step
         const auto v = [&](int l) { return fmaf(w[l], a[l], q[l ^ 8]); };
         float p = ((v(0) + v(12)) + (v(14) + v(10))) + ((v(15) + v(11)) + (v(13) + v(9)));
         p = p + __shfl_xor(p, 32);                              // lane 16 of the pair kernel: my other half
@@ -214,15 +215,6 @@ __global__ __launch_bounds__(256) void link_rank_mlp_kernel(uint32_t m, const ui
         if (lane == 0) *reinterpret_cast<uint2 *>(counts + 2 * row) = make_uint2(gt, eq);
     }
 }
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int kPad = 8;                                  // elements behind every row of the W1 image (link_mlp_b16.hip)
-
-__device__ __forceinline__ uint32_t bf16_pair(float lo, float hi) {      // round to nearest even: v_cvt_pk_bf16_f32
-    return (uint32_t)__builtin_bit_cast(uint16_t, (__bf16)lo) | ((uint32_t)__builtin_bit_cast(uint16_t, (__bf16)hi) << 16);
-}
-__device__ __forceinline__ float widen_lo(uint32_t p) { return __uint_as_float(p << 16); }
-__device__ __forceinline__ float widen_hi(uint32_t p) { return __uint_as_float(p & 0xFFFF0000u); }
 
 template <int DB, int HB>
 __global__ __launch_bounds__(256) void link_rank_mlp_b16_kernel(uint32_t m, const uint32_t *__restrict__ src,
@@ -346,6 +338,21 @@ void require_rank_lists(const char *what, size_t m, uint32_t K, const uint32_t *
                   "link rank: counts must not overlap a list");
 }
 
+// the MLP entries; false: there is nothing to launch
+bool require_rank_mlp(const mlp_inputs &in, const uint32_t *src, const uint32_t *dst, size_t m, const uint32_t *tails, uint32_t K,
+                      size_t n_rows, uint32_t d, uint32_t hd, const float *b1, const float *w2, const float *b2,
+                      const uint32_t *counts) {
+    require_mlp_shape(d, hd);
+    MGGCN_REQUIRE(in.ldh >= d, "link rank: leading dimension < d");
+    if (!m) return false;
+    require_rank_lists("link rank mlp: null operand, or m K >= 2^31", m, K, src, dst, tails, counts, n_rows);
+    MGGCN_REQUIRE(in.H != nullptr && in.W != nullptr && b1 != nullptr && w2 != nullptr && b2 != nullptr, "link rank mlp: null operand");
+    require_images(in);
+    MGGCN_REQUIRE(!overlap(counts, m * 8, in.H, in.h_bytes(n_rows, d)) && !overlap(counts, m * 8, in.W, in.w_bytes(d, hd)),
+                  in.image() ? "link rank: counts must not overlap Hb or the image" : "link rank: counts must not overlap H or W1");
+    return true;
+}
+
 }  // namespace
 
 MGGCN_API void mggcn_link_rank_dot_f32(mggcn_stream_t stream, const uint32_t *src, const uint32_t *dst, size_t m,
@@ -369,13 +376,7 @@ MGGCN_API void mggcn_link_rank_mlp_f32(mggcn_stream_t stream, const uint32_t *sr
                                        const uint32_t *tails, uint32_t K, const float *H, size_t ldh, size_t n_rows, uint32_t d,
                                        const float *W1, const float *b1, const float *w2, const float *b2, uint32_t hd,
                                        uint32_t *counts) {
-    require_mlp_shape(d, hd);
-    MGGCN_REQUIRE(ldh >= d, "link rank: leading dimension < d");
-    if (!m) return;
-    require_rank_lists("link rank mlp: null operand, or m K >= 2^31", m, K, src, dst, tails, counts, n_rows);
-    MGGCN_REQUIRE(H != nullptr && W1 != nullptr && b1 != nullptr && w2 != nullptr && b2 != nullptr, "link rank mlp: null operand");
-    MGGCN_REQUIRE(!overlap(counts, m * 8, H, matrix_bytes(n_rows, ldh, d)) && !overlap(counts, m * 8, W1, (size_t)d * hd * 4),
-                  "link rank: counts must not overlap H or W1");
+    if (!require_rank_mlp({H, ldh, 4, W1}, src, dst, m, tails, K, n_rows, d, hd, b1, w2, b2, counts)) return;
     const bool vec = rows16(H, ldh);
     const unsigned grid = (unsigned)std::min<size_t>((m + 3) / 4, kLinkMlpWalkGrid);
     mlp_dispatch(d, hd, [&](auto db, auto hb) {
@@ -389,16 +390,7 @@ MGGCN_API void mggcn_link_rank_mlp_bf16(mggcn_stream_t stream, const uint32_t *s
                                         const uint32_t *tails, uint32_t K, const uint16_t *Hb, size_t ldhb, size_t n_rows,
                                         uint32_t d, const uint16_t *image, const float *b1, const float *w2, const float *b2,
                                         uint32_t hd, uint32_t *counts) {
-    require_mlp_shape(d, hd);
-    MGGCN_REQUIRE(ldhb >= d, "link rank: leading dimension < d");
-    if (!m) return;
-    require_rank_lists("link rank mlp: null operand, or m K >= 2^31", m, K, src, dst, tails, counts, n_rows);
-    MGGCN_REQUIRE(Hb != nullptr && image != nullptr && b1 != nullptr && w2 != nullptr && b2 != nullptr, "link rank mlp: null operand");
-    MGGCN_REQUIRE(rows16(Hb, ldhb), "link mlp bf16: Hb needs an 8-byte aligned base and a leading dimension that is a multiple of 4");
-    MGGCN_REQUIRE((reinterpret_cast<uintptr_t>(image) & 15u) == 0, "link mlp bf16: the W1 image must be 16-byte aligned");
-    MGGCN_REQUIRE(!overlap(counts, m * 8, Hb, matrix_bytes(n_rows, ldhb, d, 2)) &&
-                      !overlap(counts, m * 8, image, ((size_t)hd * (d + kPad) + (size_t)d * (hd + kPad)) * 2),
-                  "link rank: counts must not overlap Hb or the image");
+    if (!require_rank_mlp({Hb, ldhb, 2, image}, src, dst, m, tails, K, n_rows, d, hd, b1, w2, b2, counts)) return;
     const unsigned grid = (unsigned)std::min<size_t>((m + 3) / 4, kLinkMlpWalkGrid);
     mlp_dispatch(d, hd, [&](auto db, auto hb) {
         hipLaunchKernelGGL((link_rank_mlp_b16_kernel<db.value, hb.value>), dim3(grid), dim3(256), 0, as_stream(stream),
