@@ -252,6 +252,29 @@ double round_excess(const SweepHost &P) {
     return sum_mean > 0.0 ? sum_max / sum_mean - 1.0 : 0.0;
 }
 
+bool rows_have_one_value(uint32_t n_rows, const uint32_t *indptr, const float *values) {
+    if (!n_rows || !values) return false;
+    const unsigned T = row_pass_threads(n_rows, indptr);
+    std::vector<unsigned char> bad(T, 0);
+    rows_parallel(n_rows, indptr, T, [&](unsigned t, uint32_t r0, uint32_t r1) {
+        unsigned char b = 0;
+        for (uint32_t r = r0; r < r1; r++) {
+            if (indptr[r] >= indptr[r + 1]) continue;
+            uint32_t first;
+            std::memcpy(&first, &values[indptr[r]], 4);
+            b |= (unsigned char)!std::isfinite(values[indptr[r]]);
+            for (uint32_t e = indptr[r] + 1; e < indptr[r + 1]; e++) {
+                uint32_t w;
+                std::memcpy(&w, &values[e], 4);
+                b |= (unsigned char)(w != first);
+            }
+        }
+        bad[t] = b;
+    });
+    for (unsigned char b : bad) if (b) return false;
+    return true;
+}
+
 bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, const uint32_t *indices, const float *values,
                       uint32_t max_d, bool force, uint32_t d_hint, bool hot_columns, uint32_t num_cu, SweepHost &P) {
     if (!n_rows || !indices || !values) return false;
@@ -562,8 +585,14 @@ bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, 
         for (size_t r = 0; r < bins[t].size(); r++) task_rows[(size_t)t * kRW + r] = vrows[bins[t][r]].dst;
     }
     require(off < (1ull << 32), "sweep plan: entry stream exceeds 32-bit offsets");
+    // the row-value stream (plan_host.h): same tasks, order and padded lengths, 4-byte entries + one value per task row
+    const bool row_values = env_u32("MGGCN_SPMM_ROW_VALUES", 1u) != 0 &&
+                            2ull * n_cols <= (narrow ? (1ull << 24) : (uint64_t)kColMask + 1u) &&
+                            rows_have_one_value(n_rows, indptr, values);
     std::vector<Entry> &entries = P.entries;
     entries.assign(off, Entry{0u, 0u});
+    P.entries32.assign(row_values ? off : 0, 0u);
+    P.task_vals.assign(row_values ? (size_t)T * kRW : 0, 0.f);
     run_parallel([&](unsigned tid) {
         std::vector<uint32_t> cnt(n_buckets), start(n_buckets + 1), cur(n_buckets);
         for (uint32_t t = tid; t < T; t += NT) {
@@ -572,6 +601,7 @@ bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, 
             for (size_t k = 0; k < n_buckets; k++) start[k + 1] = start[k] + (cnt[k] + G - 1) / G * G;
             std::copy(start.begin(), start.begin() + n_buckets, cur.begin());
             Entry *out = entries.data() + tasks[t].beg;
+            uint32_t *words = row_values ? P.entries32.data() + tasks[t].beg : nullptr;
             const auto &bin = bins[t];
             const uint32_t base = task_col_base(t);
             for (size_t r = 0; r < bin.size(); r++) {
@@ -592,16 +622,26 @@ bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, 
                     for (uint32_t q = s0; q < s1; q += 2)                            // pair: lower column first
                         if ((out[q].x & kColMask) > (out[q + 1].x & kColMask)) std::swap(out[q], out[q + 1]);
                 out[s0].x |= kRunFlag;                                               // first entry of the run
+                if (row_values)                                  // padding (still behind the run's real entries) gathers zeros
+                    for (uint32_t q = s0; q < s1; q++) words[q] = out[q].x + (q < s0 + cnt[k] ? 0u : n_cols);
             }
             // tail padding up to the 8-entry batch: zero-valued copies of the last entry, no run flag
             const uint32_t real = (uint32_t)plen[t], padded = tasks[t].end - tasks[t].beg;
             for (uint32_t k = real; k < padded; k++) out[k] = Entry{real ? out[real - 1].x & ~kRunFlag : 0u, 0u};
+            if (!row_values) continue;
+            // ... which the row-value stream makes a run of its own, on the last real column: the kernels drop its sum
+            for (uint32_t k = real; k < padded; k++) words[k] = out[k].x | (k == real ? kRunFlag : 0u);
+            tasks[t].pad = padded - real;
+            for (size_t r = 0; r < bin.size(); r++) {
+                const VRow &v = vrows[bin[r]];
+                if (v.beg < v.end) P.task_vals[(size_t)t * kRW + r] = vv[v.beg];
+            }
         }
     });
 
     P.n_rows = n_rows; P.n_cols = n_cols; P.max_d = max_d;
     P.n_tasks = T; P.round_tasks = round_tasks; P.run_pad = G; P.lpe = lpe;
-    P.n_slots = n_slots;
+    P.n_slots = n_slots; P.row_values = row_values;
     P.panel_rows = panel_rows; P.n_entries = off; P.num_cu = num_cu;
     P.round_excess = round_excess(P);
     {   // priority rotation (float4 kernels; see rotate_priority): period 2^8 entries / every chunk of the narrow stream

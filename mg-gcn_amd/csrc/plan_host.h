@@ -58,7 +58,7 @@ constexpr uint32_t kNumCuPos = 16, kNumCuMask = 0xFFFu;
 struct SweepTask {
     uint32_t beg, end;   // entry range
     uint32_t n_rows;     // rows in use (<= kRW)
-    uint32_t pad;
+    uint32_t pad;        // row-value stream: entries of the tail run at the end of the range (below); 0 in the generic stream
 };
 
 struct SweepSplitRow {
@@ -88,8 +88,29 @@ struct SweepHost {
     // share a launch are as close in length as the plan allows.  With the knob at 0, and always in the experimental XCD
     // column layout (its task index encodes the slice), the table stays in LPT order.
     std::vector<SweepTask> tasks;
-    std::vector<Entry> entries;
+    std::vector<Entry> entries;                // generic stream (built in either case; a row-value plan does not upload it)
     std::vector<uint32_t> task_rows;           // n_tasks x kRW: output row or kSlotFlag | slot
+    // Row-value stream (MGGCN_SPMM_ROW_VALUES, default 1 = where the matrix allows it).  When every stored value of a row
+    // has the same bit pattern, for all rows of this plan (any unweighted graph's D^-1 A; split rows: every slice carries
+    // its row's value), the stream drops the value word: entries32 holds the packed words {run | row | column} of the
+    // generic stream in the same order and the same padded lengths, task_vals the value of each task row (0 for an empty
+    // or unused row).  The kernels compute fmaf(v, b, acc) with v = the run's row value: the same operands in the same
+    // order as the generic stream.  Padding, which the generic stream does with zero-valued copies:
+    //   * run padding: column = n_cols + the column of the run's last entry.  It sorts last in its pair, and the row
+    //     gathers put it where the buffer descriptor's bounds check sees it (the lane's own offset: the narrow kernel's
+    //     whole offset, the pair kernel's upper-half offset -- the pair's lower entry is always a real one at run_pad 2),
+    //     so the lane gets zeros without touching memory and adds v * 0.  Needs 2 n_cols <= 2^27 (2^24 in the narrow
+    //     form, whose offsets are 24-bit products) and, at the call, (n_cols + 1) x row pitch <= 2^32 (narrow form: 2 n_cols x
+    //     pitch, the whole product is the lane's).  With B finite the sum differs from the generic stream's at most in the
+    //     sign of an exact zero (v * 0 against 0 * b).
+    //   * tail padding up to the batch size: ONE run of its own at the end of the task (run flag set, columns = the last
+    //     entry's, so the gathers are real and in range); SweepTask::pad counts its entries and the kernels drop its sum.
+    // Everything else keeps the generic stream bit for bit: other matrices, non-finite values, the knob at 0, and any
+    // call the row-value kernels do not serve (the one-row-per-load kernels, a narrow plan at a wide width), for
+    // which the device expands this stream back into the generic one once (spmm_sweep.hip).
+    bool row_values = false;
+    std::vector<uint32_t> entries32;           // row_values: n_entries packed words
+    std::vector<float> task_vals;              // row_values: n_tasks x kRW
     std::vector<SweepSplitRow> split_rows;
 };
 
@@ -102,6 +123,8 @@ bool sweep_build_host(uint32_t n_rows, uint32_t n_cols, const uint32_t *indptr, 
 // what the rounds of a plan lose to their longest task: sum_rounds max(end - beg) / sum_rounds mean(end - beg) - 1 over
 // chunks of round_tasks tasks (0 = every launch ends together)
 double round_excess(const SweepHost &plan);
+// every row's stored values share one finite bit pattern (threaded, read-only)
+bool rows_have_one_value(uint32_t n_rows, const uint32_t *indptr, const float *values);
 
 // ---- passes of mggcn_spmm_plan_create_for over the whole matrix ----------------------------------
 // every column index < n_cols?  (one threaded read-only pass on behalf of the calling thread, which reports)

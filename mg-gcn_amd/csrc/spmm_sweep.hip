@@ -31,6 +31,10 @@
 //                                 is a power of two (d = 128 contiguous): four instructions fewer per pair
 //   spmm_sweep_quad_lds_kernel<L> d <= 64 (plan built with a width hint): 64/L rows per load,
 //                                 entries staged through LDS
+//   spmm_sweep_pair_rowv_kernel<FAST>, spmm_sweep_quad_lds_rowv_kernel<L>
+//                                 the same two bodies on the row-value stream (plan_host.h: 4-byte entries, one value per
+//                                 task row) of a matrix whose rows each hold one value; B in fp32 or bf16
+//   sweep_expand_kernel           row-value stream -> generic stream, once, for the calls those two do not serve
 //   spmm_sweep_kernel<1|2>        every other width / alignment: one row per load
 //   sweep_repack_kernel           B -> 64-byte-multiple pitch for the narrow form
 //   sweep_combine_kernel          partial rows of heavy (sliced) rows, fixed order
@@ -171,6 +175,42 @@ __device__ __forceinline__ EntryBatch load_batch(const uint2 *__restrict__ entri
     EntryBatch r;
     r.q[0] = p[0]; r.q[1] = p[1]; r.q[2] = p[2]; r.q[3] = p[3];
     return r;
+}
+
+// Row-value stream (plan_host.h: SweepHost::row_values): a batch is the 8 packed words alone, one s_load_dwordx8; the
+// value is the run's row value, fetched once per run from the task's value table.
+struct EntryBatch32 {
+    uint4 q[2];
+    __device__ __forceinline__ uint32_t pk(int u) const {
+        const uint4 &x = q[u >> 2];
+        return (u & 3) == 0 ? x.x : (u & 3) == 1 ? x.y : (u & 3) == 2 ? x.z : x.w;
+    }
+};
+
+__device__ __forceinline__ EntryBatch32 load_batch(const uint32_t *__restrict__ entries, uint32_t e) {
+    const uint4 *p = reinterpret_cast<const uint4 *>(entries + e);   // wave-uniform address
+    EntryBatch32 r;
+    r.q[0] = p[0]; r.q[1] = p[1];
+    return r;
+}
+
+// The task's kRW row values, lane r = row r.  They come through SCALAR loads and sixteen selects, not a vector load: the
+// v_readlane at a run boundary then depends on no vmcnt, so no wait lands between the gathers and their FMAs.
+__device__ __forceinline__ float load_row_values(const float *__restrict__ vals /* wave-uniform */) {
+    const int lane = threadIdx.x & 63;
+    const uint4 *p = reinterpret_cast<const uint4 *>(vals);          // 64-byte aligned: one s_load_dwordx16
+    const uint4 q[4] = {p[0], p[1], p[2], p[3]};
+    uint32_t w = 0u;
+#pragma unroll
+    for (int r = 0; r < kRW; r++) {
+        const uint4 &x = q[r >> 2];
+        const uint32_t s = (r & 3) == 0 ? x.x : (r & 3) == 1 ? x.y : (r & 3) == 2 ? x.z : x.w;
+        w = lane == r ? s : w;
+    }
+    return __builtin_bit_cast(float, w);
+}
+__device__ __forceinline__ float row_value(float lanes, uint32_t row /* wave-uniform */) {
+    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(uint32_t, lanes), row));
 }
 
 // The wave's RW = 16 accumulator rows live in REGISTERS: one 16-wide vector register
@@ -377,6 +417,13 @@ __device__ __forceinline__ void sweep_body(
         const uint32_t *__restrict__ task_rows, const TB *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, \
         float *__restrict__ C, size_t ldc, float *__restrict__ partial, uint32_t d, float alpha, float beta,   \
         uint32_t flags, float slope
+// the row-value stream's kernels: 4-byte entries and the tasks' value table
+#define MGGCN_ROWV_PARAMS(TB)                                                                                   \
+    const SweepTask *__restrict__ tasks, uint32_t task0, uint32_t n_launch, const uint32_t *__restrict__ entries,   \
+        const float *__restrict__ task_vals, const uint32_t *__restrict__ task_rows, const TB *__restrict__ B,       \
+        uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc, float *__restrict__ partial,         \
+        uint32_t d, float alpha, float beta, uint32_t flags, float slope
+#define MGGCN_SWEEP_TAIL_ARGS task_rows, B, b_bytes, row_bytes, C, ldc, partial, d, alpha, beta, flags, slope
 #define MGGCN_SWEEP_ARGS tasks, task0, n_launch, entries, task_rows, B, b_bytes, row_bytes, C, ldc, partial, d, alpha, beta, flags, slope
 
 template <int VEC>
@@ -409,10 +456,14 @@ __global__ __launch_bounds__(64 * kWavesPerBlock) void spmm_sweep_b16_kernel(MGG
 // bf16 (spmm_sweep_pair_b16_kernel): the same lanes, columns, pairs and sums; a lane fetches its four columns with a
 // buffer_load_dwordx2, so one instruction gathers two 256-byte rows (d = 128).  FAST there: pitch a power of two >= 256
 // bytes (>= 128 elements, as for fp32), and the same argument holds (the pitch is still a multiple of 32).
-template <bool FAST, typename TB>
+// ROWV (entries = the 4-byte row-value stream, task_vals = its value table): the batch is half the scalar bytes, the four
+// FMAs of a pair take the run's value as a scalar operand -- no per-pair select of "my half's value" -- and a padding
+// entry, always the upper half's at run_pad 2, carries a column past B: its lanes' offset fails the descriptor's bounds
+// check and they gather zeros.  The tail run (SweepTask::pad) is gathered like any other and its sum dropped.
+template <bool FAST, bool ROWV, typename TB, typename TE>
 __device__ __forceinline__ void sweep_pair_body(
     const SweepTask *__restrict__ tasks, uint32_t task0, uint32_t n_launch,
-    const uint2 *__restrict__ entries, const uint32_t *__restrict__ task_rows,
+    const TE *__restrict__ entries, const float *__restrict__ task_vals, const uint32_t *__restrict__ task_rows,
     const TB *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc,
     float *__restrict__ partial, uint32_t d, float alpha, float beta, uint32_t flags, float slope,
     unsigned long long *__restrict__ stamps, uint32_t wave_stride) {
@@ -443,14 +494,16 @@ __device__ __forceinline__ void sweep_pair_body(
         uint32_t cur_row = 0;
         f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
         const uint32_t my_dst = task_rows[(size_t)t * kRW + (lane & 15)];   // row table, read under the main loop
+        float my_val = 0.f, run_val = 0.f;
+        if constexpr (ROWV) my_val = load_row_values(task_vals + (size_t)t * kRW);
 
         if (task.beg < task.end) {
-            EntryBatch cur = load_batch(entries, task.beg);
+            auto cur = load_batch(entries, task.beg);
             for (uint32_t e = task.beg; e < task.end; e += 8) {
                 if ((flags & kFlagPrioRotate) && ((e - task.beg) & prio_mask) == 0)
                     rotate_priority(prio_slot, (e - task.beg) >> prio_shift);
                 const uint32_t e_next = e + 8 < task.end ? e + 8 : e;
-                const EntryBatch nxt = load_batch(entries, e_next);
+                const auto nxt = load_batch(entries, e_next);
                 f32x4_t b[4];
 #pragma unroll
                 for (int u = 0; u < 4; u++) {
@@ -472,16 +525,21 @@ __device__ __forceinline__ void sweep_pair_body(
                         MGGCN_PLANES_FOLD(cur_row, acc);
                         acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
                         cur_row = (pk >> kColBits) & (kRW - 1);
+                        if constexpr (ROWV) run_val = row_value(my_val, cur_row);
                     }
-                    const uint32_t va = __builtin_bit_cast(uint32_t, cur.val(2 * u));
-                    const uint32_t vb = __builtin_bit_cast(uint32_t, cur.val(2 * u + 1));
                     float v;
-                    if constexpr (FAST) {
-                        uint32_t sel;
-                        asm("v_mov_b32 %0, %1\n\tv_bfi_b32 %0, %2, %3, %0" : "=&v"(sel) : "s"(va), "v"(hmask), "s"(vb));
-                        v = __builtin_bit_cast(float, sel);
+                    if constexpr (ROWV) {
+                        v = run_val;
                     } else {
-                        v = __builtin_bit_cast(float, (va & ~hmask) | (vb & hmask));
+                        const uint32_t va = __builtin_bit_cast(uint32_t, cur.val(2 * u));
+                        const uint32_t vb = __builtin_bit_cast(uint32_t, cur.val(2 * u + 1));
+                        if constexpr (FAST) {
+                            uint32_t sel;
+                            asm("v_mov_b32 %0, %1\n\tv_bfi_b32 %0, %2, %3, %0" : "=&v"(sel) : "s"(va), "v"(hmask), "s"(vb));
+                            v = __builtin_bit_cast(float, sel);
+                        } else {
+                            v = __builtin_bit_cast(float, (va & ~hmask) | (vb & hmask));
+                        }
                     }
                     // (starting the new run from the product v * b instead of zeroing acc, and dropping the clamp of the
                     //  prefetch index, were measured on top of FAST: +2 % and +-0: profiles/experiments/fast_pairs_r03.log)
@@ -493,7 +551,7 @@ __device__ __forceinline__ void sweep_pair_body(
                 cur = nxt;
             }
         }
-        MGGCN_PLANES_FOLD(cur_row, acc);
+        if (!(ROWV && task.pad)) MGGCN_PLANES_FOLD(cur_row, acc);           // (the tail run's sum is dropped)
 
         // Epilogue, four rows at a time, in three phases with nothing else between the memory operations of a phase:
         // (1) the four reads of C (beta != 0: every column slice after the first), (2) all four results, (3) the four stores.
@@ -571,12 +629,18 @@ __device__ __forceinline__ void sweep_pair_body(
 template <bool FAST>
 __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_pair_kernel(
     MGGCN_PAIR_PARAMS(float)) {
-    sweep_pair_body<FAST, float>(MGGCN_SWEEP_ARGS, stamps, wave_stride);
+    sweep_pair_body<FAST, false, float>(tasks, task0, n_launch, entries, nullptr, MGGCN_SWEEP_TAIL_ARGS, stamps, wave_stride);
+}
+// (the element type of B is a template parameter here: float, or uint16_t for bf16 bits)
+template <bool FAST, typename TB>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_pair_rowv_kernel(
+    MGGCN_ROWV_PARAMS(TB), unsigned long long *__restrict__ stamps, uint32_t wave_stride) {
+    sweep_pair_body<FAST, true, TB>(tasks, task0, n_launch, entries, task_vals, MGGCN_SWEEP_TAIL_ARGS, stamps, wave_stride);
 }
 template <bool FAST>
 __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_pair_b16_kernel(
     MGGCN_PAIR_PARAMS(uint16_t)) {
-    sweep_pair_body<FAST, uint16_t>(MGGCN_SWEEP_ARGS, stamps, wave_stride);
+    sweep_pair_body<FAST, false, uint16_t>(tasks, task0, n_launch, entries, nullptr, MGGCN_SWEEP_TAIL_ARGS, stamps, wave_stride);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -640,13 +704,17 @@ template <int LPE> __device__ __forceinline__ float reduce_groups(float x) {
 // bf16 (spmm_sweep_quad_lds_b16_kernel): the same LPE, groups and sums -- a lane fetches its four columns with a
 // buffer_load_dwordx2 -- over the bf16 image re-pitched to a multiple of 64 bytes (d = 41: 128 B, one line per row
 // against up to two at the fp32 image's 192 B).
-template <int LPE, typename TB>
+// ROWV (the 4-byte row-value stream): a chunk of 128 entries is 512 B (a lane stages two of them, a uint2), a lane reads
+// its entry with a ds_read_b32 and the FMAs take the run's value as a scalar operand.  The whole offset of a gather is the
+// lane's own here, so a padding entry's column past B gathers zeros in any position of a group.
+template <int LPE, bool ROWV, typename TB, typename TE, typename TR>
 __device__ __forceinline__ void sweep_quad_lds_body(
     const SweepTask *__restrict__ tasks, uint32_t task0, uint32_t n_launch,
-    const uint2 *__restrict__ entries, const uint32_t *__restrict__ task_rows,
+    const TE *__restrict__ entries, const float *__restrict__ task_vals, const uint32_t *__restrict__ task_rows,
     const TB *__restrict__ B, uint32_t b_bytes, uint32_t row_bytes, float *__restrict__ C, size_t ldc,
     float *__restrict__ partial, uint32_t d, float alpha, float beta, uint32_t flags, float slope,
-    uint4 (&ring)[kWavesPerBlock][2][64]) {   // per wave: two slots of 128 entries
+    TR (&ring)[kWavesPerBlock][2][64]) {      // per wave: two slots of 128 entries (TR = two entries: uint4, ROWV uint2)
+    static_assert(sizeof(TR) == 2 * sizeof(TE), "a lane stages two entries");
     const int lane = threadIdx.x & 63;
     const uint32_t wib = __builtin_amdgcn_readfirstlane((uint32_t)(threadIdx.x >> 6));
     const uint32_t local = blockIdx.x * kWavesPerBlock + wib;
@@ -667,14 +735,16 @@ __device__ __forceinline__ void sweep_quad_lds_body(
     MGGCN_PLANES_ZERO();
     uint32_t cur_row = 0;
     f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+    float my_val = 0.f, run_val = 0.f;
+    if constexpr (ROWV) my_val = load_row_values(task_vals + (size_t)t * kRW);
 
     const uint32_t n_ent = task.end - task.beg;           // multiple of STEP
     if (n_ent) {
-        // every chunk is loaded as 128 entries (1 KiB) starting at entry c * CH; CH of them are used
-        const uint4 *stream = reinterpret_cast<const uint4 *>(entries + task.beg) + lane;   // 2 entries per uint4
+        // every chunk is loaded as 128 entries (1 KiB; ROWV 512 B) starting at entry c * CH; CH of them are used
+        const TR *stream = reinterpret_cast<const TR *>(entries + task.beg) + lane;   // 2 entries per lane
         const uint32_t n_chunks = (n_ent + CH - 1) / CH;  // the plan leaves a chunk of slack after the last task
         ring[wib][0][lane] = stream[0];
-        uint4 pre = stream[n_chunks > 1 ? CH / 2 : 0];
+        TR pre = stream[n_chunks > 1 ? CH / 2 : 0];
         const uint32_t prio_slot = blockIdx.x / ((flags >> kNumCuPos) & kNumCuMask);
         const uint32_t prio_shift = (flags >> kPrioShiftPos) & 15u;          // in chunks of CH (~128) entries here
         f32x4_t b[4];
@@ -685,12 +755,15 @@ __device__ __forceinline__ void sweep_quad_lds_body(
             ring[wib][(c + 1) & 1][lane] = pre;           // chunk c+1 (slot last read during chunk c-1)
             pre = stream[(size_t)(CH / 2) * (c + 2 < n_chunks ? c + 2 : c)];
             __builtin_amdgcn_wave_barrier();
-            const uint2 *slot = reinterpret_cast<const uint2 *>(&ring[wib][c & 1][0]) + grp;
+            const TE *slot = reinterpret_cast<const TE *>(&ring[wib][c & 1][0]) + grp;
             const uint32_t n_steps = min((uint32_t)(CH / STEP), (n_ent - c * CH) / STEP);
             for (uint32_t s = 0; s < n_steps; s++) {
                 uint2 ent[4];
 #pragma unroll
-                for (int u = 0; u < 4; u++) ent[u] = slot[s * STEP + u * G];
+                for (int u = 0; u < 4; u++) {
+                    if constexpr (ROWV) ent[u] = make_uint2(slot[s * STEP + u * G], 0u);
+                    else ent[u] = slot[s * STEP + u * G];
+                }
                 // (b is zeroed ONCE, in front of the chunk loop: lanes past the row never load and keep their zeros --
                 //  zeroing it here was sixteen v_mov per step, four per gather)
                 if (active) {                                    // lanes past the row issue no load (3 % faster)
@@ -705,8 +778,9 @@ __device__ __forceinline__ void sweep_quad_lds_body(
                         MGGCN_PLANES_FOLD(cur_row, acc);
                         acc = (f32x4_t){0.f, 0.f, 0.f, 0.f};
                         cur_row = (pk >> kColBits) & (kRW - 1);
+                        if constexpr (ROWV) run_val = row_value(my_val, cur_row);
                     }
-                    const float v = __builtin_bit_cast(float, ent[u].y);
+                    const float v = ROWV ? run_val : __builtin_bit_cast(float, ent[u].y);
                     acc[0] = fmaf(v, b[u][0], acc[0]);
                     acc[1] = fmaf(v, b[u][1], acc[1]);
                     acc[2] = fmaf(v, b[u][2], acc[2]);
@@ -716,7 +790,7 @@ __device__ __forceinline__ void sweep_quad_lds_body(
             __builtin_amdgcn_wave_barrier();
         }
     }
-    MGGCN_PLANES_FOLD(cur_row, acc);
+    if (!(ROWV && task.pad)) MGGCN_PLANES_FOLD(cur_row, acc);               // (the tail run's sum is dropped)
 
     // four rows at a time, three phases (reads of C, results, stores) -- see the pair kernel's epilogue
     auto emit4_any = [&](auto has_beta_c, uint32_t r0, float (&x)[4][4]) {
@@ -774,13 +848,19 @@ template <int LPE>
 __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_quad_lds_kernel(
     MGGCN_SWEEP_PARAMS(float)) {
     __shared__ uint4 ring[kWavesPerBlock][2][64];
-    sweep_quad_lds_body<LPE, float>(MGGCN_SWEEP_ARGS, ring);
+    sweep_quad_lds_body<LPE, false, float>(tasks, task0, n_launch, entries, nullptr, MGGCN_SWEEP_TAIL_ARGS, ring);
+}
+template <int LPE, typename TB>
+__global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_quad_lds_rowv_kernel(
+    MGGCN_ROWV_PARAMS(TB)) {
+    __shared__ uint2 ring[kWavesPerBlock][2][64];
+    sweep_quad_lds_body<LPE, true, TB>(tasks, task0, n_launch, entries, task_vals, MGGCN_SWEEP_TAIL_ARGS, ring);
 }
 template <int LPE>
 __global__ __launch_bounds__(64 * kWavesPerBlock) __attribute__((amdgpu_num_vgpr(64))) void spmm_sweep_quad_lds_b16_kernel(
     MGGCN_SWEEP_PARAMS(uint16_t)) {
     __shared__ uint4 ring[kWavesPerBlock][2][64];
-    sweep_quad_lds_body<LPE, uint16_t>(MGGCN_SWEEP_ARGS, ring);
+    sweep_quad_lds_body<LPE, false, uint16_t>(tasks, task0, n_launch, entries, nullptr, MGGCN_SWEEP_TAIL_ARGS, ring);
 }
 
 // bf16 image of B for the narrow form / the permuted plan: pitch dp elements (a multiple of 4), columns d..dp-1 zero
@@ -818,6 +898,23 @@ __global__ __launch_bounds__(256) void sweep_combine_kernel(
     }
 }
 
+// Row-value stream -> generic stream, bit for bit what the builder would have made (plan_host.h): one block per task.
+__global__ __launch_bounds__(256) void sweep_expand_kernel(const SweepTask *__restrict__ tasks, uint32_t n_tasks,
+                                                           const uint32_t *__restrict__ words, const float *__restrict__ task_vals,
+                                                           uint32_t n_cols, uint2 *__restrict__ out) {
+    for (uint32_t t = blockIdx.x; t < n_tasks; t += gridDim.x) {
+        const SweepTask task = tasks[t];
+        for (uint32_t i = task.beg + threadIdx.x; i < task.end; i += blockDim.x) {
+            const uint32_t x = words[i];
+            uint2 o;
+            if (i >= task.end - task.pad) o = make_uint2(x & ~kRunFlag, 0u);                 // tail padding
+            else if ((x & kColMask) >= n_cols) o = make_uint2(x - n_cols, 0u);                // run padding
+            else o = make_uint2(x, __builtin_bit_cast(uint32_t, task_vals[(size_t)t * kRW + ((x >> kColBits) & (kRW - 1))]));
+            out[i] = o;
+        }
+    }
+}
+
 }  // namespace
 
 // the host side of a sweep plan (mggcn_plan::SweepHost: tasks, entry stream, row tables, knobs) + its device image
@@ -827,12 +924,17 @@ struct SweepPlan {
     uint32_t run_pad = 2;          // every (panel,row) run is a multiple of this many entries
     uint32_t lpe = 0;              // narrow form: lanes per entry of the gather kernel (run_pad = 64 / lpe); 0 = wide form
     SweepTask *d_tasks = nullptr;
-    uint2 *d_entries = nullptr;
+    // the generic stream.  A row-value plan (row_values: d_entries32 + d_task_vals) has none until a call needs it
+    // (sweep_generic_stream: a one-row-per-load width, a narrow plan at a wide width); then it is expanded once.
+    mutable uint2 *d_entries = nullptr;
+    bool row_values = false;
+    uint32_t *d_entries32 = nullptr;
+    float *d_task_vals = nullptr;
     uint32_t *d_task_rows = nullptr;
     SweepSplitRow *d_split = nullptr;
     float *d_partial = nullptr;
     unsigned long long *d_stamps = nullptr;   // diagnostics: 3 words per task (MGGCN_SPMM_STAMPS=1)
-    size_t bytes = 0;
+    mutable size_t bytes = 0;
     // tuning knobs, read from the environment ONCE when the plan is built (never on the launch path)
     uint32_t panel_rows = 0, num_cu = 0;
     uint64_t n_entries = 0;        // padded entry stream length
@@ -864,15 +966,24 @@ SweepPlan *sweep_plan_build(uint32_t n_rows, uint32_t n_cols, const uint32_t *in
     p->panel_rows = h.panel_rows; p->n_entries = h.n_entries; p->num_cu = h.num_cu;
     p->prio_bits_wide = h.prio_bits_wide; p->prio_bits_narrow = h.prio_bits_narrow; p->tasks_per_wave = h.tasks_per_wave;
     p->allow_quad = h.allow_quad; p->allow_vec4 = h.allow_vec4; p->fast_pairs = h.fast_pairs;
-    p->round_excess = h.round_excess;
-    const size_t tb = h.tasks.size() * sizeof(SweepTask), eb = h.entries.size() * sizeof(uint2);
+    p->round_excess = h.round_excess; p->row_values = h.row_values;
+    const size_t tb = h.tasks.size() * sizeof(SweepTask), eb = h.row_values ? 0 : h.entries.size() * sizeof(uint2);
+    const size_t wb = h.entries32.size() * sizeof(uint32_t), vb = h.task_vals.size() * sizeof(float);
     const size_t rb = h.task_rows.size() * sizeof(uint32_t), sb = h.split_rows.size() * sizeof(SweepSplitRow);
     const size_t pb = (size_t)h.n_slots * max_d * sizeof(float);
     MGGCN_CHECK_HIP(hipMalloc(&p->d_tasks, tb));
     MGGCN_CHECK_HIP(hipMemcpy(p->d_tasks, h.tasks.data(), tb, hipMemcpyHostToDevice));
-    MGGCN_CHECK_HIP(hipMalloc(&p->d_entries, eb + 2048));          // + a chunk: the LDS-staged kernel reads whole 1 KiB chunks
-    MGGCN_CHECK_HIP(hipMemset(reinterpret_cast<char *>(p->d_entries) + eb, 0, 2048));
-    if (eb) MGGCN_CHECK_HIP(hipMemcpy(p->d_entries, h.entries.data(), eb, hipMemcpyHostToDevice));
+    if (h.row_values) {
+        MGGCN_CHECK_HIP(hipMalloc(&p->d_entries32, wb + 2048));    // + a chunk, as below
+        MGGCN_CHECK_HIP(hipMemset(reinterpret_cast<char *>(p->d_entries32) + wb, 0, 2048));
+        if (wb) MGGCN_CHECK_HIP(hipMemcpy(p->d_entries32, h.entries32.data(), wb, hipMemcpyHostToDevice));
+        MGGCN_CHECK_HIP(hipMalloc(&p->d_task_vals, vb));
+        MGGCN_CHECK_HIP(hipMemcpy(p->d_task_vals, h.task_vals.data(), vb, hipMemcpyHostToDevice));
+    } else {
+        MGGCN_CHECK_HIP(hipMalloc(&p->d_entries, eb + 2048));      // + a chunk: the LDS-staged kernel reads whole 1 KiB chunks
+        MGGCN_CHECK_HIP(hipMemset(reinterpret_cast<char *>(p->d_entries) + eb, 0, 2048));
+        if (eb) MGGCN_CHECK_HIP(hipMemcpy(p->d_entries, h.entries.data(), eb, hipMemcpyHostToDevice));
+    }
     MGGCN_CHECK_HIP(hipMalloc(&p->d_task_rows, rb));
     MGGCN_CHECK_HIP(hipMemcpy(p->d_task_rows, h.task_rows.data(), rb, hipMemcpyHostToDevice));
     if (sb) {
@@ -884,14 +995,31 @@ SweepPlan *sweep_plan_build(uint32_t n_rows, uint32_t n_cols, const uint32_t *in
         MGGCN_CHECK_HIP(hipMalloc(&p->d_stamps, (size_t)h.n_tasks * 3 * sizeof(unsigned long long)));
         MGGCN_CHECK_HIP(hipMemset(p->d_stamps, 0, (size_t)h.n_tasks * 3 * sizeof(unsigned long long)));
     }
-    p->bytes = tb + eb + rb + sb + pb;
+    p->bytes = tb + eb + wb + vb + rb + sb + pb;
     return p;
+}
+
+// the generic stream of a row-value plan, expanded on first use (like the plan's bf16 scratch: the first call pays)
+static const uint2 *sweep_generic_stream(hipStream_t st, const SweepPlan *p) {
+    if (!p->d_entries) {
+        const size_t eb = (size_t)p->n_entries * sizeof(uint2);
+        MGGCN_CHECK_HIP(hipMalloc(&p->d_entries, eb + 2048));
+        MGGCN_CHECK_HIP(hipMemset(reinterpret_cast<char *>(p->d_entries) + eb, 0, 2048));
+        hipLaunchKernelGGL(sweep_expand_kernel, dim3(std::max(1u, std::min(p->n_tasks, 65536u))), dim3(256), 0, st, p->d_tasks,
+                           p->n_tasks, p->d_entries32, p->d_task_vals, p->n_cols, p->d_entries);
+        MGGCN_CHECK_LAUNCH();
+        MGGCN_CHECK_HIP(hipStreamSynchronize(st));                 // later calls may come on another stream
+        p->bytes += eb;
+    }
+    return p->d_entries;
 }
 
 void sweep_plan_destroy(SweepPlan *p) {
     if (!p) return;
     if (p->d_tasks) MGGCN_CHECK_HIP(hipFree(p->d_tasks));
     if (p->d_entries) MGGCN_CHECK_HIP(hipFree(p->d_entries));
+    if (p->d_entries32) MGGCN_CHECK_HIP(hipFree(p->d_entries32));
+    if (p->d_task_vals) MGGCN_CHECK_HIP(hipFree(p->d_task_vals));
     if (p->d_task_rows) MGGCN_CHECK_HIP(hipFree(p->d_task_rows));
     if (p->d_split) MGGCN_CHECK_HIP(hipFree(p->d_split));
     if (p->d_partial) MGGCN_CHECK_HIP(hipFree(p->d_partial));
@@ -904,9 +1032,9 @@ size_t sweep_plan_bytes(const SweepPlan *p) { return p ? p->bytes : 0; }
 // one line per slice plan for MGGCN_SPMM_PLAN_LOG / mggcn_spmm_plan_describe
 int sweep_plan_describe(const SweepPlan *p, char *out, size_t cap) {
     if (!p) return 0;
-    return std::snprintf(out, cap, "tasks=%u rounds=%u panel_rows=%u run_pad=%u lpe=%u entries=%llu split_rows=%u slots=%u round_excess=%.4f",
+    return std::snprintf(out, cap, "tasks=%u rounds=%u panel_rows=%u run_pad=%u lpe=%u entries=%llu split_rows=%u slots=%u values=%s round_excess=%.4f",
                          p->n_tasks, (p->n_tasks + p->round_tasks - 1) / p->round_tasks, p->panel_rows, p->run_pad, p->lpe,
-                         (unsigned long long)p->n_entries, p->n_split_rows, p->n_slots, p->round_excess);
+                         (unsigned long long)p->n_entries, p->n_split_rows, p->n_slots, p->row_values ? "row" : "entry", p->round_excess);
 }
 uint32_t sweep_plan_tasks(const SweepPlan *p) { return p ? p->n_tasks : 0; }
 uint32_t sweep_plan_split_rows(const SweepPlan *p) { return p ? p->n_split_rows : 0; }
@@ -968,11 +1096,15 @@ namespace {
 template <typename TB> struct SweepKernels;
 template <> struct SweepKernels<float> {
     template <int L> static constexpr auto narrow = spmm_sweep_quad_lds_kernel<L>;
+    template <int L> static constexpr auto narrow_rowv = spmm_sweep_quad_lds_rowv_kernel<L, float>;
     template <bool F> static constexpr auto pair = spmm_sweep_pair_kernel<F>;
+    template <bool F> static constexpr auto pair_rowv = spmm_sweep_pair_rowv_kernel<F, float>;
     template <int V> static constexpr auto generic = spmm_sweep_kernel<V>;
 };
 template <> struct SweepKernels<uint16_t> {
     template <int L> static constexpr auto narrow = spmm_sweep_quad_lds_b16_kernel<L>;
+    template <int L> static constexpr auto narrow_rowv = spmm_sweep_quad_lds_rowv_kernel<L, uint16_t>;
+    template <bool F> static constexpr auto pair_rowv = spmm_sweep_pair_rowv_kernel<F, uint16_t>;
     template <bool F> static constexpr auto pair = spmm_sweep_pair_b16_kernel<F>;
     template <int V> static constexpr auto generic = spmm_sweep_b16_kernel<V>;
 };
@@ -1002,35 +1134,63 @@ void sweep_launch_t(hipStream_t st, const SweepPlan *p, const TB *B, size_t ldb,
     // the knobs (priority rotation, tasks per wave, kernel gates) were read once, when the plan was built
     const uint32_t wide_flags = (flags & 0xFFu) | p->prio_bits_wide;
     const uint32_t narrow_flags = (flags & 0xFFu) | p->prio_bits_narrow;
+    // Row-value plan: its own kernels where the padding contract holds (plan_host.h) -- the narrow form or the pair form at
+    // run_pad 2, the padding column's offset inside 32 bits; any other call (a one-row-per-load width, a narrow plan at a
+    // wide width) runs today's kernels on the generic stream, expanded on first use.
+    const bool fast = vec4 && ldb >= 128u && (row_bytes & (row_bytes - 1u)) == 0 && p->fast_pairs;   // power-of-two pitch >= 128 elements
+    const bool rowv = p->row_values && (quad || (vec4 && p->run_pad == 2)) &&
+                      (quad ? 2ull * p->n_cols : (uint64_t)p->n_cols + 1u) * row_bytes <= (1ull << 32);   // (narrow: the whole product)
+    const uint2 *entries = (p->row_values && !rowv) ? sweep_generic_stream(st, p) : p->d_entries;
     for (uint32_t t0 = 0; t0 < p->n_tasks; t0 += per_launch) {
         const uint32_t n_launch = std::min(per_launch, p->n_tasks - t0);
         const uint32_t n_waves = tpw > 1 ? std::min(n_launch, p->round_tasks) : n_launch;
         const dim3 grid((n_waves + kWavesPerBlock - 1) / kWavesPerBlock), block(64 * kWavesPerBlock);
 #define MGGCN_LAUNCH_NARROW(L)                                                                             \
-    hipLaunchKernelGGL((K::template narrow<L>), grid, block, 0, st, p->d_tasks, t0, n_launch, p->d_entries, \
+    hipLaunchKernelGGL((K::template narrow<L>), grid, block, 0, st, p->d_tasks, t0, n_launch, entries, \
                        p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d, alpha, beta, narrow_flags, slope)
-        if (quad) {
+#define MGGCN_LAUNCH_NARROW_ROWV(L)                                                                                    \
+    hipLaunchKernelGGL((K::template narrow_rowv<L>), grid, block, 0, st, p->d_tasks, t0, n_launch, p->d_entries32,       \
+                       p->d_task_vals, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d, alpha, beta, narrow_flags, slope)
+        {
+            if (rowv && quad) {
+                if (p->lpe == 4) MGGCN_LAUNCH_NARROW_ROWV(4);
+                else if (p->lpe == 8) MGGCN_LAUNCH_NARROW_ROWV(8);
+                else if (p->lpe == 12) MGGCN_LAUNCH_NARROW_ROWV(12);
+                else MGGCN_LAUNCH_NARROW_ROWV(16);
+            } else if (rowv && fast) {
+                hipLaunchKernelGGL((K::template pair_rowv<true>), grid, block, 0, st, p->d_tasks, t0, n_launch,
+                                   p->d_entries32, p->d_task_vals, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
+                                   alpha, beta, wide_flags, slope, p->d_stamps, tpw > 1 ? p->round_tasks : n_launch);
+            } else if (rowv) {
+                hipLaunchKernelGGL((K::template pair_rowv<false>), grid, block, 0, st, p->d_tasks, t0, n_launch,
+                                   p->d_entries32, p->d_task_vals, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
+                                   alpha, beta, wide_flags, slope, p->d_stamps, tpw > 1 ? p->round_tasks : n_launch);
+            }
+        }
+#undef MGGCN_LAUNCH_NARROW_ROWV
+        if (rowv) {
+        } else if (quad) {
             if (p->lpe == 4) MGGCN_LAUNCH_NARROW(4);
             else if (p->lpe == 8) MGGCN_LAUNCH_NARROW(8);
             else if (p->lpe == 12) MGGCN_LAUNCH_NARROW(12);
             else MGGCN_LAUNCH_NARROW(16);
         }
 #undef MGGCN_LAUNCH_NARROW
-        else if (vec4 && ldb >= 128u && (row_bytes & (row_bytes - 1u)) == 0 && p->fast_pairs)   // power-of-two pitch >= 128 elements
+        else if (fast)
             hipLaunchKernelGGL((K::template pair<true>), grid, block, 0, st, p->d_tasks, t0, n_launch,
-                               p->d_entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
+                               entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
                                alpha, beta, wide_flags, slope, p->d_stamps, tpw > 1 ? p->round_tasks : n_launch);
         else if (vec4)
             hipLaunchKernelGGL((K::template pair<false>), grid, block, 0, st, p->d_tasks, t0, n_launch,
-                               p->d_entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
+                               entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
                                alpha, beta, wide_flags, slope, p->d_stamps, tpw > 1 ? p->round_tasks : n_launch);
         else if (vec2)
             hipLaunchKernelGGL((K::template generic<2>), grid, block, 0, st, p->d_tasks, t0, n_launch,
-                               p->d_entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
+                               entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
                                alpha, beta, flags, slope);
         else
             hipLaunchKernelGGL((K::template generic<1>), grid, block, 0, st, p->d_tasks, t0, n_launch,
-                               p->d_entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
+                               entries, p->d_task_rows, B, b_bytes, row_bytes, C, ldc, p->d_partial, d,
                                alpha, beta, flags, slope);
         MGGCN_CHECK_LAUNCH();
     }
